@@ -24,6 +24,12 @@ configs[3] (HC level 9 of 1 MiB blocks), configs[4] (XXH32 / XXH64 of 4 KiB buff
 the stand-in for configs[0]'s Silesia/dickens block, compressed bytes checked against the reference library), and
 `end_to_end`: the host-pointer batch API on the headline blocks from pageable host memory, PCIe included (never `value`).
 Every cpu_baseline carries best-of-N and the median over the N runs, for all host threads and for one thread.
+
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, W warm-up steps, N timed steps, the
+round-trip check of the headline blocks and the line (its `roofline` objects come from the timed steps' own HIP events and the
+committed traffic file).  `--full` adds everything else above: the live PMC traffic passes, `cpu_baseline` and `configs`; the
+`--no-*` switches still trim a `--full` run.  `--dump-outputs DIR` writes what the last timed step computed (sizes of every
+block, the bytes of a fixed seeded sample of blocks) as float32 / float64 .npy files: see dump_outputs().
 """
 import argparse
 import hashlib
@@ -221,6 +227,43 @@ def cpu_entry(fn):
         return {"value": None, "unit": "GB/s", "cores": len(os.sched_getaffinity(0)), "kind": "port", "sample": "failed: %r" % (e,)}
 
 
+DUMP_SEED = 0x4C5A3447
+DUMP_BLOCKS = 64                 # sampled blocks whose bytes are written
+DUMP_ROW_BUDGET = 20 << 20       # bytes of float32 per sampled-bytes file
+DUMP_SIZES_MAX = 1 << 19         # entries of a sizes file (float64)
+
+
+def dump_outputs(d, comp, clen, back, dlen, n, blk, cap):
+    """What the headline's last timed step handed its caller, as DIR/<name>.npy (float32 / float64, < 64 MB in all):
+    compressed_sizes / decompressed_sizes  the return values of the compress / safe-decompress launches, one per block (float64;
+                                           a seeded sample of DUMP_SIZES_MAX blocks when the batch has more, sizes_index says which)
+    sample_index                           the blocks (rank 0's shard) whose bytes follow, DUMP_BLOCKS of them drawn with DUMP_SEED
+    compressed_sample                      those blocks' compressed bytes (float32, one row per block, zero past the block's size)
+    decompressed_sample                    those blocks' decompressed bytes (float32)
+    Rows are cut at DUMP_ROW_BUDGET / 4 / DUMP_BLOCKS bytes when the blocks are larger than that."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    cl = clen.cpu().numpy().astype(np.float64)
+    dl = dlen.cpu().numpy().astype(np.float64)
+    if n > DUMP_SIZES_MAX:
+        si = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_SIZES_MAX, replace=False))
+        cl, dl = cl[si], dl[si]
+        np.save(os.path.join(d, "sizes_index.npy"), si.astype(np.float64))
+    np.save(os.path.join(d, "compressed_sizes.npy"), cl)
+    np.save(os.path.join(d, "decompressed_sizes.npy"), dl)
+    k = min(n, DUMP_BLOCKS)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    row = DUMP_ROW_BUDGET // 4 // k
+    it = torch.from_numpy(idx).to(comp.device)
+    wc, wd = min(cap, row), min(blk, row)
+    cs = comp.view(n, cap)[it, :wc].cpu().numpy().astype(np.float32)
+    cs[np.arange(wc)[None, :] >= clen[it].cpu().numpy()[:, None]] = 0.0     # the slot past the stream is not output
+    np.save(os.path.join(d, "sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "compressed_sample.npy"), cs)
+    np.save(os.path.join(d, "decompressed_sample.npy"), back.view(n, blk)[it, :wd].cpu().numpy().astype(np.float32))
+
+
 def relaunch(n):
     """`bench.py --gpus N` started without a launcher: become N ranks under torch.distributed.run"""
     s = socket.socket()
@@ -247,7 +290,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the configs[2..4] / decompress_fast sub-objects")
     ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from profiles/traffic.json only (no PMC child runs)")
+    ap.add_argument("--full", action="store_true", help="also the live PMC traffic passes, cpu_baseline and the configs legs (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:            # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_extra_configs = args.no_live_traffic = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch(args.gpus)
@@ -375,6 +424,8 @@ def main():
     dev_index = dev.index or 0
     ok = all_ok(ok)
     nbytes = float(n) * blk
+    if args.dump_outputs and rank == 0:      # before the --full legs reuse comp / back
+        dump_outputs(args.dump_outputs, comp, clen, back, dlen, n, blk, cap)
 
     def roof(kernel, alg_bytes, secs, traffic=None):
         return {"kernel": kernel, "bound": "hbm", "achieved": round(alg_bytes / secs / 1e9, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",

@@ -68,6 +68,12 @@ def sha(b):
     return hashlib.sha256(b).hexdigest()
 
 
+def calgary(name):
+    """a whole Calgary corpus file (book1, geo, pic: the reference's test resources), stored xz-compressed under tests/golden/calgary"""
+    import lzma
+    return lzma.decompress(open(os.path.join(GOLD, "calgary", name + ".xz"), "rb").read())
+
+
 def rnd_inputs(O, corpus, seed, count, max_n=70000):
     """deterministic mixed bag of inputs: random, text, image, low-entropy, periodic, synthetic"""
     rng = random.Random(seed)

@@ -4,13 +4,14 @@
 * calgary slices (the only real-world data in the reference: src/test-resources/calgary/{book1,geo,pic},
   used by LZ4Test.java:335-348) -- small prefixes only, as input fixtures for the GPU box where
   /root/reference does not exist;
+* the three whole files, xz-compressed under calgary/ (the full-file rows of the golden table are tested on them);
 * golden.json: for every named input the outputs of the REFERENCE ITSELF (the prebuilt
   liblz4-java.so = liblz4 1.9.3 + xxhash 0.6.5 that LZ4Factory.nativeInstance() loads): compressed
   size + sha256 of LZ4_compress_default and LZ4_compress_HC(9), XXH32/XXH64 with seeds 0 and
   0x9747b28c, plus decoder return codes on the reference's malformed vectors (LZ4Test.java:350-419).
   SURVEY.md Appendix E is a subset of this table.
 """
-import hashlib, json, os, sys
+import hashlib, json, lzma, os, sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", ".."))
 from oracle import oracle as O
@@ -25,6 +26,9 @@ def main():
     slices = {"book1_200000.bin": book1[:200000], "geo_65536.bin": geo[:65536], "pic_65536.bin": pic[:65536]}
     for name, data in slices.items():
         open(os.path.join(HERE, name), "wb").write(data)
+    os.makedirs(os.path.join(HERE, "calgary"), exist_ok=True)   # the whole files, for the tests of the full-file rows
+    for name, data in (("book1", book1), ("geo", geo), ("pic", pic)):
+        open(os.path.join(HERE, "calgary", name + ".xz"), "wb").write(lzma.compress(data, preset=9 | lzma.PRESET_EXTREME))
     inputs = {
         "book1": book1, "geo": geo, "pic": pic,
         "book1[:65536]": book1[:65536], "geo[:65536]": geo[:65536], "pic[:65536]": pic[:65536],

@@ -5,7 +5,7 @@ export GRAFT_REPO_ROOT=$PWD
 out=gpurun_out/${1:-r05k}; mkdir -p $out
 timeout 1500 python -m pytest tests -m gpu -q --durations=10 > $out/pytest.log 2>&1; echo "pytest rc=$?" >> $out/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?" >> $out/smoke.log
-timeout 900 python bench.py > $out/bench_line.json 2> $out/bench.err; echo "bench rc=$?" >> $out/bench.err
+timeout 900 python bench.py --full > $out/bench_line.json 2> $out/bench.err; echo "bench rc=$?" >> $out/bench.err
 tail -14 $out/pytest.log; tail -2 $out/smoke.log; tail -3 $out/bench.err; python - <<'PY'
 import json,sys
 try:

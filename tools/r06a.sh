@@ -8,4 +8,4 @@ tail -4 $out/pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?" >> $out/smoke.log; tail -2 $out/smoke.log
 timeout 600 python tools/ring_matrix.py cfg2_256,cfg2_1024,cfg2_2048,cfg2_4096,appf256,appf2048,appf4096,book2048,book4096 d > $out/matrix.log 2>&1
 tail -14 $out/matrix.log
-timeout 900 python bench.py > $out/bench.log 2>&1; tail -1 $out/bench.log > $out/bench_line.json; tail -c 1500 $out/bench.log
+timeout 900 python bench.py --full > $out/bench.log 2>&1; tail -1 $out/bench.log > $out/bench_line.json; tail -c 1500 $out/bench.log
