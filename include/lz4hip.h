@@ -11,6 +11,8 @@
  *   lz4hip_decompress_fast*   <- ..._LZ4_1decompress_1fast -> LZ4_decompress_fast (LZ4JNI.c:140-180, call :169)
  *   lz4hip_compress_hc*       <- ..._LZ4_1compressHC       -> LZ4_compress_HC     (LZ4JNI.c:93-133,  call :122)
  *   lz4hip_compress_bound     <- ..._LZ4_1compressBound    -> LZ4_compressBound   (LZ4JNI.c:234-239)
+ *   lz4hip_compress_fast_accel*  = LZ4_compress_fast(src, dst, n, cap, acceleration) of liblz4's main API (exported by the
+ *                                reference's liblz4-java.so; no JNI entry of the reference reaches it)
  *   lz4hip_xxh32* / xxh64*    <- Java_net_jpountz_xxhash_XXHashJNI_XXH32 / XXH64
  *                                (src/jni/net_jpountz_xxhash_XXHashJNI.c:42-59 / :152-169, calls :54 / :164)
  *
@@ -98,6 +100,20 @@ int lz4hip_compress_bound(int n);
 int lz4hip_compress_fast_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                int32_t* out_len, uint32_t n_blocks);
+/* ACCELERATED FAST COMPRESS: the bytes and return value of LZ4_compress_fast(src, dst, n, cap, acceleration), liblz4 1.9.3.
+ * A higher acceleration probes fewer positions (each miss-run starts with step counter acceleration << 6 instead of 1 << 6):
+ * faster parsing, a lower ratio.  acceleration is clamped as liblz4 does: < 1 -> 1, > 65537 (LZ4_ACCELERATION_MAX) -> 65537.
+ *   - after clamping, acceleration 1 IS lz4hip_compress_fast_batch / _batch_dev / lz4hip_compress_fast: same call, same kernels;
+ *   - 2 .. 65537 run their own kernel (compress_fast_accel_cu_kernel: one sequence per wavefront step, five wavefronts per CU,
+ *     byU16 tables below 65547 bytes, byU32 above, blocks up to 0x7E000000 bytes);
+ *   - results as for lz4hip_compress_fast*: out_len[i] > 0 compressed size, 0 = dst_cap[i] too small (also: src_len[i] < 0 or
+ *     > 0x7E000000, dst_cap[i] < 0); library failures as the status / LZ4HIP_LIB_ERROR of the call;
+ *   - the host batch shards over the initialised devices and returns only the useful bytes of every slot, as the fast path does;
+ *   - single calls (lz4hip_compress_fast_accel) are coalesced with concurrent calls of the SAME clamped acceleration only: every
+ *     value has a combiner of its own, so one launch never mixes accelerations.                                                  */
+int lz4hip_compress_fast_accel_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                     uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                     int32_t* out_len, uint32_t n_blocks, int acceleration);
 int lz4hip_compress_hc_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                              uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                              int32_t* out_len, uint32_t n_blocks, int level);
@@ -132,6 +148,10 @@ int lz4hip_xxh64_batch(const uint8_t* buf, const uint64_t* off, const int32_t* l
 int lz4hip_compress_fast_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                    uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                    int32_t* out_len, uint32_t n_blocks, int device, void* stream);
+/* accelerated fast compress (see lz4hip_compress_fast_accel_batch), device pointers, asynchronous */
+int lz4hip_compress_fast_accel_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                         uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                         int32_t* out_len, uint32_t n_blocks, int acceleration, int device, void* stream);
 /* HC: levels follow liblz4 (< 1 -> 9, > 12 -> 12): 1..9 = hash-chain strategy with lazy evaluation, 10..12 = optimal
  * parser (lz4-java levels 10..17).  Levels 10..12 are FUNCTIONAL ONLY: byte-identical output, but the optimal parser's table
  * walk is wave-uniform scalar work (about 1.0 / 0.7 GB/s per GPU at levels 10 / 12 -- no faster than the reference on the host's
@@ -169,6 +189,7 @@ int lz4hip_xxh64_batch_dev(const uint8_t* buf, const uint64_t* off, const int32_
 #define LZ4HIP_LIB_ERROR(status) ((int)(INT32_MIN + (-(status))))
 #define LZ4HIP_IS_LIB_ERROR(ret) ((ret) < (int)(INT32_MIN + 64))
 int lz4hip_compress_fast(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap);
+int lz4hip_compress_fast_accel(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int acceleration);  /* LZ4_compress_fast */
 int lz4hip_compress_hc(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level);
 int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap);
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len);

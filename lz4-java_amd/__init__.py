@@ -46,12 +46,14 @@ C_ABI = {
     "lz4hip_last_decode_route": (C.c_int, [C.c_int, C.POINTER(C.c_uint32)]),
     "lz4hip_compress_bound": (C.c_int, [C.c_int]),
     "lz4hip_compress_fast_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
+    "lz4hip_compress_fast_accel_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_int]),
     "lz4hip_compress_hc_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_int]),
     "lz4hip_decompress_safe_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_decompress_fast_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
+    "lz4hip_compress_fast_accel_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_hc_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_int]),
     "lz4hip_compress_hc_batch_dev_ws": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
@@ -60,6 +62,7 @@ C_ABI = {
     "lz4hip_xxh32_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_xxh64_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "lz4hip_compress_fast_accel": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_compress_hc": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_decompress_safe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
@@ -215,13 +218,19 @@ class LZ4Compressor:
 
 
 class LZ4HIPCompressor(LZ4Compressor):
-    """twin of lz4/LZ4JNICompressor.java: fast compressor over lz4hip_compress_fast"""
+    """twin of lz4/LZ4JNICompressor.java: fast compressor over lz4hip_compress_fast.  acceleration != 1: the bytes of liblz4's
+    LZ4_compress_fast(..., acceleration) (lz4hip_compress_fast_accel; values below 1 act as 1, above 65537 as 65537)"""
+
+    def __init__(self, acceleration=1):
+        self.acceleration = int(acceleration)
 
     def _native(self, sp, src_len, dp, max_dest_len):
-        return _single(lib().lz4hip_compress_fast(sp, src_len, dp, max_dest_len))
+        if self.acceleration == 1:
+            return _single(lib().lz4hip_compress_fast(sp, src_len, dp, max_dest_len))
+        return _single(lib().lz4hip_compress_fast_accel(sp, src_len, dp, max_dest_len, self.acceleration))
 
     def __str__(self):
-        return "LZ4HIPCompressor"
+        return "LZ4HIPCompressor" if self.acceleration == 1 else "LZ4HIPCompressor(acceleration=%d)" % self.acceleration
 
 
 class LZ4HCHIPCompressor(LZ4Compressor):
@@ -325,8 +334,11 @@ class LZ4Factory:
             cls._HIP = cls("HIP")
         return cls._HIP
 
-    def fastCompressor(self):
-        return self._fast
+    def fastCompressor(self, acceleration=1):
+        """acceleration 1 (the default): the factory's compressor; any other value: a compressor bound to it (LZ4_compress_fast)"""
+        if acceleration == 1:
+            return self._fast
+        return LZ4HIPCompressor(acceleration)
 
     def highCompressor(self, compressionLevel=9):
         if compressionLevel > 17:
@@ -534,7 +546,7 @@ class LZ4HIPBatch:
                 _check_range(buf, off[i], length[i])
 
     @classmethod
-    def _call(cls, fn, src, srcOff, srcLen, dst, dstOff, dstCap):
+    def _call(cls, fn, src, srcOff, srcLen, dst, dstOff, dstCap, *extra):
         n = len(srcOff)
         if not (len(srcLen) == len(dstOff) == len(dstCap) == n):
             raise ValueError("per-block arrays differ in length")
@@ -544,15 +556,18 @@ class LZ4HIPBatch:
         dp, dk = _rw_ptr(dst)
         out = (C.c_int32 * max(n, 1))()
         _chk(getattr(lib(), fn)(sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), dp, _arr(C.c_uint64, dstOff),
-                                _arr(C.c_int32, dstCap), out, n))
+                                _arr(C.c_int32, dstCap), out, n, *extra))
         if hasattr(srcOff, "dtype"):
             import numpy as np
             return np.frombuffer(out, dtype=np.int32, count=n).copy()
         return list(out[:n])
 
     @classmethod
-    def compress(cls, src, srcOff, srcLen, dst, dstOff, dstCap):
-        return cls._call("lz4hip_compress_fast_batch", src, srcOff, srcLen, dst, dstOff, dstCap)
+    def compress(cls, src, srcOff, srcLen, dst, dstOff, dstCap, acceleration=1):
+        """acceleration != 1: LZ4_compress_fast(..., acceleration) per block (lz4hip_compress_fast_accel_batch)"""
+        if acceleration == 1:
+            return cls._call("lz4hip_compress_fast_batch", src, srcOff, srcLen, dst, dstOff, dstCap)
+        return cls._call("lz4hip_compress_fast_accel_batch", src, srcOff, srcLen, dst, dstOff, dstCap, int(acceleration))
 
     @classmethod
     def compressHC(cls, src, srcOff, srcLen, dst, dstOff, dstCap, level=9):
@@ -656,8 +671,15 @@ class DeviceBatch:
                                 dst_cap.data_ptr(), out.data_ptr(), src_off.numel(), dev, st))
 
     @classmethod
-    def compress_fast(cls, src, src_off, src_len, dst, dst_off, dst_cap, out):
-        cls._call("lz4hip_compress_fast_batch_dev", src, src_off, src_len, dst, dst_off, dst_cap, out)
+    def compress_fast(cls, src, src_off, src_len, dst, dst_off, dst_cap, out, acceleration=1):
+        """acceleration != 1: LZ4_compress_fast(..., acceleration) per block (lz4hip_compress_fast_accel_batch_dev)"""
+        if acceleration == 1:
+            cls._call("lz4hip_compress_fast_batch_dev", src, src_off, src_len, dst, dst_off, dst_cap, out)
+            return
+        dev, st = cls._stream_dev(src)
+        _chk(lib().lz4hip_compress_fast_accel_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
+                                                        dst_off.data_ptr(), dst_cap.data_ptr(), out.data_ptr(), src_off.numel(),
+                                                        int(acceleration), dev, st))
 
     @classmethod
     def compress_hc(cls, src, src_off, src_len, dst, dst_off, dst_cap, out, level=9):

@@ -10,6 +10,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <map>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -66,7 +67,8 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
   ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC };
+// OP_COMPRESS_ACCEL: LZ4_compress_fast with acceleration 2 .. 65537, the value travels as `level` (acceleration 1 is OP_COMPRESS_FAST)
+enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL };
 // tuning knobs (lz4hip_set_option): atomics, so that a caller changing one while other threads launch is a race on the VALUE chosen,
 // never undefined behaviour; every launch reads each knob once
 std::atomic<int> g_decode_lanes{0};   // "decode_lanes"; 0 = kernel default
@@ -150,6 +152,18 @@ int launch_fast(const lz4hip::BatchArgs& a, hipStream_t st) {
   return le;
 }
 
+// LZ4_compress_fast(..., accel), accel already clamped to 2 .. 65537 (compress_fast_accel_cu_kernel; one queue word of scratch)
+int launch_accel(const lz4hip::BatchArgs& a, int accel, hipStream_t st) {
+  uint32_t* q = nullptr;
+  hipError_t e = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
+  if (e != hipSuccess) return (int)e;
+  const int le = lz4hip::launch_compress_fast_accel(a, (uint32_t)accel, q, cu_count(), st);
+  (void)hipFreeAsync(q, st);
+  return le;
+}
+// liblz4's acceleration handling (LZ4_compress_fast_extState): < 1 -> 1, > LZ4_ACCELERATION_MAX -> 65537
+int accel_clamp(int a) { return a < 1 ? 1 : a > 65537 ? 65537 : a; }
+
 // the decode knobs are process-wide and set one at a time: a combination no kernel exists for is said here, by name (round-5 advisor: it
 // used to surface as a bare "kernel launch: invalid value")
 const char* decode_knobs_error(int lanes, int pipe, int ring) {
@@ -202,10 +216,11 @@ int launch_decode(const lz4hip::BatchArgs& a, bool safe, hipStream_t st) {
   return lz4hip::launch_decompress(a, safe, g_decode_lanes.load(), g_decode_pipe.load(), g_decode_stage.load(), g_decode_ring.load(), st, route);
 }
 
-int launch_op(Op op, const lz4hip::BatchArgs& a, hipStream_t st) {
+int launch_op(Op op, const lz4hip::BatchArgs& a, hipStream_t st, int level = 0) {
   int e = 0;
   switch (op) {
     case OP_COMPRESS_FAST: e = launch_fast(a, st); break;
+    case OP_COMPRESS_ACCEL: e = launch_accel(a, level, st); break;
     case OP_DECODE_SAFE: e = launch_decode(a, true, st); break;
     case OP_DECODE_FAST: e = launch_decode(a, false, st); break;
     case OP_COMPRESS_HC: return fail(LZ4HIP_E_ARG, "internal: HC goes through dev_hc");
@@ -227,7 +242,7 @@ int dev_batch(Op op, const uint8_t* src, const uint64_t* src_off, const int32_t*
   if (!g.ok) return fail(LZ4HIP_E_HIP, "hipSetDevice failed");
   lz4hip::BatchArgs a{src, src_off, src_len, dst, dst_off, dst_cap, out, n};
   if (op == OP_COMPRESS_HC) return dev_hc(a, level, (hipStream_t)stream);
-  return launch_op(op, a, (hipStream_t)stream);
+  return launch_op(op, a, (hipStream_t)stream, level);
 }
 
 // ---- host-pointer path ---------------------------------------------------------------------------
@@ -489,7 +504,7 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
     if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (e = s.h_dst.reserve(db + 64)) != hipSuccess || (e = s.h_meta.reserve(meta)) != hipSuccess ||
         (e = s.d_src.reserve(sb + 64)) != hipSuccess || (e = s.d_dst.reserve(db + 64)) != hipSuccess || (e = s.d_meta.reserve(meta)) != hipSuccess ||
         (op == OP_COMPRESS_HC && (e = s.d_ws.reserve(lz4hip::hc_ws_bytes(sb, nb, level))) != hipSuccess) ||
-        ((op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC) && ((e = s.d_pack.reserve(db + 64)) != hipSuccess || (e = s.d_poff.reserve((size_t)nb * 8u)) != hipSuccess))) {
+        ((op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL) && ((e = s.d_pack.reserve(db + 64)) != hipSuccess || (e = s.d_poff.reserve((size_t)nb * 8u)) != hipSuccess))) {
       rc = bad("staging allocation", e);
       break;
     }
@@ -519,10 +534,11 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
       case OP_DECODE_SAFE: le = launch_decode(a, true, s.st); break;
       case OP_DECODE_FAST: le = launch_decode(a, false, s.st); break;
       case OP_COMPRESS_HC: le = lz4hip::launch_compress_hc(a, level, s.d_ws.p, sb, s.st); break;
+      case OP_COMPRESS_ACCEL: le = launch_accel(a, level, s.st); break;
     }
     if (le == LZ4HIP_E_ARG) { *err = lz4hip_last_error(); rc = le; break; }   // (a decode knob combination without a kernel: launch_decode has said which, on this thread)
     if (le) { rc = bad("kernel launch", (hipError_t)le); break; }
-    s.packed = (op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC);
+    s.packed = (op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL);
     // the sizes travel first; compress ops: the finisher fetches exactly the packed bytes once it has them
     if (!single && ((e = hipEventRecord(s.ev_k, s.st)) != hipSuccess || (e = hipStreamWaitEvent(s.q_out, s.ev_k, 0)) != hipSuccess)) { rc = bad("kernel event", e); break; }
     if ((e = hipMemcpyAsync(hm + (size_t)nb * 24u, dm + (size_t)nb * 24u, (size_t)nb * 4u, hipMemcpyDeviceToHost, s.q_out)) != hipSuccess) { rc = bad("D2H out", e); break; }
@@ -712,6 +728,14 @@ struct Combiner {
   bool leader = false;
 };
 Combiner g_comb[4][13];   // [op][HC level]
+// accelerated compress: one combiner per (clamped) acceleration, so calls with different values never share a launch; created on first
+// use and kept (at most 65536 of them)
+std::mutex g_accel_comb_mu;
+std::map<int, Combiner> g_accel_comb;
+Combiner& accel_combiner(int accel) {
+  std::lock_guard<std::mutex> lk(g_accel_comb_mu);
+  return g_accel_comb[accel];   // (std::map: references stay valid while other entries are added)
+}
 
 // one host batch for all of `batch`; returns its rc (every request gets its out[]); may throw (allocation of the index vectors,
 // thread creation inside host_batch)
@@ -751,7 +775,10 @@ void run_combined(Op op, int level, std::vector<Req*>& batch) noexcept {
 
 int single(Op op, const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level = 0) {
   Req r{src, src_len, dst, dst_cap};
-  Combiner& c = g_comb[(int)op][level < 0 || level > 12 ? 0 : level];
+  Combiner* cp;
+  try { cp = op == OP_COMPRESS_ACCEL ? &accel_combiner(level) : &g_comb[(int)op][level < 0 || level > 12 ? 0 : level]; }
+  catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
+  Combiner& c = *cp;
   {
     std::unique_lock<std::mutex> lk(c.mu);
     try { c.q.push_back(&r); }
@@ -1225,6 +1252,12 @@ int lz4hip_compress_fast_batch(const uint8_t* src, const uint64_t* src_off, cons
                                const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n) {
   return host_batch(OP_COMPRESS_FAST, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
 }
+int lz4hip_compress_fast_accel_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                     const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int acceleration) {
+  const int a = accel_clamp(acceleration);
+  if (a == 1) return lz4hip_compress_fast_batch(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
+  return host_batch(OP_COMPRESS_ACCEL, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, a);
+}
 int lz4hip_decompress_safe_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                  const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n) {
   return host_batch(OP_DECODE_SAFE, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
@@ -1250,6 +1283,13 @@ int lz4hip_xxh64_batch(const uint8_t* buf, const uint64_t* off, const int32_t* l
 int lz4hip_compress_fast_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                    const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int device, void* stream) {
   return dev_batch(OP_COMPRESS_FAST, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, device, stream);
+}
+int lz4hip_compress_fast_accel_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                         const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int acceleration,
+                                         int device, void* stream) {
+  const int a = accel_clamp(acceleration);
+  if (a == 1) return lz4hip_compress_fast_batch_dev(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, device, stream);
+  return dev_batch(OP_COMPRESS_ACCEL, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, device, stream, a);
 }
 int lz4hip_decompress_safe_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                      const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int device, void* stream) {
@@ -1331,6 +1371,11 @@ int lz4hip_dbg_compress_fast_profile_dev(const uint8_t* src, const uint64_t* src
 
 // ---- single-block convenience ----
 int lz4hip_compress_fast(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap) { return single(OP_COMPRESS_FAST, src, src_len, dst, dst_cap); }
+int lz4hip_compress_fast_accel(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int acceleration) {
+  const int a = accel_clamp(acceleration);
+  if (a == 1) return lz4hip_compress_fast(src, src_len, dst, dst_cap);
+  return single(OP_COMPRESS_ACCEL, src, src_len, dst, dst_cap, a);
+}
 int lz4hip_compress_hc(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level) {
   int lv;
   if (hc_level(level, &lv)) return LZ4HIP_LIB_ERROR(LZ4HIP_E_UNSUPPORTED);

@@ -27,6 +27,9 @@ int launch_compress_fast_v2w(const BatchArgs& a, uint32_t* q, uint32_t* routed, 
 // 1 (default): blocks of 65547 bytes .. 4 MiB run on ten pairs per CU with compact table entries (compress_fast_v2wp_cu_kernel); 0: five pairs for all
 void set_compress_pack(int v);
 int launch_compress_fast_ms(const BatchArgs& a, uint32_t* q, const uint32_t* routed, bool first, uint32_t n_cus, void* stream);
+// LZ4_compress_fast(..., accel) for accel 2 .. 65537 (clamped by the caller; acceleration 1 is launch_compress_fast_v2w's): the
+// one-sequence-per-step core of lz4_fast_core.h with its ACC switch, five wavefronts per CU drawing blocks from q = one device uint32_t
+int launch_compress_fast_accel(const BatchArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream);
 #ifdef LZ4HIP_DEV_TOOLS
 int launch_compress_fast_prof(const BatchArgs& a, uint64_t* prof, int core, void* stream);  // developer build only (tools/build_variant.sh dev -DLZ4HIP_DEV_TOOLS)
 #endif

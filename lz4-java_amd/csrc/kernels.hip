@@ -8,6 +8,9 @@
 //                          per finder (no LDS needed) takes the batches through a ring in global memory and does all the output.
 //                          ms: every sequence of a 64-position window per step (lz4_fast_ms_core.h), for blocks of short sequences.
 //                          Bound: the serial parse chain of a wavefront x 5 chains per CU (roofline: HBM, 1+1/ratio B/B).
+//   compress_fast_accel_cu_kernel
+//                        : LZ4_compress_fast with acceleration 2 .. 65537: the one-sequence-per-step core of lz4_fast_core.h with
+//                          its ACC switch, 5 wavefronts per CU drawing blocks from a queue (acceleration 1 is the kernels above).
 //   decode_kernel<GL, SAFE, PIPE, STAGE>
 //                        : GL lanes per block, 64/GL blocks per wavefront, algorithm in lz4_decode_core.h; PIPE = software-
 //                          pipelined loop for small batches, STAGE = output through LDS as whole lines for large ones.
@@ -350,6 +353,52 @@ int launch_compress_fast_ms(const BatchArgs& a, uint32_t* q, const uint32_t* rou
   }
   const uint32_t wgs = (a.n + WAVES_PER_CU - 1u) / WAVES_PER_CU;
   hipLaunchKernelGGL(compress_fast_ms_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a, q, routed);
+  return (int)hipGetLastError();
+}
+
+// LZ4_compress_fast with acceleration 2 .. 65537: the one-sequence-per-step core with its ACC switch on (lz4_fast_core.h), byU16 below
+// 65547 bytes, byU32 (64-bit entries) above.  Same shape as the window-parallel kernel: WAVES_PER_CU wavefronts per workgroup, one
+// 32 KB table each, blocks drawn from the queue word q[0].
+__device__ __forceinline__ void compress_fast_accel_block(const BatchArgs& a, uint32_t b, uint64_t* table, uint32_t accel) {
+  const int32_t n = uniform_i32(a.src_len[b]);
+  const int32_t cap = uniform_i32(a.dst_cap[b]);
+  uint32_t r = 0;
+  if (n >= 0 && (uint32_t)n <= 0x7E000000u && cap >= 0) {
+    const uint8_t* s = uniform_ptr(a.src + a.src_off[b]);
+    uint8_t* d = uniform_ptr(a.dst + a.dst_off[b]);
+    WaveDev w(table);
+    DirectOut<WaveDev> out(w, s, (uint32_t)n, d, (uint32_t)cap);
+    if (n < 65547) {
+      FastCore<WaveDev, true, DirectOut<WaveDev>, false, true> c(w, out, s, (uint32_t)n);
+      c.accel = accel;
+      r = c.run();
+    } else {
+      FastCore<WaveDev, false, DirectOut<WaveDev>, false, true> c(w, out, s, (uint32_t)n);
+      c.accel = accel;
+      r = c.run();
+    }
+  }
+  if (__lane_id() == 0) a.out[b] = (int32_t)r;
+}
+__global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_accel_cu_kernel(BatchArgs a, uint32_t* q, uint32_t accel) {
+  __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
+  uint64_t* table = tables[threadIdx.x >> 6];
+  for (;;) {
+    uint32_t b = 0;
+    if (__lane_id() == 0) b = atomicAdd(q, 1u);
+    b = __builtin_amdgcn_readfirstlane(b);
+    if (b >= a.n) return;
+    compress_fast_accel_block(a, b, table, accel);
+    WaveDev::sync();  // the table is reused
+  }
+}
+int launch_compress_fast_accel(const BatchArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream) {
+  if (a.n == 0) return 0;
+  if (accel < 2u || accel > 65537u) return (int)hipErrorInvalidValue;   // (the caller clamps; 1 is the plain compressor's)
+  hipError_t e = hipMemsetAsync(q, 0, sizeof(uint32_t), (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  const uint32_t wgs = (a.n + WAVES_PER_CU - 1u) / WAVES_PER_CU;
+  hipLaunchKernelGGL(compress_fast_accel_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a, q, accel);
   return (int)hipGetLastError();
 }
 

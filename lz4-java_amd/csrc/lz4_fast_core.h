@@ -226,7 +226,11 @@ constexpr uint32_t SEQ_NOCHECK = 1u << 29, SEQ_LIT_MASK = (1u << 29) - 1u;
 // LZ4FrameOutputStream): the 4096 entries are 32 bits, {position (22 bits), fingerprint (10 bits)}, 16 KB instead of 32 -- twice the
 // match-finder chains per CU (kernels.hip, compress_fast_v2w8_cu_kernel).  A narrower fingerprint only means more tentative hits that
 // their candidate bytes rule out; what is accepted and what the table holds are liblz4's at any width.
-template <class W, bool U16, class Out = DirectOut<W>, bool PK = false>
+// ACC: LZ4_compress_fast(..., acceleration) -- every miss-run starts with searchMatchNb = accel << 6 instead of 1 << 6, so probe k
+// of a run sits at S + g_a(k) (see g_acc); `accel` (>= 1, clamped by the caller) is read only then.  Its steps no longer sit on
+// consecutive positions beyond the first two probes, so literals always come from the source, never from the window registers.
+// ACC = false is the acceleration-1 core every other kernel runs, unchanged.
+template <class W, bool U16, class Out = DirectOut<W>, bool PK = false, bool ACC = false>
 struct FastCore {
   static_assert(!(U16 && PK), "compact entries are a byU32 layout");
   static constexpr bool S32 = U16 || PK;           // entries are 32 bits
@@ -256,6 +260,7 @@ struct FastCore {
   // short sequences -- the window-parallel core (lz4_fast_ms_core.h) is the faster one for it; loop() then stops with
   // `bailed` set and the caller leaves the block to that core.
   uint32_t dense64 = 0;
+  uint32_t accel = 1;   // (ACC only) liblz4's acceleration, 1 .. 65537
   bool bailed = false, probe_done = false, one_done = false;
   uint32_t p_S = 0, p_ip = 0;
 
@@ -290,6 +295,12 @@ struct FastCore {
     VU T = k + 62u;
     VU M = T >> 6;
     return W::select(k >= 1u, VU(1u), VU(0u)) + 32u * M * (M - 1u) + M * (T - 64u * M + 1u);
+  }
+  // ACC: searchMatchNb starts at accel << 6, so every step after the first is accel - 1 longer: g_a(0) = 0, g_a(k) = g(k) + (a-1)(k-1).
+  // (u32 throughout: a probe that is still valid has g(k) <= n and (a-1)(k-1) <= n, the 64 lanes of a step add < 64 * (a + k/64))
+  LZ4HIP_DEV VU g_acc(VU k) const {
+    if constexpr (ACC) return g(k) + W::select(k >= 1u, k - 1u, VU(0u)) * (accel - 1u);
+    else return g(k);
   }
 
   // ---- match extension ------------------------------------------------------------------------
@@ -351,8 +362,9 @@ struct FastCore {
     const VB sp_isrun = j >= nspecial;
     const VU k = j - nspecial + r;
     VU prun, pnext;
-    if (LZ4HIP_LIKELY(r + 64u - nspecial <= 65u)) { prun = k + S; pnext = prun + 1u; }  // probes 0..65 of a run are consecutive
-    else { prun = g(k) + S; pnext = g(k + 1u) + S; }
+    // probes 0..65 of a run are consecutive (ACC: only probes 0 and 1, and a step has more lanes than that)
+    if (!ACC && LZ4HIP_LIKELY(r + 64u - nspecial <= 65u)) { prun = k + S; pnext = prun + 1u; }
+    else { prun = g_acc(k) + S; pnext = g_acc(k + 1u) + S; }
     sp_pos = W::select(sp_isrun, prun, W::select(j == 0u, VU(ip - 2u), VU(ip)));
     // special lanes (0,1 of a post step) are always valid; lane 0 of a post step only inserts
     sp_validm = w.ballot(pnext <= mfl1) | (uint64_t)(post ? 3u : 0u);
@@ -577,7 +589,8 @@ struct FastCore {
         const uint32_t lit = (hpos - back) - anchor;
         // literals straight from this step's window registers: lane l (>= 1) of a post step sits on position
         // anchor + l - 1 (its run started in this step); needs at most one length byte each and lane 63 free
-        const bool regs = Out::kUsesWindowRegs && was_post && mc < 270u &&
+        // (ACC: lane l >= 4 sits further on -- the literals come from the source)
+        const bool regs = !ACC && Out::kUsesWindowRegs && was_post && mc < 270u &&
                           (1u + (lit >= 15u ? 1u : 0u) + lit + 2u + (mc >= 15u ? 1u : 0u) <= 63u);
         out.seq(lit, mc, hpos - mpos, anchor, !hit_post, regs, b0);
       }

@@ -62,13 +62,18 @@ class LZ4Compressor {
   bytes compress(const bytes& src) const { return compress(src, 0, (int)src.size()); }
 };
 
+// acceleration != 1: the bytes of liblz4's LZ4_compress_fast(..., acceleration) (lz4hip_compress_fast_accel; < 1 acts as 1, > 65537 as 65537)
 class LZ4HIPCompressor final : public LZ4Compressor {
+  int accel_;
  public:
   using LZ4Compressor::compress;
+  explicit LZ4HIPCompressor(int acceleration = 1) : accel_(acceleration) {}
+  int acceleration() const { return accel_; }
   int compress(const bytes& src, int srcOff, int srcLen, bytes& dest, int destOff, int maxDestLen) const override {
     util::checkRange(src, srcOff, srcLen);
     util::checkRange(dest, destOff, maxDestLen);
-    const int result = libCheck(lz4hip_compress_fast(src.data() + srcOff, srcLen, dest.data() + destOff, maxDestLen));
+    const int result = libCheck(accel_ == 1 ? lz4hip_compress_fast(src.data() + srcOff, srcLen, dest.data() + destOff, maxDestLen)
+                                            : lz4hip_compress_fast_accel(src.data() + srcOff, srcLen, dest.data() + destOff, maxDestLen, accel_));
     if (result <= 0) throw LZ4Exception("maxDestLen is too small");
     return result;
   }
@@ -139,6 +144,10 @@ class LZ4Factory {
  public:
   static LZ4Factory& hipInstance() { static LZ4Factory f; return f; }
   const LZ4Compressor& fastCompressor() const { return fast_; }
+  // a fast compressor bound to LZ4_compress_fast's acceleration (1 = the bytes of fastCompressor())
+  std::unique_ptr<LZ4Compressor> fastCompressor(int acceleration) const {
+    return std::unique_ptr<LZ4Compressor>(new LZ4HIPCompressor(acceleration));
+  }
   std::unique_ptr<LZ4Compressor> highCompressor(int compressionLevel = 9) const {  // clamp: LZ4Factory.java:263-270
     if (compressionLevel > 17) compressionLevel = 17; else if (compressionLevel < 1) compressionLevel = 9;
     return std::unique_ptr<LZ4Compressor>(new LZ4HCHIPCompressor(compressionLevel));

@@ -61,6 +61,16 @@ public final class LZ4HIPBatch {
     run(0, 0, src, srcOff, srcLen, dest, destOff, destCap, outLen);
   }
 
+  /**
+   * The bytes of liblz4's {@code LZ4_compress_fast(..., acceleration)} per block (acceleration below 1 acts as 1, above 65537 as
+   * 65537; 1 is {@link #compress(ByteBuffer, long[], int[], ByteBuffer, long[], int[], int[])}).  outLen[i] &gt; 0: compressed size;
+   * 0: destCap[i] too small.
+   */
+  public static void compress(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen,
+      int acceleration) {
+    run(4, acceleration, src, srcOff, srcLen, dest, destOff, destCap, outLen);
+  }
+
   /** outLen[i] &gt;= 0: decompressed size; &lt; 0: -(input position)-1. */
   public static void decompressSafe(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen) {
     run(1, 0, src, srcOff, srcLen, dest, destOff, destCap, outLen);

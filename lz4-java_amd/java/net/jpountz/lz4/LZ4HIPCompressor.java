@@ -28,17 +28,36 @@ import java.nio.ByteBuffer;
  * Fast {@link LZ4Compressor} of the "HIP" family: byte-identical output to {@code LZ4JNICompressor}
  * (liblz4 1.9.3 LZ4_compress_default), computed on the GPU.  Same checks, same order and same
  * exception as LZ4JNICompressor.java:35-82.
+ *
+ * {@code new LZ4HIPCompressor(acceleration)}: the bytes of liblz4's {@code LZ4_compress_fast(..., acceleration)} instead (below 1
+ * acts as 1, above 65537 as 65537).  {@link #INSTANCE} is acceleration 1.
  */
 final class LZ4HIPCompressor extends LZ4Compressor {
 
   public static final LZ4Compressor INSTANCE = new LZ4HIPCompressor();
   private static LZ4Compressor SAFE_INSTANCE;
 
+  private final int acceleration;
+
+  LZ4HIPCompressor() {
+    this(1);
+  }
+
+  LZ4HIPCompressor(int acceleration) {
+    this.acceleration = acceleration;
+  }
+
+  private int nativeCompress(byte[] srcArr, ByteBuffer srcBuf, int srcOff, int srcLen, byte[] destArr, ByteBuffer destBuf, int destOff, int maxDestLen) {
+    return acceleration == 1
+        ? LZ4HIPJNI.LZ4HIP_compress_fast(srcArr, srcBuf, srcOff, srcLen, destArr, destBuf, destOff, maxDestLen)
+        : LZ4HIPJNI.LZ4HIP_compress_fast_accel(srcArr, srcBuf, srcOff, srcLen, destArr, destBuf, destOff, maxDestLen, acceleration);
+  }
+
   @Override
   public int compress(byte[] src, int srcOff, int srcLen, byte[] dest, int destOff, int maxDestLen) {
     checkRange(src, srcOff, srcLen);
     checkRange(dest, destOff, maxDestLen);
-    final int result = LZ4HIPJNI.LZ4HIP_compress_fast(src, null, srcOff, srcLen, dest, null, destOff, maxDestLen);
+    final int result = nativeCompress(src, null, srcOff, srcLen, dest, null, destOff, maxDestLen);
     if (result <= 0) {
       throw new LZ4Exception(result == 0 ? "maxDestLen is too small" : "liblz4hip: " + LZ4HIPJNI.lastError());
     }
@@ -66,10 +85,25 @@ final class LZ4HIPCompressor extends LZ4Compressor {
       } else {
         destBuf = dest;
       }
-      final int result = LZ4HIPJNI.LZ4HIP_compress_fast(srcArr, srcBuf, srcOff, srcLen, destArr, destBuf, destOff, maxDestLen);
+      final int result = nativeCompress(srcArr, srcBuf, srcOff, srcLen, destArr, destBuf, destOff, maxDestLen);
       if (result <= 0) {
         throw new LZ4Exception(result == 0 ? "maxDestLen is too small" : "liblz4hip: " + LZ4HIPJNI.lastError());
       }
+      return result;
+    } else if (acceleration != 1) {
+      // neither array-backed nor direct, accelerated: the safe instance would produce acceleration-1 bytes, so the block goes
+      // through byte[] copies instead
+      final byte[] srcArr = new byte[srcLen];
+      final byte[] destArr = new byte[maxDestLen];
+      final ByteBuffer s = src.duplicate();
+      s.clear();   // (position 0, limit = capacity: the checked range, whatever the caller's position / limit are)
+      s.position(srcOff);
+      s.get(srcArr, 0, srcLen);
+      final int result = compress(srcArr, 0, srcLen, destArr, 0, maxDestLen);
+      final ByteBuffer d = dest.duplicate();
+      d.clear();
+      d.position(destOff);
+      d.put(destArr, 0, result);
       return result;
     } else {
       // neither array-backed nor direct: same escape hatch as the JNI family (LZ4JNICompressor.java:75-80)

@@ -48,6 +48,9 @@ enum LZ4HIPJNI {
    * library failure (no GPU, HIP error), which the callers turn into an LZ4Exception as well */
   static native int LZ4HIP_compress_fast(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
                                          byte[] destArray, ByteBuffer destBuffer, int destOff, int maxDestLen);
+  /* LZ4_compress_fast(..., acceleration): the arguments, NULL / pinning rules and return conventions of LZ4HIP_compress_fast */
+  static native int LZ4HIP_compress_fast_accel(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
+                                               byte[] destArray, ByteBuffer destBuffer, int destOff, int maxDestLen, int acceleration);
   static native int LZ4HIP_compressHC(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
                                       byte[] destArray, ByteBuffer destBuffer, int destOff, int maxDestLen, int compressionLevel);
   static native int LZ4HIP_decompress_fast(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcCap,
@@ -57,7 +60,8 @@ enum LZ4HIPJNI {
   static native int LZ4HIP_compressBound(int len);
 
   /* batches over DIRECT buffers (so the shim never pins the Java heap across a kernel):
-   * op 0 = fast compress, 1 = safe decompress, 2 = fast decompress, 3 = HC compress(level).
+   * op 0 = fast compress, 1 = safe decompress, 2 = fast decompress, 3 = HC compress(level),
+   * 4 = accelerated fast compress (level = acceleration).
    * Returns 0 or a negative lz4hip_status; per-block results land in outLen. */
   static native int LZ4HIP_batch(int op, int level, ByteBuffer src, long[] srcOff, int[] srcLen,
                                  ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, int nBlocks);

@@ -91,6 +91,7 @@ static jint run_single(JNIEnv* env, int op, int level, jbyteArray srcArray, jobj
     case 0: result = lz4hip_compress_fast(in.p, srcLen, out.p, destLen); break;
     case 1: result = lz4hip_decompress_safe(in.p, srcLen, out.p, destLen); break;
     case 2: result = lz4hip_decompress_fast(in.p, srcLen /* readable capacity */, out.p, destLen); break;
+    case 4: result = lz4hip_compress_fast_accel(in.p, srcLen, out.p, destLen, level /* acceleration */); break;
     default: result = lz4hip_compress_hc(in.p, srcLen, out.p, destLen, level); break;
   }
   region_out(env, NULL, 0, 0, &in);
@@ -107,6 +108,13 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1fast(JNI
     jint srcOff, jint srcLen, jbyteArray destArray, jobject destBuffer, jint destOff, jint maxDestLen) {
   (void)cls;
   return run_single(env, 0, 0, srcArray, srcBuffer, srcOff, srcLen, destArray, destBuffer, destOff, maxDestLen);
+}
+
+/* LZ4_compress_fast(..., acceleration): same arguments, staging and return convention as LZ4HIP_compress_fast */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1fast_1accel(JNIEnv* env, jclass cls, jbyteArray srcArray, jobject srcBuffer,
+    jint srcOff, jint srcLen, jbyteArray destArray, jobject destBuffer, jint destOff, jint maxDestLen, jint acceleration) {
+  (void)cls;
+  return run_single(env, 4, acceleration, srcArray, srcBuffer, srcOff, srcLen, destArray, destBuffer, destOff, maxDestLen);
 }
 
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compressHC(JNIEnv* env, jclass cls, jbyteArray srcArray, jobject srcBuffer,
@@ -155,6 +163,7 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batch(JNIEnv* env,
       case 0: rc = lz4hip_compress_fast_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)dc, (int32_t*)ol, (uint32_t)n); break;
       case 1: rc = lz4hip_decompress_safe_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)dc, (int32_t*)ol, (uint32_t)n); break;
       case 2: rc = lz4hip_decompress_fast_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)dc, (int32_t*)ol, (uint32_t)n); break;
+      case 4: rc = lz4hip_compress_fast_accel_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)dc, (int32_t*)ol, (uint32_t)n, level); break;
       default: rc = lz4hip_compress_hc_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)dc, (int32_t*)ol, (uint32_t)n, level); break;
     }
   }

@@ -35,12 +35,13 @@ def gather_sizes(local_sizes, n_blocks, group=None):
     return torch.cat(parts)
 
 
-def compress_sharded(codec, n_blocks, group=None):
+def compress_sharded(codec, n_blocks, group=None, acceleration=None):
     """Runs `codec(b0, b1) -> int32 tensor of sizes for blocks [b0, b1)` on this rank's range and
     returns (my_range, all_sizes).  On a GPU rank `codec` launches DeviceBatch.compress_fast on the
-    rank's slice; the function itself is device-agnostic."""
+    rank's slice; the function itself is device-agnostic.  acceleration (LZ4_compress_fast's): passed
+    on as codec(b0, b1, acceleration=...) for a codec that takes one; None calls codec(b0, b1)."""
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0
     b0, b1 = block_range(n_blocks, world, rank)
-    local = codec(b0, b1)
+    local = codec(b0, b1) if acceleration is None else codec(b0, b1, acceleration=acceleration)
     return (b0, b1), gather_sizes(local, n_blocks, group)

@@ -1,0 +1,178 @@
+/* tests/jni_stub/fake_jni_accel.c -- TEST INFRASTRUCTURE ONLY.
+ *
+ * The accelerated fast-compress native of the JNI shim (LZ4HIPJNI.LZ4HIP_compress_fast_accel and LZ4HIP_batch op 4) executed
+ * without a JVM, with the same fake JNIEnv as fake_jni.c (a byte[] / int[] / long[] is a malloc'd buffer with pin accounting, a
+ * direct ByteBuffer is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built by tests/test_gpu_accel.py /
+ * tests/test_accel_abi.py.
+ *
+ *   fake_jni_accel --no-gpu            anywhere: the new native fails LOUDLY without a device (library error code, nothing leaked)
+ *   fake_jni_accel <input> <out-dir>   on a GPU box: compresses <input> through every argument shape at accelerations 1 and 8 and
+ *                                      writes the streams to <out-dir>/accel_<a>.bin (the test compares them with the reference
+ *                                      library's LZ4_compress_fast); prints "fake_jni_accel: N checks ok"
+ */
+#include <jni.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "lz4hip.h"
+
+typedef struct {
+  int kind;          /* 1 = byte[], 2 = int[], 3 = long[], 4 = direct ByteBuffer, 5 = heap ByteBuffer (no direct address) */
+  uint8_t* data;
+  size_t bytes;
+  int pins;
+  int refuse_pin;
+} fobj;
+
+static long g_alloc = 0;
+void* t_malloc(size_t n) { g_alloc++; return malloc(n); }
+void t_free(void* p) { if (p) g_alloc--; free(p); }
+
+static const char* g_exc_class = NULL;
+static char g_exc_msg[512];
+static int g_checks = 0;
+
+#define CHECK(c) do { if (!(c)) { fprintf(stderr, "fake_jni_accel: CHECK failed at line %d: %s (pending exception: %s \"%s\")\n", __LINE__, #c, \
+    g_exc_class ? g_exc_class : "none", g_exc_msg); exit(1); } g_checks++; } while (0)
+
+static jclass f_FindClass(JNIEnv* e, const char* name) { (void)e; return (jclass)strdup(name); }
+static jint f_ThrowNew(JNIEnv* e, jclass c, const char* msg) { (void)e; g_exc_class = (const char*)c; snprintf(g_exc_msg, sizeof g_exc_msg, "%s", msg ? msg : ""); return 0; }
+static jobject f_NewGlobalRef(JNIEnv* e, jobject o) { (void)e; return o; }
+static void* f_GetCritical(JNIEnv* e, jarray a, jboolean* isCopy) {
+  (void)e; fobj* o = (fobj*)a;
+  if (isCopy) *isCopy = 0;
+  if (o->refuse_pin) return NULL;
+  o->pins++;
+  return o->data;
+}
+static void f_ReleaseCritical(JNIEnv* e, jarray a, void* p, jint mode) { (void)e; (void)mode; fobj* o = (fobj*)a; if (p != o->data) { fprintf(stderr, "release of a foreign pointer\n"); exit(1); } o->pins--; }
+static void* f_GetDirect(JNIEnv* e, jobject b) { (void)e; fobj* o = (fobj*)b; return o->kind == 4 ? o->data : NULL; }
+static jstring f_NewStringUTF(JNIEnv* e, const char* s) { (void)e; return (jstring)strdup(s ? s : ""); }
+static jlong* f_GetLongs(JNIEnv* e, jlongArray a, jboolean* c) { (void)e; if (c) *c = 0; ((fobj*)a)->pins++; return (jlong*)((fobj*)a)->data; }
+static jint* f_GetInts(JNIEnv* e, jintArray a, jboolean* c) { (void)e; if (c) *c = 0; ((fobj*)a)->pins++; return (jint*)((fobj*)a)->data; }
+static void f_RelLongs(JNIEnv* e, jlongArray a, jlong* p, jint m) { (void)e; (void)p; (void)m; ((fobj*)a)->pins--; }
+static void f_RelInts(JNIEnv* e, jintArray a, jint* p, jint m) { (void)e; (void)p; (void)m; ((fobj*)a)->pins--; }
+static jint f_ArrayLength(JNIEnv* e, jarray a) { (void)e; const fobj* o = (const fobj*)a; return (jint)(o->bytes / (o->kind == 3 ? 8u : o->kind == 2 ? 4u : 1u)); }
+
+static const struct JNINativeInterface_ g_table = {f_FindClass, f_ThrowNew, f_NewGlobalRef, f_GetCritical, f_ReleaseCritical, f_GetDirect,
+                                                   f_NewStringUTF, f_GetLongs, f_GetInts, f_RelLongs, f_RelInts, f_ArrayLength};
+static JNIEnv g_env = &g_table;
+
+static fobj* mk(int kind, size_t bytes) { fobj* o = calloc(1, sizeof *o); o->kind = kind; o->bytes = bytes; o->data = calloc(bytes ? bytes : 1, 1); return o; }
+static int no_exc(void) { return g_exc_class == NULL; }
+static void clear_exc(void) { g_exc_class = NULL; g_exc_msg[0] = 0; }
+/* every byte of o outside [off, off + n) still holds `fill` */
+static int guarded(const fobj* o, size_t off, size_t n, uint8_t fill) {
+  for (size_t i = 0; i < o->bytes; i++)
+    if ((i < off || i >= off + n) && o->data[i] != fill) return 0;
+  return 1;
+}
+
+JNIEXPORT void JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_init(JNIEnv*, jclass);
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1fast(JNIEnv*, jclass, jbyteArray, jobject, jint, jint, jbyteArray, jobject, jint, jint);
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1fast_1accel(JNIEnv*, jclass, jbyteArray, jobject, jint, jint, jbyteArray, jobject, jint, jint, jint);
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batch(JNIEnv*, jclass, jint, jint, jobject, jlongArray, jintArray, jobject, jlongArray, jintArray, jintArray, jint);
+JNIEXPORT jstring JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_lastError(JNIEnv*, jclass);
+
+#define ACCEL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1fast_1accel
+
+int main(int argc, char** argv) {
+  JNIEnv* env = &g_env;
+  Java_net_jpountz_lz4_LZ4HIPJNI_init(env, NULL);
+  CHECK(no_exc());
+  if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+    fobj* src = mk(1, 64); fobj* dst = mk(1, 128);
+    for (int a = -3; a <= 9; a += 4) {   /* (acceleration 1 and below go through the plain fast path: loud as well) */
+      jint r = ACCEL(env, NULL, (jbyteArray)src, NULL, 7, 20, (jbyteArray)dst, NULL, 3, 100, a);
+      CHECK(LZ4HIP_IS_LIB_ERROR(r) && no_exc() && g_alloc == 0 && src->pins == 0 && dst->pins == 0);
+    }
+    const char* msg = (const char*)Java_net_jpountz_lz4_LZ4HIPJNI_lastError(env, NULL);
+    CHECK(msg && strlen(msg) > 0);
+    printf("fake_jni_accel: %d checks ok (no device: every compute call failed loudly)\n", g_checks);
+    return 0;
+  }
+  if (argc < 3) { fprintf(stderr, "usage: fake_jni_accel --no-gpu | <input> <out-dir>\n"); return 2; }
+  FILE* f = fopen(argv[1], "rb");
+  CHECK(f != NULL);
+  fseek(f, 0, SEEK_END);
+  const long n = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  CHECK(n > 1000 && n < (1 << 24));
+  const int bound = (int)n + (int)n / 255 + 16;
+  const size_t SO = 5, DO = 7;   /* offsets of the regions inside their arrays / buffers */
+  fobj* asrc = mk(1, (size_t)n + 16); fobj* dsrc = mk(4, (size_t)n + 16);
+  CHECK(fread(asrc->data + SO, 1, (size_t)n, f) == (size_t)n);
+  fclose(f);
+  memcpy(dsrc->data + SO, asrc->data + SO, (size_t)n);
+  fobj* adst = mk(1, (size_t)bound + 32); fobj* ddst = mk(4, (size_t)bound + 32);
+  const int accels[2] = {1, 8};
+  jint sizes[2] = {0, 0};
+  for (int t = 0; t < 2; t++) {
+    const int a = accels[t];
+    /* byte[] -> byte[] */
+    memset(adst->data, 0xEE, adst->bytes);
+    jint r = ACCEL(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, (jbyteArray)adst, NULL, (jint)DO, bound, a);
+    CHECK(no_exc() && r > 0 && g_alloc == 0 && asrc->pins == 0 && adst->pins == 0);
+    CHECK(guarded(adst, DO, (size_t)r, 0xEE));
+    sizes[t] = r;
+    char path[4096];
+    snprintf(path, sizeof path, "%s/accel_%d.bin", argv[2], a);
+    FILE* o = fopen(path, "wb");
+    CHECK(o != NULL && fwrite(adst->data + DO, 1, (size_t)r, o) == (size_t)r);
+    fclose(o);
+    /* direct -> direct (NULL arrays): the same bytes */
+    memset(ddst->data, 0xEE, ddst->bytes);
+    jint r2 = ACCEL(env, NULL, NULL, (jobject)dsrc, (jint)SO, (jint)n, NULL, (jobject)ddst, (jint)DO, bound, a);
+    CHECK(no_exc() && r2 == r && memcmp(ddst->data + DO, adst->data + DO, (size_t)r) == 0 && guarded(ddst, DO, (size_t)r, 0xEE) && g_alloc == 0);
+    /* byte[] -> direct and direct -> byte[] */
+    memset(ddst->data, 0xEE, ddst->bytes);
+    r2 = ACCEL(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, NULL, (jobject)ddst, (jint)DO, bound, a);
+    CHECK(no_exc() && r2 == r && memcmp(ddst->data + DO, adst->data + DO, (size_t)r) == 0 && g_alloc == 0 && asrc->pins == 0);
+    fobj* adst2 = mk(1, (size_t)bound + 32);
+    memset(adst2->data, 0xEE, adst2->bytes);
+    r2 = ACCEL(env, NULL, NULL, (jobject)dsrc, (jint)SO, (jint)n, (jbyteArray)adst2, NULL, (jint)DO, bound, a);
+    CHECK(no_exc() && r2 == r && memcmp(adst2->data + DO, adst->data + DO, (size_t)r) == 0 && guarded(adst2, DO, (size_t)r, 0xEE) && g_alloc == 0);
+    /* too small by one byte: 0, and the staged byte[] destination is not touched at all */
+    memset(adst2->data, 0xEE, adst2->bytes);
+    r2 = ACCEL(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, (jbyteArray)adst2, NULL, (jint)DO, r - 1, a);
+    CHECK(no_exc() && r2 == 0 && guarded(adst2, 0, 0, 0xEE) && g_alloc == 0 && adst2->pins == 0);
+    /* ... a direct destination: nothing outside the slot */
+    memset(ddst->data, 0xEE, ddst->bytes);
+    r2 = ACCEL(env, NULL, NULL, (jobject)dsrc, (jint)SO, (jint)n, NULL, (jobject)ddst, (jint)DO, r - 1, a);
+    CHECK(no_exc() && r2 == 0 && guarded(ddst, DO, (size_t)r - 1, 0xEE));
+    free(adst2->data); free(adst2);
+  }
+  /* acceleration 1 through the new native IS the plain native */
+  { fobj* p = mk(1, (size_t)bound + 32);
+    jint r = Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1fast(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, (jbyteArray)p, NULL, (jint)DO, bound);
+    fobj* q = mk(1, (size_t)bound + 32);
+    jint r2 = ACCEL(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, (jbyteArray)q, NULL, (jint)DO, bound, -4);   /* clamps to 1 */
+    CHECK(no_exc() && r == sizes[0] && r2 == r && memcmp(p->data, q->data, p->bytes) == 0); }
+  /* a heap ByteBuffer where a direct one is required: no address, OutOfMemoryError as for the plain native */
+  { fobj* hb = mk(5, 64);
+    (void)ACCEL(env, NULL, NULL, (jobject)hb, 0, 20, (jbyteArray)adst, NULL, 0, 100, 8);
+    CHECK(g_exc_class && strcmp(g_exc_class, "java/lang/OutOfMemoryError") == 0 && g_alloc == 0);
+    clear_exc(); }
+  /* `out` cannot be pinned: `in` is released, OutOfMemoryError */
+  { fobj* nopin = mk(1, (size_t)bound); nopin->refuse_pin = 1;
+    (void)ACCEL(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, (jbyteArray)nopin, NULL, 0, bound, 8);
+    CHECK(g_exc_class && strcmp(g_exc_class, "java/lang/OutOfMemoryError") == 0 && g_alloc == 0 && asrc->pins == 0 && nopin->pins == 0);
+    clear_exc(); }
+  /* the batch entry, op 4: two copies of the input at acceleration 8 -> the single call's bytes twice */
+  { fobj* bsrc = mk(4, 2 * (size_t)n); fobj* bdst = mk(4, 2 * (size_t)bound);
+    memcpy(bsrc->data, asrc->data + SO, (size_t)n); memcpy(bsrc->data + n, asrc->data + SO, (size_t)n);
+    fobj* so = mk(3, 16); fobj* sl = mk(2, 8); fobj* dof = mk(3, 16); fobj* dc = mk(2, 8); fobj* ol = mk(2, 8);
+    ((jlong*)so->data)[0] = 0; ((jlong*)so->data)[1] = n; ((jint*)sl->data)[0] = ((jint*)sl->data)[1] = (jint)n;
+    ((jlong*)dof->data)[0] = 0; ((jlong*)dof->data)[1] = bound; ((jint*)dc->data)[0] = ((jint*)dc->data)[1] = bound;
+    jint rc = Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batch(env, NULL, 4, 8, (jobject)bsrc, (jlongArray)so, (jintArray)sl, (jobject)bdst,
+                                                           (jlongArray)dof, (jintArray)dc, (jintArray)ol, 2);
+    const jint* out = (const jint*)ol->data;
+    CHECK(rc == 0 && out[0] == sizes[1] && out[1] == sizes[1] && so->pins == 0 && ol->pins == 0);
+    fobj* ref8 = mk(1, (size_t)bound + 32);
+    (void)ACCEL(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, (jbyteArray)ref8, NULL, 0, bound, 8);
+    CHECK(memcmp(bdst->data, ref8->data, (size_t)sizes[1]) == 0 && memcmp(bdst->data + bound, ref8->data, (size_t)sizes[1]) == 0); }
+  CHECK(sizes[1] > sizes[0]);   /* acceleration 8 trades ratio for speed: a bigger stream on this input */
+  printf("fake_jni_accel: %d checks ok\n", g_checks);
+  return 0;
+}
