@@ -13,6 +13,8 @@
  *   lz4hip_compress_bound     <- ..._LZ4_1compressBound    -> LZ4_compressBound   (LZ4JNI.c:234-239)
  *   lz4hip_compress_fast_accel*  = LZ4_compress_fast(src, dst, n, cap, acceleration) of liblz4's main API (exported by the
  *                                reference's liblz4-java.so; no JNI entry of the reference reaches it)
+ *   lz4hip_compress_dest_size*   = LZ4_compress_destSize(src, dst, &srcSize, targetDstSize) of liblz4's main API (exported by
+ *                                the reference's liblz4-java.so; no JNI entry of the reference reaches it)
  *   lz4hip_xxh32* / xxh64*    <- Java_net_jpountz_xxhash_XXHashJNI_XXH32 / XXH64
  *                                (src/jni/net_jpountz_xxhash_XXHashJNI.c:42-59 / :152-169, calls :54 / :164)
  *
@@ -114,6 +116,23 @@ int lz4hip_compress_fast_batch(const uint8_t* src, const uint64_t* src_off, cons
 int lz4hip_compress_fast_accel_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                      int32_t* out_len, uint32_t n_blocks, int acceleration);
+/* COMPRESS TO A TARGET SIZE: the bytes, return value and consumed size of LZ4_compress_destSize(src, dst, &srcSize, targetDstSize),
+ * liblz4 1.9.3: as much of block i as fits in exactly target_size[i] bytes.  Acceleration 1; the table type follows the whole
+ * src_len[i] (byU16 below 65547 bytes, byU32 from there on, blocks up to 0x7E000000 bytes).
+ *   - out_len[i] is liblz4's return value: the bytes written (<= target_size[i]), 0 for target_size[i] <= 0 and for src_len[i] < 0
+ *     or > 0x7E000000; an empty block gives the single token 0x00 (1 byte) for any target >= 1;
+ *   - src_consumed[i] is what liblz4 leaves in *srcSizePtr: the input bytes the output covers (decoding out_len[i] bytes gives back
+ *     exactly src[0 .. src_consumed[i])), and src_len[i] itself where it returns 0 up front;
+ *   - target_size[i] >= compressBound(src_len[i]): the bytes of lz4hip_compress_fast, all of the input consumed;
+ *   - block i's slot is dst[dst_off[i] .. + target_size[i]): nothing is written past it;
+ *   - one kernel (compress_fast_dest_cu_kernel: the one-sequence-per-step core in fill mode, five wavefronts per CU); a block stops
+ *     once its target is full, so its time follows the input consumed, not src_len[i];
+ *   - the host batch shards over the initialised devices, returns only the useful bytes of every slot as the fast path does and
+ *     brings src_consumed back with the sizes; library failures as the status of the call;
+ *   - single calls (lz4hip_compress_dest_size) are coalesced with concurrent destSize calls only, through a combiner of their own. */
+int lz4hip_compress_dest_size_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                    uint8_t* dst, const uint64_t* dst_off, const int32_t* target_size,
+                                    int32_t* out_len, int32_t* src_consumed, uint32_t n_blocks);
 int lz4hip_compress_hc_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                              uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                              int32_t* out_len, uint32_t n_blocks, int level);
@@ -152,6 +171,10 @@ int lz4hip_compress_fast_batch_dev(const uint8_t* src, const uint64_t* src_off, 
 int lz4hip_compress_fast_accel_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                          uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                          int32_t* out_len, uint32_t n_blocks, int acceleration, int device, void* stream);
+/* compress to a target size (see lz4hip_compress_dest_size_batch), device pointers, asynchronous */
+int lz4hip_compress_dest_size_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                        uint8_t* dst, const uint64_t* dst_off, const int32_t* target_size,
+                                        int32_t* out_len, int32_t* src_consumed, uint32_t n_blocks, int device, void* stream);
 /* HC: levels follow liblz4 (< 1 -> 9, > 12 -> 12): 1..9 = hash-chain strategy with lazy evaluation, 10..12 = optimal
  * parser (lz4-java levels 10..17).  Levels 10..12 are FUNCTIONAL ONLY: byte-identical output, but the optimal parser's table
  * walk is wave-uniform scalar work (about 1.0 / 0.7 GB/s per GPU at levels 10 / 12 -- no faster than the reference on the host's
@@ -190,6 +213,9 @@ int lz4hip_xxh64_batch_dev(const uint8_t* buf, const uint64_t* off, const int32_
 #define LZ4HIP_IS_LIB_ERROR(ret) ((ret) < (int)(INT32_MIN + 64))
 int lz4hip_compress_fast(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap);
 int lz4hip_compress_fast_accel(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int acceleration);  /* LZ4_compress_fast */
+/* LZ4_compress_destSize: *src_size in = block size, out = input consumed; returns the bytes written.  A library failure returns
+ * LZ4HIP_LIB_ERROR(status) and leaves *src_size untouched; src_size == NULL is LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
+int lz4hip_compress_dest_size(const uint8_t* src, int* src_size, uint8_t* dst, int target_size);
 int lz4hip_compress_hc(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level);
 int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap);
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len);

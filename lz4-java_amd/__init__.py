@@ -47,6 +47,7 @@ C_ABI = {
     "lz4hip_compress_bound": (C.c_int, [C.c_int]),
     "lz4hip_compress_fast_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_compress_fast_accel_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_int]),
+    "lz4hip_compress_dest_size_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_compress_hc_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_int]),
     "lz4hip_decompress_safe_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_decompress_fast_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
@@ -54,6 +55,7 @@ C_ABI = {
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_fast_accel_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "lz4hip_compress_dest_size_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_hc_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_int]),
     "lz4hip_compress_hc_batch_dev_ws": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
@@ -63,6 +65,7 @@ C_ABI = {
     "lz4hip_xxh64_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_compress_fast_accel": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "lz4hip_compress_dest_size": (C.c_int, [C.c_void_p, _i32p, C.c_void_p, C.c_int]),
     "lz4hip_compress_hc": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_decompress_safe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
@@ -228,6 +231,20 @@ class LZ4HIPCompressor(LZ4Compressor):
         if self.acceleration == 1:
             return _single(lib().lz4hip_compress_fast(sp, src_len, dp, max_dest_len))
         return _single(lib().lz4hip_compress_fast_accel(sp, src_len, dp, max_dest_len, self.acceleration))
+
+    def compressDestSize(self, src, srcOff, srcLen, dest, destOff, targetDestSize):
+        """liblz4's LZ4_compress_destSize: compresses as much of src[srcOff:srcOff+srcLen] as fits in exactly targetDestSize bytes
+        at dest[destOff:] -> (written, consumed): the bytes written and the source bytes they cover (lz4hip_compress_dest_size).
+        liblz4 has no accelerated destSize: an accelerated compressor raises NotImplementedError."""
+        if self.acceleration > 1:
+            raise NotImplementedError("compressDestSize: liblz4 has no accelerated destSize (acceleration %d)" % self.acceleration)
+        dp, dk = _rw_ptr(dest)                      # the argument checks of compress()
+        _check_range(src, srcOff, srcLen)
+        _check_range(dest, destOff, targetDestSize)
+        sp, sk = _ro_ptr(src)
+        size = C.c_int32(srcLen)
+        written = _single(lib().lz4hip_compress_dest_size(sp + srcOff, C.byref(size), dp + destOff, targetDestSize))
+        return written, size.value
 
     def __str__(self):
         return "LZ4HIPCompressor" if self.acceleration == 1 else "LZ4HIPCompressor(acceleration=%d)" % self.acceleration
@@ -570,6 +587,26 @@ class LZ4HIPBatch:
         return cls._call("lz4hip_compress_fast_accel_batch", src, srcOff, srcLen, dst, dstOff, dstCap, int(acceleration))
 
     @classmethod
+    def compressDestSize(cls, src, srcOff, srcLen, dst, dstOff, targetSize):
+        """LZ4_compress_destSize per block: as much of block i as fits in exactly targetSize[i] bytes at dst[dstOff[i]:]
+        -> (outLen, srcConsumed) (lz4hip_compress_dest_size_batch; lists, or int32 arrays for numpy inputs)"""
+        n = len(srcOff)
+        if not (len(srcLen) == len(dstOff) == len(targetSize) == n):
+            raise ValueError("per-block arrays differ in length")
+        cls._check_ranges(src, srcOff, srcLen)
+        cls._check_ranges(dst, dstOff, targetSize)
+        sp, sk = _ro_ptr(src)
+        dp, dk = _rw_ptr(dst)
+        out = (C.c_int32 * max(n, 1))()
+        consumed = (C.c_int32 * max(n, 1))()
+        _chk(lib().lz4hip_compress_dest_size_batch(sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), dp, _arr(C.c_uint64, dstOff),
+                                                   _arr(C.c_int32, targetSize), out, consumed, n))
+        if hasattr(srcOff, "dtype"):
+            import numpy as np
+            return (np.frombuffer(out, dtype=np.int32, count=n).copy(), np.frombuffer(consumed, dtype=np.int32, count=n).copy())
+        return list(out[:n]), list(consumed[:n])
+
+    @classmethod
     def compressHC(cls, src, srcOff, srcLen, dst, dstOff, dstCap, level=9):
         n = len(srcOff)
         if not (len(srcLen) == len(dstOff) == len(dstCap) == n):
@@ -680,6 +717,15 @@ class DeviceBatch:
         _chk(lib().lz4hip_compress_fast_accel_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
                                                         dst_off.data_ptr(), dst_cap.data_ptr(), out.data_ptr(), src_off.numel(),
                                                         int(acceleration), dev, st))
+
+    @classmethod
+    def compress_dest_size(cls, src, src_off, src_len, dst, dst_off, target_size, out, consumed):
+        """LZ4_compress_destSize per block (lz4hip_compress_dest_size_batch_dev): out = bytes written, consumed = input consumed;
+        block i's slot is dst[dst_off[i] : + target_size[i]]"""
+        dev, st = cls._stream_dev(src)
+        _chk(lib().lz4hip_compress_dest_size_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
+                                                       dst_off.data_ptr(), target_size.data_ptr(), out.data_ptr(), consumed.data_ptr(),
+                                                       src_off.numel(), dev, st))
 
     @classmethod
     def compress_hc(cls, src, src_off, src_len, dst, dst_off, dst_cap, out, level=9):

@@ -68,7 +68,8 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 };
 
 // OP_COMPRESS_ACCEL: LZ4_compress_fast with acceleration 2 .. 65537, the value travels as `level` (acceleration 1 is OP_COMPRESS_FAST)
-enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL };
+// OP_COMPRESS_DEST: LZ4_compress_destSize, dst_cap = the target size; a second per-block output array carries the consumed sizes
+enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST };
 // tuning knobs (lz4hip_set_option): atomics, so that a caller changing one while other threads launch is a race on the VALUE chosen,
 // never undefined behaviour; every launch reads each knob once
 std::atomic<int> g_decode_lanes{0};   // "decode_lanes"; 0 = kernel default
@@ -164,6 +165,16 @@ int launch_accel(const lz4hip::BatchArgs& a, int accel, hipStream_t st) {
 // liblz4's acceleration handling (LZ4_compress_fast_extState): < 1 -> 1, > LZ4_ACCELERATION_MAX -> 65537
 int accel_clamp(int a) { return a < 1 ? 1 : a > 65537 ? 65537 : a; }
 
+// LZ4_compress_destSize (compress_fast_dest_cu_kernel; one queue word of scratch)
+int launch_dest(const lz4hip::BatchArgs& a, int32_t* consumed, hipStream_t st) {
+  uint32_t* q = nullptr;
+  hipError_t e = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
+  if (e != hipSuccess) return (int)e;
+  const int le = lz4hip::launch_compress_dest_size(a, consumed, q, cu_count(), st);
+  (void)hipFreeAsync(q, st);
+  return le;
+}
+
 // the decode knobs are process-wide and set one at a time: a combination no kernel exists for is said here, by name (round-5 advisor: it
 // used to surface as a bare "kernel launch: invalid value")
 const char* decode_knobs_error(int lanes, int pipe, int ring) {
@@ -224,6 +235,7 @@ int launch_op(Op op, const lz4hip::BatchArgs& a, hipStream_t st, int level = 0) 
     case OP_DECODE_SAFE: e = launch_decode(a, true, st); break;
     case OP_DECODE_FAST: e = launch_decode(a, false, st); break;
     case OP_COMPRESS_HC: return fail(LZ4HIP_E_ARG, "internal: HC goes through dev_hc");
+    case OP_COMPRESS_DEST: return fail(LZ4HIP_E_ARG, "internal: destSize goes through dev_dest_batch");
   }
   if (e == LZ4HIP_E_ARG) return e;        // (decode_knobs_error: the message is set)
   if (e != 0) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
@@ -243,6 +255,23 @@ int dev_batch(Op op, const uint8_t* src, const uint64_t* src_off, const int32_t*
   lz4hip::BatchArgs a{src, src_off, src_len, dst, dst_off, dst_cap, out, n};
   if (op == OP_COMPRESS_HC) return dev_hc(a, level, (hipStream_t)stream);
   return launch_op(op, a, (hipStream_t)stream, level);
+}
+
+// LZ4_compress_destSize on device pointers: dev_batch's checks, plus the consumed-size array
+int dev_dest_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                   const int32_t* target, int32_t* out, int32_t* consumed, uint32_t n, int device, void* stream) {
+  int rc = ensure_init();
+  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (n == 0) return LZ4HIP_OK;
+  if (!src || !src_off || !src_len || !dst || !dst_off || !target || !out || !consumed) return fail(LZ4HIP_E_ARG, "null pointer argument");
+  int ord;
+  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
+  DeviceGuard g(ord);
+  if (!g.ok) return fail(LZ4HIP_E_HIP, "hipSetDevice failed");
+  lz4hip::BatchArgs a{src, src_off, src_len, dst, dst_off, target, out, n};
+  const int e = launch_dest(a, consumed, (hipStream_t)stream);
+  if (e != 0) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
+  return LZ4HIP_OK;
 }
 
 // ---- host-pointer path ---------------------------------------------------------------------------
@@ -388,8 +417,9 @@ void par_blocks(uint32_t i0, uint32_t i1, size_t bytes, F f) {  // f(i) for i in
 // finisher thread per chunk waits for chunk c - 1 and hands its bytes to the caller's slots.  (Rounds 1-2 did pack, the
 // synchronous D2H of the packed bytes and the unpack one after the other on the calling thread: 44 ms per GiB, twice what the
 // link needs -- tools/host_path_probe.py.)
+// OP_COMPRESS_DEST: `consumed` (the second per-block output) travels behind out[] in the metadata and comes back with the sizes
 int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
-               const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, uint32_t b0, uint32_t b1, std::string* err) {
+               const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, int32_t* consumed, uint32_t b0, uint32_t b1, std::string* err) {
   auto bad_to = [](std::string* where, const char* what, hipError_t e) {
     char buf[512];
     snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
@@ -428,6 +458,7 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
     const uint32_t nb = s.i1 - s.i0;
     const int32_t* hout = (const int32_t*)((const uint8_t*)s.h_meta.p + (size_t)nb * 24u);
     memcpy(out + s.i0, hout, (size_t)nb * 4u);
+    if (op == OP_COMPRESS_DEST) memcpy(consumed + s.i0, hout + nb, (size_t)nb * 4u);
     const uint8_t* hd = (const uint8_t*)s.h_dst.p;
     const uint32_t i0 = s.i0;
     if (s.packed) {   // the sizes are here: fetch exactly the useful bytes (already packed on the device), then hand them out
@@ -500,11 +531,12 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
     s.so.resize(nb); s.dof.resize(nb);
     { size_t so = 0, dofs = 0;
       for (uint32_t t = 0; t < nb; t++) { s.so[t] = so; s.dof[t] = dofs; so += (slen_of(i + t) + 15u) & ~(size_t)15u; dofs += (dcap_of(i + t) + 15u) & ~(size_t)15u; } }
-    const size_t meta = (size_t)nb * 28u;   // so[nb] u64 | dof[nb] u64 | src_len[nb] | dst_cap[nb] | out[nb]
+    const size_t nout = op == OP_COMPRESS_DEST ? 2u : 1u;   // out[] (and consumed[])
+    const size_t meta = (size_t)nb * (24u + 4u * nout);   // so[nb] u64 | dof[nb] u64 | src_len[nb] | dst_cap[nb] | out[nb] | (consumed[nb])
     if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (e = s.h_dst.reserve(db + 64)) != hipSuccess || (e = s.h_meta.reserve(meta)) != hipSuccess ||
         (e = s.d_src.reserve(sb + 64)) != hipSuccess || (e = s.d_dst.reserve(db + 64)) != hipSuccess || (e = s.d_meta.reserve(meta)) != hipSuccess ||
         (op == OP_COMPRESS_HC && (e = s.d_ws.reserve(lz4hip::hc_ws_bytes(sb, nb, level))) != hipSuccess) ||
-        ((op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL) && ((e = s.d_pack.reserve(db + 64)) != hipSuccess || (e = s.d_poff.reserve((size_t)nb * 8u)) != hipSuccess))) {
+        ((op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST) && ((e = s.d_pack.reserve(db + 64)) != hipSuccess || (e = s.d_poff.reserve((size_t)nb * 8u)) != hipSuccess))) {
       rc = bad("staging allocation", e);
       break;
     }
@@ -535,13 +567,14 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
       case OP_DECODE_FAST: le = launch_decode(a, false, s.st); break;
       case OP_COMPRESS_HC: le = lz4hip::launch_compress_hc(a, level, s.d_ws.p, sb, s.st); break;
       case OP_COMPRESS_ACCEL: le = launch_accel(a, level, s.st); break;
+      case OP_COMPRESS_DEST: le = launch_dest(a, (int32_t*)(dm + (size_t)nb * 28u), s.st); break;
     }
     if (le == LZ4HIP_E_ARG) { *err = lz4hip_last_error(); rc = le; break; }   // (a decode knob combination without a kernel: launch_decode has said which, on this thread)
     if (le) { rc = bad("kernel launch", (hipError_t)le); break; }
-    s.packed = (op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL);
+    s.packed = (op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST);
     // the sizes travel first; compress ops: the finisher fetches exactly the packed bytes once it has them
     if (!single && ((e = hipEventRecord(s.ev_k, s.st)) != hipSuccess || (e = hipStreamWaitEvent(s.q_out, s.ev_k, 0)) != hipSuccess)) { rc = bad("kernel event", e); break; }
-    if ((e = hipMemcpyAsync(hm + (size_t)nb * 24u, dm + (size_t)nb * 24u, (size_t)nb * 4u, hipMemcpyDeviceToHost, s.q_out)) != hipSuccess) { rc = bad("D2H out", e); break; }
+    if ((e = hipMemcpyAsync(hm + (size_t)nb * 24u, dm + (size_t)nb * 24u, (size_t)nb * 4u * nout, hipMemcpyDeviceToHost, s.q_out)) != hipSuccess) { rc = bad("D2H out", e); break; }
     if (s.packed) {
       if ((e = hipEventRecord(s.done, s.q_out)) != hipSuccess) { rc = bad("hipEventRecord", e); break; }   // sizes on the host
       if ((le = lz4hip::launch_pack(a, (uint64_t*)s.d_poff.p, (uint8_t*)s.d_pack.p, s.st)) != 0) { rc = bad("kernel launch", (hipError_t)le); break; }
@@ -580,11 +613,12 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
 }
 
 int host_batch(Op op, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
-               const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, uint32_t n, int level = 0) {
+               const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, uint32_t n, int level = 0, int32_t* consumed = nullptr) {
   int rc = ensure_init();
   if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
   if (n == 0) return LZ4HIP_OK;
-  if (!src || !src_off || !src_len || !dst || !dst_off || !dst_cap || !out) return fail(LZ4HIP_E_ARG, "null pointer argument");
+  if (!src || !src_off || !src_len || !dst || !dst_off || !dst_cap || !out || (op == OP_COMPRESS_DEST && !consumed))
+    return fail(LZ4HIP_E_ARG, "null pointer argument");
   std::vector<int> devs;
   { std::lock_guard<std::mutex> lk(g_mu); devs = g_devs; }
   int prev = -1;
@@ -594,12 +628,12 @@ int host_batch(Op op, const uint8_t* src, const uint64_t* src_off, const int32_t
   std::vector<int> rcs(D, 0);
   std::vector<std::string> errs(D);
   if (D == 1) {
-    rcs[0] = host_shard(op, level, devs[0], src, src_off, src_len, dst, dst_off, dst_cap, out, 0, n, &errs[0]);
+    rcs[0] = host_shard(op, level, devs[0], src, src_off, src_len, dst, dst_off, dst_cap, out, consumed, 0, n, &errs[0]);
   } else {
     std::vector<std::thread> th;
     for (uint32_t d = 0; d < D; d++) {
       const uint32_t b0 = (uint32_t)((uint64_t)n * d / D), b1 = (uint32_t)((uint64_t)n * (d + 1) / D);
-      th.emplace_back([&, d, b0, b1] { rcs[d] = host_shard(op, level, devs[d], src, src_off, src_len, dst, dst_off, dst_cap, out, b0, b1, &errs[d]); });
+      th.emplace_back([&, d, b0, b1] { rcs[d] = host_shard(op, level, devs[d], src, src_off, src_len, dst, dst_off, dst_cap, out, consumed, b0, b1, &errs[d]); });
     }
     for (auto& t : th) t.join();
   }
@@ -720,6 +754,7 @@ int host_xxh(bool is64, const uint8_t* buf, const uint64_t* off, const int32_t* 
 struct Req {
   const uint8_t* src; int32_t len; uint8_t* dst; int32_t cap;
   int32_t out = 0; int rc = 0; bool done = false; std::string err;
+  int32_t consumed = 0;   // (OP_COMPRESS_DEST)
 };
 struct Combiner {
   std::mutex mu;
@@ -736,6 +771,7 @@ Combiner& accel_combiner(int accel) {
   std::lock_guard<std::mutex> lk(g_accel_comb_mu);
   return g_accel_comb[accel];   // (std::map: references stay valid while other entries are added)
 }
+Combiner g_dest_comb;   // LZ4_compress_destSize: coalesced only with other destSize calls
 
 // one host batch for all of `batch`; returns its rc (every request gets its out[]); may throw (allocation of the index vectors,
 // thread creation inside host_batch)
@@ -750,10 +786,13 @@ int run_batch_once(Op op, int level, const std::vector<Req*>& batch) {
     if (!dbase || r->dst < dbase) dbase = r->dst;
   }
   std::vector<uint64_t> so(n), dof(n);
-  std::vector<int32_t> sl(n), dc(n), out(n, 0);
+  std::vector<int32_t> sl(n), dc(n), out(n, 0), cons(op == OP_COMPRESS_DEST ? n : 0u, 0);
   for (uint32_t i = 0; i < n; i++) { so[i] = (uint64_t)(batch[i]->src - sbase); dof[i] = (uint64_t)(batch[i]->dst - dbase); sl[i] = batch[i]->len; dc[i] = batch[i]->cap; }
-  const int rc = host_batch(op, sbase, so.data(), sl.data(), dbase, dof.data(), dc.data(), out.data(), n, level);
-  for (uint32_t i = 0; i < n; i++) { batch[i]->rc = rc; batch[i]->out = out[i]; if (rc) batch[i]->err = g_err; }
+  const int rc = host_batch(op, sbase, so.data(), sl.data(), dbase, dof.data(), dc.data(), out.data(), n, level, cons.data());
+  for (uint32_t i = 0; i < n; i++) {
+    batch[i]->rc = rc; batch[i]->out = out[i]; if (rc) batch[i]->err = g_err;
+    if (op == OP_COMPRESS_DEST) batch[i]->consumed = cons[i];
+  }
   return rc;
 }
 
@@ -773,10 +812,11 @@ void run_combined(Op op, int level, std::vector<Req*>& batch) noexcept {
   }
 }
 
-int single(Op op, const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level = 0) {
+// consumed: OP_COMPRESS_DEST's input consumed (written only on success)
+int single(Op op, const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level = 0, int32_t* consumed = nullptr) {
   Req r{src, src_len, dst, dst_cap};
   Combiner* cp;
-  try { cp = op == OP_COMPRESS_ACCEL ? &accel_combiner(level) : &g_comb[(int)op][level < 0 || level > 12 ? 0 : level]; }
+  try { cp = op == OP_COMPRESS_ACCEL ? &accel_combiner(level) : op == OP_COMPRESS_DEST ? &g_dest_comb : &g_comb[(int)op][level < 0 || level > 12 ? 0 : level]; }
   catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
   Combiner& c = *cp;
   {
@@ -800,6 +840,7 @@ int single(Op op, const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, in
     }
   }
   if (r.rc) { g_err = r.err; return LZ4HIP_LIB_ERROR(r.rc); }
+  if (consumed) *consumed = r.consumed;
   return r.out;
 }
 
@@ -1258,6 +1299,10 @@ int lz4hip_compress_fast_accel_batch(const uint8_t* src, const uint64_t* src_off
   if (a == 1) return lz4hip_compress_fast_batch(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
   return host_batch(OP_COMPRESS_ACCEL, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, a);
 }
+int lz4hip_compress_dest_size_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                    const uint64_t* dst_off, const int32_t* target_size, int32_t* out_len, int32_t* src_consumed, uint32_t n) {
+  return host_batch(OP_COMPRESS_DEST, src, src_off, src_len, dst, dst_off, target_size, out_len, n, 0, src_consumed);
+}
 int lz4hip_decompress_safe_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                  const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n) {
   return host_batch(OP_DECODE_SAFE, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
@@ -1290,6 +1335,11 @@ int lz4hip_compress_fast_accel_batch_dev(const uint8_t* src, const uint64_t* src
   const int a = accel_clamp(acceleration);
   if (a == 1) return lz4hip_compress_fast_batch_dev(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, device, stream);
   return dev_batch(OP_COMPRESS_ACCEL, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, device, stream, a);
+}
+int lz4hip_compress_dest_size_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                        const uint64_t* dst_off, const int32_t* target_size, int32_t* out_len, int32_t* src_consumed,
+                                        uint32_t n, int device, void* stream) {
+  return dev_dest_batch(src, src_off, src_len, dst, dst_off, target_size, out_len, src_consumed, n, device, stream);
 }
 int lz4hip_decompress_safe_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                      const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int device, void* stream) {
@@ -1375,6 +1425,13 @@ int lz4hip_compress_fast_accel(const uint8_t* src, int src_len, uint8_t* dst, in
   const int a = accel_clamp(acceleration);
   if (a == 1) return lz4hip_compress_fast(src, src_len, dst, dst_cap);
   return single(OP_COMPRESS_ACCEL, src, src_len, dst, dst_cap, a);
+}
+int lz4hip_compress_dest_size(const uint8_t* src, int* src_size, uint8_t* dst, int target_size) {
+  if (!src_size) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, "null src_size"));
+  int32_t c = 0;
+  const int r = single(OP_COMPRESS_DEST, src, *src_size, dst, target_size, 0, &c);
+  if (!LZ4HIP_IS_LIB_ERROR(r)) *src_size = c;
+  return r;
 }
 int lz4hip_compress_hc(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level) {
   int lv;

@@ -30,6 +30,10 @@ int launch_compress_fast_ms(const BatchArgs& a, uint32_t* q, const uint32_t* rou
 // LZ4_compress_fast(..., accel) for accel 2 .. 65537 (clamped by the caller; acceleration 1 is launch_compress_fast_v2w's): the
 // one-sequence-per-step core of lz4_fast_core.h with its ACC switch, five wavefronts per CU drawing blocks from q = one device uint32_t
 int launch_compress_fast_accel(const BatchArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream);
+// LZ4_compress_destSize: a.dst_cap[i] is the target size; out[i] = bytes written, consumed[i] = input consumed (src_len[i] where
+// liblz4 returns 0 without touching it).  The one-sequence core with DirectOut's FILL switch, five wavefronts per CU drawing blocks
+// from q = one device uint32_t
+int launch_compress_dest_size(const BatchArgs& a, int32_t* consumed, uint32_t* q, uint32_t n_cus, void* stream);
 #ifdef LZ4HIP_DEV_TOOLS
 int launch_compress_fast_prof(const BatchArgs& a, uint64_t* prof, int core, void* stream);  // developer build only (tools/build_variant.sh dev -DLZ4HIP_DEV_TOOLS)
 #endif

@@ -11,6 +11,9 @@
 //   compress_fast_accel_cu_kernel
 //                        : LZ4_compress_fast with acceleration 2 .. 65537: the one-sequence-per-step core of lz4_fast_core.h with
 //                          its ACC switch, 5 wavefronts per CU drawing blocks from a queue (acceleration 1 is the kernels above).
+//   compress_fast_dest_cu_kernel
+//                        : LZ4_compress_destSize: the same core and shape with DirectOut's FILL switch; a block ends once its
+//                          target is full, so the work follows the input consumed.
 //   decode_kernel<GL, SAFE, PIPE, STAGE>
 //                        : GL lanes per block, 64/GL blocks per wavefront, algorithm in lz4_decode_core.h; PIPE = software-
 //                          pipelined loop for small batches, STAGE = output through LDS as whole lines for large ones.
@@ -399,6 +402,51 @@ int launch_compress_fast_accel(const BatchArgs& a, uint32_t accel, uint32_t* q, 
   if (e != hipSuccess) return (int)e;
   const uint32_t wgs = (a.n + WAVES_PER_CU - 1u) / WAVES_PER_CU;
   hipLaunchKernelGGL(compress_fast_accel_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a, q, accel);
+  return (int)hipGetLastError();
+}
+
+// LZ4_compress_destSize: the one-sequence-per-step core (acceleration 1) with DirectOut's FILL switch on (lz4_fast_core.h), byU16 below
+// 65547 bytes, byU32 above; dst_cap[b] is the target.  Same shape as the accelerated kernel.  A block whose target is full stops at the
+// next step, so the steps spent on it follow the input it consumes, not src_len.
+__device__ __forceinline__ void compress_fast_dest_block(const BatchArgs& a, int32_t* consumed, uint32_t b, uint64_t* table) {
+  const int32_t n = uniform_i32(a.src_len[b]);
+  const int32_t t = uniform_i32(a.dst_cap[b]);
+  uint32_t r = 0;
+  int32_t c = n;   // (liblz4 leaves *srcSizePtr untouched where it returns 0 up front)
+  if (t > 0 && n >= 0 && (uint32_t)n <= 0x7E000000u) {
+    const uint8_t* s = uniform_ptr(a.src + a.src_off[b]);
+    uint8_t* d = uniform_ptr(a.dst + a.dst_off[b]);
+    WaveDev w(table);
+    DirectOut<WaveDev, true> out(w, s, (uint32_t)n, d, (uint32_t)t);
+    if (n < 65547) {
+      FastCore<WaveDev, true, DirectOut<WaveDev, true>> core(w, out, s, (uint32_t)n);
+      r = core.run();
+    } else {
+      FastCore<WaveDev, false, DirectOut<WaveDev, true>> core(w, out, s, (uint32_t)n);
+      r = core.run();
+    }
+    c = (int32_t)out.consumed;
+  }
+  if (__lane_id() == 0) { a.out[b] = (int32_t)r; consumed[b] = c; }
+}
+__global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_dest_cu_kernel(BatchArgs a, int32_t* consumed, uint32_t* q) {
+  __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
+  uint64_t* table = tables[threadIdx.x >> 6];
+  for (;;) {
+    uint32_t b = 0;
+    if (__lane_id() == 0) b = atomicAdd(q, 1u);
+    b = __builtin_amdgcn_readfirstlane(b);
+    if (b >= a.n) return;
+    compress_fast_dest_block(a, consumed, b, table);
+    WaveDev::sync();  // the table is reused
+  }
+}
+int launch_compress_dest_size(const BatchArgs& a, int32_t* consumed, uint32_t* q, uint32_t n_cus, void* stream) {
+  if (a.n == 0) return 0;
+  hipError_t e = hipMemsetAsync(q, 0, sizeof(uint32_t), (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  const uint32_t wgs = (a.n + WAVES_PER_CU - 1u) / WAVES_PER_CU;
+  hipLaunchKernelGGL(compress_fast_dest_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a, consumed, q);
   return (int)hipGetLastError();
 }
 

@@ -75,8 +75,13 @@ struct FastStats {  // optional counters (host simulator / profiling kernel); th
 //   ParkOut    (lz4_fast_v2_core.h) parks {match start, length, offset} one lane per sequence and writes 64 at a time.
 // (A third policy, descriptors pushed to a ring drained by a second wavefront, measured 8 % slower than DirectOut in round 1
 // and was removed.)
+// DirectOut<W, FILL = true> is liblz4's fillOutput (LZ4_compress_destSize): `cap` is the target size t.  The parse is the default
+// one; only emission and termination differ.  A sequence that fails liblz4's literal check stops the block with the last literals
+// starting at its literal start; one that fails the match check is written with a shortened match (6 bytes of room are left, a
+// further sequence needs 11) and stops the block after it; the last literals are then truncated to fit.  `consumed` is the input
+// that the output covers.  t >= compressBound(n) is `limited` false: the default bytes, all of the input.
 // ---------------------------------------------------------------------------------------------------
-template <class W>
+template <class W, bool FILL = false>
 struct DirectOut {
   using VU = typename W::VU;
   using VU64 = typename W::VU64;
@@ -90,6 +95,8 @@ struct DirectOut {
   uint32_t cap;
   bool limited;
   uint32_t op = 0;
+  uint32_t consumed = 0;     // (FILL) input bytes the output covers, once the block is done
+  uint32_t stop_anchor = 0;  // (FILL) where the last literals start after a stop
 
   LZ4HIP_DEV DirectOut(W& w_, const uint8_t* s, uint32_t n_, uint8_t* d, uint32_t cap_) : w(w_), src(s), n(n_), dst(d), cap(cap_) {
     limited = cap < n + n / 255u + 16u;
@@ -109,10 +116,15 @@ struct DirectOut {
 
   LZ4HIP_DEV void put_ext_at(uint32_t o, uint32_t len, uint32_t cnt) { put_ext(o, len, cnt); }
 
-  // last literals: token + run + raw bytes; returns total size or 0
+  // last literals: token + run + raw bytes; returns total size or 0 (FILL: the run is truncated to fit instead)
   LZ4HIP_COLD uint32_t emit_last(uint32_t anchor) {
-    const uint32_t last = n - anchor;
-    if (limited && (uint64_t)op + last + 1u + (last + 255u - 15u) / 255u > cap) return 0;
+    uint32_t last = n - anchor;
+    if (limited && (uint64_t)op + last + 1u + (last + 255u - 15u) / 255u > cap) {
+      if constexpr (!FILL) return 0;
+      last = cap - op - 1u;             // (op < cap: a stop leaves at least 6 bytes, the start at least 1)
+      last -= (last + 256u - 15u) / 256u;
+    }
+    if constexpr (FILL) consumed = anchor + last;
     const uint32_t nlx = ext_count(last);
     w.st8(dst, VU(op), VU((last < 15u ? last : 15u) << 4), w.lane() == 0u);
     if (nlx) put_ext(op + 1u, last, nlx);
@@ -135,7 +147,8 @@ struct DirectOut {
     pend.have = false;
     const uint32_t lit = pend.lit, mc = pend.mc, offset = pend.offset;
     const uint32_t token = ((lit < 15u ? lit : 15u) << 4) | (mc < 15u ? mc : 15u);
-    if (LZ4HIP_LIKELY(pend.regs && !limited)) {
+    // (FILL: no check can fire while op + 72 <= cap -- regs means at most 63 bytes and at most one match-length byte)
+    if (LZ4HIP_LIKELY(pend.regs && (!limited || (FILL && op + 72u <= cap)))) {
       // The common case, branch-free, ONE store instruction, no cross-lane traffic (regs implies at most one length byte
       // each and total <= 63: no division, no loop): lane 0 writes the token; lane l >= 1 writes output byte l + nlx, so
       // the literal it needs (literal l-1) is byte 0 of its own window word; when a literal-length byte exists (nlx == 1)
@@ -161,8 +174,25 @@ struct DirectOut {
   // everything else: a limited output buffer (liblz4's two capacity checks), literals that are not in the window registers,
   // long length runs
   LZ4HIP_COLD bool emit_checked(uint32_t lit, uint32_t mc, uint32_t offset, uint32_t token) {
-    const uint32_t nlx = ext_count(lit), nmx = ext_count(mc);
-    if (limited) {
+    const uint32_t nlx = ext_count(lit);
+    if constexpr (FILL) {
+      if (limited) {
+        // liblz4's fillOutput checks: the literal check (it also covers the _next_match check of a sequence without literals)
+        if ((uint64_t)op + 1u + nlx + lit + 11u > cap) { stop_anchor = pend.anchor; return false; }
+        const uint32_t p = op + 1u + nlx + lit + 2u;   // output position after the offset (p + 9 <= cap here)
+        if ((uint64_t)p + 6u + (mc + 240u) / 255u > cap) {
+          // the match description does not fit: shortened to what leaves exactly 6 bytes (never longer than mc), then stop
+          const uint32_t mcs = 14u + (cap - p - 6u) * 255u;
+          const uint32_t nms = ext_count(mcs);
+          emit_generic(lit, mcs, offset, nlx, nms, (token & 0xF0u) | (mcs < 15u ? mcs : 15u), 1u + nlx + lit + 2u + nms);
+          op += 1u + nlx + lit + 2u + nms;
+          stop_anchor = pend.anchor + lit + 4u + mcs;
+          return false;
+        }
+      }
+    }
+    const uint32_t nmx = ext_count(mc);
+    if (!FILL && limited) {
       if (pend.check_lits && (uint64_t)op + 1u + lit + (2u + 1u + 5u) + lit / 255u > cap) return false;
       if ((uint64_t)op + 1u + nlx + lit + 2u + (1u + 5u) + (mc + 240u) / 255u > cap) return false;
     }
@@ -214,10 +244,19 @@ struct DirectOut {
     pend_b0 = b0;
   }
   LZ4HIP_DEV uint32_t last(uint32_t anchor) {
-    if (!emit_pending()) return 0;
+    if (!emit_pending()) return stop();
     return emit_last(anchor);
   }
+  // what a stop (overlap_point() or the pending sequence of last() returned false) makes of the block: 0 = it does not fit;
+  // FILL: the last literals from the stop anchor, truncated to fit -- not from the finder's anchor, which is one step further on
+  LZ4HIP_DEV uint32_t stop() {
+    if constexpr (FILL) return emit_last(stop_anchor);
+    else return 0u;
+  }
 };
+// the result of FastCore at a stop of its output policy: 0 (did not fit) except for DirectOut's fill mode
+template <class O> LZ4HIP_DEV uint32_t out_stop(O&) { return 0u; }
+template <class W, bool FILL> LZ4HIP_DEV uint32_t out_stop(DirectOut<W, FILL>& o) { return o.stop(); }
 
 // flag / mask of a packed literal length (lz4_fast_ms_core.h): bit 29 = liblz4's _next_match path (no literal-capacity check)
 constexpr uint32_t SEQ_NOCHECK = 1u << 29, SEQ_LIT_MASK = (1u << 29) - 1u;
@@ -477,7 +516,7 @@ struct FastCore {
       LZ4HIP_PHASE(2, hpos);             // t[2]: commit issue + candidate-fetch issue
 
       // ---- [4] write out the previous sequence while those loads are in flight ----
-      if (!out.overlap_point()) return 0;
+      if (!out.overlap_point()) return out_stop(out);
       LZ4HIP_PHASE(3, hpos);             // t[3]: emission of the previous sequence
 
       // ---- [5] intra-step bucket collisions (rare): undo, resolve exactly, commit again ----
@@ -606,7 +645,7 @@ struct FastCore {
         if (--probe_cd == 0u) {
           if (probe_anchor == 0u) { probe_anchor = anchor; probe_cd = 64u; }
           else {  // sequence 96 done: the next step is a post step at ip_new
-            if (!out.overlap_point()) return 0u;
+            if (!out.overlap_point()) return out_stop(out);
             probe_done = true;
             bailed = anchor - probe_anchor < dense64;
             p_S = S; p_ip = ip;

@@ -77,6 +77,18 @@ class LZ4HIPCompressor final : public LZ4Compressor {
     if (result <= 0) throw LZ4Exception("maxDestLen is too small");
     return result;
   }
+  // liblz4's LZ4_compress_destSize: compresses as much of src[srcOff, srcOff + srcLen) as fits in exactly targetDestSize bytes at
+  // dest + destOff; returns the bytes written and sets srcLen to the source bytes they cover (lz4hip_compress_dest_size).  liblz4
+  // has no accelerated destSize: an accelerated compressor throws std::logic_error.
+  int compressDestSize(const bytes& src, int srcOff, int& srcLen, bytes& dest, int destOff, int targetDestSize) const {
+    if (accel_ > 1) throw std::logic_error("compressDestSize: liblz4 has no accelerated destSize");
+    util::checkRange(src, srcOff, srcLen);
+    util::checkRange(dest, destOff, targetDestSize);
+    int size = srcLen;
+    const int result = libCheck(lz4hip_compress_dest_size(src.data() + srcOff, &size, dest.data() + destOff, targetDestSize));
+    srcLen = size;
+    return result;
+  }
 };
 
 class LZ4HCHIPCompressor final : public LZ4Compressor {

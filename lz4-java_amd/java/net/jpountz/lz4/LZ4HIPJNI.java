@@ -51,6 +51,10 @@ enum LZ4HIPJNI {
   /* LZ4_compress_fast(..., acceleration): the arguments, NULL / pinning rules and return conventions of LZ4HIP_compress_fast */
   static native int LZ4HIP_compress_fast_accel(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
                                                byte[] destArray, ByteBuffer destBuffer, int destOff, int maxDestLen, int acceleration);
+  /* LZ4_compress_destSize: srcSize[0] = block size in, input consumed out (untouched on a library failure); returns the bytes
+   * written (at most targetDestSize) or a library failure as above.  Same NULL / pinning rules as LZ4HIP_compress_fast */
+  static native int LZ4HIP_compress_dest_size(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int[] srcSize,
+                                              byte[] destArray, ByteBuffer destBuffer, int destOff, int targetDestSize);
   static native int LZ4HIP_compressHC(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
                                       byte[] destArray, ByteBuffer destBuffer, int destOff, int maxDestLen, int compressionLevel);
   static native int LZ4HIP_decompress_fast(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcCap,
@@ -65,6 +69,10 @@ enum LZ4HIPJNI {
    * Returns 0 or a negative lz4hip_status; per-block results land in outLen. */
   static native int LZ4HIP_batch(int op, int level, ByteBuffer src, long[] srcOff, int[] srcLen,
                                  ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, int nBlocks);
+  /* LZ4_compress_destSize per block over DIRECT buffers: block i fills at most dest[destOff[i], + targetSize[i]); outLen = bytes
+   * written, srcConsumed = input consumed.  Returns 0 or a negative lz4hip_status (a null argument: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchDestSize(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetSize,
+                                         int[] outLen, int[] srcConsumed, int nBlocks);
 
   /** Container blocks assembled on the device (LZ4HIPBatch.containerBlocks); returns bytes written or the negative lz4hip_status. */
   static native long LZ4HIP_containerBlocks(int kind, int flags, int level, ByteBuffer src, long srcOff, long len, int blockSize,

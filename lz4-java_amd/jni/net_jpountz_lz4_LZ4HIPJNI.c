@@ -117,6 +117,37 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1fast_1ac
   return run_single(env, 4, acceleration, srcArray, srcBuffer, srcOff, srcLen, destArray, destBuffer, destOff, maxDestLen);
 }
 
+/* LZ4_compress_destSize: srcSize[0] = the block size in, the input consumed out; returns the bytes written (<= targetDestSize) or a
+ * library error (srcSize[0] untouched).  Same staging as LZ4HIP_compress_fast; a NULL or empty srcSize is LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1dest_1size(JNIEnv* env, jclass cls, jbyteArray srcArray, jobject srcBuffer,
+    jint srcOff, jintArray srcSize, jbyteArray destArray, jobject destBuffer, jint destOff, jint targetDestSize) {
+  (void)cls;
+  if (srcSize == NULL || (*env)->GetArrayLength(env, srcSize) < 1) return lz4hip_compress_dest_size(NULL, NULL, NULL, 0);
+  jint* sz = (*env)->GetIntArrayElements(env, srcSize, NULL);
+  if (sz == NULL) { throw_OOM(env); return 0; }
+  const jint srcLen = sz[0];
+  region_t in, out;
+  if (region_in(env, srcArray, srcBuffer, srcOff, srcLen, 1, &in) != 0) {
+    (*env)->ReleaseIntArrayElements(env, srcSize, sz, JNI_ABORT);
+    throw_OOM(env);
+    return 0;
+  }
+  if (region_in(env, destArray, destBuffer, destOff, targetDestSize, 0, &out) != 0) {
+    region_out(env, NULL, 0, 0, &in);
+    (*env)->ReleaseIntArrayElements(env, srcSize, sz, JNI_ABORT);
+    throw_OOM(env);
+    return 0;
+  }
+  int consumed = srcLen;
+  const int result = lz4hip_compress_dest_size(in.p, &consumed, out.p, targetDestSize);
+  region_out(env, NULL, 0, 0, &in);
+  sz[0] = consumed;   /* (untouched on a library error) */
+  (*env)->ReleaseIntArrayElements(env, srcSize, sz, 0);
+  const jint produced = !LZ4HIP_IS_LIB_ERROR(result) && result > 0 ? result : 0;
+  if (region_out(env, destArray, destOff, produced, &out) != 0) { throw_OOM(env); return 0; }
+  return result;
+}
+
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compressHC(JNIEnv* env, jclass cls, jbyteArray srcArray, jobject srcBuffer,
     jint srcOff, jint srcLen, jbyteArray destArray, jobject destBuffer, jint destOff, jint maxDestLen, jint level) {
   (void)cls;
@@ -172,6 +203,36 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batch(JNIEnv* env,
   if (dof) (*env)->ReleaseLongArrayElements(env, destOff, dof, JNI_ABORT);
   if (dc) (*env)->ReleaseIntArrayElements(env, destCap, dc, JNI_ABORT);
   if (ol) (*env)->ReleaseIntArrayElements(env, outLen, ol, 0);
+  return rc;
+}
+
+/* LZ4_compress_destSize over many blocks, direct buffers (lz4hip_compress_dest_size_batch): outLen[i] = bytes written in block i's
+ * slot dest[destOff[i] .. + targetSize[i]), srcConsumed[i] = input consumed.  Returns 0 or a negative lz4hip_status; a NULL array or
+ * buffer is LZ4HIP_E_ARG */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchDestSize(JNIEnv* env, jclass cls, jobject src, jlongArray srcOff,
+    jintArray srcLen, jobject dest, jlongArray destOff, jintArray targetSize, jintArray outLen, jintArray srcConsumed, jint n) {
+  (void)cls;
+  if (src == NULL || dest == NULL || srcOff == NULL || srcLen == NULL || destOff == NULL || targetSize == NULL || outLen == NULL ||
+      srcConsumed == NULL) return LZ4HIP_E_ARG;
+  const uint8_t* s = (const uint8_t*)(*env)->GetDirectBufferAddress(env, src);
+  uint8_t* d = (uint8_t*)(*env)->GetDirectBufferAddress(env, dest);
+  if (s == NULL || d == NULL) return LZ4HIP_E_ARG;
+  jlong* so = (*env)->GetLongArrayElements(env, srcOff, NULL);
+  jint* sl = (*env)->GetIntArrayElements(env, srcLen, NULL);
+  jlong* dof = (*env)->GetLongArrayElements(env, destOff, NULL);
+  jint* ts = (*env)->GetIntArrayElements(env, targetSize, NULL);
+  jint* ol = (*env)->GetIntArrayElements(env, outLen, NULL);
+  jint* sc = (*env)->GetIntArrayElements(env, srcConsumed, NULL);
+  jint rc = LZ4HIP_E_NOMEM;
+  if (so && sl && dof && ts && ol && sc)
+    rc = lz4hip_compress_dest_size_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)ts, (int32_t*)ol,
+                                         (int32_t*)sc, (uint32_t)n);
+  if (so) (*env)->ReleaseLongArrayElements(env, srcOff, so, JNI_ABORT);
+  if (sl) (*env)->ReleaseIntArrayElements(env, srcLen, sl, JNI_ABORT);
+  if (dof) (*env)->ReleaseLongArrayElements(env, destOff, dof, JNI_ABORT);
+  if (ts) (*env)->ReleaseIntArrayElements(env, targetSize, ts, JNI_ABORT);
+  if (ol) (*env)->ReleaseIntArrayElements(env, outLen, ol, 0);
+  if (sc) (*env)->ReleaseIntArrayElements(env, srcConsumed, sc, 0);
   return rc;
 }
 

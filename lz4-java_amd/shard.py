@@ -45,3 +45,14 @@ def compress_sharded(codec, n_blocks, group=None, acceleration=None):
     b0, b1 = block_range(n_blocks, world, rank)
     local = codec(b0, b1) if acceleration is None else codec(b0, b1, acceleration=acceleration)
     return (b0, b1), gather_sizes(local, n_blocks, group)
+
+
+def compress_dest_size_sharded(codec, n_blocks, group=None):
+    """LZ4_compress_destSize over a sharded batch: runs `codec(b0, b1) -> (sizes, consumed)`, two int32
+    tensors for blocks [b0, b1) (on a GPU rank: DeviceBatch.compress_dest_size on the rank's slice), and
+    returns (my_range, all_sizes, all_consumed), both gathered in block order."""
+    world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+    rank = dist.get_rank(group) if world > 1 else 0
+    b0, b1 = block_range(n_blocks, world, rank)
+    sizes, consumed = codec(b0, b1)
+    return (b0, b1), gather_sizes(sizes, n_blocks, group), gather_sizes(consumed, n_blocks, group)

@@ -1,0 +1,188 @@
+/* tests/jni_stub/fake_jni_destsize.c -- TEST INFRASTRUCTURE ONLY.
+ *
+ * The destSize natives of the JNI shim (LZ4HIPJNI.LZ4HIP_compress_dest_size and LZ4HIP_batchDestSize) executed without a JVM, with
+ * the same fake JNIEnv as fake_jni.c (a byte[] / int[] / long[] is a malloc'd buffer with pin accounting, a direct ByteBuffer is a
+ * pointer; the shim's malloc / free are counted through shim_alloc.h).  Built by tests/test_destsize_abi.py / tests/test_gpu_destsize.py.
+ *
+ *   fake_jni_destsize --no-gpu                   anywhere: NULL arrays are argument errors, every compute call fails LOUDLY without
+ *                                                a device (library error code, srcSize untouched, nothing leaked or left pinned)
+ *   fake_jni_destsize <input> <target> <out-dir> on a GPU box: compresses <input> into <target> bytes through every argument shape and
+ *                                                the batch native, writes the stream and the consumed size to <out-dir>/dest.bin /
+ *                                                dest.txt (the test compares them with the reference's LZ4_compress_destSize);
+ *                                                prints "fake_jni_destsize: N checks ok"
+ */
+#include <jni.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "lz4hip.h"
+
+typedef struct {
+  int kind;          /* 1 = byte[], 2 = int[], 3 = long[], 4 = direct ByteBuffer, 5 = heap ByteBuffer (no direct address) */
+  uint8_t* data;
+  size_t bytes;
+  int pins;
+  int refuse_pin;
+} fobj;
+
+static long g_alloc = 0;
+void* t_malloc(size_t n) { g_alloc++; return malloc(n); }
+void t_free(void* p) { if (p) g_alloc--; free(p); }
+
+static const char* g_exc_class = NULL;
+static char g_exc_msg[512];
+static int g_checks = 0;
+
+#define CHECK(c) do { if (!(c)) { fprintf(stderr, "fake_jni_destsize: CHECK failed at line %d: %s (pending exception: %s \"%s\")\n", __LINE__, #c, \
+    g_exc_class ? g_exc_class : "none", g_exc_msg); exit(1); } g_checks++; } while (0)
+
+static jclass f_FindClass(JNIEnv* e, const char* name) { (void)e; return (jclass)strdup(name); }
+static jint f_ThrowNew(JNIEnv* e, jclass c, const char* msg) { (void)e; g_exc_class = (const char*)c; snprintf(g_exc_msg, sizeof g_exc_msg, "%s", msg ? msg : ""); return 0; }
+static jobject f_NewGlobalRef(JNIEnv* e, jobject o) { (void)e; return o; }
+static void* f_GetCritical(JNIEnv* e, jarray a, jboolean* isCopy) {
+  (void)e; fobj* o = (fobj*)a;
+  if (isCopy) *isCopy = 0;
+  if (o->refuse_pin) return NULL;
+  o->pins++;
+  return o->data;
+}
+static void f_ReleaseCritical(JNIEnv* e, jarray a, void* p, jint mode) { (void)e; (void)mode; fobj* o = (fobj*)a; if (p != o->data) { fprintf(stderr, "release of a foreign pointer\n"); exit(1); } o->pins--; }
+static void* f_GetDirect(JNIEnv* e, jobject b) { (void)e; fobj* o = (fobj*)b; return o->kind == 4 ? o->data : NULL; }
+static jstring f_NewStringUTF(JNIEnv* e, const char* s) { (void)e; return (jstring)strdup(s ? s : ""); }
+static jlong* f_GetLongs(JNIEnv* e, jlongArray a, jboolean* c) { (void)e; if (c) *c = 0; ((fobj*)a)->pins++; return (jlong*)((fobj*)a)->data; }
+static jint* f_GetInts(JNIEnv* e, jintArray a, jboolean* c) { (void)e; if (c) *c = 0; ((fobj*)a)->pins++; return (jint*)((fobj*)a)->data; }
+static void f_RelLongs(JNIEnv* e, jlongArray a, jlong* p, jint m) { (void)e; (void)p; (void)m; ((fobj*)a)->pins--; }
+static void f_RelInts(JNIEnv* e, jintArray a, jint* p, jint m) { (void)e; (void)p; (void)m; ((fobj*)a)->pins--; }
+static jint f_ArrayLength(JNIEnv* e, jarray a) { (void)e; const fobj* o = (const fobj*)a; return (jint)(o->bytes / (o->kind == 3 ? 8u : o->kind == 2 ? 4u : 1u)); }
+
+static const struct JNINativeInterface_ g_table = {f_FindClass, f_ThrowNew, f_NewGlobalRef, f_GetCritical, f_ReleaseCritical, f_GetDirect,
+                                                   f_NewStringUTF, f_GetLongs, f_GetInts, f_RelLongs, f_RelInts, f_ArrayLength};
+static JNIEnv g_env = &g_table;
+
+static fobj* mk(int kind, size_t bytes) { fobj* o = calloc(1, sizeof *o); o->kind = kind; o->bytes = bytes; o->data = calloc(bytes ? bytes : 1, 1); return o; }
+static int no_exc(void) { return g_exc_class == NULL; }
+static void clear_exc(void) { g_exc_class = NULL; g_exc_msg[0] = 0; }
+/* every byte of o outside [off, off + n) still holds `fill` */
+static int guarded(const fobj* o, size_t off, size_t n, uint8_t fill) {
+  for (size_t i = 0; i < o->bytes; i++)
+    if ((i < off || i >= off + n) && o->data[i] != fill) return 0;
+  return 1;
+}
+
+JNIEXPORT void JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_init(JNIEnv*, jclass);
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1dest_1size(JNIEnv*, jclass, jbyteArray, jobject, jint, jintArray, jbyteArray, jobject, jint, jint);
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchDestSize(JNIEnv*, jclass, jobject, jlongArray, jintArray, jobject, jlongArray, jintArray, jintArray, jintArray, jint);
+JNIEXPORT jstring JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_lastError(JNIEnv*, jclass);
+
+#define DEST Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1dest_1size
+#define BATCH Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchDestSize
+
+static fobj* int1(jint v) { fobj* o = mk(2, 4); ((jint*)o->data)[0] = v; return o; }
+static jint get1(const fobj* o) { return ((const jint*)o->data)[0]; }
+
+int main(int argc, char** argv) {
+  JNIEnv* env = &g_env;
+  Java_net_jpountz_lz4_LZ4HIPJNI_init(env, NULL);
+  CHECK(no_exc());
+  fobj* src = mk(1, 64); fobj* dst = mk(1, 128); fobj* dsrc = mk(4, 64); fobj* ddst = mk(4, 128);
+  /* NULL / empty srcSize: an argument error, whatever the device */
+  { jint r = DEST(env, NULL, (jbyteArray)src, NULL, 0, NULL, (jbyteArray)dst, NULL, 0, 100);
+    CHECK(r == LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) && no_exc() && g_alloc == 0 && src->pins == 0 && dst->pins == 0);
+    fobj* empty = mk(2, 0);
+    r = DEST(env, NULL, (jbyteArray)src, NULL, 0, (jintArray)empty, (jbyteArray)dst, NULL, 0, 100);
+    CHECK(r == LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) && no_exc() && g_alloc == 0 && empty->pins == 0); }
+  /* NULL arrays / buffers of the batch native: LZ4HIP_E_ARG, nothing pinned */
+  { fobj* so = mk(3, 8); fobj* sl = int1(20); fobj* dof = mk(3, 8); fobj* ts = int1(100); fobj* ol = int1(-7); fobj* sc = int1(-7);
+    fobj* a[6] = {so, sl, dof, ts, ol, sc};
+    for (int k = 0; k < 8; k++) {
+      jint rc = BATCH(env, NULL, k == 6 ? NULL : (jobject)dsrc, k == 0 ? NULL : (jlongArray)so, k == 1 ? NULL : (jintArray)sl, k == 7 ? NULL : (jobject)ddst,
+                      k == 2 ? NULL : (jlongArray)dof, k == 3 ? NULL : (jintArray)ts, k == 4 ? NULL : (jintArray)ol, k == 5 ? NULL : (jintArray)sc, 1);
+      CHECK(rc == LZ4HIP_E_ARG && no_exc() && get1(ol) == -7 && get1(sc) == -7);
+      for (int t = 0; t < 6; t++) CHECK(a[t]->pins == 0);
+    }
+    /* heap ByteBuffers where direct ones are required */
+    fobj* hb = mk(5, 64);
+    CHECK(BATCH(env, NULL, (jobject)hb, (jlongArray)so, (jintArray)sl, (jobject)ddst, (jlongArray)dof, (jintArray)ts, (jintArray)ol, (jintArray)sc, 1) == LZ4HIP_E_ARG);
+    if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+      const jint rc = BATCH(env, NULL, (jobject)dsrc, (jlongArray)so, (jintArray)sl, (jobject)ddst, (jlongArray)dof, (jintArray)ts, (jintArray)ol, (jintArray)sc, 1);
+      CHECK(rc == LZ4HIP_E_NO_DEVICE && no_exc() && get1(sc) == -7);
+      for (int t = 0; t < 6; t++) CHECK(a[t]->pins == 0);
+    } }
+  if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+    fobj* sz = int1(40);
+    jint r = DEST(env, NULL, (jbyteArray)src, NULL, 7, (jintArray)sz, (jbyteArray)dst, NULL, 3, 100);
+    CHECK(LZ4HIP_IS_LIB_ERROR(r) && no_exc() && get1(sz) == 40 && g_alloc == 0 && src->pins == 0 && dst->pins == 0 && sz->pins == 0);
+    r = DEST(env, NULL, NULL, (jobject)dsrc, 0, (jintArray)sz, NULL, (jobject)ddst, 0, 30);
+    CHECK(LZ4HIP_IS_LIB_ERROR(r) && no_exc() && get1(sz) == 40 && g_alloc == 0);
+    const char* msg = (const char*)Java_net_jpountz_lz4_LZ4HIPJNI_lastError(env, NULL);
+    CHECK(msg && strlen(msg) > 0);
+    printf("fake_jni_destsize: %d checks ok (no device: every compute call failed loudly)\n", g_checks);
+    return 0;
+  }
+  if (argc < 4) { fprintf(stderr, "usage: fake_jni_destsize --no-gpu | <input> <target> <out-dir>\n"); return 2; }
+  FILE* f = fopen(argv[1], "rb");
+  CHECK(f != NULL);
+  fseek(f, 0, SEEK_END);
+  const long n = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  CHECK(n > 1000 && n < (1 << 24));
+  const int t = atoi(argv[2]);
+  CHECK(t > 0 && t < n);
+  const size_t SO = 5, DO = 7;
+  fobj* asrc = mk(1, (size_t)n + 16); fobj* dsrc2 = mk(4, (size_t)n + 16);
+  CHECK(fread(asrc->data + SO, 1, (size_t)n, f) == (size_t)n);
+  fclose(f);
+  memcpy(dsrc2->data + SO, asrc->data + SO, (size_t)n);
+  fobj* adst = mk(1, (size_t)t + 32); fobj* ddst2 = mk(4, (size_t)t + 32);
+  /* byte[] -> byte[] */
+  memset(adst->data, 0xEE, adst->bytes);
+  fobj* sz = int1((jint)n);
+  const jint r = DEST(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jintArray)sz, (jbyteArray)adst, NULL, (jint)DO, t);
+  const jint consumed = get1(sz);
+  CHECK(no_exc() && r > 0 && r <= t && consumed > 0 && consumed < n && g_alloc == 0 && asrc->pins == 0 && adst->pins == 0 && sz->pins == 0);
+  CHECK(guarded(adst, DO, (size_t)r, 0xEE));
+  char path[4096];
+  snprintf(path, sizeof path, "%s/dest.bin", argv[3]);
+  FILE* o = fopen(path, "wb");
+  CHECK(o != NULL && fwrite(adst->data + DO, 1, (size_t)r, o) == (size_t)r);
+  fclose(o);
+  snprintf(path, sizeof path, "%s/dest.txt", argv[3]);
+  o = fopen(path, "w");
+  CHECK(o != NULL);
+  fprintf(o, "%d %d\n", (int)r, (int)consumed);
+  fclose(o);
+  /* direct -> direct (NULL arrays), byte[] -> direct, direct -> byte[]: the same bytes, nothing outside the slot */
+  for (int shape = 0; shape < 3; shape++) {
+    fobj* adst2 = mk(1, (size_t)t + 32);
+    memset(ddst2->data, 0xEE, ddst2->bytes); memset(adst2->data, 0xEE, adst2->bytes);
+    ((jint*)sz->data)[0] = (jint)n;
+    const int dir_in = shape != 1, dir_out = shape != 2;
+    const jint r2 = DEST(env, NULL, dir_in ? NULL : (jbyteArray)asrc, dir_in ? (jobject)dsrc2 : NULL, (jint)SO, (jintArray)sz,
+                         dir_out ? NULL : (jbyteArray)adst2, dir_out ? (jobject)ddst2 : NULL, (jint)DO, t);
+    const fobj* d = dir_out ? ddst2 : adst2;
+    CHECK(no_exc() && r2 == r && get1(sz) == consumed && memcmp(d->data + DO, adst->data + DO, (size_t)r) == 0 && guarded(d, DO, (size_t)r, 0xEE) && g_alloc == 0);
+    free(adst2->data); free(adst2);
+  }
+  /* `out` cannot be pinned: `in` and srcSize are released, OutOfMemoryError */
+  { fobj* nopin = mk(1, (size_t)t); nopin->refuse_pin = 1;
+    ((jint*)sz->data)[0] = (jint)n;
+    (void)DEST(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jintArray)sz, (jbyteArray)nopin, NULL, 0, t);
+    CHECK(g_exc_class && strcmp(g_exc_class, "java/lang/OutOfMemoryError") == 0 && g_alloc == 0 && asrc->pins == 0 && nopin->pins == 0 && sz->pins == 0);
+    clear_exc(); }
+  /* the batch native: two copies of the input -> the single call's bytes and consumed size twice, slots untouched past t */
+  { fobj* bsrc = mk(4, 2 * (size_t)n); fobj* bdst = mk(4, 2 * (size_t)t + 64);
+    memset(bdst->data, 0xEE, bdst->bytes);
+    memcpy(bsrc->data, asrc->data + SO, (size_t)n); memcpy(bsrc->data + n, asrc->data + SO, (size_t)n);
+    fobj* so = mk(3, 16); fobj* sl = mk(2, 8); fobj* dof = mk(3, 16); fobj* ts = mk(2, 8); fobj* ol = mk(2, 8); fobj* sc = mk(2, 8);
+    ((jlong*)so->data)[0] = 0; ((jlong*)so->data)[1] = n; ((jint*)sl->data)[0] = ((jint*)sl->data)[1] = (jint)n;
+    ((jlong*)dof->data)[0] = 0; ((jlong*)dof->data)[1] = t + 32; ((jint*)ts->data)[0] = ((jint*)ts->data)[1] = t;
+    const jint rc = BATCH(env, NULL, (jobject)bsrc, (jlongArray)so, (jintArray)sl, (jobject)bdst, (jlongArray)dof, (jintArray)ts, (jintArray)ol, (jintArray)sc, 2);
+    const jint* out = (const jint*)ol->data; const jint* cs = (const jint*)sc->data;
+    CHECK(rc == 0 && out[0] == r && out[1] == r && cs[0] == consumed && cs[1] == consumed && so->pins == 0 && ol->pins == 0 && sc->pins == 0);
+    CHECK(memcmp(bdst->data, adst->data + DO, (size_t)r) == 0 && memcmp(bdst->data + t + 32, adst->data + DO, (size_t)r) == 0);
+    for (size_t i = (size_t)t; i < (size_t)t + 32; i++) CHECK(bdst->data[i] == 0xEE);
+    for (size_t i = 2 * (size_t)t + 32; i < bdst->bytes; i++) CHECK(bdst->data[i] == 0xEE); }
+  printf("fake_jni_destsize: %d checks ok\n", g_checks);
+  return 0;
+}
