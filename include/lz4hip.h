@@ -15,6 +15,8 @@
  *                                reference's liblz4-java.so; no JNI entry of the reference reaches it)
  *   lz4hip_compress_dest_size*   = LZ4_compress_destSize(src, dst, &srcSize, targetDstSize) of liblz4's main API (exported by
  *                                the reference's liblz4-java.so; no JNI entry of the reference reaches it)
+ *   lz4hip_decompress_safe_partial* = LZ4_decompress_safe_partial(src, dst, srcSize, targetOutputSize, dstCapacity) of liblz4's
+ *                                main API (exported by the reference's liblz4-java.so; no JNI entry of the reference reaches it)
  *   lz4hip_xxh32* / xxh64*    <- Java_net_jpountz_xxhash_XXHashJNI_XXH32 / XXH64
  *                                (src/jni/net_jpountz_xxhash_XXHashJNI.c:42-59 / :152-169, calls :54 / :164)
  *
@@ -84,7 +86,9 @@ int lz4hip_version(void);
  *   parked hits a partner wavefront writes out, blocks of short sequences by the window-parallel core), 3 (lean core only) or 1
  *   (window-parallel core only); "compress_switch" = routing threshold of the adaptive scheme in bytes per sequence (default 16);
  * "compress_pack" = 1 (default) / 0: blocks of 65547 bytes .. 4 MiB are compressed with 32-bit table entries on ten match-finder chains
- *   per CU instead of five (0: every block on the five-chain kernel).                                                           */
+ *   per CU instead of five (0: every block on the five-chain kernel).
+ * The decode_* knobs and the device-side route do not apply to the partial decoder (lz4hip_decompress_safe_partial*): it always runs the
+ * 4-lane staged loop from 40960 blocks on and the 8-lane deep loop below.                                                        */
 int lz4hip_set_option(const char* name, int value);
 /* diagnostic: what the device-side route of a device's last routed decode launch decided (device = index as in the _dev calls) -- out6
  * (8 words) = { route (0 lane-group default of the batch size, 1 ring loop, 2 wave loop, 3 deep loop instead of the staged one), hops
@@ -133,6 +137,24 @@ int lz4hip_compress_fast_accel_batch(const uint8_t* src, const uint64_t* src_off
 int lz4hip_compress_dest_size_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                     uint8_t* dst, const uint64_t* dst_off, const int32_t* target_size,
                                     int32_t* out_len, int32_t* src_consumed, uint32_t n_blocks);
+/* DECODE A PREFIX: the return value and bytes of LZ4_decompress_safe_partial(src, dst, src_len, target_len, dst_cap), liblz4 1.9.3:
+ * the first min(target_len[i], dst_cap[i]) bytes of block i, or fewer where the stream ends first -- a cut stream (a prefix of the
+ * compressed bytes) decodes to what its bytes hold.
+ *   - out_len[i] is liblz4's return value: the bytes decoded (<= min(target_len[i], dst_cap[i])), or -(input position) - 1;
+ *     target 0 gives 0 whatever the source holds, an empty source with a target > 0 gives -1;
+ *   - block i's slot is dst[dst_off[i] .. + dst_cap[i]): nothing is written at or past dst_off[i] + min(target_len[i], dst_cap[i]);
+ *   - a negative src_len[i], target_len[i] or dst_cap[i] gives -1 (the engine's rule: liblz4's behaviour there is undefined);
+ *   - a match of offset 0 (invalid: no compressor emits one) that the cut falls in is zero-filled, as offset-0 matches are
+ *     everywhere in this engine; liblz4 leaves those bytes as its buffer held them;
+ *   - two kernels: >= 40960 blocks decode_partial_kernel (4 lanes per block, output staged in LDS), fewer decode_partial_deep_kernel
+ *     (8 lanes, the deep loop) -- the safe decoder's unrouted lane-group loops with the core's PARTIAL switch; a block stops at its
+ *     target, so its time follows the bytes decoded;
+ *   - the host batch shards over the initialised devices and returns only the decoded bytes of every slot; library failures as
+ *     the status of the call;
+ *   - single calls (lz4hip_decompress_safe_partial) are coalesced with concurrent partial calls only, through a combiner of their own. */
+int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                         uint8_t* dst, const uint64_t* dst_off, const int32_t* target_len,
+                                         const int32_t* dst_cap, int32_t* out_len, uint32_t n_blocks);
 int lz4hip_compress_hc_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                              uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                              int32_t* out_len, uint32_t n_blocks, int level);
@@ -175,6 +197,10 @@ int lz4hip_compress_fast_accel_batch_dev(const uint8_t* src, const uint64_t* src
 int lz4hip_compress_dest_size_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                         uint8_t* dst, const uint64_t* dst_off, const int32_t* target_size,
                                         int32_t* out_len, int32_t* src_consumed, uint32_t n_blocks, int device, void* stream);
+/* decode a prefix (see lz4hip_decompress_safe_partial_batch), device pointers, asynchronous */
+int lz4hip_decompress_safe_partial_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                             uint8_t* dst, const uint64_t* dst_off, const int32_t* target_len,
+                                             const int32_t* dst_cap, int32_t* out_len, uint32_t n_blocks, int device, void* stream);
 /* HC: levels follow liblz4 (< 1 -> 9, > 12 -> 12): 1..9 = hash-chain strategy with lazy evaluation, 10..12 = optimal
  * parser (lz4-java levels 10..17).  Levels 10..12 are FUNCTIONAL ONLY: byte-identical output, but the optimal parser's table
  * walk is wave-uniform scalar work (about 1.0 / 0.7 GB/s per GPU at levels 10 / 12 -- no faster than the reference on the host's
@@ -219,6 +245,7 @@ int lz4hip_compress_dest_size(const uint8_t* src, int* src_size, uint8_t* dst, i
 int lz4hip_compress_hc(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level);
 int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap);
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len);
+int lz4hip_decompress_safe_partial(const uint8_t* src, int src_len, uint8_t* dst, int target_size, int dst_cap);  /* LZ4_decompress_safe_partial */
 int lz4hip_xxh32(const uint8_t* buf, int len, uint32_t seed, uint32_t* out);
 int lz4hip_xxh64(const uint8_t* buf, int len, uint64_t seed, uint64_t* out);
 

@@ -51,11 +51,13 @@ C_ABI = {
     "lz4hip_compress_hc_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_int]),
     "lz4hip_decompress_safe_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_decompress_fast_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
+    "lz4hip_decompress_safe_partial_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_fast_accel_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_dest_size_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
+    "lz4hip_decompress_safe_partial_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_hc_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_int]),
     "lz4hip_compress_hc_batch_dev_ws": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
@@ -69,6 +71,7 @@ C_ABI = {
     "lz4hip_compress_hc": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_decompress_safe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "lz4hip_decompress_safe_partial": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_xxh32": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, _u32p]),
     "lz4hip_xxh64": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _u64p]),
     "lz4hip_xxh32_stream_create": (C.c_int, [C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -290,6 +293,21 @@ class LZ4SafeDecompressor:
         _check_range(dest, destOff, maxDestLen)
         sp, sk = _ro_ptr(src)
         result = _single(lib().lz4hip_decompress_safe(sp + srcOff, srcLen, dp + destOff, maxDestLen))
+        if result < 0:
+            raise LZ4Exception("Error decoding offset %d of input buffer" % (srcOff - result))
+        return result
+
+    def decompressPartial(self, src, srcOff, srcLen, dest, destOff, targetLen, maxDestLen=None):
+        """liblz4's LZ4_decompress_safe_partial: decodes the first min(targetLen, maxDestLen) bytes of the block in
+        src[srcOff:srcOff+srcLen] (fewer where the stream ends first: a cut stream decodes to what its bytes hold) into dest[destOff:]
+        and returns the count; nothing is written past destOff + min(targetLen, maxDestLen) (lz4hip_decompress_safe_partial)"""
+        destOff = 0 if destOff is None else destOff
+        maxDestLen = len(dest) - destOff if maxDestLen is None else maxDestLen
+        dp, dk = _rw_ptr(dest)
+        _check_range(src, srcOff, srcLen)
+        _check_range(dest, destOff, maxDestLen)
+        sp, sk = _ro_ptr(src)
+        result = _single(lib().lz4hip_decompress_safe_partial(sp + srcOff, srcLen, dp + destOff, targetLen, maxDestLen))
         if result < 0:
             raise LZ4Exception("Error decoding offset %d of input buffer" % (srcOff - result))
         return result
@@ -666,6 +684,26 @@ class LZ4HIPBatch:
         return cls._call("lz4hip_decompress_fast_batch", src, srcOff, srcCap, dst, dstOff, dstLen)
 
     @classmethod
+    def decompressSafePartial(cls, src, srcOff, srcLen, dst, dstOff, targetLen, dstCap):
+        """LZ4_decompress_safe_partial per block: the first min(targetLen[i], dstCap[i]) bytes of block i into the slot
+        dst[dstOff[i]:+dstCap[i]] -> liblz4's return values (lz4hip_decompress_safe_partial_batch; lists, or an int32 array for numpy
+        inputs); nothing is written past dstOff[i] + min(targetLen[i], dstCap[i])"""
+        n = len(srcOff)
+        if not (len(srcLen) == len(dstOff) == len(targetLen) == len(dstCap) == n):
+            raise ValueError("per-block arrays differ in length")
+        cls._check_ranges(src, srcOff, srcLen)
+        cls._check_ranges(dst, dstOff, dstCap)
+        sp, sk = _ro_ptr(src)
+        dp, dk = _rw_ptr(dst)
+        out = (C.c_int32 * max(n, 1))()
+        _chk(lib().lz4hip_decompress_safe_partial_batch(sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), dp, _arr(C.c_uint64, dstOff),
+                                                        _arr(C.c_int32, targetLen), _arr(C.c_int32, dstCap), out, n))
+        if hasattr(srcOff, "dtype"):
+            import numpy as np
+            return np.frombuffer(out, dtype=np.int32, count=n).copy()
+        return list(out[:n])
+
+    @classmethod
     def xxh32(cls, buf, off, length, seed=0):
         n = len(off)
         if len(length) != n:
@@ -777,6 +815,15 @@ class DeviceBatch:
     @classmethod
     def decompress_fast(cls, src, src_off, src_cap, dst, dst_off, dst_len, out):
         cls._call("lz4hip_decompress_fast_batch_dev", src, src_off, src_cap, dst, dst_off, dst_len, out)
+
+    @classmethod
+    def decompress_safe_partial(cls, src, src_off, src_len, dst, dst_off, target_len, dst_cap, out):
+        """LZ4_decompress_safe_partial per block (lz4hip_decompress_safe_partial_batch_dev): out = liblz4's return values; block i
+        decodes into min(target_len[i], dst_cap[i]) bytes of its slot dst[dst_off[i] : + dst_cap[i]]"""
+        dev, st = cls._stream_dev(src)
+        _chk(lib().lz4hip_decompress_safe_partial_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
+                                                            dst_off.data_ptr(), target_len.data_ptr(), dst_cap.data_ptr(), out.data_ptr(),
+                                                            src_off.numel(), dev, st))
 
     @classmethod
     def xxh32(cls, buf, off, length, seed, out):

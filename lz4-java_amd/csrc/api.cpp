@@ -69,7 +69,9 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 
 // OP_COMPRESS_ACCEL: LZ4_compress_fast with acceleration 2 .. 65537, the value travels as `level` (acceleration 1 is OP_COMPRESS_FAST)
 // OP_COMPRESS_DEST: LZ4_compress_destSize, dst_cap = the target size; a second per-block output array carries the consumed sizes
-enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST };
+// OP_DECODE_PARTIAL: LZ4_decompress_safe_partial; on the host path dst_cap already holds min(target, capacity), or -1 where one of
+// them is negative (partial_room), and the kernels get that array as the target too
+enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL };
 // tuning knobs (lz4hip_set_option): atomics, so that a caller changing one while other threads launch is a race on the VALUE chosen,
 // never undefined behaviour; every launch reads each knob once
 std::atomic<int> g_decode_lanes{0};   // "decode_lanes"; 0 = kernel default
@@ -236,6 +238,7 @@ int launch_op(Op op, const lz4hip::BatchArgs& a, hipStream_t st, int level = 0) 
     case OP_DECODE_FAST: e = launch_decode(a, false, st); break;
     case OP_COMPRESS_HC: return fail(LZ4HIP_E_ARG, "internal: HC goes through dev_hc");
     case OP_COMPRESS_DEST: return fail(LZ4HIP_E_ARG, "internal: destSize goes through dev_dest_batch");
+    case OP_DECODE_PARTIAL: return fail(LZ4HIP_E_ARG, "internal: partial decoding goes through dev_partial_batch");
   }
   if (e == LZ4HIP_E_ARG) return e;        // (decode_knobs_error: the message is set)
   if (e != 0) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
@@ -273,6 +276,25 @@ int dev_dest_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* s
   if (e != 0) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
   return LZ4HIP_OK;
 }
+
+// LZ4_decompress_safe_partial on device pointers: dev_batch's checks, plus the per-block target array
+int dev_partial_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                      const int32_t* target, const int32_t* dst_cap, int32_t* out, uint32_t n, int device, void* stream) {
+  int rc = ensure_init();
+  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (n == 0) return LZ4HIP_OK;
+  if (!src || !src_off || !src_len || !dst || !dst_off || !target || !dst_cap || !out) return fail(LZ4HIP_E_ARG, "null pointer argument");
+  int ord;
+  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
+  DeviceGuard g(ord);
+  if (!g.ok) return fail(LZ4HIP_E_HIP, "hipSetDevice failed");
+  lz4hip::BatchArgs a{src, src_off, src_len, dst, dst_off, dst_cap, out, n};
+  const int e = lz4hip::launch_decompress_partial(a, target, stream);
+  if (e != 0) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
+  return LZ4HIP_OK;
+}
+// the bytes block i of a partial decode may fill: min(target, capacity), or -1 (the kernels' -1) where one of them is negative
+int32_t partial_room(int32_t target, int32_t cap) { return (target < 0 || cap < 0) ? -1 : std::min(target, cap); }
 
 // ---- host-pointer path ---------------------------------------------------------------------------
 // ---- staging of the host-pointer batch API --------------------------------------------------------------------------
@@ -568,6 +590,7 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
       case OP_COMPRESS_HC: le = lz4hip::launch_compress_hc(a, level, s.d_ws.p, sb, s.st); break;
       case OP_COMPRESS_ACCEL: le = launch_accel(a, level, s.st); break;
       case OP_COMPRESS_DEST: le = launch_dest(a, (int32_t*)(dm + (size_t)nb * 28u), s.st); break;
+      case OP_DECODE_PARTIAL: le = lz4hip::launch_decompress_partial(a, a.dst_cap, s.st); break;   // (dst_cap = partial_room: the target)
     }
     if (le == LZ4HIP_E_ARG) { *err = lz4hip_last_error(); rc = le; break; }   // (a decode knob combination without a kernel: launch_decode has said which, on this thread)
     if (le) { rc = bad("kernel launch", (hipError_t)le); break; }
@@ -772,6 +795,7 @@ Combiner& accel_combiner(int accel) {
   return g_accel_comb[accel];   // (std::map: references stay valid while other entries are added)
 }
 Combiner g_dest_comb;   // LZ4_compress_destSize: coalesced only with other destSize calls
+Combiner g_partial_comb;   // LZ4_decompress_safe_partial: coalesced only with other partial decodes (the request's cap = partial_room)
 
 // one host batch for all of `batch`; returns its rc (every request gets its out[]); may throw (allocation of the index vectors,
 // thread creation inside host_batch)
@@ -816,7 +840,7 @@ void run_combined(Op op, int level, std::vector<Req*>& batch) noexcept {
 int single(Op op, const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level = 0, int32_t* consumed = nullptr) {
   Req r{src, src_len, dst, dst_cap};
   Combiner* cp;
-  try { cp = op == OP_COMPRESS_ACCEL ? &accel_combiner(level) : op == OP_COMPRESS_DEST ? &g_dest_comb : &g_comb[(int)op][level < 0 || level > 12 ? 0 : level]; }
+  try { cp = op == OP_COMPRESS_ACCEL ? &accel_combiner(level) : op == OP_COMPRESS_DEST ? &g_dest_comb : op == OP_DECODE_PARTIAL ? &g_partial_comb : &g_comb[(int)op][level < 0 || level > 12 ? 0 : level]; }
   catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
   Combiner& c = *cp;
   {
@@ -1303,6 +1327,18 @@ int lz4hip_compress_dest_size_batch(const uint8_t* src, const uint64_t* src_off,
                                     const uint64_t* dst_off, const int32_t* target_size, int32_t* out_len, int32_t* src_consumed, uint32_t n) {
   return host_batch(OP_COMPRESS_DEST, src, src_off, src_len, dst, dst_off, target_size, out_len, n, 0, src_consumed);
 }
+int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                         const uint64_t* dst_off, const int32_t* target_len, const int32_t* dst_cap, int32_t* out_len,
+                                         uint32_t n) {
+  int rc = ensure_init();
+  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (n == 0) return LZ4HIP_OK;
+  if (!target_len || !dst_cap) return fail(LZ4HIP_E_ARG, "null pointer argument");
+  std::vector<int32_t> room;
+  try { room.resize(n); } catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
+  for (uint32_t i = 0; i < n; i++) room[i] = partial_room(target_len[i], dst_cap[i]);
+  return host_batch(OP_DECODE_PARTIAL, src, src_off, src_len, dst, dst_off, room.data(), out_len, n);
+}
 int lz4hip_decompress_safe_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                  const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n) {
   return host_batch(OP_DECODE_SAFE, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
@@ -1340,6 +1376,11 @@ int lz4hip_compress_dest_size_batch_dev(const uint8_t* src, const uint64_t* src_
                                         const uint64_t* dst_off, const int32_t* target_size, int32_t* out_len, int32_t* src_consumed,
                                         uint32_t n, int device, void* stream) {
   return dev_dest_batch(src, src_off, src_len, dst, dst_off, target_size, out_len, src_consumed, n, device, stream);
+}
+int lz4hip_decompress_safe_partial_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                             const uint64_t* dst_off, const int32_t* target_len, const int32_t* dst_cap, int32_t* out_len,
+                                             uint32_t n, int device, void* stream) {
+  return dev_partial_batch(src, src_off, src_len, dst, dst_off, target_len, dst_cap, out_len, n, device, stream);
 }
 int lz4hip_decompress_safe_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                      const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int device, void* stream) {
@@ -1440,6 +1481,9 @@ int lz4hip_compress_hc(const uint8_t* src, int src_len, uint8_t* dst, int dst_ca
 }
 int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap) { return single(OP_DECODE_SAFE, src, src_len, dst, dst_cap); }
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len) { return single(OP_DECODE_FAST, src, src_cap, dst, dst_len); }
+int lz4hip_decompress_safe_partial(const uint8_t* src, int src_len, uint8_t* dst, int target_size, int dst_cap) {
+  return single(OP_DECODE_PARTIAL, src, src_len, dst, partial_room(target_size, dst_cap));
+}
 int lz4hip_xxh32(const uint8_t* buf, int len, uint32_t seed, uint32_t* out) {
   const uint64_t zero = 0;
   int32_t l = len;

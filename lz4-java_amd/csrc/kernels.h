@@ -68,6 +68,10 @@ int launch_container_read(int kind, int block_checksum, const uint8_t* body, uin
 void set_route_short(int bytes_per_sequence);
 int last_decode_route(uint32_t* out6);   // diagnostic (8 words): {route, sampled hops, sampled stream bytes, average compressed size, offsets within 6 KB, sequences looked at, their output bytes, 0} of the current device's last routed launch (synchronises)
 int launch_decompress(const BatchArgs& a, bool safe, int lanes_per_block, int pipe, int stage, int ring, void* stream, uint32_t* route_word = nullptr);
+// LZ4_decompress_safe_partial: block i decodes into min(target[i], a.dst_cap[i]) bytes (-1 where one of them or src_len[i] is
+// negative); out[i] = liblz4's return value.  >= 40960 blocks: decode_partial_kernel<4, 0, true> (staged), fewer:
+// decode_partial_deep_kernel<8>; the decode knobs and the device-side route do not apply
+int launch_decompress_partial(const BatchArgs& a, const int32_t* target, void* stream);
 int launch_xxh32(const uint8_t* buf, const uint64_t* off, const int32_t* len, uint32_t seed, uint32_t* out, uint32_t n, void* stream);
 int launch_xxh64(const uint8_t* buf, const uint64_t* off, const int32_t* len, uint64_t seed, uint64_t* out, uint32_t n, void* stream);
 // streaming xxhash: `rec` = device record of xxh_stream_rec_bytes() bytes (the digest so far sits at xxh_stream_digest_offset());

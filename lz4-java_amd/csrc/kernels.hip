@@ -17,6 +17,9 @@
 //   decode_kernel<GL, SAFE, PIPE, STAGE>
 //                        : GL lanes per block, 64/GL blocks per wavefront, algorithm in lz4_decode_core.h; PIPE = software-
 //                          pipelined loop for small batches, STAGE = output through LDS as whole lines for large ones.
+//   decode_partial_kernel<GL, PIPE, STAGE>, decode_partial_deep_kernel<GL>
+//                        : LZ4_decompress_safe_partial: decode_kernel's and decode_deep_kernel's safe forms with the core's PARTIAL
+//                          switch and a per-block target next to BatchArgs.
 //                          Bound: HBM (reads C, writes N per block; match sources are random lines).
 //   hc_build_kernel / hc_parse_kernel
 //                        : LZ4 HC levels 1..12 (lz4_hc_core.h): chain deltas through a 128 KB LDS head table, then the parse.
@@ -1174,6 +1177,35 @@ __global__ __launch_bounds__(256, LZ4HIP_DEEP_WGS) void decode_deep_kernel(Batch
   if (g.l == 0) a.out[gid] = r;
 }
 
+// LZ4_decompress_safe_partial: twins of decode_kernel<GL, true, PIPE, STAGE> and decode_deep_kernel<GL, true> (same launch bounds, same
+// LDS) with lz4_decode_core.h's PARTIAL switch; block i decodes into min(target[i], dst_cap[i]) bytes, and a negative size gives -1
+__device__ __forceinline__ int partial_out_size(const BatchArgs& a, const int32_t* target, uint32_t i) {
+  const int32_t t = target[i], c = a.dst_cap[i];
+  return (t < 0 || c < 0) ? -1 : (t < c ? t : c);
+}
+template <int GL, int PIPE, bool STAGE>
+__global__ __launch_bounds__(256) void decode_partial_kernel(BatchArgs a, const int32_t* target) {
+  constexpr uint32_t kPer = PIPE == 2 ? GroupDev<GL>::kStreamLds : GroupDev<GL>::kStage;
+  __shared__ __attribute__((aligned(16))) uint8_t stage_mem[((STAGE || PIPE == 2) ? (256 / GL) * kPer : 16) + LZ4HIP_LDS_PAD];
+  const uint32_t gid = (blockIdx.x * 256u + threadIdx.x) / GL;
+  if (gid >= a.n) return;  // a whole group leaves together
+  GroupDev<GL> g;
+  uint8_t* stage = (STAGE || PIPE == 2) ? stage_mem + (threadIdx.x / GL) * kPer : nullptr;
+  const int r = decode_block<GroupDev<GL>, true, PIPE, STAGE, true>(g, a.src + a.src_off[gid], a.src_len[gid], a.dst + a.dst_off[gid],
+                                                                  partial_out_size(a, target, gid), stage);
+  if (g.l == 0) a.out[gid] = r;
+}
+template <int GL>
+__global__ __launch_bounds__(256, LZ4HIP_DEEP_WGS) void decode_partial_deep_kernel(BatchArgs a, const int32_t* target) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage_mem[(256 / GL) * GroupDev<GL>::kStreamLds + LZ4HIP_LDS_PAD];
+  const uint32_t gid = (blockIdx.x * 256u + threadIdx.x) / GL;
+  if (gid >= a.n) return;
+  GroupDev<GL> g;
+  const int r = decode_block<GroupDev<GL>, true, 2, false, true>(g, a.src + a.src_off[gid], a.src_len[gid], a.dst + a.dst_off[gid],
+                                                                 partial_out_size(a, target, gid), stage_mem + (threadIdx.x / GL) * GroupDev<GL>::kStreamLds);
+  if (g.l == 0) a.out[gid] = r;
+}
+
 // the ring loop's kernel (lz4_decode_ring.h): per block a stream ring and an output ring of KW bytes in LDS.  One wavefront per
 // workgroup: the LDS a workgroup asks for is what one wavefront's 64 / GL blocks need, so the CU fills to the last wavefront
 // (KW 512, 4 lanes: 16 blocks x 832 bytes = 13 KB, 12 wavefronts per CU; KW 4096, 16 lanes: 4 x 4.6 KB, 8 per CU).
@@ -1621,6 +1653,17 @@ int launch_decompress(const BatchArgs& a, bool safe, int lanes_per_block, int pi
     case 8:
     default: return launch_decode_gl<8>(a, safe, p, sg, st);
   }
+}
+
+// LZ4_decompress_safe_partial: the two lane-group decoders an unrouted safe decode of the same batch size gets -- >= 40960 blocks:
+// 4 lanes per block, the plain loop with output staging; fewer: 8 lanes, the deep loop.  No route, no wave / pair / trio / ring loop
+// (each of them ends a block in code of its own) and no decode_* knob.
+int launch_decompress_partial(const BatchArgs& a, const int32_t* target, void* stream) {
+  if (a.n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (a.n >= 40960u) hipLaunchKernelGGL((decode_partial_kernel<4, 0, true>), dim3((a.n + 63u) / 64u), dim3(256), 0, st, a, target);
+  else hipLaunchKernelGGL((decode_partial_deep_kernel<8>), dim3((a.n + 31u) / 32u), dim3(256), 0, st, a, target);
+  return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -43,6 +43,13 @@
 #include "lz4_decode_trio.h"
 namespace lz4hip {
 
+// PARTIAL decoding: a literal or match length of `base` plus the extension bytes' 32-bit sum `ext` (liblz4 adds that unsigned sum to a
+// size_t), as an int that compares with `room` as the real length does: the length itself if it is <= room, else room + 1
+LZ4HIP_DEV int partial_run(uint32_t base, uint32_t ext, int room) {
+  const int64_t n = (int64_t)base + (int64_t)ext;
+  return n > (int64_t)room ? room + 1 : (int)n;
+}
+
 // SAFE: LZ4_decompress_safe(src, dst, src_size, out_size) -> decoded size or negative.
 // !SAFE: LZ4_decompress_fast(src, dst, out_size) -> bytes consumed or negative; `src_size` is then
 //        the readable capacity of the source slot and is never exceeded (liblz4 itself trusts the
@@ -61,8 +68,14 @@ namespace lz4hip {
 //       8 = the trio loop of lz4_decode_trio.h (THREE WAVEFRONTS PER BLOCK: the caller is the copier; a planner and a scanner wavefront run trio_service on the same LDS).
 // STAGE: the interior loop writes through an LDS staging buffer (`stage`, Grp::kStage bytes for this block) and output leaves
 //        it as whole 128-byte lines (group_dev.h st_*).
-template <class Grp, bool SAFE, int PIPE = 0, bool STAGE = false>
+// PARTIAL (SAFE only): LZ4_decompress_safe_partial(src, dst, src_size, target, cap) with out_size = min(target, cap) -- liblz4
+//        1.9.3's partialDecoding: decoding stops once out_size bytes are out, or where the input ends; a literal run or a match
+//        longer than what remains is cut, not an error.  Only the end-of-block code differs: every interior loop and tier 1 stay
+//        >= 32 bytes away from oend.  A match of offset 0 (no compressor emits one) that is cut zero-fills like every other offset-0
+//        match here; liblz4 copies those bytes onto themselves, so its output there is whatever its buffer held.
+template <class Grp, bool SAFE, int PIPE = 0, bool STAGE = false, bool PARTIAL = false>
 LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* dst, int out_size, uint8_t* stage = nullptr) {
+  static_assert(!PARTIAL || SAFE, "partial decoding is a safe-decoder mode");
   int ip = 0, op = 0;
   const int iend = src_size, oend = out_size;  // iend: real end (SAFE) / read bound (!SAFE)
   const int shortiend = iend - (SAFE ? 14 : 8) - 2;
@@ -73,6 +86,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
 #define LZ4HIP_LEN_CAP 0x7F000000  /* a run this long can never fit; stops 32-bit wrap on absurd input */
 #define LZ4HIP_NEED_IN(k) do { if (!SAFE && ip + (int)(k) > iend) goto output_error; } while (0)
   if (out_size < 0 || src_size < 0) return -1;
+  if (PARTIAL && out_size == 0) return 0;
   if (SAFE && out_size == 0) return (src_size == 1 && g.ld8(src) == 0) ? 0 : -1;
   if (!SAFE && out_size == 0) { LZ4HIP_NEED_IN(1); return g.ld8(src) == 0 ? 1 : -1; }
   if (SAFE && src_size == 0) return -1;
@@ -320,16 +334,18 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
         if (SAFE && ip >= iend - 15) goto output_error;
         uint32_t s = (w4 >> 8) & 255u;  // readable: ip+4 <= iend held (SAFE: ip < iend-15; !SAFE: checked next)
         if (!SAFE && ip + 3 > iend) { LZ4HIP_NEED_IN(1); s = g.ld8(src + ip); }
+        if (PARTIAL) length = 0;  // (PARTIAL: `length` sums the extension bytes in 32 bits, as liblz4 does; the 15 is added after)
         for (;;) {
           ip++;
-          length += (int)s;
+          if (PARTIAL) length = (int)((uint32_t)length + s); else length += (int)s;
           if (SAFE && ip >= iend - 15) break;
           if (s != 255u) break;
           LZ4HIP_NEED_IN(1);
           s = g.ld8(src + ip);
-          if (length > LZ4HIP_LEN_CAP) goto output_error;
+          if (!PARTIAL && length > LZ4HIP_LEN_CAP) goto output_error;
         }
-        if ((uint32_t)length > (uint32_t)(oend - op)) goto output_error;  // cannot fit: every tier rejects it at this ip
+        if (PARTIAL) length = partial_run(15u, (uint32_t)length, iend - ip < oend - op ? iend - ip : oend - op);   // (cut at safe_literal_copy)
+        else if ((uint32_t)length > (uint32_t)(oend - op)) goto output_error;  // cannot fit: every tier rejects it at this ip
         cpy = op + length;
         if (SAFE) { if (cpy > oend - 32 || ip + length > iend - 32) goto safe_literal_copy; }
         else      { if (cpy > oend - 8) goto safe_literal_copy; }
@@ -356,16 +372,18 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
         if (SAFE && offset > op) goto output_error;
         uint32_t s = (w4 >> 16) & 255u;
         if (ip + 2 > iend) { LZ4HIP_NEED_IN(1); s = g.ld8(src + ip); }  // (SAFE: error follows below anyway)
+        if (PARTIAL) length = 0;
         for (;;) {  // read_variable_length(limit iend-4, loop check when SAFE)
           ip++;
-          length += (int)s;
+          if (PARTIAL) length = (int)((uint32_t)length + s); else length += (int)s;
           if (SAFE && ip >= iend - 4) goto output_error;
           if (s != 255u) break;
           LZ4HIP_NEED_IN(1);
           s = g.ld8(src + ip);
-          if (length > LZ4HIP_LEN_CAP) goto output_error;
+          if (!PARTIAL && length > LZ4HIP_LEN_CAP) goto output_error;
         }
-        if ((uint32_t)length > (uint32_t)(oend - op)) goto output_error;  // (offset <= op was checked / is checked first by liblz4 too)
+        if (PARTIAL) length = partial_run(15u, (uint32_t)length, oend - op - 4);   // (cut at safe_match_copy)
+        else if ((uint32_t)length > (uint32_t)(oend - op)) goto output_error;  // (offset <= op was checked / is checked first by liblz4 too)
         length += 4;
         if (op + length >= oend - 64) goto safe_match_copy;
       } else {
@@ -407,53 +425,70 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
     }
     if (length == 15) {
       if (SAFE && ip >= iend - 15) goto output_error;
+      if (PARTIAL) length = 0;
       for (;;) {
         LZ4HIP_NEED_IN(1);
         const uint32_t s = g.ld8(src + ip);
         ip++;
-        length += (int)s;
-        if (length > LZ4HIP_LEN_CAP) goto output_error;
+        if (PARTIAL) length = (int)((uint32_t)length + s); else length += (int)s;
+        if (!PARTIAL && length > LZ4HIP_LEN_CAP) goto output_error;
         if (SAFE && ip >= iend - 15) break;
         if (s != 255u) break;
       }
-      if ((uint32_t)length > (uint32_t)(oend - op)) goto output_error;
+      if (PARTIAL) length = partial_run(15u, (uint32_t)length, iend - ip < oend - op ? iend - ip : oend - op);
+      else if ((uint32_t)length > (uint32_t)(oend - op)) goto output_error;
     }
     cpy = op + length;
   safe_literal_copy:
     if ((SAFE && (cpy > oend - 12 || ip + length > iend - (2 + 1 + 5))) || (!SAFE && cpy > oend - 8)) {
-      if (!SAFE && cpy != oend) goto output_error;
-      if (SAFE && (ip + length != iend || cpy > oend)) goto output_error;
+      if constexpr (PARTIAL) {   // the run is cut to the input, then to the output; decoding goes on only if an offset can follow
+        if (length > iend - ip) { length = iend - ip; cpy = op + length; }
+        if (cpy > oend) { cpy = oend; length = oend - op; }
+      } else {
+        if (!SAFE && cpy != oend) goto output_error;
+        if (SAFE && (ip + length != iend || cpy > oend)) goto output_error;
+      }
       LZ4HIP_NEED_IN(length);
       g.copy_lits(dst + op, src + ip, (uint32_t)length, false);
       ip += length;
       op += length;
-      break;
+      if (!PARTIAL || cpy == oend || ip >= iend - 2) break;
+    } else {
+      LZ4HIP_NEED_IN(length);
+      g.copy_lits(dst + op, src + ip, (uint32_t)length, false);
+      ip += length;
+      op = cpy;
     }
-    LZ4HIP_NEED_IN(length);
-    g.copy_lits(dst + op, src + ip, (uint32_t)length, false);
-    ip += length;
-    op = cpy;
     LZ4HIP_NEED_IN(2);
     offset = (int)g.ld16(src + ip);
     ip += 2;
     length = (int)(token & 15u);
   copy_match_label:
     if (length == 15) {
+      if (PARTIAL) length = 0;
       for (;;) {
         LZ4HIP_NEED_IN(1);
         const uint32_t s = g.ld8(src + ip);
         ip++;
-        length += (int)s;
+        if (PARTIAL) length = (int)((uint32_t)length + s); else length += (int)s;
         if (SAFE && ip >= iend - 4) goto output_error;
-        if (length > LZ4HIP_LEN_CAP) goto output_error;
+        if (!PARTIAL && length > LZ4HIP_LEN_CAP) goto output_error;
         if (s != 255u) break;
       }
-      if (offset <= op && (uint32_t)length > (uint32_t)(oend - op)) goto output_error;
+      if (PARTIAL) length = partial_run(15u, (uint32_t)length, oend - op - 4);
+      else if (offset <= op && (uint32_t)length > (uint32_t)(oend - op)) goto output_error;
     }
     length += 4;
   safe_match_copy:
     if (offset > op) goto output_error;
     cpy = op + length;
+    if (PARTIAL && cpy > oend - 12) {   // liblz4's MATCH_SAFEGUARD_DISTANCE: copy what fits (byte-forward: overlapping matches included)
+      const int mlen = length < oend - op ? length : oend - op;
+      g.copy_match(dst, (uint32_t)op, (uint32_t)offset, (uint32_t)mlen, false);
+      op += mlen;
+      if (op == oend) break;
+      continue;
+    }
     if (cpy > oend - 5) goto output_error;  // the last 5 bytes are always literals
     g.copy_match(dst, (uint32_t)op, (uint32_t)offset, (uint32_t)length, false);
     op = cpy;

@@ -5,6 +5,7 @@
 //   net::jpountz::lz4::LZ4Factory::hipInstance()     <- LZ4Factory.java:91-126 (new fourth accessor), :229-291
 //   LZ4Compressor::compress / maxCompressedLength   <- LZ4Compressor.java:36,59 ; LZ4JNICompressor.java:35-43
 //   LZ4SafeDecompressor::decompress                 <- LZ4SafeDecompressor.java:45 ; LZ4JNISafeDecompressor.java:34-43
+//   LZ4SafeDecompressor::decompressPartial          =  LZ4_decompress_safe_partial of liblz4's main API (no reference entry reaches it)
 //   LZ4FastDecompressor::decompress                 <- LZ4FastDecompressor.java:48 ; LZ4JNIFastDecompressor.java:35-44
 //   LZ4Exception                                    <- LZ4Exception.java
 //   net::jpountz::xxhash::XXHashFactory::hipInstance().hash32()/hash64()  <- XXHashFactory.java:80,211,220
@@ -119,6 +120,15 @@ class LZ4SafeDecompressor {
     bytes out((size_t)maxDestLen);
     out.resize((size_t)decompress(src, 0, (int)src.size(), out, 0, maxDestLen));
     return out;
+  }
+  // liblz4's LZ4_decompress_safe_partial: decodes the first min(targetLen, maxDestLen) bytes of the block (fewer where a cut stream
+  // ends first) into dest + destOff and returns the count; nothing is written past destOff + min(targetLen, maxDestLen)
+  int decompressPartial(const bytes& src, int srcOff, int srcLen, bytes& dest, int destOff, int targetLen, int maxDestLen) const {
+    util::checkRange(src, srcOff, srcLen);
+    util::checkRange(dest, destOff, maxDestLen);
+    const int result = libCheck(lz4hip_decompress_safe_partial(src.data() + srcOff, srcLen, dest.data() + destOff, targetLen, maxDestLen));
+    if (result < 0) throw LZ4Exception("Error decoding offset " + std::to_string(srcOff - result) + " of input buffer");
+    return result;
   }
 };
 

@@ -88,6 +88,23 @@ public final class LZ4HIPBatch {
     }
   }
 
+  /**
+   * liblz4's {@code LZ4_decompress_safe_partial} per block: the first {@code min(targetLen[i], destCap[i])} bytes of block i (fewer
+   * where a cut stream ends first) into the slot {@code dest[destOff[i], destOff[i]+destCap[i])}, nothing past
+   * {@code destOff[i] + min(targetLen[i], destCap[i])}.  outLen[i] &gt;= 0: bytes decoded; &lt; 0: -(input position)-1.
+   */
+  public static void decompressSafePartial(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetLen,
+      int[] destCap, int[] outLen) {
+    check(src, dest, srcOff, srcLen, destOff, destCap, outLen);
+    if (targetLen.length != srcOff.length) {
+      throw new IllegalArgumentException("per-block arrays must have the same length");
+    }
+    final int rc = LZ4HIPJNI.LZ4HIP_batchSafePartial(src, srcOff, srcLen, dest, destOff, targetLen, destCap, outLen, srcOff.length);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
   /** outLen[i] &gt;= 0: decompressed size; &lt; 0: -(input position)-1. */
   public static void decompressSafe(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen) {
     run(1, 0, src, srcOff, srcLen, dest, destOff, destCap, outLen);

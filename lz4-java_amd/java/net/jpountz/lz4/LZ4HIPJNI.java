@@ -61,6 +61,10 @@ enum LZ4HIPJNI {
                                            byte[] destArray, ByteBuffer destBuffer, int destOff, int destLen);
   static native int LZ4HIP_decompress_safe(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
                                            byte[] destArray, ByteBuffer destBuffer, int destOff, int maxDestLen);
+  /* LZ4_decompress_safe_partial: the first min(targetLen, maxDestLen) decoded bytes; liblz4's return value or a library failure as
+   * above.  Same NULL / pinning rules as LZ4HIP_decompress_safe */
+  static native int LZ4HIP_decompress_safe_partial(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
+                                                   byte[] destArray, ByteBuffer destBuffer, int destOff, int targetLen, int maxDestLen);
   static native int LZ4HIP_compressBound(int len);
 
   /* batches over DIRECT buffers (so the shim never pins the Java heap across a kernel):
@@ -73,6 +77,10 @@ enum LZ4HIPJNI {
    * written, srcConsumed = input consumed.  Returns 0 or a negative lz4hip_status (a null argument: LZ4HIP_E_ARG). */
   static native int LZ4HIP_batchDestSize(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetSize,
                                          int[] outLen, int[] srcConsumed, int nBlocks);
+  /* LZ4_decompress_safe_partial per block over DIRECT buffers: block i decodes into at most dest[destOff[i], + min(targetLen[i],
+   * destCap[i])); outLen = liblz4's return values.  Returns 0 or a negative lz4hip_status (a null argument: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchSafePartial(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetLen,
+                                            int[] destCap, int[] outLen, int nBlocks);
 
   /** Container blocks assembled on the device (LZ4HIPBatch.containerBlocks); returns bytes written or the negative lz4hip_status. */
   static native long LZ4HIP_containerBlocks(int kind, int flags, int level, ByteBuffer src, long srcOff, long len, int blockSize,

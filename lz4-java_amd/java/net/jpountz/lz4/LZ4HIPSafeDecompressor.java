@@ -62,4 +62,41 @@ final class LZ4HIPSafeDecompressor extends LZ4SafeDecompressor {
     }
     return LZ4Factory.safeInstance().safeDecompressor().decompress(src, srcOff, srcLen, dest, destOff, maxDestLen);
   }
+
+  /**
+   * liblz4's {@code LZ4_decompress_safe_partial}: decodes the first {@code min(targetLen, maxDestLen)} bytes of the block (fewer
+   * where a cut stream ends first) into {@code dest[destOff, ...)} and returns the count; nothing is written past
+   * {@code destOff + min(targetLen, maxDestLen)}.  The argument checks and the exception message are decompress()'s.
+   */
+  public final int decompressPartial(byte[] src, int srcOff, int srcLen, byte[] dest, int destOff, int targetLen, int maxDestLen) {
+    SafeUtils.checkRange(src, srcOff, srcLen);
+    SafeUtils.checkRange(dest, destOff, maxDestLen);
+    final int result = LZ4HIPJNI.LZ4HIP_decompress_safe_partial(src, null, srcOff, srcLen, dest, null, destOff, targetLen, maxDestLen);
+    if (result < 0) {
+      throw new LZ4Exception(result <= Integer.MIN_VALUE + 63 ? "liblz4hip: " + LZ4HIPJNI.lastError()
+                                                               : "Error decoding offset " + (srcOff - result) + " of input buffer");
+    }
+    return result;
+  }
+
+  /** {@link #decompressPartial(byte[], int, int, byte[], int, int, int)} over heap or direct buffers (positions untouched). */
+  public int decompressPartial(ByteBuffer src, int srcOff, int srcLen, ByteBuffer dest, int destOff, int targetLen, int maxDestLen) {
+    ByteBufferUtils.checkNotReadOnly(dest);
+    ByteBufferUtils.checkRange(src, srcOff, srcLen);
+    ByteBufferUtils.checkRange(dest, destOff, maxDestLen);
+    if (!(src.hasArray() || src.isDirect()) || !(dest.hasArray() || dest.isDirect())) {
+      throw new IllegalArgumentException("decompressPartial needs heap-backed or direct ByteBuffers");
+    }
+    final byte[] srcArr = src.hasArray() ? src.array() : null;
+    final byte[] destArr = dest.hasArray() ? dest.array() : null;
+    final int so = srcArr != null ? srcOff + src.arrayOffset() : srcOff;
+    final int dof = destArr != null ? destOff + dest.arrayOffset() : destOff;
+    final int result = LZ4HIPJNI.LZ4HIP_decompress_safe_partial(srcArr, srcArr == null ? src : null, so, srcLen,
+                                                                destArr, destArr == null ? dest : null, dof, targetLen, maxDestLen);
+    if (result < 0) {
+      throw new LZ4Exception(result <= Integer.MIN_VALUE + 63 ? "liblz4hip: " + LZ4HIPJNI.lastError()
+                                                               : "Error decoding offset " + (srcOff - result) + " of input buffer");
+    }
+    return result;
+  }
 }

@@ -92,6 +92,7 @@ static jint run_single(JNIEnv* env, int op, int level, jbyteArray srcArray, jobj
     case 1: result = lz4hip_decompress_safe(in.p, srcLen, out.p, destLen); break;
     case 2: result = lz4hip_decompress_fast(in.p, srcLen /* readable capacity */, out.p, destLen); break;
     case 4: result = lz4hip_compress_fast_accel(in.p, srcLen, out.p, destLen, level /* acceleration */); break;
+    case 5: result = lz4hip_decompress_safe_partial(in.p, srcLen, out.p, level /* target */, destLen); break;
     default: result = lz4hip_compress_hc(in.p, srcLen, out.p, destLen, level); break;
   }
   region_out(env, NULL, 0, 0, &in);
@@ -158,6 +159,14 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1safe(J
     jint srcOff, jint srcLen, jbyteArray destArray, jobject destBuffer, jint destOff, jint maxDestLen) {
   (void)cls;
   return run_single(env, 1, 0, srcArray, srcBuffer, srcOff, srcLen, destArray, destBuffer, destOff, maxDestLen);
+}
+
+/* LZ4_decompress_safe_partial: the first min(targetLen, maxDestLen) decoded bytes; same arguments, staging and return convention as
+ * LZ4HIP_decompress_safe, and only the decoded bytes go back to a heap array */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1safe_1partial(JNIEnv* env, jclass cls, jbyteArray srcArray,
+    jobject srcBuffer, jint srcOff, jint srcLen, jbyteArray destArray, jobject destBuffer, jint destOff, jint targetLen, jint maxDestLen) {
+  (void)cls;
+  return run_single(env, 5, targetLen, srcArray, srcBuffer, srcOff, srcLen, destArray, destBuffer, destOff, maxDestLen);
 }
 
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1fast(JNIEnv* env, jclass cls, jbyteArray srcArray, jobject srcBuffer,
@@ -233,6 +242,36 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchDestSize(JNIE
   if (ts) (*env)->ReleaseIntArrayElements(env, targetSize, ts, JNI_ABORT);
   if (ol) (*env)->ReleaseIntArrayElements(env, outLen, ol, 0);
   if (sc) (*env)->ReleaseIntArrayElements(env, srcConsumed, sc, 0);
+  return rc;
+}
+
+/* LZ4_decompress_safe_partial over many blocks, direct buffers (lz4hip_decompress_safe_partial_batch): block i decodes into at most
+ * dest[destOff[i] .. + min(targetLen[i], destCap[i])), outLen[i] = liblz4's return value.  Returns 0 or a negative lz4hip_status; a
+ * NULL array or buffer is LZ4HIP_E_ARG */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafePartial(JNIEnv* env, jclass cls, jobject src, jlongArray srcOff,
+    jintArray srcLen, jobject dest, jlongArray destOff, jintArray targetLen, jintArray destCap, jintArray outLen, jint n) {
+  (void)cls;
+  if (src == NULL || dest == NULL || srcOff == NULL || srcLen == NULL || destOff == NULL || targetLen == NULL || destCap == NULL ||
+      outLen == NULL) return LZ4HIP_E_ARG;
+  const uint8_t* s = (const uint8_t*)(*env)->GetDirectBufferAddress(env, src);
+  uint8_t* d = (uint8_t*)(*env)->GetDirectBufferAddress(env, dest);
+  if (s == NULL || d == NULL) return LZ4HIP_E_ARG;
+  jlong* so = (*env)->GetLongArrayElements(env, srcOff, NULL);
+  jint* sl = (*env)->GetIntArrayElements(env, srcLen, NULL);
+  jlong* dof = (*env)->GetLongArrayElements(env, destOff, NULL);
+  jint* tl = (*env)->GetIntArrayElements(env, targetLen, NULL);
+  jint* dc = (*env)->GetIntArrayElements(env, destCap, NULL);
+  jint* ol = (*env)->GetIntArrayElements(env, outLen, NULL);
+  jint rc = LZ4HIP_E_NOMEM;
+  if (so && sl && dof && tl && dc && ol)
+    rc = lz4hip_decompress_safe_partial_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)tl,
+                                              (const int32_t*)dc, (int32_t*)ol, (uint32_t)n);
+  if (so) (*env)->ReleaseLongArrayElements(env, srcOff, so, JNI_ABORT);
+  if (sl) (*env)->ReleaseIntArrayElements(env, srcLen, sl, JNI_ABORT);
+  if (dof) (*env)->ReleaseLongArrayElements(env, destOff, dof, JNI_ABORT);
+  if (tl) (*env)->ReleaseIntArrayElements(env, targetLen, tl, JNI_ABORT);
+  if (dc) (*env)->ReleaseIntArrayElements(env, destCap, dc, JNI_ABORT);
+  if (ol) (*env)->ReleaseIntArrayElements(env, outLen, ol, 0);
   return rc;
 }
 

@@ -1,0 +1,186 @@
+/* tests/jni_stub/fake_jni_partial.c -- TEST INFRASTRUCTURE ONLY.
+ *
+ * The partial-decode natives of the JNI shim (LZ4HIPJNI.LZ4HIP_decompress_safe_partial and LZ4HIP_batchSafePartial) executed without a
+ * JVM, with the same fake JNIEnv as fake_jni.c (a byte[] / int[] / long[] is a malloc'd buffer with pin accounting, a direct ByteBuffer
+ * is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built by tests/test_partial_abi.py / tests/test_gpu_partial.py.
+ *
+ *   fake_jni_partial --no-gpu                          anywhere: NULL arrays are argument errors, every compute call fails LOUDLY
+ *                                                      without a device (library error code, nothing leaked or left pinned)
+ *   fake_jni_partial <stream> <target> <cap> <out-dir> on a GPU box: decodes the LZ4 block <stream> into min(<target>, <cap>) bytes
+ *                                                      through every argument shape and the batch native, writes the bytes and the
+ *                                                      return value to <out-dir>/partial.bin / partial.txt (the test compares them
+ *                                                      with the reference's LZ4_decompress_safe_partial); prints
+ *                                                      "fake_jni_partial: N checks ok"
+ */
+#include <jni.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "lz4hip.h"
+
+typedef struct {
+  int kind;          /* 1 = byte[], 2 = int[], 3 = long[], 4 = direct ByteBuffer, 5 = heap ByteBuffer (no direct address) */
+  uint8_t* data;
+  size_t bytes;
+  int pins;
+  int refuse_pin;
+} fobj;
+
+static long g_alloc = 0;
+void* t_malloc(size_t n) { g_alloc++; return malloc(n); }
+void t_free(void* p) { if (p) g_alloc--; free(p); }
+
+static const char* g_exc_class = NULL;
+static char g_exc_msg[512];
+static int g_checks = 0;
+
+#define CHECK(c) do { if (!(c)) { fprintf(stderr, "fake_jni_partial: CHECK failed at line %d: %s (pending exception: %s \"%s\")\n", __LINE__, #c, \
+    g_exc_class ? g_exc_class : "none", g_exc_msg); exit(1); } g_checks++; } while (0)
+
+static jclass f_FindClass(JNIEnv* e, const char* name) { (void)e; return (jclass)strdup(name); }
+static jint f_ThrowNew(JNIEnv* e, jclass c, const char* msg) { (void)e; g_exc_class = (const char*)c; snprintf(g_exc_msg, sizeof g_exc_msg, "%s", msg ? msg : ""); return 0; }
+static jobject f_NewGlobalRef(JNIEnv* e, jobject o) { (void)e; return o; }
+static void* f_GetCritical(JNIEnv* e, jarray a, jboolean* isCopy) {
+  (void)e; fobj* o = (fobj*)a;
+  if (isCopy) *isCopy = 0;
+  if (o->refuse_pin) return NULL;
+  o->pins++;
+  return o->data;
+}
+static void f_ReleaseCritical(JNIEnv* e, jarray a, void* p, jint mode) { (void)e; (void)mode; fobj* o = (fobj*)a; if (p != o->data) { fprintf(stderr, "release of a foreign pointer\n"); exit(1); } o->pins--; }
+static void* f_GetDirect(JNIEnv* e, jobject b) { (void)e; fobj* o = (fobj*)b; return o->kind == 4 ? o->data : NULL; }
+static jstring f_NewStringUTF(JNIEnv* e, const char* s) { (void)e; return (jstring)strdup(s ? s : ""); }
+static jlong* f_GetLongs(JNIEnv* e, jlongArray a, jboolean* c) { (void)e; if (c) *c = 0; ((fobj*)a)->pins++; return (jlong*)((fobj*)a)->data; }
+static jint* f_GetInts(JNIEnv* e, jintArray a, jboolean* c) { (void)e; if (c) *c = 0; ((fobj*)a)->pins++; return (jint*)((fobj*)a)->data; }
+static void f_RelLongs(JNIEnv* e, jlongArray a, jlong* p, jint m) { (void)e; (void)p; (void)m; ((fobj*)a)->pins--; }
+static void f_RelInts(JNIEnv* e, jintArray a, jint* p, jint m) { (void)e; (void)p; (void)m; ((fobj*)a)->pins--; }
+static jint f_ArrayLength(JNIEnv* e, jarray a) { (void)e; const fobj* o = (const fobj*)a; return (jint)(o->bytes / (o->kind == 3 ? 8u : o->kind == 2 ? 4u : 1u)); }
+
+static const struct JNINativeInterface_ g_table = {f_FindClass, f_ThrowNew, f_NewGlobalRef, f_GetCritical, f_ReleaseCritical, f_GetDirect,
+                                                   f_NewStringUTF, f_GetLongs, f_GetInts, f_RelLongs, f_RelInts, f_ArrayLength};
+static JNIEnv g_env = &g_table;
+
+static fobj* mk(int kind, size_t bytes) { fobj* o = calloc(1, sizeof *o); o->kind = kind; o->bytes = bytes; o->data = calloc(bytes ? bytes : 1, 1); return o; }
+static int no_exc(void) { return g_exc_class == NULL; }
+static void clear_exc(void) { g_exc_class = NULL; g_exc_msg[0] = 0; }
+/* every byte of o outside [off, off + n) still holds `fill` */
+static int guarded(const fobj* o, size_t off, size_t n, uint8_t fill) {
+  for (size_t i = 0; i < o->bytes; i++)
+    if ((i < off || i >= off + n) && o->data[i] != fill) return 0;
+  return 1;
+}
+
+JNIEXPORT void JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_init(JNIEnv*, jclass);
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1safe_1partial(JNIEnv*, jclass, jbyteArray, jobject, jint, jint, jbyteArray, jobject, jint, jint, jint);
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafePartial(JNIEnv*, jclass, jobject, jlongArray, jintArray, jobject, jlongArray, jintArray, jintArray, jintArray, jint);
+JNIEXPORT jstring JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_lastError(JNIEnv*, jclass);
+
+#define PART Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1safe_1partial
+#define BATCH Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafePartial
+
+static fobj* int1(jint v) { fobj* o = mk(2, 4); ((jint*)o->data)[0] = v; return o; }
+static jint get1(const fobj* o) { return ((const jint*)o->data)[0]; }
+
+int main(int argc, char** argv) {
+  JNIEnv* env = &g_env;
+  Java_net_jpountz_lz4_LZ4HIPJNI_init(env, NULL);
+  CHECK(no_exc());
+  fobj* src = mk(1, 64); fobj* dst = mk(1, 128); fobj* dsrc = mk(4, 64); fobj* ddst = mk(4, 128);
+  /* NULL arrays / buffers of the batch native: LZ4HIP_E_ARG, nothing pinned */
+  { fobj* so = mk(3, 8); fobj* sl = int1(20); fobj* dof = mk(3, 8); fobj* tl = int1(50); fobj* dc = int1(100); fobj* ol = int1(-7);
+    fobj* a[6] = {so, sl, dof, tl, dc, ol};
+    for (int k = 0; k < 8; k++) {
+      jint rc = BATCH(env, NULL, k == 6 ? NULL : (jobject)dsrc, k == 0 ? NULL : (jlongArray)so, k == 1 ? NULL : (jintArray)sl, k == 7 ? NULL : (jobject)ddst,
+                      k == 2 ? NULL : (jlongArray)dof, k == 3 ? NULL : (jintArray)tl, k == 4 ? NULL : (jintArray)dc, k == 5 ? NULL : (jintArray)ol, 1);
+      CHECK(rc == LZ4HIP_E_ARG && no_exc() && get1(ol) == -7);
+      for (int t = 0; t < 6; t++) CHECK(a[t]->pins == 0);
+    }
+    /* heap ByteBuffers where direct ones are required */
+    fobj* hb = mk(5, 64);
+    CHECK(BATCH(env, NULL, (jobject)hb, (jlongArray)so, (jintArray)sl, (jobject)ddst, (jlongArray)dof, (jintArray)tl, (jintArray)dc, (jintArray)ol, 1) == LZ4HIP_E_ARG);
+    if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+      const jint rc = BATCH(env, NULL, (jobject)dsrc, (jlongArray)so, (jintArray)sl, (jobject)ddst, (jlongArray)dof, (jintArray)tl, (jintArray)dc, (jintArray)ol, 1);
+      CHECK(rc == LZ4HIP_E_NO_DEVICE && no_exc());
+      for (int t = 0; t < 6; t++) CHECK(a[t]->pins == 0);
+    } }
+  if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+    memset(dst->data, 0xEE, dst->bytes);
+    jint r = PART(env, NULL, (jbyteArray)src, NULL, 7, 20, (jbyteArray)dst, NULL, 3, 50, 100);
+    CHECK(LZ4HIP_IS_LIB_ERROR(r) && no_exc() && g_alloc == 0 && src->pins == 0 && dst->pins == 0 && guarded(dst, 0, 0, 0xEE));
+    r = PART(env, NULL, NULL, (jobject)dsrc, 0, 20, NULL, (jobject)ddst, 0, 0, 30);   /* (target 0 included: no answer without a device) */
+    CHECK(LZ4HIP_IS_LIB_ERROR(r) && no_exc() && g_alloc == 0);
+    const char* msg = (const char*)Java_net_jpountz_lz4_LZ4HIPJNI_lastError(env, NULL);
+    CHECK(msg && strlen(msg) > 0);
+    printf("fake_jni_partial: %d checks ok (no device: every compute call failed loudly)\n", g_checks);
+    return 0;
+  }
+  if (argc < 5) { fprintf(stderr, "usage: fake_jni_partial --no-gpu | <stream> <target> <cap> <out-dir>\n"); return 2; }
+  FILE* f = fopen(argv[1], "rb");
+  CHECK(f != NULL);
+  fseek(f, 0, SEEK_END);
+  const long n = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  CHECK(n > 0 && n < (1 << 24));
+  const int t = atoi(argv[2]), cap = atoi(argv[3]);
+  CHECK(t >= 0 && cap >= 0);
+  const int room = t < cap ? t : cap;
+  const size_t SO = 5, DO = 7;
+  fobj* asrc = mk(1, (size_t)n + 16); fobj* dsrc2 = mk(4, (size_t)n + 16);
+  CHECK(fread(asrc->data + SO, 1, (size_t)n, f) == (size_t)n);
+  fclose(f);
+  memcpy(dsrc2->data + SO, asrc->data + SO, (size_t)n);
+  fobj* adst = mk(1, (size_t)cap + 32); fobj* ddst2 = mk(4, (size_t)cap + 32);
+  /* byte[] -> byte[] */
+  memset(adst->data, 0xEE, adst->bytes);
+  const jint r = PART(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, (jbyteArray)adst, NULL, (jint)DO, t, cap);
+  CHECK(no_exc() && !LZ4HIP_IS_LIB_ERROR(r) && r <= room && g_alloc == 0 && asrc->pins == 0 && adst->pins == 0);
+  const size_t got = r > 0 ? (size_t)r : 0;
+  CHECK(guarded(adst, DO, got, 0xEE));
+  char path[4096];
+  snprintf(path, sizeof path, "%s/partial.bin", argv[4]);
+  FILE* o = fopen(path, "wb");
+  CHECK(o != NULL && fwrite(adst->data + DO, 1, got, o) == got);
+  fclose(o);
+  snprintf(path, sizeof path, "%s/partial.txt", argv[4]);
+  o = fopen(path, "w");
+  CHECK(o != NULL);
+  fprintf(o, "%d\n", (int)r);
+  fclose(o);
+  /* direct -> direct (NULL arrays), byte[] -> direct, direct -> byte[]: the same result, nothing written past DO + room */
+  for (int shape = 0; shape < 3; shape++) {
+    fobj* adst2 = mk(1, (size_t)cap + 32);
+    memset(ddst2->data, 0xEE, ddst2->bytes); memset(adst2->data, 0xEE, adst2->bytes);
+    const int dir_in = shape != 1, dir_out = shape != 2;
+    const jint r2 = PART(env, NULL, dir_in ? NULL : (jbyteArray)asrc, dir_in ? (jobject)dsrc2 : NULL, (jint)SO, (jint)n,
+                         dir_out ? NULL : (jbyteArray)adst2, dir_out ? (jobject)ddst2 : NULL, (jint)DO, t, cap);
+    const fobj* d = dir_out ? ddst2 : adst2;
+    CHECK(no_exc() && r2 == r && memcmp(d->data + DO, adst->data + DO, got) == 0 && g_alloc == 0);
+    if (dir_out) for (size_t i = DO + (size_t)room; i < d->bytes; i++) CHECK(d->data[i] == 0xEE);
+    else CHECK(guarded(d, DO, got, 0xEE));
+    free(adst2->data); free(adst2);
+  }
+  /* `out` cannot be pinned: `in` is released, OutOfMemoryError */
+  { fobj* nopin = mk(1, (size_t)cap + 1); nopin->refuse_pin = 1;
+    (void)PART(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, (jbyteArray)nopin, NULL, 0, t, cap);
+    CHECK(g_alloc == 0 && asrc->pins == 0 && nopin->pins == 0);
+    if (r > 0) CHECK(g_exc_class && strcmp(g_exc_class, "java/lang/OutOfMemoryError") == 0);
+    clear_exc(); }
+  /* the batch native: two copies of the stream, the second with target 0 -> the single call's result, then 0; slots untouched past
+   * min(target, cap) */
+  { fobj* bsrc = mk(4, 2 * (size_t)n); fobj* bdst = mk(4, 2 * (size_t)cap + 64);
+    memset(bdst->data, 0xEE, bdst->bytes);
+    memcpy(bsrc->data, asrc->data + SO, (size_t)n); memcpy(bsrc->data + n, asrc->data + SO, (size_t)n);
+    fobj* so = mk(3, 16); fobj* sl = mk(2, 8); fobj* dof = mk(3, 16); fobj* tl = mk(2, 8); fobj* dc = mk(2, 8); fobj* ol = mk(2, 8);
+    ((jlong*)so->data)[0] = 0; ((jlong*)so->data)[1] = n; ((jint*)sl->data)[0] = ((jint*)sl->data)[1] = (jint)n;
+    ((jlong*)dof->data)[0] = 0; ((jlong*)dof->data)[1] = cap + 32; ((jint*)tl->data)[0] = t; ((jint*)tl->data)[1] = 0;
+    ((jint*)dc->data)[0] = ((jint*)dc->data)[1] = cap;
+    const jint rc = BATCH(env, NULL, (jobject)bsrc, (jlongArray)so, (jintArray)sl, (jobject)bdst, (jlongArray)dof, (jintArray)tl, (jintArray)dc, (jintArray)ol, 2);
+    const jint* out = (const jint*)ol->data;
+    CHECK(rc == 0 && out[0] == r && out[1] == 0 && so->pins == 0 && ol->pins == 0 && tl->pins == 0 && dc->pins == 0);
+    CHECK(memcmp(bdst->data, adst->data + DO, got) == 0);
+    for (size_t i = (size_t)room; i < (size_t)cap + 32; i++) CHECK(bdst->data[i] == 0xEE);
+    for (size_t i = (size_t)cap + 32; i < bdst->bytes; i++) CHECK(bdst->data[i] == 0xEE); }
+  printf("fake_jni_partial: %d checks ok\n", g_checks);
+  return 0;
+}
