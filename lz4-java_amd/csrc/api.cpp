@@ -35,6 +35,8 @@ int fail(int status, const char* what, hipError_t e = hipSuccess) {
   return status;
 }
 
+const char* const kNullArg = "null pointer argument";
+
 #define HIPCHK(call)                                                   \
   do {                                                                 \
     hipError_t e_ = (call);                                            \
@@ -67,11 +69,31 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
   ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-// OP_COMPRESS_ACCEL: LZ4_compress_fast with acceleration 2 .. 65537, the value travels as `level` (acceleration 1 is OP_COMPRESS_FAST)
+// OP_COMPRESS_ACCEL: LZ4_compress_fast with acceleration 2 .. 65537 (acceleration 1 is OP_COMPRESS_FAST)
 // OP_COMPRESS_DEST: LZ4_compress_destSize, dst_cap = the target size; a second per-block output array carries the consumed sizes
 // OP_DECODE_PARTIAL: LZ4_decompress_safe_partial; on the host path dst_cap already holds min(target, capacity), or -1 where one of
 // them is negative (partial_room), and the kernels get that array as the target too
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL };
+constexpr int OP_COUNT = OP_DECODE_PARTIAL + 1;   // (the last enumerator)
+// What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
+// a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
+constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST; }
+// a second per-block result (BlockCall::consumed) travels behind out[]
+constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST; }
+// out[i] counts SOURCE bytes read: a block that succeeded filled its whole dst_cap[i]
+constexpr bool op_fills_capacity(Op op) { return op == OP_DECODE_FAST; }
+// needs the chain-delta workspace (BlockCall::hc_ws / hc_span)
+constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC; }
+
+// One block operation, from its entry point to launch_block.
+struct BlockCall {
+  Op op;
+  int param = 0;                    // OP_COMPRESS_HC: the level (hc_level); OP_COMPRESS_ACCEL: the acceleration (accel_clamp, >= 2)
+  const int32_t* target = nullptr;  // OP_DECODE_PARTIAL: per-block target sizes; nullptr: dst_cap already is partial_room (host path)
+  int32_t* consumed = nullptr;      // op_has_consumed: the input consumed per block
+  void* hc_ws = nullptr;            // op_uses_hc_ws: device workspace for hc_span bytes of source; nullptr: launch_block learns the
+  uint64_t hc_span = 0;             // span and allocates one (hc_workspace)
+};
 // tuning knobs (lz4hip_set_option): atomics, so that a caller changing one while other threads launch is a race on the VALUE chosen,
 // never undefined behaviour; every launch reads each knob once
 std::atomic<int> g_decode_lanes{0};   // "decode_lanes"; 0 = kernel default
@@ -94,10 +116,11 @@ int hc_level(int level, int* out) {
   return LZ4HIP_OK;
 }
 
-// HC on device pointers.  The chain-delta workspace is indexed by source offset, so its size depends on the batch's source span
-// (max of src_off + src_len), which lives in device memory: this entry learns it with ONE synchronisation of the caller's stream
-// (stated in lz4hip.h); lz4hip_compress_hc_batch_dev_ws takes span and workspace from the caller and never synchronises.
-int dev_hc(const lz4hip::BatchArgs& a, int level, hipStream_t st) {
+// HC on device pointers without a workspace from the caller.  The chain-delta workspace is indexed by source offset, so its size
+// depends on the batch's source span (max of src_off + src_len), which lives in device memory: it is learnt with ONE synchronisation
+// of the caller's stream (stated in lz4hip.h); lz4hip_compress_hc_batch_dev_ws takes span and workspace from the caller and never
+// synchronises.  Returns a status (message set); *ws is the caller's to hipFreeAsync on `st`.
+int hc_workspace(const lz4hip::BatchArgs& a, int level, hipStream_t st, void** ws, uint64_t* span_out) {
   uint64_t* d_span = nullptr;
   uint64_t span = 0;
   HIPCHK(hipMallocAsync((void**)&d_span, 8, st));
@@ -109,73 +132,36 @@ int dev_hc(const lz4hip::BatchArgs& a, int level, hipStream_t st) {
   (void)hipFreeAsync(d_span, st);   // (on every path: round 1 leaked it when a call above failed)
   if (e) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
   if (he != hipSuccess) return fail(LZ4HIP_E_HIP, "HC span query", he);
-  void* ws = nullptr;
-  if (hipMallocAsync(&ws, lz4hip::hc_ws_bytes(span, a.n, level), st) != hipSuccess) return fail(LZ4HIP_E_NOMEM, "HC workspace allocation failed");
-  e = lz4hip::launch_compress_hc(a, level, ws, span, st);
-  (void)hipFreeAsync(ws, st);
-  if (e) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
+  if (hipMallocAsync(ws, lz4hip::hc_ws_bytes(span, a.n, level), st) != hipSuccess) return fail(LZ4HIP_E_NOMEM, "HC workspace allocation failed");
+  *span_out = span;
   return LZ4HIP_OK;
-}
-
-// number of CUs of the current device (cached per ordinal)
-uint32_t cu_count() {
-  static std::mutex mu;
-  static std::vector<int> cache(64, 0);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!cache[dev]) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cache[dev] = v;
-  }
-  return (uint32_t)cache[dev];
 }
 
 // fast compress: the cores of kernels.h, selected by "compress_core"
 int launch_fast(const lz4hip::BatchArgs& a, hipStream_t st) {
   // scratch: three queue words + the routed-block list of the adaptive scheme
   uint32_t* scratch = nullptr;
-  const uint32_t cus = cu_count();
+  const uint32_t cus = lz4hip::device_cus();
   const int core = g_compress_core.load(std::memory_order_relaxed);
   const size_t mail_words = core != 1 ? lz4hip::compress_fast_v2w_scratch_words(cus) : 0u;   // rings of the finder/writer pairs
   hipError_t e = hipMallocAsync((void**)&scratch, (3 + (size_t)a.n + mail_words) * sizeof(uint32_t), st);
   if (e != hipSuccess) return (int)e;
   const uint32_t dense64 = 64u * (uint32_t)g_compress_switch.load(std::memory_order_relaxed);
   int le;
-  switch (core) {
-    case 1: le = lz4hip::launch_compress_fast_ms(a, scratch, nullptr, true, cus, st); break;
-    case 3: le = lz4hip::launch_compress_fast_v2w(a, scratch, nullptr, 0u, cus, scratch + 3 + a.n, st); break;
-    default:   // 5: adaptive
-      le = lz4hip::launch_compress_fast_v2w(a, scratch, scratch + 3, dense64, cus, scratch + 3 + a.n, st);
-      if (le == 0) le = lz4hip::launch_compress_fast_ms(a, scratch, scratch + 3, false, cus, st);
-      break;
+  if (core == 1) {
+    le = lz4hip::launch_compress_fast_ms(a, scratch, nullptr, true, cus, st);
+  } else if (core == 3) {
+    le = lz4hip::launch_compress_fast_v2w(a, scratch, nullptr, 0u, cus, scratch + 3 + a.n, st);
+  } else {   // 5: adaptive
+    le = lz4hip::launch_compress_fast_v2w(a, scratch, scratch + 3, dense64, cus, scratch + 3 + a.n, st);
+    if (le == 0) le = lz4hip::launch_compress_fast_ms(a, scratch, scratch + 3, false, cus, st);
   }
   (void)hipFreeAsync(scratch, st);
   return le;
 }
 
-// LZ4_compress_fast(..., accel), accel already clamped to 2 .. 65537 (compress_fast_accel_cu_kernel; one queue word of scratch)
-int launch_accel(const lz4hip::BatchArgs& a, int accel, hipStream_t st) {
-  uint32_t* q = nullptr;
-  hipError_t e = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
-  if (e != hipSuccess) return (int)e;
-  const int le = lz4hip::launch_compress_fast_accel(a, (uint32_t)accel, q, cu_count(), st);
-  (void)hipFreeAsync(q, st);
-  return le;
-}
 // liblz4's acceleration handling (LZ4_compress_fast_extState): < 1 -> 1, > LZ4_ACCELERATION_MAX -> 65537
 int accel_clamp(int a) { return a < 1 ? 1 : a > 65537 ? 65537 : a; }
-
-// LZ4_compress_destSize (compress_fast_dest_cu_kernel; one queue word of scratch)
-int launch_dest(const lz4hip::BatchArgs& a, int32_t* consumed, hipStream_t st) {
-  uint32_t* q = nullptr;
-  hipError_t e = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
-  if (e != hipSuccess) return (int)e;
-  const int le = lz4hip::launch_compress_dest_size(a, consumed, q, cu_count(), st);
-  (void)hipFreeAsync(q, st);
-  return le;
-}
 
 // the decode knobs are process-wide and set one at a time: a combination no kernel exists for is said here, by name (round-5 advisor: it
 // used to surface as a bare "kernel launch: invalid value")
@@ -225,73 +211,63 @@ void route_release(int d) {   // lz4hip_shutdown (the device is current)
 
 int launch_decode(const lz4hip::BatchArgs& a, bool safe, hipStream_t st) {
   if (const char* why = decode_knobs_error(g_decode_lanes.load(), g_decode_pipe.load(), g_decode_ring.load())) return fail(LZ4HIP_E_ARG, why);
-  uint32_t* route = a.n > 16u * cu_count() ? route_word() : nullptr;   // (nullptr: no device-side route, the lane-group default of the batch size)
+  uint32_t* route = a.n > 16u * lz4hip::device_cus() ? route_word() : nullptr;   // (nullptr: no device-side route, the lane-group default of the batch size)
   return lz4hip::launch_decompress(a, safe, g_decode_lanes.load(), g_decode_pipe.load(), g_decode_stage.load(), g_decode_ring.load(), st, route);
 }
 
-int launch_op(Op op, const lz4hip::BatchArgs& a, hipStream_t st, int level = 0) {
-  int e = 0;
-  switch (op) {
-    case OP_COMPRESS_FAST: e = launch_fast(a, st); break;
-    case OP_COMPRESS_ACCEL: e = launch_accel(a, level, st); break;
-    case OP_DECODE_SAFE: e = launch_decode(a, true, st); break;
-    case OP_DECODE_FAST: e = launch_decode(a, false, st); break;
-    case OP_COMPRESS_HC: return fail(LZ4HIP_E_ARG, "internal: HC goes through dev_hc");
-    case OP_COMPRESS_DEST: return fail(LZ4HIP_E_ARG, "internal: destSize goes through dev_dest_batch");
-    case OP_DECODE_PARTIAL: return fail(LZ4HIP_E_ARG, "internal: partial decoding goes through dev_partial_batch");
+// The one place where a block operation reaches its kernels, on device arrays: the device-pointer entry points (dev_batch) and the
+// host-pointer path (host_shard) both come here.  Returns 0, a launcher's hipError_t (> 0), or a status (< 0) whose message is set.
+int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st) {
+  switch (c.op) {
+    case OP_COMPRESS_FAST: return launch_fast(a, st);
+    case OP_DECODE_SAFE: return launch_decode(a, true, st);
+    case OP_DECODE_FAST: return launch_decode(a, false, st);
+    case OP_DECODE_PARTIAL: return lz4hip::launch_decompress_partial(a, c.target ? c.target : a.dst_cap, st);
+    case OP_COMPRESS_HC: {
+      void* ws = c.hc_ws;
+      uint64_t span = c.hc_span;
+      if (!ws) { const int rc = hc_workspace(a, c.param, st, &ws, &span); if (rc) return rc; }
+      const int e = lz4hip::launch_compress_hc(a, c.param, ws, span, st);
+      if (!c.hc_ws) (void)hipFreeAsync(ws, st);
+      return e;
+    }
+    case OP_COMPRESS_ACCEL:   // the one-sequence kernels (compress_fast_accel_cu_kernel, compress_fast_dest_cu_kernel) draw blocks
+    case OP_COMPRESS_DEST: {  // from one queue word of scratch
+      uint32_t* q = nullptr;
+      const hipError_t me = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
+      if (me != hipSuccess) return (int)me;
+      const int e = c.op == OP_COMPRESS_ACCEL ? lz4hip::launch_compress_fast_accel(a, (uint32_t)c.param, q, lz4hip::device_cus(), st)
+                                              : lz4hip::launch_compress_dest_size(a, c.consumed, q, lz4hip::device_cus(), st);
+      (void)hipFreeAsync(q, st);
+      return e;
+    }
   }
-  if (e == LZ4HIP_E_ARG) return e;        // (decode_knobs_error: the message is set)
-  if (e != 0) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
-  return LZ4HIP_OK;
+  return fail(LZ4HIP_E_ARG, "unknown block operation");
 }
 
-int dev_batch(Op op, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
-              const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, uint32_t n, int device, void* stream, int level = 0) {
+// The prologue and epilogue of every entry point that takes a device index: the engine is up, the empty batch (`empty`; false where
+// the entry has none) is fine, the entry's own argument check (`arg_error`: a message, or nullptr -- which pointers may be NULL
+// differs), the device's ordinal, that device current for the body and the caller's restored after it.  `body` returns what
+// launch_block returns.
+template <class Body>
+int on_device(int device, bool empty, const char* arg_error, Body body) {
   int rc = ensure_init();
   if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (n == 0) return LZ4HIP_OK;
-  if (!src || !src_off || !src_len || !dst || !dst_off || !dst_cap || !out) return fail(LZ4HIP_E_ARG, "null pointer argument");
+  if (empty) return LZ4HIP_OK;
+  if (arg_error) return fail(LZ4HIP_E_ARG, arg_error);
   int ord;
   if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
   DeviceGuard g(ord);
   if (!g.ok) return fail(LZ4HIP_E_HIP, "hipSetDevice failed");
-  lz4hip::BatchArgs a{src, src_off, src_len, dst, dst_off, dst_cap, out, n};
-  if (op == OP_COMPRESS_HC) return dev_hc(a, level, (hipStream_t)stream);
-  return launch_op(op, a, (hipStream_t)stream, level);
+  const int e = body();
+  if (e < 0) return e;   // (the message is set: decode_knobs_error, hc_workspace)
+  return e ? fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e) : LZ4HIP_OK;
 }
 
-// LZ4_compress_destSize on device pointers: dev_batch's checks, plus the consumed-size array
-int dev_dest_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
-                   const int32_t* target, int32_t* out, int32_t* consumed, uint32_t n, int device, void* stream) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (n == 0) return LZ4HIP_OK;
-  if (!src || !src_off || !src_len || !dst || !dst_off || !target || !out || !consumed) return fail(LZ4HIP_E_ARG, "null pointer argument");
-  int ord;
-  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
-  DeviceGuard g(ord);
-  if (!g.ok) return fail(LZ4HIP_E_HIP, "hipSetDevice failed");
-  lz4hip::BatchArgs a{src, src_off, src_len, dst, dst_off, target, out, n};
-  const int e = launch_dest(a, consumed, (hipStream_t)stream);
-  if (e != 0) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
-  return LZ4HIP_OK;
-}
-
-// LZ4_decompress_safe_partial on device pointers: dev_batch's checks, plus the per-block target array
-int dev_partial_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
-                      const int32_t* target, const int32_t* dst_cap, int32_t* out, uint32_t n, int device, void* stream) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (n == 0) return LZ4HIP_OK;
-  if (!src || !src_off || !src_len || !dst || !dst_off || !target || !dst_cap || !out) return fail(LZ4HIP_E_ARG, "null pointer argument");
-  int ord;
-  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
-  DeviceGuard g(ord);
-  if (!g.ok) return fail(LZ4HIP_E_HIP, "hipSetDevice failed");
-  lz4hip::BatchArgs a{src, src_off, src_len, dst, dst_off, dst_cap, out, n};
-  const int e = lz4hip::launch_decompress_partial(a, target, stream);
-  if (e != 0) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
-  return LZ4HIP_OK;
+// a block operation on device pointers; `extra_error`: the entry's check of what it takes beyond the seven arrays
+int dev_batch(const BlockCall& c, const lz4hip::BatchArgs& a, int device, void* stream, const char* extra_error = nullptr) {
+  const bool null_arg = !a.src || !a.src_off || !a.src_len || !a.dst || !a.dst_off || !a.dst_cap || !a.out || (op_has_consumed(c.op) && !c.consumed);
+  return on_device(device, a.n == 0, null_arg ? kNullArg : extra_error, [&] { return launch_block(c, a, (hipStream_t)stream); });
 }
 // the bytes block i of a partial decode may fill: min(target, capacity), or -1 (the kernels' -1) where one of them is negative
 int32_t partial_room(int32_t target, int32_t cap) { return (target < 0 || cap < 0) ? -1 : std::min(target, cap); }
@@ -439,9 +415,9 @@ void par_blocks(uint32_t i0, uint32_t i1, size_t bytes, F f) {  // f(i) for i in
 // finisher thread per chunk waits for chunk c - 1 and hands its bytes to the caller's slots.  (Rounds 1-2 did pack, the
 // synchronous D2H of the packed bytes and the unpack one after the other on the calling thread: 44 ms per GiB, twice what the
 // link needs -- tools/host_path_probe.py.)
-// OP_COMPRESS_DEST: `consumed` (the second per-block output) travels behind out[] in the metadata and comes back with the sizes
-int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
-               const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, int32_t* consumed, uint32_t b0, uint32_t b1, std::string* err) {
+// op_has_consumed: c.consumed (the second per-block output) travels behind out[] in the metadata and comes back with the sizes
+int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+               const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, uint32_t b0, uint32_t b1, std::string* err) {
   auto bad_to = [](std::string* where, const char* what, hipError_t e) {
     char buf[512];
     snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
@@ -480,7 +456,7 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
     const uint32_t nb = s.i1 - s.i0;
     const int32_t* hout = (const int32_t*)((const uint8_t*)s.h_meta.p + (size_t)nb * 24u);
     memcpy(out + s.i0, hout, (size_t)nb * 4u);
-    if (op == OP_COMPRESS_DEST) memcpy(consumed + s.i0, hout + nb, (size_t)nb * 4u);
+    if (op_has_consumed(c.op)) memcpy(c.consumed + s.i0, hout + nb, (size_t)nb * 4u);
     const uint8_t* hd = (const uint8_t*)s.h_dst.p;
     const uint32_t i0 = s.i0;
     if (s.packed) {   // the sizes are here: fetch exactly the useful bytes (already packed on the device), then hand them out
@@ -492,9 +468,10 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
       s.dst_bytes = (size_t)total;
     }
     add(t_d2h, now() - c0); c0 = now();
+    const bool fills = op_fills_capacity(c.op);
     par_blocks(s.i0, s.i1, s.dst_bytes, [=, &s](uint32_t i) {
       int64_t produced;   // (bytes past a result stay untouched in the caller's slot)
-      if (op == OP_DECODE_FAST) produced = out[i] > 0 ? dst_cap[i] : 0;
+      if (fills) produced = out[i] > 0 ? dst_cap[i] : 0;
       else produced = out[i] > 0 ? out[i] : 0;
       if (produced > 0) memcpy(dst + dst_off[i], hd + s.dof[i - i0], (size_t)produced);
     });
@@ -553,12 +530,12 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
     s.so.resize(nb); s.dof.resize(nb);
     { size_t so = 0, dofs = 0;
       for (uint32_t t = 0; t < nb; t++) { s.so[t] = so; s.dof[t] = dofs; so += (slen_of(i + t) + 15u) & ~(size_t)15u; dofs += (dcap_of(i + t) + 15u) & ~(size_t)15u; } }
-    const size_t nout = op == OP_COMPRESS_DEST ? 2u : 1u;   // out[] (and consumed[])
+    const size_t nout = op_has_consumed(c.op) ? 2u : 1u;   // out[] (and consumed[])
     const size_t meta = (size_t)nb * (24u + 4u * nout);   // so[nb] u64 | dof[nb] u64 | src_len[nb] | dst_cap[nb] | out[nb] | (consumed[nb])
     if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (e = s.h_dst.reserve(db + 64)) != hipSuccess || (e = s.h_meta.reserve(meta)) != hipSuccess ||
         (e = s.d_src.reserve(sb + 64)) != hipSuccess || (e = s.d_dst.reserve(db + 64)) != hipSuccess || (e = s.d_meta.reserve(meta)) != hipSuccess ||
-        (op == OP_COMPRESS_HC && (e = s.d_ws.reserve(lz4hip::hc_ws_bytes(sb, nb, level))) != hipSuccess) ||
-        ((op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST) && ((e = s.d_pack.reserve(db + 64)) != hipSuccess || (e = s.d_poff.reserve((size_t)nb * 8u)) != hipSuccess))) {
+        (op_uses_hc_ws(c.op) && (e = s.d_ws.reserve(lz4hip::hc_ws_bytes(sb, nb, c.param))) != hipSuccess) ||
+        (op_compresses(c.op) && ((e = s.d_pack.reserve(db + 64)) != hipSuccess || (e = s.d_poff.reserve((size_t)nb * 8u)) != hipSuccess))) {
       rc = bad("staging allocation", e);
       break;
     }
@@ -582,19 +559,13 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
     if (!single && ((e = hipEventRecord(s.ev_in, s.q_in)) != hipSuccess || (e = hipStreamWaitEvent(s.st, s.ev_in, 0)) != hipSuccess)) { rc = bad("H2D event", e); break; }
     lz4hip::BatchArgs a{(const uint8_t*)s.d_src.p, (const uint64_t*)dm, (const int32_t*)(dm + (size_t)nb * 16u), (uint8_t*)s.d_dst.p,
                         (const uint64_t*)(dm + (size_t)nb * 8u), (const int32_t*)(dm + (size_t)nb * 20u), (int32_t*)(dm + (size_t)nb * 24u), nb};
-    int le = 0;
-    switch (op) {
-      case OP_COMPRESS_FAST: le = launch_fast(a, s.st); break;
-      case OP_DECODE_SAFE: le = launch_decode(a, true, s.st); break;
-      case OP_DECODE_FAST: le = launch_decode(a, false, s.st); break;
-      case OP_COMPRESS_HC: le = lz4hip::launch_compress_hc(a, level, s.d_ws.p, sb, s.st); break;
-      case OP_COMPRESS_ACCEL: le = launch_accel(a, level, s.st); break;
-      case OP_COMPRESS_DEST: le = launch_dest(a, (int32_t*)(dm + (size_t)nb * 28u), s.st); break;
-      case OP_DECODE_PARTIAL: le = lz4hip::launch_decompress_partial(a, a.dst_cap, s.st); break;   // (dst_cap = partial_room: the target)
-    }
-    if (le == LZ4HIP_E_ARG) { *err = lz4hip_last_error(); rc = le; break; }   // (a decode knob combination without a kernel: launch_decode has said which, on this thread)
+    BlockCall dc = c;   // the call on this chunk's device arrays
+    if (op_has_consumed(c.op)) dc.consumed = (int32_t*)(dm + (size_t)nb * 28u);
+    if (op_uses_hc_ws(c.op)) { dc.hc_ws = s.d_ws.p; dc.hc_span = sb; }
+    int le = launch_block(dc, a, s.st);
+    if (le < 0) { *err = lz4hip_last_error(); rc = le; break; }   // (a decode knob combination without a kernel: launch_decode has said which, on this thread)
     if (le) { rc = bad("kernel launch", (hipError_t)le); break; }
-    s.packed = (op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST);
+    s.packed = op_compresses(c.op);
     // the sizes travel first; compress ops: the finisher fetches exactly the packed bytes once it has them
     if (!single && ((e = hipEventRecord(s.ev_k, s.st)) != hipSuccess || (e = hipStreamWaitEvent(s.q_out, s.ev_k, 0)) != hipSuccess)) { rc = bad("kernel event", e); break; }
     if ((e = hipMemcpyAsync(hm + (size_t)nb * 24u, dm + (size_t)nb * 24u, (size_t)nb * 4u * nout, hipMemcpyDeviceToHost, s.q_out)) != hipSuccess) { rc = bad("D2H out", e); break; }
@@ -630,33 +601,30 @@ int host_shard(Op op, int level, int ord, const uint8_t* src, const uint64_t* sr
   }
   if (prof)
     fprintf(stderr, "[lz4hip host_shard op %d, %u blocks] total %.1f ms: loop %.1f (reap %.1f | alloc %.1f | pack %.1f | enqueue %.1f), drain %.1f; finishers: wait %.1f + d2h %.1f + unpack %.1f\n",
-            (int)op, b1 - b0, 1e3 * (now() - t_begin), 1e3 * t_loop, 1e3 * t_reap, 1e3 * t_alloc, 1e3 * t_pack, 1e3 * t_enq,
+            (int)c.op, b1 - b0, 1e3 * (now() - t_begin), 1e3 * t_loop, 1e3 * t_reap, 1e3 * t_alloc, 1e3 * t_pack, 1e3 * t_enq,
             1e3 * (now() - t_begin - t_loop), 1e3 * t_wait.load(), 1e3 * t_d2h.load(), 1e3 * t_unpack.load());
   return rc;
 }
 
-int host_batch(Op op, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
-               const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, uint32_t n, int level = 0, int32_t* consumed = nullptr) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (n == 0) return LZ4HIP_OK;
-  if (!src || !src_off || !src_len || !dst || !dst_off || !dst_cap || !out || (op == OP_COMPRESS_DEST && !consumed))
-    return fail(LZ4HIP_E_ARG, "null pointer argument");
+// A host batch over the initialised devices: contiguous block ranges per device, a thread per device, the
+// caller's current device restored, the first error reported.  Batches of fewer than 2 x per_device blocks stay on one device.
+// shard(ordinal, b0, b1, &error text) does one device's share.
+template <class Shard>
+int fan_out(uint32_t n, uint32_t per_device, Shard shard) {
   std::vector<int> devs;
   { std::lock_guard<std::mutex> lk(g_mu); devs = g_devs; }
   int prev = -1;
   (void)hipGetDevice(&prev);
-  // contiguous block ranges per device; small batches stay on one device
-  const uint32_t D = (uint32_t)std::min<size_t>(devs.size(), std::max<uint32_t>(1u, n / 64u));
+  const uint32_t D = (uint32_t)std::min<size_t>(devs.size(), std::max<uint32_t>(1u, n / per_device));
   std::vector<int> rcs(D, 0);
   std::vector<std::string> errs(D);
   if (D == 1) {
-    rcs[0] = host_shard(op, level, devs[0], src, src_off, src_len, dst, dst_off, dst_cap, out, consumed, 0, n, &errs[0]);
+    rcs[0] = shard(devs[0], 0u, n, &errs[0]);
   } else {
     std::vector<std::thread> th;
     for (uint32_t d = 0; d < D; d++) {
       const uint32_t b0 = (uint32_t)((uint64_t)n * d / D), b1 = (uint32_t)((uint64_t)n * (d + 1) / D);
-      th.emplace_back([&, d, b0, b1] { rcs[d] = host_shard(op, level, devs[d], src, src_off, src_len, dst, dst_off, dst_cap, out, consumed, b0, b1, &errs[d]); });
+      th.emplace_back([&, d, b0, b1] { rcs[d] = shard(devs[d], b0, b1, &errs[d]); });
     }
     for (auto& t : th) t.join();
   }
@@ -664,6 +632,18 @@ int host_batch(Op op, const uint8_t* src, const uint64_t* src_off, const int32_t
   for (uint32_t d = 0; d < D; d++)
     if (rcs[d]) return fail(rcs[d], errs[d].c_str());
   return LZ4HIP_OK;
+}
+
+int host_batch(const BlockCall& c, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+               const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, uint32_t n) {
+  int rc = ensure_init();
+  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (n == 0) return LZ4HIP_OK;
+  if (!src || !src_off || !src_len || !dst || !dst_off || !dst_cap || !out || (op_has_consumed(c.op) && !c.consumed))
+    return fail(LZ4HIP_E_ARG, kNullArg);
+  return fan_out(n, 64u, [&](int ord, uint32_t b0, uint32_t b1, std::string* err) {
+    return host_shard(c, ord, src, src_off, src_len, dst, dst_off, dst_cap, out, b0, b1, err);
+  });
 }
 
 // hashes of one device's share [b0, b1) of a host batch: the same pinned, double-buffered staging as host_shard (chunks of
@@ -743,29 +723,10 @@ int host_xxh(bool is64, const uint8_t* buf, const uint64_t* off, const int32_t* 
   int rc = ensure_init();
   if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
   if (n == 0) return LZ4HIP_OK;
-  if (!buf || !off || !len || !out) return fail(LZ4HIP_E_ARG, "null pointer argument");
-  std::vector<int> devs;
-  { std::lock_guard<std::mutex> lk(g_mu); devs = g_devs; }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  // contiguous ranges per device, like the LZ4 batches; small batches stay on one device
-  const uint32_t D = (uint32_t)std::min<size_t>(devs.size(), std::max<uint32_t>(1u, n / 1024u));
-  std::vector<int> rcs(D, 0);
-  std::vector<std::string> errs(D);
-  if (D == 1) {
-    rcs[0] = xxh_shard<T>(is64, devs[0], buf, off, len, seed, out, 0, n, &errs[0]);
-  } else {
-    std::vector<std::thread> th;
-    for (uint32_t d = 0; d < D; d++) {
-      const uint32_t b0 = (uint32_t)((uint64_t)n * d / D), b1 = (uint32_t)((uint64_t)n * (d + 1) / D);
-      th.emplace_back([&, d, b0, b1] { rcs[d] = xxh_shard<T>(is64, devs[d], buf, off, len, seed, out, b0, b1, &errs[d]); });
-    }
-    for (auto& t : th) t.join();
-  }
-  if (prev >= 0) (void)hipSetDevice(prev);
-  for (uint32_t d = 0; d < D; d++)
-    if (rcs[d]) return fail(rcs[d], errs[d].c_str());
-  return LZ4HIP_OK;
+  if (!buf || !off || !len || !out) return fail(LZ4HIP_E_ARG, kNullArg);
+  return fan_out(n, 1024u, [&](int ord, uint32_t b0, uint32_t b1, std::string* err) {
+    return xxh_shard<T>(is64, ord, buf, off, len, seed, out, b0, b1, err);
+  });
 }
 
 // ---- single-block calls: coalesced ---------------------------------------------------------------------------------------
@@ -777,7 +738,7 @@ int host_xxh(bool is64, const uint8_t* buf, const uint64_t* off, const int32_t* 
 struct Req {
   const uint8_t* src; int32_t len; uint8_t* dst; int32_t cap;
   int32_t out = 0; int rc = 0; bool done = false; std::string err;
-  int32_t consumed = 0;   // (OP_COMPRESS_DEST)
+  int32_t consumed = 0;   // (op_has_consumed)
 };
 struct Combiner {
   std::mutex mu;
@@ -785,21 +746,25 @@ struct Combiner {
   std::vector<Req*> q;
   bool leader = false;
 };
-Combiner g_comb[4][13];   // [op][HC level]
-// accelerated compress: one combiner per (clamped) acceleration, so calls with different values never share a launch; created on first
-// use and kept (at most 65536 of them)
+// Calls are coalesced only with calls of the same operation, HC level and acceleration: one combiner per operation, HC's per level,
+// accelerated compress's per (clamped) acceleration -- created on first use and kept (at most 65536 of them)
+Combiner g_comb[OP_COUNT];
+Combiner g_hc_comb[13];   // [HC level]
 std::mutex g_accel_comb_mu;
 std::map<int, Combiner> g_accel_comb;
-Combiner& accel_combiner(int accel) {
-  std::lock_guard<std::mutex> lk(g_accel_comb_mu);
-  return g_accel_comb[accel];   // (std::map: references stay valid while other entries are added)
+// nullptr: no combiner for this call (an operation or level outside the tables); may throw (the map's allocation)
+Combiner* combiner_for(const BlockCall& c) {
+  if (c.op == OP_COMPRESS_ACCEL) {
+    std::lock_guard<std::mutex> lk(g_accel_comb_mu);
+    return &g_accel_comb[c.param];   // (std::map: references stay valid while other entries are added)
+  }
+  if (c.op == OP_COMPRESS_HC) return c.param >= 1 && c.param <= 12 ? &g_hc_comb[c.param] : nullptr;
+  return (int)c.op >= 0 && (int)c.op < OP_COUNT ? &g_comb[c.op] : nullptr;
 }
-Combiner g_dest_comb;   // LZ4_compress_destSize: coalesced only with other destSize calls
-Combiner g_partial_comb;   // LZ4_decompress_safe_partial: coalesced only with other partial decodes (the request's cap = partial_room)
 
 // one host batch for all of `batch`; returns its rc (every request gets its out[]); may throw (allocation of the index vectors,
 // thread creation inside host_batch)
-int run_batch_once(Op op, int level, const std::vector<Req*>& batch) {
+int run_batch_once(const BlockCall& c, const std::vector<Req*>& batch) {
   static uint8_t dummy_in = 0, dummy_out = 0;
   const uint32_t n = (uint32_t)batch.size();
   const uint8_t* sbase = nullptr; uint8_t* dbase = nullptr;
@@ -810,12 +775,14 @@ int run_batch_once(Op op, int level, const std::vector<Req*>& batch) {
     if (!dbase || r->dst < dbase) dbase = r->dst;
   }
   std::vector<uint64_t> so(n), dof(n);
-  std::vector<int32_t> sl(n), dc(n), out(n, 0), cons(op == OP_COMPRESS_DEST ? n : 0u, 0);
+  std::vector<int32_t> sl(n), dc(n), out(n, 0), cons(op_has_consumed(c.op) ? n : 0u, 0);
   for (uint32_t i = 0; i < n; i++) { so[i] = (uint64_t)(batch[i]->src - sbase); dof[i] = (uint64_t)(batch[i]->dst - dbase); sl[i] = batch[i]->len; dc[i] = batch[i]->cap; }
-  const int rc = host_batch(op, sbase, so.data(), sl.data(), dbase, dof.data(), dc.data(), out.data(), n, level, cons.data());
+  BlockCall bc = c;   // (the leader's call: the batch's consumed sizes go to the requests, not to the leader's caller)
+  bc.consumed = cons.data();
+  const int rc = host_batch(bc, sbase, so.data(), sl.data(), dbase, dof.data(), dc.data(), out.data(), n);
   for (uint32_t i = 0; i < n; i++) {
     batch[i]->rc = rc; batch[i]->out = out[i]; if (rc) batch[i]->err = g_err;
-    if (op == OP_COMPRESS_DEST) batch[i]->consumed = cons[i];
+    if (op_has_consumed(c.op)) batch[i]->consumed = cons[i];
   }
   return rc;
 }
@@ -824,47 +791,48 @@ int run_batch_once(Op op, int level, const std::vector<Req*>& batch) {
 // caller's huge block, a HIP error) every request is run again on its own, so only the caller whose request is the cause sees
 // the failure.  Exceptions (bad_alloc of the index vectors, system_error from thread creation) become LZ4HIP_E_NOMEM for the
 // requests concerned; nothing propagates into the leader's bookkeeping.
-void run_combined(Op op, int level, std::vector<Req*>& batch) noexcept {
+void run_combined(const BlockCall& c, std::vector<Req*>& batch) noexcept {
   int rc;
-  try { rc = run_batch_once(op, level, batch); }
+  try { rc = run_batch_once(c, batch); }
   catch (...) { rc = LZ4HIP_E_NOMEM; for (Req* r : batch) { r->rc = rc; r->out = 0; r->err = "out of memory while combining single-block calls"; } }
   if (rc == 0 || batch.size() < 2) return;
   for (Req* r : batch) {
     std::vector<Req*> one;
-    try { one.push_back(r); (void)run_batch_once(op, level, one); }
+    try { one.push_back(r); (void)run_batch_once(c, one); }
     catch (...) { r->rc = LZ4HIP_E_NOMEM; r->out = 0; r->err = "out of memory"; }
   }
 }
 
-// consumed: OP_COMPRESS_DEST's input consumed (written only on success)
-int single(Op op, const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level = 0, int32_t* consumed = nullptr) {
+// c.consumed: where this caller's consumed size goes (op_has_consumed; written only on success)
+int single(const BlockCall& c, const uint8_t* src, int src_len, uint8_t* dst, int dst_cap) {
   Req r{src, src_len, dst, dst_cap};
   Combiner* cp;
-  try { cp = op == OP_COMPRESS_ACCEL ? &accel_combiner(level) : op == OP_COMPRESS_DEST ? &g_dest_comb : op == OP_DECODE_PARTIAL ? &g_partial_comb : &g_comb[(int)op][level < 0 || level > 12 ? 0 : level]; }
+  try { cp = combiner_for(c); }
   catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
-  Combiner& c = *cp;
+  if (!cp) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, "no combiner for this operation"));
+  Combiner& cb = *cp;
   {
-    std::unique_lock<std::mutex> lk(c.mu);
-    try { c.q.push_back(&r); }
+    std::unique_lock<std::mutex> lk(cb.mu);
+    try { cb.q.push_back(&r); }
     catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
     while (!r.done) {
-      if (!c.leader) {
-        c.leader = true;
+      if (!cb.leader) {
+        cb.leader = true;
         std::vector<Req*> batch;
-        batch.swap(c.q);          // (contains r: only a leader takes requests out of the queue; swap does not throw)
+        batch.swap(cb.q);          // (contains r: only a leader takes requests out of the queue; swap does not throw)
         lk.unlock();
-        run_combined(op, level, batch);   // noexcept: the leader always comes back to hand the results out
+        run_combined(c, batch);   // noexcept: the leader always comes back to hand the results out
         lk.lock();
         for (Req* x : batch) x->done = true;
-        c.leader = false;
-        c.cv.notify_all();
+        cb.leader = false;
+        cb.cv.notify_all();
       } else {
-        c.cv.wait(lk);
+        cb.cv.wait(lk);
       }
     }
   }
   if (r.rc) { g_err = r.err; return LZ4HIP_LIB_ERROR(r.rc); }
-  if (consumed) *consumed = r.consumed;
+  if (c.consumed) *c.consumed = r.consumed;
   return r.out;
 }
 
@@ -888,7 +856,7 @@ uint32_t max_cu_count() {
   cached.store(v, std::memory_order_relaxed);
   return v;
 }
-// cus: the CU count the launch will use (cu_count() under the DeviceGuard of the launch device) or max_cu_count() for a query
+// cus: the CU count the launch will use (device_cus() under the DeviceGuard of the launch device) or max_cu_count() for a query
 ContainerPlan container_plan(uint64_t n_bytes, uint32_t block_size, int hc_lv, uint32_t cus) {
   ContainerPlan p{};
   p.n = (uint32_t)((n_bytes + block_size - 1u) / block_size);
@@ -906,6 +874,15 @@ int container_args(int kind, uint64_t n_bytes, uint32_t block_size, int level, i
   if (level != 0 && hc_level(level, hc_lv)) return fail(LZ4HIP_E_UNSUPPORTED, "unsupported compression level");
   return 0;
 }
+// the launch both container entries make: `ws` = p.total bytes of device scratch, cut up as container_plan says; the launch device is current
+int launch_container(int kind, int flags, int hc_lv, const uint8_t* src, uint64_t n_bytes, uint32_t block_size, uint8_t* dst, uint64_t dst_cap,
+                     uint64_t* total_dev, void* ws, const ContainerPlan& p, void* stream) {
+  uint8_t* w = (uint8_t*)(((uintptr_t)ws + 255u) & ~(uintptr_t)255u);
+  return lz4hip::launch_container_blocks(kind, flags & 1, hc_lv, src, n_bytes, block_size, dst, dst_cap, (unsigned long long*)total_dev, w,
+                                         p.hcws ? w + p.cws : nullptr, (uint32_t*)(w + p.cws + p.hcws),
+                                         64u * (uint32_t)g_compress_switch.load(std::memory_order_relaxed), lz4hip::device_cus(),
+                                         g_compress_core.load(std::memory_order_relaxed), stream);
+}
 }  // namespace
 
 extern "C" {
@@ -920,22 +897,15 @@ size_t lz4hip_container_workspace_bytes(uint64_t n_bytes, uint32_t block_size, i
 int lz4hip_container_blocks_dev(int kind, int flags, int level, const uint8_t* src, uint64_t n_bytes, uint32_t block_size, uint8_t* dst, uint64_t dst_cap,
                                 uint64_t* total_dev, void* ws, size_t ws_bytes, int device, void* stream) {
   int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");   // (the answer without a device, whatever the arguments)
   int lv;
   if ((rc = container_args(kind, n_bytes, block_size, level, &lv)) != 0) return rc;
-  if ((n_bytes && !src) || !dst || !total_dev || !ws) return fail(LZ4HIP_E_ARG, "null pointer argument");
-  int ord;
-  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
-  DeviceGuard g(ord);   // (before the plan: its ring words are a function of the LAUNCH device's CU count)
-  const ContainerPlan p = container_plan(n_bytes, block_size, lv, cu_count());
-  if (ws_bytes < p.total) return fail(LZ4HIP_E_ARG, "container workspace too small (lz4hip_container_workspace_bytes)");
-  uint8_t* w = (uint8_t*)(((uintptr_t)ws + 255u) & ~(uintptr_t)255u);
-  const int e = lz4hip::launch_container_blocks(kind, flags & 1, lv, src, n_bytes, block_size, dst, dst_cap, (unsigned long long*)total_dev, w,
-                                                p.hcws ? w + p.cws : nullptr, (uint32_t*)(w + p.cws + p.hcws),
-                                                64u * (uint32_t)g_compress_switch.load(std::memory_order_relaxed), cu_count(),
-                                                g_compress_core.load(std::memory_order_relaxed), stream);
-  if (e) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
-  return LZ4HIP_OK;
+  return on_device(device, false, (n_bytes && !src) || !dst || !total_dev || !ws ? kNullArg : nullptr, [&] {
+    // (on the launch device: the plan's ring words are a function of ITS CU count)
+    const ContainerPlan p = container_plan(n_bytes, block_size, lv, lz4hip::device_cus());
+    if (ws_bytes < p.total) return fail(LZ4HIP_E_ARG, "container workspace too small (lz4hip_container_workspace_bytes)");
+    return launch_container(kind, flags, lv, src, n_bytes, block_size, dst, dst_cap, total_dev, ws, p, stream);
+  });
 }
 int lz4hip_container_blocks(int kind, int flags, int level, const uint8_t* src, uint64_t n_bytes, uint32_t block_size, uint8_t* dst, uint64_t dst_cap,
                             uint64_t* out_bytes) {
@@ -943,13 +913,13 @@ int lz4hip_container_blocks(int kind, int flags, int level, const uint8_t* src, 
   if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
   int lv;
   if ((rc = container_args(kind, n_bytes, block_size, level, &lv)) != 0) return rc;
-  if ((n_bytes && !src) || !dst || !out_bytes) return fail(LZ4HIP_E_ARG, "null pointer argument");
+  if ((n_bytes && !src) || !dst || !out_bytes) return fail(LZ4HIP_E_ARG, kNullArg);
   *out_bytes = 0;
   if (n_bytes == 0) return LZ4HIP_OK;
   int ord;
   if (ordinal(0, &ord)) return fail(LZ4HIP_E_NO_DEVICE, "no device");
   DeviceGuard g(ord);
-  const ContainerPlan p = container_plan(n_bytes, block_size, lv, cu_count());
+  const ContainerPlan p = container_plan(n_bytes, block_size, lv, lz4hip::device_cus());
   const uint64_t worst = n_bytes + (uint64_t)p.n * (kind == 0 ? 8u : 21u);
   hipStream_t st = nullptr;
   uint8_t *d_src = nullptr, *d_dst = nullptr, *d_ws = nullptr;
@@ -968,11 +938,7 @@ int lz4hip_container_blocks(int kind, int flags, int level, const uint8_t* src, 
       (he = hipMallocAsync((void**)&d_ws, p.total, st)) != hipSuccess || (he = hipMallocAsync((void**)&d_total, 8, st)) != hipSuccess)
     return done(fail(he == hipErrorOutOfMemory ? LZ4HIP_E_NOMEM : LZ4HIP_E_HIP, "device allocation", he));
   if ((he = hipMemcpyAsync(d_src, src, n_bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return done(fail(LZ4HIP_E_HIP, "H2D", he));
-  uint8_t* w = (uint8_t*)(((uintptr_t)d_ws + 255u) & ~(uintptr_t)255u);
-  const int e = lz4hip::launch_container_blocks(kind, flags & 1, lv, d_src, n_bytes, block_size, d_dst, worst, (unsigned long long*)d_total, w,
-                                                p.hcws ? w + p.cws : nullptr, (uint32_t*)(w + p.cws + p.hcws),
-                                                64u * (uint32_t)g_compress_switch.load(std::memory_order_relaxed), cu_count(),
-                                                g_compress_core.load(std::memory_order_relaxed), st);
+  const int e = launch_container(kind, flags, lv, d_src, n_bytes, block_size, d_dst, worst, d_total, d_ws, p, st);
   if (e) return done(fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e));
   uint64_t total = 0;
   if ((he = hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st)) != hipSuccess || (he = hipStreamSynchronize(st)) != hipSuccess)
@@ -986,22 +952,19 @@ int lz4hip_container_blocks(int kind, int flags, int level, const uint8_t* src, 
 size_t lz4hip_container_decode_workspace_bytes(uint32_t n_max) { return lz4hip::container_read_ws_bytes(n_max) + 256u; }
 int lz4hip_container_decode_dev(int kind, int flags, const uint8_t* body, uint64_t body_bytes, uint32_t max_block, uint8_t* dst, uint64_t slot_bytes,
                                 uint32_t n_max, int32_t* sizes_dev, uint64_t* info_dev, void* ws, size_t ws_bytes, int device, void* stream) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (kind != 0 && kind != 1) return fail(LZ4HIP_E_ARG, "container kind must be 0 (LZ4 Frame blocks) or 1 (LZ4Block blocks)");
-  if ((body_bytes && !body) || !dst || !sizes_dev || !info_dev || !ws) return fail(LZ4HIP_E_ARG, "null pointer argument");
-  if (n_max == 0 || n_max > 0x7FFFFFFFu) return fail(LZ4HIP_E_ARG, "n_max must be 1 .. 2^31 - 1");
-  if (slot_bytes == 0 || slot_bytes > 0x7FFFFFFFull || (kind == 0 && (max_block == 0 || slot_bytes < max_block)))
-    return fail(LZ4HIP_E_ARG, "slot_bytes must be 1 .. 2^31 - 1 and, for frame blocks, at least the frame's block maximum size");
-  if (ws_bytes < lz4hip_container_decode_workspace_bytes(n_max)) return fail(LZ4HIP_E_ARG, "workspace too small (lz4hip_container_decode_workspace_bytes)");
-  int ord;
-  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
-  DeviceGuard g(ord);
-  uint8_t* w = (uint8_t*)(((uintptr_t)ws + 255u) & ~(uintptr_t)255u);
-  const int e = lz4hip::launch_container_read(kind, flags & 1, body, body_bytes, max_block, dst, slot_bytes, n_max, sizes_dev,
-                                              (unsigned long long*)info_dev, w, stream);
-  if (e) return fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e);
-  return LZ4HIP_OK;
+  const char* arg_error =
+      (kind != 0 && kind != 1) ? "container kind must be 0 (LZ4 Frame blocks) or 1 (LZ4Block blocks)"
+      : ((body_bytes && !body) || !dst || !sizes_dev || !info_dev || !ws) ? kNullArg
+      : (n_max == 0 || n_max > 0x7FFFFFFFu) ? "n_max must be 1 .. 2^31 - 1"
+      : (slot_bytes == 0 || slot_bytes > 0x7FFFFFFFull || (kind == 0 && (max_block == 0 || slot_bytes < max_block)))
+          ? "slot_bytes must be 1 .. 2^31 - 1 and, for frame blocks, at least the frame's block maximum size"
+      : ws_bytes < lz4hip_container_decode_workspace_bytes(n_max) ? "workspace too small (lz4hip_container_decode_workspace_bytes)"
+      : nullptr;
+  return on_device(device, false, arg_error, [&] {
+    uint8_t* w = (uint8_t*)(((uintptr_t)ws + 255u) & ~(uintptr_t)255u);
+    return lz4hip::launch_container_read(kind, flags & 1, body, body_bytes, max_block, dst, slot_bytes, n_max, sizes_dev,
+                                         (unsigned long long*)info_dev, w, stream);
+  });
 }
 // Host-side walk of the size words / headers of a container body IN HOST MEMORY (no device work, no decoding): how many whole blocks
 // of the first n_max the body holds, how many bytes their decoded forms can need at most (frame: max_block per compressed block, the
@@ -1051,7 +1014,7 @@ static void container_prewalk(int kind, int flags, const uint8_t* body, uint64_t
 int lz4hip_container_decode_bound(int kind, int flags, const uint8_t* body, uint64_t body_bytes, uint32_t max_block, uint32_t n_max,
                                   uint32_t* n_blocks, uint64_t* dst_bytes) {
   if (kind != 0 && kind != 1) return fail(LZ4HIP_E_ARG, "container kind must be 0 (LZ4 Frame blocks) or 1 (LZ4Block blocks)");
-  if ((body_bytes && !body) || !n_blocks || !dst_bytes) return fail(LZ4HIP_E_ARG, "null pointer argument");
+  if ((body_bytes && !body) || !n_blocks || !dst_bytes) return fail(LZ4HIP_E_ARG, kNullArg);
   if (n_max == 0 || n_max > 0x7FFFFFFFu || max_block == 0 || max_block > 0x7FFFFFFFu) return fail(LZ4HIP_E_ARG, "n_max and max_block must be 1 .. 2^31 - 1");
   uint64_t smax = 0;
   container_prewalk(kind, flags, body, body_bytes, max_block, n_max, n_blocks, dst_bytes, &smax);
@@ -1063,7 +1026,7 @@ int lz4hip_container_decode(int kind, int flags, const uint8_t* body, uint64_t b
   int rc = ensure_init();
   if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
   if (kind != 0 && kind != 1) return fail(LZ4HIP_E_ARG, "container kind must be 0 (LZ4 Frame blocks) or 1 (LZ4Block blocks)");
-  if ((body_bytes && !body) || !sizes || !info || (dst_cap && !dst)) return fail(LZ4HIP_E_ARG, "null pointer argument");
+  if ((body_bytes && !body) || !sizes || !info || (dst_cap && !dst)) return fail(LZ4HIP_E_ARG, kNullArg);
   if (n_max == 0 || n_max > 0x7FFFFFFFu || max_block == 0 || max_block > 0x7FFFFFFFu) return fail(LZ4HIP_E_ARG, "n_max and max_block must be 1 .. 2^31 - 1");
   for (int i = 0; i < 5; i++) info[i] = 0;
   int ord;
@@ -1153,7 +1116,7 @@ constexpr size_t XXH_STAGE_MAX = 64u << 20;
 int xxh_stream_create(bool is64, uint64_t seed, lz4hip_xxh_stream** out) {
   int rc = ensure_init();
   if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (!out) return fail(LZ4HIP_E_ARG, "null pointer argument");
+  if (!out) return fail(LZ4HIP_E_ARG, kNullArg);
   int ord;
   if (ordinal(0, &ord)) return fail(LZ4HIP_E_NO_DEVICE, "no device");
   DeviceGuard g(ord);
@@ -1252,15 +1215,10 @@ extern "C" {
 __attribute__((visibility("default"))) int lz4hip_dbg_ring_stats(unsigned long long* out8) { return lz4hip::ring_stats_fetch(out8); }
 #endif
 int lz4hip_last_decode_route(int device, uint32_t* out6) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (!out6) return fail(LZ4HIP_E_ARG, "null pointer argument");
-  int ord;
-  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
-  DeviceGuard g(ord);
-  const int e = lz4hip::last_decode_route(out6);
-  if (e) return fail(LZ4HIP_E_HIP, "hipMemcpyFromSymbol", (hipError_t)e);
-  return LZ4HIP_OK;
+  return on_device(device, false, out6 ? nullptr : kNullArg, [&] {
+    const int e = lz4hip::last_decode_route(out6);
+    return e ? fail(LZ4HIP_E_HIP, "hipMemcpyFromSymbol", (hipError_t)e) : 0;
+  });
 }
 int lz4hip_set_option(const char* name, int value) {
   if (name && strcmp(name, "decode_stage") == 0) {
@@ -1315,17 +1273,17 @@ int lz4hip_compress_bound(int n) {
 // ---- host-pointer batch API ----
 int lz4hip_compress_fast_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n) {
-  return host_batch(OP_COMPRESS_FAST, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
+  return host_batch({OP_COMPRESS_FAST}, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
 }
 int lz4hip_compress_fast_accel_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                      const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int acceleration) {
   const int a = accel_clamp(acceleration);
   if (a == 1) return lz4hip_compress_fast_batch(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
-  return host_batch(OP_COMPRESS_ACCEL, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, a);
+  return host_batch({OP_COMPRESS_ACCEL, a}, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
 }
 int lz4hip_compress_dest_size_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                     const uint64_t* dst_off, const int32_t* target_size, int32_t* out_len, int32_t* src_consumed, uint32_t n) {
-  return host_batch(OP_COMPRESS_DEST, src, src_off, src_len, dst, dst_off, target_size, out_len, n, 0, src_consumed);
+  return host_batch({OP_COMPRESS_DEST, 0, nullptr, src_consumed}, src, src_off, src_len, dst, dst_off, target_size, out_len, n);
 }
 int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                          const uint64_t* dst_off, const int32_t* target_len, const int32_t* dst_cap, int32_t* out_len,
@@ -1333,25 +1291,25 @@ int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src
   int rc = ensure_init();
   if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
   if (n == 0) return LZ4HIP_OK;
-  if (!target_len || !dst_cap) return fail(LZ4HIP_E_ARG, "null pointer argument");
+  if (!target_len || !dst_cap) return fail(LZ4HIP_E_ARG, kNullArg);
   std::vector<int32_t> room;
   try { room.resize(n); } catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
   for (uint32_t i = 0; i < n; i++) room[i] = partial_room(target_len[i], dst_cap[i]);
-  return host_batch(OP_DECODE_PARTIAL, src, src_off, src_len, dst, dst_off, room.data(), out_len, n);
+  return host_batch({OP_DECODE_PARTIAL}, src, src_off, src_len, dst, dst_off, room.data(), out_len, n);
 }
 int lz4hip_decompress_safe_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                  const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n) {
-  return host_batch(OP_DECODE_SAFE, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
+  return host_batch({OP_DECODE_SAFE}, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
 }
 int lz4hip_decompress_fast_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_cap, uint8_t* dst,
                                  const uint64_t* dst_off, const int32_t* dst_len, int32_t* out_consumed, uint32_t n) {
-  return host_batch(OP_DECODE_FAST, src, src_off, src_cap, dst, dst_off, dst_len, out_consumed, n);
+  return host_batch({OP_DECODE_FAST}, src, src_off, src_cap, dst, dst_off, dst_len, out_consumed, n);
 }
 int lz4hip_compress_hc_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                              const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int level) {
   int lv;
   if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
-  return host_batch(OP_COMPRESS_HC, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, lv);
+  return host_batch({OP_COMPRESS_HC, lv}, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
 }
 int lz4hip_xxh32_batch(const uint8_t* buf, const uint64_t* off, const int32_t* len, uint32_t seed, uint32_t* out, uint32_t n) {
   return host_xxh<uint32_t>(false, buf, off, len, seed, out, n);
@@ -1363,32 +1321,33 @@ int lz4hip_xxh64_batch(const uint8_t* buf, const uint64_t* off, const int32_t* l
 // ---- device-pointer batch API ----
 int lz4hip_compress_fast_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                    const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int device, void* stream) {
-  return dev_batch(OP_COMPRESS_FAST, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, device, stream);
+  return dev_batch({OP_COMPRESS_FAST}, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream);
 }
 int lz4hip_compress_fast_accel_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                          const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int acceleration,
                                          int device, void* stream) {
   const int a = accel_clamp(acceleration);
   if (a == 1) return lz4hip_compress_fast_batch_dev(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, device, stream);
-  return dev_batch(OP_COMPRESS_ACCEL, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, device, stream, a);
+  return dev_batch({OP_COMPRESS_ACCEL, a}, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream);
 }
 int lz4hip_compress_dest_size_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                         const uint64_t* dst_off, const int32_t* target_size, int32_t* out_len, int32_t* src_consumed,
                                         uint32_t n, int device, void* stream) {
-  return dev_dest_batch(src, src_off, src_len, dst, dst_off, target_size, out_len, src_consumed, n, device, stream);
+  return dev_batch({OP_COMPRESS_DEST, 0, nullptr, src_consumed}, {src, src_off, src_len, dst, dst_off, target_size, out_len, n}, device, stream);
 }
 int lz4hip_decompress_safe_partial_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                              const uint64_t* dst_off, const int32_t* target_len, const int32_t* dst_cap, int32_t* out_len,
                                              uint32_t n, int device, void* stream) {
-  return dev_partial_batch(src, src_off, src_len, dst, dst_off, target_len, dst_cap, out_len, n, device, stream);
+  return dev_batch({OP_DECODE_PARTIAL, 0, target_len}, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream,
+                   target_len ? nullptr : kNullArg);
 }
 int lz4hip_decompress_safe_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                      const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int device, void* stream) {
-  return dev_batch(OP_DECODE_SAFE, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, device, stream);
+  return dev_batch({OP_DECODE_SAFE}, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream);
 }
 int lz4hip_decompress_fast_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_cap, uint8_t* dst,
                                      const uint64_t* dst_off, const int32_t* dst_len, int32_t* out_consumed, uint32_t n, int device, void* stream) {
-  return dev_batch(OP_DECODE_FAST, src, src_off, src_cap, dst, dst_off, dst_len, out_consumed, n, device, stream);
+  return dev_batch({OP_DECODE_FAST}, {src, src_off, src_cap, dst, dst_off, dst_len, out_consumed, n}, device, stream);
 }
 size_t lz4hip_hc_workspace_bytes(uint64_t src_span, uint32_t n_blocks, int level) {
   int lv;
@@ -1400,46 +1359,22 @@ int lz4hip_compress_hc_batch_dev_ws(const uint8_t* src, const uint64_t* src_off,
                                     uint64_t src_span, void* ws, size_t ws_bytes) {
   int lv;
   if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (n == 0) return LZ4HIP_OK;
-  if (!src || !src_off || !src_len || !dst || !dst_off || !dst_cap || !out_len || !ws) return fail(LZ4HIP_E_ARG, "null pointer argument");
-  if (ws_bytes < lz4hip::hc_ws_bytes(src_span, n, lv)) return fail(LZ4HIP_E_ARG, "HC workspace too small for the source span");
-  int ord;
-  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
-  DeviceGuard g(ord);
-  if (!g.ok) return fail(LZ4HIP_E_HIP, "hipSetDevice failed");
-  lz4hip::BatchArgs a{src, src_off, src_len, dst, dst_off, dst_cap, out_len, n};
-  const int e = lz4hip::launch_compress_hc(a, lv, ws, src_span, (hipStream_t)stream);
-  return e ? fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e) : LZ4HIP_OK;
+  return dev_batch({OP_COMPRESS_HC, lv, nullptr, nullptr, ws, src_span}, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream,
+                   !ws ? kNullArg : ws_bytes < lz4hip::hc_ws_bytes(src_span, n, lv) ? "HC workspace too small for the source span" : nullptr);
 }
 int lz4hip_compress_hc_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                  const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int level, int device, void* stream) {
   int lv;
   if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
-  return dev_batch(OP_COMPRESS_HC, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, device, stream, lv);
+  return dev_batch({OP_COMPRESS_HC, lv}, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream);
 }
 int lz4hip_xxh32_batch_dev(const uint8_t* buf, const uint64_t* off, const int32_t* len, uint32_t seed, uint32_t* out, uint32_t n, int device, void* stream) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (n == 0) return LZ4HIP_OK;
-  if (!buf || !off || !len || !out) return fail(LZ4HIP_E_ARG, "null pointer argument");
-  int ord;
-  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
-  DeviceGuard g(ord);
-  int e = lz4hip::launch_xxh32(buf, off, len, seed, out, n, stream);
-  return e ? fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e) : LZ4HIP_OK;
+  return on_device(device, n == 0, !buf || !off || !len || !out ? kNullArg : nullptr,
+                   [&] { return lz4hip::launch_xxh32(buf, off, len, seed, out, n, stream); });
 }
 int lz4hip_xxh64_batch_dev(const uint8_t* buf, const uint64_t* off, const int32_t* len, uint64_t seed, uint64_t* out, uint32_t n, int device, void* stream) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (n == 0) return LZ4HIP_OK;
-  if (!buf || !off || !len || !out) return fail(LZ4HIP_E_ARG, "null pointer argument");
-  int ord;
-  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
-  DeviceGuard g(ord);
-  int e = lz4hip::launch_xxh64(buf, off, len, seed, out, n, stream);
-  return e ? fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e) : LZ4HIP_OK;
+  return on_device(device, n == 0, !buf || !off || !len || !out ? kNullArg : nullptr,
+                   [&] { return lz4hip::launch_xxh64(buf, off, len, seed, out, n, stream); });
 }
 
 #ifdef LZ4HIP_DEV_TOOLS
@@ -1447,42 +1382,35 @@ int lz4hip_xxh64_batch_dev(const uint8_t* buf, const uint64_t* off, const int32_
 int lz4hip_dbg_compress_fast_profile_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                          const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, uint64_t* prof,
                                          int device, void* stream) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (n == 0) return LZ4HIP_OK;
-  if (!src || !src_off || !src_len || !dst || !dst_off || !dst_cap || !out_len || !prof) return fail(LZ4HIP_E_ARG, "null pointer argument");
-  int ord;
-  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
-  DeviceGuard g(ord);
-  lz4hip::BatchArgs a{src, src_off, src_len, dst, dst_off, dst_cap, out_len, n};
-  int e = lz4hip::launch_compress_fast_prof(a, prof, g_compress_core.load() == 1 ? 1 : 3, stream);
-  return e ? fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e) : LZ4HIP_OK;
+  const lz4hip::BatchArgs a{src, src_off, src_len, dst, dst_off, dst_cap, out_len, n};
+  return on_device(device, n == 0, !src || !src_off || !src_len || !dst || !dst_off || !dst_cap || !out_len || !prof ? kNullArg : nullptr,
+                   [&] { return lz4hip::launch_compress_fast_prof(a, prof, g_compress_core.load() == 1 ? 1 : 3, stream); });
 }
 #endif  // LZ4HIP_DEV_TOOLS
 
 // ---- single-block convenience ----
-int lz4hip_compress_fast(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap) { return single(OP_COMPRESS_FAST, src, src_len, dst, dst_cap); }
+int lz4hip_compress_fast(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap) { return single({OP_COMPRESS_FAST}, src, src_len, dst, dst_cap); }
 int lz4hip_compress_fast_accel(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int acceleration) {
   const int a = accel_clamp(acceleration);
   if (a == 1) return lz4hip_compress_fast(src, src_len, dst, dst_cap);
-  return single(OP_COMPRESS_ACCEL, src, src_len, dst, dst_cap, a);
+  return single({OP_COMPRESS_ACCEL, a}, src, src_len, dst, dst_cap);
 }
 int lz4hip_compress_dest_size(const uint8_t* src, int* src_size, uint8_t* dst, int target_size) {
   if (!src_size) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, "null src_size"));
   int32_t c = 0;
-  const int r = single(OP_COMPRESS_DEST, src, *src_size, dst, target_size, 0, &c);
+  const int r = single({OP_COMPRESS_DEST, 0, nullptr, &c}, src, *src_size, dst, target_size);
   if (!LZ4HIP_IS_LIB_ERROR(r)) *src_size = c;
   return r;
 }
 int lz4hip_compress_hc(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level) {
   int lv;
   if (hc_level(level, &lv)) return LZ4HIP_LIB_ERROR(LZ4HIP_E_UNSUPPORTED);
-  return single(OP_COMPRESS_HC, src, src_len, dst, dst_cap, lv);
+  return single({OP_COMPRESS_HC, lv}, src, src_len, dst, dst_cap);
 }
-int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap) { return single(OP_DECODE_SAFE, src, src_len, dst, dst_cap); }
-int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len) { return single(OP_DECODE_FAST, src, src_cap, dst, dst_len); }
+int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap) { return single({OP_DECODE_SAFE}, src, src_len, dst, dst_cap); }
+int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len) { return single({OP_DECODE_FAST}, src, src_cap, dst, dst_len); }
 int lz4hip_decompress_safe_partial(const uint8_t* src, int src_len, uint8_t* dst, int target_size, int dst_cap) {
-  return single(OP_DECODE_PARTIAL, src, src_len, dst, partial_room(target_size, dst_cap));
+  return single({OP_DECODE_PARTIAL}, src, src_len, dst, partial_room(target_size, dst_cap));
 }
 int lz4hip_xxh32(const uint8_t* buf, int len, uint32_t seed, uint32_t* out) {
   const uint64_t zero = 0;
@@ -1557,14 +1485,8 @@ void lz4hip_xxh_stream_free(lz4hip_xxh_stream* st) {
 
 int lz4hip_gen_blocks_dev(uint8_t* dst, uint64_t stride, int32_t block_len, uint64_t seed, uint64_t first_idx, uint32_t litmax,
                           uint32_t win, uint32_t n_blocks, int device, void* stream) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
-  if (!dst || block_len < 0 || litmax == 0 || win == 0) return fail(LZ4HIP_E_ARG, "bad argument");
-  int ord;
-  if (ordinal(device, &ord)) return fail(LZ4HIP_E_ARG, "bad device index");
-  DeviceGuard g(ord);
-  int e = lz4hip::launch_gen_blocks(dst, stride, block_len, seed, first_idx, litmax, win, n_blocks, stream);
-  return e ? fail(LZ4HIP_E_HIP, "kernel launch", (hipError_t)e) : LZ4HIP_OK;
+  return on_device(device, false, !dst || block_len < 0 || litmax == 0 || win == 0 ? "bad argument" : nullptr,
+                   [&] { return lz4hip::launch_gen_blocks(dst, stride, block_len, seed, first_idx, litmax, win, n_blocks, stream); });
 }
 
 }  // extern "C"

@@ -12,6 +12,9 @@ struct BatchArgs {
   int32_t* out; uint32_t n;
 };
 
+// compute units of the current device (cached per device; 256 where the runtime cannot say)
+uint32_t device_cus();
+
 // Fast compress, two kernels (same bytes):
 //   launch_compress_fast_v2w lean finder loop (lz4_fast_v2_core.h; common step hand-scheduled, lz4_fast_v2_asm.h) with a writer
 //                            wavefront per finder: bare hits parked in lanes, handed over 64 at a time: the default

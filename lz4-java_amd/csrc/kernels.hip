@@ -1310,7 +1310,7 @@ __global__ __launch_bounds__(192 * W, WPE) void decode_trio_kernel(BatchArgs a, 
   G g;
   trio_quit(g, lds);
 }
-static uint32_t device_cus() {   // compute units of the current device (cached per device)
+uint32_t device_cus() {   // compute units of the current device (cached per device)
   static std::atomic<uint32_t> cus[64];
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) d = 0;

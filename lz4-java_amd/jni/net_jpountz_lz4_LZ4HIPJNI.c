@@ -185,33 +185,68 @@ JNIEXPORT jstring JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_lastError(JNIEnv* env, 
   return (*env)->NewStringUTF(env, lz4hip_last_error());
 }
 
-/* many blocks, direct buffers: nothing is copied on the host side, liblz4hip stages H2D/D2H itself */
+/* ---- the batch natives: many blocks, direct buffers: nothing is copied on the host side, liblz4hip stages H2D/D2H itself ---- */
+/* A long[] / int[] descriptor array of a batch native. */
+enum { INTS = 0, LONGS = 1 };
+typedef struct {
+  jarray arr;
+  int is_long;  /* LONGS (offsets) or INTS */
+  jint mode;    /* how it is released: JNI_ABORT for an input, 0 for an output (copied back) */
+  void* p;      /* its elements while pinned */
+} batch_array_t;
+/* The arguments of a batch native made addressable: the two direct buffers and up to six descriptor arrays. */
+typedef struct {
+  const uint8_t* src;
+  uint8_t* dst;
+  int n_arrays;
+  batch_array_t a[6];
+} batch_args_t;
+
+static void batch_release(JNIEnv* env, batch_args_t* b) {
+  for (int i = 0; i < b->n_arrays; i++) {
+    batch_array_t* a = &b->a[i];
+    if (a->p == NULL) continue;
+    if (a->is_long) (*env)->ReleaseLongArrayElements(env, (jlongArray)a->arr, (jlong*)a->p, a->mode);
+    else (*env)->ReleaseIntArrayElements(env, (jintArray)a->arr, (jint*)a->p, a->mode);
+    a->p = NULL;
+  }
+}
+
+/* 0: everything is addressable (batch_release when done).  LZ4HIP_E_ARG: a NULL array or buffer, or a buffer that is not direct --
+ * decided before the env is asked for anything (Get*ArrayElements of a null reference is undefined in a JVM).  LZ4HIP_E_NOMEM: an
+ * array cannot be pinned.  Nothing stays pinned after an error. */
+static jint batch_pin(JNIEnv* env, jobject src, jobject dest, batch_args_t* b) {
+  if (src == NULL || dest == NULL) return LZ4HIP_E_ARG;
+  for (int i = 0; i < b->n_arrays; i++)
+    if (b->a[i].arr == NULL) return LZ4HIP_E_ARG;
+  b->src = (const uint8_t*)(*env)->GetDirectBufferAddress(env, src);
+  b->dst = (uint8_t*)(*env)->GetDirectBufferAddress(env, dest);
+  if (b->src == NULL || b->dst == NULL) return LZ4HIP_E_ARG;
+  for (int i = 0; i < b->n_arrays; i++) {
+    batch_array_t* a = &b->a[i];
+    a->p = a->is_long ? (void*)(*env)->GetLongArrayElements(env, (jlongArray)a->arr, NULL) : (void*)(*env)->GetIntArrayElements(env, (jintArray)a->arr, NULL);
+    if (a->p == NULL) { batch_release(env, b); return LZ4HIP_E_NOMEM; }
+  }
+  return 0;
+}
+
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batch(JNIEnv* env, jclass cls, jint op, jint level, jobject src, jlongArray srcOff,
     jintArray srcLen, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen, jint n) {
   (void)cls;
-  const uint8_t* s = (const uint8_t*)(*env)->GetDirectBufferAddress(env, src);
-  uint8_t* d = (uint8_t*)(*env)->GetDirectBufferAddress(env, dest);
-  if (s == NULL || d == NULL) return LZ4HIP_E_ARG;
-  jlong* so = (*env)->GetLongArrayElements(env, srcOff, NULL);
-  jint* sl = (*env)->GetIntArrayElements(env, srcLen, NULL);
-  jlong* dof = (*env)->GetLongArrayElements(env, destOff, NULL);
-  jint* dc = (*env)->GetIntArrayElements(env, destCap, NULL);
-  jint* ol = (*env)->GetIntArrayElements(env, outLen, NULL);
-  jint rc = LZ4HIP_E_NOMEM;
-  if (so && sl && dof && dc && ol) {
-    switch (op) {
-      case 0: rc = lz4hip_compress_fast_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)dc, (int32_t*)ol, (uint32_t)n); break;
-      case 1: rc = lz4hip_decompress_safe_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)dc, (int32_t*)ol, (uint32_t)n); break;
-      case 2: rc = lz4hip_decompress_fast_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)dc, (int32_t*)ol, (uint32_t)n); break;
-      case 4: rc = lz4hip_compress_fast_accel_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)dc, (int32_t*)ol, (uint32_t)n, level); break;
-      default: rc = lz4hip_compress_hc_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)dc, (int32_t*)ol, (uint32_t)n, level); break;
-    }
+  batch_args_t b = {NULL, NULL, 5, {{srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT}, {destCap, INTS, JNI_ABORT}, {outLen, INTS, 0}}};
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  const uint64_t *so = b.a[0].p, *dof = b.a[2].p;
+  const int32_t *sl = b.a[1].p, *dc = b.a[3].p;
+  int32_t* ol = b.a[4].p;
+  switch (op) {
+    case 0: rc = lz4hip_compress_fast_batch(b.src, so, sl, b.dst, dof, dc, ol, (uint32_t)n); break;
+    case 1: rc = lz4hip_decompress_safe_batch(b.src, so, sl, b.dst, dof, dc, ol, (uint32_t)n); break;
+    case 2: rc = lz4hip_decompress_fast_batch(b.src, so, sl, b.dst, dof, dc, ol, (uint32_t)n); break;
+    case 4: rc = lz4hip_compress_fast_accel_batch(b.src, so, sl, b.dst, dof, dc, ol, (uint32_t)n, level); break;
+    default: rc = lz4hip_compress_hc_batch(b.src, so, sl, b.dst, dof, dc, ol, (uint32_t)n, level); break;
   }
-  if (so) (*env)->ReleaseLongArrayElements(env, srcOff, so, JNI_ABORT);
-  if (sl) (*env)->ReleaseIntArrayElements(env, srcLen, sl, JNI_ABORT);
-  if (dof) (*env)->ReleaseLongArrayElements(env, destOff, dof, JNI_ABORT);
-  if (dc) (*env)->ReleaseIntArrayElements(env, destCap, dc, JNI_ABORT);
-  if (ol) (*env)->ReleaseIntArrayElements(env, outLen, ol, 0);
+  batch_release(env, &b);
   return rc;
 }
 
@@ -221,27 +256,12 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batch(JNIEnv* env,
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchDestSize(JNIEnv* env, jclass cls, jobject src, jlongArray srcOff,
     jintArray srcLen, jobject dest, jlongArray destOff, jintArray targetSize, jintArray outLen, jintArray srcConsumed, jint n) {
   (void)cls;
-  if (src == NULL || dest == NULL || srcOff == NULL || srcLen == NULL || destOff == NULL || targetSize == NULL || outLen == NULL ||
-      srcConsumed == NULL) return LZ4HIP_E_ARG;
-  const uint8_t* s = (const uint8_t*)(*env)->GetDirectBufferAddress(env, src);
-  uint8_t* d = (uint8_t*)(*env)->GetDirectBufferAddress(env, dest);
-  if (s == NULL || d == NULL) return LZ4HIP_E_ARG;
-  jlong* so = (*env)->GetLongArrayElements(env, srcOff, NULL);
-  jint* sl = (*env)->GetIntArrayElements(env, srcLen, NULL);
-  jlong* dof = (*env)->GetLongArrayElements(env, destOff, NULL);
-  jint* ts = (*env)->GetIntArrayElements(env, targetSize, NULL);
-  jint* ol = (*env)->GetIntArrayElements(env, outLen, NULL);
-  jint* sc = (*env)->GetIntArrayElements(env, srcConsumed, NULL);
-  jint rc = LZ4HIP_E_NOMEM;
-  if (so && sl && dof && ts && ol && sc)
-    rc = lz4hip_compress_dest_size_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)ts, (int32_t*)ol,
-                                         (int32_t*)sc, (uint32_t)n);
-  if (so) (*env)->ReleaseLongArrayElements(env, srcOff, so, JNI_ABORT);
-  if (sl) (*env)->ReleaseIntArrayElements(env, srcLen, sl, JNI_ABORT);
-  if (dof) (*env)->ReleaseLongArrayElements(env, destOff, dof, JNI_ABORT);
-  if (ts) (*env)->ReleaseIntArrayElements(env, targetSize, ts, JNI_ABORT);
-  if (ol) (*env)->ReleaseIntArrayElements(env, outLen, ol, 0);
-  if (sc) (*env)->ReleaseIntArrayElements(env, srcConsumed, sc, 0);
+  batch_args_t b = {NULL, NULL, 6, {{srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT}, {targetSize, INTS, JNI_ABORT}, {outLen, INTS, 0},
+                                    {srcConsumed, INTS, 0}}};
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  rc = lz4hip_compress_dest_size_batch(b.src, b.a[0].p, b.a[1].p, b.dst, b.a[2].p, b.a[3].p, b.a[4].p, b.a[5].p, (uint32_t)n);
+  batch_release(env, &b);
   return rc;
 }
 
@@ -251,27 +271,12 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchDestSize(JNIE
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafePartial(JNIEnv* env, jclass cls, jobject src, jlongArray srcOff,
     jintArray srcLen, jobject dest, jlongArray destOff, jintArray targetLen, jintArray destCap, jintArray outLen, jint n) {
   (void)cls;
-  if (src == NULL || dest == NULL || srcOff == NULL || srcLen == NULL || destOff == NULL || targetLen == NULL || destCap == NULL ||
-      outLen == NULL) return LZ4HIP_E_ARG;
-  const uint8_t* s = (const uint8_t*)(*env)->GetDirectBufferAddress(env, src);
-  uint8_t* d = (uint8_t*)(*env)->GetDirectBufferAddress(env, dest);
-  if (s == NULL || d == NULL) return LZ4HIP_E_ARG;
-  jlong* so = (*env)->GetLongArrayElements(env, srcOff, NULL);
-  jint* sl = (*env)->GetIntArrayElements(env, srcLen, NULL);
-  jlong* dof = (*env)->GetLongArrayElements(env, destOff, NULL);
-  jint* tl = (*env)->GetIntArrayElements(env, targetLen, NULL);
-  jint* dc = (*env)->GetIntArrayElements(env, destCap, NULL);
-  jint* ol = (*env)->GetIntArrayElements(env, outLen, NULL);
-  jint rc = LZ4HIP_E_NOMEM;
-  if (so && sl && dof && tl && dc && ol)
-    rc = lz4hip_decompress_safe_partial_batch(s, (const uint64_t*)so, (const int32_t*)sl, d, (const uint64_t*)dof, (const int32_t*)tl,
-                                              (const int32_t*)dc, (int32_t*)ol, (uint32_t)n);
-  if (so) (*env)->ReleaseLongArrayElements(env, srcOff, so, JNI_ABORT);
-  if (sl) (*env)->ReleaseIntArrayElements(env, srcLen, sl, JNI_ABORT);
-  if (dof) (*env)->ReleaseLongArrayElements(env, destOff, dof, JNI_ABORT);
-  if (tl) (*env)->ReleaseIntArrayElements(env, targetLen, tl, JNI_ABORT);
-  if (dc) (*env)->ReleaseIntArrayElements(env, destCap, dc, JNI_ABORT);
-  if (ol) (*env)->ReleaseIntArrayElements(env, outLen, ol, 0);
+  batch_args_t b = {NULL, NULL, 6, {{srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT}, {targetLen, INTS, JNI_ABORT}, {destCap, INTS, JNI_ABORT},
+                                    {outLen, INTS, 0}}};
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  rc = lz4hip_decompress_safe_partial_batch(b.src, b.a[0].p, b.a[1].p, b.dst, b.a[2].p, b.a[3].p, b.a[4].p, b.a[5].p, (uint32_t)n);
+  batch_release(env, &b);
   return rc;
 }
 

@@ -1,6 +1,6 @@
 /* tests/jni_stub/fake_jni.c -- TEST INFRASTRUCTURE ONLY.
  *
- * Executes the JNI shim (lz4-java_amd/jni/net_jpountz_lz4_LZ4HIPJNI.c) without a JVM: a fake JNIEnv function table in
+ * Executes the JNI shim (lz4-java_amd/jni/net_jpountz_lz4_LZ4HIPJNI.c) without a JVM: a fake JNIEnv function table (fake_env.h) in
  * which a Java byte[] / int[] / long[] is a malloc'd buffer with pin accounting and a direct ByteBuffer is a pointer.  The shim is
  * compiled against tests/jni_stub/jni.h into this program and linked with liblz4hip.so, so every Java_net_jpountz_* entry point
  * the Java classes declare runs against the real C ABI -- including the paths the reference gets wrong or cannot have (the
@@ -10,60 +10,8 @@
  *   fake_jni --no-gpu   anywhere: only what must hold without a device (every compute call fails LOUDLY: exception or error code)
  * The shim's malloc/free are counted (-Dmalloc=t_malloc -Dfree=t_free on its translation unit).
  */
-#include <jni.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include "lz4hip.h"
-
-/* ---- fake objects ---- */
-typedef struct {
-  int kind;          /* 1 = byte[], 2 = int[], 3 = long[], 4 = direct ByteBuffer, 5 = heap ByteBuffer (no direct address) */
-  uint8_t* data;
-  size_t bytes;
-  int pins;          /* outstanding Get*Critical / Get*ArrayElements */
-  int refuse_pin;    /* GetPrimitiveArrayCritical returns NULL (a VM that cannot pin) */
-} fobj;
-
-static long g_alloc = 0;       /* outstanding shim allocations */
-void* t_malloc(size_t n) { g_alloc++; return malloc(n); }
-void t_free(void* p) { if (p) g_alloc--; free(p); }
-
-static const char* g_exc_class = NULL;
-static char g_exc_msg[512];
-static int g_checks = 0;
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "fake_jni: CHECK failed at line %d: %s (pending exception: %s \"%s\")\n", __LINE__, #c, \
-    g_exc_class ? g_exc_class : "none", g_exc_msg); exit(1); } g_checks++; } while (0)
-
-static jclass f_FindClass(JNIEnv* e, const char* name) { (void)e; return (jclass)strdup(name); }
-static jint f_ThrowNew(JNIEnv* e, jclass c, const char* msg) { (void)e; g_exc_class = (const char*)c; snprintf(g_exc_msg, sizeof g_exc_msg, "%s", msg ? msg : ""); return 0; }
-static jobject f_NewGlobalRef(JNIEnv* e, jobject o) { (void)e; return o; }
-static void* f_GetCritical(JNIEnv* e, jarray a, jboolean* isCopy) {
-  (void)e; fobj* o = (fobj*)a;
-  if (isCopy) *isCopy = 0;
-  if (o->refuse_pin) return NULL;
-  o->pins++;
-  return o->data;
-}
-static void f_ReleaseCritical(JNIEnv* e, jarray a, void* p, jint mode) { (void)e; (void)mode; fobj* o = (fobj*)a; if (p != o->data) { fprintf(stderr, "release of a foreign pointer\n"); exit(1); } o->pins--; }
-static void* f_GetDirect(JNIEnv* e, jobject b) { (void)e; fobj* o = (fobj*)b; return o->kind == 4 ? o->data : NULL; }
-static jstring f_NewStringUTF(JNIEnv* e, const char* s) { (void)e; return (jstring)strdup(s ? s : ""); }
-static jlong* f_GetLongs(JNIEnv* e, jlongArray a, jboolean* c) { (void)e; if (c) *c = 0; ((fobj*)a)->pins++; return (jlong*)((fobj*)a)->data; }
-static jint* f_GetInts(JNIEnv* e, jintArray a, jboolean* c) { (void)e; if (c) *c = 0; ((fobj*)a)->pins++; return (jint*)((fobj*)a)->data; }
-static void f_RelLongs(JNIEnv* e, jlongArray a, jlong* p, jint m) { (void)e; (void)p; (void)m; ((fobj*)a)->pins--; }
-static void f_RelInts(JNIEnv* e, jintArray a, jint* p, jint m) { (void)e; (void)p; (void)m; ((fobj*)a)->pins--; }
-
-static jint f_ArrayLength(JNIEnv* e, jarray a) { (void)e; const fobj* o = (const fobj*)a; return (jint)(o->bytes / (o->kind == 3 ? 8u : o->kind == 2 ? 4u : 1u)); }
-
-static const struct JNINativeInterface_ g_table = {f_FindClass, f_ThrowNew, f_NewGlobalRef, f_GetCritical, f_ReleaseCritical, f_GetDirect,
-                                                   f_NewStringUTF, f_GetLongs, f_GetInts, f_RelLongs, f_RelInts, f_ArrayLength};
-static JNIEnv g_env = &g_table;
-
-static fobj* mk(int kind, size_t bytes) { fobj* o = calloc(1, sizeof *o); o->kind = kind; o->bytes = bytes; o->data = calloc(bytes ? bytes : 1, 1); return o; }
-static int no_exc(void) { return g_exc_class == NULL; }
-static void clear_exc(void) { g_exc_class = NULL; g_exc_msg[0] = 0; }
+#define FAKE_JNI_NAME "fake_jni"
+#include "fake_env.h"
 
 /* ---- the shim's entry points (same translation unit names as the Java natives) ---- */
 JNIEXPORT void JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_init(JNIEnv*, jclass);
@@ -109,6 +57,17 @@ int main(int argc, char** argv) {
 
   fobj* src = mk(1, 64); fobj* dst = mk(1, 128); fobj* back = mk(1, 64);
   memcpy(src->data + 7, SELFTEST_IN, 20);
+  /* NULL descriptor arrays of LZ4HIP_batch: LZ4HIP_E_ARG before the env is asked for their elements, whatever the device; nothing
+     pinned, outLen untouched */
+  { fobj* bsrc = mk(4, 64); fobj* bdst = mk(4, 128);
+    fobj* so = mk(3, 8); fobj* sl = int1(20); fobj* dof = mk(3, 8); fobj* dc = int1(100); fobj* ol = int1(-7);
+    fobj* a[5] = {so, sl, dof, dc, ol};
+    for (int k = 0; k < 5; k++) {
+      jint rc = Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batch(env, NULL, 0, 0, (jobject)bsrc, k == 0 ? NULL : (jlongArray)so, k == 1 ? NULL : (jintArray)sl, (jobject)bdst,
+                                                             k == 2 ? NULL : (jlongArray)dof, k == 3 ? NULL : (jintArray)dc, k == 4 ? NULL : (jintArray)ol, 1);
+      CHECK(rc == LZ4HIP_E_ARG && no_exc() && get1(ol) == -7);
+      for (int t = 0; t < 5; t++) CHECK(a[t]->pins == 0);
+    } }
   if (!gpu) {
     /* no device: every compute call reports a LIBRARY error (never a fake result), hashes throw, nothing leaks or stays pinned */
     jint r = Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1fast(env, NULL, (jbyteArray)src, NULL, 7, 20, (jbyteArray)dst, NULL, 3, 100);

@@ -1,7 +1,7 @@
 /* tests/jni_stub/fake_jni_partial.c -- TEST INFRASTRUCTURE ONLY.
  *
  * The partial-decode natives of the JNI shim (LZ4HIPJNI.LZ4HIP_decompress_safe_partial and LZ4HIP_batchSafePartial) executed without a
- * JVM, with the same fake JNIEnv as fake_jni.c (a byte[] / int[] / long[] is a malloc'd buffer with pin accounting, a direct ByteBuffer
+ * JVM, with the fake JNIEnv of fake_env.h (a byte[] / int[] / long[] is a malloc'd buffer with pin accounting, a direct ByteBuffer
  * is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built by tests/test_partial_abi.py / tests/test_gpu_partial.py.
  *
  *   fake_jni_partial --no-gpu                          anywhere: NULL arrays are argument errors, every compute call fails LOUDLY
@@ -12,64 +12,8 @@
  *                                                      with the reference's LZ4_decompress_safe_partial); prints
  *                                                      "fake_jni_partial: N checks ok"
  */
-#include <jni.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include "lz4hip.h"
-
-typedef struct {
-  int kind;          /* 1 = byte[], 2 = int[], 3 = long[], 4 = direct ByteBuffer, 5 = heap ByteBuffer (no direct address) */
-  uint8_t* data;
-  size_t bytes;
-  int pins;
-  int refuse_pin;
-} fobj;
-
-static long g_alloc = 0;
-void* t_malloc(size_t n) { g_alloc++; return malloc(n); }
-void t_free(void* p) { if (p) g_alloc--; free(p); }
-
-static const char* g_exc_class = NULL;
-static char g_exc_msg[512];
-static int g_checks = 0;
-
-#define CHECK(c) do { if (!(c)) { fprintf(stderr, "fake_jni_partial: CHECK failed at line %d: %s (pending exception: %s \"%s\")\n", __LINE__, #c, \
-    g_exc_class ? g_exc_class : "none", g_exc_msg); exit(1); } g_checks++; } while (0)
-
-static jclass f_FindClass(JNIEnv* e, const char* name) { (void)e; return (jclass)strdup(name); }
-static jint f_ThrowNew(JNIEnv* e, jclass c, const char* msg) { (void)e; g_exc_class = (const char*)c; snprintf(g_exc_msg, sizeof g_exc_msg, "%s", msg ? msg : ""); return 0; }
-static jobject f_NewGlobalRef(JNIEnv* e, jobject o) { (void)e; return o; }
-static void* f_GetCritical(JNIEnv* e, jarray a, jboolean* isCopy) {
-  (void)e; fobj* o = (fobj*)a;
-  if (isCopy) *isCopy = 0;
-  if (o->refuse_pin) return NULL;
-  o->pins++;
-  return o->data;
-}
-static void f_ReleaseCritical(JNIEnv* e, jarray a, void* p, jint mode) { (void)e; (void)mode; fobj* o = (fobj*)a; if (p != o->data) { fprintf(stderr, "release of a foreign pointer\n"); exit(1); } o->pins--; }
-static void* f_GetDirect(JNIEnv* e, jobject b) { (void)e; fobj* o = (fobj*)b; return o->kind == 4 ? o->data : NULL; }
-static jstring f_NewStringUTF(JNIEnv* e, const char* s) { (void)e; return (jstring)strdup(s ? s : ""); }
-static jlong* f_GetLongs(JNIEnv* e, jlongArray a, jboolean* c) { (void)e; if (c) *c = 0; ((fobj*)a)->pins++; return (jlong*)((fobj*)a)->data; }
-static jint* f_GetInts(JNIEnv* e, jintArray a, jboolean* c) { (void)e; if (c) *c = 0; ((fobj*)a)->pins++; return (jint*)((fobj*)a)->data; }
-static void f_RelLongs(JNIEnv* e, jlongArray a, jlong* p, jint m) { (void)e; (void)p; (void)m; ((fobj*)a)->pins--; }
-static void f_RelInts(JNIEnv* e, jintArray a, jint* p, jint m) { (void)e; (void)p; (void)m; ((fobj*)a)->pins--; }
-static jint f_ArrayLength(JNIEnv* e, jarray a) { (void)e; const fobj* o = (const fobj*)a; return (jint)(o->bytes / (o->kind == 3 ? 8u : o->kind == 2 ? 4u : 1u)); }
-
-static const struct JNINativeInterface_ g_table = {f_FindClass, f_ThrowNew, f_NewGlobalRef, f_GetCritical, f_ReleaseCritical, f_GetDirect,
-                                                   f_NewStringUTF, f_GetLongs, f_GetInts, f_RelLongs, f_RelInts, f_ArrayLength};
-static JNIEnv g_env = &g_table;
-
-static fobj* mk(int kind, size_t bytes) { fobj* o = calloc(1, sizeof *o); o->kind = kind; o->bytes = bytes; o->data = calloc(bytes ? bytes : 1, 1); return o; }
-static int no_exc(void) { return g_exc_class == NULL; }
-static void clear_exc(void) { g_exc_class = NULL; g_exc_msg[0] = 0; }
-/* every byte of o outside [off, off + n) still holds `fill` */
-static int guarded(const fobj* o, size_t off, size_t n, uint8_t fill) {
-  for (size_t i = 0; i < o->bytes; i++)
-    if ((i < off || i >= off + n) && o->data[i] != fill) return 0;
-  return 1;
-}
+#define FAKE_JNI_NAME "fake_jni_partial"
+#include "fake_env.h"
 
 JNIEXPORT void JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_init(JNIEnv*, jclass);
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1safe_1partial(JNIEnv*, jclass, jbyteArray, jobject, jint, jint, jbyteArray, jobject, jint, jint, jint);
@@ -78,9 +22,6 @@ JNIEXPORT jstring JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_lastError(JNIEnv*, jcla
 
 #define PART Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1safe_1partial
 #define BATCH Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafePartial
-
-static fobj* int1(jint v) { fobj* o = mk(2, 4); ((jint*)o->data)[0] = v; return o; }
-static jint get1(const fobj* o) { return ((const jint*)o->data)[0]; }
 
 int main(int argc, char** argv) {
   JNIEnv* env = &g_env;

@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from jni_build import build_fake_jni
 
 NEW = ("lz4hip_compress_dest_size_batch", "lz4hip_compress_dest_size_batch_dev", "lz4hip_compress_dest_size")
 LIB_ERROR = lambda status: -2 ** 31 + (-status)   # LZ4HIP_LIB_ERROR
@@ -199,20 +200,7 @@ def test_jni_dest_size_natives_declared_and_checked_without_device(tmp_path):
     assert "LZ4HIPJNI.LZ4HIP_compress_dest_size(" in open(os.path.join(jdir, "LZ4HIPCompressor.java")).read()
     assert "Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1dest_1size" in shim
     assert "Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchDestSize" in shim
-    exe = build_fake_jni_destsize(tmp_path)
+    exe = build_fake_jni("fake_jni_destsize", tmp_path)
     if no_device():
         out = subprocess.check_output([exe, "--no-gpu"]).decode()
         assert "checks ok" in out, out
-
-
-def build_fake_jni_destsize(tmp_path):
-    """the shim (malloc / free counted, as tests/jni_stub/build.sh does) + tests/jni_stub/fake_jni_destsize.c -> an executable"""
-    d = os.path.join(ROOT, "tests", "jni_stub")
-    inc = ["-I" + d, "-I" + os.path.join(ROOT, "include")]
-    shim_o, drv_o, exe = str(tmp_path / "shim.o"), str(tmp_path / "fake_jni_destsize.o"), str(tmp_path / "fake_jni_destsize")
-    subprocess.check_call(["gcc", "-O1", "-std=gnu11", "-Wall"] + inc + ["-Dmalloc=t_malloc", "-Dfree=t_free", "-include", os.path.join(d, "shim_alloc.h"),
-                           "-c", os.path.join(ROOT, "lz4-java_amd", "jni", "net_jpountz_lz4_LZ4HIPJNI.c"), "-o", shim_o])
-    subprocess.check_call(["gcc", "-O1", "-std=gnu11", "-Wall"] + inc + ["-c", os.path.join(d, "fake_jni_destsize.c"), "-o", drv_o])
-    subprocess.check_call(["gcc", drv_o, shim_o, "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    return exe

@@ -169,8 +169,8 @@ def test_jni_accel_native_full_scenarios(lz4fast, tmp_path):
     """the shim's new native over the fake JNIEnv (tests/jni_stub/fake_jni_accel.c): arrays, direct buffers, NULL arrays, a heap
     buffer without an address, a destination that cannot be pinned, too small a destination, the batch op; the streams of
     accelerations 1 and 8 are the reference's"""
-    from test_accel_abi import build_fake_jni_accel
-    exe = build_fake_jni_accel(tmp_path)
+    from jni_build import build_fake_jni
+    exe = build_fake_jni("fake_jni_accel", tmp_path)
     v = calgary("book1")[100000:165536]
     inp = tmp_path / "in.bin"
     inp.write_bytes(v)

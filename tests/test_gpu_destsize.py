@@ -259,8 +259,8 @@ def test_cpp_mirror(lz4dest, tmp_path):
 def test_jni_dest_size_full_scenarios(lz4dest, tmp_path):
     """the shim's new natives over the fake JNIEnv (tests/jni_stub/fake_jni_destsize.c): arrays, direct buffers, NULL arrays, a
     destination that cannot be pinned, the batch native; the stream and consumed size are the reference's"""
-    from test_destsize_abi import build_fake_jni_destsize
-    exe = build_fake_jni_destsize(tmp_path)
+    from jni_build import build_fake_jni
+    exe = build_fake_jni("fake_jni_destsize", tmp_path)
     v = calgary("book1")[100000:165536]
     (tmp_path / "in.bin").write_bytes(v)
     out = subprocess.check_output([exe, str(tmp_path / "in.bin"), "16384", str(tmp_path)], timeout=300).decode()

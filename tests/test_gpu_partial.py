@@ -247,8 +247,8 @@ def test_partial_cpp_mirror(tmp_path, cases, want):
 
 
 def test_partial_jni_shim(tmp_path, cases, want):
-    from test_partial_abi import build_fake_jni_partial
-    exe = build_fake_jni_partial(tmp_path)
+    from jni_build import build_fake_jni
+    exe = build_fake_jni("fake_jni_partial", tmp_path)
     picked = [i for i in range(0, len(cases), max(1, len(cases) // 20)) if len(cases[i][0]) > 0]
     for i in picked:
         s, t, c = cases[i]
