@@ -15,6 +15,8 @@
  *                                reference's liblz4-java.so; no JNI entry of the reference reaches it)
  *   lz4hip_compress_dest_size*   = LZ4_compress_destSize(src, dst, &srcSize, targetDstSize) of liblz4's main API (exported by
  *                                the reference's liblz4-java.so; no JNI entry of the reference reaches it)
+ *   lz4hip_compress_hc_dest_size* = LZ4_compress_HC_destSize(state, src, dst, &srcSize, targetDstSize, level) of liblz4's HC API
+ *                                (exported by the reference's liblz4-java.so; no JNI entry of the reference reaches it)
  *   lz4hip_decompress_safe_partial* = LZ4_decompress_safe_partial(src, dst, srcSize, targetOutputSize, dstCapacity) of liblz4's
  *                                main API (exported by the reference's liblz4-java.so; no JNI entry of the reference reaches it)
  *   lz4hip_xxh32* / xxh64*    <- Java_net_jpountz_xxhash_XXHashJNI_XXH32 / XXH64
@@ -158,6 +160,27 @@ int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src
 int lz4hip_compress_hc_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                              uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                              int32_t* out_len, uint32_t n_blocks, int level);
+/* HC COMPRESS TO A TARGET SIZE: the bytes, return value and consumed size of LZ4_compress_HC_destSize(state, src, dst, &srcSize,
+ * targetDstSize, level), liblz4 1.9.3: as much of block i as fits in exactly target_size[i] bytes, parsed at HC level `level`
+ * (clamped as for lz4hip_compress_hc*: < 1 -> 9, > 12 -> 12; 1..9 the hash chain with lazy evaluation, 10..12 the optimal parser).
+ *   - out_len[i] is liblz4's return value: the bytes written (<= target_size[i]), 0 for target_size[i] < 1 and for src_len[i] < 0
+ *     or > 0x7E000000; an empty block gives the single token 0x00 (1 byte) for any target >= 1;
+ *   - src_consumed[i] is what liblz4 leaves in *srcSizePtr: the input bytes the output covers (decoding out_len[i] bytes gives back
+ *     exactly src[0 .. src_consumed[i])), and src_len[i] itself where it returns 0 up front;
+ *   - liblz4 makes its fillOutput checks whatever the target: the sequence that fails one has its match cut (or is dropped) and the
+ *     last literals are shortened to fit; a target that no check fails for gives the bytes of lz4hip_compress_hc, all input consumed;
+ *   - block i's slot is dst[dst_off[i] .. + target_size[i]): nothing is written at or past its end;
+ *   - two kernels: hc_build_kernel as for lz4hip_compress_hc*, then hc_parse_dest_kernel (one wavefront per block, the parser of
+ *     lz4_hc_core.h with its FILL switch).  The parse of a block stops once its target is full, so the parse time follows the input
+ *     consumed; the chain-delta build still covers the whole block;
+ *   - levels 10..12 are functional only, as they are for lz4hip_compress_hc*;
+ *   - the host batch shards over the initialised devices, returns only the useful bytes of every slot as the fast destSize path does
+ *     and brings src_consumed back with the sizes; library failures as the status of the call;
+ *   - single calls (lz4hip_compress_hc_dest_size) are coalesced with concurrent HC destSize calls of the SAME clamped level only,
+ *     through combiners of their own.                                                                                              */
+int lz4hip_compress_hc_dest_size_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                       uint8_t* dst, const uint64_t* dst_off, const int32_t* target_size,
+                                       int32_t* out_len, int32_t* src_consumed, uint32_t n_blocks, int level);
 int lz4hip_decompress_safe_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                  uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                  int32_t* out_len, uint32_t n_blocks);
@@ -220,6 +243,16 @@ int lz4hip_compress_hc_batch_dev_ws(const uint8_t* src, const uint64_t* src_off,
                                     uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                     int32_t* out_len, uint32_t n_blocks, int level, int device, void* stream,
                                     uint64_t src_span, void* ws, size_t ws_bytes);
+/* HC compress to a target size (see lz4hip_compress_hc_dest_size_batch), device pointers.  As lz4hip_compress_hc_batch_dev, the
+ * plain form sizes the chain workspace itself and synchronises `stream` ONCE; the _ws form is fully asynchronous and takes a
+ * workspace of at least lz4hip_hc_workspace_bytes(src_span, n_blocks, level) bytes (the same size as for lz4hip_compress_hc*).     */
+int lz4hip_compress_hc_dest_size_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                           uint8_t* dst, const uint64_t* dst_off, const int32_t* target_size,
+                                           int32_t* out_len, int32_t* src_consumed, uint32_t n_blocks, int level, int device, void* stream);
+int lz4hip_compress_hc_dest_size_batch_dev_ws(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                              uint8_t* dst, const uint64_t* dst_off, const int32_t* target_size,
+                                              int32_t* out_len, int32_t* src_consumed, uint32_t n_blocks, int level, int device, void* stream,
+                                              uint64_t src_span, void* ws, size_t ws_bytes);
 int lz4hip_decompress_safe_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                      int32_t* out_len, uint32_t n_blocks, int device, void* stream);
@@ -243,6 +276,9 @@ int lz4hip_compress_fast_accel(const uint8_t* src, int src_len, uint8_t* dst, in
  * LZ4HIP_LIB_ERROR(status) and leaves *src_size untouched; src_size == NULL is LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
 int lz4hip_compress_dest_size(const uint8_t* src, int* src_size, uint8_t* dst, int target_size);
 int lz4hip_compress_hc(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level);
+/* LZ4_compress_HC_destSize: *src_size in = block size, out = input consumed; returns the bytes written.  A library failure returns
+ * LZ4HIP_LIB_ERROR(status) and leaves *src_size untouched; src_size == NULL is LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
+int lz4hip_compress_hc_dest_size(const uint8_t* src, int* src_size, uint8_t* dst, int target_size, int level);
 int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap);
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len);
 int lz4hip_decompress_safe_partial(const uint8_t* src, int src_len, uint8_t* dst, int target_size, int dst_cap);  /* LZ4_decompress_safe_partial */

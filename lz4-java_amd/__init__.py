@@ -49,6 +49,7 @@ C_ABI = {
     "lz4hip_compress_fast_accel_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_int]),
     "lz4hip_compress_dest_size_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_compress_hc_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_int]),
+    "lz4hip_compress_hc_dest_size_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, _i32p, C.c_uint32, C.c_int]),
     "lz4hip_decompress_safe_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_decompress_fast_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_decompress_safe_partial_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, _i32p, C.c_uint32]),
@@ -59,6 +60,8 @@ C_ABI = {
     "lz4hip_compress_dest_size_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_decompress_safe_partial_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "lz4hip_compress_hc_dest_size_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
+    "lz4hip_compress_hc_dest_size_batch_dev_ws": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
     "lz4hip_hc_workspace_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_int]),
     "lz4hip_compress_hc_batch_dev_ws": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
     "lz4hip_decompress_safe_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
@@ -69,6 +72,7 @@ C_ABI = {
     "lz4hip_compress_fast_accel": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_compress_dest_size": (C.c_int, [C.c_void_p, _i32p, C.c_void_p, C.c_int]),
     "lz4hip_compress_hc": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "lz4hip_compress_hc_dest_size": (C.c_int, [C.c_void_p, _i32p, C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_decompress_safe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_safe_partial": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
@@ -267,6 +271,18 @@ class LZ4HCHIPCompressor(LZ4Compressor):
             return super().compress(src, srcOff, srcLen, dest, destOff, maxDestLen)
         except LZ4Exception:
             raise LZ4Exception()  # LZ4HCJNICompressor.java:47-49 throws without a message
+
+    def compressDestSize(self, src, srcOff, srcLen, dest, destOff, targetDestSize):
+        """liblz4's LZ4_compress_HC_destSize at this compressor's level: compresses as much of src[srcOff:srcOff+srcLen] as fits in
+        exactly targetDestSize bytes at dest[destOff:] -> (written, consumed): the bytes written and the source bytes they cover
+        (lz4hip_compress_hc_dest_size)."""
+        dp, dk = _rw_ptr(dest)                      # the argument checks of compress()
+        _check_range(src, srcOff, srcLen)
+        _check_range(dest, destOff, targetDestSize)
+        sp, sk = _ro_ptr(src)
+        size = C.c_int32(srcLen)
+        written = _single(lib().lz4hip_compress_hc_dest_size(sp + srcOff, C.byref(size), dp + destOff, targetDestSize, self.compressionLevel))
+        return written, size.value
 
 
 # ----------------------------------------------------------------------------------------------
@@ -638,6 +654,26 @@ class LZ4HIPBatch:
                                             _arr(C.c_int32, dstCap), out, n, level))
         return list(out[:n])
 
+    @classmethod
+    def compressHCDestSize(cls, src, srcOff, srcLen, dst, dstOff, targetSize, level=9):
+        """LZ4_compress_HC_destSize per block at HC level `level`: as much of block i as fits in exactly targetSize[i] bytes at
+        dst[dstOff[i]:] -> (outLen, srcConsumed) (lz4hip_compress_hc_dest_size_batch; lists, or int32 arrays for numpy inputs)"""
+        n = len(srcOff)
+        if not (len(srcLen) == len(dstOff) == len(targetSize) == n):
+            raise ValueError("per-block arrays differ in length")
+        cls._check_ranges(src, srcOff, srcLen)
+        cls._check_ranges(dst, dstOff, targetSize)
+        sp, sk = _ro_ptr(src)
+        dp, dk = _rw_ptr(dst)
+        out = (C.c_int32 * max(n, 1))()
+        consumed = (C.c_int32 * max(n, 1))()
+        _chk(lib().lz4hip_compress_hc_dest_size_batch(sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), dp, _arr(C.c_uint64, dstOff),
+                                                      _arr(C.c_int32, targetSize), out, consumed, n, int(level)))
+        if hasattr(srcOff, "dtype"):
+            import numpy as np
+            return (np.frombuffer(out, dtype=np.int32, count=n).copy(), np.frombuffer(consumed, dtype=np.int32, count=n).copy())
+        return list(out[:n]), list(consumed[:n])
+
     FRAME_BLOCKS, LZ4BLOCK_BLOCKS = 0, 1
 
     @staticmethod
@@ -778,6 +814,28 @@ class DeviceBatch:
                                                    dst_off.data_ptr(), dst_cap.data_ptr(), out.data_ptr(), src_off.numel(), level, dev, st,
                                                    span, ws.data_ptr(), nb))
         ws.record_stream(torch.cuda.current_stream(src.device))
+
+    @classmethod
+    def compress_hc_dest_size(cls, src, src_off, src_len, dst, dst_off, target_size, out, consumed, level=9):
+        """LZ4_compress_HC_destSize per block (lz4hip_compress_hc_dest_size_batch_dev_ws): out = bytes written, consumed = input
+        consumed; block i's slot is dst[dst_off[i] : + target_size[i]].  Asynchronous, the workspace as in compress_hc"""
+        import torch
+        dev, st = cls._stream_dev(src)
+        span = src.numel() * src.element_size()
+        nb = lib().lz4hip_hc_workspace_bytes(span, src_off.numel(), level)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=src.device)
+        _chk(lib().lz4hip_compress_hc_dest_size_batch_dev_ws(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
+                                                             dst_off.data_ptr(), target_size.data_ptr(), out.data_ptr(), consumed.data_ptr(),
+                                                             src_off.numel(), level, dev, st, span, ws.data_ptr(), nb))
+        ws.record_stream(torch.cuda.current_stream(src.device))
+
+    @classmethod
+    def compress_hc_dest_size_sync(cls, src, src_off, src_len, dst, dst_off, target_size, out, consumed, level=9):
+        """the entry that sizes its own workspace (synchronises the stream once)"""
+        dev, st = cls._stream_dev(src)
+        _chk(lib().lz4hip_compress_hc_dest_size_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
+                                                          dst_off.data_ptr(), target_size.data_ptr(), out.data_ptr(), consumed.data_ptr(),
+                                                          src_off.numel(), level, dev, st))
 
     @classmethod
     def container_blocks(cls, kind, src, block_size, dst, total, block_checksum=False, level=0):

@@ -73,22 +73,23 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // OP_COMPRESS_DEST: LZ4_compress_destSize, dst_cap = the target size; a second per-block output array carries the consumed sizes
 // OP_DECODE_PARTIAL: LZ4_decompress_safe_partial; on the host path dst_cap already holds min(target, capacity), or -1 where one of
 // them is negative (partial_room), and the kernels get that array as the target too
-enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL };
-constexpr int OP_COUNT = OP_DECODE_PARTIAL + 1;   // (the last enumerator)
+// OP_COMPRESS_HC_DEST: LZ4_compress_HC_destSize: OP_COMPRESS_HC's level and workspace, OP_COMPRESS_DEST's target and consumed sizes
+enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST };
+constexpr int OP_COUNT = OP_COMPRESS_HC_DEST + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
-constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST; }
+constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
 // a second per-block result (BlockCall::consumed) travels behind out[]
-constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST; }
+constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
 // out[i] counts SOURCE bytes read: a block that succeeded filled its whole dst_cap[i]
 constexpr bool op_fills_capacity(Op op) { return op == OP_DECODE_FAST; }
 // needs the chain-delta workspace (BlockCall::hc_ws / hc_span)
-constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC; }
+constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC || op == OP_COMPRESS_HC_DEST; }
 
 // One block operation, from its entry point to launch_block.
 struct BlockCall {
   Op op;
-  int param = 0;                    // OP_COMPRESS_HC: the level (hc_level); OP_COMPRESS_ACCEL: the acceleration (accel_clamp, >= 2)
+  int param = 0;                    // op_uses_hc_ws: the level (hc_level); OP_COMPRESS_ACCEL: the acceleration (accel_clamp, >= 2)
   const int32_t* target = nullptr;  // OP_DECODE_PARTIAL: per-block target sizes; nullptr: dst_cap already is partial_room (host path)
   int32_t* consumed = nullptr;      // op_has_consumed: the input consumed per block
   void* hc_ws = nullptr;            // op_uses_hc_ws: device workspace for hc_span bytes of source; nullptr: launch_block learns the
@@ -223,11 +224,13 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
     case OP_DECODE_SAFE: return launch_decode(a, true, st);
     case OP_DECODE_FAST: return launch_decode(a, false, st);
     case OP_DECODE_PARTIAL: return lz4hip::launch_decompress_partial(a, c.target ? c.target : a.dst_cap, st);
-    case OP_COMPRESS_HC: {
+    case OP_COMPRESS_HC:
+    case OP_COMPRESS_HC_DEST: {
       void* ws = c.hc_ws;
       uint64_t span = c.hc_span;
       if (!ws) { const int rc = hc_workspace(a, c.param, st, &ws, &span); if (rc) return rc; }
-      const int e = lz4hip::launch_compress_hc(a, c.param, ws, span, st);
+      const int e = c.op == OP_COMPRESS_HC ? lz4hip::launch_compress_hc(a, c.param, ws, span, st)
+                                           : lz4hip::launch_compress_hc_dest(a, c.consumed, c.param, ws, span, st);
       if (!c.hc_ws) (void)hipFreeAsync(ws, st);
       return e;
     }
@@ -750,6 +753,7 @@ struct Combiner {
 // accelerated compress's per (clamped) acceleration -- created on first use and kept (at most 65536 of them)
 Combiner g_comb[OP_COUNT];
 Combiner g_hc_comb[13];   // [HC level]
+Combiner g_hc_dest_comb[13];   // [HC level]: LZ4_compress_HC_destSize, coalesced only with destSize calls of the same level
 std::mutex g_accel_comb_mu;
 std::map<int, Combiner> g_accel_comb;
 // nullptr: no combiner for this call (an operation or level outside the tables); may throw (the map's allocation)
@@ -759,6 +763,7 @@ Combiner* combiner_for(const BlockCall& c) {
     return &g_accel_comb[c.param];   // (std::map: references stay valid while other entries are added)
   }
   if (c.op == OP_COMPRESS_HC) return c.param >= 1 && c.param <= 12 ? &g_hc_comb[c.param] : nullptr;
+  if (c.op == OP_COMPRESS_HC_DEST) return c.param >= 1 && c.param <= 12 ? &g_hc_dest_comb[c.param] : nullptr;
   return (int)c.op >= 0 && (int)c.op < OP_COUNT ? &g_comb[c.op] : nullptr;
 }
 
@@ -1311,6 +1316,13 @@ int lz4hip_compress_hc_batch(const uint8_t* src, const uint64_t* src_off, const 
   if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
   return host_batch({OP_COMPRESS_HC, lv}, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
 }
+int lz4hip_compress_hc_dest_size_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                       const uint64_t* dst_off, const int32_t* target_size, int32_t* out_len, int32_t* src_consumed,
+                                       uint32_t n, int level) {
+  int lv;
+  if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
+  return host_batch({OP_COMPRESS_HC_DEST, lv, nullptr, src_consumed}, src, src_off, src_len, dst, dst_off, target_size, out_len, n);
+}
 int lz4hip_xxh32_batch(const uint8_t* buf, const uint64_t* off, const int32_t* len, uint32_t seed, uint32_t* out, uint32_t n) {
   return host_xxh<uint32_t>(false, buf, off, len, seed, out, n);
 }
@@ -1368,6 +1380,21 @@ int lz4hip_compress_hc_batch_dev(const uint8_t* src, const uint64_t* src_off, co
   if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
   return dev_batch({OP_COMPRESS_HC, lv}, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream);
 }
+int lz4hip_compress_hc_dest_size_batch_dev_ws(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                              const uint64_t* dst_off, const int32_t* target_size, int32_t* out_len, int32_t* src_consumed,
+                                              uint32_t n, int level, int device, void* stream, uint64_t src_span, void* ws, size_t ws_bytes) {
+  int lv;
+  if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
+  return dev_batch({OP_COMPRESS_HC_DEST, lv, nullptr, src_consumed, ws, src_span}, {src, src_off, src_len, dst, dst_off, target_size, out_len, n},
+                   device, stream, !ws ? kNullArg : ws_bytes < lz4hip::hc_ws_bytes(src_span, n, lv) ? "HC workspace too small for the source span" : nullptr);
+}
+int lz4hip_compress_hc_dest_size_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                           const uint64_t* dst_off, const int32_t* target_size, int32_t* out_len, int32_t* src_consumed,
+                                           uint32_t n, int level, int device, void* stream) {
+  int lv;
+  if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
+  return dev_batch({OP_COMPRESS_HC_DEST, lv, nullptr, src_consumed}, {src, src_off, src_len, dst, dst_off, target_size, out_len, n}, device, stream);
+}
 int lz4hip_xxh32_batch_dev(const uint8_t* buf, const uint64_t* off, const int32_t* len, uint32_t seed, uint32_t* out, uint32_t n, int device, void* stream) {
   return on_device(device, n == 0, !buf || !off || !len || !out ? kNullArg : nullptr,
                    [&] { return lz4hip::launch_xxh32(buf, off, len, seed, out, n, stream); });
@@ -1406,6 +1433,15 @@ int lz4hip_compress_hc(const uint8_t* src, int src_len, uint8_t* dst, int dst_ca
   int lv;
   if (hc_level(level, &lv)) return LZ4HIP_LIB_ERROR(LZ4HIP_E_UNSUPPORTED);
   return single({OP_COMPRESS_HC, lv}, src, src_len, dst, dst_cap);
+}
+int lz4hip_compress_hc_dest_size(const uint8_t* src, int* src_size, uint8_t* dst, int target_size, int level) {
+  if (!src_size) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, "null src_size"));
+  int lv;
+  if (hc_level(level, &lv)) return LZ4HIP_LIB_ERROR(LZ4HIP_E_UNSUPPORTED);
+  int32_t c = 0;
+  const int r = single({OP_COMPRESS_HC_DEST, lv, nullptr, &c}, src, *src_size, dst, target_size);
+  if (!LZ4HIP_IS_LIB_ERROR(r)) *src_size = c;
+  return r;
 }
 int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap) { return single({OP_DECODE_SAFE}, src, src_len, dst, dst_cap); }
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len) { return single({OP_DECODE_FAST}, src, src_cap, dst, dst_len); }

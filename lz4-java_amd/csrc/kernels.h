@@ -44,6 +44,11 @@ int launch_compress_fast_prof(const BatchArgs& a, uint64_t* prof, int core, void
 int launch_hc_span(const uint64_t* src_off, const int32_t* src_len, uint32_t n, uint64_t* out_dev, void* stream);
 size_t hc_ws_bytes(uint64_t span, uint32_t n_blocks, int level);
 int launch_compress_hc(const BatchArgs& a, int level, void* ws, uint64_t span, void* stream);
+// LZ4_compress_HC_destSize: a.dst_cap[i] is the target size; out[i] = bytes written, consumed[i] = input consumed (src_len[i] where
+// liblz4 returns 0 without touching it).  hc_build_kernel as it is, then hc_parse_dest_kernel (the parser's FILL switch); same
+// workspace as launch_compress_hc.  The parse of a block stops once its target is full, so the parse time follows the input
+// consumed; the delta[] build still covers the whole block.
+int launch_compress_hc_dest(const BatchArgs& a, int32_t* consumed, int level, void* ws, uint64_t span, void* stream);
 // after a compress launch: moves the out[i] > 0 useful bytes of every slot to pack + sum(out[0..i)); poff: u64[n] scratch
 int launch_pack(const BatchArgs& a, uint64_t* poff, uint8_t* pack, void* stream);
 // Device-side container assembly (kernels.hip): the data blocks of an LZ4 Frame (kind 0; block_checksum: XXH32 of each stored

@@ -258,8 +258,16 @@ struct HcSearch {
 
 // ---------------------------------------------------------------------------------------------------
 // phase 2: the lazy parse + sequence emission (one wavefront per block)
+//
+// HcParse<W, FILL = true> is liblz4's fillOutput (LZ4_compress_HC_destSize): `cap` is the target size t.  The parse is the default
+// one up to the first sequence that fails one of liblz4's two output checks, which fill mode always makes, against t - 5
+// (LASTLITERALS are held back).  That sequence is not an error (over()): if its literals still fit before t - 8, its match is cut
+// to what the remaining length bytes can say and written without a check, provided the cut match still leaves liblz4's MFLIMIT
+// rule intact; then the last literals follow, against t itself, truncated to fit.  `consumed` is the input that the output covers.
+// Every store is exact (st8 / put_run / w.copy write the bytes of the sequence and nothing after them), so nothing at or past t is
+// touched.  FILL = false is what every other instantiation uses: the code it generates does not change.
 // ---------------------------------------------------------------------------------------------------
-template <class W>
+template <class W, bool FILL = false>
 struct HcParse {
   using VU = typename W::VU;
   using VU64 = typename W::VU64;
@@ -273,6 +281,7 @@ struct HcParse {
   int cap;
   bool limited;
   int op = 0, anchor = 0;
+  int consumed = 0;  // (FILL) input bytes the output covers, once the block is done
 
   // LZ4HC_InsertAndGetWiderMatch for the wave-uniform searches of the lazy evaluation.  s.wider() spends three dependent
   // loads per chain node (link, 2-byte pre-test, 4 bytes, then the counts); here the wave first walks the links alone (one
@@ -355,12 +364,20 @@ struct HcParse {
     }
   }
 
-  // LZ4HC_encodeSequence; returns true on output overflow
+  // LZ4HC_encodeSequence; returns true on output overflow (op, ip and anchor are then unchanged).  FILL: liblz4's two checks
+  // against the lowered limit t - 5 (below 0 for t < 5: signed), always made; CHECK = false is its `notLimited` call of over()
+  template <bool CHECK = true>
   LZ4HIP_DEV bool encode(int& ip, int ml, int ref) {
     const uint32_t lit = (uint32_t)(ip - anchor), mc = (uint32_t)(ml - 4);
     const uint32_t nlx = lit >= 15u ? (lit - 15u) / 255u + 1u : 0u;
     const uint32_t nmx = mc >= 15u ? (mc - 15u) / 255u + 1u : 0u;
-    if (limited) {
+    if constexpr (FILL) {
+      if (CHECK) {
+        const int64_t lim = (int64_t)cap - 5;
+        if ((int64_t)op + 1 + lit / 255u + lit + (2 + 1 + 5) > lim) return true;
+        if ((int64_t)op + 1 + nlx + lit + 2 + mc / 255u + (1 + 5) > lim) return true;
+      }
+    } else if (limited) {
       if ((uint64_t)op + 1u + lit / 255u + lit + (2u + 1u + 5u) > (uint64_t)cap) return true;
       if ((uint64_t)op + 1u + nlx + lit + 2u + mc / 255u + (1u + 5u) > (uint64_t)cap) return true;
     }
@@ -422,6 +439,7 @@ struct HcParse {
   // table walk is wave-uniform scalar work (all lanes redundantly, like the lazy parse of levels 1..9), the searches are
   // s.wider() with liblz4's pattern analysis and chain swap, the sequence writer is the cooperative encode() above.
   LZ4HIP_DEV int last_literals() {
+    if constexpr (FILL) return last_literals_fill();
     const uint32_t last = (uint32_t)(n - anchor);
     const uint32_t ll_add = (last + 255u - 15u) / 255u;
     if (limited && (uint64_t)op + 1u + ll_add + last > (uint64_t)cap) return 0;
@@ -430,6 +448,42 @@ struct HcParse {
     if (last >= 15u) put_run(o + 1u, last - 15u);
     w.copy(dst, o + 1u + ll_add, src, (uint32_t)anchor, last);
     return (int)(o + 1u + ll_add + last);
+  }
+  // FILL: liblz4's last literals under fillOutput, against the target itself: a run that does not fit is shortened to fill it
+  LZ4HIP_DEV int last_literals_fill() {
+    uint32_t last = (uint32_t)(n - anchor);
+    if ((uint64_t)op + 1u + (last + 255u - 15u) / 255u + last > (uint64_t)cap) {
+      last = (uint32_t)(cap - op) - 1u;  // (op < cap: a written sequence leaves at least 6 bytes, the start at least 1)
+      last -= (last + 256u - 15u) / 256u;
+    }
+    consumed = anchor + (int)last;
+    const uint32_t ll_add = (last + 255u - 15u) / 255u;
+    const uint32_t o = (uint32_t)op;
+    w.st8(dst, VU(o), VU((last < 15u ? last : 15u) << 4), w.lane() == 0u);
+    if (last >= 15u) put_run(o + 1u, last - 15u);
+    w.copy(dst, o + 1u + ll_add, src, (uint32_t)anchor, last);
+    return (int)(o + 1u + ll_add + last);
+  }
+
+  // what an encode() that returned true makes of a FILL block (every other block returns 0 there: it does not fit): liblz4's
+  // _dest_overflow with the pending match {ml, ref} at ip -- cut and written if its literals fit, dropped otherwise -- then the
+  // last literals.  Wave-uniform, like encode().  (The callers say `FILL ? over(..) : 0`: with the call behind a function the
+  // compiler allocated two scalar registers of hc_parse_kernel differently.)
+  LZ4HIP_DEV int over(int ip, int ml, int ref) {
+    if constexpr (FILL) {
+      const int64_t lim = (int64_t)cap - 5;
+      const int64_t ll = ip - anchor;
+      const int64_t lit_end = (int64_t)op + 1 + (ll + 240) / 255 + ll;  // op + ll_totalCost
+      const int64_t max_lit_pos = lim - 3;                               // 2 for the offset, 1 for the token
+      if (lit_end <= max_lit_pos) {
+        const int64_t max_ml = 4 + 14 + (max_lit_pos - lit_end) * 255;
+        if ((int64_t)ml > max_ml) ml = (int)max_ml;
+        if ((lim + 5) - (lit_end + 2) - 1 + ml >= 12) encode<false>(ip, ml, ref);
+      }
+      return last_literals();
+    } else {
+      return 0;
+    }
   }
 
   LZ4HIP_DEV static int lit_price(int litlen) { return litlen >= 15 ? litlen + 1 + (litlen - 15) / 255 : litlen; }
@@ -460,7 +514,7 @@ struct HcParse {
         const int first_len = find_longer(ip, matchlimit, 3, first_off);
         if (first_len == 0) { ip++; continue; }
         if (first_len > sufficient) {  // good enough: immediate encoding
-          if (encode(ip, first_len, ip - first_off)) return 0;
+          if (encode(ip, first_len, ip - first_off)) return FILL ? over(ip, first_len, ip - first_off) : 0;
           continue;
         }
         for (int r = 0; r < 4; r++) { o_ml[r] = 1; o_off[r] = 0; o_ll[r] = llen + r; price[r] = lit_price(llen + r); }
@@ -535,7 +589,7 @@ struct HcParse {
           const int m = o_ml[r], off = o_off[r];
           if (m == 1) { ip++; r++; continue; }  // literal
           r += m;
-          if (encode(ip, m, ip - off)) return 0;
+          if (encode(ip, m, ip - off)) return FILL ? over(ip, m, ip - off) : 0;
         }
       }
     }
@@ -554,7 +608,7 @@ struct HcParse {
         if (ip + ml <= mflimit) ml2 = wider_wave(ip + ml - 2, ip, matchlimit, ml, ref2, start2);
         else ml2 = ml;
         if (ml2 == ml) {  // no better match: encode ML1
-          if (encode(ip, ml, ref)) return 0;
+          if (encode(ip, ml, ref)) return FILL ? over(ip, ml, ref) : 0;
           continue;
         }
         if (start0 < ip) {
@@ -576,9 +630,9 @@ struct HcParse {
         else ml3 = ml2;
         if (ml3 == ml2) {  // no better match: encode ML1 and ML2
           if (start2 < ip + ml) ml = start2 - ip;
-          if (encode(ip, ml, ref)) return 0;
+          if (encode(ip, ml, ref)) return FILL ? over(ip, ml, ref) : 0;
           ip = start2;
-          if (encode(ip, ml2, ref2)) return 0;
+          if (encode(ip, ml2, ref2)) return FILL ? over(ip, ml2, ref2) : 0;
           continue;
         }
         if (start3 < ip + ml + 3) {  // not enough space for match 2: remove it
@@ -588,7 +642,7 @@ struct HcParse {
               start2 += correction; ref2 += correction; ml2 -= correction;
               if (ml2 < 4) { start2 = start3; ref2 = ref3; ml2 = ml3; }
             }
-            if (encode(ip, ml, ref)) return 0;
+            if (encode(ip, ml, ref)) return FILL ? over(ip, ml, ref) : 0;
             ip = start3; ref = ref3; ml = ml3;
             start0 = start2; ref0 = ref2; ml0 = ml2;
             goto search2;
@@ -607,7 +661,7 @@ struct HcParse {
             ml = start2 - ip;
           }
         }
-        if (encode(ip, ml, ref)) return 0;
+        if (encode(ip, ml, ref)) return FILL ? over(ip, ml, ref) : 0;
         ip = start2; ref = ref2; ml = ml2;
         start2 = start3; ref2 = ref3; ml2 = ml3;
         goto search3;

@@ -104,6 +104,17 @@ class LZ4HCHIPCompressor final : public LZ4Compressor {
     if (result <= 0) throw LZ4Exception("");
     return result;
   }
+  // liblz4's LZ4_compress_HC_destSize at this compressor's level: compresses as much of src[srcOff, srcOff + srcLen) as fits in
+  // exactly targetDestSize bytes at dest + destOff; returns the bytes written and sets srcLen to the source bytes they cover
+  // (lz4hip_compress_hc_dest_size)
+  int compressDestSize(const bytes& src, int srcOff, int& srcLen, bytes& dest, int destOff, int targetDestSize) const {
+    util::checkRange(src, srcOff, srcLen);
+    util::checkRange(dest, destOff, targetDestSize);
+    int size = srcLen;
+    const int result = libCheck(lz4hip_compress_hc_dest_size(src.data() + srcOff, &size, dest.data() + destOff, targetDestSize, level_));
+    srcLen = size;
+    return result;
+  }
 };
 
 class LZ4SafeDecompressor {

@@ -28,6 +28,9 @@ import java.nio.ByteBuffer;
 /**
  * High-compression {@link LZ4Compressor} of the "HIP" family (twin of LZ4HCJNICompressor.java:30-89).
  * LZ4Factory needs the INSTANCE field and the declared (int) constructor (LZ4Factory.java:193-202).
+ *
+ * {@code compressDestSize}: liblz4's {@code LZ4_compress_HC_destSize} at this compressor's level -- as much of the source as
+ * fits in exactly {@code targetDestSize} bytes.
  */
 final class LZ4HCHIPCompressor extends LZ4Compressor {
 
@@ -69,5 +72,67 @@ final class LZ4HCHIPCompressor extends LZ4Compressor {
       return result;
     }
     return LZ4Factory.safeInstance().highCompressor(compressionLevel).compress(src, srcOff, srcLen, dest, destOff, maxDestLen);
+  }
+
+  private int nativeDestSize(byte[] srcArr, ByteBuffer srcBuf, int srcOff, int srcLen, byte[] destArr, ByteBuffer destBuf, int destOff,
+      int targetDestSize, int[] srcConsumed) {
+    if (srcConsumed.length < 1) {
+      throw new IllegalArgumentException("srcConsumed must hold one element");
+    }
+    final int[] size = {srcLen};
+    final int result = LZ4HIPJNI.LZ4HIP_compressHC_dest_size(srcArr, srcBuf, srcOff, size, destArr, destBuf, destOff, targetDestSize,
+                                                             compressionLevel);
+    if (result < 0) {
+      throw new LZ4Exception("liblz4hip: " + LZ4HIPJNI.lastError());
+    }
+    srcConsumed[0] = size[0];
+    return result;
+  }
+
+  /**
+   * Compresses as much of {@code src[srcOff, srcOff+srcLen)} as fits in exactly {@code targetDestSize} bytes at
+   * {@code dest[destOff..)}: returns the bytes written and sets {@code srcConsumed[0]} to the source bytes they cover.
+   */
+  public int compressDestSize(byte[] src, int srcOff, int srcLen, byte[] dest, int destOff, int targetDestSize, int[] srcConsumed) {
+    checkRange(src, srcOff, srcLen);
+    checkRange(dest, destOff, targetDestSize);
+    return nativeDestSize(src, null, srcOff, srcLen, dest, null, destOff, targetDestSize, srcConsumed);
+  }
+
+  /** {@link #compressDestSize(byte[], int, int, byte[], int, int, int[])} on buffers (positions and limits are not used). */
+  public int compressDestSize(ByteBuffer src, int srcOff, int srcLen, ByteBuffer dest, int destOff, int targetDestSize, int[] srcConsumed) {
+    checkNotReadOnly(dest);
+    checkRange(src, srcOff, srcLen);
+    checkRange(dest, destOff, targetDestSize);
+    if ((src.hasArray() || src.isDirect()) && (dest.hasArray() || dest.isDirect())) {
+      byte[] srcArr = null, destArr = null;
+      ByteBuffer srcBuf = null, destBuf = null;
+      if (src.hasArray()) {
+        srcArr = src.array();
+        srcOff += src.arrayOffset();
+      } else {
+        srcBuf = src;
+      }
+      if (dest.hasArray()) {
+        destArr = dest.array();
+        destOff += dest.arrayOffset();
+      } else {
+        destBuf = dest;
+      }
+      return nativeDestSize(srcArr, srcBuf, srcOff, srcLen, destArr, destBuf, destOff, targetDestSize, srcConsumed);
+    }
+    // neither array-backed nor direct: through byte[] copies (no other family has this call to fall back to)
+    final byte[] srcArr = new byte[srcLen];
+    final byte[] destArr = new byte[targetDestSize];
+    final ByteBuffer s = src.duplicate();
+    s.clear();
+    s.position(srcOff);
+    s.get(srcArr, 0, srcLen);
+    final int result = compressDestSize(srcArr, 0, srcLen, destArr, 0, targetDestSize, srcConsumed);
+    final ByteBuffer d = dest.duplicate();
+    d.clear();
+    d.position(destOff);
+    d.put(destArr, 0, result);
+    return result;
   }
 }

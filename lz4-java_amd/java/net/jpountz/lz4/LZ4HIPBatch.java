@@ -105,6 +105,23 @@ public final class LZ4HIPBatch {
     }
   }
 
+  /**
+   * liblz4's {@code LZ4_compress_HC_destSize} per block at HC level {@code level}: as much of block i as fits in exactly
+   * {@code targetSize[i]} bytes, written to the slot {@code dest[destOff[i], destOff[i]+targetSize[i])}.  outLen[i]: bytes written
+   * (0 for an empty target); srcConsumed[i]: the source bytes they cover.
+   */
+  public static void compressHCDestSize(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetSize,
+      int[] outLen, int[] srcConsumed, int level) {
+    check(src, dest, srcOff, srcLen, destOff, targetSize, outLen);
+    if (srcConsumed.length < srcOff.length) {
+      throw new IllegalArgumentException("per-block arrays must have the same length");
+    }
+    final int rc = LZ4HIPJNI.LZ4HIP_batchHCDestSize(src, srcOff, srcLen, dest, destOff, targetSize, outLen, srcConsumed, srcOff.length, level);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
   /** outLen[i] &gt;= 0: decompressed size; &lt; 0: -(input position)-1. */
   public static void decompressSafe(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen) {
     run(1, 0, src, srcOff, srcLen, dest, destOff, destCap, outLen);

@@ -57,6 +57,11 @@ enum LZ4HIPJNI {
                                               byte[] destArray, ByteBuffer destBuffer, int destOff, int targetDestSize);
   static native int LZ4HIP_compressHC(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
                                       byte[] destArray, ByteBuffer destBuffer, int destOff, int maxDestLen, int compressionLevel);
+  /* LZ4_compress_HC_destSize at compressionLevel: the arguments, NULL / pinning rules and return conventions of
+   * LZ4HIP_compress_dest_size */
+  static native int LZ4HIP_compressHC_dest_size(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int[] srcSize,
+                                                byte[] destArray, ByteBuffer destBuffer, int destOff, int targetDestSize,
+                                                int compressionLevel);
   static native int LZ4HIP_decompress_fast(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcCap,
                                            byte[] destArray, ByteBuffer destBuffer, int destOff, int destLen);
   static native int LZ4HIP_decompress_safe(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
@@ -81,6 +86,9 @@ enum LZ4HIPJNI {
    * destCap[i])); outLen = liblz4's return values.  Returns 0 or a negative lz4hip_status (a null argument: LZ4HIP_E_ARG). */
   static native int LZ4HIP_batchSafePartial(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetLen,
                                             int[] destCap, int[] outLen, int nBlocks);
+  /* LZ4_compress_HC_destSize per block at HC level `level`: the arguments and return conventions of LZ4HIP_batchDestSize */
+  static native int LZ4HIP_batchHCDestSize(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetSize,
+                                           int[] outLen, int[] srcConsumed, int nBlocks, int level);
 
   /** Container blocks assembled on the device (LZ4HIPBatch.containerBlocks); returns bytes written or the negative lz4hip_status. */
   static native long LZ4HIP_containerBlocks(int kind, int flags, int level, ByteBuffer src, long srcOff, long len, int blockSize,

@@ -118,12 +118,13 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1fast_1ac
   return run_single(env, 4, acceleration, srcArray, srcBuffer, srcOff, srcLen, destArray, destBuffer, destOff, maxDestLen);
 }
 
-/* LZ4_compress_destSize: srcSize[0] = the block size in, the input consumed out; returns the bytes written (<= targetDestSize) or a
- * library error (srcSize[0] untouched).  Same staging as LZ4HIP_compress_fast; a NULL or empty srcSize is LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
-JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1dest_1size(JNIEnv* env, jclass cls, jbyteArray srcArray, jobject srcBuffer,
-    jint srcOff, jintArray srcSize, jbyteArray destArray, jobject destBuffer, jint destOff, jint targetDestSize) {
-  (void)cls;
-  if (srcSize == NULL || (*env)->GetArrayLength(env, srcSize) < 1) return lz4hip_compress_dest_size(NULL, NULL, NULL, 0);
+/* LZ4_compress_destSize (hc == 0) / LZ4_compress_HC_destSize at `level` (hc != 0): srcSize[0] = the block size in, the input
+ * consumed out; returns the bytes written (<= targetDestSize) or a library error (srcSize[0] untouched).  Same staging as
+ * LZ4HIP_compress_fast; a NULL or empty srcSize is LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
+static jint dest_size_single(JNIEnv* env, int hc, int level, jbyteArray srcArray, jobject srcBuffer, jint srcOff, jintArray srcSize,
+    jbyteArray destArray, jobject destBuffer, jint destOff, jint targetDestSize) {
+  if (srcSize == NULL || (*env)->GetArrayLength(env, srcSize) < 1)
+    return hc ? lz4hip_compress_hc_dest_size(NULL, NULL, NULL, 0, level) : lz4hip_compress_dest_size(NULL, NULL, NULL, 0);
   jint* sz = (*env)->GetIntArrayElements(env, srcSize, NULL);
   if (sz == NULL) { throw_OOM(env); return 0; }
   const jint srcLen = sz[0];
@@ -140,13 +141,24 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1dest_1si
     return 0;
   }
   int consumed = srcLen;
-  const int result = lz4hip_compress_dest_size(in.p, &consumed, out.p, targetDestSize);
+  const int result = hc ? lz4hip_compress_hc_dest_size(in.p, &consumed, out.p, targetDestSize, level)
+                        : lz4hip_compress_dest_size(in.p, &consumed, out.p, targetDestSize);
   region_out(env, NULL, 0, 0, &in);
   sz[0] = consumed;   /* (untouched on a library error) */
   (*env)->ReleaseIntArrayElements(env, srcSize, sz, 0);
   const jint produced = !LZ4HIP_IS_LIB_ERROR(result) && result > 0 ? result : 0;
   if (region_out(env, destArray, destOff, produced, &out) != 0) { throw_OOM(env); return 0; }
   return result;
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1dest_1size(JNIEnv* env, jclass cls, jbyteArray srcArray, jobject srcBuffer,
+    jint srcOff, jintArray srcSize, jbyteArray destArray, jobject destBuffer, jint destOff, jint targetDestSize) {
+  (void)cls;
+  return dest_size_single(env, 0, 0, srcArray, srcBuffer, srcOff, srcSize, destArray, destBuffer, destOff, targetDestSize);
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compressHC_1dest_1size(JNIEnv* env, jclass cls, jbyteArray srcArray,
+    jobject srcBuffer, jint srcOff, jintArray srcSize, jbyteArray destArray, jobject destBuffer, jint destOff, jint targetDestSize, jint level) {
+  (void)cls;
+  return dest_size_single(env, 1, level, srcArray, srcBuffer, srcOff, srcSize, destArray, destBuffer, destOff, targetDestSize);
 }
 
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compressHC(JNIEnv* env, jclass cls, jbyteArray srcArray, jobject srcBuffer,
@@ -261,6 +273,20 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchDestSize(JNIE
   jint rc = batch_pin(env, src, dest, &b);
   if (rc != 0) return rc;
   rc = lz4hip_compress_dest_size_batch(b.src, b.a[0].p, b.a[1].p, b.dst, b.a[2].p, b.a[3].p, b.a[4].p, b.a[5].p, (uint32_t)n);
+  batch_release(env, &b);
+  return rc;
+}
+
+/* LZ4_compress_HC_destSize at HC level `level` over many blocks (lz4hip_compress_hc_dest_size_batch): the arguments, results and
+ * NULL rule of LZ4HIP_batchDestSize */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchHCDestSize(JNIEnv* env, jclass cls, jobject src, jlongArray srcOff,
+    jintArray srcLen, jobject dest, jlongArray destOff, jintArray targetSize, jintArray outLen, jintArray srcConsumed, jint n, jint level) {
+  (void)cls;
+  batch_args_t b = {NULL, NULL, 6, {{srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT}, {targetSize, INTS, JNI_ABORT}, {outLen, INTS, 0},
+                                    {srcConsumed, INTS, 0}}};
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  rc = lz4hip_compress_hc_dest_size_batch(b.src, b.a[0].p, b.a[1].p, b.dst, b.a[2].p, b.a[3].p, b.a[4].p, b.a[5].p, (uint32_t)n, level);
   batch_release(env, &b);
   return rc;
 }

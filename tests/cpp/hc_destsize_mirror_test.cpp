@@ -1,0 +1,45 @@
+// tests/cpp/hc_destsize_mirror_test.cpp -- exercises LZ4HCHIPCompressor::compressDestSize of the C++ host mirror
+// (lz4-java_amd/host/lz4hip.hpp).  Built and run by tests/test_gpu_hc_destsize.py with an input file, a target size and an HC level:
+//   hc_destsize_mirror_test <input> <target> <out> <level>   writes the stream to <out> and prints "<written> <consumed>"
+// Exit code 0 = all good; with no GPU it must fail loudly (exit code 3).
+#include <cstdio>
+#include <stdexcept>
+#include "../../lz4-java_amd/host/lz4hip.hpp"
+
+using namespace net::jpountz;
+
+int main(int argc, char** argv) {
+  if (argc < 5) { fprintf(stderr, "usage: hc_destsize_mirror_test <input> <target> <out> <level>\n"); return 2; }
+  FILE* f = fopen(argv[1], "rb");
+  if (!f) return 2;
+  bytes in;
+  for (int c; (c = fgetc(f)) != EOF;) in.push_back((uint8_t)c);
+  fclose(f);
+  const int t = atoi(argv[2]);
+  try {
+    const lz4::LZ4HCHIPCompressor c(atoi(argv[4]));
+    const int off = 3;                          // regions away from byte 0 of both vectors
+    bytes src(in.size() + off);
+    std::copy(in.begin(), in.end(), src.begin() + off);
+    bytes dst((size_t)t + 16, 0xEE);
+    int len = (int)in.size();
+    const int w = c.compressDestSize(src, off, len, dst, 5, t);
+    if (w <= 0 || w > t || len <= 0 || len > (int)in.size()) return 1;
+    for (size_t i = 0; i < dst.size(); i++)
+      if ((i < 5 || i >= (size_t)(5 + w)) && dst[i] != 0xEE) { fprintf(stderr, "byte %zu outside the output changed\n", i); return 1; }
+    // the stream decodes to exactly the consumed prefix
+    if (lz4::LZ4Factory::hipInstance().safeDecompressor().decompress(bytes(dst.begin() + 5, dst.begin() + 5 + w), len) !=
+        bytes(in.begin(), in.begin() + len)) return 1;
+    bool threw = false;
+    try { int l2 = (int)in.size(); (void)c.compressDestSize(src, off, l2, dst, 10, t + 10); } catch (const std::out_of_range&) { threw = true; }
+    if (!threw) return 1;
+    FILE* o = fopen(argv[3], "wb");
+    if (!o || fwrite(dst.data() + 5, 1, (size_t)w, o) != (size_t)w) return 1;
+    fclose(o);
+    printf("%d %d\n", w, len);
+    return 0;
+  } catch (const lz4::LZ4Exception& e) {
+    fprintf(stderr, "%s\n", e.what());
+    return 3;
+  }
+}
