@@ -184,6 +184,23 @@ int lz4hip_compress_hc_dest_size_batch(const uint8_t* src, const uint64_t* src_o
 int lz4hip_decompress_safe_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                  uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                  int32_t* out_len, uint32_t n_blocks);
+/* DECODED SIZE, NO OUTPUT BUFFER: out_len[i] is the value LZ4_decompress_safe(src_i, dst, src_len[i], dst_cap[i]) of liblz4 1.9.3
+ * returns -- the decoded size, or -(input position) - 1 -- for every input, valid or malformed.  There is no dst: that value never
+ * depends on the bytes a destination holds, only on the stream, its length and the capacity, so the kernel moves through the block
+ * without copying anything.  For a batch of blocks whose decoded sizes are unknown or untrusted this replaces a decode into
+ * worst-case slots (a block can expand 255 times).
+ *   - dst_cap[i] is an argument, not a buffer size: liblz4's three tiers are chosen by the distance to the output's end, so which
+ *     malformed streams are accepted depends on it.  out_len[i] >= 0 means that lz4hip_decompress_safe* with that capacity succeeds
+ *     and returns exactly that number: the query is a validator too;
+ *   - to learn the size of a block of unknown size pass an upper bound (at most 255 * src_len[i], or the format's block limit);
+ *   - a negative src_len[i] or dst_cap[i] gives -1, as for the decoders;
+ *   - one kernel, decode_size_kernel: a wavefront per block, the stream read once through an LDS ring (it reads the compressed
+ *     bytes and writes 4 bytes per block); no route, no decode_* knob applies;
+ *   - the host batch shards over the initialised devices; it stages the streams only -- no destination is allocated or copied on
+ *     either side; library failures as the status of the call;
+ *   - single calls (lz4hip_decompressed_size) are coalesced with concurrent size queries only, through a combiner of their own. */
+int lz4hip_decompressed_size_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                   const int32_t* dst_cap, int32_t* out_len, uint32_t n_blocks);
 /* FAST DECODER CONTRACT.  src_cap[i] bounds how far block i may be read (the Java array/buffer length past srcOff):
  * unlike liblz4's LZ4_decompress_fast (which trusts the stream and reads wherever it points) this implementation never reads
  * beyond src_cap[i] bytes of the source slot and never before the destination slot.
@@ -256,6 +273,9 @@ int lz4hip_compress_hc_dest_size_batch_dev_ws(const uint8_t* src, const uint64_t
 int lz4hip_decompress_safe_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                      int32_t* out_len, uint32_t n_blocks, int device, void* stream);
+/* decoded sizes without an output buffer (see lz4hip_decompressed_size_batch), device pointers, asynchronous */
+int lz4hip_decompressed_size_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                       const int32_t* dst_cap, int32_t* out_len, uint32_t n_blocks, int device, void* stream);
 int lz4hip_decompress_fast_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_cap,
                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_len,
                                      int32_t* out_consumed, uint32_t n_blocks, int device, void* stream);
@@ -282,6 +302,7 @@ int lz4hip_compress_hc_dest_size(const uint8_t* src, int* src_size, uint8_t* dst
 int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap);
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len);
 int lz4hip_decompress_safe_partial(const uint8_t* src, int src_len, uint8_t* dst, int target_size, int dst_cap);  /* LZ4_decompress_safe_partial */
+int lz4hip_decompressed_size(const uint8_t* src, int src_len, int dst_cap);  /* what LZ4_decompress_safe(src, dst, src_len, dst_cap) would return; no dst */
 int lz4hip_xxh32(const uint8_t* buf, int len, uint32_t seed, uint32_t* out);
 int lz4hip_xxh64(const uint8_t* buf, int len, uint64_t seed, uint64_t* out);
 

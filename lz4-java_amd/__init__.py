@@ -53,6 +53,7 @@ C_ABI = {
     "lz4hip_decompress_safe_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_decompress_fast_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_decompress_safe_partial_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, _i32p, C.c_uint32]),
+    "lz4hip_decompressed_size_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
@@ -66,6 +67,7 @@ C_ABI = {
     "lz4hip_compress_hc_batch_dev_ws": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
     "lz4hip_decompress_safe_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_decompress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
+    "lz4hip_decompressed_size_batch_dev": (C.c_int, [C.c_void_p] * 5 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_xxh32_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_xxh64_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
@@ -76,6 +78,7 @@ C_ABI = {
     "lz4hip_decompress_safe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_safe_partial": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "lz4hip_decompressed_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_xxh32": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, _u32p]),
     "lz4hip_xxh64": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _u64p]),
     "lz4hip_xxh32_stream_create": (C.c_int, [C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -324,6 +327,18 @@ class LZ4SafeDecompressor:
         _check_range(dest, destOff, maxDestLen)
         sp, sk = _ro_ptr(src)
         result = _single(lib().lz4hip_decompress_safe_partial(sp + srcOff, srcLen, dp + destOff, targetLen, maxDestLen))
+        if result < 0:
+            raise LZ4Exception("Error decoding offset %d of input buffer" % (srcOff - result))
+        return result
+
+    def decompressedLength(self, src, srcOff, srcLen, maxDestLen):
+        """what decompress(src, srcOff, srcLen, dest, destOff, maxDestLen) would return -- the decoded size of the block in
+        src[srcOff:srcOff+srcLen] for a destination of maxDestLen bytes -- without a destination: nothing is decoded into memory
+        (lz4hip_decompressed_size).  A stream that decompress() rejects with that capacity raises the same LZ4Exception"""
+        _check_range(src, srcOff, srcLen)
+        _check_length(maxDestLen)
+        sp, sk = _ro_ptr(src)
+        result = _single(lib().lz4hip_decompressed_size(sp + srcOff, srcLen, maxDestLen))
         if result < 0:
             raise LZ4Exception("Error decoding offset %d of input buffer" % (srcOff - result))
         return result
@@ -740,6 +755,55 @@ class LZ4HIPBatch:
         return list(out[:n])
 
     @classmethod
+    def decompressedLengths(cls, src, srcOff, srcLen, maxDestLen):
+        """what LZ4_decompress_safe would return per block -- the decoded size of src[srcOff[i]:+srcLen[i]] for a capacity of
+        maxDestLen[i] bytes, or liblz4's negative code -- without any destination buffer (lz4hip_decompressed_size_batch; a list, or
+        an int32 array for numpy inputs).  A result >= 0 means decompressSafe with that capacity succeeds and returns that number"""
+        n = len(srcOff)
+        if not (len(srcLen) == len(maxDestLen) == n):
+            raise ValueError("per-block arrays differ in length")
+        cls._check_ranges(src, srcOff, srcLen)
+        for c in maxDestLen:
+            _check_length(c)
+        sp, sk = _ro_ptr(src)
+        out = (C.c_int32 * max(n, 1))()
+        _chk(lib().lz4hip_decompressed_size_batch(sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), _arr(C.c_int32, maxDestLen), out, n))
+        if hasattr(srcOff, "dtype"):
+            import numpy as np
+            return np.frombuffer(out, dtype=np.int32, count=n).copy()
+        return list(out[:n])
+
+    @classmethod
+    def decompressSafeSized(cls, src, srcOff, srcLen, maxDestLen):
+        """the batch twin of LZ4SafeDecompressor.decompress(src, maxDestLen) -> right-sized array: the sizes are queried first
+        (decompressedLengths), a buffer of exactly sum(max(size, 0)) bytes is allocated with the blocks packed back to back, and
+        every block that decodes is decoded into its slot.  Returns (buffer, offsets, lengths): lengths[i] is the decoded size, or
+        liblz4's negative code for a block that does not decode with capacity maxDestLen[i] -- such a block has an empty slot.
+        The worst-case n * maxDestLen bytes are never allocated"""
+        sizes = [int(v) for v in cls.decompressedLengths(src, srcOff, srcLen, maxDestLen)]
+        offsets, total = [], 0
+        for v in sizes:
+            offsets.append(total)
+            total += max(v, 0)
+        buf = bytearray(total)
+        good = [i for i, v in enumerate(sizes) if v >= 0]
+        if good:
+            # every slot is decoded with its own size as the capacity.  liblz4 accepts a conforming block that way; a stream it
+            # accepts only with room to spare (one that breaks the format's end rules, e.g. fewer than five last literals) comes
+            # back with another value and is decoded once more, alone, through a scratch of its maxDestLen
+            got = cls.decompressSafe(src, [srcOff[i] for i in good], [srcLen[i] for i in good], buf, [offsets[i] for i in good],
+                                     [sizes[i] for i in good])
+            for i, r in zip(good, got):
+                if int(r) == sizes[i]:
+                    continue
+                scratch = bytearray(max(int(maxDestLen[i]), 1))
+                r2 = cls.decompressSafe(src, [srcOff[i]], [srcLen[i]], scratch, [0], [int(maxDestLen[i])])[0]
+                if int(r2) != sizes[i]:
+                    raise LZ4HIPError("block %d: the decoder returned %d where the size query promised %d" % (i, int(r2), sizes[i]))
+                buf[offsets[i]:offsets[i] + sizes[i]] = scratch[:sizes[i]]
+        return buf, offsets, sizes
+
+    @classmethod
     def xxh32(cls, buf, off, length, seed=0):
         n = len(off)
         if len(length) != n:
@@ -882,6 +946,14 @@ class DeviceBatch:
         _chk(lib().lz4hip_decompress_safe_partial_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
                                                             dst_off.data_ptr(), target_len.data_ptr(), dst_cap.data_ptr(), out.data_ptr(),
                                                             src_off.numel(), dev, st))
+
+    @classmethod
+    def decoded_size(cls, src, src_off, src_len, dst_cap, out):
+        """the decoded-size query (lz4hip_decompressed_size_batch_dev): out[i] = what decompress_safe would return for block i with
+        capacity dst_cap[i]; there is no destination tensor and nothing but out is written"""
+        dev, st = cls._stream_dev(src)
+        _chk(lib().lz4hip_decompressed_size_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst_cap.data_ptr(),
+                                                      out.data_ptr(), src_off.numel(), dev, st))
 
     @classmethod
     def xxh32(cls, buf, off, length, seed, out):

@@ -74,8 +74,10 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // OP_DECODE_PARTIAL: LZ4_decompress_safe_partial; on the host path dst_cap already holds min(target, capacity), or -1 where one of
 // them is negative (partial_room), and the kernels get that array as the target too
 // OP_COMPRESS_HC_DEST: LZ4_compress_HC_destSize: OP_COMPRESS_HC's level and workspace, OP_COMPRESS_DEST's target and consumed sizes
-enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST };
-constexpr int OP_COUNT = OP_COMPRESS_HC_DEST + 1;   // (the last enumerator)
+// OP_DECODED_SIZE: the value LZ4_decompress_safe would return for (src, src_len, dst_cap), and no output buffer at all
+enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
+          OP_DECODED_SIZE };
+constexpr int OP_COUNT = OP_DECODED_SIZE + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
 constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
@@ -83,6 +85,8 @@ constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_
 constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
 // out[i] counts SOURCE bytes read: a block that succeeded filled its whole dst_cap[i]
 constexpr bool op_fills_capacity(Op op) { return op == OP_DECODE_FAST; }
+// writes no output buffer: dst and dst_off may be NULL, nothing is allocated, staged or copied back for them (dst_cap is an input)
+constexpr bool op_writes_no_output(Op op) { return op == OP_DECODED_SIZE; }
 // needs the chain-delta workspace (BlockCall::hc_ws / hc_span)
 constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC || op == OP_COMPRESS_HC_DEST; }
 
@@ -224,6 +228,7 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
     case OP_DECODE_SAFE: return launch_decode(a, true, st);
     case OP_DECODE_FAST: return launch_decode(a, false, st);
     case OP_DECODE_PARTIAL: return lz4hip::launch_decompress_partial(a, c.target ? c.target : a.dst_cap, st);
+    case OP_DECODED_SIZE: return lz4hip::launch_decoded_size(a, st);
     case OP_COMPRESS_HC:
     case OP_COMPRESS_HC_DEST: {
       void* ws = c.hc_ws;
@@ -269,7 +274,8 @@ int on_device(int device, bool empty, const char* arg_error, Body body) {
 
 // a block operation on device pointers; `extra_error`: the entry's check of what it takes beyond the seven arrays
 int dev_batch(const BlockCall& c, const lz4hip::BatchArgs& a, int device, void* stream, const char* extra_error = nullptr) {
-  const bool null_arg = !a.src || !a.src_off || !a.src_len || !a.dst || !a.dst_off || !a.dst_cap || !a.out || (op_has_consumed(c.op) && !c.consumed);
+  const bool null_arg = !a.src || !a.src_off || !a.src_len || (!op_writes_no_output(c.op) && (!a.dst || !a.dst_off)) || !a.dst_cap || !a.out ||
+                        (op_has_consumed(c.op) && !c.consumed);
   return on_device(device, a.n == 0, null_arg ? kNullArg : extra_error, [&] { return launch_block(c, a, (hipStream_t)stream); });
 }
 // the bytes block i of a partial decode may fill: min(target, capacity), or -1 (the kernels' -1) where one of them is negative
@@ -437,7 +443,8 @@ int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* 
   if (!pair) return bad("stream/event creation", e);
   struct Return { DevCtx& c; SlotPair* p; ~Return() { c.give_back(p); } } give_back_on_exit{cx, pair};
   auto slen_of = [&](uint32_t i) -> size_t { return src_len[i] > 0 ? (size_t)src_len[i] : 0; };
-  auto dcap_of = [&](uint32_t i) -> size_t { return dst_cap[i] > 0 ? (size_t)dst_cap[i] : 0; };
+  const bool no_output = op_writes_no_output(c.op);   // (dst / dst_off may be NULL: no destination bytes exist on either side)
+  auto dcap_of = [&](uint32_t i) -> size_t { return !no_output && dst_cap[i] > 0 ? (size_t)dst_cap[i] : 0; };
   const bool prof = getenv("LZ4HIP_HOST_PROF") != nullptr;   // developer diagnostics: where the time of the stages goes
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   std::atomic<double> t_wait{0}, t_d2h{0}, t_unpack{0};
@@ -472,7 +479,7 @@ int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* 
     }
     add(t_d2h, now() - c0); c0 = now();
     const bool fills = op_fills_capacity(c.op);
-    par_blocks(s.i0, s.i1, s.dst_bytes, [=, &s](uint32_t i) {
+    if (!no_output) par_blocks(s.i0, s.i1, s.dst_bytes, [=, &s](uint32_t i) {
       int64_t produced;   // (bytes past a result stay untouched in the caller's slot)
       if (fills) produced = out[i] > 0 ? dst_cap[i] : 0;
       else produced = out[i] > 0 ? out[i] : 0;
@@ -535,8 +542,8 @@ int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* 
       for (uint32_t t = 0; t < nb; t++) { s.so[t] = so; s.dof[t] = dofs; so += (slen_of(i + t) + 15u) & ~(size_t)15u; dofs += (dcap_of(i + t) + 15u) & ~(size_t)15u; } }
     const size_t nout = op_has_consumed(c.op) ? 2u : 1u;   // out[] (and consumed[])
     const size_t meta = (size_t)nb * (24u + 4u * nout);   // so[nb] u64 | dof[nb] u64 | src_len[nb] | dst_cap[nb] | out[nb] | (consumed[nb])
-    if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (e = s.h_dst.reserve(db + 64)) != hipSuccess || (e = s.h_meta.reserve(meta)) != hipSuccess ||
-        (e = s.d_src.reserve(sb + 64)) != hipSuccess || (e = s.d_dst.reserve(db + 64)) != hipSuccess || (e = s.d_meta.reserve(meta)) != hipSuccess ||
+    if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (!no_output && (e = s.h_dst.reserve(db + 64)) != hipSuccess) || (e = s.h_meta.reserve(meta)) != hipSuccess ||
+        (e = s.d_src.reserve(sb + 64)) != hipSuccess || (!no_output && (e = s.d_dst.reserve(db + 64)) != hipSuccess) || (e = s.d_meta.reserve(meta)) != hipSuccess ||
         (op_uses_hc_ws(c.op) && (e = s.d_ws.reserve(lz4hip::hc_ws_bytes(sb, nb, c.param))) != hipSuccess) ||
         (op_compresses(c.op) && ((e = s.d_pack.reserve(db + 64)) != hipSuccess || (e = s.d_poff.reserve((size_t)nb * 8u)) != hipSuccess))) {
       rc = bad("staging allocation", e);
@@ -560,7 +567,7 @@ int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* 
     if (sb && (e = hipMemcpyAsync(s.d_src.p, hs, sb, hipMemcpyHostToDevice, s.q_in)) != hipSuccess) { rc = bad("H2D src", e); break; }
     if ((e = hipMemcpyAsync(dm, hm, (size_t)nb * 24u, hipMemcpyHostToDevice, s.q_in)) != hipSuccess) { rc = bad("H2D meta", e); break; }
     if (!single && ((e = hipEventRecord(s.ev_in, s.q_in)) != hipSuccess || (e = hipStreamWaitEvent(s.st, s.ev_in, 0)) != hipSuccess)) { rc = bad("H2D event", e); break; }
-    lz4hip::BatchArgs a{(const uint8_t*)s.d_src.p, (const uint64_t*)dm, (const int32_t*)(dm + (size_t)nb * 16u), (uint8_t*)s.d_dst.p,
+    lz4hip::BatchArgs a{(const uint8_t*)s.d_src.p, (const uint64_t*)dm, (const int32_t*)(dm + (size_t)nb * 16u), no_output ? nullptr : (uint8_t*)s.d_dst.p,
                         (const uint64_t*)(dm + (size_t)nb * 8u), (const int32_t*)(dm + (size_t)nb * 20u), (int32_t*)(dm + (size_t)nb * 24u), nb};
     BlockCall dc = c;   // the call on this chunk's device arrays
     if (op_has_consumed(c.op)) dc.consumed = (int32_t*)(dm + (size_t)nb * 28u);
@@ -642,7 +649,7 @@ int host_batch(const BlockCall& c, const uint8_t* src, const uint64_t* src_off, 
   int rc = ensure_init();
   if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
   if (n == 0) return LZ4HIP_OK;
-  if (!src || !src_off || !src_len || !dst || !dst_off || !dst_cap || !out || (op_has_consumed(c.op) && !c.consumed))
+  if (!src || !src_off || !src_len || (!op_writes_no_output(c.op) && (!dst || !dst_off)) || !dst_cap || !out || (op_has_consumed(c.op) && !c.consumed))
     return fail(LZ4HIP_E_ARG, kNullArg);
   return fan_out(n, 64u, [&](int ord, uint32_t b0, uint32_t b1, std::string* err) {
     return host_shard(c, ord, src, src_off, src_len, dst, dst_off, dst_cap, out, b0, b1, err);
@@ -1302,6 +1309,10 @@ int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src
   for (uint32_t i = 0; i < n; i++) room[i] = partial_room(target_len[i], dst_cap[i]);
   return host_batch({OP_DECODE_PARTIAL}, src, src_off, src_len, dst, dst_off, room.data(), out_len, n);
 }
+int lz4hip_decompressed_size_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, const int32_t* dst_cap,
+                                   int32_t* out_len, uint32_t n) {
+  return host_batch({OP_DECODED_SIZE}, src, src_off, src_len, nullptr, nullptr, dst_cap, out_len, n);
+}
 int lz4hip_decompress_safe_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                  const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n) {
   return host_batch({OP_DECODE_SAFE}, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
@@ -1352,6 +1363,10 @@ int lz4hip_decompress_safe_partial_batch_dev(const uint8_t* src, const uint64_t*
                                              uint32_t n, int device, void* stream) {
   return dev_batch({OP_DECODE_PARTIAL, 0, target_len}, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream,
                    target_len ? nullptr : kNullArg);
+}
+int lz4hip_decompressed_size_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, const int32_t* dst_cap,
+                                       int32_t* out_len, uint32_t n, int device, void* stream) {
+  return dev_batch({OP_DECODED_SIZE}, {src, src_off, src_len, nullptr, nullptr, dst_cap, out_len, n}, device, stream);
 }
 int lz4hip_decompress_safe_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                      const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int device, void* stream) {
@@ -1445,6 +1460,7 @@ int lz4hip_compress_hc_dest_size(const uint8_t* src, int* src_size, uint8_t* dst
 }
 int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap) { return single({OP_DECODE_SAFE}, src, src_len, dst, dst_cap); }
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len) { return single({OP_DECODE_FAST}, src, src_cap, dst, dst_len); }
+int lz4hip_decompressed_size(const uint8_t* src, int src_len, int dst_cap) { return single({OP_DECODED_SIZE}, src, src_len, nullptr, dst_cap); }
 int lz4hip_decompress_safe_partial(const uint8_t* src, int src_len, uint8_t* dst, int target_size, int dst_cap) {
   return single({OP_DECODE_PARTIAL}, src, src_len, dst, partial_room(target_size, dst_cap));
 }

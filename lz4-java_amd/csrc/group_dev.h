@@ -974,4 +974,28 @@ struct BlockWaveDev : GroupDev<64, 0> {
   }
 };
 
+// ---- backend of the decoded-size query (lz4_decode_size.h): ONE WAVEFRONT PER BLOCK, the wave backend's stream ring (KS bytes + 16
+// tail of LDS) and lane-parallel side, NO output: the copies do nothing, so decode_block moves ip / op and checks, and never touches
+// dst.  Loads are made wave-uniform on the spot: the parse of the exact code is scalar work.
+template <int KS>
+struct SizeWaveDev : BlockWaveDev<256, KS> {
+  typedef BlockWaveDev<256, KS> Wave;
+  static constexpr uint32_t kSizeLds = (uint32_t)KS + 16u;
+  static constexpr bool kExactLengthSum = true;   // (decode_block EXACT: liblz4's error position for a length run that cannot fit)
+  uint32_t sz_lo = 1u, sz_avail = 0u;   // the stream ring holds the stream's bytes [sz_lo, sz_avail): nothing yet
+  __device__ __forceinline__ SizeWaveDev() : Wave() {}
+  __device__ __forceinline__ void sz_begin(uint8_t* lds) { this->wsb = lds; }
+  __device__ __forceinline__ static uint32_t ld8(const uint8_t* p) { return Wave::uni(Wave::ld8(p)); }
+  __device__ __forceinline__ static uint32_t ld16(const uint8_t* p) { return Wave::uni(Wave::ld16(p)); }
+  __device__ __forceinline__ static uint32_t ld32(const uint8_t* p) { return Wave::uni(Wave::ld32(p)); }
+  __device__ __forceinline__ static uint64_t ld64(const uint8_t* p) {
+    const uint64_t v = Wave::ld64(p);
+    return (uint64_t)Wave::uni((uint32_t)v) | ((uint64_t)Wave::uni((uint32_t)(v >> 32)) << 32);
+  }
+  __device__ __forceinline__ static void copy_lits(uint8_t*, const uint8_t*, uint32_t, bool) {}
+  __device__ __forceinline__ static void copy_lits_wide(uint8_t*, const uint8_t*, uint32_t) {}
+  __device__ __forceinline__ static void copy_match(uint8_t*, uint32_t, uint32_t, uint32_t, bool) {}
+  __device__ __forceinline__ static void copy_match_wide(uint8_t*, uint32_t, uint32_t, uint32_t) {}
+};
+
 }  // namespace lz4hip

@@ -80,6 +80,10 @@ int launch_decompress(const BatchArgs& a, bool safe, int lanes_per_block, int pi
 // negative); out[i] = liblz4's return value.  >= 40960 blocks: decode_partial_kernel<4, 0, true> (staged), fewer:
 // decode_partial_deep_kernel<8>; the decode knobs and the device-side route do not apply
 int launch_decompress_partial(const BatchArgs& a, const int32_t* target, void* stream);
+// The decoded-size query: out[i] = the value LZ4_decompress_safe would return for block i with capacity a.dst_cap[i] (-1 where it or
+// src_len[i] is negative); a.dst and a.dst_off are ignored (may be nullptr) and no output buffer exists.  decode_size_kernel<4, 2048, true>:
+// a wavefront per block; no route word, no sampler, no decode knob
+int launch_decoded_size(const BatchArgs& a, void* stream);
 int launch_xxh32(const uint8_t* buf, const uint64_t* off, const int32_t* len, uint32_t seed, uint32_t* out, uint32_t n, void* stream);
 int launch_xxh64(const uint8_t* buf, const uint64_t* off, const int32_t* len, uint64_t seed, uint64_t* out, uint32_t n, void* stream);
 // streaming xxhash: `rec` = device record of xxh_stream_rec_bytes() bytes (the digest so far sits at xxh_stream_digest_offset());

@@ -20,6 +20,9 @@
 //   decode_partial_kernel<GL, PIPE, STAGE>, decode_partial_deep_kernel<GL>
 //                        : LZ4_decompress_safe_partial: decode_kernel's and decode_deep_kernel's safe forms with the core's PARTIAL
 //                          switch and a per-block target next to BatchArgs.
+//   decode_size_kernel<W, KS, FAST>
+//                        : the decoded-size query (lz4_decode_size.h): a wavefront per block, the stream through an LDS ring, no
+//                          output buffer.  Reads C, writes 4 bytes per block.
 //                          Bound: HBM (reads C, writes N per block; match sources are random lines).
 //   hc_build_kernel / hc_parse_kernel
 //                        : LZ4 HC levels 1..12 (lz4_hc_core.h): chain deltas through a 128 KB LDS head table, then the parse.
@@ -1691,6 +1694,34 @@ int launch_decompress_partial(const BatchArgs& a, const int32_t* target, void* s
   hipStream_t st = (hipStream_t)stream;
   if (a.n >= 40960u) hipLaunchKernelGGL((decode_partial_kernel<4, 0, true>), dim3((a.n + 63u) / 64u), dim3(256), 0, st, a, target);
   else hipLaunchKernelGGL((decode_partial_deep_kernel<8>), dim3((a.n + 31u) / 32u), dim3(256), 0, st, a, target);
+  return (int)hipGetLastError();
+}
+
+// The decoded-size query (lz4_decode_size.h): out[i] = what LZ4_decompress_safe(src_i, dst, src_len[i], dst_cap[i]) would return, and
+// nothing else is written -- a.dst and a.dst_off are not looked at.  ONE WAVEFRONT PER BLOCK, W wavefronts per workgroup, each with a
+// stream ring of KS bytes in LDS; no barrier, the wavefronts are independent and take the blocks blockIdx.x * W + wave, + gridDim.x * W,
+// ... -- or, spread (wave_spread: a batch that would leave CUs empty), blockIdx.x + wave * gridDim.x, ...  A negative src_len[i] or
+// dst_cap[i] gives -1 (decode_block's first test).  FAST false: the exact path alone (developer A/B builds and the tests' cross-check).
+template <int W, int KS, bool FAST>
+__global__ __launch_bounds__(64 * W) void decode_size_kernel(BatchArgs a, uint32_t spread) {
+  typedef SizeWaveDev<KS> G;
+  __shared__ __attribute__((aligned(16))) uint8_t size_mem[W * G::kSizeLds];
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  uint8_t* lds = size_mem + wave * G::kSizeLds;
+  for (uint32_t b = spread ? blockIdx.x + wave * gridDim.x : blockIdx.x * W + wave; b < a.n; b += gridDim.x * W) {
+    G g;
+    const int r = decoded_size<G, FAST>(g, a.src + a.src_off[b], a.src_len[b], a.dst_cap[b], lds);
+    if (g.l == 0) a.out[b] = r;
+  }
+}
+// Four wavefronts per workgroup, up to eight workgroups per CU (a wavefront's state is its 2 KB ring and a few dozen registers: the
+// CU holds all 32); more blocks than that are taken in turns.
+int launch_decoded_size(const BatchArgs& a, void* stream) {
+  if (a.n == 0) return 0;
+  constexpr uint32_t W = 4u;
+  const uint32_t cus = device_cus(), spread = wave_spread(a.n, W, cus), wgs = (a.n + W - 1u) / W;
+  const uint32_t grid = spread ? (a.n < cus ? a.n : cus) : (wgs < 8u * cus ? wgs : 8u * cus);
+  hipLaunchKernelGGL((decode_size_kernel<4, 2048, true>), dim3(grid), dim3(64 * W), 0, (hipStream_t)stream, a, spread);
   return (int)hipGetLastError();
 }
 

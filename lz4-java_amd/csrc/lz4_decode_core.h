@@ -41,6 +41,7 @@
 #include "lz4_decode_wave.h"
 #include "lz4_decode_pair.h"
 #include "lz4_decode_trio.h"
+#include "lz4_decode_size.h"
 namespace lz4hip {
 
 // PARTIAL decoding: a literal or match length of `base` plus the extension bytes' 32-bit sum `ext` (liblz4 adds that unsigned sum to a
@@ -49,6 +50,10 @@ LZ4HIP_DEV int partial_run(uint32_t base, uint32_t ext, int room) {
   const int64_t n = (int64_t)base + (int64_t)ext;
   return n > (int64_t)room ? room + 1 : (int)n;
 }
+
+// a backend asks for liblz4's own 32-bit length sums in the full decoder (decode_block EXACT) with a member  static constexpr bool kExactLengthSum = true
+template <class G, class = void> struct exact_length_sum { static constexpr bool value = false; };
+template <class G> struct exact_length_sum<G, decltype((void)G::kExactLengthSum)> { static constexpr bool value = G::kExactLengthSum; };
 
 // SAFE: LZ4_decompress_safe(src, dst, src_size, out_size) -> decoded size or negative.
 // !SAFE: LZ4_decompress_fast(src, dst, out_size) -> bytes consumed or negative; `src_size` is then
@@ -66,6 +71,7 @@ LZ4HIP_DEV int partial_run(uint32_t base, uint32_t ext, int room) {
 //       7 = the pair loop of lz4_decode_pair.h (TWO WAVEFRONTS PER BLOCK: the caller is the copier, `stage` = the pair's LDS: the rings of 4 / 5 and a mailbox; a second wavefront
 //       runs pair_parser_service on the same LDS).
 //       8 = the trio loop of lz4_decode_trio.h (THREE WAVEFRONTS PER BLOCK: the caller is the copier; a planner and a scanner wavefront run trio_service on the same LDS).
+//       9 = the size loop of lz4_decode_size.h (ONE WAVEFRONT PER BLOCK, a backend that copies nothing: `stage` = its stream ring, dst is never touched): the decoded-size query.
 // STAGE: the interior loop writes through an LDS staging buffer (`stage`, Grp::kStage bytes for this block) and output leaves
 //        it as whole 128-byte lines (group_dev.h st_*).
 // PARTIAL (SAFE only): LZ4_decompress_safe_partial(src, dst, src_size, target, cap) with out_size = min(target, cap) -- liblz4
@@ -76,6 +82,10 @@ LZ4HIP_DEV int partial_run(uint32_t base, uint32_t ext, int room) {
 template <class Grp, bool SAFE, int PIPE = 0, bool STAGE = false, bool PARTIAL = false>
 LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* dst, int out_size, uint8_t* stage = nullptr) {
   static_assert(!PARTIAL || SAFE, "partial decoding is a safe-decoder mode");
+  // EXACT (a backend that sets kExactLengthSum: the decoded-size query, whose value is liblz4's on EVERY input): a length's extension bytes are summed
+  // in 32 bits, as liblz4 sums them, to the run's end -- the error position of a run that cannot fit is then liblz4's.  The decoders stop such a run at
+  // LZ4HIP_LEN_CAP instead: also an error, reported where the cap was passed.  WRAP: the 32-bit sum, PARTIAL's too
+  constexpr bool EXACT = !PARTIAL && exact_length_sum<Grp>::value, WRAP = PARTIAL || EXACT;
   int ip = 0, op = 0;
   const int iend = src_size, oend = out_size;  // iend: real end (SAFE) / read bound (!SAFE)
   const int shortiend = iend - (SAFE ? 14 : 8) - 2;
@@ -156,6 +166,9 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
     }
     if constexpr (PIPE == 8) {   // the trio loop (lz4_decode_trio.h): this wavefront copies, a planner and a scanner wavefront run ahead in the stream
       if (ip + 1536 <= iend && ip <= iend - 306 && op <= oend - 606) decode_trio_loop<Grp>(g, src, iend, dst, oend, ip, op, stage);
+    }
+    if constexpr (PIPE == 9) {   // the size loop (lz4_decode_size.h): it moves ip / op over every sequence that provably passes; what it leaves at ip is done by the exact code below, which comes back
+      if (ip <= iend - 306 && op <= oend - 606) decode_size_loop(g, src, iend, oend, ip, op, stage);
     }
     if ((PIPE == 1 || (PIPE == 2 && ip + 2048 > iend) || (PIPE == 3 && ip + 320 > iend) || (PIPE == 4 && ip + 1024 > iend) || ((PIPE == 5 || PIPE == 6 || PIPE == 7 || PIPE == 8) && ip + 1536 > iend)) && ip <= iend - 306 && op <= oend - 606) {   // (2 .. 8: only the tail of the stream)
       // ---- the same loop, software-pipelined.  A wavefront's memory operations retire in order, so a wait for a load also
@@ -334,17 +347,18 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
         if (SAFE && ip >= iend - 15) goto output_error;
         uint32_t s = (w4 >> 8) & 255u;  // readable: ip+4 <= iend held (SAFE: ip < iend-15; !SAFE: checked next)
         if (!SAFE && ip + 3 > iend) { LZ4HIP_NEED_IN(1); s = g.ld8(src + ip); }
-        if (PARTIAL) length = 0;  // (PARTIAL: `length` sums the extension bytes in 32 bits, as liblz4 does; the 15 is added after)
+        if (WRAP) length = 0;  // (PARTIAL: `length` sums the extension bytes in 32 bits, as liblz4 does; the 15 is added after)
         for (;;) {
           ip++;
-          if (PARTIAL) length = (int)((uint32_t)length + s); else length += (int)s;
+          if (WRAP) length = (int)((uint32_t)length + s); else length += (int)s;
           if (SAFE && ip >= iend - 15) break;
           if (s != 255u) break;
           LZ4HIP_NEED_IN(1);
           s = g.ld8(src + ip);
-          if (!PARTIAL && length > LZ4HIP_LEN_CAP) goto output_error;
+          if (!WRAP && length > LZ4HIP_LEN_CAP) goto output_error;
         }
         if (PARTIAL) length = partial_run(15u, (uint32_t)length, iend - ip < oend - op ? iend - ip : oend - op);   // (cut at safe_literal_copy)
+        else if (EXACT) { const int64_t n = (int64_t)15 + (int64_t)(uint32_t)length; if (n > (int64_t)(oend - op)) goto output_error; length = (int)n; }
         else if ((uint32_t)length > (uint32_t)(oend - op)) goto output_error;  // cannot fit: every tier rejects it at this ip
         cpy = op + length;
         if (SAFE) { if (cpy > oend - 32 || ip + length > iend - 32) goto safe_literal_copy; }
@@ -372,17 +386,18 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
         if (SAFE && offset > op) goto output_error;
         uint32_t s = (w4 >> 16) & 255u;
         if (ip + 2 > iend) { LZ4HIP_NEED_IN(1); s = g.ld8(src + ip); }  // (SAFE: error follows below anyway)
-        if (PARTIAL) length = 0;
+        if (WRAP) length = 0;
         for (;;) {  // read_variable_length(limit iend-4, loop check when SAFE)
           ip++;
-          if (PARTIAL) length = (int)((uint32_t)length + s); else length += (int)s;
+          if (WRAP) length = (int)((uint32_t)length + s); else length += (int)s;
           if (SAFE && ip >= iend - 4) goto output_error;
           if (s != 255u) break;
           LZ4HIP_NEED_IN(1);
           s = g.ld8(src + ip);
-          if (!PARTIAL && length > LZ4HIP_LEN_CAP) goto output_error;
+          if (!WRAP && length > LZ4HIP_LEN_CAP) goto output_error;
         }
         if (PARTIAL) length = partial_run(15u, (uint32_t)length, oend - op - 4);   // (cut at safe_match_copy)
+        else if (EXACT) { const int64_t n = (int64_t)15 + (int64_t)(uint32_t)length; if (n > (int64_t)(oend - op)) goto output_error; length = (int)n; }
         else if ((uint32_t)length > (uint32_t)(oend - op)) goto output_error;  // (offset <= op was checked / is checked first by liblz4 too)
         length += 4;
         if (op + length >= oend - 64) goto safe_match_copy;
@@ -425,17 +440,18 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
     }
     if (length == 15) {
       if (SAFE && ip >= iend - 15) goto output_error;
-      if (PARTIAL) length = 0;
+      if (WRAP) length = 0;
       for (;;) {
         LZ4HIP_NEED_IN(1);
         const uint32_t s = g.ld8(src + ip);
         ip++;
-        if (PARTIAL) length = (int)((uint32_t)length + s); else length += (int)s;
-        if (!PARTIAL && length > LZ4HIP_LEN_CAP) goto output_error;
+        if (WRAP) length = (int)((uint32_t)length + s); else length += (int)s;
+        if (!WRAP && length > LZ4HIP_LEN_CAP) goto output_error;
         if (SAFE && ip >= iend - 15) break;
         if (s != 255u) break;
       }
       if (PARTIAL) length = partial_run(15u, (uint32_t)length, iend - ip < oend - op ? iend - ip : oend - op);
+      else if (EXACT) { const int64_t n = (int64_t)15 + (int64_t)(uint32_t)length; if (n > (int64_t)(oend - op)) goto output_error; length = (int)n; }
       else if ((uint32_t)length > (uint32_t)(oend - op)) goto output_error;
     }
     cpy = op + length;
@@ -465,17 +481,18 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
     length = (int)(token & 15u);
   copy_match_label:
     if (length == 15) {
-      if (PARTIAL) length = 0;
+      if (WRAP) length = 0;
       for (;;) {
         LZ4HIP_NEED_IN(1);
         const uint32_t s = g.ld8(src + ip);
         ip++;
-        if (PARTIAL) length = (int)((uint32_t)length + s); else length += (int)s;
+        if (WRAP) length = (int)((uint32_t)length + s); else length += (int)s;
         if (SAFE && ip >= iend - 4) goto output_error;
-        if (!PARTIAL && length > LZ4HIP_LEN_CAP) goto output_error;
+        if (!WRAP && length > LZ4HIP_LEN_CAP) goto output_error;
         if (s != 255u) break;
       }
       if (PARTIAL) length = partial_run(15u, (uint32_t)length, oend - op - 4);
+      else if (EXACT) { const int64_t n = (int64_t)15 + (int64_t)(uint32_t)length; if (n > (int64_t)(oend - op)) goto output_error; length = (int)n; }   // (an offset past op fails below, at this ip too)
       else if (offset <= op && (uint32_t)length > (uint32_t)(oend - op)) goto output_error;
     }
     length += 4;
@@ -498,6 +515,14 @@ output_error:
   return -ip - 1;
 #undef LZ4HIP_NEED_IN
 #undef LZ4HIP_LEN_CAP
+}
+
+// The decoded-size query (lz4_decode_size.h): what LZ4_decompress_safe(src, dst, src_size, cap) returns, from (src, src_size, cap) alone.
+// `Grp` is a backend whose copies do nothing; dst is never touched.  FAST: the size loop in front of the exact path (`lds`: the
+// backend's stream ring); !FAST: the exact path alone
+template <class Grp, bool FAST>
+LZ4HIP_DEV int decoded_size(Grp& g, const uint8_t* src, int src_size, int cap, uint8_t* lds = nullptr) {
+  return decode_block<Grp, true, FAST ? 9 : 0>(g, src, src_size, nullptr, cap, lds);
 }
 
 }  // namespace lz4hip

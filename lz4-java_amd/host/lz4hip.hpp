@@ -6,6 +6,9 @@
 //   LZ4Compressor::compress / maxCompressedLength   <- LZ4Compressor.java:36,59 ; LZ4JNICompressor.java:35-43
 //   LZ4SafeDecompressor::decompress                 <- LZ4SafeDecompressor.java:45 ; LZ4JNISafeDecompressor.java:34-43
 //   LZ4SafeDecompressor::decompressPartial          =  LZ4_decompress_safe_partial of liblz4's main API (no reference entry reaches it)
+//   LZ4SafeDecompressor::decompressedLength, LZ4HIPBatch::decompressedLengths / decompressSafeSized
+//                                                   =  the decoded size without a destination; the batch twin of the allocating
+//                                                      overloads LZ4SafeDecompressor.java:117-137 without their worst-case buffer
 //   LZ4FastDecompressor::decompress                 <- LZ4FastDecompressor.java:48 ; LZ4JNIFastDecompressor.java:35-44
 //   LZ4Exception                                    <- LZ4Exception.java
 //   net::jpountz::xxhash::XXHashFactory::hipInstance().hash32()/hash64()  <- XXHashFactory.java:80,211,220
@@ -140,6 +143,72 @@ class LZ4SafeDecompressor {
     const int result = libCheck(lz4hip_decompress_safe_partial(src.data() + srcOff, srcLen, dest.data() + destOff, targetLen, maxDestLen));
     if (result < 0) throw LZ4Exception("Error decoding offset " + std::to_string(srcOff - result) + " of input buffer");
     return result;
+  }
+  // what decompress(src, srcOff, srcLen, dest, destOff, maxDestLen) would return, without a destination: nothing is decoded into
+  // memory (lz4hip_decompressed_size).  A stream that decompress() rejects with that capacity throws the same LZ4Exception
+  int decompressedLength(const bytes& src, int srcOff, int srcLen, int maxDestLen) const {
+    util::checkRange(src, srcOff, srcLen);
+    util::checkLength(maxDestLen);
+    const int result = libCheck(lz4hip_decompressed_size(src.data() + srcOff, srcLen, maxDestLen));
+    if (result < 0) throw LZ4Exception("Error decoding offset " + std::to_string(srcOff - result) + " of input buffer");
+    return result;
+  }
+};
+
+// Many blocks per call, host memory.  decompressedLengths: what LZ4_decompress_safe would return per block for a capacity of
+// maxDestLen[i] -- no destination exists (lz4hip_decompressed_size_batch).  decompressSafeSized: the batch twin of
+// LZ4SafeDecompressor::decompress(src, maxDestLen) -> right-sized vector: the sizes are queried, exactly sum(max(size, 0)) bytes are
+// allocated with the blocks packed back to back, and every block that decodes is decoded into its slot; lengths[i] < 0 (liblz4's
+// code) marks a block that does not decode with capacity maxDestLen[i], its slot is empty.
+struct LZ4HIPBatch {
+  struct Sized { bytes data; std::vector<uint64_t> offsets; std::vector<int32_t> lengths; };
+  static void checkBlocks(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen, const std::vector<int32_t>& maxDestLen) {
+    if (srcLen.size() != srcOff.size() || maxDestLen.size() != srcOff.size()) throw std::invalid_argument("per-block arrays differ in length");
+    for (size_t i = 0; i < srcOff.size(); i++) {
+      if (srcLen[i] < 0 || maxDestLen[i] < 0) throw std::invalid_argument("lengths must be >= 0");
+      if (srcOff[i] > src.size() || (uint64_t)srcLen[i] > src.size() - srcOff[i]) throw std::out_of_range("block " + std::to_string(i));
+    }
+  }
+  static void status(int rc) { if (rc != 0) throw LZ4Exception(std::string("liblz4hip status ") + std::to_string(rc) + ": " + lz4hip_last_error()); }
+  static std::vector<int32_t> decompressedLengths(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen,
+                                                  const std::vector<int32_t>& maxDestLen) {
+    checkBlocks(src, srcOff, srcLen, maxDestLen);
+    std::vector<int32_t> out(srcOff.size(), 0);
+    status(lz4hip_decompressed_size_batch(src.data(), srcOff.data(), srcLen.data(), maxDestLen.data(), out.data(), (uint32_t)srcOff.size()));
+    return out;
+  }
+  static Sized decompressSafeSized(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen,
+                                   const std::vector<int32_t>& maxDestLen) {
+    Sized r;
+    r.lengths = decompressedLengths(src, srcOff, srcLen, maxDestLen);
+    const size_t n = srcOff.size();
+    r.offsets.resize(n);
+    uint64_t total = 0;
+    std::vector<uint64_t> so, dof;
+    std::vector<int32_t> sl, dc;
+    std::vector<size_t> idx;
+    for (size_t i = 0; i < n; i++) {
+      r.offsets[i] = total;
+      if (r.lengths[i] < 0) continue;
+      so.push_back(srcOff[i]); sl.push_back(srcLen[i]); dof.push_back(total); dc.push_back(r.lengths[i]); idx.push_back(i);
+      total += (uint64_t)r.lengths[i];
+    }
+    r.data.resize((size_t)total);
+    if (idx.empty()) return r;
+    bytes one(1);                                 // (an all-empty result still hands the library a destination pointer)
+    uint8_t* dst = total ? r.data.data() : one.data();
+    std::vector<int32_t> got(idx.size(), 0);
+    status(lz4hip_decompress_safe_batch(src.data(), so.data(), sl.data(), dst, dof.data(), dc.data(), got.data(), (uint32_t)idx.size()));
+    for (size_t k = 0; k < idx.size(); k++) {
+      if (got[k] == dc[k]) continue;
+      // a stream liblz4 accepts only with room to spare (it breaks the format's end rules): once more, alone, with its maxDestLen
+      const size_t i = idx[k];
+      bytes scratch((size_t)maxDestLen[i] + 1);
+      const int r2 = libCheck(lz4hip_decompress_safe(src.data() + srcOff[i], srcLen[i], scratch.data(), maxDestLen[i]));
+      if (r2 != r.lengths[i]) throw LZ4Exception("block " + std::to_string(i) + ": the decoder disagrees with the size query");
+      std::copy(scratch.begin(), scratch.begin() + r2, r.data.begin() + (size_t)r.offsets[i]);
+    }
+    return r;
   }
 };
 

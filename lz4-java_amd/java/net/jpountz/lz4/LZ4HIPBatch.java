@@ -122,6 +122,31 @@ public final class LZ4HIPBatch {
     }
   }
 
+  /**
+   * The decoded size of every block without a destination buffer: outLen[i] is what {@link #decompressSafe} would report for block i
+   * with a slot of {@code destCap[i]} bytes -- the decoded size, or -(input position)-1 -- and nothing is decoded into memory.
+   * For blocks whose sizes are unknown or untrusted this replaces a decode into worst-case slots; outLen[i] &gt;= 0 means that
+   * decompressSafe with that capacity succeeds and returns that number.
+   */
+  public static void decompressedLengths(ByteBuffer src, long[] srcOff, int[] srcLen, int[] destCap, int[] outLen) {
+    if (!src.isDirect()) {
+      throw new IllegalArgumentException("LZ4HIPBatch needs direct ByteBuffers");
+    }
+    final int n = srcOff.length;
+    if (srcLen.length != n || destCap.length != n || outLen.length != n) {
+      throw new IllegalArgumentException("per-block arrays must have the same length");
+    }
+    for (int i = 0; i < n; i++) {
+      if (srcOff[i] < 0 || srcLen[i] < 0 || srcOff[i] + srcLen[i] > src.capacity() || destCap[i] < 0) {
+        throw new IndexOutOfBoundsException("block " + i + " lies outside its buffer");
+      }
+    }
+    final int rc = LZ4HIPJNI.LZ4HIP_batchDecompressedLengths(src, srcOff, srcLen, destCap, outLen, n);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
   /** outLen[i] &gt;= 0: decompressed size; &lt; 0: -(input position)-1. */
   public static void decompressSafe(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen) {
     run(1, 0, src, srcOff, srcLen, dest, destOff, destCap, outLen);

@@ -70,6 +70,9 @@ enum LZ4HIPJNI {
    * above.  Same NULL / pinning rules as LZ4HIP_decompress_safe */
   static native int LZ4HIP_decompress_safe_partial(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
                                                    byte[] destArray, ByteBuffer destBuffer, int destOff, int targetLen, int maxDestLen);
+  /* the decoded-size query: what LZ4HIP_decompress_safe would return for the same source and maxDestLen, without a destination
+   * (lz4hip_decompressed_size); liblz4's return value or a library failure as above.  Exactly one of srcArray / srcBuffer is non-null */
+  static native int LZ4HIP_decompressed_length(byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen, int maxDestLen);
   static native int LZ4HIP_compressBound(int len);
 
   /* batches over DIRECT buffers (so the shim never pins the Java heap across a kernel):
@@ -89,6 +92,10 @@ enum LZ4HIPJNI {
   /* LZ4_compress_HC_destSize per block at HC level `level`: the arguments and return conventions of LZ4HIP_batchDestSize */
   static native int LZ4HIP_batchHCDestSize(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetSize,
                                            int[] outLen, int[] srcConsumed, int nBlocks, int level);
+
+  /* the decoded-size query per block over a DIRECT source buffer, no destination: outLen[i] = what LZ4_decompress_safe would return for
+   * block i with capacity destCap[i].  Returns 0 or a negative lz4hip_status (a null argument: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchDecompressedLengths(ByteBuffer src, long[] srcOff, int[] srcLen, int[] destCap, int[] outLen, int nBlocks);
 
   /** Container blocks assembled on the device (LZ4HIPBatch.containerBlocks); returns bytes written or the negative lz4hip_status. */
   static native long LZ4HIP_containerBlocks(int kind, int flags, int level, ByteBuffer src, long srcOff, long len, int blockSize,

@@ -99,4 +99,41 @@ final class LZ4HIPSafeDecompressor extends LZ4SafeDecompressor {
     }
     return result;
   }
+
+  /**
+   * What {@code decompress(src, srcOff, srcLen, dest, destOff, maxDestLen)} would return -- the decoded size of the block for a
+   * destination of {@code maxDestLen} bytes -- without a destination: nothing is decoded into memory.  The argument checks and the
+   * exception message are decompress()'s; the dispatch is decompress()'s too (heap arrays are staged, direct buffers used in place).
+   */
+  public final int decompressedLength(byte[] src, int srcOff, int srcLen, int maxDestLen) {
+    SafeUtils.checkRange(src, srcOff, srcLen);
+    if (maxDestLen < 0) {
+      throw new IllegalArgumentException("maxDestLen must be >= 0");
+    }
+    final int result = LZ4HIPJNI.LZ4HIP_decompressed_length(src, null, srcOff, srcLen, maxDestLen);
+    if (result < 0) {
+      throw new LZ4Exception(result <= Integer.MIN_VALUE + 63 ? "liblz4hip: " + LZ4HIPJNI.lastError()
+                                                               : "Error decoding offset " + (srcOff - result) + " of input buffer");
+    }
+    return result;
+  }
+
+  /** {@link #decompressedLength(byte[], int, int, int)} over a heap or direct buffer (its position is untouched). */
+  public int decompressedLength(ByteBuffer src, int srcOff, int srcLen, int maxDestLen) {
+    ByteBufferUtils.checkRange(src, srcOff, srcLen);
+    if (maxDestLen < 0) {
+      throw new IllegalArgumentException("maxDestLen must be >= 0");
+    }
+    if (!(src.hasArray() || src.isDirect())) {
+      throw new IllegalArgumentException("decompressedLength needs a heap-backed or direct ByteBuffer");
+    }
+    final byte[] srcArr = src.hasArray() ? src.array() : null;
+    final int so = srcArr != null ? srcOff + src.arrayOffset() : srcOff;
+    final int result = LZ4HIPJNI.LZ4HIP_decompressed_length(srcArr, srcArr == null ? src : null, so, srcLen, maxDestLen);
+    if (result < 0) {
+      throw new LZ4Exception(result <= Integer.MIN_VALUE + 63 ? "liblz4hip: " + LZ4HIPJNI.lastError()
+                                                               : "Error decoding offset " + (srcOff - result) + " of input buffer");
+    }
+    return result;
+  }
 }

@@ -181,6 +181,19 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1safe_1
   return run_single(env, 5, targetLen, srcArray, srcBuffer, srcOff, srcLen, destArray, destBuffer, destOff, maxDestLen);
 }
 
+/* The decoded-size query (lz4hip_decompressed_size): what LZ4HIP_decompress_safe would return for the same source and maxDestLen,
+ * without a destination -- only the source is made addressable (a heap array is staged, a direct buffer is used in place).  Returns
+ * liblz4's value or a library failure as above */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompressed_1length(JNIEnv* env, jclass cls, jbyteArray srcArray,
+    jobject srcBuffer, jint srcOff, jint srcLen, jint maxDestLen) {
+  (void)cls;
+  region_t in;
+  if (region_in(env, srcArray, srcBuffer, srcOff, srcLen, 1, &in) != 0) { throw_OOM(env); return 0; }
+  const int result = lz4hip_decompressed_size(in.p, srcLen, maxDestLen);
+  region_out(env, NULL, 0, 0, &in);
+  return result;
+}
+
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1fast(JNIEnv* env, jclass cls, jbyteArray srcArray, jobject srcBuffer,
     jint srcOff, jint srcCap, jbyteArray destArray, jobject destBuffer, jint destOff, jint destLen) {
   (void)cls;
@@ -302,6 +315,20 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafePartial(J
   jint rc = batch_pin(env, src, dest, &b);
   if (rc != 0) return rc;
   rc = lz4hip_decompress_safe_partial_batch(b.src, b.a[0].p, b.a[1].p, b.dst, b.a[2].p, b.a[3].p, b.a[4].p, b.a[5].p, (uint32_t)n);
+  batch_release(env, &b);
+  return rc;
+}
+
+/* The decoded-size query over many blocks, a direct source buffer (lz4hip_decompressed_size_batch): outLen[i] = what
+ * LZ4_decompress_safe would return for block i with capacity destCap[i].  There is no destination buffer (batch_pin gets the source in
+ * its place: its address is not used).  Returns 0 or a negative lz4hip_status; a NULL array or buffer is LZ4HIP_E_ARG */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchDecompressedLengths(JNIEnv* env, jclass cls, jobject src, jlongArray srcOff,
+    jintArray srcLen, jintArray destCap, jintArray outLen, jint n) {
+  (void)cls;
+  batch_args_t b = {NULL, NULL, 4, {{srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {destCap, INTS, JNI_ABORT}, {outLen, INTS, 0}}};
+  jint rc = batch_pin(env, src, src, &b);
+  if (rc != 0) return rc;
+  rc = lz4hip_decompressed_size_batch(b.src, b.a[0].p, b.a[1].p, b.a[2].p, b.a[3].p, (uint32_t)n);
   batch_release(env, &b);
   return rc;
 }
