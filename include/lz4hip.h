@@ -92,11 +92,11 @@ int lz4hip_version(void);
  * The decode_* knobs and the device-side route do not apply to the partial decoder (lz4hip_decompress_safe_partial*): it always runs the
  * 4-lane staged loop from 40960 blocks on and the 8-lane deep loop below.                                                        */
 int lz4hip_set_option(const char* name, int value);
-/* diagnostic: what the device-side route of a device's last routed decode launch decided (device = index as in the _dev calls) -- out6
+/* diagnostic: what the device-side route of a device's last routed decode launch decided (device = index as in the _dev calls) -- out8
  * (8 words) = { route (0 lane-group default of the batch size, 1 ring loop, 2 wave loop, 3 deep loop instead of the staged one), hops
  * counted by the sampler, stream bytes it walked, average compressed size of 64 blocks, sampled match offsets within 6 KB, sampled
  * sequences, their output bytes, 0 }; synchronises the device                                                                  */
-int lz4hip_last_decode_route(int device, uint32_t* out6);
+int lz4hip_last_decode_route(int device, uint32_t* out8);
 
 /* == LZ4_compressBound (LZ4JNI.c:237): n + n/255 + 16, 0 if n < 0 or n > 0x7E000000            */
 int lz4hip_compress_bound(int n);

@@ -850,7 +850,7 @@ int single(const BlockCall& c, const uint8_t* src, int src_len, uint8_t* dst, in
 
 }  // namespace
 
-// ---- device-side container assembly (kernels.hip launch_container_blocks) ------------------------------------------------------
+// ---- device-side container assembly (container.hip launch_container_blocks) ------------------------------------------------------
 namespace {
 struct ContainerPlan { size_t cws, hcws, qwords, total; uint32_t n; };
 // the largest CU count of any visible device: what a workspace must be sized for when the device is not known yet
@@ -1226,9 +1226,9 @@ namespace lz4hip { int ring_stats_fetch(unsigned long long* out8); }
 extern "C" {
 __attribute__((visibility("default"))) int lz4hip_dbg_ring_stats(unsigned long long* out8) { return lz4hip::ring_stats_fetch(out8); }
 #endif
-int lz4hip_last_decode_route(int device, uint32_t* out6) {
-  return on_device(device, false, out6 ? nullptr : kNullArg, [&] {
-    const int e = lz4hip::last_decode_route(out6);
+int lz4hip_last_decode_route(int device, uint32_t* out8) {
+  return on_device(device, false, out8 ? nullptr : kNullArg, [&] {
+    const int e = lz4hip::last_decode_route(out8);
     return e ? fail(LZ4HIP_E_HIP, "hipMemcpyFromSymbol", (hipError_t)e) : 0;
   });
 }

@@ -1,0 +1,584 @@
+// container.hip -- what sits around the block kernels on the launch stream (gfx950): packing of compressed slots, and the device-side
+// assembly and read path of LZ4 Frame / LZ4Block containers.  These kernels call no algorithm core; the compress, decode and xxhash
+// launches between them go through kernels.h.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "kernels.h"
+
+namespace lz4hip {
+
+// ------------------------------------------------------------------------------------------------
+// packing of compressed slots (host-pointer batch API): slot i holds out[i] > 0 useful bytes at dst + dst_off[i]; they are
+// moved to pack + sum(out[0..i)) so that only useful bytes cross PCIe
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void pack_scan_kernel(const int32_t* out, uint32_t n, uint64_t* poff) {
+  __shared__ uint64_t part[1024];
+  const uint32_t t = threadIdx.x;
+  const uint32_t per = (n + 1023u) / 1024u;
+  const uint32_t i0 = t * per, i1 = (i0 + per < n) ? i0 + per : n;
+  uint64_t s = 0;
+  for (uint32_t i = i0; i < i1; i++) s += out[i] > 0 ? (uint64_t)out[i] : 0ull;
+  part[t] = s;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024u; d <<= 1) {   // inclusive scan of the 1024 partial sums
+    const uint64_t v = t >= d ? part[t - d] : 0ull;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint64_t run = part[t] - s;
+  for (uint32_t i = i0; i < i1; i++) { poff[i] = run; run += out[i] > 0 ? (uint64_t)out[i] : 0ull; }
+}
+__global__ __launch_bounds__(256) void pack_copy_kernel(BatchArgs a, const uint64_t* poff, uint8_t* pack) {
+  const uint32_t b = blockIdx.x;
+  const int32_t r = a.out[b];
+  if (r <= 0) return;
+  const uint8_t* s = a.dst + a.dst_off[b];   // (slots are 16-byte aligned in the staging layout; pack offsets are not)
+  uint8_t* d = pack + poff[b];
+  const uint32_t len = (uint32_t)r, body = len & ~15u;
+  for (uint32_t i = threadIdx.x * 16u; i < body; i += 256u * 16u) {
+    uint4 v;
+    __builtin_memcpy(&v, s + i, 16);
+    __builtin_memcpy(d + i, &v, 16);
+  }
+  const uint32_t i = body + threadIdx.x;
+  if (i < len) d[i] = s[i];
+}
+int launch_pack(const BatchArgs& a, uint64_t* poff, uint8_t* pack, void* stream) {
+  if (a.n == 0) return 0;
+  hipLaunchKernelGGL(pack_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const int32_t*)a.out, a.n, poff);
+  hipLaunchKernelGGL(pack_copy_kernel, dim3(a.n), dim3(256), 0, (hipStream_t)stream, a, (const uint64_t*)poff, pack);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Device-side container assembly: the data blocks of an LZ4 Frame
+// (LZ4FrameOutputStream.writeBlock, /root/reference/src/java/net/jpountz/lz4/LZ4FrameOutputStream.java:199-235: size word with the
+// "stored uncompressed" bit, payload, optional XXH32 of the stored payload) or of lz4-java's "LZ4Block" container
+// (LZ4BlockOutputStream.flushBufferedData, LZ4BlockOutputStream.java:203-227: 21-byte header {magic, method | level, compressed
+// length, original length, XXH32(original, seed 0x9747b28c) & 0x0FFFFFFF}, payload) are laid out in device memory behind the
+// compress launch: raw-fallback decision, exclusive scan of the stored sizes, headers, payload compaction, checksums -- all on
+// the launch stream, so nothing but the finished container bytes crosses PCIe and no host pass sits between compress and D2H.
+// kind 0 = LZ4 Frame blocks, 1 = LZ4Block blocks.
+// ------------------------------------------------------------------------------------------------
+// block i = src[i * block_size .. +len_i), its compress slot = slots + i * bound
+__global__ void container_layout_kernel(uint64_t n_bytes, uint32_t block_size, uint32_t bound, uint32_t n, uint64_t* src_off, int32_t* src_len,
+                                        uint64_t* slot_off, int32_t* slot_cap) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t o = (uint64_t)i * block_size;
+  src_off[i] = o;
+  src_len[i] = (int32_t)(n_bytes - o < block_size ? n_bytes - o : block_size);
+  slot_off[i] = (uint64_t)i * bound;
+  slot_cap[i] = (int32_t)bound;
+}
+// stored length of every block (the compressed bytes, or the block itself when compression does not gain: clen >= len, the
+// reference's test in both writers) and where its header goes: one workgroup, exclusive scan; total -> *total
+__global__ __launch_bounds__(1024) void container_scan_kernel(int kind, int block_checksum, uint32_t n, const int32_t* src_len, const int32_t* clen,
+                                                               int32_t* stored, uint64_t* hdr_off, unsigned long long* total) {
+  __shared__ uint64_t part[1024];
+  const uint32_t t = threadIdx.x;
+  const uint32_t per = (n + 1023u) / 1024u;
+  const uint32_t i0 = t * per < n ? t * per : n, i1 = (i0 + per < n) ? i0 + per : n;
+  const uint64_t fixed = kind == 0 ? (block_checksum ? 8u : 4u) : 21u;
+  uint64_t s = 0;
+  for (uint32_t i = i0; i < i1; i++) {
+    const int32_t l = src_len[i], c = clen[i];
+    const bool raw = c <= 0 || c >= l;
+    stored[i] = raw ? (l | (int32_t)0x80000000) : c;     // (sign bit: stored uncompressed)
+    s += fixed + (uint64_t)(raw ? l : c);
+  }
+  part[t] = s;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024u; d <<= 1) {
+    const uint64_t v = t >= d ? part[t - d] : 0ull;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint64_t run = part[t] - s;
+  for (uint32_t i = i0; i < i1; i++) { hdr_off[i] = run; run += fixed + (uint64_t)(stored[i] & 0x7FFFFFFF); }
+  if (t == 1023u) *total = part[1023];
+}
+// header + payload of every block (one workgroup per block); hashes: kind 1 only (XXH32 of the ORIGINAL blocks, seed 0x9747b28c)
+__global__ __launch_bounds__(256) void container_copy_kernel(int kind, int block_checksum, uint32_t level_nibble, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                                             const uint8_t* slots, const uint64_t* slot_off, const int32_t* stored, const uint64_t* hdr_off,
+                                                             const uint32_t* hashes, uint8_t* dst, uint64_t dst_cap, uint64_t* pay_off, int32_t* pay_len) {
+  const uint32_t b = blockIdx.x;
+  const int32_t st = stored[b];
+  const bool raw = st < 0;
+  const uint32_t len = (uint32_t)(st & 0x7FFFFFFF);
+  const uint32_t hl = kind == 0 ? 4u : 21u;
+  const uint64_t ho = hdr_off[b];
+  // a block that does not fit [0, dst_cap) is skipped whole -- header, payload and (frame blocks with block checksums) the 4 bytes
+  // behind the payload, exactly the bytes container_scan_kernel counted for it -- and its payload length is recorded as 0 so that
+  // the checksum pass that follows never reads dst beyond dst_cap (the caller compares *total with the capacity before it uses dst)
+  const bool fits = ho + hl + len + ((kind == 0 && block_checksum) ? 4u : 0u) <= dst_cap;
+  if (threadIdx.x == 0) { pay_off[b] = fits ? ho + hl : 0ull; pay_len[b] = fits ? (int32_t)len : 0; }
+  if (!fits) return;
+  uint8_t* h = dst + ho;
+  if (threadIdx.x < hl) {
+    uint8_t v;
+    const uint32_t t = threadIdx.x;
+    if (kind == 0) {
+      const uint32_t w = len | (raw ? 0x80000000u : 0u);
+      v = (uint8_t)(w >> (8u * t));
+    } else {
+      const uint32_t olen = (uint32_t)src_len[b], chk = hashes[b] & 0x0FFFFFFFu;
+      if (t < 8u) v = (uint8_t)"LZ4Block"[t];
+      else if (t == 8u) v = (uint8_t)((raw ? 0x10u : 0x20u) | level_nibble);
+      else if (t < 13u) v = (uint8_t)(len >> (8u * (t - 9u)));
+      else if (t < 17u) v = (uint8_t)(olen >> (8u * (t - 13u)));
+      else v = (uint8_t)(chk >> (8u * (t - 17u)));
+    }
+    h[t] = v;
+  }
+  const uint8_t* s = raw ? src + src_off[b] : slots + slot_off[b];
+  uint8_t* d = h + hl;
+  // (neither side is 16-byte aligned in general: unaligned 16-byte accesses are single instructions here)
+  const uint32_t body = len & ~15u;
+  for (uint32_t i = threadIdx.x * 16u; i < body; i += 256u * 16u) {
+    uint4 v;
+    __builtin_memcpy(&v, s + i, 16);
+    __builtin_memcpy(d + i, &v, 16);
+  }
+  const uint32_t i = body + threadIdx.x;
+  if (i < len) d[i] = s[i];
+}
+// kind 0 with block checksums: the XXH32 (seed 0) of each stored payload goes behind it
+__global__ void container_put_hashes_kernel(uint32_t n, const uint64_t* pay_off, const int32_t* pay_len, const uint32_t* hashes, uint8_t* dst, uint64_t dst_cap) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  if (pay_off[i] == 0ull) return;   // (a block container_copy_kernel skipped: payloads start behind a header, never at 0)
+  const uint64_t o = pay_off[i] + (uint64_t)pay_len[i];
+  if (o + 4u > dst_cap) return;
+  const uint32_t h = hashes[i];
+  dst[o] = (uint8_t)h; dst[o + 1] = (uint8_t)(h >> 8); dst[o + 2] = (uint8_t)(h >> 16); dst[o + 3] = (uint8_t)(h >> 24);
+}
+size_t container_ws_bytes(uint64_t n_bytes, uint32_t block_size) {
+  const uint64_t n = (n_bytes + block_size - 1u) / block_size;
+  const uint64_t bound = (uint64_t)block_size + block_size / 255u + 16u;
+  // src_off, slot_off, hdr_off, pay_off (u64) | src_len, slot_cap, clen, stored, pay_len (i32) | hashes (u32) | total (u64) | slots
+  return (size_t)(((n * (4u * 8u + 6u * 4u) + 8u + 255u) & ~(uint64_t)255u) + n * ((bound + 15u) & ~(uint64_t)15u));
+}
+int launch_container_blocks(int kind, int block_checksum, int hc_level, const uint8_t* src, uint64_t n_bytes, uint32_t block_size, uint8_t* dst, uint64_t dst_cap,
+                            unsigned long long* total, void* ws, void* hc_ws, uint32_t* q_scratch, uint32_t dense64, uint32_t n_cus, int core, void* stream) {
+  if (n_bytes == 0) { return (int)hipMemsetAsync(total, 0, 8, (hipStream_t)stream); }
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t n = (uint32_t)((n_bytes + block_size - 1u) / block_size);
+  const uint32_t bound = (uint32_t)(((uint64_t)block_size + block_size / 255u + 16u + 15u) & ~15ull);
+  uint8_t* p = (uint8_t*)ws;
+  uint64_t* src_off = (uint64_t*)p; uint64_t* slot_off = src_off + n; uint64_t* hdr_off = slot_off + n; uint64_t* pay_off = hdr_off + n;
+  int32_t* src_len = (int32_t*)(pay_off + n); int32_t* slot_cap = src_len + n; int32_t* clen = slot_cap + n; int32_t* stored = clen + n; int32_t* pay_len = stored + n;
+  uint32_t* hashes = (uint32_t*)(pay_len + n);
+  uint8_t* slots = p + (((size_t)n * (4u * 8u + 6u * 4u) + 8u + 255u) & ~(size_t)255u);
+  hipLaunchKernelGGL(container_layout_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, n_bytes, block_size, bound, n, src_off, src_len, slot_off, slot_cap);
+  BatchArgs a{src, src_off, src_len, slots, slot_off, slot_cap, clen, n};
+  int e;
+  if (hc_level > 0) e = launch_compress_hc(a, hc_level, hc_ws, n_bytes, stream);
+  else if (core == 1) e = launch_compress_fast_ms(a, q_scratch, nullptr, true, n_cus, stream);
+  else if (core == 3) e = launch_compress_fast_v2w(a, q_scratch, nullptr, 0u, n_cus, q_scratch + 3 + n, stream);
+  else {
+    e = launch_compress_fast_v2w(a, q_scratch, q_scratch + 3, dense64, n_cus, q_scratch + 3 + n, stream);
+    if (e == 0) e = launch_compress_fast_ms(a, q_scratch, q_scratch + 3, false, n_cus, stream);
+  }
+  if (e) return e;
+  if (kind == 1 && (e = launch_xxh32(src, src_off, src_len, 0x9747b28cu, hashes, n, stream)) != 0) return e;
+  hipLaunchKernelGGL(container_scan_kernel, dim3(1), dim3(1024), 0, st, kind, block_checksum, n, (const int32_t*)src_len, (const int32_t*)clen, stored, hdr_off, total);
+  uint32_t nib = 0;   // LZ4BlockOutputStream.compressionLevel (:57-69): max(0, ceil(log2(blockSize)) - 10)
+  if (kind == 1) { uint32_t cl = 32u - (uint32_t)__builtin_clz(block_size - 1u); if (cl < 10u) cl = 10u; nib = cl - 10u; }
+  hipLaunchKernelGGL(container_copy_kernel, dim3(n), dim3(256), 0, st, kind, block_checksum, nib, src, (const uint64_t*)src_off, (const int32_t*)src_len, (const uint8_t*)slots,
+                     (const uint64_t*)slot_off, (const int32_t*)stored, (const uint64_t*)hdr_off, (const uint32_t*)hashes, dst, dst_cap, pay_off, pay_len);
+  if (kind == 0 && block_checksum) {
+    if ((e = launch_xxh32(dst, pay_off, pay_len, 0u, hashes, n, stream)) != 0) return e;
+    hipLaunchKernelGGL(container_put_hashes_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, n, (const uint64_t*)pay_off, (const int32_t*)pay_len, (const uint32_t*)hashes, dst, dst_cap);
+  }
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Device-side container READ path: the data blocks of an LZ4 Frame body
+// (LZ4FrameInputStream.readBlock, /root/reference/src/java/net/jpountz/lz4/LZ4FrameInputStream.java:258-322) or of an lz4-java
+// "LZ4Block" stream (LZ4BlockInputStream.refill, LZ4BlockInputStream.java:191-264) that lie in device memory are walked, verified and
+// decoded on the launch stream: (1) one wavefront walks the size words / 21-byte headers (a serial chain: every header's position
+// follows from the one before) into the batch arrays, applying the readers' header rules in their order; (2) frame block checksums
+// (XXH32, seed 0, of the STORED payload) are hashed where the payloads lie; (3) compressed blocks are decoded -- LZ4_decompress_safe
+// into a slot of the frame's block maximum, or, for LZ4Block, the fast decoder into originalLen bytes, whose return value must be the
+// header's compressed length --, raw blocks copied; (4) LZ4Block checksums (XXH32 of the DECODED bytes, seed 0x9747b28c, low 28 bits)
+// are hashed where the blocks now lie; (5) one pass finds the first block that fails, in the readers' order of checks per block
+// (frame: size > max, premature end, checksum, decode; LZ4Block: header rules, premature end, decode / consumed length, checksum),
+// and reports {blocks delivered, body bytes consumed, why it stopped, decoded bytes}.  Block k decodes to dst + k * slot_bytes.
+// Stop reasons (info[2]):
+enum { CR_END = 0, CR_MORE = 1, CR_TRUNCATED = 2, CR_BLOCK_TOO_BIG = 3, CR_BLOCK_CHECKSUM = 4, CR_DECODE = 5, CR_CORRUPT = 6, CR_SLOTS = 7 };
+//   CR_END        the end mark (frame) / the empty block (LZ4Block) was reached: consumed includes it
+//   CR_MORE       the body ended exactly at a block boundary      CR_SLOTS  n_max blocks are delivered, more follow
+//   CR_TRUNCATED  the body ended inside a header, a payload or a checksum ("Stream ended prematurely")
+//   CR_BLOCK_TOO_BIG / CR_BLOCK_CHECKSUM / CR_DECODE (info[4] = liblz4's negative code)   frame errors, LZ4FrameInputStream.java:284-311
+//   CR_CORRUPT    LZ4Block "Stream is corrupted" (every rule of LZ4BlockInputStream.java:200-259)
+// ------------------------------------------------------------------------------------------------
+struct ContainerRead {   // arrays of n_max entries in the workspace
+  uint64_t* src_off; int32_t* src_len; uint64_t* dst_off; int32_t* dst_cap; int32_t* out;   // the decode batch
+  uint64_t* pay_off; int32_t* pay_len;      // stored payloads (frame checksums are taken over these)
+  uint64_t* end_off;                         // body offset behind block k (incl. its checksum word)
+  uint32_t* stored;                          // stored checksum (frame) / check field (LZ4Block)
+  uint32_t* hashes;                          // computed
+  int32_t* meta;                             // bit 0: raw block; bits 8..: LZ4Block originalLen is in dst_cap
+  uint32_t* walk;                            // [0] blocks walked, [1] stop reason of the walk, [2..3] body offset where it stopped
+};
+__device__ __forceinline__ uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+__global__ __launch_bounds__(64) void container_walk_kernel(int kind, int block_checksum, const uint8_t* body, uint64_t body_bytes, uint32_t max_block,
+                                                            uint64_t slot_bytes, uint32_t n_max, ContainerRead c, const uint32_t* par_ok) {
+  if (par_ok && *par_ok != 0u) return;   // (the parallel walk of an LZ4Block stream, below, has done it)
+  // every entry gets a value (the decode launch covers all n_max slots): blocks that are not walked decode nothing
+  for (uint32_t i = threadIdx.x; i < n_max; i += 64u) { c.src_off[i] = 0; c.src_len[i] = 0; c.dst_off[i] = (uint64_t)i * slot_bytes; c.dst_cap[i] = 0; c.out[i] = 0;
+                                                        c.pay_off[i] = 0; c.pay_len[i] = 0; c.end_off[i] = 0; c.stored[i] = 0; c.hashes[i] = 0; c.meta[i] = 0; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  uint64_t p = 0;
+  uint32_t k = 0, why = CR_SLOTS;
+  while (k < n_max) {
+    if (p == body_bytes) { why = CR_MORE; break; }
+    if (kind == 0) {
+      if (p + 4u > body_bytes) { why = CR_TRUNCATED; break; }
+      const uint32_t word = rd32(body + p);
+      const uint32_t size = word & 0x7FFFFFFFu;
+      if (size == 0u) { p += 4u; why = CR_END; break; }                       // LZ4FrameInputStream.java:264-276 (the caller reads what follows)
+      if (size > max_block) { why = CR_BLOCK_TOO_BIG; break; }                 // :284-286
+      const uint64_t need = 4ull + size + (block_checksum ? 4u : 0u);
+      if (p + need > body_bytes) { why = CR_TRUNCATED; break; }                // :289-295 PREMATURE_EOS
+      const bool raw = (word & 0x80000000u) != 0u;
+      c.pay_off[k] = p + 4u; c.pay_len[k] = (int32_t)size;
+      c.src_off[k] = p + 4u; c.src_len[k] = raw ? 0 : (int32_t)size;
+      c.dst_cap[k] = raw ? 0 : (int32_t)(max_block < slot_bytes ? max_block : (uint32_t)slot_bytes);
+      c.meta[k] = raw ? 1 : 0;
+      if (raw && size > slot_bytes) { why = CR_BLOCK_TOO_BIG; break; }
+      if (block_checksum) c.stored[k] = rd32(body + p + 4u + size);
+      p += need;
+      c.end_off[k] = p;
+      k++;
+    } else {
+      if (p + 21u > body_bytes) { why = CR_TRUNCATED; break; }                 // LZ4BlockInputStream.java:192-199
+      const uint8_t* h = body + p;
+      const char* magic = "LZ4Block";
+      bool bad = false;
+      for (int i = 0; i < 8; i++) bad |= h[i] != (uint8_t)magic[i];           // :200-204
+      const uint32_t token = h[8], method = token & 0xF0u, level = 10u + (token & 0x0Fu);
+      bad |= method != 0x10u && method != 0x20u;                               // :208-210
+      const int32_t clen = (int32_t)rd32(h + 9), olen = (int32_t)rd32(h + 13);
+      const uint32_t check = rd32(h + 17);
+      bad |= olen > (int32_t)(1u << level) || olen < 0 || clen < 0 || (olen == 0 && clen != 0) || (olen != 0 && clen == 0) ||
+             (method == 0x10u && olen != clen);                                // :215-222
+      if (bad) { why = CR_CORRUPT; break; }
+      if (olen == 0) {                                                         // :223-233: the empty block
+        if (check != 0u) { why = CR_CORRUPT; break; }
+        p += 21u; why = CR_END; break;
+      }
+      if (max_block != 0u && (uint32_t)olen > max_block) { why = CR_BLOCK_TOO_BIG; break; }   // (a block bigger than the caller allows: not a stream error, the readers take the host walk)
+      if (p + 21u + (uint64_t)clen > body_bytes) { why = CR_TRUNCATED; break; }
+      // clen bytes of LZ4 decode to at most 255 x clen bytes: a header that announces more cannot decode (the reference reads the payload,
+      // fails in the decompressor and says "Stream is corrupted", :236-253) -- said here, so that nobody has to size a slot by it
+      if (method == 0x20u && (uint64_t)olen > 255ull * (uint64_t)clen + 64u) { why = CR_CORRUPT; break; }
+      if ((uint64_t)olen > slot_bytes) { why = CR_BLOCK_TOO_BIG; break; }      // (the caller's slots are too small: not a stream error)
+      const bool raw = method == 0x10u;
+      c.pay_off[k] = p + 21u; c.pay_len[k] = clen;
+      c.src_off[k] = p + 21u; c.src_len[k] = raw ? 0 : clen;                   // (fast decoder: src_len = readable bytes of the slot)
+      c.dst_cap[k] = raw ? 0 : olen;
+      c.meta[k] = (raw ? 1 : 0) | (olen << 1);
+      c.stored[k] = check;
+      p += 21u + (uint64_t)clen;
+      c.end_off[k] = p;
+      k++;
+    }
+  }
+  if (k == n_max && p == body_bytes) why = CR_MORE;   // (every slot used and nothing left: not "more follows")
+  c.walk[0] = k; c.walk[1] = why; c.walk[2] = (uint32_t)p; c.walk[3] = (uint32_t)(p >> 32);
+}
+// ---- The walk in PARALLEL (round 5; the round-4 verdict: the one-lane walk costs 6x the decode of the same blocks -- one dependent DRAM
+// load per block, 36.7 ms for 65536 x 64 KiB against 6.1 ms).  An LZ4Block header starts with the 8-byte magic "LZ4Block"
+// (LZ4BlockOutputStream.java:39); an LZ4 Frame has no marker in front of a block, but a size word can be validated speculatively by the
+// chain of size words behind it (frame_candidate below).  The body is cut into up to 1024 REGIONS,
+//   K0 container_find_kernel: a wavefront per region finds the region's first structurally valid header (coalesced scan, ballot);
+//   K1 container_walk_par_kernel (one workgroup, a lane per region): every lane walks the chain from its region's candidate to the
+//      region's end, COUNTING; one thread stitches the segments in stream order -- the chain position that arrives in a region must BE
+//      that region's first candidate (it then is a header of the true chain, by induction from offset 0), a region the chain jumps over
+//      lies inside a payload and is skipped --; then the lanes walk once more and fill the batch arrays from their block index on.
+// The stop reason, the consumed position and every array entry are the serial walk's (same rules in the same order, container_walk_kernel
+// above): tests compare the two.  Whatever the stitch cannot vouch for -- a damaged header on the chain, a magic inside a payload in
+// front of a region's true header, a cut tail -- sets *par_ok = 0 and the serial walk, launched behind, does the whole body.
+// ------------------------------------------------------------------------------------------------
+#define LZ4HIP_WALK_LANES 1024u
+#define LZ4HIP_WALK_NONE 0xFFFFFFFFFFFFFFFFull
+// the structural rules of an LZ4Block header (LZ4BlockInputStream.java:200-222), as container_walk_kernel applies them
+__device__ __forceinline__ bool lz4block_header_bad(const uint8_t* h, int32_t& clen, int32_t& olen, uint32_t& check, uint32_t& method) {
+  const char* magic = "LZ4Block";
+  bool bad = false;
+  for (int i = 0; i < 8; i++) bad |= h[i] != (uint8_t)magic[i];
+  const uint32_t token = h[8], level = 10u + (token & 0x0Fu);
+  method = token & 0xF0u;
+  bad |= method != 0x10u && method != 0x20u;
+  clen = (int32_t)rd32(h + 9); olen = (int32_t)rd32(h + 13); check = rd32(h + 17);
+  bad |= olen > (int32_t)(1u << level) || olen < 0 || clen < 0 || (olen == 0 && clen != 0) || (olen != 0 && clen == 0) || (method == 0x10u && olen != clen);
+  return bad;
+}
+// LZ4 Frame bodies (kind 0) have no marker, but a size word can be VALIDATED speculatively: a position is a candidate when the chain of
+// size words that starts there holds for `hops` blocks (each size 1 .. max_block, each block inside the body; the end mark, the end of the
+// body and a block cut short end the chain as they end the real one).  A random position passes one hop with probability ~max_block / 2^31:
+// three hops of 64 KiB blocks 2^-42 per position, five hops of 4 MiB blocks 2^-45.  Correctness does not rest on that -- the stitch only
+// accepts a candidate the true chain lands on -- it only decides how often the serial walk has to do the body instead.
+__device__ __forceinline__ bool frame_candidate(const uint8_t* body, uint64_t body_bytes, uint64_t p, uint32_t max_block, uint32_t cks, uint32_t hops) {
+  for (uint32_t h = 0; h < hops; h++) {
+    if (p + 4u > body_bytes) return h != 0u;               // (a cut tail ends a real chain too; the first word must be whole)
+    const uint32_t size = rd32(body + p) & 0x7FFFFFFFu;
+    if (size == 0u) return true;                           // the end mark
+    if (size > max_block) return false;
+    const uint64_t need = 4ull + size + cks;
+    if (p + need > body_bytes) return true;                // a block cut short: "Stream ended prematurely" on the real chain
+    p += need;
+    if (p == body_bytes) return true;
+  }
+  return true;
+}
+__global__ __launch_bounds__(256) void container_find_kernel(int kind, uint32_t max_block, uint32_t cks, const uint8_t* body, uint64_t body_bytes, uint64_t region,
+                                                             uint32_t lanes, uint64_t* first) {
+  const uint32_t w = (blockIdx.x * 256u + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+  if (w >= lanes) return;
+  const uint64_t lo = (uint64_t)w * region, hi = (w + 1u == lanes) ? body_bytes : lo + region;   // candidates p: lo <= p < hi
+  const uint32_t hops = max_block <= (256u << 10) ? 3u : 5u;
+  const uint32_t minb = kind == 1 ? 21u : 4u;              // a candidate's header lies inside the body
+  uint64_t found = LZ4HIP_WALK_NONE;
+  for (uint64_t base = lo; base < hi; base += 1024u) {
+    const uint64_t q = base + lane * 16u;
+    uint64_t mine = LZ4HIP_WALK_NONE;
+    if (q < hi && q + minb <= body_bytes) {
+      // 16 candidate positions q .. q + 15 (bytes read: [q, q + 23) where they exist)
+      uint8_t b[24];
+      const uint64_t avail = body_bytes - q < 24u ? body_bytes - q : 24u;
+      if (avail == 24u) { __builtin_memcpy(b, body + q, 24); } else { for (uint32_t i = 0; i < 24u; i++) b[i] = i < avail ? body[q + i] : 0; }
+#pragma unroll
+      for (uint32_t j = 0; j < 16u; j++) {
+        if (mine != LZ4HIP_WALK_NONE || q + j >= hi || q + j + minb > body_bytes) continue;
+        if (kind == 1) {
+          if (b[j] == 'L' && b[j + 1] == 'Z' && b[j + 2] == '4' && b[j + 3] == 'B' && b[j + 4] == 'l' && b[j + 5] == 'o' && b[j + 6] == 'c' && b[j + 7] == 'k') {
+            int32_t clen, olen; uint32_t check, method;
+            if (!lz4block_header_bad(body + q + j, clen, olen, check, method)) mine = q + j;
+          }
+        } else {
+          const uint32_t size = ((uint32_t)b[j] | ((uint32_t)b[j + 1] << 8) | ((uint32_t)b[j + 2] << 16) | ((uint32_t)b[j + 3] << 24)) & 0x7FFFFFFFu;
+          if (size <= max_block && frame_candidate(body, body_bytes, q + j, max_block, cks, hops)) mine = q + j;
+        }
+      }
+    }
+    const uint64_t hit = __builtin_amdgcn_ballot_w64(mine != LZ4HIP_WALK_NONE);
+    if (hit) {
+      const int src = __builtin_ctzll(hit);
+      found = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, src);
+      break;
+    }
+  }
+  if (lane == 0) first[w] = found;
+}
+// one lane's walk of its region: from p on, headers by the serial walk's rules; COUNT blocks (fill == false) or write their entries from
+// block index k0 on, at most `limit` of them (fill == true).  Ends at the region's end `hi` (hand-over: why stays CR_SLOTS), at the end of
+// the body (CR_MORE) or at the first header that stops the serial walk (its reason).  Returns the blocks taken; p = where it ended.
+__device__ __forceinline__ uint32_t lz4block_walk_region(int kind, uint32_t max_block, uint32_t cks, const uint8_t* body, uint64_t body_bytes, uint64_t slot_bytes,
+                                                         uint64_t& p, uint64_t hi, bool last, uint32_t& why, bool fill, uint32_t k0, uint32_t limit, const ContainerRead& c) {
+  uint32_t k = 0;
+  why = CR_SLOTS;
+  while (k < limit) {
+    if (p == body_bytes) { why = CR_MORE; break; }
+    if (!last && p >= hi) break;
+    if (kind == 0) {                                       // LZ4 Frame: the size words (LZ4FrameInputStream.java:258-322), as container_walk_kernel
+      if (p + 4u > body_bytes) { why = CR_TRUNCATED; break; }
+      const uint32_t word = rd32(body + p), size = word & 0x7FFFFFFFu;
+      if (size == 0u) { p += 4u; why = CR_END; break; }
+      if (size > max_block) { why = CR_BLOCK_TOO_BIG; break; }
+      const uint64_t need = 4ull + size + cks;
+      if (p + need > body_bytes) { why = CR_TRUNCATED; break; }
+      const bool raw = (word & 0x80000000u) != 0u;
+      if (raw && size > slot_bytes) { why = CR_BLOCK_TOO_BIG; break; }
+      if (fill) {
+        const uint32_t b = k0 + k;
+        c.pay_off[b] = p + 4u; c.pay_len[b] = (int32_t)size;
+        c.src_off[b] = p + 4u; c.src_len[b] = raw ? 0 : (int32_t)size;
+        c.dst_cap[b] = raw ? 0 : (int32_t)(max_block < slot_bytes ? max_block : (uint32_t)slot_bytes);
+        c.meta[b] = raw ? 1 : 0;
+        if (cks) c.stored[b] = rd32(body + p + 4u + size);
+        c.end_off[b] = p + need;
+      }
+      p += need;
+      k++;
+      continue;
+    }
+    if (p + 21u > body_bytes) { why = CR_TRUNCATED; break; }
+    int32_t clen, olen; uint32_t check, method;
+    if (lz4block_header_bad(body + p, clen, olen, check, method)) { why = CR_CORRUPT; break; }
+    if (olen == 0) {
+      if (check != 0u) { why = CR_CORRUPT; break; }
+      p += 21u; why = CR_END; break;
+    }
+    if (max_block != 0u && (uint32_t)olen > max_block) { why = CR_BLOCK_TOO_BIG; break; }
+    if (p + 21u + (uint64_t)clen > body_bytes) { why = CR_TRUNCATED; break; }
+    if (method == 0x20u && (uint64_t)olen > 255ull * (uint64_t)clen + 64u) { why = CR_CORRUPT; break; }   // (cannot decode: container_walk_kernel)
+    if ((uint64_t)olen > slot_bytes) { why = CR_BLOCK_TOO_BIG; break; }
+    if (fill) {
+      const uint32_t b = k0 + k;
+      const bool raw = method == 0x10u;
+      c.pay_off[b] = p + 21u; c.pay_len[b] = clen;
+      c.src_off[b] = p + 21u; c.src_len[b] = raw ? 0 : clen;
+      c.dst_cap[b] = raw ? 0 : olen;
+      c.meta[b] = (raw ? 1 : 0) | (olen << 1);
+      c.stored[b] = check;
+      c.end_off[b] = p + 21u + (uint64_t)clen;
+    }
+    p += 21u + (uint64_t)clen;
+    k++;
+  }
+  return k;
+}
+__global__ __launch_bounds__(1024) void container_walk_par_kernel(int kind, uint32_t max_block, uint32_t cks, const uint8_t* body, uint64_t body_bytes, uint64_t slot_bytes,
+                                                                  uint32_t n_max, uint64_t region, uint32_t lanes, const uint64_t* first, ContainerRead c, uint32_t* par_ok) {
+  __shared__ uint32_t s_cnt[LZ4HIP_WALK_LANES], s_why[LZ4HIP_WALK_LANES], s_base[LZ4HIP_WALK_LANES], s_limit[LZ4HIP_WALK_LANES];
+  __shared__ uint64_t s_end[LZ4HIP_WALK_LANES];
+  __shared__ uint32_t s_ok, s_total, s_stop_why, s_stop_lane;
+  __shared__ uint64_t s_stop_pos;
+  const uint32_t t = threadIdx.x;
+  // every entry gets a value (the decode launch covers all n_max slots): blocks that are not walked decode nothing
+  for (uint32_t i = t; i < n_max; i += LZ4HIP_WALK_LANES) { c.src_off[i] = 0; c.src_len[i] = 0; c.dst_off[i] = (uint64_t)i * slot_bytes; c.dst_cap[i] = 0; c.out[i] = 0;
+                                                            c.pay_off[i] = 0; c.pay_len[i] = 0; c.end_off[i] = 0; c.stored[i] = 0; c.hashes[i] = 0; c.meta[i] = 0; }
+  const uint64_t lo = (uint64_t)t * region, hi = lo + region;
+  const bool last = t + 1u == lanes;
+  if (t < lanes) {
+    uint64_t p = first[t];
+    uint32_t why = CR_SLOTS, k = 0;
+    if (p != LZ4HIP_WALK_NONE) k = lz4block_walk_region(kind, max_block, cks, body, body_bytes, slot_bytes, p, hi, last, why, false, 0u, 0xFFFFFFFFu, c);
+    s_cnt[t] = k; s_why[t] = why; s_end[t] = p; s_limit[t] = 0u;
+  }
+  __syncthreads();
+  if (t == 0) {
+    // the stitch: cur = where the true chain stands; it starts at offset 0
+    uint64_t cur = 0;
+    uint32_t k = 0, ok = 1u, why = CR_SLOTS, stop_lane = 0xFFFFFFFFu;
+    if (body_bytes == 0) { why = CR_MORE; }
+    else for (uint32_t i = 0; i < lanes; i++) {
+      const uint64_t rhi = (i + 1u == lanes) ? LZ4HIP_WALK_NONE : (uint64_t)(i + 1u) * region;
+      if (cur >= rhi) continue;                              // the chain jumps over this region: it lies inside a payload
+      if (first[i] != cur) { ok = 0u; break; }               // (no candidate where the chain arrives, or a magic in front of it: the serial walk decides)
+      s_base[i] = k;
+      if (k + s_cnt[i] >= n_max) {                           // the slots run out inside this lane (or exactly at its end)
+        s_limit[i] = n_max - k; stop_lane = i; why = CR_SLOTS; k = n_max; break;
+      }
+      s_limit[i] = s_cnt[i];
+      k += s_cnt[i]; cur = s_end[i];
+      if (s_why[i] != CR_SLOTS) { why = s_why[i]; stop_lane = i; break; }
+    }
+    // (a chain that ran through every lane ends with the last lane's reason: CR_MORE at the end of the body or a stop)
+    s_ok = ok; s_total = k; s_stop_why = why; s_stop_lane = stop_lane; s_stop_pos = cur;
+  }
+  __syncthreads();
+  if (s_ok == 0u) { if (t == 0) *par_ok = 0u; return; }
+  if (t < lanes && s_limit[t] != 0u) {
+    uint64_t p = first[t];
+    uint32_t why;
+    (void)lz4block_walk_region(kind, max_block, cks, body, body_bytes, slot_bytes, p, hi, last, why, true, s_base[t], s_limit[t], c);
+    if (t == s_stop_lane && s_stop_why == CR_SLOTS) s_stop_pos = p;   // the slots ran out in this lane: the walk stands behind its last block
+  }
+  __syncthreads();
+  if (t == 0) {
+    uint32_t why = s_stop_why;
+    const uint64_t p = s_stop_pos;
+    if (s_total == n_max && p == body_bytes) why = CR_MORE;   // (every slot used and nothing left: not "more follows")
+    c.walk[0] = s_total; c.walk[1] = why; c.walk[2] = (uint32_t)p; c.walk[3] = (uint32_t)(p >> 32);
+    *par_ok = 1u;
+  }
+}
+
+// raw blocks: payload -> slot (one workgroup per block); also the length array of the LZ4Block checksum pass
+__global__ __launch_bounds__(256) void container_raw_kernel(int kind, const uint8_t* body, uint8_t* dst, ContainerRead c, int32_t* hash_len) {
+  const uint32_t b = blockIdx.x;
+  if (b >= c.walk[0]) { if (threadIdx.x == 0) hash_len[b] = 0; return; }
+  const bool raw = (c.meta[b] & 1) != 0;
+  const uint32_t len = (uint32_t)c.pay_len[b];
+  if (threadIdx.x == 0) hash_len[b] = kind == 1 ? (raw ? (int32_t)len : (c.meta[b] >> 1)) : 0;
+  if (!raw) return;
+  const uint8_t* s = body + c.pay_off[b];
+  uint8_t* d = dst + c.dst_off[b];
+  const uint32_t body16 = len & ~15u;
+  for (uint32_t i = threadIdx.x * 16u; i < body16; i += 256u * 16u) { uint4 v; __builtin_memcpy(&v, s + i, 16); __builtin_memcpy(d + i, &v, 16); }
+  const uint32_t i = body16 + threadIdx.x;
+  if (i < len) d[i] = s[i];
+  if (threadIdx.x == 0) c.out[b] = (int32_t)len;
+}
+// the first block that fails, in stream order, with the readers' order of checks inside a block
+__global__ __launch_bounds__(1024) void container_verdict_kernel(int kind, int block_checksum, ContainerRead c, int32_t* sizes, unsigned long long* info) {
+  __shared__ uint32_t first_bad;
+  __shared__ unsigned long long total;
+  if (threadIdx.x == 0) { first_bad = 0xFFFFFFFFu; total = 0; }
+  __syncthreads();
+  const uint32_t n = c.walk[0];
+  for (uint32_t b = threadIdx.x; b < n; b += 1024u) {
+    const bool raw = (c.meta[b] & 1) != 0;
+    bool bad;
+    if (kind == 0) bad = (block_checksum && c.hashes[b] != c.stored[b]) || (!raw && c.out[b] < 0);
+    else bad = (!raw && c.out[b] != c.pay_len[b]) || ((c.hashes[b] & 0x0FFFFFFFu) != c.stored[b]);   // consumed == compressedLen, then the check
+    if (bad) atomicMin(&first_bad, b);
+  }
+  __syncthreads();
+  const uint32_t nok = first_bad < n ? first_bad : n;
+  for (uint32_t b = threadIdx.x; b < n; b += 1024u) {
+    const bool raw = (c.meta[b] & 1) != 0;
+    const int32_t sz = kind == 0 ? c.out[b] : (raw ? c.pay_len[b] : (c.meta[b] >> 1));
+    sizes[b] = sz;
+    if (b < nok) atomicAdd(&total, (unsigned long long)(sz > 0 ? sz : 0));
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t why = c.walk[1];
+    long long code = 0;
+    if (nok < n) {
+      const bool raw = (c.meta[nok] & 1) != 0;
+      if (kind == 0) { if (block_checksum && c.hashes[nok] != c.stored[nok]) why = CR_BLOCK_CHECKSUM; else { why = CR_DECODE; code = c.out[nok]; } }
+      else { why = CR_CORRUPT; (void)raw; }
+    }
+    info[0] = nok;
+    info[1] = nok < n ? (nok ? c.end_off[nok - 1u] : 0ull) : ((unsigned long long)c.walk[2] | ((unsigned long long)c.walk[3] << 32));
+    info[2] = why;
+    info[3] = total;
+    info[4] = (unsigned long long)code;
+  }
+}
+size_t container_read_ws_bytes(uint32_t n_max) { return (size_t)n_max * (4u * 8u + 8u * 4u) + 64u + 16u + LZ4HIP_WALK_LANES * 8u; }   // (+ the parallel walk's candidate per region)
+int launch_container_read(int kind, int block_checksum, const uint8_t* body, uint64_t body_bytes, uint32_t max_block, uint8_t* dst, uint64_t slot_bytes,
+                          uint32_t n_max, int32_t* sizes, unsigned long long* info, void* ws, void* stream) {
+  if (n_max == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  uint8_t* p = (uint8_t*)ws;
+  ContainerRead c;
+  c.src_off = (uint64_t*)p; c.dst_off = c.src_off + n_max; c.pay_off = c.dst_off + n_max; c.end_off = c.pay_off + n_max;
+  c.src_len = (int32_t*)(c.end_off + n_max); c.dst_cap = c.src_len + n_max; c.out = c.dst_cap + n_max; c.pay_len = c.out + n_max;
+  c.stored = (uint32_t*)(c.pay_len + n_max); c.hashes = c.stored + n_max; c.meta = (int32_t*)(c.hashes + n_max);
+  int32_t* hash_len = c.meta + n_max;
+  c.walk = (uint32_t*)(hash_len + n_max);
+  uint32_t* par_ok = nullptr;
+  if (body_bytes >= 65536u) {   // the walk in parallel (smaller bodies: the serial walk is a few loads)
+    uint64_t* first = (uint64_t*)(((uintptr_t)(c.walk + 16) + 7u) & ~(uintptr_t)7u);
+    par_ok = c.walk + 9;
+    uint32_t lanes = (uint32_t)(body_bytes / 16384u < LZ4HIP_WALK_LANES ? body_bytes / 16384u : LZ4HIP_WALK_LANES);
+    if (lanes == 0u) lanes = 1u;
+    const uint64_t region = ((body_bytes + lanes - 1u) / lanes + 1023u) & ~1023ull;
+    lanes = (uint32_t)((body_bytes + region - 1u) / region);
+    const uint32_t cks = (kind == 0 && block_checksum) ? 4u : 0u;
+    hipLaunchKernelGGL(container_find_kernel, dim3((lanes + 3u) / 4u), dim3(256), 0, st, kind, max_block, cks, body, body_bytes, region, lanes, first);
+    hipLaunchKernelGGL(container_walk_par_kernel, dim3(1), dim3(LZ4HIP_WALK_LANES), 0, st, kind, max_block, cks, body, body_bytes, slot_bytes, n_max, region, lanes, first, c, par_ok);
+  }
+  hipLaunchKernelGGL(container_walk_kernel, dim3(1), dim3(64), 0, st, kind, block_checksum, body, body_bytes, max_block, slot_bytes, n_max, c, par_ok);
+  int e;
+  if (kind == 0 && block_checksum && (e = launch_xxh32(body, c.pay_off, c.pay_len, 0u, c.hashes, n_max, stream)) != 0) return e;
+  BatchArgs a{body, c.src_off, c.src_len, dst, c.dst_off, c.dst_cap, c.out, n_max};
+  if ((e = launch_decompress(a, kind == 0, 0, -1, -1, 0, stream, c.walk + 8)) != 0) return e;   // (c.walk + 8: a scratch word for the device-side route, so that a frame of 12288+ big blocks gets the ring loop like a plain batch)
+  hipLaunchKernelGGL(container_raw_kernel, dim3(n_max), dim3(256), 0, st, kind, body, dst, c, hash_len);
+  if (kind == 1 && (e = launch_xxh32(dst, c.dst_off, hash_len, 0x9747b28cu, c.hashes, n_max, stream)) != 0) return e;
+  hipLaunchKernelGGL(container_verdict_kernel, dim3(1), dim3(1024), 0, st, kind, block_checksum, c, sizes, info);
+  return (int)hipGetLastError();
+}
+
+}  // namespace lz4hip

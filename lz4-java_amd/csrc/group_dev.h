@@ -15,7 +15,17 @@
 #endif
 namespace lz4hip {
 #ifdef LZ4HIP_RING_DBG
-__device__ unsigned long long g_ring_stat[8];   // developer build: trips, stalled trips, frozen trips, (re-)seeds, trips spent waiting for another block, loop entries
+// developer build: trips, stalled trips, frozen trips, (re-)seeds, trips spent waiting for another block, loop entries.  One copy per
+// translation unit that includes this header (static: the decoder families are separate units); ring_stats_take adds this unit's copy
+// to sum8 and clears it (kernels_internal.h has the units that count, decode.hip's ring_stats_fetch adds them up)
+static __device__ unsigned long long g_ring_stat[8];
+static inline int ring_stats_take(unsigned long long* sum8) {
+  unsigned long long v[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  hipError_t e = hipMemcpyFromSymbol(v, HIP_SYMBOL(g_ring_stat), sizeof v);
+  if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_ring_stat), z, sizeof z);
+  for (int i = 0; i < 8 && e == hipSuccess; i++) sum8[i] += v[i];
+  return (int)e;
+}
 #endif
 
 // KW: bytes of the output ring of the ring loop (lz4_decode_ring.h; 0 = the other loops)

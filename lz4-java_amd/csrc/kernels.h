@@ -1,4 +1,4 @@
-// kernels.h -- host-callable launchers of the gfx950 kernels (kernels.hip).  All pointers are device
+// kernels.h -- host-callable launchers of the gfx950 kernels (one csrc/*.hip unit per kernel family).  All pointers are device
 // pointers; launches are asynchronous on `stream`.  Return value: hipError_t as int.
 #pragma once
 #include <stdint.h>
@@ -51,7 +51,7 @@ int launch_compress_hc(const BatchArgs& a, int level, void* ws, uint64_t span, v
 int launch_compress_hc_dest(const BatchArgs& a, int32_t* consumed, int level, void* ws, uint64_t span, void* stream);
 // after a compress launch: moves the out[i] > 0 useful bytes of every slot to pack + sum(out[0..i)); poff: u64[n] scratch
 int launch_pack(const BatchArgs& a, uint64_t* poff, uint8_t* pack, void* stream);
-// Device-side container assembly (kernels.hip): the data blocks of an LZ4 Frame (kind 0; block_checksum: XXH32 of each stored
+// Device-side container assembly (container.hip): the data blocks of an LZ4 Frame (kind 0; block_checksum: XXH32 of each stored
 // payload) or of lz4-java's LZ4Block container (kind 1) for src[0, n_bytes) cut into block_size pieces -> dst, *total = bytes
 // written (if it exceeds dst_cap nothing past dst_cap was written and the caller must not use the result).  ws: device scratch of
 // container_ws_bytes(); hc_level > 0: LZ4 HC at that level (hc_ws = hc_ws_bytes(n_bytes, n, level)), else the fast compressor
@@ -59,7 +59,7 @@ int launch_pack(const BatchArgs& a, uint64_t* poff, uint8_t* pack, void* stream)
 size_t container_ws_bytes(uint64_t n_bytes, uint32_t block_size);
 int launch_container_blocks(int kind, int block_checksum, int hc_level, const uint8_t* src, uint64_t n_bytes, uint32_t block_size, uint8_t* dst, uint64_t dst_cap,
                             unsigned long long* total, void* ws, void* hc_ws, uint32_t* q_scratch, uint32_t dense64, uint32_t n_cus, int core, void* stream);
-// Device-side container READ path (kernels.hip): the data blocks of an LZ4 Frame body (kind 0; block_checksum: a XXH32 word behind
+// Device-side container READ path (container.hip): the data blocks of an LZ4 Frame body (kind 0; block_checksum: a XXH32 word behind
 // each payload) or of an LZ4Block stream (kind 1) in body[0, body_bytes) are walked, verified and decoded; block k decodes to
 // dst + k * slot_bytes, sizes[k] = its decoded size, info[0..4] = {blocks delivered, body bytes consumed, stop reason, decoded bytes,
 // liblz4 code of a failed decode}; ws = container_read_ws_bytes(n_max) bytes of device scratch
@@ -74,7 +74,7 @@ int launch_container_read(int kind, int block_checksum, const uint8_t* body, uin
 // on the device (decode_route_kernel): by the blocks' compressed sizes between the deep loop and the ring loop (12288 .. 40959 blocks), by
 // the streams' sequence density between the lane-group loops and the wave kernel (set_route_short: average output bytes per sequence up to which a batch is text-like, 0 = never) and between the staged and the deep loop (40960 blocks and more: near sources)
 void set_route_short(int bytes_per_sequence);
-int last_decode_route(uint32_t* out6);   // diagnostic (8 words): {route, sampled hops, sampled stream bytes, average compressed size, offsets within 6 KB, sequences looked at, their output bytes, 0} of the current device's last routed launch (synchronises)
+int last_decode_route(uint32_t* out8);   // diagnostic (8 words): {route, sampled hops, sampled stream bytes, average compressed size, offsets within 6 KB, sequences looked at, their output bytes, 0} of the current device's last routed launch (synchronises)
 int launch_decompress(const BatchArgs& a, bool safe, int lanes_per_block, int pipe, int stage, int ring, void* stream, uint32_t* route_word = nullptr);
 // LZ4_decompress_safe_partial: block i decodes into min(target[i], a.dst_cap[i]) bytes (-1 where one of them or src_len[i] is
 // negative); out[i] = liblz4's return value.  >= 40960 blocks: decode_partial_kernel<4, 0, true> (staged), fewer:

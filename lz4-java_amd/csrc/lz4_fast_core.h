@@ -263,7 +263,7 @@ constexpr uint32_t SEQ_NOCHECK = 1u << 29, SEQ_LIT_MASK = (1u << 29) - 1u;
 
 // PK (byU32 blocks of at most 4 MiB only -- the largest block of the LZ4 Frame format and its default in the reference's
 // LZ4FrameOutputStream): the 4096 entries are 32 bits, {position (22 bits), fingerprint (10 bits)}, 16 KB instead of 32 -- twice the
-// match-finder chains per CU (kernels.hip, compress_fast_v2w8_cu_kernel).  A narrower fingerprint only means more tentative hits that
+// match-finder chains per CU (compress_fast.hip, compress_fast_v2w8_cu_kernel).  A narrower fingerprint only means more tentative hits that
 // their candidate bytes rule out; what is accepted and what the table holds are liblz4's at any width.
 // ACC: LZ4_compress_fast(..., acceleration) -- every miss-run starts with searchMatchNb = accel << 6 instead of 1 << 6, so probe k
 // of a run sits at S + g_a(k) (see g_acc); `accel` (>= 1, clamped by the caller) is read only then.  Its steps no longer sit on

@@ -1,4 +1,4 @@
-// mail_ring.h -- the finder / writer hand-over of the default fast-compress kernel (kernels.hip, compress_fast_v2w_cu_kernel).
+// mail_ring.h -- the finder / writer hand-over of the default fast-compress kernel (compress_fast.hip, compress_fast_v2w_cu_kernel).
 //
 // A finder wavefront (lz4_fast_v2_core.h) parks bare hits 64 at a time; every full batch -- 3 x 64 words + a header {kind, block,
 // count, x} -- goes into a slot of a small ring in global memory, and a WRITER wavefront of the same workgroup takes the slots in
@@ -10,7 +10,7 @@
 // is left to the window-parallel kernel: forget it), EXIT (the queue is empty).
 //
 // Written against the wave backend W and a memory policy M { peek, peek_far, acquire, publish, nap_finder, nap_writer, uptr, u32,
-// block_begin, result }: the device policy (kernels.hip, MailDev) orders at workgroup scope; the CPU suite's policy
+// block_begin, result }: the device policy (compress_fast.hip, MailDev) orders at workgroup scope; the CPU suite's policy
 // (tests/hostsim) uses two host threads with acquire / release atomics, a ring of two slots and random naps, and runs THIS source.
 #pragma once
 #include "lz4_fast_v2_core.h"

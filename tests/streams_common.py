@@ -74,7 +74,7 @@ class OracleEngine:
 
 
 class OracleDeviceEngine(OracleEngine):
-    """OracleEngine + `containerDecode`: a host restatement of the device read path (kernels.hip container_walk_kernel / _raw_kernel /
+    """OracleEngine + `containerDecode`: a host restatement of the device read path (container.hip container_walk_kernel / _raw_kernel /
     _verdict_kernel: the walk's rules in their order, the first failing block in the readers' order of checks), so that the CPU suite
     runs the readers' DEVICE-PATH logic (chunking, hand-back of unconsumed bytes, stop reasons -> exceptions) that
     tests/test_gpu_streams.py runs on the GPU.  Test infrastructure only."""

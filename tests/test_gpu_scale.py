@@ -432,7 +432,7 @@ def test_host_batch_many_chunks_ragged_concurrent_callers(amd, ref, O):
 
 def test_batches_that_are_not_a_multiple_of_a_workgroup_per_cu_vs_reference(amd, ref):
     """The trio and wave kernels give a workgroup W blocks; a batch that is not a multiple of W x CUs is SPREAD -- wavefront k of workgroup i takes
-    block i + k * grid, every CU gets ceil(n / CUs) blocks (kernels.hip wave_spread) -- where that puts fewer blocks on a CU than packing W neighbours
+    block i + k * grid, every CU gets ceil(n / CUs) blocks (kernels_internal.h wave_spread) -- where that puts fewer blocks on a CU than packing W neighbours
     does.  Batch sizes on both sides of every W (trio 1 / 2 / 4 / 5, wave 8 / 16) with every knob at its default, safe and fast decoders: sizes and
     bytes against the source, a sample of streams against the reference's own bytes, a damaged sample against LZ4_decompress_safe (LZ4JNI.c:216)."""
     import numpy as np

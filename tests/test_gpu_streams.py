@@ -205,7 +205,7 @@ def test_device_container_exact_capacity_and_too_small(amd, O, corpus):
 
 
 def test_lz4block_parallel_walk_equals_serial_rules(S, amd, O, port, corpus):
-    """LZ4Block streams of more than 64 KB are walked IN PARALLEL on the device (kernels.hip container_find_kernel +
+    """LZ4Block streams of more than 64 KB are walked IN PARALLEL on the device (container.hip container_find_kernel +
     container_walk_par_kernel: a candidate header per region, a lane per region, a stitch in stream order; the serial walk behind it
     for whatever the stitch cannot vouch for).  lz4hip_container_decode against the host restatement of the walk's rules
     (streams_common.OracleDeviceEngine.containerDecode: LZ4BlockInputStream.java:191-264 in order): blocks delivered, their sizes and

@@ -128,7 +128,7 @@ def test_bench_live_traffic_falls_back_without_a_gpu(monkeypatch):
 
 def test_bench_names_the_decoder_the_library_routes_to():
     """bench.py's roofline objects name the decoder instantiation by batch size (decode_kernel_name); the table must be the one of
-    lz4-java_amd/csrc/kernels.hip launch_decompress / launch_decode_wave on a 256-CU device -- and every name it can return must be
+    lz4-java_amd/csrc/decode.hip launch_decompress / decode_wave.hip launch_decode_wave on a 256-CU device -- and every name it can return must be
     a key of profiles/traffic.json's per-kernel table when the committed passes are current (a renamed kernel would silently lose
     its `traffic`)."""
     import json
@@ -143,7 +143,7 @@ def test_bench_names_the_decoder_the_library_routes_to():
         assert bench.decode_kernel_name(n) == name, (n, bench.decode_kernel_name(n))
     assert bench.decode_kernel_name(16384, big_blocks=True) == "decode_ring_kernel<4, 2048, true>"
     assert bench.decode_kernel_name(65536, safe=False) == "decode_kernel<4, false, 0, true>"
-    src = open(os.path.join(ROOT, "lz4-java_amd", "csrc", "kernels.hip")).read()
+    src = open(os.path.join(ROOT, "lz4-java_amd", "csrc", "decode.hip")).read()
     assert "a.n <= 5u * device_cus()" in src and "a.n <= 16u * device_cus()" in src and "a.n >= 40960u ? 4 : 8" in src and "a.n >= 16384u && a.n < 40960u" in src and "a.n <= 32u * device_cus()" in src   # the thresholds the table restates
     tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
     if tr.get("kernel_source_hash") == bench.kernel_source_hash():
