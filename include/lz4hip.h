@@ -19,6 +19,9 @@
  *                                (exported by the reference's liblz4-java.so; no JNI entry of the reference reaches it)
  *   lz4hip_decompress_safe_partial* = LZ4_decompress_safe_partial(src, dst, srcSize, targetOutputSize, dstCapacity) of liblz4's
  *                                main API (exported by the reference's liblz4-java.so; no JNI entry of the reference reaches it)
+ *   lz4hip_decompress_safe_dict* = LZ4_decompress_safe_usingDict(src, dst, srcSize, dstCapacity, dictStart, dictSize) of liblz4's
+ *                                main API, for a dictionary that is not contiguous with dst (exported by the reference's
+ *                                liblz4-java.so; no JNI entry of the reference reaches it)
  *   lz4hip_xxh32* / xxh64*    <- Java_net_jpountz_xxhash_XXHashJNI_XXH32 / XXH64
  *                                (src/jni/net_jpountz_xxhash_XXHashJNI.c:42-59 / :152-169, calls :54 / :164)
  *
@@ -90,7 +93,8 @@ int lz4hip_version(void);
  * "compress_pack" = 1 (default) / 0: blocks of 65547 bytes .. 4 MiB are compressed with 32-bit table entries on ten match-finder chains
  *   per CU instead of five (0: every block on the five-chain kernel).
  * The decode_* knobs and the device-side route do not apply to the partial decoder (lz4hip_decompress_safe_partial*): it always runs the
- * 4-lane staged loop from 40960 blocks on and the 8-lane deep loop below.                                                        */
+ * 4-lane staged loop from 40960 blocks on and the 8-lane deep loop below.  Nor do they apply to the dictionary decoder
+ * (lz4hip_decompress_safe_dict*), which picks its two loops the same way.                                                       */
 int lz4hip_set_option(const char* name, int value);
 /* diagnostic: what the device-side route of a device's last routed decode launch decided (device = index as in the _dev calls) -- out8
  * (8 words) = { route (0 lane-group default of the batch size, 1 ring loop, 2 wave loop, 3 deep loop instead of the staged one), hops
@@ -157,6 +161,38 @@ int lz4hip_compress_dest_size_batch(const uint8_t* src, const uint64_t* src_off,
 int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                          uint8_t* dst, const uint64_t* dst_off, const int32_t* target_len,
                                          const int32_t* dst_cap, int32_t* out_len, uint32_t n_blocks);
+/* DECODE AGAINST A DICTIONARY: the return value and bytes of LZ4_decompress_safe_usingDict(src, dst, src_len, dst_cap, dict,
+ * dict_len), liblz4 1.9.3, for a dictionary that is NOT contiguous with dst (liblz4's external-dictionary mode) -- records that
+ * were each compressed alone against one shared dictionary (LZ4_loadDict + LZ4_compress_fast_continue, LZ4_loadDictHC +
+ * LZ4_compress_HC_continue), every one of them readable on its own.  Decoding only: there is no dictionary compressor, no
+ * dictionary form of the fast decoder, of the partial decoder or of the size query, and no prefix mode (linked blocks).
+ *   - out_len[i] is liblz4's return value on valid AND malformed streams: the decoded size, or -(input position) - 1;
+ *   - offsets: with dict_len < 65536 an offset is valid iff offset <= output position + dict_len; with dict_len >= 65536 no
+ *     offset is rejected and only the dictionary's last 64 KB can be reached (liblz4's rule, checked where the safe decoder
+ *     checks offset > output position: in front of a match length's extension bytes in the fast tier, behind them elsewhere);
+ *   - a match that starts before the block takes (offset - output position) bytes from the dictionary's end, or fewer if it is
+ *     shorter, and the rest from the block's own start, byte by byte (the rest may overlap what it writes); it is an error if it
+ *     ends within the last 5 bytes of dst_cap[i], and no other end-of-block rule applies to it;
+ *   - dict_len == 0 is lz4hip_decompress_safe* exactly; a negative src_len[i] or dst_cap[i] gives -1;
+ *   - nothing outside [dict, dict + dict_len) is read and nothing outside block i's slot dst[dst_off[i] .. + dst_cap[i]) is written;
+ *   - a handle (lz4hip_dict_create) keeps the true length and the last 64 KB, resident on every initialised device (a device
+ *     initialised later gets its copy on first use; creating a handle does not initialise the engine); it is immutable: any number
+ *     of threads may decode against it, and it must outlive every call that uses it.  dict == NULL, out == NULL or a negative length
+ *     is LZ4HIP_E_ARG.  Creating a handle needs no device (lz4hip_dict_size then still answers); decoding against it without one is
+ *     LZ4HIP_E_NO_DEVICE;
+ *   - two kernels: >= 40960 blocks decode_dict_kernel (4 lanes per block, output staged in LDS), fewer decode_dict_deep_kernel
+ *     (8 lanes, the deep loop, the pipelined loop for streams under 2 KB) -- the safe decoder's unrouted lane-group loops with the
+ *     core's DICT switch: their interior loops also take the matches that lie wholly inside the dictionary; the decode_* knobs
+ *     and the device-side route do not apply;
+ *   - the host batch shards over the initialised devices as the safe decoder's does; library failures as the status of the call;
+ *   - single calls (lz4hip_decompress_safe_dict) are coalesced only with concurrent calls on the SAME handle.                   */
+typedef struct lz4hip_dict lz4hip_dict;
+int lz4hip_dict_create(const uint8_t* dict, int dict_len, lz4hip_dict** out);
+int lz4hip_dict_size(const lz4hip_dict* dict);   /* the true length given to lz4hip_dict_create (NULL: LZ4HIP_E_ARG) */
+void lz4hip_dict_free(lz4hip_dict* dict);        /* NULL is fine; no call on the handle may be in flight */
+int lz4hip_decompress_safe_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                      int32_t* out_len, uint32_t n_blocks, const lz4hip_dict* dict);
 int lz4hip_compress_hc_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                              uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                              int32_t* out_len, uint32_t n_blocks, int level);
@@ -241,6 +277,14 @@ int lz4hip_compress_dest_size_batch_dev(const uint8_t* src, const uint64_t* src_
 int lz4hip_decompress_safe_partial_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                              uint8_t* dst, const uint64_t* dst_off, const int32_t* target_len,
                                              const int32_t* dst_cap, int32_t* out_len, uint32_t n_blocks, int device, void* stream);
+/* decode against a dictionary (see lz4hip_decompress_safe_dict_batch): device pointers, dict_dev[0 .. dict_len) the caller's device
+ * memory on `device` (the whole dictionary or, equally, its last 64 KB with dict_len >= 65536); asynchronous, no synchronisation:
+ * the dictionary must stay valid until the work on `stream` is done.  dict_len < 0, or dict_dev == NULL with dict_len > 0, is
+ * LZ4HIP_E_ARG */
+int lz4hip_decompress_safe_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                          uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                          int32_t* out_len, uint32_t n_blocks, const uint8_t* dict_dev, int dict_len,
+                                          int device, void* stream);
 /* HC: levels follow liblz4 (< 1 -> 9, > 12 -> 12): 1..9 = hash-chain strategy with lazy evaluation, 10..12 = optimal
  * parser (lz4-java levels 10..17).  Levels 10..12 are FUNCTIONAL ONLY: byte-identical output, but the optimal parser's table
  * walk is wave-uniform scalar work (about 1.0 / 0.7 GB/s per GPU at levels 10 / 12 -- no faster than the reference on the host's
@@ -303,6 +347,7 @@ int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int ds
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len);
 int lz4hip_decompress_safe_partial(const uint8_t* src, int src_len, uint8_t* dst, int target_size, int dst_cap);  /* LZ4_decompress_safe_partial */
 int lz4hip_decompressed_size(const uint8_t* src, int src_len, int dst_cap);  /* what LZ4_decompress_safe(src, dst, src_len, dst_cap) would return; no dst */
+int lz4hip_decompress_safe_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, const lz4hip_dict* dict);  /* LZ4_decompress_safe_usingDict; dict == NULL: LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
 int lz4hip_xxh32(const uint8_t* buf, int len, uint32_t seed, uint32_t* out);
 int lz4hip_xxh64(const uint8_t* buf, int len, uint64_t seed, uint64_t* out);
 

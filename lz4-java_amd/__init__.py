@@ -54,12 +54,17 @@ C_ABI = {
     "lz4hip_decompress_fast_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_decompress_safe_partial_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, _i32p, C.c_uint32]),
     "lz4hip_decompressed_size_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, _i32p, _i32p, C.c_uint32]),
+    "lz4hip_dict_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "lz4hip_dict_size": (C.c_int, [C.c_void_p]),
+    "lz4hip_dict_free": (None, [C.c_void_p]),
+    "lz4hip_decompress_safe_dict_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_void_p]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_fast_accel_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_dest_size_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_decompress_safe_partial_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
+    "lz4hip_decompress_safe_dict_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_dest_size_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_dest_size_batch_dev_ws": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
@@ -78,6 +83,7 @@ C_ABI = {
     "lz4hip_decompress_safe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_safe_partial": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "lz4hip_decompress_safe_dict": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "lz4hip_decompressed_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_xxh32": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, _u32p]),
     "lz4hip_xxh64": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _u64p]),
@@ -291,6 +297,46 @@ class LZ4HCHIPCompressor(LZ4Compressor):
 # ----------------------------------------------------------------------------------------------
 # decompressors
 # ----------------------------------------------------------------------------------------------
+class LZ4Dictionary:
+    """A shared dictionary for LZ4_decompress_safe_usingDict (lz4hip_dict_create): the handle keeps the true length and the last 64 KB,
+    resident on every initialised device.  Immutable; any number of threads may decode against it.  close() -- or leaving a `with`
+    block -- frees it; no call that uses it may be in flight then."""
+
+    def __init__(self, data):
+        n = len(data)
+        p, keep = _ro_ptr(data if n else b"\0")
+        self._h = C.c_void_p(None)
+        _chk(lib().lz4hip_dict_create(p, n, C.byref(self._h)))
+
+    def _handle(self):
+        if not self._h:
+            raise AssertionError("Already closed")
+        return self._h
+
+    def __len__(self):
+        return lib().lz4hip_dict_size(self._handle())
+
+    def close(self):
+        if self._h:
+            lib().lz4hip_dict_free(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __repr__(self):
+        return "LZ4Dictionary(%s)" % ("%d bytes" % len(self) if self._h else "closed")
+
+
 class LZ4SafeDecompressor:
     """lz4/LZ4SafeDecompressor.java; JNI twin LZ4JNISafeDecompressor.java:34-43"""
 
@@ -312,6 +358,21 @@ class LZ4SafeDecompressor:
         _check_range(dest, destOff, maxDestLen)
         sp, sk = _ro_ptr(src)
         result = _single(lib().lz4hip_decompress_safe(sp + srcOff, srcLen, dp + destOff, maxDestLen))
+        if result < 0:
+            raise LZ4Exception("Error decoding offset %d of input buffer" % (srcOff - result))
+        return result
+
+    def decompressWithDict(self, dictionary, src, srcOff, srcLen, dest, destOff, maxDestLen=None):
+        """liblz4's LZ4_decompress_safe_usingDict against an LZ4Dictionary (not contiguous with dest): decodes the block in
+        src[srcOff:srcOff+srcLen], which was compressed against that dictionary, into dest[destOff:] and returns the decoded size
+        (lz4hip_decompress_safe_dict)"""
+        destOff = 0 if destOff is None else destOff
+        maxDestLen = len(dest) - destOff if maxDestLen is None else maxDestLen
+        dp, dk = _rw_ptr(dest)
+        _check_range(src, srcOff, srcLen)
+        _check_range(dest, destOff, maxDestLen)
+        sp, sk = _ro_ptr(src)
+        result = _single(lib().lz4hip_decompress_safe_dict(sp + srcOff, srcLen, dp + destOff, maxDestLen, dictionary._handle()))
         if result < 0:
             raise LZ4Exception("Error decoding offset %d of input buffer" % (srcOff - result))
         return result
@@ -735,6 +796,12 @@ class LZ4HIPBatch:
         return cls._call("lz4hip_decompress_fast_batch", src, srcOff, srcCap, dst, dstOff, dstLen)
 
     @classmethod
+    def decompressSafeDict(cls, src, srcOff, srcLen, dst, dstOff, dstCap, dictionary):
+        """LZ4_decompress_safe_usingDict per block against one LZ4Dictionary -> liblz4's return values
+        (lz4hip_decompress_safe_dict_batch)"""
+        return cls._call("lz4hip_decompress_safe_dict_batch", src, srcOff, srcLen, dst, dstOff, dstCap, dictionary._handle())
+
+    @classmethod
     def decompressSafePartial(cls, src, srcOff, srcLen, dst, dstOff, targetLen, dstCap):
         """LZ4_decompress_safe_partial per block: the first min(targetLen[i], dstCap[i]) bytes of block i into the slot
         dst[dstOff[i]:+dstCap[i]] -> liblz4's return values (lz4hip_decompress_safe_partial_batch; lists, or an int32 array for numpy
@@ -937,6 +1004,17 @@ class DeviceBatch:
     @classmethod
     def decompress_fast(cls, src, src_off, src_cap, dst, dst_off, dst_len, out):
         cls._call("lz4hip_decompress_fast_batch_dev", src, src_off, src_cap, dst, dst_off, dst_len, out)
+
+    @classmethod
+    def decompress_safe_dict(cls, src, src_off, src_len, dst, dst_off, dst_cap, out, dictionary):
+        """LZ4_decompress_safe_usingDict per block (lz4hip_decompress_safe_dict_batch_dev): `dictionary` is a uint8 tensor on the
+        blocks' device holding the whole dictionary (or its last 64 KB or more); out = liblz4's return values.  The tensor must stay
+        alive until the work on the stream is done"""
+        dev, st = cls._stream_dev(src)
+        _chk(lib().lz4hip_decompress_safe_dict_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
+                                                         dst_off.data_ptr(), dst_cap.data_ptr(), out.data_ptr(), src_off.numel(),
+                                                         dictionary.data_ptr() if dictionary.numel() else None, dictionary.numel(),
+                                                         dev, st))
 
     @classmethod
     def decompress_safe_partial(cls, src, src_off, src_len, dst, dst_off, target_len, dst_cap, out):

@@ -75,9 +75,11 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // them is negative (partial_room), and the kernels get that array as the target too
 // OP_COMPRESS_HC_DEST: LZ4_compress_HC_destSize: OP_COMPRESS_HC's level and workspace, OP_COMPRESS_DEST's target and consumed sizes
 // OP_DECODED_SIZE: the value LZ4_decompress_safe would return for (src, src_len, dst_cap), and no output buffer at all
+// OP_DECODE_DICT: LZ4_decompress_safe_usingDict against one dictionary per call: a handle (BlockCall::dict, resident on the device the
+// launch runs on) or the caller's device memory (BlockCall::dict_dev / dict_len)
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
-          OP_DECODED_SIZE };
-constexpr int OP_COUNT = OP_DECODED_SIZE + 1;   // (the last enumerator)
+          OP_DECODED_SIZE, OP_DECODE_DICT };
+constexpr int OP_COUNT = OP_DECODE_DICT + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
 constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
@@ -98,7 +100,13 @@ struct BlockCall {
   int32_t* consumed = nullptr;      // op_has_consumed: the input consumed per block
   void* hc_ws = nullptr;            // op_uses_hc_ws: device workspace for hc_span bytes of source; nullptr: launch_block learns the
   uint64_t hc_span = 0;             // span and allocates one (hc_workspace)
+  const lz4hip_dict* dict = nullptr;    // OP_DECODE_DICT: the dictionary handle (host path, single calls) ...
+  const uint8_t* dict_dev = nullptr;    // ... or, without a handle, the caller's dictionary in device memory and
+  int32_t dict_len = 0;                 // its length
 };
+// the handle's bytes on the CURRENT device (uploaded on first use where lz4hip_dict_create found the device not yet initialised):
+// one past the last byte, and the true length; a status (message set) on failure
+int dict_resident(const lz4hip_dict* d, const uint8_t** dict_end, int32_t* dict_len);
 // tuning knobs (lz4hip_set_option): atomics, so that a caller changing one while other threads launch is a race on the VALUE chosen,
 // never undefined behaviour; every launch reads each knob once
 std::atomic<int> g_decode_lanes{0};   // "decode_lanes"; 0 = kernel default
@@ -229,6 +237,12 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
     case OP_DECODE_FAST: return launch_decode(a, false, st);
     case OP_DECODE_PARTIAL: return lz4hip::launch_decompress_partial(a, c.target ? c.target : a.dst_cap, st);
     case OP_DECODED_SIZE: return lz4hip::launch_decoded_size(a, st);
+    case OP_DECODE_DICT: {
+      const uint8_t* dict_end = c.dict_len > 0 ? c.dict_dev + c.dict_len : nullptr;
+      int32_t dict_len = c.dict_len;
+      if (c.dict) { const int rc = dict_resident(c.dict, &dict_end, &dict_len); if (rc) return rc; }
+      return lz4hip::launch_decompress_dict(a, dict_end, dict_len, st);
+    }
     case OP_COMPRESS_HC:
     case OP_COMPRESS_HC_DEST: {
       void* ws = c.hc_ws;
@@ -763,8 +777,10 @@ Combiner g_hc_comb[13];   // [HC level]
 Combiner g_hc_dest_comb[13];   // [HC level]: LZ4_compress_HC_destSize, coalesced only with destSize calls of the same level
 std::mutex g_accel_comb_mu;
 std::map<int, Combiner> g_accel_comb;
+Combiner* dict_combiner(const lz4hip_dict* d);   // (the handle's own: single calls coalesce only with calls on the same handle)
 // nullptr: no combiner for this call (an operation or level outside the tables); may throw (the map's allocation)
 Combiner* combiner_for(const BlockCall& c) {
+  if (c.op == OP_DECODE_DICT) return c.dict ? dict_combiner(c.dict) : nullptr;
   if (c.op == OP_COMPRESS_ACCEL) {
     std::lock_guard<std::mutex> lk(g_accel_comb_mu);
     return &g_accel_comb[c.param];   // (std::map: references stay valid while other entries are added)
@@ -848,6 +864,43 @@ int single(const BlockCall& c, const uint8_t* src, int src_len, uint8_t* dst, in
   return r.out;
 }
 
+}  // namespace
+
+// ---- dictionary handles (LZ4_decompress_safe_usingDict) ------------------------------------------------------------------------------
+// The true length (liblz4's offset check needs it while it is below 64 KB) and the last 64 KB, which is all a decoder can reach; a
+// copy of those bytes on every initialised device, made by lz4hip_dict_create, or on a device's first use where the engine was
+// initialised (again) later.  The handle is immutable after creation: any number of threads may decode against it.
+struct lz4hip_dict {
+  int32_t len = 0;               // the dictionary's true length
+  std::vector<uint8_t> tail;     // its last min(len, 65536) bytes
+  std::mutex mu;                 // guards dev[]
+  uint8_t* dev[64] = {};         // [HIP ordinal]: the tail in device memory
+  Combiner comb;                 // single calls on this handle
+};
+namespace {
+Combiner* dict_combiner(const lz4hip_dict* d) { return &const_cast<lz4hip_dict*>(d)->comb; }
+int dict_upload(lz4hip_dict* d, int ord) {   // (d->mu held or the handle not yet published; the device is current)
+  if (d->dev[ord] || d->tail.empty()) return LZ4HIP_OK;
+  uint8_t* p = nullptr;
+  if (hipMalloc((void**)&p, d->tail.size()) != hipSuccess) return fail(LZ4HIP_E_NOMEM, "hipMalloc of the dictionary failed");
+  const hipError_t e = hipMemcpy(p, d->tail.data(), d->tail.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(p); return fail(LZ4HIP_E_HIP, "dictionary upload", e); }
+  d->dev[ord] = p;
+  return LZ4HIP_OK;
+}
+int dict_resident(const lz4hip_dict* cd, const uint8_t** dict_end, int32_t* dict_len) {
+  lz4hip_dict* d = const_cast<lz4hip_dict*>(cd);
+  int ord = -1;
+  if (hipGetDevice(&ord) != hipSuccess || ord < 0 || ord >= 64) return fail(LZ4HIP_E_HIP, "hipGetDevice failed");
+  *dict_len = d->len;
+  *dict_end = nullptr;
+  if (d->tail.empty()) return LZ4HIP_OK;
+  std::lock_guard<std::mutex> lk(d->mu);
+  const int rc = dict_upload(d, ord);
+  if (rc) return rc;
+  *dict_end = d->dev[ord] + d->tail.size();
+  return LZ4HIP_OK;
+}
 }  // namespace
 
 // ---- device-side container assembly (container.hip launch_container_blocks) ------------------------------------------------------
@@ -1309,6 +1362,48 @@ int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src
   for (uint32_t i = 0; i < n; i++) room[i] = partial_room(target_len[i], dst_cap[i]);
   return host_batch({OP_DECODE_PARTIAL}, src, src_off, src_len, dst, dst_off, room.data(), out_len, n);
 }
+int lz4hip_dict_create(const uint8_t* dict, int dict_len, lz4hip_dict** out) {
+  if (!dict || !out || dict_len < 0) return fail(LZ4HIP_E_ARG, !dict || !out ? kNullArg : "negative dictionary length");
+  lz4hip_dict* d = new (std::nothrow) lz4hip_dict();
+  if (!d) return fail(LZ4HIP_E_NOMEM, "out of memory");
+  d->len = dict_len;
+  const size_t keep = std::min<size_t>((size_t)dict_len, 65536u);
+  try { d->tail.assign(dict + ((size_t)dict_len - keep), dict + dict_len); }
+  catch (...) { delete d; return fail(LZ4HIP_E_NOMEM, "out of memory"); }
+  // resident on every initialised device.  Creating a handle initialises nothing (lz4hip_init's device list stays the caller's to
+  // choose): where the engine is not up yet, or has no device, the handle only answers lz4hip_dict_size until a decode brings its
+  // device's copy (dict_resident) -- or fails with LZ4HIP_E_NO_DEVICE like every other compute entry point
+  std::vector<int> devs;
+  { std::lock_guard<std::mutex> lk(g_mu); if (g_inited) devs = g_devs; }
+  for (int ord : devs) {
+    if (ord < 0 || ord >= 64) continue;
+    DeviceGuard g(ord);
+    const int rc = g.ok ? dict_upload(d, ord) : fail(LZ4HIP_E_HIP, "hipSetDevice failed");
+    if (rc) { lz4hip_dict_free(d); return rc; }
+  }
+  *out = d;
+  return LZ4HIP_OK;
+}
+int lz4hip_dict_size(const lz4hip_dict* dict) { return dict ? dict->len : fail(LZ4HIP_E_ARG, kNullArg); }
+void lz4hip_dict_free(lz4hip_dict* dict) {
+  if (!dict) return;
+  for (int ord = 0; ord < 64; ord++) {
+    if (!dict->dev[ord]) continue;
+    DeviceGuard g(ord);
+    if (g.ok) (void)hipFree(dict->dev[ord]);
+  }
+  delete dict;
+}
+int lz4hip_decompress_safe_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                      const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, const lz4hip_dict* dict) {
+  int rc = ensure_init();
+  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (n == 0) return LZ4HIP_OK;
+  if (!dict) return fail(LZ4HIP_E_ARG, kNullArg);
+  BlockCall c{OP_DECODE_DICT};
+  c.dict = dict;
+  return host_batch(c, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
+}
 int lz4hip_decompressed_size_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, const int32_t* dst_cap,
                                    int32_t* out_len, uint32_t n) {
   return host_batch({OP_DECODED_SIZE}, src, src_off, src_len, nullptr, nullptr, dst_cap, out_len, n);
@@ -1363,6 +1458,15 @@ int lz4hip_decompress_safe_partial_batch_dev(const uint8_t* src, const uint64_t*
                                              uint32_t n, int device, void* stream) {
   return dev_batch({OP_DECODE_PARTIAL, 0, target_len}, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream,
                    target_len ? nullptr : kNullArg);
+}
+int lz4hip_decompress_safe_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                          const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n,
+                                          const uint8_t* dict_dev, int dict_len, int device, void* stream) {
+  BlockCall c{OP_DECODE_DICT};
+  c.dict_dev = dict_dev;
+  c.dict_len = dict_len;
+  return dev_batch(c, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream,
+                   dict_len < 0 ? "negative dictionary length" : (dict_len > 0 && !dict_dev) ? kNullArg : nullptr);
 }
 int lz4hip_decompressed_size_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, const int32_t* dst_cap,
                                        int32_t* out_len, uint32_t n, int device, void* stream) {
@@ -1461,6 +1565,14 @@ int lz4hip_compress_hc_dest_size(const uint8_t* src, int* src_size, uint8_t* dst
 int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap) { return single({OP_DECODE_SAFE}, src, src_len, dst, dst_cap); }
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len) { return single({OP_DECODE_FAST}, src, src_cap, dst, dst_len); }
 int lz4hip_decompressed_size(const uint8_t* src, int src_len, int dst_cap) { return single({OP_DECODED_SIZE}, src, src_len, nullptr, dst_cap); }
+int lz4hip_decompress_safe_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, const lz4hip_dict* dict) {
+  int rc = ensure_init();
+  if (rc) return LZ4HIP_LIB_ERROR(fail(rc, "no HIP device: liblz4hip has no CPU fallback"));
+  if (!dict) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, kNullArg));
+  BlockCall c{OP_DECODE_DICT};
+  c.dict = dict;
+  return single(c, src, src_len, dst, dst_cap);
+}
 int lz4hip_decompress_safe_partial(const uint8_t* src, int src_len, uint8_t* dst, int target_size, int dst_cap) {
   return single({OP_DECODE_PARTIAL}, src, src_len, dst, partial_room(target_size, dst_cap));
 }

@@ -6,6 +6,9 @@
 //   decode_partial_kernel<GL, PIPE, STAGE>, decode_partial_deep_kernel<GL>
 //                        : LZ4_decompress_safe_partial: decode_kernel's and decode_deep_kernel's safe forms with the core's PARTIAL
 //                          switch and a per-block target next to BatchArgs.
+//   decode_dict_kernel<GL, PIPE, STAGE>, decode_dict_deep_kernel<GL>
+//                        : LZ4_decompress_safe_usingDict (external dictionary): the same two safe forms with the core's DICT switch;
+//                          the dictionary's end pointer and length travel next to BatchArgs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
@@ -76,6 +79,32 @@ __global__ __launch_bounds__(256, LZ4HIP_DEEP_WGS) void decode_partial_deep_kern
   if (g.l == 0) a.out[gid] = r;
 }
 
+// LZ4_decompress_safe_usingDict: twins of decode_kernel<GL, true, PIPE, STAGE> and decode_deep_kernel<GL, true> (same launch bounds, same
+// LDS) with lz4_decode_core.h's DICT switch; every block of the launch decodes against the one dictionary [dict_end - dict_len, dict_end),
+// of which only the last 64 KB are ever read; a negative size gives -1
+template <int GL, int PIPE, bool STAGE>
+__global__ __launch_bounds__(256) void decode_dict_kernel(BatchArgs a, const uint8_t* dict_end, int32_t dict_len) {
+  constexpr uint32_t kPer = PIPE == 2 ? GroupDev<GL>::kStreamLds : GroupDev<GL>::kStage;
+  __shared__ __attribute__((aligned(16))) uint8_t stage_mem[((STAGE || PIPE == 2) ? (256 / GL) * kPer : 16) + LZ4HIP_LDS_PAD];
+  const uint32_t gid = (blockIdx.x * 256u + threadIdx.x) / GL;
+  if (gid >= a.n) return;  // a whole group leaves together
+  GroupDev<GL> g;
+  uint8_t* stage = (STAGE || PIPE == 2) ? stage_mem + (threadIdx.x / GL) * kPer : nullptr;
+  const int r = decode_block<GroupDev<GL>, true, PIPE, STAGE, false, true>(g, a.src + a.src_off[gid], a.src_len[gid], a.dst + a.dst_off[gid],
+                                                                         a.dst_cap[gid], stage, dict_end, dict_len);
+  if (g.l == 0) a.out[gid] = r;
+}
+template <int GL>
+__global__ __launch_bounds__(256, LZ4HIP_DEEP_WGS) void decode_dict_deep_kernel(BatchArgs a, const uint8_t* dict_end, int32_t dict_len) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage_mem[(256 / GL) * GroupDev<GL>::kStreamLds + LZ4HIP_LDS_PAD];
+  const uint32_t gid = (blockIdx.x * 256u + threadIdx.x) / GL;
+  if (gid >= a.n) return;
+  GroupDev<GL> g;
+  const int r = decode_block<GroupDev<GL>, true, 2, false, false, true>(g, a.src + a.src_off[gid], a.src_len[gid], a.dst + a.dst_off[gid], a.dst_cap[gid],
+                                                                        stage_mem + (threadIdx.x / GL) * GroupDev<GL>::kStreamLds, dict_end, dict_len);
+  if (g.l == 0) a.out[gid] = r;
+}
+
 template <int GL>
 static int launch_decode_gl(const BatchArgs& a, bool safe, int pipe, bool stage, hipStream_t st, const uint32_t* route, uint32_t want) {
   const uint32_t per_wg = 256u / GL;
@@ -116,6 +145,17 @@ int launch_decompress_partial(const BatchArgs& a, const int32_t* target, void* s
   hipStream_t st = (hipStream_t)stream;
   if (a.n >= 40960u) hipLaunchKernelGGL((decode_partial_kernel<4, 0, true>), dim3((a.n + 63u) / 64u), dim3(256), 0, st, a, target);
   else hipLaunchKernelGGL((decode_partial_deep_kernel<8>), dim3((a.n + 31u) / 32u), dim3(256), 0, st, a, target);
+  return (int)hipGetLastError();
+}
+
+// LZ4_decompress_safe_usingDict: the same two lane-group decoders by batch size as the partial decoder's.  dict_end = one past the
+// dictionary's last byte in device memory (not looked at when dict_len == 0); no route, no decode_* knob.
+int launch_decompress_dict(const BatchArgs& a, const uint8_t* dict_end, int32_t dict_len, void* stream) {
+  if (a.n == 0) return 0;
+  if (dict_len < 0 || (dict_len > 0 && !dict_end)) return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  if (a.n >= 40960u) hipLaunchKernelGGL((decode_dict_kernel<4, 0, true>), dim3((a.n + 63u) / 64u), dim3(256), 0, st, a, dict_end, dict_len);
+  else hipLaunchKernelGGL((decode_dict_deep_kernel<8>), dim3((a.n + 31u) / 32u), dim3(256), 0, st, a, dict_end, dict_len);
   return (int)hipGetLastError();
 }
 

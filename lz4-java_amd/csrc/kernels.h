@@ -80,6 +80,11 @@ int launch_decompress(const BatchArgs& a, bool safe, int lanes_per_block, int pi
 // negative); out[i] = liblz4's return value.  >= 40960 blocks: decode_partial_kernel<4, 0, true> (staged), fewer:
 // decode_partial_deep_kernel<8>; the decode knobs and the device-side route do not apply
 int launch_decompress_partial(const BatchArgs& a, const int32_t* target, void* stream);
+// LZ4_decompress_safe_usingDict (a dictionary that is not contiguous with the destination): every block decodes against the one
+// dictionary [dict_end - dict_len, dict_end) in device memory, of which only the last 64 KB are read (dict_len == 0: the plain safe
+// decoder, dict_end is not looked at); out[i] = liblz4's return value.  >= 40960 blocks: decode_dict_kernel<4, 0, true> (staged),
+// fewer: decode_dict_deep_kernel<8>; the decode knobs and the device-side route do not apply
+int launch_decompress_dict(const BatchArgs& a, const uint8_t* dict_end, int32_t dict_len, void* stream);
 // The decoded-size query: out[i] = the value LZ4_decompress_safe would return for block i with capacity a.dst_cap[i] (-1 where it or
 // src_len[i] is negative); a.dst and a.dst_off are ignored (may be nullptr) and no output buffer exists.  decode_size_kernel<4, 2048, true>:
 // a wavefront per block; no route word, no sampler, no decode knob

@@ -36,6 +36,30 @@
 #ifndef LZ4HIP_DECODE_REENTER
 #define LZ4HIP_DECODE_REENTER 1   // 0: the interior loop is entered once per block (round 1 behaviour; developer A/B builds)
 #endif
+#ifndef LZ4HIP_DICT_INTERIOR
+#define LZ4HIP_DICT_INTERIOR 1    // 0: the interior loops leave every match that starts in the dictionary to the exact path (developer A/B builds: tools/dict_decode_sweep.py)
+#endif
+#ifndef LZ4HIP_DECODE_INTERIOR
+#define LZ4HIP_DECODE_INTERIOR 1  // 0: the plain interior loop is never entered -- the exact tiers alone (the CPU simulator's builds)
+#endif
+namespace lz4hip {
+// The two copies of decode_block's dictionary mode (DICT, below), in front of the interior loops that use them.
+template <class Grp>
+LZ4HIP_DEV int dict_match_copy(Grp& g, uint8_t* dst, int op, int back, int length, const uint8_t* dict_end) {   // back = offset - op > 0; returns op + length
+  const int c = length < back ? length : back;
+  g.copy_lits(dst + op, dict_end - back, (uint32_t)c, false);
+  op += c;
+  if (length > c) { g.copy_match(dst, (uint32_t)op, (uint32_t)op, (uint32_t)(length - c), false); op += length - c; }   // (the rest: dst[op + i] = dst[i])
+  return op;
+}
+// a match wholly inside the dictionary, in an interior loop (>= 300 bytes of room in dst): whole steps while the step's over-read stays
+// inside the dictionary, byte-exact at its end
+template <class Grp>
+LZ4HIP_DEV void dict_copy_interior(Grp& g, uint8_t* d, const uint8_t* dict_end, int back, int ml) {
+  if (back - ml >= (int)g.slack()) g.copy_lits_wide(d, dict_end - back, (uint32_t)ml);
+  else g.copy_lits(d, dict_end - back, (uint32_t)ml, false);
+}
+}  // namespace lz4hip
 #include "lz4_decode_deep.h"
 #include "lz4_decode_ring.h"
 #include "lz4_decode_wave.h"
@@ -79,9 +103,19 @@ template <class G> struct exact_length_sum<G, decltype((void)G::kExactLengthSum)
 //        longer than what remains is cut, not an error.  Only the end-of-block code differs: every interior loop and tier 1 stay
 //        >= 32 bytes away from oend.  A match of offset 0 (no compressor emits one) that is cut zero-fills like every other offset-0
 //        match here; liblz4 copies those bytes onto themselves, so its output there is whatever its buffer held.
-template <class Grp, bool SAFE, int PIPE = 0, bool STAGE = false, bool PARTIAL = false>
-LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* dst, int out_size, uint8_t* stage = nullptr) {
+// DICT (SAFE only, not PARTIAL): LZ4_decompress_safe_usingDict(src, dst, src_size, out_size, dict_end - dict_len, dict_len) for a dictionary
+//        that is NOT contiguous with dst (liblz4 1.9.3's usingExtDict).  An offset may reach offset - op bytes before the block: it is
+//        valid iff offset <= op + dict_len, and never rejected once dict_len >= 65536 (liblz4's checkOffset), tested where the plain
+//        decoder tests offset > op.  Such a match takes min(length, offset - op) bytes from the dictionary's end and the rest from the
+//        block's own start, byte-forward (dict_match_copy); it must end at or before oend - 5 and meets no other end-of-block rule.
+//        Only [dict_end - min(dict_len, 65535), dict_end) is ever read, and never wildly.  The interior loops (plain, staged, pipelined,
+//        deep) take the matches that lie wholly in the dictionary as copies from a foreign pointer, like literals; a match that
+//        straddles the block's start goes to the exact code.  dict_len == 0 is the plain decoder.
+template <class Grp, bool SAFE, int PIPE = 0, bool STAGE = false, bool PARTIAL = false, bool DICT = false>
+LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* dst, int out_size, uint8_t* stage = nullptr,
+                            const uint8_t* dict_end = nullptr, int dict_len = 0) {
   static_assert(!PARTIAL || SAFE, "partial decoding is a safe-decoder mode");
+  static_assert(!DICT || (SAFE && !PARTIAL && PIPE <= 2), "the dictionary decoder is a safe-decoder mode of the plain, staged, pipelined and deep loops");
   // EXACT (a backend that sets kExactLengthSum: the decoded-size query, whose value is liblz4's on EVERY input): a length's extension bytes are summed
   // in 32 bits, as liblz4 sums them, to the run's end -- the error position of a run that cannot fit is then liblz4's.  The decoders stop such a run at
   // LZ4HIP_LEN_CAP instead: also an error, reported where the cap was passed.  WRAP: the 32-bit sum, PARTIAL's too
@@ -95,6 +129,10 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
 
 #define LZ4HIP_LEN_CAP 0x7F000000  /* a run this long can never fit; stops 32-bit wrap on absurd input */
 #define LZ4HIP_NEED_IN(k) do { if (!SAFE && ip + (int)(k) > iend) goto output_error; } while (0)
+  /* the offset check at output position p; DICT: liblz4's checkOffset (dict_len < 64 KB) against the dictionary's start */
+#define LZ4HIP_OFF_BAD(p) (DICT ? (dict_len < 65536 && offset > (p) + dict_len) : offset > (p))
+  /* DICT, interior loops: the match (off, ml) at output position p starts before the block and lies wholly inside the dictionary */
+#define LZ4HIP_IN_DICT(off, p, ml) (DICT && LZ4HIP_DICT_INTERIOR && (off) > (p) && (ml) <= (off) - (p) && (off) - (p) <= dict_len)
   if (out_size < 0 || src_size < 0) return -1;
   if (PARTIAL && out_size == 0) return 0;
   if (SAFE && out_size == 0) return (src_size == 1 && g.ld8(src) == 0) ? 0 : -1;
@@ -112,7 +150,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
     // steady state costs two dependent loads per sequence: {offset word + literals} and {match source}.
     if constexpr (PIPE == 2) {
       if (ip + 2048 <= iend && ip <= iend - 306 && op <= oend - 606)
-        if (decode_deep_loop(g, src, iend, dst, oend, ip, op, stage)) goto interior;
+        if (decode_deep_loop<Grp, DICT>(g, src, iend, dst, oend, ip, op, stage, dict_end, (uint32_t)dict_len)) goto interior;
     }
     if constexpr (PIPE == 3) {   // the ring loop (lz4_decode_ring.h): stream and recent output in LDS at `stage` (Grp::kRingLds bytes)
       // It wants 64 output bytes in front of it (its flusher stores whole aligned steps).  They are decoded HERE, by the plain
@@ -206,7 +244,10 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
           nxt = (uint32_t)(o8 >> 24);
         }
         ml += 4;
-        if (off > op + lit) { have_o8 = false; return false; }  // invalid offset: the exact path produces liblz4's error code
+        if (off > op + lit) {  // invalid offset: the exact path produces liblz4's error code
+          if constexpr (DICT) { if (!LZ4HIP_IN_DICT(off, op + lit, ml)) { have_o8 = false; return false; } }   // (a match wholly inside the dictionary stays here)
+          else { have_o8 = false; return false; }
+        }
         const uint8_t* lit_src = src + ip + hdr;
         {
           // the next sequence's header is in nxt: if it can run in this loop, request its offset word now (the address the
@@ -225,6 +266,27 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
         // simple: one step each, and the match source [op+lit-off, +ml+slack) ends before this sequence's own output;
         // dep: the source reaches into the bytes the pending sequence has yet to store
         const uint32_t ulit = (uint32_t)lit, uml = (uint32_t)ml, uoff = (uint32_t)off, sl = g.slack();
+        if constexpr (DICT) {
+          if (off > op + lit) {   // wholly inside the dictionary: a source that waits for no store; simple while the step's over-read stays inside it
+            const int back = off - op - lit;
+            const bool dsimple = ulit <= g.step() && uml <= g.step() && (uint32_t)back >= uml + sl;
+            if (have_p && !dsimple) { g.seq_store(pnd, dst + p_op, p_lit, p_ml); have_p = false; }
+            if (dsimple) {
+              g.seq_load(cur, lit_src, ulit, dict_end - back, uml);
+              if (have_p) g.seq_store(pnd, dst + p_op, p_lit, p_ml);
+              have_p = true; p_in0 = cur_is0; p_op = (uint32_t)op; p_lit = ulit; p_ml = uml;
+              op += lit;
+            } else {
+              g.copy_lits_wide(dst + op, lit_src, ulit);
+              op += lit;
+              dict_copy_interior(g, dst + op, dict_end, back, ml);
+            }
+            op += ml;
+            ip += adv;
+            t4 = nxt;
+            return ip <= iend - 306 && op <= oend - 606;
+          }
+        }
         const bool simple = ulit <= g.step() && uml <= g.step() && uoff >= ulit + uml + sl;
         const bool dep = have_p && uoff < ulit + uml + sl + p_lit + p_ml;
         if (have_p && (!simple || dep)) { g.seq_store(pnd, dst + p_op, p_lit, p_ml); have_p = false; }
@@ -277,9 +339,19 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
           nxt = (uint32_t)(o8 >> 24);
         }
         ml += 4;
-        if (off > op + lit) break;
+        if (off > op + lit && !LZ4HIP_IN_DICT(off, op + lit, ml)) break;
         op += lit;
-        if ((uint32_t)(op - off) + (uint32_t)ml + g.slack() > g.fl) {
+        if (DICT && off > op) {   // wholly inside the dictionary: staged like literals; at the dictionary's end byte-exact, straight to memory
+          if (off - op - ml >= (int)g.slack()) {
+            g.st_lits(dst, (uint32_t)op, dict_end - (off - op), (uint32_t)ml);
+            op += ml;
+          } else {
+            g.st_flush_all(dst, (uint32_t)op);
+            g.copy_lits(dst + op, dict_end - (off - op), (uint32_t)ml, false);
+            op += ml;
+            g.fl = (uint32_t)op;
+          }
+        } else if ((uint32_t)(op - off) + (uint32_t)ml + g.slack() > g.fl) {
           g.st_flush_all(dst, (uint32_t)op);
           g.copy_match_wide(dst, (uint32_t)op, (uint32_t)off, (uint32_t)ml);
           op += ml;
@@ -297,7 +369,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
       } while (ip <= iend - 306 && op <= oend - 606);
       g.st_flush_all(dst, (uint32_t)op);  // the exact code below reads and writes memory
     }
-    if (!STAGE && !PIPE && ip <= iend - 306 && op <= oend - 606) {
+    if (!STAGE && !PIPE && LZ4HIP_DECODE_INTERIOR && ip <= iend - 306 && op <= oend - 606) {
       uint32_t t4 = g.ld32(src + ip);  // {token, first literal-length byte, ...} of the sequence at ip
       do {
         int lit = (int)((t4 >> 4) & 15u);
@@ -322,9 +394,10 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
           nxt = (uint32_t)(o8 >> 24);
         }
         ml += 4;
-        if (off > op + lit) break;  // invalid offset: let the exact path produce liblz4's error code
+        if (off > op + lit && !LZ4HIP_IN_DICT(off, op + lit, ml)) break;  // invalid offset: let the exact path produce liblz4's error code
         op += lit;
-        g.copy_match_wide(dst, (uint32_t)op, (uint32_t)off, (uint32_t)ml);
+        if (DICT && off > op) dict_copy_interior(g, dst + op, dict_end, off - op, ml);   // wholly inside the dictionary
+        else g.copy_match_wide(dst, (uint32_t)op, (uint32_t)off, (uint32_t)ml);
         op += ml;
         ip += adv;
         t4 = nxt;
@@ -383,7 +456,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
       ip += 2;
       length = (int)(token & 15u);
       if (length == 15) {
-        if (SAFE && offset > op) goto output_error;
+        if (SAFE && LZ4HIP_OFF_BAD(op)) goto output_error;
         uint32_t s = (w4 >> 16) & 255u;
         if (ip + 2 > iend) { LZ4HIP_NEED_IN(1); s = g.ld8(src + ip); }  // (SAFE: error follows below anyway)
         if (WRAP) length = 0;
@@ -405,11 +478,15 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
         length += 4;
         if (op + length >= oend - 64) goto safe_match_copy;
       }
-      if (offset > op) goto output_error;  // liblz4 checks this only when SAFE; the HIP engine never reads before dst
+      if (LZ4HIP_OFF_BAD(op)) goto output_error;  // liblz4 checks this only when SAFE; the HIP engine never reads before dst
       // next token word (SAFE: ip < iend holds after a non-final sequence)
       if (ip + 4 <= iend) { w4 = g.ld32(src + ip); } else { LZ4HIP_NEED_IN(1); w4 = g.ld8(src + ip); }
-      g.copy_match(dst, (uint32_t)op, (uint32_t)offset, (uint32_t)length, true);
-      op += length;
+      if (DICT && offset > op) {   // the match starts in the dictionary (op + length < oend - 64 here)
+        op = dict_match_copy(g, dst, op, offset - op, length, dict_end);
+      } else {
+        g.copy_match(dst, (uint32_t)op, (uint32_t)offset, (uint32_t)length, true);
+        op += length;
+      }
       // The interior loop left on a sequence it does not handle (a length run of two or more bytes, ...); that sequence has now
       // been decoded with every check: back to the interior loop while the block is still far from both ends.  (Round 1 entered
       // it once per block: data with an occasional long match or literal run fell off the fast path for the rest of the block.)
@@ -493,11 +570,16 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
       }
       if (PARTIAL) length = partial_run(15u, (uint32_t)length, oend - op - 4);
       else if (EXACT) { const int64_t n = (int64_t)15 + (int64_t)(uint32_t)length; if (n > (int64_t)(oend - op)) goto output_error; length = (int)n; }   // (an offset past op fails below, at this ip too)
-      else if (offset <= op && (uint32_t)length > (uint32_t)(oend - op)) goto output_error;
+      else if ((DICT || offset <= op) && (uint32_t)length > (uint32_t)(oend - op)) goto output_error;   // (DICT: an offset past the dictionary fails below, at this ip too)
     }
     length += 4;
   safe_match_copy:
-    if (offset > op) goto output_error;
+    if (LZ4HIP_OFF_BAD(op)) goto output_error;
+    if (DICT && offset > op) {   // the match starts in the dictionary: its only end-of-block rule is liblz4's last five literals
+      if (length > oend - 5 - op) goto output_error;
+      op = dict_match_copy(g, dst, op, offset - op, length, dict_end);
+      continue;
+    }
     cpy = op + length;
     if (PARTIAL && cpy > oend - 12) {   // liblz4's MATCH_SAFEGUARD_DISTANCE: copy what fits (byte-forward: overlapping matches included)
       const int mlen = length < oend - op ? length : oend - op;
@@ -513,6 +595,8 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
   return SAFE ? op : ip;
 output_error:
   return -ip - 1;
+#undef LZ4HIP_IN_DICT
+#undef LZ4HIP_OFF_BAD
 #undef LZ4HIP_NEED_IN
 #undef LZ4HIP_LEN_CAP
 }

@@ -24,8 +24,13 @@
 
 namespace lz4hip {
 
-template <class Grp>
-LZ4HIP_DEV bool decode_deep_loop(Grp& g, const uint8_t* src, const int iend, uint8_t* dst, const int oend, int& ip_io, int& op_io, uint8_t* stage) {
+// DICT (decode_block's dictionary mode): a match that lies wholly inside the dictionary ([dict_end - dict_len, dict_end)) is a sequence of
+// this loop too -- its source is a foreign pointer that depends on no slot -- as long as a whole step's read stays inside the dictionary;
+// the few that start within a step (64 bytes) of the dictionary's end are copied the wide way, byte-exact where they have to be.  A match that straddles the
+// block's start, or an offset past the dictionary, leaves the loop like an invalid offset.
+template <class Grp, bool DICT = false>
+LZ4HIP_DEV bool decode_deep_loop(Grp& g, const uint8_t* src, const int iend, uint8_t* dst, const int oend, int& ip_io, int& op_io, uint8_t* stage,
+                                 const uint8_t* dict_end = nullptr, const uint32_t dict_len = 0) {
   constexpr uint32_t KS = Grp::kStream, PC = Grp::kPiece, STEP = 64u;
   typedef typename Grp::LChunk LChunk;   // a group's 64-byte step (per lane: LB bytes)
   uint32_t ip = (uint32_t)ip_io, op = (uint32_t)op_io;
@@ -89,37 +94,74 @@ LZ4HIP_DEV bool decode_deep_loop(Grp& g, const uint8_t* src, const int iend, uin
     const uint32_t nxt = (uint32_t)(o8 >> (m15 ? 24 : 16));                                                                    \
     const uint32_t adv = hdr + lit + (m15 ? 3u : 2u);                                                                          \
     const uint32_t mpos = op + lit - off;            /* where the match copies from */                                         \
+    if constexpr (DICT) {                                                                                                      \
+      const uint32_t back = off - op - lit;          /* ... or, past the block's start, this far before the dictionary's end */\
+      if (LZ4HIP_DICT_INTERIOR && ((off > op + lit) & (ml <= back) & (back <= dict_len))) {   /* wholly inside the dictionary */\
+        LZ4HIP_TRIP_DICT(c, a, RETIRE_REST, AIM_REST, REFILL)                                                                  \
+      } else {                                                                                                                 \
+        LZ4HIP_TRIP_BODY(c, a, RETIRE_REST, AIM_REST, REFILL)                                                                  \
+      }                                                                                                                        \
+    } else {                                                                                                                   \
+      LZ4HIP_TRIP_BODY(c, a, RETIRE_REST, AIM_REST, REFILL)                                                                    \
+    }                                                                                                                          \
+  }
+  // the trip from the sequence's parsed header on
+#define LZ4HIP_TRIP_BODY(c, a, RETIRE_REST, AIM_REST, REFILL)                                                                  \
     if ((l15 & (e1 == 255u)) | (m15 & (e2 == 255u)) | (off > op + lit)) {   /* not for this loop (nothing of it done) */       \
       LZ4HIP_RETIRE(a); RETIRE_REST; break; }                                                                                  \
-    if (LZ4HIP_UNLIKELY((lit > STEP) | (ml > STEP) | (mpos + ml > sop##a))) {                                                   \
-      /* the slots first: the source reaches into bytes that wait in one, or this sequence is copied the wide way */          \
+    if (LZ4HIP_UNLIKELY((lit > STEP) | (ml > STEP) | (mpos + ml > sop##a))) {                                                  \
+      /* the slots first: the source reaches into bytes that wait in one, or this sequence is copied the wide way */           \
       LZ4HIP_RETIRE(a); RETIRE_REST;                                                                                           \
       const bool simple = (lit <= STEP) & (ml <= STEP) & (mpos + ml <= op);                                                    \
       uint32_t aim = op;                                                                                                       \
       if (!simple) {                                                                                                           \
         g.copy_lits_wide(dst + op, src + ip + hdr, lit);                                                                       \
         g.copy_match_wide(dst, op + lit, off, ml);                                                                             \
-        aim = op + lit + ml;                         /* (empty slots aim behind what has just been written) */                \
+        aim = op + lit + ml;                         /* (empty slots aim behind what has just been written) */                 \
       }                                                                                                                        \
       LZ4HIP_AIM(a); AIM_REST;                                                                                                 \
       if (!simple) {                                                                                                           \
         LZ4HIP_AIM(c); op = aim; ip += adv; t4 = nxt;                                                                          \
-        if (fetched != avail) { g.sr_put(rf_pos, rf); avail = rf_pos + PC; }   /* (a piece on its way lands before the rotation restarts) */ \
+        if (fetched != avail) { g.sr_put(rf_pos, rf); avail = rf_pos + PC; }   /* (a piece on its way lands before the rotation restarts) */\
         if (!((ip <= ilim) & (op <= olim) & (ip + 288u <= avail))) break;                                                      \
         continue;                                                                                                              \
       }                                                                                                                        \
     }                                                                                                                          \
-    if (REFILL == 1) {   /* the next piece of the stream, when the ring has room for it and the stream has it */              \
+    if (REFILL == 1) {   /* the next piece of the stream, when the ring has room for it and the stream has it */               \
       LZ4HIP_REFILL_FETCH                                                                                                      \
     }                                                                                                                          \
     v##c = g.sr_step(ip + hdr);                                                                                                \
-    u##c = g.step_load_upto(dst + mpos, ml, dst + mpos - g.lane_bytes());   /* (lanes beyond the match re-read its first bytes: no line of their own) */ \
+    u##c = g.step_load_upto(dst + mpos, ml, dst + mpos - g.lane_bytes());   /* (lanes beyond the match re-read its first bytes: no line of their own) */\
     sop##c = op; lit##c = lit;                                                                                                 \
     LZ4HIP_RETIRE(a);                                                                                                          \
     if (REFILL == 2) { LZ4HIP_REFILL_PUT }                                                                                     \
     op += lit + ml; ip += adv; t4 = nxt;                                                                                       \
-    if (!((ip <= ilim) & (op <= olim) & (ip + 288u <= avail))) { RETIRE_REST; LZ4HIP_RETIRE(c); break; }                       \
-  }
+    if (!((ip <= ilim) & (op <= olim) & (ip + 288u <= avail))) { RETIRE_REST; LZ4HIP_RETIRE(c); break; }
+  // the same for a match wholly inside the dictionary (DICT): its source waits for no slot; within a step of the dictionary's end it is
+  // copied the wide way, byte-exact where a step's read would pass the end
+#define LZ4HIP_TRIP_DICT(c, a, RETIRE_REST, AIM_REST, REFILL)                                                                  \
+    if ((l15 & (e1 == 255u)) | (m15 & (e2 == 255u))) { LZ4HIP_RETIRE(a); RETIRE_REST; break; }                                 \
+    if (LZ4HIP_UNLIKELY((lit > STEP) | (ml > STEP) | (back < STEP))) {                                                         \
+      LZ4HIP_RETIRE(a); RETIRE_REST;                                                                                           \
+      g.copy_lits_wide(dst + op, src + ip + hdr, lit);                                                                         \
+      dict_copy_interior(g, dst + op + lit, dict_end, (int)back, (int)ml);                                                     \
+      const uint32_t aim = op + lit + ml;                                                                                      \
+      LZ4HIP_AIM(a); AIM_REST; LZ4HIP_AIM(c);                                                                                  \
+      op = aim; ip += adv; t4 = nxt;                                                                                           \
+      if (fetched != avail) { g.sr_put(rf_pos, rf); avail = rf_pos + PC; }                                                     \
+      if (!((ip <= ilim) & (op <= olim) & (ip + 288u <= avail))) break;                                                        \
+      continue;                                                                                                                \
+    }                                                                                                                          \
+    if (REFILL == 1) {   /* the next piece of the stream, when the ring has room for it and the stream has it */               \
+      LZ4HIP_REFILL_FETCH                                                                                                      \
+    }                                                                                                                          \
+    v##c = g.sr_step(ip + hdr);                                                                                                \
+    u##c = g.step_load_upto((dict_end - back), ml, (dict_end - back) - g.lane_bytes());   /* (lanes beyond the match re-read its first bytes: no line of their own) */\
+    sop##c = op; lit##c = lit;                                                                                                 \
+    LZ4HIP_RETIRE(a);                                                                                                          \
+    if (REFILL == 2) { LZ4HIP_REFILL_PUT }                                                                                     \
+    op += lit + ml; ip += adv; t4 = nxt;                                                                                       \
+    if (!((ip <= ilim) & (op <= olim) & (ip + 288u <= avail))) { RETIRE_REST; LZ4HIP_RETIRE(c); break; }
   for (;;) {
 #if LZ4HIP_DEEP_SLOTS == 6
     LZ4HIP_TRIP(0, 1, 2, 3, 4, 5, 1)
@@ -147,6 +189,8 @@ LZ4HIP_DEV bool decode_deep_loop(Grp& g, const uint8_t* src, const int iend, uin
 #undef LZ4HIP_REFILL_PUT
 #undef LZ4HIP_TRIP
 #undef LZ4HIP_TRIP_
+#undef LZ4HIP_TRIP_BODY
+#undef LZ4HIP_TRIP_DICT
 #undef LZ4HIP_REST
 #undef LZ4HIP_AIM
 #undef LZ4HIP_RETIRE

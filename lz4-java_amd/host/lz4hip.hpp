@@ -6,6 +6,9 @@
 //   LZ4Compressor::compress / maxCompressedLength   <- LZ4Compressor.java:36,59 ; LZ4JNICompressor.java:35-43
 //   LZ4SafeDecompressor::decompress                 <- LZ4SafeDecompressor.java:45 ; LZ4JNISafeDecompressor.java:34-43
 //   LZ4SafeDecompressor::decompressPartial          =  LZ4_decompress_safe_partial of liblz4's main API (no reference entry reaches it)
+//   LZ4Dictionary, LZ4SafeDecompressor::decompressWithDict, LZ4HIPBatch::decompressSafeDict
+//                                                   =  LZ4_decompress_safe_usingDict of liblz4's main API against a dictionary that is not
+//                                                      contiguous with the destination (no reference entry reaches it)
 //   LZ4SafeDecompressor::decompressedLength, LZ4HIPBatch::decompressedLengths / decompressSafeSized
 //                                                   =  the decoded size without a destination; the batch twin of the allocating
 //                                                      overloads LZ4SafeDecompressor.java:117-137 without their worst-case buffer
@@ -120,6 +123,25 @@ class LZ4HCHIPCompressor final : public LZ4Compressor {
   }
 };
 
+// A shared dictionary for LZ4_decompress_safe_usingDict (lz4hip_dict_create): the handle keeps the true length and the last 64 KB,
+// resident on every initialised device.  Immutable: any number of threads may decode against it; it must outlive the calls that use it.
+class LZ4Dictionary {
+  lz4hip_dict* h_ = nullptr;
+ public:
+  LZ4Dictionary(const uint8_t* data, int length) {
+    const int rc = lz4hip_dict_create(data, length, &h_);
+    if (rc == LZ4HIP_E_ARG) throw std::invalid_argument(std::string("LZ4Dictionary: ") + lz4hip_last_error());
+    if (rc != 0) throw LZ4Exception(std::string("liblz4hip status ") + std::to_string(rc) + ": " + lz4hip_last_error());
+  }
+  explicit LZ4Dictionary(const bytes& data) : LZ4Dictionary(data.empty() ? reinterpret_cast<const uint8_t*>("") : data.data(), (int)data.size()) {}
+  LZ4Dictionary(const LZ4Dictionary&) = delete;
+  LZ4Dictionary& operator=(const LZ4Dictionary&) = delete;
+  LZ4Dictionary(LZ4Dictionary&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  ~LZ4Dictionary() { lz4hip_dict_free(h_); }
+  int size() const { return lz4hip_dict_size(h_); }
+  const lz4hip_dict* handle() const { return h_; }
+};
+
 class LZ4SafeDecompressor {
  public:
   int decompress(const bytes& src, int srcOff, int srcLen, bytes& dest, int destOff, int maxDestLen) const {
@@ -134,6 +156,15 @@ class LZ4SafeDecompressor {
     bytes out((size_t)maxDestLen);
     out.resize((size_t)decompress(src, 0, (int)src.size(), out, 0, maxDestLen));
     return out;
+  }
+  // liblz4's LZ4_decompress_safe_usingDict: decodes a block that was compressed against `dict` (which is not contiguous with dest)
+  // into dest + destOff and returns the decoded size (lz4hip_decompress_safe_dict)
+  int decompressWithDict(const LZ4Dictionary& dict, const bytes& src, int srcOff, int srcLen, bytes& dest, int destOff, int maxDestLen) const {
+    util::checkRange(src, srcOff, srcLen);
+    util::checkRange(dest, destOff, maxDestLen);
+    const int result = libCheck(lz4hip_decompress_safe_dict(src.data() + srcOff, srcLen, dest.data() + destOff, maxDestLen, dict.handle()));
+    if (result < 0) throw LZ4Exception("Error decoding offset " + std::to_string(srcOff - result) + " of input buffer");
+    return result;
   }
   // liblz4's LZ4_decompress_safe_partial: decodes the first min(targetLen, maxDestLen) bytes of the block (fewer where a cut stream
   // ends first) into dest + destOff and returns the count; nothing is written past destOff + min(targetLen, maxDestLen)
@@ -170,6 +201,20 @@ struct LZ4HIPBatch {
     }
   }
   static void status(int rc) { if (rc != 0) throw LZ4Exception(std::string("liblz4hip status ") + std::to_string(rc) + ": " + lz4hip_last_error()); }
+  // LZ4_decompress_safe_usingDict per block against one dictionary: block i decodes into dest[destOff[i], + maxDestLen[i]); returns
+  // liblz4's values (lz4hip_decompress_safe_dict_batch)
+  static std::vector<int32_t> decompressSafeDict(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen, bytes& dest,
+                                                 const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen, const LZ4Dictionary& dict) {
+    checkBlocks(src, srcOff, srcLen, maxDestLen);
+    if (destOff.size() != srcOff.size()) throw std::invalid_argument("per-block arrays differ in length");
+    for (size_t i = 0; i < destOff.size(); i++)
+      if (destOff[i] > dest.size() || (uint64_t)maxDestLen[i] > dest.size() - destOff[i]) throw std::out_of_range("slot " + std::to_string(i));
+    std::vector<int32_t> out(srcOff.size(), 0);
+    bytes one(1);                                 // (an empty destination still hands the library a pointer)
+    status(lz4hip_decompress_safe_dict_batch(src.data(), srcOff.data(), srcLen.data(), dest.empty() ? one.data() : dest.data(), destOff.data(),
+                                             maxDestLen.data(), out.data(), (uint32_t)srcOff.size(), dict.handle()));
+    return out;
+  }
   static std::vector<int32_t> decompressedLengths(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen,
                                                   const std::vector<int32_t>& maxDestLen) {
     checkBlocks(src, srcOff, srcLen, maxDestLen);

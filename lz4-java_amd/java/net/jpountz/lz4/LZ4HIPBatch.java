@@ -89,6 +89,20 @@ public final class LZ4HIPBatch {
   }
 
   /**
+   * liblz4's {@code LZ4_decompress_safe_usingDict} per block against one shared dictionary (not contiguous with {@code dest}): block i,
+   * compressed alone against {@code dict}, decodes into the slot {@code dest[destOff[i], destOff[i]+destCap[i])}.
+   * outLen[i] &gt;= 0: the decoded size; &lt; 0: -(input position)-1.
+   */
+  public static void decompressSafeDict(LZ4HIPDictionary dict, ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff,
+      int[] destCap, int[] outLen) {
+    check(src, dest, srcOff, srcLen, destOff, destCap, outLen);
+    final int rc = LZ4HIPJNI.LZ4HIP_batchSafeDict(dict.handle(), src, srcOff, srcLen, dest, destOff, destCap, outLen, srcOff.length);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /**
    * liblz4's {@code LZ4_decompress_safe_partial} per block: the first {@code min(targetLen[i], destCap[i])} bytes of block i (fewer
    * where a cut stream ends first) into the slot {@code dest[destOff[i], destOff[i]+destCap[i])}, nothing past
    * {@code destOff[i] + min(targetLen[i], destCap[i])}.  outLen[i] &gt;= 0: bytes decoded; &lt; 0: -(input position)-1.

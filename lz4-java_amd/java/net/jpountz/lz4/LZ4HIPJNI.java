@@ -89,6 +89,19 @@ enum LZ4HIPJNI {
    * destCap[i])); outLen = liblz4's return values.  Returns 0 or a negative lz4hip_status (a null argument: LZ4HIP_E_ARG). */
   static native int LZ4HIP_batchSafePartial(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetLen,
                                             int[] destCap, int[] outLen, int nBlocks);
+  /* LZ4_decompress_safe_usingDict against a dictionary that is not contiguous with the destination (LZ4HIPDictionary keeps the handle).
+   * dictCreate copies the bytes of the array or direct buffer and returns the handle, or 0 (lastError() says why); dictSize is the true
+   * length; dictFree takes 0 too. */
+  static native long LZ4HIP_dictCreate(byte[] dictArray, ByteBuffer dictBuffer, int off, int len);
+  static native int LZ4HIP_dictSize(long dict);
+  static native void LZ4HIP_dictFree(long dict);
+  /* the decoded size, a negative liblz4 code or a library failure as LZ4HIP_decompress_safe; same NULL / pinning rules */
+  static native int LZ4HIP_decompress_safe_dict(long dict, byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
+                                                byte[] destArray, ByteBuffer destBuffer, int destOff, int maxDestLen);
+  /* per block over DIRECT buffers against one dictionary: outLen = liblz4's return values.  Returns 0 or a negative lz4hip_status (a
+   * null argument or a 0 handle: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchSafeDict(long dict, ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff,
+                                         int[] destCap, int[] outLen, int nBlocks);
   /* LZ4_compress_HC_destSize per block at HC level `level`: the arguments and return conventions of LZ4HIP_batchDestSize */
   static native int LZ4HIP_batchHCDestSize(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetSize,
                                            int[] outLen, int[] srcConsumed, int nBlocks, int level);

@@ -64,6 +64,43 @@ final class LZ4HIPSafeDecompressor extends LZ4SafeDecompressor {
   }
 
   /**
+   * liblz4's {@code LZ4_decompress_safe_usingDict}: decodes a block that was compressed against {@code dict} (a dictionary that is not
+   * contiguous with {@code dest}) into {@code dest[destOff, ...)} and returns the decoded size.  The argument checks and the exception
+   * message are decompress()'s.
+   */
+  public final int decompressWithDict(LZ4HIPDictionary dict, byte[] src, int srcOff, int srcLen, byte[] dest, int destOff, int maxDestLen) {
+    SafeUtils.checkRange(src, srcOff, srcLen);
+    SafeUtils.checkRange(dest, destOff, maxDestLen);
+    final int result = LZ4HIPJNI.LZ4HIP_decompress_safe_dict(dict.handle(), src, null, srcOff, srcLen, dest, null, destOff, maxDestLen);
+    if (result < 0) {
+      throw new LZ4Exception(result <= Integer.MIN_VALUE + 63 ? "liblz4hip: " + LZ4HIPJNI.lastError()
+                                                               : "Error decoding offset " + (srcOff - result) + " of input buffer");
+    }
+    return result;
+  }
+
+  /** {@link #decompressWithDict(LZ4HIPDictionary, byte[], int, int, byte[], int, int)} over heap or direct buffers (positions untouched). */
+  public int decompressWithDict(LZ4HIPDictionary dict, ByteBuffer src, int srcOff, int srcLen, ByteBuffer dest, int destOff, int maxDestLen) {
+    ByteBufferUtils.checkNotReadOnly(dest);
+    ByteBufferUtils.checkRange(src, srcOff, srcLen);
+    ByteBufferUtils.checkRange(dest, destOff, maxDestLen);
+    if (!(src.hasArray() || src.isDirect()) || !(dest.hasArray() || dest.isDirect())) {
+      throw new IllegalArgumentException("decompressWithDict needs heap-backed or direct ByteBuffers");
+    }
+    final byte[] srcArr = src.hasArray() ? src.array() : null;
+    final byte[] destArr = dest.hasArray() ? dest.array() : null;
+    final int so = srcArr != null ? srcOff + src.arrayOffset() : srcOff;
+    final int dof = destArr != null ? destOff + dest.arrayOffset() : destOff;
+    final int result = LZ4HIPJNI.LZ4HIP_decompress_safe_dict(dict.handle(), srcArr, srcArr == null ? src : null, so, srcLen,
+                                                             destArr, destArr == null ? dest : null, dof, maxDestLen);
+    if (result < 0) {
+      throw new LZ4Exception(result <= Integer.MIN_VALUE + 63 ? "liblz4hip: " + LZ4HIPJNI.lastError()
+                                                               : "Error decoding offset " + (srcOff - result) + " of input buffer");
+    }
+    return result;
+  }
+
+  /**
    * liblz4's {@code LZ4_decompress_safe_partial}: decodes the first {@code min(targetLen, maxDestLen)} bytes of the block (fewer
    * where a cut stream ends first) into {@code dest[destOff, ...)} and returns the count; nothing is written past
    * {@code destOff + min(targetLen, maxDestLen)}.  The argument checks and the exception message are decompress()'s.

@@ -319,6 +319,62 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafePartial(J
   return rc;
 }
 
+/* ---- LZ4_decompress_safe_usingDict against a dictionary handle (lz4hip_dict_create): LZ4HIPDictionary.java keeps the handle as a long ---- */
+
+/* the dictionary bytes of a heap array or a direct buffer -> a handle, or 0 (lz4hip_last_error() says why: a NULL or negative argument
+ * is LZ4HIP_E_ARG); the bytes are copied, nothing stays pinned */
+JNIEXPORT jlong JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1dictCreate(JNIEnv* env, jclass cls, jbyteArray dictArray, jobject dictBuffer, jint off, jint len) {
+  (void)cls;
+  lz4hip_dict* h = NULL;
+  if ((dictArray == NULL && dictBuffer == NULL) || off < 0 || len < 0) { (void)lz4hip_dict_create(NULL, len, &h); return 0; }   /* (sets the message) */
+  region_t in;
+  if (region_in(env, dictArray, dictBuffer, off, len, 1, &in) != 0) { throw_OOM(env); return 0; }
+  const int rc = lz4hip_dict_create(in.p, len, &h);
+  region_out(env, NULL, 0, 0, &in);
+  return rc == 0 ? (jlong)(intptr_t)h : 0;
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1dictSize(JNIEnv* env, jclass cls, jlong dict) {
+  (void)env; (void)cls;
+  return lz4hip_dict_size((const lz4hip_dict*)(intptr_t)dict);
+}
+JNIEXPORT void JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1dictFree(JNIEnv* env, jclass cls, jlong dict) {
+  (void)env; (void)cls;
+  lz4hip_dict_free((lz4hip_dict*)(intptr_t)dict);
+}
+
+/* LZ4_decompress_safe_usingDict: the arguments, staging and return convention of LZ4HIP_decompress_safe behind the handle (0: a
+ * library error, LZ4HIP_E_ARG) */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1safe_1dict(JNIEnv* env, jclass cls, jlong dict, jbyteArray srcArray,
+    jobject srcBuffer, jint srcOff, jint srcLen, jbyteArray destArray, jobject destBuffer, jint destOff, jint maxDestLen) {
+  (void)cls;
+  region_t in, out;
+  if (region_in(env, srcArray, srcBuffer, srcOff, srcLen, 1, &in) != 0) { throw_OOM(env); return 0; }
+  if (region_in(env, destArray, destBuffer, destOff, maxDestLen, 0, &out) != 0) {
+    region_out(env, NULL, 0, 0, &in); /* release `in` too */
+    throw_OOM(env);
+    return 0;
+  }
+  const int result = lz4hip_decompress_safe_dict(in.p, srcLen, out.p, maxDestLen, (const lz4hip_dict*)(intptr_t)dict);
+  region_out(env, NULL, 0, 0, &in);
+  const jint produced = (!LZ4HIP_IS_LIB_ERROR(result) && result > 0) ? result : 0;
+  if (region_out(env, destArray, destOff, produced, &out) != 0) { throw_OOM(env); return 0; }
+  return result;
+}
+
+/* LZ4_decompress_safe_usingDict over many blocks against one handle, direct buffers (lz4hip_decompress_safe_dict_batch): outLen[i] =
+ * liblz4's return value.  Returns 0 or a negative lz4hip_status; a NULL array or buffer or a 0 handle is LZ4HIP_E_ARG */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafeDict(JNIEnv* env, jclass cls, jlong dict, jobject src, jlongArray srcOff,
+    jintArray srcLen, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen, jint n) {
+  (void)cls;
+  if (dict == 0) return LZ4HIP_E_ARG;
+  batch_args_t b = {NULL, NULL, 5, {{srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT}, {destCap, INTS, JNI_ABORT}, {outLen, INTS, 0}}};
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  rc = lz4hip_decompress_safe_dict_batch(b.src, b.a[0].p, b.a[1].p, b.dst, b.a[2].p, b.a[3].p, b.a[4].p, (uint32_t)n, (const lz4hip_dict*)(intptr_t)dict);
+  batch_release(env, &b);
+  return rc;
+}
+
 /* The decoded-size query over many blocks, a direct source buffer (lz4hip_decompressed_size_batch): outLen[i] = what
  * LZ4_decompress_safe would return for block i with capacity destCap[i].  There is no destination buffer (batch_pin gets the source in
  * its place: its address is not used).  Returns 0 or a negative lz4hip_status; a NULL array or buffer is LZ4HIP_E_ARG */

@@ -1,0 +1,63 @@
+"""Child process of tests/test_gpu_dict.py: initialises liblz4hip on a device LIST WITH REPEATS ([0] * D), so that the dictionary
+decoder's host batch takes the multi-device branch of csrc/api.cpp (contiguous block ranges per listed device, the handle resident on
+each) on a box with one GPU, and checks a batch of records -- valid, damaged and cut, with ragged capacities -- against the reference
+library's LZ4_decompress_safe_usingDict: return values, bytes and the untouched bytes behind every result.  A handle created BEFORE
+lz4hip_init is used too (its device copy is made on first use).  Prints 'dict multidev ok D=<D>'."""
+import ctypes as C
+import importlib
+import os
+import random
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np  # noqa: E402
+from oracle import oracle as O  # noqa: E402
+from dict_common import RefDict, book1  # noqa: E402
+from partial_common import damaged  # noqa: E402
+
+D = int(sys.argv[1])
+n = 64 * D * 3 + 11
+amd = importlib.import_module("lz4-java_amd")
+L = amd.lib()
+b = book1()
+rd = RefDict(O.ref())
+for dict_len, early in ((4096, False), (70000, True)):
+    d = b[:dict_len]
+    if early:
+        L.lz4hip_shutdown()
+        handle = amd.LZ4Dictionary(d)          # no device is initialised yet on this pass
+    ids = (C.c_int * D)(*([0] * D))
+    assert L.lz4hip_init(ids, D) == 0, L.lz4hip_last_error()
+    assert L.lz4hip_device_count() == D
+    if not early:
+        handle = amd.LZ4Dictionary(d)
+    assert len(handle) == dict_len
+    rng = random.Random(90 + D + dict_len)
+    srcs, caps = [], []
+    for i in range(n):
+        size = rng.choice([64, 300, 1000, 4096, 20000])
+        o = rng.randrange(200000, len(b) - size)
+        s = rd.compress(d, b[o:o + size], 9 if i % 3 == 0 else 0)
+        k = rng.random()
+        if k < 0.15:
+            s = s[:rng.randrange(len(s) + 1)]
+        elif k < 0.3:
+            s = damaged(s, rng, 2)
+        srcs.append(s)
+        caps.append(rng.choice([size, size + 100, max(size - 7, 0), size + 1]))
+    want = [rd.decode(s, c, d) for s, c in zip(srcs, caps)]
+    so = np.concatenate([[0], np.cumsum([len(s) for s in srcs])[:-1]]).astype(np.uint64)
+    do = np.concatenate([[0], np.cumsum([c + 8 for c in caps])[:-1]]).astype(np.uint64)
+    dst = bytearray(b"\xee" * (int(sum(caps)) + 8 * n))
+    out = amd.LZ4HIPBatch.decompressSafeDict(b"".join(srcs) + b"\0", so, np.array([len(s) for s in srcs], dtype=np.int32), dst, do,
+                                             np.array(caps, dtype=np.int32), handle)
+    for i in range(n):
+        r, by = want[i]
+        assert int(out[i]) == r, ("result", dict_len, i, len(srcs[i]), caps[i], int(out[i]), r)
+        o = int(do[i])
+        assert bytes(dst[o:o + max(r, 0)]) == by, ("bytes", dict_len, i)
+        assert dst[o + max(r, 0):o + caps[i] + 8] == b"\xee" * (caps[i] + 8 - max(r, 0)), ("written past the result", dict_len, i)
+    handle.close()
+print("dict multidev ok D=%d blocks=%d" % (D, n))
