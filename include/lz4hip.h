@@ -249,7 +249,10 @@ int lz4hip_decompressed_size_batch(const uint8_t* src, const uint64_t* src_off, 
  *     bytes outside the slot.
  * The behaviour is pinned by 600 vectors in tests/golden/fast_decode_contract.json (generated from oracle/lz4_oracle.c
  * lz4o_decompress_fast_bounded; its valid cases are cross-checked against the reference library) and tested on the CPU
- * (tests/test_oracle.py) and on the GPU (tests/test_gpu_scale.py).                                                        */
+ * (tests/test_oracle.py; tests/test_fast_contract_hostsim.py: one loop of every decoder family in the lane simulator) and on
+ * the GPU (tests/test_gpu_scale.py; tests/test_gpu_fast_contract.py: valid, damaged, cut and padded streams through the fast
+ * decoder of EVERY decode kernel and batch-size route, twice, with different bytes around every source and destination slot --
+ * the cases and the layout are tests/fast_contract_common.py's).                                                           */
 int lz4hip_decompress_fast_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_cap,
                                  uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_len,
                                  int32_t* out_consumed, uint32_t n_blocks);

@@ -2,7 +2,7 @@
 is ISA and has no CPU simulator -- its one real bug (tests/golden/regress/r03_binary_alphabet_*.bin) was found by tools/gpu_fuzz.py
 at volume, not by the suite.  These run the same scripts with fixed seeds that differ from every other test's: every compress core
 with full and tight capacities, every decoder variant, HC levels on subsets (gpu_fuzz.py); long valid and damaged streams through the
-deep / windowed decoder loops at 4 / 8 / 16 lanes (gpu_fuzz_deep.py); blocks of 65547 bytes and more -- the 64-bit-entry form of
+deep / windowed decoder loops at 4 / 8 / 16 lanes, safe decoder and fast decoder (gpu_fuzz_deep.py); blocks of 65547 bytes and more -- the 64-bit-entry form of
 the hand-scheduled loop, csrc/lz4_fast_v2_asm32.h -- with full and tight capacities (gpu_fuzz_u32.py).  Everything is compared with
 the reference library."""
 import os
@@ -34,6 +34,8 @@ def test_gpu_fuzz_deep_slice(pipe, ring):
     loop (its default ring for the batch and the smallest one)"""
     out = run("gpu_fuzz_deep.py", 400, 2026 + pipe, env={"FUZZ_PIPE": str(pipe), "FUZZ_RING": str(ring)})
     assert "deep fuzz ok" in out
+    safe, fast = out.count("return codes and bytes equal the reference's"), out.count("fast decoder: return codes and bytes equal the bounded oracle's")
+    assert safe >= 1 and fast == safe, out[-2000:]   # (a line of either decoder per lanes value)
 
 
 @pytest.mark.parametrize("seed", [90210, 1729])

@@ -10,6 +10,7 @@ import random
 import pytest
 
 from conftest import rnd_inputs, sha
+from fast_contract_common import DECODE_VARIANTS
 
 pytestmark = pytest.mark.gpu
 
@@ -139,14 +140,7 @@ def test_decode_fuzz_bit_exact(amd, ref, O, corpus):
             c, cap = bytearray(rng.randbytes(rng.randrange(1, 40))), rng.randrange(0, 200)
         streams.append(bytes(c)); caps.append(cap)
     # pipe: the pipelined interior loop; stage: output staging in LDS (plain loop only)
-    for lanes, pipe, stage, ring in ((0, -1, -1, 0), (4, 0, 0, 0), (4, 1, 0, 0), (8, 1, 0, 0), (16, 0, 0, 0), (64, 0, 0, 0), (64, 1, 0, 0), (4, 0, 1, 0), (8, 0, 1, 0),
-                                     (32, 0, 1, 0), (64, 0, 1, 0),
-                                     (4, 2, 0, 0), (8, 2, 0, 0), (16, 2, 0, 0),     # pipe 2: the deep interior loop (lz4_decode_deep.h)
-                                     (1, 3, 0, 256), (1, 3, 0, 512), (4, 3, 0, 512), (4, 3, 0, 1024), (4, 3, 0, 2048), (8, 3, 0, 512), (8, 3, 0, 4096), (16, 3, 0, 4096),   # pipe 3: the ring loop (lz4_decode_ring.h); (4, 3, 2048) is the routed default of 12288..40959 big blocks
-                                     (64, 4, 0, 0), (64, 4, 0, 8192), (64, 4, 0, 16384), (64, 4, 0, 32768), (64, 4, 0, 65536),   # pipe 4: the wave loop (lz4_decode_wave.h), a wavefront per block
-                                     (64, 5, 0, 0), (64, 5, 0, 8192), (64, 5, 0, 16384), (64, 5, 0, 32768), (64, 5, 0, 65536),   # pipe 5: its parallel form, several sequences of the block per trip
-                                     (64, 7, 0, 0), (64, 7, 0, 16384), (64, 7, 0, 32768), (64, 7, 0, 65536),   # pipe 7: the pair loop (lz4_decode_pair.h), a parser and a copier wavefront per block
-                                     (64, 8, 0, 0), (64, 8, 0, 8192), (64, 8, 0, 16384), (64, 8, 0, 32768), (64, 8, 0, 65536)):   # pipe 8: the trio loop (lz4_decode_trio.h): scanner, planner, copier
+    for lanes, pipe, stage, ring in DECODE_VARIANTS:   # every decoder kernel (fast_contract_common.py says which is which)
         amd.set_option("decode_lanes", lanes)
         amd.set_option("decode_pipe", pipe)
         amd.set_option("decode_stage", stage)
