@@ -164,8 +164,9 @@ int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src
 /* DECODE AGAINST A DICTIONARY: the return value and bytes of LZ4_decompress_safe_usingDict(src, dst, src_len, dst_cap, dict,
  * dict_len), liblz4 1.9.3, for a dictionary that is NOT contiguous with dst (liblz4's external-dictionary mode) -- records that
  * were each compressed alone against one shared dictionary (LZ4_loadDict + LZ4_compress_fast_continue, LZ4_loadDictHC +
- * LZ4_compress_HC_continue), every one of them readable on its own.  Decoding only: there is no dictionary compressor, no
- * dictionary form of the fast decoder, of the partial decoder or of the size query, and no prefix mode (linked blocks).
+ * LZ4_compress_HC_continue), every one of them readable on its own.  The fast writer of such records is
+ * lz4hip_compress_fast_dict* below; there is no HC dictionary compressor, no dictionary form of the fast decoder, of the partial
+ * decoder or of the size query, and no prefix mode (linked blocks).
  *   - out_len[i] is liblz4's return value on valid AND malformed streams: the decoded size, or -(input position) - 1;
  *   - offsets: with dict_len < 65536 an offset is valid iff offset <= output position + dict_len; with dict_len >= 65536 no
  *     offset is rejected and only the dictionary's last 64 KB can be reached (liblz4's rule, checked where the safe decoder
@@ -193,6 +194,29 @@ void lz4hip_dict_free(lz4hip_dict* dict);        /* NULL is fine; no call on the
 int lz4hip_decompress_safe_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                       uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                       int32_t* out_len, uint32_t n_blocks, const lz4hip_dict* dict);
+/* COMPRESS AGAINST A DICTIONARY: for every block i, on a fresh stream,
+ *     LZ4_loadDict(s, dict, dict_len);  LZ4_compress_fast_continue(s, src_i, dst_i, src_len[i], dst_cap[i], 1)
+ * of liblz4 1.9.3 with a dictionary that is NOT contiguous with the source (its external-dictionary mode): the return value and the
+ * bytes, byte for byte.  Blocks are independent, nothing carries over from one to the next; lz4hip_decompress_safe_dict* reads them.
+ *   - out_len[i] > 0 is the compressed size; 0: dst_cap[i] is too small (LZ4_compress_default's capacity rule), or src_len[i] < 0,
+ *     src_len[i] > 0x7E000000 or dst_cap[i] < 0;
+ *   - every block is parsed with liblz4's byU32 table whatever its size, so an empty dictionary does NOT give
+ *     lz4hip_compress_fast's bytes for blocks under 65547 bytes (from there on it does);
+ *   - only the dictionary's last 64 KB count, and a dictionary of fewer than 8 bytes is none (LZ4_loadDict returns 0);
+ *   - a match may start in the dictionary (its offset then exceeds its position in the block) and, where it runs to the dictionary's
+ *     end, goes on against the block's own start; the dictionary's last 7 positions are never match candidates;
+ *   - nothing outside the dictionary's kept bytes and block i's source is read, nothing outside block i's slot is written;
+ *   - the handle is the decoder's (lz4hip_dict_create).  The compressor also needs the table LZ4_loadDict leaves: 32 KB of device
+ *     memory per device, built by a kernel at the handle's first compress on that device (that one call waits for its stream once;
+ *     a handle that only decodes never has one) and freed by lz4hip_dict_free;
+ *   - one kernel, compress_fast_dict_cu_kernel: the one-sequence core with its DICT switch, five wavefronts per CU, each loading its
+ *     table from the image per block; acceleration is 1, there is no attach-dictionary, prefix or HC form and no LZ4_saveDict;
+ *   - dict == NULL is LZ4HIP_E_ARG, no device LZ4HIP_E_NO_DEVICE; the host batch shards over the initialised devices and brings
+ *     back only the bytes each block produced, as lz4hip_compress_fast_batch does;
+ *   - single calls (lz4hip_compress_fast_dict) are coalesced only with concurrent compress calls on the SAME handle.            */
+int lz4hip_compress_fast_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                    uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                    int32_t* out_len, uint32_t n_blocks, const lz4hip_dict* dict);
 int lz4hip_compress_hc_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                              uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                              int32_t* out_len, uint32_t n_blocks, int level);
@@ -288,6 +312,12 @@ int lz4hip_decompress_safe_dict_batch_dev(const uint8_t* src, const uint64_t* sr
                                           uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                           int32_t* out_len, uint32_t n_blocks, const uint8_t* dict_dev, int dict_len,
                                           int device, void* stream);
+/* compress against a dictionary (see lz4hip_compress_fast_dict_batch): device pointers on `device`, and the HANDLE -- the compressor
+ * needs its table image, not only the bytes; asynchronous, except that a handle's first compress on a device builds the image and
+ * waits for `stream` once.  dict == NULL is LZ4HIP_E_ARG */
+int lz4hip_compress_fast_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                        uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                        int32_t* out_len, uint32_t n_blocks, const lz4hip_dict* dict, int device, void* stream);
 /* HC: levels follow liblz4 (< 1 -> 9, > 12 -> 12): 1..9 = hash-chain strategy with lazy evaluation, 10..12 = optimal
  * parser (lz4-java levels 10..17).  Levels 10..12 are FUNCTIONAL ONLY: byte-identical output, but the optimal parser's table
  * walk is wave-uniform scalar work (about 1.0 / 0.7 GB/s per GPU at levels 10 / 12 -- no faster than the reference on the host's
@@ -350,6 +380,7 @@ int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int ds
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len);
 int lz4hip_decompress_safe_partial(const uint8_t* src, int src_len, uint8_t* dst, int target_size, int dst_cap);  /* LZ4_decompress_safe_partial */
 int lz4hip_decompressed_size(const uint8_t* src, int src_len, int dst_cap);  /* what LZ4_decompress_safe(src, dst, src_len, dst_cap) would return; no dst */
+int lz4hip_compress_fast_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, const lz4hip_dict* dict);  /* LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream; dict == NULL: LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
 int lz4hip_decompress_safe_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, const lz4hip_dict* dict);  /* LZ4_decompress_safe_usingDict; dict == NULL: LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
 int lz4hip_xxh32(const uint8_t* buf, int len, uint32_t seed, uint32_t* out);
 int lz4hip_xxh64(const uint8_t* buf, int len, uint64_t seed, uint64_t* out);

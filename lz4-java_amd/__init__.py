@@ -57,6 +57,7 @@ C_ABI = {
     "lz4hip_dict_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "lz4hip_dict_size": (C.c_int, [C.c_void_p]),
     "lz4hip_dict_free": (None, [C.c_void_p]),
+    "lz4hip_compress_fast_dict_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_void_p]),
     "lz4hip_decompress_safe_dict_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_void_p]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
@@ -64,6 +65,7 @@ C_ABI = {
     "lz4hip_compress_fast_accel_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_dest_size_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_decompress_safe_partial_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
+    "lz4hip_compress_fast_dict_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
     "lz4hip_decompress_safe_dict_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_dest_size_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
@@ -83,6 +85,7 @@ C_ABI = {
     "lz4hip_decompress_safe": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "lz4hip_decompress_safe_partial": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "lz4hip_compress_fast_dict": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "lz4hip_decompress_safe_dict": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "lz4hip_decompressed_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_xxh32": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, _u32p]),
@@ -262,6 +265,31 @@ class LZ4HIPCompressor(LZ4Compressor):
         written = _single(lib().lz4hip_compress_dest_size(sp + srcOff, C.byref(size), dp + destOff, targetDestSize))
         return written, size.value
 
+    def compressWithDict(self, dictionary, src, srcOff=None, srcLen=None, dest=None, destOff=None, maxDestLen=None):
+        """liblz4's LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream (the dictionary not contiguous with src): the block
+        src[srcOff:srcOff+srcLen] compressed alone against an LZ4Dictionary (lz4hip_compress_fast_dict); the forms of compress():
+        compressWithDict(d, src[, srcOff, srcLen]) -> bytes | compressWithDict(d, src, srcOff, srcLen, dest, destOff[, maxDestLen]) -> int.
+        LZ4SafeDecompressor.decompressWithDict reads it.  liblz4 has no accelerated form here: an accelerated compressor raises
+        NotImplementedError."""
+        if self.acceleration > 1:
+            raise NotImplementedError("compressWithDict: acceleration %d is not supported" % self.acceleration)
+        if dest is None:
+            srcOff = 0 if srcOff is None else srcOff
+            srcLen = len(src) - srcOff if srcLen is None else srcLen
+            out = bytearray(self.maxCompressedLength(srcLen))
+            n = self.compressWithDict(dictionary, src, srcOff, srcLen, out, 0, len(out))
+            return bytes(out[:n])
+        destOff = 0 if destOff is None else destOff
+        maxDestLen = len(dest) - destOff if maxDestLen is None else maxDestLen
+        dp, dk = _rw_ptr(dest)
+        _check_range(src, srcOff, srcLen)
+        _check_range(dest, destOff, maxDestLen)
+        sp, sk = _ro_ptr(src)
+        result = _single(lib().lz4hip_compress_fast_dict(sp + srcOff, srcLen, dp + destOff, maxDestLen, dictionary._handle()))
+        if result <= 0:
+            raise LZ4Exception("maxDestLen is too small")
+        return result
+
     def __str__(self):
         return "LZ4HIPCompressor" if self.acceleration == 1 else "LZ4HIPCompressor(acceleration=%d)" % self.acceleration
 
@@ -298,8 +326,9 @@ class LZ4HCHIPCompressor(LZ4Compressor):
 # decompressors
 # ----------------------------------------------------------------------------------------------
 class LZ4Dictionary:
-    """A shared dictionary for LZ4_decompress_safe_usingDict (lz4hip_dict_create): the handle keeps the true length and the last 64 KB,
-    resident on every initialised device.  Immutable; any number of threads may decode against it.  close() -- or leaving a `with`
+    """A shared dictionary for LZ4_decompress_safe_usingDict and for LZ4_loadDict + LZ4_compress_fast_continue (lz4hip_dict_create):
+    the handle keeps the true length and the last 64 KB, resident on every initialised device (and, from its first compress on a
+    device, the 32 KB table LZ4_loadDict leaves).  Immutable; any number of threads may compress and decode against it.  close() -- or leaving a `with`
     block -- frees it; no call that uses it may be in flight then."""
 
     def __init__(self, data):
@@ -796,6 +825,12 @@ class LZ4HIPBatch:
         return cls._call("lz4hip_decompress_fast_batch", src, srcOff, srcCap, dst, dstOff, dstLen)
 
     @classmethod
+    def compressDict(cls, src, srcOff, srcLen, dst, dstOff, dstCap, dictionary):
+        """LZ4_loadDict + LZ4_compress_fast_continue per block, a fresh stream each, against one LZ4Dictionary -> compressed sizes,
+        0 where dstCap[i] is too small (lz4hip_compress_fast_dict_batch)"""
+        return cls._call("lz4hip_compress_fast_dict_batch", src, srcOff, srcLen, dst, dstOff, dstCap, dictionary._handle())
+
+    @classmethod
     def decompressSafeDict(cls, src, srcOff, srcLen, dst, dstOff, dstCap, dictionary):
         """LZ4_decompress_safe_usingDict per block against one LZ4Dictionary -> liblz4's return values
         (lz4hip_decompress_safe_dict_batch)"""
@@ -1004,6 +1039,16 @@ class DeviceBatch:
     @classmethod
     def decompress_fast(cls, src, src_off, src_cap, dst, dst_off, dst_len, out):
         cls._call("lz4hip_decompress_fast_batch_dev", src, src_off, src_cap, dst, dst_off, dst_len, out)
+
+    @classmethod
+    def compress_dict(cls, src, src_off, src_len, dst, dst_off, dst_cap, out, dictionary):
+        """LZ4_loadDict + LZ4_compress_fast_continue per block, a fresh stream each (lz4hip_compress_fast_dict_batch_dev):
+        `dictionary` is an LZ4Dictionary -- the handle, since the compressor needs its table image; out = compressed sizes, 0 where
+        dst_cap[i] is too small.  Asynchronous, but a dictionary's first compress on a device waits for the stream once"""
+        dev, st = cls._stream_dev(src)
+        _chk(lib().lz4hip_compress_fast_dict_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
+                                                       dst_off.data_ptr(), dst_cap.data_ptr(), out.data_ptr(), src_off.numel(),
+                                                       dictionary._handle(), dev, st))
 
     @classmethod
     def decompress_safe_dict(cls, src, src_off, src_len, dst, dst_off, dst_cap, out, dictionary):

@@ -77,12 +77,14 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // OP_DECODED_SIZE: the value LZ4_decompress_safe would return for (src, src_len, dst_cap), and no output buffer at all
 // OP_DECODE_DICT: LZ4_decompress_safe_usingDict against one dictionary per call: a handle (BlockCall::dict, resident on the device the
 // launch runs on) or the caller's device memory (BlockCall::dict_dev / dict_len)
+// OP_COMPRESS_DICT: LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream per block, against a handle (BlockCall::dict) -- always
+// a handle: the compressor needs the dictionary's table image (dict_compress_state), not only its bytes
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
-          OP_DECODED_SIZE, OP_DECODE_DICT };
-constexpr int OP_COUNT = OP_DECODE_DICT + 1;   // (the last enumerator)
+          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT };
+constexpr int OP_COUNT = OP_COMPRESS_DICT + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
-constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
+constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT; }
 // a second per-block result (BlockCall::consumed) travels behind out[]
 constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
 // out[i] counts SOURCE bytes read: a block that succeeded filled its whole dst_cap[i]
@@ -100,13 +102,17 @@ struct BlockCall {
   int32_t* consumed = nullptr;      // op_has_consumed: the input consumed per block
   void* hc_ws = nullptr;            // op_uses_hc_ws: device workspace for hc_span bytes of source; nullptr: launch_block learns the
   uint64_t hc_span = 0;             // span and allocates one (hc_workspace)
-  const lz4hip_dict* dict = nullptr;    // OP_DECODE_DICT: the dictionary handle (host path, single calls) ...
+  const lz4hip_dict* dict = nullptr;    // OP_COMPRESS_DICT: the dictionary handle; OP_DECODE_DICT: the handle (host path, single calls) ...
   const uint8_t* dict_dev = nullptr;    // ... or, without a handle, the caller's dictionary in device memory and
   int32_t dict_len = 0;                 // its length
 };
 // the handle's bytes on the CURRENT device (uploaded on first use where lz4hip_dict_create found the device not yet initialised):
 // one past the last byte, and the true length; a status (message set) on failure
 int dict_resident(const lz4hip_dict* d, const uint8_t** dict_end, int32_t* dict_len);
+// what the dictionary compressor needs of the handle on the CURRENT device: the end of the kept tail, its length as LZ4_loadDict keeps
+// it (lz4hip::dict_keep: 0 = no dictionary) and the table image, built at the handle's first compress on the device (that one call
+// waits for `st` once, so that calls on other streams find the image complete)
+int dict_compress_state(const lz4hip_dict* d, hipStream_t st, const uint8_t** dict_end, int32_t* keep, const void** image);
 // tuning knobs (lz4hip_set_option): atomics, so that a caller changing one while other threads launch is a race on the VALUE chosen,
 // never undefined behaviour; every launch reads each knob once
 std::atomic<int> g_decode_lanes{0};   // "decode_lanes"; 0 = kernel default
@@ -253,12 +259,22 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
       if (!c.hc_ws) (void)hipFreeAsync(ws, st);
       return e;
     }
-    case OP_COMPRESS_ACCEL:   // the one-sequence kernels (compress_fast_accel_cu_kernel, compress_fast_dest_cu_kernel) draw blocks
-    case OP_COMPRESS_DEST: {  // from one queue word of scratch
+    case OP_COMPRESS_DICT:
+    case OP_COMPRESS_ACCEL:   // the one-sequence kernels (compress_fast_accel_cu_kernel, compress_fast_dest_cu_kernel,
+    case OP_COMPRESS_DEST: {  // compress_fast_dict_cu_kernel) draw blocks from one queue word of scratch
+      const uint8_t* dict_end = nullptr;
+      int32_t keep = 0;
+      const void* image = nullptr;
+      if (c.op == OP_COMPRESS_DICT) {
+        if (!c.dict) return fail(LZ4HIP_E_ARG, kNullArg);
+        const int rc = dict_compress_state(c.dict, st, &dict_end, &keep, &image);
+        if (rc) return rc;
+      }
       uint32_t* q = nullptr;
       const hipError_t me = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
       if (me != hipSuccess) return (int)me;
-      const int e = c.op == OP_COMPRESS_ACCEL ? lz4hip::launch_compress_fast_accel(a, (uint32_t)c.param, q, lz4hip::device_cus(), st)
+      const int e = c.op == OP_COMPRESS_DICT  ? lz4hip::launch_compress_fast_dict(a, dict_end, keep, image, q, lz4hip::device_cus(), st)
+                  : c.op == OP_COMPRESS_ACCEL ? lz4hip::launch_compress_fast_accel(a, (uint32_t)c.param, q, lz4hip::device_cus(), st)
                                               : lz4hip::launch_compress_dest_size(a, c.consumed, q, lz4hip::device_cus(), st);
       (void)hipFreeAsync(q, st);
       return e;
@@ -777,10 +793,10 @@ Combiner g_hc_comb[13];   // [HC level]
 Combiner g_hc_dest_comb[13];   // [HC level]: LZ4_compress_HC_destSize, coalesced only with destSize calls of the same level
 std::mutex g_accel_comb_mu;
 std::map<int, Combiner> g_accel_comb;
-Combiner* dict_combiner(const lz4hip_dict* d);   // (the handle's own: single calls coalesce only with calls on the same handle)
+Combiner* dict_combiner(const lz4hip_dict* d, bool compress);   // (the handle's own: single calls coalesce only with calls of the same operation on the same handle)
 // nullptr: no combiner for this call (an operation or level outside the tables); may throw (the map's allocation)
 Combiner* combiner_for(const BlockCall& c) {
-  if (c.op == OP_DECODE_DICT) return c.dict ? dict_combiner(c.dict) : nullptr;
+  if (c.op == OP_DECODE_DICT || c.op == OP_COMPRESS_DICT) return c.dict ? dict_combiner(c.dict, c.op == OP_COMPRESS_DICT) : nullptr;
   if (c.op == OP_COMPRESS_ACCEL) {
     std::lock_guard<std::mutex> lk(g_accel_comb_mu);
     return &g_accel_comb[c.param];   // (std::map: references stay valid while other entries are added)
@@ -866,19 +882,26 @@ int single(const BlockCall& c, const uint8_t* src, int src_len, uint8_t* dst, in
 
 }  // namespace
 
-// ---- dictionary handles (LZ4_decompress_safe_usingDict) ------------------------------------------------------------------------------
+// ---- dictionary handles (LZ4_decompress_safe_usingDict, LZ4_loadDict + LZ4_compress_fast_continue) ------------------------------------------------------------------------------
 // The true length (liblz4's offset check needs it while it is below 64 KB) and the last 64 KB, which is all a decoder can reach; a
 // copy of those bytes on every initialised device, made by lz4hip_dict_create, or on a device's first use where the engine was
 // initialised (again) later.  The handle is immutable after creation: any number of threads may decode against it.
+// A compressor also needs the table LZ4_loadDict leaves (32 KB, lz4hip::launch_dict_image): built per device at the handle's first
+// compress there, never for a handle that only decodes, and freed with the handle.
 struct lz4hip_dict {
   int32_t len = 0;               // the dictionary's true length
   std::vector<uint8_t> tail;     // its last min(len, 65536) bytes
   std::mutex mu;                 // guards dev[]
   uint8_t* dev[64] = {};         // [HIP ordinal]: the tail in device memory
-  Combiner comb;                 // single calls on this handle
+  void* image[64] = {};          // [HIP ordinal]: the compressor's table image (only where dict_keep(len) > 0, from the first compress on)
+  Combiner comb;                 // single decode calls on this handle
+  Combiner comb_c;               // single compress calls on this handle
 };
 namespace {
-Combiner* dict_combiner(const lz4hip_dict* d) { return &const_cast<lz4hip_dict*>(d)->comb; }
+Combiner* dict_combiner(const lz4hip_dict* d, bool compress) {
+  lz4hip_dict* m = const_cast<lz4hip_dict*>(d);
+  return compress ? &m->comb_c : &m->comb;
+}
 int dict_upload(lz4hip_dict* d, int ord) {   // (d->mu held or the handle not yet published; the device is current)
   if (d->dev[ord] || d->tail.empty()) return LZ4HIP_OK;
   uint8_t* p = nullptr;
@@ -899,6 +922,29 @@ int dict_resident(const lz4hip_dict* cd, const uint8_t** dict_end, int32_t* dict
   const int rc = dict_upload(d, ord);
   if (rc) return rc;
   *dict_end = d->dev[ord] + d->tail.size();
+  return LZ4HIP_OK;
+}
+int dict_compress_state(const lz4hip_dict* cd, hipStream_t st, const uint8_t** dict_end, int32_t* keep, const void** image) {
+  lz4hip_dict* d = const_cast<lz4hip_dict*>(cd);
+  int ord = -1;
+  if (hipGetDevice(&ord) != hipSuccess || ord < 0 || ord >= 64) return fail(LZ4HIP_E_HIP, "hipGetDevice failed");
+  *keep = (int32_t)lz4hip::dict_keep(d->len);
+  *dict_end = nullptr;
+  *image = nullptr;
+  if (*keep == 0) return LZ4HIP_OK;   // (under 8 bytes: LZ4_loadDict loads nothing)
+  std::lock_guard<std::mutex> lk(d->mu);
+  const int rc = dict_upload(d, ord);
+  if (rc) return rc;
+  if (!d->image[ord]) {
+    void* p = nullptr;
+    if (hipMalloc(&p, lz4hip::kDictImageBytes) != hipSuccess) return fail(LZ4HIP_E_NOMEM, "hipMalloc of the dictionary's table image failed");
+    const int le = lz4hip::launch_dict_image(d->dev[ord] + (d->tail.size() - (size_t)*keep), *keep, p, st);
+    const hipError_t e = le ? (hipError_t)le : hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipFree(p); return fail(LZ4HIP_E_HIP, "dictionary table image", e); }
+    d->image[ord] = p;
+  }
+  *dict_end = d->dev[ord] + d->tail.size();
+  *image = d->image[ord];
   return LZ4HIP_OK;
 }
 }  // namespace
@@ -1388,9 +1434,10 @@ int lz4hip_dict_size(const lz4hip_dict* dict) { return dict ? dict->len : fail(L
 void lz4hip_dict_free(lz4hip_dict* dict) {
   if (!dict) return;
   for (int ord = 0; ord < 64; ord++) {
-    if (!dict->dev[ord]) continue;
+    if (!dict->dev[ord] && !dict->image[ord]) continue;
     DeviceGuard g(ord);
-    if (g.ok) (void)hipFree(dict->dev[ord]);
+    if (g.ok && dict->dev[ord]) (void)hipFree(dict->dev[ord]);
+    if (g.ok && dict->image[ord]) (void)hipFree(dict->image[ord]);
   }
   delete dict;
 }
@@ -1401,6 +1448,16 @@ int lz4hip_decompress_safe_dict_batch(const uint8_t* src, const uint64_t* src_of
   if (n == 0) return LZ4HIP_OK;
   if (!dict) return fail(LZ4HIP_E_ARG, kNullArg);
   BlockCall c{OP_DECODE_DICT};
+  c.dict = dict;
+  return host_batch(c, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
+}
+int lz4hip_compress_fast_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                    const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, const lz4hip_dict* dict) {
+  int rc = ensure_init();
+  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (n == 0) return LZ4HIP_OK;
+  if (!dict) return fail(LZ4HIP_E_ARG, kNullArg);
+  BlockCall c{OP_COMPRESS_DICT};
   c.dict = dict;
   return host_batch(c, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
 }
@@ -1467,6 +1524,13 @@ int lz4hip_decompress_safe_dict_batch_dev(const uint8_t* src, const uint64_t* sr
   c.dict_len = dict_len;
   return dev_batch(c, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream,
                    dict_len < 0 ? "negative dictionary length" : (dict_len > 0 && !dict_dev) ? kNullArg : nullptr);
+}
+int lz4hip_compress_fast_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                        const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n,
+                                        const lz4hip_dict* dict, int device, void* stream) {
+  BlockCall c{OP_COMPRESS_DICT};
+  c.dict = dict;
+  return dev_batch(c, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream, dict ? nullptr : kNullArg);
 }
 int lz4hip_decompressed_size_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, const int32_t* dst_cap,
                                        int32_t* out_len, uint32_t n, int device, void* stream) {
@@ -1570,6 +1634,14 @@ int lz4hip_decompress_safe_dict(const uint8_t* src, int src_len, uint8_t* dst, i
   if (rc) return LZ4HIP_LIB_ERROR(fail(rc, "no HIP device: liblz4hip has no CPU fallback"));
   if (!dict) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, kNullArg));
   BlockCall c{OP_DECODE_DICT};
+  c.dict = dict;
+  return single(c, src, src_len, dst, dst_cap);
+}
+int lz4hip_compress_fast_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, const lz4hip_dict* dict) {
+  int rc = ensure_init();
+  if (rc) return LZ4HIP_LIB_ERROR(fail(rc, "no HIP device: liblz4hip has no CPU fallback"));
+  if (!dict) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, kNullArg));
+  BlockCall c{OP_COMPRESS_DICT};
   c.dict = dict;
   return single(c, src, src_len, dst, dst_cap);
 }

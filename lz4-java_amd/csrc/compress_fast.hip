@@ -11,6 +11,9 @@
 //   compress_fast_accel_cu_kernel
 //                        : LZ4_compress_fast with acceleration 2 .. 65537: the one-sequence-per-step core of lz4_fast_core.h with
 //                          its ACC switch, 5 wavefronts per CU drawing blocks from a queue (acceleration 1 is the kernels above).
+//   compress_fast_dict_cu_kernel
+//                        : LZ4_loadDict + LZ4_compress_fast_continue, a fresh stream per block: the same core and shape with the DICT
+//                          switch; every table starts as the dictionary's image (dict_image_kernel builds it once per handle).
 //   compress_fast_dest_cu_kernel
 //                        : LZ4_compress_destSize: the same core and shape with DirectOut's FILL switch; a block ends once its
 //                          target is full, so the work follows the input consumed.
@@ -376,6 +379,62 @@ int launch_compress_fast_accel(const BatchArgs& a, uint32_t accel, uint32_t* q, 
   if (e != hipSuccess) return (int)e;
   const uint32_t wgs = (a.n + WAVES_PER_CU - 1u) / WAVES_PER_CU;
   hipLaunchKernelGGL(compress_fast_accel_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a, q, accel);
+  return (int)hipGetLastError();
+}
+
+// LZ4_loadDict + LZ4_compress_fast_continue, a fresh stream per block: the one-sequence-per-step core with its DICT switch on
+// (lz4_fast_core.h) -- byU32 and 64-bit entries at every size, as liblz4's external-dictionary mode.  Same shape as the accelerated
+// kernel.  Per block the table is loaded from the dictionary's 32 KB image (dict_image_kernel, once per handle and device; L2-resident
+// while a batch runs) instead of being cleared; keep == 0 (no dictionary) clears it.
+__device__ __forceinline__ void compress_fast_dict_block(const BatchArgs& a, uint32_t b, uint64_t* table, const uint8_t* tail, uint32_t keep,
+                                                         const uint8_t* image) {
+  const int32_t n = uniform_i32(a.src_len[b]);
+  const int32_t cap = uniform_i32(a.dst_cap[b]);
+  uint32_t r = 0;
+  if (n >= 0 && (uint32_t)n <= 0x7E000000u && cap >= 0) {
+    const uint8_t* s = uniform_ptr(a.src + a.src_off[b]);
+    uint8_t* d = uniform_ptr(a.dst + a.dst_off[b]);
+    WaveDev w(table);
+    DirectOut<WaveDev> out(w, s, (uint32_t)n, d, (uint32_t)cap);
+    FastCore<WaveDev, false, DirectOut<WaveDev>, false, false, true> c(w, out, s, (uint32_t)n);
+    if (keep) { c.dict = tail; c.keep = keep; c.image = image; }
+    r = c.run();
+  }
+  if (__lane_id() == 0) a.out[b] = (int32_t)r;
+}
+__global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_dict_cu_kernel(BatchArgs a, const uint8_t* tail, uint32_t keep, const uint8_t* image,
+                                                                                  uint32_t* q) {
+  __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
+  uint64_t* table = tables[threadIdx.x >> 6];
+  for (;;) {
+    uint32_t b = 0;
+    if (__lane_id() == 0) b = atomicAdd(q, 1u);
+    b = __builtin_amdgcn_readfirstlane(b);
+    if (b >= a.n) return;
+    compress_fast_dict_block(a, b, table, tail, keep, image);
+    WaveDev::sync();  // the table is reused
+  }
+}
+int launch_compress_fast_dict(const BatchArgs& a, const uint8_t* dict_end, int32_t keep, const void* image, uint32_t* q, uint32_t n_cus,
+                              void* stream) {
+  if (a.n == 0) return 0;
+  if (keep != 0 && (keep < 8 || keep > 65536 || !dict_end || !image)) return (int)hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(q, 0, sizeof(uint32_t), (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  const uint32_t wgs = (a.n + WAVES_PER_CU - 1u) / WAVES_PER_CU;
+  hipLaunchKernelGGL(compress_fast_dict_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a,
+                     keep ? dict_end - keep : (const uint8_t*)nullptr, (uint32_t)keep, (const uint8_t*)image, q);
+  return (int)hipGetLastError();
+}
+// the dictionary's table image: one wavefront, once per handle and device
+__global__ __launch_bounds__(64) void dict_image_kernel(const uint8_t* tail, uint32_t keep, uint8_t* image) {
+  __shared__ __attribute__((aligned(16))) uint64_t table[LZ4HIP_TABLE_U64];
+  WaveDev w(table);
+  dict_image_build(w, tail, keep, image);
+}
+int launch_dict_image(const uint8_t* tail, int32_t keep, void* image, void* stream) {
+  if (keep < 8 || keep > 65536 || !tail || !image) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(dict_image_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, tail, (uint32_t)keep, (uint8_t*)image);
   return (int)hipGetLastError();
 }
 

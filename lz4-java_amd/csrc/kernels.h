@@ -33,6 +33,19 @@ int launch_compress_fast_ms(const BatchArgs& a, uint32_t* q, const uint32_t* rou
 // LZ4_compress_fast(..., accel) for accel 2 .. 65537 (clamped by the caller; acceleration 1 is launch_compress_fast_v2w's): the
 // one-sequence-per-step core of lz4_fast_core.h with its ACC switch, five wavefronts per CU drawing blocks from q = one device uint32_t
 int launch_compress_fast_accel(const BatchArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream);
+// What LZ4_loadDict keeps of a dictionary of `len` bytes: nothing below 8 bytes (it returns 0 and the stream has no dictionary), else
+// the last 64 KB
+constexpr uint32_t dict_keep(int32_t len) { return len < 8 ? 0u : (len > 65536 ? 65536u : (uint32_t)len); }
+// LZ4_loadDict + LZ4_compress_fast_continue(acceleration 1) on a fresh stream per block, all blocks against one dictionary: the
+// one-sequence core with its DICT switch (byU32 at every size), five wavefronts per CU drawing blocks from q = one device uint32_t.
+// [dict_end - keep, dict_end) is the dictionary's kept tail in device memory and `image` its table image (launch_dict_image), both
+// unused with keep == 0 (a dictionary under 8 bytes is none); keep is dict_keep()'s value: 0 or 8 .. 65536
+int launch_compress_fast_dict(const BatchArgs& a, const uint8_t* dict_end, int32_t keep, const void* image, uint32_t* q, uint32_t n_cus,
+                              void* stream);
+// the table LZ4_loadDict leaves for the kept tail [tail, tail + keep), keep >= 8, in the DICT core's entry layout: kDictImageBytes
+// bytes of device memory at `image` (dict_image_build of lz4_fast_core.h, one wavefront)
+constexpr size_t kDictImageBytes = 32768;
+int launch_dict_image(const uint8_t* tail, int32_t keep, void* image, void* stream);
 // LZ4_compress_destSize: a.dst_cap[i] is the target size; out[i] = bytes written, consumed[i] = input consumed (src_len[i] where
 // liblz4 returns 0 without touching it).  The one-sequence core with DirectOut's FILL switch, five wavefronts per CU drawing blocks
 // from q = one device uint32_t

@@ -269,9 +269,37 @@ constexpr uint32_t SEQ_NOCHECK = 1u << 29, SEQ_LIT_MASK = (1u << 29) - 1u;
 // of a run sits at S + g_a(k) (see g_acc); `accel` (>= 1, clamped by the caller) is read only then.  Its steps no longer sit on
 // consecutive positions beyond the first two probes, so literals always come from the source, never from the window registers.
 // ACC = false is the acceleration-1 core every other kernel runs, unchanged.
-template <class W, bool U16, class Out = DirectOut<W>, bool PK = false, bool ACC = false>
-struct FastCore {
+// DICT: LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream, liblz4's external-dictionary mode (byU32 at every size, 64-bit
+// entries).  The table holds INDEXES: block position p is kDictBase + p, byte j of the dictionary's kept tail (its last `keep` <= 64 KB
+// bytes) is kDictBase - keep + j, so a dictionary candidate is an index below kDictBase.  The table starts as the image LZ4_loadDict
+// leaves (dict_image_build below) instead of cleared, position 0 is inserted explicitly, and a candidate must also lie at or above
+// kDictBase - keep (liblz4's dictSmall check; it is what rejects the empty entries, index 0).  The candidate side of every comparison
+// reads the tail or the source, whichever the index names: the buffer (cs, cn) is chosen per hit (locate).  A dictionary match that
+// runs to the dictionary's end goes on against the block's own start.  Nothing outside the tail and [src, src + n) is read.
+// DICT = false compiles to what it did before the switch existed.
+// (the DICT core's extra state lives in a base of its own, so that every other core is the struct it was)
+template <bool DICT> struct DictState {
+  // never read: the names exist so that the `if constexpr (DICT)` branches parse
+  static constexpr const uint8_t* dict = nullptr; static constexpr const uint8_t* image = nullptr; static constexpr const uint8_t* cs = nullptr;
+  static constexpr uint32_t keep = 0, cn = 0;
+  static constexpr bool cdict = false;
+};
+template <> struct DictState<true> {
+  // set by the caller before run(): the kept tail [dict, dict + keep), keep = 0 or 8 .. 65536, and the table image of
+  // dict_image_build (4096 entries; nullptr with keep == 0)
+  const uint8_t* dict = nullptr;
+  uint32_t keep = 0;
+  const uint8_t* image = nullptr;
+  // the buffer the current candidate lives in -- the tail or the source -- and its length
+  const uint8_t* cs = nullptr;
+  uint32_t cn = 0;
+  bool cdict = false;
+};
+template <class W, bool U16, class Out = DirectOut<W>, bool PK = false, bool ACC = false, bool DICT = false>
+struct FastCore : DictState<DICT> {
   static_assert(!(U16 && PK), "compact entries are a byU32 layout");
+  static_assert(!DICT || (!U16 && !PK && !ACC), "the dictionary core is byU32 with 64-bit entries, acceleration 1");
+  static constexpr uint32_t kDictBase = 65536u;   // DICT: index of block position 0 (the stream's offset after LZ4_loadDict)
   static constexpr bool S32 = U16 || PK;           // entries are 32 bits
   static constexpr uint32_t kPackMaxN = 1u << 22;  // PK: positions have 22 bits
   using VU = typename W::VU;
@@ -302,6 +330,8 @@ struct FastCore {
   uint32_t accel = 1;   // (ACC only) liblz4's acceleration, 1 .. 65537
   bool bailed = false, probe_done = false, one_done = false;
   uint32_t p_S = 0, p_ip = 0;
+  using DictState<DICT>::dict; using DictState<DICT>::keep; using DictState<DICT>::image;
+  using DictState<DICT>::cs; using DictState<DICT>::cn; using DictState<DICT>::cdict;
 
   LZ4HIP_DEV FastCore(W& w_, Out& out_, const uint8_t* s, uint32_t n_, FastStats* st_ = nullptr)
       : w(w_), out(out_), src(s), n(n_), st(st_) {
@@ -328,6 +358,27 @@ struct FastCore {
     else return (x * 2654435761u) >> 16;
   }
   LZ4HIP_DEV static uint32_t se_pos(E e) { return (uint32_t)(e >> PSHIFT); }
+  // candidate side of a comparison: the source itself unless DICT
+  LZ4HIP_DEV const uint8_t* cbase() const { if constexpr (DICT) return cs; else return src; }
+  LZ4HIP_DEV uint32_t climit() const { if constexpr (DICT) return cn; else return n; }
+  // where the forward count of a hit stops: matchlimit unless DICT (locate)
+  LZ4HIP_DEV uint32_t flimit(uint32_t lim) const { if constexpr (DICT) return lim; else return matchlimit; }
+  // DICT: where the candidate of index `idx` lives.  Chooses (cs, cn), returns the candidate's offset in that buffer -- which is also how
+  // far a catch-up may go back: to the tail's start or to the block's -- and sets `lim`, where a forward count from hpos stops: matchlimit,
+  // or the dictionary's end.  (A tentative hit passed the lower-bound check, and LZ4_loadDict inserts only positions with 8 bytes behind
+  // them.)  Without a hit the speculative loads read the block's start.
+  LZ4HIP_DEV uint32_t locate(bool have_hit, uint32_t idx, uint32_t hpos, uint32_t& lim) {
+    lim = matchlimit;
+    cdict = have_hit && idx < kDictBase;
+    if (cdict) {
+      cs = dict; cn = keep;
+      const uint32_t dl = kDictBase - idx;
+      if (hpos + dl < lim) lim = hpos + dl;
+      return idx - (kDictBase - keep);
+    }
+    cs = src; cn = n;
+    return have_hit ? idx - kDictBase : 0u;
+  }
 
   // probe k of a miss-run starting at S sits at S + g(k): liblz4's `step = searchMatchNb++ >> 6`
   LZ4HIP_DEV static VU g(VU k) {
@@ -349,7 +400,7 @@ struct FastCore {
     if (tail == 0) return 0;
     const VB act = w.lane() < tail;
     const VU ca = w.ld8(src, w.lane() + pa_t, act);
-    const VU cb = w.ld8(src, w.lane() + pb_t, act);
+    const VU cb = w.ld8(cbase(), w.lane() + pb_t, act);
     const uint64_t bad = w.ballot(act & (ca != cb));
     return bad ? (uint32_t)ctz64(bad) : tail;
   }
@@ -361,7 +412,7 @@ struct FastCore {
       const VU off = w.lane() * 8u + cnt;
       const VU pa = off + a;
       const VB full = pa + 8u <= limit;
-      const VU64 x = w.ldu64(src, W::vmin(pa, n - 8u)) ^ w.ldu64(src, W::vmin(off + b, n - 8u));
+      const VU64 x = w.ldu64(src, W::vmin(pa, n - 8u)) ^ w.ldu64(cbase(), W::vmin(off + b, climit() - 8u));
       const VB diff = full & (x != VU64(0));
       const uint64_t dm = w.ballot(diff);
       const uint64_t stop = dm | w.ballot(!full);
@@ -380,7 +431,7 @@ struct FastCore {
       const VU jj = w.lane() + back;
       const VB act = jj < maxback;
       const VU ca = w.ld8(src, (ip - 1u) - jj, act);
-      const VU cb = w.ld8(src, (m - 1u) - jj, act);
+      const VU cb = w.ld8(cbase(), (m - 1u) - jj, act);
       const uint64_t am = w.ballot(act);
       const uint64_t bad = w.ballot(act & (ca != cb));
       if (bad) return back + (uint32_t)ctz64(bad);
@@ -416,6 +467,24 @@ struct FastCore {
   // ---- the compressor ------------------------------------------------------------------------
   LZ4HIP_DEV uint32_t run() {
     if (n < 13u) return out.last(0u);  // all literals (n == 0: the single token 0x00)
+    if constexpr (DICT) {
+      // the table as LZ4_loadDict leaves it (no image: no dictionary, every entry empty = index 0, which the lower-bound check
+      // rejects), then liblz4's first insert, position 0
+      if (image) {
+        for (uint32_t i = 0; i < (1u << HLOG); i += 64u) {
+          const VU h = w.lane() + i;
+          w.template lds_wr<S32>(h, w.ldu64(image, h * 8u), VB(true));
+        }
+      } else {
+        w.template lds_fill<S32>(1u << HLOG, (E)0);
+      }
+      w.sync();
+      const VU64 x0 = w.ldu64(src, VU(0u));
+      const VU h0 = W::lo32(((x0 << 24) * 889523592379ull) >> (64 - HLOG));
+      (void)w.template lds_max<S32>(h0, mk_entry(VU(kDictBase), fp32(W::lo32(x0))), w.lane() == 0u);
+      w.sync();
+      return loop<0>(false, 1u, 0u, 0u);
+    }
 
     // every bucket starts as {pos 0, fp(bytes at 0)}: liblz4's zeroed table makes position 0 the
     // candidate of an empty bucket, and its explicit first insert (position 0) is then implied.
@@ -474,10 +543,11 @@ struct FastCore {
       LZ4HIP_PHASE(0, w.bcast(h, 0));   // t[0]: input window arrived + hash
       // ---- [2] table lookup, tentative hits, commit ----
       const VE e = w.template lds_rdu<S32>(h);
-      const VE newe = mk_entry(pos, fp);
+      const VE newe = mk_entry(DICT ? pos + kDictBase : pos, fp);
       // (ballots of plain compares are free -- the compare already writes the lane mask; the masks are combined on the scalar side)
       uint64_t tmask = w.ballot(e_fp(e) == fp) & probem;
-      if constexpr (!U16) tmask &= w.ballot(e_pos(e) + MAXD >= pos);
+      if constexpr (DICT) tmask &= w.ballot(e_pos(e) + MAXD >= pos + kDictBase) & w.ballot(e_pos(e) >= kDictBase - keep);
+      else if constexpr (!U16) tmask &= w.ballot(e_pos(e) + MAXD >= pos);
       const uint64_t imask = ~validm;
       uint32_t k0 = tmask ? (uint32_t)ctz64(tmask) : 64u;
       const uint32_t kinv = imask ? (uint32_t)ctz64(imask) : 64u;
@@ -492,13 +562,15 @@ struct FastCore {
       const uint32_t kk = have_hit ? k0 : 0u;
       uint32_t hpos = w.bcast(pos, (int)kk);
       uint32_t mpos = se_pos(w.template bcast_e<S32>(e, (int)kk));
+      [[maybe_unused]] uint32_t midx = 0u, lim = 0u;   // DICT: the candidate's index (mpos becomes its offset in cs); where the forward count stops
+      if constexpr (DICT) { midx = mpos; mpos = locate(have_hit, midx, hpos, lim); }
       bool hit_post = post && k0 == 1u;
       uint32_t maxback = (!have_hit || hit_post) ? 0u : ((hpos - anchor) < mpos ? (hpos - anchor) : mpos);
       // (only the first kSpecLanes lanes take part -- 8 bytes each: the candidate side is a random re-read of the block and
       // every further 128 bytes are one more cache line that mostly misses L2; longer matches take count_fwd's extra round trip)
       // (lanes past kSpecLanes repeat the last taking lane's address: same cache line, no exec-mask region around the loads)
       VU64 fa = w.ldu64(src, W::vmin(o8s + hpos, n - 8u));   // kept apart from fb: xor-ing here would wait for the loads
-      VU64 fb = w.ldu64_cand(src, W::vmin(o8s + mpos, n - 8u));
+      VU64 fb = w.ldu64_cand(cbase(), W::vmin(o8s + mpos, climit() - 8u));
       VU ba, bb;
       uint64_t bactm = maxback >= 64u ? ~0ull : ((1ull << maxback) - 1ull);
       {
@@ -506,7 +578,7 @@ struct FastCore {
         // (opaque index: keeps the {scalar base + 32-bit lane offset} form; the optimiser otherwise folds the subtraction into a
         // 64-bit address per lane)
         ba = w.ldu8(src, W::opaque(W::select(bact, (hpos - 1u) - j, VU(0u))));
-        bb = w.ldu8(src, W::opaque(W::select(bact, (mpos - 1u) - j, VU(0u))));
+        bb = w.ldu8(cbase(), W::opaque(W::select(bact, (mpos - 1u) - j, VU(0u))));
       }
       if (LZ4HIP_UNLIKELY(hpos >= pf_trig)) {
         w.prefetch4k(src, pf_end, n);
@@ -541,9 +613,11 @@ struct FastCore {
           pendm &= ~gm;
         }
         uint64_t t2 = w.ballot(e_fp(se) == fp) & inm & probem;
-        if constexpr (!U16) t2 &= w.ballot(e_pos(se) + MAXD >= pos);
+        if constexpr (DICT) t2 &= w.ballot(e_pos(se) + MAXD >= pos + kDictBase) & w.ballot(e_pos(se) >= kDictBase - keep);
+        else if constexpr (!U16) t2 &= w.ballot(e_pos(se) + MAXD >= pos);
         const bool had = have_hit;
         const uint32_t hpos_old = hpos, mpos_old = mpos;
+        [[maybe_unused]] const uint32_t midx_old = midx;
         if (t2) {
           k0 = (uint32_t)ctz64(t2);
           ncommit = k0 + 1u;
@@ -556,15 +630,16 @@ struct FastCore {
         if (have_hit) {
           hpos = w.bcast(pos, (int)k0);
           mpos = se_pos(w.template bcast_e<S32>(se, (int)k0));
-          if (!had || hpos != hpos_old || mpos != mpos_old) {  // the speculation fetched the wrong candidate
+          if constexpr (DICT) { midx = mpos; mpos = locate(true, midx, hpos, lim); }
+          if (!had || hpos != hpos_old || (DICT ? midx != midx_old : mpos != mpos_old)) {  // the speculation fetched the wrong candidate
             hit_post = post && k0 == 1u;
             maxback = hit_post ? 0u : ((hpos - anchor) < mpos ? (hpos - anchor) : mpos);
             fa = w.ldu64(src, W::vmin(o8s + hpos, n - 8u));
-            fb = w.ldu64_cand(src, W::vmin(o8s + mpos, n - 8u));
+            fb = w.ldu64_cand(cbase(), W::vmin(o8s + mpos, climit() - 8u));
             bactm = maxback >= 64u ? ~0ull : ((1ull << maxback) - 1ull);
             const VB bact = w.lanes(bactm);
             ba = w.ldu8(src, W::select(bact, (hpos - 1u) - j, VU(0u)));
-            bb = w.ldu8(src, W::select(bact, (mpos - 1u) - j, VU(0u)));
+            bb = w.ldu8(cbase(), W::select(bact, (mpos - 1u) - j, VU(0u)));
           }
         }
       }
@@ -590,18 +665,26 @@ struct FastCore {
       uint32_t cnt;  // equal bytes from hpos on (>= 4)
       {
         constexpr uint64_t specm = (1ull << kSpecLanes) - 1ull;
-        const uint64_t fullm = w.ballot(o8 + (hpos + 8u) <= matchlimit);
+        const uint64_t fullm = w.ballot(o8 + (hpos + 8u) <= flimit(lim));
         const VU64 xz = W::select(j == 0u, fx & VU64(0xFFFFFFFF00000000ull), fx);
         const uint64_t dm = w.ballot(xz != VU64(0)) & fullm & specm;
         const uint64_t stop = dm | (~fullm & specm);
         if (LZ4HIP_UNLIKELY(stop == 0)) {
-          cnt = 8u * kSpecLanes + count_fwd(hpos + 8u * kSpecLanes, mpos + 8u * kSpecLanes, matchlimit);
+          cnt = 8u * kSpecLanes + count_fwd(hpos + 8u * kSpecLanes, mpos + 8u * kSpecLanes, flimit(lim));
         } else {
           const int f = ctz64(stop);
           cnt = 8u * (uint32_t)f;
           if (LZ4HIP_LIKELY((dm >> f) & 1u)) cnt += (uint32_t)(ctz64(w.bcast64(xz, f)) >> 3);
-          else if (cnt >= 4u) cnt += count_tail(hpos + cnt, mpos + cnt, matchlimit);
-          else cnt = 4u + count_tail(hpos + 4u, mpos + 4u, matchlimit);  // lane 0 itself straddles the limit
+          else if (cnt >= 4u) cnt += count_tail(hpos + cnt, mpos + cnt, flimit(lim));
+          else cnt = 4u + count_tail(hpos + 4u, mpos + 4u, flimit(lim));  // lane 0 itself straddles the limit
+        }
+      }
+      if constexpr (DICT) {
+        // the match ran to the dictionary's end: liblz4 goes on comparing against the block's own start, up to matchlimit
+        if (cdict && lim < matchlimit && hpos + cnt == lim) {
+          cs = src; cn = n;
+          cnt += count_fwd(lim, 0u, matchlimit);
+          cs = dict; cn = keep;   // (the catch-up below is on the dictionary side again)
         }
       }
       const uint32_t ip_new = hpos + cnt;
@@ -631,7 +714,8 @@ struct FastCore {
         // (ACC: lane l >= 4 sits further on -- the literals come from the source)
         const bool regs = !ACC && Out::kUsesWindowRegs && was_post && mc < 270u &&
                           (1u + (lit >= 15u ? 1u : 0u) + lit + 2u + (mc >= 15u ? 1u : 0u) <= 63u);
-        out.seq(lit, mc, hpos - mpos, anchor, !hit_post, regs, b0);
+        if constexpr (DICT) out.seq(lit, mc, (hpos + kDictBase) - midx, anchor, !hit_post, regs, b0);
+        else out.seq(lit, mc, hpos - mpos, anchor, !hit_post, regs, b0);
       }
       anchor = ip_new;
       LZ4HIP_PHASE(6, ip_new);           // t[6]: match length + catch-up + bookkeeping
@@ -657,5 +741,32 @@ struct FastCore {
 #undef LZ4HIP_PHASE
   }
 };
+
+// The table LZ4_loadDict leaves, in FastCore<.., DICT>'s entry layout: tail positions 0, 3, 6, ... while p <= keep - 8 (so the last 7
+// positions are never candidates), index kDictBase - keep + p, the last insert of a bucket wins (atomic max on the index, as in the
+// core).  One wavefront builds it in its own table (w's LDS) and writes the 4096 entries to image[0 .. 32768).  keep >= 8.
+template <class W>
+LZ4HIP_DEV void dict_image_build(W& w, const uint8_t* tail, uint32_t keep, uint8_t* image) {
+  using Core = FastCore<W, false, DirectOut<W>, false, false, true>;
+  using VU = typename W::VU;
+  using VU64 = typename W::VU64;
+  using VB = typename W::VB;
+  w.template lds_fill<false>(1u << Core::HLOG, (uint64_t)0);
+  w.sync();
+  for (uint32_t base = 0; base + 8u <= keep; base += 3u * 64u) {
+    const VU p = w.lane() * 3u + base;
+    const VB act = p + 8u <= keep;
+    const VU64 x = w.ldu64(tail, W::vmin(p, keep - 8u));
+    const VU h = W::lo32(((x << 24) * 889523592379ull) >> (64 - Core::HLOG));
+    (void)w.template lds_max<false>(h, Core::mk_entry(p + (Core::kDictBase - keep), Core::fp32(W::lo32(x))), act);
+  }
+  w.sync();
+  for (uint32_t i = 0; i < (1u << Core::HLOG); i += 64u) {
+    const VU h = w.lane() + i;
+    const VU64 e = w.template lds_rdu<false>(h);
+    w.st32(image, h * 8u, W::lo32(e), VB(true));
+    w.st32(image, h * 8u + 4u, W::lo32(e >> 32), VB(true));
+  }
+}
 
 }  // namespace lz4hip

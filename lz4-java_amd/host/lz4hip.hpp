@@ -9,6 +9,9 @@
 //   LZ4Dictionary, LZ4SafeDecompressor::decompressWithDict, LZ4HIPBatch::decompressSafeDict
 //                                                   =  LZ4_decompress_safe_usingDict of liblz4's main API against a dictionary that is not
 //                                                      contiguous with the destination (no reference entry reaches it)
+//   LZ4HIPCompressor::compressWithDict, LZ4HIPBatch::compressDict
+//                                                   =  LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream per block: the writer
+//                                                      of the records decompressWithDict reads (no reference entry reaches it)
 //   LZ4SafeDecompressor::decompressedLength, LZ4HIPBatch::decompressedLengths / decompressSafeSized
 //                                                   =  the decoded size without a destination; the batch twin of the allocating
 //                                                      overloads LZ4SafeDecompressor.java:117-137 without their worst-case buffer
@@ -69,6 +72,7 @@ class LZ4Compressor {
   bytes compress(const bytes& src) const { return compress(src, 0, (int)src.size()); }
 };
 
+class LZ4Dictionary;
 // acceleration != 1: the bytes of liblz4's LZ4_compress_fast(..., acceleration) (lz4hip_compress_fast_accel; < 1 acts as 1, > 65537 as 65537)
 class LZ4HIPCompressor final : public LZ4Compressor {
   int accel_;
@@ -96,6 +100,10 @@ class LZ4HIPCompressor final : public LZ4Compressor {
     srcLen = size;
     return result;
   }
+  // liblz4's LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream: src[srcOff, srcOff + srcLen) compressed alone against `dict`
+  // (which is not contiguous with src) into dest + destOff; returns the compressed size (lz4hip_compress_fast_dict).  There is no
+  // accelerated form: an accelerated compressor throws std::logic_error.
+  int compressWithDict(const LZ4Dictionary& dict, const bytes& src, int srcOff, int srcLen, bytes& dest, int destOff, int maxDestLen) const;
 };
 
 class LZ4HCHIPCompressor final : public LZ4Compressor {
@@ -123,8 +131,9 @@ class LZ4HCHIPCompressor final : public LZ4Compressor {
   }
 };
 
-// A shared dictionary for LZ4_decompress_safe_usingDict (lz4hip_dict_create): the handle keeps the true length and the last 64 KB,
-// resident on every initialised device.  Immutable: any number of threads may decode against it; it must outlive the calls that use it.
+// A shared dictionary for LZ4_decompress_safe_usingDict and LZ4_loadDict + LZ4_compress_fast_continue (lz4hip_dict_create): the handle
+// keeps the true length and the last 64 KB, resident on every initialised device (and the table LZ4_loadDict leaves, from its first
+// compress on a device).  Immutable: any number of threads may compress and decode against it; it must outlive the calls that use it.
 class LZ4Dictionary {
   lz4hip_dict* h_ = nullptr;
  public:
@@ -141,6 +150,16 @@ class LZ4Dictionary {
   int size() const { return lz4hip_dict_size(h_); }
   const lz4hip_dict* handle() const { return h_; }
 };
+
+inline int LZ4HIPCompressor::compressWithDict(const LZ4Dictionary& dict, const bytes& src, int srcOff, int srcLen, bytes& dest, int destOff,
+                                              int maxDestLen) const {
+  if (accel_ > 1) throw std::logic_error("compressWithDict: no accelerated form");
+  util::checkRange(src, srcOff, srcLen);
+  util::checkRange(dest, destOff, maxDestLen);
+  const int result = libCheck(lz4hip_compress_fast_dict(src.data() + srcOff, srcLen, dest.data() + destOff, maxDestLen, dict.handle()));
+  if (result <= 0) throw LZ4Exception("maxDestLen is too small");
+  return result;
+}
 
 class LZ4SafeDecompressor {
  public:
@@ -201,6 +220,20 @@ struct LZ4HIPBatch {
     }
   }
   static void status(int rc) { if (rc != 0) throw LZ4Exception(std::string("liblz4hip status ") + std::to_string(rc) + ": " + lz4hip_last_error()); }
+  // LZ4_loadDict + LZ4_compress_fast_continue per block, a fresh stream each, against one dictionary: block i is compressed into
+  // dest[destOff[i], + maxDestLen[i]); returns the compressed sizes, 0 where the slot is too small (lz4hip_compress_fast_dict_batch)
+  static std::vector<int32_t> compressDict(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen, bytes& dest,
+                                           const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen, const LZ4Dictionary& dict) {
+    checkBlocks(src, srcOff, srcLen, maxDestLen);
+    if (destOff.size() != srcOff.size()) throw std::invalid_argument("per-block arrays differ in length");
+    for (size_t i = 0; i < destOff.size(); i++)
+      if (destOff[i] > dest.size() || (uint64_t)maxDestLen[i] > dest.size() - destOff[i]) throw std::out_of_range("slot " + std::to_string(i));
+    std::vector<int32_t> out(srcOff.size(), 0);
+    bytes one(1);                                 // (empty buffers still hand the library a pointer)
+    status(lz4hip_compress_fast_dict_batch(src.empty() ? one.data() : src.data(), srcOff.data(), srcLen.data(), dest.empty() ? one.data() : dest.data(),
+                                           destOff.data(), maxDestLen.data(), out.data(), (uint32_t)srcOff.size(), dict.handle()));
+    return out;
+  }
   // LZ4_decompress_safe_usingDict per block against one dictionary: block i decodes into dest[destOff[i], + maxDestLen[i]); returns
   // liblz4's values (lz4hip_decompress_safe_dict_batch)
   static std::vector<int32_t> decompressSafeDict(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen, bytes& dest,

@@ -89,6 +89,21 @@ public final class LZ4HIPBatch {
   }
 
   /**
+   * liblz4's {@code LZ4_loadDict} + {@code LZ4_compress_fast_continue} per block, a fresh stream each, against one shared dictionary
+   * (not contiguous with {@code src}): block i is compressed alone against {@code dict} into the slot
+   * {@code dest[destOff[i], destOff[i]+destCap[i])}; {@link #decompressSafeDict} reads it.  outLen[i] &gt; 0: the compressed size;
+   * 0: the slot is too small.
+   */
+  public static void compressDict(LZ4HIPDictionary dict, ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff,
+      int[] destCap, int[] outLen) {
+    check(src, dest, srcOff, srcLen, destOff, destCap, outLen);
+    final int rc = LZ4HIPJNI.LZ4HIP_batchCompressDict(dict.handle(), src, srcOff, srcLen, dest, destOff, destCap, outLen, srcOff.length);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /**
    * liblz4's {@code LZ4_decompress_safe_usingDict} per block against one shared dictionary (not contiguous with {@code dest}): block i,
    * compressed alone against {@code dict}, decodes into the slot {@code dest[destOff[i], destOff[i]+destCap[i])}.
    * outLen[i] &gt;= 0: the decoded size; &lt; 0: -(input position)-1.

@@ -119,6 +119,48 @@ final class LZ4HIPCompressor extends LZ4Compressor {
     }
   }
 
+  /**
+   * liblz4's {@code LZ4_loadDict} + {@code LZ4_compress_fast_continue} on a fresh stream: {@code src[srcOff, srcOff+srcLen)} compressed
+   * alone against {@code dict} (which is not contiguous with {@code src}) into {@code dest[destOff, ...)}; returns the compressed size.
+   * {@code LZ4HIPSafeDecompressor.decompressWithDict} reads it.  The argument checks and the exception are compress()'s; there is no
+   * accelerated form, so an accelerated compressor throws {@link UnsupportedOperationException}.
+   */
+  public int compressWithDict(LZ4HIPDictionary dict, byte[] src, int srcOff, int srcLen, byte[] dest, int destOff, int maxDestLen) {
+    if (acceleration > 1) {
+      throw new UnsupportedOperationException("compressWithDict has no accelerated form (acceleration " + acceleration + ")");
+    }
+    checkRange(src, srcOff, srcLen);
+    checkRange(dest, destOff, maxDestLen);
+    final int result = LZ4HIPJNI.LZ4HIP_compress_fast_dict(dict.handle(), src, null, srcOff, srcLen, dest, null, destOff, maxDestLen);
+    if (result <= 0) {
+      throw new LZ4Exception(result == 0 ? "maxDestLen is too small" : "liblz4hip: " + LZ4HIPJNI.lastError());
+    }
+    return result;
+  }
+
+  /** {@link #compressWithDict(LZ4HIPDictionary, byte[], int, int, byte[], int, int)} over heap or direct buffers (positions untouched). */
+  public int compressWithDict(LZ4HIPDictionary dict, ByteBuffer src, int srcOff, int srcLen, ByteBuffer dest, int destOff, int maxDestLen) {
+    if (acceleration > 1) {
+      throw new UnsupportedOperationException("compressWithDict has no accelerated form (acceleration " + acceleration + ")");
+    }
+    checkNotReadOnly(dest);
+    checkRange(src, srcOff, srcLen);
+    checkRange(dest, destOff, maxDestLen);
+    if (!(src.hasArray() || src.isDirect()) || !(dest.hasArray() || dest.isDirect())) {
+      throw new IllegalArgumentException("compressWithDict needs heap-backed or direct ByteBuffers");
+    }
+    final byte[] srcArr = src.hasArray() ? src.array() : null;
+    final byte[] destArr = dest.hasArray() ? dest.array() : null;
+    final int so = srcArr != null ? srcOff + src.arrayOffset() : srcOff;
+    final int dof = destArr != null ? destOff + dest.arrayOffset() : destOff;
+    final int result = LZ4HIPJNI.LZ4HIP_compress_fast_dict(dict.handle(), srcArr, srcArr == null ? src : null, so, srcLen,
+                                                           destArr, destArr == null ? dest : null, dof, maxDestLen);
+    if (result <= 0) {
+      throw new LZ4Exception(result == 0 ? "maxDestLen is too small" : "liblz4hip: " + LZ4HIPJNI.lastError());
+    }
+    return result;
+  }
+
   private int nativeDestSize(byte[] srcArr, ByteBuffer srcBuf, int srcOff, int srcLen, byte[] destArr, ByteBuffer destBuf, int destOff,
       int targetDestSize, int[] srcConsumed) {
     if (acceleration > 1) {

@@ -102,6 +102,14 @@ enum LZ4HIPJNI {
    * null argument or a 0 handle: LZ4HIP_E_ARG). */
   static native int LZ4HIP_batchSafeDict(long dict, ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff,
                                          int[] destCap, int[] outLen, int nBlocks);
+  /* LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream against a dictionary handle: the compressed size, 0 (maxDestLen too
+   * small) or a library failure as LZ4HIP_compress_fast; same NULL / pinning rules */
+  static native int LZ4HIP_compress_fast_dict(long dict, byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
+                                              byte[] destArray, ByteBuffer destBuffer, int destOff, int maxDestLen);
+  /* per block over DIRECT buffers against one dictionary: outLen = the compressed sizes, 0 where destCap[i] is too small.  Returns 0 or
+   * a negative lz4hip_status (a null argument or a 0 handle: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchCompressDict(long dict, ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff,
+                                             int[] destCap, int[] outLen, int nBlocks);
   /* LZ4_compress_HC_destSize per block at HC level `level`: the arguments and return conventions of LZ4HIP_batchDestSize */
   static native int LZ4HIP_batchHCDestSize(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetSize,
                                            int[] outLen, int[] srcConsumed, int nBlocks, int level);
