@@ -164,8 +164,8 @@ int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src
 /* DECODE AGAINST A DICTIONARY: the return value and bytes of LZ4_decompress_safe_usingDict(src, dst, src_len, dst_cap, dict,
  * dict_len), liblz4 1.9.3, for a dictionary that is NOT contiguous with dst (liblz4's external-dictionary mode) -- records that
  * were each compressed alone against one shared dictionary (LZ4_loadDict + LZ4_compress_fast_continue, LZ4_loadDictHC +
- * LZ4_compress_HC_continue), every one of them readable on its own.  The fast writer of such records is
- * lz4hip_compress_fast_dict* below; there is no HC dictionary compressor, no dictionary form of the fast decoder, of the partial
+ * LZ4_compress_HC_continue), every one of them readable on its own.  The writers of such records are
+ * lz4hip_compress_fast_dict* and lz4hip_compress_hc_dict* below; there is no dictionary form of the fast decoder, of the partial
  * decoder or of the size query, and no prefix mode (linked blocks).
  *   - out_len[i] is liblz4's return value on valid AND malformed streams: the decoded size, or -(input position) - 1;
  *   - offsets: with dict_len < 65536 an offset is valid iff offset <= output position + dict_len; with dict_len >= 65536 no
@@ -210,13 +210,43 @@ int lz4hip_decompress_safe_dict_batch(const uint8_t* src, const uint64_t* src_of
  *     memory per device, built by a kernel at the handle's first compress on that device (that one call waits for its stream once;
  *     a handle that only decodes never has one) and freed by lz4hip_dict_free;
  *   - one kernel, compress_fast_dict_cu_kernel: the one-sequence core with its DICT switch, five wavefronts per CU, each loading its
- *     table from the image per block; acceleration is 1, there is no attach-dictionary, prefix or HC form and no LZ4_saveDict;
+ *     table from the image per block; acceleration is 1, there is no attach-dictionary or prefix form and no LZ4_saveDict (the HC
+ *     form is lz4hip_compress_hc_dict* below);
  *   - dict == NULL is LZ4HIP_E_ARG, no device LZ4HIP_E_NO_DEVICE; the host batch shards over the initialised devices and brings
  *     back only the bytes each block produced, as lz4hip_compress_fast_batch does;
  *   - single calls (lz4hip_compress_fast_dict) are coalesced only with concurrent compress calls on the SAME handle.            */
 int lz4hip_compress_fast_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                     uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                     int32_t* out_len, uint32_t n_blocks, const lz4hip_dict* dict);
+/* HC COMPRESS AGAINST A DICTIONARY: for every block i, on a fresh stream,
+ *     LZ4_resetStreamHC_fast(s, level);  LZ4_loadDictHC(s, dict, dict_len);
+ *     LZ4_compress_HC_continue(s, src_i, dst_i, src_len[i], dst_cap[i])
+ * of liblz4 1.9.3 with a dictionary that is NOT contiguous with the source (its external-dictionary mode): the return value and the
+ * bytes, byte for byte.  Blocks are independent, nothing carries over from one to the next; lz4hip_decompress_safe_dict* reads them.
+ *   - out_len[i] > 0 is the compressed size; 0 where liblz4 returns 0 (dst_cap[i] below the bound and the output does not fit, or
+ *     src_len[i] > 0x7E000000) and for a negative src_len[i] or dst_cap[i], as for lz4hip_compress_hc*;
+ *   - levels as for lz4hip_compress_hc*: < 1 -> 9, > 12 -> 12; 1..9 the hash chain with lazy evaluation (9: pattern analysis),
+ *     10..12 the optimal parser (functional only);
+ *   - only the dictionary's last 64 KB count and there is no minimum length: a dictionary of 4 bytes has one candidate position,
+ *     one of 0..3 bytes has none.  The dictionary's last three positions are never match candidates;
+ *   - a match may start in the dictionary (its offset then exceeds its position in the block) and, where it runs to the dictionary's
+ *     end, goes on against the block's own start;
+ *   - nothing outside the dictionary's kept bytes and block i's source is read, nothing outside block i's slot is written.  One
+ *     consequence: where the chain swap of levels 10..12 lands on one of the dictionary's last three positions, liblz4 compares
+ *     bytes behind the dictionary's end; here such a position never matches;
+ *   - the handle is the decoder's (lz4hip_dict_create).  The HC compressor also needs what LZ4_loadDictHC leaves -- the head table
+ *     and the dictionary's chain deltas: 128 KB + 2 bytes per kept byte of device memory per device --, built by a kernel
+ *     (hc_dict_image_kernel) at the handle's first HC compress on that device: that one call waits for its stream once.  The image
+ *     does not depend on the level, exists beside the fast compressor's, and is freed by lz4hip_dict_free;
+ *   - kernels: hc_build_dict_kernel (hc_build_kernel's twin; each record's head table starts as the image's, 128 KB read per record
+ *     whatever its size) and hc_parse_dict_kernel (hc_parse_kernel's twin); the workspace is lz4hip_hc_workspace_bytes, unchanged;
+ *     there is no attach-dictionary, prefix or destSize form and no LZ4_saveDict; no existing entry point changed behaviour;
+ *   - dict == NULL is LZ4HIP_E_ARG, no device LZ4HIP_E_NO_DEVICE; the host batch shards over the initialised devices and brings
+ *     back only the bytes each block produced;
+ *   - single calls (lz4hip_compress_hc_dict) are coalesced only with concurrent calls on the SAME handle at the same clamped level. */
+int lz4hip_compress_hc_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                  uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                  int32_t* out_len, uint32_t n_blocks, int level, const lz4hip_dict* dict);
 int lz4hip_compress_hc_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                              uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                              int32_t* out_len, uint32_t n_blocks, int level);
@@ -315,6 +345,18 @@ int lz4hip_decompress_safe_dict_batch_dev(const uint8_t* src, const uint64_t* sr
 /* compress against a dictionary (see lz4hip_compress_fast_dict_batch): device pointers on `device`, and the HANDLE -- the compressor
  * needs its table image, not only the bytes; asynchronous, except that a handle's first compress on a device builds the image and
  * waits for `stream` once.  dict == NULL is LZ4HIP_E_ARG */
+/* HC compress against a dictionary (see lz4hip_compress_hc_dict_batch): device pointers on `device`, and the HANDLE.  The plain form
+ * sizes the chain workspace itself and synchronises `stream` once, as lz4hip_compress_hc_batch_dev does; the _ws form takes the span
+ * (max of src_off + src_len) and a workspace of lz4hip_hc_workspace_bytes(src_span, n_blocks, level) bytes from the caller and is
+ * fully asynchronous -- except that the handle's first HC compress on a device builds its image there and waits for `stream` once.  A
+ * block whose source reaches past src_span gives 0 and leaves the workspace alone.  dict == NULL (or ws == NULL) is LZ4HIP_E_ARG */
+int lz4hip_compress_hc_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                      int32_t* out_len, uint32_t n_blocks, int level, const lz4hip_dict* dict, int device, void* stream);
+int lz4hip_compress_hc_dict_batch_dev_ws(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                         uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                         int32_t* out_len, uint32_t n_blocks, int level, const lz4hip_dict* dict, int device, void* stream,
+                                         uint64_t src_span, void* ws, size_t ws_bytes);
 int lz4hip_compress_fast_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                         uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                         int32_t* out_len, uint32_t n_blocks, const lz4hip_dict* dict, int device, void* stream);
@@ -380,6 +422,7 @@ int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int ds
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len);
 int lz4hip_decompress_safe_partial(const uint8_t* src, int src_len, uint8_t* dst, int target_size, int dst_cap);  /* LZ4_decompress_safe_partial */
 int lz4hip_decompressed_size(const uint8_t* src, int src_len, int dst_cap);  /* what LZ4_decompress_safe(src, dst, src_len, dst_cap) would return; no dst */
+int lz4hip_compress_hc_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level, const lz4hip_dict* dict);  /* LZ4_loadDictHC + LZ4_compress_HC_continue on a fresh stream; dict == NULL: LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
 int lz4hip_compress_fast_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, const lz4hip_dict* dict);  /* LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream; dict == NULL: LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
 int lz4hip_decompress_safe_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, const lz4hip_dict* dict);  /* LZ4_decompress_safe_usingDict; dict == NULL: LZ4HIP_LIB_ERROR(LZ4HIP_E_ARG) */
 int lz4hip_xxh32(const uint8_t* buf, int len, uint32_t seed, uint32_t* out);

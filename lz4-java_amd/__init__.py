@@ -59,6 +59,7 @@ C_ABI = {
     "lz4hip_dict_free": (None, [C.c_void_p]),
     "lz4hip_compress_fast_dict_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_void_p]),
     "lz4hip_decompress_safe_dict_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_void_p]),
+    "lz4hip_compress_hc_dict_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
@@ -66,6 +67,8 @@ C_ABI = {
     "lz4hip_compress_dest_size_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_decompress_safe_partial_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_fast_dict_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
+    "lz4hip_compress_hc_dict_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "lz4hip_compress_hc_dict_batch_dev_ws": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
     "lz4hip_decompress_safe_dict_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_dest_size_batch_dev": (C.c_int, [C.c_void_p] * 8 + [C.c_uint32, C.c_int, C.c_int, C.c_void_p]),
@@ -87,6 +90,7 @@ C_ABI = {
     "lz4hip_decompress_safe_partial": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_compress_fast_dict": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "lz4hip_decompress_safe_dict": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "lz4hip_compress_hc_dict": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "lz4hip_decompressed_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "lz4hip_xxh32": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32, _u32p]),
     "lz4hip_xxh64": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _u64p]),
@@ -321,14 +325,37 @@ class LZ4HCHIPCompressor(LZ4Compressor):
         written = _single(lib().lz4hip_compress_hc_dest_size(sp + srcOff, C.byref(size), dp + destOff, targetDestSize, self.compressionLevel))
         return written, size.value
 
+    def compressWithDict(self, dictionary, src, srcOff=None, srcLen=None, dest=None, destOff=None, maxDestLen=None):
+        """liblz4's LZ4_loadDictHC + LZ4_compress_HC_continue on a fresh stream at this compressor's level (the dictionary not
+        contiguous with src): the block src[srcOff:srcOff+srcLen] compressed alone against an LZ4Dictionary (lz4hip_compress_hc_dict);
+        the forms of compress(): compressWithDict(d, src[, srcOff, srcLen]) -> bytes | compressWithDict(d, src, srcOff, srcLen, dest,
+        destOff[, maxDestLen]) -> int.  LZ4SafeDecompressor.decompressWithDict reads it."""
+        if dest is None:
+            srcOff = 0 if srcOff is None else srcOff
+            srcLen = len(src) - srcOff if srcLen is None else srcLen
+            out = bytearray(self.maxCompressedLength(srcLen))
+            n = self.compressWithDict(dictionary, src, srcOff, srcLen, out, 0, len(out))
+            return bytes(out[:n])
+        destOff = 0 if destOff is None else destOff
+        maxDestLen = len(dest) - destOff if maxDestLen is None else maxDestLen
+        dp, dk = _rw_ptr(dest)
+        _check_range(src, srcOff, srcLen)
+        _check_range(dest, destOff, maxDestLen)
+        sp, sk = _ro_ptr(src)
+        result = _single(lib().lz4hip_compress_hc_dict(sp + srcOff, srcLen, dp + destOff, maxDestLen, self.compressionLevel, dictionary._handle()))
+        if result <= 0:
+            raise LZ4Exception()
+        return result
+
 
 # ----------------------------------------------------------------------------------------------
 # decompressors
 # ----------------------------------------------------------------------------------------------
 class LZ4Dictionary:
-    """A shared dictionary for LZ4_decompress_safe_usingDict and for LZ4_loadDict + LZ4_compress_fast_continue (lz4hip_dict_create):
-    the handle keeps the true length and the last 64 KB, resident on every initialised device (and, from its first compress on a
-    device, the 32 KB table LZ4_loadDict leaves).  Immutable; any number of threads may compress and decode against it.  close() -- or leaving a `with`
+    """A shared dictionary for LZ4_decompress_safe_usingDict, for LZ4_loadDict + LZ4_compress_fast_continue and for LZ4_loadDictHC +
+    LZ4_compress_HC_continue (lz4hip_dict_create): the handle keeps the true length and the last 64 KB, resident on every initialised
+    device (and, from its first compress on a device, the 32 KB table LZ4_loadDict leaves; from its first HC compress, the 128 KB head
+    table and 2 bytes per kept byte that LZ4_loadDictHC leaves).  Immutable; any number of threads may compress and decode against it.  close() -- or leaving a `with`
     block -- frees it; no call that uses it may be in flight then."""
 
     def __init__(self, data):
@@ -831,6 +858,12 @@ class LZ4HIPBatch:
         return cls._call("lz4hip_compress_fast_dict_batch", src, srcOff, srcLen, dst, dstOff, dstCap, dictionary._handle())
 
     @classmethod
+    def compressHCDict(cls, src, srcOff, srcLen, dst, dstOff, dstCap, dictionary, level=9):
+        """LZ4_loadDictHC + LZ4_compress_HC_continue per block at HC level `level`, a fresh stream each, against one LZ4Dictionary ->
+        compressed sizes, 0 where liblz4 returns 0 (lz4hip_compress_hc_dict_batch)"""
+        return cls._call("lz4hip_compress_hc_dict_batch", src, srcOff, srcLen, dst, dstOff, dstCap, int(level), dictionary._handle())
+
+    @classmethod
     def decompressSafeDict(cls, src, srcOff, srcLen, dst, dstOff, dstCap, dictionary):
         """LZ4_decompress_safe_usingDict per block against one LZ4Dictionary -> liblz4's return values
         (lz4hip_decompress_safe_dict_batch)"""
@@ -1049,6 +1082,33 @@ class DeviceBatch:
         _chk(lib().lz4hip_compress_fast_dict_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
                                                        dst_off.data_ptr(), dst_cap.data_ptr(), out.data_ptr(), src_off.numel(),
                                                        dictionary._handle(), dev, st))
+
+    @classmethod
+    def compress_hc_dict(cls, src, src_off, src_len, dst, dst_off, dst_cap, out, dictionary, level=9, span=None, ws=None):
+        """LZ4_loadDictHC + LZ4_compress_HC_continue per block, a fresh stream each (lz4hip_compress_hc_dict_batch_dev_ws):
+        `dictionary` is an LZ4Dictionary; out = compressed sizes, 0 where liblz4 returns 0.  The workspace as in compress_hc, or the
+        caller's (span = the source bytes it is for, ws = a uint8 tensor).  Asynchronous, but a dictionary's first HC compress on a
+        device waits for the stream once"""
+        import torch
+        dev, st = cls._stream_dev(src)
+        if span is None:
+            span = src.numel() * src.element_size()
+        own = ws is None
+        if own:
+            ws = torch.empty(max(lib().lz4hip_hc_workspace_bytes(span, src_off.numel(), level), 1), dtype=torch.uint8, device=src.device)
+        _chk(lib().lz4hip_compress_hc_dict_batch_dev_ws(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
+                                                        dst_off.data_ptr(), dst_cap.data_ptr(), out.data_ptr(), src_off.numel(), int(level),
+                                                        dictionary._handle(), dev, st, span, ws.data_ptr(), ws.numel()))
+        if own:
+            ws.record_stream(torch.cuda.current_stream(src.device))
+
+    @classmethod
+    def compress_hc_dict_sync(cls, src, src_off, src_len, dst, dst_off, dst_cap, out, dictionary, level=9):
+        """the entry that sizes its own workspace (lz4hip_compress_hc_dict_batch_dev; synchronises the stream once)"""
+        dev, st = cls._stream_dev(src)
+        _chk(lib().lz4hip_compress_hc_dict_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), dst.data_ptr(),
+                                                     dst_off.data_ptr(), dst_cap.data_ptr(), out.data_ptr(), src_off.numel(), int(level),
+                                                     dictionary._handle(), dev, st))
 
     @classmethod
     def decompress_safe_dict(cls, src, src_off, src_len, dst, dst_off, dst_cap, out, dictionary):

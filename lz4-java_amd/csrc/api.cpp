@@ -79,12 +79,14 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // launch runs on) or the caller's device memory (BlockCall::dict_dev / dict_len)
 // OP_COMPRESS_DICT: LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream per block, against a handle (BlockCall::dict) -- always
 // a handle: the compressor needs the dictionary's table image (dict_compress_state), not only its bytes
+// OP_COMPRESS_HC_DICT: LZ4_loadDictHC + LZ4_compress_HC_continue on a fresh stream per block, against a handle (BlockCall::dict):
+// OP_COMPRESS_HC's level and workspace, and the handle's HC image (dict_hc_state)
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
-          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT };
-constexpr int OP_COUNT = OP_COMPRESS_DICT + 1;   // (the last enumerator)
+          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT };
+constexpr int OP_COUNT = OP_COMPRESS_HC_DICT + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
-constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT; }
+constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT; }
 // a second per-block result (BlockCall::consumed) travels behind out[]
 constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
 // out[i] counts SOURCE bytes read: a block that succeeded filled its whole dst_cap[i]
@@ -92,7 +94,7 @@ constexpr bool op_fills_capacity(Op op) { return op == OP_DECODE_FAST; }
 // writes no output buffer: dst and dst_off may be NULL, nothing is allocated, staged or copied back for them (dst_cap is an input)
 constexpr bool op_writes_no_output(Op op) { return op == OP_DECODED_SIZE; }
 // needs the chain-delta workspace (BlockCall::hc_ws / hc_span)
-constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC || op == OP_COMPRESS_HC_DEST; }
+constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_HC_DICT; }
 
 // One block operation, from its entry point to launch_block.
 struct BlockCall {
@@ -102,7 +104,7 @@ struct BlockCall {
   int32_t* consumed = nullptr;      // op_has_consumed: the input consumed per block
   void* hc_ws = nullptr;            // op_uses_hc_ws: device workspace for hc_span bytes of source; nullptr: launch_block learns the
   uint64_t hc_span = 0;             // span and allocates one (hc_workspace)
-  const lz4hip_dict* dict = nullptr;    // OP_COMPRESS_DICT: the dictionary handle; OP_DECODE_DICT: the handle (host path, single calls) ...
+  const lz4hip_dict* dict = nullptr;    // OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT: the dictionary handle; OP_DECODE_DICT: the handle (host path, single calls) ...
   const uint8_t* dict_dev = nullptr;    // ... or, without a handle, the caller's dictionary in device memory and
   int32_t dict_len = 0;                 // its length
 };
@@ -113,6 +115,9 @@ int dict_resident(const lz4hip_dict* d, const uint8_t** dict_end, int32_t* dict_
 // it (lz4hip::dict_keep: 0 = no dictionary) and the table image, built at the handle's first compress on the device (that one call
 // waits for `st` once, so that calls on other streams find the image complete)
 int dict_compress_state(const lz4hip_dict* d, hipStream_t st, const uint8_t** dict_end, int32_t* keep, const void** image);
+// the same for the HC dictionary compressor: the kept tail as LZ4_loadDictHC keeps it (lz4hip::hc_dict_keep: no minimum) and the HC
+// image (lz4hip::hc_dict_image_bytes), built at the handle's first HC compress on the device (that one call waits for `st` once)
+int dict_hc_state(const lz4hip_dict* d, hipStream_t st, const uint8_t** dict_end, uint32_t* keep, const void** image);
 // tuning knobs (lz4hip_set_option): atomics, so that a caller changing one while other threads launch is a race on the VALUE chosen,
 // never undefined behaviour; every launch reads each knob once
 std::atomic<int> g_decode_lanes{0};   // "decode_lanes"; 0 = kernel default
@@ -250,12 +255,22 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
       return lz4hip::launch_decompress_dict(a, dict_end, dict_len, st);
     }
     case OP_COMPRESS_HC:
+    case OP_COMPRESS_HC_DICT:
     case OP_COMPRESS_HC_DEST: {
+      const uint8_t* dict_end = nullptr;
+      uint32_t keep = 0;
+      const void* image = nullptr;
+      if (c.op == OP_COMPRESS_HC_DICT) {
+        if (!c.dict) return fail(LZ4HIP_E_ARG, kNullArg);
+        const int rc = dict_hc_state(c.dict, st, &dict_end, &keep, &image);
+        if (rc) return rc;
+      }
       void* ws = c.hc_ws;
       uint64_t span = c.hc_span;
       if (!ws) { const int rc = hc_workspace(a, c.param, st, &ws, &span); if (rc) return rc; }
-      const int e = c.op == OP_COMPRESS_HC ? lz4hip::launch_compress_hc(a, c.param, ws, span, st)
-                                           : lz4hip::launch_compress_hc_dest(a, c.consumed, c.param, ws, span, st);
+      const int e = c.op == OP_COMPRESS_HC      ? lz4hip::launch_compress_hc(a, c.param, ws, span, st)
+                  : c.op == OP_COMPRESS_HC_DICT ? lz4hip::launch_compress_hc_dict(a, c.param, ws, span, dict_end, keep, image, st)
+                                                : lz4hip::launch_compress_hc_dest(a, c.consumed, c.param, ws, span, st);
       if (!c.hc_ws) (void)hipFreeAsync(ws, st);
       return e;
     }
@@ -794,9 +809,11 @@ Combiner g_hc_dest_comb[13];   // [HC level]: LZ4_compress_HC_destSize, coalesce
 std::mutex g_accel_comb_mu;
 std::map<int, Combiner> g_accel_comb;
 Combiner* dict_combiner(const lz4hip_dict* d, bool compress);   // (the handle's own: single calls coalesce only with calls of the same operation on the same handle)
+Combiner* dict_hc_combiner(const lz4hip_dict* d, int level);    // (the handle's own, per clamped HC level)
 // nullptr: no combiner for this call (an operation or level outside the tables); may throw (the map's allocation)
 Combiner* combiner_for(const BlockCall& c) {
   if (c.op == OP_DECODE_DICT || c.op == OP_COMPRESS_DICT) return c.dict ? dict_combiner(c.dict, c.op == OP_COMPRESS_DICT) : nullptr;
+  if (c.op == OP_COMPRESS_HC_DICT) return c.dict && c.param >= 1 && c.param <= 12 ? dict_hc_combiner(c.dict, c.param) : nullptr;
   if (c.op == OP_COMPRESS_ACCEL) {
     std::lock_guard<std::mutex> lk(g_accel_comb_mu);
     return &g_accel_comb[c.param];   // (std::map: references stay valid while other entries are added)
@@ -887,7 +904,9 @@ int single(const BlockCall& c, const uint8_t* src, int src_len, uint8_t* dst, in
 // copy of those bytes on every initialised device, made by lz4hip_dict_create, or on a device's first use where the engine was
 // initialised (again) later.  The handle is immutable after creation: any number of threads may decode against it.
 // A compressor also needs the table LZ4_loadDict leaves (32 KB, lz4hip::launch_dict_image): built per device at the handle's first
-// compress there, never for a handle that only decodes, and freed with the handle.
+// compress there, never for a handle that only decodes, and freed with the handle.  The HC compressor's image (the head table and
+// the chain deltas LZ4_loadDictHC leaves: 128 KB + 2 bytes per kept byte, lz4hip::launch_hc_dict_image) likewise, at the first HC
+// compress; the two images are independent.
 struct lz4hip_dict {
   int32_t len = 0;               // the dictionary's true length
   std::vector<uint8_t> tail;     // its last min(len, 65536) bytes
@@ -896,12 +915,15 @@ struct lz4hip_dict {
   void* image[64] = {};          // [HIP ordinal]: the compressor's table image (only where dict_keep(len) > 0, from the first compress on)
   Combiner comb;                 // single decode calls on this handle
   Combiner comb_c;               // single compress calls on this handle
+  void* hc_image[64] = {};       // [HIP ordinal]: the HC compressor's image (from the first HC compress on)
+  Combiner comb_hc[13];          // [HC level]: single HC compress calls on this handle
 };
 namespace {
 Combiner* dict_combiner(const lz4hip_dict* d, bool compress) {
   lz4hip_dict* m = const_cast<lz4hip_dict*>(d);
   return compress ? &m->comb_c : &m->comb;
 }
+Combiner* dict_hc_combiner(const lz4hip_dict* d, int level) { return &const_cast<lz4hip_dict*>(d)->comb_hc[level]; }
 int dict_upload(lz4hip_dict* d, int ord) {   // (d->mu held or the handle not yet published; the device is current)
   if (d->dev[ord] || d->tail.empty()) return LZ4HIP_OK;
   uint8_t* p = nullptr;
@@ -945,6 +967,28 @@ int dict_compress_state(const lz4hip_dict* cd, hipStream_t st, const uint8_t** d
   }
   *dict_end = d->dev[ord] + d->tail.size();
   *image = d->image[ord];
+  return LZ4HIP_OK;
+}
+int dict_hc_state(const lz4hip_dict* cd, hipStream_t st, const uint8_t** dict_end, uint32_t* keep, const void** image) {
+  lz4hip_dict* d = const_cast<lz4hip_dict*>(cd);
+  int ord = -1;
+  if (hipGetDevice(&ord) != hipSuccess || ord < 0 || ord >= 64) return fail(LZ4HIP_E_HIP, "hipGetDevice failed");
+  *keep = lz4hip::hc_dict_keep(d->len);   // (= tail.size(): LZ4_loadDictHC has no minimum length)
+  *dict_end = nullptr;
+  *image = nullptr;
+  std::lock_guard<std::mutex> lk(d->mu);
+  const int rc = dict_upload(d, ord);
+  if (rc) return rc;
+  if (!d->hc_image[ord]) {   // (also for an empty dictionary: the record's build starts from the image's -- empty -- head table)
+    void* p = nullptr;
+    if (hipMalloc(&p, lz4hip::hc_dict_image_bytes(*keep)) != hipSuccess) return fail(LZ4HIP_E_NOMEM, "hipMalloc of the dictionary's HC image failed");
+    const int le = lz4hip::launch_hc_dict_image(d->dev[ord], *keep, p, st);
+    const hipError_t e = le ? (hipError_t)le : hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipFree(p); return fail(LZ4HIP_E_HIP, "dictionary HC image", e); }
+    d->hc_image[ord] = p;
+  }
+  if (*keep) *dict_end = d->dev[ord] + d->tail.size();
+  *image = d->hc_image[ord];
   return LZ4HIP_OK;
 }
 }  // namespace
@@ -1434,10 +1478,11 @@ int lz4hip_dict_size(const lz4hip_dict* dict) { return dict ? dict->len : fail(L
 void lz4hip_dict_free(lz4hip_dict* dict) {
   if (!dict) return;
   for (int ord = 0; ord < 64; ord++) {
-    if (!dict->dev[ord] && !dict->image[ord]) continue;
+    if (!dict->dev[ord] && !dict->image[ord] && !dict->hc_image[ord]) continue;
     DeviceGuard g(ord);
     if (g.ok && dict->dev[ord]) (void)hipFree(dict->dev[ord]);
     if (g.ok && dict->image[ord]) (void)hipFree(dict->image[ord]);
+    if (g.ok && dict->hc_image[ord]) (void)hipFree(dict->hc_image[ord]);
   }
   delete dict;
 }
@@ -1458,6 +1503,18 @@ int lz4hip_compress_fast_dict_batch(const uint8_t* src, const uint64_t* src_off,
   if (n == 0) return LZ4HIP_OK;
   if (!dict) return fail(LZ4HIP_E_ARG, kNullArg);
   BlockCall c{OP_COMPRESS_DICT};
+  c.dict = dict;
+  return host_batch(c, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
+}
+int lz4hip_compress_hc_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                  const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int level, const lz4hip_dict* dict) {
+  int rc = ensure_init();
+  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (n == 0) return LZ4HIP_OK;
+  if (!dict) return fail(LZ4HIP_E_ARG, kNullArg);
+  int lv;
+  if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
+  BlockCall c{OP_COMPRESS_HC_DICT, lv};
   c.dict = dict;
   return host_batch(c, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
 }
@@ -1563,6 +1620,25 @@ int lz4hip_compress_hc_batch_dev(const uint8_t* src, const uint64_t* src_off, co
   if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
   return dev_batch({OP_COMPRESS_HC, lv}, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream);
 }
+int lz4hip_compress_hc_dict_batch_dev_ws(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst, const uint64_t* dst_off,
+                                         const int32_t* dst_cap, int32_t* out_len, uint32_t n, int level, const lz4hip_dict* dict, int device,
+                                         void* stream, uint64_t src_span, void* ws, size_t ws_bytes) {
+  int lv;
+  if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
+  BlockCall c{OP_COMPRESS_HC_DICT, lv, nullptr, nullptr, ws, src_span};
+  c.dict = dict;
+  return dev_batch(c, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream,
+                   !dict || !ws ? kNullArg : ws_bytes < lz4hip::hc_ws_bytes(src_span, n, lv) ? "HC workspace too small for the source span" : nullptr);
+}
+int lz4hip_compress_hc_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
+                                      const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int level,
+                                      const lz4hip_dict* dict, int device, void* stream) {
+  int lv;
+  if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
+  BlockCall c{OP_COMPRESS_HC_DICT, lv};
+  c.dict = dict;
+  return dev_batch(c, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream, dict ? nullptr : kNullArg);
+}
 int lz4hip_compress_hc_dest_size_batch_dev_ws(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                               const uint64_t* dst_off, const int32_t* target_size, int32_t* out_len, int32_t* src_consumed,
                                               uint32_t n, int level, int device, void* stream, uint64_t src_span, void* ws, size_t ws_bytes) {
@@ -1642,6 +1718,16 @@ int lz4hip_compress_fast_dict(const uint8_t* src, int src_len, uint8_t* dst, int
   if (rc) return LZ4HIP_LIB_ERROR(fail(rc, "no HIP device: liblz4hip has no CPU fallback"));
   if (!dict) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, kNullArg));
   BlockCall c{OP_COMPRESS_DICT};
+  c.dict = dict;
+  return single(c, src, src_len, dst, dst_cap);
+}
+int lz4hip_compress_hc_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level, const lz4hip_dict* dict) {
+  int rc = ensure_init();
+  if (rc) return LZ4HIP_LIB_ERROR(fail(rc, "no HIP device: liblz4hip has no CPU fallback"));
+  if (!dict) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, kNullArg));
+  int lv;
+  if (hc_level(level, &lv)) return LZ4HIP_LIB_ERROR(LZ4HIP_E_UNSUPPORTED);
+  BlockCall c{OP_COMPRESS_HC_DICT, lv};
   c.dict = dict;
   return single(c, src, src_len, dst, dst_cap);
 }

@@ -62,6 +62,15 @@ int launch_compress_hc(const BatchArgs& a, int level, void* ws, uint64_t span, v
 // workspace as launch_compress_hc.  The parse of a block stops once its target is full, so the parse time follows the input
 // consumed; the delta[] build still covers the whole block.
 int launch_compress_hc_dest(const BatchArgs& a, int32_t* consumed, int level, void* ws, uint64_t span, void* stream);
+// LZ4_loadDictHC + LZ4_compress_HC_continue on a fresh stream per block, all blocks against one dictionary (external-dictionary mode):
+// hc_build_dict_kernel + hc_parse_dict_kernel, same workspace as launch_compress_hc.  [dict_end - K, dict_end) is the dictionary's
+// kept tail in device memory, K = hc_dict_keep(its length) = 0 .. 65536 (K == 0: dict_end is not looked at), `image` its image:
+// hc_dict_image_bytes(K) bytes of device memory filled by launch_hc_dict_image (one wavefront; the image does not depend on the level)
+constexpr uint32_t hc_dict_keep(int32_t len) { return len > 65536 ? 65536u : (uint32_t)len; }
+constexpr size_t hc_dict_image_bytes(uint32_t K) { return 131072u + 2u * (size_t)K; }
+int launch_hc_dict_image(const uint8_t* tail, uint32_t K, void* image, void* stream);
+int launch_compress_hc_dict(const BatchArgs& a, int level, void* ws, uint64_t span, const uint8_t* dict_end, uint32_t K, const void* image,
+                            void* stream);
 // after a compress launch: moves the out[i] > 0 useful bytes of every slot to pack + sum(out[0..i)); poff: u64[n] scratch
 int launch_pack(const BatchArgs& a, uint64_t* poff, uint8_t* pack, void* stream);
 // Device-side container assembly (container.hip): the data blocks of an LZ4 Frame (kind 0; block_checksum: XXH32 of each stored

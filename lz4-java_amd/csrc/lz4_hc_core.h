@@ -61,16 +61,20 @@ constexpr int HC_OPT_INTS = 4 * (HC_OPT_NUM + HC_OPT_TRAILING);  // per-block wo
 // ---------------------------------------------------------------------------------------------------
 // phase 1: delta[] builder (one wavefront, 128 KB LDS head table)
 // ---------------------------------------------------------------------------------------------------
-template <class W>
+// DICT (a record behind a dictionary, LZ4_loadDictHC + LZ4_compress_HC_continue): the caller has loaded the head table with the
+// one the build over the dictionary's kept tail ended with, and src[0] has index `first` = HC_BIAS + kept bytes instead of HC_BIAS.
+// A link that reaches into the dictionary is a plain index distance; the dictionary's own links are the handle's (HcDictRef).
+template <class W, bool DICT = false>
 struct HcBuild {
   using VU = typename W::VU;
   using VU64 = typename W::VU64;
   using VB = typename W::VB;
 
-  LZ4HIP_DEV static void run(W& w, const uint8_t* src, uint32_t n, uint16_t* delta) {
+  LZ4HIP_DEV static void run(W& w, const uint8_t* src, uint32_t n, uint16_t* delta, uint32_t first = HC_BIAS) {
     if (n < 4u) return;
     const uint32_t last = n - 4u;  // last position whose 4-byte hash is readable
-    w.template lds_fill<true>(32768u, 0u);
+    const uint32_t bias = DICT ? first : HC_BIAS;
+    if constexpr (!DICT) w.template lds_fill<true>(32768u, 0u);
     w.sync();
     const VU j = w.lane();
     // The input words of a step do not depend on the table: they are requested one group of U steps ahead, so the only
@@ -88,7 +92,7 @@ struct HcBuild {
         if (p0 > last) break;
         const VU p = j + p0;
         const VB valid = p <= last;
-        const VU idx = p + HC_BIAS;
+        const VU idx = p + bias;
         const VU h = (x[u] * 2654435761u) >> 17;
         // ONE LDS round trip per step: the atomic max returns the bucket's value right before this lane's insert.  The lanes of
         // an instruction execute in some order; if the lanes sharing a bucket happened to go in rising position order, every
@@ -106,7 +110,7 @@ struct HcBuild {
           const VB has = grp & (lower != VU64(0));
           const VU srcl = VU(63u) - W::clz64(lower);
           // the group's first lane takes what the bucket held before this step: the value the lane that executed first got back
-          const uint64_t fm = w.ballot(grp & (old < p0 + HC_BIAS));
+          const uint64_t fm = w.ballot(grp & (old < p0 + bias));
           const uint32_t before = w.bcast(old, ctz64(fm));
           prev = W::select(has, w.template shfl_e<true>(idx, srcl), W::select(grp, VU(before), prev));
           pend &= ~gm;
@@ -119,10 +123,39 @@ struct HcBuild {
   }
 };
 
+// The dictionary's part of the chain (LZ4_loadDictHC), the same for every record of every batch at every level: delta[] over the
+// kept tail [tail, tail + K), 0 <= K <= 65536, into ddelta[0 .. K), and the head table the build ends with, left in the wave's LDS
+// for the caller to copy out.  liblz4 inserts positions 0 .. K - 4: the last three entries are 0, and K < 4 leaves an empty table.
+template <class W>
+LZ4HIP_DEV void hc_dict_image_build(W& w, const uint8_t* tail, uint32_t K, uint16_t* ddelta) {
+  using VU = typename W::VU;
+  const VU q = w.lane() + (K > 3u ? K - 3u : 0u);
+  w.st16(ddelta, q, VU(0u), q < K);
+  if (K >= 4u) {
+    HcBuild<W>::run(w, tail, K, ddelta);
+  } else {
+    w.template lds_fill<true>(32768u, 0u);
+    w.sync();
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // read-only chain search (LZ4HC_InsertAndGetWiderMatch on the static delta[]), scalar per caller
 // ---------------------------------------------------------------------------------------------------
-struct HcSearch {
+// What a DICT search knows of the dictionary (nothing otherwise).  Positions are relative to the record's start: a record position
+// p >= 0 is src[p], a dictionary position -K <= p < 0 is dend[p]; liblz4's index of position p is first() + p (its dictLimit is
+// first(), its lowLimit HC_BIAS).  ddelta_end[p], p < 0, is the dictionary's own delta[] (0 for its last three positions, which
+// liblz4 never inserts).
+template <bool DICT> struct HcDictRef {};
+template <> struct HcDictRef<true> {
+  const uint8_t* dend = nullptr;          // one past the dictionary's last byte
+  const uint16_t* ddelta_end = nullptr;   // one past the last entry of the dictionary's delta[]
+  int K = 0;                              // kept dictionary bytes, 0 .. 65536
+  LZ4HIP_DEV uint32_t first() const { return HC_BIAS + (uint32_t)K; }
+};
+
+template <bool DICT = false>
+struct HcSearchT : HcDictRef<DICT> {
   const uint8_t* src;
   const uint16_t* delta;
   int nb_searches;
@@ -160,6 +193,7 @@ struct HcSearch {
 
   // best match for position ip that may start as early as ilow; returns the length, updates mpos/spos
   LZ4HIP_DEV int wider(int ip, int ilow, int ihigh, int longest, int& mpos, int& spos) const {
+    if constexpr (DICT) return wider_dict(ip, ilow, ihigh, longest, mpos, spos);
     const uint32_t ip_idx = (uint32_t)ip + HC_BIAS;
     const uint32_t lowest = (HC_BIAS + 65536u > ip_idx) ? HC_BIAS : ip_idx - (uint32_t)HC_MAXD;
     const int look_back = ip - ilow;
@@ -254,7 +288,197 @@ struct HcSearch {
     }
     return longest;
   }
+
+  // ---- DICT: the same search in external-dictionary mode -------------------------------------------------------------------
+  // bytes a[0..max) == b[0..max), counted; reads nothing at or past a + max / b + max
+  LZ4HIP_DEV static int count_ptr(const uint8_t* a, const uint8_t* b, int max) {
+    int i = 0;
+    while (i + 8 <= max) {
+      const uint64_t x = hc_rd64(a + i) ^ hc_rd64(b + i);
+      if (x) return i + (int)(__builtin_ctzll(x) >> 3);
+      i += 8;
+    }
+    while (i < max && a[i] == b[i]) i++;
+    return i;
+  }
+  // liblz4's chainTable entry of index mi, on either side of the dictionary's end
+  LZ4HIP_DEV uint32_t chain_dict(uint32_t mi) const {
+    if constexpr (DICT) {
+      const int p = (int)(mi - this->first());
+      // (the dictionary's last three positions are never inserted: their entries still hold the 0 the fresh stream was filled with,
+      // not the 65535 of an inserted position without a predecessor in reach)
+      if (p < 0 && p >= -3) return 0u;
+      const uint32_t d = p >= 0 ? delta[p] : this->ddelta_end[p];
+      return d ? d : (uint32_t)HC_MAXD;
+    } else {
+      return chain(mi);
+    }
+  }
+  // liblz4's lowestMatchIndex for the search at record position ip
+  LZ4HIP_DEV uint32_t lowest_dict(int ip) const {
+    if constexpr (DICT) {
+      const uint32_t ip_idx = (uint32_t)ip + this->first();
+      return (HC_BIAS + 65536u > ip_idx) ? HC_BIAS : ip_idx - (uint32_t)HC_MAXD;
+    } else {
+      return 0u;
+    }
+  }
+  // LZ4HC_protectDictEnd: false for the dictionary's last three indexes, which are no chain members
+  LZ4HIP_DEV bool protect_dict_end(uint32_t mi) const {
+    if constexpr (DICT) return (uint32_t)((this->first() - 1u) - mi) >= 3u;
+    else return true;
+  }
+  // a candidate in the dictionary (c < 0) for the search at ip: match length (0: none) and the backward extension (<= 0).  No 2-byte
+  // pre-test; the forward count runs to the dictionary's end and goes on against the record's start; the backward count stops at
+  // the dictionary's start.  A candidate with fewer than four bytes left in the dictionary (reachable only through the chain swap
+  // of levels 10..12) is no match: liblz4 reads past the dictionary's end there.
+  LZ4HIP_DEV int dict_candidate(int ip, int ilow, int ihigh, int c, uint32_t pattern, int& back) const {
+    back = 0;
+    if constexpr (DICT) {
+      const int avail = -c;
+      if (avail < 4 || hc_rd32(this->dend + c) != pattern) return 0;
+      int vlim = ip + avail;
+      if (vlim > ihigh) vlim = ihigh;
+      int ml = 4 + count_ptr(src + ip + 4, this->dend + c + 4, vlim - (ip + 4));
+      if (ip + ml == vlim && vlim < ihigh) ml += count_fwd(src, ip + ml, 0, ihigh);
+      if (ip > ilow) {
+        const int room = c + this->K;   // bytes between the dictionary's start and the candidate
+        const int mn = -((ip - ilow) < room ? (ip - ilow) : room);
+        while (back > mn && src[ip + back - 1] == this->dend[c + back - 1]) back--;
+      }
+      return ml - back;
+    } else {
+      return 0;
+    }
+  }
+
+  LZ4HIP_DEV int wider_dict(int ip, int ilow, int ihigh, int longest, int& mpos, int& spos) const {
+    if constexpr (DICT) {
+      const uint32_t first = this->first();
+      const uint32_t ip_idx = (uint32_t)ip + first;
+      const uint32_t lowest = lowest_dict(ip);
+      const int look_back = ip - ilow;
+      int attempts = nb_searches;
+      const uint32_t pattern = hc_rd32(src + ip);
+      int repeat = 0;  // 0 untested, 1 not, 2 confirmed
+      int src_pat_len = 0;
+      uint32_t mi;
+      {
+        const uint32_t d0 = delta[ip];
+        mi = d0 ? ip_idx - d0 : 0u;
+      }
+      uint32_t chain_pos = 0;
+      while (mi >= lowest && attempts > 0) {
+        attempts--;
+        const int mp = (int)(mi - first);
+        int ml = 0;
+        const uint32_t dist_next = chain_dict(mi);
+        if (mp >= 0) {  // a candidate in the record: as without a dictionary (the backward count stops at the record's start)
+          const uint32_t c32 = hc_rd32(src + mp);
+          if (hc_rd16(src + ilow + longest - 1) == hc_rd16(src + mp - look_back + longest - 1)) {
+            if (c32 == pattern) {
+              int back = 0;
+              if (look_back) {
+                const int mn = -((ip - ilow) < mp ? (ip - ilow) : mp);
+                while (back > mn && src[ip + back - 1] == src[mp + back - 1]) back--;
+              }
+              ml = 4 + count_fwd(src, ip + 4, mp + 4, ihigh) - back;
+              if (ml > longest) { longest = ml; mpos = mp + back; spos = ip + back; }
+            }
+          }
+        } else {
+          int back;
+          ml = dict_candidate(ip, ilow, ihigh, mp, pattern, back);
+          if (ml > longest) { longest = ml; mpos = mp + back; spos = ip + back; }
+        }
+        if (chain_swap && ml == longest) {
+          if (mi + (uint32_t)longest <= ip_idx) {
+            uint32_t dist_to_next = 1;
+            const int end = longest - 4 + 1;
+            int step = 1, accel = 1 << 4;
+            for (int pos = 0; pos < end; pos += step) {
+              const uint32_t cd = chain_dict(mi + (uint32_t)pos);
+              step = (accel++ >> 4);
+              if (cd > dist_to_next) { dist_to_next = cd; chain_pos = (uint32_t)pos; accel = 1 << 4; }
+            }
+            if (dist_to_next > 1) {
+              if (dist_to_next > mi) break;
+              mi -= dist_to_next;
+              continue;
+            }
+          }
+        }
+        if (pattern_analysis && dist_next == 1u && chain_pos == 0u) {
+          const uint32_t cand = mi - 1u;
+          if (repeat == 0) {
+            if (((pattern & 0xFFFFu) == (pattern >> 16)) & ((pattern & 0xFFu) == (pattern >> 24))) {
+              repeat = 2;
+              src_pat_len = count_pattern(src, ip + 4, ihigh, pattern) + 4;
+            } else {
+              repeat = 1;
+            }
+          }
+          if (repeat == 2 && cand >= lowest && protect_dict_end(cand)) {
+            const int cp = (int)(cand - first);
+            const bool ext = cp < 0;
+            // (a confirmed pattern is four equal bytes, so liblz4's rotation of it where a count crosses the dictionary's end is
+            // the identity)
+            if (hc_rd32((ext ? this->dend : src) + cp) == pattern) {
+              int fwd;
+              if (ext) {
+                fwd = count_pattern(this->dend, cp + 4, 0, pattern) + 4;
+                if (cp + fwd == 0) fwd += count_pattern(src, 0, ihigh, pattern);
+              } else {
+                fwd = count_pattern(src, cp + 4, ihigh, pattern) + 4;
+              }
+              int back;
+              if (ext) {
+                back = reverse_count_pattern(this->dend, cp, -this->K, pattern);
+              } else {
+                back = reverse_count_pattern(src, cp, 0, pattern);
+                if (cp - back == 0 && this->K > 0) back += reverse_count_pattern(this->dend, 0, -this->K, pattern);
+              }
+              {
+                const uint32_t far = cand - (uint32_t)back;
+                back = (int)(cand - (far > lowest ? far : lowest));
+              }
+              const int cur = back + fwd;
+              if (cur >= src_pat_len && fwd <= src_pat_len) {
+                const uint32_t nmi = cand + (uint32_t)fwd - (uint32_t)src_pat_len;
+                mi = protect_dict_end(nmi) ? nmi : first;
+              } else {
+                const uint32_t nmi = cand - (uint32_t)back;
+                if (!protect_dict_end(nmi)) {
+                  mi = first;
+                } else {
+                  mi = nmi;
+                  if (look_back == 0) {
+                    const int max_ml = cur < src_pat_len ? cur : src_pat_len;
+                    if (longest < max_ml) {
+                      if (ip_idx - mi > (uint32_t)HC_MAXD) break;
+                      longest = max_ml;
+                      mpos = (int)(mi - first);
+                      spos = ip;
+                    }
+                    const uint32_t d = chain_dict(mi);
+                    if (d > mi) break;
+                    mi -= d;
+                  }
+                }
+              }
+              continue;
+            }
+          }
+        }
+        mi -= chain_pos == 0u ? dist_next : chain_dict(mi + chain_pos);
+      }
+      return longest;
+    } else {
+      return longest;
+    }
+  }
 };
+using HcSearch = HcSearchT<false>;
 
 // ---------------------------------------------------------------------------------------------------
 // phase 2: the lazy parse + sequence emission (one wavefront per block)
@@ -266,15 +490,21 @@ struct HcSearch {
 // rule intact; then the last literals follow, against t itself, truncated to fit.  `consumed` is the input that the output covers.
 // Every store is exact (st8 / put_run / w.copy write the bytes of the sequence and nothing after them), so nothing at or past t is
 // touched.  FILL = false is what every other instantiation uses: the code it generates does not change.
+//
+// HcParse<W, false, DICT = true> parses a record behind a dictionary (LZ4_loadDictHC + LZ4_compress_HC_continue on a fresh stream):
+// the caller fills s.dend / s.ddelta_end / s.K after construction, and `delta` is HcBuild<W, true>'s.  A match position below 0
+// lies in the dictionary; the parse itself only ever subtracts it from a record position, which gives liblz4's offset.  DICT =
+// false is what every other instantiation uses: the code it generates does not change.
 // ---------------------------------------------------------------------------------------------------
-template <class W, bool FILL = false>
+template <class W, bool FILL = false, bool DICT = false>
 struct HcParse {
   using VU = typename W::VU;
   using VU64 = typename W::VU64;
   using VB = typename W::VB;
+  using Search = HcSearchT<DICT>;
 
   W& w;
-  HcSearch s;
+  Search s;
   const uint8_t* src;
   int n;
   uint8_t* dst;
@@ -291,6 +521,7 @@ struct HcParse {
   // start before ip) -- so the nodes that could improve are replayed in chain order against the running `longest`.
   // Repeated-byte patterns (level 9's pattern analysis may then jump along the chain) take the serial walk.
   LZ4HIP_DEV int wider_wave(int ip, int ilow, int ihigh, int longest, int& mpos, int& spos) {
+    if constexpr (DICT) return wider_wave_dict(ip, ilow, ihigh, longest, mpos, spos);
     const uint32_t pattern = hc_rd32(src + ip);
     const bool rep = ((pattern & 0xFFFFu) == (pattern >> 16)) & ((pattern & 0xFFu) == (pattern >> 24));
     if (s.pattern_analysis && rep) return s.wider(ip, ilow, ihigh, longest, mpos, spos);
@@ -324,7 +555,7 @@ struct HcParse {
           const int mn = -((int)look_back < (int)c ? look_back : (int)c);
           while (back > mn && sp[ip + back - 1] == sp[(int)c + back - 1]) back--;
         }
-        const int ml = 4 + HcSearch::count_fwd(sp, ip + 4, (int)c + 4, ihigh) - back;
+        const int ml = 4 + Search::count_fwd(sp, ip + 4, (int)c + 4, ihigh) - back;
         const uint32_t pre0 = (hc_rd16(sp + ilow + L0 - 1) == hc_rd16(sp + (int)c - look_back + L0 - 1)) ? 1u : 0u;
         return ((uint64_t)(uint32_t)ml << 32) | ((uint64_t)(uint32_t)(-back) << 1) | pre0;
       });
@@ -344,6 +575,75 @@ struct HcParse {
       }
     }
     return L;
+  }
+
+  // DICT: wider_wave with nodes on either side of the dictionary's end.  A node in the dictionary has no 2-byte pre-test.
+  LZ4HIP_DEV int wider_wave_dict(int ip, int ilow, int ihigh, int longest, int& mpos, int& spos) {
+    const uint32_t pattern = hc_rd32(src + ip);
+    const bool rep = ((pattern & 0xFFFFu) == (pattern >> 16)) & ((pattern & 0xFFu) == (pattern >> 24));
+    if (s.pattern_analysis && rep) return s.wider(ip, ilow, ihigh, longest, mpos, spos);
+    const uint32_t first = HC_BIAS + (uint32_t)dict_k();
+    const uint32_t ip_idx = (uint32_t)ip + first;
+    const uint32_t lowest = s.lowest_dict(ip);
+    const int look_back = ip - ilow;
+    const uint8_t* const sp = src;
+    const Search& sr = s;
+    int attempts = s.nb_searches;
+    uint32_t mi;
+    {
+      const uint32_t d0 = s.delta[ip];
+      mi = d0 ? ip_idx - d0 : 0u;
+    }
+    int L = longest;
+    const VU lane = w.lane();
+    while (mi >= lowest && attempts > 0) {
+      VU node = VU(0u);
+      uint32_t cnt = 0;
+      while (mi >= lowest && attempts > 0 && cnt < 64u) {
+        attempts--;
+        node = w.set_lane(node, (int)cnt, mi - first);
+        cnt++;
+        mi -= s.chain_dict(mi);
+      }
+      const int L0 = L;
+      const VU64 res = w.map_lanes64v(node, lane < cnt, [&](uint32_t, uint32_t cu, bool a) -> uint64_t {
+        if (!a) return 0ull;
+        const int c = (int)cu;
+        if (c < 0) {
+          int back;
+          const int ml = sr.dict_candidate(ip, ilow, ihigh, c, pattern, back);
+          return ml ? ((uint64_t)(uint32_t)ml << 32) | ((uint64_t)(uint32_t)(-back) << 1) | 1u : 0ull;
+        }
+        if (hc_rd32(sp + c) != pattern) return 0ull;
+        int back = 0;
+        if (look_back) {
+          const int mn = -(look_back < c ? look_back : c);
+          while (back > mn && sp[ip + back - 1] == sp[c + back - 1]) back--;
+        }
+        const int ml = 4 + Search::count_fwd(sp, ip + 4, c + 4, ihigh) - back;
+        const uint32_t pre0 = (hc_rd16(sp + ilow + L0 - 1) == hc_rd16(sp + c - look_back + L0 - 1)) ? 1u : 0u;
+        return ((uint64_t)(uint32_t)ml << 32) | ((uint64_t)(uint32_t)(-back) << 1) | pre0;
+      });
+      uint64_t imp = w.ballot(W::lo32(res >> 32) > (uint32_t)L);
+      while (imp) {
+        const int l = ctz64(imp);
+        imp &= imp - 1u;
+        const uint64_t r = w.bcast64(res, l);
+        const int ml = (int)(uint32_t)(r >> 32);
+        if (ml <= L) continue;
+        const int c = (int)w.bcast(node, l);
+        const bool pass = (c < 0 || L == L0) ? (r & 1u) != 0u : hc_rd16(sp + ilow + L - 1) == hc_rd16(sp + c - look_back + L - 1);
+        if (pass) {
+          const int back = -(int)((uint32_t)r >> 1);
+          L = ml; mpos = c + back; spos = ip + back;
+        }
+      }
+    }
+    return L;
+  }
+  LZ4HIP_DEV int dict_k() const {
+    if constexpr (DICT) return s.K;
+    else return 0;
   }
 
   LZ4HIP_DEV HcParse(W& w_, const uint8_t* src_, int n_, const uint16_t* delta, uint8_t* dst_, int cap_, int level)
@@ -399,7 +699,7 @@ struct HcParse {
   // returns the first position >= ip (and <= mflimit) whose plain search yields >= 4, or -1.
   LZ4HIP_DEV int first_match(int ip, int mflimit, int matchlimit, int& ml, int& ref) {
     while (ip <= mflimit) {
-      const HcSearch& sr = s;
+      const Search& sr = s;
       // Stage 1 (a filter, no effect on the result): a lane whose MOST RECENT chain node already matches 4 bytes has a match
       // of >= 4 for sure, so no lane behind the first such lane can be the answer -- and those are exactly the lanes with the
       // long walks (they sit inside the coming match, where every 4-gram has been seen before).  Only lanes up to it search.
@@ -408,6 +708,9 @@ struct HcParse {
         if (p > mflimit) return 0ull;
         const uint32_t d = sr.delta[p];
         if (d == 0u) return 0ull;
+        if constexpr (DICT) {   // (a link into the dictionary ends on a chain member: four bytes before its end at least)
+          if ((int)d > p) return hc_rd32(sr.dend + (p - (int)d)) == hc_rd32(sr.src + p) ? 1ull : 0ull;
+        }
         return hc_rd32(sr.src + p - (int)d) == hc_rd32(sr.src + p) ? 1ull : 0ull;   // (d <= 65535 and p - d >= 0 by construction)
       }) != VU64(0));
       const uint32_t lmax = quick ? (uint32_t)ctz64(quick) : 63u;
@@ -507,7 +810,9 @@ struct HcParse {
     int* const o_ml = opt + 2 * (HC_OPT_NUM + HC_OPT_TRAILING);     // opt[p].mlen (1 = literal)
     int* const o_ll = opt + 3 * (HC_OPT_NUM + HC_OPT_TRAILING);     // opt[p].litlen
     int ip = 0;
-    if (n >= 13) {
+    // (liblz4's optimal parser has no minimum block length of its own: a block of exactly 12 bytes searches at position 0, where
+    // only a dictionary can answer)
+    if (DICT ? n >= 12 : n >= 13) {
       while (ip <= mflimit) {
         const int llen = ip - anchor;
         int first_off = 0;

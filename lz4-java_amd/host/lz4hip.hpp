@@ -12,6 +12,9 @@
 //   LZ4HIPCompressor::compressWithDict, LZ4HIPBatch::compressDict
 //                                                   =  LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream per block: the writer
 //                                                      of the records decompressWithDict reads (no reference entry reaches it)
+//   LZ4HCHIPCompressor::compressWithDict, LZ4HIPBatch::compressHCDict
+//                                                   =  LZ4_loadDictHC + LZ4_compress_HC_continue on a fresh stream per block, at the
+//                                                      compressor's level (no reference entry reaches it)
 //   LZ4SafeDecompressor::decompressedLength, LZ4HIPBatch::decompressedLengths / decompressSafeSized
 //                                                   =  the decoded size without a destination; the batch twin of the allocating
 //                                                      overloads LZ4SafeDecompressor.java:117-137 without their worst-case buffer
@@ -129,11 +132,15 @@ class LZ4HCHIPCompressor final : public LZ4Compressor {
     srcLen = size;
     return result;
   }
+  // liblz4's LZ4_loadDictHC + LZ4_compress_HC_continue on a fresh stream at this compressor's level: src[srcOff, srcOff + srcLen)
+  // compressed alone against `dict` (which is not contiguous with src) into dest + destOff; returns the compressed size
+  // (lz4hip_compress_hc_dict)
+  int compressWithDict(const LZ4Dictionary& dict, const bytes& src, int srcOff, int srcLen, bytes& dest, int destOff, int maxDestLen) const;
 };
 
-// A shared dictionary for LZ4_decompress_safe_usingDict and LZ4_loadDict + LZ4_compress_fast_continue (lz4hip_dict_create): the handle
-// keeps the true length and the last 64 KB, resident on every initialised device (and the table LZ4_loadDict leaves, from its first
-// compress on a device).  Immutable: any number of threads may compress and decode against it; it must outlive the calls that use it.
+// A shared dictionary for LZ4_decompress_safe_usingDict, LZ4_loadDict + LZ4_compress_fast_continue and LZ4_loadDictHC +
+// LZ4_compress_HC_continue (lz4hip_dict_create): the handle keeps the true length and the last 64 KB, resident on every initialised
+// device (and the tables LZ4_loadDict / LZ4_loadDictHC leave, from its first fast / HC compress on a device).  Immutable: any number of threads may compress and decode against it; it must outlive the calls that use it.
 class LZ4Dictionary {
   lz4hip_dict* h_ = nullptr;
  public:
@@ -158,6 +165,15 @@ inline int LZ4HIPCompressor::compressWithDict(const LZ4Dictionary& dict, const b
   util::checkRange(dest, destOff, maxDestLen);
   const int result = libCheck(lz4hip_compress_fast_dict(src.data() + srcOff, srcLen, dest.data() + destOff, maxDestLen, dict.handle()));
   if (result <= 0) throw LZ4Exception("maxDestLen is too small");
+  return result;
+}
+
+inline int LZ4HCHIPCompressor::compressWithDict(const LZ4Dictionary& dict, const bytes& src, int srcOff, int srcLen, bytes& dest, int destOff,
+                                                int maxDestLen) const {
+  util::checkRange(src, srcOff, srcLen);
+  util::checkRange(dest, destOff, maxDestLen);
+  const int result = libCheck(lz4hip_compress_hc_dict(src.data() + srcOff, srcLen, dest.data() + destOff, maxDestLen, level_, dict.handle()));
+  if (result <= 0) throw LZ4Exception("");
   return result;
 }
 
@@ -232,6 +248,22 @@ struct LZ4HIPBatch {
     bytes one(1);                                 // (empty buffers still hand the library a pointer)
     status(lz4hip_compress_fast_dict_batch(src.empty() ? one.data() : src.data(), srcOff.data(), srcLen.data(), dest.empty() ? one.data() : dest.data(),
                                            destOff.data(), maxDestLen.data(), out.data(), (uint32_t)srcOff.size(), dict.handle()));
+    return out;
+  }
+  // LZ4_loadDictHC + LZ4_compress_HC_continue per block at HC level `level`, a fresh stream each, against one dictionary: block i is
+  // compressed into dest[destOff[i], + maxDestLen[i]); returns the compressed sizes, 0 where liblz4 returns 0
+  // (lz4hip_compress_hc_dict_batch)
+  static std::vector<int32_t> compressHCDict(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen, bytes& dest,
+                                             const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen, const LZ4Dictionary& dict,
+                                             int level = 9) {
+    checkBlocks(src, srcOff, srcLen, maxDestLen);
+    if (destOff.size() != srcOff.size()) throw std::invalid_argument("per-block arrays differ in length");
+    for (size_t i = 0; i < destOff.size(); i++)
+      if (destOff[i] > dest.size() || (uint64_t)maxDestLen[i] > dest.size() - destOff[i]) throw std::out_of_range("slot " + std::to_string(i));
+    std::vector<int32_t> out(srcOff.size(), 0);
+    bytes one(1);                                 // (empty buffers still hand the library a pointer)
+    status(lz4hip_compress_hc_dict_batch(src.empty() ? one.data() : src.data(), srcOff.data(), srcLen.data(), dest.empty() ? one.data() : dest.data(),
+                                         destOff.data(), maxDestLen.data(), out.data(), (uint32_t)srcOff.size(), level, dict.handle()));
     return out;
   }
   // LZ4_decompress_safe_usingDict per block against one dictionary: block i decodes into dest[destOff[i], + maxDestLen[i]); returns

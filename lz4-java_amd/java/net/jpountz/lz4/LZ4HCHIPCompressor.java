@@ -30,7 +30,8 @@ import java.nio.ByteBuffer;
  * LZ4Factory needs the INSTANCE field and the declared (int) constructor (LZ4Factory.java:193-202).
  *
  * {@code compressDestSize}: liblz4's {@code LZ4_compress_HC_destSize} at this compressor's level -- as much of the source as
- * fits in exactly {@code targetDestSize} bytes.
+ * fits in exactly {@code targetDestSize} bytes.  {@code compressWithDict}: liblz4's {@code LZ4_loadDictHC} +
+ * {@code LZ4_compress_HC_continue} on a fresh stream at this compressor's level.
  */
 final class LZ4HCHIPCompressor extends LZ4Compressor {
 
@@ -72,6 +73,42 @@ final class LZ4HCHIPCompressor extends LZ4Compressor {
       return result;
     }
     return LZ4Factory.safeInstance().highCompressor(compressionLevel).compress(src, srcOff, srcLen, dest, destOff, maxDestLen);
+  }
+
+  /**
+   * liblz4's {@code LZ4_loadDictHC} + {@code LZ4_compress_HC_continue} on a fresh stream at this compressor's level:
+   * {@code src[srcOff, srcOff+srcLen)} compressed alone against {@code dict} (which is not contiguous with {@code src}) into
+   * {@code dest[destOff, ...)}; returns the compressed size.  {@code LZ4HIPSafeDecompressor.decompressWithDict} reads it.  The argument
+   * checks and the exception are compress()'s.
+   */
+  public int compressWithDict(LZ4HIPDictionary dict, byte[] src, int srcOff, int srcLen, byte[] dest, int destOff, int maxDestLen) {
+    checkRange(src, srcOff, srcLen);
+    checkRange(dest, destOff, maxDestLen);
+    final int result = LZ4HIPJNI.LZ4HIP_compress_hc_dict(dict.handle(), compressionLevel, src, null, srcOff, srcLen, dest, null, destOff, maxDestLen);
+    if (result <= 0) {
+      throw result == 0 ? new LZ4Exception() : new LZ4Exception("liblz4hip: " + LZ4HIPJNI.lastError());
+    }
+    return result;
+  }
+
+  /** {@link #compressWithDict(LZ4HIPDictionary, byte[], int, int, byte[], int, int)} over heap or direct buffers (positions untouched). */
+  public int compressWithDict(LZ4HIPDictionary dict, ByteBuffer src, int srcOff, int srcLen, ByteBuffer dest, int destOff, int maxDestLen) {
+    checkNotReadOnly(dest);
+    checkRange(src, srcOff, srcLen);
+    checkRange(dest, destOff, maxDestLen);
+    if (!(src.hasArray() || src.isDirect()) || !(dest.hasArray() || dest.isDirect())) {
+      throw new IllegalArgumentException("compressWithDict needs heap-backed or direct ByteBuffers");
+    }
+    final byte[] srcArr = src.hasArray() ? src.array() : null;
+    final byte[] destArr = dest.hasArray() ? dest.array() : null;
+    final int so = srcArr != null ? srcOff + src.arrayOffset() : srcOff;
+    final int dof = destArr != null ? destOff + dest.arrayOffset() : destOff;
+    final int result = LZ4HIPJNI.LZ4HIP_compress_hc_dict(dict.handle(), compressionLevel, srcArr, srcArr == null ? src : null, so, srcLen,
+                                                         destArr, destArr == null ? dest : null, dof, maxDestLen);
+    if (result <= 0) {
+      throw result == 0 ? new LZ4Exception() : new LZ4Exception("liblz4hip: " + LZ4HIPJNI.lastError());
+    }
+    return result;
   }
 
   private int nativeDestSize(byte[] srcArr, ByteBuffer srcBuf, int srcOff, int srcLen, byte[] destArr, ByteBuffer destBuf, int destOff,

@@ -104,6 +104,21 @@ public final class LZ4HIPBatch {
   }
 
   /**
+   * liblz4's {@code LZ4_loadDictHC} + {@code LZ4_compress_HC_continue} per block at HC level {@code level}, a fresh stream each, against
+   * one shared dictionary (not contiguous with {@code src}): block i is compressed alone into the slot
+   * {@code dest[destOff[i], destOff[i]+destCap[i])}; {@link #decompressSafeDict} reads it.  outLen[i] &gt; 0: the compressed size;
+   * 0: liblz4 returns 0 (the slot is too small).
+   */
+  public static void compressHCDict(LZ4HIPDictionary dict, int level, ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest,
+      long[] destOff, int[] destCap, int[] outLen) {
+    check(src, dest, srcOff, srcLen, destOff, destCap, outLen);
+    final int rc = LZ4HIPJNI.LZ4HIP_batchCompressHCDict(dict.handle(), level, src, srcOff, srcLen, dest, destOff, destCap, outLen, srcOff.length);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /**
    * liblz4's {@code LZ4_decompress_safe_usingDict} per block against one shared dictionary (not contiguous with {@code dest}): block i,
    * compressed alone against {@code dict}, decodes into the slot {@code dest[destOff[i], destOff[i]+destCap[i])}.
    * outLen[i] &gt;= 0: the decoded size; &lt; 0: -(input position)-1.

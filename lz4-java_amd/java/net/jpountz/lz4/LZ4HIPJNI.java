@@ -110,6 +110,12 @@ enum LZ4HIPJNI {
    * a negative lz4hip_status (a null argument or a 0 handle: LZ4HIP_E_ARG). */
   static native int LZ4HIP_batchCompressDict(long dict, ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff,
                                              int[] destCap, int[] outLen, int nBlocks);
+  /* LZ4_loadDictHC + LZ4_compress_HC_continue on a fresh stream at HC level `level` against a dictionary handle: the conventions of
+   * LZ4HIP_compress_fast_dict and LZ4HIP_batchCompressDict */
+  static native int LZ4HIP_compress_hc_dict(long dict, int level, byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,
+                                            byte[] destArray, ByteBuffer destBuffer, int destOff, int maxDestLen);
+  static native int LZ4HIP_batchCompressHCDict(long dict, int level, ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff,
+                                               int[] destCap, int[] outLen, int nBlocks);
   /* LZ4_compress_HC_destSize per block at HC level `level`: the arguments and return conventions of LZ4HIP_batchDestSize */
   static native int LZ4HIP_batchHCDestSize(ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff, int[] targetSize,
                                            int[] outLen, int[] srcConsumed, int nBlocks, int level);

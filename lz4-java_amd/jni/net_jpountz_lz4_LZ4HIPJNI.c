@@ -408,6 +408,39 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchCompressDict(
   return rc;
 }
 
+/* LZ4_loadDictHC + LZ4_compress_HC_continue on a fresh stream at HC level `level` against a dictionary handle (lz4hip_compress_hc_dict):
+ * the conventions of LZ4HIP_compress_fast_dict */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1hc_1dict(JNIEnv* env, jclass cls, jlong dict, jint level, jbyteArray srcArray,
+    jobject srcBuffer, jint srcOff, jint srcLen, jbyteArray destArray, jobject destBuffer, jint destOff, jint maxDestLen) {
+  (void)cls;
+  region_t in, out;
+  if (region_in(env, srcArray, srcBuffer, srcOff, srcLen, 1, &in) != 0) { throw_OOM(env); return 0; }
+  if (region_in(env, destArray, destBuffer, destOff, maxDestLen, 0, &out) != 0) {
+    region_out(env, NULL, 0, 0, &in); /* release `in` too */
+    throw_OOM(env);
+    return 0;
+  }
+  const int result = lz4hip_compress_hc_dict(in.p, srcLen, out.p, maxDestLen, level, (const lz4hip_dict*)(intptr_t)dict);
+  region_out(env, NULL, 0, 0, &in);
+  const jint produced = (!LZ4HIP_IS_LIB_ERROR(result) && result > 0) ? result : 0;
+  if (region_out(env, destArray, destOff, produced, &out) != 0) { throw_OOM(env); return 0; }
+  return result;
+}
+
+/* the same over many blocks against one handle, direct buffers (lz4hip_compress_hc_dict_batch): the conventions of
+ * LZ4HIP_batchCompressDict */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchCompressHCDict(JNIEnv* env, jclass cls, jlong dict, jint level, jobject src,
+    jlongArray srcOff, jintArray srcLen, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen, jint n) {
+  (void)cls;
+  if (dict == 0) return LZ4HIP_E_ARG;
+  batch_args_t b = {NULL, NULL, 5, {{srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT}, {destCap, INTS, JNI_ABORT}, {outLen, INTS, 0}}};
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  rc = lz4hip_compress_hc_dict_batch(b.src, b.a[0].p, b.a[1].p, b.dst, b.a[2].p, b.a[3].p, b.a[4].p, (uint32_t)n, level, (const lz4hip_dict*)(intptr_t)dict);
+  batch_release(env, &b);
+  return rc;
+}
+
 /* The decoded-size query over many blocks, a direct source buffer (lz4hip_decompressed_size_batch): outLen[i] = what
  * LZ4_decompress_safe would return for block i with capacity destCap[i].  There is no destination buffer (batch_pin gets the source in
  * its place: its address is not used).  Returns 0 or a negative lz4hip_status; a NULL array or buffer is LZ4HIP_E_ARG */

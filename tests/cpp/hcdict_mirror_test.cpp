@@ -1,0 +1,71 @@
+// tests/cpp/hcdict_mirror_test.cpp -- exercises LZ4HCHIPCompressor::compressWithDict and LZ4HIPBatch::compressHCDict of the C++ host
+// mirror (lz4-java_amd/host/lz4hip.hpp).  Built and run by tests/test_hcdict_abi.py (argument checks, no device) and
+// tests/test_gpu_hcdict.py:
+//   hcdict_mirror_test <dictionary> <record> <out> <level>   writes the compressed bytes to <out> and prints their count
+// Exit code 0 = all good; with no GPU it must fail loudly (exit code 3).
+#include <cstdio>
+#include <cstdlib>
+#include <stdexcept>
+#include <string>
+#include "../../lz4-java_amd/host/lz4hip.hpp"
+
+using namespace net::jpountz;
+
+static bool slurp(const char* path, bytes& out) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  for (int c; (c = fgetc(f)) != EOF;) out.push_back((uint8_t)c);
+  fclose(f);
+  return true;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 5) { fprintf(stderr, "usage: hcdict_mirror_test <dictionary> <record> <out> <level>\n"); return 2; }
+  const int level = atoi(argv[4]);
+  bytes dictBytes, in;
+  if (!slurp(argv[1], dictBytes) || !slurp(argv[2], in)) return 2;
+  const int off = 3, doff = 5;                   // regions away from byte 0 of both vectors
+  bytes src(in.size() + off);
+  std::copy(in.begin(), in.end(), src.begin() + off);
+  const lz4::LZ4HCHIPCompressor c(level);
+  const int cap = c.maxCompressedLength((int)in.size());
+  bytes dst((size_t)cap + doff + 16, 0xEE);
+  try {   // the argument checks need no device
+    lz4::LZ4Dictionary dict(dictBytes);
+    bool threw = false;
+    try { (void)c.compressWithDict(dict, src, off, (int)in.size() + 1, dst, doff, cap); } catch (const std::out_of_range&) { threw = true; }
+    if (!threw) return 1;
+    threw = false;
+    try { (void)c.compressWithDict(dict, src, off, (int)in.size(), dst, doff, cap + 17); } catch (const std::out_of_range&) { threw = true; }
+    if (!threw) return 1;
+    threw = false;
+    try { (void)lz4::LZ4HIPBatch::compressHCDict(src, {(uint64_t)off}, {(int32_t)in.size(), 1}, dst, {0}, {cap}, dict, level); } catch (const std::invalid_argument&) { threw = true; }
+    if (!threw) return 1;
+    threw = false;
+    try { (void)lz4::LZ4HIPBatch::compressHCDict(src, {(uint64_t)off}, {(int32_t)in.size()}, dst, {(uint64_t)doff + 17}, {cap}, dict, level); } catch (const std::out_of_range&) { threw = true; }
+    if (!threw) return 1;
+    // the batch of two: the same record twice, the second slot one byte too small for anything but an empty record
+    bytes dst2((size_t)cap + 8 + 1, 0xEE);
+    const std::vector<int32_t> got = lz4::LZ4HIPBatch::compressHCDict(src, {(uint64_t)off, (uint64_t)off}, {(int32_t)in.size(), (int32_t)in.size()}, dst2,
+                                                                      {0, (uint64_t)cap + 8}, {cap, 1}, dict, level);
+    const int w = c.compressWithDict(dict, src, off, (int)in.size(), dst, doff, cap);
+    if (w <= 0 || w > cap) return 1;
+    if (got[0] != w || got[1] != (in.empty() ? 1 : 0)) { fprintf(stderr, "batch %d %d, single %d\n", got[0], got[1], w); return 1; }
+    for (int i = 0; i < w; i++)
+      if (dst2[(size_t)i] != dst[(size_t)(doff + i)]) { fprintf(stderr, "batch differs at %d\n", i); return 1; }
+    for (size_t i = (size_t)cap; i < (size_t)cap + 8; i++)
+      if (dst2[i] != 0xEE) { fprintf(stderr, "batch: byte %zu outside the slots changed\n", i); return 1; }
+    for (size_t i = 0; i < dst.size(); i++)
+      if ((i < (size_t)doff || i >= (size_t)(doff + cap)) && dst[i] != 0xEE) { fprintf(stderr, "byte %zu outside the slot changed\n", i); return 1; }
+    try { (void)c.compressWithDict(dict, src, off, (int)in.size(), dst, doff, w - 1); return 1; }
+    catch (const lz4::LZ4Exception& e) { if (std::string(e.what()) != "") throw; }   // (the HC compressor throws without a message)
+    FILE* o = fopen(argv[3], "wb");
+    if (!o || fwrite(dst.data() + doff, 1, (size_t)w, o) != (size_t)w) return 1;
+    fclose(o);
+    printf("%d\n", w);
+    return 0;
+  } catch (const lz4::LZ4Exception& e) {
+    fprintf(stderr, "%s\n", e.what());
+    return 3;
+  }
+}
