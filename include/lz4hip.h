@@ -58,7 +58,8 @@ typedef enum lz4hip_status {
   LZ4HIP_E_HIP = -2,        /* a HIP runtime call failed (see lz4hip_last_error) */
   LZ4HIP_E_ARG = -3,        /* null pointer, negative length, bad device index, ... */
   LZ4HIP_E_NOMEM = -4,      /* device or pinned-host allocation failed */
-  LZ4HIP_E_UNSUPPORTED = -5 /* e.g. HC level outside what this build implements */
+  LZ4HIP_E_UNSUPPORTED = -5, /* e.g. HC level outside what this build implements */
+  LZ4HIP_E_CHAIN_STOPPED = -6 /* never a call's status: a block behind its chain's first failed block (LZ4HIP_CHAIN_STOPPED) */
 } lz4hip_status;
 
 /* ---- lifecycle ----------------------------------------------------------------------------- */
@@ -166,7 +167,7 @@ int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src
  * were each compressed alone against one shared dictionary (LZ4_loadDict + LZ4_compress_fast_continue, LZ4_loadDictHC +
  * LZ4_compress_HC_continue), every one of them readable on its own.  The writers of such records are
  * lz4hip_compress_fast_dict* and lz4hip_compress_hc_dict* below; there is no dictionary form of the fast decoder, of the partial
- * decoder or of the size query, and no prefix mode (linked blocks).
+ * decoder or of the size query; linked blocks (liblz4's prefix mode) are lz4hip_decompress_safe_chain_batch*'s.
  *   - out_len[i] is liblz4's return value on valid AND malformed streams: the decoded size, or -(input position) - 1;
  *   - offsets: with dict_len < 65536 an offset is valid iff offset <= output position + dict_len; with dict_len >= 65536 no
  *     offset is rejected and only the dictionary's last 64 KB can be reached (liblz4's rule, checked where the safe decoder
@@ -194,6 +195,52 @@ void lz4hip_dict_free(lz4hip_dict* dict);        /* NULL is fine; no call on the
 int lz4hip_decompress_safe_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                       uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                       int32_t* out_len, uint32_t n_blocks, const lz4hip_dict* dict);
+/* DECODE CHAINS OF LINKED BLOCKS: the return values and bytes of liblz4 1.9.3's streaming decoder in its rolling-prefix mode.  A CHAIN
+ * is a run of blocks whose decoded forms lie back to back in one destination region; a match of block k may reach back into what the
+ * blocks before it decoded, and into history that was there before the chain's first block -- what LZ4_compress_fast_continue writes
+ * for a stream of messages and the `lz4` command line for a frame without block independence.  None of those blocks decodes on its
+ * own.  Chains are independent of each other; one launch decodes many of them.  For block k of chain c the result is
+ *     LZ4_setStreamDecode(sd, chain_dst - prefix_len, prefix_len);             (prefix_len may be 0)
+ *     r_k = LZ4_decompress_safe_continue(sd, src_k, chain_dst + sum(r_j, j < k), src_len_k, cap_k);
+ * with chain_dst = dst + chain_dst_off[c]: every destination is where the previous one ended (withSmallPrefix / withPrefix64k, never
+ * liblz4's external-dictionary or double-dictionary mode).
+ *   - chain c is the blocks [chain_first[c], chain_first[c + 1]) (n_chains + 1 entries, ascending from 0 to n_blocks); its region is
+ *     dst[chain_dst_off[c] .. + chain_dst_cap[c]), and chain_prefix_len[c] bytes of history lie in front of it in dst
+ *     (chain_prefix_len == NULL: no chain has any);
+ *   - out_len[i] is liblz4's r_k, on valid AND malformed streams: the decoded size, or -(input position) - 1.  The capacity liblz4
+ *     gets is cap_k = min(dst_cap[i], what is left of chain_dst_cap[c]) (and at most INT32_MAX - 65535: more than any block the
+ *     format allows can decode to); a negative src_len[i] or dst_cap[i] gives -1;
+ *   - offsets: with P = prefix_len + the bytes the chain has decoded so far, an offset is valid at output position p of the block iff
+ *     offset <= p + P; once P >= 65535 no offset is rejected (checked where the safe decoder checks offset > p, same error codes);
+ *   - a match that starts in the history obeys the ordinary end-of-block rules (unlike lz4hip_decompress_safe_dict*'s single rule),
+ *     and one that straddles the block's start is one contiguous, possibly overlapping copy;
+ *   - stored (NULL, or one byte per block): stored[i] != 0 marks a raw block, copied verbatim: out_len[i] = src_len[i], or -1 if it
+ *     does not fit in cap_k.  Later blocks may match into it;
+ *   - a block that decodes to 0 bytes changes nothing and the chain goes on; a first block without history is
+ *     lz4hip_decompress_safe exactly (which is also why there is no single-call form: a chain of one block IS that call);
+ *   - a block whose result is negative ENDS ITS CHAIN (liblz4 leaves the stream state untouched there, nothing meaningful can follow):
+ *     every block behind it gets LZ4HIP_CHAIN_STOPPED, a value no liblz4 result can equal.  chain_out_len[c] = the bytes the chain
+ *     decoded before it stopped;
+ *   - for the region [chain_dst_off[c] - min(prefix_len, 65535), chain_dst_off[c] + chain_dst_cap[c]): nothing outside it is read,
+ *     and nothing in front of chain_dst_off[c] is written.  Regions of different chains must not overlap one another's writes;
+ *   - LZ4HIP_E_ARG: a required pointer that is NULL (everything but stored and chain_prefix_len), a chain_first that is not ascending
+ *     from 0 to n_blocks, a negative chain_prefix_len[c] or one longer than chain_dst_off[c].  These are said before a device is looked
+ *     for; without a device a well-formed call is LZ4HIP_E_NO_DEVICE;
+ *   - one kernel, decode_chain_kernel: lane groups of 8 draw chains from a queue (chains differ in length) and walk their blocks in
+ *     order with the core's PREFIX switch -- the deep loop for streams of 2 KB and more, the pipelined loop and the exact tiers below;
+ *     the LDS-staged loops cannot see the history.  ONE CHAIN IS SERIAL BY CONSTRUCTION and runs on 8 lanes; the kernel waits for
+ *     no other wavefront or workgroup anywhere, and parallelism comes from the number of chains alone: thousands of chains fill the
+ *     device, a single chain is slower than one host thread (profiles/chain_decode_sweep.txt).  The decode_* knobs do not apply;
+ *   - the host form uploads the streams and, per chain, the last min(prefix_len, 65536) bytes of history from the caller's dst, and
+ *     brings back only the bytes decoded (runs less than 4 KB apart as one copy); it shards over the initialised devices at chain
+ *     boundaries;
+ *   - out of scope: linked-block compression and LZ4_saveDict, chains that start from a non-contiguous dictionary
+ *     (LZ4_decompress_safe_doubleDict), ring-buffer destinations that wrap, fast and partial decoders in chain form.              */
+int lz4hip_decompress_safe_chain_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                       const uint8_t* stored, const int32_t* dst_cap, const uint32_t* chain_first,
+                                       uint8_t* dst, const uint64_t* chain_dst_off, const uint64_t* chain_dst_cap,
+                                       const int32_t* chain_prefix_len, int32_t* out_len, uint64_t* chain_out_len,
+                                       uint32_t n_blocks, uint32_t n_chains);
 /* COMPRESS AGAINST A DICTIONARY: for every block i, on a fresh stream,
  *     LZ4_loadDict(s, dict, dict_len);  LZ4_compress_fast_continue(s, src_i, dst_i, src_len[i], dst_cap[i], 1)
  * of liblz4 1.9.3 with a dictionary that is NOT contiguous with the source (its external-dictionary mode): the return value and the
@@ -342,6 +389,15 @@ int lz4hip_decompress_safe_dict_batch_dev(const uint8_t* src, const uint64_t* sr
                                           uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                           int32_t* out_len, uint32_t n_blocks, const uint8_t* dict_dev, int dict_len,
                                           int device, void* stream);
+/* decode chains of linked blocks (see lz4hip_decompress_safe_chain_batch): device pointers -- every array, per block and per chain --,
+ * asynchronous.  The arrays cannot be looked at without waiting for the device, so only the NULL checks are LZ4HIP_E_ARG here; the
+ * kernel trusts nothing it reads from them: a chain's block range is cut to [0, n_blocks], a negative chain_prefix_len counts as 0 and
+ * one longer than chain_dst_off[c] is cut to it */
+int lz4hip_decompress_safe_chain_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                           const uint8_t* stored, const int32_t* dst_cap, const uint32_t* chain_first,
+                                           uint8_t* dst, const uint64_t* chain_dst_off, const uint64_t* chain_dst_cap,
+                                           const int32_t* chain_prefix_len, int32_t* out_len, uint64_t* chain_out_len,
+                                           uint32_t n_blocks, uint32_t n_chains, int device, void* stream);
 /* compress against a dictionary (see lz4hip_compress_fast_dict_batch): device pointers on `device`, and the HANDLE -- the compressor
  * needs its table image, not only the bytes; asynchronous, except that a handle's first compress on a device builds the image and
  * waits for `stream` once.  dict == NULL is LZ4HIP_E_ARG */
@@ -409,6 +465,8 @@ int lz4hip_xxh64_batch_dev(const uint8_t* buf, const uint64_t* off, const int32_
  * reported as INT32_MIN + (-status), which no codec result can equal: test LZ4HIP_IS_LIB_ERROR().  */
 #define LZ4HIP_LIB_ERROR(status) ((int)(INT32_MIN + (-(status))))
 #define LZ4HIP_IS_LIB_ERROR(ret) ((ret) < (int)(INT32_MIN + 64))
+/* out_len[i] of lz4hip_decompress_safe_chain_batch*: block i lies behind its chain's first failed block and was not decoded */
+#define LZ4HIP_CHAIN_STOPPED LZ4HIP_LIB_ERROR(LZ4HIP_E_CHAIN_STOPPED)
 int lz4hip_compress_fast(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap);
 int lz4hip_compress_fast_accel(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int acceleration);  /* LZ4_compress_fast */
 /* LZ4_compress_destSize: *src_size in = block size, out = input consumed; returns the bytes written.  A library failure returns

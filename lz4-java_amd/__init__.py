@@ -60,6 +60,9 @@ C_ABI = {
     "lz4hip_compress_fast_dict_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_void_p]),
     "lz4hip_decompress_safe_dict_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_void_p]),
     "lz4hip_compress_hc_dict_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_int, C.c_void_p]),
+    "lz4hip_decompress_safe_chain_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _u64p, C.c_void_p, _i32p, _u64p,
+                                                     C.c_uint32, C.c_uint32]),
+    "lz4hip_decompress_safe_chain_batch_dev": (C.c_int, [C.c_void_p] * 12 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
@@ -869,6 +872,51 @@ class LZ4HIPBatch:
         (lz4hip_decompress_safe_dict_batch)"""
         return cls._call("lz4hip_decompress_safe_dict_batch", src, srcOff, srcLen, dst, dstOff, dstCap, dictionary._handle())
 
+    CHAIN_STOPPED = _INT32_MIN + 6   # LZ4HIP_CHAIN_STOPPED: a block behind its chain's first failed block
+
+    @classmethod
+    def decompressSafeChain(cls, src, srcOff, srcLen, dstCap, chainFirst, dst, chainDstOff, chainDstCap, chainPrefixLen=None, stored=None):
+        """LZ4_decompress_safe_continue over chains of linked blocks (lz4hip_decompress_safe_chain_batch): chain c is the blocks
+        chainFirst[c] .. chainFirst[c + 1] - 1, decoded back to back into dst[chainDstOff[c]:+chainDstCap[c]] behind
+        chainPrefixLen[c] bytes of history that lie in front of it in dst (None: no history); dstCap[i] is the capacity liblz4 would be
+        given for block i, stored[i] (None: no block is) marks a raw block that is copied -> (outLen, chainOutLen): liblz4's return
+        value per block (CHAIN_STOPPED behind a chain's first negative one) and the bytes each chain decoded (lists, or int32 / uint64
+        arrays for numpy inputs)"""
+        n, nc = len(srcOff), len(chainDstOff)
+        if not (len(srcLen) == len(dstCap) == n) or (stored is not None and len(stored) != n):
+            raise ValueError("per-block arrays differ in length")
+        if len(chainFirst) != nc + 1 or len(chainDstCap) != nc or (chainPrefixLen is not None and len(chainPrefixLen) != nc):
+            raise ValueError("per-chain arrays differ in length")
+        cls._check_ranges(src, srcOff, srcLen)
+        for c in dstCap:
+            _check_length(c)
+        cls._check_ranges(dst, chainDstOff, chainDstCap)
+        prev = 0
+        for c in range(nc + 1):
+            if chainFirst[c] < prev or (c == 0 and chainFirst[0] != 0):
+                raise ValueError("chainFirst must ascend from 0 to the number of blocks")
+            prev = chainFirst[c]
+        if prev != n:
+            raise ValueError("chainFirst must ascend from 0 to the number of blocks")
+        if chainPrefixLen is not None:
+            for c in range(nc):
+                _check_length(chainPrefixLen[c])
+                if chainPrefixLen[c] > chainDstOff[c]:
+                    raise IndexError("history reaches in front of the buffer")
+        sp, sk = _ro_ptr(src)
+        dp, dk = _rw_ptr(dst)
+        out = (C.c_int32 * max(n, 1))()
+        cout = (C.c_uint64 * max(nc, 1))()
+        st = _arr(C.c_uint8, [1 if x else 0 for x in stored]) if stored is not None else None
+        pre = _arr(C.c_int32, chainPrefixLen) if chainPrefixLen is not None else None
+        _chk(lib().lz4hip_decompress_safe_chain_batch(sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), st, _arr(C.c_int32, dstCap),
+                                                      _arr(C.c_uint32, chainFirst), dp, _arr(C.c_uint64, chainDstOff), _arr(C.c_uint64, chainDstCap),
+                                                      pre, out, cout, n, nc))
+        if hasattr(srcOff, "dtype"):
+            import numpy as np
+            return np.frombuffer(out, dtype=np.int32, count=n).copy(), np.frombuffer(cout, dtype=np.uint64, count=nc).copy()
+        return list(out[:n]), list(cout[:nc])
+
     @classmethod
     def decompressSafePartial(cls, src, srcOff, srcLen, dst, dstOff, targetLen, dstCap):
         """LZ4_decompress_safe_partial per block: the first min(targetLen[i], dstCap[i]) bytes of block i into the slot
@@ -1120,6 +1168,20 @@ class DeviceBatch:
                                                          dst_off.data_ptr(), dst_cap.data_ptr(), out.data_ptr(), src_off.numel(),
                                                          dictionary.data_ptr() if dictionary.numel() else None, dictionary.numel(),
                                                          dev, st))
+
+    @classmethod
+    def decompress_safe_chain(cls, src, src_off, src_len, dst_cap, chain_first, dst, chain_dst_off, chain_dst_cap, out, chain_out,
+                              chain_prefix_len=None, stored=None):
+        """LZ4_decompress_safe_continue over chains of linked blocks (lz4hip_decompress_safe_chain_batch_dev): chain_first is an int32
+        tensor of chains + 1 entries (reinterpreted as uint32), chain_dst_off / chain_dst_cap / chain_out int64 tensors (as uint64),
+        chain_prefix_len an int32 tensor or None, stored a uint8 tensor or None; out = liblz4's return values per block
+        (LZ4HIPBatch.CHAIN_STOPPED behind a chain's first negative one), chain_out = the bytes each chain decoded"""
+        dev, st = cls._stream_dev(src)
+        _chk(lib().lz4hip_decompress_safe_chain_batch_dev(src.data_ptr(), src_off.data_ptr(), src_len.data_ptr(),
+                                                          stored.data_ptr() if stored is not None else None, dst_cap.data_ptr(),
+                                                          chain_first.data_ptr(), dst.data_ptr(), chain_dst_off.data_ptr(), chain_dst_cap.data_ptr(),
+                                                          chain_prefix_len.data_ptr() if chain_prefix_len is not None else None,
+                                                          out.data_ptr(), chain_out.data_ptr(), src_off.numel(), chain_dst_off.numel(), dev, st))
 
     @classmethod
     def decompress_safe_partial(cls, src, src_off, src_len, dst, dst_off, target_len, dst_cap, out):

@@ -81,9 +81,11 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // a handle: the compressor needs the dictionary's table image (dict_compress_state), not only its bytes
 // OP_COMPRESS_HC_DICT: LZ4_loadDictHC + LZ4_compress_HC_continue on a fresh stream per block, against a handle (BlockCall::dict):
 // OP_COMPRESS_HC's level and workspace, and the handle's HC image (dict_hc_state)
+// OP_DECOMPRESS_CHAIN: LZ4_decompress_safe_continue over chains of linked blocks: its arrays (per block AND per chain) are
+// BlockCall::chain, the seven arrays of the other operations are not used; the host path is chain_host_shard, not host_shard
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
-          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT };
-constexpr int OP_COUNT = OP_COMPRESS_HC_DICT + 1;   // (the last enumerator)
+          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN };
+constexpr int OP_COUNT = OP_DECOMPRESS_CHAIN + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
 constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT; }
@@ -107,7 +109,9 @@ struct BlockCall {
   const lz4hip_dict* dict = nullptr;    // OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT: the dictionary handle; OP_DECODE_DICT: the handle (host path, single calls) ...
   const uint8_t* dict_dev = nullptr;    // ... or, without a handle, the caller's dictionary in device memory and
   int32_t dict_len = 0;                 // its length
+  const lz4hip::ChainArgs* chain = nullptr;   // OP_DECOMPRESS_CHAIN: the call's arrays on the device
 };
+static_assert(lz4hip::kChainStopped == LZ4HIP_CHAIN_STOPPED, "the kernels' marker is the header's");
 // the handle's bytes on the CURRENT device (uploaded on first use where lz4hip_dict_create found the device not yet initialised):
 // one past the last byte, and the true length; a status (message set) on failure
 int dict_resident(const lz4hip_dict* d, const uint8_t** dict_end, int32_t* dict_len);
@@ -253,6 +257,15 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
       int32_t dict_len = c.dict_len;
       if (c.dict) { const int rc = dict_resident(c.dict, &dict_end, &dict_len); if (rc) return rc; }
       return lz4hip::launch_decompress_dict(a, dict_end, dict_len, st);
+    }
+    case OP_DECOMPRESS_CHAIN: {   // decode_chain_kernel draws chains from one queue word of scratch
+      if (!c.chain) return fail(LZ4HIP_E_ARG, kNullArg);
+      uint32_t* q = nullptr;
+      const hipError_t me = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
+      if (me != hipSuccess) return (int)me;
+      const int e = lz4hip::launch_decompress_chain(*c.chain, q, lz4hip::device_cus(), st);
+      (void)hipFreeAsync(q, st);
+      return e;
     }
     case OP_COMPRESS_HC:
     case OP_COMPRESS_HC_DICT:
@@ -699,6 +712,136 @@ int host_batch(const BlockCall& c, const uint8_t* src, const uint64_t* src_off, 
   return fan_out(n, 64u, [&](int ord, uint32_t b0, uint32_t b1, std::string* err) {
     return host_shard(c, ord, src, src_off, src_len, dst, dst_off, dst_cap, out, b0, b1, err);
   });
+}
+
+
+// ---- chains of linked blocks on the host-pointer path ----
+// One device's share [c0, c1) of a chain batch (h: the caller's HOST arrays).  Chains are staged a chunk at a time (64 MiB of streams
+// or 512 MiB of destination, one chain at least) through the first buffer set of a pooled pair: the streams and, per chain, the last
+// min(prefix_len, 65536) bytes of history from the caller's dst go up; the kernel runs; the results come back, and then only the bytes
+// each chain decoded (runs less than 4 KB apart travel as one copy).  On the device a chain's region is min(chain_dst_cap, the sum of
+// its blocks' capacities) bytes: a block's capacity is the smaller of its own and what is left, so nothing changes.
+int chain_host_shard(const lz4hip::ChainArgs& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+  auto bad = [&](const char* what, hipError_t e) {
+    char buf[512];
+    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+    *err = buf;
+    return e == hipErrorOutOfMemory ? (int)LZ4HIP_E_NOMEM : (int)LZ4HIP_E_HIP;
+  };
+  if (c1 == c0) return LZ4HIP_OK;
+  if (ord < 0 || ord >= 64) { *err = "device ordinal out of range"; return LZ4HIP_E_ARG; }
+  hipError_t e;
+  if ((e = hipSetDevice(ord)) != hipSuccess) return bad("hipSetDevice", e);
+  DevCtx& cx = g_ctx[ord];
+  SlotPair* pair = cx.acquire(&e);
+  if (!pair) return bad("stream/event creation", e);
+  struct Return { DevCtx& c; SlotPair* p; ~Return() { c.give_back(p); } } give_back_on_exit{cx, pair};
+  ChunkSlot& s = pair->slot[0];
+  const hipStream_t st = s.st;
+  auto al16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  auto slen_of = [&](uint32_t i) -> size_t { return h.src_len[i] > 0 ? (size_t)h.src_len[i] : 0; };
+  auto keep_of = [&](uint32_t c) -> size_t { const int32_t p = h.chain_prefix_len ? h.chain_prefix_len[c] : 0; return p > 65536 ? 65536u : (size_t)p; };
+  auto room_of = [&](uint32_t c) -> size_t {   // the chain's region on the device
+    uint64_t sum = 0;
+    for (uint32_t i = h.chain_first[c]; i < h.chain_first[c + 1]; i++) sum += h.dst_cap[i] > 0 ? (uint64_t)h.dst_cap[i] : 0u;
+    return (size_t)std::min<uint64_t>(sum, h.chain_dst_cap[c]);
+  };
+  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+  std::vector<uint64_t> so, cdo, room;
+  uint32_t c = c0;
+  while (c < c1) {
+    // the next chunk: chains [c, j), blocks [b0, b1)
+    uint32_t j = c;
+    size_t sb = 0, db = 0;
+    cdo.clear(); room.clear();
+    while (j < c1) {
+      size_t a = 0;
+      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) a += al16(slen_of(i));
+      const size_t r = room_of(j), d = al16(keep_of(j) + r);
+      if (j > c && (sb + a > chunk_src || db + d > chunk_dst)) break;
+      cdo.push_back(db + keep_of(j)); room.push_back(r);
+      sb += a; db += d; j++;
+    }
+    const uint32_t b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
+    so.resize(nb);
+    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { so[t] = o; o += al16(slen_of(b0 + t)); } }
+    // metadata: so[nb] u64 | chain_dst_off[nc] u64 | chain_dst_cap[nc] u64 | chain_out[nc] u64 | src_len[nb] | dst_cap[nb] | out[nb] |
+    // chain_first[nc + 1] | prefix[nc] | stored[nb] u8
+    const size_t o_cdo = 8u * nb, o_ccap = o_cdo + 8u * nc, o_cout = o_ccap + 8u * nc, o_slen = o_cout + 8u * nc, o_dcap = o_slen + 4u * nb,
+                 o_out = o_dcap + 4u * nb, o_first = o_out + 4u * nb, o_prefix = o_first + 4u * (nc + 1u), o_stored = o_prefix + 4u * nc,
+                 meta = o_stored + nb;
+    if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (e = s.h_dst.reserve(db + 64)) != hipSuccess || (e = s.h_meta.reserve(meta)) != hipSuccess ||
+        (e = s.d_src.reserve(sb + 64)) != hipSuccess || (e = s.d_dst.reserve(db + 64)) != hipSuccess || (e = s.d_meta.reserve(meta)) != hipSuccess)
+      return bad("staging allocation", e);
+    uint8_t* hs = (uint8_t*)s.h_src.p;
+    uint8_t* hd = (uint8_t*)s.h_dst.p;
+    uint8_t* hm = (uint8_t*)s.h_meta.p;
+    uint8_t* dm = (uint8_t*)s.d_meta.p;
+    uint8_t* dd = (uint8_t*)s.d_dst.p;
+    par_blocks(b0, b1, sb, [=, &so](uint32_t i) { if (h.src_len[i] > 0) memcpy(hs + so[i - b0], h.src + h.src_off[i], (size_t)h.src_len[i]); });
+    memcpy(hm, so.data(), 8u * nb);
+    memcpy(hm + o_cdo, cdo.data(), 8u * nc);
+    memcpy(hm + o_ccap, room.data(), 8u * nc);
+    memset(hm + o_cout, 0, 8u * nc);
+    memcpy(hm + o_slen, h.src_len + b0, 4u * nb);
+    memcpy(hm + o_dcap, h.dst_cap + b0, 4u * nb);
+    for (uint32_t t = 0; t <= nc; t++) { const uint32_t f = h.chain_first[c + t] - b0; memcpy(hm + o_first + 4u * t, &f, 4); }
+    for (uint32_t t = 0; t < nc; t++) { const int32_t k = (int32_t)keep_of(c + t); memcpy(hm + o_prefix + 4u * t, &k, 4); }
+    if (h.stored) memcpy(hm + o_stored, h.stored + b0, nb); else memset(hm + o_stored, 0, nb);
+    if (sb && (e = hipMemcpyAsync(s.d_src.p, hs, sb, hipMemcpyHostToDevice, st)) != hipSuccess) return bad("H2D src", e);
+    if ((e = hipMemcpyAsync(dm, hm, meta, hipMemcpyHostToDevice, st)) != hipSuccess) return bad("H2D meta", e);
+    for (uint32_t t = 0; t < nc; t++) {   // the histories
+      const size_t k = keep_of(c + t);
+      if (!k) continue;
+      memcpy(hd + cdo[t] - k, h.dst + h.chain_dst_off[c + t] - k, k);
+      if ((e = hipMemcpyAsync(dd + cdo[t] - k, hd + cdo[t] - k, k, hipMemcpyHostToDevice, st)) != hipSuccess) return bad("H2D history", e);
+    }
+    const lz4hip::ChainArgs a{(const uint8_t*)s.d_src.p, (const uint64_t*)dm, (const int32_t*)(dm + o_slen), (const uint8_t*)(dm + o_stored),
+                              (const int32_t*)(dm + o_dcap), (const uint32_t*)(dm + o_first), dd, (const uint64_t*)(dm + o_cdo),
+                              (const uint64_t*)(dm + o_ccap), (const int32_t*)(dm + o_prefix), (int32_t*)(dm + o_out), (uint64_t*)(dm + o_cout), nb, nc};
+    BlockCall call{OP_DECOMPRESS_CHAIN};
+    call.chain = &a;
+    const int le = launch_block(call, lz4hip::BatchArgs{}, st);
+    if (le < 0) { *err = lz4hip_last_error(); return le; }
+    if (le) return bad("kernel launch", (hipError_t)le);
+    if ((e = hipMemcpyAsync(hm + o_cout, dm + o_cout, o_first - o_cout, hipMemcpyDeviceToHost, st)) != hipSuccess) return bad("D2H out", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return bad("hipStreamSynchronize", e);
+    memcpy(h.out + b0, hm + o_out, 4u * nb);
+    memcpy(h.chain_out + c, hm + o_cout, 8u * nc);
+    // only the bytes decoded come back: runs of them less than 4 KB apart in one copy
+    size_t run0 = 0, run1 = 0;
+    auto flush = [&]() -> hipError_t { return run1 > run0 ? hipMemcpyAsync(hd + run0, dd + run0, run1 - run0, hipMemcpyDeviceToHost, st) : hipSuccess; };
+    for (uint32_t t = 0; t < nc; t++) {
+      const size_t n = (size_t)h.chain_out[c + t];
+      if (!n) continue;
+      if (run1 > run0 && cdo[t] <= run1 + 4096u) { run1 = cdo[t] + n; continue; }
+      if ((e = flush()) != hipSuccess) return bad("D2H dst", e);
+      run0 = cdo[t]; run1 = cdo[t] + n;
+    }
+    if ((e = flush()) != hipSuccess) return bad("D2H dst", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return bad("hipStreamSynchronize", e);
+    { const uint32_t base = c;
+      par_blocks(c, j, db, [=, &cdo](uint32_t t) { const size_t n = (size_t)h.chain_out[t]; if (n) memcpy(h.dst + h.chain_dst_off[t], hd + cdo[t - base], n); }); }
+    c = j;
+  }
+  return LZ4HIP_OK;
+}
+
+// the argument errors of a chain call that can be seen without a device; host: the arrays are the caller's host memory and are read
+const char* chain_arg_error(const lz4hip::ChainArgs& a, bool host) {
+  if (a.n_chains == 0 && a.n_blocks == 0) return nullptr;
+  if (!a.src || !a.src_off || !a.src_len || !a.dst_cap || !a.chain_first || !a.dst || !a.chain_dst_off || !a.chain_dst_cap || !a.out || !a.chain_out)
+    return kNullArg;
+  if (!host) return nullptr;
+  if (a.chain_first[0] != 0u || a.chain_first[a.n_chains] != a.n_blocks) return "chain_first must start at 0 and end at n_blocks";
+  for (uint32_t c = 0; c < a.n_chains; c++) {
+    if (a.chain_first[c] > a.chain_first[c + 1]) return "chain_first must be ascending";
+    if (a.chain_prefix_len) {
+      if (a.chain_prefix_len[c] < 0) return "negative chain_prefix_len";
+      if ((uint64_t)a.chain_prefix_len[c] > a.chain_dst_off[c]) return "chain_prefix_len reaches in front of dst";
+    }
+  }
+  return nullptr;
 }
 
 // hashes of one device's share [b0, b1) of a host batch: the same pinned, double-buffered staging as host_shard (chunks of
@@ -1496,6 +1639,19 @@ int lz4hip_decompress_safe_dict_batch(const uint8_t* src, const uint64_t* src_of
   c.dict = dict;
   return host_batch(c, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n);
 }
+int lz4hip_decompress_safe_chain_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, const uint8_t* stored,
+                                       const int32_t* dst_cap, const uint32_t* chain_first, uint8_t* dst, const uint64_t* chain_dst_off,
+                                       const uint64_t* chain_dst_cap, const int32_t* chain_prefix_len, int32_t* out_len, uint64_t* chain_out_len,
+                                       uint32_t n_blocks, uint32_t n_chains) {
+  const lz4hip::ChainArgs h{src, src_off, src_len, stored, dst_cap, chain_first, dst, chain_dst_off, chain_dst_cap, chain_prefix_len, out_len, chain_out_len,
+                            n_blocks, n_chains};
+  if (const char* why = chain_arg_error(h, true)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
+  int rc = ensure_init();
+  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (n_chains == 0) return LZ4HIP_OK;
+  // whole chains per device: a chain never leaves its lane group, let alone its device
+  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return chain_host_shard(h, ord, c0, c1, err); });
+}
 int lz4hip_compress_fast_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                     const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, const lz4hip_dict* dict) {
   int rc = ensure_init();
@@ -1581,6 +1737,17 @@ int lz4hip_decompress_safe_dict_batch_dev(const uint8_t* src, const uint64_t* sr
   c.dict_len = dict_len;
   return dev_batch(c, {src, src_off, src_len, dst, dst_off, dst_cap, out_len, n}, device, stream,
                    dict_len < 0 ? "negative dictionary length" : (dict_len > 0 && !dict_dev) ? kNullArg : nullptr);
+}
+int lz4hip_decompress_safe_chain_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, const uint8_t* stored,
+                                           const int32_t* dst_cap, const uint32_t* chain_first, uint8_t* dst, const uint64_t* chain_dst_off,
+                                           const uint64_t* chain_dst_cap, const int32_t* chain_prefix_len, int32_t* out_len, uint64_t* chain_out_len,
+                                           uint32_t n_blocks, uint32_t n_chains, int device, void* stream) {
+  const lz4hip::ChainArgs a{src, src_off, src_len, stored, dst_cap, chain_first, dst, chain_dst_off, chain_dst_cap, chain_prefix_len, out_len, chain_out_len,
+                            n_blocks, n_chains};
+  if (const char* why = chain_arg_error(a, false)) return fail(LZ4HIP_E_ARG, why);
+  BlockCall c{OP_DECOMPRESS_CHAIN};
+  c.chain = &a;
+  return on_device(device, n_chains == 0, nullptr, [&] { return launch_block(c, lz4hip::BatchArgs{}, (hipStream_t)stream); });
 }
 int lz4hip_compress_fast_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                         const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n,

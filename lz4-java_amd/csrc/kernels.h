@@ -107,6 +107,24 @@ int launch_decompress_partial(const BatchArgs& a, const int32_t* target, void* s
 // decoder, dict_end is not looked at); out[i] = liblz4's return value.  >= 40960 blocks: decode_dict_kernel<4, 0, true> (staged),
 // fewer: decode_dict_deep_kernel<8>; the decode knobs and the device-side route do not apply
 int launch_decompress_dict(const BatchArgs& a, const uint8_t* dict_end, int32_t dict_len, void* stream);
+// LZ4_decompress_safe_continue over chains of linked blocks (decode_chain.hip, lz4_decode_chain.h).  Chain c is the blocks
+// [chain_first[c], chain_first[c + 1]); their decoded forms lie back to back from dst + chain_dst_off[c] on, in at most chain_dst_cap[c]
+// bytes, behind chain_prefix_len[c] bytes of history (chain_prefix_len == nullptr: none).  Block i gets the capacity
+// min(dst_cap[i], what is left of the chain's, kChainBlockCapMax); stored (may be nullptr): stored[i] != 0 marks a raw block, copied
+// verbatim.  out[i] = liblz4's return value (a raw block: src_len[i], or -1 if it does not fit; a negative src_len / dst_cap: -1),
+// kChainStopped for the blocks behind a chain's first negative result; chain_out[c] = the bytes chain c decoded before it stopped.
+// The walk trusts nothing it reads from the arrays: a chain's block range is cut to [0, n_blocks] and its history to its offset into dst.
+struct ChainArgs {
+  const uint8_t* src; const uint64_t* src_off; const int32_t* src_len; const uint8_t* stored; const int32_t* dst_cap;
+  const uint32_t* chain_first;
+  uint8_t* dst; const uint64_t* chain_dst_off; const uint64_t* chain_dst_cap; const int32_t* chain_prefix_len;
+  int32_t* out; uint64_t* chain_out; uint32_t n_blocks, n_chains;
+};
+constexpr int32_t kChainStopped = INT32_MIN + 6;          // include/lz4hip.h LZ4HIP_CHAIN_STOPPED
+constexpr int32_t kChainBlockCapMax = INT32_MAX - 65535;  // (a block's capacity plus 65535 bytes of history is counted in an int)
+// decode_chain_kernel<8>: lane groups of 8 draw chains from the queue word q (one device uint32_t of scratch) and walk each chain's
+// blocks in order; no group waits for another anywhere.  n_cus = compute units of the device
+int launch_decompress_chain(const ChainArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
 // The decoded-size query: out[i] = the value LZ4_decompress_safe would return for block i with capacity a.dst_cap[i] (-1 where it or
 // src_len[i] is negative); a.dst and a.dst_off are ignored (may be nullptr) and no output buffer exists.  decode_size_kernel<4, 2048, true>:
 // a wavefront per block; no route word, no sampler, no decode knob

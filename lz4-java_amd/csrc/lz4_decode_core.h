@@ -111,17 +111,31 @@ template <class G> struct exact_length_sum<G, decltype((void)G::kExactLengthSum)
 //        Only [dict_end - min(dict_len, 65535), dict_end) is ever read, and never wildly.  The interior loops (plain, staged, pipelined,
 //        deep) take the matches that lie wholly in the dictionary as copies from a foreign pointer, like literals; a match that
 //        straddles the block's start goes to the exact code.  dict_len == 0 is the plain decoder.
-template <class Grp, bool SAFE, int PIPE = 0, bool STAGE = false, bool PARTIAL = false, bool DICT = false>
+// PREFIX (SAFE only, not PARTIAL, not DICT, not STAGE): one block of a chain of linked blocks -- LZ4_decompress_safe_continue of liblz4 1.9.3 in its
+//        rolling-prefix mode (withSmallPrefix / withPrefix64k): the `hist` bytes in front of dst are history (what the chain's earlier
+//        blocks decoded, and what lay in front of the chain), hist = min(real history, 65535).  A match may start in the history: an
+//        offset is valid at output position p iff offset <= p + hist, so with hist == 65535 no offset is rejected (liblz4 stops
+//        checking from 65535 bytes of prefix on).  History and block are ONE contiguous run of bytes, so the block is decoded as if
+//        it began `hist` bytes in front of dst with op = hist: every copy is the plain decoder's (a match that straddles the
+//        block's start is one overlapping copy), every end-of-block rule is the plain decoder's (they measure the distance to oend), the
+//        error codes keep their input positions, and a source in the history is an ordinary far source of the interior loops.  Only
+//        loops whose output lives in memory can see the history: plain, pipelined, deep.  Nothing in front of dst is written (a copy
+//        touches bytes behind its end only), nothing in front of dst - hist is read.  out_size + hist must not overflow an int.
+//        hist == 0 is the plain decoder.
+template <class Grp, bool SAFE, int PIPE = 0, bool STAGE = false, bool PARTIAL = false, bool DICT = false, bool PREFIX = false>
 LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* dst, int out_size, uint8_t* stage = nullptr,
-                            const uint8_t* dict_end = nullptr, int dict_len = 0) {
+                            const uint8_t* dict_end = nullptr, int dict_len = 0, int hist = 0) {
   static_assert(!PARTIAL || SAFE, "partial decoding is a safe-decoder mode");
   static_assert(!DICT || (SAFE && !PARTIAL && PIPE <= 2), "the dictionary decoder is a safe-decoder mode of the plain, staged, pipelined and deep loops");
+  static_assert(!PREFIX || (SAFE && !PARTIAL && !DICT && !STAGE && PIPE <= 2), "the linked-block decoder is a safe-decoder mode of the plain, pipelined and deep loops");
   // EXACT (a backend that sets kExactLengthSum: the decoded-size query, whose value is liblz4's on EVERY input): a length's extension bytes are summed
   // in 32 bits, as liblz4 sums them, to the run's end -- the error position of a run that cannot fit is then liblz4's.  The decoders stop such a run at
   // LZ4HIP_LEN_CAP instead: also an error, reported where the cap was passed.  WRAP: the 32-bit sum, PARTIAL's too
   constexpr bool EXACT = !PARTIAL && exact_length_sum<Grp>::value, WRAP = PARTIAL || EXACT;
-  int ip = 0, op = 0;
-  const int iend = src_size, oend = out_size;  // iend: real end (SAFE) / read bound (!SAFE)
+  const int obase = PREFIX ? hist : 0;          // (PREFIX: output positions count from the start of the history)
+  if constexpr (PREFIX) dst -= obase;
+  int ip = 0, op = obase;
+  const int iend = src_size, oend = out_size + obase;  // iend: real end (SAFE) / read bound (!SAFE)
   const int shortiend = iend - (SAFE ? 14 : 8) - 2;
   const int shortoend = oend - (SAFE ? 14 : 8) - 18;
   uint32_t token;
@@ -592,7 +606,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
     g.copy_match(dst, (uint32_t)op, (uint32_t)offset, (uint32_t)length, false);
     op = cpy;
   }
-  return SAFE ? op : ip;
+  return SAFE ? op - obase : ip;
 output_error:
   return -ip - 1;
 #undef LZ4HIP_IN_DICT

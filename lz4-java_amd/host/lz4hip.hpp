@@ -9,6 +9,8 @@
 //   LZ4Dictionary, LZ4SafeDecompressor::decompressWithDict, LZ4HIPBatch::decompressSafeDict
 //                                                   =  LZ4_decompress_safe_usingDict of liblz4's main API against a dictionary that is not
 //                                                      contiguous with the destination (no reference entry reaches it)
+//   LZ4HIPBatch::decompressSafeChain                =  LZ4_decompress_safe_continue over chains of linked blocks (liblz4's rolling-prefix
+//                                                      mode; no reference entry reaches it)
 //   LZ4HIPCompressor::compressWithDict, LZ4HIPBatch::compressDict
 //                                                   =  LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream per block: the writer
 //                                                      of the records decompressWithDict reads (no reference entry reaches it)
@@ -279,6 +281,43 @@ struct LZ4HIPBatch {
     status(lz4hip_decompress_safe_dict_batch(src.data(), srcOff.data(), srcLen.data(), dest.empty() ? one.data() : dest.data(), destOff.data(),
                                              maxDestLen.data(), out.data(), (uint32_t)srcOff.size(), dict.handle()));
     return out;
+  }
+  // LZ4_decompress_safe_continue over chains of linked blocks (lz4hip_decompress_safe_chain_batch): chain c is the blocks
+  // [chainFirst[c], chainFirst[c + 1]), decoded back to back into dest[chainDestOff[c], + chainDestCap[c]) behind chainPrefixLen[c] bytes of
+  // history that lie in front of it in dest (an empty vector: no history); maxDestLen[i] is the capacity liblz4 would be given for block
+  // i; stored[i] != 0 (an empty vector: no block is) marks a raw block that is copied.  lengths[i] = liblz4's return value,
+  // LZ4HIP_CHAIN_STOPPED behind a chain's first negative one; chainLengths[c] = the bytes chain c decoded
+  struct Chains { std::vector<int32_t> lengths; std::vector<uint64_t> chainLengths; };
+  static Chains decompressSafeChain(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen,
+                                    const std::vector<int32_t>& maxDestLen, const std::vector<uint32_t>& chainFirst, bytes& dest,
+                                    const std::vector<uint64_t>& chainDestOff, const std::vector<uint64_t>& chainDestCap,
+                                    const std::vector<int32_t>& chainPrefixLen = {}, const std::vector<uint8_t>& stored = {}) {
+    checkBlocks(src, srcOff, srcLen, maxDestLen);
+    const size_t n = srcOff.size(), nc = chainDestOff.size();
+    if (!stored.empty() && stored.size() != n) throw std::invalid_argument("per-block arrays differ in length");
+    if (chainFirst.size() != nc + 1 || chainDestCap.size() != nc || (!chainPrefixLen.empty() && chainPrefixLen.size() != nc))
+      throw std::invalid_argument("per-chain arrays differ in length");
+    if (chainFirst[0] != 0 || chainFirst[nc] != n) throw std::invalid_argument("chainFirst must ascend from 0 to the number of blocks");
+    for (size_t c = 0; c < nc; c++) {
+      if (chainFirst[c] > chainFirst[c + 1]) throw std::invalid_argument("chainFirst must ascend from 0 to the number of blocks");
+      if (chainDestOff[c] > dest.size() || chainDestCap[c] > dest.size() - chainDestOff[c]) throw std::out_of_range("chain " + std::to_string(c));
+      if (!chainPrefixLen.empty()) {
+        if (chainPrefixLen[c] < 0) throw std::invalid_argument("lengths must be >= 0");
+        if ((uint64_t)chainPrefixLen[c] > chainDestOff[c]) throw std::out_of_range("history of chain " + std::to_string(c));
+      }
+    }
+    Chains r;
+    r.lengths.assign(n, 0);
+    r.chainLengths.assign(nc, 0);
+    bytes one(1);                                 // (an empty destination still hands the library a pointer)
+    int32_t none = 0;
+    uint64_t none64 = 0;
+    status(lz4hip_decompress_safe_chain_batch(src.empty() ? one.data() : src.data(), n ? srcOff.data() : &none64, n ? srcLen.data() : &none,
+                                              stored.empty() ? nullptr : stored.data(), n ? maxDestLen.data() : &none, chainFirst.data(),
+                                              dest.empty() ? one.data() : dest.data(), nc ? chainDestOff.data() : &none64, nc ? chainDestCap.data() : &none64,
+                                              chainPrefixLen.empty() ? nullptr : chainPrefixLen.data(), n ? r.lengths.data() : &none,
+                                              nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
+    return r;
   }
   static std::vector<int32_t> decompressedLengths(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen,
                                                   const std::vector<int32_t>& maxDestLen) {

@@ -43,6 +43,19 @@ struct BatchEngine {
     if (!so.empty()) chk(lz4hip_decompress_safe_batch(src, so.data(), sl.data(), dst, d_o.data(), dc.data(), out.data(), (uint32_t)so.size()));
     return out;
   }
+  // one chain of linked blocks (lz4hip_decompress_safe_chain_batch): the blocks decode back to back into dst[dstOff, + dstCap) behind
+  // `prefix` bytes of history that lie in front of it; stored[i] != 0: a raw block, copied.  Returns liblz4's values per block
+  std::vector<int32_t> decompressSafeChain(const uint8_t* src, const std::vector<uint64_t>& so, const std::vector<int32_t>& sl,
+                                           const std::vector<uint8_t>& stored, const std::vector<int32_t>& dc, uint8_t* dst, uint64_t dstOff,
+                                           uint64_t dstCap, int32_t prefix) const {
+    std::vector<int32_t> out(so.size());
+    if (so.empty()) return out;
+    const uint32_t first[2] = {0u, (uint32_t)so.size()};
+    uint64_t done = 0;
+    chk(lz4hip_decompress_safe_chain_batch(src, so.data(), sl.data(), stored.data(), dc.data(), first, dst, &dstOff, &dstCap, &prefix, out.data(), &done,
+                                           (uint32_t)so.size(), 1u));
+    return out;
+  }
   std::vector<int32_t> decompressFast(const uint8_t* src, const std::vector<uint64_t>& so, const std::vector<int32_t>& scap, uint8_t* dst,
                                       const std::vector<uint64_t>& d_o, const std::vector<int32_t>& dl) const {
     std::vector<int32_t> out(so.size());
@@ -184,13 +197,14 @@ constexpr const char* CLOSED_STREAM = "The stream is already closed";
 
 struct FLG {  // LZ4FrameOutputStream.java:296-372
   int version, bits;
-  FLG(int v, int b) : version(v), bits(b & 0x3F) {
+  // allowDependent: a reader that decodes linked blocks (LZ4FrameInputStream, linkedBlocks = true): the one way past that check
+  FLG(int v, int b, bool allowDependent = false) : version(v), bits(b & 0x3F) {
     if (isEnabled(RESERVED_0)) throw std::runtime_error("Reserved0 field must be 0");
     if (isEnabled(RESERVED_1)) throw std::runtime_error("Reserved1 field must be 0");
-    if (!isEnabled(BLOCK_INDEPENDENCE)) throw std::runtime_error("Dependent block stream is unsupported (BLOCK_INDEPENDENCE must be set)");
+    if (!isEnabled(BLOCK_INDEPENDENCE) && !allowDependent) throw std::runtime_error("Dependent block stream is unsupported (BLOCK_INDEPENDENCE must be set)");
     if (version != 1) throw std::runtime_error("Version " + std::to_string(version) + " is unsupported");
   }
-  static FLG fromByte(uint8_t f) { return FLG((f >> 6) & 3, f & 0x3F); }
+  static FLG fromByte(uint8_t f, bool allowDependent = false) { return FLG((f >> 6) & 3, f & 0x3F, allowDependent); }
   uint8_t toByte() const { return (uint8_t)(bits | ((version & 3) << 6)); }
   bool isEnabled(int bit) const { return (bits >> bit) & 1; }
 };
@@ -294,8 +308,13 @@ class LZ4FrameOutputStream {
 
 class LZ4FrameInputStream {
  public:
-  explicit LZ4FrameInputStream(std::istream& in, bool readSingleFrame = false, BatchEngine engine = BatchEngine(), size_t batchBlocks = 64)
-      : r_(in), e_(engine), single_(readSingleFrame), batch_(batchBlocks ? batchBlocks : 1) {}
+  // linkedBlocks = true (not in the reference, whose reader refuses such frames; the default refuses them too): a frame without
+  // BLOCK_INDEPENDENCE -- what the `lz4` command line writes by default -- is read as well: its size words are walked on the host,
+  // batchBlocks at a time, and each batch is decoded as ONE chain of linked blocks whose history is the last 64 KB this reader decoded
+  // of the frame.  Checks, their order and the messages stay as they are; frames with BLOCK_INDEPENDENCE take the other paths
+  explicit LZ4FrameInputStream(std::istream& in, bool readSingleFrame = false, BatchEngine engine = BatchEngine(), size_t batchBlocks = 64,
+                               bool linkedBlocks = false)
+      : r_(in), e_(engine), single_(readSingleFrame), batch_(batchBlocks ? batchBlocks : 1), linkedBlocks_(linkedBlocks) {}
   // up to n bytes; 0 at the end of the stream
   size_t read(uint8_t* p, size_t n) {
     if (n == 0 || !fill()) return 0;
@@ -345,7 +364,9 @@ class LZ4FrameInputStream {
   void readHeader() {  // :180-224
     bytes header(2);
     readFully(header.data(), 2);
-    flgBits_ = frame::FLG::fromByte(header[0]).bits;
+    flgBits_ = frame::FLG::fromByte(header[0], linkedBlocks_).bits;
+    linked_ = !bit(frame::BLOCK_INDEPENDENCE);
+    history_.clear();
     maxBlockSize_ = frame::BD::fromByte(header[1]).getBlockMaximumSize();
     if ((flgBits_ >> frame::CONTENT_SIZE) & 1) {
       uint8_t cs[8];
@@ -412,7 +433,7 @@ class LZ4FrameInputStream {
   void readBlocks() {  // readBlock (:258-322) for up to batch_ blocks
     // (the device path takes a whole chunk from the stream: with readSingleFrame the caller reads on behind the frame, so it needs a
     // stream that can take the surplus back; any other gets the host walk, which consumes exactly the frame)
-    if (!e_.hostWalk && (!single_ || r_.seekable())) {
+    if (!linked_ && !e_.hostWalk && (!single_ || r_.seekable())) {
       readBlocksDevice();
       if (single_ && frameFinished_) r_.giveBack();
       return;
@@ -449,6 +470,29 @@ class LZ4FrameInputStream {
       if (bc) {
         const std::vector<uint32_t> h = e_.xxh32(src.data(), offs, lens, 0);
         for (size_t i = 0; i < n; i++) if (h[i] != blocks[i].stored) { bad = i; badExc = frame::BLOCK_HASH_MISMATCH; break; }
+      }
+      if (linked_) {   // one chain: the blocks decode back to back behind the history; a stored block is copied by the same call
+        const size_t hist = history_.size();
+        bytes dst(hist + bad * (size_t)maxBlockSize_ + 1u);
+        std::copy(history_.begin(), history_.end(), dst.begin());
+        std::vector<uint8_t> raw(bad);
+        for (size_t i = 0; i < bad; i++) raw[i] = blocks[i].compressed ? 0 : 1;
+        offs.resize(bad); lens.resize(bad);
+        const std::vector<int32_t> res = e_.decompressSafeChain(src.data(), offs, lens, raw, std::vector<int32_t>(bad, maxBlockSize_), dst.data(), hist,
+                                                                bad * (uint64_t)maxBlockSize_, (int32_t)hist);
+        size_t at = hist;
+        for (size_t i = 0; i < bad; i++) {
+          if (res[i] < 0) { badExc = "Error decoding offset " + std::to_string(-res[i]) + " of input buffer"; break; }   // (LZ4JNISafeDecompressor.java:39-41)
+          at += (size_t)res[i];
+        }
+        ready_.insert(ready_.end(), dst.begin() + (std::ptrdiff_t)hist, dst.begin() + (std::ptrdiff_t)at);
+        totalContentSize_ += (int64_t)(at - hist);
+        if (bit(frame::CONTENT_CHECKSUM) && at > hist) content().update(dst.data() + hist, at - hist);  // one update per batch
+        history_.assign(dst.begin() + (std::ptrdiff_t)(at > 65536u ? at - 65536u : 0u), dst.begin() + (std::ptrdiff_t)at);
+        if (!badExc.empty()) { pending_ = badExc; return; }
+        if (!exc.empty()) { pending_ = exc; return; }
+        if (endMark) this->endMark();
+        return;
       }
       std::vector<size_t> cidx;
       for (size_t i = 0; i < bad; i++) if (blocks[i].compressed) cidx.push_back(i);
@@ -496,6 +540,8 @@ class LZ4FrameInputStream {
   BatchEngine e_;
   bool single_;
   size_t batch_;
+  bool linkedBlocks_ = false, linked_ = false;   // the caller's opt-in; the current frame has no BLOCK_INDEPENDENCE
+  bytes history_;                                // linked blocks: the last 64 KB decoded of the current frame
   bool headerRead_ = false, frameFinished_ = true, inFrame_ = false;
   int flgBits_ = 0, maxBlockSize_ = 0;
   int64_t expectedContentSize_ = -1, totalContentSize_ = 0;

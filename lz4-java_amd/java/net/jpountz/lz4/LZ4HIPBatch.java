@@ -132,6 +132,61 @@ public final class LZ4HIPBatch {
     }
   }
 
+  /** {@code outLen[i]} of {@link #decompressSafeChain}: block i lies behind its chain's first failed block and was not decoded. */
+  public static final int CHAIN_STOPPED = Integer.MIN_VALUE + 6;
+
+  /**
+   * liblz4's {@code LZ4_decompress_safe_continue} over chains of linked blocks (its rolling-prefix mode): chain c is the blocks
+   * {@code chainFirst[c] .. chainFirst[c + 1] - 1}, decoded back to back into {@code dest[chainDestOff[c], chainDestOff[c]+chainDestCap[c])}
+   * behind {@code chainPrefixLen[c]} bytes of history that lie in front of it in {@code dest} ({@code null}: no history).
+   * {@code destCap[i]} is the capacity liblz4 would be given for block i; {@code stored} ({@code null}, or != 0 per block) marks raw
+   * blocks, which are copied.  outLen[i] &gt;= 0: the decoded size; &lt; 0: -(input position)-1, which ends the chain -- the blocks behind
+   * it get {@link #CHAIN_STOPPED}.  chainOutLen[c]: the bytes chain c decoded.
+   */
+  public static void decompressSafeChain(ByteBuffer src, long[] srcOff, int[] srcLen, int[] stored, int[] destCap, int[] chainFirst,
+      ByteBuffer dest, long[] chainDestOff, long[] chainDestCap, int[] chainPrefixLen, int[] outLen, long[] chainOutLen) {
+    final int n = srcOff.length, nc = chainDestOff.length;
+    if (srcLen.length != n || destCap.length != n || outLen.length != n || (stored != null && stored.length != n)) {
+      throw new IllegalArgumentException("per-block arrays differ in length");
+    }
+    if (chainFirst.length != nc + 1 || chainDestCap.length != nc || chainOutLen.length != nc || (chainPrefixLen != null && chainPrefixLen.length != nc)) {
+      throw new IllegalArgumentException("per-chain arrays differ in length");
+    }
+    if (!src.isDirect() || !dest.isDirect()) {
+      throw new IllegalArgumentException("direct buffers required");
+    }
+    if (dest.isReadOnly()) {
+      throw new java.nio.ReadOnlyBufferException();
+    }
+    for (int i = 0; i < n; i++) {
+      if (srcLen[i] < 0 || destCap[i] < 0) {
+        throw new IllegalArgumentException("lengths must be >= 0");
+      }
+      if (srcOff[i] < 0 || srcOff[i] + srcLen[i] > src.capacity()) {
+        throw new ArrayIndexOutOfBoundsException("block " + i);
+      }
+    }
+    if (chainFirst[0] != 0 || chainFirst[nc] != n) {
+      throw new IllegalArgumentException("chainFirst must ascend from 0 to the number of blocks");
+    }
+    for (int c = 0; c < nc; c++) {
+      if (chainFirst[c] > chainFirst[c + 1]) {
+        throw new IllegalArgumentException("chainFirst must ascend from 0 to the number of blocks");
+      }
+      if (chainDestOff[c] < 0 || chainDestCap[c] < 0 || chainDestOff[c] + chainDestCap[c] > dest.capacity()) {
+        throw new ArrayIndexOutOfBoundsException("chain " + c);
+      }
+      if (chainPrefixLen != null && (chainPrefixLen[c] < 0 || chainPrefixLen[c] > chainDestOff[c])) {
+        throw new ArrayIndexOutOfBoundsException("history of chain " + c);
+      }
+    }
+    final int rc = LZ4HIPJNI.LZ4HIP_batchSafeChain(src, srcOff, srcLen, stored, destCap, chainFirst, dest, chainDestOff, chainDestCap, chainPrefixLen,
+        outLen, chainOutLen, n, nc);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
   /**
    * liblz4's {@code LZ4_decompress_safe_partial} per block: the first {@code min(targetLen[i], destCap[i])} bytes of block i (fewer
    * where a cut stream ends first) into the slot {@code dest[destOff[i], destOff[i]+destCap[i])}, nothing past

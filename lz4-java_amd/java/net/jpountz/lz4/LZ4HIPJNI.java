@@ -102,6 +102,13 @@ enum LZ4HIPJNI {
    * null argument or a 0 handle: LZ4HIP_E_ARG). */
   static native int LZ4HIP_batchSafeDict(long dict, ByteBuffer src, long[] srcOff, int[] srcLen, ByteBuffer dest, long[] destOff,
                                          int[] destCap, int[] outLen, int nBlocks);
+  /* LZ4_decompress_safe_continue over chains of linked blocks, DIRECT buffers: chain c is the blocks chainFirst[c] .. chainFirst[c + 1] - 1,
+   * decoded back to back into dest[chainDestOff[c], + chainDestCap[c]) behind chainPrefixLen[c] bytes of history; stored (null, or != 0 per
+   * raw block) and chainPrefixLen may be null.  outLen = liblz4's return values (LZ4HIPBatch.CHAIN_STOPPED behind a chain's first negative
+   * one), chainOutLen = the bytes each chain decoded.  Returns 0 or a negative lz4hip_status (a null required argument: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchSafeChain(ByteBuffer src, long[] srcOff, int[] srcLen, int[] stored, int[] destCap, int[] chainFirst,
+                                          ByteBuffer dest, long[] chainDestOff, long[] chainDestCap, int[] chainPrefixLen, int[] outLen,
+                                          long[] chainOutLen, int nBlocks, int nChains);
   /* LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream against a dictionary handle: the compressed size, 0 (maxDestLen too
    * small) or a library failure as LZ4HIP_compress_fast; same NULL / pinning rules */
   static native int LZ4HIP_compress_fast_dict(long dict, byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,

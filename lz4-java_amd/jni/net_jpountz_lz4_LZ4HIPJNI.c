@@ -219,12 +219,12 @@ typedef struct {
   jint mode;    /* how it is released: JNI_ABORT for an input, 0 for an output (copied back) */
   void* p;      /* its elements while pinned */
 } batch_array_t;
-/* The arguments of a batch native made addressable: the two direct buffers and up to six descriptor arrays. */
+/* The arguments of a batch native made addressable: the two direct buffers and up to ten descriptor arrays. */
 typedef struct {
   const uint8_t* src;
   uint8_t* dst;
   int n_arrays;
-  batch_array_t a[6];
+  batch_array_t a[10];
 } batch_args_t;
 
 static void batch_release(JNIEnv* env, batch_args_t* b) {
@@ -371,6 +371,37 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafeDict(JNIE
   jint rc = batch_pin(env, src, dest, &b);
   if (rc != 0) return rc;
   rc = lz4hip_decompress_safe_dict_batch(b.src, b.a[0].p, b.a[1].p, b.dst, b.a[2].p, b.a[3].p, b.a[4].p, (uint32_t)n, (const lz4hip_dict*)(intptr_t)dict);
+  batch_release(env, &b);
+  return rc;
+}
+
+/* LZ4_decompress_safe_continue over chains of linked blocks, direct buffers (lz4hip_decompress_safe_chain_batch): chain c is the blocks
+ * chainFirst[c] .. chainFirst[c + 1] - 1, decoded back to back into dest[chainDestOff[c], + chainDestCap[c]) behind chainPrefixLen[c]
+ * bytes of history (chainPrefixLen may be NULL: none); stored may be NULL, else stored[i] != 0 marks a raw block; outLen[i] = liblz4's
+ * return value (LZ4HIP_CHAIN_STOPPED behind a chain's first negative one), chainOutLen[c] = the bytes the chain decoded.  Returns 0 or a
+ * negative lz4hip_status; a NULL required array or buffer is LZ4HIP_E_ARG */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafeChain(JNIEnv* env, jclass cls, jobject src, jlongArray srcOff, jintArray srcLen,
+    jintArray stored, jintArray destCap, jintArray chainFirst, jobject dest, jlongArray chainDestOff, jlongArray chainDestCap, jintArray chainPrefixLen,
+    jintArray outLen, jlongArray chainOutLen, jint nBlocks, jint nChains) {
+  (void)cls;
+  if (nBlocks < 0 || nChains < 0) return LZ4HIP_E_ARG;
+  batch_args_t b = {NULL, NULL, 8, {{srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {destCap, INTS, JNI_ABORT}, {chainFirst, INTS, JNI_ABORT},
+                                    {chainDestOff, LONGS, JNI_ABORT}, {chainDestCap, LONGS, JNI_ABORT}, {outLen, INTS, 0}, {chainOutLen, LONGS, 0}}};
+  if (stored != NULL) { b.a[b.n_arrays].arr = stored; b.a[b.n_arrays].is_long = INTS; b.a[b.n_arrays].mode = JNI_ABORT; b.a[b.n_arrays].p = NULL; b.n_arrays++; }
+  const int i_stored = stored != NULL ? b.n_arrays - 1 : -1;
+  if (chainPrefixLen != NULL) { b.a[b.n_arrays].arr = chainPrefixLen; b.a[b.n_arrays].is_long = INTS; b.a[b.n_arrays].mode = JNI_ABORT; b.a[b.n_arrays].p = NULL; b.n_arrays++; }
+  const int i_prefix = chainPrefixLen != NULL ? b.n_arrays - 1 : -1;
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  uint8_t* raw = NULL;   /* the C ABI takes one byte per block */
+  if (i_stored >= 0 && nBlocks > 0) {
+    raw = (uint8_t*)malloc((size_t)nBlocks);
+    if (raw == NULL) { batch_release(env, &b); return LZ4HIP_E_NOMEM; }
+    for (jint i = 0; i < nBlocks; i++) raw[i] = ((const jint*)b.a[i_stored].p)[i] != 0;
+  }
+  rc = lz4hip_decompress_safe_chain_batch(b.src, b.a[0].p, b.a[1].p, raw, b.a[2].p, (const uint32_t*)b.a[3].p, b.dst, b.a[4].p, b.a[5].p,
+                                          i_prefix >= 0 ? (const int32_t*)b.a[i_prefix].p : NULL, b.a[6].p, b.a[7].p, (uint32_t)nBlocks, (uint32_t)nChains);
+  free(raw);
   batch_release(env, &b);
   return rc;
 }

@@ -45,6 +45,7 @@ class HIPEngine:
         return LZ4HIPBatch.compressHC(src, srcOff, srcLen, dst, dstOff, dstCap, self.hcLevel)
 
     decompressSafe = staticmethod(LZ4HIPBatch.decompressSafe)
+    decompressSafeChain = staticmethod(LZ4HIPBatch.decompressSafeChain)   # linked blocks: LZ4FrameInputStream(linkedBlocks=True)
     decompressFast = staticmethod(LZ4HIPBatch.decompressFast)
     xxh32 = staticmethod(LZ4HIPBatch.xxh32)
 
@@ -108,10 +109,12 @@ class FLG:
         RESERVED_0, RESERVED_1, CONTENT_CHECKSUM, CONTENT_SIZE, BLOCK_CHECKSUM, BLOCK_INDEPENDENCE = 0, 1, 2, 3, 4, 5
 
     DEFAULT_VERSION = 1
+    DEPENDENT_UNSUPPORTED = "Dependent block stream is unsupported (BLOCK_INDEPENDENCE must be set)"
 
-    def __init__(self, version, bits):
+    def __init__(self, version, bits, allowDependent=False):
         self.version = version
         self.bits = bits & 0x3F
+        self.allowDependent = allowDependent   # a reader that decodes linked blocks (LZ4FrameInputStream(linkedBlocks=True)): the one way past that check
         self._validate()
 
     @classmethod
@@ -122,8 +125,8 @@ class FLG:
         return cls(cls.DEFAULT_VERSION, m)
 
     @classmethod
-    def fromByte(cls, flg):
-        return cls((flg >> 6) & 3, flg & 0x3F)
+    def fromByte(cls, flg, allowDependent=False):
+        return cls((flg >> 6) & 3, flg & 0x3F, allowDependent)
 
     def toByte(self):
         return self.bits | ((self.version & 3) << 6)
@@ -136,8 +139,8 @@ class FLG:
             raise RuntimeError("Reserved0 field must be 0")
         if self.isEnabled(self.Bits.RESERVED_1):
             raise RuntimeError("Reserved1 field must be 0")
-        if not self.isEnabled(self.Bits.BLOCK_INDEPENDENCE):
-            raise RuntimeError("Dependent block stream is unsupported (BLOCK_INDEPENDENCE must be set)")
+        if not self.isEnabled(self.Bits.BLOCK_INDEPENDENCE) and not self.allowDependent:
+            raise RuntimeError(self.DEPENDENT_UNSUPPORTED)
         if self.version != self.DEFAULT_VERSION:
             raise RuntimeError("Version %d is unsupported" % self.version)
 
@@ -336,10 +339,20 @@ class LZ4FrameInputStream(io.RawIOBase):
     content checksums, content-size check -- same checks, same messages.  Block headers of up to `batchBlocks`
     blocks are parsed ahead, then the block checksums are verified in one xxh32 launch and the compressed
     blocks decoded in one safe-decompress launch.  A defect in block k surfaces when the reader reaches
-    block k, after the bytes of blocks < k have been delivered, as in the reference."""
+    block k, after the bytes of blocks < k have been delivered, as in the reference.
 
-    def __init__(self, inp, readSingleFrame=False, engine=None, batchBlocks=64, hostWalk=False):
+    linkedBlocks=True (not in the reference, whose reader refuses such frames; the default refuses them too): a frame without
+    BLOCK_INDEPENDENCE -- what the `lz4` command line writes by default -- is read as well.  Its size words are walked on the host,
+    `batchBlocks` at a time, and each batch is decoded as ONE chain of linked blocks (engine.decompressSafeChain) whose history is the
+    last 64 KB this reader decoded of the frame; stored blocks are part of the chain.  Every check, its order and every message stay as
+    they are.  Frames with BLOCK_INDEPENDENCE take the paths above whatever the flag says; an engine without decompressSafeChain keeps
+    refusing dependent frames."""
+
+    def __init__(self, inp, readSingleFrame=False, engine=None, batchBlocks=64, hostWalk=False, linkedBlocks=False):
         super().__init__()
+        self.linkedBlocks = linkedBlocks
+        self.linked = False          # the current frame has no BLOCK_INDEPENDENCE
+        self.history = bytearray()   # linked blocks: the last 64 KB decoded of the current frame
         self.hostWalk = hostWalk   # True: headers walked and checksums compared on the host around the batch launches (rounds 1-3)
         self.r = _Reader(inp)
         self.engine = engine or HIPEngine()
@@ -379,7 +392,11 @@ class LZ4FrameInputStream(io.RawIOBase):
     def _readHeader(self):  # :180-224
         fb = self.r.read_fully(2)
         header = bytearray(fb)
-        self.flg = FLG.fromByte(fb[0])
+        self.flg = FLG.fromByte(fb[0], allowDependent=self.linkedBlocks)
+        self.linked = not self.flg.isEnabled(FLG.Bits.BLOCK_INDEPENDENCE)
+        if self.linked and not hasattr(self.engine, "decompressSafeChain"):
+            raise RuntimeError(FLG.DEPENDENT_UNSUPPORTED)
+        self.history = bytearray()
         self.bd = BD.fromByte(fb[1])
         if self.flg.isEnabled(FLG.Bits.CONTENT_SIZE):
             cs = self.r.read_fully(8)
@@ -449,7 +466,7 @@ class LZ4FrameInputStream(io.RawIOBase):
         # (the device path takes a whole chunk of container bytes from `inp`: with readSingleFrame the caller reads on behind the
         # frame, so it needs an input it can hand the surplus back to -- round-4 advisor; a pipe or socket gets the host walk, which
         # consumes exactly the frame and never waits for bytes beyond it)
-        if not self.hostWalk and hasattr(self.engine, "containerDecode") and (not self.readSingleFrame or self.r.seekable()):
+        if not self.linked and not self.hostWalk and hasattr(self.engine, "containerDecode") and (not self.readSingleFrame or self.r.seekable()):
             self._readBlocksDevice()
             if self.readSingleFrame and self.frame_finished:
                 self.r.give_back()
@@ -490,6 +507,34 @@ class LZ4FrameInputStream(io.RawIOBase):
                     if h != stored:
                         bad, bad_exc = i, IOException(BLOCK_HASH_MISMATCH)
                         break
+            if self.linked:
+                # one chain: the blocks decode back to back behind the history; a stored block is copied by the same call
+                hist = len(self.history)
+                dst = bytearray(hist + bad * self.maxBlockSize)
+                dst[:hist] = self.history
+                res, done = self.engine.decompressSafeChain(src, offs[:bad], lens[:bad], [self.maxBlockSize] * bad, [0, bad], dst, [hist],
+                                                            [bad * self.maxBlockSize], [hist], [not c for c, _, _ in blocks[:bad]])
+                at = hist
+                for i in range(bad):
+                    if res[i] < 0:  # LZ4JNISafeDecompressor.java:39-41, wrapped in IOException (:307-311)
+                        bad_exc = IOException(LZ4Exception("Error decoding offset %d of input buffer" % (-res[i])))
+                        break
+                    at += res[i]
+                first = len(self.ready)
+                self.ready += dst[hist:at]
+                self.totalContentSize += at - hist
+                self.history = dst[max(at - 65536, 0):at]
+                if self.content is not None and at > hist:
+                    self.content.update(self.ready, first, at - hist)
+                if bad_exc is not None:
+                    self.pending_exc = bad_exc
+                    return
+                if exc is not None:
+                    self.pending_exc = exc
+                    return
+                if end_mark:
+                    self._endMark()
+                return
             cidx = [i for i in range(bad) if blocks[i][0]]
             outs = [None] * bad
             if cidx:
