@@ -3,23 +3,16 @@ host batch takes the multi-device branch of csrc/api.cpp (contiguous block range
 checks a ragged batch -- sizes and bytes of every block, one-byte-short capacities included -- against the reference library's
 LZ4_compress_fast.  Prints 'accel multidev ok D=<D>'."""
 import ctypes as C
-import importlib
-import os
 import random
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-from oracle import oracle as O  # noqa: E402
+import numpy as np
+from support import init_repeated, offsets   # (first: it puts the repository root on sys.path)
+from oracle import oracle as O
 
 D = int(sys.argv[1])
 n = 64 * D * 3 + 11
-amd = importlib.import_module("lz4-java_amd")
-L = amd.lib()
-ids = (C.c_int * D)(*([0] * D))
-assert L.lz4hip_init(ids, D) == 0, L.lz4hip_last_error()
-assert L.lz4hip_device_count() == D
+amd, L = init_repeated(D)
 f = C.CDLL(O.ref().path).LZ4_compress_fast
 f.restype = C.c_int
 f.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int]
@@ -40,8 +33,8 @@ for i in range(n):
 for a in (2, 8):
     want = [ref_fast(v, len(v) + len(v) // 255 + 16, a) for v in srcs]
     caps = [len(v) + len(v) // 255 + 16 if i % 7 else max(0, want[i][0] - 1) for i, v in enumerate(srcs)]
-    so = np.concatenate([[0], np.cumsum([len(v) for v in srcs])[:-1]]).astype(np.uint64)
-    do = np.concatenate([[0], np.cumsum(caps)[:-1]]).astype(np.uint64)
+    so = offsets([len(v) for v in srcs])
+    do = offsets(caps)
     dst = bytearray(int(sum(caps)) + 1)
     out = amd.LZ4HIPBatch.compress(b"".join(srcs), so, np.array([len(v) for v in srcs], dtype=np.int32), dst, do, np.array(caps, dtype=np.int32),
                                    acceleration=a)

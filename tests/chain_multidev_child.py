@@ -3,23 +3,14 @@
 its chains over them at chain boundaries, and checks a batch of chains of uneven length (valid, damaged, with history, with stored
 blocks) against the reference library's LZ4_decompress_safe_continue: values, chain lengths, bytes, and every byte that must stay
 untouched.  Prints 'chain multidev ok D=<D>'."""
-import ctypes as C
-import importlib
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-from oracle import oracle as O  # noqa: E402
-from chain_common import Packed, RefChain, book_chains, damaged_chains, hand_chains, rng_for, stored_and_empty_chains  # noqa: E402
+from support import init_devices   # (first: it puts the repository root on sys.path)
+from oracle import oracle as O
+from chain_common import Packed, RefChain, book_chains, damaged_chains, hand_chains, rng_for, stored_and_empty_chains
 
 D = int(sys.argv[1])
-ids = list(range(D)) if sys.argv[2] == "distinct" else [0] * D
-amd = importlib.import_module("lz4-java_amd")
-L = amd.lib()
-assert L.lz4hip_init((C.c_int * D)(*ids), D) == 0, L.lz4hip_last_error()
-assert L.lz4hip_device_count() == D
+amd, L = init_devices(list(range(D)) if sys.argv[2] == "distinct" else [0] * D)
 rc = RefChain(O.ref())
 rng = rng_for(70 + D)
 pool = book_chains(rc) + stored_and_empty_chains(rc) + damaged_chains(rc, rng, n_flipped=10) + hand_chains(rng)[::7]

@@ -5,16 +5,14 @@
 #include <cstdio>
 #include <stdexcept>
 #include "../../lz4-java_amd/host/lz4hip.hpp"
+#include "mirror_io.h"
 
 using namespace net::jpountz;
 
 int main(int argc, char** argv) {
   if (argc < 4) { fprintf(stderr, "usage: destsize_mirror_test <input> <target> <out>\n"); return 2; }
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
   bytes in;
-  for (int c; (c = fgetc(f)) != EOF;) in.push_back((uint8_t)c);
-  fclose(f);
+  if (!slurp(argv[1], in)) return 2;
   const int t = atoi(argv[2]);
   try {
     const lz4::LZ4HIPCompressor c, accel(8);
@@ -25,8 +23,7 @@ int main(int argc, char** argv) {
     int len = (int)in.size();
     const int w = c.compressDestSize(src, off, len, dst, 5, t);
     if (w <= 0 || w > t || len <= 0 || len > (int)in.size()) return 1;
-    for (size_t i = 0; i < dst.size(); i++)
-      if ((i < 5 || i >= (size_t)(5 + w)) && dst[i] != 0xEE) { fprintf(stderr, "byte %zu outside the output changed\n", i); return 1; }
+    if (!untouched(dst, 5, (size_t)w, "output")) return 1;
     // the stream decodes to exactly the consumed prefix
     if (lz4::LZ4Factory::hipInstance().safeDecompressor().decompress(bytes(dst.begin() + 5, dst.begin() + 5 + w), len) !=
         bytes(in.begin(), in.begin() + len)) return 1;
@@ -36,9 +33,7 @@ int main(int argc, char** argv) {
     threw = false;
     try { int l2 = (int)in.size(); (void)c.compressDestSize(src, off, l2, dst, 10, t + 10); } catch (const std::out_of_range&) { threw = true; }
     if (!threw) return 1;
-    FILE* o = fopen(argv[3], "wb");
-    if (!o || fwrite(dst.data() + 5, 1, (size_t)w, o) != (size_t)w) return 1;
-    fclose(o);
+    if (!dump(argv[3], dst.data() + 5, (size_t)w)) return 1;
     printf("%d %d\n", w, len);
     return 0;
   } catch (const lz4::LZ4Exception& e) {

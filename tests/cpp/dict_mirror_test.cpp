@@ -9,16 +9,9 @@
 #include <stdexcept>
 #include <string>
 #include "../../lz4-java_amd/host/lz4hip.hpp"
+#include "mirror_io.h"
 
 using namespace net::jpountz;
-
-static bool slurp(const char* path, bytes& out) {
-  FILE* f = fopen(path, "rb");
-  if (!f) return false;
-  for (int c; (c = fgetc(f)) != EOF;) out.push_back((uint8_t)c);
-  fclose(f);
-  return true;
-}
 
 int main(int argc, char** argv) {
   if (argc < 5) { fprintf(stderr, "usage: dict_mirror_test <dictionary> <stream> <cap> <out>\n"); return 2; }
@@ -58,8 +51,7 @@ int main(int argc, char** argv) {
       if (std::string(e.what()).rfind("Error decoding offset ", 0) != 0) throw;
       const int code = -(atoi(e.what() + 22) - off);
       if (got[0] != code || got[1] != code) { fprintf(stderr, "batch %d %d, single %d\n", got[0], got[1], code); return 1; }
-      for (size_t i = 0; i < dst.size(); i++)
-        if ((i < (size_t)doff || i >= (size_t)(doff + cap)) && dst[i] != 0xEE) { fprintf(stderr, "byte %zu outside the slot changed\n", i); return 1; }
+      if (!untouched(dst, (size_t)doff, (size_t)cap)) return 1;
       printf("error %s\n", e.what());
       return 0;
     }
@@ -72,11 +64,8 @@ int main(int argc, char** argv) {
       const bool in0 = i < (size_t)cap, in1 = i >= (size_t)cap + 8 && i < (size_t)2 * cap + 8;
       if (!in0 && !in1 && dst2[i] != 0xEE) { fprintf(stderr, "batch: byte %zu outside the slots changed\n", i); return 1; }
     }
-    for (size_t i = 0; i < dst.size(); i++)
-      if ((i < (size_t)doff || i >= (size_t)(doff + cap)) && dst[i] != 0xEE) { fprintf(stderr, "byte %zu outside the slot changed\n", i); return 1; }
-    FILE* o = fopen(argv[4], "wb");
-    if (!o || fwrite(dst.data() + doff, 1, (size_t)w, o) != (size_t)w) return 1;
-    fclose(o);
+    if (!untouched(dst, (size_t)doff, (size_t)cap)) return 1;
+    if (!dump(argv[4], dst.data() + doff, (size_t)w)) return 1;
     printf("%d\n", w);
     return 0;
   } catch (const lz4::LZ4Exception& e) {

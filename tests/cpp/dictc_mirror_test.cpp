@@ -7,16 +7,9 @@
 #include <stdexcept>
 #include <string>
 #include "../../lz4-java_amd/host/lz4hip.hpp"
+#include "mirror_io.h"
 
 using namespace net::jpountz;
-
-static bool slurp(const char* path, bytes& out) {
-  FILE* f = fopen(path, "rb");
-  if (!f) return false;
-  for (int c; (c = fgetc(f)) != EOF;) out.push_back((uint8_t)c);
-  fclose(f);
-  return true;
-}
 
 int main(int argc, char** argv) {
   if (argc < 4) { fprintf(stderr, "usage: dictc_mirror_test <dictionary> <record> <out>\n"); return 2; }
@@ -56,13 +49,10 @@ int main(int argc, char** argv) {
       if (dst2[(size_t)i] != dst[(size_t)(doff + i)]) { fprintf(stderr, "batch differs at %d\n", i); return 1; }
     for (size_t i = (size_t)cap; i < (size_t)cap + 8; i++)
       if (dst2[i] != 0xEE) { fprintf(stderr, "batch: byte %zu outside the slots changed\n", i); return 1; }
-    for (size_t i = 0; i < dst.size(); i++)
-      if ((i < (size_t)doff || i >= (size_t)(doff + cap)) && dst[i] != 0xEE) { fprintf(stderr, "byte %zu outside the slot changed\n", i); return 1; }
+    if (!untouched(dst, (size_t)doff, (size_t)cap)) return 1;
     try { (void)c.compressWithDict(dict, src, off, (int)in.size(), dst, doff, w - 1); return 1; }
     catch (const lz4::LZ4Exception& e) { if (std::string(e.what()) != "maxDestLen is too small") throw; }
-    FILE* o = fopen(argv[3], "wb");
-    if (!o || fwrite(dst.data() + doff, 1, (size_t)w, o) != (size_t)w) return 1;
-    fclose(o);
+    if (!dump(argv[3], dst.data() + doff, (size_t)w)) return 1;
     printf("%d\n", w);
     return 0;
   } catch (const lz4::LZ4Exception& e) {

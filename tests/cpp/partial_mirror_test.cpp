@@ -8,16 +8,14 @@
 #include <stdexcept>
 #include <string>
 #include "../../lz4-java_amd/host/lz4hip.hpp"
+#include "mirror_io.h"
 
 using namespace net::jpountz;
 
 int main(int argc, char** argv) {
   if (argc < 5) { fprintf(stderr, "usage: partial_mirror_test <stream> <target> <cap> <out>\n"); return 2; }
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
   bytes in;
-  for (int c; (c = fgetc(f)) != EOF;) in.push_back((uint8_t)c);
-  fclose(f);
+  if (!slurp(argv[1], in)) return 2;
   const int t = atoi(argv[2]), cap = atoi(argv[3]);
   const int room = t < cap ? t : cap;
   const int off = 3, doff = 5;                   // regions away from byte 0 of both vectors
@@ -37,17 +35,13 @@ int main(int argc, char** argv) {
       w = d.decompressPartial(src, off, (int)in.size(), dst, doff, t, cap);
     } catch (const lz4::LZ4Exception& e) {
       if (std::string(e.what()).rfind("Error decoding offset ", 0) != 0) throw;
-      for (size_t i = 0; i < dst.size(); i++)
-        if ((i < (size_t)doff || i >= (size_t)(doff + room)) && dst[i] != 0xEE) { fprintf(stderr, "byte %zu outside the slot changed\n", i); return 1; }
+      if (!untouched(dst, (size_t)doff, (size_t)room)) return 1;
       printf("error %s\n", e.what());
       return 0;
     }
     if (w < 0 || w > room) return 1;
-    for (size_t i = 0; i < dst.size(); i++)
-      if ((i < (size_t)doff || i >= (size_t)(doff + room)) && dst[i] != 0xEE) { fprintf(stderr, "byte %zu outside the slot changed\n", i); return 1; }
-    FILE* o = fopen(argv[4], "wb");
-    if (!o || fwrite(dst.data() + doff, 1, (size_t)w, o) != (size_t)w) return 1;
-    fclose(o);
+    if (!untouched(dst, (size_t)doff, (size_t)room)) return 1;
+    if (!dump(argv[4], dst.data() + doff, (size_t)w)) return 1;
     printf("%d\n", w);
     return 0;
   } catch (const lz4::LZ4Exception& e) {

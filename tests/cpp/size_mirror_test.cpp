@@ -10,16 +10,14 @@
 #include <stdexcept>
 #include <string>
 #include "../../lz4-java_amd/host/lz4hip.hpp"
+#include "mirror_io.h"
 
 using namespace net::jpountz;
 
 int main(int argc, char** argv) {
   if (argc < 4) { fprintf(stderr, "usage: size_mirror_test <stream> <cap> <out>\n"); return 2; }
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
   bytes in;
-  for (int c; (c = fgetc(f)) != EOF;) in.push_back((uint8_t)c);
-  fclose(f);
+  if (!slurp(argv[1], in)) return 2;
   const int cap = atoi(argv[2]);
   const int off = 3;                             // a region away from byte 0 of the vector
   bytes src(in.size() + off);
@@ -49,9 +47,7 @@ int main(int argc, char** argv) {
     uint64_t total = 0;
     for (size_t i = 0; i < 3; i++) { if (r.offsets[i] != total) return 1; total += sizes[i] > 0 ? (uint64_t)sizes[i] : 0; }
     if (r.data.size() != total) { fprintf(stderr, "the buffer is not the sum of the sizes\n"); return 1; }
-    FILE* o = fopen(argv[3], "wb");
-    if (!o || fwrite(r.data.data(), 1, r.data.size(), o) != r.data.size()) return 1;
-    fclose(o);
+    if (!dump(argv[3], r.data.data(), r.data.size())) return 1;
     printf("%d %d %d\n", (int)sizes[0], (int)sizes[1], (int)sizes[2]);
     return 0;
   } catch (const lz4::LZ4Exception& e) {

@@ -3,23 +3,16 @@ host batch takes the multi-device branch of csrc/api.cpp (contiguous block range
 range) on a box with one GPU, and checks a ragged batch -- sizes, consumed sizes and bytes of every block -- against the reference
 library's LZ4_compress_destSize.  Prints 'destsize multidev ok D=<D>'."""
 import ctypes as C
-import importlib
-import os
 import random
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np  # noqa: E402
-from oracle import oracle as O  # noqa: E402
+import numpy as np
+from support import init_repeated, offsets   # (first: it puts the repository root on sys.path)
+from oracle import oracle as O
 
 D = int(sys.argv[1])
 n = 64 * D * 3 + 11
-amd = importlib.import_module("lz4-java_amd")
-L = amd.lib()
-ids = (C.c_int * D)(*([0] * D))
-assert L.lz4hip_init(ids, D) == 0, L.lz4hip_last_error()
-assert L.lz4hip_device_count() == D
+amd, L = init_repeated(D)
 f = C.CDLL(O.ref().path).LZ4_compress_destSize
 f.restype = C.c_int
 f.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.POINTER(C.c_int), C.c_int]
@@ -41,8 +34,8 @@ for i in range(n):
     srcs.append(v)
     targets.append(rng.choice([4096, 16384, 1, 17, len(v) // 3 + 1, len(v) + len(v) // 255 + 16]))
 want = [ref_dest(v, t) for v, t in zip(srcs, targets)]
-so = np.concatenate([[0], np.cumsum([len(v) for v in srcs])[:-1]]).astype(np.uint64)
-do = np.concatenate([[0], np.cumsum(targets)[:-1]]).astype(np.uint64)
+so = offsets([len(v) for v in srcs])
+do = offsets(targets)
 dst = bytearray(int(sum(targets)) + 1)
 out, cons = amd.LZ4HIPBatch.compressDestSize(b"".join(srcs), so, np.array([len(v) for v in srcs], dtype=np.int32), dst, do,
                                              np.array(targets, dtype=np.int32))

@@ -3,24 +3,18 @@ decoder's host batch takes the multi-device branch of csrc/api.cpp (contiguous b
 each) on a box with one GPU, and checks a batch of records -- valid, damaged and cut, with ragged capacities -- against the reference
 library's LZ4_decompress_safe_usingDict: return values, bytes and the untouched bytes behind every result.  A handle created BEFORE
 lz4hip_init is used too (its device copy is made on first use).  Prints 'dict multidev ok D=<D>'."""
-import ctypes as C
-import importlib
-import os
 import random
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np  # noqa: E402
-from oracle import oracle as O  # noqa: E402
-from dict_common import RefDict, book1  # noqa: E402
-from partial_common import damaged  # noqa: E402
+import numpy as np
+from support import check_slots, init_repeated, package, slots   # (first: it puts the repository root on sys.path)
+from oracle import oracle as O
+from dict_common import RefDict, book1
+from partial_common import damaged
 
 D = int(sys.argv[1])
 n = 64 * D * 3 + 11
-amd = importlib.import_module("lz4-java_amd")
-L = amd.lib()
+amd, L = package()
 b = book1()
 rd = RefDict(O.ref())
 for dict_len, early in ((4096, False), (70000, True)):
@@ -28,9 +22,7 @@ for dict_len, early in ((4096, False), (70000, True)):
     if early:
         L.lz4hip_shutdown()
         handle = amd.LZ4Dictionary(d)          # no device is initialised yet on this pass
-    ids = (C.c_int * D)(*([0] * D))
-    assert L.lz4hip_init(ids, D) == 0, L.lz4hip_last_error()
-    assert L.lz4hip_device_count() == D
+    init_repeated(D)
     if not early:
         handle = amd.LZ4Dictionary(d)
     assert len(handle) == dict_len
@@ -48,16 +40,9 @@ for dict_len, early in ((4096, False), (70000, True)):
         srcs.append(s)
         caps.append(rng.choice([size, size + 100, max(size - 7, 0), size + 1]))
     want = [rd.decode(s, c, d) for s, c in zip(srcs, caps)]
-    so = np.concatenate([[0], np.cumsum([len(s) for s in srcs])[:-1]]).astype(np.uint64)
-    do = np.concatenate([[0], np.cumsum([c + 8 for c in caps])[:-1]]).astype(np.uint64)
-    dst = bytearray(b"\xee" * (int(sum(caps)) + 8 * n))
+    so, do, dst = slots(srcs, caps)
     out = amd.LZ4HIPBatch.decompressSafeDict(b"".join(srcs) + b"\0", so, np.array([len(s) for s in srcs], dtype=np.int32), dst, do,
                                              np.array(caps, dtype=np.int32), handle)
-    for i in range(n):
-        r, by = want[i]
-        assert int(out[i]) == r, ("result", dict_len, i, len(srcs[i]), caps[i], int(out[i]), r)
-        o = int(do[i])
-        assert bytes(dst[o:o + max(r, 0)]) == by, ("bytes", dict_len, i)
-        assert dst[o + max(r, 0):o + caps[i] + 8] == b"\xee" * (caps[i] + 8 - max(r, 0)), ("written past the result", dict_len, i)
+    check_slots(out, dst, do, caps, want, srcs, tag=(dict_len,))
     handle.close()
 print("dict multidev ok D=%d blocks=%d" % (D, n))

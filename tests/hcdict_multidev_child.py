@@ -3,24 +3,18 @@ compressor's host batch takes the multi-device branch of csrc/api.cpp (contiguou
 image on each), and checks a batch of records with ragged capacities at two levels against the reference library's LZ4_loadDictHC +
 LZ4_compress_HC_continue: return values, bytes and the untouched bytes behind every result.  A handle created BEFORE lz4hip_init is
 used too (its device copies are made on first use).  Prints 'hcdict multidev ok D=<D>'."""
-import ctypes as C
-import importlib
-import os
 import random
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np  # noqa: E402
-from oracle import oracle as O  # noqa: E402
-from hcdict_common import Ref, book1, bound  # noqa: E402
+import numpy as np
+from support import check_slots, init_devices, package, slots   # (first: it puts the repository root on sys.path)
+from oracle import oracle as O
+from hcdict_common import Ref, book1, bound
 
 devs = [int(a) for a in sys.argv[1:]]
 D = len(devs)
 n = 64 * D * 2 + 11
-amd = importlib.import_module("lz4-java_amd")
-L = amd.lib()
+amd, L = package()
 b = book1()
 R = Ref(O.ref())
 for dict_len, early, level in ((4096, False, 9), (70000, True, 4), (3, False, 10)):
@@ -28,9 +22,7 @@ for dict_len, early, level in ((4096, False, 9), (70000, True, 4), (3, False, 10
     if early:
         L.lz4hip_shutdown()
         handle = amd.LZ4Dictionary(d)          # no device is initialised yet on this pass
-    ids = (C.c_int * D)(*devs)
-    assert L.lz4hip_init(ids, D) == 0, L.lz4hip_last_error()
-    assert L.lz4hip_device_count() == D
+    init_devices(devs)
     if not early:
         handle = amd.LZ4Dictionary(d)
     assert len(handle) == dict_len
@@ -44,16 +36,9 @@ for dict_len, early, level in ((4096, False, 9), (70000, True, 4), (3, False, 10
         cap = rng.choice([bound(size), full[0], full[0] - 1, full[0] + 1])
         recs.append(rec); caps.append(cap)
         want.append(full if cap >= full[0] else R.compress(d, rec, level, cap))
-    so = np.concatenate([[0], np.cumsum([len(s) for s in recs])[:-1]]).astype(np.uint64)
-    do = np.concatenate([[0], np.cumsum([c + 8 for c in caps])[:-1]]).astype(np.uint64)
-    dst = bytearray(b"\xee" * (int(sum(caps)) + 8 * n))
+    so, do, dst = slots(recs, caps)
     out = amd.LZ4HIPBatch.compressHCDict(b"".join(recs) + b"\0", so, np.array([len(s) for s in recs], dtype=np.int32), dst, do,
                                          np.array(caps, dtype=np.int32), handle, level)
-    for i in range(n):
-        r, by = want[i]
-        assert int(out[i]) == r, ("result", dict_len, i, len(recs[i]), caps[i], int(out[i]), r)
-        o = int(do[i])
-        assert bytes(dst[o:o + r]) == by, ("bytes", dict_len, i)
-        assert dst[o + r:o + caps[i] + 8] == b"\xee" * (caps[i] + 8 - r), ("written past the result", dict_len, i)
+    check_slots(out, dst, do, caps, want, recs, tag=(dict_len,))
     handle.close()
 print("hcdict multidev ok D=%d blocks=%d" % (D, n))

@@ -2,7 +2,7 @@
 # builds a fake-JNI program: the JNI shim compiled against the stub jni.h (its malloc/free counted) + tests/jni_stub/<name>.c, the
 # scenarios over the fake JNIEnv of fake_env.h
 #   build.sh                   tests/jni_stub/fake_jni, in place
-#   build.sh <name> <out-dir>  <out-dir>/<name> (tests/jni_build.py)
+#   build.sh <name> <out-dir>  <out-dir>/<name> (tests/support.py: build_fake_jni)
 set -e
 here="$(cd "$(dirname "$0")" && pwd)"; root="$here/../.."
 name="${1:-fake_jni}"; out="${2:-$here}"

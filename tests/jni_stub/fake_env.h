@@ -70,4 +70,52 @@ static inline int guarded(const fobj* o, size_t off, size_t n, uint8_t fill) {
 /* an int[1] and its element */
 static inline fobj* int1(jint v) { fobj* o = mk(2, 4); ((jint*)o->data)[0] = v; return o; }
 static inline jint get1(const fobj* o) { return ((const jint*)o->data)[0]; }
+
+/* ---- what every fake_jni*.c program does around its scenarios ---- */
+#include <stdarg.h>
+/* the program was started as "<program> --no-gpu" */
+static inline int arg_no_gpu(int argc, char** argv) { return argc > 1 && strcmp(argv[1], "--no-gpu") == 0; }
+/* a new object of `kind` with the file's n bytes (fewer than 16 MiB) at offset `lead` and 16 spare bytes behind them */
+static inline fobj* slurp(const char* path, int kind, size_t lead, long* n_out) {
+  FILE* f = fopen(path, "rb");
+  CHECK(f != NULL);
+  fseek(f, 0, SEEK_END);
+  const long n = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  CHECK(n >= 0 && n < (1 << 24));
+  fobj* o = mk(kind, (size_t)n + lead + 16);
+  CHECK(fread(o->data + lead, 1, (size_t)n, f) == (size_t)n);
+  fclose(f);
+  *n_out = n;
+  return o;
+}
+/* the same bytes in a new object of another kind (a heap array's content as a direct buffer) */
+static inline fobj* copy_as(const fobj* o, int kind) { fobj* c = mk(kind, o->bytes); memcpy(c->data, o->data, o->bytes); return c; }
+/* <dir>/<name>, opened for writing */
+static inline FILE* out_file(const char* dir, const char* name, const char* mode) {
+  char path[4096];
+  snprintf(path, sizeof path, "%s/%s", dir, name);
+  FILE* o = fopen(path, mode);
+  CHECK(o != NULL);
+  return o;
+}
+static inline void write_bytes(const char* dir, const char* name, const uint8_t* p, size_t n) {
+  FILE* o = out_file(dir, name, "wb");
+  CHECK(fwrite(p, 1, n, o) == n);
+  fclose(o);
+}
+static inline void write_text(const char* dir, const char* name, const char* fmt, ...) {
+  FILE* o = out_file(dir, name, "w");
+  va_list ap;
+  va_start(ap, fmt);
+  vfprintf(o, fmt, ap);
+  va_end(ap);
+  fclose(o);
+}
+/* the closing line, and main's return value: "<program>: N checks ok", without a device "... (no device: <what failed loudly>)" */
+static inline int checks_ok(const char* no_device) {
+  if (no_device) printf(FAKE_JNI_NAME ": %d checks ok (no device: %s)\n", g_checks, no_device);
+  else printf(FAKE_JNI_NAME ": %d checks ok\n", g_checks);
+  return 0;
+}
 #endif

@@ -48,7 +48,7 @@ static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
 static uint32_t rnd(void) { rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(rng_state >> 33); }
 
 int main(int argc, char** argv) {
-  const int gpu = !(argc > 1 && strcmp(argv[1], "--no-gpu") == 0);
+  const int gpu = !arg_no_gpu(argc, argv);
   JNIEnv* env = &g_env;
   Java_net_jpountz_lz4_LZ4HIPJNI_init(env, NULL);
   CHECK(no_exc());
@@ -82,8 +82,7 @@ int main(int argc, char** argv) {
     clear_exc();
     jlong st = Java_net_jpountz_xxhash_XXHashHIPJNI_XXH32_1init(env, NULL, 0);
     CHECK(st == 0 && g_exc_class != NULL);   /* creation fails loudly too */
-    printf("fake_jni: %d checks ok (no device: every compute call failed loudly)\n", g_checks);
-    return 0;
+    return checks_ok("every compute call failed loudly");
   }
 
   /* ---- 1. LZ4Factory's constructor self-test through byte[] arguments with offsets (LZ4Factory.java:176-220) ---- */
@@ -256,6 +255,5 @@ int main(int argc, char** argv) {
     CHECK(no_exc() && dl == n && memcmp(a->data + so_, b->data + so_, (size_t)n) == 0 && a->pins == 0 && b->pins == 0 && c->pins == 0 && g_alloc == 0);
     free(a->data); free(a); free(b->data); free(b); free(c->data); free(c);
   }
-  printf("fake_jni: %d checks ok\n", g_checks);
-  return 0;
+  return checks_ok(NULL);
 }

@@ -2,7 +2,8 @@
  *
  * The accelerated fast-compress native of the JNI shim (LZ4HIPJNI.LZ4HIP_compress_fast_accel and LZ4HIP_batch op 4) executed
  * without a JVM, with the fake JNIEnv of fake_env.h (a byte[] / int[] / long[] is a malloc'd buffer with pin accounting, a
- * direct ByteBuffer is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built by tests/test_gpu_accel.py /
+ * direct ByteBuffer is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built (build_fake_jni of
+ * tests/support.py; the shared file reading, output files and closing line are fake_env.h's) by tests/test_gpu_accel.py /
  * tests/test_accel_abi.py.
  *
  *   fake_jni_accel --no-gpu            anywhere: the new native fails LOUDLY without a device (library error code, nothing leaked)
@@ -25,7 +26,7 @@ int main(int argc, char** argv) {
   JNIEnv* env = &g_env;
   Java_net_jpountz_lz4_LZ4HIPJNI_init(env, NULL);
   CHECK(no_exc());
-  if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+  if (arg_no_gpu(argc, argv)) {
     fobj* src = mk(1, 64); fobj* dst = mk(1, 128);
     for (int a = -3; a <= 9; a += 4) {   /* (acceleration 1 and below go through the plain fast path: loud as well) */
       jint r = ACCEL(env, NULL, (jbyteArray)src, NULL, 7, 20, (jbyteArray)dst, NULL, 3, 100, a);
@@ -33,22 +34,14 @@ int main(int argc, char** argv) {
     }
     const char* msg = (const char*)Java_net_jpountz_lz4_LZ4HIPJNI_lastError(env, NULL);
     CHECK(msg && strlen(msg) > 0);
-    printf("fake_jni_accel: %d checks ok (no device: every compute call failed loudly)\n", g_checks);
-    return 0;
+    return checks_ok("every compute call failed loudly");
   }
   if (argc < 3) { fprintf(stderr, "usage: fake_jni_accel --no-gpu | <input> <out-dir>\n"); return 2; }
-  FILE* f = fopen(argv[1], "rb");
-  CHECK(f != NULL);
-  fseek(f, 0, SEEK_END);
-  const long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  CHECK(n > 1000 && n < (1 << 24));
-  const int bound = (int)n + (int)n / 255 + 16;
   const size_t SO = 5, DO = 7;   /* offsets of the regions inside their arrays / buffers */
-  fobj* asrc = mk(1, (size_t)n + 16); fobj* dsrc = mk(4, (size_t)n + 16);
-  CHECK(fread(asrc->data + SO, 1, (size_t)n, f) == (size_t)n);
-  fclose(f);
-  memcpy(dsrc->data + SO, asrc->data + SO, (size_t)n);
+  long n = 0;
+  fobj* asrc = slurp(argv[1], 1, SO, &n); fobj* dsrc = copy_as(asrc, 4);
+  CHECK(n > 1000);
+  const int bound = (int)n + (int)n / 255 + 16;
   fobj* adst = mk(1, (size_t)bound + 32); fobj* ddst = mk(4, (size_t)bound + 32);
   const int accels[2] = {1, 8};
   jint sizes[2] = {0, 0};
@@ -60,11 +53,9 @@ int main(int argc, char** argv) {
     CHECK(no_exc() && r > 0 && g_alloc == 0 && asrc->pins == 0 && adst->pins == 0);
     CHECK(guarded(adst, DO, (size_t)r, 0xEE));
     sizes[t] = r;
-    char path[4096];
-    snprintf(path, sizeof path, "%s/accel_%d.bin", argv[2], a);
-    FILE* o = fopen(path, "wb");
-    CHECK(o != NULL && fwrite(adst->data + DO, 1, (size_t)r, o) == (size_t)r);
-    fclose(o);
+    char name[32];
+    snprintf(name, sizeof name, "accel_%d.bin", a);
+    write_bytes(argv[2], name, adst->data + DO, (size_t)r);
     /* direct -> direct (NULL arrays): the same bytes */
     memset(ddst->data, 0xEE, ddst->bytes);
     jint r2 = ACCEL(env, NULL, NULL, (jobject)dsrc, (jint)SO, (jint)n, NULL, (jobject)ddst, (jint)DO, bound, a);
@@ -117,6 +108,5 @@ int main(int argc, char** argv) {
     (void)ACCEL(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, (jbyteArray)ref8, NULL, 0, bound, 8);
     CHECK(memcmp(bdst->data, ref8->data, (size_t)sizes[1]) == 0 && memcmp(bdst->data + bound, ref8->data, (size_t)sizes[1]) == 0); }
   CHECK(sizes[1] > sizes[0]);   /* acceleration 8 trades ratio for speed: a bigger stream on this input */
-  printf("fake_jni_accel: %d checks ok\n", g_checks);
-  return 0;
+  return checks_ok(NULL);
 }

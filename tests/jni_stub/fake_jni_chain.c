@@ -2,7 +2,8 @@
  *
  * The linked-block native of the JNI shim (LZ4HIPJNI.LZ4HIP_batchSafeChain) executed without a JVM, with the fake JNIEnv of fake_env.h
  * (an int[] / long[] is a malloc'd buffer with pin accounting, a direct ByteBuffer is a pointer; the shim's malloc / free are counted
- * through shim_alloc.h).  Built by tests/test_chain_abi.py / tests/test_gpu_chain.py.
+ * through shim_alloc.h).  Built (build_fake_jni of
+ * tests/support.py; the shared file reading, output files and closing line are fake_env.h's) by tests/test_chain_abi.py / tests/test_gpu_chain.py.
  *
  *   fake_jni_chain --no-gpu           anywhere: NULL arrays and a bad chainFirst are argument errors, a well-formed call fails LOUDLY
  *                                     without a device (library status, nothing leaked or left pinned, nothing written)
@@ -65,7 +66,7 @@ int main(int argc, char** argv) {
   Java_net_jpountz_lz4_LZ4HIPJNI_init(env, NULL);
   CHECK(no_exc());
   (void)no_gpu_checks(env);
-  if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+  if (arg_no_gpu(argc, argv)) {
     fobj* src = mk(4, 64); fobj* dst = mk(4, 64);
     src->data[0] = 0x10; src->data[1] = 'a';
     memset(dst->data, 7, 64);
@@ -83,8 +84,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 64; i++) CHECK(dst->data[i] == 7);
     const char* msg = (const char*)Java_net_jpountz_lz4_LZ4HIPJNI_lastError(env, NULL);
     CHECK(msg && strstr(msg, "no HIP device") != NULL);
-    printf("fake_jni_chain: %d checks ok (no device: every compute call failed loudly)\n", g_checks);
-    return 0;
+    return checks_ok("every compute call failed loudly");
   }
   if (argc < 3) { fprintf(stderr, "usage: fake_jni_chain --no-gpu | <chain> <out-dir>\n"); return 2; }
   FILE* f = fopen(argv[1], "rb");
@@ -130,17 +130,11 @@ int main(int argc, char** argv) {
   for (size_t i = 0; i < GUARD; i++) CHECK(dst->data[i] == 0xEE && dst->data[GUARD + prefix + (size_t)cap64 + i] == 0xEE);
   CHECK(memcmp(dst->data + GUARD, hist, prefix) == 0);
   for (size_t i = (size_t)done; i < (size_t)cap64; i++) CHECK(dst->data[GUARD + prefix + i] == 0xEE);
-  char path[4096];
-  snprintf(path, sizeof path, "%s/chain.txt", argv[2]);
-  FILE* t = fopen(path, "w");
-  CHECK(t != NULL);
+  FILE* t = out_file(argv[2], "chain.txt", "w");
   for (uint32_t i = 0; i < n; i++) fprintf(t, "%d ", (int)((jint*)ol->data)[i]);
   fprintf(t, "| %llu\n", (unsigned long long)done);
   fclose(t);
-  snprintf(path, sizeof path, "%s/chain.out", argv[2]);
-  t = fopen(path, "wb");
-  CHECK(t != NULL && fwrite(dst->data + GUARD + prefix, 1, (size_t)done, t) == (size_t)done);
-  fclose(t);
+  write_bytes(argv[2], "chain.out", dst->data + GUARD + prefix, (size_t)done);
   if (!any_stored) {   /* stored == NULL: the same values and bytes */
     fobj* ol2 = mk(2, 4 * (size_t)n); fobj* dst2 = mk(4, dst->bytes);
     memset(dst2->data, 0xEE, dst2->bytes);
@@ -152,6 +146,5 @@ int main(int argc, char** argv) {
     CHECK(memcmp(ol2->data, ol->data, 4 * (size_t)n) == 0 && memcmp(dst2->data, dst->data, dst->bytes) == 0);
   }
   free(in);
-  printf("fake_jni_chain: %d checks ok\n", g_checks);
-  return 0;
+  return checks_ok(NULL);
 }

@@ -2,7 +2,8 @@
  *
  * The destSize natives of the JNI shim (LZ4HIPJNI.LZ4HIP_compress_dest_size and LZ4HIP_batchDestSize) executed without a JVM, with
  * the fake JNIEnv of fake_env.h (a byte[] / int[] / long[] is a malloc'd buffer with pin accounting, a direct ByteBuffer is a
- * pointer; the shim's malloc / free are counted through shim_alloc.h).  Built by tests/test_destsize_abi.py / tests/test_gpu_destsize.py.
+ * pointer; the shim's malloc / free are counted through shim_alloc.h).  Built (build_fake_jni of
+ * tests/support.py; the shared file reading, output files and closing line are fake_env.h's) by tests/test_destsize_abi.py / tests/test_gpu_destsize.py.
  *
  *   fake_jni_destsize --no-gpu                   anywhere: NULL arrays are argument errors, every compute call fails LOUDLY without
  *                                                a device (library error code, srcSize untouched, nothing leaked or left pinned)
@@ -45,12 +46,12 @@ int main(int argc, char** argv) {
     /* heap ByteBuffers where direct ones are required */
     fobj* hb = mk(5, 64);
     CHECK(BATCH(env, NULL, (jobject)hb, (jlongArray)so, (jintArray)sl, (jobject)ddst, (jlongArray)dof, (jintArray)ts, (jintArray)ol, (jintArray)sc, 1) == LZ4HIP_E_ARG);
-    if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+    if (arg_no_gpu(argc, argv)) {
       const jint rc = BATCH(env, NULL, (jobject)dsrc, (jlongArray)so, (jintArray)sl, (jobject)ddst, (jlongArray)dof, (jintArray)ts, (jintArray)ol, (jintArray)sc, 1);
       CHECK(rc == LZ4HIP_E_NO_DEVICE && no_exc() && get1(sc) == -7);
       for (int t = 0; t < 6; t++) CHECK(a[t]->pins == 0);
     } }
-  if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+  if (arg_no_gpu(argc, argv)) {
     fobj* sz = int1(40);
     jint r = DEST(env, NULL, (jbyteArray)src, NULL, 7, (jintArray)sz, (jbyteArray)dst, NULL, 3, 100);
     CHECK(LZ4HIP_IS_LIB_ERROR(r) && no_exc() && get1(sz) == 40 && g_alloc == 0 && src->pins == 0 && dst->pins == 0 && sz->pins == 0);
@@ -58,23 +59,15 @@ int main(int argc, char** argv) {
     CHECK(LZ4HIP_IS_LIB_ERROR(r) && no_exc() && get1(sz) == 40 && g_alloc == 0);
     const char* msg = (const char*)Java_net_jpountz_lz4_LZ4HIPJNI_lastError(env, NULL);
     CHECK(msg && strlen(msg) > 0);
-    printf("fake_jni_destsize: %d checks ok (no device: every compute call failed loudly)\n", g_checks);
-    return 0;
+    return checks_ok("every compute call failed loudly");
   }
   if (argc < 4) { fprintf(stderr, "usage: fake_jni_destsize --no-gpu | <input> <target> <out-dir>\n"); return 2; }
-  FILE* f = fopen(argv[1], "rb");
-  CHECK(f != NULL);
-  fseek(f, 0, SEEK_END);
-  const long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  CHECK(n > 1000 && n < (1 << 24));
+  const size_t SO = 5, DO = 7;
+  long n = 0;
+  fobj* asrc = slurp(argv[1], 1, SO, &n); fobj* dsrc2 = copy_as(asrc, 4);
+  CHECK(n > 1000);
   const int t = atoi(argv[2]);
   CHECK(t > 0 && t < n);
-  const size_t SO = 5, DO = 7;
-  fobj* asrc = mk(1, (size_t)n + 16); fobj* dsrc2 = mk(4, (size_t)n + 16);
-  CHECK(fread(asrc->data + SO, 1, (size_t)n, f) == (size_t)n);
-  fclose(f);
-  memcpy(dsrc2->data + SO, asrc->data + SO, (size_t)n);
   fobj* adst = mk(1, (size_t)t + 32); fobj* ddst2 = mk(4, (size_t)t + 32);
   /* byte[] -> byte[] */
   memset(adst->data, 0xEE, adst->bytes);
@@ -83,16 +76,8 @@ int main(int argc, char** argv) {
   const jint consumed = get1(sz);
   CHECK(no_exc() && r > 0 && r <= t && consumed > 0 && consumed < n && g_alloc == 0 && asrc->pins == 0 && adst->pins == 0 && sz->pins == 0);
   CHECK(guarded(adst, DO, (size_t)r, 0xEE));
-  char path[4096];
-  snprintf(path, sizeof path, "%s/dest.bin", argv[3]);
-  FILE* o = fopen(path, "wb");
-  CHECK(o != NULL && fwrite(adst->data + DO, 1, (size_t)r, o) == (size_t)r);
-  fclose(o);
-  snprintf(path, sizeof path, "%s/dest.txt", argv[3]);
-  o = fopen(path, "w");
-  CHECK(o != NULL);
-  fprintf(o, "%d %d\n", (int)r, (int)consumed);
-  fclose(o);
+  write_bytes(argv[3], "dest.bin", adst->data + DO, (size_t)r);
+  write_text(argv[3], "dest.txt", "%d %d\n", (int)r, (int)consumed);
   /* direct -> direct (NULL arrays), byte[] -> direct, direct -> byte[]: the same bytes, nothing outside the slot */
   for (int shape = 0; shape < 3; shape++) {
     fobj* adst2 = mk(1, (size_t)t + 32);
@@ -124,6 +109,5 @@ int main(int argc, char** argv) {
     CHECK(memcmp(bdst->data, adst->data + DO, (size_t)r) == 0 && memcmp(bdst->data + t + 32, adst->data + DO, (size_t)r) == 0);
     for (size_t i = (size_t)t; i < (size_t)t + 32; i++) CHECK(bdst->data[i] == 0xEE);
     for (size_t i = 2 * (size_t)t + 32; i < bdst->bytes; i++) CHECK(bdst->data[i] == 0xEE); }
-  printf("fake_jni_destsize: %d checks ok\n", g_checks);
-  return 0;
+  return checks_ok(NULL);
 }

@@ -2,7 +2,8 @@
  *
  * The dictionary natives of the JNI shim (LZ4HIPJNI.LZ4HIP_dictCreate / dictSize / dictFree, LZ4HIP_decompress_safe_dict and
  * LZ4HIP_batchSafeDict) executed without a JVM, with the fake JNIEnv of fake_env.h (a byte[] / int[] / long[] is a malloc'd buffer with
- * pin accounting, a direct ByteBuffer is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built by
+ * pin accounting, a direct ByteBuffer is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built (build_fake_jni of
+ * tests/support.py; the shared file reading, output files and closing line are fake_env.h's) by
  * tests/test_dict_abi.py / tests/test_gpu_dict.py.
  *
  *   fake_jni_dict --no-gpu                           anywhere: NULL arguments are argument errors, a handle is created, sized and freed
@@ -31,25 +32,11 @@ JNIEXPORT jstring JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_lastError(JNIEnv*, jcla
 #define DEC Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decompress_1safe_1dict
 #define BATCH Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafeDict
 
-static fobj* slurp(const char* path, int kind, size_t lead, long* n_out) {
-  FILE* f = fopen(path, "rb");
-  CHECK(f != NULL);
-  fseek(f, 0, SEEK_END);
-  const long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  CHECK(n >= 0 && n < (1 << 24));
-  fobj* o = mk(kind, (size_t)n + lead + 16);
-  CHECK(fread(o->data + lead, 1, (size_t)n, f) == (size_t)n);
-  fclose(f);
-  *n_out = n;
-  return o;
-}
-
 int main(int argc, char** argv) {
   JNIEnv* env = &g_env;
   Java_net_jpountz_lz4_LZ4HIPJNI_init(env, NULL);
   CHECK(no_exc());
-  const int no_gpu = argc > 1 && strcmp(argv[1], "--no-gpu") == 0;
+  const int no_gpu = arg_no_gpu(argc, argv);
   fobj* src = mk(1, 64); fobj* dst = mk(1, 128); fobj* dsrc = mk(4, 64); fobj* ddst = mk(4, 128);
   /* handles: NULL / negative arguments give 0 and a message; a heap array and a direct buffer give a handle that knows its length --
    * with or without a device; nothing stays pinned or allocated in the shim */
@@ -94,8 +81,7 @@ int main(int argc, char** argv) {
     const char* msg = (const char*)Java_net_jpountz_lz4_LZ4HIPJNI_lastError(env, NULL);
     CHECK(msg && strlen(msg) > 0);
     FREE(env, NULL, h0); FREE(env, NULL, h1); FREE(env, NULL, h2);
-    printf("fake_jni_dict: %d checks ok (no device: every decode failed loudly)\n", g_checks);
-    return 0;
+    return checks_ok("every decode failed loudly");
   }
   FREE(env, NULL, h0); FREE(env, NULL, h1); FREE(env, NULL, h2);
   if (argc < 5) { fprintf(stderr, "usage: fake_jni_dict --no-gpu | <dict> <stream> <cap> <out-dir>\n"); return 2; }
@@ -104,8 +90,7 @@ int main(int argc, char** argv) {
   fobj* adict = slurp(argv[1], 1, 3, &dn);
   fobj* asrc = slurp(argv[2], 1, SO, &n);
   CHECK(n > 0);
-  fobj* dsrc2 = mk(4, asrc->bytes);
-  memcpy(dsrc2->data, asrc->data, asrc->bytes);
+  fobj* dsrc2 = copy_as(asrc, 4);
   const int cap = atoi(argv[3]);
   CHECK(cap >= 0);
   const jlong h = CREATE(env, NULL, (jbyteArray)adict, NULL, 3, (jint)dn);
@@ -118,16 +103,8 @@ int main(int argc, char** argv) {
   CHECK(no_exc() && !LZ4HIP_IS_LIB_ERROR(r) && r <= cap && g_alloc == 0 && asrc->pins == 0 && adst->pins == 0);
   const size_t got = r > 0 ? (size_t)r : 0;
   CHECK(guarded(adst, DO, got, 0xEE));
-  char path[4096];
-  snprintf(path, sizeof path, "%s/dict.bin", argv[4]);
-  FILE* o = fopen(path, "wb");
-  CHECK(o != NULL && fwrite(adst->data + DO, 1, got, o) == got);
-  fclose(o);
-  snprintf(path, sizeof path, "%s/dict.txt", argv[4]);
-  o = fopen(path, "w");
-  CHECK(o != NULL);
-  fprintf(o, "%d\n", (int)r);
-  fclose(o);
+  write_bytes(argv[4], "dict.bin", adst->data + DO, got);
+  write_text(argv[4], "dict.txt", "%d\n", (int)r);
   /* direct -> direct (NULL arrays), byte[] -> direct, direct -> byte[]: the same result, nothing written outside the slot */
   for (int shape = 0; shape < 3; shape++) {
     fobj* adst2 = mk(1, (size_t)cap + 32);
@@ -162,6 +139,5 @@ int main(int argc, char** argv) {
     for (size_t i = (size_t)cap; i < (size_t)cap + 32; i++) CHECK(bdst->data[i] == 0xEE);
     for (size_t i = 2 * (size_t)cap + 32; i < bdst->bytes; i++) CHECK(bdst->data[i] == 0xEE); }
   FREE(env, NULL, h);
-  printf("fake_jni_dict: %d checks ok\n", g_checks);
-  return 0;
+  return checks_ok(NULL);
 }

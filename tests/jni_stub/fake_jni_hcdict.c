@@ -2,7 +2,8 @@
  *
  * The dictionary HC compress natives of the JNI shim (LZ4HIPJNI.LZ4HIP_compress_hc_dict and LZ4HIP_batchCompressHCDict, over the handles of
  * LZ4HIP_dictCreate) executed without a JVM, with the fake JNIEnv of fake_env.h (a byte[] / int[] / long[] is a malloc'd buffer with pin
- * accounting, a direct ByteBuffer is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built by
+ * accounting, a direct ByteBuffer is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built (build_fake_jni of
+ * tests/support.py; the shared file reading, output files and closing line are fake_env.h's) by
  * tests/test_hcdict_abi.py / tests/test_gpu_hcdict.py.
  *
  *   fake_jni_hcdict --no-gpu                     anywhere: NULL arguments and a 0 handle are argument errors, every compress fails LOUDLY
@@ -30,25 +31,11 @@ JNIEXPORT jstring JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_lastError(JNIEnv*, jcla
 #define BATCH(e, c, h, ...) Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchCompressHCDict(e, c, h, g_level, __VA_ARGS__)
 static jint g_level = 9;
 
-static fobj* slurp(const char* path, int kind, size_t lead, long* n_out) {
-  FILE* f = fopen(path, "rb");
-  CHECK(f != NULL);
-  fseek(f, 0, SEEK_END);
-  const long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  CHECK(n >= 0 && n < (1 << 24));
-  fobj* o = mk(kind, (size_t)n + lead + 16);
-  CHECK(fread(o->data + lead, 1, (size_t)n, f) == (size_t)n);
-  fclose(f);
-  *n_out = n;
-  return o;
-}
-
 int main(int argc, char** argv) {
   JNIEnv* env = &g_env;
   Java_net_jpountz_lz4_LZ4HIPJNI_init(env, NULL);
   CHECK(no_exc());
-  const int no_gpu = argc > 1 && strcmp(argv[1], "--no-gpu") == 0;
+  const int no_gpu = arg_no_gpu(argc, argv);
   fobj* src = mk(1, 64); fobj* dst = mk(1, 128); fobj* dsrc = mk(4, 64); fobj* ddst = mk(4, 128);
   fobj* dbytes = mk(1, 100);
   for (size_t i = 0; i < dbytes->bytes; i++) dbytes->data[i] = (uint8_t)(i * 7u);
@@ -81,8 +68,7 @@ int main(int argc, char** argv) {
     const char* msg = (const char*)Java_net_jpountz_lz4_LZ4HIPJNI_lastError(env, NULL);
     CHECK(msg && strlen(msg) > 0);
     FREE(env, NULL, h1);
-    printf("fake_jni_hcdict: %d checks ok (no device: every compress failed loudly)\n", g_checks);
-    return 0;
+    return checks_ok("every compress failed loudly");
   }
   FREE(env, NULL, h1);
   if (argc < 5) { fprintf(stderr, "usage: fake_jni_hcdict --no-gpu | <dict> <record> <out-dir> <level>\n"); return 2; }
@@ -91,8 +77,7 @@ int main(int argc, char** argv) {
   const size_t SO = 5, DO = 7;
   fobj* adict = slurp(argv[1], 1, 3, &dn);
   fobj* asrc = slurp(argv[2], 1, SO, &n);
-  fobj* dsrc2 = mk(4, asrc->bytes);
-  memcpy(dsrc2->data, asrc->data, asrc->bytes);
+  fobj* dsrc2 = copy_as(asrc, 4);
   const int cap = (int)(n + n / 255 + 16);
   const jlong h = CREATE(env, NULL, (jbyteArray)adict, NULL, 3, (jint)dn);
   CHECK(h != 0 && no_exc() && SIZE(env, NULL, h) == (jint)dn && adict->pins == 0 && g_alloc == 0);
@@ -104,11 +89,7 @@ int main(int argc, char** argv) {
   CHECK(no_exc() && !LZ4HIP_IS_LIB_ERROR(r) && r > 0 && r <= cap && g_alloc == 0 && asrc->pins == 0 && adst->pins == 0);
   const size_t got = (size_t)r;
   CHECK(guarded(adst, DO, got, 0xEE));
-  char path[4096];
-  snprintf(path, sizeof path, "%s/hcdict.bin", argv[3]);
-  FILE* o = fopen(path, "wb");
-  CHECK(o != NULL && fwrite(adst->data + DO, 1, got, o) == got);
-  fclose(o);
+  write_bytes(argv[3], "hcdict.bin", adst->data + DO, got);
   /* direct -> direct (NULL arrays), byte[] -> direct, direct -> byte[]: the same result, nothing written outside the slot */
   for (int shape = 0; shape < 3; shape++) {
     fobj* adst2 = mk(1, (size_t)cap + 32);
@@ -148,6 +129,5 @@ int main(int argc, char** argv) {
     for (size_t i = (size_t)cap; i < (size_t)cap + 32; i++) CHECK(bdst->data[i] == 0xEE);
     for (size_t i = (size_t)cap + 32 + (size_t)(r - 1); i < bdst->bytes; i++) CHECK(bdst->data[i] == 0xEE); }
   FREE(env, NULL, h);
-  printf("fake_jni_hcdict: %d checks ok\n", g_checks);
-  return 0;
+  return checks_ok(NULL);
 }

@@ -2,7 +2,8 @@
  *
  * The partial-decode natives of the JNI shim (LZ4HIPJNI.LZ4HIP_decompress_safe_partial and LZ4HIP_batchSafePartial) executed without a
  * JVM, with the fake JNIEnv of fake_env.h (a byte[] / int[] / long[] is a malloc'd buffer with pin accounting, a direct ByteBuffer
- * is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built by tests/test_partial_abi.py / tests/test_gpu_partial.py.
+ * is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built (build_fake_jni of
+ * tests/support.py; the shared file reading, output files and closing line are fake_env.h's) by tests/test_partial_abi.py / tests/test_gpu_partial.py.
  *
  *   fake_jni_partial --no-gpu                          anywhere: NULL arrays are argument errors, every compute call fails LOUDLY
  *                                                      without a device (library error code, nothing leaked or left pinned)
@@ -40,12 +41,12 @@ int main(int argc, char** argv) {
     /* heap ByteBuffers where direct ones are required */
     fobj* hb = mk(5, 64);
     CHECK(BATCH(env, NULL, (jobject)hb, (jlongArray)so, (jintArray)sl, (jobject)ddst, (jlongArray)dof, (jintArray)tl, (jintArray)dc, (jintArray)ol, 1) == LZ4HIP_E_ARG);
-    if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+    if (arg_no_gpu(argc, argv)) {
       const jint rc = BATCH(env, NULL, (jobject)dsrc, (jlongArray)so, (jintArray)sl, (jobject)ddst, (jlongArray)dof, (jintArray)tl, (jintArray)dc, (jintArray)ol, 1);
       CHECK(rc == LZ4HIP_E_NO_DEVICE && no_exc());
       for (int t = 0; t < 6; t++) CHECK(a[t]->pins == 0);
     } }
-  if (argc > 1 && strcmp(argv[1], "--no-gpu") == 0) {
+  if (arg_no_gpu(argc, argv)) {
     memset(dst->data, 0xEE, dst->bytes);
     jint r = PART(env, NULL, (jbyteArray)src, NULL, 7, 20, (jbyteArray)dst, NULL, 3, 50, 100);
     CHECK(LZ4HIP_IS_LIB_ERROR(r) && no_exc() && g_alloc == 0 && src->pins == 0 && dst->pins == 0 && guarded(dst, 0, 0, 0xEE));
@@ -53,24 +54,16 @@ int main(int argc, char** argv) {
     CHECK(LZ4HIP_IS_LIB_ERROR(r) && no_exc() && g_alloc == 0);
     const char* msg = (const char*)Java_net_jpountz_lz4_LZ4HIPJNI_lastError(env, NULL);
     CHECK(msg && strlen(msg) > 0);
-    printf("fake_jni_partial: %d checks ok (no device: every compute call failed loudly)\n", g_checks);
-    return 0;
+    return checks_ok("every compute call failed loudly");
   }
   if (argc < 5) { fprintf(stderr, "usage: fake_jni_partial --no-gpu | <stream> <target> <cap> <out-dir>\n"); return 2; }
-  FILE* f = fopen(argv[1], "rb");
-  CHECK(f != NULL);
-  fseek(f, 0, SEEK_END);
-  const long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  CHECK(n > 0 && n < (1 << 24));
+  const size_t SO = 5, DO = 7;
+  long n = 0;
+  fobj* asrc = slurp(argv[1], 1, SO, &n); fobj* dsrc2 = copy_as(asrc, 4);
+  CHECK(n > 0);
   const int t = atoi(argv[2]), cap = atoi(argv[3]);
   CHECK(t >= 0 && cap >= 0);
   const int room = t < cap ? t : cap;
-  const size_t SO = 5, DO = 7;
-  fobj* asrc = mk(1, (size_t)n + 16); fobj* dsrc2 = mk(4, (size_t)n + 16);
-  CHECK(fread(asrc->data + SO, 1, (size_t)n, f) == (size_t)n);
-  fclose(f);
-  memcpy(dsrc2->data + SO, asrc->data + SO, (size_t)n);
   fobj* adst = mk(1, (size_t)cap + 32); fobj* ddst2 = mk(4, (size_t)cap + 32);
   /* byte[] -> byte[] */
   memset(adst->data, 0xEE, adst->bytes);
@@ -78,16 +71,8 @@ int main(int argc, char** argv) {
   CHECK(no_exc() && !LZ4HIP_IS_LIB_ERROR(r) && r <= room && g_alloc == 0 && asrc->pins == 0 && adst->pins == 0);
   const size_t got = r > 0 ? (size_t)r : 0;
   CHECK(guarded(adst, DO, got, 0xEE));
-  char path[4096];
-  snprintf(path, sizeof path, "%s/partial.bin", argv[4]);
-  FILE* o = fopen(path, "wb");
-  CHECK(o != NULL && fwrite(adst->data + DO, 1, got, o) == got);
-  fclose(o);
-  snprintf(path, sizeof path, "%s/partial.txt", argv[4]);
-  o = fopen(path, "w");
-  CHECK(o != NULL);
-  fprintf(o, "%d\n", (int)r);
-  fclose(o);
+  write_bytes(argv[4], "partial.bin", adst->data + DO, got);
+  write_text(argv[4], "partial.txt", "%d\n", (int)r);
   /* direct -> direct (NULL arrays), byte[] -> direct, direct -> byte[]: the same result, nothing written past DO + room */
   for (int shape = 0; shape < 3; shape++) {
     fobj* adst2 = mk(1, (size_t)cap + 32);
@@ -122,6 +107,5 @@ int main(int argc, char** argv) {
     CHECK(memcmp(bdst->data, adst->data + DO, got) == 0);
     for (size_t i = (size_t)room; i < (size_t)cap + 32; i++) CHECK(bdst->data[i] == 0xEE);
     for (size_t i = (size_t)cap + 32; i < bdst->bytes; i++) CHECK(bdst->data[i] == 0xEE); }
-  printf("fake_jni_partial: %d checks ok\n", g_checks);
-  return 0;
+  return checks_ok(NULL);
 }

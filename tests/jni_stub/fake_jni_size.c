@@ -2,7 +2,8 @@
  *
  * The decoded-size natives of the JNI shim (LZ4HIPJNI.LZ4HIP_decompressed_length and LZ4HIP_batchDecompressedLengths) executed without
  * a JVM, with the fake JNIEnv of fake_env.h (a byte[] / int[] / long[] is a malloc'd buffer with pin accounting, a direct ByteBuffer
- * is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built by tests/test_size_abi.py / tests/test_gpu_size.py.
+ * is a pointer; the shim's malloc / free are counted through shim_alloc.h).  Built (build_fake_jni of
+ * tests/support.py; the shared file reading, output files and closing line are fake_env.h's) by tests/test_size_abi.py / tests/test_gpu_size.py.
  *
  *   fake_jni_size --no-gpu                  anywhere: NULL arrays are argument errors, every compute call fails LOUDLY without a
  *                                           device (library error code, nothing leaked or left pinned)
@@ -26,7 +27,7 @@ int main(int argc, char** argv) {
   JNIEnv* env = &g_env;
   Java_net_jpountz_lz4_LZ4HIPJNI_init(env, NULL);
   CHECK(no_exc());
-  const int no_gpu = argc > 1 && strcmp(argv[1], "--no-gpu") == 0;
+  const int no_gpu = arg_no_gpu(argc, argv);
   fobj* src = mk(1, 64); fobj* dsrc = mk(4, 64);
   /* NULL arrays / buffers of the batch native: LZ4HIP_E_ARG, nothing pinned */
   { fobj* so = mk(3, 8); fobj* sl = int1(20); fobj* dc = int1(100); fobj* ol = int1(-7);
@@ -52,35 +53,22 @@ int main(int argc, char** argv) {
     CHECK(LZ4HIP_IS_LIB_ERROR(r) && no_exc() && g_alloc == 0);
     const char* msg = (const char*)Java_net_jpountz_lz4_LZ4HIPJNI_lastError(env, NULL);
     CHECK(msg && strlen(msg) > 0);
-    printf("fake_jni_size: %d checks ok (no device: every compute call failed loudly)\n", g_checks);
-    return 0;
+    return checks_ok("every compute call failed loudly");
   }
   if (argc < 4) { fprintf(stderr, "usage: fake_jni_size --no-gpu | <stream> <cap> <out-dir>\n"); return 2; }
-  FILE* f = fopen(argv[1], "rb");
-  CHECK(f != NULL);
-  fseek(f, 0, SEEK_END);
-  const long n = ftell(f);
-  fseek(f, 0, SEEK_SET);
-  CHECK(n > 0 && n < (1 << 24));
+  const size_t SO = 5;
+  long n = 0;
+  fobj* asrc = slurp(argv[1], 1, SO, &n); fobj* dsrc2 = copy_as(asrc, 4);
+  CHECK(n > 0);
   const int cap = atoi(argv[2]);
   CHECK(cap >= 0);
-  const size_t SO = 5;
-  fobj* asrc = mk(1, (size_t)n + 16); fobj* dsrc2 = mk(4, (size_t)n + 16);
-  CHECK(fread(asrc->data + SO, 1, (size_t)n, f) == (size_t)n);
-  fclose(f);
-  memcpy(dsrc2->data + SO, asrc->data + SO, (size_t)n);
   /* byte[] */
   const jint r = SIZE(env, NULL, (jbyteArray)asrc, NULL, (jint)SO, (jint)n, cap);
   CHECK(no_exc() && !LZ4HIP_IS_LIB_ERROR(r) && r <= cap && g_alloc == 0 && asrc->pins == 0);
   /* direct buffer: the same value, nothing staged */
   const jint r2 = SIZE(env, NULL, NULL, (jobject)dsrc2, (jint)SO, (jint)n, cap);
   CHECK(no_exc() && r2 == r && g_alloc == 0);
-  char path[4096];
-  snprintf(path, sizeof path, "%s/size.txt", argv[3]);
-  FILE* o = fopen(path, "w");
-  CHECK(o != NULL);
-  fprintf(o, "%d\n", (int)r);
-  fclose(o);
+  write_text(argv[3], "size.txt", "%d\n", (int)r);
   /* a source array that cannot be pinned: OutOfMemoryError, nothing leaked */
   { fobj* nopin = mk(1, (size_t)n + 16); nopin->refuse_pin = 1;
     (void)SIZE(env, NULL, (jbyteArray)nopin, NULL, (jint)SO, (jint)n, cap);
@@ -98,11 +86,6 @@ int main(int argc, char** argv) {
     CHECK(rc == 0 && no_exc() && out[0] == r && so->pins == 0 && sl->pins == 0 && dc->pins == 0 && ol->pins == 0 && g_alloc == 0);
     CHECK(out[1] == SIZE(env, NULL, NULL, (jobject)dsrc2, (jint)SO, (jint)n, 0));
     CHECK(out[2] == SIZE(env, NULL, NULL, (jobject)dsrc2, (jint)SO, (jint)n - 1, cap));
-    snprintf(path, sizeof path, "%s/size_batch.txt", argv[3]);
-    o = fopen(path, "w");
-    CHECK(o != NULL);
-    fprintf(o, "%d %d %d\n", (int)out[0], (int)out[1], (int)out[2]);
-    fclose(o); }
-  printf("fake_jni_size: %d checks ok\n", g_checks);
-  return 0;
+    write_text(argv[3], "size_batch.txt", "%d %d %d\n", (int)out[0], (int)out[1], (int)out[2]); }
+  return checks_ok(NULL);
 }

@@ -2,32 +2,23 @@
 so that the C ABI's multi-device branch (csrc/api.cpp: D > 1 -- one thread + staging set per listed device, contiguous block ranges
 per device) runs on a box with one GPU, then pushes a ragged multi-chunk batch through every host-pointer batch
 entry point and checks every size / return code / hash and a byte sample against the reference library.  Prints 'multidev ok D=<D>'."""
-import ctypes as C
-import importlib
-import os
 import random
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np  # noqa: E402
-from oracle import oracle as O  # noqa: E402
+import numpy as np
+from support import init_repeated, offsets   # (first: it puts the repository root on sys.path)
+from oracle import oracle as O
 
 D = int(sys.argv[1])
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 5200
-amd = importlib.import_module("lz4-java_amd")
-L = amd.lib()
-ids = (C.c_int * D)(*([0] * D))
-assert L.lz4hip_init(ids, D) == 0, L.lz4hip_last_error()
-assert L.lz4hip_device_count() == D
+amd, L = init_repeated(D)
 ref = O.ref()
 rng = random.Random(50 + D)
 base = [O.gen_block(65536, 100 + s) for s in range(24)] + [rng.randbytes(65536) for _ in range(4)] + [bytes(65536)]
 lens = [rng.choice([65536, 65536, 65536, rng.randrange(0, 65537), rng.randrange(13, 2000)]) for _ in range(n)]
 srcs = [base[i % len(base)][:ln] for i, ln in enumerate(lens)]
 src = b"".join(srcs)
-so = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+so = offsets(lens)
 memo = {}
 
 
@@ -39,7 +30,7 @@ def clen(v):
 
 want = [len(clen(v)) for v in srcs]
 caps = [amd.maxCompressedLength(ln) if i % 7 else max(0, want[i] - 1) for i, ln in enumerate(lens)]   # every 7th: one byte short -> 0
-do = np.concatenate([[0], np.cumsum(caps)[:-1]]).astype(np.uint64)
+do = offsets(caps)
 dst = bytearray(int(sum(caps)) + 1)
 out = amd.LZ4HIPBatch.compress(src, so, np.array(lens, dtype=np.int32), dst, do, np.array(caps, dtype=np.int32))
 for i in range(n):
@@ -74,7 +65,7 @@ for i in sorted(edge | set(rng.sample(range(n), 600))):
 # HC level 9 through the device list as well (>= 64 blocks per listed device so that the batch is split)
 m = 64 * D + 7
 hcaps = [amd.maxCompressedLength(x) for x in lens[:m]]
-hdo = np.concatenate([[0], np.cumsum(hcaps)[:-1]]).astype(np.uint64)
+hdo = offsets(hcaps)
 hdst = bytearray(int(sum(hcaps)) + 1)
 hout = amd.LZ4HIPBatch.compressHC(src, so[:m], np.array(lens[:m], dtype=np.int32), hdst, hdo, np.array(hcaps, dtype=np.int32), 9)
 for i in range(m):

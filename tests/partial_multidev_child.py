@@ -2,26 +2,17 @@
 decoder's host batch takes the multi-device branch of csrc/api.cpp (contiguous block ranges per listed device) on a box with one GPU,
 and checks a ragged batch -- return values, bytes and the untouched bytes behind every result -- against the reference library's
 LZ4_decompress_safe_partial.  Prints 'partial multidev ok D=<D>'."""
-import ctypes as C
-import importlib
-import os
 import random
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np  # noqa: E402
-from oracle import oracle as O  # noqa: E402
-from partial_common import ref_partial  # noqa: E402
+import numpy as np
+from support import check_slots, init_repeated, slots   # (first: it puts the repository root on sys.path)
+from oracle import oracle as O
+from partial_common import ref_partial
 
 D = int(sys.argv[1])
 n = 64 * D * 3 + 11
-amd = importlib.import_module("lz4-java_amd")
-L = amd.lib()
-ids = (C.c_int * D)(*([0] * D))
-assert L.lz4hip_init(ids, D) == 0, L.lz4hip_last_error()
-assert L.lz4hip_device_count() == D
+amd, L = init_repeated(D)
 ref = O.ref()
 lz4p = ref_partial(ref)
 
@@ -40,15 +31,8 @@ for i in range(n):
     targets.append(t)
     caps.append(rng.choice([t, t + 100, max(t - 7, 0), sizes[k]]))
 want = [lz4p(s, t, c) for s, t, c in zip(srcs, targets, caps)]
-so = np.concatenate([[0], np.cumsum([len(s) for s in srcs])[:-1]]).astype(np.uint64)
-do = np.concatenate([[0], np.cumsum([c + 8 for c in caps])[:-1]]).astype(np.uint64)
-dst = bytearray(b"\xee" * (int(sum(caps)) + 8 * n))
+so, do, dst = slots(srcs, caps)
 out = amd.LZ4HIPBatch.decompressSafePartial(b"".join(srcs), so, np.array([len(s) for s in srcs], dtype=np.int32), dst, do,
                                             np.array(targets, dtype=np.int32), np.array(caps, dtype=np.int32))
-for i in range(n):
-    r, b = want[i]
-    assert int(out[i]) == r, ("result", i, len(srcs[i]), targets[i], caps[i], int(out[i]), r)
-    o = int(do[i])
-    assert bytes(dst[o:o + max(r, 0)]) == b, ("bytes", i)
-    assert dst[o + max(r, 0):o + caps[i] + 8] == b"\xee" * (caps[i] + 8 - max(r, 0)), ("written past the result", i)
+check_slots(out, dst, do, caps, want, srcs, extra=lambda i: (targets[i],))
 print("partial multidev ok D=%d blocks=%d" % (D, n))

@@ -2,26 +2,17 @@
 query's host batch takes the multi-device branch of csrc/api.cpp (contiguous block ranges per listed device) on a box with one GPU,
 and checks a ragged batch -- valid, cut and damaged streams at capacities around their sizes -- against the return value of the
 reference library's LZ4_decompress_safe.  Prints 'size multidev ok D=<D>'."""
-import ctypes as C
-import importlib
-import os
 import random
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np  # noqa: E402
-from oracle import oracle as O  # noqa: E402
-from size_common import ref_size  # noqa: E402
+import numpy as np
+from support import init_repeated, offsets   # (first: it puts the repository root on sys.path)
+from oracle import oracle as O
+from size_common import ref_size
 
 D = int(sys.argv[1])
 n = 64 * D * 3 + 11
-amd = importlib.import_module("lz4-java_amd")
-L = amd.lib()
-ids = (C.c_int * D)(*([0] * D))
-assert L.lz4hip_init(ids, D) == 0, L.lz4hip_last_error()
-assert L.lz4hip_device_count() == D
+amd, L = init_repeated(D)
 ref = O.ref()
 want = ref_size(ref)
 
@@ -41,7 +32,7 @@ for i in range(n):
     srcs.append(s)
     caps.append(rng.choice([0, 63, 64, 65, sizes[k] - 1, sizes[k], sizes[k] + 1, sizes[k] + 64, sizes[k] + 606, sizes[k] + 607, 2 * sizes[k]]))
 w = [want(s, c) for s, c in zip(srcs, caps)]
-so = np.concatenate([[0], np.cumsum([len(s) for s in srcs])[:-1]]).astype(np.uint64)
+so = offsets([len(s) for s in srcs])
 out = amd.LZ4HIPBatch.decompressedLengths(b"".join(srcs) + b"\0", so, np.array([len(s) for s in srcs], dtype=np.int32), np.array(caps, dtype=np.int32))
 for i in range(n):
     assert int(out[i]) == w[i], ("result", i, len(srcs[i]), caps[i], int(out[i]), w[i])

@@ -7,6 +7,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from support import build_fake_jni, build_mirror, typecheck_jni_shim
 
 
 def header_symbols():
@@ -136,12 +137,8 @@ def test_fails_loudly_without_gpu(amd):
 def test_cpp_host_mirror_builds_and_jni_shim_typechecks():
     """the compiled-language mirror of the reference's host API links against the C ABI; the JNI shim
     type-checks against a stub jni.h (no JDK in this image)"""
-    exe = os.path.join(ROOT, "tests", "cpp", "host_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "host_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    subprocess.check_call(["gcc", "-fsyntax-only", "-Wall", "-std=c11", "-I" + os.path.join(ROOT, "tests", "jni_stub"),
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "lz4-java_amd", "jni", "net_jpountz_lz4_LZ4HIPJNI.c")])
+    exe = build_mirror("host_mirror_test", os.path.join(ROOT, "tests", "cpp"))
+    typecheck_jni_shim()
     import torch
     if not torch.cuda.is_available():
         assert subprocess.call([exe], stderr=subprocess.DEVNULL) == 3   # loud failure, no CPU path
@@ -150,10 +147,7 @@ def test_cpp_host_mirror_builds_and_jni_shim_typechecks():
 def test_cpp_stream_mirror_builds():
     """the C++ twins of the reference's stream / container classes (lz4-java_amd/host/lz4hip_streams.hpp) compile warning-free
     and link against the C ABI; without a GPU they fail loudly like everything else"""
-    exe = os.path.join(ROOT, "tests", "cpp", "stream_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpp", "stream_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("stream_mirror_test", os.path.join(ROOT, "tests", "cpp"), werror=True)
     import torch
     if not torch.cuda.is_available():
         import tempfile
@@ -191,9 +185,8 @@ def test_jni_shim_executes_against_fake_jnienv_without_device():
     import torch
     if torch.cuda.is_available():
         pytest.skip("a device is present: covered by tests/test_gpu_jni.py")
-    d = os.path.join(ROOT, "tests", "jni_stub")
-    subprocess.check_call(["bash", os.path.join(d, "build.sh")])
-    out = subprocess.check_output([os.path.join(d, "fake_jni"), "--no-gpu"]).decode()
+    exe = build_fake_jni("fake_jni", os.path.join(ROOT, "tests", "jni_stub"))
+    out = subprocess.check_output([exe, "--no-gpu"]).decode()
     assert "checks ok" in out, out
 
 

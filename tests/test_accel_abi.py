@@ -9,14 +9,9 @@ import subprocess
 import pytest
 
 from conftest import ROOT
-from jni_build import build_fake_jni
+from support import E_NO_DEVICE, LIB_ERROR, build_fake_jni, build_mirror, no_device
 
 NEW = ("lz4hip_compress_fast_accel_batch", "lz4hip_compress_fast_accel_batch_dev", "lz4hip_compress_fast_accel")
-
-
-def no_device():
-    import torch
-    return not torch.cuda.is_available()
 
 
 def test_accel_symbols_declared_exported_and_bound(amd):
@@ -41,9 +36,9 @@ def test_accel_entry_points_fail_loudly_without_device(amd):
     src, dst = (C.c_uint8 * 64)(), (C.c_uint8 * 128)()
     so, sl, do, dc, out = (C.c_uint64 * 1)(0), (C.c_int32 * 1)(40), (C.c_uint64 * 1)(0), (C.c_int32 * 1)(100), (C.c_int32 * 1)(7)
     for a in (-5, 0, 1, 2, 8, 65537, 10 ** 6):
-        assert l.lz4hip_compress_fast_accel_batch(src, so, sl, dst, do, dc, out, 1, a) == -1            # LZ4HIP_E_NO_DEVICE
-        assert l.lz4hip_compress_fast_accel_batch_dev(src, so, sl, dst, do, dc, out, 1, a, 0, None) == -1
-        assert l.lz4hip_compress_fast_accel(src, 40, dst, 100, a) == -2 ** 31 + 1                       # LZ4HIP_LIB_ERROR(E_NO_DEVICE)
+        assert l.lz4hip_compress_fast_accel_batch(src, so, sl, dst, do, dc, out, 1, a) == E_NO_DEVICE
+        assert l.lz4hip_compress_fast_accel_batch_dev(src, so, sl, dst, do, dc, out, 1, a, 0, None) == E_NO_DEVICE
+        assert l.lz4hip_compress_fast_accel(src, 40, dst, 100, a) == LIB_ERROR(E_NO_DEVICE)
         assert out[0] == 7
     with pytest.raises(amd.LZ4HIPError):
         amd.LZ4HIPCompressor(acceleration=8).compress(b"hello hello hello hello")
@@ -99,9 +94,7 @@ int main() {
   } catch (const std::exception&) { return 3; }
 }
 ''')
-    exe = str(tmp_path / "accel_mirror")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, str(cpp), "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("accel_mirror", tmp_path, src=cpp)
     if no_device():
         p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL)
         assert p.returncode == 3 and p.stdout.decode().strip() == "8"   # loud failure, no CPU path

@@ -2,13 +2,12 @@
 FastCore<..., ACC = true> of lz4-java_amd/csrc/lz4_fast_core.h -- the core compress_fast_accel_cu_kernel runs -- against the lock-step
 lane simulator, and this file checks it bit-for-bit against the reference library's own LZ4_compress_fast."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import pytest
 
-from conftest import ROOT, rnd_inputs
+from conftest import rnd_inputs
+from support import build_sim
 
 _u8p = C.POINTER(C.c_uint8)
 ACCELS = (-5, 0, 1, 2, 3, 4, 7, 8, 9, 16, 17, 63, 64, 65, 100, 1000, 65536, 65537, 65538)
@@ -20,12 +19,7 @@ def clamp(a):
 
 
 def load_sim():
-    d = os.path.join(ROOT, "tests", "hostsim")
-    so = os.path.join(d, "libhostsim_accel.so")
-    srcs = [os.path.join(d, f) for f in ("hostsim_accel.cpp", "wave_host.h")] + [os.path.join(ROOT, "lz4-java_amd", "csrc", "lz4_fast_core.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(d, "hostsim_accel.cpp")])
-    l = C.CDLL(so)
+    l = build_sim("hostsim_accel")
     l.sim_compress_fast_accel.restype = C.c_int
     l.sim_compress_fast_accel.argtypes = [C.c_char_p, C.c_int, _u8p, C.c_int, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint64]
     l.sim_accel_offsets.restype = None

@@ -11,16 +11,10 @@ import pytest
 
 from conftest import ROOT
 from chain_common import CHAIN_STOPPED
-from jni_build import build_fake_jni
+from support import E_ARG, E_NO_DEVICE, build_fake_jni, build_mirror, no_device
 
 NEW = ("lz4hip_decompress_safe_chain_batch", "lz4hip_decompress_safe_chain_batch_dev")
-E_NO_DEVICE, E_ARG = -1, -3
 u64, i32, u32, u8 = C.c_uint64, C.c_int32, C.c_uint32, C.c_uint8
-
-
-def no_device():
-    import torch
-    return not torch.cuda.is_available()
 
 
 class Call:
@@ -129,10 +123,7 @@ def test_cpp_mirror_chain_builds_and_fails_loudly(tmp_path):
     """host/lz4hip.hpp: LZ4HIPBatch::decompressSafeChain builds; tests/cpp/chain_mirror_test.cpp passes its argument checks and exits 3
     (loud library failure) without a device; host/lz4hip_streams.hpp carries the linkedBlocks switch"""
     from chain_common import Chain, chain_file
-    exe = str(tmp_path / "chain_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "chain_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("chain_mirror_test", tmp_path)
     hpp = open(os.path.join(ROOT, "lz4-java_amd", "host", "lz4hip_streams.hpp")).read()
     assert re.search(r"size_t batchBlocks = 64,\s+bool linkedBlocks = false\)", hpp)
     if no_device():

@@ -6,14 +6,12 @@ decoded length and the bytes of every chain of tests/chain_common.py against the
 simulator flags every access outside the streams, the history, the chain's earlier output and the current block's capacity, every
 write outside that capacity, and a changed guard or history byte; each chain runs in both arena layouts (hostsim_chain.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-from conftest import ROOT
 from chain_common import (CHAIN_STOPPED, OFFSET_RULE_P, Chain, RefChain, book1, both_ways, case_set, end_rule_chains, offset_rule_chains,
                           rng_for, seq_block)
+from support import build_sim
 
 # (library, form, lanes): the exact tiers alone; plain; pipelined; deep with the pipelined loop behind it (decode_chain_kernel<8>)
 FORMS = (("exact", 0, 8), ("exact", 0, 4), ("full", 0, 8), ("full", 1, 8), ("full", 2, 8), ("full", 2, 16))
@@ -21,16 +19,9 @@ FILL = 0x5A
 
 
 def load_sims():
-    d = os.path.join(ROOT, "tests", "hostsim")
-    csrc = os.path.join(ROOT, "lz4-java_amd", "csrc")
-    srcs = [os.path.join(d, f) for f in ("hostsim_chain.cpp", "group_host.h", "wave_host.h")] + \
-           [os.path.join(csrc, f) for f in os.listdir(csrc) if f.startswith("lz4_decode_") or f == "kernels.h"]
     libs = {}
-    for name, so, flags in (("full", "libhostsim_chain.so", []), ("exact", "libhostsim_chain_exact.so", ["-DLZ4HIP_DECODE_INTERIOR=0"])):
-        so = os.path.join(d, so)
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread"] + flags + ["-o", so, os.path.join(d, "hostsim_chain.cpp")])
-        l = C.CDLL(so)
+    for name, variant, flags in (("full", "", ()), ("exact", "_exact", ("-DLZ4HIP_DECODE_INTERIOR=0",))):
+        l = build_sim("hostsim_chain", variant, flags)
         l.sim_chain.restype = C.c_int
         l.sim_chain.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_int,
                                 C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint8, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -9,16 +9,9 @@ import subprocess
 import pytest
 
 from conftest import ROOT
-from jni_build import build_fake_jni
+from support import E_ARG, E_NO_DEVICE, LIB_ERROR, build_fake_jni, build_mirror, no_device
 
 NEW = ("lz4hip_compress_dest_size_batch", "lz4hip_compress_dest_size_batch_dev", "lz4hip_compress_dest_size")
-LIB_ERROR = lambda status: -2 ** 31 + (-status)   # LZ4HIP_LIB_ERROR
-E_NO_DEVICE, E_ARG = -1, -3
-
-
-def no_device():
-    import torch
-    return not torch.cuda.is_available()
 
 
 def test_dest_size_symbols_declared_exported_and_bound(amd):
@@ -177,9 +170,7 @@ int main() {
   } catch (const lz4::LZ4Exception&) { std::printf("%d\n", len); return 3; }
 }
 ''')
-    exe = str(tmp_path / "dest_mirror")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, str(cpp), "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip",
-                           "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("dest_mirror", tmp_path, src=cpp)
     if no_device():
         p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL)
         assert p.returncode == 3 and p.stdout.decode().strip() == "1000"   # loud failure, srcLen untouched

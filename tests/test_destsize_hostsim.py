@@ -3,13 +3,12 @@ DirectOut<..., FILL = true> of lz4-java_amd/csrc/lz4_fast_core.h -- the core com
 lock-step lane simulator, with the simulator's bounds set to [src, src+n) and [dst, dst+target), and this file checks return value,
 consumed size and bytes against the reference library's own LZ4_compress_destSize."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import pytest
 
-from conftest import ROOT, calgary, rnd_inputs
+from conftest import calgary, rnd_inputs
+from support import build_sim
 
 _u8p = C.POINTER(C.c_uint8)
 
@@ -19,12 +18,7 @@ def bound(n):
 
 
 def load_sim():
-    d = os.path.join(ROOT, "tests", "hostsim")
-    so = os.path.join(d, "libhostsim_destsize.so")
-    srcs = [os.path.join(d, f) for f in ("hostsim_destsize.cpp", "wave_host.h")] + [os.path.join(ROOT, "lz4-java_amd", "csrc", "lz4_fast_core.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(d, "hostsim_destsize.cpp")])
-    l = C.CDLL(so)
+    l = build_sim("hostsim_destsize")
     l.sim_compress_dest_size.restype = C.c_int
     l.sim_compress_dest_size.argtypes = [C.c_char_p, C.c_int, _u8p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_uint64), C.c_uint64]
     return l

@@ -6,29 +6,20 @@ x dictionary of tests/dict_common.py against the reference library's own LZ4_dec
 access outside the stream, the dictionary and [dst, dst + cap); each case runs in both arena layouts (hostsim_dict.cpp), so a read past
 either end of the dictionary is caught."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-from conftest import ROOT
 from dict_common import DICT_LENS, RefDict, book1, caps_for, case_set, hand_streams, rng_for
+from support import build_sim
 
 # (library, form, lanes): the exact tiers alone; plain; staged (decode_dict_kernel<4, 0, true>); deep (decode_dict_deep_kernel<8>); pipelined
 FORMS = (("exact", 0, 4), ("exact", 0, 8), ("full", 0, 4), ("full", 0, 8), ("full", 1, 4), ("full", 2, 8), ("full", 3, 8))
 
 
 def load_sims():
-    d = os.path.join(ROOT, "tests", "hostsim")
-    csrc = os.path.join(ROOT, "lz4-java_amd", "csrc")
-    srcs = [os.path.join(d, f) for f in ("hostsim_dict.cpp", "group_host.h", "wave_host.h")] + \
-           [os.path.join(csrc, f) for f in os.listdir(csrc) if f.startswith("lz4_decode_")]
     libs = {}
-    for name, so, flags in (("full", "libhostsim_dict.so", []), ("exact", "libhostsim_dict_exact.so", ["-DLZ4HIP_DECODE_INTERIOR=0"])):
-        so = os.path.join(d, so)
-        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread"] + flags + ["-o", so, os.path.join(d, "hostsim_dict.cpp")])
-        l = C.CDLL(so)
+    for name, variant, flags in (("full", "", ()), ("exact", "_exact", ("-DLZ4HIP_DECODE_INTERIOR=0",))):
+        l = build_sim("hostsim_dict", variant, flags)
         l.sim_decompress_dict.restype = C.c_int
         l.sim_decompress_dict.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]
         libs[name] = l

@@ -5,27 +5,19 @@ shared set (tests/dictc_common.py).  Every case runs in two arena layouts; a rea
 dictionary's end or outside the source is flagged by the simulator, and the dictionary's arena neighbours hold bytes that would extend a
 match if they were read."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import pytest
 
-from conftest import ROOT
 from dictc_common import (DICT_LENS, RefDict, big_record, book1, book_records, bound, caps_for, check_hand_cases, dict_cuts, hand_cases,
                           keep_of, other_records, parse, ref_compress)
+from support import build_sim
 
 IMAGE = 32768
 
 
 def load_sim():
-    d = os.path.join(ROOT, "tests", "hostsim")
-    so = os.path.join(d, "libhostsim_dictc.so")
-    csrc = os.path.join(ROOT, "lz4-java_amd", "csrc")
-    srcs = [os.path.join(d, f) for f in ("hostsim_dictc.cpp", "wave_host.h")] + [os.path.join(csrc, f) for f in ("lz4_fast_core.h", "kernels.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(d, "hostsim_dictc.cpp")])
-    l = C.CDLL(so)
+    l = build_sim("hostsim_dictc")
     l.sim_dict_keep.restype = C.c_uint32
     l.sim_dict_keep.argtypes = [C.c_int]
     l.sim_dict_image.restype = C.c_int

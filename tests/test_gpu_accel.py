@@ -2,19 +2,17 @@
 through the host batch, the device batch, coalesced single calls, the multi-device host path, the Python factory and the JNI shim --
 checked byte for byte against the reference library's own LZ4_compress_fast (oracle.ref_path())."""
 import ctypes as C
-import os
 import random
 import subprocess
-import sys
 import threading
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, calgary, rnd_inputs
+from support import build_fake_jni, run_child
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 _u8p = C.POINTER(C.c_uint8)
 
 
@@ -148,8 +146,7 @@ def test_concurrent_single_calls_keep_their_acceleration(amd, lz4fast):
 
 def test_multidevice_host_path():
     """lz4hip_init([0, 0]) in a child process: a ragged accelerated batch across the device boundary"""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "accel_multidev_child.py"), "2"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and "accel multidev ok D=2" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "accel multidev ok D=2" in run_child("accel_multidev_child.py", "2", timeout=900)
 
 
 def test_factory_accelerated_compressor_round_trips(amd, lz4fast, O):
@@ -169,7 +166,6 @@ def test_jni_accel_native_full_scenarios(lz4fast, tmp_path):
     """the shim's new native over the fake JNIEnv (tests/jni_stub/fake_jni_accel.c): arrays, direct buffers, NULL arrays, a heap
     buffer without an address, a destination that cannot be pinned, too small a destination, the batch op; the streams of
     accelerations 1 and 8 are the reference's"""
-    from jni_build import build_fake_jni
     exe = build_fake_jni("fake_jni_accel", tmp_path)
     v = calgary("book1")[100000:165536]
     inp = tmp_path / "in.bin"

@@ -5,16 +5,13 @@ host call with chains of 1 to 70 blocks in one launch, the Python layer, the C++
 multi-device host path.  Guard bytes lie in front of every history, behind every region and between the chains; the damaged streams
 are the kind the other decoder tests use."""
 import ctypes as C
-import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from chain_common import CHAIN_STOPPED, Packed, RefChain, book1, case_set, chain_file, hand_chains, rng_for
-from jni_build import build_fake_jni
+from support import build_fake_jni, build_mirror, run_child
 import streams_common as sc
 
 pytestmark = pytest.mark.gpu
@@ -136,10 +133,7 @@ def program_cases(cases):
 
 def test_chain_cpp_mirror(cases, tmp_path):
     """tests/cpp/chain_mirror_test.cpp: LZ4HIPBatch::decompressSafeChain of host/lz4hip.hpp, two chains per call"""
-    exe = str(tmp_path / "chain_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "chain_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("chain_mirror_test", tmp_path)
     for ch, (outs, done, data) in program_cases(cases):
         (tmp_path / "c.bin").write_bytes(chain_file(ch))
         p = subprocess.run([exe, str(tmp_path / "c.bin"), str(tmp_path / "o.bin")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
@@ -179,10 +173,7 @@ def test_chain_frame_reader_with_the_engine(amd, rc, port, frame_data, tmp_path)
     if sc.LZ4_CLI is not None:
         frames += [(sc.cli(args, d), d) for args, d in ((["-1", "-B4", "-BD"], frame_data), (["-B4", "-BD", "-BX"], frame_data),
                                                         (["-B7", "-BD", "--content-size"], big))]
-    exe = str(tmp_path / "chain_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "chain_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("chain_mirror_test", tmp_path)
     for k, (frame, d) in enumerate(frames):
         assert frame[4] & 0x20 == 0
         for batch in (1, 3, 64):
@@ -198,10 +189,7 @@ def test_chain_frame_reader_with_the_engine(amd, rc, port, frame_data, tmp_path)
 
 def test_chain_multidev_host_path_on_one_gpu():
     """lz4hip_init([0] * 2): the host call takes the multi-device branch (whole chains per listed device)"""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "chain_multidev_child.py"), "2", "repeat"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=600)
-    assert p.returncode == 0, p.stderr.decode()[-3000:]
-    assert "chain multidev ok D=2" in p.stdout.decode()
+    assert "chain multidev ok D=2" in run_child("chain_multidev_child.py", "2", "repeat", timeout=600)
 
 
 def test_chain_multidev_host_path_two_gpus():
@@ -209,7 +197,4 @@ def test_chain_multidev_host_path_two_gpus():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("fewer than two GPUs")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "chain_multidev_child.py"), "2", "distinct"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=600)
-    assert p.returncode == 0, p.stderr.decode()[-3000:]
-    assert "chain multidev ok D=2" in p.stdout.decode()
+    assert "chain multidev ok D=2" in run_child("chain_multidev_child.py", "2", "distinct", timeout=600)

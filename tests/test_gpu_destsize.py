@@ -3,19 +3,17 @@ host batch, the device batch, coalesced single calls, the multi-device host path
 shim -- checked byte for byte, and consumed size for consumed size, against the reference library's own LZ4_compress_destSize
 (oracle.ref_path())."""
 import ctypes as C
-import os
 import random
 import subprocess
-import sys
 import threading
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, calgary, rnd_inputs
+from conftest import calgary, rnd_inputs
+from support import build_fake_jni, build_mirror, run_child
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 _u8p = C.POINTER(C.c_uint8)
 GUARD = 0xA5
 
@@ -242,10 +240,7 @@ def test_python_factory(amd, lz4dest, O):
 
 def test_cpp_mirror(lz4dest, tmp_path):
     """tests/cpp/destsize_mirror_test.cpp: LZ4HIPCompressor::compressDestSize of host/lz4hip.hpp, against the reference"""
-    exe = str(tmp_path / "destsize_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "destsize_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("destsize_mirror_test", tmp_path)
     v = calgary("book1")[7000:90000]
     (tmp_path / "in.bin").write_bytes(v)
     for t in (100, 4096, 30000):
@@ -259,7 +254,6 @@ def test_cpp_mirror(lz4dest, tmp_path):
 def test_jni_dest_size_full_scenarios(lz4dest, tmp_path):
     """the shim's new natives over the fake JNIEnv (tests/jni_stub/fake_jni_destsize.c): arrays, direct buffers, NULL arrays, a
     destination that cannot be pinned, the batch native; the stream and consumed size are the reference's"""
-    from jni_build import build_fake_jni
     exe = build_fake_jni("fake_jni_destsize", tmp_path)
     v = calgary("book1")[100000:165536]
     (tmp_path / "in.bin").write_bytes(v)
@@ -272,5 +266,4 @@ def test_jni_dest_size_full_scenarios(lz4dest, tmp_path):
 
 def test_multidevice_host_path():
     """lz4hip_init([0, 0]) in a child process: a ragged destSize batch across the device boundary"""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "destsize_multidev_child.py"), "2"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and "destsize multidev ok D=2" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "destsize multidev ok D=2" in run_child("destsize_multidev_child.py", "2", timeout=900)

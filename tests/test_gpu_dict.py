@@ -3,16 +3,14 @@ the shared set of tests/dict_common.py (every stream x capacity x dictionary) in
 guard bytes around every destination slot, both kernels (below and from 40960 blocks on), the host batch, coalesced single calls from
 eight threads on two handles, a handle of length 0, the Python layers, the C++ mirror, the JNI shim and the multi-device host path."""
 import ctypes as C
-import os
 import subprocess
-import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from dict_common import DICT_LENS, RefDict, book1, caps_for, case_set, rng_for
+from support import build_fake_jni, build_mirror, run_child
 
 pytestmark = pytest.mark.gpu
 GUARD = 8
@@ -269,10 +267,7 @@ def _pick(rows, L, count):
 
 
 def test_dict_cpp_mirror(tmp_path, rows):
-    exe = str(tmp_path / "dict_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "dict_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("dict_mirror_test", tmp_path)
     b = book1()
     for L in (100, 65536):
         dp = tmp_path / ("d%d.bin" % L)
@@ -290,7 +285,6 @@ def test_dict_cpp_mirror(tmp_path, rows):
 
 
 def test_dict_jni_shim(tmp_path, rows):
-    from jni_build import build_fake_jni
     exe = build_fake_jni("fake_jni_dict", tmp_path)
     b = book1()
     for L in (4096, 65537):
@@ -308,7 +302,4 @@ def test_dict_jni_shim(tmp_path, rows):
 
 def test_dict_multidev_host_path():
     """lz4hip_init([0] * 2): the host batch takes the multi-device branch (block ranges per listed device, the handle on each)"""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "dict_multidev_child.py"), "2"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=600)
-    assert p.returncode == 0, p.stderr.decode()[-3000:]
-    assert "dict multidev ok D=2" in p.stdout.decode()
+    assert "dict multidev ok D=2" in run_child("dict_multidev_child.py", "2", timeout=600)

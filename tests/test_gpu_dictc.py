@@ -4,16 +4,14 @@ reference library's own functions: the shared set of tests/dictc_common.py throu
 calls from eight threads on two handles; round trips through both dictionary decoders; the empty dictionary against the plain
 compressor; the C++ mirror, the JNI shim and the multi-device host path."""
 import ctypes as C
-import os
 import subprocess
-import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-from conftest import ROOT
 from dictc_common import (BIG, DICT_LENS, RefDict, big_record, book1, book_records, bound, caps_for, dict_cuts, hand_cases, other_records,
                           parse, ref_compress, rng_for)
+from support import build_fake_jni, build_mirror, run_child
 
 pytestmark = pytest.mark.gpu
 GUARD = 8
@@ -275,10 +273,7 @@ def test_dictc_arguments_on_a_device(amd):
 
 
 def test_dictc_cpp_mirror(tmp_path, rd):
-    exe = str(tmp_path / "dictc_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "dictc_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("dictc_mirror_test", tmp_path)
     b = book1()
     for L, n in ((100, 300), (65536, 4096), (4096, 0)):
         dp, sp, op = tmp_path / "d.bin", tmp_path / "s.bin", tmp_path / "o.bin"
@@ -290,7 +285,6 @@ def test_dictc_cpp_mirror(tmp_path, rd):
 
 
 def test_dictc_jni_shim(tmp_path, rd):
-    from jni_build import build_fake_jni
     exe = build_fake_jni("fake_jni_dictc", tmp_path)
     b = book1()
     for L, n in ((4096, 1000), (65537, 4096), (9, 300)):
@@ -303,7 +297,4 @@ def test_dictc_jni_shim(tmp_path, rd):
 
 def test_dictc_multidev_host_path():
     """lz4hip_init([0] * 2): the host batch takes the multi-device branch (block ranges per listed device, the handle's image on each)"""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "dictc_multidev_child.py"), "2"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=300)
-    assert p.returncode == 0, p.stderr.decode()[-3000:]
-    assert "dictc multidev ok D=2" in p.stdout.decode()
+    assert "dictc multidev ok D=2" in run_child("dictc_multidev_child.py", "2", timeout=300)

@@ -3,19 +3,17 @@ hc_parse_dest_kernel through the host batch, the device batch with and without a
 multi-device host path, the Python factory, the C++ mirror and the JNI shim -- checked byte for byte, and consumed size for consumed
 size, against the reference library's own LZ4_compress_HC_destSize (oracle.ref_path())."""
 import ctypes as C
-import os
 import random
 import subprocess
-import sys
 import threading
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, calgary, rnd_inputs
+from conftest import calgary, rnd_inputs
+from support import build_fake_jni, build_mirror, run_child
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 _u8p = C.POINTER(C.c_uint8)
 GUARD = 0xA5
 CHAIN_LEVELS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9)
@@ -287,10 +285,7 @@ def test_python_factory(amd, lz4hcdest, O):
 
 def test_cpp_mirror(lz4hcdest, tmp_path):
     """tests/cpp/hc_destsize_mirror_test.cpp: LZ4HCHIPCompressor::compressDestSize of host/lz4hip.hpp, against the reference"""
-    exe = str(tmp_path / "hc_destsize_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "hc_destsize_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("hc_destsize_mirror_test", tmp_path)
     v = calgary("book1")[7000:90000]
     (tmp_path / "in.bin").write_bytes(v)
     for t, level in ((100, 9), (4096, 1), (30000, 9), (4096, 10)):
@@ -305,7 +300,6 @@ def test_cpp_mirror(lz4hcdest, tmp_path):
 def test_jni_hc_dest_size_full_scenarios(lz4hcdest, tmp_path):
     """the shim's new natives over the fake JNIEnv (tests/jni_stub/fake_jni_hc_destsize.c): arrays, direct buffers, NULL arrays, a
     destination that cannot be pinned, the batch native; the stream and consumed size are the reference's"""
-    from jni_build import build_fake_jni
     exe = build_fake_jni("fake_jni_hc_destsize", tmp_path)
     v = calgary("book1")[100000:165536]
     (tmp_path / "in.bin").write_bytes(v)
@@ -319,5 +313,4 @@ def test_jni_hc_dest_size_full_scenarios(lz4hcdest, tmp_path):
 
 def test_multidevice_host_path():
     """lz4hip_init([0, 0]) in a child process: a ragged HC destSize batch across the device boundary, at level 9"""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "hc_destsize_multidev_child.py"), "2", "9"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0 and "hc destsize multidev ok D=2" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "hc destsize multidev ok D=2" in run_child("hc_destsize_multidev_child.py", "2", "9", timeout=900)

@@ -6,17 +6,15 @@ trips through the dictionary decoder; one handle used by the fast and the HC com
 two handles and two levels; the first-use image build raced by two streams; the C++ mirror, the JNI shim and two devices.  Every size a
 test states to the host path is true of the buffer it passes; malformed sizes go to device pointers with guarded slots only."""
 import ctypes as C
-import os
 import subprocess
-import sys
 import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-from conftest import ROOT
 from hcdict_common import (BIG_LEVELS, BIG_SIZES, CLAMPS, DICT_LENS, LEVELS, SMALL_SIZES, Ref, book1, book_records, bound, caps_for, clamp,
                            dict_cuts, hand_cases, has_dict_match, other_records, parse, pattern_cases)
+from support import build_fake_jni, build_mirror, run_child
 
 pytestmark = pytest.mark.gpu
 GUARD = 8
@@ -353,10 +351,7 @@ def test_hcdict_arguments_on_a_device(amd):
 
 
 def test_hcdict_cpp_mirror(tmp_path, R):
-    exe = str(tmp_path / "hcdict_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "hcdict_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("hcdict_mirror_test", tmp_path)
     b = book1()
     for L, n, level in ((100, 300, 9), (65536, 4096, 4), (4096, 0, 10)):
         dp, sp, op = tmp_path / "d.bin", tmp_path / "s.bin", tmp_path / "o.bin"
@@ -368,7 +363,6 @@ def test_hcdict_cpp_mirror(tmp_path, R):
 
 
 def test_hcdict_jni_shim(tmp_path, R):
-    from jni_build import build_fake_jni
     exe = build_fake_jni("fake_jni_hcdict", tmp_path)
     b = book1()
     for L, n, level in ((4096, 1000, 9), (65537, 4096, 3), (4, 300, 12)):
@@ -384,7 +378,4 @@ def test_hcdict_two_devices():
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "hcdict_multidev_child.py"), "0", "1"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=300)
-    assert p.returncode == 0, p.stderr.decode()[-3000:]
-    assert "hcdict multidev ok D=2" in p.stdout.decode()
+    assert "hcdict multidev ok D=2" in run_child("hcdict_multidev_child.py", "0", "1", timeout=300)

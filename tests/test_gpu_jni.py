@@ -10,12 +10,12 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from support import build_fake_jni
 
 pytestmark = pytest.mark.gpu
 
 
 def test_jni_shim_full_scenarios():
-    d = os.path.join(ROOT, "tests", "jni_stub")
-    subprocess.check_call(["bash", os.path.join(d, "build.sh")])
-    out = subprocess.check_output([os.path.join(d, "fake_jni")], timeout=300).decode()
+    exe = build_fake_jni("fake_jni", os.path.join(ROOT, "tests", "jni_stub"))
+    out = subprocess.check_output([exe], timeout=300).decode()
     assert "checks ok" in out and "no device" not in out, out

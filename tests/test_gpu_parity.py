@@ -11,6 +11,7 @@ import pytest
 
 from conftest import rnd_inputs, sha
 from fast_contract_common import DECODE_VARIANTS
+from support import build_mirror
 
 pytestmark = pytest.mark.gpu
 
@@ -564,10 +565,7 @@ def test_full_size_roundtrip_properties(amd):
 def test_cpp_host_mirror_runs():
     import os, subprocess
     from conftest import ROOT
-    exe = os.path.join(ROOT, "tests", "cpp", "host_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "cpp", "host_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("host_mirror_test", os.path.join(ROOT, "tests", "cpp"))
     assert subprocess.call([exe]) == 0
 
 

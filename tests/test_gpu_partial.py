@@ -3,17 +3,16 @@ host batch, the device batch and coalesced single calls; the Python factory, LZ4
 the multi-device host path; both kernels (below and from 40960 blocks on) with ragged targets side by side; guard bytes behind
 min(target, cap) in every slot; the negative-size rule; the long-literal stream whose run liblz4 cuts."""
 import ctypes as C
-import os
 import subprocess
-import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, calgary
+from conftest import calgary
 from partial_common import (caps_for, damaged, long_literal_stream, overlap_stream, ref_partial, rng_for, same_bytes,
                             targets_for)
+from support import build_fake_jni, build_mirror, run_child
 
 pytestmark = pytest.mark.gpu
 GUARD = 8
@@ -228,10 +227,7 @@ def test_partial_issue_examples(amd, ref, lz4p):
 
 
 def test_partial_cpp_mirror(tmp_path, cases, want):
-    exe = str(tmp_path / "partial_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "partial_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("partial_mirror_test", tmp_path)
     for i in range(0, len(cases), max(1, len(cases) // 25)):
         s, t, c = cases[i]
         wr, wb = want[i]
@@ -247,7 +243,6 @@ def test_partial_cpp_mirror(tmp_path, cases, want):
 
 
 def test_partial_jni_shim(tmp_path, cases, want):
-    from jni_build import build_fake_jni
     exe = build_fake_jni("fake_jni_partial", tmp_path)
     picked = [i for i in range(0, len(cases), max(1, len(cases) // 20)) if len(cases[i][0]) > 0]
     for i in picked:
@@ -264,7 +259,4 @@ def test_partial_jni_shim(tmp_path, cases, want):
 
 def test_partial_multidev_host_path():
     """lz4hip_init([0] * 2): the host batch takes the multi-device branch (block ranges per listed device)"""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "partial_multidev_child.py"), "2"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=600)
-    assert p.returncode == 0, p.stderr.decode()[-3000:]
-    assert "partial multidev ok D=2" in p.stdout.decode()
+    assert "partial multidev ok D=2" in run_child("partial_multidev_child.py", "2", timeout=600)

@@ -2,16 +2,14 @@
 buffer of cap + 64 bytes): the device batch at every grid shape, the host batch, coalesced single calls, the Python layers, the C++
 mirror and the JNI shim, the multi-device host path; streams longer than the kernel's LDS ring; agreement with the decoder; the
 sized decode; and that nothing but out[] is written.  Zero mismatches, nothing skipped, every test asserts its case count."""
-import os
 import subprocess
-import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from size_common import caps_for, edge_streams, long_literal_stream, ref_decode, ref_size, rng_for, seam_streams, stream_set
+from support import build_fake_jni, build_mirror, run_child
 
 pytestmark = pytest.mark.gpu
 BATCH = 3000
@@ -218,10 +216,7 @@ def test_size_single_calls_coalesced_from_threads(amd, parity):
 
 
 def test_size_cpp_mirror(tmp_path, ref, parity):
-    exe = str(tmp_path / "size_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "size_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("size_mirror_test", tmp_path)
     want, dec = ref_size(ref), ref_decode(ref)
     ran = 0
     for i in range(0, len(parity.idx), len(parity.idx) // 12):
@@ -246,7 +241,6 @@ def test_size_cpp_mirror(tmp_path, ref, parity):
 
 
 def test_size_jni_shim(tmp_path, ref, parity):
-    from jni_build import build_fake_jni
     exe = build_fake_jni("fake_jni_size", tmp_path)
     want = ref_size(ref)
     ran = 0
@@ -266,7 +260,4 @@ def test_size_jni_shim(tmp_path, ref, parity):
 
 def test_size_multidev_host_path():
     """lz4hip_init([0] * 2): the host batch takes the multi-device branch (block ranges per listed device)"""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "size_multidev_child.py"), "2"], stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=600)
-    assert p.returncode == 0, p.stderr.decode()[-3000:]
-    assert "size multidev ok D=2" in p.stdout.decode()
+    assert "size multidev ok D=2" in run_child("size_multidev_child.py", "2", timeout=600)

@@ -6,6 +6,7 @@ import io
 import pytest
 
 import streams_common as sc
+from support import build_mirror
 
 pytestmark = pytest.mark.gpu
 
@@ -83,10 +84,7 @@ def test_cpp_stream_mirror_runs_and_interoperates(S, engine):
     import subprocess
     import tempfile
     from conftest import ROOT
-    exe = os.path.join(ROOT, "tests", "cpp", "stream_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "cpp", "stream_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("stream_mirror_test", os.path.join(ROOT, "tests", "cpp"))
     with tempfile.TemporaryDirectory() as d:
         cli_payload = bytes(range(256)) * 3000 + b"tail"
         if sc.LZ4_CLI:

@@ -9,17 +9,10 @@ import subprocess
 import pytest
 
 from conftest import ROOT
-from jni_build import build_fake_jni
+from support import E_ARG, E_NO_DEVICE, LIB_ERROR, build_fake_jni, build_mirror, no_device
 
 NEW = ("lz4hip_compress_hc_dest_size_batch", "lz4hip_compress_hc_dest_size_batch_dev", "lz4hip_compress_hc_dest_size_batch_dev_ws",
        "lz4hip_compress_hc_dest_size")
-LIB_ERROR = lambda status: -2 ** 31 + (-status)   # LZ4HIP_LIB_ERROR
-E_NO_DEVICE, E_ARG = -1, -3
-
-
-def no_device():
-    import torch
-    return not torch.cuda.is_available()
 
 
 def test_hc_dest_size_symbols_declared_exported_and_bound(amd):
@@ -126,10 +119,7 @@ def test_hc_dest_size_python_layer(amd):
 def test_cpp_mirror_hc_dest_size_builds(tmp_path):
     """host/lz4hip.hpp: LZ4HCHIPCompressor::compressDestSize(src, srcOff, int& srcLen, dest, destOff, target), through
     tests/cpp/hc_destsize_mirror_test.cpp; loud without a device (exit code 3)"""
-    exe = str(tmp_path / "hc_destsize_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "hc_destsize_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("hc_destsize_mirror_test", tmp_path)
     if no_device():
         (tmp_path / "in.bin").write_bytes(b"to be or not to be, that is the question " * 40)
         p = subprocess.run([exe, str(tmp_path / "in.bin"), "100", str(tmp_path / "out.bin"), "9"], stdout=subprocess.PIPE, stderr=subprocess.PIPE)

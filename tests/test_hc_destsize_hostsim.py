@@ -13,11 +13,11 @@ import ctypes as C
 import glob
 import os
 import random
-import subprocess
 
 import pytest
 
 from conftest import ROOT, calgary
+from support import build_sim
 
 _u8p = C.POINTER(C.c_uint8)
 CHAIN_LEVELS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9)    # 0 -> 9 (the clamp)
@@ -32,13 +32,7 @@ def bound(n):
 
 
 def load_sim():
-    d = os.path.join(ROOT, "tests", "hostsim")
-    so = os.path.join(d, "libhostsim_hc_destsize.so")
-    srcs = [os.path.join(d, f) for f in ("hostsim_hc_destsize.cpp", "wave_host.h")] + \
-           [os.path.join(ROOT, "lz4-java_amd", "csrc", f) for f in ("lz4_hc_core.h", "lz4_fast_core.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(d, "hostsim_hc_destsize.cpp")])
-    l = C.CDLL(so)
+    l = build_sim("hostsim_hc_destsize")
     l.sim_compress_hc_dest_size.restype = C.c_int
     l.sim_compress_hc_dest_size.argtypes = [C.c_char_p, C.c_int, _u8p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_uint64]
     return l

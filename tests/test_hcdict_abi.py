@@ -11,16 +11,9 @@ import pytest
 
 from conftest import ROOT
 from dict_common import book1
-from jni_build import build_fake_jni
+from support import E_NO_DEVICE, LIB_ERROR, build_fake_jni, build_mirror, no_device
 
 NEW = ("lz4hip_compress_hc_dict_batch", "lz4hip_compress_hc_dict_batch_dev", "lz4hip_compress_hc_dict_batch_dev_ws", "lz4hip_compress_hc_dict")
-LIB_ERROR = lambda status: -2 ** 31 + (-status)   # LZ4HIP_LIB_ERROR
-E_NO_DEVICE, E_ARG = -1, -3
-
-
-def no_device():
-    import torch
-    return not torch.cuda.is_available()
 
 
 def test_hcdict_symbols_declared_exported_and_bound(amd):
@@ -114,10 +107,7 @@ def test_hcdict_python_layer_checks(amd):
 def test_cpp_mirror_hcdict_builds_and_fails_loudly(tmp_path):
     """host/lz4hip.hpp: LZ4HCHIPCompressor::compressWithDict and LZ4HIPBatch::compressHCDict build; tests/cpp/hcdict_mirror_test.cpp
     passes its argument checks and exits 3 (loud library failure) without a device"""
-    exe = str(tmp_path / "hcdict_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "hcdict_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("hcdict_mirror_test", tmp_path)
     if no_device():
         (tmp_path / "d.bin").write_bytes(b"0123456789")
         (tmp_path / "s.bin").write_bytes(b"abcdefgh" * 8)

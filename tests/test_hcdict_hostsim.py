@@ -5,28 +5,20 @@ value and bytes against the reference library on the shared set (tests/hcdict_co
 dictionary far from the source, and right in front of it (where the engine, unlike liblz4, still treats the two as separate), with
 different fill round each; the simulator flags a wave access outside the kept tail, the source and the slot."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import pytest
 
-from conftest import ROOT
 from hcdict_common import (BIG_LEVELS, BIG_SIZES, CLAMPS, DICT_LENS, LEVELS, SMALL_SIZES, Ref, book1, book_records, bound, caps_for,
                            check_hand_cases, clamp, dict_cuts, hand_cases, has_dict_match, has_straddle, keep_of, other_records, parse,
                            pattern_cases)
+from support import build_sim
 
 HEAD = 32768
 
 
 def load_sim():
-    d = os.path.join(ROOT, "tests", "hostsim")
-    so = os.path.join(d, "libhostsim_hcdict.so")
-    csrc = os.path.join(ROOT, "lz4-java_amd", "csrc")
-    srcs = [os.path.join(d, f) for f in ("hostsim_hcdict.cpp", "wave_host.h")] + [os.path.join(csrc, f) for f in ("lz4_hc_core.h", "lz4_fast_core.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(d, "hostsim_hcdict.cpp")])
-    l = C.CDLL(so)
+    l = build_sim("hostsim_hcdict")
     l.sim_hc_dict_image.restype = C.c_int
     l.sim_hc_dict_image.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]
     l.sim_compress_hc_dict.restype = C.c_int

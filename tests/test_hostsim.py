@@ -10,22 +10,16 @@ import subprocess
 import pytest
 
 from conftest import ROOT, rnd_inputs
+from support import HOSTSIM, build_sim, newer_than
 
 _u8p = C.POINTER(C.c_uint8)
 
 
 def load_sim():
-    d = os.path.join(ROOT, "tests", "hostsim")
     # (LZ4HIP_SIM_FLAGS: a developer / soak build of the simulator with other macros -- e.g. the wave loop's instances switching every few windows --
     # into a library of its own: <name>:<flags>)
-    extra = os.environ.get("LZ4HIP_SIM_FLAGS", "")
-    so = os.path.join(d, "libhostsim%s.so" % (("_" + extra.split(":", 1)[0]) if extra else ""))
-    srcs = [os.path.join(d, f) for f in ("hostsim.cpp", "wave_host.h", "group_host.h")] + \
-           [os.path.join(ROOT, "lz4-java_amd", "csrc", f) for f in ("lz4_fast_core.h", "lz4_fast_ms_core.h", "lz4_fast_v2_core.h", "lz4_decode_core.h", "lz4_decode_deep.h", "lz4_decode_ring.h", "lz4_decode_wave.h", "lz4_decode_pair.h", "lz4_decode_trio.h", "lz4_hc_core.h")]
-    srcs.append(os.path.join(ROOT, "lz4-java_amd", "csrc", "mail_ring.h"))
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread"] + (extra.split(":", 1)[1].split() if extra else []) + ["-o", so, os.path.join(d, "hostsim.cpp")])
-    l = C.CDLL(so)
+    name, _, extra = os.environ.get("LZ4HIP_SIM_FLAGS", "").partition(":")
+    l = build_sim("hostsim", variant="_" + name if name else "", flags=extra.split())
     l.sim_compress_fast.restype = C.c_int
     l.sim_compress_fast.argtypes = [C.c_char_p, C.c_int, _u8p, C.c_int, C.POINTER(C.c_uint64), C.c_uint64]
     l.sim_compress_fast_ms.restype = C.c_int
@@ -733,19 +727,15 @@ def test_mail_ring_abort_after_routed_block(sim, ref, O, corpus):
 # ---------------------------------------------------------------------------------------------------------------------
 def build_asmsim(tag="", defs=()):
     """the interpreter library; tag / defs: a variant -- the loops' text AND the C++ around it built with extra -D flags"""
-    d = os.path.join(ROOT, "tests", "hostsim")
-    inc, so = os.path.join(d, "lean_asm_text%s.inc" % tag), os.path.join(d, "libhostsim_asm%s.so" % tag)
+    inc = os.path.join(HOSTSIM, "lean_asm_text%s.inc" % tag)
     csrc = os.path.join(ROOT, "lz4-java_amd", "csrc")
-    srcs = [os.path.join(d, f) for f in ("hostsim_asm.cpp", "asm_emu.h", "wave_host.h", "gen_asm_text.py")] + \
-           [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".inc"))]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        rc = subprocess.call([os.sys.executable, os.path.join(d, "gen_asm_text.py"), inc] + list(defs))
+    inputs = [os.path.join(HOSTSIM, "gen_asm_text.py")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".h", ".inc"))]
+    if not os.path.exists(inc) or newer_than(inc, inputs):
+        rc = subprocess.call([os.sys.executable, os.path.join(HOSTSIM, "gen_asm_text.py"), inc] + list(defs))
         if rc == 3:
             pytest.skip("no hipcc here: the loops' text cannot be extracted")
         assert rc == 0
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", '-DLZ4HIP_ASM_TEXT_INC="%s"' % os.path.basename(inc)] + list(defs) +
-                              ["-o", so, os.path.join(d, "hostsim_asm.cpp")])
-    l = C.CDLL(so)
+    l = build_sim("hostsim_asm", variant=tag, flags=['-DLZ4HIP_ASM_TEXT_INC="%s"' % os.path.basename(inc)] + list(defs), extra_deps=inputs)
     l.sim_asm_compress.restype = C.c_int
     l.sim_asm_compress.argtypes = [C.c_char_p, C.c_int, _u8p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_uint64]
     return l

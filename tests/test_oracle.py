@@ -6,6 +6,7 @@ import os
 import random
 
 from conftest import calgary, rnd_inputs, sha
+from support import build_cpu_bench
 
 
 def test_golden_table_port(port, golden, corpus):
@@ -137,7 +138,7 @@ def test_cpu_bench_harness_one_block_per_thread():
     import subprocess
     odir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
     exe = os.path.join(odir, "cpu_bench_test")
-    subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-o", exe, os.path.join(odir, "cpu_bench.c"), "-ldl", "-lpthread"])
+    build_cpu_bench(exe)
     try:
         port = os.path.join(odir, "liblz4oracle.so")
         for n, blk in ((4, 65536), (3, 1 << 20)):

@@ -9,16 +9,9 @@ import subprocess
 import pytest
 
 from conftest import ROOT
-from jni_build import build_fake_jni
+from support import E_ARG, E_NO_DEVICE, LIB_ERROR, build_fake_jni, build_mirror, no_device
 
 NEW = ("lz4hip_decompress_safe_partial_batch", "lz4hip_decompress_safe_partial_batch_dev", "lz4hip_decompress_safe_partial")
-LIB_ERROR = lambda status: -2 ** 31 + (-status)   # LZ4HIP_LIB_ERROR
-E_NO_DEVICE, E_ARG = -1, -3
-
-
-def no_device():
-    import torch
-    return not torch.cuda.is_available()
 
 
 def test_partial_symbols_declared_exported_and_bound(amd):
@@ -102,10 +95,7 @@ def test_partial_python_layer(amd):
 def test_cpp_mirror_partial_builds_and_fails_loudly(tmp_path):
     """host/lz4hip.hpp: LZ4SafeDecompressor::decompressPartial(src, srcOff, srcLen, dest, destOff, targetLen, maxDestLen) builds;
     tests/cpp/partial_mirror_test.cpp exits 3 (loud library failure) without a device"""
-    exe = str(tmp_path / "partial_mirror_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + ROOT, os.path.join(ROOT, "tests", "cpp", "partial_mirror_test.cpp"),
-                           "-L" + os.path.join(ROOT, "lz4-java_amd"), "-llz4hip", "-Wl,-rpath," + os.path.join(ROOT, "lz4-java_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_mirror("partial_mirror_test", tmp_path)
     if no_device():
         stream = tmp_path / "s.bin"
         stream.write_bytes(b"\x10a")

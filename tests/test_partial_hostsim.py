@@ -3,27 +3,19 @@
 lanes, the deep loop with 8, and the plain loop with both -- with the simulator's destination bound set to min(target, cap), and this
 file checks return value and bytes against the reference library's own LZ4_decompress_safe_partial."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-from conftest import ROOT, calgary
+from conftest import calgary
 from partial_common import (caps_for, damaged, long_literal_stream, overlap_stream, ref_partial, rng_for, same_bytes,
                             targets_for)
+from support import build_sim
 
 FORMS = ((0, 4), (0, 8), (1, 4), (2, 8))   # (form, lanes): plain, plain, staged (decode_partial_kernel<4, 0, true>), deep (<8>)
 
 
 def load_sim():
-    d = os.path.join(ROOT, "tests", "hostsim")
-    so = os.path.join(d, "libhostsim_partial.so")
-    csrc = os.path.join(ROOT, "lz4-java_amd", "csrc")
-    srcs = [os.path.join(d, f) for f in ("hostsim_partial.cpp", "group_host.h", "wave_host.h")] + \
-           [os.path.join(csrc, f) for f in os.listdir(csrc) if f.startswith("lz4_decode_")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", so, os.path.join(d, "hostsim_partial.cpp")])
-    l = C.CDLL(so)
+    l = build_sim("hostsim_partial")
     l.sim_decompress_partial.restype = C.c_int
     l.sim_decompress_partial.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
     return l

@@ -4,27 +4,18 @@ forms -- the exact path alone, and the fast interior in front of it (stream ring
 and this file checks every value against the return value of the reference library's own LZ4_decompress_safe, called with a real
 buffer of cap + 64 bytes.  Zero mismatches, nothing skipped, every test asserts its case count."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-from conftest import ROOT
 from size_common import (SEAM_SIZES, caps_for, edge_streams, long_literal_stream, ref_size, rng_for, seam_streams, stream_set,
                          valid_streams)
+from support import build_sim
 
 FORMS = ((0, 2048), (1, 2048), (1, 1024))   # (fast interior, stream ring bytes): exact only; what the kernel runs; a smaller ring
 
 
 def load_sim():
-    d = os.path.join(ROOT, "tests", "hostsim")
-    so = os.path.join(d, "libhostsim_size.so")
-    csrc = os.path.join(ROOT, "lz4-java_amd", "csrc")
-    srcs = [os.path.join(d, f) for f in ("hostsim_size.cpp", "group_host.h", "wave_host.h")] + \
-           [os.path.join(csrc, f) for f in os.listdir(csrc) if f.startswith("lz4_decode_")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", so, os.path.join(d, "hostsim_size.cpp")])
-    l = C.CDLL(so)
+    l = build_sim("hostsim_size")
     l.sim_decoded_size.restype = C.c_int
     l.sim_decoded_size.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]
     return l
