@@ -234,13 +234,51 @@ int lz4hip_decompress_safe_dict_batch(const uint8_t* src, const uint64_t* src_of
  *   - the host form uploads the streams and, per chain, the last min(prefix_len, 65536) bytes of history from the caller's dst, and
  *     brings back only the bytes decoded (runs less than 4 KB apart as one copy); it shards over the initialised devices at chain
  *     boundaries;
- *   - out of scope: linked-block compression and LZ4_saveDict, chains that start from a non-contiguous dictionary
+ *   - out of scope: LZ4_saveDict, chains that start from a non-contiguous dictionary
  *     (LZ4_decompress_safe_doubleDict), ring-buffer destinations that wrap, fast and partial decoders in chain form.              */
 int lz4hip_decompress_safe_chain_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                        const uint8_t* stored, const int32_t* dst_cap, const uint32_t* chain_first,
                                        uint8_t* dst, const uint64_t* chain_dst_off, const uint64_t* chain_dst_cap,
                                        const int32_t* chain_prefix_len, int32_t* out_len, uint64_t* chain_out_len,
                                        uint32_t n_blocks, uint32_t n_chains);
+
+/* COMPRESS CHAINS OF LINKED BLOCKS: the return values and bytes of liblz4 1.9.3's streaming compressor in its prefix mode, acceleration 1
+ * -- what lz4hip_decompress_safe_chain_batch* reads and what the lz4 command line writes by default.  A CHAIN is a run of blocks whose
+ * SOURCES lie back to back in src; a match of block k may reach into the blocks before it and into history that lies directly in front
+ * of the chain.  Chains are independent of each other; one launch compresses many of them.  With chain_src = src + chain_src_off[c]
+ * and P = chain_prefix_len[c], the result for block k of chain c is
+ *     s = LZ4_createStream();  if (P > 0) LZ4_loadDict(s, chain_src - P, P);
+ *     r_k = LZ4_compress_fast_continue(s, chain_src + sum(src_len_j, j < k), dst_k, src_len_k, dst_cap_k, 1);
+ * every source follows the previous one and the first follows the loaded history (never the external-dictionary mode):
+ *   - chain c is the blocks [chain_first[c], chain_first[c + 1]) (n_chains + 1 entries, ascending from 0 to n_blocks); block i starts
+ *     where block i - 1 of its chain ended and owns the slot dst[dst_off[i] .. + dst_cap[i]) -- the outputs are separate messages and
+ *     need not be contiguous; chain_prefix_len == NULL: no chain has history.  Of a prefix only the last 65536 bytes count, and one
+ *     under 8 bytes is unreachable (LZ4_loadDict loads nothing) although it still moves the stream's indexes;
+ *   - out_len[i] > 0: the compressed size.  out_len[i] == 0: what liblz4 returns when the output does not fit (LZ4_compress_default's
+ *     capacity rule), and also the result for src_len[i] < 0, dst_cap[i] < 0, and a block with which the chain's kept history, its
+ *     consumed bytes and src_len[i] together would exceed 0x7E000000 (a chain never reaches liblz4's index renormalisation);
+ *   - a block whose result is 0 ENDS ITS CHAIN (liblz4 goes on from there with a polluted table in another mode; nothing downstream
+ *     of that is worth reproducing): every block behind it gets LZ4HIP_CHAIN_STOPPED.  chain_consumed[c] = the source bytes of the
+ *     blocks that succeeded.  With dst_cap[i] >= lz4hip_compress_bound(src_len[i]) no block fails;
+ *   - a block of 0 bytes is the single token 0x00 and the chain goes on; a block under 13 bytes is one literal run;
+ *   - there is no single-call form: chains are the unit;
+ *   - nothing outside [chain_src_off[c] - min(P, 65536), chain_src_off[c] + sum src_len) is read, nothing outside a block's slot is
+ *     written.  Slots must not overlap;
+ *   - LZ4HIP_E_ARG: a required pointer that is NULL (everything but chain_prefix_len), a chain_first that is not ascending from 0 to
+ *     n_blocks, a negative chain_prefix_len[c] or one longer than chain_src_off[c].  These are said before a device is looked for;
+ *   - one kernel, compress_fast_chain_cu_kernel: five wavefronts per CU with a 32 KB table each draw chains from a queue; a chain's
+ *     table is cleared, or built from its prefix, once, and stays in LDS from one block to the next.  ONE CHAIN IS SERIAL BY
+ *     CONSTRUCTION and runs on one wavefront; the kernel waits for no other wavefront anywhere, and parallelism comes from the
+ *     number of chains alone.  The compress_* knobs do not apply;
+ *   - the host form uploads each chain's source with the last min(P, 65536) bytes of its history, brings back only the bytes
+ *     produced, and shards over the initialised devices at chain boundaries;
+ *   - out of scope: acceleration above 1; LZ4_saveDict and resuming a stream's exact state across calls (the prefix is LZ4_loadDict's
+ *     table, which is not the table a running stream would hold: continuing a stream in a second call gives valid, decodable, but
+ *     other bytes than one long chain); sources that are not contiguous; LZ4_attach_dictionary; an HC form.                          */
+int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
+                                     const int32_t* src_len, const uint32_t* chain_first,
+                                     uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                     int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains);
 /* COMPRESS AGAINST A DICTIONARY: for every block i, on a fresh stream,
  *     LZ4_loadDict(s, dict, dict_len);  LZ4_compress_fast_continue(s, src_i, dst_i, src_len[i], dst_cap[i], 1)
  * of liblz4 1.9.3 with a dictionary that is NOT contiguous with the source (its external-dictionary mode): the return value and the
@@ -398,6 +436,15 @@ int lz4hip_decompress_safe_chain_batch_dev(const uint8_t* src, const uint64_t* s
                                            uint8_t* dst, const uint64_t* chain_dst_off, const uint64_t* chain_dst_cap,
                                            const int32_t* chain_prefix_len, int32_t* out_len, uint64_t* chain_out_len,
                                            uint32_t n_blocks, uint32_t n_chains, int device, void* stream);
+/* compress chains of linked blocks (see lz4hip_compress_fast_chain_batch): device pointers -- every array, per block and per chain --,
+ * asynchronous on `stream`, never synchronises.  Only the pointers can be checked here; the kernel trusts nothing it reads from the
+ * arrays: a chain's block range is cut to [0, n_blocks], a negative chain_prefix_len counts as 0 and one longer than chain_src_off[c]
+ * is cut to it */
+int lz4hip_compress_fast_chain_batch_dev(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
+                                         const int32_t* src_len, const uint32_t* chain_first,
+                                         uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                         int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains,
+                                         int device, void* stream);
 /* compress against a dictionary (see lz4hip_compress_fast_dict_batch): device pointers on `device`, and the HANDLE -- the compressor
  * needs its table image, not only the bytes; asynchronous, except that a handle's first compress on a device builds the image and
  * waits for `stream` once.  dict == NULL is LZ4HIP_E_ARG */
@@ -465,7 +512,8 @@ int lz4hip_xxh64_batch_dev(const uint8_t* buf, const uint64_t* off, const int32_
  * reported as INT32_MIN + (-status), which no codec result can equal: test LZ4HIP_IS_LIB_ERROR().  */
 #define LZ4HIP_LIB_ERROR(status) ((int)(INT32_MIN + (-(status))))
 #define LZ4HIP_IS_LIB_ERROR(ret) ((ret) < (int)(INT32_MIN + 64))
-/* out_len[i] of lz4hip_decompress_safe_chain_batch*: block i lies behind its chain's first failed block and was not decoded */
+/* out_len[i] of lz4hip_decompress_safe_chain_batch* and lz4hip_compress_fast_chain_batch*: block i lies behind its chain's first failed
+ * block and was not decoded / compressed */
 #define LZ4HIP_CHAIN_STOPPED LZ4HIP_LIB_ERROR(LZ4HIP_E_CHAIN_STOPPED)
 int lz4hip_compress_fast(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap);
 int lz4hip_compress_fast_accel(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int acceleration);  /* LZ4_compress_fast */

@@ -63,6 +63,8 @@ C_ABI = {
     "lz4hip_decompress_safe_chain_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _u64p, C.c_void_p, _i32p, _u64p,
                                                      C.c_uint32, C.c_uint32]),
     "lz4hip_decompress_safe_chain_batch_dev": (C.c_int, [C.c_void_p] * 12 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
+    "lz4hip_compress_fast_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32]),
+    "lz4hip_compress_fast_chain_batch_dev": (C.c_int, [C.c_void_p] * 10 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
@@ -918,6 +920,51 @@ class LZ4HIPBatch:
         return list(out[:n]), list(cout[:nc])
 
     @classmethod
+    def compressFastChain(cls, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None):
+        """LZ4_compress_fast_continue over chains of linked blocks (lz4hip_compress_fast_chain_batch): chain c is the blocks
+        chainFirst[c] .. chainFirst[c + 1] - 1, whose sources lie back to back from src[chainSrcOff[c]] on, behind chainPrefixLen[c]
+        bytes of history that lie in front of it in src (None: no history; the stream loads it with LZ4_loadDict); block i owns the
+        slot dst[dstOff[i]:+dstCap[i]] -> (outLen, chainConsumed): liblz4's return value per block (0: it did not fit, which ends
+        the chain; CHAIN_STOPPED behind a chain's first 0) and the source bytes of each chain's blocks that succeeded (lists, or
+        int32 / uint64 arrays for numpy inputs)"""
+        n, nc = len(srcLen), len(chainSrcOff)
+        if not (len(dstOff) == len(dstCap) == n):
+            raise ValueError("per-block arrays differ in length")
+        if len(chainFirst) != nc + 1 or (chainPrefixLen is not None and len(chainPrefixLen) != nc):
+            raise ValueError("per-chain arrays differ in length")
+        prev = 0
+        for c in range(nc + 1):
+            if chainFirst[c] < prev or (c == 0 and chainFirst[0] != 0):
+                raise ValueError("chainFirst must ascend from 0 to the number of blocks")
+            prev = chainFirst[c]
+        if prev != n:
+            raise ValueError("chainFirst must ascend from 0 to the number of blocks")
+        for c in range(nc):
+            total = 0
+            for i in range(chainFirst[c], chainFirst[c + 1]):
+                _check_length(srcLen[i])
+                total += srcLen[i]
+            _check_range(src, chainSrcOff[c], total)
+            if chainSrcOff[c] < 0 or chainSrcOff[c] > len(src):
+                raise IndexError(chainSrcOff[c])
+            if chainPrefixLen is not None:
+                _check_length(chainPrefixLen[c])
+                if chainPrefixLen[c] > chainSrcOff[c]:
+                    raise IndexError("history reaches in front of the buffer")
+        cls._check_ranges(dst, dstOff, dstCap)
+        sp, sk = _ro_ptr(src)
+        dp, dk = _rw_ptr(dst)
+        out = (C.c_int32 * max(n, 1))()
+        cons = (C.c_uint64 * max(nc, 1))()
+        pre = _arr(C.c_int32, chainPrefixLen) if chainPrefixLen is not None else None
+        _chk(lib().lz4hip_compress_fast_chain_batch(sp, _arr(C.c_uint64, chainSrcOff), pre, _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst), dp,
+                                                    _arr(C.c_uint64, dstOff), _arr(C.c_int32, dstCap), out, cons, n, nc))
+        if hasattr(srcLen, "dtype"):
+            import numpy as np
+            return np.frombuffer(out, dtype=np.int32, count=n).copy(), np.frombuffer(cons, dtype=np.uint64, count=nc).copy()
+        return list(out[:n]), list(cons[:nc])
+
+    @classmethod
     def decompressSafePartial(cls, src, srcOff, srcLen, dst, dstOff, targetLen, dstCap):
         """LZ4_decompress_safe_partial per block: the first min(targetLen[i], dstCap[i]) bytes of block i into the slot
         dst[dstOff[i]:+dstCap[i]] -> liblz4's return values (lz4hip_decompress_safe_partial_batch; lists, or an int32 array for numpy
@@ -1182,6 +1229,19 @@ class DeviceBatch:
                                                           chain_first.data_ptr(), dst.data_ptr(), chain_dst_off.data_ptr(), chain_dst_cap.data_ptr(),
                                                           chain_prefix_len.data_ptr() if chain_prefix_len is not None else None,
                                                           out.data_ptr(), chain_out.data_ptr(), src_off.numel(), chain_dst_off.numel(), dev, st))
+
+    @classmethod
+    def compress_fast_chain(cls, src, chain_src_off, src_len, chain_first, dst, dst_off, dst_cap, out, chain_consumed, chain_prefix_len=None):
+        """LZ4_compress_fast_continue over chains of linked blocks (lz4hip_compress_fast_chain_batch_dev): chain_first is an int32
+        tensor of chains + 1 entries (reinterpreted as uint32), chain_src_off / dst_off / chain_consumed int64 tensors (as uint64),
+        chain_prefix_len an int32 tensor or None; out = liblz4's return values per block (0 ends a chain, LZ4HIPBatch.CHAIN_STOPPED
+        behind it), chain_consumed = the source bytes of each chain's blocks that succeeded"""
+        dev, st = cls._stream_dev(src)
+        _chk(lib().lz4hip_compress_fast_chain_batch_dev(src.data_ptr(), chain_src_off.data_ptr(),
+                                                        chain_prefix_len.data_ptr() if chain_prefix_len is not None else None,
+                                                        src_len.data_ptr(), chain_first.data_ptr(), dst.data_ptr(), dst_off.data_ptr(),
+                                                        dst_cap.data_ptr(), out.data_ptr(), chain_consumed.data_ptr(), src_len.numel(),
+                                                        chain_src_off.numel(), dev, st))
 
     @classmethod
     def decompress_safe_partial(cls, src, src_off, src_len, dst, dst_off, target_len, dst_cap, out):

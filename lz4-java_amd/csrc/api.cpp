@@ -83,12 +83,14 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // OP_COMPRESS_HC's level and workspace, and the handle's HC image (dict_hc_state)
 // OP_DECOMPRESS_CHAIN: LZ4_decompress_safe_continue over chains of linked blocks: its arrays (per block AND per chain) are
 // BlockCall::chain, the seven arrays of the other operations are not used; the host path is chain_host_shard, not host_shard
+// OP_COMPRESS_CHAIN: LZ4_compress_fast_continue over chains of linked blocks: its arrays are BlockCall::cchain; the host path is
+// cchain_host_shard, which brings back only the bytes produced, as every compressor's does
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
-          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN };
-constexpr int OP_COUNT = OP_DECOMPRESS_CHAIN + 1;   // (the last enumerator)
+          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN, OP_COMPRESS_CHAIN };
+constexpr int OP_COUNT = OP_COMPRESS_CHAIN + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
-constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT; }
+constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN; }
 // a second per-block result (BlockCall::consumed) travels behind out[]
 constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
 // out[i] counts SOURCE bytes read: a block that succeeded filled its whole dst_cap[i]
@@ -110,6 +112,7 @@ struct BlockCall {
   const uint8_t* dict_dev = nullptr;    // ... or, without a handle, the caller's dictionary in device memory and
   int32_t dict_len = 0;                 // its length
   const lz4hip::ChainArgs* chain = nullptr;   // OP_DECOMPRESS_CHAIN: the call's arrays on the device
+  const lz4hip::CChainArgs* cchain = nullptr; // OP_COMPRESS_CHAIN: the call's arrays on the device
 };
 static_assert(lz4hip::kChainStopped == LZ4HIP_CHAIN_STOPPED, "the kernels' marker is the header's");
 // the handle's bytes on the CURRENT device (uploaded on first use where lz4hip_dict_create found the device not yet initialised):
@@ -264,6 +267,15 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
       const hipError_t me = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
       if (me != hipSuccess) return (int)me;
       const int e = lz4hip::launch_decompress_chain(*c.chain, q, lz4hip::device_cus(), st);
+      (void)hipFreeAsync(q, st);
+      return e;
+    }
+    case OP_COMPRESS_CHAIN: {   // compress_fast_chain_cu_kernel draws chains from one queue word of scratch
+      if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
+      uint32_t* q = nullptr;
+      const hipError_t me = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
+      if (me != hipSuccess) return (int)me;
+      const int e = lz4hip::launch_compress_fast_chain(*c.cchain, q, lz4hip::device_cus(), st);
       (void)hipFreeAsync(q, st);
       return e;
     }
@@ -839,6 +851,137 @@ const char* chain_arg_error(const lz4hip::ChainArgs& a, bool host) {
     if (a.chain_prefix_len) {
       if (a.chain_prefix_len[c] < 0) return "negative chain_prefix_len";
       if ((uint64_t)a.chain_prefix_len[c] > a.chain_dst_off[c]) return "chain_prefix_len reaches in front of dst";
+    }
+  }
+  return nullptr;
+}
+
+// ---- chains of linked blocks on the host-pointer path, compressing side ----
+// One device's share [c0, c1) of a chain-compress batch (h: the caller's HOST arrays).  Chains are staged a chunk at a time (64 MiB of
+// source or 512 MiB of slots, one chain at least) through the first buffer set of a pooled pair: each chain's source goes up with the
+// last min(prefix_len, 65536) bytes of its history in front of it; the kernel runs; the results come back, and then only the bytes
+// each block produced (runs less than 4 KB apart travel as one copy).  Of a chain's source only what its blocks can consume is
+// read: up to the first block with a negative length or with which the chain would exceed 0x7E000000 bytes (its result is 0).
+int cchain_host_shard(const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+  auto bad = [&](const char* what, hipError_t e) {
+    char buf[512];
+    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+    *err = buf;
+    return e == hipErrorOutOfMemory ? (int)LZ4HIP_E_NOMEM : (int)LZ4HIP_E_HIP;
+  };
+  if (c1 == c0) return LZ4HIP_OK;
+  if (ord < 0 || ord >= 64) { *err = "device ordinal out of range"; return LZ4HIP_E_ARG; }
+  hipError_t e;
+  if ((e = hipSetDevice(ord)) != hipSuccess) return bad("hipSetDevice", e);
+  DevCtx& cx = g_ctx[ord];
+  SlotPair* pair = cx.acquire(&e);
+  if (!pair) return bad("stream/event creation", e);
+  struct Return { DevCtx& c; SlotPair* p; ~Return() { c.give_back(p); } } give_back_on_exit{cx, pair};
+  ChunkSlot& s = pair->slot[0];
+  const hipStream_t st = s.st;
+  auto al16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
+  auto cap_of = [&](uint32_t i) -> size_t { return h.dst_cap[i] > 0 ? (size_t)h.dst_cap[i] : 0; };
+  auto keep_of = [&](uint32_t c) -> size_t { const int32_t p = h.chain_prefix_len ? h.chain_prefix_len[c] : 0; return p > 65536 ? 65536u : (size_t)p; };
+  auto span_of = [&](uint32_t c) -> size_t {   // the source bytes the chain's blocks can consume
+    const size_t k = keep_of(c);
+    uint64_t pos = k < 8u ? 0u : k;   // (the kernel's count: a prefix under 8 bytes is not kept)
+    const uint64_t pos0 = pos;
+    for (uint32_t i = h.chain_first[c]; i < h.chain_first[c + 1]; i++) {
+      if (h.src_len[i] < 0 || pos + (uint64_t)h.src_len[i] > 0x7E000000ull) break;
+      pos += (uint64_t)h.src_len[i];
+    }
+    return (size_t)(pos - pos0);
+  };
+  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+  std::vector<uint64_t> cso, dso;
+  uint32_t c = c0;
+  while (c < c1) {
+    // the next chunk: chains [c, j), blocks [b0, b1)
+    uint32_t j = c;
+    size_t sb = 0, db = 0;
+    cso.clear();
+    while (j < c1) {
+      const size_t a = al16(keep_of(j) + span_of(j));
+      size_t d = 0;
+      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) d += al16(cap_of(i));
+      if (j > c && (sb + a > chunk_src || db + d > chunk_dst)) break;
+      cso.push_back(sb + keep_of(j));
+      sb += a; db += d; j++;
+    }
+    const uint32_t b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
+    dso.resize(nb);
+    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { dso[t] = o; o += al16(cap_of(b0 + t)); } }
+    // metadata: chain_src_off[nc] u64 | dst_off[nb] u64 | chain_consumed[nc] u64 | out[nb] | src_len[nb] | dst_cap[nb] |
+    // chain_first[nc + 1] | prefix[nc]
+    const size_t o_do = 8u * nc, o_cons = o_do + 8u * nb, o_out = o_cons + 8u * nc, o_slen = o_out + 4u * nb, o_dcap = o_slen + 4u * nb,
+                 o_first = o_dcap + 4u * nb, o_prefix = o_first + 4u * (nc + 1u), meta = o_prefix + 4u * nc;
+    if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (e = s.h_dst.reserve(db + 64)) != hipSuccess || (e = s.h_meta.reserve(meta)) != hipSuccess ||
+        (e = s.d_src.reserve(sb + 64)) != hipSuccess || (e = s.d_dst.reserve(db + 64)) != hipSuccess || (e = s.d_meta.reserve(meta)) != hipSuccess)
+      return bad("staging allocation", e);
+    uint8_t* hs = (uint8_t*)s.h_src.p;
+    uint8_t* hd = (uint8_t*)s.h_dst.p;
+    uint8_t* hm = (uint8_t*)s.h_meta.p;
+    uint8_t* dm = (uint8_t*)s.d_meta.p;
+    uint8_t* dd = (uint8_t*)s.d_dst.p;
+    { const uint32_t base = c;
+      par_blocks(c, j, sb, [=, &cso](uint32_t t) {
+        const size_t k = keep_of(t), n = k + span_of(t);
+        if (n) memcpy(hs + cso[t - base] - k, h.src + h.chain_src_off[t] - k, n);
+      }); }
+    memcpy(hm, cso.data(), 8u * nc);
+    memcpy(hm + o_do, dso.data(), 8u * nb);
+    memset(hm + o_cons, 0, 8u * nc);
+    memset(hm + o_out, 0, 4u * nb);
+    memcpy(hm + o_slen, h.src_len + b0, 4u * nb);
+    memcpy(hm + o_dcap, h.dst_cap + b0, 4u * nb);
+    for (uint32_t t = 0; t <= nc; t++) { const uint32_t f = h.chain_first[c + t] - b0; memcpy(hm + o_first + 4u * t, &f, 4); }
+    for (uint32_t t = 0; t < nc; t++) { const int32_t k = (int32_t)keep_of(c + t); memcpy(hm + o_prefix + 4u * t, &k, 4); }
+    if (sb && (e = hipMemcpyAsync(s.d_src.p, hs, sb, hipMemcpyHostToDevice, st)) != hipSuccess) return bad("H2D src", e);
+    if ((e = hipMemcpyAsync(dm, hm, meta, hipMemcpyHostToDevice, st)) != hipSuccess) return bad("H2D meta", e);
+    const lz4hip::CChainArgs a{(const uint8_t*)s.d_src.p, (const uint64_t*)dm, (const int32_t*)(dm + o_prefix), (const int32_t*)(dm + o_slen),
+                               (const uint32_t*)(dm + o_first), dd, (const uint64_t*)(dm + o_do), (const int32_t*)(dm + o_dcap),
+                               (int32_t*)(dm + o_out), (uint64_t*)(dm + o_cons), nb, nc};
+    BlockCall call{OP_COMPRESS_CHAIN};
+    call.cchain = &a;
+    const int le = launch_block(call, lz4hip::BatchArgs{}, st);
+    if (le < 0) { *err = lz4hip_last_error(); return le; }
+    if (le) return bad("kernel launch", (hipError_t)le);
+    if ((e = hipMemcpyAsync(hm + o_cons, dm + o_cons, o_slen - o_cons, hipMemcpyDeviceToHost, st)) != hipSuccess) return bad("D2H out", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return bad("hipStreamSynchronize", e);
+    memcpy(h.out + b0, hm + o_out, 4u * nb);
+    memcpy(h.chain_consumed + c, hm + o_cons, 8u * nc);
+    // only the bytes produced come back: runs of them less than 4 KB apart in one copy
+    size_t run0 = 0, run1 = 0;
+    auto flush = [&]() -> hipError_t { return run1 > run0 ? hipMemcpyAsync(hd + run0, dd + run0, run1 - run0, hipMemcpyDeviceToHost, st) : hipSuccess; };
+    for (uint32_t t = 0; t < nb; t++) {
+      const int32_t r = h.out[b0 + t];
+      if (r <= 0 || (size_t)r > cap_of(b0 + t)) continue;
+      if (run1 > run0 && dso[t] <= run1 + 4096u) { run1 = dso[t] + (size_t)r; continue; }
+      if ((e = flush()) != hipSuccess) return bad("D2H dst", e);
+      run0 = dso[t]; run1 = dso[t] + (size_t)r;
+    }
+    if ((e = flush()) != hipSuccess) return bad("D2H dst", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return bad("hipStreamSynchronize", e);
+    par_blocks(b0, b1, db, [=, &dso](uint32_t i) {
+      const int32_t r = h.out[i];
+      if (r > 0 && (size_t)r <= cap_of(i)) memcpy(h.dst + h.dst_off[i], hd + dso[i - b0], (size_t)r);
+    });
+    c = j;
+  }
+  return LZ4HIP_OK;
+}
+
+// the argument errors of a chain-compress call that can be seen without a device; host: the arrays are the caller's host memory
+const char* cchain_arg_error(const lz4hip::CChainArgs& a, bool host) {
+  if (a.n_chains == 0 && a.n_blocks == 0) return nullptr;
+  if (!a.src || !a.chain_src_off || !a.src_len || !a.chain_first || !a.dst || !a.dst_off || !a.dst_cap || !a.out || !a.chain_consumed) return kNullArg;
+  if (!host) return nullptr;
+  if (a.chain_first[0] != 0u || a.chain_first[a.n_chains] != a.n_blocks) return "chain_first must start at 0 and end at n_blocks";
+  for (uint32_t c = 0; c < a.n_chains; c++) {
+    if (a.chain_first[c] > a.chain_first[c + 1]) return "chain_first must be ascending";
+    if (a.chain_prefix_len) {
+      if (a.chain_prefix_len[c] < 0) return "negative chain_prefix_len";
+      if ((uint64_t)a.chain_prefix_len[c] > a.chain_src_off[c]) return "chain_prefix_len reaches in front of src";
     }
   }
   return nullptr;
@@ -1652,6 +1795,17 @@ int lz4hip_decompress_safe_chain_batch(const uint8_t* src, const uint64_t* src_o
   // whole chains per device: a chain never leaves its lane group, let alone its device
   return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return chain_host_shard(h, ord, c0, c1, err); });
 }
+int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
+                                     const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
+                                     uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains) {
+  const lz4hip::CChainArgs h{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains};
+  if (const char* why = cchain_arg_error(h, true)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
+  int rc = ensure_init();
+  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (n_chains == 0) return LZ4HIP_OK;
+  // whole chains per device: a chain never leaves its wavefront, let alone its device
+  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard(h, ord, c0, c1, err); });
+}
 int lz4hip_compress_fast_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                     const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, const lz4hip_dict* dict) {
   int rc = ensure_init();
@@ -1747,6 +1901,15 @@ int lz4hip_decompress_safe_chain_batch_dev(const uint8_t* src, const uint64_t* s
   if (const char* why = chain_arg_error(a, false)) return fail(LZ4HIP_E_ARG, why);
   BlockCall c{OP_DECOMPRESS_CHAIN};
   c.chain = &a;
+  return on_device(device, n_chains == 0, nullptr, [&] { return launch_block(c, lz4hip::BatchArgs{}, (hipStream_t)stream); });
+}
+int lz4hip_compress_fast_chain_batch_dev(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
+                                         const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
+                                         uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains, int device, void* stream) {
+  const lz4hip::CChainArgs a{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains};
+  if (const char* why = cchain_arg_error(a, false)) return fail(LZ4HIP_E_ARG, why);
+  BlockCall c{OP_COMPRESS_CHAIN};
+  c.cchain = &a;
   return on_device(device, n_chains == 0, nullptr, [&] { return launch_block(c, lz4hip::BatchArgs{}, (hipStream_t)stream); });
 }
 int lz4hip_compress_fast_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,

@@ -27,6 +27,7 @@
 #include "kernels_internal.h"
 #include "wave_dev.h"
 #include "lz4_fast_core.h"
+#include "lz4_fast_chain.h"
 #include "lz4_fast_ms_core.h"
 #include "lz4_fast_v2_core.h"
 #include "mail_ring.h"
@@ -435,6 +436,48 @@ __global__ __launch_bounds__(64) void dict_image_kernel(const uint8_t* tail, uin
 int launch_dict_image(const uint8_t* tail, int32_t keep, void* image, void* stream) {
   if (keep < 8 || keep > 65536 || !tail || !image) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(dict_image_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, tail, (uint32_t)keep, (uint8_t*)image);
+  return (int)hipGetLastError();
+}
+
+// LZ4_compress_fast_continue over chains of linked blocks: the one-sequence-per-step core with its LINK switch on (lz4_fast_core.h), the
+// walk of lz4_fast_chain.h.  Same shape as the dictionary kernel, with a CHAIN as the unit of work: a wavefront draws a chain, builds the
+// chain's table in its 32 KB of LDS -- cleared, or LZ4_loadDict's inserts over the kept prefix (dict_table_build, no image in memory)
+// -- and walks the chain's blocks in order with the table left as the previous block left it.  One chain is serial; nothing here waits
+// for another wavefront.
+struct CChainIoDev {
+  const CChainArgs& a;
+  __device__ __forceinline__ static uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane(v); }
+  // (the builtin returns int: each half goes through uint32_t, or a low half of 2^31 and more is sign-extended over the high one)
+  __device__ __forceinline__ static uint64_t uni64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+  }
+  template <class T> __device__ __forceinline__ static T* uni_ptr(T* p) { return uniform_ptr(p); }
+  __device__ __forceinline__ void put_out(uint32_t i, int32_t r) const { if (__lane_id() == 0) a.out[i] = r; }
+  __device__ __forceinline__ void put_chain(uint32_t c, uint64_t n) const { if (__lane_id() == 0) a.chain_consumed[c] = n; }
+  __device__ __forceinline__ void begin_block(const uint8_t*, uint32_t, uint8_t*, uint32_t) const {}
+};
+__global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_chain_cu_kernel(CChainArgs a, uint32_t* q) {
+  __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
+  WaveDev w(tables[threadIdx.x >> 6]);
+  CChainIoDev io{a};
+  for (;;) {
+    // (the draw in the shape of the other queue kernels here: lane 0 adds, all 64 lanes reach the readfirstlane)
+    uint32_t c = 0;
+    if (__lane_id() == 0) c = atomicAdd(q, 1u);
+    c = __builtin_amdgcn_readfirstlane(c);
+    if (c >= a.n_chains) return;
+    cchain_walk(w, io, a, c);
+    WaveDev::sync();  // the table is reused: the next chain starts from its own
+  }
+}
+int launch_compress_fast_chain(const CChainArgs& a, uint32_t* q, uint32_t n_cus, void* stream) {
+  if (a.n_chains == 0) return 0;
+  if (!q) return (int)hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(q, 0, sizeof(uint32_t), (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  const uint32_t wgs = (a.n_chains + WAVES_PER_CU - 1u) / WAVES_PER_CU;
+  hipLaunchKernelGGL(compress_fast_chain_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a, q);
   return (int)hipGetLastError();
 }
 

@@ -125,6 +125,21 @@ constexpr int32_t kChainBlockCapMax = INT32_MAX - 65535;  // (a block's capacity
 // decode_chain_kernel<8>: lane groups of 8 draw chains from the queue word q (one device uint32_t of scratch) and walk each chain's
 // blocks in order; no group waits for another anywhere.  n_cus = compute units of the device
 int launch_decompress_chain(const ChainArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
+// LZ4_compress_fast_continue(acceleration 1) over chains of linked blocks (compress_fast.hip, lz4_fast_chain.h).  Chain c is the blocks
+// [chain_first[c], chain_first[c + 1]); their SOURCES lie back to back from src + chain_src_off[c] on, behind chain_prefix_len[c] bytes
+// of history (chain_prefix_len == nullptr: none) that the stream has loaded with LZ4_loadDict; block i owns the slot
+// dst[dst_off[i] .. + dst_cap[i]).  out[i] = liblz4's return value (0: it does not fit, or src_len[i] / dst_cap[i] is negative, or the
+// chain would exceed 0x7E000000 bytes), kChainStopped for the blocks behind a chain's first 0; chain_consumed[c] = the source bytes of
+// the blocks that succeeded.  The walk trusts nothing it reads from the arrays: a chain's block range is cut to [0, n_blocks], a
+// negative prefix counts as 0 and one longer than chain_src_off[c] is cut to it.
+struct CChainArgs {
+  const uint8_t* src; const uint64_t* chain_src_off; const int32_t* chain_prefix_len; const int32_t* src_len; const uint32_t* chain_first;
+  uint8_t* dst; const uint64_t* dst_off; const int32_t* dst_cap;
+  int32_t* out; uint64_t* chain_consumed; uint32_t n_blocks, n_chains;
+};
+// compress_fast_chain_cu_kernel: five wavefronts per CU, a 32 KB table each, draw chains from the queue word q (one device uint32_t of
+// scratch); the table stays in LDS from one block of a chain to the next; no wavefront waits for another.  n_cus = compute units
+int launch_compress_fast_chain(const CChainArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
 // The decoded-size query: out[i] = the value LZ4_decompress_safe would return for block i with capacity a.dst_cap[i] (-1 where it or
 // src_len[i] is negative); a.dst and a.dst_off are ignored (may be nullptr) and no output buffer exists.  decode_size_kernel<4, 2048, true>:
 // a wavefront per block; no route word, no sampler, no decode knob

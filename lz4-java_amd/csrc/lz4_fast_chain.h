@@ -1,0 +1,94 @@
+// lz4_fast_chain.h -- the walk over one chain of linked blocks on the compressing side (LZ4_compress_fast_continue, liblz4 1.9.3,
+// acceleration 1), shared by compress_fast.hip (compress_fast_chain_cu_kernel) and the CPU lane simulator
+// (tests/hostsim/hostsim_cchain.cpp).
+//
+// A chain is a run of blocks whose SOURCES lie back to back; block k may match into the blocks before it and into the history that
+// lies directly in front of the chain.  liblz4 defines block k's result as
+//   s = LZ4_createStream();  if (P > 0) LZ4_loadDict(s, chain_src - P, P);
+//   r_k = LZ4_compress_fast_continue(s, chain_src + sum(src_len_j, j < k), dst_k, src_len_k, dst_cap_k, 1);
+// which is its prefix mode throughout (the very first block of a stream without a dictionary runs in external-dictionary mode against
+// an empty dictionary, which parses the same way).  The rules, each confirmed against the reference library by the tests:
+//   * byU32 with the 5-byte hash at every size; ONE table for the whole chain, never cleared between its blocks;
+//   * without a prefix the stream's offset starts at 0: chain position p is index p, and an empty bucket is index 0 -- a real
+//     candidate, the plain core's "every bucket starts as position 0";
+//   * with P > 0 the offset starts at 65536 (LZ4_loadDict adds 64 KB even where it loads nothing).  P < 8 loads nothing and the prefix
+//     bytes are unreachable: keep = 0, empty buckets fall to the lower bound.  P >= 8 inserts the last keep = min(P, 65536) bytes at
+//     stride 3 (dict_table_build); the history's first byte is index 65536 - keep, which is also the lower bound of a candidate
+//     (liblz4 checks it while history plus consumed bytes are under 64 KB; beyond that the 65535-byte distance rule implies it);
+//   * a block under 13 bytes is one literal run and inserts nothing, but the index space moves on;
+//   * a block whose result is 0 (it does not fit; a negative length or capacity; history + consumed + src_len above 0x7E000000, so that
+//     liblz4's index renormalisation is never reached) ends the chain: the blocks behind it get kChainStopped.
+// The table is built at the first block that probes it (13 bytes and more): until then nothing reads it, and the four bytes at
+// chain position 0 -- the fingerprint of the empty buckets of a chain without a prefix -- exist by then.
+//
+// ONE wavefront walks a chain from its first block to its last and waits for nobody; parallelism comes from the number of chains.
+// Nothing outside [chain_src - keep, chain_src + sum src_len) is read, nothing at or past the current block's end, and nothing outside
+// a block's slot is written.
+//
+// Io: uni(v) / uni_ptr(p): a wave-uniform value back in scalar registers (identity on the host); put_out(i, r) / put_chain(c, bytes):
+// the results (lane 0 writes them, vector stores); begin_block(buf, end, d, cap): the block about to run may read [buf, buf + end) and
+// write [d, d + cap) (the simulator's bounds; nothing on the device).
+#pragma once
+#include <stdint.h>
+#include "kernels.h"
+#include "lz4_fast_core.h"
+
+namespace lz4hip {
+
+constexpr uint32_t kChainSpanMax = 0x7E000000u;   // kept history + the chain's source: liblz4's indexes stay below their renormalisation
+
+// the table a chain starts with, in w's LDS: [buf, buf + keep) is the kept history (keep = 0 or 8 .. 65536), prefixed: P > 0
+template <class W>
+LZ4HIP_DEV void link_table_init(W& w, const uint8_t* buf, uint32_t keep, bool prefixed) {
+  using Core = FastCore<W, false, DirectOut<W>, false, false, false, true>;
+  if (keep) {
+    dict_table_build(w, buf, keep);
+  } else {
+    // no prefix: every bucket is {index 0, fingerprint of the bytes at position 0}; a prefix under 8 bytes: empty entries, index 0,
+    // below the lower bound
+    const uint64_t e0 = prefixed ? 0u : (uint64_t)(((w.sld32(buf, 0) * 2654435761u) >> 16) & Core::FPM);
+    w.template lds_fill<false>(1u << Core::HLOG, e0);
+    w.sync();
+  }
+}
+
+template <class W, class Io>
+LZ4HIP_DEV void cchain_walk(W& w, Io& io, const CChainArgs& a, uint32_t c) {
+  using Core = FastCore<W, false, DirectOut<W>, false, false, false, true>;
+  uint32_t b1 = io.uni(a.chain_first[c + 1]), b0 = io.uni(a.chain_first[c]);
+  if (b1 > a.n_blocks) b1 = a.n_blocks;
+  if (b0 > b1) b0 = b1;
+  const uint64_t soff = io.uni64(a.chain_src_off[c]);
+  uint64_t P = 0;
+  if (a.chain_prefix_len) { const int32_t p = (int32_t)io.uni((uint32_t)a.chain_prefix_len[c]); P = p > 0 ? (uint64_t)p : 0u; }
+  if (P > soff) P = soff;
+  const uint32_t keep = P < 8u ? 0u : (P > 65536u ? 65536u : (uint32_t)P);
+  const uint32_t ibase = P ? 65536u - keep : 0u;
+  const uint8_t* const buf = io.uni_ptr(a.src + soff - keep);
+  uint32_t pos = keep;       // where the next block starts in buf
+  bool table_ready = false;
+  uint32_t i = b0;
+  while (i < b1) {
+    const int32_t sl = (int32_t)io.uni((uint32_t)a.src_len[i]), dc = (int32_t)io.uni((uint32_t)a.dst_cap[i]);
+    uint32_t r = 0;
+    if (sl >= 0 && dc >= 0 && (uint64_t)pos + (uint32_t)sl <= kChainSpanMax) {
+      const uint32_t end = pos + (uint32_t)sl;
+      uint8_t* d = io.uni_ptr(a.dst + io.uni64(a.dst_off[i]));
+      io.begin_block(buf, end, d, (uint32_t)dc);
+      if (sl >= 13 && !table_ready) { link_table_init(w, buf, keep, P != 0u); table_ready = true; }
+      DirectOut<W> out(w, buf, end, d, (uint32_t)dc);
+      out.limited = (uint32_t)dc < (uint32_t)sl + (uint32_t)sl / 255u + 16u;   // (by the block's length, not by its end in buf)
+      Core core(w, out, buf, end);
+      core.blk = pos; core.ibase = ibase; core.lowidx = ibase;
+      r = core.run();
+    }
+    io.put_out(i, (int32_t)r);
+    i++;
+    if (r == 0u) break;
+    pos += (uint32_t)sl;
+  }
+  for (; i < b1; i++) io.put_out(i, kChainStopped);
+  io.put_chain(c, (uint64_t)(pos - keep));
+}
+
+}  // namespace lz4hip

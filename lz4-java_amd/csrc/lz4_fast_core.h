@@ -295,10 +295,21 @@ template <> struct DictState<true> {
   uint32_t cn = 0;
   bool cdict = false;
 };
-template <class W, bool U16, class Out = DirectOut<W>, bool PK = false, bool ACC = false, bool DICT = false>
-struct FastCore : DictState<DICT> {
+// LINK: one block of a chain of linked blocks (LZ4_compress_fast_continue in liblz4's prefix mode; lz4_fast_chain.h walks the chain).
+// `src` is the start of the chain's kept history and every position is a position in that one buffer: the block is [blk, n), the
+// blocks and the history in front of it are [0, blk).  byU32 with 64-bit entries at every size; the table holds INDEXES, position p is
+// ibase + p, and it is the caller's: it lives from one block of the chain to the next (link_table_init before the first block that
+// probes).  A candidate must lie at or above `lowidx` (liblz4's dictSmall check; past 64 KB of history the distance check implies it)
+// and within 65535 bytes; it is read from the same buffer, so a match may start in front of the block and run into it, and the
+// catch-up may go back to position 0.  Position blk is inserted and never probed; mflimit and matchlimit come from n, and nothing at or
+// past n is read.  LINK = false compiles to what it did before the switch existed (the state lives in a base of its own, as DictState).
+template <bool LINK> struct LinkState { static constexpr uint32_t blk = 0, ibase = 0, lowidx = 0; };
+template <> struct LinkState<true> { uint32_t blk = 0, ibase = 0, lowidx = 0; };
+template <class W, bool U16, class Out = DirectOut<W>, bool PK = false, bool ACC = false, bool DICT = false, bool LINK = false>
+struct FastCore : DictState<DICT>, LinkState<LINK> {
   static_assert(!(U16 && PK), "compact entries are a byU32 layout");
   static_assert(!DICT || (!U16 && !PK && !ACC), "the dictionary core is byU32 with 64-bit entries, acceleration 1");
+  static_assert(!LINK || (!U16 && !PK && !ACC && !DICT), "the linked-block core is byU32 with 64-bit entries, acceleration 1");
   static constexpr uint32_t kDictBase = 65536u;   // DICT: index of block position 0 (the stream's offset after LZ4_loadDict)
   static constexpr bool S32 = U16 || PK;           // entries are 32 bits
   static constexpr uint32_t kPackMaxN = 1u << 22;  // PK: positions have 22 bits
@@ -332,6 +343,7 @@ struct FastCore : DictState<DICT> {
   uint32_t p_S = 0, p_ip = 0;
   using DictState<DICT>::dict; using DictState<DICT>::keep; using DictState<DICT>::image;
   using DictState<DICT>::cs; using DictState<DICT>::cn; using DictState<DICT>::cdict;
+  using LinkState<LINK>::blk; using LinkState<LINK>::ibase; using LinkState<LINK>::lowidx;
 
   LZ4HIP_DEV FastCore(W& w_, Out& out_, const uint8_t* s, uint32_t n_, FastStats* st_ = nullptr)
       : w(w_), out(out_), src(s), n(n_), st(st_) {
@@ -466,6 +478,16 @@ struct FastCore : DictState<DICT> {
 
   // ---- the compressor ------------------------------------------------------------------------
   LZ4HIP_DEV uint32_t run() {
+    if constexpr (LINK) {
+      anchor = blk;
+      if (n - blk < 13u) return out.last(blk);  // all literals; nothing is inserted (an empty block: the single token 0x00)
+      // liblz4's first insert, the block's first position (8 bytes are there: the block has 13)
+      const VU64 x0 = w.ldu64(src, VU(blk));
+      const VU h0 = W::lo32(((x0 << 24) * 889523592379ull) >> (64 - HLOG));
+      (void)w.template lds_max<S32>(h0, mk_entry(VU(blk + ibase), fp32(W::lo32(x0))), w.lane() == 0u);
+      w.sync();
+      return loop<0>(false, blk + 1u, 0u, 0u);
+    }
     if (n < 13u) return out.last(0u);  // all literals (n == 0: the single token 0x00)
     if constexpr (DICT) {
       // the table as LZ4_loadDict leaves it (no image: no dictionary, every entry empty = index 0, which the lower-bound check
@@ -543,10 +565,11 @@ struct FastCore : DictState<DICT> {
       LZ4HIP_PHASE(0, w.bcast(h, 0));   // t[0]: input window arrived + hash
       // ---- [2] table lookup, tentative hits, commit ----
       const VE e = w.template lds_rdu<S32>(h);
-      const VE newe = mk_entry(DICT ? pos + kDictBase : pos, fp);
+      const VE newe = mk_entry(LINK ? pos + ibase : (DICT ? pos + kDictBase : pos), fp);
       // (ballots of plain compares are free -- the compare already writes the lane mask; the masks are combined on the scalar side)
       uint64_t tmask = w.ballot(e_fp(e) == fp) & probem;
       if constexpr (DICT) tmask &= w.ballot(e_pos(e) + MAXD >= pos + kDictBase) & w.ballot(e_pos(e) >= kDictBase - keep);
+      else if constexpr (LINK) tmask &= w.ballot(e_pos(e) + MAXD >= pos + ibase) & w.ballot(e_pos(e) >= lowidx);
       else if constexpr (!U16) tmask &= w.ballot(e_pos(e) + MAXD >= pos);
       const uint64_t imask = ~validm;
       uint32_t k0 = tmask ? (uint32_t)ctz64(tmask) : 64u;
@@ -564,6 +587,7 @@ struct FastCore : DictState<DICT> {
       uint32_t mpos = se_pos(w.template bcast_e<S32>(e, (int)kk));
       [[maybe_unused]] uint32_t midx = 0u, lim = 0u;   // DICT: the candidate's index (mpos becomes its offset in cs); where the forward count stops
       if constexpr (DICT) { midx = mpos; mpos = locate(have_hit, midx, hpos, lim); }
+      if constexpr (LINK) mpos -= ibase;   // (without a hit: any value, the loads below are clamped)
       bool hit_post = post && k0 == 1u;
       uint32_t maxback = (!have_hit || hit_post) ? 0u : ((hpos - anchor) < mpos ? (hpos - anchor) : mpos);
       // (only the first kSpecLanes lanes take part -- 8 bytes each: the candidate side is a random re-read of the block and
@@ -614,6 +638,7 @@ struct FastCore : DictState<DICT> {
         }
         uint64_t t2 = w.ballot(e_fp(se) == fp) & inm & probem;
         if constexpr (DICT) t2 &= w.ballot(e_pos(se) + MAXD >= pos + kDictBase) & w.ballot(e_pos(se) >= kDictBase - keep);
+        else if constexpr (LINK) t2 &= w.ballot(e_pos(se) + MAXD >= pos + ibase) & w.ballot(e_pos(se) >= lowidx);
         else if constexpr (!U16) t2 &= w.ballot(e_pos(se) + MAXD >= pos);
         const bool had = have_hit;
         const uint32_t hpos_old = hpos, mpos_old = mpos;
@@ -631,6 +656,7 @@ struct FastCore : DictState<DICT> {
           hpos = w.bcast(pos, (int)k0);
           mpos = se_pos(w.template bcast_e<S32>(se, (int)k0));
           if constexpr (DICT) { midx = mpos; mpos = locate(true, midx, hpos, lim); }
+          if constexpr (LINK) mpos -= ibase;
           if (!had || hpos != hpos_old || (DICT ? midx != midx_old : mpos != mpos_old)) {  // the speculation fetched the wrong candidate
             hit_post = post && k0 == 1u;
             maxback = hit_post ? 0u : ((hpos - anchor) < mpos ? (hpos - anchor) : mpos);
@@ -745,7 +771,9 @@ struct FastCore : DictState<DICT> {
 // The table LZ4_loadDict leaves, in FastCore<.., DICT>'s entry layout: tail positions 0, 3, 6, ... while p <= keep - 8 (so the last 7
 // positions are never candidates), index kDictBase - keep + p, the last insert of a bucket wins (atomic max on the index, as in the
 // core).  One wavefront builds it in its own table (w's LDS) and writes the 4096 entries to image[0 .. 32768).  keep >= 8.
-template <class W>
+// WRITE_OUT = false: the table is left in w's LDS and `image` is not looked at -- what the linked-block kernel starts a chain with
+// (dict_table_build).
+template <class W, bool WRITE_OUT = true>
 LZ4HIP_DEV void dict_image_build(W& w, const uint8_t* tail, uint32_t keep, uint8_t* image) {
   using Core = FastCore<W, false, DirectOut<W>, false, false, true>;
   using VU = typename W::VU;
@@ -761,12 +789,16 @@ LZ4HIP_DEV void dict_image_build(W& w, const uint8_t* tail, uint32_t keep, uint8
     (void)w.template lds_max<false>(h, Core::mk_entry(p + (Core::kDictBase - keep), Core::fp32(W::lo32(x))), act);
   }
   w.sync();
-  for (uint32_t i = 0; i < (1u << Core::HLOG); i += 64u) {
-    const VU h = w.lane() + i;
-    const VU64 e = w.template lds_rdu<false>(h);
-    w.st32(image, h * 8u, W::lo32(e), VB(true));
-    w.st32(image, h * 8u + 4u, W::lo32(e >> 32), VB(true));
+  if constexpr (WRITE_OUT) {
+    for (uint32_t i = 0; i < (1u << Core::HLOG); i += 64u) {
+      const VU h = w.lane() + i;
+      const VU64 e = w.template lds_rdu<false>(h);
+      w.st32(image, h * 8u, W::lo32(e), VB(true));
+      w.st32(image, h * 8u + 4u, W::lo32(e >> 32), VB(true));
+    }
   }
 }
+template <class W>
+LZ4HIP_DEV void dict_table_build(W& w, const uint8_t* tail, uint32_t keep) { dict_image_build<W, false>(w, tail, keep, nullptr); }
 
 }  // namespace lz4hip

@@ -9,6 +9,7 @@
 //   LZ4Dictionary, LZ4SafeDecompressor::decompressWithDict, LZ4HIPBatch::decompressSafeDict
 //                                                   =  LZ4_decompress_safe_usingDict of liblz4's main API against a dictionary that is not
 //                                                      contiguous with the destination (no reference entry reaches it)
+//   LZ4HIPBatch::compressFastChain                  =  LZ4_compress_fast_continue over chains of linked blocks (liblz4's prefix mode)
 //   LZ4HIPBatch::decompressSafeChain                =  LZ4_decompress_safe_continue over chains of linked blocks (liblz4's rolling-prefix
 //                                                      mode; no reference entry reaches it)
 //   LZ4HIPCompressor::compressWithDict, LZ4HIPBatch::compressDict
@@ -317,6 +318,48 @@ struct LZ4HIPBatch {
                                               dest.empty() ? one.data() : dest.data(), nc ? chainDestOff.data() : &none64, nc ? chainDestCap.data() : &none64,
                                               chainPrefixLen.empty() ? nullptr : chainPrefixLen.data(), n ? r.lengths.data() : &none,
                                               nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
+    return r;
+  }
+  // LZ4_compress_fast_continue over chains of linked blocks (lz4hip_compress_fast_chain_batch): chain c is the blocks
+  // [chainFirst[c], chainFirst[c + 1]), whose sources lie back to back from src[chainSrcOff[c]] on, behind chainPrefixLen[c] bytes of
+  // history that lie in front of it in src (an empty vector: no history; the stream loads it with LZ4_loadDict); block i owns the slot
+  // dest[destOff[i], + maxDestLen[i]).  lengths[i] = liblz4's return value (0: it did not fit, which ends the chain),
+  // LZ4HIP_CHAIN_STOPPED behind a chain's first 0; chainLengths[c] = the source bytes of chain c's blocks that succeeded
+  static Chains compressFastChain(const bytes& src, const std::vector<uint64_t>& chainSrcOff, const std::vector<int32_t>& srcLen,
+                                  const std::vector<uint32_t>& chainFirst, bytes& dest, const std::vector<uint64_t>& destOff,
+                                  const std::vector<int32_t>& maxDestLen, const std::vector<int32_t>& chainPrefixLen = {}) {
+    const size_t n = srcLen.size(), nc = chainSrcOff.size();
+    if (destOff.size() != n || maxDestLen.size() != n) throw std::invalid_argument("per-block arrays differ in length");
+    if (chainFirst.size() != nc + 1 || (!chainPrefixLen.empty() && chainPrefixLen.size() != nc))
+      throw std::invalid_argument("per-chain arrays differ in length");
+    if (chainFirst[0] != 0 || chainFirst[nc] != n) throw std::invalid_argument("chainFirst must ascend from 0 to the number of blocks");
+    for (size_t c = 0; c < nc; c++) {
+      if (chainFirst[c] > chainFirst[c + 1]) throw std::invalid_argument("chainFirst must ascend from 0 to the number of blocks");
+      uint64_t total = 0;
+      for (uint32_t i = chainFirst[c]; i < chainFirst[c + 1]; i++) {
+        if (srcLen[i] < 0) throw std::invalid_argument("lengths must be >= 0");
+        total += (uint64_t)srcLen[i];
+      }
+      if (chainSrcOff[c] > src.size() || total > src.size() - chainSrcOff[c]) throw std::out_of_range("chain " + std::to_string(c));
+      if (!chainPrefixLen.empty()) {
+        if (chainPrefixLen[c] < 0) throw std::invalid_argument("lengths must be >= 0");
+        if ((uint64_t)chainPrefixLen[c] > chainSrcOff[c]) throw std::out_of_range("history of chain " + std::to_string(c));
+      }
+    }
+    for (size_t i = 0; i < n; i++) {
+      if (maxDestLen[i] < 0) throw std::invalid_argument("lengths must be >= 0");
+      if (destOff[i] > dest.size() || (uint64_t)maxDestLen[i] > dest.size() - destOff[i]) throw std::out_of_range("slot " + std::to_string(i));
+    }
+    Chains r;
+    r.lengths.assign(n, 0);
+    r.chainLengths.assign(nc, 0);
+    bytes one(1);                                 // (an empty buffer still hands the library a pointer)
+    int32_t none = 0;
+    uint64_t none64 = 0;
+    status(lz4hip_compress_fast_chain_batch(src.empty() ? one.data() : src.data(), nc ? chainSrcOff.data() : &none64,
+                                            chainPrefixLen.empty() ? nullptr : chainPrefixLen.data(), n ? srcLen.data() : &none, chainFirst.data(),
+                                            dest.empty() ? one.data() : dest.data(), n ? destOff.data() : &none64, n ? maxDestLen.data() : &none,
+                                            n ? r.lengths.data() : &none, nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
     return r;
   }
   static std::vector<int32_t> decompressedLengths(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen,

@@ -56,6 +56,17 @@ struct BatchEngine {
                                            (uint32_t)so.size(), 1u));
     return out;
   }
+  // one chain of linked blocks (lz4hip_compress_fast_chain_batch): the blocks' sources lie back to back from src + srcOff on, behind
+  // `prefix` bytes of history that lie in front of them; block i owns dst[d_o[i], + dc[i]).  Returns liblz4's values per block
+  std::vector<int32_t> compressFastChain(const uint8_t* src, uint64_t srcOff, int32_t prefix, const std::vector<int32_t>& sl, uint8_t* dst,
+                                         const std::vector<uint64_t>& d_o, const std::vector<int32_t>& dc) const {
+    std::vector<int32_t> out(sl.size());
+    if (sl.empty()) return out;
+    const uint32_t first[2] = {0u, (uint32_t)sl.size()};
+    uint64_t consumed = 0;
+    chk(lz4hip_compress_fast_chain_batch(src, &srcOff, &prefix, sl.data(), first, dst, d_o.data(), dc.data(), out.data(), &consumed, (uint32_t)sl.size(), 1u));
+    return out;
+  }
   std::vector<int32_t> decompressFast(const uint8_t* src, const std::vector<uint64_t>& so, const std::vector<int32_t>& scap, uint8_t* dst,
                                       const std::vector<uint64_t>& d_o, const std::vector<int32_t>& dl) const {
     std::vector<int32_t> out(so.size());
@@ -180,6 +191,25 @@ inline Compressed compressBlocks(const BatchEngine& e, const bytes& data, int bl
   for (int32_t s : c.sizes) if (s <= 0) throw LZ4Exception("maxDestLen is too small");  // LZ4JNICompressor.java:39-41
   return c;
 }
+// the same blocks as ONE chain of linked blocks behind `history` (at most the last 64 KB written of the frame)
+inline Compressed compressChain(const BatchEngine& e, const bytes& history, const bytes& data, int blockSize) {
+  Compressed c;
+  const size_t n = (data.size() + (size_t)blockSize - 1) / (size_t)blockSize;
+  c.bound = maxCompressedLength(blockSize);
+  c.dst.resize(n * (size_t)c.bound);
+  std::vector<uint64_t> d_o(n);
+  std::vector<int32_t> dc(n, c.bound);
+  c.lens.resize(n);
+  for (size_t i = 0; i < n; i++) {
+    c.lens[i] = (int32_t)std::min<size_t>((size_t)blockSize, data.size() - i * (size_t)blockSize);
+    d_o[i] = i * (size_t)c.bound;
+  }
+  bytes src(history);
+  src.insert(src.end(), data.begin(), data.end());
+  c.sizes = e.compressFastChain(src.data(), history.size(), (int32_t)history.size(), c.lens, c.dst.data(), d_o, dc);
+  for (int32_t s : c.sizes) if (s <= 0) throw LZ4Exception("maxDestLen is too small");
+  return c;
+}
 }  // namespace detail
 
 // =====================================================================================================
@@ -221,10 +251,16 @@ struct BD {  // LZ4FrameOutputStream.java:374-404
 
 class LZ4FrameOutputStream {
  public:
+  // linkedBlocks = true (not in the reference, which writes independent blocks only; the default's bytes are unchanged): the frame is
+  // written WITHOUT the block-independence flag -- what the `lz4` command line writes by default and LZ4FrameInputStream(linkedBlocks =
+  // true) reads.  Every batch of blocks is ONE chain of linked blocks (LZ4_compress_fast_continue) whose prefix is the last 64 KB this
+  // stream wrote of the frame before; a block that does not shrink is stored raw and still counts as history.  Assembled on the host.
+  // One frame is one chain on one wavefront at a time: a FORMAT feature (smaller frames for small blocks), not a fast path.
   LZ4FrameOutputStream(std::ostream& out, frame::BLOCKSIZE blockSize = frame::SIZE_4MB, int64_t knownSize = -1,
                        std::initializer_list<frame::Bits> bits = {frame::BLOCK_INDEPENDENCE}, BatchEngine engine = BatchEngine(),
-                       size_t batchBlocks = 64)
-      : out_(out), e_(engine), flg_(1, mask(bits)), bd_(blockSize), knownSize_(knownSize), batch_(batchBlocks ? batchBlocks : 1) {
+                       size_t batchBlocks = 64, bool linkedBlocks = false)
+      : out_(out), e_(engine), flg_(1, linkedBlocks ? mask(bits) & ~(1 << frame::BLOCK_INDEPENDENCE) : mask(bits), linkedBlocks), bd_(blockSize),
+        knownSize_(knownSize), batch_(batchBlocks ? batchBlocks : 1), linked_(linkedBlocks) {
     maxBlockSize_ = bd_.getBlockMaximumSize();
     if (flg_.isEnabled(frame::CONTENT_SIZE) && knownSize < 0)
       throw std::invalid_argument("Known size must be greater than zero in order to use the known size feature");
@@ -263,12 +299,16 @@ class LZ4FrameOutputStream {
     buf_.erase(buf_.begin(), buf_.begin() + (std::ptrdiff_t)nbytes);
     if (flg_.isEnabled(frame::CONTENT_CHECKSUM)) content().update(data.data(), data.size());  // :211-213
     const bool bc = flg_.isEnabled(frame::BLOCK_CHECKSUM);
-    if (!e_.hostAssembly) {
+    if (!linked_ && !e_.hostAssembly) {
       const bytes blocks = e_.containerBlocks(0, data, maxBlockSize_, bc);
       out_.write((const char*)blocks.data(), (std::streamsize)blocks.size());
       return;
     }
-    const detail::Compressed c = detail::compressBlocks(e_, data, maxBlockSize_);
+    const detail::Compressed c = linked_ ? detail::compressChain(e_, history_, data, maxBlockSize_) : detail::compressBlocks(e_, data, maxBlockSize_);
+    if (linked_) {   // the last 64 KB written
+      history_.insert(history_.end(), data.begin(), data.end());
+      if (history_.size() > 65536) history_.erase(history_.begin(), history_.end() - 65536);
+    }
     bytes o;
     std::vector<uint64_t> spanOff;
     std::vector<int32_t> spanLen;
@@ -304,6 +344,8 @@ class LZ4FrameOutputStream {
   bytes buf_;
   std::unique_ptr<xxhash::StreamingXXHash32> content_;  // LZ4FrameOutputStream.java:116
   bool finished_ = false;
+  bool linked_ = false;   // linkedBlocks: no BLOCK_INDEPENDENCE, one chain per batch
+  bytes history_;         // (linked_) the last 64 KB written of the frame
 };
 
 class LZ4FrameInputStream {

@@ -132,7 +132,70 @@ public final class LZ4HIPBatch {
     }
   }
 
-  /** {@code outLen[i]} of {@link #decompressSafeChain}: block i lies behind its chain's first failed block and was not decoded. */
+  /**
+   * liblz4's {@code LZ4_compress_fast_continue} over chains of linked blocks (its prefix mode, acceleration 1): chain c is the blocks
+   * {@code chainFirst[c] .. chainFirst[c + 1] - 1}, whose sources lie back to back from {@code src[chainSrcOff[c]]} on, behind
+   * {@code chainPrefixLen[c]} bytes of history that lie in front of it in {@code src} ({@code null}: no history; the stream loads it with
+   * {@code LZ4_loadDict}).  Block i owns the slot {@code dest[destOff[i], destOff[i]+destCap[i])}.  outLen[i] &gt; 0: the compressed size;
+   * 0: it did not fit, which ends the chain -- the blocks behind it get {@link #CHAIN_STOPPED}.  chainConsumed[c]: the source bytes of
+   * chain c's blocks that succeeded.
+   */
+  public static void compressFastChain(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
+      ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed) {
+    final int n = srcLen.length, nc = chainSrcOff.length;
+    if (destOff.length != n || destCap.length != n || outLen.length != n) {
+      throw new IllegalArgumentException("per-block arrays differ in length");
+    }
+    if (chainFirst.length != nc + 1 || chainConsumed.length != nc || (chainPrefixLen != null && chainPrefixLen.length != nc)) {
+      throw new IllegalArgumentException("per-chain arrays differ in length");
+    }
+    if (!src.isDirect() || !dest.isDirect()) {
+      throw new IllegalArgumentException("direct buffers required");
+    }
+    if (dest.isReadOnly()) {
+      throw new java.nio.ReadOnlyBufferException();
+    }
+    if (chainFirst[0] != 0 || chainFirst[nc] != n) {
+      throw new IllegalArgumentException("chainFirst must ascend from 0 to the number of blocks");
+    }
+    for (int c = 0; c < nc; c++) {
+      if (chainFirst[c] > chainFirst[c + 1]) {
+        throw new IllegalArgumentException("chainFirst must ascend from 0 to the number of blocks");
+      }
+      long total = 0;
+      for (int i = chainFirst[c]; i < chainFirst[c + 1]; i++) {
+        if (srcLen[i] < 0) {
+          throw new IllegalArgumentException("lengths must be >= 0");
+        }
+        total += srcLen[i];
+      }
+      if (chainSrcOff[c] < 0 || chainSrcOff[c] + total > src.capacity()) {
+        throw new ArrayIndexOutOfBoundsException("chain " + c);
+      }
+      if (chainPrefixLen != null) {
+        if (chainPrefixLen[c] < 0) {
+          throw new IllegalArgumentException("lengths must be >= 0");
+        }
+        if (chainPrefixLen[c] > chainSrcOff[c]) {
+          throw new ArrayIndexOutOfBoundsException("history of chain " + c);
+        }
+      }
+    }
+    for (int i = 0; i < n; i++) {
+      if (destCap[i] < 0) {
+        throw new IllegalArgumentException("lengths must be >= 0");
+      }
+      if (destOff[i] < 0 || destOff[i] + destCap[i] > dest.capacity()) {
+        throw new ArrayIndexOutOfBoundsException("slot " + i);
+      }
+    }
+    final int rc = LZ4HIPJNI.LZ4HIP_batchFastChain(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, n, nc);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /** {@code outLen[i]} of {@link #decompressSafeChain} and {@link #compressFastChain}: block i lies behind its chain's first failed block and was not done. */
   public static final int CHAIN_STOPPED = Integer.MIN_VALUE + 6;
 
   /**

@@ -109,6 +109,14 @@ enum LZ4HIPJNI {
   static native int LZ4HIP_batchSafeChain(ByteBuffer src, long[] srcOff, int[] srcLen, int[] stored, int[] destCap, int[] chainFirst,
                                           ByteBuffer dest, long[] chainDestOff, long[] chainDestCap, int[] chainPrefixLen, int[] outLen,
                                           long[] chainOutLen, int nBlocks, int nChains);
+  /* LZ4_compress_fast_continue over chains of linked blocks, DIRECT buffers: chain c is the blocks chainFirst[c] .. chainFirst[c + 1] - 1,
+   * whose sources lie back to back from src[chainSrcOff[c]] on behind chainPrefixLen[c] bytes of history (null: none); block i owns
+   * dest[destOff[i], + destCap[i]).  outLen = liblz4's return values (0 ends a chain, LZ4HIPBatch.CHAIN_STOPPED behind it),
+   * chainConsumed = the source bytes of each chain's blocks that succeeded.  Returns 0 or a negative lz4hip_status (a null required
+   * argument: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchFastChain(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
+                                          ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed,
+                                          int nBlocks, int nChains);
   /* LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream against a dictionary handle: the compressed size, 0 (maxDestLen too
    * small) or a library failure as LZ4HIP_compress_fast; same NULL / pinning rules */
   static native int LZ4HIP_compress_fast_dict(long dict, byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,

@@ -46,6 +46,7 @@ class HIPEngine:
 
     decompressSafe = staticmethod(LZ4HIPBatch.decompressSafe)
     decompressSafeChain = staticmethod(LZ4HIPBatch.decompressSafeChain)   # linked blocks: LZ4FrameInputStream(linkedBlocks=True)
+    compressFastChain = staticmethod(LZ4HIPBatch.compressFastChain)       # linked blocks: LZ4FrameOutputStream(linkedBlocks=True)
     decompressFast = staticmethod(LZ4HIPBatch.decompressFast)
     xxh32 = staticmethod(LZ4HIPBatch.xxh32)
 
@@ -82,6 +83,20 @@ def _compress_batch(engine, data, blockSize):
         if s <= 0:
             raise LZ4Exception("maxDestLen is too small")  # LZ4JNICompressor.java:39-41
     return dst, bound, lens, sizes
+
+
+def _compress_chain(engine, history, data, blockSize):
+    """compress data[i*blockSize : +blockSize] for all i as ONE chain of linked blocks behind `history` -> as _compress_batch"""
+    n = (len(data) + blockSize - 1) // blockSize
+    bound = maxCompressedLength(blockSize)
+    dst = bytearray(n * bound)
+    lens = [min(blockSize, len(data) - i * blockSize) for i in range(n)]
+    P = len(history)
+    sizes, _ = engine.compressFastChain(history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P])
+    for s in sizes:
+        if s <= 0:
+            raise LZ4Exception("maxDestLen is too small")
+    return dst, bound, lens, list(sizes)
 
 
 # =================================================================================================
@@ -180,15 +195,34 @@ class LZ4FrameOutputStream(io.RawIOBase):
     """Twin of lz4/LZ4FrameOutputStream.java.  `out` is any object with write(bytes).  Blocks are queued until
     `batchBlocks` full blocks are buffered (or flush()/close()), then compressed in one launch; the bytes
     written are exactly the reference's for the same input and flags (flush() cuts a short block at the same
-    place the reference's flush() does)."""
+    place the reference's flush() does).
 
-    def __init__(self, out, blockSize=BLOCKSIZE.SIZE_4MB, knownSize=-1, *bits, engine=None, batchBlocks=64):
+    linkedBlocks=True (not in the reference, which writes independent blocks only; the default is False and its bytes are unchanged):
+    the frame is written WITHOUT the block-independence flag -- what the `lz4` command line writes by default, and what
+    LZ4FrameInputStream(linkedBlocks=True) reads.  Every batch of blocks is ONE chain of linked blocks (engine.compressFastChain:
+    LZ4_compress_fast_continue) whose prefix is the last 64 KB this stream wrote of the frame before; a block that does not shrink is
+    stored raw and still counts as history for the blocks behind it.  The frame is assembled on the host.  One frame is one chain on
+    one wavefront at a time: this is a FORMAT feature (smaller frames for small blocks), not a fast path -- throughput comes from
+    many chains per launch (LZ4HIPBatch.compressFastChain), not from one stream."""
+
+    def __init__(self, out, blockSize=BLOCKSIZE.SIZE_4MB, knownSize=-1, *bits, engine=None, batchBlocks=64, linkedBlocks=False):
         super().__init__()
         self.out = out
         self.engine = engine or HIPEngine()
-        if not bits:
-            bits = (FLG.Bits.BLOCK_INDEPENDENCE,)
-        self.flg = FLG.of(*bits)
+        self.linkedBlocks = linkedBlocks
+        self.history = b""   # (linkedBlocks) the last 64 KB written of the frame
+        if linkedBlocks:
+            if not hasattr(self.engine, "compressFastChain"):
+                raise ValueError("the engine cannot compress linked blocks")
+            m = 0
+            for b in bits:
+                if b != FLG.Bits.BLOCK_INDEPENDENCE:
+                    m |= 1 << b
+            self.flg = FLG(FLG.DEFAULT_VERSION, m, allowDependent=True)
+        else:
+            if not bits:
+                bits = (FLG.Bits.BLOCK_INDEPENDENCE,)
+            self.flg = FLG.of(*bits)
         self.bd = BD(blockSize)
         self.maxBlockSize = self.bd.getBlockMaximumSize()
         self.knownSize = knownSize
@@ -237,10 +271,14 @@ class LZ4FrameOutputStream(io.RawIOBase):
         if self.content is not None:
             self.content.update(data, 0, len(data))  # :211-213: the content checksum streams over the uncompressed bytes
         block_checksum = self.flg.isEnabled(FLG.Bits.BLOCK_CHECKSUM)
-        if hasattr(self.engine, "containerBlocks"):   # assembled on the device
+        if self.linkedBlocks:                          # one chain behind the last 64 KB written; assembled on the host
+            dst, bound, lens, sizes = _compress_chain(self.engine, self.history, data, self.maxBlockSize)
+            self.history = (self.history + data)[-65536:]
+        elif hasattr(self.engine, "containerBlocks"):   # assembled on the device
             self.out.write(self.engine.containerBlocks(LZ4HIPBatch.FRAME_BLOCKS, data, self.maxBlockSize, block_checksum))
             return
-        dst, bound, lens, sizes = _compress_batch(self.engine, data, self.maxBlockSize)
+        else:
+            dst, bound, lens, sizes = _compress_batch(self.engine, data, self.maxBlockSize)
         outb = bytearray()
         spans = []
         for i, (raw_len, clen) in enumerate(zip(lens, sizes)):
