@@ -403,7 +403,14 @@ int lz4hip_xxh64_batch(const uint8_t* buf, const uint64_t* off, const int32_t* l
 /* ---- device-pointer batch API ----------------------------------------------------------------
  * Same contracts, every pointer is a DEVICE pointer on `device` (an index into the initialised
  * device list), work is enqueued on `stream` (a hipStream_t, NULL = the null stream) and the call
- * returns without synchronising: no PCIe traffic, this is what bench.py times.                  */
+ * returns without synchronising: no PCIe traffic, this is what bench.py times.
+ * Offsets, strides and byte counts (src_off, dst_off, chain_*_off, off, stride * index, n_bytes, src_span) are full 64-bit values:
+ * the buffers may be tens of GiB, and a block may lie at, across or past 2^31 and 2^32 bytes from its buffer's start, at any
+ * alignment.  This is tested on the GPU: tests/far_common.py lists every *_dev function declared in this header with the test
+ * that runs it at such offsets -- tests/test_gpu_far_offsets.py for the block, dictionary, xxhash, generator and container entry
+ * points (the containers with an input, compressed slots, a container and output slots that all pass 2^32), tests/test_gpu_cchain.py
+ * for the two chain entry points -- and tests/test_far_table.py fails when a *_dev function is declared here without an entry.
+ * Not covered there: lz4hip_xxh_stream_update_dev (a pointer and a 32-bit length, no offset) and the developer profile entry.  */
 int lz4hip_compress_fast_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                    uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                    int32_t* out_len, uint32_t n_blocks, int device, void* stream);
