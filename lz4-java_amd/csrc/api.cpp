@@ -19,9 +19,11 @@
 #include <string>
 #include "../../include/lz4hip.h"
 #include "kernels.h"
+#include "host_staging.h"
 
 namespace {
 
+using staging::al16;
 thread_local std::string g_err;
 std::mutex g_mu;
 std::vector<int> g_devs;  // HIP device ordinals the engine is initialised on
@@ -50,6 +52,9 @@ int ensure_init() {
   }
   return lz4hip_init(nullptr, 0);
 }
+
+// what every compute entry point asks first: the engine is up on a device, or the status of having none (message set)
+int need_device() { const int rc = ensure_init(); return rc ? fail(rc, "no HIP device: liblz4hip has no CPU fallback") : LZ4HIP_OK; }
 
 // the HIP ordinal of engine device index `device`
 int ordinal(int device, int* out) {
@@ -246,6 +251,17 @@ int launch_decode(const lz4hip::BatchArgs& a, bool safe, hipStream_t st) {
   return lz4hip::launch_decompress(a, safe, g_decode_lanes.load(), g_decode_pipe.load(), g_decode_stage.load(), g_decode_ring.load(), st, route);
 }
 
+// a queue word of scratch around a launcher: launch(q) -> the launcher's hipError_t, which is passed on
+template <class Launch>
+int with_queue_word(hipStream_t st, Launch launch) {
+  uint32_t* q = nullptr;
+  const hipError_t me = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
+  if (me != hipSuccess) return (int)me;
+  const int e = launch(q);
+  (void)hipFreeAsync(q, st);
+  return e;
+}
+
 // The one place where a block operation reaches its kernels, on device arrays: the device-pointer entry points (dev_batch) and the
 // host-pointer path (host_shard) both come here.  Returns 0, a launcher's hipError_t (> 0), or a status (< 0) whose message is set.
 int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st) {
@@ -261,24 +277,12 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
       if (c.dict) { const int rc = dict_resident(c.dict, &dict_end, &dict_len); if (rc) return rc; }
       return lz4hip::launch_decompress_dict(a, dict_end, dict_len, st);
     }
-    case OP_DECOMPRESS_CHAIN: {   // decode_chain_kernel draws chains from one queue word of scratch
+    case OP_DECOMPRESS_CHAIN:   // decode_chain_kernel draws chains from the queue word
       if (!c.chain) return fail(LZ4HIP_E_ARG, kNullArg);
-      uint32_t* q = nullptr;
-      const hipError_t me = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
-      if (me != hipSuccess) return (int)me;
-      const int e = lz4hip::launch_decompress_chain(*c.chain, q, lz4hip::device_cus(), st);
-      (void)hipFreeAsync(q, st);
-      return e;
-    }
-    case OP_COMPRESS_CHAIN: {   // compress_fast_chain_cu_kernel draws chains from one queue word of scratch
+      return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_decompress_chain(*c.chain, q, lz4hip::device_cus(), st); });
+    case OP_COMPRESS_CHAIN:   // compress_fast_chain_cu_kernel draws chains from the queue word
       if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
-      uint32_t* q = nullptr;
-      const hipError_t me = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
-      if (me != hipSuccess) return (int)me;
-      const int e = lz4hip::launch_compress_fast_chain(*c.cchain, q, lz4hip::device_cus(), st);
-      (void)hipFreeAsync(q, st);
-      return e;
-    }
+      return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_chain(*c.cchain, q, lz4hip::device_cus(), st); });
     case OP_COMPRESS_HC:
     case OP_COMPRESS_HC_DICT:
     case OP_COMPRESS_HC_DEST: {
@@ -301,7 +305,7 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
     }
     case OP_COMPRESS_DICT:
     case OP_COMPRESS_ACCEL:   // the one-sequence kernels (compress_fast_accel_cu_kernel, compress_fast_dest_cu_kernel,
-    case OP_COMPRESS_DEST: {  // compress_fast_dict_cu_kernel) draw blocks from one queue word of scratch
+    case OP_COMPRESS_DEST: {  // compress_fast_dict_cu_kernel) draw blocks from the queue word
       const uint8_t* dict_end = nullptr;
       int32_t keep = 0;
       const void* image = nullptr;
@@ -310,14 +314,11 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
         const int rc = dict_compress_state(c.dict, st, &dict_end, &keep, &image);
         if (rc) return rc;
       }
-      uint32_t* q = nullptr;
-      const hipError_t me = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
-      if (me != hipSuccess) return (int)me;
-      const int e = c.op == OP_COMPRESS_DICT  ? lz4hip::launch_compress_fast_dict(a, dict_end, keep, image, q, lz4hip::device_cus(), st)
-                  : c.op == OP_COMPRESS_ACCEL ? lz4hip::launch_compress_fast_accel(a, (uint32_t)c.param, q, lz4hip::device_cus(), st)
-                                              : lz4hip::launch_compress_dest_size(a, c.consumed, q, lz4hip::device_cus(), st);
-      (void)hipFreeAsync(q, st);
-      return e;
+      return with_queue_word(st, [&](uint32_t* q) {
+        return c.op == OP_COMPRESS_DICT  ? lz4hip::launch_compress_fast_dict(a, dict_end, keep, image, q, lz4hip::device_cus(), st)
+             : c.op == OP_COMPRESS_ACCEL ? lz4hip::launch_compress_fast_accel(a, (uint32_t)c.param, q, lz4hip::device_cus(), st)
+                                         : lz4hip::launch_compress_dest_size(a, c.consumed, q, lz4hip::device_cus(), st);
+      });
     }
   }
   return fail(LZ4HIP_E_ARG, "unknown block operation");
@@ -329,8 +330,7 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
 // launch_block returns.
 template <class Body>
 int on_device(int device, bool empty, const char* arg_error, Body body) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (empty) return LZ4HIP_OK;
   if (arg_error) return fail(LZ4HIP_E_ARG, arg_error);
   int ord;
@@ -349,6 +349,7 @@ int dev_batch(const BlockCall& c, const lz4hip::BatchArgs& a, int device, void* 
   return on_device(device, a.n == 0, null_arg ? kNullArg : extra_error, [&] { return launch_block(c, a, (hipStream_t)stream); });
 }
 // the bytes block i of a partial decode may fill: min(target, capacity), or -1 (the kernels' -1) where one of them is negative
+size_t pos(int32_t v) { return v > 0 ? (size_t)v : 0; }   // (a negative length or capacity takes no bytes in the staging)
 int32_t partial_room(int32_t target, int32_t cap) { return (target < 0 || cap < 0) ? -1 : std::min(target, cap); }
 
 // ---- host-pointer path ---------------------------------------------------------------------------
@@ -486,35 +487,86 @@ void par_blocks(uint32_t i0, uint32_t i1, size_t bytes, F f) {  // f(i) for i in
   for (int t = 0; t < made; t++) th[t].join();
 }
 
+// "what: hipGetErrorString(e)" into *where (fail's formatter: g_err is this thread's) -> the status the C ABI reports for it
+int hip_status(std::string* where, const char* what, hipError_t e) {
+  *where = (fail(0, what, e), g_err);
+  return e == hipErrorOutOfMemory ? (int)LZ4HIP_E_NOMEM : (int)LZ4HIP_E_HIP;
+}
+
+// What every shard function below has around its work: the device `ord` current, a buffer pair of its pool for as long as the scope
+// lives, the shard's status (rc: once it is not LZ4HIP_OK the shard is over) with its message in *err.  When the shard ends in an
+// error -- or in an exception -- the streams of the pair's buffer sets are waited for before it goes back: nothing may stay in flight
+// on the cached buffers, the next caller's streams are not ordered against them.
+struct ShardScope {
+  std::string* err;
+  const int ord;
+  int rc = LZ4HIP_OK;
+  SlotPair* pair = nullptr;
+  ShardScope(int ord_, std::string* err_) : err(err_), ord(ord_) {
+    hipError_t e = hipSuccess;
+    if (ord < 0 || ord >= 64) { *err = "device ordinal out of range"; rc = LZ4HIP_E_ARG; }
+    else if (ok("hipSetDevice", hipSetDevice(ord)) && !(pair = g_ctx[ord].acquire(&e))) ok("stream/event creation", e);
+  }
+  ~ShardScope() {
+    if (!pair) return;
+    if (rc != LZ4HIP_OK || std::uncaught_exceptions())
+      for (ChunkSlot& s : pair->slot) {   // (the sets the shard did not touch are idle: their streams answer at once)
+        for (hipStream_t q : {s.st_in, s.st, s.st_out}) (void)hipStreamSynchronize(q);
+        s.i0 = s.i1 = 0;
+      }
+    g_ctx[ord].give_back(pair);
+  }
+  // every step of a shard: e is fine, or it becomes the shard's status
+  bool ok(const char* what, hipError_t e) { if (e != hipSuccess) rc = hip_status(err, what, e); return e == hipSuccess; }
+  bool launched(int le) {   // what launch_block returned: a status whose message is set on this thread (< 0), or a hipError_t
+    if (le < 0) { *err = lz4hip_last_error(); rc = le; }
+    return le >= 0 && ok("kernel launch", (hipError_t)le);
+  }
+  // the staging of a chunk of sb packed source bytes, db destination bytes (dst: it has a destination) and `meta` bytes of metadata
+  bool reserve(ChunkSlot& s, size_t sb, bool dst, size_t db, size_t meta) {
+    hipError_t e = hipSuccess;
+    for (GrowBuf* g : {&s.h_src, &s.d_src}) if (e == hipSuccess) e = g->reserve(sb + 64);
+    for (GrowBuf* g : {&s.h_dst, &s.d_dst}) if (e == hipSuccess && dst) e = g->reserve(db + 64);
+    for (GrowBuf* g : {&s.h_meta, &s.d_meta}) if (e == hipSuccess) e = g->reserve(meta);
+    return ok("staging allocation", e);
+  }
+  // the packed source and the metadata's inputs (and zeroed results) to the device, the metadata's results to the host: one copy each
+  bool upload(ChunkSlot& s, size_t sb, const staging::MetaLayout& l, hipStream_t q) {
+    return ok("H2D src", sb ? hipMemcpyAsync(s.d_src.p, s.h_src.p, sb, hipMemcpyHostToDevice, q) : hipSuccess) &&
+           ok("H2D meta", hipMemcpyAsync(s.d_meta.p, s.h_meta.p, l.upload, hipMemcpyHostToDevice, q));
+  }
+  bool fetch_results(ChunkSlot& s, const staging::MetaLayout& l, hipStream_t q) {
+    return ok("D2H out", hipMemcpyAsync((uint8_t*)s.h_meta.p + l.results, (const uint8_t*)s.d_meta.p + l.results, l.results_bytes(), hipMemcpyDeviceToHost, q));
+  }
+  bool wait(hipStream_t q) { return ok("hipStreamSynchronize", hipStreamSynchronize(q)); }
+  // only the bytes produced, from d_dst to h_dst on s.st, waited for: entry(t) as staging::for_each_run takes it
+  template <class Entry>
+  bool fetch_runs(ChunkSlot& s, uint32_t n, Entry entry) {
+    hipError_t e = hipSuccess;
+    (void)staging::for_each_run(n, entry, [&](size_t r0, size_t r1) {
+      return (int)(e = hipMemcpyAsync((uint8_t*)s.h_dst.p + r0, (const uint8_t*)s.d_dst.p + r0, r1 - r0, hipMemcpyDeviceToHost, s.st));
+    });
+    return ok("D2H dst", e) && wait(s.st);
+  }
+};
+
 // one device's share [b0, b1) of a host batch.  Three stages run side by side on LZ4HIP_HOST_SETS rotating buffer sets (default 6,
 // each a pinned pair of 64 MiB of source + the destination capacity of its chunk, allocated on first use and kept in the per-device
 // pool -- up to ~1 GiB of pinned host memory per cached pair at the defaults; LZ4HIP_HOST_SETS=2 / LZ4HIP_HOST_CHUNK_MB lower it):
-// the calling thread PACKS chunk
-// c + 1 into pinned memory and enqueues it, the GPU works on chunk c (its H2D, kernels and D2H on the set's own stream), and a
-// finisher thread per chunk waits for chunk c - 1 and hands its bytes to the caller's slots.  (Rounds 1-2 did pack, the
-// synchronous D2H of the packed bytes and the unpack one after the other on the calling thread: 44 ms per GiB, twice what the
-// link needs -- tools/host_path_probe.py.)
+// the calling thread PACKS chunk c + 1 into pinned memory and enqueues it, the GPU works on chunk c (its H2D, kernels and D2H on the
+// set's own stream), and a finisher thread per chunk waits for chunk c - 1 and hands its bytes to the caller's slots.  (Rounds 1-2 did
+// pack, the synchronous D2H of the packed bytes and the unpack one after the other on the calling thread: 44 ms per GiB, twice what
+// the link needs -- tools/host_path_probe.py.)
 // op_has_consumed: c.consumed (the second per-block output) travels behind out[] in the metadata and comes back with the sizes
 int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, uint32_t b0, uint32_t b1, std::string* err) {
-  auto bad_to = [](std::string* where, const char* what, hipError_t e) {
-    char buf[512];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    *where = buf;
-    return e == hipErrorOutOfMemory ? (int)LZ4HIP_E_NOMEM : (int)LZ4HIP_E_HIP;
-  };
-  auto bad = [&](const char* what, hipError_t e) { return bad_to(err, what, e); };
   if (b1 == b0) return LZ4HIP_OK;
-  if (ord < 0 || ord >= 64) { *err = "device ordinal out of range"; return LZ4HIP_E_ARG; }
+  ShardScope sh(ord, err);
+  int& rc = sh.rc;
+  if (rc) return rc;
   hipError_t e;
-  if ((e = hipSetDevice(ord)) != hipSuccess) return bad("hipSetDevice", e);
-  DevCtx& cx = g_ctx[ord];
-  SlotPair* pair = cx.acquire(&e);
-  if (!pair) return bad("stream/event creation", e);
-  struct Return { DevCtx& c; SlotPair* p; ~Return() { c.give_back(p); } } give_back_on_exit{cx, pair};
-  auto slen_of = [&](uint32_t i) -> size_t { return src_len[i] > 0 ? (size_t)src_len[i] : 0; };
   const bool no_output = op_writes_no_output(c.op);   // (dst / dst_off may be NULL: no destination bytes exist on either side)
-  auto dcap_of = [&](uint32_t i) -> size_t { return !no_output && dst_cap[i] > 0 ? (size_t)dst_cap[i] : 0; };
+  auto dcap_of = [&](uint32_t i) -> size_t { return no_output ? 0 : pos(dst_cap[i]); };
   const bool prof = getenv("LZ4HIP_HOST_PROF") != nullptr;   // developer diagnostics: where the time of the stages goes
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   std::atomic<double> t_wait{0}, t_d2h{0}, t_unpack{0};
@@ -529,22 +581,21 @@ int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* 
   auto finish = [&](ChunkSlot& s, Fin& f) -> int {
     if (s.i1 == s.i0) return LZ4HIP_OK;
     hipError_t fe;
-    if ((fe = hipSetDevice(ord)) != hipSuccess) return bad_to(&f.err, "hipSetDevice", fe);
+    if ((fe = hipSetDevice(ord)) != hipSuccess) return hip_status(&f.err, "hipSetDevice", fe);
     double c0 = now();
-    if ((fe = hipEventSynchronize(s.done)) != hipSuccess) return bad_to(&f.err, "hipEventSynchronize", fe);
+    if ((fe = hipEventSynchronize(s.done)) != hipSuccess) return hip_status(&f.err, "hipEventSynchronize", fe);
     add(t_wait, now() - c0); c0 = now();
     const uint32_t nb = s.i1 - s.i0;
-    const int32_t* hout = (const int32_t*)((const uint8_t*)s.h_meta.p + (size_t)nb * 24u);
-    memcpy(out + s.i0, hout, (size_t)nb * 4u);
-    if (op_has_consumed(c.op)) memcpy(c.consumed + s.i0, hout + nb, (size_t)nb * 4u);
-    const uint8_t* hd = (const uint8_t*)s.h_dst.p;
-    const uint32_t i0 = s.i0;
+    const staging::BlockMeta m(nb, op_has_consumed(c.op));
+    const int32_t* hout = m.out.in(s.h_meta.p);
+    memcpy(out + s.i0, hout, m.out.bytes());
+    if (op_has_consumed(c.op)) memcpy(c.consumed + s.i0, m.consumed.in(s.h_meta.p), m.consumed.bytes());
     if (s.packed) {   // the sizes are here: fetch exactly the useful bytes (already packed on the device), then hand them out
       uint64_t total = 0;
       for (uint32_t t = 0; t < nb; t++) { s.dof[t] = total; total += hout[t] > 0 ? (uint64_t)hout[t] : 0ull; }
-      if (s.q_out != s.st && (fe = hipStreamWaitEvent(s.q_out, s.ev_k, 0)) != hipSuccess) return bad_to(&f.err, "hipStreamWaitEvent", fe);   // (the pack kernel)
-      if (total && (fe = hipMemcpyAsync(s.h_dst.p, s.d_pack.p, (size_t)total, hipMemcpyDeviceToHost, s.q_out)) != hipSuccess) return bad_to(&f.err, "D2H packed", fe);
-      if ((fe = hipStreamSynchronize(s.q_out)) != hipSuccess) return bad_to(&f.err, "hipStreamSynchronize", fe);
+      if (s.q_out != s.st && (fe = hipStreamWaitEvent(s.q_out, s.ev_k, 0)) != hipSuccess) return hip_status(&f.err, "hipStreamWaitEvent", fe);   // (the pack kernel)
+      if (total && (fe = hipMemcpyAsync(s.h_dst.p, s.d_pack.p, (size_t)total, hipMemcpyDeviceToHost, s.q_out)) != hipSuccess) return hip_status(&f.err, "D2H packed", fe);
+      if ((fe = hipStreamSynchronize(s.q_out)) != hipSuccess) return hip_status(&f.err, "hipStreamSynchronize", fe);
       s.dst_bytes = (size_t)total;
     }
     add(t_d2h, now() - c0); c0 = now();
@@ -553,7 +604,7 @@ int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* 
       int64_t produced;   // (bytes past a result stay untouched in the caller's slot)
       if (fills) produced = out[i] > 0 ? dst_cap[i] : 0;
       else produced = out[i] > 0 ? out[i] : 0;
-      if (produced > 0) memcpy(dst + dst_off[i], hd + s.dof[i - i0], (size_t)produced);
+      if (produced > 0) memcpy(dst + dst_off[i], (const uint8_t*)s.h_dst.p + s.dof[i - s.i0], (size_t)produced);
     });
     add(t_unpack, now() - c0);
     return LZ4HIP_OK;
@@ -564,13 +615,13 @@ int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* 
     if (!f.live) return LZ4HIP_OK;
     f.th.join();
     f.live = false;
-    pair->slot[k].i0 = pair->slot[k].i1 = 0;
+    sh.pair->slot[k].i0 = sh.pair->slot[k].i1 = 0;
     if (f.rc != LZ4HIP_OK) *err = f.err;
     return f.rc;
   };
   auto start_finisher = [&](int k) {
     Fin& f = fin[k];
-    ChunkSlot& s = pair->slot[k];
+    ChunkSlot& s = sh.pair->slot[k];
     f.rc = LZ4HIP_OK;
     try {
       f.th = std::thread([&finish, &s, &f] {
@@ -588,74 +639,60 @@ int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* 
 
   const int SETS = env_int("LZ4HIP_HOST_SETS", 6, 2, SlotPair::SETS);
   const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20;
-  int rc = LZ4HIP_OK;
   uint32_t i = b0;
   int k = 0;
   double t_reap = 0, t_pack = 0, t_enq = 0, t_alloc = 0;
   const double t_begin = now();
   while (i < b1 && rc == LZ4HIP_OK) {
-    ChunkSlot& s = pair->slot[k];
+    ChunkSlot& s = sh.pair->slot[k];
     double t0 = now();
     if ((rc = reap(k)) != LZ4HIP_OK) break;   // the chunk that used this buffer set SETS rounds ago
     t_reap += now() - t0; t0 = now();
-    // the next chunk: blocks [i, j)
-    uint32_t j = i;
-    size_t sb = 0, db = 0;
-    while (j < b1 && j - i < CHUNK_BLOCKS) {
-      const size_t a = (slen_of(j) + 15u) & ~(size_t)15u, c = (dcap_of(j) + 15u) & ~(size_t)15u;
-      if (j > i && sb + a > chunk_src) break;
-      sb += a; db += c; j++;
-    }
-    const uint32_t nb = j - i;
+    // the next chunk: blocks [i, j); only its source is limited
+    const staging::Chunk ck = staging::cut_chunk(i, b1, CHUNK_BLOCKS, chunk_src, SIZE_MAX, [&](uint32_t t) { return staging::Cost{al16(pos(src_len[t])), al16(dcap_of(t))}; });
+    const uint32_t j = ck.end, nb = j - i;
+    const size_t sb = ck.src, db = ck.dst;   // packed source and destination bytes
     s.so.resize(nb); s.dof.resize(nb);
     { size_t so = 0, dofs = 0;
-      for (uint32_t t = 0; t < nb; t++) { s.so[t] = so; s.dof[t] = dofs; so += (slen_of(i + t) + 15u) & ~(size_t)15u; dofs += (dcap_of(i + t) + 15u) & ~(size_t)15u; } }
-    const size_t nout = op_has_consumed(c.op) ? 2u : 1u;   // out[] (and consumed[])
-    const size_t meta = (size_t)nb * (24u + 4u * nout);   // so[nb] u64 | dof[nb] u64 | src_len[nb] | dst_cap[nb] | out[nb] | (consumed[nb])
-    if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (!no_output && (e = s.h_dst.reserve(db + 64)) != hipSuccess) || (e = s.h_meta.reserve(meta)) != hipSuccess ||
-        (e = s.d_src.reserve(sb + 64)) != hipSuccess || (!no_output && (e = s.d_dst.reserve(db + 64)) != hipSuccess) || (e = s.d_meta.reserve(meta)) != hipSuccess ||
-        (op_uses_hc_ws(c.op) && (e = s.d_ws.reserve(lz4hip::hc_ws_bytes(sb, nb, c.param))) != hipSuccess) ||
+      for (uint32_t t = 0; t < nb; t++) { s.so[t] = so; s.dof[t] = dofs; so += al16(pos(src_len[i + t])); dofs += al16(dcap_of(i + t)); } }
+    const staging::BlockMeta m(nb, op_has_consumed(c.op));
+    if (!sh.reserve(s, sb, !no_output, db, m.l.total)) break;
+    if ((op_uses_hc_ws(c.op) && (e = s.d_ws.reserve(lz4hip::hc_ws_bytes(sb, nb, c.param))) != hipSuccess) ||
         (op_compresses(c.op) && ((e = s.d_pack.reserve(db + 64)) != hipSuccess || (e = s.d_poff.reserve((size_t)nb * 8u)) != hipSuccess))) {
-      rc = bad("staging allocation", e);
+      sh.ok("staging allocation", e);
       break;
     }
     t_alloc += now() - t0; t0 = now();
-    uint8_t* hs = (uint8_t*)s.h_src.p;
-    { const uint32_t base = i;
-      par_blocks(i, j, sb, [=, &s](uint32_t t) { if (src_len[t] > 0) memcpy(hs + s.so[t - base], src + src_off[t], (size_t)src_len[t]); }); }
-    uint8_t* hm = (uint8_t*)s.h_meta.p;
-    memcpy(hm, s.so.data(), (size_t)nb * 8u);
-    memcpy(hm + (size_t)nb * 8u, s.dof.data(), (size_t)nb * 8u);
-    memcpy(hm + (size_t)nb * 16u, src_len + i, (size_t)nb * 4u);
-    memcpy(hm + (size_t)nb * 20u, dst_cap + i, (size_t)nb * 4u);
+    uint8_t* const hs = (uint8_t*)s.h_src.p;
+    void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
+    par_blocks(i, j, sb, [=, &s](uint32_t t) { if (src_len[t] > 0) memcpy(hs + s.so[t - i], src + src_off[t], (size_t)src_len[t]); });
+    memcpy(m.src_off.in(hm), s.so.data(), m.src_off.bytes());
+    memcpy(m.dst_off.in(hm), s.dof.data(), m.dst_off.bytes());
+    memcpy(m.src_len.in(hm), src_len + i, m.src_len.bytes());
+    memcpy(m.dst_cap.in(hm), dst_cap + i, m.dst_cap.bytes());
     t_pack += now() - t0; t0 = now();
-    uint8_t* dm = (uint8_t*)s.d_meta.p;
     // a call that is ONE chunk (single blocks, small batches) has nothing to overlap: one stream, no finisher thread
     const bool single = (i == b0 && j == b1);
     s.q_in = single ? s.st : s.st_in;
     s.q_out = single ? s.st : s.st_out;
-    if (sb && (e = hipMemcpyAsync(s.d_src.p, hs, sb, hipMemcpyHostToDevice, s.q_in)) != hipSuccess) { rc = bad("H2D src", e); break; }
-    if ((e = hipMemcpyAsync(dm, hm, (size_t)nb * 24u, hipMemcpyHostToDevice, s.q_in)) != hipSuccess) { rc = bad("H2D meta", e); break; }
-    if (!single && ((e = hipEventRecord(s.ev_in, s.q_in)) != hipSuccess || (e = hipStreamWaitEvent(s.st, s.ev_in, 0)) != hipSuccess)) { rc = bad("H2D event", e); break; }
-    lz4hip::BatchArgs a{(const uint8_t*)s.d_src.p, (const uint64_t*)dm, (const int32_t*)(dm + (size_t)nb * 16u), no_output ? nullptr : (uint8_t*)s.d_dst.p,
-                        (const uint64_t*)(dm + (size_t)nb * 8u), (const int32_t*)(dm + (size_t)nb * 20u), (int32_t*)(dm + (size_t)nb * 24u), nb};
+    if (!sh.upload(s, sb, m.l, s.q_in)) break;
+    if (!single && ((e = hipEventRecord(s.ev_in, s.q_in)) != hipSuccess || (e = hipStreamWaitEvent(s.st, s.ev_in, 0)) != hipSuccess)) { sh.ok("H2D event", e); break; }
+    lz4hip::BatchArgs a{(const uint8_t*)s.d_src.p, m.src_off.in(dm), m.src_len.in(dm), no_output ? nullptr : (uint8_t*)s.d_dst.p, m.dst_off.in(dm), m.dst_cap.in(dm), m.out.in(dm), nb};
     BlockCall dc = c;   // the call on this chunk's device arrays
-    if (op_has_consumed(c.op)) dc.consumed = (int32_t*)(dm + (size_t)nb * 28u);
+    if (op_has_consumed(c.op)) dc.consumed = m.consumed.in(dm);
     if (op_uses_hc_ws(c.op)) { dc.hc_ws = s.d_ws.p; dc.hc_span = sb; }
-    int le = launch_block(dc, a, s.st);
-    if (le < 0) { *err = lz4hip_last_error(); rc = le; break; }   // (a decode knob combination without a kernel: launch_decode has said which, on this thread)
-    if (le) { rc = bad("kernel launch", (hipError_t)le); break; }
+    if (!sh.launched(launch_block(dc, a, s.st))) break;   // (< 0: e.g. a decode knob combination without a kernel, launch_decode has said which)
     s.packed = op_compresses(c.op);
     // the sizes travel first; compress ops: the finisher fetches exactly the packed bytes once it has them
-    if (!single && ((e = hipEventRecord(s.ev_k, s.st)) != hipSuccess || (e = hipStreamWaitEvent(s.q_out, s.ev_k, 0)) != hipSuccess)) { rc = bad("kernel event", e); break; }
-    if ((e = hipMemcpyAsync(hm + (size_t)nb * 24u, dm + (size_t)nb * 24u, (size_t)nb * 4u * nout, hipMemcpyDeviceToHost, s.q_out)) != hipSuccess) { rc = bad("D2H out", e); break; }
+    if (!single && ((e = hipEventRecord(s.ev_k, s.st)) != hipSuccess || (e = hipStreamWaitEvent(s.q_out, s.ev_k, 0)) != hipSuccess)) { sh.ok("kernel event", e); break; }
+    if (!sh.fetch_results(s, m.l, s.q_out)) break;
     if (s.packed) {
-      if ((e = hipEventRecord(s.done, s.q_out)) != hipSuccess) { rc = bad("hipEventRecord", e); break; }   // sizes on the host
-      if ((le = lz4hip::launch_pack(a, (uint64_t*)s.d_poff.p, (uint8_t*)s.d_pack.p, s.st)) != 0) { rc = bad("kernel launch", (hipError_t)le); break; }
-      if (!single && (e = hipEventRecord(s.ev_k, s.st)) != hipSuccess) { rc = bad("hipEventRecord", e); break; }   // packed bytes ready (the finisher waits for it)
+      if ((e = hipEventRecord(s.done, s.q_out)) != hipSuccess) { sh.ok("hipEventRecord", e); break; }   // sizes on the host
+      if (!sh.launched(lz4hip::launch_pack(a, (uint64_t*)s.d_poff.p, (uint8_t*)s.d_pack.p, s.st))) break;
+      if (!single && (e = hipEventRecord(s.ev_k, s.st)) != hipSuccess) { sh.ok("hipEventRecord", e); break; }   // packed bytes ready (the finisher waits for it)
     } else {
-      if (db && (e = hipMemcpyAsync(s.h_dst.p, s.d_dst.p, db, hipMemcpyDeviceToHost, s.q_out)) != hipSuccess) { rc = bad("D2H dst", e); break; }
-      if ((e = hipEventRecord(s.done, s.q_out)) != hipSuccess) { rc = bad("hipEventRecord", e); break; }
+      if (db && (e = hipMemcpyAsync(s.h_dst.p, s.d_dst.p, db, hipMemcpyDeviceToHost, s.q_out)) != hipSuccess) { sh.ok("D2H dst", e); break; }
+      if ((e = hipEventRecord(s.done, s.q_out)) != hipSuccess) { sh.ok("hipEventRecord", e); break; }
     }
     s.i0 = i; s.i1 = j; s.src_bytes = sb; s.dst_bytes = db;
     if (single) {
@@ -670,14 +707,11 @@ int host_shard(const BlockCall& c, int ord, const uint8_t* src, const uint64_t* 
     t_enq += now() - t0;
   }
   const double t_loop = now() - t_begin;
-  // drain (also after an error: nothing may stay in flight on the cached buffers, no finisher may outlive this call)
+  // drain (also after an error: no finisher may outlive this call; the scope then waits for the streams)
   for (int t = 0; t < SETS; t++) {
-    const int kk = (k + t) % SETS;
     std::string keep = *err;
-    const int r = reap(kk);
+    const int r = reap((k + t) % SETS);
     if (rc == LZ4HIP_OK) rc = r; else *err = keep;   // (the first error is the one reported)
-    ChunkSlot& s = pair->slot[kk];
-    if (rc != LZ4HIP_OK) { (void)hipStreamSynchronize(s.st_in); (void)hipStreamSynchronize(s.st); (void)hipStreamSynchronize(s.st_out); s.i0 = s.i1 = 0; }
   }
   if (prof)
     fprintf(stderr, "[lz4hip host_shard op %d, %u blocks] total %.1f ms: loop %.1f (reap %.1f | alloc %.1f | pack %.1f | enqueue %.1f), drain %.1f; finishers: wait %.1f + d2h %.1f + unpack %.1f\n",
@@ -716,8 +750,7 @@ int fan_out(uint32_t n, uint32_t per_device, Shard shard) {
 
 int host_batch(const BlockCall& c, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out, uint32_t n) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (n == 0) return LZ4HIP_OK;
   if (!src || !src_off || !src_len || (!op_writes_no_output(c.op) && (!dst || !dst_off)) || !dst_cap || !out || (op_has_consumed(c.op) && !c.consumed))
     return fail(LZ4HIP_E_ARG, kNullArg);
@@ -726,7 +759,6 @@ int host_batch(const BlockCall& c, const uint8_t* src, const uint64_t* src_off, 
   });
 }
 
-
 // ---- chains of linked blocks on the host-pointer path ----
 // One device's share [c0, c1) of a chain batch (h: the caller's HOST arrays).  Chains are staged a chunk at a time (64 MiB of streams
 // or 512 MiB of destination, one chain at least) through the first buffer set of a pooled pair: the streams and, per chain, the last
@@ -734,106 +766,60 @@ int host_batch(const BlockCall& c, const uint8_t* src, const uint64_t* src_off, 
 // each chain decoded (runs less than 4 KB apart travel as one copy).  On the device a chain's region is min(chain_dst_cap, the sum of
 // its blocks' capacities) bytes: a block's capacity is the smaller of its own and what is left, so nothing changes.
 int chain_host_shard(const lz4hip::ChainArgs& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
-  auto bad = [&](const char* what, hipError_t e) {
-    char buf[512];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    *err = buf;
-    return e == hipErrorOutOfMemory ? (int)LZ4HIP_E_NOMEM : (int)LZ4HIP_E_HIP;
-  };
   if (c1 == c0) return LZ4HIP_OK;
-  if (ord < 0 || ord >= 64) { *err = "device ordinal out of range"; return LZ4HIP_E_ARG; }
-  hipError_t e;
-  if ((e = hipSetDevice(ord)) != hipSuccess) return bad("hipSetDevice", e);
-  DevCtx& cx = g_ctx[ord];
-  SlotPair* pair = cx.acquire(&e);
-  if (!pair) return bad("stream/event creation", e);
-  struct Return { DevCtx& c; SlotPair* p; ~Return() { c.give_back(p); } } give_back_on_exit{cx, pair};
-  ChunkSlot& s = pair->slot[0];
+  ShardScope sh(ord, err);
+  if (sh.rc) return sh.rc;
+  ChunkSlot& s = sh.pair->slot[0];
   const hipStream_t st = s.st;
-  auto al16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  auto slen_of = [&](uint32_t i) -> size_t { return h.src_len[i] > 0 ? (size_t)h.src_len[i] : 0; };
   auto keep_of = [&](uint32_t c) -> size_t { const int32_t p = h.chain_prefix_len ? h.chain_prefix_len[c] : 0; return p > 65536 ? 65536u : (size_t)p; };
   auto room_of = [&](uint32_t c) -> size_t {   // the chain's region on the device
     uint64_t sum = 0;
-    for (uint32_t i = h.chain_first[c]; i < h.chain_first[c + 1]; i++) sum += h.dst_cap[i] > 0 ? (uint64_t)h.dst_cap[i] : 0u;
+    for (uint32_t i = h.chain_first[c]; i < h.chain_first[c + 1]; i++) sum += pos(h.dst_cap[i]);
     return (size_t)std::min<uint64_t>(sum, h.chain_dst_cap[c]);
   };
   const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
   std::vector<uint64_t> so, cdo, room;
-  uint32_t c = c0;
-  while (c < c1) {
+  for (uint32_t c = c0; c < c1;) {
     // the next chunk: chains [c, j), blocks [b0, b1)
-    uint32_t j = c;
-    size_t sb = 0, db = 0;
-    cdo.clear(); room.clear();
-    while (j < c1) {
+    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, [&](uint32_t j) {
       size_t a = 0;
-      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) a += al16(slen_of(i));
-      const size_t r = room_of(j), d = al16(keep_of(j) + r);
-      if (j > c && (sb + a > chunk_src || db + d > chunk_dst)) break;
-      cdo.push_back(db + keep_of(j)); room.push_back(r);
-      sb += a; db += d; j++;
-    }
-    const uint32_t b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
-    so.resize(nb);
-    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { so[t] = o; o += al16(slen_of(b0 + t)); } }
-    // metadata: so[nb] u64 | chain_dst_off[nc] u64 | chain_dst_cap[nc] u64 | chain_out[nc] u64 | src_len[nb] | dst_cap[nb] | out[nb] |
-    // chain_first[nc + 1] | prefix[nc] | stored[nb] u8
-    const size_t o_cdo = 8u * nb, o_ccap = o_cdo + 8u * nc, o_cout = o_ccap + 8u * nc, o_slen = o_cout + 8u * nc, o_dcap = o_slen + 4u * nb,
-                 o_out = o_dcap + 4u * nb, o_first = o_out + 4u * nb, o_prefix = o_first + 4u * (nc + 1u), o_stored = o_prefix + 4u * nc,
-                 meta = o_stored + nb;
-    if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (e = s.h_dst.reserve(db + 64)) != hipSuccess || (e = s.h_meta.reserve(meta)) != hipSuccess ||
-        (e = s.d_src.reserve(sb + 64)) != hipSuccess || (e = s.d_dst.reserve(db + 64)) != hipSuccess || (e = s.d_meta.reserve(meta)) != hipSuccess)
-      return bad("staging allocation", e);
-    uint8_t* hs = (uint8_t*)s.h_src.p;
-    uint8_t* hd = (uint8_t*)s.h_dst.p;
-    uint8_t* hm = (uint8_t*)s.h_meta.p;
-    uint8_t* dm = (uint8_t*)s.d_meta.p;
-    uint8_t* dd = (uint8_t*)s.d_dst.p;
-    par_blocks(b0, b1, sb, [=, &so](uint32_t i) { if (h.src_len[i] > 0) memcpy(hs + so[i - b0], h.src + h.src_off[i], (size_t)h.src_len[i]); });
-    memcpy(hm, so.data(), 8u * nb);
-    memcpy(hm + o_cdo, cdo.data(), 8u * nc);
-    memcpy(hm + o_ccap, room.data(), 8u * nc);
-    memset(hm + o_cout, 0, 8u * nc);
-    memcpy(hm + o_slen, h.src_len + b0, 4u * nb);
-    memcpy(hm + o_dcap, h.dst_cap + b0, 4u * nb);
-    for (uint32_t t = 0; t <= nc; t++) { const uint32_t f = h.chain_first[c + t] - b0; memcpy(hm + o_first + 4u * t, &f, 4); }
-    for (uint32_t t = 0; t < nc; t++) { const int32_t k = (int32_t)keep_of(c + t); memcpy(hm + o_prefix + 4u * t, &k, 4); }
-    if (h.stored) memcpy(hm + o_stored, h.stored + b0, nb); else memset(hm + o_stored, 0, nb);
-    if (sb && (e = hipMemcpyAsync(s.d_src.p, hs, sb, hipMemcpyHostToDevice, st)) != hipSuccess) return bad("H2D src", e);
-    if ((e = hipMemcpyAsync(dm, hm, meta, hipMemcpyHostToDevice, st)) != hipSuccess) return bad("H2D meta", e);
+      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) a += al16(pos(h.src_len[i]));
+      return staging::Cost{a, al16(keep_of(j) + room_of(j))};
+    });
+    const uint32_t j = ck.end, b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
+    so.resize(nb); cdo.resize(nc); room.resize(nc);
+    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { so[t] = o; o += al16(pos(h.src_len[b0 + t])); } }
+    { size_t o = 0; for (uint32_t t = 0; t < nc; t++) { room[t] = room_of(c + t); cdo[t] = o + keep_of(c + t); o += al16(keep_of(c + t) + room[t]); } }
+    const staging::ChainMeta m(nb, nc);
+    if (!sh.reserve(s, ck.src, true, ck.dst, m.l.total)) return sh.rc;
+    uint8_t *const hs = (uint8_t*)s.h_src.p, *const hd = (uint8_t*)s.h_dst.p, *const dd = (uint8_t*)s.d_dst.p;
+    void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
+    par_blocks(b0, b1, ck.src, [=, &so](uint32_t i) { if (h.src_len[i] > 0) memcpy(hs + so[i - b0], h.src + h.src_off[i], (size_t)h.src_len[i]); });
+    m.l.zero_results(hm);
+    memcpy(m.src_off.in(hm), so.data(), m.src_off.bytes());
+    memcpy(m.chain_dst_off.in(hm), cdo.data(), m.chain_dst_off.bytes());
+    memcpy(m.chain_dst_cap.in(hm), room.data(), m.chain_dst_cap.bytes());
+    memcpy(m.src_len.in(hm), h.src_len + b0, m.src_len.bytes());
+    memcpy(m.dst_cap.in(hm), h.dst_cap + b0, m.dst_cap.bytes());
+    for (uint32_t t = 0; t <= nc; t++) m.first.in(hm)[t] = h.chain_first[c + t] - b0;
+    for (uint32_t t = 0; t < nc; t++) m.prefix.in(hm)[t] = (int32_t)keep_of(c + t);
+    if (h.stored) memcpy(m.stored.in(hm), h.stored + b0, nb); else memset(m.stored.in(hm), 0, nb);
+    if (!sh.upload(s, ck.src, m.l, st)) return sh.rc;
     for (uint32_t t = 0; t < nc; t++) {   // the histories
       const size_t k = keep_of(c + t);
       if (!k) continue;
       memcpy(hd + cdo[t] - k, h.dst + h.chain_dst_off[c + t] - k, k);
-      if ((e = hipMemcpyAsync(dd + cdo[t] - k, hd + cdo[t] - k, k, hipMemcpyHostToDevice, st)) != hipSuccess) return bad("H2D history", e);
+      if (!sh.ok("H2D history", hipMemcpyAsync(dd + cdo[t] - k, hd + cdo[t] - k, k, hipMemcpyHostToDevice, st))) return sh.rc;
     }
-    const lz4hip::ChainArgs a{(const uint8_t*)s.d_src.p, (const uint64_t*)dm, (const int32_t*)(dm + o_slen), (const uint8_t*)(dm + o_stored),
-                              (const int32_t*)(dm + o_dcap), (const uint32_t*)(dm + o_first), dd, (const uint64_t*)(dm + o_cdo),
-                              (const uint64_t*)(dm + o_ccap), (const int32_t*)(dm + o_prefix), (int32_t*)(dm + o_out), (uint64_t*)(dm + o_cout), nb, nc};
-    BlockCall call{OP_DECOMPRESS_CHAIN};
-    call.chain = &a;
-    const int le = launch_block(call, lz4hip::BatchArgs{}, st);
-    if (le < 0) { *err = lz4hip_last_error(); return le; }
-    if (le) return bad("kernel launch", (hipError_t)le);
-    if ((e = hipMemcpyAsync(hm + o_cout, dm + o_cout, o_first - o_cout, hipMemcpyDeviceToHost, st)) != hipSuccess) return bad("D2H out", e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return bad("hipStreamSynchronize", e);
-    memcpy(h.out + b0, hm + o_out, 4u * nb);
-    memcpy(h.chain_out + c, hm + o_cout, 8u * nc);
-    // only the bytes decoded come back: runs of them less than 4 KB apart in one copy
-    size_t run0 = 0, run1 = 0;
-    auto flush = [&]() -> hipError_t { return run1 > run0 ? hipMemcpyAsync(hd + run0, dd + run0, run1 - run0, hipMemcpyDeviceToHost, st) : hipSuccess; };
-    for (uint32_t t = 0; t < nc; t++) {
-      const size_t n = (size_t)h.chain_out[c + t];
-      if (!n) continue;
-      if (run1 > run0 && cdo[t] <= run1 + 4096u) { run1 = cdo[t] + n; continue; }
-      if ((e = flush()) != hipSuccess) return bad("D2H dst", e);
-      run0 = cdo[t]; run1 = cdo[t] + n;
-    }
-    if ((e = flush()) != hipSuccess) return bad("D2H dst", e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return bad("hipStreamSynchronize", e);
-    { const uint32_t base = c;
-      par_blocks(c, j, db, [=, &cdo](uint32_t t) { const size_t n = (size_t)h.chain_out[t]; if (n) memcpy(h.dst + h.chain_dst_off[t], hd + cdo[t - base], n); }); }
+    const lz4hip::ChainArgs a{(const uint8_t*)s.d_src.p, m.src_off.in(dm), m.src_len.in(dm), m.stored.in(dm), m.dst_cap.in(dm), m.first.in(dm), dd,
+                              m.chain_dst_off.in(dm), m.chain_dst_cap.in(dm), m.prefix.in(dm), m.out.in(dm), m.chain_out.in(dm), nb, nc};
+    BlockCall call{OP_DECOMPRESS_CHAIN}; call.chain = &a;
+    if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
+    memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
+    memcpy(h.chain_out + c, m.chain_out.in(hm), m.chain_out.bytes());
+    // only the bytes decoded come back
+    if (!sh.fetch_runs(s, nc, [&](uint32_t t) { return staging::Run{(size_t)cdo[t], (size_t)h.chain_out[c + t]}; })) return sh.rc;
+    par_blocks(c, j, ck.dst, [=, &cdo](uint32_t t) { if (const size_t n = (size_t)h.chain_out[t]) memcpy(h.dst + h.chain_dst_off[t], hd + cdo[t - c], n); });
     c = j;
   }
   return LZ4HIP_OK;
@@ -842,18 +828,8 @@ int chain_host_shard(const lz4hip::ChainArgs& h, int ord, uint32_t c0, uint32_t 
 // the argument errors of a chain call that can be seen without a device; host: the arrays are the caller's host memory and are read
 const char* chain_arg_error(const lz4hip::ChainArgs& a, bool host) {
   if (a.n_chains == 0 && a.n_blocks == 0) return nullptr;
-  if (!a.src || !a.src_off || !a.src_len || !a.dst_cap || !a.chain_first || !a.dst || !a.chain_dst_off || !a.chain_dst_cap || !a.out || !a.chain_out)
-    return kNullArg;
-  if (!host) return nullptr;
-  if (a.chain_first[0] != 0u || a.chain_first[a.n_chains] != a.n_blocks) return "chain_first must start at 0 and end at n_blocks";
-  for (uint32_t c = 0; c < a.n_chains; c++) {
-    if (a.chain_first[c] > a.chain_first[c + 1]) return "chain_first must be ascending";
-    if (a.chain_prefix_len) {
-      if (a.chain_prefix_len[c] < 0) return "negative chain_prefix_len";
-      if ((uint64_t)a.chain_prefix_len[c] > a.chain_dst_off[c]) return "chain_prefix_len reaches in front of dst";
-    }
-  }
-  return nullptr;
+  if (!a.src || !a.src_off || !a.src_len || !a.dst_cap || !a.chain_first || !a.dst || !a.chain_dst_off || !a.chain_dst_cap || !a.out || !a.chain_out) return kNullArg;
+  return host ? staging::chain_shape_error(a.chain_first, a.n_chains, a.n_blocks, a.chain_prefix_len, a.chain_dst_off, true) : nullptr;
 }
 
 // ---- chains of linked blocks on the host-pointer path, compressing side ----
@@ -863,24 +839,11 @@ const char* chain_arg_error(const lz4hip::ChainArgs& a, bool host) {
 // each block produced (runs less than 4 KB apart travel as one copy).  Of a chain's source only what its blocks can consume is
 // read: up to the first block with a negative length or with which the chain would exceed 0x7E000000 bytes (its result is 0).
 int cchain_host_shard(const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
-  auto bad = [&](const char* what, hipError_t e) {
-    char buf[512];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    *err = buf;
-    return e == hipErrorOutOfMemory ? (int)LZ4HIP_E_NOMEM : (int)LZ4HIP_E_HIP;
-  };
   if (c1 == c0) return LZ4HIP_OK;
-  if (ord < 0 || ord >= 64) { *err = "device ordinal out of range"; return LZ4HIP_E_ARG; }
-  hipError_t e;
-  if ((e = hipSetDevice(ord)) != hipSuccess) return bad("hipSetDevice", e);
-  DevCtx& cx = g_ctx[ord];
-  SlotPair* pair = cx.acquire(&e);
-  if (!pair) return bad("stream/event creation", e);
-  struct Return { DevCtx& c; SlotPair* p; ~Return() { c.give_back(p); } } give_back_on_exit{cx, pair};
-  ChunkSlot& s = pair->slot[0];
+  ShardScope sh(ord, err);
+  if (sh.rc) return sh.rc;
+  ChunkSlot& s = sh.pair->slot[0];
   const hipStream_t st = s.st;
-  auto al16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-  auto cap_of = [&](uint32_t i) -> size_t { return h.dst_cap[i] > 0 ? (size_t)h.dst_cap[i] : 0; };
   auto keep_of = [&](uint32_t c) -> size_t { const int32_t p = h.chain_prefix_len ? h.chain_prefix_len[c] : 0; return p > 65536 ? 65536u : (size_t)p; };
   auto span_of = [&](uint32_t c) -> size_t {   // the source bytes the chain's blocks can consume
     const size_t k = keep_of(c);
@@ -892,80 +855,45 @@ int cchain_host_shard(const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_
     }
     return (size_t)(pos - pos0);
   };
+  auto produced = [&](uint32_t i) -> size_t { const int32_t r = h.out[i]; return r > 0 && (size_t)r <= pos(h.dst_cap[i]) ? (size_t)r : 0; };   // (h.out: once it is back)
   const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
   std::vector<uint64_t> cso, dso;
-  uint32_t c = c0;
-  while (c < c1) {
+  for (uint32_t c = c0; c < c1;) {
     // the next chunk: chains [c, j), blocks [b0, b1)
-    uint32_t j = c;
-    size_t sb = 0, db = 0;
-    cso.clear();
-    while (j < c1) {
-      const size_t a = al16(keep_of(j) + span_of(j));
+    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, [&](uint32_t j) {
       size_t d = 0;
-      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) d += al16(cap_of(i));
-      if (j > c && (sb + a > chunk_src || db + d > chunk_dst)) break;
-      cso.push_back(sb + keep_of(j));
-      sb += a; db += d; j++;
-    }
-    const uint32_t b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
-    dso.resize(nb);
-    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { dso[t] = o; o += al16(cap_of(b0 + t)); } }
-    // metadata: chain_src_off[nc] u64 | dst_off[nb] u64 | chain_consumed[nc] u64 | out[nb] | src_len[nb] | dst_cap[nb] |
-    // chain_first[nc + 1] | prefix[nc]
-    const size_t o_do = 8u * nc, o_cons = o_do + 8u * nb, o_out = o_cons + 8u * nc, o_slen = o_out + 4u * nb, o_dcap = o_slen + 4u * nb,
-                 o_first = o_dcap + 4u * nb, o_prefix = o_first + 4u * (nc + 1u), meta = o_prefix + 4u * nc;
-    if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (e = s.h_dst.reserve(db + 64)) != hipSuccess || (e = s.h_meta.reserve(meta)) != hipSuccess ||
-        (e = s.d_src.reserve(sb + 64)) != hipSuccess || (e = s.d_dst.reserve(db + 64)) != hipSuccess || (e = s.d_meta.reserve(meta)) != hipSuccess)
-      return bad("staging allocation", e);
-    uint8_t* hs = (uint8_t*)s.h_src.p;
-    uint8_t* hd = (uint8_t*)s.h_dst.p;
-    uint8_t* hm = (uint8_t*)s.h_meta.p;
-    uint8_t* dm = (uint8_t*)s.d_meta.p;
-    uint8_t* dd = (uint8_t*)s.d_dst.p;
-    { const uint32_t base = c;
-      par_blocks(c, j, sb, [=, &cso](uint32_t t) {
-        const size_t k = keep_of(t), n = k + span_of(t);
-        if (n) memcpy(hs + cso[t - base] - k, h.src + h.chain_src_off[t] - k, n);
-      }); }
-    memcpy(hm, cso.data(), 8u * nc);
-    memcpy(hm + o_do, dso.data(), 8u * nb);
-    memset(hm + o_cons, 0, 8u * nc);
-    memset(hm + o_out, 0, 4u * nb);
-    memcpy(hm + o_slen, h.src_len + b0, 4u * nb);
-    memcpy(hm + o_dcap, h.dst_cap + b0, 4u * nb);
-    for (uint32_t t = 0; t <= nc; t++) { const uint32_t f = h.chain_first[c + t] - b0; memcpy(hm + o_first + 4u * t, &f, 4); }
-    for (uint32_t t = 0; t < nc; t++) { const int32_t k = (int32_t)keep_of(c + t); memcpy(hm + o_prefix + 4u * t, &k, 4); }
-    if (sb && (e = hipMemcpyAsync(s.d_src.p, hs, sb, hipMemcpyHostToDevice, st)) != hipSuccess) return bad("H2D src", e);
-    if ((e = hipMemcpyAsync(dm, hm, meta, hipMemcpyHostToDevice, st)) != hipSuccess) return bad("H2D meta", e);
-    const lz4hip::CChainArgs a{(const uint8_t*)s.d_src.p, (const uint64_t*)dm, (const int32_t*)(dm + o_prefix), (const int32_t*)(dm + o_slen),
-                               (const uint32_t*)(dm + o_first), dd, (const uint64_t*)(dm + o_do), (const int32_t*)(dm + o_dcap),
-                               (int32_t*)(dm + o_out), (uint64_t*)(dm + o_cons), nb, nc};
-    BlockCall call{OP_COMPRESS_CHAIN};
-    call.cchain = &a;
-    const int le = launch_block(call, lz4hip::BatchArgs{}, st);
-    if (le < 0) { *err = lz4hip_last_error(); return le; }
-    if (le) return bad("kernel launch", (hipError_t)le);
-    if ((e = hipMemcpyAsync(hm + o_cons, dm + o_cons, o_slen - o_cons, hipMemcpyDeviceToHost, st)) != hipSuccess) return bad("D2H out", e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return bad("hipStreamSynchronize", e);
-    memcpy(h.out + b0, hm + o_out, 4u * nb);
-    memcpy(h.chain_consumed + c, hm + o_cons, 8u * nc);
-    // only the bytes produced come back: runs of them less than 4 KB apart in one copy
-    size_t run0 = 0, run1 = 0;
-    auto flush = [&]() -> hipError_t { return run1 > run0 ? hipMemcpyAsync(hd + run0, dd + run0, run1 - run0, hipMemcpyDeviceToHost, st) : hipSuccess; };
-    for (uint32_t t = 0; t < nb; t++) {
-      const int32_t r = h.out[b0 + t];
-      if (r <= 0 || (size_t)r > cap_of(b0 + t)) continue;
-      if (run1 > run0 && dso[t] <= run1 + 4096u) { run1 = dso[t] + (size_t)r; continue; }
-      if ((e = flush()) != hipSuccess) return bad("D2H dst", e);
-      run0 = dso[t]; run1 = dso[t] + (size_t)r;
-    }
-    if ((e = flush()) != hipSuccess) return bad("D2H dst", e);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return bad("hipStreamSynchronize", e);
-    par_blocks(b0, b1, db, [=, &dso](uint32_t i) {
-      const int32_t r = h.out[i];
-      if (r > 0 && (size_t)r <= cap_of(i)) memcpy(h.dst + h.dst_off[i], hd + dso[i - b0], (size_t)r);
+      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) d += al16(pos(h.dst_cap[i]));
+      return staging::Cost{al16(keep_of(j) + span_of(j)), d};
     });
+    const uint32_t j = ck.end, b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
+    cso.resize(nc); dso.resize(nb);
+    { size_t o = 0; for (uint32_t t = 0; t < nc; t++) { cso[t] = o + keep_of(c + t); o += al16(keep_of(c + t) + span_of(c + t)); } }
+    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { dso[t] = o; o += al16(pos(h.dst_cap[b0 + t])); } }
+    const staging::CChainMeta m(nb, nc);
+    if (!sh.reserve(s, ck.src, true, ck.dst, m.l.total)) return sh.rc;
+    uint8_t *const hs = (uint8_t*)s.h_src.p, *const hd = (uint8_t*)s.h_dst.p;
+    void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
+    par_blocks(c, j, ck.src, [=, &cso](uint32_t t) {
+      const size_t k = keep_of(t), n = k + span_of(t);
+      if (n) memcpy(hs + cso[t - c] - k, h.src + h.chain_src_off[t] - k, n);
+    });
+    m.l.zero_results(hm);
+    memcpy(m.chain_src_off.in(hm), cso.data(), m.chain_src_off.bytes());
+    memcpy(m.dst_off.in(hm), dso.data(), m.dst_off.bytes());
+    memcpy(m.src_len.in(hm), h.src_len + b0, m.src_len.bytes());
+    memcpy(m.dst_cap.in(hm), h.dst_cap + b0, m.dst_cap.bytes());
+    for (uint32_t t = 0; t <= nc; t++) m.first.in(hm)[t] = h.chain_first[c + t] - b0;
+    for (uint32_t t = 0; t < nc; t++) m.prefix.in(hm)[t] = (int32_t)keep_of(c + t);
+    if (!sh.upload(s, ck.src, m.l, st)) return sh.rc;
+    const lz4hip::CChainArgs a{(const uint8_t*)s.d_src.p, m.chain_src_off.in(dm), m.prefix.in(dm), m.src_len.in(dm), m.first.in(dm), (uint8_t*)s.d_dst.p,
+                               m.dst_off.in(dm), m.dst_cap.in(dm), m.out.in(dm), m.consumed.in(dm), nb, nc};
+    BlockCall call{OP_COMPRESS_CHAIN}; call.cchain = &a;
+    if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
+    memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
+    memcpy(h.chain_consumed + c, m.consumed.in(hm), m.consumed.bytes());
+    // only the bytes produced come back
+    if (!sh.fetch_runs(s, nb, [&](uint32_t t) { return staging::Run{(size_t)dso[t], produced(b0 + t)}; })) return sh.rc;
+    par_blocks(b0, b1, ck.dst, [=, &dso](uint32_t i) { if (const size_t r = produced(i)) memcpy(h.dst + h.dst_off[i], hd + dso[i - b0], r); });
     c = j;
   }
   return LZ4HIP_OK;
@@ -975,94 +903,54 @@ int cchain_host_shard(const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_
 const char* cchain_arg_error(const lz4hip::CChainArgs& a, bool host) {
   if (a.n_chains == 0 && a.n_blocks == 0) return nullptr;
   if (!a.src || !a.chain_src_off || !a.src_len || !a.chain_first || !a.dst || !a.dst_off || !a.dst_cap || !a.out || !a.chain_consumed) return kNullArg;
-  if (!host) return nullptr;
-  if (a.chain_first[0] != 0u || a.chain_first[a.n_chains] != a.n_blocks) return "chain_first must start at 0 and end at n_blocks";
-  for (uint32_t c = 0; c < a.n_chains; c++) {
-    if (a.chain_first[c] > a.chain_first[c + 1]) return "chain_first must be ascending";
-    if (a.chain_prefix_len) {
-      if (a.chain_prefix_len[c] < 0) return "negative chain_prefix_len";
-      if ((uint64_t)a.chain_prefix_len[c] > a.chain_src_off[c]) return "chain_prefix_len reaches in front of src";
-    }
-  }
-  return nullptr;
+  return host ? staging::chain_shape_error(a.chain_first, a.n_chains, a.n_blocks, a.chain_prefix_len, a.chain_src_off, false) : nullptr;
 }
 
 // hashes of one device's share [b0, b1) of a host batch: the same pinned, double-buffered staging as host_shard (chunks of
 // <= CHUNK_SRC bytes packed by several host threads while the previous chunk is on the GPU), from the same pool of buffer pairs
 template <class T>
 int xxh_shard(bool is64, int ord, const uint8_t* buf, const uint64_t* off, const int32_t* len, uint64_t seed, T* out, uint32_t b0, uint32_t b1, std::string* err) {
-  auto bad = [&](const char* what, hipError_t e) {
-    char m[512];
-    snprintf(m, sizeof m, "%s: %s", what, hipGetErrorString(e));
-    *err = m;
-    return e == hipErrorOutOfMemory ? (int)LZ4HIP_E_NOMEM : (int)LZ4HIP_E_HIP;
-  };
   if (b1 == b0) return LZ4HIP_OK;
-  hipError_t e;
-  if ((e = hipSetDevice(ord)) != hipSuccess) return bad("hipSetDevice", e);
-  DevCtx& cx = g_ctx[ord];
-  SlotPair* pair = cx.acquire(&e);
-  if (!pair) return bad("stream/event creation", e);
-  struct Return { DevCtx& c; SlotPair* p; ~Return() { c.give_back(p); } } give_back_on_exit{cx, pair};
-  auto len_of = [&](uint32_t i) -> size_t { return len[i] > 0 ? (size_t)len[i] : 0; };
-  auto finish = [&](ChunkSlot& s) -> int {
-    if (s.i1 == s.i0) return LZ4HIP_OK;
-    if ((e = hipEventSynchronize(s.done)) != hipSuccess) return bad("hipEventSynchronize", e);
-    const uint32_t nb = s.i1 - s.i0;
-    memcpy(out + s.i0, (const uint8_t*)s.h_meta.p + (((size_t)nb * 12u + 7u) & ~(size_t)7u), (size_t)nb * sizeof(T));
+  ShardScope sh(ord, err);
+  int& rc = sh.rc;
+  if (rc) return rc;
+  auto finish = [&](ChunkSlot& s) {   // the hashes of the chunk in `s`, if there is one, to the caller (waits for it)
+    const staging::HashMeta<T> m(s.i1 - s.i0);
+    if (s.i1 > s.i0 && sh.ok("hipEventSynchronize", hipEventSynchronize(s.done))) memcpy(out + s.i0, m.hash.in(s.h_meta.p), m.hash.bytes());
     s.i0 = s.i1 = 0;
-    return LZ4HIP_OK;
+    return rc == LZ4HIP_OK;
   };
-  int rc = LZ4HIP_OK;
   uint32_t i = b0;
   int k = 0;
   while (i < b1 && rc == LZ4HIP_OK) {
-    ChunkSlot& s = pair->slot[k];
-    if ((rc = finish(s)) != LZ4HIP_OK) break;
-    uint32_t j = i;
-    size_t sb = 0;
-    while (j < b1 && j - i < CHUNK_BLOCKS) {
-      const size_t a = (len_of(j) + 15u) & ~(size_t)15u;
-      if (j > i && sb + a > CHUNK_SRC) break;
-      sb += a; j++;
-    }
-    const uint32_t nb = j - i;
+    ChunkSlot& s = sh.pair->slot[k];
+    if (!finish(s)) break;
+    const staging::Chunk ck = staging::cut_chunk(i, b1, CHUNK_BLOCKS, CHUNK_SRC, SIZE_MAX, [&](uint32_t t) { return staging::Cost{al16(pos(len[t])), 0}; });
+    const uint32_t j = ck.end, nb = j - i;
     s.so.resize(nb);
-    { size_t so = 0; for (uint32_t t = 0; t < nb; t++) { s.so[t] = so; so += (len_of(i + t) + 15u) & ~(size_t)15u; } }
-    const size_t hoff = ((size_t)nb * 12u + 7u) & ~(size_t)7u;   // off[nb] u64 | len[nb] i32 | (pad to 8) | hash[nb]
-    const size_t meta = hoff + (size_t)nb * sizeof(T);
-    if ((e = s.h_src.reserve(sb + 64)) != hipSuccess || (e = s.h_meta.reserve(meta)) != hipSuccess || (e = s.d_src.reserve(sb + 64)) != hipSuccess ||
-        (e = s.d_meta.reserve(meta)) != hipSuccess) { rc = bad("staging allocation", e); break; }
-    uint8_t* hs = (uint8_t*)s.h_src.p;
-    { const uint32_t base = i;
-      par_blocks(i, j, sb, [=, &s](uint32_t t) { if (len[t] > 0) memcpy(hs + s.so[t - base], buf + off[t], (size_t)len[t]); }); }
-    uint8_t* hm = (uint8_t*)s.h_meta.p;
-    memcpy(hm, s.so.data(), (size_t)nb * 8u);
-    memcpy(hm + (size_t)nb * 8u, len + i, (size_t)nb * 4u);
-    uint8_t* dm = (uint8_t*)s.d_meta.p;
-    if (sb && (e = hipMemcpyAsync(s.d_src.p, hs, sb, hipMemcpyHostToDevice, s.st)) != hipSuccess) { rc = bad("H2D src", e); break; }
-    if ((e = hipMemcpyAsync(dm, hm, (size_t)nb * 12u, hipMemcpyHostToDevice, s.st)) != hipSuccess) { rc = bad("H2D meta", e); break; }
-    const int le = is64 ? lz4hip::launch_xxh64((const uint8_t*)s.d_src.p, (const uint64_t*)dm, (const int32_t*)(dm + (size_t)nb * 8u), seed, (uint64_t*)(dm + hoff), nb, s.st)
-                        : lz4hip::launch_xxh32((const uint8_t*)s.d_src.p, (const uint64_t*)dm, (const int32_t*)(dm + (size_t)nb * 8u), (uint32_t)seed, (uint32_t*)(dm + hoff), nb, s.st);
-    if (le) { rc = bad("kernel launch", (hipError_t)le); break; }
-    if ((e = hipMemcpyAsync(hm + hoff, dm + hoff, (size_t)nb * sizeof(T), hipMemcpyDeviceToHost, s.st)) != hipSuccess) { rc = bad("D2H hashes", e); break; }
-    if ((e = hipEventRecord(s.done, s.st)) != hipSuccess) { rc = bad("hipEventRecord", e); break; }
+    { size_t so = 0; for (uint32_t t = 0; t < nb; t++) { s.so[t] = so; so += al16(pos(len[i + t])); } }
+    const staging::HashMeta<T> m(nb);
+    if (!sh.reserve(s, ck.src, false, 0, m.l.total)) break;
+    uint8_t* const hs = (uint8_t*)s.h_src.p;
+    par_blocks(i, j, ck.src, [=, &s](uint32_t t) { if (len[t] > 0) memcpy(hs + s.so[t - i], buf + off[t], (size_t)len[t]); });
+    memcpy(m.off.in(s.h_meta.p), s.so.data(), m.off.bytes());
+    memcpy(m.len.in(s.h_meta.p), len + i, m.len.bytes());
+    void* dm = s.d_meta.p;
+    if (!sh.upload(s, ck.src, m.l, s.st)) break;
+    const int le = is64 ? lz4hip::launch_xxh64((const uint8_t*)s.d_src.p, m.off.in(dm), m.len.in(dm), seed, (uint64_t*)m.hash.in(dm), nb, s.st)
+                        : lz4hip::launch_xxh32((const uint8_t*)s.d_src.p, m.off.in(dm), m.len.in(dm), (uint32_t)seed, (uint32_t*)m.hash.in(dm), nb, s.st);
+    if (!sh.launched(le) || !sh.fetch_results(s, m.l, s.st) || !sh.ok("hipEventRecord", hipEventRecord(s.done, s.st))) break;
     s.i0 = i; s.i1 = j;
     i = j;
     k ^= 1;
   }
-  for (int t = 0; t < 2; t++) {
-    ChunkSlot& s = pair->slot[(k + t) & 1];
-    if (rc == LZ4HIP_OK) rc = finish(s);
-    else { (void)hipStreamSynchronize(s.st); s.i0 = s.i1 = 0; }
-  }
+  for (int t = 0; t < 2 && rc == LZ4HIP_OK; t++) finish(sh.pair->slot[(k + t) & 1]);
   return rc;
 }
 
 template <class T>
 int host_xxh(bool is64, const uint8_t* buf, const uint64_t* off, const int32_t* len, uint64_t seed, T* out, uint32_t n) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (n == 0) return LZ4HIP_OK;
   if (!buf || !off || !len || !out) return fail(LZ4HIP_E_ARG, kNullArg);
   return fan_out(n, 1024u, [&](int ord, uint32_t b0, uint32_t b1, std::string* err) {
@@ -1337,8 +1225,8 @@ size_t lz4hip_container_workspace_bytes(uint64_t n_bytes, uint32_t block_size, i
 }
 int lz4hip_container_blocks_dev(int kind, int flags, int level, const uint8_t* src, uint64_t n_bytes, uint32_t block_size, uint8_t* dst, uint64_t dst_cap,
                                 uint64_t* total_dev, void* ws, size_t ws_bytes, int device, void* stream) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");   // (the answer without a device, whatever the arguments)
+  int rc = need_device();
+  if (rc) return rc;   // (the answer without a device, whatever the arguments)
   int lv;
   if ((rc = container_args(kind, n_bytes, block_size, level, &lv)) != 0) return rc;
   return on_device(device, false, (n_bytes && !src) || !dst || !total_dev || !ws ? kNullArg : nullptr, [&] {
@@ -1350,8 +1238,8 @@ int lz4hip_container_blocks_dev(int kind, int flags, int level, const uint8_t* s
 }
 int lz4hip_container_blocks(int kind, int flags, int level, const uint8_t* src, uint64_t n_bytes, uint32_t block_size, uint8_t* dst, uint64_t dst_cap,
                             uint64_t* out_bytes) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  int rc = need_device();
+  if (rc) return rc;
   int lv;
   if ((rc = container_args(kind, n_bytes, block_size, level, &lv)) != 0) return rc;
   if ((n_bytes && !src) || !dst || !out_bytes) return fail(LZ4HIP_E_ARG, kNullArg);
@@ -1464,8 +1352,7 @@ int lz4hip_container_decode_bound(int kind, int flags, const uint8_t* body, uint
 // host pointers: H2D of the container bytes, the device path above, D2H of the delivered blocks back to back into dst
 int lz4hip_container_decode(int kind, int flags, const uint8_t* body, uint64_t body_bytes, uint32_t max_block, uint32_t n_max, uint8_t* dst,
                             uint64_t dst_cap, int32_t* sizes, uint64_t* info) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (kind != 0 && kind != 1) return fail(LZ4HIP_E_ARG, "container kind must be 0 (LZ4 Frame blocks) or 1 (LZ4Block blocks)");
   if ((body_bytes && !body) || !sizes || !info || (dst_cap && !dst)) return fail(LZ4HIP_E_ARG, kNullArg);
   if (n_max == 0 || n_max > 0x7FFFFFFFu || max_block == 0 || max_block > 0x7FFFFFFFu) return fail(LZ4HIP_E_ARG, "n_max and max_block must be 1 .. 2^31 - 1");
@@ -1555,8 +1442,7 @@ struct lz4hip_xxh_stream {
 namespace {
 constexpr size_t XXH_STAGE_MAX = 64u << 20;
 int xxh_stream_create(bool is64, uint64_t seed, lz4hip_xxh_stream** out) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (!out) return fail(LZ4HIP_E_ARG, kNullArg);
   int ord;
   if (ordinal(0, &ord)) return fail(LZ4HIP_E_NO_DEVICE, "no device");
@@ -1729,8 +1615,7 @@ int lz4hip_compress_dest_size_batch(const uint8_t* src, const uint64_t* src_off,
 int lz4hip_decompress_safe_partial_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                          const uint64_t* dst_off, const int32_t* target_len, const int32_t* dst_cap, int32_t* out_len,
                                          uint32_t n) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (n == 0) return LZ4HIP_OK;
   if (!target_len || !dst_cap) return fail(LZ4HIP_E_ARG, kNullArg);
   std::vector<int32_t> room;
@@ -1774,8 +1659,7 @@ void lz4hip_dict_free(lz4hip_dict* dict) {
 }
 int lz4hip_decompress_safe_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                       const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, const lz4hip_dict* dict) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (n == 0) return LZ4HIP_OK;
   if (!dict) return fail(LZ4HIP_E_ARG, kNullArg);
   BlockCall c{OP_DECODE_DICT};
@@ -1789,8 +1673,7 @@ int lz4hip_decompress_safe_chain_batch(const uint8_t* src, const uint64_t* src_o
   const lz4hip::ChainArgs h{src, src_off, src_len, stored, dst_cap, chain_first, dst, chain_dst_off, chain_dst_cap, chain_prefix_len, out_len, chain_out_len,
                             n_blocks, n_chains};
   if (const char* why = chain_arg_error(h, true)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (n_chains == 0) return LZ4HIP_OK;
   // whole chains per device: a chain never leaves its lane group, let alone its device
   return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return chain_host_shard(h, ord, c0, c1, err); });
@@ -1800,16 +1683,14 @@ int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_s
                                      uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains) {
   const lz4hip::CChainArgs h{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains};
   if (const char* why = cchain_arg_error(h, true)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (n_chains == 0) return LZ4HIP_OK;
   // whole chains per device: a chain never leaves its wavefront, let alone its device
   return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard(h, ord, c0, c1, err); });
 }
 int lz4hip_compress_fast_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                     const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, const lz4hip_dict* dict) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (n == 0) return LZ4HIP_OK;
   if (!dict) return fail(LZ4HIP_E_ARG, kNullArg);
   BlockCall c{OP_COMPRESS_DICT};
@@ -1818,8 +1699,7 @@ int lz4hip_compress_fast_dict_batch(const uint8_t* src, const uint64_t* src_off,
 }
 int lz4hip_compress_hc_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                   const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, int level, const lz4hip_dict* dict) {
-  int rc = ensure_init();
-  if (rc) return fail(rc, "no HIP device: liblz4hip has no CPU fallback");
+  if (const int rc = need_device()) return rc;
   if (n == 0) return LZ4HIP_OK;
   if (!dict) return fail(LZ4HIP_E_ARG, kNullArg);
   int lv;
@@ -2036,24 +1916,21 @@ int lz4hip_decompress_safe(const uint8_t* src, int src_len, uint8_t* dst, int ds
 int lz4hip_decompress_fast(const uint8_t* src, int src_cap, uint8_t* dst, int dst_len) { return single({OP_DECODE_FAST}, src, src_cap, dst, dst_len); }
 int lz4hip_decompressed_size(const uint8_t* src, int src_len, int dst_cap) { return single({OP_DECODED_SIZE}, src, src_len, nullptr, dst_cap); }
 int lz4hip_decompress_safe_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, const lz4hip_dict* dict) {
-  int rc = ensure_init();
-  if (rc) return LZ4HIP_LIB_ERROR(fail(rc, "no HIP device: liblz4hip has no CPU fallback"));
+  if (const int rc = need_device()) return LZ4HIP_LIB_ERROR(rc);
   if (!dict) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, kNullArg));
   BlockCall c{OP_DECODE_DICT};
   c.dict = dict;
   return single(c, src, src_len, dst, dst_cap);
 }
 int lz4hip_compress_fast_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, const lz4hip_dict* dict) {
-  int rc = ensure_init();
-  if (rc) return LZ4HIP_LIB_ERROR(fail(rc, "no HIP device: liblz4hip has no CPU fallback"));
+  if (const int rc = need_device()) return LZ4HIP_LIB_ERROR(rc);
   if (!dict) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, kNullArg));
   BlockCall c{OP_COMPRESS_DICT};
   c.dict = dict;
   return single(c, src, src_len, dst, dst_cap);
 }
 int lz4hip_compress_hc_dict(const uint8_t* src, int src_len, uint8_t* dst, int dst_cap, int level, const lz4hip_dict* dict) {
-  int rc = ensure_init();
-  if (rc) return LZ4HIP_LIB_ERROR(fail(rc, "no HIP device: liblz4hip has no CPU fallback"));
+  if (const int rc = need_device()) return LZ4HIP_LIB_ERROR(rc);
   if (!dict) return LZ4HIP_LIB_ERROR(fail(LZ4HIP_E_ARG, kNullArg));
   int lv;
   if (hc_level(level, &lv)) return LZ4HIP_LIB_ERROR(LZ4HIP_E_UNSUPPORTED);

@@ -1,5 +1,5 @@
 """What the tests' helper programs share: building and loading the lane simulators of tests/hostsim (build_sim), the C++ mirror
-programs of tests/cpp (build_mirror), the fake-JNI programs of tests/jni_stub (build_fake_jni) and the oracle's CPU harness; the
+programs of tests/cpp (build_mirror), its sanitized host-only programs (build_sanitized), the fake-JNI programs of tests/jni_stub (build_fake_jni) and the oracle's CPU harness; the
 status constants of the C ABI; running a child script (run_child); and what the *_multidev_child.py scripts do alike (init_repeated,
 slots, check_slots).  A plain module, imported by the test files and the child scripts."""
 import ctypes as C
@@ -80,6 +80,15 @@ def build_mirror(name, out_dir, werror=False, src=None):
     exe = os.path.join(str(out_dir), name)
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall"] + (["-Werror"] if werror else []) +
                           ["-I" + ROOT, str(src or os.path.join(ROOT, "tests", "cpp", name + ".cpp"))] + _link_lz4hip() + ["-o", exe])
+    return exe
+
+
+def build_sanitized(name, out_dir):
+    """tests/cpp/<name>.cpp, a stand-alone program of host code alone (no library, no device), with the address and undefined-behaviour
+    sanitizers, every finding fatal -> the executable <out_dir>/<name>; returns its path"""
+    exe = os.path.join(str(out_dir), name)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall",
+                           os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-o", exe])
     return exe
 
 

@@ -251,6 +251,36 @@ def test_cchain_host_call_and_python_layer(amd, cases):
     assert amd.LZ4HIPBatch.compressFastChain(b"", [], [], [0], bytearray(1), [], []) == ([], [])
 
 
+def test_cchain_host_call_in_small_chunks(amd, cases, rc, monkeypatch):
+    """the host call with 1 MiB chunks (LZ4HIP_HOST_CHUNK_MB=1, read per call): the host set, cycled until its 16-byte-rounded sources
+    (each with the kept part of its prefix) pass 2 MiB, is staged in three chunks or more through one buffer set -- the 70000-byte
+    prefixes, of which 64 KB are kept, cross chunk boundaries -- and a chain of 17 x 65536 bytes in the middle is larger than a chunk
+    by itself (a chunk takes one chain at least).  The assertions of test_cchain_host_call_and_python_layer"""
+    monkeypatch.setenv("LZ4HIP_HOST_CHUNK_MB", "1")
+    chains, want = host_set(cases)
+    assert any(len(c.history) == 70000 for c in chains)
+    rounded = lambda ch: (min(len(ch.history), 65536) + len(ch.data) + 15) & ~15
+    big = chain_of("book1 17 x 65536", (book1() * 2)[:17 * 65536], [65536] * 17)
+    assert rounded(big) > 1 << 20
+    sel, total = [], 0
+    while total <= 2 << 20 or len(sel) < len(chains):
+        sel.append(len(sel) % len(chains))
+        total += rounded(chains[sel[-1]])
+    assert total > 2 << 20
+    use, w = [chains[i] for i in sel], [want[i] for i in sel]
+    at = len(use) // 3
+    use.insert(at, big)
+    w.insert(at, rc.compress(big))
+    assert w[at][1] == 17 * 65536
+    pk = CPacked(use)
+    dst, out, cons = host_call(amd, pk)
+    bad = pk.check(dst, out, cons, w)
+    assert not bad, (len(bad), bad[:5])
+    for i in range(pk.n_blocks):   # behind what was produced -- and in the slot of a block that failed -- the caller's bytes
+        o, cap, r = pk.dst_off[i], max(pk.dst_cap[i], 0), max(out[i], 0)
+        assert dst[o + r:o + cap] == bytes([pk.fill]) * (cap - r), i
+
+
 def test_cchain_host_call_negative_values(amd, cases):
     """negative src_len / dst_cap reach the host form of the C ABI as they are (the Python layer refuses them): result 0, chain stopped"""
     import ctypes as C

@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from chain_common import CHAIN_STOPPED, Packed, RefChain, book1, case_set, chain_file, hand_chains, rng_for
+from chain_common import CHAIN_STOPPED, Chain, Packed, RefChain, book1, case_set, chain_file, hand_chains, rng_for
 from support import build_fake_jni, build_mirror, run_child
 import streams_common as sc
 
@@ -115,6 +115,37 @@ def test_chain_host_call_and_python_layer(amd, cases):
                                                     np.array(pk.chain_dst_off, dtype=np.uint64), np.array(pk.chain_dst_cap, dtype=np.uint64))
     assert out.dtype == np.int32 and cout.dtype == np.uint64
     assert not pk.check(dst, out.tolist(), cout.tolist(), [want[i] for i in sel])
+
+
+def test_chain_host_call_in_small_chunks(amd, cases, rc, monkeypatch):
+    """the host call with 1 MiB chunks (LZ4HIP_HOST_CHUNK_MB=1, read per call): the set, cycled until its 16-byte-rounded streams pass
+    2 MiB, is staged in three chunks or more through one buffer set, and a chain of seventeen stored 64 KiB blocks in the middle is
+    larger than a chunk by itself (a chunk takes one chain at least).  The assertions of test_chain_host_call_and_python_layer"""
+    monkeypatch.setenv("LZ4HIP_HOST_CHUNK_MB", "1")
+    chains, want = cases
+    rounded = lambda ch: sum((len(s) + 15) & ~15 for s, _, _ in ch.blocks)
+    data = (book1() * 2)[:17 * 65536]
+    big = Chain("17 stored x 65536", [(data[o:o + 65536], True, 65536) for o in range(0, len(data), 65536)])
+    assert rounded(big) > 1 << 20
+    sel, total = [], 0
+    while total <= 2 << 20 or len(sel) < len(chains):
+        sel.append(len(sel) % len(chains))
+        total += rounded(chains[sel[-1]])
+    assert total > 2 << 20
+    use, w = [chains[i] for i in sel], [want[i] for i in sel]
+    at = len(use) // 3
+    use.insert(at, big)
+    w.insert(at, rc.decode(big))
+    assert w[at][1] == len(data)
+    pk = Packed(use)
+    dst = bytearray(pk.dst)
+    out, cout = amd.LZ4HIPBatch.decompressSafeChain(pk.src, pk.src_off, pk.src_len, pk.dst_cap, pk.chain_first, dst, pk.chain_dst_off, pk.chain_dst_cap,
+                                                    pk.prefix, pk.stored)
+    bad = pk.check(dst, out, cout, w)
+    assert not bad, (len(bad), bad[:5])
+    for c, (outs, done, _) in enumerate(w):   # behind the decoded bytes the region is untouched
+        off = pk.chain_dst_off[c]
+        assert dst[off + done:off + pk.chain_dst_cap[c]] == bytes([pk.fill]) * (pk.chain_dst_cap[c] - done), use[c].name
 
 
 def program_cases(cases):

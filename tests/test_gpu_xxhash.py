@@ -39,6 +39,20 @@ def test_batch_random_vs_oracle(amd, ref):
             assert g == ref.xxh64(buf[o:o + n], seed), (o, n)
 
 
+def test_host_batch_across_three_chunks(amd, ref):
+    """seven buffers of 40 MiB: the host path stages 128 MiB per chunk (it has no knob), three buffers fit, so the batch is three
+    chunks and the first of the two alternating buffer sets is used again while the second is in flight"""
+    import numpy as np
+    size, n = 40 << 20, 7
+    buf = np.random.default_rng(71).integers(0, 256, n * size + 3, dtype=np.uint8).tobytes()
+    off = [3 + k * size for k in range(n)]
+    ln = [size] * (n - 1) + [size - 3]
+    assert sum(ln[:3]) <= 128 << 20 < sum(ln[:4]) and sum(ln) > 2 * (128 << 20)
+    want = [(ref.xxh32(buf[o:o + m], 0x9747b28c), ref.xxh64(buf[o:o + m], 0x9747b28c)) for o, m in zip(off, ln)]
+    assert amd.LZ4HIPBatch.xxh32(buf, off, ln, 0x9747b28c) == [w[0] for w in want]
+    assert amd.LZ4HIPBatch.xxh64(buf, off, ln, 0x9747b28c) == [w[1] for w in want]
+
+
 def test_cfg5_shape_device(amd, O, ref):
     """BASELINE.json configs[4] shape: 4 KiB slices of the 64 KiB synthetic blocks, seeds 0 and 0x9747b28c"""
     import torch

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Host-pointer batch API on headline blocks in pageable host memory: GB/s per call (PCIe both ways) and, with
-LZ4HIP_HOST_PROF=1 in the environment, the calling thread's time split per call (stderr).
-usage: host_path_probe.py [n_blocks=16384] [calls=4]"""
+LZ4HIP_HOST_PROF=1 in the environment, the calling thread's time split per call (stderr).  Per call: the block path
+(lz4hip_compress_fast_batch, lz4hip_decompress_safe_batch on n_blocks x 64 KiB), the chain paths
+(lz4hip_compress_fast_chain_batch, lz4hip_decompress_safe_chain_batch on `chains` chains of 16 x 4 KiB: the first bytes of the
+same data) and the hash path (lz4hip_xxh64_batch on the n_blocks x 64 KiB).  GB/s counts uncompressed bytes.
+usage: host_path_probe.py [n_blocks=16384] [calls=4] [chains=4096]"""
 import importlib, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -9,7 +12,10 @@ import numpy as np, torch
 amd = importlib.import_module("lz4-java_amd")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 calls = int(sys.argv[2]) if len(sys.argv) > 2 else 4
+nc = int(sys.argv[3]) if len(sys.argv) > 3 else 4096
 blk = 65536; cap = amd.maxCompressedLength(blk)
+per, cblk = 16, 4096; ccap = amd.maxCompressedLength(cblk)   # a chain: 16 blocks of 4 KiB, 64 KiB of source
+nc = min(nc, n)
 dev = torch.device("cuda:0")
 src = torch.empty(n * blk, dtype=torch.uint8, device=dev); amd.DeviceBatch.gen_blocks(src, blk, blk, n)
 h_src = src.cpu().numpy().copy()
@@ -18,18 +24,35 @@ so = np.arange(n, dtype=np.uint64) * blk; sl = np.full(n, blk, dtype=np.int32)
 co = np.arange(n, dtype=np.uint64) * cap; cc = np.full(n, cap, dtype=np.int32)
 h_dst = np.zeros(n * cap, dtype=np.uint8); h_back = np.zeros(n * blk, dtype=np.uint8)
 clen = np.zeros(n, dtype=np.int32); dlen = np.zeros(n, dtype=np.int32)
+# the chains: chain c is the 64 KiB at c * 65536 of the same source, its blocks' slots back to back in k_dst
+nb = nc * per
+k_so = np.arange(nc, dtype=np.uint64) * (per * cblk); k_sl = np.full(nb, cblk, dtype=np.int32)
+k_first = (np.arange(nc + 1, dtype=np.uint32) * per).astype(np.uint32)
+k_do = np.arange(nb, dtype=np.uint64) * ccap; k_dc = np.full(nb, ccap, dtype=np.int32)
+k_dst = np.zeros(nb * ccap, dtype=np.uint8); k_back = np.zeros(nb * cblk, dtype=np.uint8)
+k_out = np.zeros(nb, dtype=np.int32); k_cons = np.zeros(nc, dtype=np.uint64)
+k_cap = np.full(nc, per * cblk, dtype=np.uint64); k_dlen = np.zeros(nb, dtype=np.int32); k_done = np.zeros(nc, dtype=np.uint64)
+hashes = np.zeros(n, dtype=np.uint64)
 import ctypes as C
 lib = amd.lib()
 def p(a):
-    t = {np.uint64: C.POINTER(C.c_uint64), np.int32: C.POINTER(C.c_int32)}.get(a.dtype.type)
+    t = {np.uint64: C.POINTER(C.c_uint64), np.int32: C.POINTER(C.c_int32), np.uint32: C.POINTER(C.c_uint32)}.get(a.dtype.type)
     return a.ctypes.data_as(t) if t else a.ctypes.data_as(C.c_void_p)
-for c in range(calls):
+def timed(f, *a):
     t0 = time.perf_counter()
-    rc = lib.lz4hip_compress_fast_batch(p(h_src), p(so), p(sl), p(h_dst), p(co), p(cc), p(clen), n)
-    t1 = time.perf_counter()
-    assert rc == 0, rc
-    rc = lib.lz4hip_decompress_safe_batch(p(h_dst), p(co), p(clen), p(h_back), p(so), p(sl), p(dlen), n)
-    t2 = time.perf_counter()
-    assert rc == 0, rc
+    rc = f(*a)
+    dt = time.perf_counter() - t0
+    assert rc == 0, (rc, lib.lz4hip_last_error())
+    return dt
+for c in range(calls):
+    t_c = timed(lib.lz4hip_compress_fast_batch, p(h_src), p(so), p(sl), p(h_dst), p(co), p(cc), p(clen), n)
+    t_d = timed(lib.lz4hip_decompress_safe_batch, p(h_dst), p(co), p(clen), p(h_back), p(so), p(sl), p(dlen), n)
     print("call %d: compress %.1f ms (%.1f GB/s)  decompress %.1f ms (%.1f GB/s)  ok=%s" % (
-        c, 1e3 * (t1 - t0), n * blk / (t1 - t0) / 1e9, 1e3 * (t2 - t1), n * blk / (t2 - t1) / 1e9, bool((h_back == h_src).all() and (dlen == blk).all())), flush=True)
+        c, 1e3 * t_c, n * blk / t_c / 1e9, 1e3 * t_d, n * blk / t_d / 1e9, bool((h_back == h_src).all() and (dlen == blk).all())), flush=True)
+    t_kc = timed(lib.lz4hip_compress_fast_chain_batch, p(h_src), p(k_so), None, p(k_sl), p(k_first), p(k_dst), p(k_do), p(k_dc), p(k_out), p(k_cons), nb, nc)
+    t_kd = timed(lib.lz4hip_decompress_safe_chain_batch, p(k_dst), p(k_do), p(k_out), None, p(k_sl), p(k_first), p(k_back), p(k_so), p(k_cap), None,
+                 p(k_dlen), p(k_done), nb, nc)
+    t_h = timed(lib.lz4hip_xxh64_batch, p(h_src), p(so), p(sl), 0, p(hashes), n)
+    ok = bool((k_back == h_src[:nb * cblk]).all() and (k_dlen == cblk).all() and (k_cons == per * cblk).all() and (k_done == per * cblk).all())
+    print("call %d: chain compress %.1f ms (%.1f GB/s)  chain decompress %.1f ms (%.1f GB/s)  xxh64 %.1f ms (%.1f GB/s)  ok=%s" % (
+        c, 1e3 * t_kc, nb * cblk / t_kc / 1e9, 1e3 * t_kd, nb * cblk / t_kd / 1e9, 1e3 * t_h, n * blk / t_h / 1e9, ok), flush=True)
