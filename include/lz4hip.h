@@ -92,7 +92,10 @@ int lz4hip_version(void);
  *   parked hits a partner wavefront writes out, blocks of short sequences by the window-parallel core), 3 (lean core only) or 1
  *   (window-parallel core only); "compress_switch" = routing threshold of the adaptive scheme in bytes per sequence (default 16);
  * "compress_pack" = 1 (default) / 0: blocks of 65547 bytes .. 4 MiB are compressed with 32-bit table entries on ten match-finder chains
- *   per CU instead of five (0: every block on the five-chain kernel).
+ *   per CU instead of five (0: every block on the five-chain kernel);
+ * "hc_chain_segment" = 4096 .. 1073741824 (default 1048576): positions per build item of lz4hip_compress_hc_chain_batch*; every value
+ *   gives the same bytes (a segment warms its table up over the 65535 positions in front of it: at most 6.25 % more build work on a
+ *   long chain at the default, none on chains of up to 1 MiB).
  * The decode_* knobs and the device-side route do not apply to the partial decoder (lz4hip_decompress_safe_partial*): it always runs the
  * 4-lane staged loop from 40960 blocks on and the 8-lane deep loop below.  Nor do they apply to the dictionary decoder
  * (lz4hip_decompress_safe_dict*), which picks its two loops the same way.                                                       */
@@ -274,11 +277,48 @@ int lz4hip_decompress_safe_chain_batch(const uint8_t* src, const uint64_t* src_o
  *     produced, and shards over the initialised devices at chain boundaries;
  *   - out of scope: acceleration above 1; LZ4_saveDict and resuming a stream's exact state across calls (the prefix is LZ4_loadDict's
  *     table, which is not the table a running stream would hold: continuing a stream in a second call gives valid, decodable, but
- *     other bytes than one long chain); sources that are not contiguous; LZ4_attach_dictionary; an HC form.                          */
+ *     other bytes than one long chain); sources that are not contiguous; LZ4_attach_dictionary.  (No longer out of scope: an HC form
+ *     is lz4hip_compress_hc_chain_batch, below.)                                                                                    */
 int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
                                      const int32_t* src_len, const uint32_t* chain_first,
                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                      int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains);
+/* COMPRESS CHAINS OF LINKED BLOCKS AT AN HC LEVEL: the arrays of lz4hip_compress_fast_chain_batch without chain_consumed, and a level.
+ * With chain_src = src + chain_src_off[c] and P = chain_prefix_len[c], block k of chain c is, byte for byte and in its return value,
+ *     s = LZ4_createStreamHC();  LZ4_resetStreamHC_fast(s, level);  if (P > 0) LZ4_loadDictHC(s, chain_src - P, P);
+ *     r_k = LZ4_compress_HC_continue(s, chain_src + sum(src_len_j, j < k), dst_k, src_len_k, dst_cap_k);
+ * of liblz4 1.9.3: always its prefix mode, never the external-dictionary mode.  These are the linked blocks the lz4 command line
+ * writes at -3 and above; lz4hip_decompress_safe_chain_batch* reads them.
+ *   - levels are clamped as everywhere (< 1 -> 9, > 12 -> 12); levels 10..12 are functional only, as for lz4hip_compress_hc*;
+ *   - of the history only its last 65536 bytes count, and it has no minimum length (LZ4_loadDictHC has none);
+ *   - out_len[i] > 0: the compressed size.  out_len[i] == 0: liblz4 returns 0 -- dst_cap[i] is below the bound and the output does
+ *     not fit, or src_len[i] > 0x7E000000 -- and also the result for dst_cap[i] < 0 and src_len[i] < 0 (such a block counts as 0
+ *     bytes for the positions of the blocks behind it);
+ *   - A BLOCK WHOSE RESULT IS 0 DOES NOT END ITS CHAIN, unlike the fast chain's: liblz4 has taken its source into the stream's
+ *     history by then, so the blocks behind it are exactly what they would have been, and that is what they are here.  No
+ *     LZ4HIP_CHAIN_STOPPED exists in this call;
+ *   - a block of 0 bytes is the single token 0x00; a block under 13 bytes is one literal run;
+ *   - there is no single-call form: chains are the unit;
+ *   - nothing outside [chain_src_off[c] - min(P, 65536), chain_src_off[c] + sum max(src_len, 0)) is read, nothing outside a block's
+ *     slot is written (every store is exact).  Slots must not overlap;
+ *   - LZ4HIP_E_ARG: a required pointer that is NULL (everything but chain_prefix_len), a chain_first that is not ascending from 0 to
+ *     n_blocks, a negative chain_prefix_len[c] or one longer than chain_src_off[c].  These are said before a device is looked for;
+ *   - NOT SERIAL: HC's chain table is a function of the data alone, and block k's bytes depend only on the 64 KB in front of it, the
+ *     block, the level and the capacity.  Every block of every chain is parsed at the same time, one wavefront per block
+ *     (hc_parse_chain_kernel), behind a chain table built over each chain's buffer in segments ("hc_chain_segment" of
+ *     lz4hip_set_option: 4096 .. 2^30 positions, default 1 MiB; every value gives the same bytes) that workgroups draw from a queue
+ *     (hc_build_chain_kernel): a single long chain fills the device;
+ *   - the call takes host pointers: it uploads each chain's source with the last min(P, 65536) bytes of its history, brings back only
+ *     the bytes produced, and shards over the initialised devices at chain boundaries.  A stream that is cut in several places is
+ *     best passed as ONE chain (it is parallel anyway);
+ *   - out of scope: device-pointer forms (the chain workspace is indexed by source offset and the layout needs scratch of its
+ *     own; they are left to a change that can also extend the far-offset table of the device entry points); LZ4_saveDictHC;
+ *     sources that are not contiguous; LZ4_attach_HC_dictionary; a destSize form; favorDecSpeed; byte equality with the FRAMES
+ *     the lz4 command line writes (its frame layer moves its dictionary).                                                         */
+int lz4hip_compress_hc_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
+                                   const int32_t* src_len, const uint32_t* chain_first,
+                                   uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                   int32_t* out_len, uint32_t n_blocks, uint32_t n_chains, int level);
 /* COMPRESS AGAINST A DICTIONARY: for every block i, on a fresh stream,
  *     LZ4_loadDict(s, dict, dict_len);  LZ4_compress_fast_continue(s, src_i, dst_i, src_len[i], dst_cap[i], 1)
  * of liblz4 1.9.3 with a dictionary that is NOT contiguous with the source (its external-dictionary mode): the return value and the

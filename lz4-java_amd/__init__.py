@@ -65,6 +65,7 @@ C_ABI = {
     "lz4hip_decompress_safe_chain_batch_dev": (C.c_int, [C.c_void_p] * 12 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_fast_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32]),
     "lz4hip_compress_fast_chain_batch_dev": (C.c_int, [C.c_void_p] * 10 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
+    "lz4hip_compress_hc_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_uint32, C.c_int]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
@@ -920,13 +921,8 @@ class LZ4HIPBatch:
         return list(out[:n]), list(cout[:nc])
 
     @classmethod
-    def compressFastChain(cls, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None):
-        """LZ4_compress_fast_continue over chains of linked blocks (lz4hip_compress_fast_chain_batch): chain c is the blocks
-        chainFirst[c] .. chainFirst[c + 1] - 1, whose sources lie back to back from src[chainSrcOff[c]] on, behind chainPrefixLen[c]
-        bytes of history that lie in front of it in src (None: no history; the stream loads it with LZ4_loadDict); block i owns the
-        slot dst[dstOff[i]:+dstCap[i]] -> (outLen, chainConsumed): liblz4's return value per block (0: it did not fit, which ends
-        the chain; CHAIN_STOPPED behind a chain's first 0) and the source bytes of each chain's blocks that succeeded (lists, or
-        int32 / uint64 arrays for numpy inputs)"""
+    def _check_chains(cls, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen):
+        """the argument checks of the chain compressors -> (blocks, chains)"""
         n, nc = len(srcLen), len(chainSrcOff)
         if not (len(dstOff) == len(dstCap) == n):
             raise ValueError("per-block arrays differ in length")
@@ -952,6 +948,35 @@ class LZ4HIPBatch:
                 if chainPrefixLen[c] > chainSrcOff[c]:
                     raise IndexError("history reaches in front of the buffer")
         cls._check_ranges(dst, dstOff, dstCap)
+        return n, nc
+
+    @classmethod
+    def compressHCChain(cls, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None, level=9):
+        """LZ4_compress_HC_continue over chains of linked blocks, prefix mode (lz4hip_compress_hc_chain_batch): the arrays of
+        compressFastChain and an HC level (< 1 -> 9, > 12 -> 12) -> outLen: liblz4's return value per block (a list, or an int32 array
+        for numpy inputs).  A block whose result is 0 -- it did not fit -- does NOT end its chain: its source is history for the blocks
+        behind it, and there is no CHAIN_STOPPED here.  Not serial: every block of every chain is parsed at once"""
+        n, nc = cls._check_chains(src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen)
+        sp, sk = _ro_ptr(src)
+        dp, dk = _rw_ptr(dst)
+        out = (C.c_int32 * max(n, 1))()
+        pre = _arr(C.c_int32, chainPrefixLen) if chainPrefixLen is not None else None
+        _chk(lib().lz4hip_compress_hc_chain_batch(sp, _arr(C.c_uint64, chainSrcOff), pre, _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst), dp,
+                                                  _arr(C.c_uint64, dstOff), _arr(C.c_int32, dstCap), out, n, nc, int(level)))
+        if hasattr(srcLen, "dtype"):
+            import numpy as np
+            return np.frombuffer(out, dtype=np.int32, count=n).copy()
+        return list(out[:n])
+
+    @classmethod
+    def compressFastChain(cls, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None):
+        """LZ4_compress_fast_continue over chains of linked blocks (lz4hip_compress_fast_chain_batch): chain c is the blocks
+        chainFirst[c] .. chainFirst[c + 1] - 1, whose sources lie back to back from src[chainSrcOff[c]] on, behind chainPrefixLen[c]
+        bytes of history that lie in front of it in src (None: no history; the stream loads it with LZ4_loadDict); block i owns the
+        slot dst[dstOff[i]:+dstCap[i]] -> (outLen, chainConsumed): liblz4's return value per block (0: it did not fit, which ends
+        the chain; CHAIN_STOPPED behind a chain's first 0) and the source bytes of each chain's blocks that succeeded (lists, or
+        int32 / uint64 arrays for numpy inputs)"""
+        n, nc = cls._check_chains(src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen)
         sp, sk = _ro_ptr(src)
         dp, dk = _rw_ptr(dst)
         out = (C.c_int32 * max(n, 1))()

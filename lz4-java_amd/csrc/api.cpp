@@ -90,12 +90,14 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // BlockCall::chain, the seven arrays of the other operations are not used; the host path is chain_host_shard, not host_shard
 // OP_COMPRESS_CHAIN: LZ4_compress_fast_continue over chains of linked blocks: its arrays are BlockCall::cchain; the host path is
 // cchain_host_shard, which brings back only the bytes produced, as every compressor's does
+// OP_COMPRESS_HC_CHAIN: LZ4_compress_HC_continue over chains of linked blocks (prefix mode): OP_COMPRESS_CHAIN's arrays and host path
+// (no chain_consumed: a block that returns 0 does not stop its chain), OP_COMPRESS_HC's level and workspace
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
-          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN, OP_COMPRESS_CHAIN };
-constexpr int OP_COUNT = OP_COMPRESS_CHAIN + 1;   // (the last enumerator)
+          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN, OP_COMPRESS_CHAIN, OP_COMPRESS_HC_CHAIN };
+constexpr int OP_COUNT = OP_COMPRESS_HC_CHAIN + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
-constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN; }
+constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN; }
 // a second per-block result (BlockCall::consumed) travels behind out[]
 constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
 // out[i] counts SOURCE bytes read: a block that succeeded filled its whole dst_cap[i]
@@ -103,7 +105,13 @@ constexpr bool op_fills_capacity(Op op) { return op == OP_DECODE_FAST; }
 // writes no output buffer: dst and dst_off may be NULL, nothing is allocated, staged or copied back for them (dst_cap is an input)
 constexpr bool op_writes_no_output(Op op) { return op == OP_DECODED_SIZE; }
 // needs the chain-delta workspace (BlockCall::hc_ws / hc_span)
-constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_HC_DICT; }
+constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_HC_CHAIN; }
+// its arrays are BlockCall::cchain (chains of linked blocks), its host path cchain_host_shard
+constexpr bool op_takes_cchain(Op op) { return op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN; }
+// a block that returns 0 ends its chain (and chain_consumed[] says how far the chain came)
+constexpr bool op_chain_stops(Op op) { return op == OP_COMPRESS_CHAIN; }
+// its layout kernel needs scratch beside the workspace (BlockCall::hc_scratch)
+constexpr bool op_needs_chain_scratch(Op op) { return op == OP_COMPRESS_HC_CHAIN; }
 
 // One block operation, from its entry point to launch_block.
 struct BlockCall {
@@ -117,7 +125,8 @@ struct BlockCall {
   const uint8_t* dict_dev = nullptr;    // ... or, without a handle, the caller's dictionary in device memory and
   int32_t dict_len = 0;                 // its length
   const lz4hip::ChainArgs* chain = nullptr;   // OP_DECOMPRESS_CHAIN: the call's arrays on the device
-  const lz4hip::CChainArgs* cchain = nullptr; // OP_COMPRESS_CHAIN: the call's arrays on the device
+  const lz4hip::CChainArgs* cchain = nullptr; // op_takes_cchain: the call's arrays on the device
+  void* hc_scratch = nullptr;           // op_needs_chain_scratch: lz4hip::hc_chain_scratch_bytes of device memory
 };
 static_assert(lz4hip::kChainStopped == LZ4HIP_CHAIN_STOPPED, "the kernels' marker is the header's");
 // the handle's bytes on the CURRENT device (uploaded on first use where lz4hip_dict_create found the device not yet initialised):
@@ -142,6 +151,9 @@ std::atomic<int> g_decode_ring{0};    // "decode_ring": bytes of the ring loop's
 // forced modes exist so that the suite can put every input through each kernel).  "compress_switch" = bytes per sequence below
 // which a block counts as dense and goes to the window-parallel core (probe: sequences 32..95 of the block)
 std::atomic<int> g_compress_core{5};
+// lz4hip_set_option "hc_chain_segment": positions per build item of the HC chain compressor (launch_compress_hc_chain); every value
+// gives the same bytes
+std::atomic<int> g_hc_chain_segment{1 << 20};
 std::atomic<int> g_compress_switch{16};   // (tools/switch_probe.py: 20 sent word-like data of 9 bytes per sequence to the slower core; 12 loses text)
 
 // liblz4's level handling: < 1 -> 9, > 12 -> 12; 10..12 are the optimal parser (lz4-java levels 10..17)
@@ -283,6 +295,14 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
     case OP_COMPRESS_CHAIN:   // compress_fast_chain_cu_kernel draws chains from the queue word
       if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
       return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_chain(*c.cchain, q, lz4hip::device_cus(), st); });
+    case OP_COMPRESS_HC_CHAIN: {   // layout, segment build and parse kernels behind one scratch allocation
+      if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
+      // (workspace and scratch are the buffer set's.  As a stream-ordered allocation made here, the scratch read as zeros in the parse
+      // kernel in a third of the second calls of a process on the MI355X, behind a memset and a kernel that had written it: DESIGN.md 2.3)
+      if (!c.hc_ws || !c.hc_scratch) return fail(LZ4HIP_E_ARG, kNullArg);
+      const uint32_t seg = (uint32_t)g_hc_chain_segment.load(std::memory_order_relaxed);
+      return lz4hip::launch_compress_hc_chain(*c.cchain, c.param, c.hc_ws, c.hc_span, seg, c.hc_scratch, lz4hip::device_cus(), st);
+    }
     case OP_COMPRESS_HC:
     case OP_COMPRESS_HC_DICT:
     case OP_COMPRESS_HC_DEST: {
@@ -838,14 +858,22 @@ const char* chain_arg_error(const lz4hip::ChainArgs& a, bool host) {
 // last min(prefix_len, 65536) bytes of its history in front of it; the kernel runs; the results come back, and then only the bytes
 // each block produced (runs less than 4 KB apart travel as one copy).  Of a chain's source only what its blocks can consume is
 // read: up to the first block with a negative length or with which the chain would exceed 0x7E000000 bytes (its result is 0).
-int cchain_host_shard(const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+// op_chain_stops(c.op) false (the HC chain): every block's source is read, a negative length counts as 0 bytes, a history of any
+// length is kept, nothing travels in chain_consumed[], and the chunk's workspace is sized by its packed source.
+int cchain_host_shard(const BlockCall& proto, const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
   if (c1 == c0) return LZ4HIP_OK;
   ShardScope sh(ord, err);
   if (sh.rc) return sh.rc;
   ChunkSlot& s = sh.pair->slot[0];
   const hipStream_t st = s.st;
   auto keep_of = [&](uint32_t c) -> size_t { const int32_t p = h.chain_prefix_len ? h.chain_prefix_len[c] : 0; return p > 65536 ? 65536u : (size_t)p; };
+  const bool stops = op_chain_stops(proto.op);
   auto span_of = [&](uint32_t c) -> size_t {   // the source bytes the chain's blocks can consume
+    if (!stops) {
+      size_t sum = 0;
+      for (uint32_t i = h.chain_first[c]; i < h.chain_first[c + 1]; i++) sum += pos(h.src_len[i]);
+      return sum;
+    }
     const size_t k = keep_of(c);
     uint64_t pos = k < 8u ? 0u : k;   // (the kernel's count: a prefix under 8 bytes is not kept)
     const uint64_t pos0 = pos;
@@ -871,6 +899,9 @@ int cchain_host_shard(const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_
     { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { dso[t] = o; o += al16(pos(h.dst_cap[b0 + t])); } }
     const staging::CChainMeta m(nb, nc);
     if (!sh.reserve(s, ck.src, true, ck.dst, m.l.total)) return sh.rc;
+    if (op_uses_hc_ws(proto.op) && !sh.ok("staging allocation", s.d_ws.reserve(lz4hip::hc_ws_bytes(ck.src, nb, proto.param)))) return sh.rc;
+    // (the layout's scratch for the largest segment count the knob allows, in the buffer set's unused offsets buffer)
+    if (op_needs_chain_scratch(proto.op) && !sh.ok("staging allocation", s.d_poff.reserve(lz4hip::hc_chain_scratch_bytes(ck.src, nb, nc, 4096u)))) return sh.rc;
     uint8_t *const hs = (uint8_t*)s.h_src.p, *const hd = (uint8_t*)s.h_dst.p;
     void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
     par_blocks(c, j, ck.src, [=, &cso](uint32_t t) {
@@ -886,11 +917,13 @@ int cchain_host_shard(const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_
     for (uint32_t t = 0; t < nc; t++) m.prefix.in(hm)[t] = (int32_t)keep_of(c + t);
     if (!sh.upload(s, ck.src, m.l, st)) return sh.rc;
     const lz4hip::CChainArgs a{(const uint8_t*)s.d_src.p, m.chain_src_off.in(dm), m.prefix.in(dm), m.src_len.in(dm), m.first.in(dm), (uint8_t*)s.d_dst.p,
-                               m.dst_off.in(dm), m.dst_cap.in(dm), m.out.in(dm), m.consumed.in(dm), nb, nc};
-    BlockCall call{OP_COMPRESS_CHAIN}; call.cchain = &a;
+                               m.dst_off.in(dm), m.dst_cap.in(dm), m.out.in(dm), stops ? m.consumed.in(dm) : nullptr, nb, nc};
+    BlockCall call = proto; call.cchain = &a;
+    if (op_uses_hc_ws(proto.op)) { call.hc_ws = s.d_ws.p; call.hc_span = ck.src; }
+    if (op_needs_chain_scratch(proto.op)) call.hc_scratch = s.d_poff.p;
     if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
     memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
-    memcpy(h.chain_consumed + c, m.consumed.in(hm), m.consumed.bytes());
+    if (stops) memcpy(h.chain_consumed + c, m.consumed.in(hm), m.consumed.bytes());
     // only the bytes produced come back
     if (!sh.fetch_runs(s, nb, [&](uint32_t t) { return staging::Run{(size_t)dso[t], produced(b0 + t)}; })) return sh.rc;
     par_blocks(b0, b1, ck.dst, [=, &dso](uint32_t i) { if (const size_t r = produced(i)) memcpy(h.dst + h.dst_off[i], hd + dso[i - b0], r); });
@@ -900,9 +933,9 @@ int cchain_host_shard(const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_
 }
 
 // the argument errors of a chain-compress call that can be seen without a device; host: the arrays are the caller's host memory
-const char* cchain_arg_error(const lz4hip::CChainArgs& a, bool host) {
+const char* cchain_arg_error(const lz4hip::CChainArgs& a, bool host, bool stops) {
   if (a.n_chains == 0 && a.n_blocks == 0) return nullptr;
-  if (!a.src || !a.chain_src_off || !a.src_len || !a.chain_first || !a.dst || !a.dst_off || !a.dst_cap || !a.out || !a.chain_consumed) return kNullArg;
+  if (!a.src || !a.chain_src_off || !a.src_len || !a.chain_first || !a.dst || !a.dst_off || !a.dst_cap || !a.out || (stops && !a.chain_consumed)) return kNullArg;
   return host ? staging::chain_shape_error(a.chain_first, a.n_chains, a.n_blocks, a.chain_prefix_len, a.chain_src_off, false) : nullptr;
 }
 
@@ -1584,6 +1617,11 @@ int lz4hip_set_option(const char* name, int value) {
     lz4hip::set_compress_pack(value);
     return LZ4HIP_OK;
   }
+  if (name && strcmp(name, "hc_chain_segment") == 0) {   // positions per build item of the HC chain compressor: every value gives the same bytes
+    if (value < 4096 || value > (1 << 30)) return fail(LZ4HIP_E_ARG, "hc_chain_segment must be 4096 .. 1073741824");
+    g_hc_chain_segment = value;
+    return LZ4HIP_OK;
+  }
   if (name && strcmp(name, "compress_switch") == 0) {
     if (value < 0 || value > 1024) return fail(LZ4HIP_E_ARG, "compress_switch must be 0..1024");
     g_compress_switch = value;
@@ -1682,11 +1720,23 @@ int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_s
                                      const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
                                      uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains) {
   const lz4hip::CChainArgs h{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains};
-  if (const char* why = cchain_arg_error(h, true)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
+  if (const char* why = cchain_arg_error(h, true, op_chain_stops(OP_COMPRESS_CHAIN))) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
   if (const int rc = need_device()) return rc;
   if (n_chains == 0) return LZ4HIP_OK;
   // whole chains per device: a chain never leaves its wavefront, let alone its device
-  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard(h, ord, c0, c1, err); });
+  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard({OP_COMPRESS_CHAIN}, h, ord, c0, c1, err); });
+}
+int lz4hip_compress_hc_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
+                                   const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
+                                   uint32_t n_blocks, uint32_t n_chains, int level) {
+  const lz4hip::CChainArgs h{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, nullptr, n_blocks, n_chains};
+  if (const char* why = cchain_arg_error(h, true, op_chain_stops(OP_COMPRESS_HC_CHAIN))) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
+  if (const int rc = need_device()) return rc;
+  if (n_chains == 0) return LZ4HIP_OK;
+  int lv;
+  if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
+  // whole chains per device: a device's workspace and staging hold a chain's buffer in one piece
+  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard({OP_COMPRESS_HC_CHAIN, lv}, h, ord, c0, c1, err); });
 }
 int lz4hip_compress_fast_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                     const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, const lz4hip_dict* dict) {
@@ -1787,7 +1837,7 @@ int lz4hip_compress_fast_chain_batch_dev(const uint8_t* src, const uint64_t* cha
                                          const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
                                          uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains, int device, void* stream) {
   const lz4hip::CChainArgs a{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains};
-  if (const char* why = cchain_arg_error(a, false)) return fail(LZ4HIP_E_ARG, why);
+  if (const char* why = cchain_arg_error(a, false, op_chain_stops(OP_COMPRESS_CHAIN))) return fail(LZ4HIP_E_ARG, why);
   BlockCall c{OP_COMPRESS_CHAIN};
   c.cchain = &a;
   return on_device(device, n_chains == 0, nullptr, [&] { return launch_block(c, lz4hip::BatchArgs{}, (hipStream_t)stream); });

@@ -67,6 +67,26 @@ struct HashMeta {   // the hashes (xxh_shard): T = uint32_t / uint64_t
   explicit HashMeta(size_t nb) : off(l.input<uint64_t>(nb)), len(l.input<int32_t>(nb)), hash(l.result<T>(nb)) {}
 };
 
+// The scratch of the HC chain compressor's layout kernel (compress_hc.hip) for n_blocks blocks in n_chains chains whose regions end at or
+// before `span`, with build segments of `seg` positions (4096 .. 2^30): byte offsets of its arrays, 8-byte ones first.  max_items: a
+// chain of N buffer bytes lists ceil((N - 3) / seg) <= N / seg + 1 items, and the chains' buffers lie side by side inside the span,
+// so span / seg + n_chains + 1 is never exceeded (capped where a uint32_t ends; the layout kernel lists nothing past it).
+struct HcChainScratchLayout {
+  uint32_t max_items;
+  size_t blk_start, chain_buf, chain_len, items, blk_hist, words, total;
+  HcChainScratchLayout(uint64_t span, uint32_t n_blocks, uint32_t n_chains, uint32_t seg) {
+    const uint64_t m = span / (seg ? seg : 1u) + (uint64_t)n_chains + 1u;
+    max_items = m > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)m;
+    blk_start = 0;                                        // u64[n_blocks]
+    chain_buf = blk_start + 8u * (size_t)n_blocks;        // u64[n_chains]
+    chain_len = chain_buf + 8u * (size_t)n_chains;        // u64[n_chains]
+    items = chain_len + 8u * (size_t)n_chains;            // {u32, u32}[max_items]
+    blk_hist = items + 8u * (size_t)max_items;            // u32[n_blocks]
+    words = blk_hist + 4u * (size_t)n_blocks;             // u32[2]
+    total = words + 8u;
+  }
+};
+
 // The next chunk of the units [begin, end) -- blocks, chains, buffers: units are taken while the chunk stays within src_limit and
 // dst_limit bytes and max_units units; the first unit is taken whatever it costs, so a single unit always fits.  cost(u) -> the
 // bytes unit u takes in the packed source and destination, rounded as the caller packs them.

@@ -140,6 +140,16 @@ struct CChainArgs {
 // compress_fast_chain_cu_kernel: five wavefronts per CU, a 32 KB table each, draw chains from the queue word q (one device uint32_t of
 // scratch); the table stays in LDS from one block of a chain to the next; no wavefront waits for another.  n_cus = compute units
 int launch_compress_fast_chain(const CChainArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
+// LZ4_compress_HC_continue over chains of linked blocks, prefix mode (compress_hc.hip): CChainArgs as above with chain_consumed unused
+// (nullptr); the history is what LZ4_loadDictHC keeps (its last 64 KB, no minimum).  out[i] = liblz4's return value; a block that
+// returns 0 (it does not fit, or src_len[i] / dst_cap[i] is negative) does NOT stop its chain: its source is history for the blocks
+// behind it (a negative length counts as 0 bytes).  Every block of every chain is parsed at once, a wavefront per block; the delta[]
+// build runs over (chain, segment) items of `seg` positions (4096 .. 2^30; every value gives the same bytes).  `ws` = device workspace
+// of hc_ws_bytes(span, n_blocks, level) bytes, span = the maximum over chains of the region's end; the regions of different chains,
+// history included, must not overlap.  `scratch` = hc_chain_scratch_bytes(span, n_blocks, n_chains, seg) bytes of device memory that
+// the caller keeps (not a stream-ordered allocation made for the launch).
+size_t hc_chain_scratch_bytes(uint64_t span, uint32_t n_blocks, uint32_t n_chains, uint32_t seg);
+int launch_compress_hc_chain(const CChainArgs& a, int level, void* ws, uint64_t span, uint32_t seg, void* scratch, uint32_t n_cus, void* stream);
 // The decoded-size query: out[i] = the value LZ4_decompress_safe would return for block i with capacity a.dst_cap[i] (-1 where it or
 // src_len[i] is negative); a.dst and a.dst_off are ignored (may be nullptr) and no output buffer exists.  decode_size_kernel<4, 2048, true>:
 // a wavefront per block; no route word, no sampler, no decode knob

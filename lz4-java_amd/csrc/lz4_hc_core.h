@@ -64,13 +64,17 @@ constexpr int HC_OPT_INTS = 4 * (HC_OPT_NUM + HC_OPT_TRAILING);  // per-block wo
 // DICT (a record behind a dictionary, LZ4_loadDictHC + LZ4_compress_HC_continue): the caller has loaded the head table with the
 // one the build over the dictionary's kept tail ended with, and src[0] has index `first` = HC_BIAS + kept bytes instead of HC_BIAS.
 // A link that reaches into the dictionary is a plain index distance; the dictionary's own links are the handle's (HcDictRef).
-template <class W, bool DICT = false>
+// SEG (one segment of a chain of linked blocks, hc_build_chain_kernel): entries are stored from position `store_from` on only.  The
+// positions in front of it -- the caller starts the run up to 65535 positions early -- only warm the head table up: every link a
+// position >= store_from can store has a distance of at most 65535, so its entry is the one a build from the buffer's start stores.
+// SEG = false is what every other instantiation uses: the code it generates does not change.
+template <class W, bool DICT = false, bool SEG = false>
 struct HcBuild {
   using VU = typename W::VU;
   using VU64 = typename W::VU64;
   using VB = typename W::VB;
 
-  LZ4HIP_DEV static void run(W& w, const uint8_t* src, uint32_t n, uint16_t* delta, uint32_t first = HC_BIAS) {
+  LZ4HIP_DEV static void run(W& w, const uint8_t* src, uint32_t n, uint16_t* delta, uint32_t first = HC_BIAS, uint32_t store_from = 0u) {
     if (n < 4u) return;
     const uint32_t last = n - 4u;  // last position whose 4-byte hash is readable
     const uint32_t bias = DICT ? first : HC_BIAS;
@@ -116,12 +120,27 @@ struct HcBuild {
           pend &= ~gm;
         }
         const VU dist = idx - prev;
-        w.st16(delta, p, W::select(dist > (uint32_t)HC_MAXD, VU(0u), dist), valid);
+        if constexpr (SEG) w.st16(delta, p, W::select(dist > (uint32_t)HC_MAXD, VU(0u), dist), valid & (p >= store_from));
+        else w.st16(delta, p, W::select(dist > (uint32_t)HC_MAXD, VU(0u), dist), valid);
         w.sync();
       }
     }
   }
 };
+
+// One build item of a chain of linked blocks: segment k (`seg` positions, 4096 .. 2^30) of the chain's buffer buf[0, len) -- its kept
+// history, then its sources, built as ONE run of positions: the last three positions of a block hash bytes of the next one, as
+// liblz4's late insert does, and only the buffer's last three positions have no entry.  The cuts are fixed positions, not block
+// boundaries.  A segment that starts at position `from` runs from max(0, from - 65535) on and stores from `from` on; positions count
+// from where the run starts, so the run's length does not depend on the chain's.
+template <class W>
+LZ4HIP_DEV void hc_chain_build_segment(W& w, const uint8_t* buf, uint64_t len, uint32_t seg, uint32_t k, uint16_t* delta) {
+  const uint64_t from = (uint64_t)k * seg;
+  if (len < 4u || from > len - 4u) return;
+  const uint64_t warm = from > (uint64_t)HC_MAXD ? from - (uint64_t)HC_MAXD : 0ull;
+  const uint64_t end = from + seg < len - 3u ? from + seg : len - 3u;   // one past the segment's last position
+  HcBuild<W, false, true>::run(w, buf + warm, (uint32_t)(end + 3u - warm), delta + warm, HC_BIAS, (uint32_t)(from - warm));
+}
 
 // The dictionary's part of the chain (LZ4_loadDictHC), the same for every record of every batch at every level: delta[] over the
 // kept tail [tail, tail + K), 0 <= K <= 65536, into ddelta[0 .. K), and the head table the build ends with, left in the wave's LDS
@@ -154,7 +173,11 @@ template <> struct HcDictRef<true> {
   LZ4HIP_DEV uint32_t first() const { return HC_BIAS + (uint32_t)K; }
 };
 
-template <bool DICT = false>
+// PREFIX (a block of a chain of linked blocks, liblz4's prefix mode): `src` is the start of the block's BUFFER -- up to 64 KB of
+// history, then the block -- and positions count from there.  A candidate in the history is an ordinary candidate; the one thing the
+// search itself does differently is that pattern analysis counts backward no further than the lowest index allows (the result is
+// cut to it anyway: a long run in the history is not walked to its start).
+template <bool DICT = false, bool PREFIX = false>
 struct HcSearchT : HcDictRef<DICT> {
   const uint8_t* src;
   const uint16_t* delta;
@@ -257,7 +280,7 @@ struct HcSearchT : HcDictRef<DICT> {
           const int cp = (int)(cand - HC_BIAS);
           if (hc_rd32(src + cp) == pattern) {
             const int fwd = count_pattern(src, cp + 4, ihigh, pattern) + 4;
-            int back = reverse_count_pattern(src, cp, 0, pattern);
+            int back = reverse_count_pattern(src, cp, PREFIX ? (int)(lowest - HC_BIAS) : 0, pattern);
             {
               const uint32_t far = cand - (uint32_t)back;
               back = (int)(cand - (far > lowest ? far : lowest));
@@ -495,13 +518,29 @@ using HcSearch = HcSearchT<false>;
 // the caller fills s.dend / s.ddelta_end / s.K after construction, and `delta` is HcBuild<W, true>'s.  A match position below 0
 // lies in the dictionary; the parse itself only ever subtracts it from a record position, which gives liblz4's offset.  DICT =
 // false is what every other instantiation uses: the code it generates does not change.
+//
+// HcParse<W, false, false, PREFIX = true> parses one block of a chain of linked blocks (LZ4_compress_HC_continue in prefix mode).
+// `src` is the start of the block's buffer, `n` the buffer's length, `delta` the chain's delta[] at the buffer's start
+// (HcBuild<W, false, true>); set_history(h) after construction says where the block begins: positions [0, h) are history, h =
+// min(65536, what the chain holds in front of the block).  With positions counted from the buffer's start liblz4's lowLimit is
+// HC_BIAS, as it is without history, so the searches are the plain ones; the parse starts at h, and everything liblz4 derives from
+// the block's own length (the minimum length, the capacity test) takes n - h.  PREFIX = false is what every other instantiation
+// uses: the code it generates does not change.
 // ---------------------------------------------------------------------------------------------------
-template <class W, bool FILL = false, bool DICT = false>
-struct HcParse {
+template <bool PREFIX> struct HcPrefixRef {
+  LZ4HIP_DEV int start() const { return 0; }
+};
+template <> struct HcPrefixRef<true> {
+  int hist = 0;   // history bytes in front of the block
+  LZ4HIP_DEV int start() const { return hist; }
+};
+
+template <class W, bool FILL = false, bool DICT = false, bool PREFIX = false>
+struct HcParse : HcPrefixRef<PREFIX> {
   using VU = typename W::VU;
   using VU64 = typename W::VU64;
   using VB = typename W::VB;
-  using Search = HcSearchT<DICT>;
+  using Search = HcSearchT<DICT, PREFIX>;
 
   W& w;
   Search s;
@@ -656,6 +695,16 @@ struct HcParse {
     limited = (uint32_t)cap < (uint32_t)n + (uint32_t)n / 255u + 16u;
   }
 
+  // PREFIX: the block begins at buffer position h
+  LZ4HIP_DEV void set_history(int h) {
+    if constexpr (PREFIX) {
+      this->hist = h;
+      anchor = h;
+      const uint32_t len = (uint32_t)(n - h);
+      limited = (uint32_t)cap < len + len / 255u + 16u;
+    }
+  }
+
   LZ4HIP_DEV void put_run(uint32_t o, uint32_t len) {  // 255-run encoding of len (>= 0): 255,...,255,rem
     const uint32_t cnt = len / 255u + 1u, rem = len - 255u * (cnt - 1u);
     for (uint32_t base = 0; base < cnt; base += 64u) {
@@ -710,6 +759,9 @@ struct HcParse {
         if (d == 0u) return 0ull;
         if constexpr (DICT) {   // (a link into the dictionary ends on a chain member: four bytes before its end at least)
           if ((int)d > p) return hc_rd32(sr.dend + (p - (int)d)) == hc_rd32(sr.src + p) ? 1ull : 0ull;
+        }
+        if constexpr (PREFIX) {   // (no link of a built chain reaches in front of the buffer; nothing is read there whatever delta[] holds)
+          if ((int)d > p) return 0ull;
         }
         return hc_rd32(sr.src + p - (int)d) == hc_rd32(sr.src + p) ? 1ull : 0ull;   // (d <= 65535 and p - d >= 0 by construction)
       }) != VU64(0));
@@ -809,10 +861,10 @@ struct HcParse {
     int* const o_off = opt + (HC_OPT_NUM + HC_OPT_TRAILING);        // opt[p].off
     int* const o_ml = opt + 2 * (HC_OPT_NUM + HC_OPT_TRAILING);     // opt[p].mlen (1 = literal)
     int* const o_ll = opt + 3 * (HC_OPT_NUM + HC_OPT_TRAILING);     // opt[p].litlen
-    int ip = 0;
+    int ip = this->start();
     // (liblz4's optimal parser has no minimum block length of its own: a block of exactly 12 bytes searches at position 0, where
-    // only a dictionary can answer)
-    if (DICT ? n >= 12 : n >= 13) {
+    // only a dictionary -- or a chain's history -- can answer)
+    if (PREFIX || (DICT ? n >= 12 : n >= 13)) {
       while (ip <= mflimit) {
         const int llen = ip - anchor;
         int first_off = 0;
@@ -903,8 +955,8 @@ struct HcParse {
 
   LZ4HIP_DEV int run() {
     const int mflimit = n - 12, matchlimit = n - 5;
-    int ip = 0, ml = 0, ml0, ml2, ml3, ref = 0, ref0, ref2 = 0, ref3 = 0, start0, start2 = 0, start3 = 0;
-    if (n >= 13) {
+    int ip = this->start(), ml = 0, ml0, ml2, ml3, ref = 0, ref0, ref2 = 0, ref3 = 0, start0, start2 = 0, start3 = 0;
+    if (n - this->start() >= 13) {
       for (;;) {
         ip = first_match(ip, mflimit, matchlimit, ml, ref);
         if (ip < 0) break;
@@ -975,5 +1027,14 @@ struct HcParse {
     return last_literals();
   }
 };
+
+// One block of a chain of linked blocks: n bytes at buf + hist, behind hist = min(65536, what the chain holds in front of it) bytes of
+// history at buf; delta = the chain's delta[] at buf (hc_chain_build_segment).  -> LZ4_compress_HC_continue's return value
+template <class W>
+LZ4HIP_DEV int hc_chain_parse_block(W& w, const uint8_t* buf, uint32_t hist, int n, const uint16_t* delta, uint8_t* dst, int cap, int level, int* opt) {
+  HcParse<W, false, false, true> p(w, buf, (int)hist + n, delta, dst, cap, level);
+  p.set_history((int)hist);
+  return level >= 10 ? p.run_opt(level, opt) : p.run();
+}
 
 }  // namespace lz4hip

@@ -10,6 +10,7 @@
 //                                                   =  LZ4_decompress_safe_usingDict of liblz4's main API against a dictionary that is not
 //                                                      contiguous with the destination (no reference entry reaches it)
 //   LZ4HIPBatch::compressFastChain                  =  LZ4_compress_fast_continue over chains of linked blocks (liblz4's prefix mode)
+//   LZ4HIPBatch::compressHCChain                    =  LZ4_compress_HC_continue over chains of linked blocks (prefix mode; not serial)
 //   LZ4HIPBatch::decompressSafeChain                =  LZ4_decompress_safe_continue over chains of linked blocks (liblz4's rolling-prefix
 //                                                      mode; no reference entry reaches it)
 //   LZ4HIPCompressor::compressWithDict, LZ4HIPBatch::compressDict
@@ -328,6 +329,43 @@ struct LZ4HIPBatch {
   static Chains compressFastChain(const bytes& src, const std::vector<uint64_t>& chainSrcOff, const std::vector<int32_t>& srcLen,
                                   const std::vector<uint32_t>& chainFirst, bytes& dest, const std::vector<uint64_t>& destOff,
                                   const std::vector<int32_t>& maxDestLen, const std::vector<int32_t>& chainPrefixLen = {}) {
+    checkChains(src, chainSrcOff, srcLen, chainFirst, dest, destOff, maxDestLen, chainPrefixLen);
+    const size_t n = srcLen.size(), nc = chainSrcOff.size();
+    Chains r;
+    r.lengths.assign(n, 0);
+    r.chainLengths.assign(nc, 0);
+    bytes one(1);                                 // (an empty buffer still hands the library a pointer)
+    int32_t none = 0;
+    uint64_t none64 = 0;
+    status(lz4hip_compress_fast_chain_batch(src.empty() ? one.data() : src.data(), nc ? chainSrcOff.data() : &none64,
+                                            chainPrefixLen.empty() ? nullptr : chainPrefixLen.data(), n ? srcLen.data() : &none, chainFirst.data(),
+                                            dest.empty() ? one.data() : dest.data(), n ? destOff.data() : &none64, n ? maxDestLen.data() : &none,
+                                            n ? r.lengths.data() : &none, nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
+    return r;
+  }
+  // LZ4_compress_HC_continue over chains of linked blocks, prefix mode (lz4hip_compress_hc_chain_batch): compressFastChain's arrays
+  // and an HC level (< 1 -> 9, > 12 -> 12) -> liblz4's return value per block.  A block whose result is 0 -- it did not fit -- does
+  // NOT end its chain: its source is history for the blocks behind it, and there is no LZ4HIP_CHAIN_STOPPED here.  Not serial: every
+  // block of every chain is parsed at once
+  static std::vector<int32_t> compressHCChain(const bytes& src, const std::vector<uint64_t>& chainSrcOff, const std::vector<int32_t>& srcLen,
+                                              const std::vector<uint32_t>& chainFirst, bytes& dest, const std::vector<uint64_t>& destOff,
+                                              const std::vector<int32_t>& maxDestLen, const std::vector<int32_t>& chainPrefixLen = {}, int level = 9) {
+    checkChains(src, chainSrcOff, srcLen, chainFirst, dest, destOff, maxDestLen, chainPrefixLen);
+    const size_t n = srcLen.size(), nc = chainSrcOff.size();
+    std::vector<int32_t> lengths(n, 0);
+    bytes one(1);                                 // (an empty buffer still hands the library a pointer)
+    int32_t none = 0;
+    uint64_t none64 = 0;
+    status(lz4hip_compress_hc_chain_batch(src.empty() ? one.data() : src.data(), nc ? chainSrcOff.data() : &none64,
+                                          chainPrefixLen.empty() ? nullptr : chainPrefixLen.data(), n ? srcLen.data() : &none, chainFirst.data(),
+                                          dest.empty() ? one.data() : dest.data(), n ? destOff.data() : &none64, n ? maxDestLen.data() : &none,
+                                          n ? lengths.data() : &none, (uint32_t)n, (uint32_t)nc, level));
+    return lengths;
+  }
+  // the argument checks of the two chain compressors
+  static void checkChains(const bytes& src, const std::vector<uint64_t>& chainSrcOff, const std::vector<int32_t>& srcLen,
+                          const std::vector<uint32_t>& chainFirst, const bytes& dest, const std::vector<uint64_t>& destOff,
+                          const std::vector<int32_t>& maxDestLen, const std::vector<int32_t>& chainPrefixLen) {
     const size_t n = srcLen.size(), nc = chainSrcOff.size();
     if (destOff.size() != n || maxDestLen.size() != n) throw std::invalid_argument("per-block arrays differ in length");
     if (chainFirst.size() != nc + 1 || (!chainPrefixLen.empty() && chainPrefixLen.size() != nc))
@@ -350,17 +388,6 @@ struct LZ4HIPBatch {
       if (maxDestLen[i] < 0) throw std::invalid_argument("lengths must be >= 0");
       if (destOff[i] > dest.size() || (uint64_t)maxDestLen[i] > dest.size() - destOff[i]) throw std::out_of_range("slot " + std::to_string(i));
     }
-    Chains r;
-    r.lengths.assign(n, 0);
-    r.chainLengths.assign(nc, 0);
-    bytes one(1);                                 // (an empty buffer still hands the library a pointer)
-    int32_t none = 0;
-    uint64_t none64 = 0;
-    status(lz4hip_compress_fast_chain_batch(src.empty() ? one.data() : src.data(), nc ? chainSrcOff.data() : &none64,
-                                            chainPrefixLen.empty() ? nullptr : chainPrefixLen.data(), n ? srcLen.data() : &none, chainFirst.data(),
-                                            dest.empty() ? one.data() : dest.data(), n ? destOff.data() : &none64, n ? maxDestLen.data() : &none,
-                                            n ? r.lengths.data() : &none, nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
-    return r;
   }
   static std::vector<int32_t> decompressedLengths(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen,
                                                   const std::vector<int32_t>& maxDestLen) {

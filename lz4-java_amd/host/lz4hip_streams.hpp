@@ -67,6 +67,15 @@ struct BatchEngine {
     chk(lz4hip_compress_fast_chain_batch(src, &srcOff, &prefix, sl.data(), first, dst, d_o.data(), dc.data(), out.data(), &consumed, (uint32_t)sl.size(), 1u));
     return out;
   }
+  // the same chain at an HC level (lz4hip_compress_hc_chain_batch): a block that does not fit gives 0 and the chain goes on
+  std::vector<int32_t> compressHCChain(const uint8_t* src, uint64_t srcOff, int32_t prefix, const std::vector<int32_t>& sl, uint8_t* dst,
+                                       const std::vector<uint64_t>& d_o, const std::vector<int32_t>& dc, int level) const {
+    std::vector<int32_t> out(sl.size());
+    if (sl.empty()) return out;
+    const uint32_t first[2] = {0u, (uint32_t)sl.size()};
+    chk(lz4hip_compress_hc_chain_batch(src, &srcOff, &prefix, sl.data(), first, dst, d_o.data(), dc.data(), out.data(), (uint32_t)sl.size(), 1u, level));
+    return out;
+  }
   std::vector<int32_t> decompressFast(const uint8_t* src, const std::vector<uint64_t>& so, const std::vector<int32_t>& scap, uint8_t* dst,
                                       const std::vector<uint64_t>& d_o, const std::vector<int32_t>& dl) const {
     std::vector<int32_t> out(so.size());
@@ -191,8 +200,9 @@ inline Compressed compressBlocks(const BatchEngine& e, const bytes& data, int bl
   for (int32_t s : c.sizes) if (s <= 0) throw LZ4Exception("maxDestLen is too small");  // LZ4JNICompressor.java:39-41
   return c;
 }
-// the same blocks as ONE chain of linked blocks behind `history` (at most the last 64 KB written of the frame)
-inline Compressed compressChain(const BatchEngine& e, const bytes& history, const bytes& data, int blockSize) {
+// the same blocks as ONE chain of linked blocks behind `history` (at most the last 64 KB written of the frame); hc: the HC chain at
+// `level` (LZ4_compress_HC_continue) instead of the fast chain
+inline Compressed compressChain(const BatchEngine& e, const bytes& history, const bytes& data, int blockSize, bool hc = false, int level = 0) {
   Compressed c;
   const size_t n = (data.size() + (size_t)blockSize - 1) / (size_t)blockSize;
   c.bound = maxCompressedLength(blockSize);
@@ -206,7 +216,8 @@ inline Compressed compressChain(const BatchEngine& e, const bytes& history, cons
   }
   bytes src(history);
   src.insert(src.end(), data.begin(), data.end());
-  c.sizes = e.compressFastChain(src.data(), history.size(), (int32_t)history.size(), c.lens, c.dst.data(), d_o, dc);
+  c.sizes = hc ? e.compressHCChain(src.data(), history.size(), (int32_t)history.size(), c.lens, c.dst.data(), d_o, dc, level)
+               : e.compressFastChain(src.data(), history.size(), (int32_t)history.size(), c.lens, c.dst.data(), d_o, dc);
   for (int32_t s : c.sizes) if (s <= 0) throw LZ4Exception("maxDestLen is too small");
   return c;
 }
@@ -256,6 +267,10 @@ class LZ4FrameOutputStream {
   // true) reads.  Every batch of blocks is ONE chain of linked blocks (LZ4_compress_fast_continue) whose prefix is the last 64 KB this
   // stream wrote of the frame before; a block that does not shrink is stored raw and still counts as history.  Assembled on the host.
   // One frame is one chain on one wavefront at a time: a FORMAT feature (smaller frames for small blocks), not a fast path.
+  // With a trailing `level` (the second constructor) every batch is one HC chain at that level (LZ4_compress_HC_continue in prefix mode,
+  // < 1 -> 9, > 12 -> 12) behind the last 64 KB written.  A block of an HC chain depends on the 64 KB in front of it and on nothing
+  // else: the frame's bytes do not depend on batchBlocks, and the blocks of a batch are parsed at the same time, a wavefront each --
+  // here a single stream does fill the device.
   LZ4FrameOutputStream(std::ostream& out, frame::BLOCKSIZE blockSize = frame::SIZE_4MB, int64_t knownSize = -1,
                        std::initializer_list<frame::Bits> bits = {frame::BLOCK_INDEPENDENCE}, BatchEngine engine = BatchEngine(),
                        size_t batchBlocks = 64, bool linkedBlocks = false)
@@ -271,6 +286,12 @@ class LZ4FrameOutputStream {
     if (flg_.isEnabled(frame::CONTENT_SIZE)) detail::putLE64(head, (uint64_t)knownSize_);
     head.push_back((uint8_t)((e_.xxh32_one(head.data() + 4, head.size() - 4, 0) >> 8) & 0xFF));
     out_.write((const char*)head.data(), (std::streamsize)head.size());
+  }
+  LZ4FrameOutputStream(std::ostream& out, frame::BLOCKSIZE blockSize, int64_t knownSize, std::initializer_list<frame::Bits> bits, BatchEngine engine,
+                       size_t batchBlocks, bool linkedBlocks, int level)
+      : LZ4FrameOutputStream(out, blockSize, knownSize, bits, engine, batchBlocks, requireLinked(linkedBlocks)) {
+    hc_ = true;
+    level_ = level;
   }
   ~LZ4FrameOutputStream() { try { close(); } catch (...) {} }
   void write(const uint8_t* p, size_t n) {
@@ -293,6 +314,10 @@ class LZ4FrameOutputStream {
 
  private:
   static int mask(std::initializer_list<frame::Bits> bits) { int m = 0; for (auto b : bits) m |= 1 << b; return m; }
+  static bool requireLinked(bool linkedBlocks) {   // (before anything is written)
+    if (!linkedBlocks) throw std::invalid_argument("level selects the linked-block compressor: it needs linkedBlocks = true");
+    return true;
+  }
   void writeBlocks(size_t nbytes) {  // writeBlock (:199-235) for every block of buf_[:nbytes] at once
     if (nbytes == 0) return;
     bytes data(buf_.begin(), buf_.begin() + (std::ptrdiff_t)nbytes);
@@ -304,7 +329,7 @@ class LZ4FrameOutputStream {
       out_.write((const char*)blocks.data(), (std::streamsize)blocks.size());
       return;
     }
-    const detail::Compressed c = linked_ ? detail::compressChain(e_, history_, data, maxBlockSize_) : detail::compressBlocks(e_, data, maxBlockSize_);
+    const detail::Compressed c = linked_ ? detail::compressChain(e_, history_, data, maxBlockSize_, hc_, level_) : detail::compressBlocks(e_, data, maxBlockSize_);
     if (linked_) {   // the last 64 KB written
       history_.insert(history_.end(), data.begin(), data.end());
       if (history_.size() > 65536) history_.erase(history_.begin(), history_.end() - 65536);
@@ -345,6 +370,8 @@ class LZ4FrameOutputStream {
   std::unique_ptr<xxhash::StreamingXXHash32> content_;  // LZ4FrameOutputStream.java:116
   bool finished_ = false;
   bool linked_ = false;   // linkedBlocks: no BLOCK_INDEPENDENCE, one chain per batch
+  bool hc_ = false;       // (linked_) the HC chain at level_ instead of the fast chain
+  int level_ = 0;
   bytes history_;         // (linked_) the last 64 KB written of the frame
 };
 

@@ -142,11 +142,41 @@ public final class LZ4HIPBatch {
    */
   public static void compressFastChain(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
       ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed) {
+    if (chainConsumed.length != chainSrcOff.length) {
+      throw new IllegalArgumentException("per-chain arrays differ in length");
+    }
+    checkChains(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen);
+    final int n = srcLen.length, nc = chainSrcOff.length;
+    final int rc = LZ4HIPJNI.LZ4HIP_batchFastChain(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, n, nc);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /**
+   * liblz4's {@code LZ4_compress_HC_continue} over chains of linked blocks (its prefix mode) at HC level {@code level} (&lt; 1: 9, &gt; 12: 12):
+   * the arrays of {@link #compressFastChain} without {@code chainConsumed}.  outLen[i] &gt; 0: the compressed size; 0: it did not fit --
+   * which does NOT end the chain: the block's source is history for the blocks behind it, and no block gets {@link #CHAIN_STOPPED}.  Not
+   * serial: every block of every chain is parsed at the same time.
+   */
+  public static void compressHCChain(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
+      ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, int level) {
+    checkChains(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen);
+    final int rc = LZ4HIPJNI.LZ4HIP_batchHCChain(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, srcLen.length,
+        chainSrcOff.length, level);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /** the argument checks of the two chain compressors */
+  private static void checkChains(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
+      ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen) {
     final int n = srcLen.length, nc = chainSrcOff.length;
     if (destOff.length != n || destCap.length != n || outLen.length != n) {
       throw new IllegalArgumentException("per-block arrays differ in length");
     }
-    if (chainFirst.length != nc + 1 || chainConsumed.length != nc || (chainPrefixLen != null && chainPrefixLen.length != nc)) {
+    if (chainFirst.length != nc + 1 || (chainPrefixLen != null && chainPrefixLen.length != nc)) {
       throw new IllegalArgumentException("per-chain arrays differ in length");
     }
     if (!src.isDirect() || !dest.isDirect()) {
@@ -188,10 +218,6 @@ public final class LZ4HIPBatch {
       if (destOff[i] < 0 || destOff[i] + destCap[i] > dest.capacity()) {
         throw new ArrayIndexOutOfBoundsException("slot " + i);
       }
-    }
-    final int rc = LZ4HIPJNI.LZ4HIP_batchFastChain(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, n, nc);
-    if (rc != 0) {
-      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
     }
   }
 

@@ -117,6 +117,11 @@ enum LZ4HIPJNI {
   static native int LZ4HIP_batchFastChain(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
                                           ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed,
                                           int nBlocks, int nChains);
+  /* LZ4_compress_HC_continue over chains of linked blocks (prefix mode) at HC level `level`, DIRECT buffers: the arrays of
+   * LZ4HIP_batchFastChain without chainConsumed.  outLen = liblz4's return values; a 0 does not end a chain.  Returns 0 or a negative
+   * lz4hip_status (a null required argument: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchHCChain(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
+                                        ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, int nBlocks, int nChains, int level);
   /* LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream against a dictionary handle: the compressed size, 0 (maxDestLen too
    * small) or a library failure as LZ4HIP_compress_fast; same NULL / pinning rules */
   static native int LZ4HIP_compress_fast_dict(long dict, byte[] srcArray, ByteBuffer srcBuffer, int srcOff, int srcLen,

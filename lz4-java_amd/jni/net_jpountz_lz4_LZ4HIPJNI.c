@@ -424,6 +424,24 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastChain(JNI
   return rc;
 }
 
+/* LZ4_compress_HC_continue over chains of linked blocks at an HC level, DIRECT buffers: chainPrefixLen may be null */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchHCChain(JNIEnv* env, jclass cls, jobject src, jlongArray chainSrcOff,
+    jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen,
+    jint nBlocks, jint nChains, jint level) {
+  (void)cls;
+  if (nBlocks < 0 || nChains < 0) return LZ4HIP_E_ARG;
+  batch_args_t b = {NULL, NULL, 6, {{chainSrcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {chainFirst, INTS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT},
+                                    {destCap, INTS, JNI_ABORT}, {outLen, INTS, 0}}};
+  if (chainPrefixLen != NULL) { b.a[b.n_arrays].arr = chainPrefixLen; b.a[b.n_arrays].is_long = INTS; b.a[b.n_arrays].mode = JNI_ABORT; b.a[b.n_arrays].p = NULL; b.n_arrays++; }
+  const int i_prefix = chainPrefixLen != NULL ? b.n_arrays - 1 : -1;
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  rc = lz4hip_compress_hc_chain_batch(b.src, b.a[0].p, i_prefix >= 0 ? (const int32_t*)b.a[i_prefix].p : NULL, b.a[1].p, (const uint32_t*)b.a[2].p, b.dst,
+                                      b.a[3].p, b.a[4].p, b.a[5].p, (uint32_t)nBlocks, (uint32_t)nChains, (int)level);
+  batch_release(env, &b);
+  return rc;
+}
+
 /* LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream, against a dictionary handle: the arguments, staging and return
  * convention of LZ4HIP_compress_fast behind the handle (0 handle: a library error, LZ4HIP_E_ARG) */
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1compress_1fast_1dict(JNIEnv* env, jclass cls, jlong dict, jbyteArray srcArray,

@@ -47,6 +47,7 @@ class HIPEngine:
     decompressSafe = staticmethod(LZ4HIPBatch.decompressSafe)
     decompressSafeChain = staticmethod(LZ4HIPBatch.decompressSafeChain)   # linked blocks: LZ4FrameInputStream(linkedBlocks=True)
     compressFastChain = staticmethod(LZ4HIPBatch.compressFastChain)       # linked blocks: LZ4FrameOutputStream(linkedBlocks=True)
+    compressHCChain = staticmethod(LZ4HIPBatch.compressHCChain)           # linked blocks at an HC level: LZ4FrameOutputStream(linkedBlocks=True, level=N)
     decompressFast = staticmethod(LZ4HIPBatch.decompressFast)
     xxh32 = staticmethod(LZ4HIPBatch.xxh32)
 
@@ -85,14 +86,18 @@ def _compress_batch(engine, data, blockSize):
     return dst, bound, lens, sizes
 
 
-def _compress_chain(engine, history, data, blockSize):
-    """compress data[i*blockSize : +blockSize] for all i as ONE chain of linked blocks behind `history` -> as _compress_batch"""
+def _compress_chain(engine, history, data, blockSize, level=None):
+    """compress data[i*blockSize : +blockSize] for all i as ONE chain of linked blocks behind `history` -> as _compress_batch; level
+    None: the fast chain (LZ4_compress_fast_continue), else the HC chain at that level (LZ4_compress_HC_continue)"""
     n = (len(data) + blockSize - 1) // blockSize
     bound = maxCompressedLength(blockSize)
     dst = bytearray(n * bound)
     lens = [min(blockSize, len(data) - i * blockSize) for i in range(n)]
     P = len(history)
-    sizes, _ = engine.compressFastChain(history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P])
+    if level is None:
+        sizes, _ = engine.compressFastChain(history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P])
+    else:
+        sizes = engine.compressHCChain(history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P], level)
     for s in sizes:
         if s <= 0:
             raise LZ4Exception("maxDestLen is too small")
@@ -201,18 +206,26 @@ class LZ4FrameOutputStream(io.RawIOBase):
     the frame is written WITHOUT the block-independence flag -- what the `lz4` command line writes by default, and what
     LZ4FrameInputStream(linkedBlocks=True) reads.  Every batch of blocks is ONE chain of linked blocks (engine.compressFastChain:
     LZ4_compress_fast_continue) whose prefix is the last 64 KB this stream wrote of the frame before; a block that does not shrink is
-    stored raw and still counts as history for the blocks behind it.  The frame is assembled on the host.  One frame is one chain on
-    one wavefront at a time: this is a FORMAT feature (smaller frames for small blocks), not a fast path -- throughput comes from
-    many chains per launch (LZ4HIPBatch.compressFastChain), not from one stream."""
+    stored raw and still counts as history for the blocks behind it.  The frame is assembled on the host.  With level=None (the
+    default) one frame is one chain on one wavefront at a time: a FORMAT feature (smaller frames for small blocks), not a fast path --
+    throughput comes from many chains per launch (LZ4HIPBatch.compressFastChain), not from one stream.
 
-    def __init__(self, out, blockSize=BLOCKSIZE.SIZE_4MB, knownSize=-1, *bits, engine=None, batchBlocks=64, linkedBlocks=False):
+    linkedBlocks=True, level=N: every batch is one HC chain at level N (engine.compressHCChain: LZ4_compress_HC_continue in prefix
+    mode, what `lz4 -3` and above write as blocks) behind the last 64 KB written.  A block of an HC chain depends on the 64 KB in
+    front of it and on nothing else, so THE FRAME'S BYTES DO NOT DEPEND ON batchBlocks, and the blocks of a batch are parsed at the
+    same time, a wavefront each: here a single stream does fill the device, the more blocks a batch holds the better."""
+
+    def __init__(self, out, blockSize=BLOCKSIZE.SIZE_4MB, knownSize=-1, *bits, engine=None, batchBlocks=64, linkedBlocks=False, level=None):
         super().__init__()
         self.out = out
         self.engine = engine or HIPEngine()
         self.linkedBlocks = linkedBlocks
+        self.level = level   # (linkedBlocks) None: the fast chain; else the HC chain's level
         self.history = b""   # (linkedBlocks) the last 64 KB written of the frame
+        if level is not None and not linkedBlocks:
+            raise ValueError("level selects the linked-block compressor: it needs linkedBlocks=True (independent HC blocks: HIPEngine(hcLevel))")
         if linkedBlocks:
-            if not hasattr(self.engine, "compressFastChain"):
+            if not hasattr(self.engine, "compressFastChain" if level is None else "compressHCChain"):
                 raise ValueError("the engine cannot compress linked blocks")
             m = 0
             for b in bits:
@@ -272,7 +285,7 @@ class LZ4FrameOutputStream(io.RawIOBase):
             self.content.update(data, 0, len(data))  # :211-213: the content checksum streams over the uncompressed bytes
         block_checksum = self.flg.isEnabled(FLG.Bits.BLOCK_CHECKSUM)
         if self.linkedBlocks:                          # one chain behind the last 64 KB written; assembled on the host
-            dst, bound, lens, sizes = _compress_chain(self.engine, self.history, data, self.maxBlockSize)
+            dst, bound, lens, sizes = _compress_chain(self.engine, self.history, data, self.maxBlockSize, self.level)
             self.history = (self.history + data)[-65536:]
         elif hasattr(self.engine, "containerBlocks"):   # assembled on the device
             self.out.write(self.engine.containerBlocks(LZ4HIPBatch.FRAME_BLOCKS, data, self.maxBlockSize, block_checksum))
