@@ -287,106 +287,85 @@ int launch_compress_fast_v2w(const BatchArgs& a, uint32_t* q, uint32_t* routed, 
   return (int)hipGetLastError();
 }
 
-
-// window-parallel core (lz4_fast_ms_core.h): every sequence of a 64-position window per step
-__device__ __forceinline__ void compress_fast_ms_block(const BatchArgs& a, uint32_t b, uint64_t* table) {
-  const int32_t n = uniform_i32(a.src_len[b]);
-  const int32_t cap = uniform_i32(a.dst_cap[b]);
-  uint32_t r = 0;
-  if (n >= 0 && (uint32_t)n <= 0x7E000000u && cap >= 0) {
-    const uint8_t* s = uniform_ptr(a.src + a.src_off[b]);
-    uint8_t* d = uniform_ptr(a.dst + a.dst_off[b]);
-    WaveDev w(table);
-    DirectOut<WaveDev> out(w, s, (uint32_t)n, d, (uint32_t)cap);
-    if (n < 65547) {
-      FastCoreMS<WaveDev, true> c(w, out, s, (uint32_t)n);
-      r = c.run();
-    } else {
-      FastCoreMS<WaveDev, false> c(w, out, s, (uint32_t)n);
-      r = c.run();
-    }
+// The one-wavefront-per-block kernels (ms, accel, dict, dest; chain draws chains): WAVES_PER_CU wavefronts per workgroup, a 32 KB table
+// each, units drawn from a queue word.  A kernel is its name, its arguments, the draw loop and the FastForm it names: the block shell
+// is lz4_fast_core.h's fast_block_run, which the CPU lane simulator runs as well; BlockIoDev is the device's side of it (per-block
+// values back in scalar registers, kernels_internal.h uniform_*; lane 0 stores the results) and launch_queue_kernel the launch.
+// (The draw loop is written out in every kernel: behind a function that takes the body as a callable the cores are optimised once
+// more on their way into the kernel, and three of four kernels come out with other instructions.)
+struct BlockIoDev {
+  const BatchArgs& a;
+  int32_t* consumed = nullptr;   // FILL forms only
+  __device__ __forceinline__ static int32_t i32(int32_t v) { return uniform_i32(v); }
+  template <class T> __device__ __forceinline__ static T* ptr(T* p) { return uniform_ptr(p); }
+  __device__ __forceinline__ void begin_block(WaveDev&, const uint8_t*, uint32_t, uint8_t*, uint32_t) const {}
+  __device__ __forceinline__ void put(uint32_t b, uint32_t r) const { if (__lane_id() == 0) a.out[b] = (int32_t)r; }
+  __device__ __forceinline__ void put(uint32_t b, uint32_t r, int32_t c) const { if (__lane_id() == 0) { a.out[b] = (int32_t)r; consumed[b] = c; } }
+};
+// q_words: the queue words at q to zero in front of the launch (0: an earlier launch of the same pass has)
+template <class... P, class... A>
+static int launch_queue_kernel(void (*kernel)(P...), uint32_t units, uint32_t* q, uint32_t q_words, uint32_t n_cus, void* stream, A... args) {
+  if (q_words) {
+    hipError_t e = hipMemsetAsync(q, 0, q_words * sizeof(uint32_t), (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
   }
-  if (__lane_id() == 0) a.out[b] = (int32_t)r;
+  const uint32_t wgs = (units + WAVES_PER_CU - 1u) / WAVES_PER_CU;
+  hipLaunchKernelGGL(kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, args...);
+  return (int)hipGetLastError();
 }
-// CU-filling form (see the residency note above): WAVES_PER_CU wavefronts per workgroup drawing from q[2] either the blocks
+
+// window-parallel core (lz4_fast_ms_core.h): every sequence of a 64-position window per step.  Draws from q[2] either the blocks
 // listed in routed[0 .. q[1]) (second pass of the adaptive scheme; an empty list costs one queue draw per wavefront) or, with
 // routed == nullptr, every block of the batch
 __global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_ms_cu_kernel(BatchArgs a, uint32_t* q, const uint32_t* routed) {
   __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
-  uint64_t* table = tables[threadIdx.x >> 6];
+  WaveDev w(tables[threadIdx.x >> 6]);
+  BlockIoDev io{a};
   const uint32_t count = routed ? __builtin_amdgcn_readfirstlane(q[1]) : a.n;
   for (;;) {
     uint32_t i = 0;
     if (__lane_id() == 0) i = atomicAdd(q + 2, 1u);
     i = __builtin_amdgcn_readfirstlane(i);
     if (i >= count) return;
-    const uint32_t b = routed ? __builtin_amdgcn_readfirstlane(routed[i]) : i;
-    compress_fast_ms_block(a, b, table);
+    FastBlockArgs x;
+    fast_block_run<FastFormMS<WaveDev>>(w, io, a, routed ? __builtin_amdgcn_readfirstlane(routed[i]) : i, x);
     WaveDev::sync();  // the table is reused
   }
 }
 // `first` = this is the first launch that uses q (zero it)
 int launch_compress_fast_ms(const BatchArgs& a, uint32_t* q, const uint32_t* routed, bool first, uint32_t n_cus, void* stream) {
   if (a.n == 0) return 0;
-  if (first) {
-    hipError_t e = hipMemsetAsync(q, 0, 3 * sizeof(uint32_t), (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-  }
-  const uint32_t wgs = (a.n + WAVES_PER_CU - 1u) / WAVES_PER_CU;
-  hipLaunchKernelGGL(compress_fast_ms_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a, q, routed);
-  return (int)hipGetLastError();
+  return launch_queue_kernel(compress_fast_ms_cu_kernel, a.n, q, first ? 3u : 0u, n_cus, stream, a, q, routed);
 }
 
-// LZ4_compress_fast with acceleration 2 .. 65537: the one-sequence-per-step core with its ACC switch on (lz4_fast_core.h), byU16 below
-// 65547 bytes, byU32 (64-bit entries) above.  Same shape as the window-parallel kernel: WAVES_PER_CU wavefronts per workgroup, one
-// 32 KB table each, blocks drawn from the queue word q[0].
-__device__ __forceinline__ void compress_fast_accel_block(const BatchArgs& a, uint32_t b, uint64_t* table, uint32_t accel) {
-  const int32_t n = uniform_i32(a.src_len[b]);
-  const int32_t cap = uniform_i32(a.dst_cap[b]);
-  uint32_t r = 0;
-  if (n >= 0 && (uint32_t)n <= 0x7E000000u && cap >= 0) {
-    const uint8_t* s = uniform_ptr(a.src + a.src_off[b]);
-    uint8_t* d = uniform_ptr(a.dst + a.dst_off[b]);
-    WaveDev w(table);
-    DirectOut<WaveDev> out(w, s, (uint32_t)n, d, (uint32_t)cap);
-    if (n < 65547) {
-      FastCore<WaveDev, true, DirectOut<WaveDev>, false, true> c(w, out, s, (uint32_t)n);
-      c.accel = accel;
-      r = c.run();
-    } else {
-      FastCore<WaveDev, false, DirectOut<WaveDev>, false, true> c(w, out, s, (uint32_t)n);
-      c.accel = accel;
-      r = c.run();
-    }
-  }
-  if (__lane_id() == 0) a.out[b] = (int32_t)r;
-}
+// LZ4_compress_fast with acceleration 2 .. 65537: the one-sequence-per-step core with its ACC switch on, blocks drawn from q[0]
 __global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_accel_cu_kernel(BatchArgs a, uint32_t* q, uint32_t accel) {
   __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
-  uint64_t* table = tables[threadIdx.x >> 6];
+  WaveDev w(tables[threadIdx.x >> 6]);
+  BlockIoDev io{a};
   for (;;) {
     uint32_t b = 0;
     if (__lane_id() == 0) b = atomicAdd(q, 1u);
     b = __builtin_amdgcn_readfirstlane(b);
     if (b >= a.n) return;
-    compress_fast_accel_block(a, b, table, accel);
+    FastBlockArgs x;
+    x.accel = accel;
+    fast_block_run<FastForm<WaveDev, false, true>>(w, io, a, b, x);
     WaveDev::sync();  // the table is reused
   }
 }
 int launch_compress_fast_accel(const BatchArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream) {
   if (a.n == 0) return 0;
   if (accel < 2u || accel > 65537u) return (int)hipErrorInvalidValue;   // (the caller clamps; 1 is the plain compressor's)
-  hipError_t e = hipMemsetAsync(q, 0, sizeof(uint32_t), (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  const uint32_t wgs = (a.n + WAVES_PER_CU - 1u) / WAVES_PER_CU;
-  hipLaunchKernelGGL(compress_fast_accel_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a, q, accel);
-  return (int)hipGetLastError();
+  return launch_queue_kernel(compress_fast_accel_cu_kernel, a.n, q, 1u, n_cus, stream, a, q, accel);
 }
 
-// LZ4_loadDict + LZ4_compress_fast_continue, a fresh stream per block: the one-sequence-per-step core with its DICT switch on
-// (lz4_fast_core.h) -- byU32 and 64-bit entries at every size, as liblz4's external-dictionary mode.  Same shape as the accelerated
-// kernel.  Per block the table is loaded from the dictionary's 32 KB image (dict_image_kernel, once per handle and device; L2-resident
-// while a batch runs) instead of being cleared; keep == 0 (no dictionary) clears it.
+// LZ4_loadDict + LZ4_compress_fast_continue, a fresh stream per block: the DICT switch -- byU32 and 64-bit entries at every size, as
+// liblz4's external-dictionary mode.  Per block the table is loaded from the dictionary's 32 KB image (dict_image_kernel, once per handle
+// and device; L2-resident while a batch runs) instead of being cleared; keep == 0 (no dictionary) clears it.
+// (This kernel keeps a block shell of its own: through fast_block_run -- FastForm<WaveDev, false, false, true>, the form the lane
+// simulator runs -- it computes the same but comes out with other instructions: values that depend on `keep` alone are hoisted out
+// of the draw loop.  Any change to the shell in lz4_fast_core.h is to be made here as well.)
 __device__ __forceinline__ void compress_fast_dict_block(const BatchArgs& a, uint32_t b, uint64_t* table, const uint8_t* tail, uint32_t keep,
                                                          const uint8_t* image) {
   const int32_t n = uniform_i32(a.src_len[b]);
@@ -420,12 +399,8 @@ int launch_compress_fast_dict(const BatchArgs& a, const uint8_t* dict_end, int32
                               void* stream) {
   if (a.n == 0) return 0;
   if (keep != 0 && (keep < 8 || keep > 65536 || !dict_end || !image)) return (int)hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(q, 0, sizeof(uint32_t), (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  const uint32_t wgs = (a.n + WAVES_PER_CU - 1u) / WAVES_PER_CU;
-  hipLaunchKernelGGL(compress_fast_dict_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a,
-                     keep ? dict_end - keep : (const uint8_t*)nullptr, (uint32_t)keep, (const uint8_t*)image, q);
-  return (int)hipGetLastError();
+  return launch_queue_kernel(compress_fast_dict_cu_kernel, a.n, q, 1u, n_cus, stream, a, keep ? dict_end - keep : (const uint8_t*)nullptr,
+                             (uint32_t)keep, (const uint8_t*)image, q);
 }
 // the dictionary's table image: one wavefront, once per handle and device
 __global__ __launch_bounds__(64) void dict_image_kernel(const uint8_t* tail, uint32_t keep, uint8_t* image) {
@@ -439,11 +414,10 @@ int launch_dict_image(const uint8_t* tail, int32_t keep, void* image, void* stre
   return (int)hipGetLastError();
 }
 
-// LZ4_compress_fast_continue over chains of linked blocks: the one-sequence-per-step core with its LINK switch on (lz4_fast_core.h), the
-// walk of lz4_fast_chain.h.  Same shape as the dictionary kernel, with a CHAIN as the unit of work: a wavefront draws a chain, builds the
-// chain's table in its 32 KB of LDS -- cleared, or LZ4_loadDict's inserts over the kept prefix (dict_table_build, no image in memory)
-// -- and walks the chain's blocks in order with the table left as the previous block left it.  One chain is serial; nothing here waits
-// for another wavefront.
+// LZ4_compress_fast_continue over chains of linked blocks: the LINK switch and the walk of lz4_fast_chain.h, with a CHAIN as the unit of
+// work: a wavefront draws a chain, builds the chain's table in its 32 KB of LDS -- cleared, or LZ4_loadDict's inserts over the kept prefix
+// (dict_table_build, no image in memory) -- and walks the chain's blocks in order with the table left as the previous block left it.
+// One chain is serial; nothing here waits for another wavefront.
 struct CChainIoDev {
   const CChainArgs& a;
   __device__ __forceinline__ static uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane(v); }
@@ -462,7 +436,6 @@ __global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_chain_cu_kern
   WaveDev w(tables[threadIdx.x >> 6]);
   CChainIoDev io{a};
   for (;;) {
-    // (the draw in the shape of the other queue kernels here: lane 0 adds, all 64 lanes reach the readfirstlane)
     uint32_t c = 0;
     if (__lane_id() == 0) c = atomicAdd(q, 1u);
     c = __builtin_amdgcn_readfirstlane(c);
@@ -474,56 +447,28 @@ __global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_chain_cu_kern
 int launch_compress_fast_chain(const CChainArgs& a, uint32_t* q, uint32_t n_cus, void* stream) {
   if (a.n_chains == 0) return 0;
   if (!q) return (int)hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(q, 0, sizeof(uint32_t), (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  const uint32_t wgs = (a.n_chains + WAVES_PER_CU - 1u) / WAVES_PER_CU;
-  hipLaunchKernelGGL(compress_fast_chain_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a, q);
-  return (int)hipGetLastError();
+  return launch_queue_kernel(compress_fast_chain_cu_kernel, a.n_chains, q, 1u, n_cus, stream, a, q);
 }
 
-// LZ4_compress_destSize: the one-sequence-per-step core (acceleration 1) with DirectOut's FILL switch on (lz4_fast_core.h), byU16 below
-// 65547 bytes, byU32 above; dst_cap[b] is the target.  Same shape as the accelerated kernel.  A block whose target is full stops at the
-// next step, so the steps spent on it follow the input it consumes, not src_len.
-__device__ __forceinline__ void compress_fast_dest_block(const BatchArgs& a, int32_t* consumed, uint32_t b, uint64_t* table) {
-  const int32_t n = uniform_i32(a.src_len[b]);
-  const int32_t t = uniform_i32(a.dst_cap[b]);
-  uint32_t r = 0;
-  int32_t c = n;   // (liblz4 leaves *srcSizePtr untouched where it returns 0 up front)
-  if (t > 0 && n >= 0 && (uint32_t)n <= 0x7E000000u) {
-    const uint8_t* s = uniform_ptr(a.src + a.src_off[b]);
-    uint8_t* d = uniform_ptr(a.dst + a.dst_off[b]);
-    WaveDev w(table);
-    DirectOut<WaveDev, true> out(w, s, (uint32_t)n, d, (uint32_t)t);
-    if (n < 65547) {
-      FastCore<WaveDev, true, DirectOut<WaveDev, true>> core(w, out, s, (uint32_t)n);
-      r = core.run();
-    } else {
-      FastCore<WaveDev, false, DirectOut<WaveDev, true>> core(w, out, s, (uint32_t)n);
-      r = core.run();
-    }
-    c = (int32_t)out.consumed;
-  }
-  if (__lane_id() == 0) { a.out[b] = (int32_t)r; consumed[b] = c; }
-}
+// LZ4_compress_destSize: the one-sequence-per-step core (acceleration 1) with DirectOut's FILL switch on; dst_cap[b] is the target.  A
+// block whose target is full stops at the next step, so the steps spent on it follow the input it consumes, not src_len.
 __global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_dest_cu_kernel(BatchArgs a, int32_t* consumed, uint32_t* q) {
   __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
-  uint64_t* table = tables[threadIdx.x >> 6];
+  WaveDev w(tables[threadIdx.x >> 6]);
+  BlockIoDev io{a, consumed};
   for (;;) {
     uint32_t b = 0;
     if (__lane_id() == 0) b = atomicAdd(q, 1u);
     b = __builtin_amdgcn_readfirstlane(b);
     if (b >= a.n) return;
-    compress_fast_dest_block(a, consumed, b, table);
+    FastBlockArgs x;
+    fast_block_run<FastForm<WaveDev, true>>(w, io, a, b, x);
     WaveDev::sync();  // the table is reused
   }
 }
 int launch_compress_dest_size(const BatchArgs& a, int32_t* consumed, uint32_t* q, uint32_t n_cus, void* stream) {
   if (a.n == 0) return 0;
-  hipError_t e = hipMemsetAsync(q, 0, sizeof(uint32_t), (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  const uint32_t wgs = (a.n + WAVES_PER_CU - 1u) / WAVES_PER_CU;
-  hipLaunchKernelGGL(compress_fast_dest_cu_kernel, dim3(wgs < n_cus ? wgs : n_cus), dim3(64 * WAVES_PER_CU), 0, (hipStream_t)stream, a, consumed, q);
-  return (int)hipGetLastError();
+  return launch_queue_kernel(compress_fast_dest_cu_kernel, a.n, q, 1u, n_cus, stream, a, consumed, q);
 }
 
 #if LZ4HIP_V2_ASM_PROF

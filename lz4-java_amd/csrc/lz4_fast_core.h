@@ -40,6 +40,7 @@
 #define LZ4HIP_FP_MASK ((1u << LZ4HIP_FP_BITS) - 1u)
 #include <stdint.h>
 #include <stddef.h>
+#include "kernels.h"   // BatchArgs
 
 #ifndef LZ4HIP_DEV
 #if defined(__HIPCC__)
@@ -277,6 +278,12 @@ constexpr uint32_t SEQ_NOCHECK = 1u << 29, SEQ_LIT_MASK = (1u << 29) - 1u;
 // reads the tail or the source, whichever the index names: the buffer (cs, cn) is chosen per hit (locate).  A dictionary match that
 // runs to the dictionary's end goes on against the block's own start.  Nothing outside the tail and [src, src + n) is read.
 // DICT = false compiles to what it did before the switch existed.
+// a form's own state: what the block shell (end of this file) gives a core before run(), and reads after it
+struct FastBlockArgs {
+  uint32_t accel = 1;                                                                // ACC: 2 .. 65537
+  const uint8_t* dict = nullptr; uint32_t keep = 0; const uint8_t* image = nullptr;  // DICT: FastCore's fields; keep == 0: no dictionary
+  uint32_t dense64 = 0; bool bailed = false; FastStats* st = nullptr;                // SIM: the density probe and what it did; counters
+};
 // (the DICT core's extra state lives in a base of its own, so that every other core is the struct it was)
 template <bool DICT> struct DictState {
   // never read: the names exist so that the `if constexpr (DICT)` branches parse
@@ -349,6 +356,13 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
       : w(w_), out(out_), src(s), n(n_), st(st_) {
     mfl1 = n - 11u;
     matchlimit = n - 5u;
+  }
+  template <bool SIM> LZ4HIP_DEV void setup(const FastBlockArgs& x) {   // (SIM: see FastForm)
+    if constexpr (ACC) accel = x.accel;
+    if constexpr (DICT) {
+      if (x.keep) { dict = x.dict; keep = x.keep; image = x.image; }
+    }
+    if constexpr (SIM) dense64 = x.dense64;
   }
 
   // ---- table entry helpers ---------------------------------------------------------------
@@ -800,5 +814,56 @@ LZ4HIP_DEV void dict_image_build(W& w, const uint8_t* tail, uint32_t keep, uint8
 }
 template <class W>
 LZ4HIP_DEV void dict_table_build(W& w, const uint8_t* tail, uint32_t keep) { dict_image_build<W, false>(w, tail, keep, nullptr); }
+
+// ---------------------------------------------------------------------------------------------------
+// The block shell: everything around a core's run() for ONE block, stated once for the kernels (compress_fast.hip) and the CPU lane
+// simulator (tests/hostsim/block_host.h): liblz4's up-front returns, the output policy, the table layout by size (byU16 below 65547
+// bytes, byU32 from there on; DICT: byU32 at every size), the form's state, run(), the results.  A new operation adds a switch to the
+// core and a kernel that names its form; it does not restate this.
+//   Form  FastForm<W, FILL, ACC, DICT> here, FastFormMS<W> in lz4_fast_ms_core.h.  SIM: the simulator's extras -- counters, the
+//         density probe -- which the shell must not see as run-time values: a kernel's code would come out differently.
+//   a, b  the batch and the block in it (dst_cap[b] is the target of a FILL form); the simulator makes a batch of one.
+//   Io    i32(v) / ptr(p): a wave-uniform value back in scalar registers (identity on the host); begin_block(w, s, n, d, cap): the
+//         block may read [s, s + n) and write [d, d + cap) (the simulator's bounds; nothing on the device); put(b, r) /
+//         put(b, r, consumed): the results.  A FILL form's up-front 0 leaves consumed at src_len, as liblz4 leaves *srcSizePtr.
+// ---------------------------------------------------------------------------------------------------
+template <class W, bool FILL = false, bool ACC = false, bool DICT = false, bool SIM = false>
+struct FastForm {
+  using Out = DirectOut<W, FILL>;
+  template <bool U16> using Core = FastCore<W, U16, Out, false, ACC, DICT>;
+  static constexpr bool kFill = FILL, kDict = DICT, kSim = SIM;
+};
+template <class Form, class W, class Io>
+LZ4HIP_DEV void fast_block_run(W& w, Io& io, const BatchArgs& a, uint32_t b, FastBlockArgs& x) {
+  const int32_t n = io.i32(a.src_len[b]);
+  const int32_t cap = io.i32(a.dst_cap[b]);
+  uint32_t r = 0;
+  int32_t used = n;
+  if ((!Form::kFill || cap > 0) && n >= 0 && (uint32_t)n <= 0x7E000000u && (Form::kFill || cap >= 0)) {
+    const uint8_t* s = io.ptr(a.src + a.src_off[b]);
+    uint8_t* d = io.ptr(a.dst + a.dst_off[b]);
+    io.begin_block(w, s, (uint32_t)n, d, (uint32_t)cap);
+    typename Form::Out out(w, s, (uint32_t)n, d, (uint32_t)cap);
+    if constexpr (Form::kDict) {
+      typename Form::template Core<false> c(w, out, s, (uint32_t)n, Form::kSim ? x.st : nullptr);
+      c.template setup<Form::kSim>(x);
+      r = c.run();
+      if constexpr (Form::kSim) x.bailed = c.bailed;
+    } else if (n < 65547) {
+      typename Form::template Core<true> c(w, out, s, (uint32_t)n, Form::kSim ? x.st : nullptr);
+      c.template setup<Form::kSim>(x);
+      r = c.run();
+      if constexpr (Form::kSim) x.bailed = c.bailed;
+    } else {
+      typename Form::template Core<false> c(w, out, s, (uint32_t)n, Form::kSim ? x.st : nullptr);
+      c.template setup<Form::kSim>(x);
+      r = c.run();
+      if constexpr (Form::kSim) x.bailed = c.bailed;
+    }
+    if constexpr (Form::kFill) used = (int32_t)out.consumed;
+  }
+  if constexpr (Form::kFill) io.put(b, r, used);
+  else io.put(b, r);
+}
 
 }  // namespace lz4hip

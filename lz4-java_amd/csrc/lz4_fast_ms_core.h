@@ -395,4 +395,12 @@ struct FastCoreMS : FastCore<W, U16, DirectOut<W>> {
   }
 };
 
+// the window-parallel core as a form of the block shell (lz4_fast_core.h fast_block_run)
+template <class W, bool SIM = false>
+struct FastFormMS {
+  using Out = DirectOut<W>;
+  template <bool U16> using Core = FastCoreMS<W, U16>;
+  static constexpr bool kFill = false, kDict = false, kSim = SIM;
+};
+
 }  // namespace lz4hip

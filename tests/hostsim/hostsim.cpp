@@ -8,6 +8,7 @@
 #include "../../lz4-java_amd/csrc/lz4_fast_ms_core.h"
 #include "../../lz4-java_amd/csrc/lz4_fast_v2_core.h"
 #include "wave_host.h"
+#include "block_host.h"
 #include "../../lz4-java_amd/csrc/lz4_decode_core.h"
 #include "group_host.h"
 #include "../../lz4-java_amd/csrc/lz4_hc_core.h"
@@ -51,41 +52,23 @@ std::atomic<int> MailHost::oob{0};
 
 extern "C" {
 
+// The one-block entries below run the block shell the kernels run (lz4_fast_core.h fast_block_run, block_host.h).
 // returns compressed size (0 = does not fit), or -1000 if the simulated wave touched memory
 // outside [src, src+n) / [dst, dst+cap)
 int sim_compress_fast(const uint8_t* src, int n, uint8_t* dst, int cap, uint64_t* stats4, uint64_t rng_seed) {
-  if (n < 0 || (uint32_t)n > 0x7E000000u || cap < 0) return 0;
   hostsim::WaveHost w;
-  if (rng_seed) w.rng = rng_seed;
-  w.bounds(src, (size_t)n, dst, (size_t)cap);
-  lz4hip::FastStats st = {0, 0, 0, 0};
-  uint32_t r;
-  lz4hip::DirectOut<hostsim::WaveHost> out(w, src, (uint32_t)n, dst, (uint32_t)cap);
-  if (n < 65547) {
-    lz4hip::FastCore<hostsim::WaveHost, true> c(w, out, src, (uint32_t)n, &st);
-    r = c.run();
-  } else {
-    lz4hip::FastCore<hostsim::WaveHost, false> c(w, out, src, (uint32_t)n, &st);
-    r = c.run();
-  }
-  if (stats4) { stats4[0] = st.steps; stats4[1] = st.slow_steps; stats4[2] = st.false_pos; stats4[3] = st.sequences; }
-  if (w.oob) return -1000;
-  return (int)r;
+  hostsim::BlockHost io(src, n, dst, cap);
+  return hostsim::sim_fast_block<lz4hip::FastForm<hostsim::WaveHost, false, false, false, true>>(w, io, stats4, rng_seed);
 }
 
 // one-sequence-per-step core with the density probe of the adaptive scheme: -2 = the core left the block to the
 // window-parallel core (sequences 32..95 cover fewer than dense64 bytes)
 int sim_compress_fast_probe(const uint8_t* src, int n, uint8_t* dst, int cap, uint32_t dense64) {
-  if (n < 0 || (uint32_t)n > 0x7E000000u || cap < 0) return 0;
   hostsim::WaveHost w;
-  w.bounds(src, (size_t)n, dst, (size_t)cap);
-  lz4hip::DirectOut<hostsim::WaveHost> out(w, src, (uint32_t)n, dst, (uint32_t)cap);
-  uint32_t r;
-  bool bailed;
-  if (n < 65547) { lz4hip::FastCore<hostsim::WaveHost, true> c(w, out, src, (uint32_t)n); c.dense64 = dense64; r = c.run(); bailed = c.bailed; }
-  else { lz4hip::FastCore<hostsim::WaveHost, false> c(w, out, src, (uint32_t)n); c.dense64 = dense64; r = c.run(); bailed = c.bailed; }
-  if (w.oob) return -1000;
-  return bailed ? -2 : (int)r;
+  hostsim::BlockHost io(src, n, dst, cap);
+  io.x.dense64 = dense64;
+  const int r = hostsim::sim_fast_block<lz4hip::FastForm<hostsim::WaveHost, false, false, false, true>>(w, io, nullptr, 0);
+  return r != -1000 && io.x.bailed ? -2 : r;
 }
 
 // lean core + parked/batched emission (lz4_fast_v2_core.h); blocks >= 65547 bytes: the generic loop over the same output policy
@@ -163,23 +146,9 @@ int sim_compress_fast_v2_probe(const uint8_t* src, int n, uint8_t* dst, int cap,
 
 // window-parallel core (lz4_fast_ms_core.h): every sequence of a 64-position window per step
 int sim_compress_fast_ms(const uint8_t* src, int n, uint8_t* dst, int cap, uint64_t* stats4, uint64_t rng_seed) {
-  if (n < 0 || (uint32_t)n > 0x7E000000u || cap < 0) return 0;
   hostsim::WaveHost w;
-  if (rng_seed) w.rng = rng_seed;
-  w.bounds(src, (size_t)n, dst, (size_t)cap);
-  lz4hip::FastStats st = {0, 0, 0, 0};
-  uint32_t r;
-  lz4hip::DirectOut<hostsim::WaveHost> out(w, src, (uint32_t)n, dst, (uint32_t)cap);
-  if (n < 65547) {
-    lz4hip::FastCoreMS<hostsim::WaveHost, true> c(w, out, src, (uint32_t)n, &st);
-    r = c.run();
-  } else {
-    lz4hip::FastCoreMS<hostsim::WaveHost, false> c(w, out, src, (uint32_t)n, &st);
-    r = c.run();
-  }
-  if (stats4) { stats4[0] = st.steps; stats4[1] = st.slow_steps; stats4[2] = st.false_pos; stats4[3] = st.sequences; }
-  if (w.oob) return -1000;
-  return (int)r;
+  hostsim::BlockHost io(src, n, dst, cap);
+  return hostsim::sim_fast_block<lz4hip::FastFormMS<hostsim::WaveHost, true>>(w, io, stats4, rng_seed);
 }
 
 void sim_ring_stats(unsigned long long* out3) { out3[0] = hostsim::GroupHost::ring_trips; out3[1] = hostsim::GroupHost::ring_entries; out3[2] = hostsim::GroupHost::ring_repl; }

@@ -5,31 +5,17 @@
 #include <stdint.h>
 #include "../../lz4-java_amd/csrc/lz4_fast_core.h"
 #include "wave_host.h"
+#include "block_host.h"
 
 extern "C" {
 
-// returns compressed size (0 = does not fit), or -1000 if the simulated wave touched memory outside [src, src+n) / [dst, dst+cap).
+// the block shell compress_fast_accel_cu_kernel runs (fast_block_run): returns compressed size (0 = does not fit), or -1000 if the simulated wave touched memory outside [src, src+n) / [dst, dst+cap).
 // `accel` is used as given (the library clamps it to 2 .. 65537 before the kernel sees it; 1 is the plain core)
 int sim_compress_fast_accel(const uint8_t* src, int n, uint8_t* dst, int cap, uint32_t accel, uint64_t* stats4, uint64_t rng_seed) {
-  if (n < 0 || (uint32_t)n > 0x7E000000u || cap < 0) return 0;
   hostsim::WaveHost w;
-  if (rng_seed) w.rng = rng_seed;
-  w.bounds(src, (size_t)n, dst, (size_t)cap);
-  lz4hip::FastStats st = {0, 0, 0, 0};
-  uint32_t r;
-  lz4hip::DirectOut<hostsim::WaveHost> out(w, src, (uint32_t)n, dst, (uint32_t)cap);
-  if (n < 65547) {
-    lz4hip::FastCore<hostsim::WaveHost, true, lz4hip::DirectOut<hostsim::WaveHost>, false, true> c(w, out, src, (uint32_t)n, &st);
-    c.accel = accel;
-    r = c.run();
-  } else {
-    lz4hip::FastCore<hostsim::WaveHost, false, lz4hip::DirectOut<hostsim::WaveHost>, false, true> c(w, out, src, (uint32_t)n, &st);
-    c.accel = accel;
-    r = c.run();
-  }
-  if (stats4) { stats4[0] = st.steps; stats4[1] = st.slow_steps; stats4[2] = st.false_pos; stats4[3] = st.sequences; }
-  if (w.oob) return -1000;
-  return (int)r;
+  hostsim::BlockHost io(src, n, dst, cap);
+  io.x.accel = accel;
+  return hostsim::sim_fast_block<lz4hip::FastForm<hostsim::WaveHost, false, true, false, true>>(w, io, stats4, rng_seed);
 }
 
 // the probe offsets g_a(k0 .. k0+63) of a miss-run (lane k - k0 holds g_a(k)), as the core computes them

@@ -6,6 +6,7 @@
 #include "../../lz4-java_amd/csrc/kernels.h"
 #include "../../lz4-java_amd/csrc/lz4_fast_core.h"
 #include "wave_host.h"
+#include "block_host.h"
 
 namespace {
 
@@ -53,6 +54,17 @@ struct WaveHostD : hostsim::WaveHost {
   }
 };
 
+// the block as the shell sees it (block_host.h), with the tail and the image readable as well
+struct BlockHostD : hostsim::BlockHost {
+  using hostsim::BlockHost::BlockHost;
+  const uint8_t* tail = nullptr; uint32_t keep = 0; const uint8_t* image = nullptr;
+  void begin_block(WaveHostD& w, const uint8_t* s, uint32_t len, uint8_t* d, uint32_t room) {
+    w.readable(0, s, len);
+    if (keep) { w.readable(1, tail, keep); w.readable(2, image, 32768); }
+    w.writable(0, d, room);
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -71,24 +83,15 @@ int sim_dict_image(const uint8_t* tail, uint32_t keep, uint8_t* image, uint64_t 
   return w.oob ? -1000 : 0;
 }
 
+// FastForm<.., DICT>'s block through the shell (fast_block_run; compress_fast_dict_cu_kernel keeps a copy of its own, see there):
 // returns compressed size (0 = does not fit), or -1000 if the simulated wave read outside [src, src+n), the tail and the image, or
 // wrote outside [dst, dst+cap).  keep == 0: no dictionary (tail and image unused)
 int sim_compress_fast_dict(const uint8_t* tail, uint32_t keep, const uint8_t* image, const uint8_t* src, int n, uint8_t* dst, int cap,
                            uint64_t* stats4, uint64_t rng_seed) {
-  if (n < 0 || (uint32_t)n > 0x7E000000u || cap < 0) return 0;
   WaveHostD w;
-  if (rng_seed) w.rng = rng_seed;
-  w.readable(0, src, (size_t)n);
-  if (keep) { w.readable(1, tail, keep); w.readable(2, image, 32768); }
-  w.writable(0, dst, (size_t)cap);
-  lz4hip::FastStats st = {0, 0, 0, 0};
-  lz4hip::DirectOut<WaveHostD> out(w, src, (uint32_t)n, dst, (uint32_t)cap);
-  lz4hip::FastCore<WaveHostD, false, lz4hip::DirectOut<WaveHostD>, false, false, true> c(w, out, src, (uint32_t)n, &st);
-  if (keep) { c.dict = tail; c.keep = keep; c.image = image; }
-  const uint32_t r = c.run();
-  if (stats4) { stats4[0] = st.steps; stats4[1] = st.slow_steps; stats4[2] = st.false_pos; stats4[3] = st.sequences; }
-  if (w.oob) return -1000;
-  return (int)r;
+  BlockHostD io(src, n, dst, cap);
+  io.x.dict = io.tail = tail; io.x.keep = io.keep = keep; io.x.image = io.image = image;
+  return hostsim::sim_fast_block<lz4hip::FastForm<WaveHostD, false, false, true, true>>(w, io, stats4, rng_seed);
 }
 
 }  // extern "C"
