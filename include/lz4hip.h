@@ -88,6 +88,8 @@ int lz4hip_version(void);
  *   whole 128-byte lines (faster when the batch is bandwidth-bound);
  * "decode_route_short" = 0 .. 255 (default 8): average output bytes per sequence up to which the device-side route sends a batch (of near match
  *   sources) to the wave loop; 0 = never;
+ * "decode_route_slots" = 1 .. 256 (default 256): how many of the device's route words (below) are handed out, round robin; every value gives
+ *   the same bytes (1: every routed launch reuses the word of the one before it -- what the suite sets to exercise that);
  * "compress_core" = 5 (default: adaptive two-pass -- blocks of long sequences are finished by the lean core (lz4_fast_v2_core.h), whose
  *   parked hits a partner wavefront writes out, blocks of short sequences by the window-parallel core), 3 (lean core only) or 1
  *   (window-parallel core only); "compress_switch" = routing threshold of the adaptive scheme in bytes per sequence (default 16);
@@ -96,6 +98,9 @@ int lz4hip_version(void);
  * "hc_chain_segment" = 4096 .. 1073741824 (default 1048576): positions per build item of lz4hip_compress_hc_chain_batch*; every value
  *   gives the same bytes (a segment warms its table up over the 65535 positions in front of it: at most 6.25 % more build work on a
  *   long chain at the default, none on chains of up to 1 MiB).
+ * Routed launches on any number of streams of a device are independent: the word a launch's route kernel writes and its candidate kernels
+ * read is one of a per-device ring, and a word's next use is ordered -- on the device, by an event; the host never waits -- behind the
+ * last candidate kernel of the launch that used it before, on whatever stream either runs.
  * The decode_* knobs and the device-side route do not apply to the partial decoder (lz4hip_decompress_safe_partial*): it always runs the
  * 4-lane staged loop from 40960 blocks on and the 8-lane deep loop below.  Nor do they apply to the dictionary decoder
  * (lz4hip_decompress_safe_dict*), which picks its two loops the same way.                                                       */
@@ -103,7 +108,8 @@ int lz4hip_set_option(const char* name, int value);
 /* diagnostic: what the device-side route of a device's last routed decode launch decided (device = index as in the _dev calls) -- out8
  * (8 words) = { route (0 lane-group default of the batch size, 1 ring loop, 2 wave loop, 3 deep loop instead of the staged one), hops
  * counted by the sampler, stream bytes it walked, average compressed size of 64 blocks, sampled match offsets within 6 KB, sampled
- * sequences, their output bytes, 0 }; synchronises the device                                                                  */
+ * sequences, their output bytes, 0 }; synchronises the device.  It describes the device's last routed launch on WHICHEVER stream it ran:
+ * a single-stream diagnostic -- with routed launches in flight on several streams it answers for whichever route kernel ran last       */
 int lz4hip_last_decode_route(int device, uint32_t* out8);
 
 /* == LZ4_compressBound (LZ4JNI.c:237): n + n/255 + 16, 0 if n < 0 or n > 0x7E000000            */
@@ -450,7 +456,10 @@ int lz4hip_xxh64_batch(const uint8_t* buf, const uint64_t* off, const int32_t* l
  * that runs it at such offsets -- tests/test_gpu_far_offsets.py for the block, dictionary, xxhash, generator and container entry
  * points (the containers with an input, compressed slots, a container and output slots that all pass 2^32), tests/test_gpu_cchain.py
  * for the two chain entry points -- and tests/test_far_table.py fails when a *_dev function is declared here without an entry.
- * Not covered there: lz4hip_xxh_stream_update_dev (a pointer and a 32-bit length, no offset) and the developer profile entry.  */
+ * Not covered there: lz4hip_xxh_stream_update_dev (a pointer and a 32-bit length, no offset) and the developer profile entry.
+ * The stream contract -- enqueued on `stream`, no wait for it but where an entry's comment says so, any number of streams at once -- is
+ * tested the same way: tests/userstream_common.py lists every *_dev function with what this header says about its synchronisation,
+ * tests/test_userstream_table.py keeps that list complete, tests/test_gpu_user_streams.py runs every entry on streams of the caller's. */
 int lz4hip_compress_fast_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                    uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                    int32_t* out_len, uint32_t n_blocks, int device, void* stream);
@@ -495,6 +504,9 @@ int lz4hip_compress_fast_chain_batch_dev(const uint8_t* src, const uint64_t* cha
 /* compress against a dictionary (see lz4hip_compress_fast_dict_batch): device pointers on `device`, and the HANDLE -- the compressor
  * needs its table image, not only the bytes; asynchronous, except that a handle's first compress on a device builds the image and
  * waits for `stream` once.  dict == NULL is LZ4HIP_E_ARG */
+int lz4hip_compress_fast_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                        uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                        int32_t* out_len, uint32_t n_blocks, const lz4hip_dict* dict, int device, void* stream);
 /* HC compress against a dictionary (see lz4hip_compress_hc_dict_batch): device pointers on `device`, and the HANDLE.  The plain form
  * sizes the chain workspace itself and synchronises `stream` once, as lz4hip_compress_hc_batch_dev does; the _ws form takes the span
  * (max of src_off + src_len) and a workspace of lz4hip_hc_workspace_bytes(src_span, n_blocks, level) bytes from the caller and is
@@ -507,9 +519,6 @@ int lz4hip_compress_hc_dict_batch_dev_ws(const uint8_t* src, const uint64_t* src
                                          uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                          int32_t* out_len, uint32_t n_blocks, int level, const lz4hip_dict* dict, int device, void* stream,
                                          uint64_t src_span, void* ws, size_t ws_bytes);
-int lz4hip_compress_fast_dict_batch_dev(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
-                                        uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
-                                        int32_t* out_len, uint32_t n_blocks, const lz4hip_dict* dict, int device, void* stream);
 /* HC: levels follow liblz4 (< 1 -> 9, > 12 -> 12): 1..9 = hash-chain strategy with lazy evaluation, 10..12 = optimal
  * parser (lz4-java levels 10..17).  Levels 10..12 are FUNCTIONAL ONLY: byte-identical output, but the optimal parser's table
  * walk is wave-uniform scalar work (about 1.0 / 0.7 GB/s per GPU at levels 10 / 12 -- no faster than the reference on the host's

@@ -1304,13 +1304,17 @@ class DeviceBatch:
 
 
 def set_option(name, value):
+    """a tuning knob of include/lz4hip.h: "decode_stage", "decode_pipe", "decode_route_short", "decode_route_slots" (1 .. 256 of the route
+    ring's slots handed out), "decode_ring", "decode_lanes", "compress_core", "compress_pack", "hc_chain_segment", "compress_switch".  Every
+    setting produces the same bytes; an unknown name or a value outside the knob's range raises LZ4HIPError"""
     _chk(lib().lz4hip_set_option(name.encode(), value))
 
 
 def last_decode_route(device=0):
     """diagnostic: (route, sampled hops, sampled stream bytes, average compressed size, sampled offsets within 6 KB, sampled sequences,
     their output bytes, 0) of the last decode launch that was routed on the device (more than 16 blocks per compute unit, every knob at
-    its default); route 0 = lane-group default of the batch size, 1 = ring loop, 2 = wave loop, 3 = deep loop instead of the staged one"""
+    its default); route 0 = lane-group default of the batch size, 1 = ring loop, 2 = wave loop, 3 = deep loop instead of the staged one.
+    The last routed launch on WHICHEVER stream it ran: a single-stream diagnostic"""
     out = (C.c_uint32 * 8)()
     _chk(lib().lz4hip_last_decode_route(device, out))
     return tuple(int(x) for x in out)

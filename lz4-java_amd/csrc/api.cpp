@@ -185,15 +185,80 @@ int hc_workspace(const lz4hip::BatchArgs& a, int level, hipStream_t st, void** w
   return LZ4HIP_OK;
 }
 
+// The scratch a device entry point takes for itself -- queue words, the routed-block list, the mail rings -- comes from buffers that live
+// as long as the engine, not from the stream-ordered allocator.  (It was hipMallocAsync + hipFreeAsync around every launch.  Measured
+// on the MI355X, tests/test_gpu_user_streams.py: with work pending on the stream, the SECOND such call blocked the host in
+// hipMallocAsync until the stream had drained -- the first call's hipFreeAsync'd block was the pool's only one, and the runtime waited
+// for it instead of handing it out in stream order -- so two compress calls in a row did not "return without synchronising".  DESIGN.md
+// 2.3 has the other incident with such an allocation.)  A buffer is handed to a launch on the stream that used it last -- the
+// stream's own order is enough -- or once the event recorded behind its last user's kernels is complete; otherwise a new one is made.
+// In the steady state that is no allocation and no wait: one buffer per stream that has launches in flight at the same time.
+struct ScratchBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;      // behind the last kernel that used the buffer
+  hipStream_t last = nullptr;   // the stream ev was recorded on
+  bool held = false;            // between scratch_acquire and scratch_release of a host thread
+};
+struct ScratchPool {
+  std::mutex mu;
+  std::vector<ScratchBuf*> bufs;
+};
+ScratchPool g_scratch[64];
+ScratchBuf* scratch_acquire(size_t bytes, hipStream_t st) {
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return nullptr;
+  ScratchPool& P = g_scratch[d];
+  std::lock_guard<std::mutex> lk(P.mu);
+  ScratchBuf* pick = nullptr;
+  for (ScratchBuf* b : P.bufs)
+    if (!b->held && b->bytes >= bytes && b->last == st) { pick = b; break; }
+  if (!pick)
+    for (ScratchBuf* b : P.bufs)
+      if (!b->held && b->bytes >= bytes && hipEventQuery(b->ev) == hipSuccess) { pick = b; break; }
+  if (!pick) {
+    size_t cap = 64u << 10;
+    while (cap < bytes) cap <<= 1;
+    ScratchBuf* b = new (std::nothrow) ScratchBuf();
+    if (!b) return nullptr;
+    if (hipMalloc(&b->p, cap) != hipSuccess) { delete b; return nullptr; }
+    if (hipEventCreateWithFlags(&b->ev, hipEventDisableTiming) != hipSuccess) { (void)hipFree(b->p); delete b; return nullptr; }
+    b->bytes = cap;
+    try { P.bufs.push_back(b); } catch (...) { (void)hipEventDestroy(b->ev); (void)hipFree(b->p); delete b; return nullptr; }
+    pick = b;
+  }
+  pick->held = true;
+  return pick;
+}
+void scratch_release(ScratchBuf* b, hipStream_t st) {   // behind the launch's last kernel (also of a launch that failed half way)
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) d = 0;
+  std::lock_guard<std::mutex> lk(g_scratch[d].mu);
+  // (without its event nothing says when the buffer is free: it is not handed out again, and goes with the others at shutdown)
+  if (hipEventRecord(b->ev, st) != hipSuccess) b->bytes = 0;
+  b->last = st;
+  b->held = false;
+}
+void scratch_free_all(int d) {   // lz4hip_shutdown (the device is current)
+  if (d < 0 || d >= 64) return;
+  std::lock_guard<std::mutex> lk(g_scratch[d].mu);
+  for (ScratchBuf* b : g_scratch[d].bufs) {
+    (void)hipFree(b->p);
+    (void)hipEventDestroy(b->ev);
+    delete b;
+  }
+  g_scratch[d].bufs.clear();
+}
+
 // fast compress: the cores of kernels.h, selected by "compress_core"
 int launch_fast(const lz4hip::BatchArgs& a, hipStream_t st) {
   // scratch: three queue words + the routed-block list of the adaptive scheme
-  uint32_t* scratch = nullptr;
   const uint32_t cus = lz4hip::device_cus();
   const int core = g_compress_core.load(std::memory_order_relaxed);
   const size_t mail_words = core != 1 ? lz4hip::compress_fast_v2w_scratch_words(cus) : 0u;   // rings of the finder/writer pairs
-  hipError_t e = hipMallocAsync((void**)&scratch, (3 + (size_t)a.n + mail_words) * sizeof(uint32_t), st);
-  if (e != hipSuccess) return (int)e;
+  ScratchBuf* sb = scratch_acquire((3 + (size_t)a.n + mail_words) * sizeof(uint32_t), st);
+  if (!sb) return (int)hipErrorOutOfMemory;
+  uint32_t* scratch = (uint32_t*)sb->p;
   const uint32_t dense64 = 64u * (uint32_t)g_compress_switch.load(std::memory_order_relaxed);
   int le;
   if (core == 1) {
@@ -204,7 +269,7 @@ int launch_fast(const lz4hip::BatchArgs& a, hipStream_t st) {
     le = lz4hip::launch_compress_fast_v2w(a, scratch, scratch + 3, dense64, cus, scratch + 3 + a.n, st);
     if (le == 0) le = lz4hip::launch_compress_fast_ms(a, scratch, scratch + 3, false, cus, st);
   }
-  (void)hipFreeAsync(scratch, st);
+  scratch_release(sb, st);
   return le;
 }
 
@@ -229,48 +294,75 @@ const char* decode_knobs_error(int lanes, int pipe, int ring) {
   return nullptr;
 }
 
-// The device-side route's word: one of kRouteWords words of a per-device buffer, handed out round robin.  (It was a stream-ordered
-// allocation per launch: hipMallocAsync + hipFreeAsync in front of and behind EVERY routed launch -- tens of microseconds on the headline's
-// 6 ms decode, measured with the route's kernels in profiles/r06l_bench_kernel_trace.txt.)  A word is only meaningful between a launch's
-// route kernel and its candidate kernels, which follow it in stream order: a slot would have to come round again -- 256 routed launches
-// later -- while they are still in flight to be disturbed.
+// The device-side route's word: one of kRouteWords words of a per-device buffer, handed out round robin to the routed launches of ALL
+// streams of the device.  (It was a stream-ordered allocation per launch: hipMallocAsync + hipFreeAsync in front of and behind EVERY
+// routed launch -- tens of microseconds on the headline's 6 ms decode, measured with the route's kernels in
+// profiles/r06l_bench_kernel_trace.txt.)  A word is meaningful from a launch's route kernel to the end of its LAST candidate kernel:
+// every workgroup of every candidate reads it when it starts, and the later workgroups of a launch of more than 64 blocks per CU start
+// while the earlier ones run.  So a slot's next use is ordered behind its previous user's last candidate kernel, on whatever stream
+// either ran: each slot has an event (no timing) recorded behind the candidates, and a launch that finds its slot last used on ANOTHER
+// stream makes its own stream wait for that event in front of its route kernel (on the same stream the order is the stream's; the
+// pattern is xxh_stream_launch's).  No host synchronisation, no allocation per launch.  The lock is held from the slot's choice to the
+// record of its event: two host threads that meet in one slot launch one behind the other.  "decode_route_slots" = how many of the
+// slots are handed out (1: every routed launch reuses the one before it -- what the suite runs to exercise the wait).
 constexpr uint32_t kRouteWords = 256u;
-uint32_t* g_route_ring[64];
-std::atomic<uint32_t> g_route_next[64];
-std::mutex g_route_mu;
-uint32_t* route_word() {
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return nullptr;
-  uint32_t* ring = __atomic_load_n(&g_route_ring[d], __ATOMIC_ACQUIRE);
-  if (!ring) {
-    std::lock_guard<std::mutex> lk(g_route_mu);
-    ring = g_route_ring[d];
-    if (!ring) {
-      if (hipMalloc((void**)&ring, kRouteWords * sizeof(uint32_t)) != hipSuccess) return nullptr;
-      __atomic_store_n(&g_route_ring[d], ring, __ATOMIC_RELEASE);
-    }
-  }
-  return ring + (g_route_next[d].fetch_add(1u, std::memory_order_relaxed) % kRouteWords);
-}
+std::atomic<int> g_route_slots{(int)kRouteWords};   // "decode_route_slots"
+struct RouteRing {
+  uint32_t* words = nullptr;
+  uint32_t next = 0;
+  hipEvent_t ev[kRouteWords] = {};      // created at the slot's first use
+  hipStream_t last[kRouteWords] = {};   // the stream ev was last recorded on
+  bool used[kRouteWords] = {};
+  std::mutex mu;
+};
+RouteRing g_route[64];
 void route_release(int d) {   // lz4hip_shutdown (the device is current)
-  std::lock_guard<std::mutex> lk(g_route_mu);
-  if (d >= 0 && d < 64 && g_route_ring[d]) { (void)hipFree(g_route_ring[d]); g_route_ring[d] = nullptr; }
+  if (d < 0 || d >= 64) return;
+  RouteRing& r = g_route[d];
+  std::lock_guard<std::mutex> lk(r.mu);
+  if (r.words) { (void)hipFree(r.words); r.words = nullptr; }
+  for (uint32_t i = 0; i < kRouteWords; i++) {
+    if (r.ev[i]) { (void)hipEventDestroy(r.ev[i]); r.ev[i] = nullptr; }
+    r.used[i] = false;
+    r.last[i] = nullptr;
+  }
+  r.next = 0;
 }
 
 int launch_decode(const lz4hip::BatchArgs& a, bool safe, hipStream_t st) {
-  if (const char* why = decode_knobs_error(g_decode_lanes.load(), g_decode_pipe.load(), g_decode_ring.load())) return fail(LZ4HIP_E_ARG, why);
-  uint32_t* route = a.n > 16u * lz4hip::device_cus() ? route_word() : nullptr;   // (nullptr: no device-side route, the lane-group default of the batch size)
-  return lz4hip::launch_decompress(a, safe, g_decode_lanes.load(), g_decode_pipe.load(), g_decode_stage.load(), g_decode_ring.load(), st, route);
+  const int lanes = g_decode_lanes.load(), pipe = g_decode_pipe.load(), stage = g_decode_stage.load(), ring = g_decode_ring.load();
+  if (const char* why = decode_knobs_error(lanes, pipe, ring)) return fail(LZ4HIP_E_ARG, why);
+  // (no route word: no device-side route, the lane-group default of the batch size -- launch_decompress routes under the same condition)
+  if (!(a.n > 16u * lz4hip::device_cus() && lanes == 0 && pipe < 0 && stage < 0)) return lz4hip::launch_decompress(a, safe, lanes, pipe, stage, ring, st, nullptr);
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return lz4hip::launch_decompress(a, safe, lanes, pipe, stage, ring, st, nullptr);
+  RouteRing& r = g_route[d];
+  std::lock_guard<std::mutex> lk(r.mu);
+  if (!r.words && hipMalloc((void**)&r.words, kRouteWords * sizeof(uint32_t)) != hipSuccess) {
+    r.words = nullptr;
+    return lz4hip::launch_decompress(a, safe, lanes, pipe, stage, ring, st, nullptr);
+  }
+  const uint32_t slots = (uint32_t)g_route_slots.load(std::memory_order_relaxed);
+  const uint32_t k = r.next % slots;
+  r.next = (k + 1u) % slots;
+  if (!r.ev[k]) HIPCHK(hipEventCreateWithFlags(&r.ev[k], hipEventDisableTiming));
+  if (r.used[k] && r.last[k] != st) HIPCHK(hipStreamWaitEvent(st, r.ev[k], 0));   // behind the slot's previous user's last candidate
+  const int e = lz4hip::launch_decompress(a, safe, lanes, pipe, stage, ring, st, r.words + k);
+  // (also after a failed launch: whatever part of it was enqueued reads the word)
+  const hipError_t re = hipEventRecord(r.ev[k], st);
+  r.used[k] = true;
+  r.last[k] = st;
+  if (e == 0 && re != hipSuccess) return fail(LZ4HIP_E_HIP, "hipEventRecord", re);
+  return e;
 }
 
 // a queue word of scratch around a launcher: launch(q) -> the launcher's hipError_t, which is passed on
 template <class Launch>
 int with_queue_word(hipStream_t st, Launch launch) {
-  uint32_t* q = nullptr;
-  const hipError_t me = hipMallocAsync((void**)&q, sizeof(uint32_t), st);
-  if (me != hipSuccess) return (int)me;
-  const int e = launch(q);
-  (void)hipFreeAsync(q, st);
+  ScratchBuf* sb = scratch_acquire(sizeof(uint32_t), st);
+  if (!sb) return (int)hipErrorOutOfMemory;
+  const int e = launch((uint32_t*)sb->p);
+  scratch_release(sb, st);
   return e;
 }
 
@@ -1556,7 +1648,7 @@ void lz4hip_shutdown(void) {
   (void)hipGetDevice(&prev);
   for (int ord : g_devs) {
     if (ord < 0 || ord >= 64) continue;
-    if (hipSetDevice(ord) == hipSuccess) { g_ctx[ord].release(); route_release(ord); }
+    if (hipSetDevice(ord) == hipSuccess) { g_ctx[ord].release(); route_release(ord); scratch_free_all(ord); }
   }
   if (prev >= 0) (void)hipSetDevice(prev);
   g_devs.clear();
@@ -1594,6 +1686,11 @@ int lz4hip_set_option(const char* name, int value) {
   if (name && strcmp(name, "decode_route_short") == 0) {   // average output bytes per sampled sequence up to which a batch of more than 16 blocks per CU goes to the wave kernel; 0: never
     if (value < 0 || value > 255) return fail(LZ4HIP_E_ARG, "decode_route_short must be 0 .. 255");
     lz4hip::set_route_short(value);
+    return LZ4HIP_OK;
+  }
+  if (name && strcmp(name, "decode_route_slots") == 0) {   // how many of the route ring's slots are handed out; every value gives the same bytes
+    if (value < 1 || value > (int)kRouteWords) return fail(LZ4HIP_E_ARG, "decode_route_slots must be 1 .. 256");
+    g_route_slots = value;
     return LZ4HIP_OK;
   }
   if (name && strcmp(name, "decode_ring") == 0) {

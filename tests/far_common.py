@@ -194,7 +194,7 @@ def compress_blocks(corpus, sizes):
     return [("book1 %d" % n, b[:n]) for n in sizes] + [("random 3000", random.Random(5).randbytes(3000))]
 
 
-def _compress_items(blocks, fn):
+def compress_items(blocks, fn):
     """every block at the bound (fits), at the reference's size (fits exactly) and one byte below it (does not: 0); fn(v, cap) -> (r, bytes)"""
     items = []
     for name, v in blocks:
@@ -208,19 +208,19 @@ def _compress_items(blocks, fn):
 
 
 def compress_fast_cases(ref, corpus):
-    return layout(_compress_items(compress_blocks(corpus, FAST_SIZES), ref.compress_fast_raw))
+    return layout(compress_items(compress_blocks(corpus, FAST_SIZES), ref.compress_fast_raw))
 
 
 def compress_accel_cases(ref, corpus, a):
     rm = RefMore(ref)
-    return layout(_compress_items(compress_blocks(corpus, FAST_SIZES), lambda v, cap: rm.accel(v, cap, a)))
+    return layout(compress_items(compress_blocks(corpus, FAST_SIZES), lambda v, cap: rm.accel(v, cap, a)))
 
 
 def compress_hc_cases(ref, corpus, level):
-    return layout(_compress_items(compress_blocks(corpus, HC_SIZES), lambda v, cap: ref.compress_hc_raw(v, level, cap)))
+    return layout(compress_items(compress_blocks(corpus, HC_SIZES), lambda v, cap: ref.compress_hc_raw(v, level, cap)))
 
 
-def _dest_items(blocks, full, fn):
+def dest_items(blocks, full, fn):
     """targets below, at and above the full compressed size, and the zero result (target 0); fn(v, t) -> (ret, consumed, bytes)"""
     items = []
     for name, v in blocks:
@@ -234,12 +234,12 @@ def _dest_items(blocks, full, fn):
 
 def dest_size_cases(ref, corpus):
     rm = RefMore(ref)
-    return layout(_dest_items(compress_blocks(corpus, (0, 13, 1000, 65546, 65547)), lambda v: len(ref.compress_fast(v)), rm.dest_size))
+    return layout(dest_items(compress_blocks(corpus, (0, 13, 1000, 65546, 65547)), lambda v: len(ref.compress_fast(v)), rm.dest_size))
 
 
 def hc_dest_size_cases(ref, corpus, level):
     rm = RefMore(ref)
-    return layout(_dest_items(compress_blocks(corpus, (0, 13, 1000, 70000)), lambda v: ref.compress_hc_raw(v, level, bound(len(v)))[0],
+    return layout(dest_items(compress_blocks(corpus, (0, 13, 1000, 70000)), lambda v: ref.compress_hc_raw(v, level, bound(len(v)))[0],
                               lambda v, t: rm.hc_dest_size(v, t, level)))
 
 
@@ -258,7 +258,7 @@ def compress_dict_cases(ref, L):
     from dict_common import RefDict
     from dictc_common import ref_compress
     rd, d = RefDict(ref), dict_of(L)
-    return layout(_compress_items(dict_records(), lambda v, cap: ref_compress(rd, d, v, cap)))
+    return layout(compress_items(dict_records(), lambda v, cap: ref_compress(rd, d, v, cap)))
 
 
 _HC_REF = {}
@@ -268,7 +268,7 @@ def compress_hc_dict_cases(ref, L, level=9):
     from hcdict_common import Ref
     R = _HC_REF.setdefault(id(ref), Ref(ref))
     d = dict_of(L)
-    return layout(_compress_items(dict_records(), lambda v, cap: R.compress(d, v, level, cap)))
+    return layout(compress_items(dict_records(), lambda v, cap: R.compress(d, v, level, cap)))
 
 
 def damage(valid, seed):
@@ -298,40 +298,58 @@ def decode_streams(ref, O, corpus):
     return [(name, ref.compress_fast(v), len(v)) for name, v in vs]
 
 
-def decode_safe_cases(ref, O, corpus):
+# the decoders' items, before layout() places them: cases = [(name, stream, capacity)] (tests/userstream_common.py builds its own lists)
+def decode_safe_items(ref, cases):
     items = []
-    for name, s, cap in damage(decode_streams(ref, O, corpus), 8):
+    for name, s, cap in cases:
         r, by = ref.decompress_safe_raw(s, cap)
         items.append((name, s, cap, cap, r, by[:r] if r >= 0 else None, 0))
-    return layout(items)
+    return items
+
+
+def decode_safe_cases(ref, O, corpus):
+    return layout(decode_safe_items(ref, damage(decode_streams(ref, O, corpus), 8)))
 
 
 def decode_fast_cases(ref, O, corpus):
     """the fast decoder: the slot is the stream (src_cap = its length), p1 = the decoded size asked for; O.decompress_fast_bounded"""
+    return layout(decode_fast_items(O, damage(decode_streams(ref, O, corpus), 9)))
+
+
+def decode_fast_items(O, cases):
     items = []
-    for name, s, n in damage(decode_streams(ref, O, corpus), 9):
+    for name, s, n in cases:
         r, by = O.decompress_fast_bounded(s, len(s), n)
         items.append((name, s, n, n, r, by if r >= 0 else None, 0))
-    return layout(items)
+    return items
 
 
 def decode_partial_cases(ref, O, corpus):
     """targets of 1, 4096 and the whole block; p1 = target, p2 = capacity; the slot owns min(target, capacity) bytes"""
+    return layout(decode_partial_items(ref, damage(decode_streams(ref, O, corpus), 10)))
+
+
+def decode_partial_items(ref, cases, targets=lambda k, cap: (1, 4096, cap)):
+    """targets(k, cap): the targets of case k"""
     from partial_common import ref_partial
     run = ref_partial(ref)
     items = []
-    for name, s, cap in damage(decode_streams(ref, O, corpus), 10):
-        for t in (1, 4096, cap):
+    for k, (name, s, cap) in enumerate(cases):
+        for t in targets(k, cap):
             r, by = run(s, t, cap)
             items.append(("%s target %d" % (name, t), s, min(t, cap), t, r, by if r >= 0 else None, cap))
-    return layout(items)
+    return items
 
 
 def decode_size_cases(ref, O, corpus):
     """the size query has no destination: only the sources are placed"""
+    return layout(decode_size_items(ref, damage(decode_streams(ref, O, corpus), 11)))
+
+
+def decode_size_items(ref, cases):
     from size_common import ref_size
     run = ref_size(ref)
-    return layout([(name, s, 0, cap, run(s, cap), None, 0) for name, s, cap in damage(decode_streams(ref, O, corpus), 11)])
+    return [(name, s, 0, cap, run(s, cap), None, 0) for name, s, cap in cases]
 
 
 def decode_dict_cases(ref, L):
@@ -344,11 +362,15 @@ def decode_dict_cases(ref, L):
         if v:
             valid.append((name + " fast", rd.compress(d, v), len(v)))
             valid.append((name + " hc9", rd.compress(d, v, 9), len(v)))
+    return layout(decode_dict_items(rd, d, damage(valid, 12 + L)))
+
+
+def decode_dict_items(rd, d, cases):
     items = []
-    for name, s, cap in damage(valid, 12 + L):
+    for name, s, cap in cases:
         r, by = rd.decode(s, cap, d)
         items.append((name, s, cap, cap, r, by if r >= 0 else None, 0))
-    return layout(items)
+    return items
 
 
 ROUTED_SIZES = (1024, 16384)     # 1 KiB: the route kernel reads the sizes only; 16 KiB: streams of 4 KiB and more, whose middle it samples

@@ -129,6 +129,8 @@ def test_fails_loudly_without_gpu(amd):
         amd.set_option("decode_route_short", 256)
     with pytest.raises(amd.LZ4HIPError):
         amd.set_option("decode_pipe", 6)
+    for v, ok in ((1, True), (256, True), (0, False), (257, False)):      # the route ring's slots: 1 .. 256, anything else LZ4HIP_E_ARG
+        assert amd.lib().lz4hip_set_option(b"decode_route_slots", v) == (0 if ok else -3), v
     for v in (7, 8, -1):
         amd.set_option("decode_pipe", v)
     assert amd.lib().lz4hip_device_count() == 0
