@@ -42,6 +42,19 @@
 #ifndef LZ4HIP_DECODE_INTERIOR
 #define LZ4HIP_DECODE_INTERIOR 1  // 0: the plain interior loop is never entered -- the exact tiers alone (the CPU simulator's builds)
 #endif
+// The interior loops' distance from a block's two ends: every one of them (the loops below and lz4_decode_deep.h .. lz4_decode_size.h)
+// runs a sequence without liblz4's per-sequence checks only while ip <= iend - LZ4HIP_DECODE_IN_MARGIN and
+// op <= oend - LZ4HIP_DECODE_OUT_MARGIN.  A "simple" sequence (one extension byte per length) consumes <= 274 and produces <= 542
+// bytes.  What the loops need of the rest (profiles/decode_margin_audit.txt, loop by loop): 279 of the input margin -- the 8 bytes read
+// at the literals' end, which is also liblz4's rule that literals end 8 bytes in front of iend -- and 547 / 549 / 557 of the output
+// margin for lane groups of 16+ / 8 / 4 lanes: liblz4's five last literals, or the 3 / 7 / 15 bytes a lane's store runs past a match's end.
+// The other 27 and 49 bytes are slack no loop uses.  Overridable for the lane simulator's mutant builds alone (tests/test_margin_hostsim.py).
+#ifndef LZ4HIP_DECODE_IN_MARGIN
+#define LZ4HIP_DECODE_IN_MARGIN 306
+#endif
+#ifndef LZ4HIP_DECODE_OUT_MARGIN
+#define LZ4HIP_DECODE_OUT_MARGIN 606
+#endif
 namespace lz4hip {
 // The two copies of decode_block's dictionary mode (DICT, below), in front of the interior loops that use them.
 template <class Grp>
@@ -155,7 +168,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
 
   if (oend - op >= 64) {
   interior:
-    // ---- tier 1, interior fast loop.  While the block is far from both buffer ends (ip <= iend-306, op <= oend-606)
+    // ---- tier 1, interior fast loop.  While the block is far from both buffer ends (ip <= iend-306, op <= oend-606: LZ4HIP_DECODE_IN_MARGIN / _OUT_MARGIN)
     // and the sequence is "simple" -- literal and match lengths need at most ONE extension byte (<= 269 / <= 273),
     // offset <= op -- every check of liblz4's fast loop provably passes (a sequence consumes <= 274 and produces
     // <= 542 bytes), so only those few conditions are tested.  Anything else falls through, with ip/op still at the
@@ -163,7 +176,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
     // The 8 bytes fetched at the offset position also hold the NEXT sequence's token (and its first length byte), so the
     // steady state costs two dependent loads per sequence: {offset word + literals} and {match source}.
     if constexpr (PIPE == 2) {
-      if (ip + 2048 <= iend && ip <= iend - 306 && op <= oend - 606)
+      if (ip + 2048 <= iend && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN)
         if (decode_deep_loop<Grp, DICT>(g, src, iend, dst, oend, ip, op, stage, dict_end, (uint32_t)dict_len)) goto interior;
     }
     if constexpr (PIPE == 3) {   // the ring loop (lz4_decode_ring.h): stream and recent output in LDS at `stage` (Grp::kRingLds bytes)
@@ -171,7 +184,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
       // interior loop, and not by the exact code below one sequence per round of `goto interior`: the blocks of a wavefront need
       // different numbers of sequences for their first 64 bytes, and blocks that reach the ring loop in different rounds of an
       // enclosing loop run it one after the other, not side by side (measured: 5.4 of 16 blocks per trip, 3x the time).
-      if (op < 64 && ip <= iend - 306 && op <= oend - 606) {
+      if (op < 64 && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN) {
         uint32_t t4 = g.ld32(src + ip);
         do {
           int lit = (int)((t4 >> 4) & 15u), ml = (int)(t4 & 15u), hdr = 1;
@@ -200,29 +213,29 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
           op += ml;
           ip += adv;
           t4 = nxt;
-        } while (op < 64 && ip <= iend - 306 && op <= oend - 606);
+        } while (op < 64 && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN);
       }
-      if (op >= 64 && ip + 320 <= iend && ip <= iend - 306 && op <= oend - 606)
+      if (op >= 64 && ip + 320 <= iend && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN)
         if (decode_ring_loop(g, src, iend, dst, oend, ip, op, stage)) goto interior;
     }
     if constexpr (PIPE == 4) {   // the wave loop (lz4_decode_wave.h); what it leaves at ip is done by the exact code below, which comes back
-      if (ip + 1024 <= iend && ip <= iend - 306 && op <= oend - 606) decode_wave_loop(g, src, iend, dst, oend, ip, op, stage);
+      if (ip + 1024 <= iend && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN) decode_wave_loop(g, src, iend, dst, oend, ip, op, stage);
     }
     if constexpr (PIPE == 5 || PIPE == 6) {   // the parallel wave loop: several sequences of the block per trip (6: one window of the stream per trip whatever the backend's ring -- the simulator's way to the form a 1 KB stream ring runs)
-      if (ip + 1536 <= iend && ip <= iend - 306 && op <= oend - 606)
+      if (ip + 1536 <= iend && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN)
         if (decode_wave_par_loop<Grp, false>(g, src, iend, dst, oend, ip, op, stage))             // (true: the stream is full of sequences -- the loop's SHORT instance)
-          if (ip + 1536 <= iend && ip <= iend - 306 && op <= oend - 606) (void)decode_wave_par_loop<Grp, true>(g, src, iend, dst, oend, ip, op, stage);
+          if (ip + 1536 <= iend && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN) (void)decode_wave_par_loop<Grp, true>(g, src, iend, dst, oend, ip, op, stage);
     }
     if constexpr (PIPE == 7) {   // the pair loop (lz4_decode_pair.h): this wavefront copies, its partner wavefront parses the stream a trip or two ahead
-      if (ip + 1536 <= iend && ip <= iend - 306 && op <= oend - 606) decode_pair_loop<Grp>(g, src, iend, dst, oend, ip, op, stage);
+      if (ip + 1536 <= iend && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN) decode_pair_loop<Grp>(g, src, iend, dst, oend, ip, op, stage);
     }
     if constexpr (PIPE == 8) {   // the trio loop (lz4_decode_trio.h): this wavefront copies, a planner and a scanner wavefront run ahead in the stream
-      if (ip + 1536 <= iend && ip <= iend - 306 && op <= oend - 606) decode_trio_loop<Grp>(g, src, iend, dst, oend, ip, op, stage);
+      if (ip + 1536 <= iend && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN) decode_trio_loop<Grp>(g, src, iend, dst, oend, ip, op, stage);
     }
     if constexpr (PIPE == 9) {   // the size loop (lz4_decode_size.h): it moves ip / op over every sequence that provably passes; what it leaves at ip is done by the exact code below, which comes back
-      if (ip <= iend - 306 && op <= oend - 606) decode_size_loop(g, src, iend, oend, ip, op, stage);
+      if (ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN) decode_size_loop(g, src, iend, oend, ip, op, stage);
     }
-    if ((PIPE == 1 || (PIPE == 2 && ip + 2048 > iend) || (PIPE == 3 && ip + 320 > iend) || (PIPE == 4 && ip + 1024 > iend) || ((PIPE == 5 || PIPE == 6 || PIPE == 7 || PIPE == 8) && ip + 1536 > iend)) && ip <= iend - 306 && op <= oend - 606) {   // (2 .. 8: only the tail of the stream)
+    if ((PIPE == 1 || (PIPE == 2 && ip + 2048 > iend) || (PIPE == 3 && ip + 320 > iend) || (PIPE == 4 && ip + 1024 > iend) || ((PIPE == 5 || PIPE == 6 || PIPE == 7 || PIPE == 8) && ip + 1536 > iend)) && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN) {   // (2 .. 8: only the tail of the stream)
       // ---- the same loop, software-pipelined.  A wavefront's memory operations retire in order, so a wait for a load also
       // waits for every OLDER store.  Here (a) the next sequence's offset word is requested as soon as this sequence's header
       // is parsed, (b) a "simple" sequence (literals and match take one step each, match source entirely before the
@@ -265,10 +278,10 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
         const uint8_t* lit_src = src + ip + hdr;
         {
           // the next sequence's header is in nxt: if it can run in this loop, request its offset word now (the address the
-          // next trip computes from t4 = nxt; ip + adv <= iend - 306 leaves >= 306 readable bytes, the word ends <= 279 in)
+          // next trip computes from t4 = nxt; ip + adv <= iend - LZ4HIP_DECODE_IN_MARGIN leaves >= 306 readable bytes, the word ends <= 279 in)
           have_o8 = false;
           int lit2 = (int)((nxt >> 4) & 15u), hdr2 = 1;
-          bool ok2 = ip + adv <= iend - 306;
+          bool ok2 = ip + adv <= iend - LZ4HIP_DECODE_IN_MARGIN;
           if (lit2 == 15) {
             const uint32_t e2 = (nxt >> 8) & 255u;
             if (e2 == 255u) ok2 = false;
@@ -298,7 +311,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
             op += ml;
             ip += adv;
             t4 = nxt;
-            return ip <= iend - 306 && op <= oend - 606;
+            return ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN;
           }
         }
         const bool simple = ulit <= g.step() && uml <= g.step() && uoff >= ulit + uml + sl;
@@ -317,12 +330,12 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
         op += ml;
         ip += adv;
         t4 = nxt;
-        return ip <= iend - 306 && op <= oend - 606;
+        return ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN;
       };
       while (trip(R0, R1, true) && trip(R1, R0, false)) {}
       if (have_p) g.seq_store(p_in0 ? R0 : R1, dst + p_op, p_lit, p_ml);  // the exact code below reads what is in memory
     }
-    if (STAGE && !PIPE && ip <= iend - 306 && op <= oend - 606) {
+    if (STAGE && !PIPE && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN) {
       // ---- the plain loop below, writing through the staging buffer.  Match sources are read from memory only: a source that
       // reaches past the flushed position (rare unless offsets are short) flushes everything first, and that match is then
       // written straight to memory.  Whole lines are flushed every second sequence -- on a schedule, not when a block happens
@@ -380,10 +393,10 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
 #define LZ4HIP_STAGE_EVERY 2
 #endif
         if (++it % LZ4HIP_STAGE_EVERY == 0u) g.st_flush_lines(dst, (uint32_t)op);
-      } while (ip <= iend - 306 && op <= oend - 606);
+      } while (ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN);
       g.st_flush_all(dst, (uint32_t)op);  // the exact code below reads and writes memory
     }
-    if (!STAGE && !PIPE && LZ4HIP_DECODE_INTERIOR && ip <= iend - 306 && op <= oend - 606) {
+    if (!STAGE && !PIPE && LZ4HIP_DECODE_INTERIOR && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN) {
       uint32_t t4 = g.ld32(src + ip);  // {token, first literal-length byte, ...} of the sequence at ip
       do {
         int lit = (int)((t4 >> 4) & 15u);
@@ -415,7 +428,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
         op += ml;
         ip += adv;
         t4 = nxt;
-      } while (ip <= iend - 306 && op <= oend - 606);
+      } while (ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN);
     }
     // ---- tier 1: fast loop.  Software-pipelined: the word holding {offset, first match-length byte}
     // is requested BEFORE the literal copy, and the next sequence's token word BEFORE the match copy,
@@ -504,7 +517,7 @@ LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* d
       // The interior loop left on a sequence it does not handle (a length run of two or more bytes, ...); that sequence has now
       // been decoded with every check: back to the interior loop while the block is still far from both ends.  (Round 1 entered
       // it once per block: data with an occasional long match or literal run fell off the fast path for the rest of the block.)
-      if (LZ4HIP_DECODE_REENTER && ip <= iend - 306 && op <= oend - 606) goto interior;
+      if (LZ4HIP_DECODE_REENTER && ip <= iend - LZ4HIP_DECODE_IN_MARGIN && op <= oend - LZ4HIP_DECODE_OUT_MARGIN) goto interior;
     }
   }
 

@@ -34,7 +34,7 @@ LZ4HIP_DEV bool decode_deep_loop(Grp& g, const uint8_t* src, const int iend, uin
   constexpr uint32_t KS = Grp::kStream, PC = Grp::kPiece, STEP = 64u;
   typedef typename Grp::LChunk LChunk;   // a group's 64-byte step (per lane: LB bytes)
   uint32_t ip = (uint32_t)ip_io, op = (uint32_t)op_io;
-  const uint32_t ilim = (uint32_t)iend - 306u, olim = (uint32_t)oend - 606u;
+  const uint32_t ilim = (uint32_t)iend - (uint32_t)LZ4HIP_DECODE_IN_MARGIN, olim = (uint32_t)oend - (uint32_t)LZ4HIP_DECODE_OUT_MARGIN;
   g.sr_begin(stage);
   // the ring holds the stream bytes [.., avail); `fetched` is the end of what has been requested
   uint32_t avail = ip & ~(PC - 1u);

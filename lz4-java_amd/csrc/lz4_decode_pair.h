@@ -80,7 +80,7 @@ LZ4HIP_DEV void pair_parse_loop(Grp& g, const uint8_t* src, const uint32_t iend,
   typedef typename Grp::VB VB;
   constexpr uint32_t STEP = 256u, TRIPMAX = 2048u, AHEAD = 512u;   // (lz4_decode_wave.h)
   const uint32_t KW = g.wv_ring(), KS = g.wv_stream();
-  const uint32_t ilim = iend - 306u, olim = oend - 606u;
+  const uint32_t ilim = iend - (uint32_t)LZ4HIP_DECODE_IN_MARGIN, olim = oend - (uint32_t)LZ4HIP_DECODE_OUT_MARGIN;
   const uint32_t op0 = op;
   uint32_t head = 0u, tail_seen = 0u;          // (both counters start at zero with every entry: the copier reset them before it raised CMD)
   uint32_t qip[PAIR_SLOTS];                    // stream positions of the messages in flight, oldest first (the last `head - tail` entries)
@@ -280,7 +280,7 @@ LZ4HIP_DEV void decode_pair_loop(Grp& g, const uint8_t* src, const int iend, uin
   typedef typename Grp::VB VB;
   constexpr uint32_t STEP = 256u;
   uint32_t ip = (uint32_t)ip_io, op = (uint32_t)op_io;
-  const uint32_t ilim = (uint32_t)iend - 306u, olim = (uint32_t)oend - 606u;
+  const uint32_t ilim = (uint32_t)iend - (uint32_t)LZ4HIP_DECODE_IN_MARGIN, olim = (uint32_t)oend - (uint32_t)LZ4HIP_DECODE_OUT_MARGIN;
   g.wv_begin(lds, dst);
   g.pm_begin(lds);
   const uint32_t db = g.wv_dbase();

@@ -53,7 +53,7 @@ LZ4HIP_DEV bool decode_ring_loop(Grp& g, const uint8_t* src, const int iend, uin
   const uint32_t STEP = g.ring_step();     // bytes of a step: what the block's lanes move at once, the flusher's and the refill's unit (64; 16 with a lane per block)
   const uint32_t PIECE = g.ring_piece();   // bytes of literals / of match a trip emits at most (60: a 64-byte step written at an odd address covers 64 - 3; 16)
   uint32_t ip = (uint32_t)ip_io, op = (uint32_t)op_io;
-  const uint32_t ilim = (uint32_t)iend - 306u, olim = (uint32_t)oend - 606u;
+  const uint32_t ilim = (uint32_t)iend - (uint32_t)LZ4HIP_DECODE_IN_MARGIN, olim = (uint32_t)oend - (uint32_t)LZ4HIP_DECODE_OUT_MARGIN;
   g.ring_begin(lds, dst);
   uint32_t avail, fetched, rf_pos, fl, rlo, mt0;
   uint32_t t4 = g.ld32(src + ip);      // the token word at ip

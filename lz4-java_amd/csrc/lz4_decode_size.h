@@ -46,7 +46,7 @@ LZ4HIP_DEV void decode_size_loop(Grp& g, const uint8_t* src, const int iend, con
   constexpr uint32_t AHEAD = 512u;   // stream bytes a trip may read from ip on: a sequence that starts at window position <= 250 has its offset word at <= 250 + 2 + 254 and reads 4 bytes there
   const uint32_t KS = g.wv_stream();
   uint32_t ip = (uint32_t)ip_io, op = (uint32_t)op_io;
-  const uint32_t ilim = (uint32_t)iend - 306u, olim = (uint32_t)oend - 606u;
+  const uint32_t ilim = (uint32_t)iend - (uint32_t)LZ4HIP_DECODE_IN_MARGIN, olim = (uint32_t)oend - (uint32_t)LZ4HIP_DECODE_OUT_MARGIN;
   g.sz_begin(lds);
   uint32_t lo = g.sz_lo, avail = g.sz_avail;
   const VU lane = g.vlane();

@@ -139,7 +139,7 @@ LZ4HIP_DEV void trio_plan_loop(Grp& g, const uint32_t iend, const uint32_t oend,
   typedef typename Grp::VB VB;
   constexpr uint32_t STEP = 256u, TRIPMAX = 2048u;
   const uint32_t KW = g.wv_ring();
-  const uint32_t ilim = iend - 306u, olim = oend - 606u;
+  const uint32_t ilim = iend - (uint32_t)LZ4HIP_DECODE_IN_MARGIN, olim = oend - (uint32_t)LZ4HIP_DECODE_OUT_MARGIN;
   const uint32_t op0 = op;
   uint32_t head = 0u, tail_seen = 0u, stail = 0u;
   auto post = [&](const VU& w0, const VU& w1) {
@@ -307,7 +307,7 @@ LZ4HIP_DEV void decode_trio_loop(Grp& g, const uint8_t* src, const int iend, uin
   typedef typename Grp::VB VB;
   constexpr uint32_t STEP = 256u;
   uint32_t ip = (uint32_t)ip_io, op = (uint32_t)op_io;
-  const uint32_t ilim = (uint32_t)iend - 306u, olim = (uint32_t)oend - 606u;
+  const uint32_t ilim = (uint32_t)iend - (uint32_t)LZ4HIP_DECODE_IN_MARGIN, olim = (uint32_t)oend - (uint32_t)LZ4HIP_DECODE_OUT_MARGIN;
   g.wv_begin(lds, dst);
   g.pm_begin(lds);
   const uint32_t db = g.wv_dbase();

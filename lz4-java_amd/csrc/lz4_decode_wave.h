@@ -68,7 +68,7 @@ LZ4HIP_DEV void decode_wave_loop(Grp& g, const uint8_t* src, const int iend, uin
   constexpr uint32_t STEP = 256u, PIECE = 252u;
   const uint32_t KW = g.wv_ring(), KS = g.wv_stream();
   uint32_t ip = (uint32_t)ip_io, op = (uint32_t)op_io;
-  const uint32_t ilim = (uint32_t)iend - 306u, olim = (uint32_t)oend - 606u;
+  const uint32_t ilim = (uint32_t)iend - (uint32_t)LZ4HIP_DECODE_IN_MARGIN, olim = (uint32_t)oend - (uint32_t)LZ4HIP_DECODE_OUT_MARGIN;
 
   // ---- the first sequence, from memory: if it is not simple the loop is not entered at all (a block of long runs costs the exact
   // path what it always did, not a seed and a flush per sequence) ----
@@ -292,7 +292,7 @@ LZ4HIP_DEV bool decode_wave_par_loop(Grp& g, const uint8_t* src, const int iend,
                                            // (512: what a 1 KB stream ring always holds in front of ip with one refill step on its way)
   const uint32_t KW = g.wv_ring(), KS = g.wv_stream();
   uint32_t ip = (uint32_t)ip_io, op = (uint32_t)op_io;
-  const uint32_t ilim = (uint32_t)iend - 306u, olim = (uint32_t)oend - 606u;
+  const uint32_t ilim = (uint32_t)iend - (uint32_t)LZ4HIP_DECODE_IN_MARGIN, olim = (uint32_t)oend - (uint32_t)LZ4HIP_DECODE_OUT_MARGIN;
   g.wv_begin(lds, dst);
   const uint32_t db = g.wv_dbase();
   const uint32_t op0 = op;
