@@ -284,7 +284,8 @@ int lz4hip_decompress_safe_chain_batch(const uint8_t* src, const uint64_t* src_o
  *   - out of scope: acceleration above 1; LZ4_saveDict and resuming a stream's exact state across calls (the prefix is LZ4_loadDict's
  *     table, which is not the table a running stream would hold: continuing a stream in a second call gives valid, decodable, but
  *     other bytes than one long chain); sources that are not contiguous; LZ4_attach_dictionary.  (No longer out of scope: an HC form
- *     is lz4hip_compress_hc_chain_batch, below.)                                                                                    */
+ *     is lz4hip_compress_hc_chain_batch, below.)  (No longer out of scope: resuming a stream's exact state across calls, LZ4_saveDict
+ *     included, is lz4hip_compress_fast_stream_batch, below.)                                                                       */
 int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
                                      const int32_t* src_len, const uint32_t* chain_first,
                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
@@ -325,6 +326,58 @@ int lz4hip_compress_hc_chain_batch(const uint8_t* src, const uint64_t* chain_src
                                    const int32_t* src_len, const uint32_t* chain_first,
                                    uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                    int32_t* out_len, uint32_t n_blocks, uint32_t n_chains, int level);
+/* COMPRESS STREAMS THAT ARE CONTINUED BY ANY NUMBER OF CALLS: a set of n_streams compress streams whose state -- the hash table and the
+ * index position, what an LZ4_stream_t carries beside its history -- is RESIDENT ON THE DEVICE between calls.  The arrays of
+ * lz4hip_compress_fast_stream_batch are lz4hip_compress_fast_chain_batch's, with one addition: chain c of a call is the next run of
+ * blocks of stream stream_id[c].  stream_id is STRICTLY ASCENDING: a stream appears at most once per call.
+ * THE CONTRACT: for every stream, the results are byte for byte and return value for return value what ONE LZ4_stream_t of liblz4
+ * 1.9.3 gives over all the calls that ever named the stream since its creation or last reset, however the blocks were cut into calls.
+ *   - a fresh stream (created, or reset) is exactly lz4hip_compress_fast_chain_batch's chain: LZ4_loadDict of chain_prefix_len[c] bytes
+ *     when that is above 0, then LZ4_compress_fast_continue block by block, with all its rules (the 8-byte minimum of a prefix, the
+ *     indexes starting at 65536 behind a prefix, blocks under 13 bytes);
+ *   - a stream that has run before continues in liblz4's prefix mode: the source follows directly behind chain_prefix_len[c] bytes in
+ *     src, and those bytes must be the last bytes the stream consumed (or loaded).  That is the caller who left the data in place, and
+ *     the caller who called LZ4_saveDict(s, buf, k) and put the next block behind buf + k.  The history that counts is
+ *     min(chain_prefix_len[c], 65536, what the stream holds); a shorter one than the stream holds is LZ4_saveDict with a smaller size
+ *     (candidates below it are refused, liblz4's dictSmall rule) and is what the stream holds from then on.  There is no 8-byte
+ *     minimum here.  chain_prefix_len[c] == 0 (or chain_prefix_len == NULL) on a stream that has run is legal and is NOT a reset;
+ *   - out_len, chain_consumed (this call's bytes) and LZ4HIP_CHAIN_STOPPED behave as for the chain call.  A block whose result is 0
+ *     stops its STREAM: the rest of the call's blocks and every block of later calls get LZ4HIP_CHAIN_STOPPED, and nothing is
+ *     consumed, until the stream is reset;
+ *   - the index limit applies to the stream's life: a block with which loaded history + everything consumed since the reset +
+ *     src_len[i] would pass 0x7E000000 gives 0 and stops the stream.  A STREAM CARRIES JUST UNDER 2 GiB BETWEEN RESETS;
+ *   - a call that fails with a library status after its launch leaves EVERY stream it named stopped (on several devices too, where part
+ *     of the call may have succeeded); streams a call does not name are untouched;
+ *   - lz4hip_cstreams_reset makes the n listed streams (NULL: all of them) fresh; lz4hip_cstreams_consumed reports, for the streams
+ *     [first, first + n), the bytes consumed since the reset and whether the stream is stopped (either array may be NULL);
+ *   - calls on one set are serialised (as the streaming-xxhash handles are); different sets are independent.  lz4hip_cstreams_free
+ *     waits for a call in flight but must not race with one: no call may arrive while or after the set is freed.  Sets are freed before
+ *     lz4hip_shutdown();
+ *   - LZ4HIP_E_ARG, said before a device is looked for: a NULL set or required pointer, ids that are not strictly ascending or are
+ *     >= n_streams, a chain_first that is not ascending from 0 to n_blocks, a negative chain_prefix_len[c] or one longer than
+ *     chain_src_off[c].  Without a device lz4hip_cstreams_create and the compress call are LZ4HIP_E_NO_DEVICE;
+ *   - DEVICE MEMORY: a 32 KB table image plus a 32-byte record per stream (65536 streams are about 2 GiB); lz4hip_cstreams_create
+ *     answers LZ4HIP_E_NOMEM.  The streams are divided into contiguous id ranges over the devices initialised at create, and a
+ *     call is sharded at those boundaries;
+ *   - one kernel, compress_fast_stream_cu_kernel: compress_fast_chain_cu_kernel's shape; a wavefront that draws a stream loads its
+ *     table image into LDS (or builds the fresh table), walks the call's blocks and stores table and record back: 64 KB of state
+ *     traffic per stream and call, whatever its blocks' sizes;
+ *   - the host form uploads each chain's source with the last min(chain_prefix_len[c], 65536) bytes in front of it and brings back
+ *     only the bytes produced;
+ *   - out of scope: a device-pointer form (as for lz4hip_compress_hc_chain_batch: left to a change that can also extend the far-offset
+ *     table of the device entry points); acceleration above 1; the external-dictionary mode (a source that does not follow its
+ *     history); LZ4_attach_dictionary; an HC form; streams longer than the index limit.                                             */
+typedef struct lz4hip_cstreams lz4hip_cstreams;
+int lz4hip_cstreams_create(uint32_t n_streams, lz4hip_cstreams** out);
+int lz4hip_cstreams_count(const lz4hip_cstreams* set);
+int lz4hip_cstreams_reset(lz4hip_cstreams* set, const uint32_t* stream_id, uint32_t n);
+int lz4hip_cstreams_consumed(lz4hip_cstreams* set, uint32_t first, uint32_t n, uint64_t* consumed, uint8_t* stopped);
+void lz4hip_cstreams_free(lz4hip_cstreams* set);
+int lz4hip_compress_fast_stream_batch(lz4hip_cstreams* set, const uint32_t* stream_id,
+                                      const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
+                                      const int32_t* src_len, const uint32_t* chain_first,
+                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                      int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains);
 /* COMPRESS AGAINST A DICTIONARY: for every block i, on a fresh stream,
  *     LZ4_loadDict(s, dict, dict_len);  LZ4_compress_fast_continue(s, src_i, dst_i, src_len[i], dst_cap[i], 1)
  * of liblz4 1.9.3 with a dictionary that is NOT contiguous with the source (its external-dictionary mode): the return value and the

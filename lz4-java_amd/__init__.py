@@ -66,6 +66,13 @@ C_ABI = {
     "lz4hip_compress_fast_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32]),
     "lz4hip_compress_fast_chain_batch_dev": (C.c_int, [C.c_void_p] * 10 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_uint32, C.c_int]),
+    "lz4hip_cstreams_create": (C.c_int, [C.c_uint32, C.POINTER(C.c_void_p)]),
+    "lz4hip_cstreams_count": (C.c_int, [C.c_void_p]),
+    "lz4hip_cstreams_reset": (C.c_int, [C.c_void_p, _u32p, C.c_uint32]),
+    "lz4hip_cstreams_consumed": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u64p, C.c_void_p]),
+    "lz4hip_cstreams_free": (None, [C.c_void_p]),
+    "lz4hip_compress_fast_stream_batch": (C.c_int, [C.c_void_p, _u32p, C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p,
+                                                    C.c_uint32, C.c_uint32]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
@@ -990,6 +997,38 @@ class LZ4HIPBatch:
         return list(out[:n]), list(cons[:nc])
 
     @classmethod
+    def compressFastStream(cls, streams, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None):
+        """LZ4_compress_fast_continue on streams that are continued from call to call (lz4hip_compress_fast_stream_batch): the arrays of
+        compressFastChain, and chain c is the next run of blocks of stream streamId[c] of the CompressStreams set `streams` (ids
+        strictly ascending).  For a stream that has run before, chainPrefixLen[c] is how many of the last bytes it consumed lie in front
+        of the source (LZ4_saveDict's size; 0 is legal and no reset) -> (outLen, chainConsumed) as compressFastChain's; a block whose
+        result is 0 stops its STREAM until it is reset"""
+        n, nc = cls._check_chains(src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen)
+        if len(streamId) != nc:
+            raise ValueError("per-chain arrays differ in length")
+        ns = len(streams)
+        if hasattr(streamId, "dtype"):
+            import numpy as np
+            ids = np.asarray(streamId, dtype=np.int64)
+            bad = nc and (ids[0] < 0 or ids[-1] >= ns or (np.diff(ids) <= 0).any())
+        else:
+            bad = any(streamId[c] < 0 or streamId[c] >= ns or (c and streamId[c] <= streamId[c - 1]) for c in range(nc))
+        if bad:
+            raise ValueError("streamId must be strictly ascending and below the number of streams")
+        sp, sk = _ro_ptr(src)
+        dp, dk = _rw_ptr(dst)
+        out = (C.c_int32 * max(n, 1))()
+        cons = (C.c_uint64 * max(nc, 1))()
+        pre = _arr(C.c_int32, chainPrefixLen) if chainPrefixLen is not None else None
+        _chk(lib().lz4hip_compress_fast_stream_batch(streams._handle(), _arr(C.c_uint32, streamId), sp, _arr(C.c_uint64, chainSrcOff), pre,
+                                                     _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst), dp, _arr(C.c_uint64, dstOff),
+                                                     _arr(C.c_int32, dstCap), out, cons, n, nc))
+        if hasattr(srcLen, "dtype"):
+            import numpy as np
+            return np.frombuffer(out, dtype=np.int32, count=n).copy(), np.frombuffer(cons, dtype=np.uint64, count=nc).copy()
+        return list(out[:n]), list(cons[:nc])
+
+    @classmethod
     def decompressSafePartial(cls, src, srcOff, srcLen, dst, dstOff, targetLen, dstCap):
         """LZ4_decompress_safe_partial per block: the first min(targetLen[i], dstCap[i]) bytes of block i into the slot
         dst[dstOff[i]:+dstCap[i]] -> liblz4's return values (lz4hip_decompress_safe_partial_batch; lists, or an int32 array for numpy
@@ -1079,6 +1118,63 @@ class LZ4HIPBatch:
         out = (C.c_uint64 * max(n, 1))()
         _chk(lib().lz4hip_xxh64_batch(p, _arr(C.c_uint64, off), _arr(C.c_int32, length), seed & 0xFFFFFFFFFFFFFFFF, out, n))
         return list(out[:n])
+
+
+class CompressStreams:
+    """A set of n compress streams whose state -- the hash table and index position an LZ4_stream_t carries beside its history -- is
+    resident on the device between calls (lz4hip_cstreams_create): about 32 KB of device memory per stream.  Every stream gives, over
+    all the calls that name it, the bytes ONE LZ4_stream_t of liblz4 gives, however its blocks are cut into calls.  Calls on one set
+    are serialised.  close() -- or leaving a `with` block -- frees it, before lz4hip_shutdown()."""
+
+    def __init__(self, n):
+        self._h = C.c_void_p(None)
+        if n < 1:
+            raise ValueError("a set has at least one stream")
+        _chk(lib().lz4hip_cstreams_create(int(n), C.byref(self._h)))
+
+    def _handle(self):
+        if not self._h:
+            raise AssertionError("Already closed")
+        return self._h
+
+    def __len__(self):
+        return lib().lz4hip_cstreams_count(self._handle())
+
+    def compress(self, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None):
+        """LZ4HIPBatch.compressFastStream on this set"""
+        return LZ4HIPBatch.compressFastStream(self, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen)
+
+    def reset(self, streamId=None):
+        """makes the listed streams (None: all of them) fresh"""
+        if streamId is None:
+            _chk(lib().lz4hip_cstreams_reset(self._handle(), None, 0))
+        else:
+            _chk(lib().lz4hip_cstreams_reset(self._handle(), _arr(C.c_uint32, streamId), len(streamId)))
+
+    def consumed(self, first=0, n=None):
+        """-> (bytes consumed since the reset, stopped) of the streams first .. first + n - 1, two lists"""
+        n = len(self) - first if n is None else n
+        cons = (C.c_uint64 * max(n, 1))()
+        stop = (C.c_uint8 * max(n, 1))()
+        _chk(lib().lz4hip_cstreams_consumed(self._handle(), first, n, cons, stop))
+        return list(cons[:n]), [bool(v) for v in stop[:n]]
+
+    def close(self):
+        if self._h:
+            lib().lz4hip_cstreams_free(self._h)
+            self._h = C.c_void_p(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 # ----------------------------------------------------------------------------------------------

@@ -92,12 +92,14 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // cchain_host_shard, which brings back only the bytes produced, as every compressor's does
 // OP_COMPRESS_HC_CHAIN: LZ4_compress_HC_continue over chains of linked blocks (prefix mode): OP_COMPRESS_CHAIN's arrays and host path
 // (no chain_consumed: a block that returns 0 does not stop its chain), OP_COMPRESS_HC's level and workspace
+// OP_COMPRESS_STREAM: LZ4_compress_fast_continue on streams whose state is resident on the device (lz4hip_cstreams): OP_COMPRESS_CHAIN's
+// arrays and host path, plus the slot of every chain's stream and the device's share of the set's state (BlockCall::cs_*)
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
-          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN, OP_COMPRESS_CHAIN, OP_COMPRESS_HC_CHAIN };
-constexpr int OP_COUNT = OP_COMPRESS_HC_CHAIN + 1;   // (the last enumerator)
+          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN, OP_COMPRESS_CHAIN, OP_COMPRESS_HC_CHAIN, OP_COMPRESS_STREAM };
+constexpr int OP_COUNT = OP_COMPRESS_STREAM + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
-constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN; }
+constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN || op == OP_COMPRESS_STREAM; }
 // a second per-block result (BlockCall::consumed) travels behind out[]
 constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
 // out[i] counts SOURCE bytes read: a block that succeeded filled its whole dst_cap[i]
@@ -107,9 +109,11 @@ constexpr bool op_writes_no_output(Op op) { return op == OP_DECODED_SIZE; }
 // needs the chain-delta workspace (BlockCall::hc_ws / hc_span)
 constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_HC_CHAIN; }
 // its arrays are BlockCall::cchain (chains of linked blocks), its host path cchain_host_shard
-constexpr bool op_takes_cchain(Op op) { return op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN; }
+constexpr bool op_takes_cchain(Op op) { return op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN || op == OP_COMPRESS_STREAM; }
 // a block that returns 0 ends its chain (and chain_consumed[] says how far the chain came)
-constexpr bool op_chain_stops(Op op) { return op == OP_COMPRESS_CHAIN; }
+constexpr bool op_chain_stops(Op op) { return op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_STREAM; }
+// its chains continue resident streams: no 8-byte minimum on the history kept (the device knows what a stream holds), a slot per chain
+constexpr bool op_resumes_streams(Op op) { return op == OP_COMPRESS_STREAM; }
 // its layout kernel needs scratch beside the workspace (BlockCall::hc_scratch)
 constexpr bool op_needs_chain_scratch(Op op) { return op == OP_COMPRESS_HC_CHAIN; }
 
@@ -127,6 +131,11 @@ struct BlockCall {
   const lz4hip::ChainArgs* chain = nullptr;   // OP_DECOMPRESS_CHAIN: the call's arrays on the device
   const lz4hip::CChainArgs* cchain = nullptr; // op_takes_cchain: the call's arrays on the device
   void* hc_scratch = nullptr;           // op_needs_chain_scratch: lz4hip::hc_chain_scratch_bytes of device memory
+  // op_resumes_streams: the device's share of the set's state (kernels.h CStreamArgs) and, on the device, the slot of every chain
+  uint32_t* cs_rec = nullptr; uint64_t* cs_tables = nullptr; const uint32_t* cs_slot = nullptr;
+  // ... and on the host path: the caller's stream ids, the id of the share's slot 0, the set's marks of streams to stop (may be nullptr)
+  const uint32_t* cs_ids = nullptr; uint32_t cs_id0 = 0; const uint8_t* cs_poisoned = nullptr;
+  bool* cs_launched = nullptr;          // (host path, may be nullptr) set once a kernel of the shard has been enqueued
 };
 static_assert(lz4hip::kChainStopped == LZ4HIP_CHAIN_STOPPED, "the kernels' marker is the header's");
 // the handle's bytes on the CURRENT device (uploaded on first use where lz4hip_dict_create found the device not yet initialised):
@@ -387,6 +396,11 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
     case OP_COMPRESS_CHAIN:   // compress_fast_chain_cu_kernel draws chains from the queue word
       if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
       return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_chain(*c.cchain, q, lz4hip::device_cus(), st); });
+    case OP_COMPRESS_STREAM: {   // compress_fast_stream_cu_kernel draws chains from the queue word
+      if (!c.cchain || !c.cs_rec || !c.cs_tables || !c.cs_slot) return fail(LZ4HIP_E_ARG, kNullArg);
+      const lz4hip::CStreamArgs sa{*c.cchain, c.cs_slot, c.cs_rec, c.cs_tables};
+      return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_stream(sa, q, lz4hip::device_cus(), st); });
+    }
     case OP_COMPRESS_HC_CHAIN: {   // layout, segment build and parse kernels behind one scratch allocation
       if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
       // (workspace and scratch are the buffer set's.  As a stream-ordered allocation made here, the scratch read as zeros in the parse
@@ -952,6 +966,8 @@ const char* chain_arg_error(const lz4hip::ChainArgs& a, bool host) {
 // read: up to the first block with a negative length or with which the chain would exceed 0x7E000000 bytes (its result is 0).
 // op_chain_stops(c.op) false (the HC chain): every block's source is read, a negative length counts as 0 bytes, a history of any
 // length is kept, nothing travels in chain_consumed[], and the chunk's workspace is sized by its packed source.
+// op_resumes_streams(c.op) (resident streams): chain c continues stream proto.cs_ids[c]; its slot in the device's share of the set
+// travels in the metadata, with the stop mark of a stream that an earlier call left in an unknown state.
 int cchain_host_shard(const BlockCall& proto, const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
   if (c1 == c0) return LZ4HIP_OK;
   ShardScope sh(ord, err);
@@ -959,7 +975,7 @@ int cchain_host_shard(const BlockCall& proto, const lz4hip::CChainArgs& h, int o
   ChunkSlot& s = sh.pair->slot[0];
   const hipStream_t st = s.st;
   auto keep_of = [&](uint32_t c) -> size_t { const int32_t p = h.chain_prefix_len ? h.chain_prefix_len[c] : 0; return p > 65536 ? 65536u : (size_t)p; };
-  const bool stops = op_chain_stops(proto.op);
+  const bool stops = op_chain_stops(proto.op), resumes = op_resumes_streams(proto.op);
   auto span_of = [&](uint32_t c) -> size_t {   // the source bytes the chain's blocks can consume
     if (!stops) {
       size_t sum = 0;
@@ -967,7 +983,9 @@ int cchain_host_shard(const BlockCall& proto, const lz4hip::CChainArgs& h, int o
       return sum;
     }
     const size_t k = keep_of(c);
-    uint64_t pos = k < 8u ? 0u : k;   // (the kernel's count: a prefix under 8 bytes is not kept)
+    // (the kernel's count: a prefix under 8 bytes is not kept.  A resident stream's count is the device's: every block that can run
+    // in a stream that has consumed nothing is read)
+    uint64_t pos = (k < 8u || resumes) ? 0u : k;
     const uint64_t pos0 = pos;
     for (uint32_t i = h.chain_first[c]; i < h.chain_first[c + 1]; i++) {
       if (h.src_len[i] < 0 || pos + (uint64_t)h.src_len[i] > 0x7E000000ull) break;
@@ -989,7 +1007,7 @@ int cchain_host_shard(const BlockCall& proto, const lz4hip::CChainArgs& h, int o
     cso.resize(nc); dso.resize(nb);
     { size_t o = 0; for (uint32_t t = 0; t < nc; t++) { cso[t] = o + keep_of(c + t); o += al16(keep_of(c + t) + span_of(c + t)); } }
     { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { dso[t] = o; o += al16(pos(h.dst_cap[b0 + t])); } }
-    const staging::CChainMeta m(nb, nc);
+    const staging::CChainMeta m(nb, nc, resumes);
     if (!sh.reserve(s, ck.src, true, ck.dst, m.l.total)) return sh.rc;
     if (op_uses_hc_ws(proto.op) && !sh.ok("staging allocation", s.d_ws.reserve(lz4hip::hc_ws_bytes(ck.src, nb, proto.param)))) return sh.rc;
     // (the layout's scratch for the largest segment count the knob allows, in the buffer set's unused offsets buffer)
@@ -1007,12 +1025,18 @@ int cchain_host_shard(const BlockCall& proto, const lz4hip::CChainArgs& h, int o
     memcpy(m.dst_cap.in(hm), h.dst_cap + b0, m.dst_cap.bytes());
     for (uint32_t t = 0; t <= nc; t++) m.first.in(hm)[t] = h.chain_first[c + t] - b0;
     for (uint32_t t = 0; t < nc; t++) m.prefix.in(hm)[t] = (int32_t)keep_of(c + t);
+    if (resumes)
+      for (uint32_t t = 0; t < nc; t++) {
+        const uint32_t id = proto.cs_ids[c + t];
+        m.slot.in(hm)[t] = (id - proto.cs_id0) | (proto.cs_poisoned && proto.cs_poisoned[id] ? lz4hip::kStreamForceStop : 0u);
+      }
     if (!sh.upload(s, ck.src, m.l, st)) return sh.rc;
     const lz4hip::CChainArgs a{(const uint8_t*)s.d_src.p, m.chain_src_off.in(dm), m.prefix.in(dm), m.src_len.in(dm), m.first.in(dm), (uint8_t*)s.d_dst.p,
                                m.dst_off.in(dm), m.dst_cap.in(dm), m.out.in(dm), stops ? m.consumed.in(dm) : nullptr, nb, nc};
     BlockCall call = proto; call.cchain = &a;
     if (op_uses_hc_ws(proto.op)) { call.hc_ws = s.d_ws.p; call.hc_span = ck.src; }
     if (op_needs_chain_scratch(proto.op)) call.hc_scratch = s.d_poff.p;
+    if (resumes) { call.cs_slot = m.slot.in(dm); if (proto.cs_launched) *proto.cs_launched = true; }
     if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
     memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
     if (stops) memcpy(h.chain_consumed + c, m.consumed.in(hm), m.consumed.bytes());
@@ -1547,6 +1571,46 @@ int lz4hip_container_decode(int kind, int flags, const uint8_t* body, uint64_t b
 #endif
 }  // extern "C"
 
+// ---- resident compress streams (lz4hip_compress_fast_stream_batch) ---------------------------------------------------------
+// A set of n streams whose state -- a record of lz4hip::kStreamRecWords words and a 32 KB table image each (kernels.h CStreamArgs) --
+// lives in device memory between calls.  The streams are divided into contiguous id ranges over the devices the engine was initialised
+// on at create; a call is sharded at those boundaries.  A record of zeros is a fresh stream, so create and reset are memsets.
+struct lz4hip_cstreams {
+  struct Part { int ord = 0; uint32_t lo = 0, hi = 0; uint32_t* rec = nullptr; uint64_t* tables = nullptr; };
+  uint32_t n = 0;
+  std::vector<Part> parts;
+  // streams a call that failed after its launch has named: stopped at their next call (the slot's kStreamForceStop) and reported as
+  // stopped, until they are reset
+  std::vector<uint8_t> poisoned;
+  std::mutex mu;   // calls on one set are serialised, as the streaming-xxhash handles are
+};
+namespace {
+constexpr size_t kStreamRecBytes = lz4hip::kStreamRecWords * sizeof(uint32_t), kStreamTableBytes = 32768;
+void cstreams_release(lz4hip_cstreams* set) {
+  for (auto& p : set->parts) {
+    DeviceGuard g(p.ord);
+    if (p.rec) (void)hipFree(p.rec);
+    if (p.tables) (void)hipFree(p.tables);
+  }
+  delete set;
+}
+// the argument errors of a stream call that can be seen without a device: what does not depend on the set first (so that it is said,
+// and can be tested, where no set can exist), then the set, then the ids against it
+const char* cstream_arg_error(const lz4hip_cstreams* set, const uint32_t* stream_id, const lz4hip::CChainArgs& h) {
+  if (h.n_chains != 0 || h.n_blocks != 0) {
+    if (!stream_id) return kNullArg;
+    if (const char* why = cchain_arg_error(h, true, true)) return why;
+    for (uint32_t c = 1; c < h.n_chains; c++)
+      if (stream_id[c] <= stream_id[c - 1]) return "stream_id must be strictly ascending";
+  }
+  if (!set) return "null stream set";
+  for (uint32_t c = 0; c < h.n_chains; c++) {
+    if (stream_id[c] >= set->n) return "stream_id out of range";
+  }
+  return nullptr;
+}
+}  // namespace
+
 // ---- streaming xxhash (StreamingXXHash32JNI / StreamingXXHash64JNI: XXHashJNI.c:89-145, :199-255) ------------------------
 struct lz4hip_xxh_stream {
   bool is64;
@@ -1822,6 +1886,147 @@ int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_s
   if (n_chains == 0) return LZ4HIP_OK;
   // whole chains per device: a chain never leaves its wavefront, let alone its device
   return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard({OP_COMPRESS_CHAIN}, h, ord, c0, c1, err); });
+}
+int lz4hip_cstreams_create(uint32_t n_streams, lz4hip_cstreams** out) {
+  if (!out || n_streams == 0 || n_streams > 0x7FFFFFFFu) return fail(LZ4HIP_E_ARG, !out ? kNullArg : "n_streams must be 1 .. 2^31 - 1");
+  *out = nullptr;
+  if (const int rc = need_device()) return rc;
+  std::vector<int> devs;
+  { std::lock_guard<std::mutex> lk(g_mu); devs = g_devs; }
+  auto* set = new (std::nothrow) lz4hip_cstreams();
+  if (!set) return fail(LZ4HIP_E_NOMEM, "out of memory");
+  try {
+    set->n = n_streams;
+    set->poisoned.assign(n_streams, 0);
+    const uint32_t D = (uint32_t)std::min<size_t>(devs.size(), n_streams);
+    set->parts.resize(D);
+    for (uint32_t d = 0; d < D; d++) {
+      lz4hip_cstreams::Part& p = set->parts[d];
+      p.ord = devs[d];
+      p.lo = (uint32_t)((uint64_t)n_streams * d / D); p.hi = (uint32_t)((uint64_t)n_streams * (d + 1) / D);
+    }
+  } catch (...) { delete set; return fail(LZ4HIP_E_NOMEM, "out of memory"); }
+  for (auto& p : set->parts) {
+    DeviceGuard g(p.ord);
+    const size_t k = p.hi - p.lo;
+    hipError_t e = g.ok ? hipMalloc((void**)&p.rec, k * kStreamRecBytes) : hipErrorInvalidDevice;
+    if (e == hipSuccess) e = hipMalloc((void**)&p.tables, k * kStreamTableBytes);
+    if (e == hipSuccess) e = hipMemset(p.rec, 0, k * kStreamRecBytes);
+    // (the launches run on non-blocking streams, which are not ordered behind the null stream: the zeros are there before anyone is told)
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      cstreams_release(set);
+      return fail(e == hipErrorOutOfMemory ? LZ4HIP_E_NOMEM : LZ4HIP_E_HIP, "allocation of the streams' state", e);
+    }
+  }
+  *out = set;
+  return LZ4HIP_OK;
+}
+int lz4hip_cstreams_count(const lz4hip_cstreams* set) { return set ? (int)set->n : fail(LZ4HIP_E_ARG, kNullArg); }
+void lz4hip_cstreams_free(lz4hip_cstreams* set) {
+  if (!set) return;
+  // (as lz4hip_xxh_stream_free: a call in flight on another thread ends first, but free must not RACE with a call -- one that arrives
+  // while or after the set is freed uses freed memory; the header says so)
+  { std::lock_guard<std::mutex> lk(set->mu); }
+  cstreams_release(set);
+}
+int lz4hip_cstreams_reset(lz4hip_cstreams* set, const uint32_t* stream_id, uint32_t n) {
+  if (!set) return fail(LZ4HIP_E_ARG, kNullArg);
+  if (stream_id)
+    for (uint32_t i = 0; i < n; i++)
+      if (stream_id[i] >= set->n) return fail(LZ4HIP_E_ARG, "stream_id out of range");
+  std::lock_guard<std::mutex> lk(set->mu);
+  for (auto& p : set->parts) {
+    DeviceGuard g(p.ord);
+    if (!g.ok) return fail(LZ4HIP_E_HIP, "hipSetDevice failed");
+    if (!stream_id) { HIPCHK(hipMemset(p.rec, 0, (size_t)(p.hi - p.lo) * kStreamRecBytes)); continue; }
+    // (runs of consecutive ids are one memset)
+    for (uint32_t i = 0; i < n;) {
+      uint32_t j = i + 1;
+      while (j < n && stream_id[j] == stream_id[j - 1] + 1u) j++;
+      const uint32_t a = std::max(stream_id[i], p.lo), b = std::min(stream_id[j - 1] + 1u, p.hi);
+      if (a < b) HIPCHK(hipMemset((uint8_t*)p.rec + (size_t)(a - p.lo) * kStreamRecBytes, 0, (size_t)(b - a) * kStreamRecBytes));
+      i = j;
+    }
+  }
+  // (the next launch runs on a non-blocking stream, which is not ordered behind the null stream's memsets: wait for them here)
+  for (auto& p : set->parts) {
+    DeviceGuard g(p.ord);
+    if (!g.ok) return fail(LZ4HIP_E_HIP, "hipSetDevice failed");
+    HIPCHK(hipStreamSynchronize(nullptr));
+  }
+  if (!stream_id) std::fill(set->poisoned.begin(), set->poisoned.end(), 0);
+  else for (uint32_t i = 0; i < n; i++) set->poisoned[stream_id[i]] = 0;
+  return LZ4HIP_OK;
+}
+int lz4hip_cstreams_consumed(lz4hip_cstreams* set, uint32_t first, uint32_t n, uint64_t* consumed, uint8_t* stopped) {
+  if (!set || (n && !consumed && !stopped)) return fail(LZ4HIP_E_ARG, kNullArg);
+  if ((uint64_t)first + n > set->n) return fail(LZ4HIP_E_ARG, "stream range out of bounds");
+  std::lock_guard<std::mutex> lk(set->mu);
+  std::vector<uint32_t> words;
+  try { words.resize((size_t)n * lz4hip::kStreamRecWords); } catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
+  for (auto& p : set->parts) {
+    const uint32_t a = std::max(first, p.lo), b = std::min(first + n, p.hi);
+    if (a >= b) continue;
+    DeviceGuard g(p.ord);
+    if (!g.ok) return fail(LZ4HIP_E_HIP, "hipSetDevice failed");
+    HIPCHK(hipMemcpy(words.data() + (size_t)(a - first) * lz4hip::kStreamRecWords, (const uint8_t*)p.rec + (size_t)(a - p.lo) * kStreamRecBytes,
+                     (size_t)(b - a) * kStreamRecBytes, hipMemcpyDeviceToHost));
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t* w = words.data() + (size_t)i * lz4hip::kStreamRecWords;
+    if (consumed) consumed[i] = ((uint64_t)w[5] << 32) | w[4];
+    if (stopped) stopped[i] = ((w[2] & lz4hip::kStreamStopped) || set->poisoned[first + i]) ? 1 : 0;
+  }
+  return LZ4HIP_OK;
+}
+int lz4hip_compress_fast_stream_batch(lz4hip_cstreams* set, const uint32_t* stream_id, const uint8_t* src, const uint64_t* chain_src_off,
+                                      const int32_t* chain_prefix_len, const int32_t* src_len, const uint32_t* chain_first, uint8_t* dst,
+                                      const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks,
+                                      uint32_t n_chains) {
+  const lz4hip::CChainArgs h{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains};
+  if (const char* why = cstream_arg_error(set, stream_id, h)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
+  if (const int rc = need_device()) return rc;
+  if (n_chains == 0) return LZ4HIP_OK;
+  std::lock_guard<std::mutex> lk(set->mu);
+  // whole streams per device, at the boundaries the set was created with: [c0, c1) of the call's chains are part p's
+  struct Share { const lz4hip_cstreams::Part* p; uint32_t c0, c1; int rc = 0; std::string err; bool launched = false; };
+  std::vector<Share> shares;
+  try {
+    for (const auto& p : set->parts) {
+      const uint32_t c0 = (uint32_t)(std::lower_bound(stream_id, stream_id + n_chains, p.lo) - stream_id);
+      const uint32_t c1 = (uint32_t)(std::lower_bound(stream_id, stream_id + n_chains, p.hi) - stream_id);
+      if (c1 > c0) shares.push_back(Share{&p, c0, c1});
+    }
+  } catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  auto run = [&](Share& s) {
+    BlockCall call{OP_COMPRESS_STREAM};
+    call.cs_rec = s.p->rec; call.cs_tables = s.p->tables; call.cs_ids = stream_id; call.cs_id0 = s.p->lo; call.cs_poisoned = set->poisoned.data();
+    call.cs_launched = &s.launched;
+    try { s.rc = cchain_host_shard(call, h, s.p->ord, s.c0, s.c1, &s.err); }
+    catch (...) { s.rc = LZ4HIP_E_NOMEM; s.err = "out of memory"; }
+  };
+  if (shares.size() == 1) {
+    run(shares[0]);
+  } else {
+    std::vector<std::thread> th;
+    try { for (auto& s : shares) th.emplace_back([&run, &s] { run(s); }); }
+    catch (...) { for (auto& t : th) t.join(); if (prev >= 0) (void)hipSetDevice(prev); return fail(LZ4HIP_E_NOMEM, "out of memory or threads"); }
+    for (auto& t : th) t.join();
+  }
+  if (prev >= 0) (void)hipSetDevice(prev);
+  // the call failed after a launch: some of the streams it named have gone on and some have not, and the caller has no results to tell
+  // which, so EVERY stream the call named is stopped until it is reset (those of the shares that succeeded too)
+  bool failed = false, launched = false;
+  for (auto& s : shares) { failed |= s.rc != 0; launched |= s.launched; }
+  if (failed && launched)
+    for (uint32_t c = 0; c < n_chains; c++) set->poisoned[stream_id[c]] = 1;
+  for (auto& s : shares)
+    if (s.rc) return fail(s.rc, s.err.c_str());
+  return LZ4HIP_OK;
 }
 int lz4hip_compress_hc_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
                                    const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,

@@ -450,6 +450,48 @@ int launch_compress_fast_chain(const CChainArgs& a, uint32_t* q, uint32_t n_cus,
   return launch_queue_kernel(compress_fast_chain_cu_kernel, a.n_chains, q, 1u, n_cus, stream, a, q);
 }
 
+// LZ4_compress_fast_continue on streams whose state is resident on the device: the chain kernel's shape and lz4_fast_chain.h's
+// cstream_walk.  A wavefront that draws chain c loads the stream's 32 KB table image from device memory into its LDS (or builds the
+// fresh table), walks the call's blocks and stores table and record back.  The state was written by an earlier launch and is read
+// through ordinary global loads; one wavefront owns a stream for the whole launch (the host hands every slot out once), so nothing
+// inside a launch needs a fence.  The image moves 16 bytes per lane, 1 KB per instruction, both ways.
+struct CStreamIoDev : CChainIoDev {
+  __device__ __forceinline__ void begin_state(const uint8_t*) const {}
+  __device__ __forceinline__ void end_state() const {}
+  __device__ __forceinline__ static void table_load(WaveDev& w, const uint8_t* image) {
+    const uint4* g = (const uint4*)image;
+    uint4* t = (uint4*)w.lds;
+    for (uint32_t i = __lane_id(); i < LZ4HIP_TABLE_U64 / 2u; i += 64u) t[i] = g[i];
+    WaveDev::sync();
+  }
+  __device__ __forceinline__ static void table_store(WaveDev& w, uint8_t* image) {
+    uint4* g = (uint4*)image;
+    const uint4* t = (const uint4*)w.lds;
+    for (uint32_t i = __lane_id(); i < LZ4HIP_TABLE_U64 / 2u; i += 64u) g[i] = t[i];
+  }
+  __device__ __forceinline__ static void put_rec(uint32_t* rec, uint32_t idx, uint32_t held, uint32_t flags, uint32_t span, uint64_t total) {
+    if (__lane_id() == 0) { rec[0] = idx; rec[1] = held; rec[2] = flags; rec[3] = span; rec[4] = (uint32_t)total; rec[5] = (uint32_t)(total >> 32); }
+  }
+};
+__global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_stream_cu_kernel(CStreamArgs a, uint32_t* q) {
+  __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
+  WaveDev w(tables[threadIdx.x >> 6]);
+  CStreamIoDev io{{a.c}};
+  for (;;) {
+    uint32_t c = 0;
+    if (__lane_id() == 0) c = atomicAdd(q, 1u);
+    c = __builtin_amdgcn_readfirstlane(c);
+    if (c >= a.c.n_chains) return;
+    cstream_walk(w, io, a, c);
+    WaveDev::sync();  // the table is reused: the next stream loads or builds its own
+  }
+}
+int launch_compress_fast_stream(const CStreamArgs& a, uint32_t* q, uint32_t n_cus, void* stream) {
+  if (a.c.n_chains == 0) return 0;
+  if (!q || !a.slot || !a.rec || !a.tables) return (int)hipErrorInvalidValue;
+  return launch_queue_kernel(compress_fast_stream_cu_kernel, a.c.n_chains, q, 1u, n_cus, stream, a, q);
+}
+
 // LZ4_compress_destSize: the one-sequence-per-step core (acceleration 1) with DirectOut's FILL switch on; dst_cap[b] is the target.  A
 // block whose target is full stops at the next step, so the steps spent on it follow the input it consumes, not src_len.
 __global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_dest_cu_kernel(BatchArgs a, int32_t* consumed, uint32_t* q) {

@@ -53,12 +53,13 @@ struct ChainMeta {   // chain decode (chain_host_shard): nb blocks in nc chains;
         dst_cap(l.input<int32_t>(nb)), prefix(l.input<int32_t>(nc)), first(l.input<uint32_t>(nc + 1)), stored(l.input<uint8_t>(nb)),
         chain_out(l.result<uint64_t>(nc, true)), out(l.result<int32_t>(nb)) {}
 };
-struct CChainMeta {   // chain compress (cchain_host_shard): out[] and chain_consumed[] go up zeroed
+struct CChainMeta {   // chain compress (cchain_host_shard): out[] and chain_consumed[] go up zeroed; slot[] only for resident streams
   MetaLayout l;
-  Region<uint64_t> chain_src_off, dst_off; Region<int32_t> src_len, dst_cap, prefix; Region<uint32_t> first; Region<uint64_t> consumed; Region<int32_t> out;
-  CChainMeta(size_t nb, size_t nc)
+  Region<uint64_t> chain_src_off, dst_off; Region<int32_t> src_len, dst_cap, prefix; Region<uint32_t> first, slot; Region<uint64_t> consumed; Region<int32_t> out;
+  CChainMeta(size_t nb, size_t nc, bool has_slot = false)
       : chain_src_off(l.input<uint64_t>(nc)), dst_off(l.input<uint64_t>(nb)), src_len(l.input<int32_t>(nb)), dst_cap(l.input<int32_t>(nb)),
-        prefix(l.input<int32_t>(nc)), first(l.input<uint32_t>(nc + 1)), consumed(l.result<uint64_t>(nc, true)), out(l.result<int32_t>(nb, true)) {}
+        prefix(l.input<int32_t>(nc)), first(l.input<uint32_t>(nc + 1)), slot(l.input<uint32_t>(has_slot ? nc : 0)),
+        consumed(l.result<uint64_t>(nc, true)), out(l.result<int32_t>(nb, true)) {}
 };
 template <class T>
 struct HashMeta {   // the hashes (xxh_shard): T = uint32_t / uint64_t

@@ -140,6 +140,22 @@ struct CChainArgs {
 // compress_fast_chain_cu_kernel: five wavefronts per CU, a 32 KB table each, draw chains from the queue word q (one device uint32_t of
 // scratch); the table stays in LDS from one block of a chain to the next; no wavefront waits for another.  n_cus = compute units
 int launch_compress_fast_chain(const CChainArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
+// LZ4_compress_fast_continue on streams whose state stays on the device between launches (compress_fast.hip, lz4_fast_chain.h
+// cstream_walk).  Chain c of `c` is the next run of blocks of the stream in slot (slot[c] & 0x7FFFFFFF); bit 31 set: the stream is stopped
+// before the walk (the host's mark of a call that failed half way).  Slot s owns the record rec[s * kStreamRecWords ..] and the table
+// image tables[s * 4096 ..] (32 KB).  A record of zeros is a fresh stream.  Record words:
+//   [0] the stream index of the next byte (liblz4's currentOffset)   [1] the history the stream holds, capped at 65536 (its dictSize)
+//   [2] flags (kStream*)   [3] loaded history + bytes consumed, what the 0x7E000000 limit counts   [4], [5] bytes consumed, low and high
+// No slot may appear twice in a launch: one wavefront owns a stream from the load of its state to the store.
+constexpr uint32_t kStreamRecWords = 8;
+constexpr uint32_t kStreamUsed = 1u, kStreamTable = 2u, kStreamStopped = 4u, kStreamPrefixed = 8u;   // ran before; the image is the table; stopped; began with LZ4_loadDict
+constexpr uint32_t kStreamForceStop = 0x80000000u;
+struct CStreamArgs {
+  CChainArgs c; const uint32_t* slot; uint32_t* rec; uint64_t* tables;
+};
+// compress_fast_stream_cu_kernel: compress_fast_chain_cu_kernel's shape; a wavefront that draws a chain loads the stream's table into
+// its LDS (or builds the fresh one), walks the call's blocks and stores table and record back
+int launch_compress_fast_stream(const CStreamArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
 // LZ4_compress_HC_continue over chains of linked blocks, prefix mode (compress_hc.hip): CChainArgs as above with chain_consumed unused
 // (nullptr); the history is what LZ4_loadDictHC keeps (its last 64 KB, no minimum).  out[i] = liblz4's return value; a block that
 // returns 0 (it does not fit, or src_len[i] / dst_cap[i] is negative) does NOT stop its chain: its source is history for the blocks

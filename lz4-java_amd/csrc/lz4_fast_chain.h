@@ -1,6 +1,7 @@
 // lz4_fast_chain.h -- the walk over one chain of linked blocks on the compressing side (LZ4_compress_fast_continue, liblz4 1.9.3,
 // acceleration 1), shared by compress_fast.hip (compress_fast_chain_cu_kernel) and the CPU lane simulator
-// (tests/hostsim/hostsim_cchain.cpp).
+// (tests/hostsim/hostsim_cchain.cpp); behind it, the same walk for streams whose state stays on the device between launches
+// (cstream_walk: compress_fast_stream_cu_kernel, tests/hostsim/hostsim_cstream.cpp).
 //
 // A chain is a run of blocks whose SOURCES lie back to back; block k may match into the blocks before it and into the history that
 // lies directly in front of the chain.  liblz4 defines block k's result as
@@ -52,6 +53,7 @@ LZ4HIP_DEV void link_table_init(W& w, const uint8_t* buf, uint32_t keep, bool pr
   }
 }
 
+// (cstream_walk below holds a copy of this block loop: a change here is to be made there as well)
 template <class W, class Io>
 LZ4HIP_DEV void cchain_walk(W& w, Io& io, const CChainArgs& a, uint32_t c) {
   using Core = FastCore<W, false, DirectOut<W>, false, false, false, true>;
@@ -89,6 +91,109 @@ LZ4HIP_DEV void cchain_walk(W& w, Io& io, const CChainArgs& a, uint32_t c) {
   }
   for (; i < b1; i++) io.put_out(i, kChainStopped);
   io.put_chain(c, (uint64_t)(pos - keep));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The same walk for a stream whose state outlives the launch (compress_fast_stream_cu_kernel, tests/hostsim/hostsim_cstream.cpp):
+// chain c of the call is the next run of blocks of the stream in slot s.slot[c], and what ONE LZ4_stream_t would carry from call to call
+// -- its table, its index position, the history it holds -- is loaded from the slot before the walk and stored back behind it
+// (kernels.h CStreamArgs: the record's words).  (A walk of its own beside cchain_walk, not a switch in it: cchain_walk's kernel keeps
+// the instructions it has -- even the per-block body alone, as one inline helper for both walks, changed them: 3202 -> 3189, DESIGN.md
+// 2.1.  A change to the block loop there is to be made here as well.)
+//   * a fresh stream (a record of zeros) is cchain_walk's chain, rule for rule; with a prefix of 8 bytes and more its table is built
+//     before the first block, not at the first block that probes: the loaded bytes need not be in front of a later call's source;
+//   * a stream that has run continues in liblz4's prefix mode: the source follows kept = min(chain_prefix_len, 65536, held) bytes of its
+//     history (no 8-byte minimum: that is LZ4_loadDict's).  kept < held is LZ4_saveDict with a smaller size.  buf[0] is index
+//     idx - kept, and that is the lower bound of a candidate whatever the table holds: where liblz4 does not check it (held >= 64 KB, or
+//     held == idx) the 65535-byte distance rule or index 0 imply it, so an entry that points in front of this call's buf is never read;
+//   * a stream that has seen only blocks under 13 bytes has no table yet.  Its empty buckets are index 0.  With idx - kept > 0 index 0 is
+//     below the bound for good (the bound never falls: held only grows by what is consumed), so the fingerprint does not matter and
+//     the buckets are zeros; with idx - kept == 0 the stream's first four bytes are buf[0 .. 4) and the fingerprint is theirs;
+//   * the 0x7E000000 limit counts loaded history + everything consumed since the reset + src_len: the one-call chain's count;
+//   * a block whose result is 0 stops the STREAM: the record keeps kStreamStopped until the host zeroes it (reset).
+// Io, beyond cchain_walk's: begin_state(image) / end_state(): the walk is about to read or write the slot's 32 KB image, and is done
+// (the simulator's bounds); table_load(w, image) / table_store(w, image): the image to and from w's table, wave-wide; put_rec(rec, ...):
+// the record's words, from lane 0.
+template <class W, class Io>
+LZ4HIP_DEV void cstream_walk(W& w, Io& io, const CStreamArgs& s, uint32_t c) {
+  using Core = FastCore<W, false, DirectOut<W>, false, false, false, true>;
+  const CChainArgs& a = s.c;
+  uint32_t b1 = io.uni(a.chain_first[c + 1]), b0 = io.uni(a.chain_first[c]);
+  if (b1 > a.n_blocks) b1 = a.n_blocks;
+  if (b0 > b1) b0 = b1;
+  const uint32_t sv = io.uni(s.slot[c]), slot = sv & ~kStreamForceStop;
+  uint32_t* const rec = io.uni_ptr(s.rec + (size_t)slot * kStreamRecWords);
+  uint8_t* const image = (uint8_t*)io.uni_ptr(s.tables + (size_t)slot * (1u << Core::HLOG));
+  uint32_t idx = io.uni(rec[0]), held = io.uni(rec[1]), flags = io.uni(rec[2]), span = io.uni(rec[3]);
+  uint64_t total = ((uint64_t)io.uni(rec[5]) << 32) | io.uni(rec[4]);
+  uint32_t i = b0;
+  if ((sv & kStreamForceStop) || (flags & kStreamStopped)) {
+    for (; i < b1; i++) io.put_out(i, kChainStopped);
+    io.put_chain(c, 0u);
+    io.put_rec(rec, idx, held, flags | kStreamStopped, span, total);
+    return;
+  }
+  const uint64_t soff = io.uni64(a.chain_src_off[c]);
+  uint64_t P = 0;
+  if (a.chain_prefix_len) { const int32_t p = (int32_t)io.uni((uint32_t)a.chain_prefix_len[c]); P = p > 0 ? (uint64_t)p : 0u; }
+  if (P > soff) P = soff;
+  const bool fresh = !(flags & kStreamUsed);
+  uint32_t kept;
+  if (fresh) {
+    kept = P < 8u ? 0u : (P > 65536u ? 65536u : (uint32_t)P);
+    idx = P ? 65536u : 0u;
+    held = kept; span = kept; total = 0u;
+    flags = kStreamUsed | (P ? kStreamPrefixed : 0u);
+  } else {
+    kept = P > held ? held : (uint32_t)P;   // (held <= 65536)
+  }
+  const uint32_t ibase = idx - kept;
+  const uint8_t* const buf = io.uni_ptr(a.src + soff - kept);
+  uint32_t pos = kept;       // where the next block starts in buf
+  bool table_ready = (flags & kStreamTable) != 0u, dirty = false;
+  if (table_ready) {
+    io.begin_state(image);
+    io.table_load(w, image);
+    io.end_state();
+  } else if (fresh && kept) {
+    io.begin_block(buf, kept, nullptr, 0u);
+    link_table_init(w, buf, kept, true);
+    table_ready = dirty = true;
+  }
+  bool stopped = false;
+  while (i < b1) {
+    const int32_t sl = (int32_t)io.uni((uint32_t)a.src_len[i]), dc = (int32_t)io.uni((uint32_t)a.dst_cap[i]);
+    uint32_t r = 0;
+    if (sl >= 0 && dc >= 0 && (uint64_t)span + (uint32_t)sl <= kChainSpanMax) {
+      const uint32_t end = pos + (uint32_t)sl;
+      uint8_t* d = io.uni_ptr(a.dst + io.uni64(a.dst_off[i]));
+      io.begin_block(buf, end, d, (uint32_t)dc);
+      if (sl >= 13) {
+        if (!table_ready) { link_table_init(w, buf, 0u, (flags & kStreamPrefixed) != 0u || ibase != 0u); table_ready = true; }
+        dirty = true;
+      }
+      DirectOut<W> out(w, buf, end, d, (uint32_t)dc);
+      out.limited = (uint32_t)dc < (uint32_t)sl + (uint32_t)sl / 255u + 16u;   // (by the block's length, not by its end in buf)
+      Core core(w, out, buf, end);
+      core.blk = pos; core.ibase = ibase; core.lowidx = ibase;
+      r = core.run();
+    }
+    io.put_out(i, (int32_t)r);
+    i++;
+    if (r == 0u) { stopped = true; break; }
+    pos += (uint32_t)sl; span += (uint32_t)sl;
+  }
+  for (; i < b1; i++) io.put_out(i, kChainStopped);
+  io.put_chain(c, (uint64_t)(pos - kept));
+  // a stopped stream's table is never read again
+  if (table_ready && dirty && !stopped) {
+    w.sync();
+    io.begin_state(image);
+    io.table_store(w, image);
+    io.end_state();
+  }
+  io.put_rec(rec, ibase + pos, pos > 65536u ? 65536u : pos, flags | (table_ready ? kStreamTable : 0u) | (stopped ? kStreamStopped : 0u), span,
+             total + (uint64_t)(pos - kept));
 }
 
 }  // namespace lz4hip

@@ -10,6 +10,8 @@
 //                                                   =  LZ4_decompress_safe_usingDict of liblz4's main API against a dictionary that is not
 //                                                      contiguous with the destination (no reference entry reaches it)
 //   LZ4HIPBatch::compressFastChain                  =  LZ4_compress_fast_continue over chains of linked blocks (liblz4's prefix mode)
+//   CompressStreams                                 =  LZ4_compress_fast_continue on streams that go on from call to call: ONE LZ4_stream_t each,
+//                                                      its state resident on the device (LZ4_saveDict through chainPrefixLen)
 //   LZ4HIPBatch::compressHCChain                    =  LZ4_compress_HC_continue over chains of linked blocks (prefix mode; not serial)
 //   LZ4HIPBatch::decompressSafeChain                =  LZ4_decompress_safe_continue over chains of linked blocks (liblz4's rolling-prefix
 //                                                      mode; no reference entry reaches it)
@@ -429,6 +431,61 @@ struct LZ4HIPBatch {
     }
     return r;
   }
+};
+
+// A set of n compress streams whose state -- the hash table and index position an LZ4_stream_t carries beside its history -- is resident
+// on the device between calls (lz4hip_cstreams_create; about 32 KB of device memory per stream).  compress(): the arrays of
+// LZ4HIPBatch::compressFastChain, and chain c is the next run of blocks of stream streamId[c] (strictly ascending).  Every stream gives,
+// over all the calls that name it, the bytes ONE LZ4_stream_t of liblz4 gives, however its blocks are cut into calls; for a stream
+// that has run, chainPrefixLen[c] is how many of the last bytes it consumed lie in front of the source (LZ4_saveDict's size; 0 is
+// legal and no reset).  A block whose result is 0 stops its stream until reset().  Calls on one set are serialised; the set is
+// destroyed before lz4hip_shutdown().
+class CompressStreams {
+ public:
+  explicit CompressStreams(uint32_t n) { LZ4HIPBatch::status(lz4hip_cstreams_create(n, &h_)); }
+  ~CompressStreams() { lz4hip_cstreams_free(h_); }
+  CompressStreams(const CompressStreams&) = delete;
+  CompressStreams& operator=(const CompressStreams&) = delete;
+  uint32_t size() const { return (uint32_t)lz4hip_cstreams_count(h_); }
+  LZ4HIPBatch::Chains compress(const std::vector<uint32_t>& streamId, const bytes& src, const std::vector<uint64_t>& chainSrcOff,
+                               const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst, bytes& dest,
+                               const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen,
+                               const std::vector<int32_t>& chainPrefixLen = {}) {
+    LZ4HIPBatch::checkChains(src, chainSrcOff, srcLen, chainFirst, dest, destOff, maxDestLen, chainPrefixLen);
+    const size_t n = srcLen.size(), nc = chainSrcOff.size();
+    if (streamId.size() != nc) throw std::invalid_argument("per-chain arrays differ in length");
+    for (size_t c = 0; c < nc; c++)
+      if (streamId[c] >= size() || (c && streamId[c] <= streamId[c - 1]))
+        throw std::invalid_argument("streamId must be strictly ascending and below the number of streams");
+    LZ4HIPBatch::Chains r;
+    r.lengths.assign(n, 0);
+    r.chainLengths.assign(nc, 0);
+    bytes one(1);                                 // (an empty buffer still hands the library a pointer)
+    int32_t none = 0;
+    uint32_t none32 = 0;
+    uint64_t none64 = 0;
+    LZ4HIPBatch::status(lz4hip_compress_fast_stream_batch(h_, nc ? streamId.data() : &none32, src.empty() ? one.data() : src.data(),
+                                                          nc ? chainSrcOff.data() : &none64, chainPrefixLen.empty() ? nullptr : chainPrefixLen.data(),
+                                                          n ? srcLen.data() : &none, chainFirst.data(), dest.empty() ? one.data() : dest.data(),
+                                                          n ? destOff.data() : &none64, n ? maxDestLen.data() : &none, n ? r.lengths.data() : &none,
+                                                          nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
+    return r;
+  }
+  void reset() { LZ4HIPBatch::status(lz4hip_cstreams_reset(h_, nullptr, 0)); }
+  void reset(const std::vector<uint32_t>& streamId) {
+    if (!streamId.empty()) LZ4HIPBatch::status(lz4hip_cstreams_reset(h_, streamId.data(), (uint32_t)streamId.size()));
+  }
+  struct State { std::vector<uint64_t> consumed; std::vector<uint8_t> stopped; };
+  State consumed(uint32_t first, uint32_t n) {
+    State s;
+    s.consumed.assign(n, 0);
+    s.stopped.assign(n, 0);
+    if (n) LZ4HIPBatch::status(lz4hip_cstreams_consumed(h_, first, n, s.consumed.data(), s.stopped.data()));
+    return s;
+  }
+
+ private:
+  lz4hip_cstreams* h_ = nullptr;
 };
 
 class LZ4FastDecompressor {

@@ -221,6 +221,26 @@ inline Compressed compressChain(const BatchEngine& e, const bytes& history, cons
   for (int32_t s : c.sizes) if (s <= 0) throw LZ4Exception("maxDestLen is too small");
   return c;
 }
+// the same blocks as the next run of blocks of stream 0 of `streams` (the frame's own resident stream), which has consumed `history`
+// (at most its last 64 KB) before
+inline Compressed compressStream(CompressStreams& streams, const bytes& history, const bytes& data, int blockSize) {
+  Compressed c;
+  const size_t n = (data.size() + (size_t)blockSize - 1) / (size_t)blockSize;
+  c.bound = maxCompressedLength(blockSize);
+  c.dst.resize(n * (size_t)c.bound);
+  std::vector<uint64_t> d_o(n);
+  std::vector<int32_t> dc(n, c.bound);
+  c.lens.resize(n);
+  for (size_t i = 0; i < n; i++) {
+    c.lens[i] = (int32_t)std::min<size_t>((size_t)blockSize, data.size() - i * (size_t)blockSize);
+    d_o[i] = i * (size_t)c.bound;
+  }
+  bytes src(history);
+  src.insert(src.end(), data.begin(), data.end());
+  c.sizes = streams.compress({0u}, src, {(uint64_t)history.size()}, c.lens, {0u, (uint32_t)n}, c.dst, d_o, dc, {(int32_t)history.size()}).lengths;
+  for (int32_t s : c.sizes) if (s <= 0) throw LZ4Exception("maxDestLen is too small");
+  return c;
+}
 }  // namespace detail
 
 // =====================================================================================================
@@ -271,6 +291,10 @@ class LZ4FrameOutputStream {
   // < 1 -> 9, > 12 -> 12) behind the last 64 KB written.  A block of an HC chain depends on the 64 KB in front of it and on nothing
   // else: the frame's bytes do not depend on batchBlocks, and the blocks of a batch are parsed at the same time, a wavefront each --
   // here a single stream does fill the device.
+  // streamState(true), before the first write (the fast chain only; off by default, whose bytes are unchanged): the frame is ONE compress
+  // stream whose table and index position stay on the device from batch to batch (a CompressStreams set of one, made at the first
+  // batch), so the blocks are what ONE LZ4_stream_t writes for the whole frame and the frame's bytes do not depend on batchBlocks or on
+  // flush() calls that fall on block boundaries.
   LZ4FrameOutputStream(std::ostream& out, frame::BLOCKSIZE blockSize = frame::SIZE_4MB, int64_t knownSize = -1,
                        std::initializer_list<frame::Bits> bits = {frame::BLOCK_INDEPENDENCE}, BatchEngine engine = BatchEngine(),
                        size_t batchBlocks = 64, bool linkedBlocks = false)
@@ -300,6 +324,11 @@ class LZ4FrameOutputStream {
     if (buf_.size() >= batch_ * (size_t)maxBlockSize_) writeBlocks(buf_.size() / (size_t)maxBlockSize_ * (size_t)maxBlockSize_);
   }
   void write(const bytes& b) { write(b.data(), b.size()); }
+  void streamState(bool on) {
+    if (on && (!linked_ || hc_)) throw std::invalid_argument("streamState continues the fast chain's stream: it needs linkedBlocks = true and no level");
+    if (wroteBlocks_ || finished_) throw IllegalStateException("streamState is chosen before the first block is written");
+    streamState_ = on;
+  }
   void flush() { if (!finished_) { writeBlocks(buf_.size()); out_.flush(); } }  // :279-286: flush() writes the pending (possibly short) block
   void close() {                                                                  // :289-298
     if (finished_) return;
@@ -329,7 +358,11 @@ class LZ4FrameOutputStream {
       out_.write((const char*)blocks.data(), (std::streamsize)blocks.size());
       return;
     }
-    const detail::Compressed c = linked_ ? detail::compressChain(e_, history_, data, maxBlockSize_, hc_, level_) : detail::compressBlocks(e_, data, maxBlockSize_);
+    wroteBlocks_ = true;
+    if (linked_ && streamState_ && !streams_) streams_.reset(new CompressStreams(1));
+    const detail::Compressed c = linked_ ? (streamState_ ? detail::compressStream(*streams_, history_, data, maxBlockSize_)
+                                                         : detail::compressChain(e_, history_, data, maxBlockSize_, hc_, level_))
+                                         : detail::compressBlocks(e_, data, maxBlockSize_);
     if (linked_) {   // the last 64 KB written
       history_.insert(history_.end(), data.begin(), data.end());
       if (history_.size() > 65536) history_.erase(history_.begin(), history_.end() - 65536);
@@ -373,6 +406,9 @@ class LZ4FrameOutputStream {
   bool hc_ = false;       // (linked_) the HC chain at level_ instead of the fast chain
   int level_ = 0;
   bytes history_;         // (linked_) the last 64 KB written of the frame
+  bool wroteBlocks_ = false;                   // a batch has gone to the compressor: the frame's way of compressing is fixed
+  bool streamState_ = false;                   // (linked_, fast chain) one resident stream for the whole frame
+  std::unique_ptr<CompressStreams> streams_;   // ... made at the first batch
 };
 
 class LZ4FrameInputStream {

@@ -154,6 +154,100 @@ public final class LZ4HIPBatch {
   }
 
   /**
+   * liblz4's {@code LZ4_compress_fast_continue} on streams that go on from call to call: the arrays of {@link #compressFastChain}, and
+   * chain c is the next run of blocks of stream {@code streamId[c]} of {@code streams} (strictly ascending: a stream once per call).
+   * Every stream gives, over all the calls that name it, the bytes ONE {@code LZ4_stream_t} gives, however its blocks are cut into
+   * calls.  For a stream that has run, {@code chainPrefixLen[c]} is how many of the last bytes it consumed lie in front of the source
+   * ({@code LZ4_saveDict}'s size; 0 is legal and no reset).  A block whose result is 0 stops its stream -- {@link #CHAIN_STOPPED} from
+   * then on -- until {@link CompressStreams#reset}.
+   */
+  public static void compressFastStream(CompressStreams streams, int[] streamId, ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen,
+      int[] srcLen, int[] chainFirst, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed) {
+    if (chainConsumed.length != chainSrcOff.length || streamId.length != chainSrcOff.length) {
+      throw new IllegalArgumentException("per-chain arrays differ in length");
+    }
+    final int ns = streams.size();
+    for (int c = 0; c < streamId.length; c++) {
+      if (streamId[c] < 0 || streamId[c] >= ns || (c > 0 && streamId[c] <= streamId[c - 1])) {
+        throw new IllegalArgumentException("streamId must be strictly ascending and below the number of streams");
+      }
+    }
+    checkChains(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen);
+    final int rc = LZ4HIPJNI.LZ4HIP_batchFastStream(streams.handle(), streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff,
+        destCap, outLen, chainConsumed, srcLen.length, chainSrcOff.length);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /**
+   * A set of compress streams whose state -- the hash table and index position an {@code LZ4_stream_t} carries beside its history -- is
+   * resident on the device between calls (about 32 KB of device memory per stream).  Calls on one set are serialised; close it before
+   * the library is shut down.
+   */
+  public static final class CompressStreams implements java.io.Closeable {
+    private long handle;
+
+    public CompressStreams(int nStreams) {
+      if (nStreams < 1) {
+        throw new IllegalArgumentException("a set has at least one stream");
+      }
+      handle = LZ4HIPJNI.LZ4HIP_cstreamsCreate(nStreams);
+      if (handle == 0) {
+        throw new LZ4Exception("liblz4hip: " + LZ4HIPJNI.lastError());
+      }
+    }
+
+    long handle() {
+      if (handle == 0) {
+        throw new IllegalStateException("Already closed");
+      }
+      return handle;
+    }
+
+    public int size() {
+      return LZ4HIPJNI.LZ4HIP_cstreamsCount(handle());
+    }
+
+    /** {@link LZ4HIPBatch#compressFastStream} on this set */
+    public void compress(int[] streamId, ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
+        ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed) {
+      compressFastStream(this, streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed);
+    }
+
+    /** makes the listed streams ({@code null}: all of them) fresh */
+    public void reset(int[] streamId) {
+      final int rc = LZ4HIPJNI.LZ4HIP_cstreamsReset(handle(), streamId, streamId == null ? 0 : streamId.length);
+      if (rc != 0) {
+        throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+      }
+    }
+
+    /** the bytes consumed since the reset, and whether the stream is stopped, for the streams first .. first + consumed.length - 1 */
+    public void consumed(int first, long[] consumed, boolean[] stopped) {
+      if (stopped.length != consumed.length) {
+        throw new IllegalArgumentException("arrays differ in length");
+      }
+      final int[] st = new int[consumed.length];
+      final int rc = LZ4HIPJNI.LZ4HIP_cstreamsConsumed(handle(), first, consumed.length, consumed, st);
+      if (rc != 0) {
+        throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+      }
+      for (int i = 0; i < st.length; i++) {
+        stopped[i] = st[i] != 0;
+      }
+    }
+
+    @Override
+    public synchronized void close() {
+      if (handle != 0) {
+        LZ4HIPJNI.LZ4HIP_cstreamsFree(handle);
+        handle = 0;
+      }
+    }
+  }
+
+  /**
    * liblz4's {@code LZ4_compress_HC_continue} over chains of linked blocks (its prefix mode) at HC level {@code level} (&lt; 1: 9, &gt; 12: 12):
    * the arrays of {@link #compressFastChain} without {@code chainConsumed}.  outLen[i] &gt; 0: the compressed size; 0: it did not fit --
    * which does NOT end the chain: the block's source is history for the blocks behind it, and no block gets {@link #CHAIN_STOPPED}.  Not

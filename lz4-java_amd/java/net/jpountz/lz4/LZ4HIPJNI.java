@@ -117,6 +117,21 @@ enum LZ4HIPJNI {
   static native int LZ4HIP_batchFastChain(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
                                           ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed,
                                           int nBlocks, int nChains);
+  /* Resident compress streams (lz4hip_cstreams_*): cstreamsCreate returns the handle of a set of nStreams streams, or 0 (lastError() says
+   * why); cstreamsCount the number of streams; cstreamsFree takes 0 too; cstreamsReset makes the n listed streams fresh (null: all);
+   * cstreamsConsumed fills consumed[i] / stopped[i] (!= 0: stopped) for the streams first .. first + n - 1.  Reset and consumed return 0
+   * or a negative lz4hip_status (a 0 handle or a null required array: LZ4HIP_E_ARG). */
+  static native long LZ4HIP_cstreamsCreate(int nStreams);
+  static native int LZ4HIP_cstreamsCount(long set);
+  static native void LZ4HIP_cstreamsFree(long set);
+  static native int LZ4HIP_cstreamsReset(long set, int[] streamId, int n);
+  static native int LZ4HIP_cstreamsConsumed(long set, int first, int n, long[] consumed, int[] stopped);
+  /* LZ4_compress_fast_continue on resident streams, DIRECT buffers: the arguments of LZ4HIP_batchFastChain behind the set and streamId,
+   * the stream of every chain (strictly ascending).  Every stream gives, over all the calls that name it, what ONE LZ4_stream_t gives; a
+   * 0 stops the stream until it is reset.  Returns 0 or a negative lz4hip_status (a 0 handle or a null required argument: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchFastStream(long set, int[] streamId, ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen,
+                                           int[] chainFirst, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed,
+                                           int nBlocks, int nChains);
   /* LZ4_compress_HC_continue over chains of linked blocks (prefix mode) at HC level `level`, DIRECT buffers: the arrays of
    * LZ4HIP_batchFastChain without chainConsumed.  outLen = liblz4's return values; a 0 does not end a chain.  Returns 0 or a negative
    * lz4hip_status (a null required argument: LZ4HIP_E_ARG). */

@@ -424,6 +424,74 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastChain(JNI
   return rc;
 }
 
+/* Resident compress streams (lz4hip_cstreams_*): a set of nStreams streams whose tables and index positions stay on the device between
+ * calls.  cstreamsCreate returns the handle, or 0 (lastError() says why); cstreamsCount is the number of streams; cstreamsFree takes
+ * 0 too. */
+JNIEXPORT jlong JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1cstreamsCreate(JNIEnv* env, jclass cls, jint nStreams) {
+  (void)env; (void)cls;
+  lz4hip_cstreams* h = NULL;
+  if (lz4hip_cstreams_create(nStreams < 0 ? 0u : (uint32_t)nStreams, &h) != 0) return 0;   /* (sets the message) */
+  return (jlong)(intptr_t)h;
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1cstreamsCount(JNIEnv* env, jclass cls, jlong set) {
+  (void)env; (void)cls;
+  return lz4hip_cstreams_count((const lz4hip_cstreams*)(intptr_t)set);
+}
+JNIEXPORT void JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1cstreamsFree(JNIEnv* env, jclass cls, jlong set) {
+  (void)env; (void)cls;
+  lz4hip_cstreams_free((lz4hip_cstreams*)(intptr_t)set);
+}
+/* makes the listed streams fresh (streamId == NULL: all of them).  Returns 0 or a negative lz4hip_status; a 0 handle is LZ4HIP_E_ARG */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1cstreamsReset(JNIEnv* env, jclass cls, jlong set, jintArray streamId, jint n) {
+  (void)cls;
+  if (set == 0 || n < 0) return LZ4HIP_E_ARG;
+  if (streamId == NULL) return lz4hip_cstreams_reset((lz4hip_cstreams*)(intptr_t)set, NULL, 0);
+  jint* ids = (*env)->GetIntArrayElements(env, streamId, NULL);
+  if (ids == NULL) return LZ4HIP_E_NOMEM;
+  const jint rc = lz4hip_cstreams_reset((lz4hip_cstreams*)(intptr_t)set, (const uint32_t*)ids, (uint32_t)n);
+  (*env)->ReleaseIntArrayElements(env, streamId, ids, JNI_ABORT);
+  return rc;
+}
+/* consumed[i] = the bytes stream first + i has consumed since its reset, stopped[i] != 0: it is stopped; n entries each.  Returns 0 or a
+ * negative lz4hip_status; a 0 handle or a NULL array is LZ4HIP_E_ARG, nothing stays pinned */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1cstreamsConsumed(JNIEnv* env, jclass cls, jlong set, jint first, jint n, jlongArray consumed,
+    jintArray stopped) {
+  (void)cls;
+  if (set == 0 || first < 0 || n < 0 || consumed == NULL || stopped == NULL) return LZ4HIP_E_ARG;
+  uint8_t* st = (uint8_t*)malloc(n > 0 ? (size_t)n : 1u);   /* the C ABI writes one byte per stream */
+  if (st == NULL) return LZ4HIP_E_NOMEM;
+  jlong* c = (*env)->GetLongArrayElements(env, consumed, NULL);
+  jint* s = c != NULL ? (*env)->GetIntArrayElements(env, stopped, NULL) : NULL;
+  jint rc = LZ4HIP_E_NOMEM;
+  if (c != NULL && s != NULL) {
+    rc = lz4hip_cstreams_consumed((lz4hip_cstreams*)(intptr_t)set, (uint32_t)first, (uint32_t)n, (uint64_t*)c, st);
+    if (rc == 0) for (jint i = 0; i < n; i++) s[i] = st[i] != 0;
+  }
+  if (s != NULL) (*env)->ReleaseIntArrayElements(env, stopped, s, rc == 0 ? 0 : JNI_ABORT);
+  if (c != NULL) (*env)->ReleaseLongArrayElements(env, consumed, c, rc == 0 ? 0 : JNI_ABORT);
+  free(st);
+  return rc;
+}
+/* LZ4_compress_fast_continue on resident streams, DIRECT buffers: LZ4HIP_batchFastChain's arguments behind the set and the stream of
+ * every chain (strictly ascending); chainPrefixLen may be null.  A 0 handle is LZ4HIP_E_ARG */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStream(JNIEnv* env, jclass cls, jlong set, jintArray streamId, jobject src,
+    jlongArray chainSrcOff, jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap,
+    jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains) {
+  (void)cls;
+  if (set == 0 || nBlocks < 0 || nChains < 0) return LZ4HIP_E_ARG;
+  batch_args_t b = {NULL, NULL, 8, {{chainSrcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {chainFirst, INTS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT},
+                                    {destCap, INTS, JNI_ABORT}, {outLen, INTS, 0}, {chainConsumed, LONGS, 0}, {streamId, INTS, JNI_ABORT}}};
+  if (chainPrefixLen != NULL) { b.a[b.n_arrays].arr = chainPrefixLen; b.a[b.n_arrays].is_long = INTS; b.a[b.n_arrays].mode = JNI_ABORT; b.a[b.n_arrays].p = NULL; b.n_arrays++; }
+  const int i_prefix = chainPrefixLen != NULL ? b.n_arrays - 1 : -1;
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  rc = lz4hip_compress_fast_stream_batch((lz4hip_cstreams*)(intptr_t)set, (const uint32_t*)b.a[7].p, b.src, b.a[0].p,
+                                         i_prefix >= 0 ? (const int32_t*)b.a[i_prefix].p : NULL, b.a[1].p, (const uint32_t*)b.a[2].p, b.dst, b.a[3].p, b.a[4].p,
+                                         b.a[5].p, b.a[6].p, (uint32_t)nBlocks, (uint32_t)nChains);
+  batch_release(env, &b);
+  return rc;
+}
+
 /* LZ4_compress_HC_continue over chains of linked blocks at an HC level, DIRECT buffers: chainPrefixLen may be null */
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchHCChain(JNIEnv* env, jclass cls, jobject src, jlongArray chainSrcOff,
     jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen,

@@ -18,7 +18,7 @@ check the container logic without a GPU.
 import io
 import struct
 
-from . import LZ4Exception, LZ4HIPBatch, maxCompressedLength
+from . import CompressStreams, LZ4Exception, LZ4HIPBatch, maxCompressedLength
 
 _U32 = struct.Struct("<I")
 _I32 = struct.Struct("<i")
@@ -48,6 +48,7 @@ class HIPEngine:
     decompressSafeChain = staticmethod(LZ4HIPBatch.decompressSafeChain)   # linked blocks: LZ4FrameInputStream(linkedBlocks=True)
     compressFastChain = staticmethod(LZ4HIPBatch.compressFastChain)       # linked blocks: LZ4FrameOutputStream(linkedBlocks=True)
     compressHCChain = staticmethod(LZ4HIPBatch.compressHCChain)           # linked blocks at an HC level: LZ4FrameOutputStream(linkedBlocks=True, level=N)
+    newCompressStreams = staticmethod(CompressStreams)                    # a frame's own resident stream: LZ4FrameOutputStream(linkedBlocks=True, streamState=True)
     decompressFast = staticmethod(LZ4HIPBatch.decompressFast)
     xxh32 = staticmethod(LZ4HIPBatch.xxh32)
 
@@ -86,15 +87,18 @@ def _compress_batch(engine, data, blockSize):
     return dst, bound, lens, sizes
 
 
-def _compress_chain(engine, history, data, blockSize, level=None):
+def _compress_chain(engine, history, data, blockSize, level=None, streams=None):
     """compress data[i*blockSize : +blockSize] for all i as ONE chain of linked blocks behind `history` -> as _compress_batch; level
-    None: the fast chain (LZ4_compress_fast_continue), else the HC chain at that level (LZ4_compress_HC_continue)"""
+    None: the fast chain (LZ4_compress_fast_continue), else the HC chain at that level (LZ4_compress_HC_continue); streams: a set
+    whose stream 0 is the frame's and goes on from the batch before (`history` is what it has consumed, at most 64 KB of it)"""
     n = (len(data) + blockSize - 1) // blockSize
     bound = maxCompressedLength(blockSize)
     dst = bytearray(n * bound)
     lens = [min(blockSize, len(data) - i * blockSize) for i in range(n)]
     P = len(history)
-    if level is None:
+    if streams is not None:
+        sizes, _ = streams.compress([0], history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P])
+    elif level is None:
         sizes, _ = engine.compressFastChain(history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P])
     else:
         sizes = engine.compressHCChain(history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P], level)
@@ -213,17 +217,29 @@ class LZ4FrameOutputStream(io.RawIOBase):
     linkedBlocks=True, level=N: every batch is one HC chain at level N (engine.compressHCChain: LZ4_compress_HC_continue in prefix
     mode, what `lz4 -3` and above write as blocks) behind the last 64 KB written.  A block of an HC chain depends on the 64 KB in
     front of it and on nothing else, so THE FRAME'S BYTES DO NOT DEPEND ON batchBlocks, and the blocks of a batch are parsed at the
-    same time, a wavefront each: here a single stream does fill the device, the more blocks a batch holds the better."""
+    same time, a wavefront each: here a single stream does fill the device, the more blocks a batch holds the better.
 
-    def __init__(self, out, blockSize=BLOCKSIZE.SIZE_4MB, knownSize=-1, *bits, engine=None, batchBlocks=64, linkedBlocks=False, level=None):
+    linkedBlocks=True, streamState=True (the fast chain only; the default is False and its bytes are unchanged): the frame is ONE
+    compress stream whose table and index position stay on the device from batch to batch (engine.newCompressStreams: a
+    CompressStreams set of one), so the blocks are what ONE LZ4_stream_t writes for the whole frame and THE FRAME'S BYTES DO NOT DEPEND
+    ON batchBlocks or on flush() calls that fall on block boundaries.  The stream is freed by close()."""
+
+    def __init__(self, out, blockSize=BLOCKSIZE.SIZE_4MB, knownSize=-1, *bits, engine=None, batchBlocks=64, linkedBlocks=False, level=None,
+                 streamState=False):
         super().__init__()
         self.out = out
         self.engine = engine or HIPEngine()
         self.linkedBlocks = linkedBlocks
         self.level = level   # (linkedBlocks) None: the fast chain; else the HC chain's level
         self.history = b""   # (linkedBlocks) the last 64 KB written of the frame
+        self._streams = None # (streamState) the frame's resident stream, made at the first batch
+        self._streamState = bool(streamState)   # (fixed for the frame: a frame that changed it half way would not be ONE stream's)
         if level is not None and not linkedBlocks:
             raise ValueError("level selects the linked-block compressor: it needs linkedBlocks=True (independent HC blocks: HIPEngine(hcLevel))")
+        if streamState and (not linkedBlocks or level is not None):
+            raise ValueError("streamState continues the fast chain's stream: it needs linkedBlocks=True and no level")
+        if streamState and not hasattr(self.engine, "newCompressStreams"):
+            raise ValueError("the engine has no resident compress streams")
         if linkedBlocks:
             if not hasattr(self.engine, "compressFastChain" if level is None else "compressHCChain"):
                 raise ValueError("the engine cannot compress linked blocks")
@@ -285,7 +301,9 @@ class LZ4FrameOutputStream(io.RawIOBase):
             self.content.update(data, 0, len(data))  # :211-213: the content checksum streams over the uncompressed bytes
         block_checksum = self.flg.isEnabled(FLG.Bits.BLOCK_CHECKSUM)
         if self.linkedBlocks:                          # one chain behind the last 64 KB written; assembled on the host
-            dst, bound, lens, sizes = _compress_chain(self.engine, self.history, data, self.maxBlockSize, self.level)
+            if self._streamState and self._streams is None:
+                self._streams = self.engine.newCompressStreams(1)
+            dst, bound, lens, sizes = _compress_chain(self.engine, self.history, data, self.maxBlockSize, self.level, self._streams)
             self.history = (self.history + data)[-65536:]
         elif hasattr(self.engine, "containerBlocks"):   # assembled on the device
             self.out.write(self.engine.containerBlocks(LZ4HIPBatch.FRAME_BLOCKS, data, self.maxBlockSize, block_checksum))
@@ -334,6 +352,9 @@ class LZ4FrameOutputStream(io.RawIOBase):
             self._writeEndMark()
             if hasattr(self.out, "flush"):
                 self.out.flush()
+        if self._streams is not None:
+            self._streams.close()
+            self._streams = None
         self._closed = True
         super().close()
 

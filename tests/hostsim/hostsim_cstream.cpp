@@ -1,0 +1,60 @@
+// tests/hostsim/hostsim_cstream.cpp -- TEST INFRASTRUCTURE ONLY.
+// The resident-stream compressor (lz4_fast_chain.h: cstream_walk over FastCore<..., LINK = true>, what compress_fast_stream_cu_kernel
+// runs) compiled against the lock-step host backend, in a library of its own (tests/test_cstream_hostsim.py).  Nothing here is linked
+// into liblz4hip.so.
+//
+// The state of the streams -- records and table images, kernels.h CStreamArgs -- is the caller's host memory and lives from one call to
+// the next, as the device's does between launches.  The bounds follow the walk: while block [blk, end) of a call runs, the simulated
+// wave may read the kept history and the call's source up to `end` and write the block's slot; while a table image is loaded or
+// stored, that stream's 32 KB image and nothing else.
+#include <stdint.h>
+#include <string.h>
+#include "../../lz4-java_amd/csrc/kernels.h"
+#include "../../lz4-java_amd/csrc/lz4_fast_chain.h"
+#include "wave_host.h"
+
+namespace {
+
+struct CStreamIoHost {
+  hostsim::WaveHost& w;
+  const lz4hip::CChainArgs& a;
+  static uint32_t uni(uint32_t v) { return v; }
+  static uint64_t uni64(uint64_t v) { return v; }
+  template <class T> static T* uni_ptr(T* p) { return p; }
+  void put_out(uint32_t i, int32_t r) const { a.out[i] = r; }
+  void put_chain(uint32_t c, uint64_t n) const { a.chain_consumed[c] = n; }
+  void begin_block(const uint8_t* buf, uint32_t end, uint8_t* d, uint32_t cap) const { w.bounds(buf, end, d, cap); }
+  void begin_state(uint8_t* image) const { w.bounds(image, 32768, image, 32768); }
+  void end_state() const { w.bounds(nullptr, 0, nullptr, 0); }
+  static void table_load(hostsim::WaveHost& w, const uint8_t* image) { if (w.in_ok(image, 32768)) memcpy(w.lds.data(), image, 32768); }
+  static void table_store(hostsim::WaveHost& w, uint8_t* image) { if (w.out_ok(image, 32768)) memcpy(image, w.lds.data(), 32768); }
+  static void put_rec(uint32_t* rec, uint32_t idx, uint32_t held, uint32_t flags, uint32_t span, uint64_t total) {
+    rec[0] = idx; rec[1] = held; rec[2] = flags; rec[3] = span; rec[4] = (uint32_t)total; rec[5] = (uint32_t)(total >> 32);
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+uint32_t sim_cstream_rec_words() { return lz4hip::kStreamRecWords; }
+
+// one call of lz4hip_compress_fast_stream_batch on host arrays: chain c continues the stream in slot[c] of the state (rec, tables), chain
+// after chain on ONE simulated wavefront whose table is never touched between two chains (what a wavefront of the kernel that draws
+// several streams sees).  0, or -1000 if the simulated wave read or wrote outside the bounds above
+int sim_cstream_batch(const uint32_t* slot, uint32_t* rec, uint64_t* tables, const uint8_t* src, const uint64_t* chain_src_off,
+                      const int32_t* chain_prefix_len, const int32_t* src_len, const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off,
+                      const int32_t* dst_cap, int32_t* out, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains, uint64_t rng_seed) {
+  const lz4hip::CStreamArgs s{{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out, chain_consumed, n_blocks, n_chains},
+                              slot, rec, tables};
+  hostsim::WaveHost w;
+  if (rng_seed) w.rng = rng_seed;
+  CStreamIoHost io{w, s.c};
+  for (uint32_t c = 0; c < n_chains; c++) {
+    w.bounds(nullptr, 0, nullptr, 0);
+    lz4hip::cstream_walk(w, io, s, c);
+  }
+  return w.oob ? -1000 : 0;
+}
+
+}  // extern "C"
