@@ -244,12 +244,78 @@ int lz4hip_decompress_safe_dict_batch(const uint8_t* src, const uint64_t* src_of
  *     brings back only the bytes decoded (runs less than 4 KB apart as one copy); it shards over the initialised devices at chain
  *     boundaries;
  *   - out of scope: LZ4_saveDict, chains that start from a non-contiguous dictionary
- *     (LZ4_decompress_safe_doubleDict), ring-buffer destinations that wrap, fast and partial decoders in chain form.              */
+ *     (LZ4_decompress_safe_doubleDict), ring-buffer destinations that wrap, fast and partial decoders in chain form.  (No longer
+ *     out of scope: dictionaries elsewhere, destinations that wrap or alternate and save areas are
+ *     lz4hip_decompress_safe_stream_batch, below.)                                                                                */
 int lz4hip_decompress_safe_chain_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                        const uint8_t* stored, const int32_t* dst_cap, const uint32_t* chain_first,
                                        uint8_t* dst, const uint64_t* chain_dst_off, const uint64_t* chain_dst_cap,
                                        const int32_t* chain_prefix_len, int32_t* out_len, uint64_t* chain_out_len,
                                        uint32_t n_blocks, uint32_t n_chains);
+
+/* DECODE STREAMS WHOSE BLOCKS LAND ANYWHERE: LZ4_decompress_safe_continue of liblz4 1.9.3 in every mode of its LZ4_streamDecode_t, so
+ * that a consumer of a long stream needs no destination as long as the stream: a ring buffer, two alternating block buffers, a 64 KB
+ * save area in front of a block buffer, a stream that starts from a dictionary lying somewhere else.  The chain call above is the
+ * rolling-prefix mode alone; this one adds LZ4_decompress_safe_forceExtDict (after a jump) and LZ4_decompress_safe_doubleDict (while a
+ * short prefix grows behind an external dictionary).
+ *
+ * A stream's state is liblz4's four fields, written as offsets into dst: the prefix [prefix_end - prefix_len, prefix_end) is what was
+ * decoded contiguously last, the external dictionary [ext_end - ext_len, ext_end) is what the prefix was before the last jump.  All
+ * zero is a fresh stream; LZ4_setStreamDecode(sd, dst + p, n) is {p + n, n, 0, 0}.  The state is plain host data, read and written
+ * by the call: there is no handle and nothing stays on a device between calls.  For a block decoded to d = dst_off[i], capacity cap:
+ *     if prefix_len == 0:                 r = LZ4_decompress_safe;                 r > 0: prefix_len = r, prefix_end = d + r
+ *     else if prefix_end == d:
+ *         if   prefix_len >= 65535:       r = ..._withPrefix64k                    (the external dictionary is ignored)
+ *         elif ext_len == 0:              r = ..._withSmallPrefix(prefix_len)
+ *         else:                           r = ..._doubleDict(prefix_len, ext)
+ *                                                                                  r > 0: prefix_len += r, prefix_end += r
+ *     else (a jump):                      ext_len = prefix_len, ext_end = prefix_end     BEFORE decoding, whatever r turns out to be
+ *                                         r = ..._forceExtDict(ext);               r > 0: prefix_len = r, prefix_end = d + r
+ * r <= 0 leaves the prefix as it was -- so a 0-byte block at a new place drops the old external dictionary and leaves the prefix
+ * standing as its own external dictionary: liblz4's behaviour, reproduced.  The history a doubleDict block sees is the last 64 KB of
+ * ext ++ prefix: a match that starts in the external dictionary and runs past its end continues at the start of the prefix.
+ *   - stream c is the blocks [chain_first[c], chain_first[c + 1]) of this call (n_chains + 1 entries, ascending from 0 to n_blocks),
+ *     decoded in order, each to its own dst_off[i] with the capacity min(dst_cap[i], INT32_MAX - 65535); state[c] is read in front
+ *     of the first and written back behind the last.  A later call carries on from the state the earlier one left;
+ *   - out_len[i] is liblz4's r, on valid AND malformed streams.  A negative src_len[i] or dst_cap[i] counts as a block liblz4 answered
+ *     with -1 (a jump's ext = prefix is applied first, as it would be).  A negative result ENDS THE STREAM'S PART OF THE CALL: every
+ *     block behind it gets LZ4HIP_CHAIN_STOPPED, and the state written back is the one in front of the failed block (with the jump's
+ *     ext = prefix if it was a jump).  A result of 0 goes on;
+ *   - THE WINDOW: every slot [dst_off[i], dst_off[i] + dst_cap[i]) of stream c lies inside [chain_win_off[c], + chain_win_len[c]): the
+ *     ring, the pair of buffers, the save area plus block area.  It is what the call mirrors on the device.  A history PIECE is the
+ *     last min(len, 65535) bytes in front of prefix_end or ext_end -- nothing in front of it is ever read.  A piece lies wholly inside
+ *     the window, or wholly outside it (it ends at or before chain_win_off[c], or starts at or behind the window's end).  An outside
+ *     piece is only read, may be shared by any number of streams (one dictionary for all) and is uploaded once per staged chunk; an
+ *     outside prefix that ends exactly at chain_win_off[c] stays contiguous with the window (once blocks have been decoded behind
+ *     it the prefix reaches across that edge: the later calls name a window that begins where the dictionary does).  Windows of
+ *     different streams must not overlap;
+ *   - WHAT IS GUARANTEED: out_len and the state written back are liblz4's on every input -- the decoder's control flow never depends
+ *     on copied bytes.  The BYTES are liblz4's whenever a block's slot does not overlap the history the block can reach: the last
+ *     min(prefix_len, 65535) bytes of the prefix and the last 65535 - min(prefix_len, 65535) bytes (at most ext_len) of the external
+ *     dictionary.  Where they overlap, the bytes of matches that read the overlapped part are unspecified (the lanes of a group copy
+ *     in wider steps than liblz4's); still nothing outside the slot is written and nothing outside window and history pieces is read.
+ *     THE RING RULE that follows: a ring that wraps to 0 when the next block no longer fits is safe from 65535 + 2 x maxBlock bytes
+ *     on.  liblz4's minimal ring (65536 + 14 + maxBlock, LZ4_DECODER_RING_BUFFER_SIZE) and small rings kept in step with the
+ *     encoder's are out of scope: they need a store-exact, strictly in-order copy path -- the follow-up to this call;
+ *   - LZ4HIP_E_ARG: a required pointer that is NULL (all are required), a chain_first that is not ascending from 0 to n_blocks, a slot
+ *     outside its stream's window, a history piece that straddles a window edge, a history longer than its end offset.  These are
+ *     said before a device is looked for; without a device a well-formed call is LZ4HIP_E_NO_DEVICE;
+ *   - one kernel, decode_stream_kernel, of decode_chain_kernel's shape: lane groups of 8 draw streams from a queue and walk their
+ *     blocks of the call in order; per block the state picks the core's PREFIX instance or its PREFIX && DICT instance, with the deep
+ *     loop for streams of 2 KB and more, the pipelined loop and the exact tiers below.  ONE STREAM IS SERIAL BY CONSTRUCTION; nothing
+ *     waits for another wavefront or workgroup, and parallelism comes from the number of streams alone.  A stream that never jumps
+ *     runs the chain kernel's code.  The decode_* knobs do not apply;
+ *   - the host form uploads the compressed blocks and each stream's history pieces (the external dictionary's only while the prefix
+ *     is shorter than 65535 bytes), and brings back each block's r decoded bytes (runs less than 4 KB apart as one copy) -- nothing
+ *     else of dst is written; it shards over the initialised devices at stream boundaries;
+ *   - out of scope: a device-pointer form (as for lz4hip_compress_hc_chain_batch: left to a change that can also extend the far-offset
+ *     and stream-contract tables of the device entry points), stored blocks, fast and partial decoders in stream form,
+ *     LZ4_decoderRingBufferSize.                                                                                                 */
+typedef struct lz4hip_dstream_state { uint64_t prefix_end, prefix_len, ext_end, ext_len; } lz4hip_dstream_state;   /* all zero: a fresh stream */
+int lz4hip_decompress_safe_stream_batch(lz4hip_dstream_state* state, const uint8_t* src, const uint64_t* src_off,
+                                        const int32_t* src_len, const uint32_t* chain_first, uint8_t* dst,
+                                        const uint64_t* dst_off, const int32_t* dst_cap, const uint64_t* chain_win_off,
+                                        const uint64_t* chain_win_len, int32_t* out_len, uint32_t n_blocks, uint32_t n_chains);
 
 /* COMPRESS CHAINS OF LINKED BLOCKS: the return values and bytes of liblz4 1.9.3's streaming compressor in its prefix mode, acceleration 1
  * -- what lz4hip_decompress_safe_chain_batch* reads and what the lz4 command line writes by default.  A CHAIN is a run of blocks whose

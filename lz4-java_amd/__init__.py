@@ -63,6 +63,8 @@ C_ABI = {
     "lz4hip_decompress_safe_chain_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _u64p, C.c_void_p, _i32p, _u64p,
                                                      C.c_uint32, C.c_uint32]),
     "lz4hip_decompress_safe_chain_batch_dev": (C.c_int, [C.c_void_p] * 12 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
+    "lz4hip_decompress_safe_stream_batch": (C.c_int, [_u64p, C.c_void_p, _u64p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _u64p, _u64p, _i32p,
+                                                      C.c_uint32, C.c_uint32]),
     "lz4hip_compress_fast_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32]),
     "lz4hip_compress_fast_chain_batch_dev": (C.c_int, [C.c_void_p] * 10 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_uint32, C.c_int]),
@@ -928,6 +930,48 @@ class LZ4HIPBatch:
         return list(out[:n]), list(cout[:nc])
 
     @classmethod
+    def decompressSafeStream(cls, state, src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainWinOff, chainWinLen):
+        """LZ4_decompress_safe_continue on streams whose blocks land anywhere -- rings, alternating buffers, save areas, dictionaries
+        elsewhere (lz4hip_decompress_safe_stream_batch): stream c is the blocks chainFirst[c] .. chainFirst[c + 1] - 1 of this call,
+        block i is decoded to dst[dstOff[i]:+dstCap[i]], inside the stream's window dst[chainWinOff[c]:+chainWinLen[c]].  state[c] is
+        the stream's (prefixEnd, prefixLen, extEnd, extLen) as offsets into dst -- (0, 0, 0, 0) is a fresh stream,
+        LZ4_setStreamDecode(dst + p, n) is (p + n, n, 0, 0) -> (outLen, newState): liblz4's return value per block (CHAIN_STOPPED
+        behind a stream's first negative one; a list, or an int32 array for numpy inputs) and the list of the streams' states behind
+        the call, to be handed to the next one.  DecodeStreams keeps the states for its caller"""
+        n, nc = len(srcOff), len(state)
+        if not (len(srcLen) == len(dstOff) == len(dstCap) == n):
+            raise ValueError("per-block arrays differ in length")
+        if len(chainFirst) != nc + 1 or len(chainWinOff) != nc or len(chainWinLen) != nc:
+            raise ValueError("per-stream arrays differ in length")
+        cls._check_ranges(src, srcOff, srcLen)
+        cls._check_ranges(dst, dstOff, dstCap)
+        cls._check_ranges(dst, chainWinOff, chainWinLen)
+        prev = 0
+        for c in range(nc + 1):
+            if chainFirst[c] < prev or (c == 0 and chainFirst[0] != 0):
+                raise ValueError("chainFirst must ascend from 0 to the number of blocks")
+            prev = chainFirst[c]
+        if prev != n:
+            raise ValueError("chainFirst must ascend from 0 to the number of blocks")
+        flat = (C.c_uint64 * max(4 * nc, 1))()
+        for c in range(nc):
+            pe, pl, ee, el = (int(v) for v in state[c])
+            if min(pe, pl, ee, el) < 0 or pl > pe or el > ee or (pl and pe > len(dst)) or (el and ee > len(dst)):
+                raise IndexError("history outside the buffer")
+            flat[4 * c:4 * c + 4] = (pe, pl, ee, el)
+        sp, sk = _ro_ptr(src)
+        dp, dk = _rw_ptr(dst)
+        out = (C.c_int32 * max(n, 1))()
+        _chk(lib().lz4hip_decompress_safe_stream_batch(flat, sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst), dp,
+                                                       _arr(C.c_uint64, dstOff), _arr(C.c_int32, dstCap), _arr(C.c_uint64, chainWinOff),
+                                                       _arr(C.c_uint64, chainWinLen), out, n, nc))
+        new = [tuple(flat[4 * c:4 * c + 4]) for c in range(nc)]
+        if hasattr(srcOff, "dtype"):
+            import numpy as np
+            return np.frombuffer(out, dtype=np.int32, count=n).copy(), new
+        return list(out[:n]), new
+
+    @classmethod
     def _check_chains(cls, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen):
         """the argument checks of the chain compressors -> (blocks, chains)"""
         n, nc = len(srcLen), len(chainSrcOff)
@@ -1175,6 +1219,47 @@ class CompressStreams:
 
     def __exit__(self, *a):
         self.close()
+
+
+class DecodeStreams:
+    """The states of n decode streams -- per stream what an LZ4_streamDecode_t of liblz4 holds: (prefixEnd, prefixLen, extEnd, extLen) as
+    offsets into the one destination buffer its caller decodes into.  Plain host data: there is nothing to close and nothing on a
+    device.  Every stream gives, over all the calls that name it, the values and bytes ONE LZ4_streamDecode_t gives, however its
+    blocks are cut into calls (LZ4HIPBatch.decompressSafeStream says when the bytes are liblz4's: the ring rule)."""
+
+    def __init__(self, n):
+        if n < 1:
+            raise ValueError("a set has at least one stream")
+        self._state = [(0, 0, 0, 0)] * int(n)
+
+    def __len__(self):
+        return len(self._state)
+
+    def set(self, streamId, prefixEnd, prefixLen):
+        """LZ4_setStreamDecode: the stream starts behind the prefixLen bytes of dictionary that end at dst[prefixEnd]"""
+        if prefixLen < 0 or prefixLen > prefixEnd:
+            raise IndexError("history reaches in front of the buffer")
+        self._state[streamId] = (int(prefixEnd), int(prefixLen), 0, 0)
+
+    def reset(self, streamId=None):
+        """makes the listed streams (None: all of them) fresh"""
+        for c in (range(len(self._state)) if streamId is None else streamId):
+            self._state[c] = (0, 0, 0, 0)
+
+    def state(self, streamId=None):
+        """-> the (prefixEnd, prefixLen, extEnd, extLen) of the listed streams (None: all of them)"""
+        return [self._state[c] for c in (range(len(self._state)) if streamId is None else streamId)]
+
+    def decompress(self, streamId, src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainWinOff, chainWinLen):
+        """LZ4HIPBatch.decompressSafeStream for the streams streamId (distinct ids, one per chain of the call) -> outLen"""
+        ids = [int(c) for c in streamId]
+        if len(set(ids)) != len(ids):
+            raise ValueError("a stream is named twice")
+        out, new = LZ4HIPBatch.decompressSafeStream([self._state[c] for c in ids], src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap,
+                                                    chainWinOff, chainWinLen)
+        for c, s in zip(ids, new):
+            self._state[c] = s
+        return out
 
 
 # ----------------------------------------------------------------------------------------------

@@ -94,9 +94,12 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // (no chain_consumed: a block that returns 0 does not stop its chain), OP_COMPRESS_HC's level and workspace
 // OP_COMPRESS_STREAM: LZ4_compress_fast_continue on streams whose state is resident on the device (lz4hip_cstreams): OP_COMPRESS_CHAIN's
 // arrays and host path, plus the slot of every chain's stream and the device's share of the set's state (BlockCall::cs_*)
+// OP_DECOMPRESS_STREAM: LZ4_decompress_safe_continue on streams whose blocks land anywhere (every mode of LZ4_streamDecode_t): its
+// arrays and state records are BlockCall::dstream; the host path is dstream_host_shard
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
-          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN, OP_COMPRESS_CHAIN, OP_COMPRESS_HC_CHAIN, OP_COMPRESS_STREAM };
-constexpr int OP_COUNT = OP_COMPRESS_STREAM + 1;   // (the last enumerator)
+          OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN, OP_COMPRESS_CHAIN, OP_COMPRESS_HC_CHAIN, OP_COMPRESS_STREAM,
+          OP_DECOMPRESS_STREAM };
+constexpr int OP_COUNT = OP_DECOMPRESS_STREAM + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
 constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN || op == OP_COMPRESS_STREAM; }
@@ -130,6 +133,7 @@ struct BlockCall {
   int32_t dict_len = 0;                 // its length
   const lz4hip::ChainArgs* chain = nullptr;   // OP_DECOMPRESS_CHAIN: the call's arrays on the device
   const lz4hip::CChainArgs* cchain = nullptr; // op_takes_cchain: the call's arrays on the device
+  const lz4hip::DStreamArgs* dstream = nullptr;   // OP_DECOMPRESS_STREAM: the call's arrays and state records on the device
   void* hc_scratch = nullptr;           // op_needs_chain_scratch: lz4hip::hc_chain_scratch_bytes of device memory
   // op_resumes_streams: the device's share of the set's state (kernels.h CStreamArgs) and, on the device, the slot of every chain
   uint32_t* cs_rec = nullptr; uint64_t* cs_tables = nullptr; const uint32_t* cs_slot = nullptr;
@@ -393,6 +397,9 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
     case OP_DECOMPRESS_CHAIN:   // decode_chain_kernel draws chains from the queue word
       if (!c.chain) return fail(LZ4HIP_E_ARG, kNullArg);
       return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_decompress_chain(*c.chain, q, lz4hip::device_cus(), st); });
+    case OP_DECOMPRESS_STREAM:   // decode_stream_kernel draws streams from the queue word
+      if (!c.dstream) return fail(LZ4HIP_E_ARG, kNullArg);
+      return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_decompress_stream(*c.dstream, q, lz4hip::device_cus(), st); });
     case OP_COMPRESS_CHAIN:   // compress_fast_chain_cu_kernel draws chains from the queue word
       if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
       return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_chain(*c.cchain, q, lz4hip::device_cus(), st); });
@@ -956,6 +963,106 @@ const char* chain_arg_error(const lz4hip::ChainArgs& a, bool host) {
   if (a.n_chains == 0 && a.n_blocks == 0) return nullptr;
   if (!a.src || !a.src_off || !a.src_len || !a.dst_cap || !a.chain_first || !a.dst || !a.chain_dst_off || !a.chain_dst_cap || !a.out || !a.chain_out) return kNullArg;
   return host ? staging::chain_shape_error(a.chain_first, a.n_chains, a.n_blocks, a.chain_prefix_len, a.chain_dst_off, true) : nullptr;
+}
+
+// ---- streams whose blocks land anywhere, on the host-pointer path ----
+// the caller's HOST arrays of a stream-decode call
+struct DStreamHost {
+  lz4hip_dstream_state* state; const uint8_t* src; const uint64_t* src_off; const int32_t* src_len; const uint32_t* chain_first;
+  uint8_t* dst; const uint64_t* dst_off; const int32_t* dst_cap; const uint64_t* win_off; const uint64_t* win_len; int32_t* out;
+  uint32_t n_blocks, n_chains;
+};
+static_assert(sizeof(lz4hip_dstream_state) == sizeof(staging::DsState) && sizeof(lz4hip_dstream_state) == sizeof(lz4hip::DStreamState) &&
+              offsetof(lz4hip_dstream_state, ext_end) == offsetof(staging::DsState, ext_end) && offsetof(lz4hip_dstream_state, ext_end) == offsetof(lz4hip::DStreamState, ext_end),
+              "one state record: the header's, the staging arithmetic's, the kernels'");
+// One device's share [c0, c1) of a stream-decode batch.  Streams are staged a chunk at a time (64 MiB of compressed bytes or 512 MiB of
+// device image, one stream at least) through the first buffer set of a pooled pair.  The image (host_staging.h DsImage) mirrors every
+// stream's window, with lead room for a prefix that ends where the window begins, and holds the outside history pieces apart, each
+// once.  Up go the compressed bytes, the state records in device terms and the history pieces (the external dictionary's only while
+// the prefix is shorter than 65535 bytes: behind that liblz4 never looks at it); the kernel runs; the results and records come back,
+// then each block's decoded bytes (runs less than 4 KB apart travel as one copy) -- nothing else of the caller's dst is written.
+int dstream_host_shard(const DStreamHost& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+  if (c1 == c0) return LZ4HIP_OK;
+  ShardScope sh(ord, err);
+  if (sh.rc) return sh.rc;
+  ChunkSlot& s = sh.pair->slot[0];
+  const hipStream_t st = s.st;
+  const staging::DsState* const hstate = (const staging::DsState*)h.state;
+  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+  std::vector<uint64_t> so, ddo;
+  std::vector<staging::Run> runs;
+  for (uint32_t c = c0; c < c1;) {
+    // the next chunk: streams [c, j), blocks [b0, b1)
+    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, [&](uint32_t j) {
+      size_t a = 0;
+      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) a += al16(pos(h.src_len[i]));
+      return staging::Cost{a, staging::dstream_cost(hstate[j], h.win_off[j], h.win_len[j])};
+    });
+    const uint32_t j = ck.end, b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
+    const staging::DsImage im(hstate + c, h.win_off + c, h.win_len + c, nc);
+    so.resize(nb); ddo.resize(nb);
+    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { so[t] = o; o += al16(pos(h.src_len[b0 + t])); } }
+    for (uint32_t t = 0; t < nc; t++)
+      for (uint32_t i = h.chain_first[c + t]; i < h.chain_first[c + t + 1]; i++) ddo[i - b0] = im.win[t] + (h.dst_off[i] - h.win_off[c + t]);
+    const staging::DsMetaLayout m(nb, nc);
+    if (!sh.reserve(s, ck.src, true, im.total, m.l.total)) return sh.rc;
+    uint8_t *const hs = (uint8_t*)s.h_src.p, *const hd = (uint8_t*)s.h_dst.p, *const dd = (uint8_t*)s.d_dst.p;
+    void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
+    par_blocks(b0, b1, ck.src, [=, &so](uint32_t i) { if (h.src_len[i] > 0) memcpy(hs + so[i - b0], h.src + h.src_off[i], (size_t)h.src_len[i]); });
+    memcpy(m.src_off.in(hm), so.data(), m.src_off.bytes());
+    memcpy(m.dst_off.in(hm), ddo.data(), m.dst_off.bytes());
+    memcpy(m.src_len.in(hm), h.src_len + b0, m.src_len.bytes());
+    memcpy(m.dst_cap.in(hm), h.dst_cap + b0, m.dst_cap.bytes());
+    for (uint32_t t = 0; t <= nc; t++) m.first.in(hm)[t] = h.chain_first[c + t] - b0;
+    memcpy(m.state.in(hm), im.dev.data(), m.state.bytes());
+    if (!sh.upload(s, ck.src, m.l, st)) return sh.rc;
+    // the history pieces: into the pinned mirror, then up as joined runs (what a joined run carries between two pieces lands in
+    // window bytes no block may rely on)
+    runs.clear();
+    auto piece = [&](size_t dev_end, uint64_t host_end, uint64_t keep) {
+      memcpy(hd + dev_end - keep, h.dst + host_end - keep, (size_t)keep);
+      runs.push_back(staging::Run{dev_end - (size_t)keep, (size_t)keep});
+    };
+    for (uint32_t t = 0; t < nc; t++) {
+      const staging::DsState& hs0 = hstate[c + t];
+      if (im.prefix[t].kind == staging::DS_INSIDE || im.prefix[t].kind == staging::DS_LEAD) piece((size_t)im.dev[t].prefix_end, hs0.prefix_end, im.prefix[t].keep);
+      if (im.ext[t].kind == staging::DS_INSIDE && hs0.prefix_len < staging::kDsKeep) piece((size_t)im.dev[t].ext_end, hs0.ext_end, im.ext[t].keep);
+    }
+    for (const staging::DsApart& a : im.apart) piece(a.dev + (size_t)a.keep, a.end, a.keep);
+    staging::merge_runs(runs);
+    for (const staging::Run& r : runs)
+      if (!sh.ok("H2D history", hipMemcpyAsync(dd + r.off, hd + r.off, r.len, hipMemcpyHostToDevice, st))) return sh.rc;
+    const lz4hip::DStreamArgs a{(const uint8_t*)s.d_src.p, m.src_off.in(dm), m.src_len.in(dm), m.first.in(dm), dd, m.dst_off.in(dm), m.dst_cap.in(dm),
+                                (lz4hip::DStreamState*)m.state.in(dm), m.out.in(dm), nb, nc};
+    BlockCall call{OP_DECOMPRESS_STREAM}; call.dstream = &a;
+    if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
+    memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
+    for (uint32_t t = 0; t < nc; t++) {   // the records, in the caller's terms again
+      const staging::DsState was = hstate[c + t], now = m.state.in(hm)[t];
+      h.state[c + t].prefix_end = im.to_host(t, now.prefix_end, was, h.win_off[c + t], h.win_len[c + t]);
+      h.state[c + t].prefix_len = now.prefix_len;
+      h.state[c + t].ext_end = im.to_host(t, now.ext_end, was, h.win_off[c + t], h.win_len[c + t]);
+      h.state[c + t].ext_len = now.ext_len;
+    }
+    // only the bytes decoded come back
+    runs.clear();
+    for (uint32_t i = b0; i < b1; i++) if (h.out[i] > 0) runs.push_back(staging::Run{(size_t)ddo[i - b0], (size_t)h.out[i]});
+    staging::merge_runs(runs);
+    for (const staging::Run& r : runs)
+      if (!sh.ok("D2H dst", hipMemcpyAsync(hd + r.off, dd + r.off, r.len, hipMemcpyDeviceToHost, st))) return sh.rc;
+    if (!sh.wait(st)) return sh.rc;
+    // (in block order on one thread: where two slots of a call overlap, the later block's bytes are the ones that stay, as on the device)
+    for (uint32_t i = b0; i < b1; i++) if (h.out[i] > 0) memcpy(h.dst + h.dst_off[i], hd + ddo[i - b0], (size_t)h.out[i]);
+    c = j;
+  }
+  return LZ4HIP_OK;
+}
+
+// the argument errors of a stream-decode call, all of which can be seen without a device (the arrays are the caller's host memory)
+const char* dstream_arg_error(const DStreamHost& h) {
+  if (h.n_chains == 0 && h.n_blocks == 0) return nullptr;
+  if (!h.state || !h.src || !h.src_off || !h.src_len || !h.chain_first || !h.dst || !h.dst_off || !h.dst_cap || !h.win_off || !h.win_len || !h.out) return kNullArg;
+  return staging::dstream_shape_error((const staging::DsState*)h.state, h.chain_first, h.n_chains, h.n_blocks, h.dst_off, h.dst_cap, h.win_off, h.win_len);
 }
 
 // ---- chains of linked blocks on the host-pointer path, compressing side ----
@@ -1876,6 +1983,17 @@ int lz4hip_decompress_safe_chain_batch(const uint8_t* src, const uint64_t* src_o
   if (n_chains == 0) return LZ4HIP_OK;
   // whole chains per device: a chain never leaves its lane group, let alone its device
   return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return chain_host_shard(h, ord, c0, c1, err); });
+}
+int lz4hip_decompress_safe_stream_batch(lz4hip_dstream_state* state, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                        const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                        const uint64_t* chain_win_off, const uint64_t* chain_win_len, int32_t* out_len, uint32_t n_blocks,
+                                        uint32_t n_chains) {
+  const DStreamHost h{state, src, src_off, src_len, chain_first, dst, dst_off, dst_cap, chain_win_off, chain_win_len, out_len, n_blocks, n_chains};
+  if (const char* why = dstream_arg_error(h)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
+  if (const int rc = need_device()) return rc;
+  if (n_chains == 0) return LZ4HIP_OK;
+  // whole streams per device: a stream never leaves its lane group, let alone its device
+  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return dstream_host_shard(h, ord, c0, c1, err); });
 }
 int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
                                      const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,

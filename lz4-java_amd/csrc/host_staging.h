@@ -1,10 +1,13 @@
 // host_staging.h -- the arithmetic of staging a host batch (api.cpp's shard functions), free of HIP so that it is compiled and tested
 // without a device (tests/cpp/host_staging_test.cpp): where a chunk's metadata arrays lie in their one buffer, where a chunk ends,
-// which produced bytes travel back in one copy, and the shape the arrays of a chain call must have.
+// which produced bytes travel back in one copy, the shape the arrays of a chain call must have, and where the windows and history
+// pieces of a stream-decode call lie in the device image.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
+#include <vector>
 
 namespace staging {
 
@@ -134,6 +137,124 @@ inline const char* chain_shape_error(const uint32_t* chain_first, uint32_t n_cha
       return in_dst ? "chain_prefix_len reaches in front of dst" : "chain_prefix_len reaches in front of src";
   }
   return nullptr;
+}
+
+// ---- the stream decoder's device image (api.cpp dstream_host_shard) ----
+// A stream's state is liblz4's four fields as offsets into the caller's destination base (include/lz4hip.h lz4hip_dstream_state).  Of
+// each history -- the prefix and the external dictionary -- only the PIECE [end - min(len, 65535), end) can be read.  A stream's window
+// [win_off, win_off + win_len) is mirrored whole on the device; a piece lies inside it (DS_INSIDE), or outside it: a prefix that ends
+// exactly at win_off stays contiguous with the window, in lead room in front of the mirror (DS_LEAD), every other outside piece is
+// uploaded apart (DS_APART), once per chunk however many streams name it.  A piece that straddles a window edge is an error.
+struct DsState { uint64_t prefix_end, prefix_len, ext_end, ext_len; };
+constexpr uint64_t kDsKeep = 65535;
+constexpr uint64_t kDsNoPrefix = UINT64_MAX, kDsNoExt = UINT64_MAX - 1u;   // the device's word for the end of a history of no bytes
+enum DsKind : uint8_t { DS_NONE, DS_INSIDE, DS_LEAD, DS_APART };
+struct DsPiece { DsKind kind = DS_NONE; uint64_t keep = 0; };
+struct DsMetaLayout {   // stream decode (dstream_host_shard): nb blocks in nc streams; the state records go up and come back
+  MetaLayout l;
+  Region<uint64_t> src_off, dst_off; Region<int32_t> src_len, dst_cap; Region<uint32_t> first; Region<DsState> state; Region<int32_t> out;
+  DsMetaLayout(size_t nb, size_t nc)
+      : src_off(l.input<uint64_t>(nb)), dst_off(l.input<uint64_t>(nb)), src_len(l.input<int32_t>(nb)), dst_cap(l.input<int32_t>(nb)),
+        first(l.input<uint32_t>(nc + 1)), state(l.take<DsState>(nc, true, true)), out(l.result<int32_t>(nb)) {}
+};
+
+// the piece of the history (end, len) against the window -> a message, or nullptr with *p filled in
+inline const char* dstream_piece(uint64_t end, uint64_t len, uint64_t win_off, uint64_t win_len, bool is_prefix, DsPiece* p) {
+  *p = DsPiece{};
+  if (len == 0) return nullptr;
+  if (len > end) return is_prefix ? "prefix_len reaches in front of dst" : "ext_len reaches in front of dst";
+  p->keep = len < kDsKeep ? len : kDsKeep;
+  const uint64_t start = end - p->keep, wend = win_off + win_len;
+  if (start >= win_off && end <= wend) p->kind = DS_INSIDE;
+  else if (end <= win_off) p->kind = is_prefix && end == win_off ? DS_LEAD : DS_APART;
+  else if (start >= wend) p->kind = DS_APART;
+  else return is_prefix ? "the prefix straddles an edge of the stream's window" : "the external dictionary straddles an edge of the stream's window";
+  return nullptr;
+}
+
+// What can be said about a stream-decode call without a device: chain_first runs from 0 to n_blocks and ascends, every window has
+// an end, every slot lies inside its stream's window, every history piece is placeable.  -> a message, or nullptr
+inline const char* dstream_shape_error(const DsState* state, const uint32_t* chain_first, uint32_t n_chains, uint32_t n_blocks, const uint64_t* dst_off,
+                                       const int32_t* dst_cap, const uint64_t* win_off, const uint64_t* win_len) {
+  if (chain_first[0] != 0u || chain_first[n_chains] != n_blocks) return "chain_first must start at 0 and end at n_blocks";
+  for (uint32_t c = 0; c < n_chains; c++)
+    if (chain_first[c] > chain_first[c + 1]) return "chain_first must be ascending";
+  for (uint32_t c = 0; c < n_chains; c++) {
+    if (win_off[c] + win_len[c] < win_off[c]) return "a stream's window wraps around the address space";
+    const uint64_t wend = win_off[c] + win_len[c];
+    for (uint32_t i = chain_first[c]; i < chain_first[c + 1]; i++) {
+      const uint64_t cap = dst_cap[i] > 0 ? (uint64_t)dst_cap[i] : 0u;
+      if (dst_off[i] < win_off[c] || dst_off[i] > wend || cap > wend - dst_off[i]) return "a block's slot lies outside its stream's window";
+    }
+    DsPiece p;
+    if (const char* why = dstream_piece(state[c].prefix_end, state[c].prefix_len, win_off[c], win_len[c], true, &p)) return why;
+    if (const char* why = dstream_piece(state[c].ext_end, state[c].ext_len, win_off[c], win_len[c], false, &p)) return why;
+  }
+  return nullptr;
+}
+
+// the bytes stream c takes in the device image when it stands alone (cut_chunk's cost: shared pieces are counted once per stream)
+inline size_t dstream_cost(const DsState& s, uint64_t win_off, uint64_t win_len) {
+  DsPiece p, e;
+  (void)dstream_piece(s.prefix_end, s.prefix_len, win_off, win_len, true, &p);
+  (void)dstream_piece(s.ext_end, s.ext_len, win_off, win_len, false, &e);
+  return al16((size_t)(p.kind == DS_LEAD ? p.keep : 0u)) + al16((size_t)win_len) + (p.kind == DS_APART ? al16((size_t)p.keep) : 0u) +
+         (e.kind == DS_APART ? al16((size_t)e.keep) : 0u);
+}
+
+// One chunk's image: stream t's window is mirrored at device offset win[t] (16-aligned, its lead room directly in front of it); the
+// pieces uploaded apart follow the windows.  dev[t] is the state the kernel gets: lengths as they are, ends as device offsets.
+struct DsApart { uint64_t end, keep; size_t dev; };   // the caller's bytes [end - keep, end) at device offset dev
+struct DsImage {
+  std::vector<size_t> win;
+  std::vector<DsPiece> prefix, ext;
+  std::vector<DsApart> apart;
+  std::vector<DsState> dev;
+  size_t total = 0;
+  size_t apart_at(uint64_t end, uint64_t keep) {   // (chunks hold few distinct outside pieces -- a shared dictionary is one)
+    for (const DsApart& a : apart) if (a.end == end && a.keep == keep) return a.dev;
+    apart.push_back(DsApart{end, keep, total});
+    total += al16((size_t)keep);
+    return apart.back().dev;
+  }
+  // state / win_off / win_len: the chunk's first stream's (nc streams); the call has passed dstream_shape_error
+  DsImage(const DsState* state, const uint64_t* win_off, const uint64_t* win_len, uint32_t nc) : win(nc), prefix(nc), ext(nc), dev(nc) {
+    for (uint32_t t = 0; t < nc; t++) {
+      (void)dstream_piece(state[t].prefix_end, state[t].prefix_len, win_off[t], win_len[t], true, &prefix[t]);
+      (void)dstream_piece(state[t].ext_end, state[t].ext_len, win_off[t], win_len[t], false, &ext[t]);
+      win[t] = total + al16((size_t)(prefix[t].kind == DS_LEAD ? prefix[t].keep : 0u));
+      total = win[t] + al16((size_t)win_len[t]);
+    }
+    for (uint32_t t = 0; t < nc; t++) {
+      dev[t] = DsState{kDsNoPrefix, state[t].prefix_len, kDsNoExt, state[t].ext_len};
+      if (prefix[t].kind == DS_INSIDE || prefix[t].kind == DS_LEAD) dev[t].prefix_end = win[t] + (state[t].prefix_end - win_off[t]);
+      if (prefix[t].kind == DS_APART) dev[t].prefix_end = apart_at(state[t].prefix_end, prefix[t].keep) + prefix[t].keep;
+      if (ext[t].kind == DS_INSIDE) dev[t].ext_end = win[t] + (state[t].ext_end - win_off[t]);
+      if (ext[t].kind == DS_APART) dev[t].ext_end = apart_at(state[t].ext_end, ext[t].keep) + ext[t].keep;
+    }
+  }
+  // an end offset the kernel wrote back, in the caller's terms: a position of the mirrored window (its two ends included), or one of
+  // the two ends the stream came with (host: its state before the call)
+  uint64_t to_host(uint32_t t, uint64_t v, const DsState& host, uint64_t win_off, uint64_t win_len) const {
+    if (v == kDsNoPrefix) return host.prefix_end;
+    if (v == kDsNoExt) return host.ext_end;
+    if (v >= win[t] && v - win[t] <= win_len) return win_off + (v - win[t]);
+    return v == dev[t].prefix_end ? host.prefix_end : host.ext_end;
+  }
+};
+
+// runs in any order, overlapping ones included -> ascending, disjoint, those at most RUN_GAP bytes apart joined
+inline void merge_runs(std::vector<Run>& r) {
+  std::sort(r.begin(), r.end(), [](const Run& a, const Run& b) { return a.off < b.off; });
+  size_t n = 0;
+  for (const Run& e : r) {
+    if (!e.len) continue;
+    if (n && e.off <= r[n - 1].off + r[n - 1].len + RUN_GAP) {
+      const size_t end = std::max(r[n - 1].off + r[n - 1].len, e.off + e.len);
+      r[n - 1].len = end - r[n - 1].off;
+    } else r[n++] = e;
+  }
+  r.resize(n);
 }
 
 }  // namespace staging

@@ -125,6 +125,21 @@ constexpr int32_t kChainBlockCapMax = INT32_MAX - 65535;  // (a block's capacity
 // decode_chain_kernel<8>: lane groups of 8 draw chains from the queue word q (one device uint32_t of scratch) and walk each chain's
 // blocks in order; no group waits for another anywhere.  n_cus = compute units of the device
 int launch_decompress_chain(const ChainArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
+// LZ4_decompress_safe_continue on streams whose blocks land anywhere (decode_stream.hip, lz4_decode_stream.h): every mode of liblz4
+// 1.9.3's LZ4_streamDecode_t, not the rolling prefix alone.  Stream c is the blocks [chain_first[c], chain_first[c + 1]); block i is
+// decoded to dst + dst_off[i] with the capacity min(dst_cap[i], kChainBlockCapMax).  state[c] is liblz4's four fields as offsets into
+// dst (include/lz4hip.h lz4hip_dstream_state), read at the stream's first block of the launch and written back behind its last.
+// out[i] = liblz4's return value (a negative src_len / dst_cap: -1), kChainStopped for the blocks behind a stream's first negative
+// result.  The walk trusts nothing it reads from the arrays: a stream's block range is cut to [0, n_blocks].
+struct DStreamState { uint64_t prefix_end, prefix_len, ext_end, ext_len; };
+struct DStreamArgs {
+  const uint8_t* src; const uint64_t* src_off; const int32_t* src_len; const uint32_t* chain_first;
+  uint8_t* dst; const uint64_t* dst_off; const int32_t* dst_cap;
+  DStreamState* state; int32_t* out; uint32_t n_blocks, n_chains;
+};
+// decode_stream_kernel<8>: decode_chain_kernel's shape -- lane groups of 8 draw streams from the queue word q (one device uint32_t
+// of scratch) and walk each stream's blocks of this launch in order; no group waits for another anywhere.  n_cus = compute units
+int launch_decompress_stream(const DStreamArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
 // LZ4_compress_fast_continue(acceleration 1) over chains of linked blocks (compress_fast.hip, lz4_fast_chain.h).  Chain c is the blocks
 // [chain_first[c], chain_first[c + 1]); their SOURCES lie back to back from src + chain_src_off[c] on, behind chain_prefix_len[c] bytes
 // of history (chain_prefix_len == nullptr: none) that the stream has loaded with LZ4_loadDict; block i owns the slot

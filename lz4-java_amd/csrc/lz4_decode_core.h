@@ -56,7 +56,8 @@
 #define LZ4HIP_DECODE_OUT_MARGIN 606
 #endif
 namespace lz4hip {
-// The two copies of decode_block's dictionary mode (DICT, below), in front of the interior loops that use them.
+// The two copies of decode_block's dictionary mode (DICT, below), in front of the interior loops that use them.  dst is where output
+// position 0 lies: the block's start, or with PREFIX the start of the prefix -- where a match goes on behind the dictionary's end.
 template <class Grp>
 LZ4HIP_DEV int dict_match_copy(Grp& g, uint8_t* dst, int op, int back, int length, const uint8_t* dict_end) {   // back = offset - op > 0; returns op + length
   const int c = length < back ? length : back;
@@ -124,7 +125,7 @@ template <class G> struct exact_length_sum<G, decltype((void)G::kExactLengthSum)
 //        Only [dict_end - min(dict_len, 65535), dict_end) is ever read, and never wildly.  The interior loops (plain, staged, pipelined,
 //        deep) take the matches that lie wholly in the dictionary as copies from a foreign pointer, like literals; a match that
 //        straddles the block's start goes to the exact code.  dict_len == 0 is the plain decoder.
-// PREFIX (SAFE only, not PARTIAL, not DICT, not STAGE): one block of a chain of linked blocks -- LZ4_decompress_safe_continue of liblz4 1.9.3 in its
+// PREFIX (SAFE only, not PARTIAL, not STAGE): one block of a chain of linked blocks -- LZ4_decompress_safe_continue of liblz4 1.9.3 in its
 //        rolling-prefix mode (withSmallPrefix / withPrefix64k): the `hist` bytes in front of dst are history (what the chain's earlier
 //        blocks decoded, and what lay in front of the chain), hist = min(real history, 65535).  A match may start in the history: an
 //        offset is valid at output position p iff offset <= p + hist, so with hist == 65535 no offset is rejected (liblz4 stops
@@ -135,12 +136,19 @@ template <class G> struct exact_length_sum<G, decltype((void)G::kExactLengthSum)
 //        loops whose output lives in memory can see the history: plain, pipelined, deep.  Nothing in front of dst is written (a copy
 //        touches bytes behind its end only), nothing in front of dst - hist is read.  out_size + hist must not overflow an int.
 //        hist == 0 is the plain decoder.
+// PREFIX && DICT: LZ4_decompress_safe_doubleDict -- a prefix of hist < 65535 bytes in front of dst AND an external dictionary behind it
+//        (the stream decoder, lz4_decode_stream.h).  The block's logical history is dictionary ++ prefix.  Output positions count from
+//        the start of the prefix, as in PREFIX, so DICT's tests read unchanged with the prefix's start in the place of the block's:
+//        an offset past position p is a dictionary match of offset - p bytes back from dict_end, valid iff offset <= p + dict_len
+//        (never rejected once dict_len >= 65536), and a match that runs past the dictionary's end continues at the start of the
+//        PREFIX -- which is where `dst` points once it has been moved back by hist, so dict_match_copy's "the block's own start" is
+//        the prefix's start here.  hist == 0 is DICT, dict_len == 0 is PREFIX.
 template <class Grp, bool SAFE, int PIPE = 0, bool STAGE = false, bool PARTIAL = false, bool DICT = false, bool PREFIX = false>
 LZ4HIP_DEV int decode_block(Grp& g, const uint8_t* src, int src_size, uint8_t* dst, int out_size, uint8_t* stage = nullptr,
                             const uint8_t* dict_end = nullptr, int dict_len = 0, int hist = 0) {
   static_assert(!PARTIAL || SAFE, "partial decoding is a safe-decoder mode");
   static_assert(!DICT || (SAFE && !PARTIAL && PIPE <= 2), "the dictionary decoder is a safe-decoder mode of the plain, staged, pipelined and deep loops");
-  static_assert(!PREFIX || (SAFE && !PARTIAL && !DICT && !STAGE && PIPE <= 2), "the linked-block decoder is a safe-decoder mode of the plain, pipelined and deep loops");
+  static_assert(!PREFIX || (SAFE && !PARTIAL && !STAGE && PIPE <= 2), "the linked-block decoder is a safe-decoder mode of the plain, pipelined and deep loops");
   // EXACT (a backend that sets kExactLengthSum: the decoded-size query, whose value is liblz4's on EVERY input): a length's extension bytes are summed
   // in 32 bits, as liblz4 sums them, to the run's end -- the error position of a run that cannot fit is then liblz4's.  The decoders stop such a run at
   // LZ4HIP_LEN_CAP instead: also an error, reported where the cap was passed.  WRAP: the 32-bit sum, PARTIAL's too

@@ -15,6 +15,8 @@
 //   LZ4HIPBatch::compressHCChain                    =  LZ4_compress_HC_continue over chains of linked blocks (prefix mode; not serial)
 //   LZ4HIPBatch::decompressSafeChain                =  LZ4_decompress_safe_continue over chains of linked blocks (liblz4's rolling-prefix
 //                                                      mode; no reference entry reaches it)
+//   LZ4HIPBatch::decompressSafeStream, DecodeStreams =  LZ4_decompress_safe_continue on streams whose blocks land anywhere (rings, alternating
+//                                                      buffers, save areas, dictionaries elsewhere): every mode of LZ4_streamDecode_t
 //   LZ4HIPCompressor::compressWithDict, LZ4HIPBatch::compressDict
 //                                                   =  LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream per block: the writer
 //                                                      of the records decompressWithDict reads (no reference entry reaches it)
@@ -323,6 +325,40 @@ struct LZ4HIPBatch {
                                               nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
     return r;
   }
+  // LZ4_decompress_safe_continue on streams whose blocks land anywhere (lz4hip_decompress_safe_stream_batch): stream c is the blocks
+  // [chainFirst[c], chainFirst[c + 1]) of this call, block i is decoded to dest[destOff[i], + maxDestLen[i]), inside the stream's window
+  // dest[chainWinOff[c], + chainWinLen[c]).  state[c] is liblz4's LZ4_streamDecode_t as offsets into dest -- all zero: a fresh stream,
+  // LZ4_setStreamDecode(dest + p, n): {p + n, n, 0, 0} -- read and written back.  -> liblz4's return value per block,
+  // LZ4HIP_CHAIN_STOPPED behind a stream's first negative one of the call.  The header says when the bytes are liblz4's (the ring rule)
+  static std::vector<int32_t> decompressSafeStream(std::vector<lz4hip_dstream_state>& state, const bytes& src, const std::vector<uint64_t>& srcOff,
+                                                   const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst, bytes& dest,
+                                                   const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen,
+                                                   const std::vector<uint64_t>& chainWinOff, const std::vector<uint64_t>& chainWinLen) {
+    checkBlocks(src, srcOff, srcLen, maxDestLen);
+    const size_t n = srcOff.size(), nc = state.size();
+    if (destOff.size() != n) throw std::invalid_argument("per-block arrays differ in length");
+    if (chainFirst.size() != nc + 1 || chainWinOff.size() != nc || chainWinLen.size() != nc) throw std::invalid_argument("per-stream arrays differ in length");
+    if (chainFirst[0] != 0 || chainFirst[nc] != n) throw std::invalid_argument("chainFirst must ascend from 0 to the number of blocks");
+    for (size_t c = 0; c < nc; c++) {
+      if (chainFirst[c] > chainFirst[c + 1]) throw std::invalid_argument("chainFirst must ascend from 0 to the number of blocks");
+      if (chainWinOff[c] > dest.size() || chainWinLen[c] > dest.size() - chainWinOff[c]) throw std::out_of_range("window of stream " + std::to_string(c));
+      const lz4hip_dstream_state& s = state[c];
+      if (s.prefix_len > s.prefix_end || s.ext_len > s.ext_end || (s.prefix_len && s.prefix_end > dest.size()) || (s.ext_len && s.ext_end > dest.size()))
+        throw std::out_of_range("history of stream " + std::to_string(c));
+    }
+    for (size_t i = 0; i < n; i++)
+      if (destOff[i] > dest.size() || (uint64_t)maxDestLen[i] > dest.size() - destOff[i]) throw std::out_of_range("slot " + std::to_string(i));
+    std::vector<int32_t> lengths(n, 0);
+    bytes one(1);                                 // (an empty buffer still hands the library a pointer)
+    int32_t none = 0;
+    uint64_t none64 = 0;
+    lz4hip_dstream_state none_state{0, 0, 0, 0};
+    status(lz4hip_decompress_safe_stream_batch(nc ? state.data() : &none_state, src.empty() ? one.data() : src.data(), n ? srcOff.data() : &none64,
+                                               n ? srcLen.data() : &none, chainFirst.data(), dest.empty() ? one.data() : dest.data(),
+                                               n ? destOff.data() : &none64, n ? maxDestLen.data() : &none, nc ? chainWinOff.data() : &none64,
+                                               nc ? chainWinLen.data() : &none64, n ? lengths.data() : &none, (uint32_t)n, (uint32_t)nc));
+    return lengths;
+  }
   // LZ4_compress_fast_continue over chains of linked blocks (lz4hip_compress_fast_chain_batch): chain c is the blocks
   // [chainFirst[c], chainFirst[c + 1]), whose sources lie back to back from src[chainSrcOff[c]] on, behind chainPrefixLen[c] bytes of
   // history that lie in front of it in src (an empty vector: no history; the stream loads it with LZ4_loadDict); block i owns the slot
@@ -486,6 +522,44 @@ class CompressStreams {
 
  private:
   lz4hip_cstreams* h_ = nullptr;
+};
+
+// The states of n decode streams: per stream what an LZ4_streamDecode_t of liblz4 holds, as offsets into the one destination its caller
+// decodes into.  Plain host data: nothing on a device, nothing to destroy.  decompress(): the arrays of LZ4HIPBatch::decompressSafeStream,
+// and chain c of the call is the next run of blocks of stream streamId[c] (distinct ids).  Every stream gives, over all the calls that
+// name it, the values ONE LZ4_streamDecode_t gives, however its blocks are cut into calls.
+class DecodeStreams {
+ public:
+  explicit DecodeStreams(uint32_t n) : state_(n, lz4hip_dstream_state{0, 0, 0, 0}) {
+    if (!n) throw std::invalid_argument("a set has at least one stream");
+  }
+  uint32_t size() const { return (uint32_t)state_.size(); }
+  // LZ4_setStreamDecode: the stream starts behind the prefixLen bytes of dictionary that end at dest[prefixEnd]
+  void set(uint32_t streamId, uint64_t prefixEnd, uint64_t prefixLen) {
+    if (prefixLen > prefixEnd) throw std::out_of_range("history of stream " + std::to_string(streamId));
+    state_.at(streamId) = lz4hip_dstream_state{prefixEnd, prefixLen, 0, 0};
+  }
+  void reset() { for (lz4hip_dstream_state& s : state_) s = lz4hip_dstream_state{0, 0, 0, 0}; }
+  void reset(const std::vector<uint32_t>& streamId) { for (uint32_t c : streamId) state_.at(c) = lz4hip_dstream_state{0, 0, 0, 0}; }
+  const lz4hip_dstream_state& state(uint32_t streamId) const { return state_.at(streamId); }
+  std::vector<int32_t> decompress(const std::vector<uint32_t>& streamId, const bytes& src, const std::vector<uint64_t>& srcOff,
+                                  const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst, bytes& dest,
+                                  const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen,
+                                  const std::vector<uint64_t>& chainWinOff, const std::vector<uint64_t>& chainWinLen) {
+    std::vector<lz4hip_dstream_state> st;
+    std::vector<uint8_t> seen(state_.size(), 0);
+    for (uint32_t c : streamId) {
+      if (c >= state_.size() || seen[c]) throw std::invalid_argument("streamId must be distinct and below the number of streams");
+      seen[c] = 1;
+      st.push_back(state_[c]);
+    }
+    std::vector<int32_t> r = LZ4HIPBatch::decompressSafeStream(st, src, srcOff, srcLen, chainFirst, dest, destOff, maxDestLen, chainWinOff, chainWinLen);
+    for (size_t k = 0; k < streamId.size(); k++) state_[streamId[k]] = st[k];
+    return r;
+  }
+
+ private:
+  std::vector<lz4hip_dstream_state> state_;
 };
 
 class LZ4FastDecompressor {

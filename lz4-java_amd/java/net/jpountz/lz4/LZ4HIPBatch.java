@@ -371,6 +371,128 @@ public final class LZ4HIPBatch {
   }
 
   /**
+   * liblz4's {@code LZ4_decompress_safe_continue} on streams whose blocks land anywhere -- a ring buffer, two alternating block buffers, a
+   * save area in front of a block buffer, a stream that starts from a dictionary elsewhere: every mode of an {@code LZ4_streamDecode_t}.
+   * Stream c is the blocks {@code chainFirst[c] .. chainFirst[c+1]-1} of this call; block i is decoded to
+   * {@code dest[destOff[i], destOff[i]+destCap[i])}, inside the stream's window {@code dest[chainWinOff[c], +chainWinLen[c])}.
+   * {@code state} holds four longs per stream -- prefixEnd, prefixLen, extEnd, extLen, offsets into dest; all zero is a fresh stream,
+   * {@code LZ4_setStreamDecode(dest + p, n)} is {p + n, n, 0, 0} -- and is read and written back.  outLen[i] = liblz4's return value,
+   * {@link #CHAIN_STOPPED} behind a stream's first negative one of the call.  include/lz4hip.h says when the bytes are liblz4's (the
+   * ring rule).  {@link DecodeStreams} keeps the states for its caller.
+   */
+  public static void decompressSafeStream(long[] state, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest,
+      long[] destOff, int[] destCap, long[] chainWinOff, long[] chainWinLen, int[] outLen) {
+    final int n = srcOff.length, nc = chainWinOff.length;
+    if (srcLen.length != n || destOff.length != n || destCap.length != n || outLen.length != n) {
+      throw new IllegalArgumentException("per-block arrays differ in length");
+    }
+    if (chainFirst.length != nc + 1 || chainWinLen.length != nc || state.length != 4 * nc) {
+      throw new IllegalArgumentException("per-stream arrays differ in length");
+    }
+    if (!src.isDirect() || !dest.isDirect()) {
+      throw new IllegalArgumentException("direct buffers required");
+    }
+    if (dest.isReadOnly()) {
+      throw new java.nio.ReadOnlyBufferException();
+    }
+    for (int i = 0; i < n; i++) {
+      if (srcLen[i] < 0 || destCap[i] < 0) {
+        throw new IllegalArgumentException("lengths must be >= 0");
+      }
+      if (srcOff[i] < 0 || srcOff[i] + srcLen[i] > src.capacity()) {
+        throw new ArrayIndexOutOfBoundsException("block " + i);
+      }
+      if (destOff[i] < 0 || destOff[i] + destCap[i] > dest.capacity()) {
+        throw new ArrayIndexOutOfBoundsException("slot " + i);
+      }
+    }
+    if (chainFirst[0] != 0 || chainFirst[nc] != n) {
+      throw new IllegalArgumentException("chainFirst must ascend from 0 to the number of blocks");
+    }
+    for (int c = 0; c < nc; c++) {
+      if (chainFirst[c] > chainFirst[c + 1]) {
+        throw new IllegalArgumentException("chainFirst must ascend from 0 to the number of blocks");
+      }
+      if (chainWinOff[c] < 0 || chainWinLen[c] < 0 || chainWinOff[c] + chainWinLen[c] > dest.capacity()) {
+        throw new ArrayIndexOutOfBoundsException("window of stream " + c);
+      }
+      final long pe = state[4 * c], pl = state[4 * c + 1], ee = state[4 * c + 2], el = state[4 * c + 3];
+      if (pl < 0 || el < 0 || pl > pe || el > ee || (pl > 0 && pe > dest.capacity()) || (el > 0 && ee > dest.capacity())) {
+        throw new ArrayIndexOutOfBoundsException("history of stream " + c);
+      }
+    }
+    final int rc = LZ4HIPJNI.LZ4HIP_batchSafeStream(state, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff, chainWinLen, outLen, n, nc);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /**
+   * The states of n decode streams: per stream what an {@code LZ4_streamDecode_t} of liblz4 holds, as offsets into the one destination
+   * its caller decodes into.  Plain host data: nothing on a device, nothing to close.  Every stream gives, over all the calls that name
+   * it, the values ONE {@code LZ4_streamDecode_t} gives, however its blocks are cut into calls.
+   */
+  public static final class DecodeStreams {
+    private final long[] state;
+
+    public DecodeStreams(int n) {
+      if (n < 1) {
+        throw new IllegalArgumentException("a set has at least one stream");
+      }
+      state = new long[4 * n];
+    }
+
+    public int size() {
+      return state.length / 4;
+    }
+
+    /** {@code LZ4_setStreamDecode}: the stream starts behind the prefixLen bytes of dictionary that end at dest[prefixEnd]. */
+    public void set(int streamId, long prefixEnd, long prefixLen) {
+      if (prefixLen < 0 || prefixLen > prefixEnd) {
+        throw new ArrayIndexOutOfBoundsException("history of stream " + streamId);
+      }
+      state[4 * streamId] = prefixEnd;
+      state[4 * streamId + 1] = prefixLen;
+      state[4 * streamId + 2] = 0;
+      state[4 * streamId + 3] = 0;
+    }
+
+    /** makes the listed streams (null: all of them) fresh */
+    public void reset(int[] streamId) {
+      if (streamId == null) {
+        java.util.Arrays.fill(state, 0L);
+        return;
+      }
+      for (int c : streamId) {
+        java.util.Arrays.fill(state, 4 * c, 4 * c + 4, 0L);
+      }
+    }
+
+    /** {prefixEnd, prefixLen, extEnd, extLen} of one stream */
+    public long[] state(int streamId) {
+      return java.util.Arrays.copyOfRange(state, 4 * streamId, 4 * streamId + 4);
+    }
+
+    /** {@link LZ4HIPBatch#decompressSafeStream} for the streams streamId (distinct ids, one per chain of the call). */
+    public void decompress(int[] streamId, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest, long[] destOff,
+        int[] destCap, long[] chainWinOff, long[] chainWinLen, int[] outLen) {
+      final long[] st = new long[4 * streamId.length];
+      final boolean[] seen = new boolean[size()];
+      for (int k = 0; k < streamId.length; k++) {
+        if (streamId[k] < 0 || streamId[k] >= size() || seen[streamId[k]]) {
+          throw new IllegalArgumentException("streamId must be distinct and below the number of streams");
+        }
+        seen[streamId[k]] = true;
+        System.arraycopy(state, 4 * streamId[k], st, 4 * k, 4);
+      }
+      decompressSafeStream(st, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff, chainWinLen, outLen);
+      for (int k = 0; k < streamId.length; k++) {
+        System.arraycopy(st, 4 * k, state, 4 * streamId[k], 4);
+      }
+    }
+  }
+
+  /**
    * liblz4's {@code LZ4_decompress_safe_partial} per block: the first {@code min(targetLen[i], destCap[i])} bytes of block i (fewer
    * where a cut stream ends first) into the slot {@code dest[destOff[i], destOff[i]+destCap[i])}, nothing past
    * {@code destOff[i] + min(targetLen[i], destCap[i])}.  outLen[i] &gt;= 0: bytes decoded; &lt; 0: -(input position)-1.

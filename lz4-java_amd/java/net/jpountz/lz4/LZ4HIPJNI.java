@@ -109,6 +109,14 @@ enum LZ4HIPJNI {
   static native int LZ4HIP_batchSafeChain(ByteBuffer src, long[] srcOff, int[] srcLen, int[] stored, int[] destCap, int[] chainFirst,
                                           ByteBuffer dest, long[] chainDestOff, long[] chainDestCap, int[] chainPrefixLen, int[] outLen,
                                           long[] chainOutLen, int nBlocks, int nChains);
+  /* LZ4_decompress_safe_continue on streams whose blocks land anywhere, DIRECT buffers: stream c is the blocks chainFirst[c] ..
+   * chainFirst[c + 1] - 1 of this call, block i is decoded to dest[destOff[i], + destCap[i]) inside the window dest[chainWinOff[c], +
+   * chainWinLen[c]); state holds four longs per stream (prefixEnd, prefixLen, extEnd, extLen: offsets into dest), read and written back.
+   * outLen = liblz4's return values (LZ4HIPBatch.CHAIN_STOPPED behind a stream's first negative one of the call).  Returns 0 or a negative
+   * lz4hip_status (a null argument: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchSafeStream(long[] state, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest,
+                                           long[] destOff, int[] destCap, long[] chainWinOff, long[] chainWinLen, int[] outLen,
+                                           int nBlocks, int nChains);
   /* LZ4_compress_fast_continue over chains of linked blocks, DIRECT buffers: chain c is the blocks chainFirst[c] .. chainFirst[c + 1] - 1,
    * whose sources lie back to back from src[chainSrcOff[c]] on behind chainPrefixLen[c] bytes of history (null: none); block i owns
    * dest[destOff[i], + destCap[i]).  outLen = liblz4's return values (0 ends a chain, LZ4HIPBatch.CHAIN_STOPPED behind it),
