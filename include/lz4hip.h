@@ -351,7 +351,8 @@ int lz4hip_decompress_safe_stream_batch(lz4hip_dstream_state* state, const uint8
  *     table, which is not the table a running stream would hold: continuing a stream in a second call gives valid, decodable, but
  *     other bytes than one long chain); sources that are not contiguous; LZ4_attach_dictionary.  (No longer out of scope: an HC form
  *     is lz4hip_compress_hc_chain_batch, below.)  (No longer out of scope: resuming a stream's exact state across calls, LZ4_saveDict
- *     included, is lz4hip_compress_fast_stream_batch, below.)                                                                       */
+ *     included, is lz4hip_compress_fast_stream_batch, below.)  (No longer out of scope: sources that are not contiguous, on a
+ *     resident stream, is lz4hip_compress_fast_stream_ext_batch, below.)                                                            */
 int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
                                      const int32_t* src_len, const uint32_t* chain_first,
                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
@@ -432,7 +433,8 @@ int lz4hip_compress_hc_chain_batch(const uint8_t* src, const uint64_t* chain_src
  *     only the bytes produced;
  *   - out of scope: a device-pointer form (as for lz4hip_compress_hc_chain_batch: left to a change that can also extend the far-offset
  *     table of the device entry points); acceleration above 1; the external-dictionary mode (a source that does not follow its
- *     history); LZ4_attach_dictionary; an HC form; streams longer than the index limit.                                             */
+ *     history); LZ4_attach_dictionary; an HC form; streams longer than the index limit.  (No longer out of scope: the
+ *     external-dictionary mode is lz4hip_compress_fast_stream_ext_batch, below.)                                                    */
 typedef struct lz4hip_cstreams lz4hip_cstreams;
 int lz4hip_cstreams_create(uint32_t n_streams, lz4hip_cstreams** out);
 int lz4hip_cstreams_count(const lz4hip_cstreams* set);
@@ -444,6 +446,63 @@ int lz4hip_compress_fast_stream_batch(lz4hip_cstreams* set, const uint32_t* stre
                                       const int32_t* src_len, const uint32_t* chain_first,
                                       uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                       int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains);
+/* COMPRESS STREAMS WHOSE SOURCES LAND ANYWHERE -- a ring that wraps, two alternating buffers, a save area, a dictionary elsewhere: the
+ * same sets, the same streams and THE SAME CONTRACT as lz4hip_compress_fast_stream_batch: for every stream, byte for byte and return
+ * value for return value what ONE LZ4_stream_t of liblz4 1.9.3 gives over all the calls that named the stream since its creation or
+ * last reset -- through both entry points, in any interleaving, however the blocks are cut into calls.  What is new: every block has
+ * ITS OWN src_off[i], and a block whose source does not follow the stream's history runs in liblz4's external-dictionary mode.
+ *   - where the history lies: per call and stream, it ends at chain_hist_end[c] in this call's src, with chain_hist_len[c] bytes of it
+ *     present.  What counts is min(chain_hist_len[c], 65536, what the stream holds); a shorter value than the stream holds is
+ *     LZ4_saveDict with a smaller size, as for the call above.  After the call the history ends where the stream's last block of
+ *     one byte and more ended, and the caller says so in the next call (or where it has moved the bytes to);
+ *   - a fresh stream loads those bytes as LZ4_loadDict does (the 8-byte minimum, indexes from 65536).  A fresh stream whose first
+ *     block does not follow that history is lz4hip_compress_fast_dict*'s block, byte for byte;
+ *   - the state machine per block, LZ4_compress_fast_continue's.  D = [D_end - D_len, D_end) is the history, the block is
+ *     [s, s + n), s = src_off[i]:
+ *       1. D_len < 4 and D_end != s: the history is dropped;
+ *       2. s + n > D_end - D_len and s + n < D_end (the source overlaps its own history): D_len = D_end - (s + n), at most 64 KB, and
+ *          under 4 bytes it becomes 0;
+ *       3. D_end == s: prefix mode, the block of the call above; candidates below idx - D_len are refused while D_len < 64 KB and
+ *          D_len < idx; afterwards D_len += n, D_end = s + n;
+ *       4. otherwise external-dictionary mode: the indexes [idx - D_len, idx) name the bytes of D, those from idx on the block; the same
+ *          lower bound; a match that reaches D_end goes on at the block's start; the backward catch-up stops at the start of the
+ *          buffer the match lies in.  Afterwards D is the block alone: D_end = s + n, D_len = n (a block of 0 bytes at a jump drops the
+ *          history entirely);
+ *       5. idx += n.
+ *   - A CALL IS A SNAPSHOT: all blocks of a call are read from src as it is during the call.  A producer that writes over its ring
+ *     ends the call in front of the first block whose bytes land on anything an earlier block of the same call reads -- its source,
+ *     or the history it can reach -- as a caller of liblz4 compresses a block before it writes the next over old data;
+ *   - a source that runs over the END of its history (rule 2 catches only one that ends inside it) sees the history as it is now,
+ *     as liblz4 does.  ONE EXCEPTION to byte equality: such a source that begins EXACTLY at its history's first byte (one reused
+ *     buffer, a longer block than the one before).  liblz4 then takes matches inside the block for dictionary matches and cuts them
+ *     short; the engine finds the ordinary, longer ones.  Return values may differ by a few bytes; both outputs are valid LZ4.  The
+ *     input is misuse either way: the history was overwritten, and liblz4's own output does not decode there;
+ *   - the table is byU32, acceleration 1; a block under 13 bytes is one literal run that still moves the index space; the
+ *     0x7E000000 life limit, a result of 0 stopping the stream, LZ4HIP_CHAIN_STOPPED, chain_consumed, lz4hip_cstreams_reset and
+ *     lz4hip_cstreams_consumed, and what a library failure after the launch leaves behind are the call above's;
+ *   - the window: every source [src_off[i], + src_len[i]) of stream c lies inside [chain_win_off[c], + chain_win_len[c]) -- the ring,
+ *     the pair of buffers, the save area plus the block area.  The history PIECE, the last min(chain_hist_len[c], 65536) bytes in front
+ *     of chain_hist_end[c], lies wholly inside the window or wholly outside it; one that ends exactly at the window's start stays
+ *     contiguous with it (a caller whose dictionary leads into the window widens the window once the history has grown out of the
+ *     dictionary).  Outside pieces may be shared by streams.  Sources are only read: windows of different streams may overlap.
+ *     Destination slots may not overlap;
+ *   - nothing outside the call's sources and history pieces is read, nothing outside a block's slot is written;
+ *   - LZ4HIP_E_ARG, said before a device is looked for: a NULL set or pointer (ALL pointers are required), ids that are not strictly
+ *     ascending or are >= n_streams, a chain_first that is not ascending from 0 to n_blocks, a source outside its window, a history
+ *     piece that straddles a window edge, a chain_hist_len[c] longer than chain_hist_end[c], a negative chain_hist_len[c].  Without
+ *     a device a well-formed call is LZ4HIP_E_NO_DEVICE;
+ *   - one kernel, compress_fast_xstream_cu_kernel: compress_fast_stream_cu_kernel's shape and state traffic; per block the walk
+ *     chooses, on wave-uniform values, between the linked-block core and the core that is linked-block and dictionary at once;
+ *   - the host form mirrors the USED part of every window on the device (the call's sources and the history piece), uploads each
+ *     outside piece once per staged chunk, brings back only the bytes produced, and shards at the set's device ranges;
+ *   - out of scope: device-pointer forms (as above: left to a change that can also extend the far-offset and stream-contract tables
+ *     of the device entry points); acceleration above 1; LZ4_attach_dictionary; an HC form; streams past the index limit.          */
+int lz4hip_compress_fast_stream_ext_batch(lz4hip_cstreams* set, const uint32_t* stream_id,
+                                          const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, const uint32_t* chain_first,
+                                          const uint64_t* chain_hist_end, const int32_t* chain_hist_len,
+                                          const uint64_t* chain_win_off, const uint64_t* chain_win_len,
+                                          uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                          int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains);
 /* COMPRESS AGAINST A DICTIONARY: for every block i, on a fresh stream,
  *     LZ4_loadDict(s, dict, dict_len);  LZ4_compress_fast_continue(s, src_i, dst_i, src_len[i], dst_cap[i], 1)
  * of liblz4 1.9.3 with a dictionary that is NOT contiguous with the source (its external-dictionary mode): the return value and the

@@ -75,6 +75,8 @@ C_ABI = {
     "lz4hip_cstreams_free": (None, [C.c_void_p]),
     "lz4hip_compress_fast_stream_batch": (C.c_int, [C.c_void_p, _u32p, C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p,
                                                     C.c_uint32, C.c_uint32]),
+    "lz4hip_compress_fast_stream_ext_batch": (C.c_int, [C.c_void_p, _u32p, C.c_void_p, _u64p, _i32p, _u32p, _u64p, _i32p, _u64p, _u64p, C.c_void_p, _u64p,
+                                                        _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
@@ -1073,6 +1075,33 @@ class LZ4HIPBatch:
         return list(out[:n]), list(cons[:nc])
 
     @classmethod
+    def compressFastStreamAt(cls, streams, streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dst, dstOff, dstCap):
+        """The same streams when their sources land anywhere -- a ring that wraps, alternating buffers, a dictionary elsewhere
+        (lz4hip_compress_fast_stream_ext_batch): every block has its own srcOff[i] inside its stream's window [chainWinOff[c],
+        + chainWinLen[c]); the stream's history ends at chainHistEnd[c] in src with chainHistLen[c] bytes of it present.  A block that
+        does not follow its history runs in liblz4's external-dictionary mode.  A call is a snapshot of src -> (outLen, chainConsumed)
+        as compressFastStream's"""
+        n, nc = len(srcLen), len(streamId)
+        if not (len(srcOff) == len(dstOff) == len(dstCap) == n) or not (len(chainHistEnd) == len(chainHistLen) == len(chainWinOff) == len(chainWinLen) == nc) \
+                or len(chainFirst) != nc + 1:
+            raise ValueError("array lengths differ")
+        ns = len(streams)
+        if any(streamId[c] < 0 or streamId[c] >= ns or (c and streamId[c] <= streamId[c - 1]) for c in range(nc)):
+            raise ValueError("streamId must be strictly ascending and below the number of streams")
+        sp, sk = _ro_ptr(src)
+        dp, dk = _rw_ptr(dst)
+        out = (C.c_int32 * max(n, 1))()
+        cons = (C.c_uint64 * max(nc, 1))()
+        _chk(lib().lz4hip_compress_fast_stream_ext_batch(streams._handle(), _arr(C.c_uint32, streamId), sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen),
+                                                         _arr(C.c_uint32, chainFirst), _arr(C.c_uint64, chainHistEnd), _arr(C.c_int32, chainHistLen),
+                                                         _arr(C.c_uint64, chainWinOff), _arr(C.c_uint64, chainWinLen), dp, _arr(C.c_uint64, dstOff),
+                                                         _arr(C.c_int32, dstCap), out, cons, n, nc))
+        if hasattr(srcLen, "dtype"):
+            import numpy as np
+            return np.frombuffer(out, dtype=np.int32, count=n).copy(), np.frombuffer(cons, dtype=np.uint64, count=nc).copy()
+        return list(out[:n]), list(cons[:nc])
+
+    @classmethod
     def decompressSafePartial(cls, src, srcOff, srcLen, dst, dstOff, targetLen, dstCap):
         """LZ4_decompress_safe_partial per block: the first min(targetLen[i], dstCap[i]) bytes of block i into the slot
         dst[dstOff[i]:+dstCap[i]] -> liblz4's return values (lz4hip_decompress_safe_partial_batch; lists, or an int32 array for numpy
@@ -1187,6 +1216,11 @@ class CompressStreams:
     def compress(self, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None):
         """LZ4HIPBatch.compressFastStream on this set"""
         return LZ4HIPBatch.compressFastStream(self, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen)
+
+    def compressAt(self, streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dst, dstOff, dstCap):
+        """LZ4HIPBatch.compressFastStreamAt on this set: sources that land anywhere"""
+        return LZ4HIPBatch.compressFastStreamAt(self, streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dst, dstOff,
+                                                dstCap)
 
     def reset(self, streamId=None):
         """makes the listed streams (None: all of them) fresh"""

@@ -96,13 +96,15 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // arrays and host path, plus the slot of every chain's stream and the device's share of the set's state (BlockCall::cs_*)
 // OP_DECOMPRESS_STREAM: LZ4_decompress_safe_continue on streams whose blocks land anywhere (every mode of LZ4_streamDecode_t): its
 // arrays and state records are BlockCall::dstream; the host path is dstream_host_shard
+// OP_COMPRESS_XSTREAM: the same resident streams when their sources land anywhere (liblz4's external-dictionary mode included): its
+// arrays are BlockCall::cxstream, which carries the device's share of the set's state; the host path is cxstream_host_shard
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
           OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN, OP_COMPRESS_CHAIN, OP_COMPRESS_HC_CHAIN, OP_COMPRESS_STREAM,
-          OP_DECOMPRESS_STREAM };
-constexpr int OP_COUNT = OP_DECOMPRESS_STREAM + 1;   // (the last enumerator)
+          OP_DECOMPRESS_STREAM, OP_COMPRESS_XSTREAM };
+constexpr int OP_COUNT = OP_COMPRESS_XSTREAM + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
-constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN || op == OP_COMPRESS_STREAM; }
+constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN || op == OP_COMPRESS_STREAM || op == OP_COMPRESS_XSTREAM; }
 // a second per-block result (BlockCall::consumed) travels behind out[]
 constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
 // out[i] counts SOURCE bytes read: a block that succeeded filled its whole dst_cap[i]
@@ -134,6 +136,7 @@ struct BlockCall {
   const lz4hip::ChainArgs* chain = nullptr;   // OP_DECOMPRESS_CHAIN: the call's arrays on the device
   const lz4hip::CChainArgs* cchain = nullptr; // op_takes_cchain: the call's arrays on the device
   const lz4hip::DStreamArgs* dstream = nullptr;   // OP_DECOMPRESS_STREAM: the call's arrays and state records on the device
+  const lz4hip::CXStreamArgs* cxstream = nullptr; // OP_COMPRESS_XSTREAM: the call's arrays on the device, the slots and the set's state
   void* hc_scratch = nullptr;           // op_needs_chain_scratch: lz4hip::hc_chain_scratch_bytes of device memory
   // op_resumes_streams: the device's share of the set's state (kernels.h CStreamArgs) and, on the device, the slot of every chain
   uint32_t* cs_rec = nullptr; uint64_t* cs_tables = nullptr; const uint32_t* cs_slot = nullptr;
@@ -408,6 +411,9 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
       const lz4hip::CStreamArgs sa{*c.cchain, c.cs_slot, c.cs_rec, c.cs_tables};
       return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_stream(sa, q, lz4hip::device_cus(), st); });
     }
+    case OP_COMPRESS_XSTREAM:   // compress_fast_xstream_cu_kernel draws chains from the queue word
+      if (!c.cxstream) return fail(LZ4HIP_E_ARG, kNullArg);
+      return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_xstream(*c.cxstream, q, lz4hip::device_cus(), st); });
     case OP_COMPRESS_HC_CHAIN: {   // layout, segment build and parse kernels behind one scratch allocation
       if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
       // (workspace and scratch are the buffer set's.  As a stream-ordered allocation made here, the scratch read as zeros in the parse
@@ -1162,6 +1168,98 @@ const char* cchain_arg_error(const lz4hip::CChainArgs& a, bool host, bool stops)
   return host ? staging::chain_shape_error(a.chain_first, a.n_chains, a.n_blocks, a.chain_prefix_len, a.chain_src_off, false) : nullptr;
 }
 
+// ---- resident streams whose sources land anywhere, on the host-pointer path ----
+// the caller's HOST arrays of lz4hip_compress_fast_stream_ext_batch
+struct CXStreamHost {
+  const uint8_t* src; const uint64_t* src_off; const int32_t* src_len; const uint32_t* chain_first; const uint64_t* hist_end; const int32_t* hist_len;
+  const uint64_t* win_off; const uint64_t* win_len; uint8_t* dst; const uint64_t* dst_off; const int32_t* dst_cap; int32_t* out; uint64_t* chain_consumed;
+  uint32_t n_blocks, n_chains;
+};
+// One device's share [c0, c1) of such a call: cchain_host_shard's frame (chunks of 64 MiB of image or 512 MiB of slots, one stream at
+// least, through the first buffer set of a pooled pair; proto.cs_*: the share's slots and state) around the image of host_staging.h
+// CxImage.  Per stream the used part of its window is mirrored: up go the sources that can run and the history pieces -- those inside a
+// window or in front of it where they lie in the mirror, those apart once per chunk -- as runs (what a joined run carries between two
+// pieces lands in mirror bytes nothing reads); the kernel gets every offset in device terms; the results come back, then only the
+// bytes each block produced.
+int cxstream_host_shard(const BlockCall& proto, const CXStreamHost& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+  if (c1 == c0) return LZ4HIP_OK;
+  ShardScope sh(ord, err);
+  if (sh.rc) return sh.rc;
+  ChunkSlot& s = sh.pair->slot[0];
+  const hipStream_t st = s.st;
+  auto produced = [&](uint32_t i) -> size_t { const int32_t r = h.out[i]; return r > 0 && (size_t)r <= pos(h.dst_cap[i]) ? (size_t)r : 0; };   // (h.out: once it is back)
+  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+  std::vector<uint64_t> dso;
+  std::vector<staging::Run> runs;
+  for (uint32_t c = c0; c < c1;) {
+    // the next chunk: streams [c, j), blocks [b0, b1)
+    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, [&](uint32_t j) {
+      size_t d = 0;
+      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) d += al16(pos(h.dst_cap[i]));
+      staging::DsPiece p;
+      (void)staging::cxstream_piece(h.hist_end[j], h.hist_len[j], h.win_off[j], h.win_len[j], &p);
+      return staging::Cost{staging::cxstream_cost(staging::cxstream_hull(h.chain_first, j, h.src_off, h.src_len, h.hist_end[j], p, h.win_off[j]), p), d};
+    });
+    const uint32_t j = ck.end, b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
+    const staging::CxImage im(h.chain_first, c, nc, h.src_off, h.src_len, h.hist_end, h.hist_len, h.win_off, h.win_len);
+    dso.resize(nb);
+    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { dso[t] = o; o += al16(pos(h.dst_cap[b0 + t])); } }
+    const staging::CXStreamMeta m(nb, nc);
+    if (!sh.reserve(s, im.total, true, ck.dst, m.l.total)) return sh.rc;
+    uint8_t *const hs = (uint8_t*)s.h_src.p, *const ds = (uint8_t*)s.d_src.p, *const hd = (uint8_t*)s.h_dst.p;
+    void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
+    m.l.zero_results(hm);
+    runs.clear();
+    // (of a stream's sources only what its blocks can consume: up to the first block with a negative length.  The copies into the
+    // pinned mirror run stream by stream on several threads; a stream's mirror is its own, so no two threads write one byte -- two
+    // sources of ONE stream may overlap, and their bytes are the same bytes)
+    par_blocks(c, j, im.total, [=, &im](uint32_t u) {
+      const uint32_t t = u - c;
+      for (uint32_t i = h.chain_first[u]; i < h.chain_first[u + 1] && h.src_len[i] >= 0; i++)
+        if (h.src_len[i] > 0) memcpy(hs + (size_t)im.to_dev(t, h.src_off[i]), h.src + h.src_off[i], (size_t)h.src_len[i]);
+      const staging::DsPiece& p = im.piece[t];
+      if (p.kind == staging::DS_INSIDE || p.kind == staging::DS_LEAD) memcpy(hs + im.hist_dev[t] - p.keep, h.src + h.hist_end[u] - p.keep, (size_t)p.keep);
+    });
+    for (uint32_t t = 0; t < nc; t++) {
+      for (uint32_t i = h.chain_first[c + t]; i < h.chain_first[c + t + 1] && h.src_len[i] >= 0; i++)
+        if (h.src_len[i] > 0) runs.push_back(staging::Run{(size_t)im.to_dev(t, h.src_off[i]), (size_t)h.src_len[i]});
+      const staging::DsPiece& p = im.piece[t];
+      if (p.kind == staging::DS_INSIDE || p.kind == staging::DS_LEAD) runs.push_back(staging::Run{(size_t)(im.hist_dev[t] - p.keep), (size_t)p.keep});
+    }
+    for (const staging::DsApart& a : im.apart) {
+      memcpy(hs + a.dev, h.src + a.end - a.keep, (size_t)a.keep);
+      runs.push_back(staging::Run{a.dev, (size_t)a.keep});
+    }
+    staging::merge_runs(runs);
+    for (uint32_t t = 0; t < nc; t++) {
+      for (uint32_t i = h.chain_first[c + t]; i < h.chain_first[c + t + 1]; i++) m.src_off.in(hm)[i - b0] = im.to_dev(t, h.src_off[i]);
+      m.hist_end.in(hm)[t] = im.hist_dev[t];
+      m.hist_len.in(hm)[t] = (int32_t)im.piece[t].keep;
+      const uint32_t id = proto.cs_ids[c + t];
+      m.slot.in(hm)[t] = (id - proto.cs_id0) | (proto.cs_poisoned && proto.cs_poisoned[id] ? lz4hip::kStreamForceStop : 0u);
+    }
+    memcpy(m.dst_off.in(hm), dso.data(), m.dst_off.bytes());
+    memcpy(m.src_len.in(hm), h.src_len + b0, m.src_len.bytes());
+    memcpy(m.dst_cap.in(hm), h.dst_cap + b0, m.dst_cap.bytes());
+    for (uint32_t t = 0; t <= nc; t++) m.first.in(hm)[t] = h.chain_first[c + t] - b0;
+    for (const staging::Run& r : runs)
+      if (!sh.ok("H2D src", hipMemcpyAsync(ds + r.off, hs + r.off, r.len, hipMemcpyHostToDevice, st))) return sh.rc;
+    if (!sh.upload(s, 0, m.l, st)) return sh.rc;
+    const lz4hip::CXStreamArgs a{{{ds, nullptr, m.hist_len.in(dm), m.src_len.in(dm), m.first.in(dm), (uint8_t*)s.d_dst.p, m.dst_off.in(dm), m.dst_cap.in(dm),
+                                   m.out.in(dm), m.consumed.in(dm), nb, nc}, m.slot.in(dm), proto.cs_rec, proto.cs_tables}, m.src_off.in(dm), m.hist_end.in(dm)};
+    BlockCall call = proto; call.cxstream = &a;
+    if (proto.cs_launched) *proto.cs_launched = true;
+    if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
+    memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
+    memcpy(h.chain_consumed + c, m.consumed.in(hm), m.consumed.bytes());
+    // only the bytes produced come back
+    if (!sh.fetch_runs(s, nb, [&](uint32_t t) { return staging::Run{(size_t)dso[t], produced(b0 + t)}; })) return sh.rc;
+    par_blocks(b0, b1, ck.dst, [=, &dso](uint32_t i) { if (const size_t r = produced(i)) memcpy(h.dst + h.dst_off[i], hd + dso[i - b0], r); });
+    c = j;
+  }
+  return LZ4HIP_OK;
+}
+
 // hashes of one device's share [b0, b1) of a host batch: the same pinned, double-buffered staging as host_shard (chunks of
 // <= CHUNK_SRC bytes packed by several host threads while the previous chunk is on the GPU), from the same pool of buffer pairs
 template <class T>
@@ -1716,6 +1814,65 @@ const char* cstream_arg_error(const lz4hip_cstreams* set, const uint32_t* stream
   }
   return nullptr;
 }
+// the argument errors of lz4hip_compress_fast_stream_ext_batch, in the same order: the arrays, then the set, then the ids against it
+const char* cxstream_arg_error(const lz4hip_cstreams* set, const uint32_t* stream_id, const CXStreamHost& h) {
+  if (h.n_chains != 0 || h.n_blocks != 0) {
+    if (!stream_id || !h.src || !h.src_off || !h.src_len || !h.chain_first || !h.hist_end || !h.hist_len || !h.win_off || !h.win_len || !h.dst || !h.dst_off ||
+        !h.dst_cap || !h.out || !h.chain_consumed) return kNullArg;
+    if (const char* why = staging::cxstream_shape_error(h.chain_first, h.n_chains, h.n_blocks, h.src_off, h.src_len, h.hist_end, h.hist_len, h.win_off, h.win_len))
+      return why;
+    for (uint32_t c = 1; c < h.n_chains; c++)
+      if (stream_id[c] <= stream_id[c - 1]) return "stream_id must be strictly ascending";
+  }
+  if (!set) return "null stream set";
+  for (uint32_t c = 0; c < h.n_chains; c++) {
+    if (stream_id[c] >= set->n) return "stream_id out of range";
+  }
+  return nullptr;
+}
+// One call on a set, for both entry points: whole streams per device, at the boundaries the set was created with -- [c0, c1) of the
+// call's chains are part p's -- every share through shard(call, ord, c0, c1, err) with the share's state in call.cs_*, side by side
+// where there are several.  The set is locked for the call.
+template <class Shard>
+int cstreams_call(lz4hip_cstreams* set, const uint32_t* stream_id, uint32_t n_chains, Op op, Shard shard) {
+  std::lock_guard<std::mutex> lk(set->mu);
+  struct Share { const lz4hip_cstreams::Part* p; uint32_t c0, c1; int rc = 0; std::string err; bool launched = false; };
+  std::vector<Share> shares;
+  try {
+    for (const auto& p : set->parts) {
+      const uint32_t c0 = (uint32_t)(std::lower_bound(stream_id, stream_id + n_chains, p.lo) - stream_id);
+      const uint32_t c1 = (uint32_t)(std::lower_bound(stream_id, stream_id + n_chains, p.hi) - stream_id);
+      if (c1 > c0) shares.push_back(Share{&p, c0, c1});
+    }
+  } catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  auto run = [&](Share& s) {
+    BlockCall call{op};
+    call.cs_rec = s.p->rec; call.cs_tables = s.p->tables; call.cs_ids = stream_id; call.cs_id0 = s.p->lo; call.cs_poisoned = set->poisoned.data();
+    call.cs_launched = &s.launched;
+    try { s.rc = shard(call, s.p->ord, s.c0, s.c1, &s.err); }
+    catch (...) { s.rc = LZ4HIP_E_NOMEM; s.err = "out of memory"; }
+  };
+  if (shares.size() == 1) {
+    run(shares[0]);
+  } else {
+    std::vector<std::thread> th;
+    try { for (auto& s : shares) th.emplace_back([&run, &s] { run(s); }); }
+    catch (...) { for (auto& t : th) t.join(); if (prev >= 0) (void)hipSetDevice(prev); return fail(LZ4HIP_E_NOMEM, "out of memory or threads"); }
+    for (auto& t : th) t.join();
+  }
+  if (prev >= 0) (void)hipSetDevice(prev);
+  // the call failed after a launch: some of the streams it named have gone on and some have not, and the caller has no results to tell
+  // which, so EVERY stream the call named is stopped until it is reset (those of the shares that succeeded too)
+  bool failed = false, launched = false;
+  for (auto& s : shares) { failed |= s.rc != 0; launched |= s.launched; }
+  if (failed && launched)
+    for (uint32_t c = 0; c < n_chains; c++) set->poisoned[stream_id[c]] = 1;
+  for (auto& s : shares)
+    if (s.rc) return fail(s.rc, s.err.c_str());
+  return LZ4HIP_OK;
+}
 }  // namespace
 
 // ---- streaming xxhash (StreamingXXHash32JNI / StreamingXXHash64JNI: XXHashJNI.c:89-145, :199-255) ------------------------
@@ -2107,44 +2264,20 @@ int lz4hip_compress_fast_stream_batch(lz4hip_cstreams* set, const uint32_t* stre
   if (const char* why = cstream_arg_error(set, stream_id, h)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
   if (const int rc = need_device()) return rc;
   if (n_chains == 0) return LZ4HIP_OK;
-  std::lock_guard<std::mutex> lk(set->mu);
-  // whole streams per device, at the boundaries the set was created with: [c0, c1) of the call's chains are part p's
-  struct Share { const lz4hip_cstreams::Part* p; uint32_t c0, c1; int rc = 0; std::string err; bool launched = false; };
-  std::vector<Share> shares;
-  try {
-    for (const auto& p : set->parts) {
-      const uint32_t c0 = (uint32_t)(std::lower_bound(stream_id, stream_id + n_chains, p.lo) - stream_id);
-      const uint32_t c1 = (uint32_t)(std::lower_bound(stream_id, stream_id + n_chains, p.hi) - stream_id);
-      if (c1 > c0) shares.push_back(Share{&p, c0, c1});
-    }
-  } catch (...) { return fail(LZ4HIP_E_NOMEM, "out of memory"); }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  auto run = [&](Share& s) {
-    BlockCall call{OP_COMPRESS_STREAM};
-    call.cs_rec = s.p->rec; call.cs_tables = s.p->tables; call.cs_ids = stream_id; call.cs_id0 = s.p->lo; call.cs_poisoned = set->poisoned.data();
-    call.cs_launched = &s.launched;
-    try { s.rc = cchain_host_shard(call, h, s.p->ord, s.c0, s.c1, &s.err); }
-    catch (...) { s.rc = LZ4HIP_E_NOMEM; s.err = "out of memory"; }
-  };
-  if (shares.size() == 1) {
-    run(shares[0]);
-  } else {
-    std::vector<std::thread> th;
-    try { for (auto& s : shares) th.emplace_back([&run, &s] { run(s); }); }
-    catch (...) { for (auto& t : th) t.join(); if (prev >= 0) (void)hipSetDevice(prev); return fail(LZ4HIP_E_NOMEM, "out of memory or threads"); }
-    for (auto& t : th) t.join();
-  }
-  if (prev >= 0) (void)hipSetDevice(prev);
-  // the call failed after a launch: some of the streams it named have gone on and some have not, and the caller has no results to tell
-  // which, so EVERY stream the call named is stopped until it is reset (those of the shares that succeeded too)
-  bool failed = false, launched = false;
-  for (auto& s : shares) { failed |= s.rc != 0; launched |= s.launched; }
-  if (failed && launched)
-    for (uint32_t c = 0; c < n_chains; c++) set->poisoned[stream_id[c]] = 1;
-  for (auto& s : shares)
-    if (s.rc) return fail(s.rc, s.err.c_str());
-  return LZ4HIP_OK;
+  return cstreams_call(set, stream_id, n_chains, OP_COMPRESS_STREAM,
+                       [&](const BlockCall& call, int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard(call, h, ord, c0, c1, err); });
+}
+int lz4hip_compress_fast_stream_ext_batch(lz4hip_cstreams* set, const uint32_t* stream_id, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                          const uint32_t* chain_first, const uint64_t* chain_hist_end, const int32_t* chain_hist_len,
+                                          const uint64_t* chain_win_off, const uint64_t* chain_win_len, uint8_t* dst, const uint64_t* dst_off,
+                                          const int32_t* dst_cap, int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains) {
+  const CXStreamHost h{src, src_off, src_len, chain_first, chain_hist_end, chain_hist_len, chain_win_off, chain_win_len, dst, dst_off, dst_cap, out_len,
+                       chain_consumed, n_blocks, n_chains};
+  if (const char* why = cxstream_arg_error(set, stream_id, h)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
+  if (const int rc = need_device()) return rc;
+  if (n_chains == 0) return LZ4HIP_OK;
+  return cstreams_call(set, stream_id, n_chains, OP_COMPRESS_XSTREAM,
+                       [&](const BlockCall& call, int ord, uint32_t c0, uint32_t c1, std::string* err) { return cxstream_host_shard(call, h, ord, c0, c1, err); });
 }
 int lz4hip_compress_hc_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
                                    const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,

@@ -492,6 +492,32 @@ int launch_compress_fast_stream(const CStreamArgs& a, uint32_t* q, uint32_t n_cu
   return launch_queue_kernel(compress_fast_stream_cu_kernel, a.c.n_chains, q, 1u, n_cus, stream, a, q);
 }
 
+// The resident streams when their sources land anywhere: the same shape and state, lz4_fast_chain.h's cxstream_walk.  Per block the walk
+// chooses between the LINK core (the source follows its history) and the LINK + DICT core (the history lies elsewhere) on offsets and
+// lengths that are read through readfirstlane (io.uni / uni64): the choice and everything it depends on stay in scalar registers, and
+// both cores work on the one table in LDS.
+struct CXStreamIoDev : CStreamIoDev {
+  __device__ __forceinline__ void begin_xblock(const uint8_t*, uint32_t, const uint8_t*, uint32_t, uint8_t*, uint32_t) const {}
+};
+__global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_xstream_cu_kernel(CXStreamArgs a, uint32_t* q) {
+  __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
+  WaveDev w(tables[threadIdx.x >> 6]);
+  CXStreamIoDev io{{{a.s.c}}};
+  for (;;) {
+    uint32_t c = 0;
+    if (__lane_id() == 0) c = atomicAdd(q, 1u);
+    c = __builtin_amdgcn_readfirstlane(c);
+    if (c >= a.s.c.n_chains) return;
+    cxstream_walk(w, io, a, c);
+    WaveDev::sync();  // the table is reused: the next stream loads or builds its own
+  }
+}
+int launch_compress_fast_xstream(const CXStreamArgs& a, uint32_t* q, uint32_t n_cus, void* stream) {
+  if (a.s.c.n_chains == 0) return 0;
+  if (!q || !a.s.slot || !a.s.rec || !a.s.tables || !a.src_off || !a.chain_hist_end || !a.s.c.chain_prefix_len) return (int)hipErrorInvalidValue;
+  return launch_queue_kernel(compress_fast_xstream_cu_kernel, a.s.c.n_chains, q, 1u, n_cus, stream, a, q);
+}
+
 // LZ4_compress_destSize: the one-sequence-per-step core (acceleration 1) with DirectOut's FILL switch on; dst_cap[b] is the target.  A
 // block whose target is full stops at the next step, so the steps spent on it follow the input it consumes, not src_len.
 __global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_dest_cu_kernel(BatchArgs a, int32_t* consumed, uint32_t* q) {

@@ -1,7 +1,8 @@
 // host_staging.h -- the arithmetic of staging a host batch (api.cpp's shard functions), free of HIP so that it is compiled and tested
 // without a device (tests/cpp/host_staging_test.cpp): where a chunk's metadata arrays lie in their one buffer, where a chunk ends,
-// which produced bytes travel back in one copy, the shape the arrays of a chain call must have, and where the windows and history
-// pieces of a stream-decode call lie in the device image.
+// which produced bytes travel back in one copy, the shape the arrays of a chain call must have, where the windows and history
+// pieces of a stream-decode call lie in the device image, and where the used parts of the windows and the history pieces of a
+// stream-compress call whose sources land anywhere lie in theirs.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -41,7 +42,7 @@ struct MetaLayout {
   size_t results_bytes() const { return total - results; }
   void zero_results(void* host) const { if (upload > results) memset((uint8_t*)host + results, 0, upload - results); }
 };
-// The four layouts.  (Members are initialised in the order they are declared: that order is the order in the buffer.)
+// The layouts.  (Members are initialised in the order they are declared: that order is the order in the buffer.)
 struct BlockMeta {   // the block operations (host_shard): nb blocks; consumed[] only where the operation has a second result
   MetaLayout l;
   Region<uint64_t> src_off, dst_off; Region<int32_t> src_len, dst_cap, out, consumed;
@@ -62,6 +63,14 @@ struct CChainMeta {   // chain compress (cchain_host_shard): out[] and chain_con
   CChainMeta(size_t nb, size_t nc, bool has_slot = false)
       : chain_src_off(l.input<uint64_t>(nc)), dst_off(l.input<uint64_t>(nb)), src_len(l.input<int32_t>(nb)), dst_cap(l.input<int32_t>(nb)),
         prefix(l.input<int32_t>(nc)), first(l.input<uint32_t>(nc + 1)), slot(l.input<uint32_t>(has_slot ? nc : 0)),
+        consumed(l.result<uint64_t>(nc, true)), out(l.result<int32_t>(nb, true)) {}
+};
+struct CXStreamMeta {   // resident streams whose sources land anywhere (cxstream_host_shard): out[] and chain_consumed[] go up zeroed
+  MetaLayout l;
+  Region<uint64_t> src_off, dst_off, hist_end; Region<int32_t> src_len, dst_cap, hist_len; Region<uint32_t> first, slot; Region<uint64_t> consumed; Region<int32_t> out;
+  CXStreamMeta(size_t nb, size_t nc)
+      : src_off(l.input<uint64_t>(nb)), dst_off(l.input<uint64_t>(nb)), hist_end(l.input<uint64_t>(nc)), src_len(l.input<int32_t>(nb)), dst_cap(l.input<int32_t>(nb)),
+        hist_len(l.input<int32_t>(nc)), first(l.input<uint32_t>(nc + 1)), slot(l.input<uint32_t>(nc)),
         consumed(l.result<uint64_t>(nc, true)), out(l.result<int32_t>(nb, true)) {}
 };
 template <class T>
@@ -241,6 +250,94 @@ struct DsImage {
     if (v >= win[t] && v - win[t] <= win_len) return win_off + (v - win[t]);
     return v == dev[t].prefix_end ? host.prefix_end : host.ext_end;
   }
+};
+
+// ---- the stream compressor's device image when sources land anywhere (api.cpp cxstream_host_shard) ----
+// Per call and stream the caller says where the stream's history ends in src and how much of it is there; the PIECE that can be read is
+// its last min(len, 65536) bytes (LZ4_loadDict's and LZ4_saveDict's 64 KB: one byte more than the decoder's piece).  Against the
+// stream's window it is placed as the decoder's pieces are: inside, contiguous in front of it (it ends at win_off), or apart.  Of a window
+// only the USED part is mirrored: the hull [lo, hi) of the call's sources and of a piece that is inside or contiguous, at the device
+// offset base; x in the hull is base + (x - lo), so every comparison of offsets the walk makes holds on the device as it does in the
+// caller's terms.  Pieces apart follow the hulls, each once per chunk.
+constexpr uint64_t kCxKeep = 65536;
+inline const char* cxstream_piece(uint64_t end, int32_t len, uint64_t win_off, uint64_t win_len, DsPiece* p) {
+  *p = DsPiece{};
+  if (len < 0) return "negative chain_hist_len";
+  if (len == 0) return nullptr;
+  if ((uint64_t)len > end) return "chain_hist_len reaches in front of src";
+  p->keep = (uint64_t)len < kCxKeep ? (uint64_t)len : kCxKeep;
+  const uint64_t start = end - p->keep, wend = win_off + win_len;
+  if (start >= win_off && end <= wend) p->kind = DS_INSIDE;
+  else if (end <= win_off) p->kind = end == win_off ? DS_LEAD : DS_APART;
+  else if (start >= wend) p->kind = DS_APART;
+  else return "the history straddles an edge of the stream's window";
+  return nullptr;
+}
+// What can be said about a call without a device: the shape of chain_first, every window has an end, every source lies inside its
+// stream's window (a negative length: its offset does), every history piece is placeable.  -> a message, or nullptr
+inline const char* cxstream_shape_error(const uint32_t* chain_first, uint32_t n_chains, uint32_t n_blocks, const uint64_t* src_off, const int32_t* src_len,
+                                        const uint64_t* hist_end, const int32_t* hist_len, const uint64_t* win_off, const uint64_t* win_len) {
+  if (chain_first[0] != 0u || chain_first[n_chains] != n_blocks) return "chain_first must start at 0 and end at n_blocks";
+  for (uint32_t c = 0; c < n_chains; c++)
+    if (chain_first[c] > chain_first[c + 1]) return "chain_first must be ascending";
+  for (uint32_t c = 0; c < n_chains; c++) {
+    if (win_off[c] + win_len[c] < win_off[c]) return "a stream's window wraps around the address space";
+    const uint64_t wend = win_off[c] + win_len[c];
+    for (uint32_t i = chain_first[c]; i < chain_first[c + 1]; i++) {
+      const uint64_t n = src_len[i] > 0 ? (uint64_t)src_len[i] : 0u;
+      if (src_off[i] < win_off[c] || src_off[i] > wend || n > wend - src_off[i]) return "a block's source lies outside its stream's window";
+    }
+    DsPiece p;
+    if (const char* why = cxstream_piece(hist_end[c], hist_len[c], win_off[c], win_len[c], &p)) return why;
+  }
+  return nullptr;
+}
+struct CxHull { uint64_t lo = 0, hi = 0; };
+// the used part of stream c's window: the call has passed cxstream_shape_error.  A block that cannot run -- a negative length --
+// counts with its offset alone; a stream without blocks and without a piece in reach of its window has an empty hull at win_off
+inline CxHull cxstream_hull(const uint32_t* chain_first, uint32_t c, const uint64_t* src_off, const int32_t* src_len, uint64_t hist_end, const DsPiece& p,
+                            uint64_t win_off) {
+  CxHull h;
+  bool any = false;
+  auto take = [&](uint64_t a, uint64_t b) { if (!any) { h.lo = a; h.hi = b; any = true; } else { if (a < h.lo) h.lo = a; if (b > h.hi) h.hi = b; } };
+  for (uint32_t i = chain_first[c]; i < chain_first[c + 1]; i++) take(src_off[i], src_off[i] + (src_len[i] > 0 ? (uint64_t)src_len[i] : 0u));
+  if (p.kind == DS_INSIDE || p.kind == DS_LEAD) take(hist_end - p.keep, hist_end);
+  if (!any) h.lo = h.hi = win_off;
+  return h;
+}
+// the bytes stream c takes in the device image when it stands alone (cut_chunk's cost: shared pieces are counted once per stream)
+inline size_t cxstream_cost(const CxHull& h, const DsPiece& p) { return al16((size_t)(h.hi - h.lo)) + (p.kind == DS_APART ? al16((size_t)p.keep) : 0u); }
+// One chunk's image: nc streams from the chunk's first on.  hist_dev[t]: where stream t's history ends on the device (0 with no piece:
+// the walk looks at no byte of a history of length 0)
+struct CxImage {
+  std::vector<CxHull> hull;
+  std::vector<size_t> base;
+  std::vector<DsPiece> piece;
+  std::vector<DsApart> apart;
+  std::vector<uint64_t> hist_dev;
+  size_t total = 0;
+  size_t apart_at(uint64_t end, uint64_t keep) {   // (chunks hold few distinct outside pieces -- a shared dictionary is one)
+    for (const DsApart& a : apart) if (a.end == end && a.keep == keep) return a.dev;
+    apart.push_back(DsApart{end, keep, total});
+    total += al16((size_t)keep);
+    return apart.back().dev;
+  }
+  CxImage(const uint32_t* chain_first, uint32_t c0, uint32_t nc, const uint64_t* src_off, const int32_t* src_len, const uint64_t* hist_end,
+          const int32_t* hist_len, const uint64_t* win_off, const uint64_t* win_len)
+      : hull(nc), base(nc), piece(nc), hist_dev(nc) {
+    for (uint32_t t = 0; t < nc; t++) {
+      (void)cxstream_piece(hist_end[c0 + t], hist_len[c0 + t], win_off[c0 + t], win_len[c0 + t], &piece[t]);
+      hull[t] = cxstream_hull(chain_first, c0 + t, src_off, src_len, hist_end[c0 + t], piece[t], win_off[c0 + t]);
+      base[t] = total;
+      total += al16((size_t)(hull[t].hi - hull[t].lo));
+    }
+    for (uint32_t t = 0; t < nc; t++) {
+      hist_dev[t] = 0;
+      if (piece[t].kind == DS_INSIDE || piece[t].kind == DS_LEAD) hist_dev[t] = to_dev(t, hist_end[c0 + t]);
+      if (piece[t].kind == DS_APART) hist_dev[t] = apart_at(hist_end[c0 + t], piece[t].keep) + piece[t].keep;
+    }
+  }
+  uint64_t to_dev(uint32_t t, uint64_t x) const { return base[t] + (x - hull[t].lo); }
 };
 
 // runs in any order, overlapping ones included -> ascending, disjoint, those at most RUN_GAP bytes apart joined

@@ -171,6 +171,16 @@ struct CStreamArgs {
 // compress_fast_stream_cu_kernel: compress_fast_chain_cu_kernel's shape; a wavefront that draws a chain loads the stream's table into
 // its LDS (or builds the fresh one), walks the call's blocks and stores table and record back
 int launch_compress_fast_stream(const CStreamArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
+// The same streams when their sources land anywhere -- rings, alternating buffers, a dictionary elsewhere (lz4_fast_chain.h
+// cxstream_walk: liblz4's prefix and external-dictionary modes, chosen block by block).  s: as above, with s.c.chain_src_off unused
+// (nullptr) and s.c.chain_prefix_len[c] = the bytes of the stream's history that are present; src_off[i]: block i's own source offset;
+// chain_hist_end[c]: where stream c's history ends in s.c.src at its first block of the launch.  Same record, same image: launches of
+// the two kernels alternate on a slot.  The walk trusts the offsets: the host path checks them against the stream's window.
+struct CXStreamArgs {
+  CStreamArgs s; const uint64_t* src_off; const uint64_t* chain_hist_end;
+};
+// compress_fast_xstream_cu_kernel: compress_fast_stream_cu_kernel's shape
+int launch_compress_fast_xstream(const CXStreamArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
 // LZ4_compress_HC_continue over chains of linked blocks, prefix mode (compress_hc.hip): CChainArgs as above with chain_consumed unused
 // (nullptr); the history is what LZ4_loadDictHC keeps (its last 64 KB, no minimum).  out[i] = liblz4's return value; a block that
 // returns 0 (it does not fit, or src_len[i] / dst_cap[i] is negative) does NOT stop its chain: its source is history for the blocks

@@ -1,7 +1,8 @@
 // lz4_fast_chain.h -- the walk over one chain of linked blocks on the compressing side (LZ4_compress_fast_continue, liblz4 1.9.3,
 // acceleration 1), shared by compress_fast.hip (compress_fast_chain_cu_kernel) and the CPU lane simulator
 // (tests/hostsim/hostsim_cchain.cpp); behind it, the same walk for streams whose state stays on the device between launches
-// (cstream_walk: compress_fast_stream_cu_kernel, tests/hostsim/hostsim_cstream.cpp).
+// (cstream_walk: compress_fast_stream_cu_kernel, tests/hostsim/hostsim_cstream.cpp), and for such streams when their sources land
+// anywhere (cxstream_walk: compress_fast_xstream_cu_kernel, tests/hostsim/hostsim_cxstream.cpp).
 //
 // A chain is a run of blocks whose SOURCES lie back to back; block k may match into the blocks before it and into the history that
 // lies directly in front of the chain.  liblz4 defines block k's result as
@@ -53,7 +54,8 @@ LZ4HIP_DEV void link_table_init(W& w, const uint8_t* buf, uint32_t keep, bool pr
   }
 }
 
-// (cstream_walk below holds a copy of this block loop: a change here is to be made there as well)
+// (cstream_walk below holds a copy of this block loop, and cxstream_walk behind it a copy of its prefix-mode branch: a change here is
+// to be made there as well)
 template <class W, class Io>
 LZ4HIP_DEV void cchain_walk(W& w, Io& io, const CChainArgs& a, uint32_t c) {
   using Core = FastCore<W, false, DirectOut<W>, false, false, false, true>;
@@ -99,7 +101,8 @@ LZ4HIP_DEV void cchain_walk(W& w, Io& io, const CChainArgs& a, uint32_t c) {
 // -- its table, its index position, the history it holds -- is loaded from the slot before the walk and stored back behind it
 // (kernels.h CStreamArgs: the record's words).  (A walk of its own beside cchain_walk, not a switch in it: cchain_walk's kernel keeps
 // the instructions it has -- even the per-block body alone, as one inline helper for both walks, changed them: 3202 -> 3189, DESIGN.md
-// 2.1.  A change to the block loop there is to be made here as well.)
+// 2.1.  A change to the block loop there is to be made here as well, and one to the prologue and epilogue here -- the record, the image,
+// the stop -- in cxstream_walk, which holds a copy of them.)
 //   * a fresh stream (a record of zeros) is cchain_walk's chain, rule for rule; with a prefix of 8 bytes and more its table is built
 //     before the first block, not at the first block that probes: the loaded bytes need not be in front of a later call's source;
 //   * a stream that has run continues in liblz4's prefix mode: the source follows kept = min(chain_prefix_len, 65536, held) bytes of its
@@ -194,6 +197,142 @@ LZ4HIP_DEV void cstream_walk(W& w, Io& io, const CStreamArgs& s, uint32_t c) {
   }
   io.put_rec(rec, ibase + pos, pos > 65536u ? 65536u : pos, flags | (table_ready ? kStreamTable : 0u) | (stopped ? kStreamStopped : 0u), span,
              total + (uint64_t)(pos - kept));
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The walk for a resident stream whose sources land ANYWHERE (compress_fast_xstream_cu_kernel, tests/hostsim/hostsim_cxstream.cpp): every
+// block has its own source offset, and the stream's history D = [D_end - D_len, D_end) lies wherever the blocks before left it -- a
+// ring that wraps, two alternating buffers, a save area.  Same record, same 32 KB image, same rules as cstream_walk (the two walks
+// alternate on one slot); what is new is liblz4's per-block state machine (LZ4_compress_fast_continue, 1.9.3), applied to offsets into
+// a.s.c.src.  At the stream's first block of the launch D_end = chain_hist_end[c] and D_len = min(chain_hist_len[c], 65536, what the
+// record holds); a fresh stream loads those bytes as LZ4_loadDict does (8-byte minimum, indexes from 65536).  Then, for a block [s, s + n):
+//   1. D_len < 4 and D_end != s: the history is dropped;
+//   2. s + n inside (D_end - D_len, D_end): the source overlaps its history, of which [s + n, D_end) stays -- at most 64 KB, nothing
+//      under 4 bytes;
+//   3. D_end == s: prefix mode, cstream_walk's LINK block on the buffer that begins at D's first byte; D grows by the block;
+//   4. otherwise external-dictionary mode: the LINK + DICT core (lz4_fast_core.h) -- indexes [idx - D_len, idx) name D's bytes, the block
+//      starts at idx; afterwards D is the block alone (a 0-byte block: nothing);
+//   5. idx += n.
+// In both modes idx - D_len is the lower bound of a candidate, whatever the table holds: where liblz4 does not check it (D_len >= 64 KB,
+// or D_len == idx) the distance rule or index 0 imply it.  D_len is capped at 64 KB from call to call and in front of an external block:
+// nothing further back can be reached, and liblz4's own cap in rule 2 makes the trimmed size the same.  A block in external mode whose
+// bytes overlap D's (rule 2 does not catch a source that runs over D's END) reads D as it is now, as liblz4 does: FastCore's alias_hi.
+// ONE EXCEPTION, not reproduced: such a source that begins EXACTLY at D's first byte (one reused buffer, a longer block than the one
+// before).  liblz4 tells a match in the external dictionary by `lowLimit == dictionary`, which then holds for matches inside the block
+// too, so it cuts their forward count at D's would-be end; the engine's matches are the longer, ordinary ones.  Both outputs are
+// valid LZ4 of an input that is misuse either way (D was overwritten: liblz4's own output does not decode there).
+// A stream without a table (blocks under 13 bytes only) builds it at its first block that probes: empty buckets are index 0, a real
+// candidate only while idx - D_len == 0, when the stream's first four bytes are D's (or, with no history at all, the block's).
+// Io, beyond cstream_walk's: begin_xblock(hist, hist_len, blk, n, d, cap): the block about to run may read both pieces.
+template <class W, class Io>
+LZ4HIP_DEV void cxstream_walk(W& w, Io& io, const CXStreamArgs& x, uint32_t c) {
+  using Link = FastCore<W, false, DirectOut<W>, false, false, false, true>;
+  using Ext = FastCore<W, false, DirectOut<W>, false, false, true, true>;
+  const CStreamArgs& s = x.s;
+  const CChainArgs& a = s.c;
+  uint32_t b1 = io.uni(a.chain_first[c + 1]), b0 = io.uni(a.chain_first[c]);
+  if (b1 > a.n_blocks) b1 = a.n_blocks;
+  if (b0 > b1) b0 = b1;
+  const uint32_t sv = io.uni(s.slot[c]), slot = sv & ~kStreamForceStop;
+  uint32_t* const rec = io.uni_ptr(s.rec + (size_t)slot * kStreamRecWords);
+  uint8_t* const image = (uint8_t*)io.uni_ptr(s.tables + (size_t)slot * (1u << Link::HLOG));
+  uint32_t idx = io.uni(rec[0]), held = io.uni(rec[1]), flags = io.uni(rec[2]), span = io.uni(rec[3]);
+  uint64_t total = ((uint64_t)io.uni(rec[5]) << 32) | io.uni(rec[4]);
+  uint32_t i = b0;
+  if ((sv & kStreamForceStop) || (flags & kStreamStopped)) {
+    for (; i < b1; i++) io.put_out(i, kChainStopped);
+    io.put_chain(c, 0u);
+    io.put_rec(rec, idx, held, flags | kStreamStopped, span, total);
+    return;
+  }
+  uint64_t De = io.uni64(x.chain_hist_end[c]);
+  uint64_t P = 0;
+  { const int32_t p = (int32_t)io.uni((uint32_t)a.chain_prefix_len[c]); P = p > 0 ? (uint64_t)p : 0u; }
+  if (P > De) P = De;
+  const bool fresh = !(flags & kStreamUsed);
+  uint32_t Dl;
+  if (fresh) {
+    Dl = P < 8u ? 0u : (P > 65536u ? 65536u : (uint32_t)P);
+    idx = P ? 65536u : 0u;
+    span = Dl; total = 0u;
+    flags = kStreamUsed | (P ? kStreamPrefixed : 0u);
+  } else {
+    Dl = P > held ? held : (uint32_t)P;   // (held <= 65536)
+  }
+  bool table_ready = (flags & kStreamTable) != 0u, dirty = false;
+  if (table_ready) {
+    io.begin_state(image);
+    io.table_load(w, image);
+    io.end_state();
+  } else if (fresh && Dl) {
+    const uint8_t* const hist = io.uni_ptr(a.src + De - Dl);
+    io.begin_block(hist, Dl, nullptr, 0u);
+    link_table_init(w, hist, Dl, true);
+    table_ready = dirty = true;
+  }
+  bool stopped = false;
+  uint64_t consumed = 0;
+  while (i < b1) {
+    const int32_t sl = (int32_t)io.uni((uint32_t)a.src_len[i]), dc = (int32_t)io.uni((uint32_t)a.dst_cap[i]);
+    uint32_t r = 0;
+    if (sl >= 0 && dc >= 0 && (uint64_t)span + (uint32_t)sl <= kChainSpanMax) {
+      const uint32_t n = (uint32_t)sl;
+      const uint64_t so = io.uni64(x.src_off[i]);
+      if (Dl < 4u && De != so) Dl = 0u;                          // rule 1
+      if (so + n > De - Dl && so + n < De) {                     // rule 2
+        const uint64_t t = De - (so + n);
+        Dl = t > 65536u ? 65536u : (uint32_t)t;
+        if (Dl < 4u) Dl = 0u;
+      }
+      uint8_t* d = io.uni_ptr(a.dst + io.uni64(a.dst_off[i]));
+      const bool probes = sl >= 13;
+      if (De == so) {                                            // rule 3: the block follows its history
+        const uint8_t* const buf = io.uni_ptr(a.src + so - Dl);
+        const uint32_t end = Dl + n, ibase = idx - Dl;
+        io.begin_block(buf, end, d, (uint32_t)dc);
+        if (probes) {
+          if (!table_ready) { link_table_init(w, buf, 0u, (flags & kStreamPrefixed) != 0u || ibase != 0u); table_ready = true; }
+          dirty = true;
+        }
+        DirectOut<W> out(w, buf, end, d, (uint32_t)dc);
+        out.limited = (uint32_t)dc < n + n / 255u + 16u;   // (by the block's length, not by its end in buf)
+        Link core(w, out, buf, end);
+        core.blk = Dl; core.ibase = ibase; core.lowidx = ibase;
+        r = core.run();
+        if (r) { Dl += n; De = so + n; }
+      } else {                                                   // rule 4: the history lies elsewhere
+        if (Dl > 65536u) Dl = 65536u;
+        const uint8_t* const blk = io.uni_ptr(a.src + so);
+        const uint8_t* const hist = io.uni_ptr(a.src + De - Dl);
+        const uint32_t low = idx - Dl;
+        io.begin_xblock(hist, Dl, blk, n, d, (uint32_t)dc);
+        if (probes) {
+          if (!table_ready) { link_table_init(w, Dl ? hist : blk, 0u, (flags & kStreamPrefixed) != 0u || low != 0u); table_ready = true; }
+          dirty = true;
+        }
+        DirectOut<W> out(w, blk, n, d, (uint32_t)dc);
+        Ext core(w, out, blk, n);
+        core.dict = hist; core.keep = Dl; core.ibase = idx; core.lowidx = low;
+        core.alias_hi = (Dl != 0u && so < De && so + n > De - Dl) ? idx : 0u;
+        r = core.run();
+        if (r) { Dl = n; De = so + n; }
+      }
+    }
+    io.put_out(i, (int32_t)r);
+    i++;
+    if (r == 0u) { stopped = true; break; }
+    idx += (uint32_t)sl; span += (uint32_t)sl; consumed += (uint32_t)sl;
+  }
+  for (; i < b1; i++) io.put_out(i, kChainStopped);
+  io.put_chain(c, consumed);
+  // a stopped stream's table is never read again
+  if (table_ready && dirty && !stopped) {
+    w.sync();
+    io.begin_state(image);
+    io.table_store(w, image);
+    io.end_state();
+  }
+  io.put_rec(rec, idx, Dl > 65536u ? 65536u : Dl, flags | (table_ready ? kStreamTable : 0u) | (stopped ? kStreamStopped : 0u), span, total + consumed);
 }
 
 }  // namespace lz4hip

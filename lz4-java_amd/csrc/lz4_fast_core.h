@@ -310,13 +310,22 @@ template <> struct DictState<true> {
 // and within 65535 bytes; it is read from the same buffer, so a match may start in front of the block and run into it, and the
 // catch-up may go back to position 0.  Position blk is inserted and never probed; mflimit and matchlimit come from n, and nothing at or
 // past n is read.  LINK = false compiles to what it did before the switch existed (the state lives in a base of its own, as DictState).
-template <bool LINK> struct LinkState { static constexpr uint32_t blk = 0, ibase = 0, lowidx = 0; };
-template <> struct LinkState<true> { uint32_t blk = 0, ibase = 0, lowidx = 0; };
+template <bool LINK> struct LinkState { static constexpr uint32_t blk = 0, ibase = 0, lowidx = 0, alias_hi = 0; };
+template <> struct LinkState<true> { uint32_t blk = 0, ibase = 0, lowidx = 0, alias_hi = 0; };
+// LINK and DICT together: one block of a RUNNING stream in liblz4's external-dictionary mode (LZ4_compress_fast_continue on a source that
+// does not follow its history; lz4_fast_chain.h cxstream_walk).  It is the DICT core with the stream's own numbers in the place of
+// LZ4_loadDict's: `src` is the block, block position p is index ibase + p (ibase: the stream's index position, a run-time value where
+// DICT alone has kDictBase), the history [dict, dict + keep) lies elsewhere and holds the indexes [lowidx, ibase), keep = ibase - lowidx
+// (0: no history, and `dict` is not looked at), and the table is the caller's running one -- nothing is loaded or cleared here, `image`
+// is unused.  blk stays 0.  alias_hi (0: off): the caller's mark that the block's bytes overlap the history's (a source written over
+// the ring it came from): the fingerprint of an entry below alias_hi was taken from bytes that may be gone, so such an entry is a
+// tentative hit whatever its fingerprint says, and its candidate bytes, as they are now, decide -- as liblz4's compare of them does.
 template <class W, bool U16, class Out = DirectOut<W>, bool PK = false, bool ACC = false, bool DICT = false, bool LINK = false>
 struct FastCore : DictState<DICT>, LinkState<LINK> {
   static_assert(!(U16 && PK), "compact entries are a byU32 layout");
   static_assert(!DICT || (!U16 && !PK && !ACC), "the dictionary core is byU32 with 64-bit entries, acceleration 1");
-  static_assert(!LINK || (!U16 && !PK && !ACC && !DICT), "the linked-block core is byU32 with 64-bit entries, acceleration 1");
+  static_assert(!LINK || (!U16 && !PK && !ACC), "the linked-block core is byU32 with 64-bit entries, acceleration 1");
+  static constexpr bool XLINK = LINK && DICT;     // a running stream's block against a history that lies elsewhere
   static constexpr uint32_t kDictBase = 65536u;   // DICT: index of block position 0 (the stream's offset after LZ4_loadDict)
   static constexpr bool S32 = U16 || PK;           // entries are 32 bits
   static constexpr uint32_t kPackMaxN = 1u << 22;  // PK: positions have 22 bits
@@ -350,7 +359,9 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
   uint32_t p_S = 0, p_ip = 0;
   using DictState<DICT>::dict; using DictState<DICT>::keep; using DictState<DICT>::image;
   using DictState<DICT>::cs; using DictState<DICT>::cn; using DictState<DICT>::cdict;
-  using LinkState<LINK>::blk; using LinkState<LINK>::ibase; using LinkState<LINK>::lowidx;
+  using LinkState<LINK>::blk; using LinkState<LINK>::ibase; using LinkState<LINK>::lowidx; using LinkState<LINK>::alias_hi;
+  // DICT: the index of block position 0
+  LZ4HIP_DEV uint32_t dbase() const { if constexpr (XLINK) return ibase; else return kDictBase; }
 
   LZ4HIP_DEV FastCore(W& w_, Out& out_, const uint8_t* s, uint32_t n_, FastStats* st_ = nullptr)
       : w(w_), out(out_), src(s), n(n_), st(st_) {
@@ -395,6 +406,17 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
   // them.)  Without a hit the speculative loads read the block's start.
   LZ4HIP_DEV uint32_t locate(bool have_hit, uint32_t idx, uint32_t hpos, uint32_t& lim) {
     lim = matchlimit;
+    if constexpr (XLINK) {   // the same with the stream's own index base
+      cdict = have_hit && idx < ibase;
+      if (cdict) {
+        cs = dict; cn = keep;
+        const uint32_t dl = ibase - idx;
+        if (hpos + dl < lim) lim = hpos + dl;
+        return idx - lowidx;
+      }
+      cs = src; cn = n;
+      return have_hit ? idx - ibase : 0u;
+    }
     cdict = have_hit && idx < kDictBase;
     if (cdict) {
       cs = dict; cn = keep;
@@ -404,6 +426,16 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
     }
     cs = src; cn = n;
     return have_hit ? idx - kDictBase : 0u;
+  }
+
+  // XLINK: the speculative candidate fetch.  A running stream's history may be 4 .. 7 bytes long (LZ4_loadDict's 8-byte minimum is not
+  // LZ4_saveDict's, and a stream may jump behind its first few bytes); its one possible candidate is its first byte -- index 0, the
+  // empty buckets' entry while the lower bound is 0: every inserted position has 8 bytes and more behind it -- of which liblz4 reads four.
+  // So do we: one 32-bit load inside the history in every lane (no lane is `full` there: the forward count stops at the history's end,
+  // which count_tail reaches byte by byte).  From 8 bytes on, DICT's clamped 8-byte loads.
+  LZ4HIP_DEV VU64 cand_load(VU o8s, uint32_t mpos) {
+    if (LZ4HIP_UNLIKELY(cn < 8u)) return W::u64(w.ldu32(cs, VU(mpos + 4u <= cn ? mpos : cn - 4u)));
+    return w.ldu64_cand(cs, W::vmin(o8s + mpos, cn - 8u));
   }
 
   // probe k of a miss-run starting at S sits at S + g(k): liblz4's `step = searchMatchNb++ >> 6`
@@ -492,7 +524,7 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
 
   // ---- the compressor ------------------------------------------------------------------------
   LZ4HIP_DEV uint32_t run() {
-    if constexpr (LINK) {
+    if constexpr (LINK && !DICT) {
       anchor = blk;
       if (n - blk < 13u) return out.last(blk);  // all literals; nothing is inserted (an empty block: the single token 0x00)
       // liblz4's first insert, the block's first position (8 bytes are there: the block has 13)
@@ -506,18 +538,21 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
     if constexpr (DICT) {
       // the table as LZ4_loadDict leaves it (no image: no dictionary, every entry empty = index 0, which the lower-bound check
       // rejects), then liblz4's first insert, position 0
-      if (image) {
-        for (uint32_t i = 0; i < (1u << HLOG); i += 64u) {
-          const VU h = w.lane() + i;
-          w.template lds_wr<S32>(h, w.ldu64(image, h * 8u), VB(true));
+      // (XLINK: the table is the stream's running one, as the block before left it)
+      if constexpr (!XLINK) {
+        if (image) {
+          for (uint32_t i = 0; i < (1u << HLOG); i += 64u) {
+            const VU h = w.lane() + i;
+            w.template lds_wr<S32>(h, w.ldu64(image, h * 8u), VB(true));
+          }
+        } else {
+          w.template lds_fill<S32>(1u << HLOG, (E)0);
         }
-      } else {
-        w.template lds_fill<S32>(1u << HLOG, (E)0);
+        w.sync();
       }
-      w.sync();
       const VU64 x0 = w.ldu64(src, VU(0u));
       const VU h0 = W::lo32(((x0 << 24) * 889523592379ull) >> (64 - HLOG));
-      (void)w.template lds_max<S32>(h0, mk_entry(VU(kDictBase), fp32(W::lo32(x0))), w.lane() == 0u);
+      (void)w.template lds_max<S32>(h0, mk_entry(VU(dbase()), fp32(W::lo32(x0))), w.lane() == 0u);
       w.sync();
       return loop<0>(false, 1u, 0u, 0u);
     }
@@ -582,7 +617,8 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
       const VE newe = mk_entry(LINK ? pos + ibase : (DICT ? pos + kDictBase : pos), fp);
       // (ballots of plain compares are free -- the compare already writes the lane mask; the masks are combined on the scalar side)
       uint64_t tmask = w.ballot(e_fp(e) == fp) & probem;
-      if constexpr (DICT) tmask &= w.ballot(e_pos(e) + MAXD >= pos + kDictBase) & w.ballot(e_pos(e) >= kDictBase - keep);
+      if constexpr (XLINK) tmask = (tmask | (w.ballot(e_pos(e) < alias_hi) & probem)) & w.ballot(e_pos(e) + MAXD >= pos + ibase) & w.ballot(e_pos(e) >= lowidx);
+      else if constexpr (DICT) tmask &= w.ballot(e_pos(e) + MAXD >= pos + kDictBase) & w.ballot(e_pos(e) >= kDictBase - keep);
       else if constexpr (LINK) tmask &= w.ballot(e_pos(e) + MAXD >= pos + ibase) & w.ballot(e_pos(e) >= lowidx);
       else if constexpr (!U16) tmask &= w.ballot(e_pos(e) + MAXD >= pos);
       const uint64_t imask = ~validm;
@@ -601,14 +637,16 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
       uint32_t mpos = se_pos(w.template bcast_e<S32>(e, (int)kk));
       [[maybe_unused]] uint32_t midx = 0u, lim = 0u;   // DICT: the candidate's index (mpos becomes its offset in cs); where the forward count stops
       if constexpr (DICT) { midx = mpos; mpos = locate(have_hit, midx, hpos, lim); }
-      if constexpr (LINK) mpos -= ibase;   // (without a hit: any value, the loads below are clamped)
+      if constexpr (LINK && !DICT) mpos -= ibase;   // (without a hit: any value, the loads below are clamped)
       bool hit_post = post && k0 == 1u;
       uint32_t maxback = (!have_hit || hit_post) ? 0u : ((hpos - anchor) < mpos ? (hpos - anchor) : mpos);
       // (only the first kSpecLanes lanes take part -- 8 bytes each: the candidate side is a random re-read of the block and
       // every further 128 bytes are one more cache line that mostly misses L2; longer matches take count_fwd's extra round trip)
       // (lanes past kSpecLanes repeat the last taking lane's address: same cache line, no exec-mask region around the loads)
       VU64 fa = w.ldu64(src, W::vmin(o8s + hpos, n - 8u));   // kept apart from fb: xor-ing here would wait for the loads
-      VU64 fb = w.ldu64_cand(cbase(), W::vmin(o8s + mpos, climit() - 8u));
+      VU64 fb;
+      if constexpr (XLINK) fb = cand_load(o8s, mpos);
+      else fb = w.ldu64_cand(cbase(), W::vmin(o8s + mpos, climit() - 8u));
       VU ba, bb;
       uint64_t bactm = maxback >= 64u ? ~0ull : ((1ull << maxback) - 1ull);
       {
@@ -651,7 +689,8 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
           pendm &= ~gm;
         }
         uint64_t t2 = w.ballot(e_fp(se) == fp) & inm & probem;
-        if constexpr (DICT) t2 &= w.ballot(e_pos(se) + MAXD >= pos + kDictBase) & w.ballot(e_pos(se) >= kDictBase - keep);
+        if constexpr (XLINK) t2 = (t2 | (w.ballot(e_pos(se) < alias_hi) & inm & probem)) & w.ballot(e_pos(se) + MAXD >= pos + ibase) & w.ballot(e_pos(se) >= lowidx);
+        else if constexpr (DICT) t2 &= w.ballot(e_pos(se) + MAXD >= pos + kDictBase) & w.ballot(e_pos(se) >= kDictBase - keep);
         else if constexpr (LINK) t2 &= w.ballot(e_pos(se) + MAXD >= pos + ibase) & w.ballot(e_pos(se) >= lowidx);
         else if constexpr (!U16) t2 &= w.ballot(e_pos(se) + MAXD >= pos);
         const bool had = have_hit;
@@ -670,12 +709,13 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
           hpos = w.bcast(pos, (int)k0);
           mpos = se_pos(w.template bcast_e<S32>(se, (int)k0));
           if constexpr (DICT) { midx = mpos; mpos = locate(true, midx, hpos, lim); }
-          if constexpr (LINK) mpos -= ibase;
+          if constexpr (LINK && !DICT) mpos -= ibase;
           if (!had || hpos != hpos_old || (DICT ? midx != midx_old : mpos != mpos_old)) {  // the speculation fetched the wrong candidate
             hit_post = post && k0 == 1u;
             maxback = hit_post ? 0u : ((hpos - anchor) < mpos ? (hpos - anchor) : mpos);
             fa = w.ldu64(src, W::vmin(o8s + hpos, n - 8u));
-            fb = w.ldu64_cand(cbase(), W::vmin(o8s + mpos, climit() - 8u));
+            if constexpr (XLINK) fb = cand_load(o8s, mpos);
+            else fb = w.ldu64_cand(cbase(), W::vmin(o8s + mpos, climit() - 8u));
             bactm = maxback >= 64u ? ~0ull : ((1ull << maxback) - 1ull);
             const VB bact = w.lanes(bactm);
             ba = w.ldu8(src, W::select(bact, (hpos - 1u) - j, VU(0u)));
@@ -754,7 +794,7 @@ struct FastCore : DictState<DICT>, LinkState<LINK> {
         // (ACC: lane l >= 4 sits further on -- the literals come from the source)
         const bool regs = !ACC && Out::kUsesWindowRegs && was_post && mc < 270u &&
                           (1u + (lit >= 15u ? 1u : 0u) + lit + 2u + (mc >= 15u ? 1u : 0u) <= 63u);
-        if constexpr (DICT) out.seq(lit, mc, (hpos + kDictBase) - midx, anchor, !hit_post, regs, b0);
+        if constexpr (DICT) out.seq(lit, mc, (hpos + dbase()) - midx, anchor, !hit_post, regs, b0);
         else out.seq(lit, mc, hpos - mpos, anchor, !hit_post, regs, b0);
       }
       anchor = ip_new;

@@ -507,6 +507,36 @@ class CompressStreams {
                                                           nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
     return r;
   }
+  // The same streams when their sources land anywhere -- a ring that wraps, alternating buffers, a dictionary elsewhere
+  // (lz4hip_compress_fast_stream_ext_batch): every block has its own srcOff[i] inside its stream's window [chainWinOff[c],
+  // + chainWinLen[c]); the stream's history ends at chainHistEnd[c] in src, with chainHistLen[c] bytes of it present.  A block that
+  // does not follow its history runs in liblz4's external-dictionary mode.  A call is a snapshot of src.
+  LZ4HIPBatch::Chains compressAt(const std::vector<uint32_t>& streamId, const bytes& src, const std::vector<uint64_t>& srcOff,
+                                 const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst,
+                                 const std::vector<uint64_t>& chainHistEnd, const std::vector<int32_t>& chainHistLen,
+                                 const std::vector<uint64_t>& chainWinOff, const std::vector<uint64_t>& chainWinLen, bytes& dest,
+                                 const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen) {
+    const size_t n = srcLen.size(), nc = streamId.size();
+    if (srcOff.size() != n || destOff.size() != n || maxDestLen.size() != n) throw std::invalid_argument("per-block arrays differ in length");
+    if (chainHistEnd.size() != nc || chainHistLen.size() != nc || chainWinOff.size() != nc || chainWinLen.size() != nc || chainFirst.size() != nc + 1)
+      throw std::invalid_argument("per-chain arrays differ in length");
+    for (size_t c = 0; c < nc; c++)
+      if (streamId[c] >= size() || (c && streamId[c] <= streamId[c - 1]))
+        throw std::invalid_argument("streamId must be strictly ascending and below the number of streams");
+    LZ4HIPBatch::Chains r;
+    r.lengths.assign(n, 0);
+    r.chainLengths.assign(nc, 0);
+    bytes one(1);                                 // (an empty buffer still hands the library a pointer)
+    int32_t none = 0;
+    uint32_t none32 = 0;
+    uint64_t none64 = 0;
+    LZ4HIPBatch::status(lz4hip_compress_fast_stream_ext_batch(
+        h_, nc ? streamId.data() : &none32, src.empty() ? one.data() : src.data(), n ? srcOff.data() : &none64, n ? srcLen.data() : &none, chainFirst.data(),
+        nc ? chainHistEnd.data() : &none64, nc ? chainHistLen.data() : &none, nc ? chainWinOff.data() : &none64, nc ? chainWinLen.data() : &none64,
+        dest.empty() ? one.data() : dest.data(), n ? destOff.data() : &none64, n ? maxDestLen.data() : &none, n ? r.lengths.data() : &none,
+        nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
+    return r;
+  }
   void reset() { LZ4HIPBatch::status(lz4hip_cstreams_reset(h_, nullptr, 0)); }
   void reset(const std::vector<uint32_t>& streamId) {
     if (!streamId.empty()) LZ4HIPBatch::status(lz4hip_cstreams_reset(h_, streamId.data(), (uint32_t)streamId.size()));

@@ -215,6 +215,39 @@ public final class LZ4HIPBatch {
       compressFastStream(this, streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed);
     }
 
+    /**
+     * The same streams when their sources land anywhere -- a ring that wraps, alternating buffers, a dictionary elsewhere
+     * ({@code lz4hip_compress_fast_stream_ext_batch}): every block has its own {@code srcOff[i]} inside its stream's window
+     * {@code src[chainWinOff[c], + chainWinLen[c])}; the stream's history ends at {@code chainHistEnd[c]} with {@code chainHistLen[c]}
+     * bytes of it present.  A block that does not follow its history runs in liblz4's external-dictionary mode.  A call is a snapshot
+     * of {@code src}.  Every array is required.
+     */
+    public void compressAt(int[] streamId, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, long[] chainHistEnd, int[] chainHistLen,
+        long[] chainWinOff, long[] chainWinLen, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed) {
+      final int n = srcLen.length, nc = streamId.length;
+      if (srcOff.length != n || destOff.length != n || destCap.length != n || outLen.length != n) {
+        throw new IllegalArgumentException("per-block arrays differ in length");
+      }
+      if (chainHistEnd.length != nc || chainHistLen.length != nc || chainWinOff.length != nc || chainWinLen.length != nc
+          || chainConsumed.length != nc || chainFirst.length != nc + 1) {
+        throw new IllegalArgumentException("per-chain arrays differ in length");
+      }
+      if (!src.isDirect() || !dest.isDirect()) {
+        throw new IllegalArgumentException("direct buffers only");
+      }
+      final int ns = size();
+      for (int c = 0; c < nc; c++) {
+        if (streamId[c] < 0 || streamId[c] >= ns || (c > 0 && streamId[c] <= streamId[c - 1])) {
+          throw new IllegalArgumentException("streamId must be strictly ascending and below the number of streams");
+        }
+      }
+      final int rc = LZ4HIPJNI.LZ4HIP_batchFastStreamAt(handle(), streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff,
+          chainWinLen, dest, destOff, destCap, outLen, chainConsumed, n, nc);
+      if (rc != 0) {
+        throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+      }
+    }
+
     /** makes the listed streams ({@code null}: all of them) fresh */
     public void reset(int[] streamId) {
       final int rc = LZ4HIPJNI.LZ4HIP_cstreamsReset(handle(), streamId, streamId == null ? 0 : streamId.length);

@@ -140,6 +140,12 @@ enum LZ4HIPJNI {
   static native int LZ4HIP_batchFastStream(long set, int[] streamId, ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen,
                                            int[] chainFirst, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed,
                                            int nBlocks, int nChains);
+  /* The same streams when their sources land anywhere, DIRECT buffers (lz4hip_compress_fast_stream_ext_batch): every block has its own
+   * srcOff[i] inside the window src[chainWinOff[c], + chainWinLen[c]) of its stream, whose history ends at chainHistEnd[c] with
+   * chainHistLen[c] bytes of it present.  Every array is required.  Returns 0 or a negative lz4hip_status. */
+  static native int LZ4HIP_batchFastStreamAt(long set, int[] streamId, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst,
+                                             long[] chainHistEnd, int[] chainHistLen, long[] chainWinOff, long[] chainWinLen, ByteBuffer dest,
+                                             long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed, int nBlocks, int nChains);
   /* LZ4_compress_HC_continue over chains of linked blocks (prefix mode) at HC level `level`, DIRECT buffers: the arrays of
    * LZ4HIP_batchFastChain without chainConsumed.  outLen = liblz4's return values; a 0 does not end a chain.  Returns 0 or a negative
    * lz4hip_status (a null required argument: LZ4HIP_E_ARG). */

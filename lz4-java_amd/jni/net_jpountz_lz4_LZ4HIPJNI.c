@@ -219,12 +219,12 @@ typedef struct {
   jint mode;    /* how it is released: JNI_ABORT for an input, 0 for an output (copied back) */
   void* p;      /* its elements while pinned */
 } batch_array_t;
-/* The arguments of a batch native made addressable: the two direct buffers and up to ten descriptor arrays. */
+/* The arguments of a batch native made addressable: the two direct buffers and up to twelve descriptor arrays. */
 typedef struct {
   const uint8_t* src;
   uint8_t* dst;
   int n_arrays;
-  batch_array_t a[10];
+  batch_array_t a[12];
 } batch_args_t;
 
 static void batch_release(JNIEnv* env, batch_args_t* b) {
@@ -509,6 +509,26 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStream(JN
   rc = lz4hip_compress_fast_stream_batch((lz4hip_cstreams*)(intptr_t)set, (const uint32_t*)b.a[7].p, b.src, b.a[0].p,
                                          i_prefix >= 0 ? (const int32_t*)b.a[i_prefix].p : NULL, b.a[1].p, (const uint32_t*)b.a[2].p, b.dst, b.a[3].p, b.a[4].p,
                                          b.a[5].p, b.a[6].p, (uint32_t)nBlocks, (uint32_t)nChains);
+  batch_release(env, &b);
+  return rc;
+}
+/* The same streams when their sources land anywhere, DIRECT buffers (lz4hip_compress_fast_stream_ext_batch): every block has its own
+ * srcOff[i] inside the window src[chainWinOff[c], + chainWinLen[c]) of its stream; the stream's history ends at chainHistEnd[c] with
+ * chainHistLen[c] bytes of it present.  Every array is required.  A 0 handle is LZ4HIP_E_ARG */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStreamAt(JNIEnv* env, jclass cls, jlong set, jintArray streamId, jobject src,
+    jlongArray srcOff, jintArray srcLen, jintArray chainFirst, jlongArray chainHistEnd, jintArray chainHistLen, jlongArray chainWinOff,
+    jlongArray chainWinLen, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains) {
+  (void)cls;
+  if (set == 0 || nBlocks < 0 || nChains < 0) return LZ4HIP_E_ARG;
+  batch_args_t b = {NULL, NULL, 12, {{streamId, INTS, JNI_ABORT}, {srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {chainFirst, INTS, JNI_ABORT},
+                                     {chainHistEnd, LONGS, JNI_ABORT}, {chainHistLen, INTS, JNI_ABORT}, {chainWinOff, LONGS, JNI_ABORT},
+                                     {chainWinLen, LONGS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT}, {destCap, INTS, JNI_ABORT}, {outLen, INTS, 0},
+                                     {chainConsumed, LONGS, 0}}};
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  rc = lz4hip_compress_fast_stream_ext_batch((lz4hip_cstreams*)(intptr_t)set, (const uint32_t*)b.a[0].p, b.src, b.a[1].p, b.a[2].p, (const uint32_t*)b.a[3].p,
+                                             b.a[4].p, b.a[5].p, b.a[6].p, b.a[7].p, b.dst, b.a[8].p, b.a[9].p, b.a[10].p, b.a[11].p, (uint32_t)nBlocks,
+                                             (uint32_t)nChains);
   batch_release(env, &b);
   return rc;
 }

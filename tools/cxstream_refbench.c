@@ -1,0 +1,75 @@
+/* tools/cxstream_refbench.c -- the CPU side of tools/cxstream_sweep.py: the reference library's LZ4_compress_fast_continue on two
+ * alternating buffers of 4096 bytes per stream (its double-buffer example), ONE LZ4_stream_t per stream, on T host threads.
+ *   cxstream_refbench <liblz4 .so> <pool file> <n streams> <threads>
+ * <pool file>: pool streams of 16 x 4096 bytes back to back; stream s compresses pool stream s % pool.  Prints
+ * "<seconds> <source bytes> <compressed bytes>" (the best of three passes).  The library is loaded at run time: nothing of it is linked in. */
+#include <dlfcn.h>
+#include <pthread.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <time.h>
+
+enum { BLOCK = 4096, BLOCKS = 16 };
+typedef void* (*create_t)(void);
+typedef int (*free_t)(void*);
+typedef void (*reset_t)(void*);
+typedef int (*cont_t)(void*, const char*, char*, int, int, int);
+static create_t f_create; static free_t f_free; static reset_t f_reset; static cont_t f_cont;
+static const uint8_t* g_pool; static long g_pool_streams, g_n; static int g_threads;
+typedef struct { int t; uint64_t out; } job_t;
+
+static void* work(void* arg) {
+  job_t* j = (job_t*)arg;
+  void* st = f_create();
+  static __thread char buf[2][BLOCK];
+  char dst[BLOCK + BLOCK / 255 + 32];
+  uint64_t out = 0;
+  for (long s = j->t; s < g_n; s += g_threads) {
+    const uint8_t* raw = g_pool + (size_t)(s % g_pool_streams) * BLOCK * BLOCKS;
+    f_reset(st);
+    for (int k = 0; k < BLOCKS; k++) {
+      memcpy(buf[k & 1], raw + (size_t)k * BLOCK, BLOCK);
+      out += (uint64_t)f_cont(st, buf[k & 1], dst, BLOCK, (int)sizeof dst, 1);
+    }
+  }
+  f_free(st);
+  j->out = out;
+  return NULL;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 5) { fprintf(stderr, "usage: cxstream_refbench <liblz4 .so> <pool file> <n streams> <threads>\n"); return 2; }
+  void* h = dlopen(argv[1], RTLD_NOW);
+  if (!h) { fprintf(stderr, "%s\n", dlerror()); return 2; }
+  f_create = (create_t)dlsym(h, "LZ4_createStream"); f_free = (free_t)dlsym(h, "LZ4_freeStream");
+  f_reset = (reset_t)dlsym(h, "LZ4_resetStream_fast"); f_cont = (cont_t)dlsym(h, "LZ4_compress_fast_continue");
+  if (!f_create || !f_free || !f_reset || !f_cont) { fprintf(stderr, "a symbol is missing\n"); return 2; }
+  FILE* f = fopen(argv[2], "rb");
+  if (!f) return 2;
+  fseek(f, 0, SEEK_END);
+  const long bytes = ftell(f);
+  fseek(f, 0, SEEK_SET);
+  uint8_t* pool = (uint8_t*)malloc((size_t)bytes);
+  if (!pool || fread(pool, 1, (size_t)bytes, f) != (size_t)bytes) return 2;
+  fclose(f);
+  g_pool = pool; g_pool_streams = bytes / (BLOCK * BLOCKS); g_n = atol(argv[3]); g_threads = atoi(argv[4]);
+  if (g_pool_streams < 1 || g_n < 1 || g_threads < 1 || g_threads > 256) return 2;
+  double best = 1e30;
+  uint64_t out = 0;
+  for (int pass = 0; pass < 3; pass++) {
+    pthread_t th[256]; job_t jobs[256];
+    struct timespec a, b;
+    clock_gettime(CLOCK_MONOTONIC, &a);
+    for (int t = 0; t < g_threads; t++) { jobs[t].t = t; jobs[t].out = 0; pthread_create(&th[t], NULL, work, &jobs[t]); }
+    out = 0;
+    for (int t = 0; t < g_threads; t++) { pthread_join(th[t], NULL); out += jobs[t].out; }
+    clock_gettime(CLOCK_MONOTONIC, &b);
+    const double s = (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec);
+    if (s < best) best = s;
+  }
+  printf("%.6f %llu %llu\n", best, (unsigned long long)g_n * BLOCK * BLOCKS, (unsigned long long)out);
+  free(pool);
+  return 0;
+}
