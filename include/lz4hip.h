@@ -386,13 +386,75 @@ int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_s
  *     the bytes produced, and shards over the initialised devices at chain boundaries.  A stream that is cut in several places is
  *     best passed as ONE chain (it is parallel anyway);
  *   - out of scope: device-pointer forms (the chain workspace is indexed by source offset and the layout needs scratch of its
- *     own; they are left to a change that can also extend the far-offset table of the device entry points); LZ4_saveDictHC;
- *     sources that are not contiguous; LZ4_attach_HC_dictionary; a destSize form; favorDecSpeed; byte equality with the FRAMES
- *     the lz4 command line writes (its frame layer moves its dictionary).                                                         */
+ *     own; they are left to a change that can also extend the far-offset table of the device entry points);
+ *     LZ4_attach_HC_dictionary; a destSize form; favorDecSpeed; byte equality with the FRAMES the lz4 command line writes (its
+ *     frame layer moves its dictionary).  (No longer out of scope: LZ4_saveDictHC and sources that are not contiguous are
+ *     lz4hip_compress_hc_stream_batch, below.)                                                                                    */
 int lz4hip_compress_hc_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
                                    const int32_t* src_len, const uint32_t* chain_first,
                                    uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                    int32_t* out_len, uint32_t n_blocks, uint32_t n_chains, int level);
+/* COMPRESS HC STREAMS WHOSE SOURCES LAND ANYWHERE -- a ring that wraps, two alternating buffers, a save area (LZ4_saveDictHC), a
+ * dictionary elsewhere -- and that are continued by any number of calls.  Stream c of a call is the blocks [chain_first[c],
+ * chain_first[c + 1]); every block has ITS OWN src_off[i].
+ * THE CONTRACT: for every stream, the results are byte for byte and return value for return value what ONE LZ4_streamHC_t of liblz4
+ * 1.9.3 gives over all calls -- s = LZ4_createStreamHC(); LZ4_resetStreamHC_fast(s, level); then
+ * LZ4_compress_HC_continue(s, src + src_off[i], dst_i, src_len[i], dst_cap[i]) per block -- however the blocks are cut into calls, with
+ * the exceptions stated below.
+ *   - THE STATE is plain host data, as lz4hip_dstream_state is: state[c] is read in front of stream c's first block of the call and
+ *     written back behind its last.  There is no handle and no device memory between calls.  All zero is a fresh stream.  The prefix is
+ *     [prefix_end - prefix_len, prefix_end), the external dictionary [ext_end - ext_len, ext_end), both as offsets into this call's src
+ *     (liblz4's end, dictLimit, lowLimit and dictBase + dictLimit); index counts the bytes loaded plus consumed and exists for the life
+ *     limit only.  These are functions of addresses and lengths alone, never of compressed results;
+ *   - the state machine per block [s, s + n), s = src_off[i], n = src_len[i]:
+ *       1. s != prefix_end (a jump): the prefix becomes the external dictionary (the old one is dropped), prefix_len = 0,
+ *          prefix_end = s.  On an all-zero state this changes nothing;
+ *       2. ext_len > 0 and s + n > ext_end - ext_len and s < ext_end (the source overlaps the external dictionary):
+ *          ext_len = ext_end - min(s + n, ext_end), and under 4 bytes it becomes 0;
+ *       3. the block is compressed; the capacity rule is LZ4_compress_HC_continue's (limited output below the bound);
+ *       4. prefix_len += n, prefix_end = s + n, index += n;
+ *   - what follows: the history in reach is the last 65535 bytes of external dictionary ++ prefix; a match that runs to the external
+ *     dictionary's end goes on at the prefix's start; the backward extension of a match stops at the start of the piece the match lies
+ *     in; the last three positions of every contiguous run that a jump ended are never match candidates (liblz4 never inserts them);
+ *   - out_len[i] == 0: it does not fit, or dst_cap[i] < 0.  A RESULT OF 0 DOES NOT END THE STREAM, as in lz4hip_compress_hc_chain_batch:
+ *     the block's source is history for the blocks behind it;
+ *   - the engine's rule for src_len[i] < 0 or > 0x7E000000: the result is 0, step 1 alone is applied, nothing is consumed;
+ *   - lz4hip_hcstream_load_dict is LZ4_loadDictHC as a state edit: {dict_end, min(dict_len, 65536), 0, 0, min(dict_len, 65536)}.  A
+ *     first block that follows the dictionary runs in prefix mode, one elsewhere in external-dictionary mode: a fresh stream with a
+ *     dictionary elsewhere and one block is lz4hip_compress_hc_dict*'s block;
+ *   - lz4hip_hcstream_save_dict(st, buf_off, k) is LZ4_saveDictHC as a state edit, for the caller who has copied the prefix's last
+ *     bytes to src + buf_off: kept = min(k, 65536), below 4 it is 0, then min(kept, prefix_len); the history is those bytes, ending at
+ *     buf_off + kept, and the external dictionary is dropped.  Returns kept (LZ4HIP_E_ARG for a NULL state);
+ *   - A CALL IS A SNAPSHOT: all blocks of a call are read from src as it is during the call.  A producer that writes over its ring
+ *     ends the call in front of the first block whose bytes land on anything an earlier block of the same call reads -- its source,
+ *     or the history it can reach -- as a caller of liblz4 compresses a block before it writes the next over old data;
+ *   - levels are clamped as everywhere (< 1 -> 9, > 12 -> 12).  LEVELS 1..9 HAVE NO EXCEPTION to byte equality but one that liblz4
+ *     itself leaves to the memory layout: its 2-byte pre-test of a prefix candidate may read up to look-back bytes in front of the
+ *     prefix's first byte, whatever lies there in the caller's memory; the engine reads the external dictionary's last bytes there.
+ *     LEVELS 10..12: where the optimal parser's chain swap reads the chain entry of a position liblz4 never inserted (the three in
+ *     front of a jump), liblz4 reads a stale entry of its 64 K ring; here such a position has the entry 0 and never matches (the rule
+ *     of lz4hip_compress_hc_dict*).  On a stream younger than 64 KB the stale entry is 0 and the bytes are liblz4's; on an older
+ *     one a block may differ (both outputs are valid LZ4);
+ *   - NOT SERIAL, like the chain call: the host walks the state machine and lays every stream out as one buffer in liblz4's own index
+ *     space -- the kept external piece (only while the prefix is shorter than 65535 bytes), the kept prefix piece (at most 65536
+ *     bytes), the call's blocks -- in which a jump is contiguous; every block of every stream is parsed at once, one wavefront per block
+ *     (hc_parse_stream_kernel), behind a chain table built over the buffers in segments ("hc_chain_segment") that skips the never
+ *     inserted positions (hc_build_stream_kernel).  Only the bytes produced come back; the call shards over the initialised devices at
+ *     stream boundaries;
+ *   - nothing outside the call's sources and the kept pieces of the two histories is read, nothing outside a block's slot is written.
+ *     Slots must not overlap;
+ *   - LZ4HIP_E_ARG, said before a device is looked for: a NULL pointer (all are required), a chain_first that is not ascending from 0 to
+ *     n_blocks, a prefix_len longer than prefix_end or an ext_len longer than ext_end, a stream whose 65536 + index would pass 2^31
+ *     during the call (liblz4 reloads its dictionary there; that reload is out of scope).  Without a device a well-formed call is
+ *     LZ4HIP_E_NO_DEVICE;
+ *   - out of scope: device-pointer forms; LZ4_attach_HC_dictionary; LZ4_compress_HC_continue_destSize; favorDecSpeed; the 2 GiB
+ *     reload.                                                                                                                      */
+typedef struct lz4hip_hcstream_state { uint64_t prefix_end, prefix_len, ext_end, ext_len, index; } lz4hip_hcstream_state;   /* all zero: a fresh stream */
+int lz4hip_compress_hc_stream_batch(lz4hip_hcstream_state* state, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                    const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                    int32_t* out_len, uint32_t n_blocks, uint32_t n_chains, int level);
+int lz4hip_hcstream_load_dict(lz4hip_hcstream_state* st, uint64_t dict_end, uint64_t dict_len);
+int lz4hip_hcstream_save_dict(lz4hip_hcstream_state* st, uint64_t buf_off, int k);
 /* COMPRESS STREAMS THAT ARE CONTINUED BY ANY NUMBER OF CALLS: a set of n_streams compress streams whose state -- the hash table and the
  * index position, what an LZ4_stream_t carries beside its history -- is RESIDENT ON THE DEVICE between calls.  The arrays of
  * lz4hip_compress_fast_stream_batch are lz4hip_compress_fast_chain_batch's, with one addition: chain c of a call is the next run of

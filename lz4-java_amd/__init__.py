@@ -68,6 +68,9 @@ C_ABI = {
     "lz4hip_compress_fast_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32]),
     "lz4hip_compress_fast_chain_batch_dev": (C.c_int, [C.c_void_p] * 10 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_hc_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_uint32, C.c_int]),
+    "lz4hip_compress_hc_stream_batch": (C.c_int, [_u64p, C.c_void_p, _u64p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_uint32, C.c_int]),
+    "lz4hip_hcstream_load_dict": (C.c_int, [_u64p, C.c_uint64, C.c_uint64]),
+    "lz4hip_hcstream_save_dict": (C.c_int, [_u64p, C.c_uint64, C.c_int]),
     "lz4hip_cstreams_create": (C.c_int, [C.c_uint32, C.POINTER(C.c_void_p)]),
     "lz4hip_cstreams_count": (C.c_int, [C.c_void_p]),
     "lz4hip_cstreams_reset": (C.c_int, [C.c_void_p, _u32p, C.c_uint32]),
@@ -1022,6 +1025,43 @@ class LZ4HIPBatch:
         return list(out[:n])
 
     @classmethod
+    def compressHCStream(cls, state, src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap, level=9):
+        """LZ4_compress_HC_continue on streams whose sources land anywhere -- a ring that wraps, alternating buffers, a save area, a
+        dictionary elsewhere (lz4hip_compress_hc_stream_batch): stream c is the blocks chainFirst[c] .. chainFirst[c + 1] - 1 of this
+        call, block i is src[srcOff[i]:+srcLen[i]] and owns the slot dst[dstOff[i]:+dstCap[i]].  state[c] is the stream's (prefixEnd,
+        prefixLen, extEnd, extLen, index) as offsets into src -- five zeros are a fresh stream -> (outLen, newState): liblz4's return
+        value per block (0: it did not fit, which does not end the stream; a list, or an int32 array for numpy inputs) and the states
+        behind the call, to be handed to the next one.  A call is a snapshot of src.  CompressStreamsHC keeps the states for its
+        caller"""
+        n, nc = len(srcOff), len(state)
+        if not (len(srcLen) == len(dstOff) == len(dstCap) == n):
+            raise ValueError("per-block arrays differ in length")
+        if len(chainFirst) != nc + 1:
+            raise ValueError("per-stream arrays differ in length")
+        for i in range(n):
+            if 0 <= srcLen[i] <= 0x7E000000:   # (any other length gives 0 and reads nothing: the engine's rule)
+                _check_range(src, srcOff[i], srcLen[i])
+            elif srcOff[i] < 0 or srcOff[i] > len(src):
+                raise IndexError(srcOff[i])
+        cls._check_ranges(dst, dstOff, [max(int(c), 0) for c in dstCap])
+        flat = (C.c_uint64 * max(5 * nc, 1))()
+        for c in range(nc):
+            pe, pl, ee, el, ix = (int(v) for v in state[c])
+            if min(pe, pl, ee, el, ix) < 0 or (pl and pe > len(src)) or (el and ee > len(src)):
+                raise IndexError("history outside the buffer")
+            flat[5 * c:5 * c + 5] = (pe, pl, ee, el, ix)
+        sp, sk = _ro_ptr(src)
+        dp, dk = _rw_ptr(dst)
+        out = (C.c_int32 * max(n, 1))()
+        _chk(lib().lz4hip_compress_hc_stream_batch(flat, sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst), dp,
+                                                   _arr(C.c_uint64, dstOff), _arr(C.c_int32, dstCap), out, n, nc, int(level)))
+        new = [tuple(flat[5 * c:5 * c + 5]) for c in range(nc)]
+        if hasattr(srcLen, "dtype"):
+            import numpy as np
+            return np.frombuffer(out, dtype=np.int32, count=n).copy(), new
+        return list(out[:n]), new
+
+    @classmethod
     def compressFastChain(cls, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None):
         """LZ4_compress_fast_continue over chains of linked blocks (lz4hip_compress_fast_chain_batch): chain c is the blocks
         chainFirst[c] .. chainFirst[c + 1] - 1, whose sources lie back to back from src[chainSrcOff[c]] on, behind chainPrefixLen[c]
@@ -1291,6 +1331,57 @@ class DecodeStreams:
             raise ValueError("a stream is named twice")
         out, new = LZ4HIPBatch.decompressSafeStream([self._state[c] for c in ids], src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap,
                                                     chainWinOff, chainWinLen)
+        for c, s in zip(ids, new):
+            self._state[c] = s
+        return out
+
+
+class CompressStreamsHC:
+    """The states of n HC compress streams whose sources land anywhere -- per stream what an LZ4_streamHC_t of liblz4 keeps beside its
+    tables: (prefixEnd, prefixLen, extEnd, extLen, index) as offsets into the one source buffer its caller compresses from.  Plain host
+    data: there is nothing to close and nothing on a device.  Every stream gives, over all the calls that name it, the values and
+    bytes ONE LZ4_streamHC_t gives, however its blocks are cut into calls (include/lz4hip.h states the exceptions)."""
+
+    def __init__(self, n, level=9):
+        if n < 1:
+            raise ValueError("a set has at least one stream")
+        self.level = int(level)
+        self._state = [(0, 0, 0, 0, 0)] * int(n)
+
+    def __len__(self):
+        return len(self._state)
+
+    def reset(self, streamId=None):
+        """makes the listed streams (None: all of them) fresh"""
+        for c in (range(len(self._state)) if streamId is None else streamId):
+            self._state[c] = (0, 0, 0, 0, 0)
+
+    def state(self, streamId=None):
+        """-> the (prefixEnd, prefixLen, extEnd, extLen, index) of the listed streams (None: all of them)"""
+        return [self._state[c] for c in (range(len(self._state)) if streamId is None else streamId)]
+
+    def loadDict(self, streamId, dictEnd, dictLen):
+        """LZ4_loadDictHC: the stream is fresh behind the dictLen bytes of dictionary that end at src[dictEnd]"""
+        if dictLen < 0 or dictLen > dictEnd:
+            raise IndexError("history reaches in front of the buffer")
+        st = (C.c_uint64 * 5)()
+        _chk(lib().lz4hip_hcstream_load_dict(st, int(dictEnd), int(dictLen)))
+        self._state[streamId] = tuple(st)
+
+    def saveDict(self, streamId, bufOff, k):
+        """LZ4_saveDictHC for the caller who has copied the last k bytes the stream consumed to src[bufOff:] -> the bytes kept"""
+        st = (C.c_uint64 * 5)(*self._state[streamId])
+        kept = lib().lz4hip_hcstream_save_dict(st, int(bufOff), int(k))
+        _chk(min(kept, 0))
+        self._state[streamId] = tuple(st)
+        return kept
+
+    def compress(self, streamId, src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap):
+        """LZ4HIPBatch.compressHCStream at the set's level for the streams streamId (distinct ids, one per chain of the call) -> outLen"""
+        ids = [int(c) for c in streamId]
+        if len(set(ids)) != len(ids):
+            raise ValueError("a stream is named twice")
+        out, new = LZ4HIPBatch.compressHCStream([self._state[c] for c in ids], src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap, self.level)
         for c, s in zip(ids, new):
             self._state[c] = s
         return out

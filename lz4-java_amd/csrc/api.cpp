@@ -98,13 +98,15 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // arrays and state records are BlockCall::dstream; the host path is dstream_host_shard
 // OP_COMPRESS_XSTREAM: the same resident streams when their sources land anywhere (liblz4's external-dictionary mode included): its
 // arrays are BlockCall::cxstream, which carries the device's share of the set's state; the host path is cxstream_host_shard
+// OP_COMPRESS_HC_STREAM: LZ4_compress_HC_continue on streams whose sources land anywhere, both of its modes: its arrays are
+// BlockCall::hcstream, the linear image the host has made of the call (host_staging.h HcsImage); the host path is hcstream_host_shard
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
           OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN, OP_COMPRESS_CHAIN, OP_COMPRESS_HC_CHAIN, OP_COMPRESS_STREAM,
-          OP_DECOMPRESS_STREAM, OP_COMPRESS_XSTREAM };
-constexpr int OP_COUNT = OP_COMPRESS_XSTREAM + 1;   // (the last enumerator)
+          OP_DECOMPRESS_STREAM, OP_COMPRESS_XSTREAM, OP_COMPRESS_HC_STREAM };
+constexpr int OP_COUNT = OP_COMPRESS_HC_STREAM + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
-constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN || op == OP_COMPRESS_STREAM || op == OP_COMPRESS_XSTREAM; }
+constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN || op == OP_COMPRESS_STREAM || op == OP_COMPRESS_XSTREAM || op == OP_COMPRESS_HC_STREAM; }
 // a second per-block result (BlockCall::consumed) travels behind out[]
 constexpr bool op_has_consumed(Op op) { return op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST; }
 // out[i] counts SOURCE bytes read: a block that succeeded filled its whole dst_cap[i]
@@ -112,7 +114,7 @@ constexpr bool op_fills_capacity(Op op) { return op == OP_DECODE_FAST; }
 // writes no output buffer: dst and dst_off may be NULL, nothing is allocated, staged or copied back for them (dst_cap is an input)
 constexpr bool op_writes_no_output(Op op) { return op == OP_DECODED_SIZE; }
 // needs the chain-delta workspace (BlockCall::hc_ws / hc_span)
-constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_HC_CHAIN; }
+constexpr bool op_uses_hc_ws(Op op) { return op == OP_COMPRESS_HC || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_HC_CHAIN || op == OP_COMPRESS_HC_STREAM; }
 // its arrays are BlockCall::cchain (chains of linked blocks), its host path cchain_host_shard
 constexpr bool op_takes_cchain(Op op) { return op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN || op == OP_COMPRESS_STREAM; }
 // a block that returns 0 ends its chain (and chain_consumed[] says how far the chain came)
@@ -137,6 +139,7 @@ struct BlockCall {
   const lz4hip::CChainArgs* cchain = nullptr; // op_takes_cchain: the call's arrays on the device
   const lz4hip::DStreamArgs* dstream = nullptr;   // OP_DECOMPRESS_STREAM: the call's arrays and state records on the device
   const lz4hip::CXStreamArgs* cxstream = nullptr; // OP_COMPRESS_XSTREAM: the call's arrays on the device, the slots and the set's state
+  const lz4hip::HcStreamArgs* hcstream = nullptr; // OP_COMPRESS_HC_STREAM: the call's linear image and its arrays on the device
   void* hc_scratch = nullptr;           // op_needs_chain_scratch: lz4hip::hc_chain_scratch_bytes of device memory
   // op_resumes_streams: the device's share of the set's state (kernels.h CStreamArgs) and, on the device, the slot of every chain
   uint32_t* cs_rec = nullptr; uint64_t* cs_tables = nullptr; const uint32_t* cs_slot = nullptr;
@@ -414,6 +417,10 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
     case OP_COMPRESS_XSTREAM:   // compress_fast_xstream_cu_kernel draws chains from the queue word
       if (!c.cxstream) return fail(LZ4HIP_E_ARG, kNullArg);
       return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_xstream(*c.cxstream, q, lz4hip::device_cus(), st); });
+    case OP_COMPRESS_HC_STREAM: {   // segment build over the host's item list, then the parse; the queue word is the image's own
+      if (!c.hcstream || !c.hc_ws) return fail(LZ4HIP_E_ARG, kNullArg);
+      return lz4hip::launch_compress_hc_stream(*c.hcstream, c.param, c.hc_ws, lz4hip::device_cus(), st);
+    }
     case OP_COMPRESS_HC_CHAIN: {   // layout, segment build and parse kernels behind one scratch allocation
       if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
       // (workspace and scratch are the buffer set's.  As a stream-ordered allocation made here, the scratch read as zeros in the parse
@@ -1166,6 +1173,86 @@ const char* cchain_arg_error(const lz4hip::CChainArgs& a, bool host, bool stops)
   if (a.n_chains == 0 && a.n_blocks == 0) return nullptr;
   if (!a.src || !a.chain_src_off || !a.src_len || !a.chain_first || !a.dst || !a.dst_off || !a.dst_cap || !a.out || (stops && !a.chain_consumed)) return kNullArg;
   return host ? staging::chain_shape_error(a.chain_first, a.n_chains, a.n_blocks, a.chain_prefix_len, a.chain_src_off, false) : nullptr;
+}
+
+// ---- HC streams whose sources land anywhere, on the host-pointer path ----
+// the caller's HOST arrays of lz4hip_compress_hc_stream_batch
+struct HcStreamHost {
+  lz4hip_hcstream_state* state; const uint8_t* src; const uint64_t* src_off; const int32_t* src_len; const uint32_t* chain_first;
+  uint8_t* dst; const uint64_t* dst_off; const int32_t* dst_cap; int32_t* out; uint32_t n_blocks, n_chains;
+};
+static_assert(sizeof(lz4hip_hcstream_state) == sizeof(staging::HcsState) && offsetof(lz4hip_hcstream_state, index) == offsetof(staging::HcsState, index),
+              "the header's state record is the staging arithmetic's");
+// One device's share [c0, c1) of such a call: cchain_host_shard's frame (chunks of 64 MiB of image or 512 MiB of slots, one stream at
+// least, through the first buffer set of a pooled pair) around the linear image of host_staging.h.  The states of a chunk's streams are
+// written back once its results are on the host.
+int hcstream_host_shard(int level, const HcStreamHost& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+  if (c1 == c0) return LZ4HIP_OK;
+  ShardScope sh(ord, err);
+  if (sh.rc) return sh.rc;
+  ChunkSlot& s = sh.pair->slot[0];
+  const hipStream_t st = s.st;
+  const staging::HcsState* const state = (const staging::HcsState*)h.state;
+  auto produced = [&](uint32_t i) -> size_t { const int32_t r = h.out[i]; return r > 0 && (size_t)r <= pos(h.dst_cap[i]) ? (size_t)r : 0; };   // (h.out: once it is back)
+  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+  const uint32_t seg = (uint32_t)g_hc_chain_segment.load(std::memory_order_relaxed);
+  std::vector<uint64_t> dso;
+  std::vector<uint32_t> items;
+  for (uint32_t c = c0; c < c1;) {
+    // the next chunk: streams [c, j), blocks [b0, b1)
+    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, [&](uint32_t j) {
+      size_t d = 0;
+      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) d += al16(pos(h.dst_cap[i]));
+      return staging::Cost{staging::hcstream_cost(state[j], h.chain_first, j, h.src_len), d};
+    });
+    const uint32_t j = ck.end, b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
+    if (nb == 0) { c = j; continue; }   // (streams without blocks: their states stay as they are)
+    const staging::HcsImage im(state, h.chain_first, c, nc, h.src_off, h.src_len);
+    dso.resize(nb);
+    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { dso[t] = o; o += al16(pos(h.dst_cap[b0 + t])); } }
+    items.clear();   // positions 0 .. len - 4 get an entry: ceil((len - 3) / seg) segments per stream
+    for (uint32_t t = 0; t < nc; t++)
+      for (uint64_t k = 0, nk = im.buf_len[t] >= 4u ? (im.buf_len[t] - 3u + seg - 1u) / seg : 0u; k < nk; k++) { items.push_back(t); items.push_back((uint32_t)k); }
+    const staging::HcStreamMeta m(nb, nc, im.ends.size(), items.size() / 2u);
+    if (!sh.reserve(s, im.total, true, ck.dst, m.l.total)) return sh.rc;
+    if (!sh.ok("staging allocation", s.d_ws.reserve(lz4hip::hc_ws_bytes(im.total, nb, level)))) return sh.rc;
+    uint8_t *const hs = (uint8_t*)s.h_src.p, *const hd = (uint8_t*)s.h_dst.p;
+    void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
+    par_blocks(0, (uint32_t)im.pieces.size(), im.total, [=, &im](uint32_t t) { const staging::HcsPiece& p = im.pieces[t]; memcpy(hs + p.dev, h.src + p.src, p.len); });
+    m.l.zero_results(hm);
+    memcpy(m.blk_start.in(hm), im.blk_start.data(), m.blk_start.bytes());
+    memcpy(m.dst_off.in(hm), dso.data(), m.dst_off.bytes());
+    memcpy(m.buf_off.in(hm), im.buf_off.data(), m.buf_off.bytes());
+    memcpy(m.buf_len.in(hm), im.buf_len.data(), m.buf_len.bytes());
+    memcpy(m.src_len.in(hm), h.src_len + b0, m.src_len.bytes());
+    memcpy(m.dst_cap.in(hm), h.dst_cap + b0, m.dst_cap.bytes());
+    memcpy(m.blk_hist.in(hm), im.blk_hist.data(), m.blk_hist.bytes());
+    memcpy(m.blk_low.in(hm), im.blk_low.data(), m.blk_low.bytes());
+    memcpy(m.blk_dlim.in(hm), im.blk_dlim.data(), m.blk_dlim.bytes());
+    memcpy(m.end_first.in(hm), im.end_first.data(), m.end_first.bytes());
+    if (m.ends.n) memcpy(m.ends.in(hm), im.ends.data(), m.ends.bytes());
+    if (m.items.n) memcpy(m.items.in(hm), items.data(), m.items.bytes());
+    if (!sh.upload(s, im.total, m.l, st)) return sh.rc;
+    const lz4hip::HcStreamArgs a{(const uint8_t*)s.d_src.p, m.blk_start.in(dm), m.blk_hist.in(dm), m.blk_low.in(dm), m.blk_dlim.in(dm), m.src_len.in(dm),
+                                 (uint8_t*)s.d_dst.p, m.dst_off.in(dm), m.dst_cap.in(dm), m.out.in(dm), m.buf_off.in(dm), m.buf_len.in(dm), m.end_first.in(dm),
+                                 m.ends.in(dm), m.items.in(dm), m.queue.in(dm), (uint64_t)im.total, nb, nc, (uint32_t)im.ends.size(), (uint32_t)(items.size() / 2u), seg};
+    BlockCall call{OP_COMPRESS_HC_STREAM, level};
+    call.hcstream = &a; call.hc_ws = s.d_ws.p; call.hc_span = im.total;
+    if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
+    memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
+    // only the bytes produced come back
+    if (!sh.fetch_runs(s, nb, [&](uint32_t t) { return staging::Run{(size_t)dso[t], produced(b0 + t)}; })) return sh.rc;
+    par_blocks(b0, b1, ck.dst, [=, &dso](uint32_t i) { if (const size_t r = produced(i)) memcpy(h.dst + h.dst_off[i], hd + dso[i - b0], r); });
+    memcpy(h.state + c, im.after.data(), (size_t)nc * sizeof(staging::HcsState));
+    c = j;
+  }
+  return LZ4HIP_OK;
+}
+// the argument errors of such a call that can be seen without a device
+const char* hcstream_arg_error(const HcStreamHost& h) {
+  if (h.n_chains == 0 && h.n_blocks == 0) return nullptr;
+  if (!h.state || !h.src || !h.src_off || !h.src_len || !h.chain_first || !h.dst || !h.dst_off || !h.dst_cap || !h.out) return kNullArg;
+  return staging::hcstream_shape_error((const staging::HcsState*)h.state, h.chain_first, h.n_chains, h.n_blocks, h.src_len);
 }
 
 // ---- resident streams whose sources land anywhere, on the host-pointer path ----
@@ -2290,6 +2377,33 @@ int lz4hip_compress_hc_chain_batch(const uint8_t* src, const uint64_t* chain_src
   if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
   // whole chains per device: a device's workspace and staging hold a chain's buffer in one piece
   return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard({OP_COMPRESS_HC_CHAIN, lv}, h, ord, c0, c1, err); });
+}
+int lz4hip_compress_hc_stream_batch(lz4hip_hcstream_state* state, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                    const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
+                                    uint32_t n_blocks, uint32_t n_chains, int level) {
+  const HcStreamHost h{state, src, src_off, src_len, chain_first, dst, dst_off, dst_cap, out_len, n_blocks, n_chains};
+  if (const char* why = hcstream_arg_error(h)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
+  if (const int rc = need_device()) return rc;
+  if (n_chains == 0) return LZ4HIP_OK;
+  int lv;
+  if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
+  // whole streams per device: a device's workspace and staging hold a stream's linear buffer in one piece
+  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return hcstream_host_shard(lv, h, ord, c0, c1, err); });
+}
+int lz4hip_hcstream_load_dict(lz4hip_hcstream_state* st, uint64_t dict_end, uint64_t dict_len) {
+  if (!st) return fail(LZ4HIP_E_ARG, kNullArg);
+  if (dict_len > dict_end) return fail(LZ4HIP_E_ARG, "dict_len reaches in front of src");
+  const staging::HcsState v = staging::hcs_load_dict(dict_end, dict_len);
+  memcpy(st, &v, sizeof v);
+  return LZ4HIP_OK;
+}
+int lz4hip_hcstream_save_dict(lz4hip_hcstream_state* st, uint64_t buf_off, int k) {
+  if (!st) return fail(LZ4HIP_E_ARG, kNullArg);
+  staging::HcsState v;
+  memcpy(&v, st, sizeof v);
+  const int kept = staging::hcs_save_dict(v, buf_off, k);
+  memcpy(st, &v, sizeof v);
+  return kept;
 }
 int lz4hip_compress_fast_dict_batch(const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, uint8_t* dst,
                                     const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint32_t n, const lz4hip_dict* dict) {

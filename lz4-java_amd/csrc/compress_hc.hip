@@ -14,6 +14,9 @@
 //                        : LZ4_compress_HC_continue over chains of linked blocks (prefix mode).  Every block of every chain is parsed at
 //                          once (HcParse's PREFIX switch) behind a delta[] built over each chain's buffer in segments that workgroups
 //                          draw from a queue (HcBuild's SEG switch); the layout kernel makes the per-block offsets and the item list.
+//   hc_build_stream_kernel / hc_parse_stream_kernel
+//                        : LZ4_compress_HC_continue on streams whose sources land anywhere (both of its modes), over the linear image the
+//                          host makes of a call (host_staging.h HcsImage): HcBuild's RUNS switch, HcParse's DICT and PREFIX switches.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
@@ -290,6 +293,58 @@ int launch_compress_hc_chain(const CChainArgs& a, int level, void* ws, uint64_t 
   const uint32_t wgs = s.max_items < n_cus ? s.max_items : n_cus;
   hipLaunchKernelGGL(hc_build_chain_kernel, dim3(wgs ? wgs : 1u), dim3(64), 0, (hipStream_t)stream, a, s, (uint16_t*)ws, seg);
   hipLaunchKernelGGL(hc_parse_chain_kernel, dim3(a.n_blocks), dim3(64), 0, (hipStream_t)stream, a, s, (const uint16_t*)ws, level, opt);
+  return (int)hipGetLastError();
+}
+// ------------------------------------------------------------------------------------------------
+// HC compress over streams whose sources land anywhere (LZ4_compress_HC_continue in both of its modes).  The stream's bookkeeping is a
+// function of addresses and lengths alone, so the host has walked it and laid every stream out in liblz4's index space (HcsImage):
+//   hc_build_stream_kernel  hc_build_chain_kernel's queue and segment warm-up over the host's item list, with HcBuild's RUNS switch
+//                           (the last three positions of a run that a jump ended are never inserted)
+//   hc_parse_stream_kernel  HcParse's DICT and PREFIX switches together, grid = n_blocks
+// Nothing that is read from the arrays is trusted to lie inside the image.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void hc_build_stream_kernel(HcStreamArgs a, uint16_t* ws, uint32_t seg) {
+  __shared__ __attribute__((aligned(16))) uint32_t head[32768];  // 128 KB: liblz4's HC hashTable
+  WaveDev w(head);
+  for (;;) {
+    uint32_t t = 0;
+    if (__lane_id() == 0) t = atomicAdd(a.queue, 1u);
+    t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+    if (t >= a.n_items) return;
+    const uint32_t c = a.items[2u * t], k = a.items[2u * t + 1u];
+    if (c >= a.n_streams) continue;
+    const uint64_t buf = a.buf_off[c], len = a.buf_len[c];
+    const uint32_t e0 = a.end_first[c], e1 = a.end_first[c + 1];
+    if (buf > a.span || len > a.span - buf || len > 0xFFFF0000ull || e0 > e1 || e1 > a.n_ends) continue;
+    hc_stream_build_segment(w, a.src + buf, len, seg, k, ws + buf, a.ends + e0, e1 - e0);
+    WaveDev::sync();   // the head table is reused: the next segment starts from its own
+  }
+}
+__global__ __launch_bounds__(64) void hc_parse_stream_kernel(HcStreamArgs a, const uint16_t* ws, int level, int* opt_ws) {
+  const uint32_t b = blockIdx.x;
+  const int32_t n = a.src_len[b];
+  const int32_t cap = a.dst_cap[b];
+  const uint32_t hist = a.blk_hist[b], low = a.blk_low[b], dlim = a.blk_dlim[b];
+  const uint64_t start = a.blk_start[b];
+  int r = 0;
+  if (n >= 0 && (uint32_t)n <= 0x7E000000u && cap >= 0 && hist <= 65536u && low <= dlim && dlim <= hist && start >= hist && start <= a.span &&
+      (uint64_t)n <= a.span - start) {
+    const uint64_t view = start - hist;
+    WaveDev w(nullptr);
+    r = hc_stream_parse_block(w, a.src + view, hist, low, dlim, n, ws + view, a.dst + a.dst_off[b], cap, level, opt_ws + (size_t)b * HC_OPT_INTS);
+  }
+  if (threadIdx.x == 0) a.out[b] = r;
+}
+int launch_compress_hc_stream(const HcStreamArgs& a, int level, void* ws, uint32_t n_cus, void* stream) {
+  if (a.n_blocks == 0) return 0;
+  if (a.seg < 4096u || a.seg > (1u << 30)) return (int)hipErrorInvalidValue;
+  const size_t d = (((size_t)a.span * 2u + 64u) + 255u) & ~(size_t)255u;
+  int* const opt = level >= 10 ? (int*)((uint8_t*)ws + d) : nullptr;
+  if (a.n_items) {
+    const uint32_t wgs = a.n_items < n_cus ? a.n_items : n_cus;
+    hipLaunchKernelGGL(hc_build_stream_kernel, dim3(wgs ? wgs : 1u), dim3(64), 0, (hipStream_t)stream, a, (uint16_t*)ws, a.seg);
+  }
+  hipLaunchKernelGGL(hc_parse_stream_kernel, dim3(a.n_blocks), dim3(64), 0, (hipStream_t)stream, a, (const uint16_t*)ws, level, opt);
   return (int)hipGetLastError();
 }
 int launch_compress_hc_dest(const BatchArgs& a, int32_t* consumed, int level, void* ws, uint64_t span, void* stream) {

@@ -2,7 +2,8 @@
 // without a device (tests/cpp/host_staging_test.cpp): where a chunk's metadata arrays lie in their one buffer, where a chunk ends,
 // which produced bytes travel back in one copy, the shape the arrays of a chain call must have, where the windows and history
 // pieces of a stream-decode call lie in the device image, and where the used parts of the windows and the history pieces of a
-// stream-compress call whose sources land anywhere lie in theirs.
+// stream-compress call whose sources land anywhere lie in theirs, and the state machine and the linear image of an HC stream-compress
+// call (one buffer per stream in liblz4's index space).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -72,6 +73,16 @@ struct CXStreamMeta {   // resident streams whose sources land anywhere (cxstrea
       : src_off(l.input<uint64_t>(nb)), dst_off(l.input<uint64_t>(nb)), hist_end(l.input<uint64_t>(nc)), src_len(l.input<int32_t>(nb)), dst_cap(l.input<int32_t>(nb)),
         hist_len(l.input<int32_t>(nc)), first(l.input<uint32_t>(nc + 1)), slot(l.input<uint32_t>(nc)),
         consumed(l.result<uint64_t>(nc, true)), out(l.result<int32_t>(nb, true)) {}
+};
+struct HcStreamMeta {   // HC streams whose sources land anywhere (hcstream_host_shard): the image's arrays; the build's queue word goes up zeroed
+  MetaLayout l;
+  Region<uint64_t> blk_start, dst_off, buf_off, buf_len; Region<int32_t> src_len, dst_cap; Region<uint32_t> blk_hist, blk_low, blk_dlim, end_first, ends, items, queue;
+  Region<int32_t> out;
+  HcStreamMeta(size_t nb, size_t nc, size_t n_ends, size_t n_items)
+      : blk_start(l.input<uint64_t>(nb)), dst_off(l.input<uint64_t>(nb)), buf_off(l.input<uint64_t>(nc)), buf_len(l.input<uint64_t>(nc)),
+        src_len(l.input<int32_t>(nb)), dst_cap(l.input<int32_t>(nb)), blk_hist(l.input<uint32_t>(nb)), blk_low(l.input<uint32_t>(nb)),
+        blk_dlim(l.input<uint32_t>(nb)), end_first(l.input<uint32_t>(nc + 1)), ends(l.input<uint32_t>(n_ends)), items(l.input<uint32_t>(2 * n_items)),
+        queue(l.result<uint32_t>(1, true)), out(l.result<int32_t>(nb)) {}
 };
 template <class T>
 struct HashMeta {   // the hashes (xxh_shard): T = uint32_t / uint64_t
@@ -338,6 +349,126 @@ struct CxImage {
     }
   }
   uint64_t to_dev(uint32_t t, uint64_t x) const { return base[t] + (x - hull[t].lo); }
+};
+
+// ---- the HC stream compressor when sources land anywhere (api.cpp hcstream_host_shard) ----
+// A stream's state is liblz4's bookkeeping as offsets into the caller's source base (include/lz4hip.h lz4hip_hcstream_state): the prefix
+// [prefix_end - prefix_len, prefix_end), the external dictionary [ext_end - ext_len, ext_end), and the bytes loaded plus consumed.  It is
+// a function of addresses and lengths alone, so the whole call is walked here, before anything is compressed.
+struct HcsState { uint64_t prefix_end, prefix_len, ext_end, ext_len, index; };
+constexpr uint64_t kHcsKeep = 65536, kHcsMaxBlock = 0x7E000000ull, kHcsLife = 0x80000000ull;
+inline bool hcs_runs(int32_t n) { return n >= 0 && (uint64_t)n <= kHcsMaxBlock; }   // otherwise: 0, step 1 only, nothing consumed
+// LZ4_loadDictHC / LZ4_saveDictHC as state edits
+inline HcsState hcs_load_dict(uint64_t dict_end, uint64_t dict_len) {
+  const uint64_t k = dict_len < kHcsKeep ? dict_len : kHcsKeep;
+  return HcsState{dict_end, k, 0, 0, k};
+}
+inline int hcs_save_dict(HcsState& st, uint64_t buf_off, int k) {
+  uint64_t kept = k < 0 ? 0u : ((uint64_t)k < kHcsKeep ? (uint64_t)k : kHcsKeep);
+  if (kept < 4u) kept = 0;
+  if (kept > st.prefix_len) kept = st.prefix_len;
+  st.prefix_end = buf_off + kept;
+  st.prefix_len = kept;
+  st.ext_len = 0;
+  return (int)kept;
+}
+// steps 1 and 2 of the state machine in front of the block [s, s + n) -> true at a jump; n = 0 for a block that cannot run
+inline bool hcs_enter(HcsState& st, uint64_t s, uint64_t n, bool runs) {
+  const bool jump = s != st.prefix_end;
+  if (jump) { st.ext_end = st.prefix_end; st.ext_len = st.prefix_len; st.prefix_len = 0; st.prefix_end = s; }
+  if (runs && st.ext_len > 0 && s + n > st.ext_end - st.ext_len && s < st.ext_end) {
+    st.ext_len = st.ext_end - (s + n < st.ext_end ? s + n : st.ext_end);
+    if (st.ext_len < 4u) st.ext_len = 0;
+  }
+  return jump;
+}
+inline void hcs_leave(HcsState& st, uint64_t s, uint64_t n) { st.prefix_len += n; st.prefix_end = s + n; st.index += n; }
+// what of a state's histories a call stages: the prefix's last 64 KB, and of the external piece what the first block can still reach
+// while the prefix is shorter than 65535 bytes
+inline uint64_t hcs_prefix_keep(const HcsState& st) { return st.prefix_len < kHcsKeep ? st.prefix_len : kHcsKeep; }
+inline uint64_t hcs_ext_keep(const HcsState& st) {
+  const uint64_t pk = hcs_prefix_keep(st);
+  if (pk >= kHcsKeep - 1u) return 0;
+  return st.ext_len < kHcsKeep - pk ? st.ext_len : kHcsKeep - pk;
+}
+// What can be said about a call without a device -> a message, or nullptr
+inline const char* hcstream_shape_error(const HcsState* state, const uint32_t* chain_first, uint32_t n_chains, uint32_t n_blocks, const int32_t* src_len) {
+  if (chain_first[0] != 0u || chain_first[n_chains] != n_blocks) return "chain_first must start at 0 and end at n_blocks";
+  for (uint32_t c = 0; c < n_chains; c++)
+    if (chain_first[c] > chain_first[c + 1]) return "chain_first must be ascending";
+  for (uint32_t c = 0; c < n_chains; c++) {
+    if (state[c].prefix_len > state[c].prefix_end) return "prefix_len reaches in front of src";
+    if (state[c].ext_len > state[c].ext_end) return "ext_len reaches in front of src";
+    uint64_t index = state[c].index;
+    if (index > kHcsLife) return "a stream past the 2 GiB index limit (liblz4 reloads its dictionary there: out of scope)";
+    for (uint32_t i = chain_first[c]; i < chain_first[c + 1]; i++) {
+      if (hcs_runs(src_len[i])) index += (uint64_t)src_len[i];
+      if (kHcsKeep + index > kHcsLife) return "a stream would pass the 2 GiB index limit during the call (liblz4 reloads its dictionary there: out of scope)";
+    }
+  }
+  return nullptr;
+}
+// the bytes stream c's linear buffer takes (cut_chunk's cost)
+inline size_t hcstream_cost(const HcsState& st, const uint32_t* chain_first, uint32_t c, const int32_t* src_len) {
+  uint64_t n = hcs_ext_keep(st) + hcs_prefix_keep(st);
+  for (uint32_t i = chain_first[c]; i < chain_first[c + 1]; i++) if (hcs_runs(src_len[i])) n += (uint64_t)src_len[i];
+  return al16((size_t)n);
+}
+// One chunk's image.  Every stream gets ONE buffer in liblz4's own index space: the kept external piece, the kept prefix piece, then the
+// call's blocks in order -- a jump is contiguous there.  Per block: where it starts in the image, how much lies in front of it in its
+// VIEW (hist = min(65536, what the buffer holds in front of it)), and liblz4's lowLimit and dictLimit as positions of that view, cut to
+// its start (what lies below the view cannot be reached: 65535 is the longest distance, and the backward extension of a match ends
+// at the pending literals, which begin inside the block).  Per stream: the buffer, its run ends (positions at which a jump ended a
+// contiguous run, ascending, counted from the buffer's start) and the state behind its last block.
+struct HcsPiece { uint64_t src; size_t dev, len; };   // the caller's bytes [src, src + len) at image offset dev
+struct HcsImage {
+  std::vector<HcsPiece> pieces;
+  std::vector<uint64_t> blk_start;
+  std::vector<uint32_t> blk_hist, blk_low, blk_dlim;
+  std::vector<uint64_t> buf_off, buf_len;
+  std::vector<uint32_t> end_first, ends;
+  std::vector<HcsState> after;
+  size_t total = 0;
+  // stream c0 + t is blocks [chain_first[c0 + t], chain_first[c0 + t + 1]); the call has passed hcstream_shape_error
+  HcsImage(const HcsState* state, const uint32_t* chain_first, uint32_t c0, uint32_t nc, const uint64_t* src_off, const int32_t* src_len) {
+    const uint32_t b0 = chain_first[c0], nb = chain_first[c0 + nc] - b0;
+    blk_start.resize(nb); blk_hist.resize(nb); blk_low.resize(nb); blk_dlim.resize(nb);
+    buf_off.resize(nc); buf_len.resize(nc); end_first.resize(nc + 1); after.resize(nc);
+    for (uint32_t t = 0; t < nc; t++) {
+      HcsState st = state[c0 + t];
+      const uint64_t ek = hcs_ext_keep(st), pk = hcs_prefix_keep(st);
+      const size_t base = total;
+      end_first[t] = (uint32_t)ends.size();
+      if (ek) pieces.push_back(HcsPiece{st.ext_end - ek, base, (size_t)ek});
+      if (pk) pieces.push_back(HcsPiece{st.prefix_end - pk, base + (size_t)ek, (size_t)pk});
+      if (ek) ends.push_back((uint32_t)ek);
+      uint64_t L = ek + pk;          // the buffer's length so far
+      uint64_t dlim = ek;            // where the prefix begins in the buffer
+      uint64_t ext_avail = ek;       // bytes of the external piece the buffer holds in front of dlim
+      for (uint32_t i = chain_first[c0 + t]; i < chain_first[c0 + t + 1]; i++) {
+        const bool runs = hcs_runs(src_len[i]);
+        const uint64_t s = src_off[i], n = runs ? (uint64_t)src_len[i] : 0u;
+        if (hcs_enter(st, s, n, runs)) {
+          ext_avail = L - dlim;
+          dlim = L;
+          if (ends.size() == end_first[t] || ends.back() != (uint32_t)L) ends.push_back((uint32_t)L);
+        }
+        const uint64_t low = dlim - (st.ext_len < ext_avail ? st.ext_len : ext_avail);
+        const uint64_t hist = L < kHcsKeep ? L : kHcsKeep, view = L - hist;
+        blk_start[i - b0] = base + L;
+        blk_hist[i - b0] = (uint32_t)hist;
+        blk_low[i - b0] = (uint32_t)((low > view ? low : view) - view);
+        blk_dlim[i - b0] = (uint32_t)((dlim > view ? dlim : view) - view);
+        if (!runs) continue;
+        if (n) pieces.push_back(HcsPiece{s, base + (size_t)L, (size_t)n});
+        L += n;
+        hcs_leave(st, s, n);
+      }
+      buf_off[t] = base; buf_len[t] = L; after[t] = st;
+      total += al16((size_t)L);
+    }
+    end_first[nc] = (uint32_t)ends.size();
+  }
 };
 
 // runs in any order, overlapping ones included -> ascending, disjoint, those at most RUN_GAP bytes apart joined

@@ -191,6 +191,21 @@ int launch_compress_fast_xstream(const CXStreamArgs& a, uint32_t* q, uint32_t n_
 // the caller keeps (not a stream-ordered allocation made for the launch).
 size_t hc_chain_scratch_bytes(uint64_t span, uint32_t n_blocks, uint32_t n_chains, uint32_t seg);
 int launch_compress_hc_chain(const CChainArgs& a, int level, void* ws, uint64_t span, uint32_t seg, void* scratch, uint32_t n_cus, void* stream);
+// LZ4_compress_HC_continue on streams whose sources land anywhere (compress_hc.hip): the host has walked the call's state machine and laid
+// every stream out as ONE buffer in liblz4's index space (host_staging.h HcsImage), so nothing here is serial.  src: the image of `span`
+// bytes; per block its start in the image, the bytes of its view in front of it (0 .. 65536), liblz4's lowLimit and dictLimit as
+// positions of the view (low <= dlim <= hist), its length, slot and capacity; per stream its buffer [buf_off, + buf_len) and its run
+// ends ends[end_first[t] .. end_first[t + 1]) (ascending, counted from the buffer's start; n_ends in all); items: the build's
+// {stream, segment} pairs of `seg` positions (4096 .. 2^30), drawn from the queue word (zeroed by the caller).  out[i] = liblz4's return value; a block
+// whose length or capacity is negative, or whose numbers do not fit the image, gives 0.  `ws` = hc_ws_bytes(span, n_blocks, level).
+struct HcStreamArgs {
+  const uint8_t* src; const uint64_t* blk_start; const uint32_t* blk_hist; const uint32_t* blk_low; const uint32_t* blk_dlim; const int32_t* src_len;
+  uint8_t* dst; const uint64_t* dst_off; const int32_t* dst_cap; int32_t* out;
+  const uint64_t* buf_off; const uint64_t* buf_len; const uint32_t* end_first; const uint32_t* ends; const uint32_t* items; uint32_t* queue;
+  uint64_t span; uint32_t n_blocks, n_streams, n_ends, n_items, seg;
+};
+// hc_build_stream_kernel (one wavefront per CU: the 128 KB head table) + hc_parse_stream_kernel (a wavefront per block)
+int launch_compress_hc_stream(const HcStreamArgs& a, int level, void* ws, uint32_t n_cus, void* stream);
 // The decoded-size query: out[i] = the value LZ4_decompress_safe would return for block i with capacity a.dst_cap[i] (-1 where it or
 // src_len[i] is negative); a.dst and a.dst_off are ignored (may be nullptr) and no output buffer exists.  decode_size_kernel<4, 2048, true>:
 // a wavefront per block; no route word, no sampler, no decode knob

@@ -21,6 +21,7 @@
 // Backend W: wave_dev.h on the GPU, tests/hostsim/wave_host.h in the CPU test-suite.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 #include "lz4_fast_core.h"  // LZ4HIP_DEV, ctz64
 
 #ifndef LZ4HIP_DEV
@@ -68,13 +69,21 @@ constexpr int HC_OPT_INTS = 4 * (HC_OPT_NUM + HC_OPT_TRAILING);  // per-block wo
 // positions in front of it -- the caller starts the run up to 65535 positions early -- only warm the head table up: every link a
 // position >= store_from can store has a distance of at most 65535, so its entry is the one a build from the buffer's start stores.
 // SEG = false is what every other instantiation uses: the code it generates does not change.
-template <class W, bool DICT = false, bool SEG = false>
+// RUNS (on top of SEG: a stream whose sources land anywhere, laid out in liblz4's index space, hc_build_stream_kernel): `ends` are the
+// n_ends positions, ascending and counted from the buffer's start, at which a jump ended a contiguous run; src[0] is the buffer's
+// position pos0.  liblz4 never inserts the last three positions of such a run (LZ4HC_setExternalDict inserts up to end - 4 and moves
+// nextToUpdate past the rest): a position p with p + 4 > its run's end stores 0 and does not enter the head table.  The cursor over
+// `ends` is wave-uniform and lives in a register (run_runs, a loop of its own).  RUNS = false is what every other instantiation uses: the
+// code it generates does not change.
+template <class W, bool DICT = false, bool SEG = false, bool RUNS = false>
 struct HcBuild {
   using VU = typename W::VU;
   using VU64 = typename W::VU64;
   using VB = typename W::VB;
 
-  LZ4HIP_DEV static void run(W& w, const uint8_t* src, uint32_t n, uint16_t* delta, uint32_t first = HC_BIAS, uint32_t store_from = 0u) {
+  LZ4HIP_DEV static void run(W& w, const uint8_t* src, uint32_t n, uint16_t* delta, uint32_t first = HC_BIAS, uint32_t store_from = 0u,
+                             const uint32_t* ends = nullptr, uint32_t n_ends = 0u, uint32_t pos0 = 0u) {
+    if constexpr (RUNS) return run_runs(w, src, n, delta, store_from, ends, n_ends, pos0);
     if (n < 4u) return;
     const uint32_t last = n - 4u;  // last position whose 4-byte hash is readable
     const uint32_t bias = DICT ? first : HC_BIAS;
@@ -126,6 +135,93 @@ struct HcBuild {
       }
     }
   }
+
+  // RUNS: the same loop with the cursor over the run ends.  (A function of its own, so that run() above keeps the text -- and every other
+  // instantiation the instructions -- it had.)
+  LZ4HIP_DEV static void run_runs(W& w, const uint8_t* src, uint32_t n, uint16_t* delta, uint32_t store_from, const uint32_t* ends, uint32_t n_ends,
+                                  uint32_t pos0) {
+    if (n < 4u) return;
+    // (RUNS) the cursor: `next` is the first run end behind the step at hand, as a position of this run (none: all ones).  It lives in a
+    // register; `ends` is read only when the cursor moves, so a step with no end in reach costs one scalar compare
+    uint32_t cur = 0u, next = 0xFFFFFFFFu;
+    if constexpr (RUNS) {
+      while (cur < n_ends && ends[cur] <= pos0) cur++;
+      if (cur < n_ends) next = ends[cur] - pos0;
+    }
+    const uint32_t last = n - 4u;  // last position whose 4-byte hash is readable
+    const uint32_t bias = HC_BIAS;
+    if constexpr (!DICT) w.template lds_fill<true>(32768u, 0u);
+    w.sync();
+    const VU j = w.lane();
+    // The input words of a step do not depend on the table: they are requested one group of U steps ahead, so the only
+    // latency left in a step is the LDS round trip (one wavefront per CU runs here -- the 128 KB head table -- and nothing
+    // else would hide a global load).
+    constexpr uint32_t U = 4u;
+    VU xn[U];
+    for (uint32_t u = 0; u < U; u++) xn[u] = w.ldu32(src, W::vmin(j + u * 64u, last));
+    for (uint32_t g0 = 0; g0 <= last; g0 += 64u * U) {
+      VU x[U];
+      for (uint32_t u = 0; u < U; u++) x[u] = xn[u];
+      for (uint32_t u = 0; u < U; u++) xn[u] = w.ldu32(src, W::vmin(j + (g0 + 64u * U + u * 64u), last));
+      // (RUNS) the group's steps come twice: NEAR = true looks for the run ends in reach of each step, NEAR = false is the plain SEG
+      // step.  A group with no end in reach -- every group of a stream that never jumps -- takes the plain one: one scalar compare per group
+      auto steps = [&](auto near_tag) {
+      constexpr bool NEAR = decltype(near_tag)::value;
+      for (uint32_t u = 0; u < U; u++) {
+        const uint32_t p0 = g0 + u * 64u;
+        if (p0 > last) break;
+        const VU p = j + p0;
+        VB valid = p <= last;
+        if constexpr (NEAR) {   // (an end e concerns the step's positions [p0, p0 + 63] when p0 < e <= p0 + 66)
+          while (next <= p0) { cur++; next = cur < n_ends ? ends[cur] - pos0 : 0xFFFFFFFFu; }
+          if (next <= p0 + 66u) {
+            uint32_t e = next;
+            for (uint32_t k = cur;;) {
+              valid = valid & !((p + 3u >= VU(e)) & (p < VU(e)));
+              if (++k >= n_ends || ends[k] - pos0 > p0 + 66u) break;
+              e = ends[k] - pos0;
+            }
+          }
+        }
+        const VU idx = p + bias;
+        const VU h = (x[u] * 2654435761u) >> 17;
+        // ONE LDS round trip per step: the atomic max returns the bucket's value right before this lane's insert.  The lanes of
+        // an instruction execute in some order; if the lanes sharing a bucket happened to go in rising position order, every
+        // returned value already is the previous occurrence.  If not, the lane that went too late got back a position ABOVE its
+        // own -- that flags the bucket, and its group is put in order with ballots below.
+        const VU old = w.template lds_max<true>(h, idx, valid);
+        VU prev = old;
+        uint64_t pend = w.ballot(valid & (old > idx));
+        while (pend) {
+          const int d = ctz64(pend);
+          const uint32_t hd = w.bcast(h, d);
+          const VB grp = valid & (h == hd);
+          const uint64_t gm = w.ballot(grp);
+          const VU64 lower = w.lanemask_lt() & VU64(gm);
+          const VB has = grp & (lower != VU64(0));
+          const VU srcl = VU(63u) - W::clz64(lower);
+          // the group's first lane takes what the bucket held before this step: the value the lane that executed first got back
+          const uint64_t fm = w.ballot(grp & (old < p0 + bias));
+          const uint32_t before = w.bcast(old, ctz64(fm));
+          prev = W::select(has, w.template shfl_e<true>(idx, srcl), W::select(grp, VU(before), prev));
+          pend &= ~gm;
+        }
+        const VU dist = idx - prev;
+        if constexpr (NEAR) w.st16(delta, p, W::select((dist > (uint32_t)HC_MAXD) | !valid, VU(0u), dist), (p <= last) & (p >= store_from));
+        else if constexpr (SEG) w.st16(delta, p, W::select(dist > (uint32_t)HC_MAXD, VU(0u), dist), valid & (p >= store_from));
+        else w.st16(delta, p, W::select(dist > (uint32_t)HC_MAXD, VU(0u), dist), valid);
+        w.sync();
+      }
+      };
+      if constexpr (RUNS) {
+        while (next <= g0) { cur++; next = cur < n_ends ? ends[cur] - pos0 : 0xFFFFFFFFu; }   // (an end at or below g0 concerns no step of the group)
+        if (next <= g0 + 64u * U + 2u) steps(std::true_type{});
+        else steps(std::false_type{});
+      } else {
+        steps(std::false_type{});
+      }
+    }
+  }
 };
 
 // One build item of a chain of linked blocks: segment k (`seg` positions, 4096 .. 2^30) of the chain's buffer buf[0, len) -- its kept
@@ -140,6 +236,18 @@ LZ4HIP_DEV void hc_chain_build_segment(W& w, const uint8_t* buf, uint64_t len, u
   const uint64_t warm = from > (uint64_t)HC_MAXD ? from - (uint64_t)HC_MAXD : 0ull;
   const uint64_t end = from + seg < len - 3u ? from + seg : len - 3u;   // one past the segment's last position
   HcBuild<W, false, true>::run(w, buf + warm, (uint32_t)(end + 3u - warm), delta + warm, HC_BIAS, (uint32_t)(from - warm));
+}
+
+// The same item for a stream whose sources land anywhere: buf[0, len) is the stream's linear buffer (host_staging.h HcsImage: the kept
+// external piece, the kept prefix piece, the call's blocks, in index order), `ends` its run ends.
+template <class W>
+LZ4HIP_DEV void hc_stream_build_segment(W& w, const uint8_t* buf, uint64_t len, uint32_t seg, uint32_t k, uint16_t* delta, const uint32_t* ends,
+                                        uint32_t n_ends) {
+  const uint64_t from = (uint64_t)k * seg;
+  if (len < 4u || from > len - 4u) return;
+  const uint64_t warm = from > (uint64_t)HC_MAXD ? from - (uint64_t)HC_MAXD : 0ull;
+  const uint64_t end = from + seg < len - 3u ? from + seg : len - 3u;
+  HcBuild<W, false, true, true>::run(w, buf + warm, (uint32_t)(end + 3u - warm), delta + warm, HC_BIAS, (uint32_t)(from - warm), ends, n_ends, (uint32_t)warm);
 }
 
 // The dictionary's part of the chain (LZ4_loadDictHC), the same for every record of every batch at every level: delta[] over the
@@ -177,8 +285,23 @@ template <> struct HcDictRef<true> {
 // history, then the block -- and positions count from there.  A candidate in the history is an ordinary candidate; the one thing the
 // search itself does differently is that pattern analysis counts backward no further than the lowest index allows (the result is
 // cut to it anyway: a long run in the history is not walked to its start).
+//
+// DICT and PREFIX together (a block of a stream whose sources land anywhere, liblz4's external-dictionary mode as LZ4_compress_HC_continue
+// reaches it after a jump): `src` is the start of the block's VIEW of its stream's linear buffer -- liblz4's own index space, in which the
+// kept external piece [low, dlim) lies directly in front of the prefix [dlim, ...), so a match that runs to the external piece's end goes
+// on at the prefix's start by an ordinary forward count.  What the search does differently from the prefix search: the lowest index is
+// max(low, ip - 65535); a candidate below dlim has no 2-byte pre-test, is no match with fewer than four bytes left in front of dlim
+// (liblz4 reads past the dictionary's end there, the rule of dict_candidate above) and extends backward to `low`, one at or above dlim
+// to dlim; the three positions in front of dlim are no chain members (their entry reads 0, LZ4HC_protectDictEnd keeps pattern
+// analysis off them).  HcDictRef's members are unused here.
+template <bool LIN> struct HcLinRef {};
+template <> struct HcLinRef<true> {
+  int low = 0;    // liblz4's lowLimit as a position of the view
+  int dlim = 0;   // liblz4's dictLimit: where the prefix begins, low <= dlim <= the block's start
+};
+
 template <bool DICT = false, bool PREFIX = false>
-struct HcSearchT : HcDictRef<DICT> {
+struct HcSearchT : HcDictRef<DICT>, HcLinRef<DICT && PREFIX> {
   const uint8_t* src;
   const uint16_t* delta;
   int nb_searches;
@@ -216,6 +339,7 @@ struct HcSearchT : HcDictRef<DICT> {
 
   // best match for position ip that may start as early as ilow; returns the length, updates mpos/spos
   LZ4HIP_DEV int wider(int ip, int ilow, int ihigh, int longest, int& mpos, int& spos) const {
+    if constexpr (DICT && PREFIX) return wider_lin(ip, ilow, ihigh, longest, mpos, spos);
     if constexpr (DICT) return wider_dict(ip, ilow, ihigh, longest, mpos, spos);
     const uint32_t ip_idx = (uint32_t)ip + HC_BIAS;
     const uint32_t lowest = (HC_BIAS + 65536u > ip_idx) ? HC_BIAS : ip_idx - (uint32_t)HC_MAXD;
@@ -500,6 +624,144 @@ struct HcSearchT : HcDictRef<DICT> {
       return longest;
     }
   }
+
+  // ---- DICT and PREFIX: the same search over a stream's linear buffer (HcLinRef) ------------------------------------------------
+  LZ4HIP_DEV int lin_low() const {
+    if constexpr (DICT && PREFIX) return this->low;
+    else return 0;
+  }
+  LZ4HIP_DEV int lin_dlim() const {
+    if constexpr (DICT && PREFIX) return this->dlim;
+    else return 0;
+  }
+  // liblz4's lowestMatchIndex for the search at view position ip
+  LZ4HIP_DEV uint32_t lowest_lin(int ip) const {
+    const uint32_t ip_idx = (uint32_t)ip + HC_BIAS, low_idx = (uint32_t)lin_low() + HC_BIAS;
+    return (low_idx + 65536u > ip_idx) ? low_idx : ip_idx - (uint32_t)HC_MAXD;
+  }
+  // liblz4's chainTable entry of index mi: 0 for the three positions in front of dlim, which a jump left uninserted
+  LZ4HIP_DEV uint32_t chain_lin(uint32_t mi) const {
+    const int p = (int)(mi - HC_BIAS);
+    if (p < lin_dlim() && p >= lin_dlim() - 3) return 0u;
+    const uint32_t d = delta[p];
+    return d ? d : (uint32_t)HC_MAXD;
+  }
+  // LZ4HC_protectDictEnd
+  LZ4HIP_DEV bool protect_lin(uint32_t mi) const { return (uint32_t)(((uint32_t)lin_dlim() + HC_BIAS - 1u) - mi) >= 3u; }
+  // the candidate at view position c for the search at ip, against the running `longest`: match length (0: none, or the 2-byte
+  // pre-test of a prefix candidate fails) and the backward extension (<= 0)
+  LZ4HIP_DEV int lin_candidate(int ip, int ilow, int ihigh, int c, uint32_t pattern, int longest, int& back) const {
+    back = 0;
+    const int dl = lin_dlim();
+    if (c >= dl) {
+      const uint32_t c32 = hc_rd32(src + c);
+      const int look_back = ip - ilow;
+      if (hc_rd16(src + ilow + longest - 1) != hc_rd16(src + c - look_back + longest - 1) || c32 != pattern) return 0;
+      const int room = c - dl;
+      const int mn = -(look_back < room ? look_back : room);
+      while (back > mn && src[ip + back - 1] == src[c + back - 1]) back--;
+    } else {
+      if (dl - c < 4 || hc_rd32(src + c) != pattern) return 0;
+      const int room = c - lin_low();
+      const int mn = -((ip - ilow) < room ? (ip - ilow) : room);
+      while (back > mn && src[ip + back - 1] == src[c + back - 1]) back--;
+    }
+    return 4 + count_fwd(src, ip + 4, c + 4, ihigh) - back;
+  }
+
+  LZ4HIP_DEV int wider_lin(int ip, int ilow, int ihigh, int longest, int& mpos, int& spos) const {
+    const uint32_t ip_idx = (uint32_t)ip + HC_BIAS;
+    const uint32_t dl_idx = (uint32_t)lin_dlim() + HC_BIAS;
+    const uint32_t lowest = lowest_lin(ip);
+    const int look_back = ip - ilow;
+    int attempts = nb_searches;
+    const uint32_t pattern = hc_rd32(src + ip);
+    int repeat = 0;  // 0 untested, 1 not, 2 confirmed
+    int src_pat_len = 0;
+    uint32_t mi;
+    {
+      const uint32_t d0 = delta[ip];
+      mi = d0 ? ip_idx - d0 : 0u;
+    }
+    uint32_t chain_pos = 0;
+    while (mi >= lowest && attempts > 0) {
+      attempts--;
+      const int mp = (int)(mi - HC_BIAS);
+      const uint32_t dist_next = chain_lin(mi);
+      int back;
+      const int ml = lin_candidate(ip, ilow, ihigh, mp, pattern, longest, back);
+      if (ml > longest) { longest = ml; mpos = mp + back; spos = ip + back; }
+      if (chain_swap && ml == longest) {
+        if (mi + (uint32_t)longest <= ip_idx) {
+          uint32_t dist_to_next = 1;
+          const int end = longest - 4 + 1;
+          int step = 1, accel = 1 << 4;
+          for (int pos = 0; pos < end; pos += step) {
+            const uint32_t cd = chain_lin(mi + (uint32_t)pos);
+            step = (accel++ >> 4);
+            if (cd > dist_to_next) { dist_to_next = cd; chain_pos = (uint32_t)pos; accel = 1 << 4; }
+          }
+          if (dist_to_next > 1) {
+            if (dist_to_next > mi) break;
+            mi -= dist_to_next;
+            continue;
+          }
+        }
+      }
+      if (pattern_analysis && dist_next == 1u && chain_pos == 0u) {
+        const uint32_t cand = mi - 1u;
+        if (repeat == 0) {
+          if (((pattern & 0xFFFFu) == (pattern >> 16)) & ((pattern & 0xFFu) == (pattern >> 24))) {
+            repeat = 2;
+            src_pat_len = count_pattern(src, ip + 4, ihigh, pattern) + 4;
+          } else {
+            repeat = 1;
+          }
+        }
+        if (repeat == 2 && cand >= lowest && protect_lin(cand)) {
+          const int cp = (int)(cand - HC_BIAS);
+          // (a confirmed pattern is four equal bytes: liblz4's rotation of it where a count crosses dlim is the identity, and both of
+          // its counts -- forward through the external piece's end into the prefix, backward through the prefix's start into the
+          // external piece -- are plain counts over the linear buffer, the backward one down to `low`, then cut to the lowest index)
+          if (hc_rd32(src + cp) == pattern) {
+            const int fwd = count_pattern(src, cp + 4, ihigh, pattern) + 4;
+            int back = reverse_count_pattern(src, cp, (int)(lowest - HC_BIAS), pattern);
+            {
+              const uint32_t far = cand - (uint32_t)back;
+              back = (int)(cand - (far > lowest ? far : lowest));
+            }
+            const int cur = back + fwd;
+            if (cur >= src_pat_len && fwd <= src_pat_len) {
+              const uint32_t nmi = cand + (uint32_t)fwd - (uint32_t)src_pat_len;
+              mi = protect_lin(nmi) ? nmi : dl_idx;
+            } else {
+              const uint32_t nmi = cand - (uint32_t)back;
+              if (!protect_lin(nmi)) {
+                mi = dl_idx;
+              } else {
+                mi = nmi;
+                if (look_back == 0) {
+                  const int max_ml = cur < src_pat_len ? cur : src_pat_len;
+                  if (longest < max_ml) {
+                    if (ip_idx - mi > (uint32_t)HC_MAXD) break;
+                    longest = max_ml;
+                    mpos = (int)(mi - HC_BIAS);
+                    spos = ip;
+                  }
+                  const uint32_t d = chain_lin(mi);
+                  if (d > mi) break;
+                  mi -= d;
+                }
+              }
+            }
+            continue;
+          }
+        }
+      }
+      mi -= chain_pos == 0u ? dist_next : chain_lin(mi + chain_pos);
+    }
+    return longest;
+  }
 };
 using HcSearch = HcSearchT<false>;
 
@@ -560,6 +822,7 @@ struct HcParse : HcPrefixRef<PREFIX> {
   // start before ip) -- so the nodes that could improve are replayed in chain order against the running `longest`.
   // Repeated-byte patterns (level 9's pattern analysis may then jump along the chain) take the serial walk.
   LZ4HIP_DEV int wider_wave(int ip, int ilow, int ihigh, int longest, int& mpos, int& spos) {
+    if constexpr (DICT && PREFIX) return wider_wave_lin(ip, ilow, ihigh, longest, mpos, spos);
     if constexpr (DICT) return wider_wave_dict(ip, ilow, ihigh, longest, mpos, spos);
     const uint32_t pattern = hc_rd32(src + ip);
     const bool rep = ((pattern & 0xFFFFu) == (pattern >> 16)) & ((pattern & 0xFFu) == (pattern >> 24));
@@ -680,6 +943,75 @@ struct HcParse : HcPrefixRef<PREFIX> {
     }
     return L;
   }
+  // DICT and PREFIX: wider_wave over a stream's linear buffer.  A node below dlim has no 2-byte pre-test.
+  LZ4HIP_DEV int wider_wave_lin(int ip, int ilow, int ihigh, int longest, int& mpos, int& spos) {
+    const uint32_t pattern = hc_rd32(src + ip);
+    const bool rep = ((pattern & 0xFFFFu) == (pattern >> 16)) & ((pattern & 0xFFu) == (pattern >> 24));
+    if (s.pattern_analysis && rep) return s.wider(ip, ilow, ihigh, longest, mpos, spos);
+    const uint32_t ip_idx = (uint32_t)ip + HC_BIAS;
+    const uint32_t lowest = s.lowest_lin(ip);
+    const int look_back = ip - ilow;
+    const int dl = s.lin_dlim();
+    const uint8_t* const sp = src;
+    const Search& sr = s;
+    int attempts = s.nb_searches;
+    uint32_t mi;
+    {
+      const uint32_t d0 = s.delta[ip];
+      mi = d0 ? ip_idx - d0 : 0u;
+    }
+    int L = longest;
+    const VU lane = w.lane();
+    while (mi >= lowest && attempts > 0) {
+      VU node = VU(0u);
+      uint32_t cnt = 0;
+      while (mi >= lowest && attempts > 0 && cnt < 64u) {
+        attempts--;
+        node = w.set_lane(node, (int)cnt, mi - HC_BIAS);
+        cnt++;
+        mi -= s.chain_lin(mi);
+      }
+      const int L0 = L;
+      const VU64 res = w.map_lanes64v(node, lane < cnt, [&](uint32_t, uint32_t cu, bool a) -> uint64_t {
+        if (!a) return 0ull;
+        const int c = (int)cu;
+        if (c < dl) {
+          int back;
+          const int ml = sr.lin_candidate(ip, ilow, ihigh, c, pattern, 3, back);
+          return ml ? ((uint64_t)(uint32_t)ml << 32) | ((uint64_t)(uint32_t)(-back) << 1) | 1u : 0ull;
+        }
+        if (hc_rd32(sp + c) != pattern) return 0ull;
+        int back = 0;
+        if (look_back) {
+          const int room = c - dl;
+          const int mn = -(look_back < room ? look_back : room);
+          while (back > mn && sp[ip + back - 1] == sp[c + back - 1]) back--;
+        }
+        const int ml = 4 + Search::count_fwd(sp, ip + 4, c + 4, ihigh) - back;
+        const uint32_t pre0 = (hc_rd16(sp + ilow + L0 - 1) == hc_rd16(sp + c - look_back + L0 - 1)) ? 1u : 0u;
+        return ((uint64_t)(uint32_t)ml << 32) | ((uint64_t)(uint32_t)(-back) << 1) | pre0;
+      });
+      uint64_t imp = w.ballot(W::lo32(res >> 32) > (uint32_t)L);
+      while (imp) {
+        const int l = ctz64(imp);
+        imp &= imp - 1u;
+        const uint64_t r = w.bcast64(res, l);
+        const int ml = (int)(uint32_t)(r >> 32);
+        if (ml <= L) continue;
+        const int c = (int)w.bcast(node, l);
+        const bool pass = (c < dl || L == L0) ? (r & 1u) != 0u : hc_rd16(sp + ilow + L - 1) == hc_rd16(sp + c - look_back + L - 1);
+        if (pass) {
+          const int back = -(int)((uint32_t)r >> 1);
+          L = ml; mpos = c + back; spos = ip + back;
+        }
+      }
+    }
+    return L;
+  }
+  // DICT and PREFIX: where the external piece [low, dlim) lies in the block's view
+  LZ4HIP_DEV void set_lin(int low, int dlim) {
+    if constexpr (DICT && PREFIX) { s.low = low; s.dlim = dlim; }
+  }
   LZ4HIP_DEV int dict_k() const {
     if constexpr (DICT) return s.K;
     else return 0;
@@ -757,6 +1089,11 @@ struct HcParse : HcPrefixRef<PREFIX> {
         if (p > mflimit) return 0ull;
         const uint32_t d = sr.delta[p];
         if (d == 0u) return 0ull;
+        if constexpr (DICT && PREFIX) {   // (sure only for a node at or above the lowest index; one below dlim is a chain member: four bytes in front of dlim at least)
+          const int c = p - (int)d;
+          if (c < 0 || (uint32_t)c + HC_BIAS < sr.lowest_lin(p)) return 0ull;
+          return hc_rd32(sr.src + c) == hc_rd32(sr.src + p) ? 1ull : 0ull;
+        } else
         if constexpr (DICT) {   // (a link into the dictionary ends on a chain member: four bytes before its end at least)
           if ((int)d > p) return hc_rd32(sr.dend + (p - (int)d)) == hc_rd32(sr.src + p) ? 1ull : 0ull;
         }
@@ -1034,6 +1371,21 @@ template <class W>
 LZ4HIP_DEV int hc_chain_parse_block(W& w, const uint8_t* buf, uint32_t hist, int n, const uint16_t* delta, uint8_t* dst, int cap, int level, int* opt) {
   HcParse<W, false, false, true> p(w, buf, (int)hist + n, delta, dst, cap, level);
   p.set_history((int)hist);
+  return level >= 10 ? p.run_opt(level, opt) : p.run();
+}
+
+// One block of a stream whose sources land anywhere: n bytes at view + hist, behind hist = min(65536, what the stream's linear buffer
+// holds in front of it) bytes; low <= dlim <= hist are liblz4's lowLimit and dictLimit as positions of the view (cut to its start);
+// delta = the buffer's delta[] at the view (hc_stream_build_segment).  -> LZ4_compress_HC_continue's return value
+template <class W>
+LZ4HIP_DEV int hc_stream_parse_block(W& w, const uint8_t* view, uint32_t hist, uint32_t low, uint32_t dlim, int n, const uint16_t* delta, uint8_t* dst,
+                                     int cap, int level, int* opt) {
+  // (dlim == 0: the prefix begins where the view begins -- a stream that has not jumped within reach, or one behind LZ4_saveDictHC.  Every
+  // rule of the linear search then says what the prefix search says: the lowest index, the backward limit, no position in front of dlim)
+  if (dlim == 0u) return hc_chain_parse_block(w, view, hist, n, delta, dst, cap, level, opt);
+  HcParse<W, false, true, true> p(w, view, (int)hist + n, delta, dst, cap, level);
+  p.set_history((int)hist);
+  p.set_lin((int)low, (int)dlim);
   return level >= 10 ? p.run_opt(level, opt) : p.run();
 }
 

@@ -13,6 +13,8 @@
 //   CompressStreams                                 =  LZ4_compress_fast_continue on streams that go on from call to call: ONE LZ4_stream_t each,
 //                                                      its state resident on the device (LZ4_saveDict through chainPrefixLen)
 //   LZ4HIPBatch::compressHCChain                    =  LZ4_compress_HC_continue over chains of linked blocks (prefix mode; not serial)
+//   LZ4HIPBatch::compressHCStream, CompressStreamsHC =  LZ4_compress_HC_continue on streams whose sources land anywhere (rings, alternating
+//                                                      buffers, save areas with LZ4_saveDictHC, dictionaries elsewhere): ONE LZ4_streamHC_t each
 //   LZ4HIPBatch::decompressSafeChain                =  LZ4_decompress_safe_continue over chains of linked blocks (liblz4's rolling-prefix
 //                                                      mode; no reference entry reaches it)
 //   LZ4HIPBatch::decompressSafeStream, DecodeStreams =  LZ4_decompress_safe_continue on streams whose blocks land anywhere (rings, alternating
@@ -400,6 +402,41 @@ struct LZ4HIPBatch {
                                           n ? lengths.data() : &none, (uint32_t)n, (uint32_t)nc, level));
     return lengths;
   }
+  // LZ4_compress_HC_continue on streams whose sources land anywhere -- a ring that wraps, alternating buffers, a save area, a dictionary
+  // elsewhere (lz4hip_compress_hc_stream_batch): stream c is the blocks [chainFirst[c], chainFirst[c + 1]) of this call, block i is
+  // src[srcOff[i], + srcLen[i]) and owns the slot dest[destOff[i], + maxDestLen[i]).  state[c] is liblz4's bookkeeping as offsets into src
+  // -- all zero: a fresh stream -- read and written back.  -> liblz4's return value per block (0: it did not fit, which does not end the
+  // stream).  A call is a snapshot of src; the header states the exceptions to byte equality
+  static std::vector<int32_t> compressHCStream(std::vector<lz4hip_hcstream_state>& state, const bytes& src, const std::vector<uint64_t>& srcOff,
+                                               const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst, bytes& dest,
+                                               const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen, int level = 9) {
+    const size_t n = srcOff.size(), nc = state.size();
+    if (srcLen.size() != n || destOff.size() != n || maxDestLen.size() != n) throw std::invalid_argument("per-block arrays differ in length");
+    if (chainFirst.size() != nc + 1) throw std::invalid_argument("per-stream arrays differ in length");
+    if (chainFirst[0] != 0 || chainFirst[nc] != n) throw std::invalid_argument("chainFirst must ascend from 0 to the number of blocks");
+    for (size_t c = 0; c < nc; c++) {
+      if (chainFirst[c] > chainFirst[c + 1]) throw std::invalid_argument("chainFirst must ascend from 0 to the number of blocks");
+      const lz4hip_hcstream_state& s = state[c];
+      if (s.prefix_len > s.prefix_end || s.ext_len > s.ext_end || (s.prefix_len && s.prefix_end > src.size()) || (s.ext_len && s.ext_end > src.size()))
+        throw std::out_of_range("history of stream " + std::to_string(c));
+    }
+    for (size_t i = 0; i < n; i++) {
+      const uint64_t len = srcLen[i] >= 0 && srcLen[i] <= 0x7E000000 ? (uint64_t)srcLen[i] : 0u;   // (any other length reads nothing: the engine's rule)
+      if (srcOff[i] > src.size() || len > src.size() - srcOff[i]) throw std::out_of_range("source " + std::to_string(i));
+      const uint64_t cap = maxDestLen[i] > 0 ? (uint64_t)maxDestLen[i] : 0u;
+      if (destOff[i] > dest.size() || cap > dest.size() - destOff[i]) throw std::out_of_range("slot " + std::to_string(i));
+    }
+    std::vector<int32_t> lengths(n, 0);
+    bytes one(1);                                 // (an empty buffer still hands the library a pointer)
+    int32_t none = 0;
+    uint64_t none64 = 0;
+    lz4hip_hcstream_state none_state{0, 0, 0, 0, 0};
+    status(lz4hip_compress_hc_stream_batch(nc ? state.data() : &none_state, src.empty() ? one.data() : src.data(), n ? srcOff.data() : &none64,
+                                           n ? srcLen.data() : &none, chainFirst.data(), dest.empty() ? one.data() : dest.data(),
+                                           n ? destOff.data() : &none64, n ? maxDestLen.data() : &none, n ? lengths.data() : &none, (uint32_t)n,
+                                           (uint32_t)nc, level));
+    return lengths;
+  }
   // the argument checks of the two chain compressors
   static void checkChains(const bytes& src, const std::vector<uint64_t>& chainSrcOff, const std::vector<int32_t>& srcLen,
                           const std::vector<uint32_t>& chainFirst, const bytes& dest, const std::vector<uint64_t>& destOff,
@@ -590,6 +627,52 @@ class DecodeStreams {
 
  private:
   std::vector<lz4hip_dstream_state> state_;
+};
+
+// The states of n HC compress streams whose sources land anywhere: per stream what an LZ4_streamHC_t of liblz4 keeps beside its tables,
+// as offsets into the one source its caller compresses from.  Plain host data: nothing on a device, nothing to destroy.  compress(): the
+// arrays of LZ4HIPBatch::compressHCStream at the set's level, and chain c of the call is the next run of blocks of stream streamId[c]
+// (distinct ids).  Every stream gives, over all the calls that name it, the values ONE LZ4_streamHC_t gives, however its blocks are cut
+// into calls (include/lz4hip.h states the exceptions).
+class CompressStreamsHC {
+ public:
+  explicit CompressStreamsHC(uint32_t n, int level = 9) : level_(level), state_(n, lz4hip_hcstream_state{0, 0, 0, 0, 0}) {
+    if (!n) throw std::invalid_argument("a set has at least one stream");
+  }
+  uint32_t size() const { return (uint32_t)state_.size(); }
+  int level() const { return level_; }
+  // LZ4_loadDictHC: the stream is fresh behind the dictLen bytes of dictionary that end at src[dictEnd]
+  void loadDict(uint32_t streamId, uint64_t dictEnd, uint64_t dictLen) {
+    if (dictLen > dictEnd) throw std::out_of_range("history of stream " + std::to_string(streamId));
+    LZ4HIPBatch::status(lz4hip_hcstream_load_dict(&state_.at(streamId), dictEnd, dictLen));
+  }
+  // LZ4_saveDictHC for the caller who has copied the last k bytes the stream consumed to src[bufOff ..] -> the bytes kept
+  int saveDict(uint32_t streamId, uint64_t bufOff, int k) {
+    const int kept = lz4hip_hcstream_save_dict(&state_.at(streamId), bufOff, k);
+    if (kept < 0) LZ4HIPBatch::status(kept);
+    return kept;
+  }
+  void reset() { for (lz4hip_hcstream_state& s : state_) s = lz4hip_hcstream_state{0, 0, 0, 0, 0}; }
+  void reset(const std::vector<uint32_t>& streamId) { for (uint32_t c : streamId) state_.at(c) = lz4hip_hcstream_state{0, 0, 0, 0, 0}; }
+  const lz4hip_hcstream_state& state(uint32_t streamId) const { return state_.at(streamId); }
+  std::vector<int32_t> compress(const std::vector<uint32_t>& streamId, const bytes& src, const std::vector<uint64_t>& srcOff,
+                                const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst, bytes& dest,
+                                const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen) {
+    std::vector<lz4hip_hcstream_state> st;
+    std::vector<uint8_t> seen(state_.size(), 0);
+    for (uint32_t c : streamId) {
+      if (c >= state_.size() || seen[c]) throw std::invalid_argument("streamId must be distinct and below the number of streams");
+      seen[c] = 1;
+      st.push_back(state_[c]);
+    }
+    std::vector<int32_t> r = LZ4HIPBatch::compressHCStream(st, src, srcOff, srcLen, chainFirst, dest, destOff, maxDestLen, level_);
+    for (size_t k = 0; k < streamId.size(); k++) state_[streamId[k]] = st[k];
+    return r;
+  }
+
+ private:
+  int level_;
+  std::vector<lz4hip_hcstream_state> state_;
 };
 
 class LZ4FastDecompressor {

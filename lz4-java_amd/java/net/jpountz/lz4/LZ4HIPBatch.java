@@ -526,6 +526,146 @@ public final class LZ4HIPBatch {
   }
 
   /**
+   * liblz4's {@code LZ4_compress_HC_continue} on streams whose sources land anywhere -- a ring that wraps, two alternating block buffers, a
+   * save area kept with {@code LZ4_saveDictHC}, a dictionary elsewhere.  Stream c is the blocks {@code chainFirst[c] .. chainFirst[c+1]-1}
+   * of this call; block i is {@code src[srcOff[i], srcOff[i]+srcLen[i])} and owns the slot {@code dest[destOff[i], destOff[i]+destCap[i])}.
+   * {@code state} holds five longs per stream -- prefixEnd, prefixLen, extEnd, extLen, index, offsets into src; all zero is a fresh
+   * stream -- and is read and written back.  outLen[i] = liblz4's return value; 0 (it did not fit) does not end the stream.  A call is a
+   * snapshot of src; include/lz4hip.h states the contract and its exceptions.  {@link CompressStreamsHC} keeps the states for its caller.
+   */
+  public static void compressHCStream(long[] state, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest,
+      long[] destOff, int[] destCap, int[] outLen, int level) {
+    final int n = srcOff.length, nc = chainFirst.length - 1;
+    if (srcLen.length != n || destOff.length != n || destCap.length != n || outLen.length != n) {
+      throw new IllegalArgumentException("per-block arrays differ in length");
+    }
+    if (nc < 0 || state.length != 5 * nc) {
+      throw new IllegalArgumentException("per-stream arrays differ in length");
+    }
+    if (!src.isDirect() || !dest.isDirect()) {
+      throw new IllegalArgumentException("direct buffers required");
+    }
+    if (dest.isReadOnly()) {
+      throw new java.nio.ReadOnlyBufferException();
+    }
+    for (int i = 0; i < n; i++) {
+      final long len = srcLen[i] >= 0 && srcLen[i] <= 0x7E000000 ? srcLen[i] : 0;   // (any other length reads nothing: the engine's rule)
+      if (srcOff[i] < 0 || srcOff[i] + len > src.capacity()) {
+        throw new ArrayIndexOutOfBoundsException("block " + i);
+      }
+      if (destOff[i] < 0 || destOff[i] + Math.max(destCap[i], 0) > dest.capacity()) {
+        throw new ArrayIndexOutOfBoundsException("slot " + i);
+      }
+    }
+    if (chainFirst[0] != 0 || chainFirst[nc] != n) {
+      throw new IllegalArgumentException("chainFirst must ascend from 0 to the number of blocks");
+    }
+    for (int c = 0; c < nc; c++) {
+      if (chainFirst[c] > chainFirst[c + 1]) {
+        throw new IllegalArgumentException("chainFirst must ascend from 0 to the number of blocks");
+      }
+      final long pe = state[5 * c], pl = state[5 * c + 1], ee = state[5 * c + 2], el = state[5 * c + 3];
+      if (pl < 0 || el < 0 || pl > pe || el > ee || (pl > 0 && pe > src.capacity()) || (el > 0 && ee > src.capacity()) || state[5 * c + 4] < 0) {
+        throw new ArrayIndexOutOfBoundsException("history of stream " + c);
+      }
+    }
+    final int rc = LZ4HIPJNI.LZ4HIP_batchHCStream(state, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, outLen, n, nc, level);
+    if (rc != 0) {
+      throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /**
+   * The states of n HC compress streams whose sources land anywhere: per stream what an {@code LZ4_streamHC_t} of liblz4 keeps beside
+   * its tables, as offsets into the one source its caller compresses from.  Plain host data: nothing on a device, nothing to close.
+   * Every stream gives, over all the calls that name it, the values ONE {@code LZ4_streamHC_t} gives, however its blocks are cut into
+   * calls.  {@code loadDict} and {@code saveDict} are the two state edits include/lz4hip.h states ({@code lz4hip_hcstream_load_dict},
+   * {@code lz4hip_hcstream_save_dict}).
+   */
+  public static final class CompressStreamsHC {
+    private final long[] state;
+    private final int level;
+
+    public CompressStreamsHC(int n, int level) {
+      if (n < 1) {
+        throw new IllegalArgumentException("a set has at least one stream");
+      }
+      state = new long[5 * n];
+      this.level = level;
+    }
+
+    public int size() {
+      return state.length / 5;
+    }
+
+    public int level() {
+      return level;
+    }
+
+    /** {@code LZ4_loadDictHC}: the stream is fresh behind the dictLen bytes of dictionary that end at src[dictEnd]. */
+    public void loadDict(int streamId, long dictEnd, long dictLen) {
+      if (dictLen < 0 || dictLen > dictEnd) {
+        throw new ArrayIndexOutOfBoundsException("history of stream " + streamId);
+      }
+      final long kept = Math.min(dictLen, 65536);
+      final int o = 5 * streamId;
+      state[o] = dictEnd;
+      state[o + 1] = kept;
+      state[o + 2] = 0;
+      state[o + 3] = 0;
+      state[o + 4] = kept;
+    }
+
+    /** {@code LZ4_saveDictHC} for the caller who has copied the last k bytes the stream consumed to src[bufOff ..] -> the bytes kept. */
+    public int saveDict(int streamId, long bufOff, int k) {
+      final int o = 5 * streamId;
+      long kept = Math.min(Math.max(k, 0), 65536);
+      if (kept < 4) {
+        kept = 0;
+      }
+      kept = Math.min(kept, state[o + 1]);
+      state[o] = bufOff + kept;
+      state[o + 1] = kept;
+      state[o + 3] = 0;
+      return (int) kept;
+    }
+
+    /** makes the listed streams (null: all of them) fresh */
+    public void reset(int[] streamId) {
+      if (streamId == null) {
+        java.util.Arrays.fill(state, 0L);
+        return;
+      }
+      for (int c : streamId) {
+        java.util.Arrays.fill(state, 5 * c, 5 * c + 5, 0L);
+      }
+    }
+
+    /** {prefixEnd, prefixLen, extEnd, extLen, index} of one stream */
+    public long[] state(int streamId) {
+      return java.util.Arrays.copyOfRange(state, 5 * streamId, 5 * streamId + 5);
+    }
+
+    /** {@link LZ4HIPBatch#compressHCStream} at the set's level for the streams streamId (distinct ids, one per chain of the call). */
+    public void compress(int[] streamId, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest, long[] destOff,
+        int[] destCap, int[] outLen) {
+      final long[] st = new long[5 * streamId.length];
+      final boolean[] seen = new boolean[size()];
+      for (int k = 0; k < streamId.length; k++) {
+        if (streamId[k] < 0 || streamId[k] >= size() || seen[streamId[k]]) {
+          throw new IllegalArgumentException("streamId must be distinct and below the number of streams");
+        }
+        seen[streamId[k]] = true;
+        System.arraycopy(state, 5 * streamId[k], st, 5 * k, 5);
+      }
+      compressHCStream(st, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, outLen, level);
+      for (int k = 0; k < streamId.length; k++) {
+        System.arraycopy(st, 5 * k, state, 5 * streamId[k], 5);
+      }
+    }
+  }
+
+  /**
    * liblz4's {@code LZ4_decompress_safe_partial} per block: the first {@code min(targetLen[i], destCap[i])} bytes of block i (fewer
    * where a cut stream ends first) into the slot {@code dest[destOff[i], destOff[i]+destCap[i])}, nothing past
    * {@code destOff[i] + min(targetLen[i], destCap[i])}.  outLen[i] &gt;= 0: bytes decoded; &lt; 0: -(input position)-1.

@@ -117,6 +117,12 @@ enum LZ4HIPJNI {
   static native int LZ4HIP_batchSafeStream(long[] state, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest,
                                            long[] destOff, int[] destCap, long[] chainWinOff, long[] chainWinLen, int[] outLen,
                                            int nBlocks, int nChains);
+  /* LZ4_compress_HC_continue on streams whose sources land anywhere, DIRECT buffers: stream c is the blocks chainFirst[c] ..
+   * chainFirst[c + 1] - 1 of this call, block i is src[srcOff[i], + srcLen[i]) and owns dest[destOff[i], + destCap[i]); state holds five
+   * longs per stream (prefixEnd, prefixLen, extEnd, extLen, index: offsets into src), read and written back.  outLen = liblz4's return
+   * values (0: it did not fit, which does not end the stream).  Returns 0 or a negative lz4hip_status (a null argument: LZ4HIP_E_ARG). */
+  static native int LZ4HIP_batchHCStream(long[] state, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest,
+                                         long[] destOff, int[] destCap, int[] outLen, int nBlocks, int nChains, int level);
   /* LZ4_compress_fast_continue over chains of linked blocks, DIRECT buffers: chain c is the blocks chainFirst[c] .. chainFirst[c + 1] - 1,
    * whose sources lie back to back from src[chainSrcOff[c]] on behind chainPrefixLen[c] bytes of history (null: none); block i owns
    * dest[destOff[i], + destCap[i]).  outLen = liblz4's return values (0 ends a chain, LZ4HIPBatch.CHAIN_STOPPED behind it),

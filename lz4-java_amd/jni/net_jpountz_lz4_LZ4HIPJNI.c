@@ -427,6 +427,25 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafeStream(JN
   return rc;
 }
 
+/* LZ4_compress_HC_continue on streams whose sources land anywhere, direct buffers (lz4hip_compress_hc_stream_batch): stream c is the blocks
+ * chainFirst[c] .. chainFirst[c + 1] - 1 of this call, block i is src[srcOff[i], + srcLen[i]) and owns dest[destOff[i], + destCap[i]); state
+ * holds five longs per stream -- prefixEnd, prefixLen, extEnd, extLen, index, offsets into src --, read and written back; outLen[i] =
+ * liblz4's return value.  Returns 0 or a negative lz4hip_status; a NULL array or buffer is LZ4HIP_E_ARG and nothing stays pinned
+ * (LZ4HIPBatch.java checks the arrays' lengths) */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchHCStream(JNIEnv* env, jclass cls, jlongArray state, jobject src, jlongArray srcOff,
+    jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen, jint nBlocks, jint nChains, jint level) {
+  (void)cls;
+  if (nBlocks < 0 || nChains < 0) return LZ4HIP_E_ARG;
+  batch_args_t b = {NULL, NULL, 7, {{state, LONGS, 0}, {srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {chainFirst, INTS, JNI_ABORT},
+                                    {destOff, LONGS, JNI_ABORT}, {destCap, INTS, JNI_ABORT}, {outLen, INTS, 0}}};
+  jint rc = batch_pin(env, src, dest, &b);
+  if (rc != 0) return rc;
+  rc = lz4hip_compress_hc_stream_batch((lz4hip_hcstream_state*)b.a[0].p, b.src, b.a[1].p, b.a[2].p, (const uint32_t*)b.a[3].p, b.dst, b.a[4].p, b.a[5].p,
+                                       b.a[6].p, (uint32_t)nBlocks, (uint32_t)nChains, level);
+  batch_release(env, &b);
+  return rc;
+}
+
 /* LZ4_compress_fast_continue over chains of linked blocks, DIRECT buffers: chainPrefixLen may be null */
 JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastChain(JNIEnv* env, jclass cls, jobject src, jlongArray chainSrcOff,
     jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen,
