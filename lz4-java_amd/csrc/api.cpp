@@ -24,6 +24,7 @@
 namespace {
 
 using staging::al16;
+using staging::pos;
 thread_local std::string g_err;
 std::mutex g_mu;
 std::vector<int> g_devs;  // HIP device ordinals the engine is initialised on
@@ -93,7 +94,7 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // OP_COMPRESS_HC_CHAIN: LZ4_compress_HC_continue over chains of linked blocks (prefix mode): OP_COMPRESS_CHAIN's arrays and host path
 // (no chain_consumed: a block that returns 0 does not stop its chain), OP_COMPRESS_HC's level and workspace
 // OP_COMPRESS_STREAM: LZ4_compress_fast_continue on streams whose state is resident on the device (lz4hip_cstreams): OP_COMPRESS_CHAIN's
-// arrays and host path, plus the slot of every chain's stream and the device's share of the set's state (BlockCall::cs_*)
+// arrays and host path, plus the slot of every chain's stream and the device's share of the set's state (BlockCall::cs_*, StreamShare)
 // OP_DECOMPRESS_STREAM: LZ4_decompress_safe_continue on streams whose blocks land anywhere (every mode of LZ4_streamDecode_t): its
 // arrays and state records are BlockCall::dstream; the host path is dstream_host_shard
 // OP_COMPRESS_XSTREAM: the same resident streams when their sources land anywhere (liblz4's external-dictionary mode included): its
@@ -143,10 +144,14 @@ struct BlockCall {
   void* hc_scratch = nullptr;           // op_needs_chain_scratch: lz4hip::hc_chain_scratch_bytes of device memory
   // op_resumes_streams: the device's share of the set's state (kernels.h CStreamArgs) and, on the device, the slot of every chain
   uint32_t* cs_rec = nullptr; uint64_t* cs_tables = nullptr; const uint32_t* cs_slot = nullptr;
-  // ... and on the host path: the caller's stream ids, the id of the share's slot 0, the set's marks of streams to stop (may be nullptr)
-  const uint32_t* cs_ids = nullptr; uint32_t cs_id0 = 0; const uint8_t* cs_poisoned = nullptr;
-  bool* cs_launched = nullptr;          // (host path, may be nullptr) set once a kernel of the shard has been enqueued
 };
+// What the host path knows of a stream set beside that, for one device's share of one call (cstreams_call makes it, the shards of
+// op_resumes_streams and OP_COMPRESS_XSTREAM read it): the caller's stream ids, one per chain of the call; the id of the share's slot 0;
+// the set's marks of streams to stop, by id (may be nullptr); *launched is set once a kernel of the shard is about to be enqueued
+struct StreamShare {
+  const uint32_t* ids = nullptr; uint32_t id0 = 0; const uint8_t* poisoned = nullptr; bool* launched = nullptr;
+};
+static_assert(staging::kSlotForceStop == lz4hip::kStreamForceStop, "the staging arithmetic's stop mark is the kernels'");
 static_assert(lz4hip::kChainStopped == LZ4HIP_CHAIN_STOPPED, "the kernels' marker is the header's");
 // the handle's bytes on the CURRENT device (uploaded on first use where lz4hip_dict_create found the device not yet initialised):
 // one past the last byte, and the true length; a status (message set) on failure
@@ -495,7 +500,6 @@ int dev_batch(const BlockCall& c, const lz4hip::BatchArgs& a, int device, void* 
   return on_device(device, a.n == 0, null_arg ? kNullArg : extra_error, [&] { return launch_block(c, a, (hipStream_t)stream); });
 }
 // the bytes block i of a partial decode may fill: min(target, capacity), or -1 (the kernels' -1) where one of them is negative
-size_t pos(int32_t v) { return v > 0 ? (size_t)v : 0; }   // (a negative length or capacity takes no bytes in the staging)
 int32_t partial_room(int32_t target, int32_t cap) { return (target < 0 || cap < 0) ? -1 : std::min(target, cap); }
 
 // ---- host-pointer path ---------------------------------------------------------------------------
@@ -685,16 +689,69 @@ struct ShardScope {
     return ok("D2H out", hipMemcpyAsync((uint8_t*)s.h_meta.p + l.results, (const uint8_t*)s.d_meta.p + l.results, l.results_bytes(), hipMemcpyDeviceToHost, q));
   }
   bool wait(hipStream_t q) { return ok("hipStreamSynchronize", hipStreamSynchronize(q)); }
-  // only the bytes produced, from d_dst to h_dst on s.st, waited for: entry(t) as staging::for_each_run takes it
+  // the chain- and stream-shaped shards' launch on the set's own stream: the kernel, the results to the host, and they are there
+  bool run(const BlockCall& call, ChunkSlot& s, const staging::MetaLayout& l) {
+    return launched(launch_block(call, lz4hip::BatchArgs{}, s.st)) && fetch_results(s, l, s.st) && wait(s.st);
+  }
+  // Runs of bytes (any order, overlapping ones included: joined here, host_staging.h merge_runs) that lie at the same offsets in a
+  // pinned mirror and in its device buffer, one copy per joined run on s.st, `what` the step's name: from the mirror up ...
+  bool upload_runs(ChunkSlot& s, const GrowBuf& host, GrowBuf& dev, std::vector<staging::Run>& runs, const char* what) {
+    staging::merge_runs(runs);
+    for (const staging::Run& r : runs)
+      if (!ok(what, hipMemcpyAsync((uint8_t*)dev.p + r.off, (const uint8_t*)host.p + r.off, r.len, hipMemcpyHostToDevice, s.st))) return false;
+    return true;
+  }
+  // ... and from d_dst down into h_dst, waited for
+  bool fetch_runs(ChunkSlot& s, std::vector<staging::Run>& runs, const char* what) {
+    staging::merge_runs(runs);
+    for (const staging::Run& r : runs)
+      if (!ok(what, hipMemcpyAsync((uint8_t*)s.h_dst.p + r.off, (const uint8_t*)s.d_dst.p + r.off, r.len, hipMemcpyDeviceToHost, s.st))) return false;
+    return wait(s.st);
+  }
+  // only the bytes produced come back: entry(t) as staging::for_each_run takes it (offsets ascending)
   template <class Entry>
   bool fetch_runs(ChunkSlot& s, uint32_t n, Entry entry) {
-    hipError_t e = hipSuccess;
-    (void)staging::for_each_run(n, entry, [&](size_t r0, size_t r1) {
-      return (int)(e = hipMemcpyAsync((uint8_t*)s.h_dst.p + r0, (const uint8_t*)s.d_dst.p + r0, r1 - r0, hipMemcpyDeviceToHost, s.st));
-    });
-    return ok("D2H dst", e) && wait(s.st);
+    runs.clear();
+    (void)staging::for_each_run(n, entry, [&](size_t r0, size_t r1) { runs.push_back(staging::Run{r0, r1 - r0}); return 0; });
+    return fetch_runs(s, runs, "D2H dst");
   }
+  // The compressors' way back, once out[] of the chunk's blocks [b0, b1) is on the host: a block produced out[i] bytes where that is a
+  // size within its capacity.  Those bytes alone come down -- block b0 + t's slot lies at dso[t] of d_dst -- and go to the caller's
+  // slots on several threads (db: the slots' bytes in all)
+  bool hand_back_produced(ChunkSlot& s, uint32_t b0, uint32_t b1, size_t db, const std::vector<uint64_t>& dso, uint8_t* dst, const uint64_t* dst_off,
+                          const int32_t* dst_cap, const int32_t* out) {
+    auto produced = [=](uint32_t i) -> size_t { const int32_t r = out[i]; return r > 0 && (size_t)r <= pos(dst_cap[i]) ? (size_t)r : 0; };
+    if (!fetch_runs(s, b1 - b0, [&](uint32_t t) { return staging::Run{(size_t)dso[t], produced(b0 + t)}; })) return false;
+    const uint8_t* const hd = (const uint8_t*)s.h_dst.p;
+    par_blocks(b0, b1, db, [=, &dso](uint32_t i) { if (const size_t r = produced(i)) memcpy(dst + dst_off[i], hd + dso[i - b0], r); });
+    return true;
+  }
+  std::vector<staging::Run> runs;   // (fetch_runs' list, kept from chunk to chunk)
 };
+
+// ---- the frame of the shards whose unit is a chain or a stream of blocks ----
+// A chunk of such a shard: the chains (streams) [c, j) of the call, their blocks [b0, b1), nc and nb of them; src, dst: what the
+// chunk costs, as its shard counts it
+struct ChainChunk { uint32_t c, j, b0, b1, nb, nc; size_t src, dst; };
+// One device's share [c0, c1) of such a call (chain_first: the caller's), a chunk at a time through the FIRST buffer set of a pooled
+// pair and on that set's stream alone -- no rotation, no finisher threads.  A chunk takes whole chains while their cost(chain) stays
+// within LZ4HIP_HOST_CHUNK_MB (64) MiB of source and 512 MiB of destination, one chain at least.  chunk(sh, s, k) stages, runs and hands
+// back chunk k; false: it failed (sh.rc and the message are set), which ends the shard -- through the scope, which waits for the streams.
+template <class CostOf, class ChunkFn>
+int chain_shard(int ord, const uint32_t* chain_first, uint32_t c0, uint32_t c1, std::string* err, CostOf cost, ChunkFn chunk) {
+  if (c1 == c0) return LZ4HIP_OK;
+  ShardScope sh(ord, err);
+  if (sh.rc) return sh.rc;
+  ChunkSlot& s = sh.pair->slot[0];
+  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+  for (uint32_t c = c0; c < c1;) {
+    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, cost);
+    const uint32_t j = ck.end, b0 = chain_first[c], b1 = chain_first[j];
+    if (!chunk(sh, s, ChainChunk{c, j, b0, b1, b1 - b0, j - c, ck.src, ck.dst})) return sh.rc;
+    c = j;
+  }
+  return LZ4HIP_OK;
+}
 
 // one device's share [b0, b1) of a host batch.  Three stages run side by side on LZ4HIP_HOST_SETS rotating buffer sets (default 6,
 // each a pinned pair of 64 MiB of source + the destination capacity of its chunk, allocated on first use and kept in the per-device
@@ -906,38 +963,40 @@ int host_batch(const BlockCall& c, const uint8_t* src, const uint64_t* src_off, 
 }
 
 // ---- chains of linked blocks on the host-pointer path ----
+// The opening of every host entry point whose unit is a chain or a stream: an argument error (why: a message or nullptr) is said without
+// a device too; then the engine has to be there; a call of no chains is done; everything else is rest().
+template <class Rest>
+int chain_entry(const char* why, uint32_t n_chains, Rest rest) {
+  if (why) return fail(LZ4HIP_E_ARG, why);
+  if (const int rc = need_device()) return rc;
+  return n_chains == 0 ? (int)LZ4HIP_OK : rest();
+}
+// ... and what the entries that hold no stream set go on with: whole chains per device
+template <class Shard>
+int whole_chains(uint32_t n_chains, Shard shard) { return fan_out(n_chains, 64u, shard); }
+
 // One device's share [c0, c1) of a chain batch (h: the caller's HOST arrays).  Chains are staged a chunk at a time (64 MiB of streams
 // or 512 MiB of destination, one chain at least) through the first buffer set of a pooled pair: the streams and, per chain, the last
 // min(prefix_len, 65536) bytes of history from the caller's dst go up; the kernel runs; the results come back, and then only the bytes
 // each chain decoded (runs less than 4 KB apart travel as one copy).  On the device a chain's region is min(chain_dst_cap, the sum of
 // its blocks' capacities) bytes: a block's capacity is the smaller of its own and what is left, so nothing changes.
 int chain_host_shard(const lz4hip::ChainArgs& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
-  if (c1 == c0) return LZ4HIP_OK;
-  ShardScope sh(ord, err);
-  if (sh.rc) return sh.rc;
-  ChunkSlot& s = sh.pair->slot[0];
-  const hipStream_t st = s.st;
   auto keep_of = [&](uint32_t c) -> size_t { const int32_t p = h.chain_prefix_len ? h.chain_prefix_len[c] : 0; return p > 65536 ? 65536u : (size_t)p; };
   auto room_of = [&](uint32_t c) -> size_t {   // the chain's region on the device
     uint64_t sum = 0;
     for (uint32_t i = h.chain_first[c]; i < h.chain_first[c + 1]; i++) sum += pos(h.dst_cap[i]);
     return (size_t)std::min<uint64_t>(sum, h.chain_dst_cap[c]);
   };
-  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+  auto cost = [&](uint32_t c) { return staging::Cost{staging::chain_packed_bytes(h.chain_first, c, h.src_len), al16(keep_of(c) + room_of(c))}; };
   std::vector<uint64_t> so, cdo, room;
-  for (uint32_t c = c0; c < c1;) {
-    // the next chunk: chains [c, j), blocks [b0, b1)
-    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, [&](uint32_t j) {
-      size_t a = 0;
-      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) a += al16(pos(h.src_len[i]));
-      return staging::Cost{a, al16(keep_of(j) + room_of(j))};
-    });
-    const uint32_t j = ck.end, b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
-    so.resize(nb); cdo.resize(nc); room.resize(nc);
-    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { so[t] = o; o += al16(pos(h.src_len[b0 + t])); } }
+  return chain_shard(ord, h.chain_first, c0, c1, err, cost, [&](ShardScope& sh, ChunkSlot& s, const ChainChunk& ck) {
+    const uint32_t c = ck.c, j = ck.j, b0 = ck.b0, b1 = ck.b1, nb = ck.nb, nc = ck.nc;
+    const hipStream_t st = s.st;
+    (void)staging::packed_offsets(h.src_len + b0, nb, so);
+    cdo.resize(nc); room.resize(nc);
     { size_t o = 0; for (uint32_t t = 0; t < nc; t++) { room[t] = room_of(c + t); cdo[t] = o + keep_of(c + t); o += al16(keep_of(c + t) + room[t]); } }
     const staging::ChainMeta m(nb, nc);
-    if (!sh.reserve(s, ck.src, true, ck.dst, m.l.total)) return sh.rc;
+    if (!sh.reserve(s, ck.src, true, ck.dst, m.l.total)) return false;
     uint8_t *const hs = (uint8_t*)s.h_src.p, *const hd = (uint8_t*)s.h_dst.p, *const dd = (uint8_t*)s.d_dst.p;
     void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
     par_blocks(b0, b1, ck.src, [=, &so](uint32_t i) { if (h.src_len[i] > 0) memcpy(hs + so[i - b0], h.src + h.src_off[i], (size_t)h.src_len[i]); });
@@ -947,28 +1006,27 @@ int chain_host_shard(const lz4hip::ChainArgs& h, int ord, uint32_t c0, uint32_t 
     memcpy(m.chain_dst_cap.in(hm), room.data(), m.chain_dst_cap.bytes());
     memcpy(m.src_len.in(hm), h.src_len + b0, m.src_len.bytes());
     memcpy(m.dst_cap.in(hm), h.dst_cap + b0, m.dst_cap.bytes());
-    for (uint32_t t = 0; t <= nc; t++) m.first.in(hm)[t] = h.chain_first[c + t] - b0;
+    staging::rebase_first(h.chain_first, c, nc, m.first.in(hm));
     for (uint32_t t = 0; t < nc; t++) m.prefix.in(hm)[t] = (int32_t)keep_of(c + t);
     if (h.stored) memcpy(m.stored.in(hm), h.stored + b0, nb); else memset(m.stored.in(hm), 0, nb);
-    if (!sh.upload(s, ck.src, m.l, st)) return sh.rc;
+    if (!sh.upload(s, ck.src, m.l, st)) return false;
     for (uint32_t t = 0; t < nc; t++) {   // the histories
       const size_t k = keep_of(c + t);
       if (!k) continue;
       memcpy(hd + cdo[t] - k, h.dst + h.chain_dst_off[c + t] - k, k);
-      if (!sh.ok("H2D history", hipMemcpyAsync(dd + cdo[t] - k, hd + cdo[t] - k, k, hipMemcpyHostToDevice, st))) return sh.rc;
+      if (!sh.ok("H2D history", hipMemcpyAsync(dd + cdo[t] - k, hd + cdo[t] - k, k, hipMemcpyHostToDevice, st))) return false;
     }
     const lz4hip::ChainArgs a{(const uint8_t*)s.d_src.p, m.src_off.in(dm), m.src_len.in(dm), m.stored.in(dm), m.dst_cap.in(dm), m.first.in(dm), dd,
                               m.chain_dst_off.in(dm), m.chain_dst_cap.in(dm), m.prefix.in(dm), m.out.in(dm), m.chain_out.in(dm), nb, nc};
     BlockCall call{OP_DECOMPRESS_CHAIN}; call.chain = &a;
-    if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
+    if (!sh.run(call, s, m.l)) return false;
     memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
     memcpy(h.chain_out + c, m.chain_out.in(hm), m.chain_out.bytes());
     // only the bytes decoded come back
-    if (!sh.fetch_runs(s, nc, [&](uint32_t t) { return staging::Run{(size_t)cdo[t], (size_t)h.chain_out[c + t]}; })) return sh.rc;
+    if (!sh.fetch_runs(s, nc, [&](uint32_t t) { return staging::Run{(size_t)cdo[t], (size_t)h.chain_out[c + t]}; })) return false;
     par_blocks(c, j, ck.dst, [=, &cdo](uint32_t t) { if (const size_t n = (size_t)h.chain_out[t]) memcpy(h.dst + h.chain_dst_off[t], hd + cdo[t - c], n); });
-    c = j;
-  }
-  return LZ4HIP_OK;
+    return true;
+  });
 }
 
 // the argument errors of a chain call that can be seen without a device; host: the arrays are the caller's host memory and are read
@@ -995,30 +1053,20 @@ static_assert(sizeof(lz4hip_dstream_state) == sizeof(staging::DsState) && sizeof
 // the prefix is shorter than 65535 bytes: behind that liblz4 never looks at it); the kernel runs; the results and records come back,
 // then each block's decoded bytes (runs less than 4 KB apart travel as one copy) -- nothing else of the caller's dst is written.
 int dstream_host_shard(const DStreamHost& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
-  if (c1 == c0) return LZ4HIP_OK;
-  ShardScope sh(ord, err);
-  if (sh.rc) return sh.rc;
-  ChunkSlot& s = sh.pair->slot[0];
-  const hipStream_t st = s.st;
   const staging::DsState* const hstate = (const staging::DsState*)h.state;
-  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+  auto cost = [&](uint32_t c) { return staging::Cost{staging::chain_packed_bytes(h.chain_first, c, h.src_len), staging::dstream_cost(hstate[c], h.win_off[c], h.win_len[c])}; };
   std::vector<uint64_t> so, ddo;
   std::vector<staging::Run> runs;
-  for (uint32_t c = c0; c < c1;) {
-    // the next chunk: streams [c, j), blocks [b0, b1)
-    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, [&](uint32_t j) {
-      size_t a = 0;
-      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) a += al16(pos(h.src_len[i]));
-      return staging::Cost{a, staging::dstream_cost(hstate[j], h.win_off[j], h.win_len[j])};
-    });
-    const uint32_t j = ck.end, b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
+  return chain_shard(ord, h.chain_first, c0, c1, err, cost, [&](ShardScope& sh, ChunkSlot& s, const ChainChunk& ck) {
+    const uint32_t c = ck.c, b0 = ck.b0, b1 = ck.b1, nb = ck.nb, nc = ck.nc;
+    const hipStream_t st = s.st;
     const staging::DsImage im(hstate + c, h.win_off + c, h.win_len + c, nc);
-    so.resize(nb); ddo.resize(nb);
-    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { so[t] = o; o += al16(pos(h.src_len[b0 + t])); } }
+    (void)staging::packed_offsets(h.src_len + b0, nb, so);
+    ddo.resize(nb);
     for (uint32_t t = 0; t < nc; t++)
       for (uint32_t i = h.chain_first[c + t]; i < h.chain_first[c + t + 1]; i++) ddo[i - b0] = im.win[t] + (h.dst_off[i] - h.win_off[c + t]);
     const staging::DsMetaLayout m(nb, nc);
-    if (!sh.reserve(s, ck.src, true, im.total, m.l.total)) return sh.rc;
+    if (!sh.reserve(s, ck.src, true, im.total, m.l.total)) return false;
     uint8_t *const hs = (uint8_t*)s.h_src.p, *const hd = (uint8_t*)s.h_dst.p, *const dd = (uint8_t*)s.d_dst.p;
     void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
     par_blocks(b0, b1, ck.src, [=, &so](uint32_t i) { if (h.src_len[i] > 0) memcpy(hs + so[i - b0], h.src + h.src_off[i], (size_t)h.src_len[i]); });
@@ -1026,9 +1074,9 @@ int dstream_host_shard(const DStreamHost& h, int ord, uint32_t c0, uint32_t c1, 
     memcpy(m.dst_off.in(hm), ddo.data(), m.dst_off.bytes());
     memcpy(m.src_len.in(hm), h.src_len + b0, m.src_len.bytes());
     memcpy(m.dst_cap.in(hm), h.dst_cap + b0, m.dst_cap.bytes());
-    for (uint32_t t = 0; t <= nc; t++) m.first.in(hm)[t] = h.chain_first[c + t] - b0;
+    staging::rebase_first(h.chain_first, c, nc, m.first.in(hm));
     memcpy(m.state.in(hm), im.dev.data(), m.state.bytes());
-    if (!sh.upload(s, ck.src, m.l, st)) return sh.rc;
+    if (!sh.upload(s, ck.src, m.l, st)) return false;
     // the history pieces: into the pinned mirror, then up as joined runs (what a joined run carries between two pieces lands in
     // window bytes no block may rely on)
     runs.clear();
@@ -1042,13 +1090,11 @@ int dstream_host_shard(const DStreamHost& h, int ord, uint32_t c0, uint32_t c1, 
       if (im.ext[t].kind == staging::DS_INSIDE && hs0.prefix_len < staging::kDsKeep) piece((size_t)im.dev[t].ext_end, hs0.ext_end, im.ext[t].keep);
     }
     for (const staging::DsApart& a : im.apart) piece(a.dev + (size_t)a.keep, a.end, a.keep);
-    staging::merge_runs(runs);
-    for (const staging::Run& r : runs)
-      if (!sh.ok("H2D history", hipMemcpyAsync(dd + r.off, hd + r.off, r.len, hipMemcpyHostToDevice, st))) return sh.rc;
+    if (!sh.upload_runs(s, s.h_dst, s.d_dst, runs, "H2D history")) return false;
     const lz4hip::DStreamArgs a{(const uint8_t*)s.d_src.p, m.src_off.in(dm), m.src_len.in(dm), m.first.in(dm), dd, m.dst_off.in(dm), m.dst_cap.in(dm),
                                 (lz4hip::DStreamState*)m.state.in(dm), m.out.in(dm), nb, nc};
     BlockCall call{OP_DECOMPRESS_STREAM}; call.dstream = &a;
-    if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
+    if (!sh.run(call, s, m.l)) return false;
     memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
     for (uint32_t t = 0; t < nc; t++) {   // the records, in the caller's terms again
       const staging::DsState was = hstate[c + t], now = m.state.in(hm)[t];
@@ -1060,15 +1106,11 @@ int dstream_host_shard(const DStreamHost& h, int ord, uint32_t c0, uint32_t c1, 
     // only the bytes decoded come back
     runs.clear();
     for (uint32_t i = b0; i < b1; i++) if (h.out[i] > 0) runs.push_back(staging::Run{(size_t)ddo[i - b0], (size_t)h.out[i]});
-    staging::merge_runs(runs);
-    for (const staging::Run& r : runs)
-      if (!sh.ok("D2H dst", hipMemcpyAsync(hd + r.off, dd + r.off, r.len, hipMemcpyDeviceToHost, st))) return sh.rc;
-    if (!sh.wait(st)) return sh.rc;
+    if (!sh.fetch_runs(s, runs, "D2H dst")) return false;
     // (in block order on one thread: where two slots of a call overlap, the later block's bytes are the ones that stay, as on the device)
     for (uint32_t i = b0; i < b1; i++) if (h.out[i] > 0) memcpy(h.dst + h.dst_off[i], hd + ddo[i - b0], (size_t)h.out[i]);
-    c = j;
-  }
-  return LZ4HIP_OK;
+    return true;
+  });
 }
 
 // the argument errors of a stream-decode call, all of which can be seen without a device (the arrays are the caller's host memory)
@@ -1086,14 +1128,9 @@ const char* dstream_arg_error(const DStreamHost& h) {
 // read: up to the first block with a negative length or with which the chain would exceed 0x7E000000 bytes (its result is 0).
 // op_chain_stops(c.op) false (the HC chain): every block's source is read, a negative length counts as 0 bytes, a history of any
 // length is kept, nothing travels in chain_consumed[], and the chunk's workspace is sized by its packed source.
-// op_resumes_streams(c.op) (resident streams): chain c continues stream proto.cs_ids[c]; its slot in the device's share of the set
+// op_resumes_streams(c.op) (resident streams): chain c continues stream share.ids[c]; its slot in the device's share of the set
 // travels in the metadata, with the stop mark of a stream that an earlier call left in an unknown state.
-int cchain_host_shard(const BlockCall& proto, const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
-  if (c1 == c0) return LZ4HIP_OK;
-  ShardScope sh(ord, err);
-  if (sh.rc) return sh.rc;
-  ChunkSlot& s = sh.pair->slot[0];
-  const hipStream_t st = s.st;
+int cchain_host_shard(const BlockCall& proto, const StreamShare& share, const lz4hip::CChainArgs& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
   auto keep_of = [&](uint32_t c) -> size_t { const int32_t p = h.chain_prefix_len ? h.chain_prefix_len[c] : 0; return p > 65536 ? 65536u : (size_t)p; };
   const bool stops = op_chain_stops(proto.op), resumes = op_resumes_streams(proto.op);
   auto span_of = [&](uint32_t c) -> size_t {   // the source bytes the chain's blocks can consume
@@ -1113,26 +1150,19 @@ int cchain_host_shard(const BlockCall& proto, const lz4hip::CChainArgs& h, int o
     }
     return (size_t)(pos - pos0);
   };
-  auto produced = [&](uint32_t i) -> size_t { const int32_t r = h.out[i]; return r > 0 && (size_t)r <= pos(h.dst_cap[i]) ? (size_t)r : 0; };   // (h.out: once it is back)
-  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+  auto cost = [&](uint32_t c) { return staging::Cost{al16(keep_of(c) + span_of(c)), staging::chain_packed_bytes(h.chain_first, c, h.dst_cap)}; };
   std::vector<uint64_t> cso, dso;
-  for (uint32_t c = c0; c < c1;) {
-    // the next chunk: chains [c, j), blocks [b0, b1)
-    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, [&](uint32_t j) {
-      size_t d = 0;
-      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) d += al16(pos(h.dst_cap[i]));
-      return staging::Cost{al16(keep_of(j) + span_of(j)), d};
-    });
-    const uint32_t j = ck.end, b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
-    cso.resize(nc); dso.resize(nb);
+  return chain_shard(ord, h.chain_first, c0, c1, err, cost, [&](ShardScope& sh, ChunkSlot& s, const ChainChunk& ck) {
+    const uint32_t c = ck.c, j = ck.j, b0 = ck.b0, nb = ck.nb, nc = ck.nc;
+    cso.resize(nc);
     { size_t o = 0; for (uint32_t t = 0; t < nc; t++) { cso[t] = o + keep_of(c + t); o += al16(keep_of(c + t) + span_of(c + t)); } }
-    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { dso[t] = o; o += al16(pos(h.dst_cap[b0 + t])); } }
+    (void)staging::packed_offsets(h.dst_cap + b0, nb, dso);
     const staging::CChainMeta m(nb, nc, resumes);
-    if (!sh.reserve(s, ck.src, true, ck.dst, m.l.total)) return sh.rc;
-    if (op_uses_hc_ws(proto.op) && !sh.ok("staging allocation", s.d_ws.reserve(lz4hip::hc_ws_bytes(ck.src, nb, proto.param)))) return sh.rc;
+    if (!sh.reserve(s, ck.src, true, ck.dst, m.l.total)) return false;
+    if (op_uses_hc_ws(proto.op) && !sh.ok("staging allocation", s.d_ws.reserve(lz4hip::hc_ws_bytes(ck.src, nb, proto.param)))) return false;
     // (the layout's scratch for the largest segment count the knob allows, in the buffer set's unused offsets buffer)
-    if (op_needs_chain_scratch(proto.op) && !sh.ok("staging allocation", s.d_poff.reserve(lz4hip::hc_chain_scratch_bytes(ck.src, nb, nc, 4096u)))) return sh.rc;
-    uint8_t *const hs = (uint8_t*)s.h_src.p, *const hd = (uint8_t*)s.h_dst.p;
+    if (op_needs_chain_scratch(proto.op) && !sh.ok("staging allocation", s.d_poff.reserve(lz4hip::hc_chain_scratch_bytes(ck.src, nb, nc, 4096u)))) return false;
+    uint8_t* const hs = (uint8_t*)s.h_src.p;
     void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
     par_blocks(c, j, ck.src, [=, &cso](uint32_t t) {
       const size_t k = keep_of(t), n = k + span_of(t);
@@ -1143,29 +1173,21 @@ int cchain_host_shard(const BlockCall& proto, const lz4hip::CChainArgs& h, int o
     memcpy(m.dst_off.in(hm), dso.data(), m.dst_off.bytes());
     memcpy(m.src_len.in(hm), h.src_len + b0, m.src_len.bytes());
     memcpy(m.dst_cap.in(hm), h.dst_cap + b0, m.dst_cap.bytes());
-    for (uint32_t t = 0; t <= nc; t++) m.first.in(hm)[t] = h.chain_first[c + t] - b0;
+    staging::rebase_first(h.chain_first, c, nc, m.first.in(hm));
     for (uint32_t t = 0; t < nc; t++) m.prefix.in(hm)[t] = (int32_t)keep_of(c + t);
-    if (resumes)
-      for (uint32_t t = 0; t < nc; t++) {
-        const uint32_t id = proto.cs_ids[c + t];
-        m.slot.in(hm)[t] = (id - proto.cs_id0) | (proto.cs_poisoned && proto.cs_poisoned[id] ? lz4hip::kStreamForceStop : 0u);
-      }
-    if (!sh.upload(s, ck.src, m.l, st)) return sh.rc;
+    if (resumes) staging::stream_slots(share.ids + c, nc, share.id0, share.poisoned, m.slot.in(hm));
+    if (!sh.upload(s, ck.src, m.l, s.st)) return false;
     const lz4hip::CChainArgs a{(const uint8_t*)s.d_src.p, m.chain_src_off.in(dm), m.prefix.in(dm), m.src_len.in(dm), m.first.in(dm), (uint8_t*)s.d_dst.p,
                                m.dst_off.in(dm), m.dst_cap.in(dm), m.out.in(dm), stops ? m.consumed.in(dm) : nullptr, nb, nc};
     BlockCall call = proto; call.cchain = &a;
     if (op_uses_hc_ws(proto.op)) { call.hc_ws = s.d_ws.p; call.hc_span = ck.src; }
     if (op_needs_chain_scratch(proto.op)) call.hc_scratch = s.d_poff.p;
-    if (resumes) { call.cs_slot = m.slot.in(dm); if (proto.cs_launched) *proto.cs_launched = true; }
-    if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
+    if (resumes) { call.cs_slot = m.slot.in(dm); if (share.launched) *share.launched = true; }
+    if (!sh.run(call, s, m.l)) return false;
     memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
     if (stops) memcpy(h.chain_consumed + c, m.consumed.in(hm), m.consumed.bytes());
-    // only the bytes produced come back
-    if (!sh.fetch_runs(s, nb, [&](uint32_t t) { return staging::Run{(size_t)dso[t], produced(b0 + t)}; })) return sh.rc;
-    par_blocks(b0, b1, ck.dst, [=, &dso](uint32_t i) { if (const size_t r = produced(i)) memcpy(h.dst + h.dst_off[i], hd + dso[i - b0], r); });
-    c = j;
-  }
-  return LZ4HIP_OK;
+    return sh.hand_back_produced(s, b0, ck.b1, ck.dst, dso, h.dst, h.dst_off, h.dst_cap, h.out);
+  });
 }
 
 // the argument errors of a chain-compress call that can be seen without a device; host: the arrays are the caller's host memory
@@ -1183,40 +1205,26 @@ struct HcStreamHost {
 };
 static_assert(sizeof(lz4hip_hcstream_state) == sizeof(staging::HcsState) && offsetof(lz4hip_hcstream_state, index) == offsetof(staging::HcsState, index),
               "the header's state record is the staging arithmetic's");
-// One device's share [c0, c1) of such a call: cchain_host_shard's frame (chunks of 64 MiB of image or 512 MiB of slots, one stream at
-// least, through the first buffer set of a pooled pair) around the linear image of host_staging.h.  The states of a chunk's streams are
-// written back once its results are on the host.
+// One device's share [c0, c1) of such a call: the frame of chain_shard (chunks of 64 MiB of image or 512 MiB of slots) around the
+// linear image of host_staging.h.  The states of a chunk's streams are written back once its results are on the host.
 int hcstream_host_shard(int level, const HcStreamHost& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
-  if (c1 == c0) return LZ4HIP_OK;
-  ShardScope sh(ord, err);
-  if (sh.rc) return sh.rc;
-  ChunkSlot& s = sh.pair->slot[0];
-  const hipStream_t st = s.st;
   const staging::HcsState* const state = (const staging::HcsState*)h.state;
-  auto produced = [&](uint32_t i) -> size_t { const int32_t r = h.out[i]; return r > 0 && (size_t)r <= pos(h.dst_cap[i]) ? (size_t)r : 0; };   // (h.out: once it is back)
-  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+  auto cost = [&](uint32_t c) { return staging::Cost{staging::hcstream_cost(state[c], h.chain_first, c, h.src_len), staging::chain_packed_bytes(h.chain_first, c, h.dst_cap)}; };
   const uint32_t seg = (uint32_t)g_hc_chain_segment.load(std::memory_order_relaxed);
   std::vector<uint64_t> dso;
   std::vector<uint32_t> items;
-  for (uint32_t c = c0; c < c1;) {
-    // the next chunk: streams [c, j), blocks [b0, b1)
-    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, [&](uint32_t j) {
-      size_t d = 0;
-      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) d += al16(pos(h.dst_cap[i]));
-      return staging::Cost{staging::hcstream_cost(state[j], h.chain_first, j, h.src_len), d};
-    });
-    const uint32_t j = ck.end, b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
-    if (nb == 0) { c = j; continue; }   // (streams without blocks: their states stay as they are)
+  return chain_shard(ord, h.chain_first, c0, c1, err, cost, [&](ShardScope& sh, ChunkSlot& s, const ChainChunk& ck) {
+    const uint32_t c = ck.c, b0 = ck.b0, nb = ck.nb, nc = ck.nc;
+    if (nb == 0) return true;   // (streams without blocks: their states stay as they are)
     const staging::HcsImage im(state, h.chain_first, c, nc, h.src_off, h.src_len);
-    dso.resize(nb);
-    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { dso[t] = o; o += al16(pos(h.dst_cap[b0 + t])); } }
+    (void)staging::packed_offsets(h.dst_cap + b0, nb, dso);
     items.clear();   // positions 0 .. len - 4 get an entry: ceil((len - 3) / seg) segments per stream
     for (uint32_t t = 0; t < nc; t++)
       for (uint64_t k = 0, nk = im.buf_len[t] >= 4u ? (im.buf_len[t] - 3u + seg - 1u) / seg : 0u; k < nk; k++) { items.push_back(t); items.push_back((uint32_t)k); }
     const staging::HcStreamMeta m(nb, nc, im.ends.size(), items.size() / 2u);
-    if (!sh.reserve(s, im.total, true, ck.dst, m.l.total)) return sh.rc;
-    if (!sh.ok("staging allocation", s.d_ws.reserve(lz4hip::hc_ws_bytes(im.total, nb, level)))) return sh.rc;
-    uint8_t *const hs = (uint8_t*)s.h_src.p, *const hd = (uint8_t*)s.h_dst.p;
+    if (!sh.reserve(s, im.total, true, ck.dst, m.l.total)) return false;
+    if (!sh.ok("staging allocation", s.d_ws.reserve(lz4hip::hc_ws_bytes(im.total, nb, level)))) return false;
+    uint8_t* const hs = (uint8_t*)s.h_src.p;
     void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
     par_blocks(0, (uint32_t)im.pieces.size(), im.total, [=, &im](uint32_t t) { const staging::HcsPiece& p = im.pieces[t]; memcpy(hs + p.dev, h.src + p.src, p.len); });
     m.l.zero_results(hm);
@@ -1232,21 +1240,18 @@ int hcstream_host_shard(int level, const HcStreamHost& h, int ord, uint32_t c0, 
     memcpy(m.end_first.in(hm), im.end_first.data(), m.end_first.bytes());
     if (m.ends.n) memcpy(m.ends.in(hm), im.ends.data(), m.ends.bytes());
     if (m.items.n) memcpy(m.items.in(hm), items.data(), m.items.bytes());
-    if (!sh.upload(s, im.total, m.l, st)) return sh.rc;
+    if (!sh.upload(s, im.total, m.l, s.st)) return false;
     const lz4hip::HcStreamArgs a{(const uint8_t*)s.d_src.p, m.blk_start.in(dm), m.blk_hist.in(dm), m.blk_low.in(dm), m.blk_dlim.in(dm), m.src_len.in(dm),
                                  (uint8_t*)s.d_dst.p, m.dst_off.in(dm), m.dst_cap.in(dm), m.out.in(dm), m.buf_off.in(dm), m.buf_len.in(dm), m.end_first.in(dm),
                                  m.ends.in(dm), m.items.in(dm), m.queue.in(dm), (uint64_t)im.total, nb, nc, (uint32_t)im.ends.size(), (uint32_t)(items.size() / 2u), seg};
     BlockCall call{OP_COMPRESS_HC_STREAM, level};
     call.hcstream = &a; call.hc_ws = s.d_ws.p; call.hc_span = im.total;
-    if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
+    if (!sh.run(call, s, m.l)) return false;
     memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
-    // only the bytes produced come back
-    if (!sh.fetch_runs(s, nb, [&](uint32_t t) { return staging::Run{(size_t)dso[t], produced(b0 + t)}; })) return sh.rc;
-    par_blocks(b0, b1, ck.dst, [=, &dso](uint32_t i) { if (const size_t r = produced(i)) memcpy(h.dst + h.dst_off[i], hd + dso[i - b0], r); });
+    if (!sh.hand_back_produced(s, b0, ck.b1, ck.dst, dso, h.dst, h.dst_off, h.dst_cap, h.out)) return false;
     memcpy(h.state + c, im.after.data(), (size_t)nc * sizeof(staging::HcsState));
-    c = j;
-  }
-  return LZ4HIP_OK;
+    return true;
+  });
 }
 // the argument errors of such a call that can be seen without a device
 const char* hcstream_arg_error(const HcStreamHost& h) {
@@ -1262,38 +1267,27 @@ struct CXStreamHost {
   const uint64_t* win_off; const uint64_t* win_len; uint8_t* dst; const uint64_t* dst_off; const int32_t* dst_cap; int32_t* out; uint64_t* chain_consumed;
   uint32_t n_blocks, n_chains;
 };
-// One device's share [c0, c1) of such a call: cchain_host_shard's frame (chunks of 64 MiB of image or 512 MiB of slots, one stream at
-// least, through the first buffer set of a pooled pair; proto.cs_*: the share's slots and state) around the image of host_staging.h
-// CxImage.  Per stream the used part of its window is mirrored: up go the sources that can run and the history pieces -- those inside a
-// window or in front of it where they lie in the mirror, those apart once per chunk -- as runs (what a joined run carries between two
-// pieces lands in mirror bytes nothing reads); the kernel gets every offset in device terms; the results come back, then only the
-// bytes each block produced.
-int cxstream_host_shard(const BlockCall& proto, const CXStreamHost& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
-  if (c1 == c0) return LZ4HIP_OK;
-  ShardScope sh(ord, err);
-  if (sh.rc) return sh.rc;
-  ChunkSlot& s = sh.pair->slot[0];
-  const hipStream_t st = s.st;
-  auto produced = [&](uint32_t i) -> size_t { const int32_t r = h.out[i]; return r > 0 && (size_t)r <= pos(h.dst_cap[i]) ? (size_t)r : 0; };   // (h.out: once it is back)
-  const size_t chunk_src = (size_t)env_int("LZ4HIP_HOST_CHUNK_MB", 64, 1, 1024) << 20, chunk_dst = (size_t)512u << 20;
+// One device's share [c0, c1) of such a call: the frame of chain_shard (chunks of 64 MiB of image or 512 MiB of slots; proto.cs_*
+// and share: the share's state and slots) around the image of host_staging.h CxImage.  Per stream the used part of its window is
+// mirrored: up go the sources that can run and the history pieces -- those inside a window or in front of it where they lie in the
+// mirror, those apart once per chunk -- as runs (what a joined run carries between two pieces lands in mirror bytes nothing reads);
+// the kernel gets every offset in device terms; the results come back, then only the bytes each block produced.
+int cxstream_host_shard(const BlockCall& proto, const StreamShare& share, const CXStreamHost& h, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+  auto cost = [&](uint32_t c) {
+    staging::DsPiece p;
+    (void)staging::cxstream_piece(h.hist_end[c], h.hist_len[c], h.win_off[c], h.win_len[c], &p);
+    return staging::Cost{staging::cxstream_cost(staging::cxstream_hull(h.chain_first, c, h.src_off, h.src_len, h.hist_end[c], p, h.win_off[c]), p),
+                         staging::chain_packed_bytes(h.chain_first, c, h.dst_cap)};
+  };
   std::vector<uint64_t> dso;
   std::vector<staging::Run> runs;
-  for (uint32_t c = c0; c < c1;) {
-    // the next chunk: streams [c, j), blocks [b0, b1)
-    const staging::Chunk ck = staging::cut_chunk(c, c1, UINT32_MAX, chunk_src, chunk_dst, [&](uint32_t j) {
-      size_t d = 0;
-      for (uint32_t i = h.chain_first[j]; i < h.chain_first[j + 1]; i++) d += al16(pos(h.dst_cap[i]));
-      staging::DsPiece p;
-      (void)staging::cxstream_piece(h.hist_end[j], h.hist_len[j], h.win_off[j], h.win_len[j], &p);
-      return staging::Cost{staging::cxstream_cost(staging::cxstream_hull(h.chain_first, j, h.src_off, h.src_len, h.hist_end[j], p, h.win_off[j]), p), d};
-    });
-    const uint32_t j = ck.end, b0 = h.chain_first[c], b1 = h.chain_first[j], nb = b1 - b0, nc = j - c;
+  return chain_shard(ord, h.chain_first, c0, c1, err, cost, [&](ShardScope& sh, ChunkSlot& s, const ChainChunk& ck) {
+    const uint32_t c = ck.c, j = ck.j, b0 = ck.b0, nb = ck.nb, nc = ck.nc;
     const staging::CxImage im(h.chain_first, c, nc, h.src_off, h.src_len, h.hist_end, h.hist_len, h.win_off, h.win_len);
-    dso.resize(nb);
-    { size_t o = 0; for (uint32_t t = 0; t < nb; t++) { dso[t] = o; o += al16(pos(h.dst_cap[b0 + t])); } }
+    (void)staging::packed_offsets(h.dst_cap + b0, nb, dso);
     const staging::CXStreamMeta m(nb, nc);
-    if (!sh.reserve(s, im.total, true, ck.dst, m.l.total)) return sh.rc;
-    uint8_t *const hs = (uint8_t*)s.h_src.p, *const ds = (uint8_t*)s.d_src.p, *const hd = (uint8_t*)s.h_dst.p;
+    if (!sh.reserve(s, im.total, true, ck.dst, m.l.total)) return false;
+    uint8_t *const hs = (uint8_t*)s.h_src.p, *const ds = (uint8_t*)s.d_src.p;
     void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
     m.l.zero_results(hm);
     runs.clear();
@@ -1317,34 +1311,27 @@ int cxstream_host_shard(const BlockCall& proto, const CXStreamHost& h, int ord, 
       memcpy(hs + a.dev, h.src + a.end - a.keep, (size_t)a.keep);
       runs.push_back(staging::Run{a.dev, (size_t)a.keep});
     }
-    staging::merge_runs(runs);
     for (uint32_t t = 0; t < nc; t++) {
       for (uint32_t i = h.chain_first[c + t]; i < h.chain_first[c + t + 1]; i++) m.src_off.in(hm)[i - b0] = im.to_dev(t, h.src_off[i]);
       m.hist_end.in(hm)[t] = im.hist_dev[t];
       m.hist_len.in(hm)[t] = (int32_t)im.piece[t].keep;
-      const uint32_t id = proto.cs_ids[c + t];
-      m.slot.in(hm)[t] = (id - proto.cs_id0) | (proto.cs_poisoned && proto.cs_poisoned[id] ? lz4hip::kStreamForceStop : 0u);
     }
+    staging::stream_slots(share.ids + c, nc, share.id0, share.poisoned, m.slot.in(hm));
     memcpy(m.dst_off.in(hm), dso.data(), m.dst_off.bytes());
     memcpy(m.src_len.in(hm), h.src_len + b0, m.src_len.bytes());
     memcpy(m.dst_cap.in(hm), h.dst_cap + b0, m.dst_cap.bytes());
-    for (uint32_t t = 0; t <= nc; t++) m.first.in(hm)[t] = h.chain_first[c + t] - b0;
-    for (const staging::Run& r : runs)
-      if (!sh.ok("H2D src", hipMemcpyAsync(ds + r.off, hs + r.off, r.len, hipMemcpyHostToDevice, st))) return sh.rc;
-    if (!sh.upload(s, 0, m.l, st)) return sh.rc;
+    staging::rebase_first(h.chain_first, c, nc, m.first.in(hm));
+    // (the source goes up as runs: upload() carries the metadata alone)
+    if (!sh.upload_runs(s, s.h_src, s.d_src, runs, "H2D src") || !sh.upload(s, 0, m.l, s.st)) return false;
     const lz4hip::CXStreamArgs a{{{ds, nullptr, m.hist_len.in(dm), m.src_len.in(dm), m.first.in(dm), (uint8_t*)s.d_dst.p, m.dst_off.in(dm), m.dst_cap.in(dm),
                                    m.out.in(dm), m.consumed.in(dm), nb, nc}, m.slot.in(dm), proto.cs_rec, proto.cs_tables}, m.src_off.in(dm), m.hist_end.in(dm)};
     BlockCall call = proto; call.cxstream = &a;
-    if (proto.cs_launched) *proto.cs_launched = true;
-    if (!sh.launched(launch_block(call, lz4hip::BatchArgs{}, st)) || !sh.fetch_results(s, m.l, st) || !sh.wait(st)) return sh.rc;
+    if (share.launched) *share.launched = true;
+    if (!sh.run(call, s, m.l)) return false;
     memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
     memcpy(h.chain_consumed + c, m.consumed.in(hm), m.consumed.bytes());
-    // only the bytes produced come back
-    if (!sh.fetch_runs(s, nb, [&](uint32_t t) { return staging::Run{(size_t)dso[t], produced(b0 + t)}; })) return sh.rc;
-    par_blocks(b0, b1, ck.dst, [=, &dso](uint32_t i) { if (const size_t r = produced(i)) memcpy(h.dst + h.dst_off[i], hd + dso[i - b0], r); });
-    c = j;
-  }
-  return LZ4HIP_OK;
+    return sh.hand_back_produced(s, b0, ck.b1, ck.dst, dso, h.dst, h.dst_off, h.dst_cap, h.out);
+  });
 }
 
 // hashes of one device's share [b0, b1) of a host batch: the same pinned, double-buffered staging as host_shard (chunks of
@@ -1368,8 +1355,7 @@ int xxh_shard(bool is64, int ord, const uint8_t* buf, const uint64_t* off, const
     if (!finish(s)) break;
     const staging::Chunk ck = staging::cut_chunk(i, b1, CHUNK_BLOCKS, CHUNK_SRC, SIZE_MAX, [&](uint32_t t) { return staging::Cost{al16(pos(len[t])), 0}; });
     const uint32_t j = ck.end, nb = j - i;
-    s.so.resize(nb);
-    { size_t so = 0; for (uint32_t t = 0; t < nb; t++) { s.so[t] = so; so += al16(pos(len[i + t])); } }
+    (void)staging::packed_offsets(len + i, nb, s.so);
     const staging::HashMeta<T> m(nb);
     if (!sh.reserve(s, ck.src, false, 0, m.l.total)) break;
     uint8_t* const hs = (uint8_t*)s.h_src.p;
@@ -1871,7 +1857,7 @@ struct lz4hip_cstreams {
   struct Part { int ord = 0; uint32_t lo = 0, hi = 0; uint32_t* rec = nullptr; uint64_t* tables = nullptr; };
   uint32_t n = 0;
   std::vector<Part> parts;
-  // streams a call that failed after its launch has named: stopped at their next call (the slot's kStreamForceStop) and reported as
+  // streams a call that failed after its launch has named: stopped at their next call (the slot's force-stop mark) and reported as
   // stopped, until they are reset
   std::vector<uint8_t> poisoned;
   std::mutex mu;   // calls on one set are serialised, as the streaming-xxhash handles are
@@ -1886,40 +1872,37 @@ void cstreams_release(lz4hip_cstreams* set) {
   }
   delete set;
 }
-// the argument errors of a stream call that can be seen without a device: what does not depend on the set first (so that it is said,
-// and can be tested, where no set can exist), then the set, then the ids against it
-const char* cstream_arg_error(const lz4hip_cstreams* set, const uint32_t* stream_id, const lz4hip::CChainArgs& h) {
-  if (h.n_chains != 0 || h.n_blocks != 0) {
+// the argument errors of a call on a set that can be seen without a device: what does not depend on the set first (so that it is said,
+// and can be tested, where no set can exist) -- the ids' array, what the call's own arrays say (arrays() -> a message or nullptr; not
+// asked of an empty call), the ids' order -- then the set, then the ids against it
+template <class Arrays>
+const char* stream_call_error(const lz4hip_cstreams* set, const uint32_t* stream_id, uint32_t n_blocks, uint32_t n_chains, Arrays arrays) {
+  if (n_chains != 0 || n_blocks != 0) {
     if (!stream_id) return kNullArg;
-    if (const char* why = cchain_arg_error(h, true, true)) return why;
-    for (uint32_t c = 1; c < h.n_chains; c++)
+    if (const char* why = arrays()) return why;
+    for (uint32_t c = 1; c < n_chains; c++)
       if (stream_id[c] <= stream_id[c - 1]) return "stream_id must be strictly ascending";
   }
   if (!set) return "null stream set";
-  for (uint32_t c = 0; c < h.n_chains; c++) {
+  for (uint32_t c = 0; c < n_chains; c++) {
     if (stream_id[c] >= set->n) return "stream_id out of range";
   }
   return nullptr;
 }
-// the argument errors of lz4hip_compress_fast_stream_ext_batch, in the same order: the arrays, then the set, then the ids against it
+const char* cstream_arg_error(const lz4hip_cstreams* set, const uint32_t* stream_id, const lz4hip::CChainArgs& h) {
+  return stream_call_error(set, stream_id, h.n_blocks, h.n_chains, [&] { return cchain_arg_error(h, true, true); });
+}
+// ... of lz4hip_compress_fast_stream_ext_batch
 const char* cxstream_arg_error(const lz4hip_cstreams* set, const uint32_t* stream_id, const CXStreamHost& h) {
-  if (h.n_chains != 0 || h.n_blocks != 0) {
-    if (!stream_id || !h.src || !h.src_off || !h.src_len || !h.chain_first || !h.hist_end || !h.hist_len || !h.win_off || !h.win_len || !h.dst || !h.dst_off ||
-        !h.dst_cap || !h.out || !h.chain_consumed) return kNullArg;
-    if (const char* why = staging::cxstream_shape_error(h.chain_first, h.n_chains, h.n_blocks, h.src_off, h.src_len, h.hist_end, h.hist_len, h.win_off, h.win_len))
-      return why;
-    for (uint32_t c = 1; c < h.n_chains; c++)
-      if (stream_id[c] <= stream_id[c - 1]) return "stream_id must be strictly ascending";
-  }
-  if (!set) return "null stream set";
-  for (uint32_t c = 0; c < h.n_chains; c++) {
-    if (stream_id[c] >= set->n) return "stream_id out of range";
-  }
-  return nullptr;
+  return stream_call_error(set, stream_id, h.n_blocks, h.n_chains, [&]() -> const char* {
+    if (!h.src || !h.src_off || !h.src_len || !h.chain_first || !h.hist_end || !h.hist_len || !h.win_off || !h.win_len || !h.dst || !h.dst_off || !h.dst_cap ||
+        !h.out || !h.chain_consumed) return kNullArg;
+    return staging::cxstream_shape_error(h.chain_first, h.n_chains, h.n_blocks, h.src_off, h.src_len, h.hist_end, h.hist_len, h.win_off, h.win_len);
+  });
 }
 // One call on a set, for both entry points: whole streams per device, at the boundaries the set was created with -- [c0, c1) of the
-// call's chains are part p's -- every share through shard(call, ord, c0, c1, err) with the share's state in call.cs_*, side by side
-// where there are several.  The set is locked for the call.
+// call's chains are part p's -- every share through shard(call, share, ord, c0, c1, err) with the share's state in call.cs_* and what
+// the host path needs beside it in share (StreamShare), side by side where there are several.  The set is locked for the call.
 template <class Shard>
 int cstreams_call(lz4hip_cstreams* set, const uint32_t* stream_id, uint32_t n_chains, Op op, Shard shard) {
   std::lock_guard<std::mutex> lk(set->mu);
@@ -1936,9 +1919,9 @@ int cstreams_call(lz4hip_cstreams* set, const uint32_t* stream_id, uint32_t n_ch
   (void)hipGetDevice(&prev);
   auto run = [&](Share& s) {
     BlockCall call{op};
-    call.cs_rec = s.p->rec; call.cs_tables = s.p->tables; call.cs_ids = stream_id; call.cs_id0 = s.p->lo; call.cs_poisoned = set->poisoned.data();
-    call.cs_launched = &s.launched;
-    try { s.rc = shard(call, s.p->ord, s.c0, s.c1, &s.err); }
+    call.cs_rec = s.p->rec; call.cs_tables = s.p->tables;
+    const StreamShare share{stream_id, s.p->lo, set->poisoned.data(), &s.launched};
+    try { s.rc = shard(call, share, s.p->ord, s.c0, s.c1, &s.err); }
     catch (...) { s.rc = LZ4HIP_E_NOMEM; s.err = "out of memory"; }
   };
   if (shares.size() == 1) {
@@ -2222,32 +2205,25 @@ int lz4hip_decompress_safe_chain_batch(const uint8_t* src, const uint64_t* src_o
                                        uint32_t n_blocks, uint32_t n_chains) {
   const lz4hip::ChainArgs h{src, src_off, src_len, stored, dst_cap, chain_first, dst, chain_dst_off, chain_dst_cap, chain_prefix_len, out_len, chain_out_len,
                             n_blocks, n_chains};
-  if (const char* why = chain_arg_error(h, true)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
-  if (const int rc = need_device()) return rc;
-  if (n_chains == 0) return LZ4HIP_OK;
   // whole chains per device: a chain never leaves its lane group, let alone its device
-  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return chain_host_shard(h, ord, c0, c1, err); });
+  return chain_entry(chain_arg_error(h, true), n_chains, [&] { return whole_chains(n_chains, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return chain_host_shard(h, ord, c0, c1, err); }); });
 }
 int lz4hip_decompress_safe_stream_batch(lz4hip_dstream_state* state, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                         const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                         const uint64_t* chain_win_off, const uint64_t* chain_win_len, int32_t* out_len, uint32_t n_blocks,
                                         uint32_t n_chains) {
   const DStreamHost h{state, src, src_off, src_len, chain_first, dst, dst_off, dst_cap, chain_win_off, chain_win_len, out_len, n_blocks, n_chains};
-  if (const char* why = dstream_arg_error(h)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
-  if (const int rc = need_device()) return rc;
-  if (n_chains == 0) return LZ4HIP_OK;
   // whole streams per device: a stream never leaves its lane group, let alone its device
-  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return dstream_host_shard(h, ord, c0, c1, err); });
+  return chain_entry(dstream_arg_error(h), n_chains, [&] { return whole_chains(n_chains, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return dstream_host_shard(h, ord, c0, c1, err); }); });
 }
 int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
                                      const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
                                      uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains) {
   const lz4hip::CChainArgs h{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains};
-  if (const char* why = cchain_arg_error(h, true, op_chain_stops(OP_COMPRESS_CHAIN))) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
-  if (const int rc = need_device()) return rc;
-  if (n_chains == 0) return LZ4HIP_OK;
   // whole chains per device: a chain never leaves its wavefront, let alone its device
-  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard({OP_COMPRESS_CHAIN}, h, ord, c0, c1, err); });
+  return chain_entry(cchain_arg_error(h, true, op_chain_stops(OP_COMPRESS_CHAIN)), n_chains, [&] {
+    return whole_chains(n_chains, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard({OP_COMPRESS_CHAIN}, {}, h, ord, c0, c1, err); });
+  });
 }
 int lz4hip_cstreams_create(uint32_t n_streams, lz4hip_cstreams** out) {
   if (!out || n_streams == 0 || n_streams > 0x7FFFFFFFu) return fail(LZ4HIP_E_ARG, !out ? kNullArg : "n_streams must be 1 .. 2^31 - 1");
@@ -2348,11 +2324,11 @@ int lz4hip_compress_fast_stream_batch(lz4hip_cstreams* set, const uint32_t* stre
                                       const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks,
                                       uint32_t n_chains) {
   const lz4hip::CChainArgs h{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains};
-  if (const char* why = cstream_arg_error(set, stream_id, h)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
-  if (const int rc = need_device()) return rc;
-  if (n_chains == 0) return LZ4HIP_OK;
-  return cstreams_call(set, stream_id, n_chains, OP_COMPRESS_STREAM,
-                       [&](const BlockCall& call, int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard(call, h, ord, c0, c1, err); });
+  return chain_entry(cstream_arg_error(set, stream_id, h), n_chains, [&] {
+    return cstreams_call(set, stream_id, n_chains, OP_COMPRESS_STREAM, [&](const BlockCall& call, const StreamShare& share, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+      return cchain_host_shard(call, share, h, ord, c0, c1, err);
+    });
+  });
 }
 int lz4hip_compress_fast_stream_ext_batch(lz4hip_cstreams* set, const uint32_t* stream_id, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                           const uint32_t* chain_first, const uint64_t* chain_hist_end, const int32_t* chain_hist_len,
@@ -2360,35 +2336,33 @@ int lz4hip_compress_fast_stream_ext_batch(lz4hip_cstreams* set, const uint32_t* 
                                           const int32_t* dst_cap, int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains) {
   const CXStreamHost h{src, src_off, src_len, chain_first, chain_hist_end, chain_hist_len, chain_win_off, chain_win_len, dst, dst_off, dst_cap, out_len,
                        chain_consumed, n_blocks, n_chains};
-  if (const char* why = cxstream_arg_error(set, stream_id, h)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
-  if (const int rc = need_device()) return rc;
-  if (n_chains == 0) return LZ4HIP_OK;
-  return cstreams_call(set, stream_id, n_chains, OP_COMPRESS_XSTREAM,
-                       [&](const BlockCall& call, int ord, uint32_t c0, uint32_t c1, std::string* err) { return cxstream_host_shard(call, h, ord, c0, c1, err); });
+  return chain_entry(cxstream_arg_error(set, stream_id, h), n_chains, [&] {
+    return cstreams_call(set, stream_id, n_chains, OP_COMPRESS_XSTREAM, [&](const BlockCall& call, const StreamShare& share, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+      return cxstream_host_shard(call, share, h, ord, c0, c1, err);
+    });
+  });
 }
 int lz4hip_compress_hc_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
                                    const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
                                    uint32_t n_blocks, uint32_t n_chains, int level) {
   const lz4hip::CChainArgs h{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, nullptr, n_blocks, n_chains};
-  if (const char* why = cchain_arg_error(h, true, op_chain_stops(OP_COMPRESS_HC_CHAIN))) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
-  if (const int rc = need_device()) return rc;
-  if (n_chains == 0) return LZ4HIP_OK;
-  int lv;
-  if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
   // whole chains per device: a device's workspace and staging hold a chain's buffer in one piece
-  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard({OP_COMPRESS_HC_CHAIN, lv}, h, ord, c0, c1, err); });
+  return chain_entry(cchain_arg_error(h, true, op_chain_stops(OP_COMPRESS_HC_CHAIN)), n_chains, [&]() -> int {
+    int lv;
+    if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
+    return whole_chains(n_chains, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard({OP_COMPRESS_HC_CHAIN, lv}, {}, h, ord, c0, c1, err); });
+  });
 }
 int lz4hip_compress_hc_stream_batch(lz4hip_hcstream_state* state, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
                                     const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
                                     uint32_t n_blocks, uint32_t n_chains, int level) {
   const HcStreamHost h{state, src, src_off, src_len, chain_first, dst, dst_off, dst_cap, out_len, n_blocks, n_chains};
-  if (const char* why = hcstream_arg_error(h)) return fail(LZ4HIP_E_ARG, why);   // (said without a device too)
-  if (const int rc = need_device()) return rc;
-  if (n_chains == 0) return LZ4HIP_OK;
-  int lv;
-  if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
   // whole streams per device: a device's workspace and staging hold a stream's linear buffer in one piece
-  return fan_out(n_chains, 64u, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return hcstream_host_shard(lv, h, ord, c0, c1, err); });
+  return chain_entry(hcstream_arg_error(h), n_chains, [&]() -> int {
+    int lv;
+    if (hc_level(level, &lv)) return LZ4HIP_E_UNSUPPORTED;
+    return whole_chains(n_chains, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return hcstream_host_shard(lv, h, ord, c0, c1, err); });
+  });
 }
 int lz4hip_hcstream_load_dict(lz4hip_hcstream_state* st, uint64_t dict_end, uint64_t dict_len) {
   if (!st) return fail(LZ4HIP_E_ARG, kNullArg);

@@ -1,6 +1,6 @@
 // host_staging.h -- the arithmetic of staging a host batch (api.cpp's shard functions), free of HIP so that it is compiled and tested
 // without a device (tests/cpp/host_staging_test.cpp): where a chunk's metadata arrays lie in their one buffer, where a chunk ends,
-// which produced bytes travel back in one copy, the shape the arrays of a chain call must have, where the windows and history
+// where its blocks lie packed and what a chunk of chains calls its chains and slots, which produced bytes travel back in one copy, the shape the arrays of a chain call must have, where the windows and history
 // pieces of a stream-decode call lie in the device image, and where the used parts of the windows and the history pieces of a
 // stream-compress call whose sources land anywhere lie in theirs, and the state machine and the linear image of an HC stream-compress
 // call (one buffer per stream in liblz4's index space).
@@ -14,6 +14,7 @@
 namespace staging {
 
 inline size_t al16(size_t v) { return (v + 15u) & ~(size_t)15u; }   // (every packed source and slot starts on a 16-byte boundary)
+inline size_t pos(int32_t v) { return v > 0 ? (size_t)v : 0; }      // (a negative length or capacity takes no bytes in the staging)
 
 // n elements of T at byte `off` of a metadata buffer: the same offset in the pinned host copy and in the device copy
 template <class T>
@@ -125,6 +126,32 @@ Chunk cut_chunk(uint32_t begin, uint32_t end, uint32_t max_units, size_t src_lim
     c.src += u.src; c.dst += u.dst; c.end++;
   }
   return c;
+}
+
+// Blocks packed one behind the other, each from a 16-byte boundary, a negative length as no bytes: where each of the n blocks starts
+// (off is resized to n) -> the bytes they take together
+inline size_t packed_offsets(const int32_t* len, size_t n, std::vector<uint64_t>& off) {
+  off.resize(n);
+  size_t o = 0;
+  for (size_t t = 0; t < n; t++) { off[t] = o; o += al16(pos(len[t])); }
+  return o;
+}
+// ... and what the blocks of chain c take of that: [chain_first[c], chain_first[c + 1]) of len[]
+inline size_t chain_packed_bytes(const uint32_t* chain_first, uint32_t c, const int32_t* len) {
+  size_t sum = 0;
+  for (uint32_t i = chain_first[c]; i < chain_first[c + 1]; i++) sum += al16(pos(len[i]));
+  return sum;
+}
+// chain_first[] of the chunk that holds the chains [c, c + nc) and nothing else: first[0 .. nc], counted from the chunk's first block
+inline void rebase_first(const uint32_t* chain_first, uint32_t c, uint32_t nc, uint32_t* first) {
+  for (uint32_t t = 0; t <= nc; t++) first[t] = chain_first[c + t] - chain_first[c];
+}
+// The slot words of nc chains that continue resident streams: stream ids[t] lies in slot ids[t] - id0 of its device's share of the set
+// (id0: the id of the share's slot 0); a stream marked in poisoned[] (by id; may be nullptr) is told to stop (kSlotForceStop: the
+// kernels' kStreamForceStop)
+constexpr uint32_t kSlotForceStop = 0x80000000u;
+inline void stream_slots(const uint32_t* ids, uint32_t nc, uint32_t id0, const uint8_t* poisoned, uint32_t* slot) {
+  for (uint32_t t = 0; t < nc; t++) slot[t] = (ids[t] - id0) | (poisoned && poisoned[ids[t]] ? kSlotForceStop : 0u);
 }
 
 // Only the bytes produced come back: entry(t) -> where entry t starts in the packed destination and how much it produced (0: skipped),

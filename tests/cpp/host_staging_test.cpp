@@ -1,5 +1,5 @@
 // tests/cpp/host_staging_test.cpp -- the arithmetic of lz4-java_amd/csrc/host_staging.h against naive restatements written here: the
-// metadata layouts, the chunk cut, the run plan and the chain-shape check.  It includes nothing else of the project and needs no device;
+// metadata layouts, the chunk cut, the run plan, the chain-shape check and what a chunk of chains calls its blocks, chains and slots.  It includes nothing else of the project and needs no device;
 // tests/test_host_staging.py builds it with the address and undefined-behaviour sanitizers and runs it.  Exit status 0 and "ok", or the
 // first failed check on stderr.
 #include "../../lz4-java_amd/csrc/host_staging.h"
@@ -234,12 +234,88 @@ static void test_shape() {
   }
 }
 
+// ---- what a chunk of chains calls its blocks, chains and slots ----
+static void test_chain_frame() {
+  int cases = 0;
+  // packed offsets: negative and zero lengths take no bytes, every other block starts on the next 16-byte boundary
+  const int32_t len[] = {5, -1, 0, 16, 17, INT32_MIN, 4096, 1, -7, 33};
+  const uint64_t want_off[] = {0, 16, 16, 16, 32, 64, 64, 4160, 4176, 4176};
+  std::vector<uint64_t> off(3, 99);   // (resized, not appended to)
+  CHECK(packed_offsets(len, 10, off) == 4176 + 48 && off == std::vector<uint64_t>(want_off, want_off + 10), "packed offsets of 10 blocks"); cases++;
+  CHECK(packed_offsets(len + 3, 2, off) == 48 && off == std::vector<uint64_t>({0, 16}), "packed offsets from block 3"); cases++;
+  CHECK(packed_offsets(len, 0, off) == 0 && off.empty(), "packed offsets of no blocks"); cases++;
+  std::mt19937_64 rng(31);
+  for (int round = 0; round < 500; round++) {   // against the naive sum, and against chain_packed_bytes over any cut into chains
+    const size_t n = rng() % 50;
+    std::vector<int32_t> l(n);
+    for (int32_t& v : l) v = (int32_t)(rng() % 5 == 0 ? -(int64_t)(rng() % 100000) : rng() % 3 ? rng() % 70 : rng() % 100000);
+    const size_t total = packed_offsets(l.data(), n, off);
+    size_t at = 0;
+    for (size_t t = 0; t < n; t++) {
+      CHECK(off[t] == at && at % 16 == 0, "round %d: block %zu at %zu, naive %zu", round, t, (size_t)off[t], at);
+      at += l[t] > 0 ? ((size_t)l[t] + 15) / 16 * 16 : 0;
+    }
+    CHECK(total == at, "round %d: total %zu, naive %zu", round, total, at);
+    std::vector<uint32_t> first{0};
+    while (first.back() < n) first.push_back(std::min<uint32_t>((uint32_t)n, first.back() + (uint32_t)(rng() % 7)));   // (empty chains included)
+    size_t sum = 0;
+    for (uint32_t c = 0; c + 1 < first.size(); c++) {
+      const size_t b = chain_packed_bytes(first.data(), c, l.data());
+      CHECK(b == (first[c + 1] < n ? off[first[c + 1]] : total) - (first[c] < n ? off[first[c]] : total), "round %d: chain %u takes %zu", round, c, b);
+      sum += b;
+    }
+    CHECK(sum == total, "round %d: the chains take %zu of %zu", round, sum, total);
+    cases++;
+  }
+  // the per-chain sum: an empty chain at the front, in the middle and at the end takes nothing, whatever its neighbours hold
+  const uint32_t cf[] = {0, 0, 2, 2, 5, 5};
+  const int32_t cl[] = {100, -3, 7, 16, 0};
+  const size_t want_sum[] = {0, 112, 0, 32, 0};
+  for (uint32_t c = 0; c < 5; c++) { CHECK(chain_packed_bytes(cf, c, cl) == want_sum[c], "chain %u of the empty-chain case", c); cases++; }
+  // first[] rebased: a chunk that starts at chain 0, one that does not, one of a single empty chain, one of no chains
+  const uint32_t first[] = {0, 3, 3, 10, 11, 40, 40, 57};
+  uint32_t out[9];
+  auto rebased = [&](uint32_t c, uint32_t nc, std::vector<uint32_t> want) {
+    std::fill(out, out + 9, 0xDEADu);
+    rebase_first(first, c, nc, out);
+    for (uint32_t t = 0; t <= nc; t++) CHECK(out[t] == want[t], "rebase_first(%u, %u)[%u] = %u", c, nc, t, out[t]);
+    CHECK(out[nc + 1] == 0xDEADu, "rebase_first(%u, %u) wrote past first[nc]", c, nc);
+    cases++;
+  };
+  rebased(0, 7, {0, 3, 3, 10, 11, 40, 40, 57});
+  rebased(0, 2, {0, 3, 3});
+  rebased(2, 3, {0, 7, 8, 37});
+  rebased(3, 4, {0, 1, 30, 30, 47});
+  rebased(5, 1, {0, 0});
+  rebased(6, 1, {0, 17});
+  rebased(4, 0, {0});
+  // the slot words: a share whose slot 0 is stream 100 (and one whose slot 0 is stream 0), with and without marks; the marks are by id
+  std::vector<uint8_t> poisoned(200, 0);
+  poisoned[104] = 1; poisoned[4] = 1; poisoned[199] = 1;   // (4 = 104 - 100: a mark looked up by slot would stop the wrong stream)
+  const uint32_t ids[] = {100, 101, 104, 150, 199};
+  uint32_t slot[6] = {7, 7, 7, 7, 7, 7};
+  stream_slots(ids, 5, 100, poisoned.data(), slot);
+  CHECK(slot[0] == 0 && slot[1] == 1 && slot[2] == (4u | 0x80000000u) && slot[3] == 50 && slot[4] == (99u | 0x80000000u) && slot[5] == 7, "slots of a share from 100, marked"); cases++;
+  stream_slots(ids, 5, 100, nullptr, slot);
+  CHECK(slot[0] == 0 && slot[1] == 1 && slot[2] == 4 && slot[3] == 50 && slot[4] == 99 && slot[5] == 7, "slots of a share from 100, no marks"); cases++;
+  stream_slots(ids + 2, 2, 100, poisoned.data(), slot);   // (a later chunk of the share: the ids from chain 2 on)
+  CHECK(slot[0] == (4u | 0x80000000u) && slot[1] == 50 && slot[2] == 4, "slots of a chunk that starts at chain 2"); cases++;
+  const uint32_t low[] = {0, 4, 5};
+  stream_slots(low, 3, 0, poisoned.data(), slot);
+  CHECK(slot[0] == 0 && slot[1] == (4u | 0x80000000u) && slot[2] == 5, "slots of a share from 0"); cases++;
+  stream_slots(low, 0, 0, poisoned.data(), slot);
+  CHECK(slot[0] == 0, "no chains, no slots"); cases++;
+  CHECK(kSlotForceStop == 0x80000000u && pos(-1) == 0 && pos(0) == 0 && pos(INT32_MIN) == 0 && pos(INT32_MAX) == (size_t)INT32_MAX, "the mark and pos"); cases++;
+  fprintf(stderr, "chain frame helpers (packed_offsets, chain_packed_bytes, rebase_first, stream_slots): %d cases\n", cases);
+}
+
 int main() {
   CHECK(al16(0) == 0 && al16(1) == 16 && al16(16) == 16 && al16(17) == 32, "al16");
   test_layouts();
   test_cut();
   test_runs();
   test_shape();
+  test_chain_frame();
   puts("ok");
   return 0;
 }

@@ -96,6 +96,26 @@ def test_64_streams_against_the_reference_and_the_one_call_chain(amd, rc, sixty_
             decoded[i] += dbuf[o:o + n]
 
 
+def test_every_third_of_120_streams_in_1_mib_chunks(amd, rc, monkeypatch):
+    """the host call with 1 MiB chunks (LZ4HIP_HOST_CHUNK_MB=1, read per call): 40 chains on the streams 0, 3, 6 .. 117 of a set of 120,
+    so that a chain's slot is never its index in the call, let alone in its chunk; two calls of 16 x 4 KiB per stream (2.5 MiB of source:
+    three chunks in the first call, more in the second, which has every stream's 64 KiB of history in front).  A slot taken from the wrong
+    chain of a second or third chunk continues another stream's text: bytes, return values and the set's own count all say so"""
+    monkeypatch.setenv("LZ4HIP_HOST_CHUNK_MB", "1")
+    b = book1()
+    ids = list(range(0, 120, 3))
+    lives = [life_of("stream %d" % i, b[5000 * i + 7:5000 * i + 7 + 32 * 4096], [4096] * 32, (16,)) for i in ids]
+    assert len(lives) == 40 and all(len(l.calls) == 2 and len(l.calls[0].data) == 65536 for l in lives)
+    eng = DevEngine(amd, 120)
+    try:
+        bad, _, rounds = drive(eng, rc, lives, random.Random(78), absent=0.0, ids=ids)
+        assert not bad, (len(bad), bad[:5])
+        assert rounds == 2
+        assert eng.consumed() == ([32 * 4096 if i % 3 == 0 else 0 for i in range(120)], [0] * 120)
+    finally:
+        eng.close()
+
+
 def test_6000_streams_three_calls_of_one_block(amd, rc):
     """more streams than resident wavefronts, every stream in every call: a table carried into the next stream a wavefront draws, or a
     state saved to the wrong slot, changes bytes.  Stream i repeats in call k what it -- and nobody else -- saw in the calls before"""
