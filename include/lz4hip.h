@@ -347,16 +347,49 @@ int lz4hip_decompress_safe_stream_batch(lz4hip_dstream_state* state, const uint8
  *     number of chains alone.  The compress_* knobs do not apply;
  *   - the host form uploads each chain's source with the last min(P, 65536) bytes of its history, brings back only the bytes
  *     produced, and shards over the initialised devices at chain boundaries;
- *   - out of scope: acceleration above 1; LZ4_saveDict and resuming a stream's exact state across calls (the prefix is LZ4_loadDict's
+ *   - out of scope: LZ4_saveDict and resuming a stream's exact state across calls (the prefix is LZ4_loadDict's
  *     table, which is not the table a running stream would hold: continuing a stream in a second call gives valid, decodable, but
  *     other bytes than one long chain); sources that are not contiguous; LZ4_attach_dictionary.  (No longer out of scope: an HC form
  *     is lz4hip_compress_hc_chain_batch, below.)  (No longer out of scope: resuming a stream's exact state across calls, LZ4_saveDict
  *     included, is lz4hip_compress_fast_stream_batch, below.)  (No longer out of scope: sources that are not contiguous, on a
- *     resident stream, is lz4hip_compress_fast_stream_ext_batch, below.)                                                            */
+ *     resident stream, is lz4hip_compress_fast_stream_ext_batch, below.)  (No longer out of scope: acceleration above 1 is
+ *     lz4hip_compress_fast_chain_accel_batch, below.)                                                                               */
 int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
                                      const int32_t* src_len, const uint32_t* chain_first,
                                      uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                      int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains);
+/* LINKED BLOCKS WITH AN ACCELERATION: the three linked-block fast compressors -- chains (above), resident streams and resident streams
+ * whose sources land anywhere (lz4hip_compress_fast_stream_batch and lz4hip_compress_fast_stream_ext_batch, below) -- with the last
+ * argument of LZ4_compress_fast_continue(stream, src, dst, srcSize, dstCapacity, acceleration), liblz4 1.9.3.  Each has the argument
+ * list of its acceleration-1 twin plus a trailing `int acceleration`, and the twin's contract word for word; these are the blocks that
+ * `lz4 --fast=N` writes (the lz4 command line links blocks by default and hands N to that call).
+ *   - ONE acceleration per call, for every block of every chain or stream in it.  It is clamped as liblz4 does: < 1 -> 1, > 65537
+ *     (LZ4_ACCELERATION_MAX) -> 65537;
+ *   - after clamping, acceleration 1 IS the twin: same call, same kernels, same bytes (as lz4hip_compress_fast_accel_batch is
+ *     lz4hip_compress_fast_batch at 1);
+ *   - acceleration changes where a miss run probes and nothing else: every run starts with liblz4's searchMatchNb = acceleration << 6
+ *     instead of 1 << 6, and the table's contents follow from that.  Return values' meaning, the stop rule (a result of 0 ends the
+ *     chain or stops the stream), the 0x7E000000 limit, blocks under 13 bytes, the prefix and history rules, argument errors, sharding
+ *     and staging are the twins';
+ *   - a stream's record and 32 KB table image keep their format: one stream may be driven by any mix of the six entry points, at a
+ *     different acceleration in every call.  The table a call leaves depends on its acceleration, and a later call sees that, at any
+ *     acceleration, as liblz4's does: the bytes are those of ONE LZ4_stream_t given the same sequence of accelerations;
+ *   - kernels: compress_fast_chain_accel_cu_kernel, compress_fast_stream_accel_cu_kernel, compress_fast_xstream_accel_cu_kernel --
+ *     their twins' shape (one wavefront per chain or stream, the table in LDS) over the one-sequence core's acceleration switch.  The
+ *     acceleration-1 kernels are instruction for instruction what they were (profiles/caccel_kernel_diff.txt);
+ *   - bit-exactness was shown against the reference library's own LZ4_compress_fast_continue on one LZ4_stream_t per chain or stream:
+ *     in the CPU lane simulator with its bounds checks on (tests/test_caccel_hostsim.py) and on the MI355X (tests/test_gpu_caccel.py);
+ *   - NO device-pointer (`*_dev`) forms: as for the stream families, they are left to a change that can also extend the far-offset and
+ *     stream-contract tables of the device entry points;
+ *   - out of scope: a per-block acceleration array; acceleration in the dictionary-handle form (lz4hip_compress_fast_dict*), which
+ *     remains the only fast form without it; device-pointer forms; LZ4_attach_dictionary; acceleration in the lean and
+ *     window-parallel block cores (acceleration 1 alone runs on them); byte equality with whole FRAMES written by the lz4 command
+ *     line -- header flags and block sizes are its own; the blocks are what is matched.                                             */
+int lz4hip_compress_fast_chain_accel_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
+                                           const int32_t* src_len, const uint32_t* chain_first,
+                                           uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                           int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains,
+                                           int acceleration);
 /* COMPRESS CHAINS OF LINKED BLOCKS AT AN HC LEVEL: the arrays of lz4hip_compress_fast_chain_batch without chain_consumed, and a level.
  * With chain_src = src + chain_src_off[c] and P = chain_prefix_len[c], block k of chain c is, byte for byte and in its return value,
  *     s = LZ4_createStreamHC();  LZ4_resetStreamHC_fast(s, level);  if (P > 0) LZ4_loadDictHC(s, chain_src - P, P);
@@ -494,9 +527,10 @@ int lz4hip_hcstream_save_dict(lz4hip_hcstream_state* st, uint64_t buf_off, int k
  *   - the host form uploads each chain's source with the last min(chain_prefix_len[c], 65536) bytes in front of it and brings back
  *     only the bytes produced;
  *   - out of scope: a device-pointer form (as for lz4hip_compress_hc_chain_batch: left to a change that can also extend the far-offset
- *     table of the device entry points); acceleration above 1; the external-dictionary mode (a source that does not follow its
+ *     table of the device entry points); the external-dictionary mode (a source that does not follow its
  *     history); LZ4_attach_dictionary; an HC form; streams longer than the index limit.  (No longer out of scope: the
- *     external-dictionary mode is lz4hip_compress_fast_stream_ext_batch, below.)                                                    */
+ *     external-dictionary mode is lz4hip_compress_fast_stream_ext_batch, below.)  (No longer out of scope: acceleration above 1 is
+ *     lz4hip_compress_fast_stream_accel_batch -- LINKED BLOCKS WITH AN ACCELERATION, above; it has no device-pointer form either.) */
 typedef struct lz4hip_cstreams lz4hip_cstreams;
 int lz4hip_cstreams_create(uint32_t n_streams, lz4hip_cstreams** out);
 int lz4hip_cstreams_count(const lz4hip_cstreams* set);
@@ -508,6 +542,12 @@ int lz4hip_compress_fast_stream_batch(lz4hip_cstreams* set, const uint32_t* stre
                                       const int32_t* src_len, const uint32_t* chain_first,
                                       uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                       int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains);
+int lz4hip_compress_fast_stream_accel_batch(lz4hip_cstreams* set, const uint32_t* stream_id,
+                                            const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len,
+                                            const int32_t* src_len, const uint32_t* chain_first,
+                                            uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                            int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains,
+                                            int acceleration);
 /* COMPRESS STREAMS WHOSE SOURCES LAND ANYWHERE -- a ring that wraps, two alternating buffers, a save area, a dictionary elsewhere: the
  * same sets, the same streams and THE SAME CONTRACT as lz4hip_compress_fast_stream_batch: for every stream, byte for byte and return
  * value for return value what ONE LZ4_stream_t of liblz4 1.9.3 gives over all the calls that named the stream since its creation or
@@ -539,9 +579,10 @@ int lz4hip_compress_fast_stream_batch(lz4hip_cstreams* set, const uint32_t* stre
  *     buffer, a longer block than the one before).  liblz4 then takes matches inside the block for dictionary matches and cuts them
  *     short; the engine finds the ordinary, longer ones.  Return values may differ by a few bytes; both outputs are valid LZ4.  The
  *     input is misuse either way: the history was overwritten, and liblz4's own output does not decode there;
- *   - the table is byU32, acceleration 1; a block under 13 bytes is one literal run that still moves the index space; the
- *     0x7E000000 life limit, a result of 0 stopping the stream, LZ4HIP_CHAIN_STOPPED, chain_consumed, lz4hip_cstreams_reset and
- *     lz4hip_cstreams_consumed, and what a library failure after the launch leaves behind are the call above's;
+ *   - the table is byU32, acceleration 1 (any acceleration: lz4hip_compress_fast_stream_ext_accel_batch); a block under 13 bytes is
+ *     one literal run that still moves the index space; the 0x7E000000 life limit, a result of 0 stopping the stream,
+ *     LZ4HIP_CHAIN_STOPPED, chain_consumed, lz4hip_cstreams_reset and lz4hip_cstreams_consumed, and what a library failure after the
+ *     launch leaves behind are the call above's;
  *   - the window: every source [src_off[i], + src_len[i]) of stream c lies inside [chain_win_off[c], + chain_win_len[c]) -- the ring,
  *     the pair of buffers, the save area plus the block area.  The history PIECE, the last min(chain_hist_len[c], 65536) bytes in front
  *     of chain_hist_end[c], lies wholly inside the window or wholly outside it; one that ends exactly at the window's start stays
@@ -558,13 +599,22 @@ int lz4hip_compress_fast_stream_batch(lz4hip_cstreams* set, const uint32_t* stre
  *   - the host form mirrors the USED part of every window on the device (the call's sources and the history piece), uploads each
  *     outside piece once per staged chunk, brings back only the bytes produced, and shards at the set's device ranges;
  *   - out of scope: device-pointer forms (as above: left to a change that can also extend the far-offset and stream-contract tables
- *     of the device entry points); acceleration above 1; LZ4_attach_dictionary; an HC form; streams past the index limit.          */
+ *     of the device entry points); LZ4_attach_dictionary; an HC form; streams past the index limit.  (No longer out of scope:
+ *     acceleration above 1 is lz4hip_compress_fast_stream_ext_accel_batch -- LINKED BLOCKS WITH AN ACCELERATION, above; no
+ *     device-pointer form either.)                                                                                                 */
 int lz4hip_compress_fast_stream_ext_batch(lz4hip_cstreams* set, const uint32_t* stream_id,
                                           const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, const uint32_t* chain_first,
                                           const uint64_t* chain_hist_end, const int32_t* chain_hist_len,
                                           const uint64_t* chain_win_off, const uint64_t* chain_win_len,
                                           uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
                                           int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains);
+int lz4hip_compress_fast_stream_ext_accel_batch(lz4hip_cstreams* set, const uint32_t* stream_id,
+                                                const uint8_t* src, const uint64_t* src_off, const int32_t* src_len, const uint32_t* chain_first,
+                                                const uint64_t* chain_hist_end, const int32_t* chain_hist_len,
+                                                const uint64_t* chain_win_off, const uint64_t* chain_win_len,
+                                                uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                                int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains,
+                                                int acceleration);
 /* COMPRESS AGAINST A DICTIONARY: for every block i, on a fresh stream,
  *     LZ4_loadDict(s, dict, dict_len);  LZ4_compress_fast_continue(s, src_i, dst_i, src_len[i], dst_cap[i], 1)
  * of liblz4 1.9.3 with a dictionary that is NOT contiguous with the source (its external-dictionary mode): the return value and the
@@ -581,8 +631,8 @@ int lz4hip_compress_fast_stream_ext_batch(lz4hip_cstreams* set, const uint32_t* 
  *     memory per device, built by a kernel at the handle's first compress on that device (that one call waits for its stream once;
  *     a handle that only decodes never has one) and freed by lz4hip_dict_free;
  *   - one kernel, compress_fast_dict_cu_kernel: the one-sequence core with its DICT switch, five wavefronts per CU, each loading its
- *     table from the image per block; acceleration is 1, there is no attach-dictionary or prefix form and no LZ4_saveDict (the HC
- *     form is lz4hip_compress_hc_dict* below);
+ *     table from the image per block; acceleration is 1 (the only fast form without the knob), there is no attach-dictionary or
+ *     prefix form and no LZ4_saveDict (the HC form is lz4hip_compress_hc_dict* below);
  *   - dict == NULL is LZ4HIP_E_ARG, no device LZ4HIP_E_NO_DEVICE; the host batch shards over the initialised devices and brings
  *     back only the bytes each block produced, as lz4hip_compress_fast_batch does;
  *   - single calls (lz4hip_compress_fast_dict) are coalesced only with concurrent compress calls on the SAME handle.            */

@@ -67,6 +67,8 @@ C_ABI = {
                                                       C.c_uint32, C.c_uint32]),
     "lz4hip_compress_fast_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32]),
     "lz4hip_compress_fast_chain_batch_dev": (C.c_int, [C.c_void_p] * 10 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
+    "lz4hip_compress_fast_chain_accel_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32,
+                                                         C.c_int]),
     "lz4hip_compress_hc_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_uint32, C.c_int]),
     "lz4hip_compress_hc_stream_batch": (C.c_int, [_u64p, C.c_void_p, _u64p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, C.c_uint32, C.c_uint32, C.c_int]),
     "lz4hip_hcstream_load_dict": (C.c_int, [_u64p, C.c_uint64, C.c_uint64]),
@@ -80,6 +82,10 @@ C_ABI = {
                                                     C.c_uint32, C.c_uint32]),
     "lz4hip_compress_fast_stream_ext_batch": (C.c_int, [C.c_void_p, _u32p, C.c_void_p, _u64p, _i32p, _u32p, _u64p, _i32p, _u64p, _u64p, C.c_void_p, _u64p,
                                                         _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32]),
+    "lz4hip_compress_fast_stream_accel_batch": (C.c_int, [C.c_void_p, _u32p, C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p,
+                                                          C.c_uint32, C.c_uint32, C.c_int]),
+    "lz4hip_compress_fast_stream_ext_accel_batch": (C.c_int, [C.c_void_p, _u32p, C.c_void_p, _u64p, _i32p, _u32p, _u64p, _i32p, _u64p, _u64p, C.c_void_p, _u64p,
+                                                              _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32, C.c_int]),
     "lz4hip_xxh32_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint32, _u32p, C.c_uint32]),
     "lz4hip_xxh64_batch": (C.c_int, [C.c_void_p, _u64p, _i32p, C.c_uint64, _u64p, C.c_uint32]),
     "lz4hip_compress_fast_batch_dev": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_int, C.c_void_p]),
@@ -1062,33 +1068,39 @@ class LZ4HIPBatch:
         return list(out[:n]), new
 
     @classmethod
-    def compressFastChain(cls, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None):
+    def compressFastChain(cls, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None, acceleration=1):
         """LZ4_compress_fast_continue over chains of linked blocks (lz4hip_compress_fast_chain_batch): chain c is the blocks
         chainFirst[c] .. chainFirst[c + 1] - 1, whose sources lie back to back from src[chainSrcOff[c]] on, behind chainPrefixLen[c]
         bytes of history that lie in front of it in src (None: no history; the stream loads it with LZ4_loadDict); block i owns the
         slot dst[dstOff[i]:+dstCap[i]] -> (outLen, chainConsumed): liblz4's return value per block (0: it did not fit, which ends
         the chain; CHAIN_STOPPED behind a chain's first 0) and the source bytes of each chain's blocks that succeeded (lists, or
-        int32 / uint64 arrays for numpy inputs)"""
+        int32 / uint64 arrays for numpy inputs).  acceleration != 1: LZ4_compress_fast_continue's last argument for every block of
+        the call (lz4hip_compress_fast_chain_accel_batch; clamped to 1 .. 65537 as liblz4 does)"""
         n, nc = cls._check_chains(src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen)
         sp, sk = _ro_ptr(src)
         dp, dk = _rw_ptr(dst)
         out = (C.c_int32 * max(n, 1))()
         cons = (C.c_uint64 * max(nc, 1))()
         pre = _arr(C.c_int32, chainPrefixLen) if chainPrefixLen is not None else None
-        _chk(lib().lz4hip_compress_fast_chain_batch(sp, _arr(C.c_uint64, chainSrcOff), pre, _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst), dp,
-                                                    _arr(C.c_uint64, dstOff), _arr(C.c_int32, dstCap), out, cons, n, nc))
+        args = (sp, _arr(C.c_uint64, chainSrcOff), pre, _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst), dp, _arr(C.c_uint64, dstOff),
+                _arr(C.c_int32, dstCap), out, cons, n, nc)
+        if acceleration == 1:
+            _chk(lib().lz4hip_compress_fast_chain_batch(*args))
+        else:
+            _chk(lib().lz4hip_compress_fast_chain_accel_batch(*args, int(acceleration)))
         if hasattr(srcLen, "dtype"):
             import numpy as np
             return np.frombuffer(out, dtype=np.int32, count=n).copy(), np.frombuffer(cons, dtype=np.uint64, count=nc).copy()
         return list(out[:n]), list(cons[:nc])
 
     @classmethod
-    def compressFastStream(cls, streams, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None):
+    def compressFastStream(cls, streams, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None, acceleration=1):
         """LZ4_compress_fast_continue on streams that are continued from call to call (lz4hip_compress_fast_stream_batch): the arrays of
         compressFastChain, and chain c is the next run of blocks of stream streamId[c] of the CompressStreams set `streams` (ids
         strictly ascending).  For a stream that has run before, chainPrefixLen[c] is how many of the last bytes it consumed lie in front
         of the source (LZ4_saveDict's size; 0 is legal and no reset) -> (outLen, chainConsumed) as compressFastChain's; a block whose
-        result is 0 stops its STREAM until it is reset"""
+        result is 0 stops its STREAM until it is reset.  acceleration != 1: LZ4_compress_fast_continue's last argument for every block
+        of THIS call (lz4hip_compress_fast_stream_accel_batch); a stream may be given another one in every call"""
         n, nc = cls._check_chains(src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen)
         if len(streamId) != nc:
             raise ValueError("per-chain arrays differ in length")
@@ -1106,21 +1118,25 @@ class LZ4HIPBatch:
         out = (C.c_int32 * max(n, 1))()
         cons = (C.c_uint64 * max(nc, 1))()
         pre = _arr(C.c_int32, chainPrefixLen) if chainPrefixLen is not None else None
-        _chk(lib().lz4hip_compress_fast_stream_batch(streams._handle(), _arr(C.c_uint32, streamId), sp, _arr(C.c_uint64, chainSrcOff), pre,
-                                                     _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst), dp, _arr(C.c_uint64, dstOff),
-                                                     _arr(C.c_int32, dstCap), out, cons, n, nc))
+        args = (streams._handle(), _arr(C.c_uint32, streamId), sp, _arr(C.c_uint64, chainSrcOff), pre, _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst),
+                dp, _arr(C.c_uint64, dstOff), _arr(C.c_int32, dstCap), out, cons, n, nc)
+        if acceleration == 1:
+            _chk(lib().lz4hip_compress_fast_stream_batch(*args))
+        else:
+            _chk(lib().lz4hip_compress_fast_stream_accel_batch(*args, int(acceleration)))
         if hasattr(srcLen, "dtype"):
             import numpy as np
             return np.frombuffer(out, dtype=np.int32, count=n).copy(), np.frombuffer(cons, dtype=np.uint64, count=nc).copy()
         return list(out[:n]), list(cons[:nc])
 
     @classmethod
-    def compressFastStreamAt(cls, streams, streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dst, dstOff, dstCap):
+    def compressFastStreamAt(cls, streams, streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dst, dstOff, dstCap,
+                             acceleration=1):
         """The same streams when their sources land anywhere -- a ring that wraps, alternating buffers, a dictionary elsewhere
         (lz4hip_compress_fast_stream_ext_batch): every block has its own srcOff[i] inside its stream's window [chainWinOff[c],
         + chainWinLen[c]); the stream's history ends at chainHistEnd[c] in src with chainHistLen[c] bytes of it present.  A block that
         does not follow its history runs in liblz4's external-dictionary mode.  A call is a snapshot of src -> (outLen, chainConsumed)
-        as compressFastStream's"""
+        as compressFastStream's.  acceleration != 1: lz4hip_compress_fast_stream_ext_accel_batch, as for compressFastStream"""
         n, nc = len(srcLen), len(streamId)
         if not (len(srcOff) == len(dstOff) == len(dstCap) == n) or not (len(chainHistEnd) == len(chainHistLen) == len(chainWinOff) == len(chainWinLen) == nc) \
                 or len(chainFirst) != nc + 1:
@@ -1132,10 +1148,13 @@ class LZ4HIPBatch:
         dp, dk = _rw_ptr(dst)
         out = (C.c_int32 * max(n, 1))()
         cons = (C.c_uint64 * max(nc, 1))()
-        _chk(lib().lz4hip_compress_fast_stream_ext_batch(streams._handle(), _arr(C.c_uint32, streamId), sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen),
-                                                         _arr(C.c_uint32, chainFirst), _arr(C.c_uint64, chainHistEnd), _arr(C.c_int32, chainHistLen),
-                                                         _arr(C.c_uint64, chainWinOff), _arr(C.c_uint64, chainWinLen), dp, _arr(C.c_uint64, dstOff),
-                                                         _arr(C.c_int32, dstCap), out, cons, n, nc))
+        args = (streams._handle(), _arr(C.c_uint32, streamId), sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst),
+                _arr(C.c_uint64, chainHistEnd), _arr(C.c_int32, chainHistLen), _arr(C.c_uint64, chainWinOff), _arr(C.c_uint64, chainWinLen), dp,
+                _arr(C.c_uint64, dstOff), _arr(C.c_int32, dstCap), out, cons, n, nc)
+        if acceleration == 1:
+            _chk(lib().lz4hip_compress_fast_stream_ext_batch(*args))
+        else:
+            _chk(lib().lz4hip_compress_fast_stream_ext_accel_batch(*args, int(acceleration)))
         if hasattr(srcLen, "dtype"):
             import numpy as np
             return np.frombuffer(out, dtype=np.int32, count=n).copy(), np.frombuffer(cons, dtype=np.uint64, count=nc).copy()
@@ -1253,14 +1272,14 @@ class CompressStreams:
     def __len__(self):
         return lib().lz4hip_cstreams_count(self._handle())
 
-    def compress(self, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None):
+    def compress(self, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen=None, acceleration=1):
         """LZ4HIPBatch.compressFastStream on this set"""
-        return LZ4HIPBatch.compressFastStream(self, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen)
+        return LZ4HIPBatch.compressFastStream(self, streamId, src, chainSrcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainPrefixLen, acceleration)
 
-    def compressAt(self, streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dst, dstOff, dstCap):
+    def compressAt(self, streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dst, dstOff, dstCap, acceleration=1):
         """LZ4HIPBatch.compressFastStreamAt on this set: sources that land anywhere"""
         return LZ4HIPBatch.compressFastStreamAt(self, streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dst, dstOff,
-                                                dstCap)
+                                                dstCap, acceleration)
 
     def reset(self, streamId=None):
         """makes the listed streams (None: all of them) fresh"""

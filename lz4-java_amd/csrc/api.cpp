@@ -128,7 +128,8 @@ constexpr bool op_needs_chain_scratch(Op op) { return op == OP_COMPRESS_HC_CHAIN
 // One block operation, from its entry point to launch_block.
 struct BlockCall {
   Op op;
-  int param = 0;                    // op_uses_hc_ws: the level (hc_level); OP_COMPRESS_ACCEL: the acceleration (accel_clamp, >= 2)
+  int param = 0;                    // op_uses_hc_ws: the level (hc_level); OP_COMPRESS_ACCEL: the acceleration (accel_clamp, >= 2);
+                                    // OP_COMPRESS_CHAIN, _STREAM, _XSTREAM: the acceleration (accel_clamp; 0 and 1: the acceleration-1 kernels)
   const int32_t* target = nullptr;  // OP_DECODE_PARTIAL: per-block target sizes; nullptr: dst_cap already is partial_room (host path)
   int32_t* consumed = nullptr;      // op_has_consumed: the input consumed per block
   void* hc_ws = nullptr;            // op_uses_hc_ws: device workspace for hc_span bytes of source; nullptr: launch_block learns the
@@ -413,15 +414,24 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
       return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_decompress_stream(*c.dstream, q, lz4hip::device_cus(), st); });
     case OP_COMPRESS_CHAIN:   // compress_fast_chain_cu_kernel draws chains from the queue word
       if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
-      return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_chain(*c.cchain, q, lz4hip::device_cus(), st); });
+      return with_queue_word(st, [&](uint32_t* q) {
+        return c.param >= 2 ? lz4hip::launch_compress_fast_chain_accel(*c.cchain, (uint32_t)c.param, q, lz4hip::device_cus(), st)
+                            : lz4hip::launch_compress_fast_chain(*c.cchain, q, lz4hip::device_cus(), st);
+      });
     case OP_COMPRESS_STREAM: {   // compress_fast_stream_cu_kernel draws chains from the queue word
       if (!c.cchain || !c.cs_rec || !c.cs_tables || !c.cs_slot) return fail(LZ4HIP_E_ARG, kNullArg);
       const lz4hip::CStreamArgs sa{*c.cchain, c.cs_slot, c.cs_rec, c.cs_tables};
-      return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_stream(sa, q, lz4hip::device_cus(), st); });
+      return with_queue_word(st, [&](uint32_t* q) {
+        return c.param >= 2 ? lz4hip::launch_compress_fast_stream_accel(sa, (uint32_t)c.param, q, lz4hip::device_cus(), st)
+                            : lz4hip::launch_compress_fast_stream(sa, q, lz4hip::device_cus(), st);
+      });
     }
     case OP_COMPRESS_XSTREAM:   // compress_fast_xstream_cu_kernel draws chains from the queue word
       if (!c.cxstream) return fail(LZ4HIP_E_ARG, kNullArg);
-      return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_compress_fast_xstream(*c.cxstream, q, lz4hip::device_cus(), st); });
+      return with_queue_word(st, [&](uint32_t* q) {
+        return c.param >= 2 ? lz4hip::launch_compress_fast_xstream_accel(*c.cxstream, (uint32_t)c.param, q, lz4hip::device_cus(), st)
+                            : lz4hip::launch_compress_fast_xstream(*c.cxstream, q, lz4hip::device_cus(), st);
+      });
     case OP_COMPRESS_HC_STREAM: {   // segment build over the host's item list, then the parse; the queue word is the image's own
       if (!c.hcstream || !c.hc_ws) return fail(LZ4HIP_E_ARG, kNullArg);
       return lz4hip::launch_compress_hc_stream(*c.hcstream, c.param, c.hc_ws, lz4hip::device_cus(), st);
@@ -1903,8 +1913,9 @@ const char* cxstream_arg_error(const lz4hip_cstreams* set, const uint32_t* strea
 // One call on a set, for both entry points: whole streams per device, at the boundaries the set was created with -- [c0, c1) of the
 // call's chains are part p's -- every share through shard(call, share, ord, c0, c1, err) with the share's state in call.cs_* and what
 // the host path needs beside it in share (StreamShare), side by side where there are several.  The set is locked for the call.
+// accel: the call's clamped acceleration, which travels in BlockCall::param.
 template <class Shard>
-int cstreams_call(lz4hip_cstreams* set, const uint32_t* stream_id, uint32_t n_chains, Op op, Shard shard) {
+int cstreams_call(lz4hip_cstreams* set, const uint32_t* stream_id, uint32_t n_chains, Op op, int accel, Shard shard) {
   std::lock_guard<std::mutex> lk(set->mu);
   struct Share { const lz4hip_cstreams::Part* p; uint32_t c0, c1; int rc = 0; std::string err; bool launched = false; };
   std::vector<Share> shares;
@@ -1918,7 +1929,7 @@ int cstreams_call(lz4hip_cstreams* set, const uint32_t* stream_id, uint32_t n_ch
   int prev = -1;
   (void)hipGetDevice(&prev);
   auto run = [&](Share& s) {
-    BlockCall call{op};
+    BlockCall call{op, accel};
     call.cs_rec = s.p->rec; call.cs_tables = s.p->tables;
     const StreamShare share{stream_id, s.p->lo, set->poisoned.data(), &s.launched};
     try { s.rc = shard(call, share, s.p->ord, s.c0, s.c1, &s.err); }
@@ -2219,10 +2230,17 @@ int lz4hip_decompress_safe_stream_batch(lz4hip_dstream_state* state, const uint8
 int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
                                      const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
                                      uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains) {
+  return lz4hip_compress_fast_chain_accel_batch(src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed,
+                                                n_blocks, n_chains, 1);
+}
+int lz4hip_compress_fast_chain_accel_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
+                                           const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,
+                                           uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains, int acceleration) {
+  const int accel = accel_clamp(acceleration);   // (1: the acceleration-1 kernel, launch_block)
   const lz4hip::CChainArgs h{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains};
   // whole chains per device: a chain never leaves its wavefront, let alone its device
   return chain_entry(cchain_arg_error(h, true, op_chain_stops(OP_COMPRESS_CHAIN)), n_chains, [&] {
-    return whole_chains(n_chains, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard({OP_COMPRESS_CHAIN}, {}, h, ord, c0, c1, err); });
+    return whole_chains(n_chains, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return cchain_host_shard({OP_COMPRESS_CHAIN, accel}, {}, h, ord, c0, c1, err); });
   });
 }
 int lz4hip_cstreams_create(uint32_t n_streams, lz4hip_cstreams** out) {
@@ -2323,9 +2341,17 @@ int lz4hip_compress_fast_stream_batch(lz4hip_cstreams* set, const uint32_t* stre
                                       const int32_t* chain_prefix_len, const int32_t* src_len, const uint32_t* chain_first, uint8_t* dst,
                                       const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks,
                                       uint32_t n_chains) {
+  return lz4hip_compress_fast_stream_accel_batch(set, stream_id, src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len,
+                                                 chain_consumed, n_blocks, n_chains, 1);
+}
+int lz4hip_compress_fast_stream_accel_batch(lz4hip_cstreams* set, const uint32_t* stream_id, const uint8_t* src, const uint64_t* chain_src_off,
+                                            const int32_t* chain_prefix_len, const int32_t* src_len, const uint32_t* chain_first, uint8_t* dst,
+                                            const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint64_t* chain_consumed,
+                                            uint32_t n_blocks, uint32_t n_chains, int acceleration) {
+  const int accel = accel_clamp(acceleration);
   const lz4hip::CChainArgs h{src, chain_src_off, chain_prefix_len, src_len, chain_first, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains};
   return chain_entry(cstream_arg_error(set, stream_id, h), n_chains, [&] {
-    return cstreams_call(set, stream_id, n_chains, OP_COMPRESS_STREAM, [&](const BlockCall& call, const StreamShare& share, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+    return cstreams_call(set, stream_id, n_chains, OP_COMPRESS_STREAM, accel, [&](const BlockCall& call, const StreamShare& share, int ord, uint32_t c0, uint32_t c1, std::string* err) {
       return cchain_host_shard(call, share, h, ord, c0, c1, err);
     });
   });
@@ -2334,10 +2360,19 @@ int lz4hip_compress_fast_stream_ext_batch(lz4hip_cstreams* set, const uint32_t* 
                                           const uint32_t* chain_first, const uint64_t* chain_hist_end, const int32_t* chain_hist_len,
                                           const uint64_t* chain_win_off, const uint64_t* chain_win_len, uint8_t* dst, const uint64_t* dst_off,
                                           const int32_t* dst_cap, int32_t* out_len, uint64_t* chain_consumed, uint32_t n_blocks, uint32_t n_chains) {
+  return lz4hip_compress_fast_stream_ext_accel_batch(set, stream_id, src, src_off, src_len, chain_first, chain_hist_end, chain_hist_len, chain_win_off,
+                                                     chain_win_len, dst, dst_off, dst_cap, out_len, chain_consumed, n_blocks, n_chains, 1);
+}
+int lz4hip_compress_fast_stream_ext_accel_batch(lz4hip_cstreams* set, const uint32_t* stream_id, const uint8_t* src, const uint64_t* src_off,
+                                                const int32_t* src_len, const uint32_t* chain_first, const uint64_t* chain_hist_end,
+                                                const int32_t* chain_hist_len, const uint64_t* chain_win_off, const uint64_t* chain_win_len, uint8_t* dst,
+                                                const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len, uint64_t* chain_consumed,
+                                                uint32_t n_blocks, uint32_t n_chains, int acceleration) {
+  const int accel = accel_clamp(acceleration);
   const CXStreamHost h{src, src_off, src_len, chain_first, chain_hist_end, chain_hist_len, chain_win_off, chain_win_len, dst, dst_off, dst_cap, out_len,
                        chain_consumed, n_blocks, n_chains};
   return chain_entry(cxstream_arg_error(set, stream_id, h), n_chains, [&] {
-    return cstreams_call(set, stream_id, n_chains, OP_COMPRESS_XSTREAM, [&](const BlockCall& call, const StreamShare& share, int ord, uint32_t c0, uint32_t c1, std::string* err) {
+    return cstreams_call(set, stream_id, n_chains, OP_COMPRESS_XSTREAM, accel, [&](const BlockCall& call, const StreamShare& share, int ord, uint32_t c0, uint32_t c1, std::string* err) {
       return cxstream_host_shard(call, share, h, ord, c0, c1, err);
     });
   });

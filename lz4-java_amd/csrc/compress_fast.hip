@@ -518,6 +518,65 @@ int launch_compress_fast_xstream(const CXStreamArgs& a, uint32_t* q, uint32_t n_
   return launch_queue_kernel(compress_fast_xstream_cu_kernel, a.s.c.n_chains, q, 1u, n_cus, stream, a, q);
 }
 
+// The three kernels above with acceleration 2 .. 65537 (LZ4_compress_fast_continue's last argument, one value for the launch): the same
+// shape, Io and walks with their ACC switch on.  Kernels of their own, so that the acceleration-1 kernels keep their instructions;
+// same arguments, record and image, so that launches of all six alternate on a stream.
+__global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_chain_accel_cu_kernel(CChainArgs a, uint32_t* q, uint32_t accel) {
+  __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
+  WaveDev w(tables[threadIdx.x >> 6]);
+  CChainIoDev io{a};
+  for (;;) {
+    uint32_t c = 0;
+    if (__lane_id() == 0) c = atomicAdd(q, 1u);
+    c = __builtin_amdgcn_readfirstlane(c);
+    if (c >= a.n_chains) return;
+    cchain_walk<true>(w, io, a, c, accel);
+    WaveDev::sync();  // the table is reused: the next chain starts from its own
+  }
+}
+int launch_compress_fast_chain_accel(const CChainArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream) {
+  if (a.n_chains == 0) return 0;
+  if (!q || accel < 2u || accel > 65537u) return (int)hipErrorInvalidValue;   // (the caller clamps; 1 is launch_compress_fast_chain's)
+  return launch_queue_kernel(compress_fast_chain_accel_cu_kernel, a.n_chains, q, 1u, n_cus, stream, a, q, accel);
+}
+__global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_stream_accel_cu_kernel(CStreamArgs a, uint32_t* q, uint32_t accel) {
+  __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
+  WaveDev w(tables[threadIdx.x >> 6]);
+  CStreamIoDev io{{a.c}};
+  for (;;) {
+    uint32_t c = 0;
+    if (__lane_id() == 0) c = atomicAdd(q, 1u);
+    c = __builtin_amdgcn_readfirstlane(c);
+    if (c >= a.c.n_chains) return;
+    cstream_walk<true>(w, io, a, c, accel);
+    WaveDev::sync();  // the table is reused: the next stream loads or builds its own
+  }
+}
+int launch_compress_fast_stream_accel(const CStreamArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream) {
+  if (a.c.n_chains == 0) return 0;
+  if (!q || !a.slot || !a.rec || !a.tables || accel < 2u || accel > 65537u) return (int)hipErrorInvalidValue;
+  return launch_queue_kernel(compress_fast_stream_accel_cu_kernel, a.c.n_chains, q, 1u, n_cus, stream, a, q, accel);
+}
+__global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_xstream_accel_cu_kernel(CXStreamArgs a, uint32_t* q, uint32_t accel) {
+  __shared__ __attribute__((aligned(16))) uint64_t tables[WAVES_PER_CU][LZ4HIP_TABLE_U64];
+  WaveDev w(tables[threadIdx.x >> 6]);
+  CXStreamIoDev io{{{a.s.c}}};
+  for (;;) {
+    uint32_t c = 0;
+    if (__lane_id() == 0) c = atomicAdd(q, 1u);
+    c = __builtin_amdgcn_readfirstlane(c);
+    if (c >= a.s.c.n_chains) return;
+    cxstream_walk<true>(w, io, a, c, accel);
+    WaveDev::sync();  // the table is reused: the next stream loads or builds its own
+  }
+}
+int launch_compress_fast_xstream_accel(const CXStreamArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream) {
+  if (a.s.c.n_chains == 0) return 0;
+  if (!q || !a.s.slot || !a.s.rec || !a.s.tables || !a.src_off || !a.chain_hist_end || !a.s.c.chain_prefix_len || accel < 2u || accel > 65537u)
+    return (int)hipErrorInvalidValue;
+  return launch_queue_kernel(compress_fast_xstream_accel_cu_kernel, a.s.c.n_chains, q, 1u, n_cus, stream, a, q, accel);
+}
+
 // LZ4_compress_destSize: the one-sequence-per-step core (acceleration 1) with DirectOut's FILL switch on; dst_cap[b] is the target.  A
 // block whose target is full stops at the next step, so the steps spent on it follow the input it consumes, not src_len.
 __global__ __launch_bounds__(64 * WAVES_PER_CU) void compress_fast_dest_cu_kernel(BatchArgs a, int32_t* consumed, uint32_t* q) {

@@ -181,6 +181,13 @@ struct CXStreamArgs {
 };
 // compress_fast_xstream_cu_kernel: compress_fast_stream_cu_kernel's shape
 int launch_compress_fast_xstream(const CXStreamArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
+// The three launches above at LZ4_compress_fast_continue's acceleration 2 .. 65537 (clamped by the caller; 1 is theirs, anything else
+// is hipErrorInvalidValue), one value for every block of the launch: compress_fast_chain_accel_cu_kernel,
+// compress_fast_stream_accel_cu_kernel, compress_fast_xstream_accel_cu_kernel -- the same shapes and walks with the core's ACC switch.
+// Same arguments, records and table images: launches at any acceleration alternate on a slot.
+int launch_compress_fast_chain_accel(const CChainArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream);
+int launch_compress_fast_stream_accel(const CStreamArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream);
+int launch_compress_fast_xstream_accel(const CXStreamArgs& a, uint32_t accel, uint32_t* q, uint32_t n_cus, void* stream);
 // LZ4_compress_HC_continue over chains of linked blocks, prefix mode (compress_hc.hip): CChainArgs as above with chain_consumed unused
 // (nullptr); the history is what LZ4_loadDictHC keeps (its last 64 KB, no minimum).  out[i] = liblz4's return value; a block that
 // returns 0 (it does not fit, or src_len[i] / dst_cap[i] is negative) does NOT stop its chain: its source is history for the blocks

@@ -27,6 +27,12 @@
 // Nothing outside [chain_src - keep, chain_src + sum src_len) is read, nothing at or past the current block's end, and nothing outside
 // a block's slot is written.
 //
+// ACC (every walk here): the call's acceleration, 2 .. 65537 after the caller's clamp, in `accel` -- the last argument of
+// LZ4_compress_fast_continue.  liblz4 lets it touch nothing but where a miss run probes (FastCore's ACC switch), so the walks are the
+// same text: returns, stop rule, span limit, short blocks, history rules, the record's words and the table image's format do not
+// change, and calls at different accelerations -- the acceleration-1 kernels among them -- alternate on one stream.  ACC = false is the
+// walk the acceleration-1 kernels run, instruction for instruction (profiles/caccel_kernel_diff.txt); `accel` is not read there.
+//
 // Io: uni(v) / uni_ptr(p): a wave-uniform value back in scalar registers (identity on the host); put_out(i, r) / put_chain(c, bytes):
 // the results (lane 0 writes them, vector stores); begin_block(buf, end, d, cap): the block about to run may read [buf, buf + end) and
 // write [d, d + cap) (the simulator's bounds; nothing on the device).
@@ -56,9 +62,9 @@ LZ4HIP_DEV void link_table_init(W& w, const uint8_t* buf, uint32_t keep, bool pr
 
 // (cstream_walk below holds a copy of this block loop, and cxstream_walk behind it a copy of its prefix-mode branch: a change here is
 // to be made there as well)
-template <class W, class Io>
-LZ4HIP_DEV void cchain_walk(W& w, Io& io, const CChainArgs& a, uint32_t c) {
-  using Core = FastCore<W, false, DirectOut<W>, false, false, false, true>;
+template <bool ACC = false, class W, class Io>
+LZ4HIP_DEV void cchain_walk(W& w, Io& io, const CChainArgs& a, uint32_t c, [[maybe_unused]] uint32_t accel = 1u) {
+  using Core = FastCore<W, false, DirectOut<W>, false, ACC, false, true>;
   uint32_t b1 = io.uni(a.chain_first[c + 1]), b0 = io.uni(a.chain_first[c]);
   if (b1 > a.n_blocks) b1 = a.n_blocks;
   if (b0 > b1) b0 = b1;
@@ -84,6 +90,7 @@ LZ4HIP_DEV void cchain_walk(W& w, Io& io, const CChainArgs& a, uint32_t c) {
       out.limited = (uint32_t)dc < (uint32_t)sl + (uint32_t)sl / 255u + 16u;   // (by the block's length, not by its end in buf)
       Core core(w, out, buf, end);
       core.blk = pos; core.ibase = ibase; core.lowidx = ibase;
+      if constexpr (ACC) core.accel = accel;
       r = core.run();
     }
     io.put_out(i, (int32_t)r);
@@ -117,9 +124,9 @@ LZ4HIP_DEV void cchain_walk(W& w, Io& io, const CChainArgs& a, uint32_t c) {
 // Io, beyond cchain_walk's: begin_state(image) / end_state(): the walk is about to read or write the slot's 32 KB image, and is done
 // (the simulator's bounds); table_load(w, image) / table_store(w, image): the image to and from w's table, wave-wide; put_rec(rec, ...):
 // the record's words, from lane 0.
-template <class W, class Io>
-LZ4HIP_DEV void cstream_walk(W& w, Io& io, const CStreamArgs& s, uint32_t c) {
-  using Core = FastCore<W, false, DirectOut<W>, false, false, false, true>;
+template <bool ACC = false, class W, class Io>
+LZ4HIP_DEV void cstream_walk(W& w, Io& io, const CStreamArgs& s, uint32_t c, [[maybe_unused]] uint32_t accel = 1u) {
+  using Core = FastCore<W, false, DirectOut<W>, false, ACC, false, true>;
   const CChainArgs& a = s.c;
   uint32_t b1 = io.uni(a.chain_first[c + 1]), b0 = io.uni(a.chain_first[c]);
   if (b1 > a.n_blocks) b1 = a.n_blocks;
@@ -179,6 +186,7 @@ LZ4HIP_DEV void cstream_walk(W& w, Io& io, const CStreamArgs& s, uint32_t c) {
       out.limited = (uint32_t)dc < (uint32_t)sl + (uint32_t)sl / 255u + 16u;   // (by the block's length, not by its end in buf)
       Core core(w, out, buf, end);
       core.blk = pos; core.ibase = ibase; core.lowidx = ibase;
+      if constexpr (ACC) core.accel = accel;
       r = core.run();
     }
     io.put_out(i, (int32_t)r);
@@ -224,10 +232,10 @@ LZ4HIP_DEV void cstream_walk(W& w, Io& io, const CStreamArgs& s, uint32_t c) {
 // A stream without a table (blocks under 13 bytes only) builds it at its first block that probes: empty buckets are index 0, a real
 // candidate only while idx - D_len == 0, when the stream's first four bytes are D's (or, with no history at all, the block's).
 // Io, beyond cstream_walk's: begin_xblock(hist, hist_len, blk, n, d, cap): the block about to run may read both pieces.
-template <class W, class Io>
-LZ4HIP_DEV void cxstream_walk(W& w, Io& io, const CXStreamArgs& x, uint32_t c) {
-  using Link = FastCore<W, false, DirectOut<W>, false, false, false, true>;
-  using Ext = FastCore<W, false, DirectOut<W>, false, false, true, true>;
+template <bool ACC = false, class W, class Io>
+LZ4HIP_DEV void cxstream_walk(W& w, Io& io, const CXStreamArgs& x, uint32_t c, [[maybe_unused]] uint32_t accel = 1u) {
+  using Link = FastCore<W, false, DirectOut<W>, false, ACC, false, true>;
+  using Ext = FastCore<W, false, DirectOut<W>, false, ACC, true, true>;
   const CStreamArgs& s = x.s;
   const CChainArgs& a = s.c;
   uint32_t b1 = io.uni(a.chain_first[c + 1]), b0 = io.uni(a.chain_first[c]);
@@ -298,6 +306,7 @@ LZ4HIP_DEV void cxstream_walk(W& w, Io& io, const CXStreamArgs& x, uint32_t c) {
         out.limited = (uint32_t)dc < n + n / 255u + 16u;   // (by the block's length, not by its end in buf)
         Link core(w, out, buf, end);
         core.blk = Dl; core.ibase = ibase; core.lowidx = ibase;
+        if constexpr (ACC) core.accel = accel;
         r = core.run();
         if (r) { Dl += n; De = so + n; }
       } else {                                                   // rule 4: the history lies elsewhere
@@ -314,6 +323,7 @@ LZ4HIP_DEV void cxstream_walk(W& w, Io& io, const CXStreamArgs& x, uint32_t c) {
         Ext core(w, out, blk, n);
         core.dict = hist; core.keep = Dl; core.ibase = idx; core.lowidx = low;
         core.alias_hi = (Dl != 0u && so < De && so + n > De - Dl) ? idx : 0u;
+        if constexpr (ACC) core.accel = accel;
         r = core.run();
         if (r) { Dl = n; De = so + n; }
       }

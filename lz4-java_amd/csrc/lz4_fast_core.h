@@ -270,6 +270,10 @@ constexpr uint32_t SEQ_NOCHECK = 1u << 29, SEQ_LIT_MASK = (1u << 29) - 1u;
 // of a run sits at S + g_a(k) (see g_acc); `accel` (>= 1, clamped by the caller) is read only then.  Its steps no longer sit on
 // consecutive positions beyond the first two probes, so literals always come from the source, never from the window registers.
 // ACC = false is the acceleration-1 core every other kernel runs, unchanged.
+// ACC with LINK, and with LINK + DICT (XLINK): LZ4_compress_fast_continue(..., acceleration) on a chain or a running stream
+// (lz4_fast_chain.h, the *_accel walks).  Nothing else in those branches knows where a run's probes sit: the candidate bounds (lowidx,
+// ibase, alias_hi, the 65535 distance), locate and cand_load work on one probe's position and entry.  (ACC with DICT alone -- the
+// dictionary-handle form -- is not built.)
 // DICT: LZ4_loadDict + LZ4_compress_fast_continue on a fresh stream, liblz4's external-dictionary mode (byU32 at every size, 64-bit
 // entries).  The table holds INDEXES: block position p is kDictBase + p, byte j of the dictionary's kept tail (its last `keep` <= 64 KB
 // bytes) is kDictBase - keep + j, so a dictionary candidate is an index below kDictBase.  The table starts as the image LZ4_loadDict
@@ -323,8 +327,8 @@ template <> struct LinkState<true> { uint32_t blk = 0, ibase = 0, lowidx = 0, al
 template <class W, bool U16, class Out = DirectOut<W>, bool PK = false, bool ACC = false, bool DICT = false, bool LINK = false>
 struct FastCore : DictState<DICT>, LinkState<LINK> {
   static_assert(!(U16 && PK), "compact entries are a byU32 layout");
-  static_assert(!DICT || (!U16 && !PK && !ACC), "the dictionary core is byU32 with 64-bit entries, acceleration 1");
-  static_assert(!LINK || (!U16 && !PK && !ACC), "the linked-block core is byU32 with 64-bit entries, acceleration 1");
+  static_assert(!DICT || (!U16 && !PK && (!ACC || LINK)), "the dictionary core is byU32 with 64-bit entries; acceleration 1 unless it is a running stream's (XLINK)");
+  static_assert(!LINK || (!U16 && !PK), "the linked-block core is byU32 with 64-bit entries");
   static constexpr bool XLINK = LINK && DICT;     // a running stream's block against a history that lies elsewhere
   static constexpr uint32_t kDictBase = 65536u;   // DICT: index of block position 0 (the stream's offset after LZ4_loadDict)
   static constexpr bool S32 = U16 || PK;           // entries are 32 bits

@@ -365,10 +365,12 @@ struct LZ4HIPBatch {
   // [chainFirst[c], chainFirst[c + 1]), whose sources lie back to back from src[chainSrcOff[c]] on, behind chainPrefixLen[c] bytes of
   // history that lie in front of it in src (an empty vector: no history; the stream loads it with LZ4_loadDict); block i owns the slot
   // dest[destOff[i], + maxDestLen[i]).  lengths[i] = liblz4's return value (0: it did not fit, which ends the chain),
-  // LZ4HIP_CHAIN_STOPPED behind a chain's first 0; chainLengths[c] = the source bytes of chain c's blocks that succeeded
+  // LZ4HIP_CHAIN_STOPPED behind a chain's first 0; chainLengths[c] = the source bytes of chain c's blocks that succeeded.
+  // acceleration: LZ4_compress_fast_continue's last argument for every block of the call (lz4hip_compress_fast_chain_accel_batch, which
+  // clamps it to 1 .. 65537 as liblz4 does; 1 is lz4hip_compress_fast_chain_batch, called as such)
   static Chains compressFastChain(const bytes& src, const std::vector<uint64_t>& chainSrcOff, const std::vector<int32_t>& srcLen,
                                   const std::vector<uint32_t>& chainFirst, bytes& dest, const std::vector<uint64_t>& destOff,
-                                  const std::vector<int32_t>& maxDestLen, const std::vector<int32_t>& chainPrefixLen = {}) {
+                                  const std::vector<int32_t>& maxDestLen, const std::vector<int32_t>& chainPrefixLen = {}, int acceleration = 1) {
     checkChains(src, chainSrcOff, srcLen, chainFirst, dest, destOff, maxDestLen, chainPrefixLen);
     const size_t n = srcLen.size(), nc = chainSrcOff.size();
     Chains r;
@@ -377,10 +379,18 @@ struct LZ4HIPBatch {
     bytes one(1);                                 // (an empty buffer still hands the library a pointer)
     int32_t none = 0;
     uint64_t none64 = 0;
-    status(lz4hip_compress_fast_chain_batch(src.empty() ? one.data() : src.data(), nc ? chainSrcOff.data() : &none64,
-                                            chainPrefixLen.empty() ? nullptr : chainPrefixLen.data(), n ? srcLen.data() : &none, chainFirst.data(),
-                                            dest.empty() ? one.data() : dest.data(), n ? destOff.data() : &none64, n ? maxDestLen.data() : &none,
-                                            n ? r.lengths.data() : &none, nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
+    const uint8_t* sp = src.empty() ? one.data() : src.data();
+    const uint64_t* cso = nc ? chainSrcOff.data() : &none64;
+    const int32_t* pre = chainPrefixLen.empty() ? nullptr : chainPrefixLen.data();
+    uint8_t* dp = dest.empty() ? one.data() : dest.data();
+    if (acceleration == 1)
+      status(lz4hip_compress_fast_chain_batch(sp, cso, pre, n ? srcLen.data() : &none, chainFirst.data(), dp, n ? destOff.data() : &none64,
+                                              n ? maxDestLen.data() : &none, n ? r.lengths.data() : &none, nc ? r.chainLengths.data() : &none64,
+                                              (uint32_t)n, (uint32_t)nc));
+    else
+      status(lz4hip_compress_fast_chain_accel_batch(sp, cso, pre, n ? srcLen.data() : &none, chainFirst.data(), dp, n ? destOff.data() : &none64,
+                                                    n ? maxDestLen.data() : &none, n ? r.lengths.data() : &none, nc ? r.chainLengths.data() : &none64,
+                                                    (uint32_t)n, (uint32_t)nc, acceleration));
     return r;
   }
   // LZ4_compress_HC_continue over chains of linked blocks, prefix mode (lz4hip_compress_hc_chain_batch): compressFastChain's arrays
@@ -512,7 +522,8 @@ struct LZ4HIPBatch {
 // over all the calls that name it, the bytes ONE LZ4_stream_t of liblz4 gives, however its blocks are cut into calls; for a stream
 // that has run, chainPrefixLen[c] is how many of the last bytes it consumed lie in front of the source (LZ4_saveDict's size; 0 is
 // legal and no reset).  A block whose result is 0 stops its stream until reset().  Calls on one set are serialised; the set is
-// destroyed before lz4hip_shutdown().
+// destroyed before lz4hip_shutdown().  acceleration (compress and compressAt): LZ4_compress_fast_continue's last argument for every block
+// of THAT call (the *_accel_batch entry points, which clamp it to 1 .. 65537; 1 is the call without it); a stream may get another in every call.
 class CompressStreams {
  public:
   explicit CompressStreams(uint32_t n) { LZ4HIPBatch::status(lz4hip_cstreams_create(n, &h_)); }
@@ -523,7 +534,7 @@ class CompressStreams {
   LZ4HIPBatch::Chains compress(const std::vector<uint32_t>& streamId, const bytes& src, const std::vector<uint64_t>& chainSrcOff,
                                const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst, bytes& dest,
                                const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen,
-                               const std::vector<int32_t>& chainPrefixLen = {}) {
+                               const std::vector<int32_t>& chainPrefixLen = {}, int acceleration = 1) {
     LZ4HIPBatch::checkChains(src, chainSrcOff, srcLen, chainFirst, dest, destOff, maxDestLen, chainPrefixLen);
     const size_t n = srcLen.size(), nc = chainSrcOff.size();
     if (streamId.size() != nc) throw std::invalid_argument("per-chain arrays differ in length");
@@ -537,11 +548,19 @@ class CompressStreams {
     int32_t none = 0;
     uint32_t none32 = 0;
     uint64_t none64 = 0;
-    LZ4HIPBatch::status(lz4hip_compress_fast_stream_batch(h_, nc ? streamId.data() : &none32, src.empty() ? one.data() : src.data(),
-                                                          nc ? chainSrcOff.data() : &none64, chainPrefixLen.empty() ? nullptr : chainPrefixLen.data(),
-                                                          n ? srcLen.data() : &none, chainFirst.data(), dest.empty() ? one.data() : dest.data(),
-                                                          n ? destOff.data() : &none64, n ? maxDestLen.data() : &none, n ? r.lengths.data() : &none,
-                                                          nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
+    const uint32_t* ids = nc ? streamId.data() : &none32;
+    const uint8_t* sp = src.empty() ? one.data() : src.data();
+    const uint64_t* cso = nc ? chainSrcOff.data() : &none64;
+    const int32_t* pre = chainPrefixLen.empty() ? nullptr : chainPrefixLen.data();
+    uint8_t* dp = dest.empty() ? one.data() : dest.data();
+    if (acceleration == 1)
+      LZ4HIPBatch::status(lz4hip_compress_fast_stream_batch(h_, ids, sp, cso, pre, n ? srcLen.data() : &none, chainFirst.data(), dp,
+                                                            n ? destOff.data() : &none64, n ? maxDestLen.data() : &none, n ? r.lengths.data() : &none,
+                                                            nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
+    else
+      LZ4HIPBatch::status(lz4hip_compress_fast_stream_accel_batch(h_, ids, sp, cso, pre, n ? srcLen.data() : &none, chainFirst.data(), dp,
+                                                                  n ? destOff.data() : &none64, n ? maxDestLen.data() : &none, n ? r.lengths.data() : &none,
+                                                                  nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc, acceleration));
     return r;
   }
   // The same streams when their sources land anywhere -- a ring that wraps, alternating buffers, a dictionary elsewhere
@@ -552,7 +571,7 @@ class CompressStreams {
                                  const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst,
                                  const std::vector<uint64_t>& chainHistEnd, const std::vector<int32_t>& chainHistLen,
                                  const std::vector<uint64_t>& chainWinOff, const std::vector<uint64_t>& chainWinLen, bytes& dest,
-                                 const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen) {
+                                 const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen, int acceleration = 1) {
     const size_t n = srcLen.size(), nc = streamId.size();
     if (srcOff.size() != n || destOff.size() != n || maxDestLen.size() != n) throw std::invalid_argument("per-block arrays differ in length");
     if (chainHistEnd.size() != nc || chainHistLen.size() != nc || chainWinOff.size() != nc || chainWinLen.size() != nc || chainFirst.size() != nc + 1)
@@ -567,11 +586,22 @@ class CompressStreams {
     int32_t none = 0;
     uint32_t none32 = 0;
     uint64_t none64 = 0;
-    LZ4HIPBatch::status(lz4hip_compress_fast_stream_ext_batch(
-        h_, nc ? streamId.data() : &none32, src.empty() ? one.data() : src.data(), n ? srcOff.data() : &none64, n ? srcLen.data() : &none, chainFirst.data(),
-        nc ? chainHistEnd.data() : &none64, nc ? chainHistLen.data() : &none, nc ? chainWinOff.data() : &none64, nc ? chainWinLen.data() : &none64,
-        dest.empty() ? one.data() : dest.data(), n ? destOff.data() : &none64, n ? maxDestLen.data() : &none, n ? r.lengths.data() : &none,
-        nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
+    const uint32_t* ids = nc ? streamId.data() : &none32;
+    const uint8_t* sp = src.empty() ? one.data() : src.data();
+    const uint64_t* he = nc ? chainHistEnd.data() : &none64;
+    const int32_t* hl = nc ? chainHistLen.data() : &none;
+    const uint64_t* wo = nc ? chainWinOff.data() : &none64;
+    const uint64_t* wl = nc ? chainWinLen.data() : &none64;
+    uint8_t* dp = dest.empty() ? one.data() : dest.data();
+    if (acceleration == 1)
+      LZ4HIPBatch::status(lz4hip_compress_fast_stream_ext_batch(h_, ids, sp, n ? srcOff.data() : &none64, n ? srcLen.data() : &none, chainFirst.data(), he, hl,
+                                                                wo, wl, dp, n ? destOff.data() : &none64, n ? maxDestLen.data() : &none,
+                                                                n ? r.lengths.data() : &none, nc ? r.chainLengths.data() : &none64, (uint32_t)n, (uint32_t)nc));
+    else
+      LZ4HIPBatch::status(lz4hip_compress_fast_stream_ext_accel_batch(h_, ids, sp, n ? srcOff.data() : &none64, n ? srcLen.data() : &none, chainFirst.data(),
+                                                                      he, hl, wo, wl, dp, n ? destOff.data() : &none64, n ? maxDestLen.data() : &none,
+                                                                      n ? r.lengths.data() : &none, nc ? r.chainLengths.data() : &none64, (uint32_t)n,
+                                                                      (uint32_t)nc, acceleration));
     return r;
   }
   void reset() { LZ4HIPBatch::status(lz4hip_cstreams_reset(h_, nullptr, 0)); }

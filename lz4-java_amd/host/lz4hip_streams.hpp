@@ -57,14 +57,19 @@ struct BatchEngine {
     return out;
   }
   // one chain of linked blocks (lz4hip_compress_fast_chain_batch): the blocks' sources lie back to back from src + srcOff on, behind
-  // `prefix` bytes of history that lie in front of them; block i owns dst[d_o[i], + dc[i]).  Returns liblz4's values per block
+  // `prefix` bytes of history that lie in front of them; block i owns dst[d_o[i], + dc[i]).  Returns liblz4's values per block.
+  // acceleration != 1: LZ4_compress_fast_continue's last argument for every block (lz4hip_compress_fast_chain_accel_batch)
   std::vector<int32_t> compressFastChain(const uint8_t* src, uint64_t srcOff, int32_t prefix, const std::vector<int32_t>& sl, uint8_t* dst,
-                                         const std::vector<uint64_t>& d_o, const std::vector<int32_t>& dc) const {
+                                         const std::vector<uint64_t>& d_o, const std::vector<int32_t>& dc, int acceleration = 1) const {
     std::vector<int32_t> out(sl.size());
     if (sl.empty()) return out;
     const uint32_t first[2] = {0u, (uint32_t)sl.size()};
     uint64_t consumed = 0;
-    chk(lz4hip_compress_fast_chain_batch(src, &srcOff, &prefix, sl.data(), first, dst, d_o.data(), dc.data(), out.data(), &consumed, (uint32_t)sl.size(), 1u));
+    if (acceleration == 1)
+      chk(lz4hip_compress_fast_chain_batch(src, &srcOff, &prefix, sl.data(), first, dst, d_o.data(), dc.data(), out.data(), &consumed, (uint32_t)sl.size(), 1u));
+    else
+      chk(lz4hip_compress_fast_chain_accel_batch(src, &srcOff, &prefix, sl.data(), first, dst, d_o.data(), dc.data(), out.data(), &consumed,
+                                                 (uint32_t)sl.size(), 1u, acceleration));
     return out;
   }
   // the same chain at an HC level (lz4hip_compress_hc_chain_batch): a block that does not fit gives 0 and the chain goes on
@@ -202,7 +207,8 @@ inline Compressed compressBlocks(const BatchEngine& e, const bytes& data, int bl
 }
 // the same blocks as ONE chain of linked blocks behind `history` (at most the last 64 KB written of the frame); hc: the HC chain at
 // `level` (LZ4_compress_HC_continue) instead of the fast chain
-inline Compressed compressChain(const BatchEngine& e, const bytes& history, const bytes& data, int blockSize, bool hc = false, int level = 0) {
+inline Compressed compressChain(const BatchEngine& e, const bytes& history, const bytes& data, int blockSize, bool hc = false, int level = 0,
+                                int acceleration = 1) {
   Compressed c;
   const size_t n = (data.size() + (size_t)blockSize - 1) / (size_t)blockSize;
   c.bound = maxCompressedLength(blockSize);
@@ -217,13 +223,13 @@ inline Compressed compressChain(const BatchEngine& e, const bytes& history, cons
   bytes src(history);
   src.insert(src.end(), data.begin(), data.end());
   c.sizes = hc ? e.compressHCChain(src.data(), history.size(), (int32_t)history.size(), c.lens, c.dst.data(), d_o, dc, level)
-               : e.compressFastChain(src.data(), history.size(), (int32_t)history.size(), c.lens, c.dst.data(), d_o, dc);
+               : e.compressFastChain(src.data(), history.size(), (int32_t)history.size(), c.lens, c.dst.data(), d_o, dc, acceleration);
   for (int32_t s : c.sizes) if (s <= 0) throw LZ4Exception("maxDestLen is too small");
   return c;
 }
 // the same blocks as the next run of blocks of stream 0 of `streams` (the frame's own resident stream), which has consumed `history`
 // (at most its last 64 KB) before
-inline Compressed compressStream(CompressStreams& streams, const bytes& history, const bytes& data, int blockSize) {
+inline Compressed compressStream(CompressStreams& streams, const bytes& history, const bytes& data, int blockSize, int acceleration = 1) {
   Compressed c;
   const size_t n = (data.size() + (size_t)blockSize - 1) / (size_t)blockSize;
   c.bound = maxCompressedLength(blockSize);
@@ -237,7 +243,7 @@ inline Compressed compressStream(CompressStreams& streams, const bytes& history,
   }
   bytes src(history);
   src.insert(src.end(), data.begin(), data.end());
-  c.sizes = streams.compress({0u}, src, {(uint64_t)history.size()}, c.lens, {0u, (uint32_t)n}, c.dst, d_o, dc, {(int32_t)history.size()}).lengths;
+  c.sizes = streams.compress({0u}, src, {(uint64_t)history.size()}, c.lens, {0u, (uint32_t)n}, c.dst, d_o, dc, {(int32_t)history.size()}, acceleration).lengths;
   for (int32_t s : c.sizes) if (s <= 0) throw LZ4Exception("maxDestLen is too small");
   return c;
 }
@@ -295,6 +301,8 @@ class LZ4FrameOutputStream {
   // stream whose table and index position stay on the device from batch to batch (a CompressStreams set of one, made at the first
   // batch), so the blocks are what ONE LZ4_stream_t writes for the whole frame and the frame's bytes do not depend on batchBlocks or on
   // flush() calls that fall on block boundaries.
+  // acceleration(N), before the first write (the fast chain, with or without streamState; 1 by default, whose bytes are unchanged): every
+  // block is compressed with LZ4_compress_fast_continue(..., N), clamped to 1 .. 65537 as liblz4 does -- the blocks `lz4 --fast=N` writes.
   LZ4FrameOutputStream(std::ostream& out, frame::BLOCKSIZE blockSize = frame::SIZE_4MB, int64_t knownSize = -1,
                        std::initializer_list<frame::Bits> bits = {frame::BLOCK_INDEPENDENCE}, BatchEngine engine = BatchEngine(),
                        size_t batchBlocks = 64, bool linkedBlocks = false)
@@ -329,6 +337,11 @@ class LZ4FrameOutputStream {
     if (wroteBlocks_ || finished_) throw IllegalStateException("streamState is chosen before the first block is written");
     streamState_ = on;
   }
+  void acceleration(int a) {
+    if (a != 1 && (!linked_ || hc_)) throw std::invalid_argument("acceleration is the fast chain's: it needs linkedBlocks = true and no level");
+    if (wroteBlocks_ || finished_) throw IllegalStateException("acceleration is chosen before the first block is written");
+    acceleration_ = a;
+  }
   void flush() { if (!finished_) { writeBlocks(buf_.size()); out_.flush(); } }  // :279-286: flush() writes the pending (possibly short) block
   void close() {                                                                  // :289-298
     if (finished_) return;
@@ -360,8 +373,8 @@ class LZ4FrameOutputStream {
     }
     wroteBlocks_ = true;
     if (linked_ && streamState_ && !streams_) streams_.reset(new CompressStreams(1));
-    const detail::Compressed c = linked_ ? (streamState_ ? detail::compressStream(*streams_, history_, data, maxBlockSize_)
-                                                         : detail::compressChain(e_, history_, data, maxBlockSize_, hc_, level_))
+    const detail::Compressed c = linked_ ? (streamState_ ? detail::compressStream(*streams_, history_, data, maxBlockSize_, acceleration_)
+                                                         : detail::compressChain(e_, history_, data, maxBlockSize_, hc_, level_, acceleration_))
                                          : detail::compressBlocks(e_, data, maxBlockSize_);
     if (linked_) {   // the last 64 KB written
       history_.insert(history_.end(), data.begin(), data.end());
@@ -408,6 +421,7 @@ class LZ4FrameOutputStream {
   bytes history_;         // (linked_) the last 64 KB written of the frame
   bool wroteBlocks_ = false;                   // a batch has gone to the compressor: the frame's way of compressing is fixed
   bool streamState_ = false;                   // (linked_, fast chain) one resident stream for the whole frame
+  int acceleration_ = 1;                       // (linked_, fast chain) LZ4_compress_fast_continue's last argument
   std::unique_ptr<CompressStreams> streams_;   // ... made at the first batch
 };
 

@@ -142,12 +142,24 @@ public final class LZ4HIPBatch {
    */
   public static void compressFastChain(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
       ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed) {
+    compressFastChain(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, 1);
+  }
+
+  /**
+   * {@link #compressFastChain} with {@code LZ4_compress_fast_continue}'s acceleration, one value for every block of the call: clamped
+   * to 1 .. 65537 as liblz4 does; 1 is the call without it.  These are the blocks {@code lz4 --fast=N} writes.
+   */
+  public static void compressFastChain(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
+      ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed, int acceleration) {
     if (chainConsumed.length != chainSrcOff.length) {
       throw new IllegalArgumentException("per-chain arrays differ in length");
     }
     checkChains(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen);
     final int n = srcLen.length, nc = chainSrcOff.length;
-    final int rc = LZ4HIPJNI.LZ4HIP_batchFastChain(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, n, nc);
+    final int rc = acceleration == 1
+        ? LZ4HIPJNI.LZ4HIP_batchFastChain(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, n, nc)
+        : LZ4HIPJNI.LZ4HIP_batchFastChainAccel(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, n, nc,
+            acceleration);
     if (rc != 0) {
       throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
     }
@@ -163,6 +175,15 @@ public final class LZ4HIPBatch {
    */
   public static void compressFastStream(CompressStreams streams, int[] streamId, ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen,
       int[] srcLen, int[] chainFirst, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed) {
+    compressFastStream(streams, streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, 1);
+  }
+
+  /**
+   * {@link #compressFastStream} with {@code LZ4_compress_fast_continue}'s acceleration for every block of THIS call (clamped to
+   * 1 .. 65537; 1 is the call without it).  A stream may be given another acceleration in every call.
+   */
+  public static void compressFastStream(CompressStreams streams, int[] streamId, ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen,
+      int[] srcLen, int[] chainFirst, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed, int acceleration) {
     if (chainConsumed.length != chainSrcOff.length || streamId.length != chainSrcOff.length) {
       throw new IllegalArgumentException("per-chain arrays differ in length");
     }
@@ -173,8 +194,11 @@ public final class LZ4HIPBatch {
       }
     }
     checkChains(src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen);
-    final int rc = LZ4HIPJNI.LZ4HIP_batchFastStream(streams.handle(), streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff,
-        destCap, outLen, chainConsumed, srcLen.length, chainSrcOff.length);
+    final int rc = acceleration == 1
+        ? LZ4HIPJNI.LZ4HIP_batchFastStream(streams.handle(), streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff,
+            destCap, outLen, chainConsumed, srcLen.length, chainSrcOff.length)
+        : LZ4HIPJNI.LZ4HIP_batchFastStreamAccel(streams.handle(), streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff,
+            destCap, outLen, chainConsumed, srcLen.length, chainSrcOff.length, acceleration);
     if (rc != 0) {
       throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
     }
@@ -215,6 +239,12 @@ public final class LZ4HIPBatch {
       compressFastStream(this, streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed);
     }
 
+    /** {@link LZ4HIPBatch#compressFastStream} on this set, at an acceleration */
+    public void compress(int[] streamId, ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
+        ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed, int acceleration) {
+      compressFastStream(this, streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, acceleration);
+    }
+
     /**
      * The same streams when their sources land anywhere -- a ring that wraps, alternating buffers, a dictionary elsewhere
      * ({@code lz4hip_compress_fast_stream_ext_batch}): every block has its own {@code srcOff[i]} inside its stream's window
@@ -224,6 +254,12 @@ public final class LZ4HIPBatch {
      */
     public void compressAt(int[] streamId, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, long[] chainHistEnd, int[] chainHistLen,
         long[] chainWinOff, long[] chainWinLen, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed) {
+      compressAt(streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dest, destOff, destCap, outLen, chainConsumed, 1);
+    }
+
+    /** {@link #compressAt} at an acceleration ({@code lz4hip_compress_fast_stream_ext_accel_batch}): as for {@link #compress} */
+    public void compressAt(int[] streamId, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, long[] chainHistEnd, int[] chainHistLen,
+        long[] chainWinOff, long[] chainWinLen, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed, int acceleration) {
       final int n = srcLen.length, nc = streamId.length;
       if (srcOff.length != n || destOff.length != n || destCap.length != n || outLen.length != n) {
         throw new IllegalArgumentException("per-block arrays differ in length");
@@ -241,8 +277,11 @@ public final class LZ4HIPBatch {
           throw new IllegalArgumentException("streamId must be strictly ascending and below the number of streams");
         }
       }
-      final int rc = LZ4HIPJNI.LZ4HIP_batchFastStreamAt(handle(), streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff,
-          chainWinLen, dest, destOff, destCap, outLen, chainConsumed, n, nc);
+      final int rc = acceleration == 1
+          ? LZ4HIPJNI.LZ4HIP_batchFastStreamAt(handle(), streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff,
+              chainWinLen, dest, destOff, destCap, outLen, chainConsumed, n, nc)
+          : LZ4HIPJNI.LZ4HIP_batchFastStreamAtAccel(handle(), streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff,
+              chainWinLen, dest, destOff, destCap, outLen, chainConsumed, n, nc, acceleration);
       if (rc != 0) {
         throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
       }

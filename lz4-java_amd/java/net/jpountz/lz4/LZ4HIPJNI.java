@@ -152,6 +152,19 @@ enum LZ4HIPJNI {
   static native int LZ4HIP_batchFastStreamAt(long set, int[] streamId, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst,
                                              long[] chainHistEnd, int[] chainHistLen, long[] chainWinOff, long[] chainWinLen, ByteBuffer dest,
                                              long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed, int nBlocks, int nChains);
+  /* The three calls above with LZ4_compress_fast_continue's acceleration as a trailing argument, one value for every block of the call
+   * (lz4hip_compress_fast_chain_accel_batch, lz4hip_compress_fast_stream_accel_batch, lz4hip_compress_fast_stream_ext_accel_batch):
+   * clamped to 1 .. 65537 as liblz4 does, and 1 is the call above.  A stream may be given another acceleration in every call. */
+  static native int LZ4HIP_batchFastChainAccel(ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen, int[] chainFirst,
+                                               ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed,
+                                               int nBlocks, int nChains, int acceleration);
+  static native int LZ4HIP_batchFastStreamAccel(long set, int[] streamId, ByteBuffer src, long[] chainSrcOff, int[] chainPrefixLen, int[] srcLen,
+                                                int[] chainFirst, ByteBuffer dest, long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed,
+                                                int nBlocks, int nChains, int acceleration);
+  static native int LZ4HIP_batchFastStreamAtAccel(long set, int[] streamId, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst,
+                                                  long[] chainHistEnd, int[] chainHistLen, long[] chainWinOff, long[] chainWinLen, ByteBuffer dest,
+                                                  long[] destOff, int[] destCap, int[] outLen, long[] chainConsumed, int nBlocks, int nChains,
+                                                  int acceleration);
   /* LZ4_compress_HC_continue over chains of linked blocks (prefix mode) at HC level `level`, DIRECT buffers: the arrays of
    * LZ4HIP_batchFastChain without chainConsumed.  outLen = liblz4's return values; a 0 does not end a chain.  Returns 0 or a negative
    * lz4hip_status (a null required argument: LZ4HIP_E_ARG). */

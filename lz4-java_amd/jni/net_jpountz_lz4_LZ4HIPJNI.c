@@ -446,11 +446,10 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchHCStream(JNIE
   return rc;
 }
 
-/* LZ4_compress_fast_continue over chains of linked blocks, DIRECT buffers: chainPrefixLen may be null */
-JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastChain(JNIEnv* env, jclass cls, jobject src, jlongArray chainSrcOff,
-    jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen,
-    jlongArray chainConsumed, jint nBlocks, jint nChains) {
-  (void)cls;
+/* LZ4_compress_fast_continue over chains of linked blocks, DIRECT buffers: chainPrefixLen may be null.  acceleration: the call's last
+ * argument; 1 is lz4hip_compress_fast_chain_batch, anything else lz4hip_compress_fast_chain_accel_batch (which clamps it) */
+static jint fast_chain(JNIEnv* env, jobject src, jlongArray chainSrcOff, jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest,
+    jlongArray destOff, jintArray destCap, jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains, jint acceleration) {
   if (nBlocks < 0 || nChains < 0) return LZ4HIP_E_ARG;
   batch_args_t b = {NULL, NULL, 7, {{chainSrcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {chainFirst, INTS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT},
                                     {destCap, INTS, JNI_ABORT}, {outLen, INTS, 0}, {chainConsumed, LONGS, 0}}};
@@ -458,10 +457,27 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastChain(JNI
   const int i_prefix = chainPrefixLen != NULL ? b.n_arrays - 1 : -1;
   jint rc = batch_pin(env, src, dest, &b);
   if (rc != 0) return rc;
-  rc = lz4hip_compress_fast_chain_batch(b.src, b.a[0].p, i_prefix >= 0 ? (const int32_t*)b.a[i_prefix].p : NULL, b.a[1].p, (const uint32_t*)b.a[2].p, b.dst,
-                                        b.a[3].p, b.a[4].p, b.a[5].p, b.a[6].p, (uint32_t)nBlocks, (uint32_t)nChains);
+  const int32_t* prefix = i_prefix >= 0 ? (const int32_t*)b.a[i_prefix].p : NULL;
+  if (acceleration == 1)
+    rc = lz4hip_compress_fast_chain_batch(b.src, b.a[0].p, prefix, b.a[1].p, (const uint32_t*)b.a[2].p, b.dst, b.a[3].p, b.a[4].p, b.a[5].p, b.a[6].p,
+                                          (uint32_t)nBlocks, (uint32_t)nChains);
+  else
+    rc = lz4hip_compress_fast_chain_accel_batch(b.src, b.a[0].p, prefix, b.a[1].p, (const uint32_t*)b.a[2].p, b.dst, b.a[3].p, b.a[4].p, b.a[5].p, b.a[6].p,
+                                                (uint32_t)nBlocks, (uint32_t)nChains, acceleration);
   batch_release(env, &b);
   return rc;
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastChain(JNIEnv* env, jclass cls, jobject src, jlongArray chainSrcOff,
+    jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen,
+    jlongArray chainConsumed, jint nBlocks, jint nChains) {
+  (void)cls;
+  return fast_chain(env, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, nBlocks, nChains, 1);
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastChainAccel(JNIEnv* env, jclass cls, jobject src, jlongArray chainSrcOff,
+    jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen,
+    jlongArray chainConsumed, jint nBlocks, jint nChains, jint acceleration) {
+  (void)cls;
+  return fast_chain(env, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, nBlocks, nChains, acceleration);
 }
 
 /* Resident compress streams (lz4hip_cstreams_*): a set of nStreams streams whose tables and index positions stay on the device between
@@ -513,11 +529,11 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1cstreamsConsumed(J
   return rc;
 }
 /* LZ4_compress_fast_continue on resident streams, DIRECT buffers: LZ4HIP_batchFastChain's arguments behind the set and the stream of
- * every chain (strictly ascending); chainPrefixLen may be null.  A 0 handle is LZ4HIP_E_ARG */
-JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStream(JNIEnv* env, jclass cls, jlong set, jintArray streamId, jobject src,
-    jlongArray chainSrcOff, jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap,
-    jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains) {
-  (void)cls;
+ * every chain (strictly ascending); chainPrefixLen may be null.  A 0 handle is LZ4HIP_E_ARG.  acceleration: as for fast_chain, for
+ * every block of THIS call (lz4hip_compress_fast_stream_accel_batch) */
+static jint fast_stream(JNIEnv* env, jlong set, jintArray streamId, jobject src, jlongArray chainSrcOff, jintArray chainPrefixLen, jintArray srcLen,
+    jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains,
+    jint acceleration) {
   if (set == 0 || nBlocks < 0 || nChains < 0) return LZ4HIP_E_ARG;
   batch_args_t b = {NULL, NULL, 8, {{chainSrcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {chainFirst, INTS, JNI_ABORT}, {destOff, LONGS, JNI_ABORT},
                                     {destCap, INTS, JNI_ABORT}, {outLen, INTS, 0}, {chainConsumed, LONGS, 0}, {streamId, INTS, JNI_ABORT}}};
@@ -525,19 +541,37 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStream(JN
   const int i_prefix = chainPrefixLen != NULL ? b.n_arrays - 1 : -1;
   jint rc = batch_pin(env, src, dest, &b);
   if (rc != 0) return rc;
-  rc = lz4hip_compress_fast_stream_batch((lz4hip_cstreams*)(intptr_t)set, (const uint32_t*)b.a[7].p, b.src, b.a[0].p,
-                                         i_prefix >= 0 ? (const int32_t*)b.a[i_prefix].p : NULL, b.a[1].p, (const uint32_t*)b.a[2].p, b.dst, b.a[3].p, b.a[4].p,
-                                         b.a[5].p, b.a[6].p, (uint32_t)nBlocks, (uint32_t)nChains);
+  const int32_t* prefix = i_prefix >= 0 ? (const int32_t*)b.a[i_prefix].p : NULL;
+  if (acceleration == 1)
+    rc = lz4hip_compress_fast_stream_batch((lz4hip_cstreams*)(intptr_t)set, (const uint32_t*)b.a[7].p, b.src, b.a[0].p, prefix, b.a[1].p,
+                                           (const uint32_t*)b.a[2].p, b.dst, b.a[3].p, b.a[4].p, b.a[5].p, b.a[6].p, (uint32_t)nBlocks, (uint32_t)nChains);
+  else
+    rc = lz4hip_compress_fast_stream_accel_batch((lz4hip_cstreams*)(intptr_t)set, (const uint32_t*)b.a[7].p, b.src, b.a[0].p, prefix, b.a[1].p,
+                                                 (const uint32_t*)b.a[2].p, b.dst, b.a[3].p, b.a[4].p, b.a[5].p, b.a[6].p, (uint32_t)nBlocks,
+                                                 (uint32_t)nChains, acceleration);
   batch_release(env, &b);
   return rc;
 }
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStream(JNIEnv* env, jclass cls, jlong set, jintArray streamId, jobject src,
+    jlongArray chainSrcOff, jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap,
+    jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains) {
+  (void)cls;
+  return fast_stream(env, set, streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, nBlocks, nChains, 1);
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStreamAccel(JNIEnv* env, jclass cls, jlong set, jintArray streamId, jobject src,
+    jlongArray chainSrcOff, jintArray chainPrefixLen, jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap,
+    jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains, jint acceleration) {
+  (void)cls;
+  return fast_stream(env, set, streamId, src, chainSrcOff, chainPrefixLen, srcLen, chainFirst, dest, destOff, destCap, outLen, chainConsumed, nBlocks, nChains,
+                     acceleration);
+}
 /* The same streams when their sources land anywhere, DIRECT buffers (lz4hip_compress_fast_stream_ext_batch): every block has its own
  * srcOff[i] inside the window src[chainWinOff[c], + chainWinLen[c]) of its stream; the stream's history ends at chainHistEnd[c] with
- * chainHistLen[c] bytes of it present.  Every array is required.  A 0 handle is LZ4HIP_E_ARG */
-JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStreamAt(JNIEnv* env, jclass cls, jlong set, jintArray streamId, jobject src,
-    jlongArray srcOff, jintArray srcLen, jintArray chainFirst, jlongArray chainHistEnd, jintArray chainHistLen, jlongArray chainWinOff,
-    jlongArray chainWinLen, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains) {
-  (void)cls;
+ * chainHistLen[c] bytes of it present.  Every array is required.  A 0 handle is LZ4HIP_E_ARG.  acceleration: as for fast_stream
+ * (lz4hip_compress_fast_stream_ext_accel_batch) */
+static jint fast_stream_at(JNIEnv* env, jlong set, jintArray streamId, jobject src, jlongArray srcOff, jintArray srcLen, jintArray chainFirst,
+    jlongArray chainHistEnd, jintArray chainHistLen, jlongArray chainWinOff, jlongArray chainWinLen, jobject dest, jlongArray destOff, jintArray destCap,
+    jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains, jint acceleration) {
   if (set == 0 || nBlocks < 0 || nChains < 0) return LZ4HIP_E_ARG;
   batch_args_t b = {NULL, NULL, 12, {{streamId, INTS, JNI_ABORT}, {srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {chainFirst, INTS, JNI_ABORT},
                                      {chainHistEnd, LONGS, JNI_ABORT}, {chainHistLen, INTS, JNI_ABORT}, {chainWinOff, LONGS, JNI_ABORT},
@@ -545,11 +579,31 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStreamAt(
                                      {chainConsumed, LONGS, 0}}};
   jint rc = batch_pin(env, src, dest, &b);
   if (rc != 0) return rc;
-  rc = lz4hip_compress_fast_stream_ext_batch((lz4hip_cstreams*)(intptr_t)set, (const uint32_t*)b.a[0].p, b.src, b.a[1].p, b.a[2].p, (const uint32_t*)b.a[3].p,
-                                             b.a[4].p, b.a[5].p, b.a[6].p, b.a[7].p, b.dst, b.a[8].p, b.a[9].p, b.a[10].p, b.a[11].p, (uint32_t)nBlocks,
-                                             (uint32_t)nChains);
+  if (acceleration == 1)
+    rc = lz4hip_compress_fast_stream_ext_batch((lz4hip_cstreams*)(intptr_t)set, (const uint32_t*)b.a[0].p, b.src, b.a[1].p, b.a[2].p, (const uint32_t*)b.a[3].p,
+                                               b.a[4].p, b.a[5].p, b.a[6].p, b.a[7].p, b.dst, b.a[8].p, b.a[9].p, b.a[10].p, b.a[11].p, (uint32_t)nBlocks,
+                                               (uint32_t)nChains);
+  else
+    rc = lz4hip_compress_fast_stream_ext_accel_batch((lz4hip_cstreams*)(intptr_t)set, (const uint32_t*)b.a[0].p, b.src, b.a[1].p, b.a[2].p,
+                                                     (const uint32_t*)b.a[3].p, b.a[4].p, b.a[5].p, b.a[6].p, b.a[7].p, b.dst, b.a[8].p, b.a[9].p, b.a[10].p,
+                                                     b.a[11].p, (uint32_t)nBlocks, (uint32_t)nChains, acceleration);
   batch_release(env, &b);
   return rc;
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStreamAt(JNIEnv* env, jclass cls, jlong set, jintArray streamId, jobject src,
+    jlongArray srcOff, jintArray srcLen, jintArray chainFirst, jlongArray chainHistEnd, jintArray chainHistLen, jlongArray chainWinOff,
+    jlongArray chainWinLen, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains) {
+  (void)cls;
+  return fast_stream_at(env, set, streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dest, destOff, destCap, outLen,
+                        chainConsumed, nBlocks, nChains, 1);
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchFastStreamAtAccel(JNIEnv* env, jclass cls, jlong set, jintArray streamId, jobject src,
+    jlongArray srcOff, jintArray srcLen, jintArray chainFirst, jlongArray chainHistEnd, jintArray chainHistLen, jlongArray chainWinOff,
+    jlongArray chainWinLen, jobject dest, jlongArray destOff, jintArray destCap, jintArray outLen, jlongArray chainConsumed, jint nBlocks, jint nChains,
+    jint acceleration) {
+  (void)cls;
+  return fast_stream_at(env, set, streamId, src, srcOff, srcLen, chainFirst, chainHistEnd, chainHistLen, chainWinOff, chainWinLen, dest, destOff, destCap, outLen,
+                        chainConsumed, nBlocks, nChains, acceleration);
 }
 
 /* LZ4_compress_HC_continue over chains of linked blocks at an HC level, DIRECT buffers: chainPrefixLen may be null */

@@ -87,19 +87,21 @@ def _compress_batch(engine, data, blockSize):
     return dst, bound, lens, sizes
 
 
-def _compress_chain(engine, history, data, blockSize, level=None, streams=None):
+def _compress_chain(engine, history, data, blockSize, level=None, streams=None, acceleration=1):
     """compress data[i*blockSize : +blockSize] for all i as ONE chain of linked blocks behind `history` -> as _compress_batch; level
     None: the fast chain (LZ4_compress_fast_continue), else the HC chain at that level (LZ4_compress_HC_continue); streams: a set
-    whose stream 0 is the frame's and goes on from the batch before (`history` is what it has consumed, at most 64 KB of it)"""
+    whose stream 0 is the frame's and goes on from the batch before (`history` is what it has consumed, at most 64 KB of it);
+    acceleration (the fast chain and the stream; 1: the calls as they were): LZ4_compress_fast_continue's last argument"""
     n = (len(data) + blockSize - 1) // blockSize
     bound = maxCompressedLength(blockSize)
     dst = bytearray(n * bound)
     lens = [min(blockSize, len(data) - i * blockSize) for i in range(n)]
     P = len(history)
+    kw = {"acceleration": acceleration} if acceleration != 1 else {}
     if streams is not None:
-        sizes, _ = streams.compress([0], history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P])
+        sizes, _ = streams.compress([0], history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P], **kw)
     elif level is None:
-        sizes, _ = engine.compressFastChain(history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P])
+        sizes, _ = engine.compressFastChain(history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P], **kw)
     else:
         sizes = engine.compressHCChain(history + data, [P], lens, [0, n], dst, [i * bound for i in range(n)], [bound] * n, [P], level)
     for s in sizes:
@@ -222,10 +224,14 @@ class LZ4FrameOutputStream(io.RawIOBase):
     linkedBlocks=True, streamState=True (the fast chain only; the default is False and its bytes are unchanged): the frame is ONE
     compress stream whose table and index position stay on the device from batch to batch (engine.newCompressStreams: a
     CompressStreams set of one), so the blocks are what ONE LZ4_stream_t writes for the whole frame and THE FRAME'S BYTES DO NOT DEPEND
-    ON batchBlocks or on flush() calls that fall on block boundaries.  The stream is freed by close()."""
+    ON batchBlocks or on flush() calls that fall on block boundaries.  The stream is freed by close().
+
+    linkedBlocks=True, acceleration=N (the fast chain, with or without streamState; the default is 1 and its bytes are unchanged):
+    every block is compressed with LZ4_compress_fast_continue(..., N) -- the blocks `lz4 --fast=N` writes (its frames' header flags
+    and block sizes are its own).  N is clamped to 1 .. 65537 as liblz4 does.  It has no meaning for an HC level."""
 
     def __init__(self, out, blockSize=BLOCKSIZE.SIZE_4MB, knownSize=-1, *bits, engine=None, batchBlocks=64, linkedBlocks=False, level=None,
-                 streamState=False):
+                 streamState=False, acceleration=1):
         super().__init__()
         self.out = out
         self.engine = engine or HIPEngine()
@@ -238,6 +244,9 @@ class LZ4FrameOutputStream(io.RawIOBase):
             raise ValueError("level selects the linked-block compressor: it needs linkedBlocks=True (independent HC blocks: HIPEngine(hcLevel))")
         if streamState and (not linkedBlocks or level is not None):
             raise ValueError("streamState continues the fast chain's stream: it needs linkedBlocks=True and no level")
+        self.acceleration = int(acceleration)   # (linkedBlocks, no level) LZ4_compress_fast_continue's last argument
+        if self.acceleration != 1 and (not linkedBlocks or level is not None):
+            raise ValueError("acceleration is the fast chain's: it needs linkedBlocks=True and no level")
         if streamState and not hasattr(self.engine, "newCompressStreams"):
             raise ValueError("the engine has no resident compress streams")
         if linkedBlocks:
@@ -303,7 +312,7 @@ class LZ4FrameOutputStream(io.RawIOBase):
         if self.linkedBlocks:                          # one chain behind the last 64 KB written; assembled on the host
             if self._streamState and self._streams is None:
                 self._streams = self.engine.newCompressStreams(1)
-            dst, bound, lens, sizes = _compress_chain(self.engine, self.history, data, self.maxBlockSize, self.level, self._streams)
+            dst, bound, lens, sizes = _compress_chain(self.engine, self.history, data, self.maxBlockSize, self.level, self._streams, self.acceleration)
             self.history = (self.history + data)[-65536:]
         elif hasattr(self.engine, "containerBlocks"):   # assembled on the device
             self.out.write(self.engine.containerBlocks(LZ4HIPBatch.FRAME_BLOCKS, data, self.maxBlockSize, block_checksum))
