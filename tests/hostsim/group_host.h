@@ -3,6 +3,9 @@
 // performs all lanes' loads first and all lanes' stores afterwards (SIMT order), with the same
 // chunking, wild over-copy and replicate logic as lz4-java_amd/csrc/group_dev.h, and records any
 // access outside the source / destination slots.
+// This twin of csrc/group_dev.h is checked primitive by primitive (the copies, seq_*, st_*, the wave loop's lane-parallel side, its
+// ring accesses and vcopy_run; not yet rg_* / rs_* / sr_* / step_*, pm_* / sq_*): tests/backend/probes.h runs on both,
+// tests/test_gpu_backend.py compares the images on the GPU, tests/test_backend_hostsim.py holds this side to plain definitions.
 #pragma once
 #include <stdint.h>
 #include <string.h>

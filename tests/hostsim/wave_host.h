@@ -5,6 +5,8 @@
 // with the oracle before any GPU time is spent.  Per-lane values are 64-element vectors; LDS
 // atomics are applied in a PSEUDO-RANDOM lane order on purpose: the algorithm must not depend on
 // the order in which the hardware serialises colliding lanes of one DS instruction.
+// This twin of csrc/wave_dev.h is checked primitive by primitive: tests/backend/probes.h runs on both, tests/test_gpu_backend.py
+// compares the images on the GPU, tests/test_backend_hostsim.py holds this side to plain definitions.
 #pragma once
 #include <stdint.h>
 #include <string.h>

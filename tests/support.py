@@ -1,5 +1,5 @@
 """What the tests' helper programs share: building and loading the lane simulators of tests/hostsim (build_sim), the C++ mirror
-programs of tests/cpp (build_mirror), its sanitized host-only programs (build_sanitized), the fake-JNI programs of tests/jni_stub (build_fake_jni) and the oracle's CPU harness; the
+programs of tests/cpp (build_mirror), the device probes of tests/backend (build_devprobe), its sanitized host-only programs (build_sanitized), the fake-JNI programs of tests/jni_stub (build_fake_jni) and the oracle's CPU harness; the
 status constants of the C ABI; running a child script (run_child); and what the *_multidev_child.py scripts do alike (init_repeated,
 slots, check_slots).  A plain module, imported by the test files and the child scripts."""
 import ctypes as C
@@ -68,6 +68,23 @@ def build_sim(stem, variant="", flags=(), extra_deps=(), src_dir=HOSTSIM, out_di
                 if os.path.exists(t):
                     os.remove(t)
     return C.CDLL(so)
+
+
+# ---- the device instantiation of the backend probes (tests/backend/devprobe.hip -> tests/backend/libdevprobe.so) ----
+DEVPROBE_SO = os.path.join(ROOT, "tests", "backend", "libdevprobe.so")
+DEVPROBE_DEPS = ("tests/backend/devprobe.hip", "tests/backend/probes.h", "lz4-java_amd/csrc/wave_dev.h", "lz4-java_amd/csrc/group_dev.h")
+
+
+def build_devprobe():
+    """tests/backend/libdevprobe.so, loaded: rebuilt when a dependency is newer (or it is missing) and hipcc exists, otherwise what
+    build() of __graft_entry__.py made.  With neither a library nor hipcc: an AssertionError that names build() -- not a skip."""
+    import __graft_entry__ as entry        # (the recipe is build()'s: one command line in one place)
+    stale = not os.path.exists(DEVPROBE_SO) or newer_than(DEVPROBE_SO, [os.path.join(ROOT, d) for d in DEVPROBE_DEPS])
+    if stale and entry.find_hipcc():
+        entry.compile_devprobe()
+    assert os.path.exists(DEVPROBE_SO), ("tests/backend/libdevprobe.so is missing and there is no hipcc to build it: "
+                                         "run build() of __graft_entry__.py where ROCm is installed (python -c 'import __graft_entry__ as g; g.build()')")
+    return C.CDLL(DEVPROBE_SO)
 
 
 def _link_lz4hip():
