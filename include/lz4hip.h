@@ -97,7 +97,9 @@ int lz4hip_version(void);
  *   per CU instead of five (0: every block on the five-chain kernel);
  * "hc_chain_segment" = 4096 .. 1073741824 (default 1048576): positions per build item of lz4hip_compress_hc_chain_batch*; every value
  *   gives the same bytes (a segment warms its table up over the 65535 positions in front of it: at most 6.25 % more build work on a
- *   long chain at the default, none on chains of up to 1 MiB).
+ *   long chain at the default, none on chains of up to 1 MiB);
+ * "dstream_inorder" = 0 (default) / 1: lz4hip_decompress_safe_stream_inorder_batch decodes in order the blocks whose slots overlap the
+ *   history they can reach / every block; where no slot overlaps both give the same bytes (that call's section, below).
  * Routed launches on any number of streams of a device are independent: the word a launch's route kernel writes and its candidate kernels
  * read is one of a per-device ring, and a word's next use is ordered -- on the device, by an event; the host never waits -- behind the
  * last candidate kernel of the launch that used it before, on whatever stream either runs.
@@ -316,6 +318,51 @@ int lz4hip_decompress_safe_stream_batch(lz4hip_dstream_state* state, const uint8
                                         const int32_t* src_len, const uint32_t* chain_first, uint8_t* dst,
                                         const uint64_t* dst_off, const int32_t* dst_cap, const uint64_t* chain_win_off,
                                         const uint64_t* chain_win_len, int32_t* out_len, uint32_t n_blocks, uint32_t n_chains);
+
+/* DECODE STREAMS WHOSE SLOTS OVERLAP THEIR HISTORY (MINIMAL RINGS): the twin of lz4hip_decompress_safe_stream_batch that lifts its one
+ * exclusion.  Same 13 arguments in the same order, same state record, same state machine, argument errors, window rules, sharding and
+ * staging; what differs is what the BYTES are where a block's slot overlaps the history the block can reach -- the layouts liblz4
+ * tells its users to use: the ring of LZ4_decoderRingBufferSize() / LZ4_DECODER_RING_BUFFER_SIZE (65536 + 14 + maxBlock), and small
+ * rings kept in step with the encoder's (liblz4's ring-buffer streaming example).
+ *   - THE CONTRACT is the plain definition: a block is decoded sequence by sequence; within a sequence the literals come first, then the
+ *     match, byte by byte, forward; each byte is read at the moment it is due; nothing is stored past the last byte of a sequence.
+ *     A match's source follows the state exactly as above: the prefix directly in front of the block, else offset - position bytes back
+ *     from ext_end, and a match that runs past the dictionary's end continues at the prefix's start, or at the block's own start when
+ *     there is no prefix.  out_len and the state written back are liblz4's on every input, as for the call above;
+ *   - THE BYTES ARE LIBLZ4'S wherever liblz4 does not itself overwrite a source before reading it: on every block of every stream an
+ *     encoder wrote that the tests decode in such rings (LZ4_compress_fast_continue on rings of 65536 + 14 + maxBlock that wrap when
+ *     the block, or maxBlock, no longer fits, with the exact and with the full capacity; rings of 1024 .. 70000 bytes kept in step
+ *     with the writer's), and on every hand-built stream whose match source lies 31 bytes or more ahead of its destination;
+ *   - THE EXCEPTION: a match whose source lies less than 31 bytes AHEAD of its own destination.  liblz4 1.9.3's fast loop copies literals
+ *     in 32-byte steps and its safe loop in 8-byte steps, past the run's end, so it overwrites such a source before the match reads
+ *     it: measured on the tests' grid of hand-built two-block streams, liblz4 leaves the plain definition in 1017 of the
+ *     3861 cases with a source 1 .. 30 bytes ahead and in none of the 4290 cases from 31 bytes on (with a short
+ *     literal tail, where only its safe loop runs, and where the match runs past the dictionary's end into the block's own first
+ *     bytes: 1 .. 8 bytes ahead alone).  There the engine's bytes are the plain definition's, not liblz4's.  Neither are they where a
+ *     hand-built match has its source BEHIND its destination inside the overlapped dictionary and is longer than that distance:
+ *     the plain definition reads what the match has just written (no encoder emits such a match).  The same arithmetic says where a real ring can come near it: in a minimal ring a source can lie as little as 16
+ *     bytes ahead of the block's first byte, so a match at the largest offsets, decoded directly behind a literal run of 15 or more
+ *     bytes, is where liblz4's own result depends on its copy widths -- no stream the tests' encoder wrote contains one, and this
+ *     consequence is stated, not measured;
+ *   - THE PER-BLOCK CHOICE: per block the walk tests, from the state it holds, whether [d, d + cap) intersects the piece of the external
+ *     dictionary the block can reach -- the last min(ext_len, 65535 - min(prefix_len if the block grows the prefix else 0, 65535))
+ *     bytes in front of ext_end, after a jump's ext = prefix (a growing prefix ends where the slot begins: it never overlaps).  Such
+ *     a block is decoded by the in-order tier (exact-extent forward copies, every match source loaded behind a wait for every store
+ *     of the sequences in front of it); every other block by exactly the code lz4hip_decompress_safe_stream_batch runs.
+ *     lz4hip_set_option("dstream_inorder", 1) sends EVERY block of this call through the in-order tier (0, the default: the
+ *     per-block test; any other value is LZ4HIP_E_ARG); where no slot overlaps, both settings give the same bytes, and the knob
+ *     never touches lz4hip_decompress_safe_stream_batch;
+ *   - THE RING RULE that now holds: any ring liblz4's own decoder accepts -- LZ4_DECODER_RING_BUFFER_SIZE(maxBlock) bytes
+ *     (lz4hip_decoder_ring_buffer_size, below) and rings in step with the writer's -- with the exception above;
+ *   - the two entry points may alternate on one stream from call to call: the state is plain host data and both read and write it alike;
+ *   - one kernel, decode_stream_inorder_kernel, of decode_stream_kernel's shape.  Host pointers only, as the call above.             */
+int lz4hip_decompress_safe_stream_inorder_batch(lz4hip_dstream_state* state, const uint8_t* src, const uint64_t* src_off,
+                                                const int32_t* src_len, const uint32_t* chain_first, uint8_t* dst,
+                                                const uint64_t* dst_off, const int32_t* dst_cap, const uint64_t* chain_win_off,
+                                                const uint64_t* chain_win_len, int32_t* out_len, uint32_t n_blocks, uint32_t n_chains);
+/* LZ4_decoderRingBufferSize(max_block) of liblz4 1.9.3: the smallest ring LZ4_decompress_safe_continue decodes blocks of up to max_block
+ * bytes into -- 65536 + 14 + max(max_block, 16); 0 for a negative max_block or one above 0x7E000000.  Needs no device.              */
+int lz4hip_decoder_ring_buffer_size(int max_block);
 
 /* COMPRESS CHAINS OF LINKED BLOCKS: the return values and bytes of liblz4 1.9.3's streaming compressor in its prefix mode, acceleration 1
  * -- what lz4hip_decompress_safe_chain_batch* reads and what the lz4 command line writes by default.  A CHAIN is a run of blocks whose

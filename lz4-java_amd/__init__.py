@@ -65,6 +65,9 @@ C_ABI = {
     "lz4hip_decompress_safe_chain_batch_dev": (C.c_int, [C.c_void_p] * 12 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_decompress_safe_stream_batch": (C.c_int, [_u64p, C.c_void_p, _u64p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _u64p, _u64p, _i32p,
                                                       C.c_uint32, C.c_uint32]),
+    "lz4hip_decompress_safe_stream_inorder_batch": (C.c_int, [_u64p, C.c_void_p, _u64p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _u64p, _u64p, _i32p,
+                                                              C.c_uint32, C.c_uint32]),
+    "lz4hip_decoder_ring_buffer_size": (C.c_int, [C.c_int]),
     "lz4hip_compress_fast_chain_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32]),
     "lz4hip_compress_fast_chain_batch_dev": (C.c_int, [C.c_void_p] * 10 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]),
     "lz4hip_compress_fast_chain_accel_batch": (C.c_int, [C.c_void_p, _u64p, C.c_void_p, _i32p, _u32p, C.c_void_p, _u64p, _i32p, _i32p, _u64p, C.c_uint32, C.c_uint32,
@@ -941,14 +944,17 @@ class LZ4HIPBatch:
         return list(out[:n]), list(cout[:nc])
 
     @classmethod
-    def decompressSafeStream(cls, state, src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainWinOff, chainWinLen):
+    def decompressSafeStream(cls, state, src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainWinOff, chainWinLen, inOrder=False):
         """LZ4_decompress_safe_continue on streams whose blocks land anywhere -- rings, alternating buffers, save areas, dictionaries
         elsewhere (lz4hip_decompress_safe_stream_batch): stream c is the blocks chainFirst[c] .. chainFirst[c + 1] - 1 of this call,
         block i is decoded to dst[dstOff[i]:+dstCap[i]], inside the stream's window dst[chainWinOff[c]:+chainWinLen[c]].  state[c] is
         the stream's (prefixEnd, prefixLen, extEnd, extLen) as offsets into dst -- (0, 0, 0, 0) is a fresh stream,
         LZ4_setStreamDecode(dst + p, n) is (p + n, n, 0, 0) -> (outLen, newState): liblz4's return value per block (CHAIN_STOPPED
         behind a stream's first negative one; a list, or an int32 array for numpy inputs) and the list of the streams' states behind
-        the call, to be handed to the next one.  DecodeStreams keeps the states for its caller"""
+        the call, to be handed to the next one.  DecodeStreams keeps the states for its caller.  inOrder=True is the twin
+        lz4hip_decompress_safe_stream_inorder_batch: the same call for streams whose slots overlap the history they can reach -- the ring
+        of decoderRingBufferSize(maxBlock) bytes, small rings kept in step with the writer's -- where the bytes are the plain
+        byte-forward definition's (include/lz4hip.h says when those are liblz4's); the two may alternate on one stream"""
         n, nc = len(srcOff), len(state)
         if not (len(srcLen) == len(dstOff) == len(dstCap) == n):
             raise ValueError("per-block arrays differ in length")
@@ -973,9 +979,10 @@ class LZ4HIPBatch:
         sp, sk = _ro_ptr(src)
         dp, dk = _rw_ptr(dst)
         out = (C.c_int32 * max(n, 1))()
-        _chk(lib().lz4hip_decompress_safe_stream_batch(flat, sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst), dp,
-                                                       _arr(C.c_uint64, dstOff), _arr(C.c_int32, dstCap), _arr(C.c_uint64, chainWinOff),
-                                                       _arr(C.c_uint64, chainWinLen), out, n, nc))
+        call = lib().lz4hip_decompress_safe_stream_inorder_batch if inOrder else lib().lz4hip_decompress_safe_stream_batch
+        _chk(call(flat, sp, _arr(C.c_uint64, srcOff), _arr(C.c_int32, srcLen), _arr(C.c_uint32, chainFirst), dp,
+                  _arr(C.c_uint64, dstOff), _arr(C.c_int32, dstCap), _arr(C.c_uint64, chainWinOff),
+                  _arr(C.c_uint64, chainWinLen), out, n, nc))
         new = [tuple(flat[4 * c:4 * c + 4]) for c in range(nc)]
         if hasattr(srcOff, "dtype"):
             import numpy as np
@@ -1320,10 +1327,12 @@ class DecodeStreams:
     device.  Every stream gives, over all the calls that name it, the values and bytes ONE LZ4_streamDecode_t gives, however its
     blocks are cut into calls (LZ4HIPBatch.decompressSafeStream says when the bytes are liblz4's: the ring rule)."""
 
-    def __init__(self, n):
+    def __init__(self, n, inOrder=False):
+        """inOrder: the set's calls go to the in-order twin (LZ4HIPBatch.decompressSafeStream(inOrder=True)) unless a call says otherwise"""
         if n < 1:
             raise ValueError("a set has at least one stream")
         self._state = [(0, 0, 0, 0)] * int(n)
+        self.inOrder = bool(inOrder)
 
     def __len__(self):
         return len(self._state)
@@ -1343,13 +1352,14 @@ class DecodeStreams:
         """-> the (prefixEnd, prefixLen, extEnd, extLen) of the listed streams (None: all of them)"""
         return [self._state[c] for c in (range(len(self._state)) if streamId is None else streamId)]
 
-    def decompress(self, streamId, src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainWinOff, chainWinLen):
-        """LZ4HIPBatch.decompressSafeStream for the streams streamId (distinct ids, one per chain of the call) -> outLen"""
+    def decompress(self, streamId, src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap, chainWinOff, chainWinLen, inOrder=None):
+        """LZ4HIPBatch.decompressSafeStream for the streams streamId (distinct ids, one per chain of the call) -> outLen.  inOrder: None =
+        the set's own setting; the two entry points may alternate on a stream from call to call"""
         ids = [int(c) for c in streamId]
         if len(set(ids)) != len(ids):
             raise ValueError("a stream is named twice")
         out, new = LZ4HIPBatch.decompressSafeStream([self._state[c] for c in ids], src, srcOff, srcLen, chainFirst, dst, dstOff, dstCap,
-                                                    chainWinOff, chainWinLen)
+                                                    chainWinOff, chainWinLen, inOrder=self.inOrder if inOrder is None else bool(inOrder))
         for c, s in zip(ids, new):
             self._state[c] = s
         return out
@@ -1628,9 +1638,16 @@ class DeviceBatch:
         _chk(lib().lz4hip_gen_blocks_dev(dst.data_ptr(), stride, block_len, seed, first_idx, litmax, win, n_blocks, dev, st))
 
 
+def decoderRingBufferSize(maxBlock):
+    """LZ4_decoderRingBufferSize: the smallest ring a stream of blocks of up to maxBlock bytes is decoded into (DecodeStreams(inOrder=True));
+    0 for a negative maxBlock or one above 0x7E000000"""
+    return int(lib().lz4hip_decoder_ring_buffer_size(int(maxBlock)))
+
+
 def set_option(name, value):
     """a tuning knob of include/lz4hip.h: "decode_stage", "decode_pipe", "decode_route_short", "decode_route_slots" (1 .. 256 of the route
-    ring's slots handed out), "decode_ring", "decode_lanes", "compress_core", "compress_pack", "hc_chain_segment", "compress_switch".  Every
+    ring's slots handed out), "decode_ring", "decode_lanes", "compress_core", "compress_pack", "hc_chain_segment", "compress_switch", "dstream_inorder"
+    (1: every block of decompressSafeStream(inOrder=True) goes through the in-order tier, not only those whose slots overlap).  Every
     setting produces the same bytes; an unknown name or a value outside the knob's range raises LZ4HIPError"""
     _chk(lib().lz4hip_set_option(name.encode(), value))
 

@@ -97,14 +97,16 @@ struct DeviceGuard {  // callers (e.g. PyTorch) own the thread's current device:
 // arrays and host path, plus the slot of every chain's stream and the device's share of the set's state (BlockCall::cs_*, StreamShare)
 // OP_DECOMPRESS_STREAM: LZ4_decompress_safe_continue on streams whose blocks land anywhere (every mode of LZ4_streamDecode_t): its
 // arrays and state records are BlockCall::dstream; the host path is dstream_host_shard
+// OP_DECOMPRESS_STREAM_INORDER: the same streams where a block's slot may overlap the history the block can reach (minimal rings): OP_DECOMPRESS_STREAM's
+// arrays, records and host path; BlockCall::param is the "dstream_inorder" knob (1: every block in order, 0: the overlapping ones)
 // OP_COMPRESS_XSTREAM: the same resident streams when their sources land anywhere (liblz4's external-dictionary mode included): its
 // arrays are BlockCall::cxstream, which carries the device's share of the set's state; the host path is cxstream_host_shard
 // OP_COMPRESS_HC_STREAM: LZ4_compress_HC_continue on streams whose sources land anywhere, both of its modes: its arrays are
 // BlockCall::hcstream, the linear image the host has made of the call (host_staging.h HcsImage); the host path is hcstream_host_shard
 enum Op { OP_COMPRESS_FAST, OP_DECODE_SAFE, OP_DECODE_FAST, OP_COMPRESS_HC, OP_COMPRESS_ACCEL, OP_COMPRESS_DEST, OP_DECODE_PARTIAL, OP_COMPRESS_HC_DEST,
           OP_DECODED_SIZE, OP_DECODE_DICT, OP_COMPRESS_DICT, OP_COMPRESS_HC_DICT, OP_DECOMPRESS_CHAIN, OP_COMPRESS_CHAIN, OP_COMPRESS_HC_CHAIN, OP_COMPRESS_STREAM,
-          OP_DECOMPRESS_STREAM, OP_COMPRESS_XSTREAM, OP_COMPRESS_HC_STREAM };
-constexpr int OP_COUNT = OP_COMPRESS_HC_STREAM + 1;   // (the last enumerator)
+          OP_DECOMPRESS_STREAM, OP_COMPRESS_XSTREAM, OP_COMPRESS_HC_STREAM, OP_DECOMPRESS_STREAM_INORDER };
+constexpr int OP_COUNT = OP_DECOMPRESS_STREAM_INORDER + 1;   // (the last enumerator)
 // What an operation is, said once; everything below asks these and launch_block, nothing else compares ops.
 // a compressor: on the host path only the bytes it produced come back, packed on the device (launch_pack)
 constexpr bool op_compresses(Op op) { return op == OP_COMPRESS_FAST || op == OP_COMPRESS_HC || op == OP_COMPRESS_ACCEL || op == OP_COMPRESS_DEST || op == OP_COMPRESS_HC_DEST || op == OP_COMPRESS_DICT || op == OP_COMPRESS_HC_DICT || op == OP_COMPRESS_CHAIN || op == OP_COMPRESS_HC_CHAIN || op == OP_COMPRESS_STREAM || op == OP_COMPRESS_XSTREAM || op == OP_COMPRESS_HC_STREAM; }
@@ -130,6 +132,7 @@ struct BlockCall {
   Op op;
   int param = 0;                    // op_uses_hc_ws: the level (hc_level); OP_COMPRESS_ACCEL: the acceleration (accel_clamp, >= 2);
                                     // OP_COMPRESS_CHAIN, _STREAM, _XSTREAM: the acceleration (accel_clamp; 0 and 1: the acceleration-1 kernels)
+                                    // OP_DECOMPRESS_STREAM_INORDER: 1 = every block in order
   const int32_t* target = nullptr;  // OP_DECODE_PARTIAL: per-block target sizes; nullptr: dst_cap already is partial_room (host path)
   int32_t* consumed = nullptr;      // op_has_consumed: the input consumed per block
   void* hc_ws = nullptr;            // op_uses_hc_ws: device workspace for hc_span bytes of source; nullptr: launch_block learns the
@@ -139,7 +142,7 @@ struct BlockCall {
   int32_t dict_len = 0;                 // its length
   const lz4hip::ChainArgs* chain = nullptr;   // OP_DECOMPRESS_CHAIN: the call's arrays on the device
   const lz4hip::CChainArgs* cchain = nullptr; // op_takes_cchain: the call's arrays on the device
-  const lz4hip::DStreamArgs* dstream = nullptr;   // OP_DECOMPRESS_STREAM: the call's arrays and state records on the device
+  const lz4hip::DStreamArgs* dstream = nullptr;   // OP_DECOMPRESS_STREAM, _INORDER: the call's arrays and state records on the device
   const lz4hip::CXStreamArgs* cxstream = nullptr; // OP_COMPRESS_XSTREAM: the call's arrays on the device, the slots and the set's state
   const lz4hip::HcStreamArgs* hcstream = nullptr; // OP_COMPRESS_HC_STREAM: the call's linear image and its arrays on the device
   void* hc_scratch = nullptr;           // op_needs_chain_scratch: lz4hip::hc_chain_scratch_bytes of device memory
@@ -170,6 +173,7 @@ std::atomic<int> g_decode_lanes{0};   // "decode_lanes"; 0 = kernel default
 std::atomic<int> g_decode_stage{-1};  // "decode_stage": 1 = LDS output staging in the plain loop
 std::atomic<int> g_decode_pipe{-1};   // "decode_pipe": 3 = ring loop, 2 = deep loop, 1/0 = pipelined interior loop on/off, -1 = kernel default
 std::atomic<int> g_decode_ring{0};    // "decode_ring": bytes of the ring loop's output ring (0 = default for the lane count)
+std::atomic<int> g_dstream_inorder{0};   // "dstream_inorder": lz4hip_decompress_safe_stream_inorder_batch decodes 1 = every block in order, 0 = those whose slot overlaps their history
 
 // lz4hip_set_option "compress_core": 5 = adaptive two-pass (default): the lean core with a writer wavefront per chain finishes
 // the blocks of long sequences, the window-parallel core the others; 3 = lean core only; 1 = window-parallel core only (the
@@ -412,6 +416,11 @@ int launch_block(const BlockCall& c, const lz4hip::BatchArgs& a, hipStream_t st)
     case OP_DECOMPRESS_STREAM:   // decode_stream_kernel draws streams from the queue word
       if (!c.dstream) return fail(LZ4HIP_E_ARG, kNullArg);
       return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_decompress_stream(*c.dstream, q, lz4hip::device_cus(), st); });
+    case OP_DECOMPRESS_STREAM_INORDER: {   // decode_stream_inorder_kernel draws streams from the queue word
+      if (!c.dstream) return fail(LZ4HIP_E_ARG, kNullArg);
+      const lz4hip::DStreamInorderArgs ia{*c.dstream, c.param ? 1u : 0u};
+      return with_queue_word(st, [&](uint32_t* q) { return lz4hip::launch_decompress_stream_inorder(ia, q, lz4hip::device_cus(), st); });
+    }
     case OP_COMPRESS_CHAIN:   // compress_fast_chain_cu_kernel draws chains from the queue word
       if (!c.cchain) return fail(LZ4HIP_E_ARG, kNullArg);
       return with_queue_word(st, [&](uint32_t* q) {
@@ -1052,6 +1061,8 @@ struct DStreamHost {
   lz4hip_dstream_state* state; const uint8_t* src; const uint64_t* src_off; const int32_t* src_len; const uint32_t* chain_first;
   uint8_t* dst; const uint64_t* dst_off; const int32_t* dst_cap; const uint64_t* win_off; const uint64_t* win_len; int32_t* out;
   uint32_t n_blocks, n_chains;
+  Op op = OP_DECOMPRESS_STREAM;   // or OP_DECOMPRESS_STREAM_INORDER, with
+  int every = 0;                  // its BlockCall::param
 };
 static_assert(sizeof(lz4hip_dstream_state) == sizeof(staging::DsState) && sizeof(lz4hip_dstream_state) == sizeof(lz4hip::DStreamState) &&
               offsetof(lz4hip_dstream_state, ext_end) == offsetof(staging::DsState, ext_end) && offsetof(lz4hip_dstream_state, ext_end) == offsetof(lz4hip::DStreamState, ext_end),
@@ -1103,7 +1114,7 @@ int dstream_host_shard(const DStreamHost& h, int ord, uint32_t c0, uint32_t c1, 
     if (!sh.upload_runs(s, s.h_dst, s.d_dst, runs, "H2D history")) return false;
     const lz4hip::DStreamArgs a{(const uint8_t*)s.d_src.p, m.src_off.in(dm), m.src_len.in(dm), m.first.in(dm), dd, m.dst_off.in(dm), m.dst_cap.in(dm),
                                 (lz4hip::DStreamState*)m.state.in(dm), m.out.in(dm), nb, nc};
-    BlockCall call{OP_DECOMPRESS_STREAM}; call.dstream = &a;
+    BlockCall call{h.op, h.every}; call.dstream = &a;
     if (!sh.run(call, s, m.l)) return false;
     memcpy(h.out + b0, m.out.in(hm), m.out.bytes());
     for (uint32_t t = 0; t < nc; t++) {   // the records, in the caller's terms again
@@ -2108,6 +2119,11 @@ int lz4hip_set_option(const char* name, int value) {
     g_decode_ring = value;
     return LZ4HIP_OK;
   }
+  if (name && strcmp(name, "dstream_inorder") == 0) {   // (the twin alone: lz4hip_decompress_safe_stream_batch never looks at it)
+    if (value != 0 && value != 1) return fail(LZ4HIP_E_ARG, "dstream_inorder must be 0 or 1");
+    g_dstream_inorder = value;
+    return LZ4HIP_OK;
+  }
   if (name && strcmp(name, "decode_lanes") == 0) {
     if (value != 0 && value != 1 && value != 4 && value != 8 && value != 16 && value != 32 && value != 64) return fail(LZ4HIP_E_ARG, "decode_lanes must be 0,1 (ring loop only),4,8,16,32,64");
     g_decode_lanes = value;
@@ -2226,6 +2242,20 @@ int lz4hip_decompress_safe_stream_batch(lz4hip_dstream_state* state, const uint8
   const DStreamHost h{state, src, src_off, src_len, chain_first, dst, dst_off, dst_cap, chain_win_off, chain_win_len, out_len, n_blocks, n_chains};
   // whole streams per device: a stream never leaves its lane group, let alone its device
   return chain_entry(dstream_arg_error(h), n_chains, [&] { return whole_chains(n_chains, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return dstream_host_shard(h, ord, c0, c1, err); }); });
+}
+int lz4hip_decompress_safe_stream_inorder_batch(lz4hip_dstream_state* state, const uint8_t* src, const uint64_t* src_off, const int32_t* src_len,
+                                                const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap,
+                                                const uint64_t* chain_win_off, const uint64_t* chain_win_len, int32_t* out_len, uint32_t n_blocks,
+                                                uint32_t n_chains) {
+  const DStreamHost h{state, src, src_off, src_len, chain_first, dst, dst_off, dst_cap, chain_win_off, chain_win_len, out_len, n_blocks, n_chains,
+                      OP_DECOMPRESS_STREAM_INORDER, g_dstream_inorder.load()};
+  return chain_entry(dstream_arg_error(h), n_chains, [&] { return whole_chains(n_chains, [&](int ord, uint32_t c0, uint32_t c1, std::string* err) { return dstream_host_shard(h, ord, c0, c1, err); }); });
+}
+// LZ4_decoderRingBufferSize (liblz4 1.9.3): 0 for a negative maxBlockSize or one above LZ4_MAX_INPUT_SIZE, else 65536 + 14 + max(maxBlockSize, 16)
+int lz4hip_decoder_ring_buffer_size(int max_block) {
+  if (max_block < 0 || max_block > 0x7E000000) return 0;
+  if (max_block < 16) max_block = 16;
+  return 65536 + 14 + max_block;
 }
 int lz4hip_compress_fast_chain_batch(const uint8_t* src, const uint64_t* chain_src_off, const int32_t* chain_prefix_len, const int32_t* src_len,
                                      const uint32_t* chain_first, uint8_t* dst, const uint64_t* dst_off, const int32_t* dst_cap, int32_t* out_len,

@@ -69,4 +69,42 @@ int launch_decompress_stream(const DStreamArgs& a, uint32_t* q, uint32_t n_cus, 
   return (int)hipGetLastError();
 }
 
+// ---- streams whose slots overlap their history (lz4_decode_inorder.h): the twin ----
+//   decode_stream_inorder_kernel<GL>
+//                        : decode_stream_kernel's shape -- groups of GL lanes draw streams from the queue word with every lane in the
+//                          add, nobody waits for another group, a fence between two blocks.  Per block the walk tests, from the state
+//                          it holds, whether the slot overlaps the piece of the external dictionary the block can reach: such a block
+//                          (or every block, a.every) is decoded by decode_block_inorder, every other one by the instance
+//                          decode_stream_kernel gives it.
+struct DStreamInorderIoDev : DStreamIoDev {
+  __device__ __forceinline__ void in_order(bool) const {}
+};
+
+template <int GL>
+__global__ __launch_bounds__(256, LZ4HIP_DSTREAM_WGS) void decode_stream_inorder_kernel(DStreamInorderArgs a, uint32_t* q) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage_mem[(256 / GL) * GroupDev<GL>::kStreamLds];
+  InOrder<GroupDev<GL>> g;
+  uint8_t* const stage = stage_mem + (threadIdx.x / GL) * GroupDev<GL>::kStreamLds;
+  DStreamInorderIoDev io{{a.s, g.l == 0}};
+  const bool every = a.every != 0u;
+  for (;;) {
+    uint32_t c = atomicAdd(q, g.l == 0 ? 1u : 0u);   // (every lane in the add, no branch in front of the broadcast: as above)
+    c = (uint32_t)__shfl((int)c, 0, GL);
+    if (c >= a.s.n_chains) return;
+    dstream_walk<InOrder<GroupDev<GL>>, DStreamInorderIoDev, 2, true>(g, io, a.s, c, stage, every);
+  }
+}
+
+int launch_decompress_stream_inorder(const DStreamInorderArgs& a, uint32_t* q, uint32_t n_cus, void* stream) {
+  if (a.s.n_chains == 0) return 0;
+  if (!q) return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(q, 0, sizeof(uint32_t), st);
+  if (e != hipSuccess) return (int)e;
+  constexpr uint32_t GL = 8u, per_wg = 256u / GL;
+  const uint32_t want = (a.s.n_chains + per_wg - 1u) / per_wg, most = (n_cus ? n_cus : 256u) * 4u;   // (as launch_decompress_stream)
+  hipLaunchKernelGGL((decode_stream_inorder_kernel<8>), dim3(want < most ? want : most), dim3(256), 0, st, a, q);
+  return (int)hipGetLastError();
+}
+
 }  // namespace lz4hip

@@ -430,6 +430,28 @@ struct GroupDev {
       }
     }
   }
+
+  // ---- the in-order tier (lz4_decode_inorder.h): copies whose source may be bytes this block, or a block before it, has stored ----
+  // Every store issued so far is complete before any load behind this point is issued: no memory operation moves across it in the
+  // compiled code, and the wavefront waits for its outstanding vector memory operations (DStreamIoDev::fence's idiom, between sequences)
+  __device__ __forceinline__ static void order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+  // d[0..len) = s[0..len) in chunks of GL bytes, a byte per lane, forward: a chunk's loads are issued before its stores and the
+  // chunks follow each other in program order (the empty asm statements keep the compiler from interleaving two chunks, which it
+  // may do where ONE lane's bytes do not overlap).  Nothing outside [s, s + len) is read, nothing outside [d, d + len) written.
+  // Byte-forward for s in front of d, or len bytes and more behind it: the copy then loads no byte it stores (the caller cuts every
+  // other copy into such pieces, an order() between them)
+  __device__ __forceinline__ void copy_fwd(uint8_t* d, const uint8_t* s, uint32_t len) const {
+    for (uint32_t i = l; i < len; i += GL) {
+      const uint8_t v = s[i];
+      asm volatile("" ::: "memory");
+      d[i] = v;
+      asm volatile("" ::: "memory");
+    }
+  }
 };
 
 

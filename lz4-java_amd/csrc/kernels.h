@@ -140,6 +140,12 @@ struct DStreamArgs {
 // decode_stream_kernel<8>: decode_chain_kernel's shape -- lane groups of 8 draw streams from the queue word q (one device uint32_t
 // of scratch) and walk each stream's blocks of this launch in order; no group waits for another anywhere.  n_cus = compute units
 int launch_decompress_stream(const DStreamArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
+// The same streams where a block's slot may overlap the history the block can reach (minimal rings; lz4_decode_inorder.h): the call's
+// arrays and records, and `every`: 0 = a block is decoded in order (decode_block_inorder) iff its slot overlaps the piece of the external
+// dictionary it can reach (lz4_decode_stream.h dstream_slot_overlaps), else by the instance decode_stream_kernel gives it; 1 = every block
+struct DStreamInorderArgs { DStreamArgs s; uint32_t every; };
+// decode_stream_inorder_kernel<8>: decode_stream_kernel's shape and queue word
+int launch_decompress_stream_inorder(const DStreamInorderArgs& a, uint32_t* q, uint32_t n_cus, void* stream);
 // LZ4_compress_fast_continue(acceleration 1) over chains of linked blocks (compress_fast.hip, lz4_fast_chain.h).  Chain c is the blocks
 // [chain_first[c], chain_first[c + 1]); their SOURCES lie back to back from src + chain_src_off[c] on, behind chain_prefix_len[c] bytes
 // of history (chain_prefix_len == nullptr: none) that the stream has loaded with LZ4_loadDict; block i owns the slot

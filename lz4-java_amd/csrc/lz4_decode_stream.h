@@ -27,12 +27,30 @@
 #include <stdint.h>
 #include "kernels.h"
 #include "lz4_decode_core.h"
+#include "lz4_decode_inorder.h"
 
 namespace lz4hip {
 
-// PIPE: as chain_walk's
-template <class Grp, class Io, int PIPE = 2>
-LZ4HIP_DEV void dstream_walk(Grp& g, Io& io, const DStreamArgs& a, uint32_t c, uint8_t* stage) {
+// INORDER walks (below): does the slot [doff, doff + cap) of a block intersect the piece of the external dictionary the block can reach --
+// the last min(ext_len, 65535 - min(the prefix the block grows, 65535)) bytes in front of ext_end, from the state AFTER a jump's
+// ext = prefix?  (A growing prefix ends where the slot begins: it never overlaps.  Without a prefix the block is decoded plain and
+// reaches nothing.)
+LZ4HIP_DEV bool dstream_slot_overlaps(const DStreamState& s, bool grows, uint64_t doff, int cap) {
+  if (cap <= 0 || s.prefix_len == 0 || s.ext_len == 0) return false;
+  const uint64_t pre = grows ? (s.prefix_len < 65535u ? s.prefix_len : 65535u) : 0u;
+  const uint64_t reach = s.ext_len < 65535u - pre ? s.ext_len : 65535u - pre;
+  return reach != 0 && doff < s.ext_end && doff + (uint64_t)cap > s.ext_end - reach;
+}
+template <class Grp, bool INORDER> struct dstream_plain { typedef Grp type; };
+template <class Grp> struct dstream_plain<Grp, true> { typedef typename Grp::Plain type; };
+
+// PIPE: as chain_walk's.  INORDER (Grp = InOrder<Base>, lz4_decode_inorder.h; Io has in_order(bool) beside the rest): a block whose slot
+// overlaps the dictionary piece it can reach -- or every block, with `every` -- is decoded by decode_block_inorder; every other block by
+// exactly the decode_block instance it gets without INORDER, on the plain backend
+template <class Grp, class Io, int PIPE = 2, bool INORDER = false>
+LZ4HIP_DEV void dstream_walk(Grp& g, Io& io, const DStreamArgs& a, uint32_t c, uint8_t* stage, bool every = false) {
+  typedef typename dstream_plain<Grp, INORDER>::type Plain;
+  Plain& pg = g;
   uint32_t b1 = a.chain_first[c + 1], b0 = a.chain_first[c];
   if (b1 > a.n_blocks) b1 = a.n_blocks;
   if (b0 > b1) b0 = b1;
@@ -51,13 +69,19 @@ LZ4HIP_DEV void dstream_walk(Grp& g, Io& io, const DStreamArgs& a, uint32_t c, u
     } else {
       const uint8_t* src = a.src + a.src_off[i];
       io.begin_block(d, cap);
+      bool ino = false;
+      if constexpr (INORDER) { ino = every || dstream_slot_overlaps(s, grows, doff, cap); io.in_order(ino); }
       if (s.prefix_len == 0) {
-        r = decode_block<Grp, true, PIPE, false, false, false, true>(g, src, sl, d, cap, stage, nullptr, 0, 0);
+        if constexpr (INORDER) { if (ino) r = decode_block_inorder<Grp, false, true>(g, src, sl, d, cap, stage, nullptr, 0, 0); }
+        if (!ino) r = decode_block<Plain, true, PIPE, false, false, false, true>(pg, src, sl, d, cap, stage, nullptr, 0, 0);
       } else if (grows && (s.prefix_len >= 65535u || s.ext_len == 0)) {
-        r = decode_block<Grp, true, PIPE, false, false, false, true>(g, src, sl, d, cap, stage, nullptr, 0, s.prefix_len >= 65535u ? 65535 : (int)s.prefix_len);
+        const int hist = s.prefix_len >= 65535u ? 65535 : (int)s.prefix_len;
+        if constexpr (INORDER) { if (ino) r = decode_block_inorder<Grp, false, true>(g, src, sl, d, cap, stage, nullptr, 0, hist); }
+        if (!ino) r = decode_block<Plain, true, PIPE, false, false, false, true>(pg, src, sl, d, cap, stage, nullptr, 0, hist);
       } else {   // doubleDict (a prefix of less than 65535 bytes in front of d) or, after a jump, forceExtDict (none)
         const int dl = s.ext_len >= 65536u ? 65536 : (int)s.ext_len;   // (from 64 KB on liblz4 rejects no offset; only the last 65535 bytes are read)
-        r = decode_block<Grp, true, PIPE, false, false, true, true>(g, src, sl, d, cap, stage, a.dst + s.ext_end, dl, grows ? (int)s.prefix_len : 0);
+        if constexpr (INORDER) { if (ino) r = decode_block_inorder<Grp, true, true>(g, src, sl, d, cap, stage, a.dst + s.ext_end, dl, grows ? (int)s.prefix_len : 0); }
+        if (!ino) r = decode_block<Plain, true, PIPE, false, false, true, true>(pg, src, sl, d, cap, stage, a.dst + s.ext_end, dl, grows ? (int)s.prefix_len : 0);
       }
     }
     io.put_out(i, r);

@@ -331,11 +331,14 @@ struct LZ4HIPBatch {
   // [chainFirst[c], chainFirst[c + 1]) of this call, block i is decoded to dest[destOff[i], + maxDestLen[i]), inside the stream's window
   // dest[chainWinOff[c], + chainWinLen[c]).  state[c] is liblz4's LZ4_streamDecode_t as offsets into dest -- all zero: a fresh stream,
   // LZ4_setStreamDecode(dest + p, n): {p + n, n, 0, 0} -- read and written back.  -> liblz4's return value per block,
-  // LZ4HIP_CHAIN_STOPPED behind a stream's first negative one of the call.  The header says when the bytes are liblz4's (the ring rule)
+  // LZ4HIP_CHAIN_STOPPED behind a stream's first negative one of the call.  The header says when the bytes are liblz4's (the ring rule).
+  // inOrder: the twin lz4hip_decompress_safe_stream_inorder_batch -- the same call for streams whose slots overlap the history they can
+  // reach (the ring of decoderRingBufferSize(maxBlock) bytes, rings in step with the writer's); the two may alternate on one stream
   static std::vector<int32_t> decompressSafeStream(std::vector<lz4hip_dstream_state>& state, const bytes& src, const std::vector<uint64_t>& srcOff,
                                                    const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst, bytes& dest,
                                                    const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen,
-                                                   const std::vector<uint64_t>& chainWinOff, const std::vector<uint64_t>& chainWinLen) {
+                                                   const std::vector<uint64_t>& chainWinOff, const std::vector<uint64_t>& chainWinLen,
+                                                   bool inOrder = false) {
     checkBlocks(src, srcOff, srcLen, maxDestLen);
     const size_t n = srcOff.size(), nc = state.size();
     if (destOff.size() != n) throw std::invalid_argument("per-block arrays differ in length");
@@ -355,12 +358,15 @@ struct LZ4HIPBatch {
     int32_t none = 0;
     uint64_t none64 = 0;
     lz4hip_dstream_state none_state{0, 0, 0, 0};
-    status(lz4hip_decompress_safe_stream_batch(nc ? state.data() : &none_state, src.empty() ? one.data() : src.data(), n ? srcOff.data() : &none64,
-                                               n ? srcLen.data() : &none, chainFirst.data(), dest.empty() ? one.data() : dest.data(),
-                                               n ? destOff.data() : &none64, n ? maxDestLen.data() : &none, nc ? chainWinOff.data() : &none64,
-                                               nc ? chainWinLen.data() : &none64, n ? lengths.data() : &none, (uint32_t)n, (uint32_t)nc));
+    // (one call, through lz4hip_decompress_safe_stream_batch(state, ...) or its in-order twin: the two take the same arguments)
+    const auto entry = inOrder ? lz4hip_decompress_safe_stream_inorder_batch : lz4hip_decompress_safe_stream_batch;
+    status(entry(nc ? state.data() : &none_state, src.empty() ? one.data() : src.data(), n ? srcOff.data() : &none64, n ? srcLen.data() : &none,
+                 chainFirst.data(), dest.empty() ? one.data() : dest.data(), n ? destOff.data() : &none64, n ? maxDestLen.data() : &none,
+                 nc ? chainWinOff.data() : &none64, nc ? chainWinLen.data() : &none64, n ? lengths.data() : &none, (uint32_t)n, (uint32_t)nc));
     return lengths;
   }
+  // LZ4_decoderRingBufferSize: the smallest ring a stream of blocks of up to maxBlock bytes is decoded into (inOrder); 0: no such ring
+  static int decoderRingBufferSize(int maxBlock) { return lz4hip_decoder_ring_buffer_size(maxBlock); }
   // LZ4_compress_fast_continue over chains of linked blocks (lz4hip_compress_fast_chain_batch): chain c is the blocks
   // [chainFirst[c], chainFirst[c + 1]), whose sources lie back to back from src[chainSrcOff[c]] on, behind chainPrefixLen[c] bytes of
   // history that lie in front of it in src (an empty vector: no history; the stream loads it with LZ4_loadDict); block i owns the slot
@@ -624,10 +630,11 @@ class CompressStreams {
 // The states of n decode streams: per stream what an LZ4_streamDecode_t of liblz4 holds, as offsets into the one destination its caller
 // decodes into.  Plain host data: nothing on a device, nothing to destroy.  decompress(): the arrays of LZ4HIPBatch::decompressSafeStream,
 // and chain c of the call is the next run of blocks of stream streamId[c] (distinct ids).  Every stream gives, over all the calls that
-// name it, the values ONE LZ4_streamDecode_t gives, however its blocks are cut into calls.
+// name it, the values ONE LZ4_streamDecode_t gives, however its blocks are cut into calls.  inOrder: the set's calls go to the in-order
+// twin (LZ4HIPBatch::decompressSafeStream(.., inOrder)); a call may say otherwise, and the two may alternate on a stream.
 class DecodeStreams {
  public:
-  explicit DecodeStreams(uint32_t n) : state_(n, lz4hip_dstream_state{0, 0, 0, 0}) {
+  explicit DecodeStreams(uint32_t n, bool inOrder = false) : state_(n, lz4hip_dstream_state{0, 0, 0, 0}), inOrder_(inOrder) {
     if (!n) throw std::invalid_argument("a set has at least one stream");
   }
   uint32_t size() const { return (uint32_t)state_.size(); }
@@ -643,6 +650,12 @@ class DecodeStreams {
                                   const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst, bytes& dest,
                                   const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen,
                                   const std::vector<uint64_t>& chainWinOff, const std::vector<uint64_t>& chainWinLen) {
+    return decompress(streamId, src, srcOff, srcLen, chainFirst, dest, destOff, maxDestLen, chainWinOff, chainWinLen, inOrder_);
+  }
+  std::vector<int32_t> decompress(const std::vector<uint32_t>& streamId, const bytes& src, const std::vector<uint64_t>& srcOff,
+                                  const std::vector<int32_t>& srcLen, const std::vector<uint32_t>& chainFirst, bytes& dest,
+                                  const std::vector<uint64_t>& destOff, const std::vector<int32_t>& maxDestLen,
+                                  const std::vector<uint64_t>& chainWinOff, const std::vector<uint64_t>& chainWinLen, bool inOrder) {
     std::vector<lz4hip_dstream_state> st;
     std::vector<uint8_t> seen(state_.size(), 0);
     for (uint32_t c : streamId) {
@@ -650,13 +663,14 @@ class DecodeStreams {
       seen[c] = 1;
       st.push_back(state_[c]);
     }
-    std::vector<int32_t> r = LZ4HIPBatch::decompressSafeStream(st, src, srcOff, srcLen, chainFirst, dest, destOff, maxDestLen, chainWinOff, chainWinLen);
+    std::vector<int32_t> r = LZ4HIPBatch::decompressSafeStream(st, src, srcOff, srcLen, chainFirst, dest, destOff, maxDestLen, chainWinOff, chainWinLen, inOrder);
     for (size_t k = 0; k < streamId.size(); k++) state_[streamId[k]] = st[k];
     return r;
   }
 
  private:
   std::vector<lz4hip_dstream_state> state_;
+  bool inOrder_;
 };
 
 // The states of n HC compress streams whose sources land anywhere: per stream what an LZ4_streamHC_t of liblz4 keeps beside its tables,

@@ -454,6 +454,16 @@ public final class LZ4HIPBatch {
    */
   public static void decompressSafeStream(long[] state, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest,
       long[] destOff, int[] destCap, long[] chainWinOff, long[] chainWinLen, int[] outLen) {
+    decompressSafeStream(state, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff, chainWinLen, outLen, false);
+  }
+
+  /**
+   * The same call; {@code inOrder}: the twin for streams whose slots overlap the history they can reach -- a ring of
+   * {@link #decoderRingBufferSize} bytes, small rings kept in step with the writer's -- where the bytes are the plain byte-forward
+   * definition's (include/lz4hip.h says when those are liblz4's).  The two may alternate on one stream from call to call.
+   */
+  public static void decompressSafeStream(long[] state, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest,
+      long[] destOff, int[] destCap, long[] chainWinOff, long[] chainWinLen, int[] outLen, boolean inOrder) {
     final int n = srcOff.length, nc = chainWinOff.length;
     if (srcLen.length != n || destOff.length != n || destCap.length != n || outLen.length != n) {
       throw new IllegalArgumentException("per-block arrays differ in length");
@@ -493,10 +503,17 @@ public final class LZ4HIPBatch {
         throw new ArrayIndexOutOfBoundsException("history of stream " + c);
       }
     }
-    final int rc = LZ4HIPJNI.LZ4HIP_batchSafeStream(state, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff, chainWinLen, outLen, n, nc);
+    final int rc = inOrder
+        ? LZ4HIPJNI.LZ4HIP_batchSafeStreamInOrder(state, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff, chainWinLen, outLen, n, nc)
+        : LZ4HIPJNI.LZ4HIP_batchSafeStream(state, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff, chainWinLen, outLen, n, nc);
     if (rc != 0) {
       throw new LZ4Exception("liblz4hip status " + rc + ": " + LZ4HIPJNI.lastError());
     }
+  }
+
+  /** {@code LZ4_decoderRingBufferSize}: the smallest ring a stream of blocks of up to maxBlock bytes is decoded into; 0: no such ring. */
+  public static int decoderRingBufferSize(int maxBlock) {
+    return LZ4HIPJNI.LZ4HIP_decoderRingBufferSize(maxBlock);
   }
 
   /**
@@ -506,12 +523,19 @@ public final class LZ4HIPBatch {
    */
   public static final class DecodeStreams {
     private final long[] state;
+    private final boolean inOrder;
 
     public DecodeStreams(int n) {
+      this(n, false);
+    }
+
+    /** inOrder: the set's calls go to the in-order twin ({@link LZ4HIPBatch#decompressSafeStream} with inOrder) unless a call says otherwise. */
+    public DecodeStreams(int n, boolean inOrder) {
       if (n < 1) {
         throw new IllegalArgumentException("a set has at least one stream");
       }
       state = new long[4 * n];
+      this.inOrder = inOrder;
     }
 
     public int size() {
@@ -548,6 +572,12 @@ public final class LZ4HIPBatch {
     /** {@link LZ4HIPBatch#decompressSafeStream} for the streams streamId (distinct ids, one per chain of the call). */
     public void decompress(int[] streamId, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest, long[] destOff,
         int[] destCap, long[] chainWinOff, long[] chainWinLen, int[] outLen) {
+      decompress(streamId, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff, chainWinLen, outLen, inOrder);
+    }
+
+    /** the same through the entry point this call names: the two may alternate on a stream from call to call */
+    public void decompress(int[] streamId, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest, long[] destOff,
+        int[] destCap, long[] chainWinOff, long[] chainWinLen, int[] outLen, boolean inOrder) {
       final long[] st = new long[4 * streamId.length];
       final boolean[] seen = new boolean[size()];
       for (int k = 0; k < streamId.length; k++) {
@@ -557,7 +587,7 @@ public final class LZ4HIPBatch {
         seen[streamId[k]] = true;
         System.arraycopy(state, 4 * streamId[k], st, 4 * k, 4);
       }
-      decompressSafeStream(st, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff, chainWinLen, outLen);
+      decompressSafeStream(st, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff, chainWinLen, outLen, inOrder);
       for (int k = 0; k < streamId.length; k++) {
         System.arraycopy(st, 4 * k, state, 4 * streamId[k], 4);
       }

@@ -117,6 +117,13 @@ enum LZ4HIPJNI {
   static native int LZ4HIP_batchSafeStream(long[] state, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest,
                                            long[] destOff, int[] destCap, long[] chainWinOff, long[] chainWinLen, int[] outLen,
                                            int nBlocks, int nChains);
+  /* The same call for streams whose slots overlap the history they can reach (liblz4's minimal ring, rings in step with the writer's):
+   * LZ4HIP_batchSafeStream's arguments, state and errors; the two may alternate on one stream from call to call. */
+  static native int LZ4HIP_batchSafeStreamInOrder(long[] state, ByteBuffer src, long[] srcOff, int[] srcLen, int[] chainFirst, ByteBuffer dest,
+                                                  long[] destOff, int[] destCap, long[] chainWinOff, long[] chainWinLen, int[] outLen,
+                                                  int nBlocks, int nChains);
+  /* LZ4_decoderRingBufferSize(maxBlock): 65536 + 14 + max(maxBlock, 16); 0 for a negative maxBlock or one above 0x7E000000. */
+  static native int LZ4HIP_decoderRingBufferSize(int maxBlock);
   /* LZ4_compress_HC_continue on streams whose sources land anywhere, DIRECT buffers: stream c is the blocks chainFirst[c] ..
    * chainFirst[c + 1] - 1 of this call, block i is src[srcOff[i], + srcLen[i]) and owns dest[destOff[i], + destCap[i]); state holds five
    * longs per stream (prefixEnd, prefixLen, extEnd, extLen, index: offsets into src), read and written back.  outLen = liblz4's return

@@ -411,20 +411,46 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafeChain(JNI
  * dest[chainWinOff[c], + chainWinLen[c]); state holds four longs per stream -- prefixEnd, prefixLen, extEnd, extLen, offsets into dest --,
  * read and written back; outLen[i] = liblz4's return value (LZ4HIP_CHAIN_STOPPED behind a stream's first negative one of the call).
  * Returns 0 or a negative lz4hip_status; a NULL array or buffer is LZ4HIP_E_ARG (LZ4HIPBatch.java checks the arrays' lengths) */
-JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafeStream(JNIEnv* env, jclass cls, jlongArray state, jobject src, jlongArray srcOff,
-    jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jlongArray chainWinOff, jlongArray chainWinLen,
-    jintArray outLen, jint nBlocks, jint nChains) {
-  (void)cls;
+typedef int (*dstream_entry_t)(lz4hip_dstream_state*, const uint8_t*, const uint64_t*, const int32_t*, const uint32_t*, uint8_t*, const uint64_t*,
+                               const int32_t*, const uint64_t*, const uint64_t*, int32_t*, uint32_t, uint32_t);
+/* the two stream-decode natives: the arrays pinned, `entry` called, everything released */
+static jint batch_safe_stream(JNIEnv* env, dstream_entry_t entry, jlongArray state, jobject src, jlongArray srcOff, jintArray srcLen, jintArray chainFirst,
+                              jobject dest, jlongArray destOff, jintArray destCap, jlongArray chainWinOff, jlongArray chainWinLen, jintArray outLen,
+                              jint nBlocks, jint nChains) {
   if (nBlocks < 0 || nChains < 0) return LZ4HIP_E_ARG;
   batch_args_t b = {NULL, NULL, 9, {{state, LONGS, 0}, {srcOff, LONGS, JNI_ABORT}, {srcLen, INTS, JNI_ABORT}, {chainFirst, INTS, JNI_ABORT},
                                     {destOff, LONGS, JNI_ABORT}, {destCap, INTS, JNI_ABORT}, {chainWinOff, LONGS, JNI_ABORT},
                                     {chainWinLen, LONGS, JNI_ABORT}, {outLen, INTS, 0}}};
   jint rc = batch_pin(env, src, dest, &b);
   if (rc != 0) return rc;
-  rc = lz4hip_decompress_safe_stream_batch((lz4hip_dstream_state*)b.a[0].p, b.src, b.a[1].p, b.a[2].p, (const uint32_t*)b.a[3].p, b.dst, b.a[4].p, b.a[5].p,
-                                           b.a[6].p, b.a[7].p, b.a[8].p, (uint32_t)nBlocks, (uint32_t)nChains);
+  rc = entry((lz4hip_dstream_state*)b.a[0].p, b.src, b.a[1].p, b.a[2].p, (const uint32_t*)b.a[3].p, b.dst, b.a[4].p, b.a[5].p, b.a[6].p, b.a[7].p, b.a[8].p,
+             (uint32_t)nBlocks, (uint32_t)nChains);
   batch_release(env, &b);
   return rc;
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafeStream(JNIEnv* env, jclass cls, jlongArray state, jobject src, jlongArray srcOff,
+    jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jlongArray chainWinOff, jlongArray chainWinLen,
+    jintArray outLen, jint nBlocks, jint nChains) {
+  (void)cls;
+  return batch_safe_stream(env, lz4hip_decompress_safe_stream_batch, state, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff, chainWinLen,
+                           outLen, nBlocks, nChains);
+}
+
+/* The same call for streams whose slots overlap the history they can reach -- liblz4's minimal ring, rings in step with the writer's
+ * (lz4hip_decompress_safe_stream_inorder_batch): the arguments, the state and the errors of LZ4HIP_batchSafeStream, which it may
+ * alternate with on one stream from call to call */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1batchSafeStreamInOrder(JNIEnv* env, jclass cls, jlongArray state, jobject src, jlongArray srcOff,
+    jintArray srcLen, jintArray chainFirst, jobject dest, jlongArray destOff, jintArray destCap, jlongArray chainWinOff, jlongArray chainWinLen,
+    jintArray outLen, jint nBlocks, jint nChains) {
+  (void)cls;
+  return batch_safe_stream(env, lz4hip_decompress_safe_stream_inorder_batch, state, src, srcOff, srcLen, chainFirst, dest, destOff, destCap, chainWinOff,
+                           chainWinLen, outLen, nBlocks, nChains);
+}
+
+/* LZ4_decoderRingBufferSize (lz4hip_decoder_ring_buffer_size): needs no device */
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1decoderRingBufferSize(JNIEnv* env, jclass cls, jint maxBlock) {
+  (void)env; (void)cls;
+  return lz4hip_decoder_ring_buffer_size(maxBlock);
 }
 
 /* LZ4_compress_HC_continue on streams whose sources land anywhere, direct buffers (lz4hip_compress_hc_stream_batch): stream c is the blocks
