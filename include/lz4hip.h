@@ -1003,6 +1003,40 @@ int lz4hip_container_decode(int kind, int flags, const uint8_t* body, uint64_t b
 int lz4hip_container_decode_bound(int kind, int flags, const uint8_t* body, uint64_t body_bytes, uint32_t max_block, uint32_t n_max,
                                   uint32_t* n_blocks, uint64_t* dst_bytes);
 
+/* ---- many containers per call (shuffle blocks, record batches) -----------------------
+ * lz4hip_container_decode reads ONE container per call: a stream, a set of device allocations and about ten launches for it.  Callers
+ * that hold thousands of small containers -- each an LZ4 Frame or an LZ4Block stream of one to a few blocks -- hand them over together:
+ * kind is 0 (LZ4 Frame bodies, starting at the first block's size word) or 1 (LZ4Block streams), one kind per call.  Item c is
+ * bodies[body_off[c], + body_len[c]) with its own max_block[c] and flags[c]; bit 0 of flags[c] means the frame has block checksums,
+ * and items with and without them may be mixed in one call.  n_max is the most blocks any one item delivers (stop reason 7 beyond it).
+ * The contract is the existing call, item by item: info[5c .. 5c + 4], the sizes sizes[item_first[c] .. item_first[c + 1]) and the
+ * bytes dst[item_dst_off[c] .. item_dst_off[c + 1]) equal what lz4hip_container_decode(kind, flags[c], bodies + body_off[c],
+ * body_len[c], max_block[c], n_max, ...) puts into info, sizes[0 .. info[0]) and dst[0 .. info[3]) -- the stop reason, the bytes
+ * consumed, liblz4's code of a failed decode and the readers' order of checks inside a block included.  Delivered blocks lie back to
+ * back, item after item; item_dst_off[n_items] is the total written, and nothing at or behind it is written.  An item that stops for
+ * any reason changes nothing about any other item.
+ *   lz4hip_container_decode_many_bound  needs no device: per item what lz4hip_container_decode_bound returns for it.  A caller sizes
+ *                                       dst by the sum of item_dst_bytes and sizes by the sum of item_blocks; hostile headers size
+ *                                       nothing, per item.
+ *   lz4hip_container_decode_many        host pointers.  item_dst_off and item_first have n_items + 1 entries, info has n_items x 5.
+ * LZ4HIP_E_ARG is said before a device is looked for: a bad kind, a NULL required pointer, n_max or a max_block[c] outside
+ * 1 .. 2^31 - 1, flag bits other than bit 0, dst_cap or sizes_cap below what the bound call reports, items that hold more than 2^31 - 1 - n_items
+ * blocks together (the call's block arrays are indexed with 32 bits: split it).  n_items == 0 is LZ4HIP_OK with
+ * item_dst_off[0] = item_first[0] = 0.  Device memory is sized by what the bodies hold and never by n_max x max_block; the items go
+ * through the host staging in groups of LZ4HIP_HOST_CHUNK_MB MiB of bodies, and a group costs one stream, one set of allocations
+ * and one launch sequence, whatever the number of items.  The call runs on the engine's first device.
+ * Every item is walked by one lane: right for many small items.  An item of thousands of blocks walks slowly there -- hand such a
+ * container to lz4hip_container_decode, whose parallel walk exists for it.
+ * Out of scope: writing many containers per call; device-pointer forms; mixing kinds in one call; sharding items over several
+ * devices; linked-block frames inside the many-call; a parallel walk inside one item.                                          */
+int lz4hip_container_decode_many_bound(int kind, const uint8_t* bodies, const uint64_t* body_off, const uint64_t* body_len,
+                                       const uint32_t* max_block, const uint8_t* flags, uint32_t n_items, uint32_t n_max,
+                                       uint32_t* item_blocks, uint64_t* item_dst_bytes);
+int lz4hip_container_decode_many(int kind, const uint8_t* bodies, const uint64_t* body_off, const uint64_t* body_len,
+                                 const uint32_t* max_block, const uint8_t* flags, uint32_t n_items, uint32_t n_max,
+                                 uint8_t* dst, uint64_t dst_cap, uint64_t* item_dst_off, uint32_t* item_first, int32_t* sizes,
+                                 uint32_t sizes_cap, uint64_t* info);
+
 /* ---- workload helper (not part of the reference API) ------------------------------------------
  * Fills n_blocks slots of `block_len` bytes at dst + i*stride with the SURVEY.md App. F synthetic
  * blocks idx = first_idx + i (deterministic, seed-addressed).  Device pointer, async on stream.

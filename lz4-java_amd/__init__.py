@@ -140,6 +140,9 @@ C_ABI = {
                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "lz4hip_container_decode": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "lz4hip_container_decode_bound": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "lz4hip_container_decode_many_bound": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, _u32p, _u8p, C.c_uint32, C.c_uint32, _u32p, _u64p]),
+    "lz4hip_container_decode_many": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, _u32p, _u8p, C.c_uint32, C.c_uint32, _u8p, C.c_uint64, _u64p, _u32p,
+                                               _i32p, C.c_uint32, _u64p]),
     "lz4hip_gen_blocks_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                         C.c_uint32, C.c_int, C.c_void_p]),
 }
@@ -871,6 +874,44 @@ class LZ4HIPBatch:
         if code >= 1 << 63:
             code -= 1 << 64
         return bytes(dst[:total]), [int(sizes[i]) for i in range(n_ok)], consumed, why, code
+
+    @staticmethod
+    def containerDecodeMany(kind, bodies, maxBlock, nMax, blockChecksum=False):
+        """containerDecode for MANY containers of one kind in one call (lz4hip_container_decode_many): `bodies` is a list of bodies,
+        maxBlock and blockChecksum lists of the same length (or one value for all) -> per item the tuple containerDecode returns.
+        A group of items costs one launch sequence, whatever their number; an item that stops changes nothing about another"""
+        import numpy as np
+        n = len(bodies)
+        mb = list(maxBlock) if hasattr(maxBlock, "__len__") else [maxBlock] * n
+        ck = list(blockChecksum) if hasattr(blockChecksum, "__len__") else [blockChecksum] * n
+        if not (len(mb) == len(ck) == n):
+            raise ValueError("per-item lists differ in length")
+        if n == 0:
+            return []
+        lens = np.fromiter((len(b) for b in bodies), dtype=np.uint64, count=n)
+        offs = np.zeros(n, dtype=np.uint64)
+        np.cumsum(lens[:-1], out=offs[1:])
+        blob = b"".join(bytes(b) if not isinstance(b, (bytes, bytearray)) else b for b in bodies)
+        sp, sk = _ro_ptr(blob if blob else b"\0")
+        mbs, fl = np.asarray(mb, dtype=np.uint32), np.asarray([1 if c else 0 for c in ck], dtype=np.uint8)
+        a = lambda v, t: v.ctypes.data_as(C.POINTER(t))
+        head = (kind, sp, a(offs, C.c_uint64), a(lens, C.c_uint64), a(mbs, C.c_uint32), a(fl, C.c_uint8), n, nMax)
+        nbs, need = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+        _chk(lib().lz4hip_container_decode_many_bound(*head, a(nbs, C.c_uint32), a(need, C.c_uint64)))
+        cap, scap = int(need.sum()), int(nbs.sum())
+        dst = np.empty(max(cap, 1), dtype=np.uint8)
+        sizes, info = np.zeros(max(scap, 1), dtype=np.int32), np.zeros(5 * n, dtype=np.uint64)
+        doff, first = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint32)
+        _chk(lib().lz4hip_container_decode_many(*head, a(dst, C.c_uint8), cap, a(doff, C.c_uint64), a(first, C.c_uint32), a(sizes, C.c_int32), scap,
+                                                a(info, C.c_uint64)))
+        out = []
+        for c in range(n):
+            n_ok, consumed, why, total, code = (int(v) for v in info[5 * c:5 * c + 5])
+            if code >= 1 << 63:
+                code -= 1 << 64
+            assert int(first[c + 1] - first[c]) == n_ok and int(doff[c + 1] - doff[c]) == total
+            out.append((dst[int(doff[c]):int(doff[c + 1])].tobytes(), [int(v) for v in sizes[int(first[c]):int(first[c + 1])]], consumed, why, code))
+        return out
 
     @classmethod
     def decompressSafe(cls, src, srcOff, srcLen, dst, dstOff, dstCap):

@@ -20,6 +20,7 @@
 #include "../../include/lz4hip.h"
 #include "kernels.h"
 #include "host_staging.h"
+#include "container_rules.h"
 
 namespace {
 
@@ -1864,6 +1865,118 @@ int lz4hip_container_decode(int kind, int flags, const uint8_t* body, uint64_t b
   }
   if ((he = hipStreamSynchronize(st)) != hipSuccess) return done(fail(LZ4HIP_E_HIP, "hipStreamSynchronize", he));
   return done(LZ4HIP_OK);
+}
+
+// ---- many containers per call ----
+// what can be said about the items of a many-call without a device -> a message, or nullptr
+static const char* container_many_arg_error(int kind, const uint8_t* bodies, const uint64_t* body_off, const uint64_t* body_len, const uint32_t* max_block,
+                                            const uint8_t* flags, uint32_t n_items, uint32_t n_max) {
+  if (kind != 0 && kind != 1) return "container kind must be 0 (LZ4 Frame blocks) or 1 (LZ4Block blocks)";
+  if (n_items && (!body_off || !body_len || !max_block || !flags)) return kNullArg;
+  for (uint32_t c = 0; c < n_items; c++) if (body_len[c] && !bodies) return kNullArg;
+  if (n_max == 0 || n_max > 0x7FFFFFFFu) return "n_max and max_block must be 1 .. 2^31 - 1";
+  for (uint32_t c = 0; c < n_items; c++) if (max_block[c] == 0 || max_block[c] > 0x7FFFFFFFu) return "n_max and max_block must be 1 .. 2^31 - 1";
+  for (uint32_t c = 0; c < n_items; c++) if (flags[c] & ~1u) return "container flags: only bit 0 (block checksums) is defined";
+  return nullptr;
+}
+// the host pre-walk of item c (container_rules.h, the step the device walk compiles): container_prewalk's numbers
+static lz4hip::container_rules::Walk container_many_prewalk(int kind, const uint8_t* bodies, const uint64_t* body_off, const uint64_t* body_len,
+                                                            const uint32_t* max_block, const uint8_t* flags, uint32_t c, uint32_t n_max) {
+  return lz4hip::container_rules::walk(body_len[c] ? bodies + body_off[c] : nullptr, body_len[c], kind, flags[c], max_block[c], UINT64_MAX, n_max, nullptr);
+}
+int lz4hip_container_decode_many_bound(int kind, const uint8_t* bodies, const uint64_t* body_off, const uint64_t* body_len, const uint32_t* max_block,
+                                       const uint8_t* flags, uint32_t n_items, uint32_t n_max, uint32_t* item_blocks, uint64_t* item_dst_bytes) {
+  if (const char* why = container_many_arg_error(kind, bodies, body_off, body_len, max_block, flags, n_items, n_max)) return fail(LZ4HIP_E_ARG, why);
+  if (n_items && (!item_blocks || !item_dst_bytes)) return fail(LZ4HIP_E_ARG, kNullArg);
+  for (uint32_t c = 0; c < n_items; c++) {
+    const auto w = container_many_prewalk(kind, bodies, body_off, body_len, max_block, flags, c, n_max);
+    item_blocks[c] = w.blocks; item_dst_bytes[c] = w.dst_bytes;
+  }
+  return LZ4HIP_OK;
+}
+// The items of a many-call through the shared staging, a group at a time (chain_shard: an item is its unit, the entries it owns in the
+// batch arrays -- first[] -- are its "blocks"): a group is the items whose bodies fit LZ4HIP_HOST_CHUNK_MB MiB and whose slots fit 512
+// MiB, one item at least.  Item c has nb[c] slots of slot[c] bytes, as lz4hip_container_decode gives that body.  A group costs one
+// upload of the packed bodies and the item arrays, one launch sequence, one copy of the results and one of the delivered bytes, which
+// the device has packed back to back.
+static int container_many_shard(int ord, int kind, const uint8_t* bodies, const uint64_t* body_off, const uint64_t* body_len, const uint32_t* max_block,
+                                const uint8_t* flags, uint32_t n_items, uint32_t n_max, const uint32_t* nb, const uint32_t* slot, const uint32_t* first,
+                                uint8_t* dst, uint64_t* item_dst_off, uint32_t* item_first, int32_t* sizes, uint64_t* info, std::string* err) {
+  auto cost = [&](uint32_t c) { return staging::Cost{al16((size_t)body_len[c]), (size_t)nb[c] * slot[c]}; };
+  uint64_t out_bytes = 0;
+  uint32_t out_blocks = 0;
+  std::vector<uint64_t> so;
+  return chain_shard(ord, first, 0, n_items, err, cost, [&](ShardScope& sh, ChunkSlot& s, const ChainChunk& ck) {
+    const uint32_t c = ck.c, nc = ck.nc, ne = ck.nb;
+    const staging::ContainerManyMeta m(nc, ne);
+    if (!sh.reserve(s, ck.src, true, ck.dst, m.l.total)) return false;
+    if (!sh.ok("staging allocation", s.d_ws.reserve(lz4hip::container_many_ws_bytes(ne, nc) + 256u)) || !sh.ok("staging allocation", s.d_pack.reserve(ck.dst + 64u))) return false;
+    uint8_t* const hs = (uint8_t*)s.h_src.p;
+    void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
+    so.resize(nc);
+    bool any_cks = false;
+    { size_t o = 0, d = 0;
+      for (uint32_t t = 0; t < nc; t++) {
+        so[t] = o; o += al16((size_t)body_len[c + t]);
+        m.body_off.in(hm)[t] = so[t]; m.body_len.in(hm)[t] = body_len[c + t]; m.dst_base.in(hm)[t] = d; d += (uint64_t)nb[c + t] * slot[c + t];
+        m.slot.in(hm)[t] = slot[c + t]; m.max_block.in(hm)[t] = max_block[c + t]; m.flags.in(hm)[t] = flags[c + t];
+        any_cks |= (flags[c + t] & 1u) != 0u;
+      } }
+    staging::rebase_first(first, c, nc, m.first.in(hm));
+    par_blocks(c, ck.j, ck.src, [=, &so](uint32_t t) { if (body_len[t]) memcpy(hs + so[t - c], bodies + body_off[t], (size_t)body_len[t]); });
+    if (!sh.upload(s, ck.src, m.l, s.st)) return false;
+    const lz4hip::ContainerManyItems items{m.body_off.in(dm), m.body_len.in(dm), m.dst_base.in(dm), m.slot.in(dm), m.max_block.in(dm), m.first.in(dm), m.flags.in(dm)};
+    if (!sh.launched(lz4hip::launch_container_read_many(kind, any_cks, (const uint8_t*)s.d_src.p, items, nc, ne, n_max, (uint8_t*)s.d_dst.p, (uint8_t*)s.d_pack.p,
+                                                        m.sizes.in(dm), (unsigned long long*)m.info.in(dm), m.item_first.in(dm),
+                                                        (unsigned long long*)m.item_dst_off.in(dm), s.d_ws.p, s.st)))
+      return false;
+    if (!sh.fetch_results(s, m.l, s.st) || !sh.wait(s.st)) return false;
+    const uint64_t* const ido = m.item_dst_off.in(hm);
+    const uint32_t* const ifi = m.item_first.in(hm);
+    const uint64_t total = ido[nc];
+    if (total > ck.dst || ifi[nc] > ne) { *sh.err = "container read: the device delivered more than the bodies can hold"; sh.rc = LZ4HIP_E_HIP; return false; }
+    if (total) {
+      if (!sh.ok("D2H dst", hipMemcpyAsync(s.h_dst.p, s.d_pack.p, (size_t)total, hipMemcpyDeviceToHost, s.st)) || !sh.wait(s.st)) return false;
+      memcpy(dst + out_bytes, s.h_dst.p, (size_t)total);
+    }
+    memcpy(info + 5u * (size_t)c, m.info.in(hm), 5u * (size_t)nc * sizeof(uint64_t));
+    if (ifi[nc]) memcpy(sizes + out_blocks, m.sizes.in(hm), (size_t)ifi[nc] * sizeof(int32_t));
+    for (uint32_t t = 0; t <= nc; t++) { item_dst_off[c + t] = out_bytes + ido[t]; item_first[c + t] = out_blocks + ifi[t]; }
+    out_bytes += total; out_blocks += ifi[nc];
+    return true;
+  });
+}
+int lz4hip_container_decode_many(int kind, const uint8_t* bodies, const uint64_t* body_off, const uint64_t* body_len, const uint32_t* max_block,
+                                 const uint8_t* flags, uint32_t n_items, uint32_t n_max, uint8_t* dst, uint64_t dst_cap, uint64_t* item_dst_off,
+                                 uint32_t* item_first, int32_t* sizes, uint32_t sizes_cap, uint64_t* info) {
+  if (kind != 0 && kind != 1) return fail(LZ4HIP_E_ARG, "container kind must be 0 (LZ4 Frame blocks) or 1 (LZ4Block blocks)");
+  if (!item_dst_off || !item_first || (n_items && !info) || (dst_cap && !dst) || (sizes_cap && !sizes)) return fail(LZ4HIP_E_ARG, kNullArg);
+  if (const char* why = container_many_arg_error(kind, bodies, body_off, body_len, max_block, flags, n_items, n_max)) return fail(LZ4HIP_E_ARG, why);
+  item_dst_off[0] = 0; item_first[0] = 0;
+  if (n_items == 0) return LZ4HIP_OK;
+  // slots and their number by what each body holds (lz4hip_container_decode): one entry more than the whole blocks present, where the
+  // device walk finds out why the run ends; each slot as big as the item's largest decoded block can be
+  std::vector<uint32_t> nb(n_items), slot(n_items), first((size_t)n_items + 1u);
+  uint64_t need_bytes = 0, need_blocks = 0, entries = 0;
+  for (uint32_t c = 0; c < n_items; c++) {
+    const auto w = container_many_prewalk(kind, bodies, body_off, body_len, max_block, flags, c, n_max);
+    nb[c] = w.blocks; slot[c] = (uint32_t)(((w.slot_max ? w.slot_max : 1u) + 63u) & ~63ull);
+    first[c] = (uint32_t)entries;
+    need_bytes += w.dst_bytes; need_blocks += w.blocks; entries += (uint64_t)w.blocks + 1u;
+    if (entries > 0x7FFFFFFFull) return fail(LZ4HIP_E_ARG, "the items hold more than 2^31 - 1 blocks: split the call");
+  }
+  first[n_items] = (uint32_t)entries;
+  if (dst_cap < need_bytes) return fail(LZ4HIP_E_ARG, "dst_cap is below the sum of item_dst_bytes (lz4hip_container_decode_many_bound)");
+  if (sizes_cap < need_blocks) return fail(LZ4HIP_E_ARG, "sizes_cap is below the sum of item_blocks (lz4hip_container_decode_many_bound)");
+  for (size_t i = 0; i < 5u * (size_t)n_items; i++) info[i] = 0;
+  if (const int rc = need_device()) return rc;
+  int ord;
+  if (ordinal(0, &ord)) return fail(LZ4HIP_E_NO_DEVICE, "no device");
+  DeviceGuard g(ord);
+  std::string err;
+  const int rc = container_many_shard(ord, kind, bodies, body_off, body_len, max_block, flags, n_items, n_max, nb.data(), slot.data(), first.data(), dst,
+                                      item_dst_off, item_first, sizes, info, &err);
+  return rc ? fail(rc, err.c_str()) : (int)LZ4HIP_OK;
 }
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "container_rules.h"
 
 namespace lz4hip {
 
@@ -578,6 +579,167 @@ int launch_container_read(int kind, int block_checksum, const uint8_t* body, uin
   hipLaunchKernelGGL(container_raw_kernel, dim3(n_max), dim3(256), 0, st, kind, body, dst, c, hash_len);
   if (kind == 1 && (e = launch_xxh32(dst, c.dst_off, hash_len, 0x9747b28cu, c.hashes, n_max, stream)) != 0) return e;
   hipLaunchKernelGGL(container_verdict_kernel, dim3(1), dim3(1024), 0, st, kind, block_checksum, c, sizes, info);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// MANY containers per launch sequence (lz4hip_container_decode_many): the bodies of a group of items -- thousands of small LZ4 Frames or
+// LZ4Block streams of one to a few blocks -- lie packed in device memory, and the read path above runs ONCE over the concatenation of
+// all items' blocks.  Item t owns the entries [first[t], first[t + 1]) of the batch arrays: the whole blocks the host's pre-walk found
+// in it plus one, where the device walk finds out why the run ends.  (1) container_walk_many_kernel, a LANE per item: items are
+// independent, the chain of headers inside an item is serial, and the 64 lanes of a wavefront step through their items' headers side
+// by side, so that a wavefront has 64 independent header loads in flight where the one-lane walk has one.  The step is
+// container_rules.h's, the text the host's pre-walk compiles.  (An item of thousands of blocks walks slowly on one lane: such a
+// container is what launch_container_read's parallel walk is for.)  (2) frame block checksums over the stored payloads (hash length 0
+// for the items without them), (3) ONE decode launch for the group, so the device-side route sees the whole batch, (4) the raw copy,
+// (5) LZ4Block checksums over the decoded bytes, (6) container_verdict_many_kernel: container_verdict_kernel's logic per item, and the
+// prefix sums over the items' delivered blocks and bytes; (7) the delivered blocks are packed back to back for one copy to the host.
+// Entries no walk took stay as the memset left them: no payload, no capacity, nothing to hash.
+// ------------------------------------------------------------------------------------------------
+struct ContainerMany {
+  ContainerRead c;                      // the batch arrays over all n_entries entries; c.walk: [0] n_entries (the raw copy's count), [8] the route word
+  int32_t* ck_len;                      // frame block checksums: the stored payload's length, 0 where the item has none
+  int32_t* hash_len;                    // LZ4Block checksums: the decoded length (container_raw_kernel)
+  int32_t* deliver; uint64_t* poff;     // the pack: bytes of a delivered block and where they go
+  uint32_t* walk;                       // per item: blocks walked, stop reason, stop offset (2 words)
+  const uint64_t* body_off; const uint64_t* body_len; const uint64_t* dst_base;   // per item: its body in the packed bodies, its first slot
+  const uint32_t* slot; const uint32_t* max_block; const uint32_t* first; const uint8_t* flags;
+  uint32_t n_items, n_entries, n_max;
+};
+__global__ __launch_bounds__(64) void container_walk_many_kernel(int kind, const uint8_t* bodies, ContainerMany m) {
+  namespace cr = container_rules;
+  const uint32_t it = blockIdx.x * 64u + threadIdx.x;
+  if (it == 0u) m.c.walk[0] = m.n_entries;
+  if (it >= m.n_items) return;
+  const uint64_t base = m.body_off[it], body_bytes = m.body_len[it], slot_bytes = m.slot[it], d0 = m.dst_base[it];
+  const uint8_t* body = bodies + base;
+  const uint32_t flags = m.flags[it], max_block = m.max_block[it];
+  const uint32_t e0 = m.first[it], room = m.first[it + 1u] - e0, n_max = m.n_max < room ? m.n_max : room;
+  uint64_t p = 0;
+  uint32_t k = 0, why = cr::STOP_SLOTS;
+  while (k < n_max) {
+    cr::Block b;
+    const uint32_t r = cr::step(body, body_bytes, p, kind, flags, max_block, slot_bytes, b);
+    if (r != cr::STEP_NEXT) { p = b.next; why = r; break; }
+    // the last entry of a range that holds fewer than n_max blocks takes no block: the pre-walk saw the run end there, and the slots
+    // behind the range are the next item's (a body that changed under the call ends as a cut one)
+    if (k + 1u == room && room <= m.n_max) { why = cr::STOP_TRUNCATED; break; }
+    p = b.next;
+    const uint32_t e = e0 + k;
+    m.c.pay_off[e] = base + b.pay_off; m.c.pay_len[e] = (int32_t)b.pay_len;
+    m.c.src_off[e] = base + b.pay_off; m.c.src_len[e] = b.raw ? 0 : (int32_t)b.pay_len;
+    m.c.dst_off[e] = d0 + (uint64_t)k * slot_bytes; m.c.dst_cap[e] = b.raw ? 0 : (int32_t)b.cap;
+    m.c.meta[e] = kind == 0 ? (int32_t)b.raw : (int32_t)(b.raw | (b.cap << 1));
+    m.c.stored[e] = b.stored;
+    m.c.end_off[e] = p;
+    m.ck_len[e] = (kind == 0 && (flags & 1u)) ? (int32_t)b.pay_len : 0;
+    k++;
+  }
+  if (k == n_max && p == body_bytes) why = cr::STOP_MORE;   // (every slot used and nothing left: not "more follows")
+  uint32_t* w = m.walk + 4u * it;
+  w[0] = k; w[1] = why; w[2] = (uint32_t)p; w[3] = (uint32_t)(p >> 32);
+}
+// per item the first block that fails, in stream order, with the readers' order of checks inside a block (container_verdict_kernel);
+// one workgroup, a run of neighbouring items per thread: verdicts, then the scan of delivered blocks and bytes over the items, then the
+// items' sizes and the pack offsets of their delivered blocks.  item_first, item_dst_off: n_items + 1 entries
+__global__ __launch_bounds__(1024) void container_verdict_many_kernel(int kind, ContainerMany m, int32_t* sizes, unsigned long long* info, uint32_t* item_first,
+                                                                       unsigned long long* item_dst_off) {
+  __shared__ uint64_t part_b[1024];
+  __shared__ uint32_t part_n[1024];
+  const ContainerRead& c = m.c;
+  const uint32_t t = threadIdx.x, n_items = m.n_items;
+  const uint32_t per = (n_items + 1023u) / 1024u;
+  const uint32_t i0 = t * per < n_items ? t * per : n_items, i1 = (i0 + per < n_items) ? i0 + per : n_items;
+  uint64_t sum_b = 0;
+  uint32_t sum_n = 0;
+  for (uint32_t it = i0; it < i1; it++) {
+    const uint32_t e0 = m.first[it], n = m.walk[4u * it];
+    const bool cks = (m.flags[it] & 1u) != 0u;
+    uint32_t nok = n;
+    unsigned long long total = 0;
+    for (uint32_t b = 0; b < n; b++) {
+      const uint32_t e = e0 + b;
+      const bool raw = (c.meta[e] & 1) != 0;
+      bool bad;
+      if (kind == 0) bad = (cks && c.hashes[e] != c.stored[e]) || (!raw && c.out[e] < 0);
+      else bad = (!raw && c.out[e] != c.pay_len[e]) || ((c.hashes[e] & 0x0FFFFFFFu) != c.stored[e]);   // consumed == compressedLen, then the check
+      if (bad) { nok = b; break; }
+      const int32_t sz = kind == 0 ? c.out[e] : (raw ? c.pay_len[e] : (c.meta[e] >> 1));
+      total += (unsigned long long)(sz > 0 ? sz : 0);
+    }
+    uint32_t why = m.walk[4u * it + 1u];
+    long long code = 0;
+    if (nok < n) {
+      const uint32_t e = e0 + nok;
+      if (kind == 0) { if (cks && c.hashes[e] != c.stored[e]) why = CR_BLOCK_CHECKSUM; else { why = CR_DECODE; code = c.out[e]; } }
+      else why = CR_CORRUPT;
+    }
+    unsigned long long* o = info + 5ull * it;
+    o[0] = nok;
+    o[1] = nok < n ? (nok ? c.end_off[e0 + nok - 1u] : 0ull) : ((unsigned long long)m.walk[4u * it + 2u] | ((unsigned long long)m.walk[4u * it + 3u] << 32));
+    o[2] = why;
+    o[3] = total;
+    o[4] = (unsigned long long)code;
+    sum_b += total; sum_n += nok;
+  }
+  part_b[t] = sum_b; part_n[t] = sum_n;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024u; d <<= 1) {   // inclusive scans of the 1024 partial sums
+    const uint64_t vb = t >= d ? part_b[t - d] : 0ull;
+    const uint32_t vn = t >= d ? part_n[t - d] : 0u;
+    __syncthreads();
+    part_b[t] += vb; part_n[t] += vn;
+    __syncthreads();
+  }
+  uint64_t run_b = part_b[t] - sum_b;
+  uint32_t run_n = part_n[t] - sum_n;
+  for (uint32_t it = i0; it < i1; it++) {
+    const uint32_t e0 = m.first[it], nok = (uint32_t)info[5ull * it];
+    item_first[it] = run_n; item_dst_off[it] = run_b;
+    for (uint32_t b = 0; b < nok; b++) {
+      const uint32_t e = e0 + b;
+      const bool raw = (c.meta[e] & 1) != 0;
+      const int32_t sz = kind == 0 ? c.out[e] : (raw ? c.pay_len[e] : (c.meta[e] >> 1));
+      sizes[run_n + b] = sz;
+      m.deliver[e] = sz > 0 ? sz : 0; m.poff[e] = run_b;
+      run_b += (uint64_t)(sz > 0 ? sz : 0);
+    }
+    run_n += nok;
+  }
+  if (t == 1023u) { item_first[n_items] = part_n[1023]; item_dst_off[n_items] = part_b[1023]; }
+}
+size_t container_many_ws_bytes(uint32_t n_entries, uint32_t n_items) {
+  return (size_t)n_entries * (5u * 8u + 10u * 4u) + (16u + 4u * (size_t)n_items) * 4u + 8u;
+}
+int launch_container_read_many(int kind, bool any_block_checksum, const uint8_t* bodies, const ContainerManyItems& items, uint32_t n_items, uint32_t n_entries,
+                               uint32_t n_max, uint8_t* dst, uint8_t* pack, int32_t* sizes, unsigned long long* info, uint32_t* item_first,
+                               unsigned long long* item_dst_off, void* ws, void* stream) {
+  if (n_items == 0 || n_entries == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t ne = n_entries;
+  hipError_t he = hipMemsetAsync(ws, 0, container_many_ws_bytes(ne, n_items), st);   // every entry of every range gets a value
+  if (he != hipSuccess) return (int)he;
+  ContainerMany m;
+  ContainerRead& c = m.c;
+  c.src_off = (uint64_t*)ws; c.dst_off = c.src_off + ne; c.pay_off = c.dst_off + ne; c.end_off = c.pay_off + ne; m.poff = c.end_off + ne;
+  c.src_len = (int32_t*)(m.poff + ne); c.dst_cap = c.src_len + ne; c.out = c.dst_cap + ne; c.pay_len = c.out + ne;
+  c.stored = (uint32_t*)(c.pay_len + ne); c.hashes = c.stored + ne; c.meta = (int32_t*)(c.hashes + ne);
+  m.hash_len = c.meta + ne; m.ck_len = m.hash_len + ne; m.deliver = m.ck_len + ne;
+  c.walk = (uint32_t*)(m.deliver + ne);
+  m.walk = c.walk + 16;
+  m.body_off = items.body_off; m.body_len = items.body_len; m.dst_base = items.dst_base; m.slot = items.slot; m.max_block = items.max_block;
+  m.first = items.first; m.flags = items.flags;
+  m.n_items = n_items; m.n_entries = ne; m.n_max = n_max;
+  hipLaunchKernelGGL(container_walk_many_kernel, dim3((n_items + 63u) / 64u), dim3(64), 0, st, kind, bodies, m);
+  int e;
+  if (kind == 0 && any_block_checksum && (e = launch_xxh32(bodies, c.pay_off, m.ck_len, 0u, c.hashes, ne, stream)) != 0) return e;
+  BatchArgs a{bodies, c.src_off, c.src_len, dst, c.dst_off, c.dst_cap, c.out, ne};
+  if ((e = launch_decompress(a, kind == 0, 0, -1, -1, 0, stream, c.walk + 8)) != 0) return e;
+  hipLaunchKernelGGL(container_raw_kernel, dim3(ne), dim3(256), 0, st, kind, bodies, dst, c, m.hash_len);   // (c.walk[0] = ne: every entry is looked at)
+  if (kind == 1 && (e = launch_xxh32(dst, c.dst_off, m.hash_len, 0x9747b28cu, c.hashes, ne, stream)) != 0) return e;
+  hipLaunchKernelGGL(container_verdict_many_kernel, dim3(1), dim3(1024), 0, st, kind, m, sizes, info, item_first, item_dst_off);
+  BatchArgs pk{nullptr, nullptr, nullptr, dst, c.dst_off, nullptr, m.deliver, ne};
+  hipLaunchKernelGGL(pack_copy_kernel, dim3(ne), dim3(256), 0, st, pk, (const uint64_t*)m.poff, pack);
   return (int)hipGetLastError();
 }
 

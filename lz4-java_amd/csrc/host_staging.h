@@ -91,6 +91,15 @@ struct HashMeta {   // the hashes (xxh_shard): T = uint32_t / uint64_t
   Region<uint64_t> off; Region<int32_t> len; Region<T> hash;
   explicit HashMeta(size_t nb) : off(l.input<uint64_t>(nb)), len(l.input<int32_t>(nb)), hash(l.result<T>(nb)) {}
 };
+struct ContainerManyMeta {   // many containers per call (container_many_shard): nc items that own ne entries of the batch arrays
+  MetaLayout l;
+  Region<uint64_t> body_off, body_len, dst_base; Region<uint32_t> slot, max_block, first; Region<uint8_t> flags;
+  Region<uint64_t> info, item_dst_off; Region<uint32_t> item_first; Region<int32_t> sizes;
+  ContainerManyMeta(size_t nc, size_t ne)
+      : body_off(l.input<uint64_t>(nc)), body_len(l.input<uint64_t>(nc)), dst_base(l.input<uint64_t>(nc)), slot(l.input<uint32_t>(nc)),
+        max_block(l.input<uint32_t>(nc)), first(l.input<uint32_t>(nc + 1)), flags(l.input<uint8_t>(nc)),
+        info(l.result<uint64_t>(5 * nc)), item_dst_off(l.result<uint64_t>(nc + 1)), item_first(l.result<uint32_t>(nc + 1)), sizes(l.result<int32_t>(ne)) {}
+};
 
 // The scratch of the HC chain compressor's layout kernel (compress_hc.hip) for n_blocks blocks in n_chains chains whose regions end at or
 // before `span`, with build segments of `seg` positions (4096 .. 2^30): byte offsets of its arrays, 8-byte ones first.  max_items: a

@@ -88,6 +88,20 @@ int launch_container_blocks(int kind, int block_checksum, int hc_level, const ui
 size_t container_read_ws_bytes(uint32_t n_max);
 int launch_container_read(int kind, int block_checksum, const uint8_t* body, uint64_t body_bytes, uint32_t max_block, uint8_t* dst, uint64_t slot_bytes,
                           uint32_t n_max, int32_t* sizes, unsigned long long* info, void* ws, void* stream);
+// The read path over MANY containers of one kind at once (container.hip): item t's body is bodies[body_off[t], + body_len[t]) with its
+// own max_block[t] and flags[t] (bit 0: block checksums); it owns the entries [first[t], first[t + 1]) of the batch arrays -- the whole
+// blocks the host's pre-walk found in it plus one -- and the slots dst + dst_base[t] + k * slot[t].  Per item info[5t .. 5t + 4] as
+// above; the delivered blocks' sizes lie back to back in sizes[item_first[t] ..) and their bytes in pack[item_dst_off[t] ..), item after
+// item (item_first, item_dst_off: n_items + 1 entries, the last one the total).  n_max: the most blocks one item delivers; n_entries =
+// first[n_items]; ws = container_many_ws_bytes(n_entries, n_items) bytes of device scratch; any_block_checksum: some flags[t] has bit 0
+struct ContainerManyItems {
+  const uint64_t* body_off; const uint64_t* body_len; const uint64_t* dst_base; const uint32_t* slot; const uint32_t* max_block; const uint32_t* first;
+  const uint8_t* flags;
+};
+size_t container_many_ws_bytes(uint32_t n_entries, uint32_t n_items);
+int launch_container_read_many(int kind, bool any_block_checksum, const uint8_t* bodies, const ContainerManyItems& items, uint32_t n_items, uint32_t n_entries,
+                               uint32_t n_max, uint8_t* dst, uint8_t* pack, int32_t* sizes, unsigned long long* info, uint32_t* item_first,
+                               unsigned long long* item_dst_off, void* ws, void* stream);
 // lanes_per_block: lanes of a wavefront that share one block in the decoder (4..64); 0 = default
 // pipe: 1 = pipelined interior loop (lz4_decode_core.h PIPE), 0 = plain, -1 = default for the batch size
 // stage: 1 = the plain interior loop writes through LDS staging (whole-line output), 0 / -1 = off

@@ -17,6 +17,7 @@
 #include <functional>
 #include <istream>
 #include <ostream>
+#include <sstream>
 #include "lz4hip.hpp"
 
 namespace net { namespace jpountz { namespace lz4 {
@@ -123,6 +124,36 @@ struct BatchEngine {
     r.sizes.resize((size_t)info[0]);
     r.consumed = info[1]; r.why = (int)info[2]; r.decoded.resize((size_t)info[3]); r.code = (int64_t)info[4];
     return r;
+  }
+  // containerDecode for MANY containers of one kind in ONE call (lz4hip_container_decode_many): item c is bodies[c] with its own
+  // maxBlock[c] and blockChecksum[c] -> per item what containerDecode returns.  A group of items costs one launch sequence, whatever
+  // their number; an item that stops changes nothing about another
+  std::vector<ContainerRun> containerDecodeMany(int kind, const std::vector<bytes>& bodies, const std::vector<uint32_t>& maxBlock, uint32_t nMax,
+                                                const std::vector<uint8_t>& blockChecksum) const {
+    const size_t n = bodies.size();
+    if (maxBlock.size() != n || blockChecksum.size() != n) throw std::invalid_argument("per-item lists differ in length");
+    std::vector<ContainerRun> out(n);
+    if (n == 0) return out;
+    std::vector<uint64_t> off(n), len(n), need(n), dstOff(n + 1), info(5 * n);
+    std::vector<uint32_t> nb(n), first(n + 1);
+    std::vector<uint8_t> flags(n);
+    bytes blob;
+    for (size_t c = 0; c < n; c++) { off[c] = blob.size(); len[c] = bodies[c].size(); flags[c] = blockChecksum[c] ? 1 : 0; blob.insert(blob.end(), bodies[c].begin(), bodies[c].end()); }
+    blob.push_back(0);
+    chk(lz4hip_container_decode_many_bound(kind, blob.data(), off.data(), len.data(), maxBlock.data(), flags.data(), (uint32_t)n, nMax, nb.data(), need.data()));
+    uint64_t cap = 0, scap = 0;
+    for (size_t c = 0; c < n; c++) { cap += need[c]; scap += nb[c]; }
+    bytes dst((size_t)cap + 1u);
+    std::vector<int32_t> sizes((size_t)scap + 1u);
+    chk(lz4hip_container_decode_many(kind, blob.data(), off.data(), len.data(), maxBlock.data(), flags.data(), (uint32_t)n, nMax, dst.data(), cap, dstOff.data(),
+                                     first.data(), sizes.data(), (uint32_t)scap, info.data()));
+    for (size_t c = 0; c < n; c++) {
+      ContainerRun& r = out[c];
+      r.decoded.assign(dst.begin() + (ptrdiff_t)dstOff[c], dst.begin() + (ptrdiff_t)dstOff[c + 1]);
+      r.sizes.assign(sizes.begin() + first[c], sizes.begin() + first[c + 1]);
+      r.consumed = info[5 * c + 1]; r.why = (int)info[5 * c + 2]; r.code = (int64_t)info[5 * c + 4];
+    }
+    return out;
   }
   uint32_t xxh32_one(const uint8_t* buf, size_t n, uint32_t seed) const {
     static const uint8_t dummy = 0;
@@ -425,6 +456,12 @@ class LZ4FrameOutputStream {
   std::unique_ptr<CompressStreams> streams_;   // ... made at the first batch
 };
 
+namespace detail {
+// a reader's next device request (readFrames / readBlockStreams hand the requests of many readers to ONE containerDecodeMany)
+struct DeviceRequest { bytes chunk; uint32_t maxBlock = 0; bool blockChecksum = false, atEof = false, set = false; };
+struct ManyDriver;
+}  // namespace detail
+
 class LZ4FrameInputStream {
  public:
   // linkedBlocks = true (not in the reference, whose reader refuses such frames; the default refuses them too): a frame without
@@ -505,12 +542,12 @@ class LZ4FrameInputStream {
   }
   bool bit(int b) const { return (flgBits_ >> b) & 1; }
   // behind the end mark (LZ4FrameInputStream.java:264-276): content checksum, content size
-  void endMark() {
+  void endMark(const uint32_t* contentHash = nullptr) {   // contentHash: the content's XXH32 where the caller has it
     try {
       if (bit(frame::CONTENT_CHECKSUM)) {
         uint8_t w4[4];
         readFully(w4, 4);
-        if (detail::getLE32(w4) != (uint32_t)content().getValue()) throw IOException("Content checksum mismatch");
+        if (detail::getLE32(w4) != (contentHash ? *contentHash : (uint32_t)content().getValue())) throw IOException("Content checksum mismatch");
       }
       if (bit(frame::CONTENT_SIZE) && expectedContentSize_ != totalContentSize_) throw IOException("Size check mismatch");
     } catch (const IOException& e) { pending_ = e.what(); return; }
@@ -520,19 +557,33 @@ class LZ4FrameInputStream {
   // blocks and a stop reason come back; what the device did not consume is read again.  Same checks in the same order, same messages;
   // a defect in block k surfaces after the bytes of the blocks before it
   void readBlocksDevice() {
-    const bool bc = bit(frame::BLOCK_CHECKSUM);
+    detail::DeviceRequest q;
+    deviceRequest(q);
+    deviceResult(q, e_.containerDecode(0, q.chunk.data(), q.chunk.size(), q.maxBlock, (uint32_t)batch_, q.blockChecksum), nullptr);
+  }
+  // the first half: the next chunk of the frame's body as containerDecode's arguments
+  void deviceRequest(detail::DeviceRequest& q) {
     const size_t want = batch_ * ((size_t)maxBlockSize_ + 8u) + 4u;
-    const bytes chunk = r_.readChunk(want);
-    const bool atEof = chunk.size() < want;
-    const BatchEngine::ContainerRun run = e_.containerDecode(0, chunk.data(), chunk.size(), (uint32_t)maxBlockSize_, (uint32_t)batch_, bc);
+    q.chunk = r_.readChunk(want);
+    q.atEof = q.chunk.size() < want;
+    q.maxBlock = (uint32_t)maxBlockSize_; q.blockChecksum = bit(frame::BLOCK_CHECKSUM); q.set = true;
+  }
+  // the second half: what containerDecode returned for the request.  whole (readFrames): a frame whose content checksum is due and whose
+  // WHOLE content is this result does not hash it; *whole = true, and the caller ends the frame with the value of its one xxh32 batch
+  // (finishWhole)
+  void deviceResult(const detail::DeviceRequest& q, const BatchEngine::ContainerRun& run, bool* whole) {
+    const bytes& chunk = q.chunk;
+    const bool atEof = q.atEof;
     const uint8_t* rest = chunk.data() + run.consumed;
     const size_t nrest = chunk.size() - (size_t)run.consumed;
+    const bool batched = whole && bit(frame::CONTENT_CHECKSUM) && run.why == BatchEngine::CR_END && totalContentSize_ == 0;
     if (!run.decoded.empty()) {
       ready_.insert(ready_.end(), run.decoded.begin(), run.decoded.end());
       totalContentSize_ += (int64_t)run.decoded.size();
-      if (bit(frame::CONTENT_CHECKSUM)) content().update(run.decoded.data(), run.decoded.size());  // one update per batch
+      if (bit(frame::CONTENT_CHECKSUM) && !batched) content().update(run.decoded.data(), run.decoded.size());  // one update per batch
     }
     r_.unread(rest, nrest);
+    if (batched) { *whole = true; return; }
     uint8_t w4[4];
     switch (run.why) {
       case BatchEngine::CR_END: endMark(); break;
@@ -548,13 +599,18 @@ class LZ4FrameInputStream {
         break;   // (else: the next call goes on from the bytes handed back)
       default: break;
     }
+    if (single_ && frameFinished_) r_.giveBack();
   }
-  void readBlocks() {  // readBlock (:258-322) for up to batch_ blocks
+  void finishWhole(uint32_t contentHash) {
+    endMark(&contentHash);
+    if (single_ && frameFinished_) r_.giveBack();
+  }
+  // defer: a device request is not run but put there, for the caller to run with other readers' (readFrames)
+  void readBlocks(detail::DeviceRequest* defer = nullptr) {  // readBlock (:258-322) for up to batch_ blocks
     // (the device path takes a whole chunk from the stream: with readSingleFrame the caller reads on behind the frame, so it needs a
     // stream that can take the surplus back; any other gets the host walk, which consumes exactly the frame)
     if (!linked_ && !e_.hostWalk && (!single_ || r_.seekable())) {
-      readBlocksDevice();
-      if (single_ && frameFinished_) r_.giveBack();
+      if (defer) deviceRequest(*defer); else readBlocksDevice();
       return;
     }
     struct Blk { bool compressed; bytes payload; uint32_t stored; };
@@ -643,18 +699,21 @@ class LZ4FrameInputStream {
     if (!exc.empty()) { pending_ = exc; return; }
     if (endMark) this->endMark();
   }
-  bool fill() {  // false at the end of the stream
+  bool fill() { return fillOr(nullptr) == 1; }   // false at the end of the stream
+  int fillOr(detail::DeviceRequest* defer) {     // 1: bytes are ready; 0: the end of the stream; 2: a device request waits in *defer
     while (ready_.empty()) {
       if (!pending_.empty()) { const std::string m = pending_; pending_.clear(); throw IOException(m); }
       if (!headerRead_ || frameFinished_) {
-        if (headerRead_ && frameFinished_ && single_ && inFrame_) return false;
-        if (!nextFrameInfo()) return false;
+        if (headerRead_ && frameFinished_ && single_ && inFrame_) return 0;
+        if (!nextFrameInfo()) return 0;
         if (frameFinished_) continue;  // only skippable frames so far
       }
-      readBlocks();
+      readBlocks(defer);
+      if (defer && defer->set) return 2;
     }
-    return true;
+    return 1;
   }
+  friend struct detail::ManyDriver;
   detail::PushbackReader r_;
   BatchEngine e_;
   bool single_;
@@ -796,15 +855,27 @@ class LZ4BlockInputStream {
   // path (the stream does not start with a header; a block bigger than the first header announced; a header whose compressedLen
   // exceeds the chunk although more input follows -- asking the device again with the same bytes would never end)
   bool refillDevice() {
+    detail::DeviceRequest q;
+    return deviceRequest(q) && deviceResult(q, e_.containerDecode(1, q.chunk.data(), q.chunk.size(), q.maxBlock, (uint32_t)batch_, false));
+  }
+  // the first half: the next chunk of the stream as containerDecode's arguments; false: this run is for the host path
+  bool deviceRequest(detail::DeviceRequest& q) {
     uint8_t head[blockstream::HEADER_LENGTH];
     const size_t hgot = r_.readUpTo(head, sizeof head);
     r_.unread(head, hgot);
     if (hgot < sizeof head || memcmp(head, blockstream::magic(), 8) != 0) return false;
-    const uint32_t maxBlock = 1u << (blockstream::COMPRESSION_LEVEL_BASE + (head[8] & 0x0F));
-    const size_t want = batch_ * ((size_t)maxBlock + sizeof head) + sizeof head;
-    const bytes chunk = r_.readChunk(want);
-    const bool atEof = chunk.size() < want;
-    const BatchEngine::ContainerRun run = e_.containerDecode(1, chunk.data(), chunk.size(), maxBlock, (uint32_t)batch_, false);
+    q.maxBlock = 1u << (blockstream::COMPRESSION_LEVEL_BASE + (head[8] & 0x0F));
+    const size_t want = batch_ * ((size_t)q.maxBlock + sizeof head) + sizeof head;
+    q.chunk = r_.readChunk(want);
+    q.atEof = q.chunk.size() < want;
+    q.set = true;
+    return true;
+  }
+  // the second half: what containerDecode returned for the request; false: this run is for the host path
+  bool deviceResult(const detail::DeviceRequest& q, const BatchEngine::ContainerRun& run) {
+    const bytes& chunk = q.chunk;
+    const bool atEof = q.atEof;
+    const size_t headLen = blockstream::HEADER_LENGTH;
     if (run.why == BatchEngine::CR_BLOCK_TOO_BIG ||
         (run.consumed == 0 && run.decoded.empty() && (run.why == BatchEngine::CR_TRUNCATED || run.why == BatchEngine::CR_MORE) && !atEof)) {
       r_.unread(chunk.data(), chunk.size());
@@ -818,18 +889,24 @@ class LZ4BlockInputStream {
     else if ((run.why == BatchEngine::CR_TRUNCATED || run.why == BatchEngine::CR_MORE) && atEof) {
       bytes drop(nrest);
       (void)r_.readUpTo(drop.data(), nrest);
-      if (nrest < sizeof head && !stopOnEmpty_) finished_ = true;   // (:192-199: the stream may end at -- or inside -- a header)
+      if (nrest < headLen && !stopOnEmpty_) finished_ = true;   // (:192-199: the stream may end at -- or inside -- a header)
       else { pending_ = "Stream ended prematurely"; pendingEof_ = true; }
     }
     return true;
   }
-  void refill() {  // LZ4BlockInputStream.java:191-264, for up to batch_ blocks
+  // defer: a device request is not run but put there, for the caller to run with other readers' (readBlockStreams: deviceDeliver)
+  void refill(detail::DeviceRequest* defer = nullptr) {  // LZ4BlockInputStream.java:191-264, for up to batch_ blocks
     // (stopOnEmptyBlock: the caller reads on behind the empty block, so the device path -- which takes whole chunks from the stream --
     // needs one that can take the surplus back)
-    if (!checksum_ && !e_.hostWalk && (!stopOnEmpty_ || r_.seekable()) && refillDevice()) {
-      if (stopOnEmpty_ && finished_) r_.giveBack();
-      return;
+    if (!checksum_ && !e_.hostWalk && (!stopOnEmpty_ || r_.seekable())) {
+      if (defer) { if (deviceRequest(*defer)) return; }
+      else if (refillDevice()) { deviceDone(); return; }
     }
+    refillHost();
+  }
+  void deviceDone() { if (stopOnEmpty_ && finished_) r_.giveBack(); }
+  void deviceDeliver(const detail::DeviceRequest& q, const BatchEngine::ContainerRun& run) { if (deviceResult(q, run)) deviceDone(); else refillHost(); }
+  void refillHost() {   // the headers walked and the checksums compared on the host around the batch launches
     struct Blk { int method; bytes payload; int32_t olen; uint32_t check; };
     std::vector<Blk> blocks;
     std::string exc;
@@ -905,7 +982,8 @@ class LZ4BlockInputStream {
     if (!exc.empty()) { pending_ = exc; pendingEof_ = eof; }
     else if (fin) finished_ = true;
   }
-  bool fill() {
+  bool fill() { return fillOr(nullptr) == 1; }
+  int fillOr(detail::DeviceRequest* defer) {     // 1: bytes are ready; 0: the end of the stream; 2: a device request waits in *defer
     while (ready_.empty()) {
       if (!pending_.empty()) {
         const std::string m = pending_;
@@ -913,11 +991,13 @@ class LZ4BlockInputStream {
         if (pendingEof_) throw EOFException(m);
         throw IOException(m);
       }
-      if (finished_) return false;
-      refill();
+      if (finished_) return 0;
+      refill(defer);
+      if (defer && defer->set) return 2;
     }
-    return true;
+    return 1;
   }
+  friend struct detail::ManyDriver;
   detail::PushbackReader r_;
   BatchEngine e_;
   bool stopOnEmpty_;
@@ -927,6 +1007,110 @@ class LZ4BlockInputStream {
   std::string pending_;
   bool pendingEof_ = false, finished_ = false;
 };
+
+// =====================================================================================================
+// many containers at once
+// =====================================================================================================
+// what a reader delivered of one item before it stopped, and the exception it raised: its class ("" = none, "IOException",
+// "EOFException", or "exception" for anything else) and message
+struct ReadResult { bytes data; std::string errorClass, error; };
+namespace detail {
+// The readers -- one per item, each the sequential reader of its item -- driven in ROUNDS: in a round every unfinished reader parses what
+// lies in front of its next blocks (its own code) and hands over the rest of its current body as a device request; the requests of all
+// readers go into ONE containerDecodeMany, and every reader takes its result as if it had made the call itself.  Content checksums: the
+// frames whose content arrived whole in a round are hashed in ONE xxh32 batch behind it; a frame that takes several rounds keeps its
+// streaming hash.
+struct ManyDriver {
+  static void deliver(LZ4FrameInputStream& r, const DeviceRequest& q, const BatchEngine::ContainerRun& run, bool* whole) { r.deviceResult(q, run, whole); }
+  static void deliver(LZ4BlockInputStream& r, const DeviceRequest& q, const BatchEngine::ContainerRun& run, bool*) { r.deviceDeliver(q, run); }
+  static void finishWhole(LZ4FrameInputStream& r, uint32_t h) { r.finishWhole(h); }
+  static void finishWhole(LZ4BlockInputStream&, uint32_t) {}
+  template <class F>
+  static void guarded(ReadResult& res, bool& live, F f) {
+    try { f(); }
+    catch (const EOFException& e) { res.errorClass = "EOFException"; res.error = e.what(); live = false; }
+    catch (const IOException& e) { res.errorClass = "IOException"; res.error = e.what(); live = false; }
+    catch (const LZ4Exception&) { throw; }   // (the library failed -- no device, no memory: that is the call's failure, not an item's result)
+    catch (const std::exception& e) { res.errorClass = "exception"; res.error = e.what(); live = false; }
+  }
+  template <class Reader>
+  static std::vector<ReadResult> run(std::deque<Reader>& readers, const BatchEngine& e, int kind, uint32_t nMax) {
+    const size_t n = readers.size();
+    std::vector<ReadResult> out(n);
+    std::vector<char> liveFlag(n, 1);
+    for (;;) {
+      std::vector<size_t> who;
+      std::vector<DeviceRequest> reqs;
+      for (size_t i = 0; i < n; i++) {
+        if (!liveFlag[i]) continue;
+        bool live = true, waits = false;
+        DeviceRequest q;
+        guarded(out[i], live, [&] {
+          for (;;) {
+            const int more = readers[i].fillOr(&q);
+            if (more == 2) { waits = true; return; }
+            if (more == 0) { live = false; return; }
+            out[i].data.insert(out[i].data.end(), readers[i].ready_.begin(), readers[i].ready_.end());
+            readers[i].ready_.clear();
+          }
+        });
+        liveFlag[i] = live;
+        if (live && waits) { who.push_back(i); reqs.push_back(std::move(q)); }
+      }
+      if (who.empty()) break;
+      std::vector<bytes> bodies(who.size());
+      std::vector<uint32_t> maxBlock(who.size());
+      std::vector<uint8_t> cks(who.size());
+      for (size_t t = 0; t < who.size(); t++) { bodies[t] = reqs[t].chunk; maxBlock[t] = reqs[t].maxBlock; cks[t] = reqs[t].blockChecksum ? 1 : 0; }
+      const std::vector<BatchEngine::ContainerRun> runs = e.containerDecodeMany(kind, bodies, maxBlock, nMax, cks);
+      std::vector<size_t> wholeWho;
+      bytes blob;
+      std::vector<uint64_t> off;
+      std::vector<int32_t> len;
+      for (size_t t = 0; t < who.size(); t++) {
+        const size_t i = who[t];
+        bool live = true, whole = false;
+        guarded(out[i], live, [&] { deliver(readers[i], reqs[t], runs[t], &whole); });
+        liveFlag[i] = live;
+        if (live && whole) {
+          wholeWho.push_back(i); off.push_back(blob.size()); len.push_back((int32_t)runs[t].decoded.size());
+          blob.insert(blob.end(), runs[t].decoded.begin(), runs[t].decoded.end());
+        }
+      }
+      if (!wholeWho.empty()) {   // one hash launch for the contents that arrived whole in this round
+        blob.push_back(0);
+        const std::vector<uint32_t> hashes = e.xxh32(blob.data(), off, len, 0);
+        for (size_t t = 0; t < wholeWho.size(); t++) finishWhole(readers[wholeWho[t]], hashes[t]);
+      }
+    }
+    return out;
+  }
+};
+}  // namespace detail
+
+// Many LZ4 Frame streams read together: per item the bytes LZ4FrameInputStream delivers of it before it stops, and the exception it raises
+// (same class, same message).  Every round of block reading is one containerDecodeMany over all unfinished items; concatenated and
+// skippable frames, end marks, content size and content checksum are the reader's own code.  Frames with linked blocks are not part of
+// the many-call: the reader refuses them, as it does alone.
+inline std::vector<ReadResult> readFrames(const std::vector<bytes>& items, BatchEngine engine = BatchEngine(), size_t batchBlocks = 64) {
+  std::deque<std::istringstream> ins;
+  std::deque<LZ4FrameInputStream> readers;
+  for (const bytes& it : items) {
+    ins.emplace_back(std::string(it.begin(), it.end()));
+    readers.emplace_back(ins.back(), false, engine, batchBlocks);
+  }
+  return detail::ManyDriver::run(readers, engine, 0, (uint32_t)(batchBlocks ? batchBlocks : 1));
+}
+// readFrames' twin over LZ4BlockInputStream
+inline std::vector<ReadResult> readBlockStreams(const std::vector<bytes>& items, BatchEngine engine = BatchEngine(), size_t batchBlocks = 256) {
+  std::deque<std::istringstream> ins;
+  std::deque<LZ4BlockInputStream> readers;
+  for (const bytes& it : items) {
+    ins.emplace_back(std::string(it.begin(), it.end()));
+    readers.emplace_back(ins.back(), true, engine, batchBlocks);
+  }
+  return detail::ManyDriver::run(readers, engine, 1, (uint32_t)(batchBlocks ? batchBlocks : 1));
+}
 
 // =====================================================================================================
 // length-prefixed blocks

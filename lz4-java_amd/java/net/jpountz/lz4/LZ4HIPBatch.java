@@ -891,4 +891,66 @@ public final class LZ4HIPBatch {
       throw new LZ4Exception("liblz4hip status " + r + ": " + LZ4HIPJNI.lastError());
     }
   }
+
+  /**
+   * What a {@link #containerDecodeMany} call over the same items can need: {@code itemBlocks[c]} = whole blocks of the first
+   * {@code nMax} that item c holds, {@code itemDstBytes[c]} = the most their decoded forms can need -- per item what
+   * {@link #containerDecodeBound} says of it.  No device work.  Size {@code dest} by the sum of {@code itemDstBytes} and
+   * {@code sizes} by the sum of {@code itemBlocks}.
+   */
+  public static void containerDecodeManyBound(int kind, ByteBuffer bodies, long[] bodyOff, long[] bodyLen, int[] maxBlock,
+                                              boolean[] blockChecksum, int nMax, int[] itemBlocks, long[] itemDstBytes) {
+    final int n = bodyOff.length;
+    if (!bodies.isDirect()) {
+      throw new IllegalArgumentException("LZ4HIPBatch needs direct ByteBuffers");
+    }
+    if (bodyLen.length != n || maxBlock.length != n || blockChecksum.length != n || itemBlocks.length < n || itemDstBytes.length < n) {
+      throw new ArrayIndexOutOfBoundsException();
+    }
+    final int r = LZ4HIPJNI.LZ4HIP_containerDecodeManyBound(kind, bodies, bodyOff, bodyLen, maxBlock, manyFlags(bodies, bodyOff, bodyLen,
+        blockChecksum), n, nMax, itemBlocks, itemDstBytes);
+    if (r != 0) {
+      throw new LZ4Exception("liblz4hip status " + r + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /**
+   * {@link #containerDecode} for MANY containers of one kind in ONE call: item c is {@code bodies[bodyOff[c], + bodyLen[c])} with its
+   * own {@code maxBlock[c]} and {@code blockChecksum[c]}.  Per item the result is what {@link #containerDecode} gives for that body:
+   * {@code info[5c .. 5c+4]}, the sizes {@code sizes[itemFirst[c] .. itemFirst[c+1])} and the bytes
+   * {@code dest[destOff + itemDstOff[c] .. destOff + itemDstOff[c+1])}; delivered blocks lie back to back, item after item.  A group of
+   * items costs one launch sequence, whatever their number; an item that stops changes nothing about another.
+   * {@code itemDstOff} and {@code itemFirst} have one entry more than there are items, {@code info} five per item.
+   */
+  public static void containerDecodeMany(int kind, ByteBuffer bodies, long[] bodyOff, long[] bodyLen, int[] maxBlock, boolean[] blockChecksum,
+                                         int nMax, ByteBuffer dest, long destOff, long[] itemDstOff, int[] itemFirst, int[] sizes, long[] info) {
+    final int n = bodyOff.length;
+    if (!bodies.isDirect() || !dest.isDirect()) {
+      throw new IllegalArgumentException("LZ4HIPBatch needs direct ByteBuffers");
+    }
+    if (dest.isReadOnly()) {
+      throw new java.nio.ReadOnlyBufferException();
+    }
+    if (bodyLen.length != n || maxBlock.length != n || blockChecksum.length != n || destOff < 0 || destOff > dest.capacity()
+        || itemDstOff.length < n + 1 || itemFirst.length < n + 1 || info.length / 5 < n) {
+      throw new ArrayIndexOutOfBoundsException();
+    }
+    final int r = LZ4HIPJNI.LZ4HIP_containerDecodeMany(kind, bodies, bodyOff, bodyLen, maxBlock, manyFlags(bodies, bodyOff, bodyLen,
+        blockChecksum), n, nMax, dest, destOff, dest.capacity() - destOff, itemDstOff, itemFirst, sizes, info);
+    if (r != 0) {
+      throw new LZ4Exception("liblz4hip status " + r + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /** the items' ranges checked against the buffer (SafeUtils.checkRange per item) -> the flag word of every item */
+  private static int[] manyFlags(ByteBuffer bodies, long[] bodyOff, long[] bodyLen, boolean[] blockChecksum) {
+    final int[] flags = new int[bodyOff.length];
+    for (int c = 0; c < bodyOff.length; c++) {
+      if (bodyOff[c] < 0 || bodyLen[c] < 0 || bodyOff[c] + bodyLen[c] > bodies.capacity()) {
+        throw new ArrayIndexOutOfBoundsException();
+      }
+      flags[c] = blockChecksum[c] ? 1 : 0;
+    }
+    return flags;
+  }
 }

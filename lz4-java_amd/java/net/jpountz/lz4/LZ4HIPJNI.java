@@ -211,5 +211,13 @@ enum LZ4HIPJNI {
   static native long LZ4HIP_containerDecodeBound(int kind, int flags, ByteBuffer src, long srcOff, long len, int maxBlock, int nMax,
       int[] blocks);
 
+  /** Many containers of one kind in one call (LZ4HIPBatch.containerDecodeMany); returns 0 or the negative lz4hip_status. */
+  static native int LZ4HIP_containerDecodeMany(int kind, ByteBuffer bodies, long[] bodyOff, long[] bodyLen, int[] maxBlock, int[] flags,
+      int nItems, int nMax, ByteBuffer dest, long destOff, long destCap, long[] itemDstOff, int[] itemFirst, int[] sizes, long[] info);
+
+  /** Per item what LZ4HIP_containerDecodeBound says of it (host-side walk, no device); returns 0 or the negative lz4hip_status. */
+  static native int LZ4HIP_containerDecodeManyBound(int kind, ByteBuffer bodies, long[] bodyOff, long[] bodyLen, int[] maxBlock, int[] flags,
+      int nItems, int nMax, int[] itemBlocks, long[] itemDstBytes);
+
   static native String lastError();
 }

@@ -787,6 +787,71 @@ JNIEXPORT jlong JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1containerDecodeBo
   return (jlong)need;
 }
 
+/* MANY containers of one kind in one call (include/lz4hip.h lz4hip_container_decode_many{,_bound}): item c is
+ * bodies[bodyOff[c], + bodyLen[c]) with its own maxBlock[c] and flags[c] (bit 0: block checksums).  bound != 0: the host-side walk alone
+ * -- outA = itemBlocks[nItems], outB = itemDstBytes[nItems], nothing else is looked at.  Otherwise the read: the delivered blocks land
+ * back to back at dest[destOff ..), outA = itemFirst[nItems + 1], outB = itemDstOff[nItems + 1], sizes[sum of itemBlocks],
+ * info[5 x nItems].  Direct buffers; NULL arrays and arrays that are too short are argument errors; returns 0 or the (negative)
+ * lz4hip_status. */
+static jint container_many(JNIEnv* env, int bound, jint kind, jobject bodies, jlongArray bodyOff, jlongArray bodyLen, jintArray maxBlock, jintArray flags,
+                           jint nItems, jint nMax, jobject dest, jlong destOff, jlong destCap, jintArray outA, jlongArray outB, jintArray sizes, jlongArray info) {
+  if (bodies == NULL || (!bound && dest == NULL)) return LZ4HIP_E_ARG;
+  const uint8_t* s = (const uint8_t*)(*env)->GetDirectBufferAddress(env, bodies);
+  uint8_t* d = bound ? NULL : (uint8_t*)(*env)->GetDirectBufferAddress(env, dest);
+  if (s == NULL || nItems < 0 || nMax <= 0 || (!bound && (d == NULL || destOff < 0 || destCap < 0))) return LZ4HIP_E_ARG;
+  if (bodyOff == NULL || bodyLen == NULL || maxBlock == NULL || flags == NULL || outA == NULL || outB == NULL || (!bound && (sizes == NULL || info == NULL)))
+    return LZ4HIP_E_ARG;   /* (GetArrayLength of a null reference crashes a real JVM) */
+  const jint nOut = bound ? nItems : nItems + 1;
+  if ((*env)->GetArrayLength(env, bodyOff) < nItems || (*env)->GetArrayLength(env, bodyLen) < nItems || (*env)->GetArrayLength(env, maxBlock) < nItems ||
+      (*env)->GetArrayLength(env, flags) < nItems || (*env)->GetArrayLength(env, outA) < nOut || (*env)->GetArrayLength(env, outB) < nOut ||
+      (!bound && (*env)->GetArrayLength(env, info) / 5 < nItems))
+    return LZ4HIP_E_ARG;
+  uint8_t* fl = (uint8_t*)malloc((size_t)nItems + 1u);
+  jlong* bo = (*env)->GetLongArrayElements(env, bodyOff, NULL);
+  jlong* bl = (*env)->GetLongArrayElements(env, bodyLen, NULL);
+  jint* mb = (*env)->GetIntArrayElements(env, maxBlock, NULL);
+  jint* fi = (*env)->GetIntArrayElements(env, flags, NULL);
+  jint* oa = (*env)->GetIntArrayElements(env, outA, NULL);
+  jlong* ob = (*env)->GetLongArrayElements(env, outB, NULL);
+  jint* sz = bound ? NULL : (*env)->GetIntArrayElements(env, sizes, NULL);
+  jlong* inf = bound ? NULL : (*env)->GetLongArrayElements(env, info, NULL);
+  jint rc = LZ4HIP_E_NOMEM;
+  if (fl && bo && bl && mb && fi && oa && ob && (bound || (sz && inf))) {
+    rc = 0;
+    for (jint c = 0; c < nItems; c++) {
+      if (bo[c] < 0 || bl[c] < 0 || fi[c] < 0 || fi[c] > 255) rc = LZ4HIP_E_ARG;
+      fl[c] = (uint8_t)fi[c];
+    }
+    if (rc == 0 && bound)
+      rc = lz4hip_container_decode_many_bound(kind, s, (const uint64_t*)bo, (const uint64_t*)bl, (const uint32_t*)mb, fl, (uint32_t)nItems, (uint32_t)nMax,
+                                              (uint32_t*)oa, (uint64_t*)ob);
+    else if (rc == 0)
+      rc = lz4hip_container_decode_many(kind, s, (const uint64_t*)bo, (const uint64_t*)bl, (const uint32_t*)mb, fl, (uint32_t)nItems, (uint32_t)nMax, d + destOff,
+                                        (uint64_t)destCap, (uint64_t*)ob, (uint32_t*)oa, (int32_t*)sz, (uint32_t)(*env)->GetArrayLength(env, sizes), (uint64_t*)inf);
+  }
+  if (bo) (*env)->ReleaseLongArrayElements(env, bodyOff, bo, 0);
+  if (bl) (*env)->ReleaseLongArrayElements(env, bodyLen, bl, 0);
+  if (mb) (*env)->ReleaseIntArrayElements(env, maxBlock, mb, 0);
+  if (fi) (*env)->ReleaseIntArrayElements(env, flags, fi, 0);
+  if (oa) (*env)->ReleaseIntArrayElements(env, outA, oa, 0);
+  if (ob) (*env)->ReleaseLongArrayElements(env, outB, ob, 0);
+  if (sz) (*env)->ReleaseIntArrayElements(env, sizes, sz, 0);
+  if (inf) (*env)->ReleaseLongArrayElements(env, info, inf, 0);
+  free(fl);
+  return rc;
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1containerDecodeMany(JNIEnv* env, jclass cls, jint kind, jobject bodies, jlongArray bodyOff,
+    jlongArray bodyLen, jintArray maxBlock, jintArray flags, jint nItems, jint nMax, jobject dest, jlong destOff, jlong destCap, jlongArray itemDstOff,
+    jintArray itemFirst, jintArray sizes, jlongArray info) {
+  (void)cls;
+  return container_many(env, 0, kind, bodies, bodyOff, bodyLen, maxBlock, flags, nItems, nMax, dest, destOff, destCap, itemFirst, itemDstOff, sizes, info);
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1containerDecodeManyBound(JNIEnv* env, jclass cls, jint kind, jobject bodies, jlongArray bodyOff,
+    jlongArray bodyLen, jintArray maxBlock, jintArray flags, jint nItems, jint nMax, jintArray itemBlocks, jlongArray itemDstBytes) {
+  (void)cls;
+  return container_many(env, 1, kind, bodies, bodyOff, bodyLen, maxBlock, flags, nItems, nMax, NULL, 0, 0, itemBlocks, itemDstBytes, NULL, NULL);
+}
+
 /* ---- xxhash (XXHashJNI.c:42-82, :152-192 counterparts) ---- */
 static int hash_region(JNIEnv* env, jbyteArray arr, jobject buf, jint off, jint len, int is64, uint64_t seed, uint64_t* out) {
   region_t in;

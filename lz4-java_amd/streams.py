@@ -18,7 +18,7 @@ check the container logic without a GPU.
 import io
 import struct
 
-from . import CompressStreams, LZ4Exception, LZ4HIPBatch, maxCompressedLength
+from . import CompressStreams, LZ4Exception, LZ4HIPBatch, LZ4HIPError, maxCompressedLength
 
 _U32 = struct.Struct("<I")
 _I32 = struct.Struct("<i")
@@ -65,6 +65,11 @@ class HIPEngine:
         """round 4: the READ side on the device -- size words / 21-byte headers walked, block checksums verified, blocks decoded or
         copied there (lz4hip_container_decode); engines without this method make the readers walk the headers on the host"""
         return LZ4HIPBatch.containerDecode(kind, body, maxBlock, nMax, blockChecksum)
+
+    def containerDecodeMany(self, kind, bodies, maxBlock, nMax, blockChecksum=False):
+        """containerDecode for many containers of one kind in ONE call (lz4hip_container_decode_many): lists in, per item the tuple
+        containerDecode returns"""
+        return LZ4HIPBatch.containerDecodeMany(kind, bodies, maxBlock, nMax, blockChecksum)
 
     @staticmethod
     def newStreamingHash32(seed):
@@ -500,20 +505,36 @@ class LZ4FrameInputStream(io.RawIOBase):
         """the same on the device (engine.containerDecode): one chunk of container bytes goes over, the decoded blocks and a stop
         reason come back; what the device did not consume is handed back to the reader.  Same checks in the same order, same
         messages; a defect in block k surfaces after the bytes of the blocks before it."""
-        B = LZ4HIPBatch
+        req = self._deviceRequest()
+        self._deviceResult(req, self.engine.containerDecode(*req[0]))
+
+    def _deviceRequest(self):
+        """the first half of _readBlocksDevice: the next chunk of the frame's body as containerDecode's arguments -> (arguments, at_eof).
+        readFrames hands the requests of many readers to ONE containerDecodeMany and gives each its result (_deviceResult)"""
         block_checksum = self.flg.isEnabled(FLG.Bits.BLOCK_CHECKSUM)
         want = self.batchBlocks * (self.maxBlockSize + 8) + 4
         chunk = self.r.read_upto(want)
-        at_eof = len(chunk) < want
-        decoded, sizes, consumed, why, code = self.engine.containerDecode(B.FRAME_BLOCKS, chunk, self.maxBlockSize, self.batchBlocks, block_checksum)
+        return (LZ4HIPBatch.FRAME_BLOCKS, chunk, self.maxBlockSize, self.batchBlocks, block_checksum), len(chunk) < want
+
+    def _deviceResult(self, req, result, whole=None):
+        """the second half: what containerDecode returned for the request.  whole (a list, readFrames): a frame whose content checksum
+        is due and whose WHOLE content is this result does not hash it; (reader, content) is appended, and the caller ends the frame
+        with the value of its one xxh32 batch (_finishWhole)"""
+        B = LZ4HIPBatch
+        (_, chunk, _, _, _), at_eof = req
+        decoded, sizes, consumed, why, code = result
         rest = chunk[consumed:]
+        batched = whole is not None and self.content is not None and why == B.CR_END and self.totalContentSize == 0
         if decoded:
             first = len(self.ready)
             self.ready += decoded
             self.totalContentSize += len(decoded)
-            if self.content is not None:  # one update per batch of decoded blocks
+            if self.content is not None and not batched:  # one update per batch of decoded blocks
                 self.content.update(self.ready, first, len(decoded))
         self.r.unread(rest)
+        if batched:
+            whole.append((self, decoded))
+            return
         if why == B.CR_END:
             self._endMark()
         elif why == B.CR_BLOCK_TOO_BIG:
@@ -527,13 +548,24 @@ class LZ4FrameInputStream(io.RawIOBase):
             self.r.read_upto(len(rest))
             self.pending_exc = IOException(PREMATURE_EOS)
         # (CR_MORE / CR_SLOTS / a chunk that ended inside a block: the next call goes on from the bytes handed back)
+        if self.readSingleFrame and self.frame_finished:
+            self.r.give_back()
 
-    def _endMark(self):
-        """behind the end mark (LZ4FrameInputStream.java:264-276): content checksum, content size"""
+    _deviceDeliver = _deviceResult   # (what _read_many hands a reader for its request of the round)
+
+    def _finishWhole(self, contentHash):
+        """the end mark of a frame whose content was hashed by the caller (_deviceResult's `whole`)"""
+        self._endMark(contentHash)
+        if self.readSingleFrame and self.frame_finished:
+            self.r.give_back()
+
+    def _endMark(self, contentHash=None):
+        """behind the end mark (LZ4FrameInputStream.java:264-276): content checksum, content size.  contentHash: the content's XXH32
+        where the caller has it; None: the streaming hash's"""
         try:
             if self.flg.isEnabled(FLG.Bits.CONTENT_CHECKSUM):
                 stored = _U32.unpack(self.r.read_fully(4))[0]
-                if stored != self.content.getValue():
+                if stored != (self.content.getValue() if contentHash is None else contentHash):
                     raise IOException("Content checksum mismatch")
             if self.flg.isEnabled(FLG.Bits.CONTENT_SIZE) and self.expectedContentSize != self.totalContentSize:
                 raise IOException("Size check mismatch")
@@ -542,15 +574,17 @@ class LZ4FrameInputStream(io.RawIOBase):
             return
         self.frame_finished = True
 
-    def _readBlocks(self):
-        """LZ4FrameInputStream.readBlock (:258-322) for up to batchBlocks blocks"""
+    def _readBlocks(self, defer=None):
+        """LZ4FrameInputStream.readBlock (:258-322) for up to batchBlocks blocks.  defer (a list): a device request is not run but
+        appended to it, for the caller to run with other readers' (readFrames)"""
         # (the device path takes a whole chunk of container bytes from `inp`: with readSingleFrame the caller reads on behind the
         # frame, so it needs an input it can hand the surplus back to -- round-4 advisor; a pipe or socket gets the host walk, which
         # consumes exactly the frame and never waits for bytes beyond it)
         if not self.linked and not self.hostWalk and hasattr(self.engine, "containerDecode") and (not self.readSingleFrame or self.r.seekable()):
-            self._readBlocksDevice()
-            if self.readSingleFrame and self.frame_finished:
-                self.r.give_back()
+            if defer is not None:
+                defer.append(self._deviceRequest())
+            else:
+                self._readBlocksDevice()
             return
         blocks = []  # (compressed?, payload, stored checksum | None)
         end_mark = False
@@ -644,8 +678,8 @@ class LZ4FrameInputStream(io.RawIOBase):
         if end_mark:
             self._endMark()
 
-    def _fill(self):
-        """False at end of stream"""
+    def _fill(self, defer=None):
+        """False at end of stream.  defer (a list): None is returned once a device request waits in it (_readBlocks)"""
         while not self.ready:
             if self.pending_exc is not None:
                 e, self.pending_exc = self.pending_exc, None
@@ -657,7 +691,9 @@ class LZ4FrameInputStream(io.RawIOBase):
                     return False
                 if self.frame_finished:  # only skippable frames so far
                     continue
-            self._readBlocks()
+            self._readBlocks(defer)
+            if defer:
+                return None
         return True
 
     def read(self, size=-1):
@@ -861,16 +897,27 @@ class LZ4BlockInputStream(io.RawIOBase):
         rules, LZ4 blocks through the fast decoder (its return value must be the header's compressed length), raw ones copied, the
         checksums of the decoded bytes compared -- every defect is "Stream is corrupted", delivered after the blocks before it.
         False: this run is for the host path (a block bigger than the first header announced)."""
-        B = LZ4HIPBatch
+        req = self._deviceRequest()
+        return req is not None and self._deviceResult(req, self.engine.containerDecode(*req[0]))
+
+    def _deviceRequest(self):
+        """the first half of _refillDevice: the next chunk of the stream as containerDecode's arguments -> (arguments, at_eof), or None:
+        this run is for the host path.  readBlockStreams hands the requests of many readers to ONE containerDecodeMany and gives each
+        its result (_deviceResult)"""
         head = self.r.read_upto(HEADER_LENGTH)
         self.r.unread(head)
         if len(head) < HEADER_LENGTH or head[:MAGIC_LENGTH] != BLOCK_MAGIC:
-            return False   # (the host path produces the reference's exception / end of stream)
+            return None   # (the host path produces the reference's exception / end of stream)
         maxBlock = 1 << (COMPRESSION_LEVEL_BASE + (head[MAGIC_LENGTH] & 0x0F))
         want = self.batchBlocks * (maxBlock + HEADER_LENGTH) + HEADER_LENGTH
         chunk = self.r.read_upto(want)
-        at_eof = len(chunk) < want
-        decoded, sizes, consumed, why, code = self.engine.containerDecode(B.LZ4BLOCK_BLOCKS, chunk, maxBlock, self.batchBlocks, False)
+        return (LZ4HIPBatch.LZ4BLOCK_BLOCKS, chunk, maxBlock, self.batchBlocks, False), len(chunk) < want
+
+    def _deviceResult(self, req, result):
+        """the second half: what containerDecode returned for the request.  False: this run is for the host path"""
+        B = LZ4HIPBatch
+        (_, chunk, _, _, _), at_eof = req
+        decoded, sizes, consumed, why, code = result
         if why == B.CR_BLOCK_TOO_BIG:
             self.r.unread(chunk)
             return False
@@ -897,14 +944,30 @@ class LZ4BlockInputStream(io.RawIOBase):
                 self.pending_exc = EOFException(PREMATURE_EOS)
         return True
 
-    def _refill(self):  # LZ4BlockInputStream.java:191-264, for up to batchBlocks blocks
+    def _refill(self, defer=None):  # LZ4BlockInputStream.java:191-264, for up to batchBlocks blocks
+        """defer (a list): a device request is not run but appended to it, for the caller to run with other readers' (readBlockStreams),
+        which then calls _deviceDone"""
         # (stopOnEmptyBlock: the caller reads on behind the empty block, so the device path -- which takes whole chunks from `inp` --
         # needs an input it can hand the surplus back to; see LZ4FrameInputStream._readBlocks)
         if (self.checksum is None and not self.hostWalk and hasattr(self.engine, "containerDecode")
-                and (not self.stopOnEmptyBlock or self.r.seekable()) and self._refillDevice()):
-            if self.stopOnEmptyBlock and self.finished:
-                self.r.give_back()
-            return
+                and (not self.stopOnEmptyBlock or self.r.seekable())):
+            if defer is not None:
+                req = self._deviceRequest()
+                if req is not None:
+                    defer.append(req)
+                    return
+            elif self._refillDevice():
+                self._deviceDone()
+                return
+        self._refillHost()
+
+    def _deviceDone(self):
+        """behind a device run that delivered (_deviceResult said True)"""
+        if self.stopOnEmptyBlock and self.finished:
+            self.r.give_back()
+
+    def _refillHost(self):
+        """the headers walked and the checksums compared on the host around the batch launches"""
         blocks = []  # (method, payload, originalLen, check)
         exc = None
         finished = False
@@ -991,14 +1054,17 @@ class LZ4BlockInputStream(io.RawIOBase):
         elif finished:
             self.finished = True
 
-    def _fill(self):
+    def _fill(self, defer=None):
+        """defer (a list): None is returned once a device request waits in it (_refill)"""
         while not self.ready:
             if self.pending_exc is not None:
                 e, self.pending_exc = self.pending_exc, None
                 raise e
             if self.finished:
                 return False
-            self._refill()
+            self._refill(defer)
+            if defer:
+                return None
         return True
 
     def read(self, size=-1):
@@ -1042,6 +1108,88 @@ class LZ4BlockInputStream(io.RawIOBase):
 
     def reset(self):  # :300-302
         raise IOException("mark/reset not supported")
+
+    def _deviceDeliver(self, req, result, whole=None):
+        """what _read_many hands a reader for its request of the round (whole: the frame reader's)"""
+        if self._deviceResult(req, result):
+            self._deviceDone()
+        else:
+            self._refillHost()
+
+
+# =================================================================================================
+# many containers at once
+# =================================================================================================
+def _read_many(readers, engine, kind):
+    """The readers -- one per item, each the sequential reader of its item -- driven in ROUNDS: in a round every unfinished reader
+    parses what lies in front of its next blocks (frame headers, skippable frames, end marks, content size and checksum: its own
+    code) and hands over the rest of its current body as a device request; the requests of all readers go into ONE
+    containerDecodeMany, and every reader takes its result as if it had made the call itself.  CR_SLOTS and CR_MORE carry on in the
+    next round.  Content checksums: the frames whose content arrived whole in a round are hashed in ONE xxh32 batch behind it; a frame
+    that takes several rounds keeps its streaming hash.
+    -> per item (data, error): the bytes the reader delivers before it stops, and None or the exception it raises"""
+    n = len(readers)
+    out, err = [bytearray() for _ in range(n)], [None] * n
+    many = getattr(engine, "containerDecodeMany", None)
+    live = list(range(n))
+    while live:
+        waiting = []
+        for i in live:
+            r, defer = readers[i], []
+            try:
+                while True:
+                    more = r._fill(defer)
+                    if more is None:
+                        waiting.append((i, defer[0]))
+                    if not more:
+                        break
+                    out[i] += r.ready
+                    r.ready.clear()
+            except LZ4HIPError:      # (the library failed -- no device, no memory: the call's failure, not an item's result)
+                raise
+            except Exception as e:   # noqa: BLE001 -- whatever the sequential reader raises is the item's result
+                err[i] = e
+        if not waiting:
+            break
+        args = [q[0] for _, q in waiting]
+        if many is not None:
+            results = many(kind, [a[1] for a in args], [a[2] for a in args], args[0][3], [a[4] for a in args])
+        else:                        # (an engine without the many-call: the same requests one by one)
+            results = [engine.containerDecode(*a) for a in args]
+        live, whole = [], []
+        for (i, req), res in zip(waiting, results):
+            try:
+                readers[i]._deviceDeliver(req, res, whole)
+                live.append(i)
+            except LZ4HIPError:
+                raise
+            except Exception as e:   # noqa: BLE001
+                err[i] = e
+        if whole:                    # one hash launch for the contents that arrived whole in this round
+            offs, o = [], 0
+            for _, d in whole:
+                offs.append(o)
+                o += len(d)
+            hashes = engine.xxh32(b"".join(bytes(d) for _, d in whole), offs, [len(d) for _, d in whole], 0)
+            for (r, _), h in zip(whole, hashes):
+                r._finishWhole(h)
+    return [(bytes(o), e) for o, e in zip(out, err)]
+
+
+def readFrames(items, engine=None, batchBlocks=64):
+    """Many LZ4 Frame streams read together: for each item (data, error) -- the bytes LZ4FrameInputStream(io.BytesIO(item)) delivers
+    before it stops, and None or the exception it raises (same class, same message).  Every round of block reading is one
+    containerDecodeMany over all unfinished items (lz4hip_container_decode_many) where the sequential readers make one containerDecode
+    each; concatenated and skippable frames, end marks, content size and content checksum are the reader's own code.  Frames with
+    linked blocks are not part of the many-call: the reader refuses them, as it does alone."""
+    engine = engine or HIPEngine()
+    return _read_many([LZ4FrameInputStream(io.BytesIO(bytes(it)), engine=engine, batchBlocks=batchBlocks) for it in items], engine, LZ4HIPBatch.FRAME_BLOCKS)
+
+
+def readBlockStreams(items, engine=None, batchBlocks=256):
+    """Many lz4-java "LZ4Block" streams read together: readFrames' twin over LZ4BlockInputStream(io.BytesIO(item))"""
+    engine = engine or HIPEngine()
+    return _read_many([LZ4BlockInputStream(io.BytesIO(bytes(it)), engine=engine, batchBlocks=batchBlocks) for it in items], engine, LZ4HIPBatch.LZ4BLOCK_BLOCKS)
 
 
 # =================================================================================================
