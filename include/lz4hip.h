@@ -1037,6 +1037,46 @@ int lz4hip_container_decode_many(int kind, const uint8_t* bodies, const uint64_t
                                  uint8_t* dst, uint64_t dst_cap, uint64_t* item_dst_off, uint32_t* item_first, int32_t* sizes,
                                  uint32_t sizes_cap, uint64_t* info);
 
+/* ---- many containers WRITTEN per call (the write side) ---------------------------------
+ * lz4hip_container_blocks writes the blocks of ONE container per call: a stream, four device allocations, an upload, six to eight
+ * launches, two synchronisations and a copy back.  Callers that write thousands of small containers hand their payloads over together:
+ * kind is 0 (LZ4 Frame blocks) or 1 (LZ4Block blocks); a call has one kind and one level (0: LZ4_compress_default, 1..17: lz4-java's
+ * HC levels), as the single call.  Item c is src[src_off[c], + src_len[c]), cut into pieces of block_size[c] bytes; items may lie
+ * anywhere in src, in any order, and may overlap.  flags[c]: bit 0 a block checksum follows every payload (kind 0 only; items with and
+ * without it mix in one call); bit 1 the caller wants content_hash[c], the XXH32 (seed 0) of the item's source -- a frame's content
+ * checksum, taken on the device while the source lies there; content_hash[c] is 0 where bit 1 is clear, and content_hash may be NULL
+ * when no item sets it.  gap_head[c] and gap_tail[c] reserve that many bytes in front of and behind item c's blocks (either array may
+ * be NULL: 0 for every item); they come back as zeros, so that a writer places the frame header, the end mark (its four zero bytes are
+ * already there) and the content checksum in place without copying the blocks again.  The frame header, the end mark and the checksum
+ * word stay with the caller, as in the single call.
+ * The contract is the existing call, item by item: dst[item_dst_off[c] + gap_head[c], item_dst_off[c + 1] - gap_tail[c]) holds exactly
+ * the bytes lz4hip_container_blocks(kind, flags[c] & 1, level, src + src_off[c], src_len[c], block_size[c], ...) writes, and the length
+ * of that range is its *out_bytes; the LZ4Block token's level nibble follows from block_size[c].  An item of 0 bytes has no blocks and
+ * contributes only its gaps.  Items lie back to back in item order; item_dst_off has n_items + 1 entries, and nothing at or behind
+ * dst + item_dst_off[n_items] is written.
+ *   lz4hip_container_blocks_many_bound  needs no device: item_blocks[c] = ceil(src_len[c] / block_size[c]); item_dst_bytes[c] =
+ *                                       gap_head[c] + src_len[c] + item_blocks[c] x (kind 0: 4 + 4 x (flags[c] & 1); kind 1: 21) +
+ *                                       gap_tail[c], the single call's own worst case.
+ *   lz4hip_container_blocks_many        host pointers; dst_cap must be at least the sum of item_dst_bytes, so the call never fails
+ *                                       on capacity after the launch.
+ * LZ4HIP_E_ARG is said before a device is looked for: a bad kind, a NULL required pointer, a block_size[c] outside 64 .. 32 MiB, a
+ * src_len[c] above 2^31 - 1, flag bits other than 0 and 1, bit 0 with kind 1, bit 1 with content_hash == NULL, dst_cap below the bound,
+ * more than 2^31 - 1 items, or more than 2^31 - 1 - n_items blocks in all (split the call).  An unsupported level is LZ4HIP_E_UNSUPPORTED.  n_items == 0 is LZ4HIP_OK
+ * with item_dst_off[0] = 0.  The items go through the host staging in groups of LZ4HIP_HOST_CHUNK_MB MiB of sources (one item at
+ * least); a group costs one upload, one launch sequence, one copy of the results and one of the finished bytes, whatever the number of
+ * items, and compress slots and HC workspace are sized by what the group holds: a block's slot is LZ4_compressBound of the item's
+ * largest block, min(block_size[c], src_len[c]), so thousands of payloads far smaller than their block size take device memory by
+ * their bytes and not by their block size.  The call runs on the engine's first device.
+ * The sizes are scanned by one workgroup, a run of neighbouring items per thread: right for many small items.  An item of millions of
+ * blocks belongs to lz4hip_container_blocks.
+ * Out of scope: device-pointer forms; mixing kinds in one call; sharding items over several devices; linked-block frames.       */
+int lz4hip_container_blocks_many_bound(int kind, const uint64_t* src_len, const uint32_t* block_size, const uint8_t* flags,
+                                       const uint32_t* gap_head, const uint32_t* gap_tail, uint32_t n_items, uint32_t* item_blocks,
+                                       uint64_t* item_dst_bytes);
+int lz4hip_container_blocks_many(int kind, int level, const uint8_t* src, const uint64_t* src_off, const uint64_t* src_len,
+                                 const uint32_t* block_size, const uint8_t* flags, const uint32_t* gap_head, const uint32_t* gap_tail,
+                                 uint32_t n_items, uint8_t* dst, uint64_t dst_cap, uint64_t* item_dst_off, uint32_t* content_hash);
+
 /* ---- workload helper (not part of the reference API) ------------------------------------------
  * Fills n_blocks slots of `block_len` bytes at dst + i*stride with the SURVEY.md App. F synthetic
  * blocks idx = first_idx + i (deterministic, seed-addressed).  Device pointer, async on stream.

@@ -143,6 +143,9 @@ C_ABI = {
     "lz4hip_container_decode_many_bound": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, _u32p, _u8p, C.c_uint32, C.c_uint32, _u32p, _u64p]),
     "lz4hip_container_decode_many": (C.c_int, [C.c_int, C.c_void_p, _u64p, _u64p, _u32p, _u8p, C.c_uint32, C.c_uint32, _u8p, C.c_uint64, _u64p, _u32p,
                                                _i32p, C.c_uint32, _u64p]),
+    "lz4hip_container_blocks_many_bound": (C.c_int, [C.c_int, _u64p, _u32p, _u8p, _u32p, _u32p, C.c_uint32, _u32p, _u64p]),
+    "lz4hip_container_blocks_many": (C.c_int, [C.c_int, C.c_int, C.c_void_p, _u64p, _u64p, _u32p, _u8p, _u32p, _u32p, C.c_uint32, _u8p, C.c_uint64, _u64p,
+                                               _u32p]),
     "lz4hip_gen_blocks_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                         C.c_uint32, C.c_int, C.c_void_p]),
 }
@@ -853,6 +856,56 @@ class LZ4HIPBatch:
         out = C.c_uint64(0)
         _chk(lib().lz4hip_container_blocks(kind, 1 if blockChecksum else 0, level, sp, len(data), blockSize, dp, cap, C.byref(out)))
         return bytes(dst[:out.value])
+
+    @staticmethod
+    def containerBlocksManyBound(kind, lengths, blockSizes, blockChecksums=False, gapHead=0, gapTail=0):
+        """lz4hip_container_blocks_many_bound (no device): per item (blocks, worst-case bytes with its gaps)"""
+        import numpy as np
+        n = len(lengths)
+        per = lambda v, t: np.asarray(list(v) if hasattr(v, "__len__") else [v] * n, dtype=t)
+        ln, bs, gh, gt = per(lengths, np.uint64), per(blockSizes, np.uint32), per(gapHead, np.uint32), per(gapTail, np.uint32)
+        fl = np.asarray([1 if c else 0 for c in (blockChecksums if hasattr(blockChecksums, "__len__") else [blockChecksums] * n)], dtype=np.uint8)
+        if not (len(ln) == len(bs) == len(gh) == len(gt) == len(fl) == n):
+            raise ValueError("per-item lists differ in length")
+        a = lambda v, t: v.ctypes.data_as(C.POINTER(t))
+        nbs, need = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint64)
+        _chk(lib().lz4hip_container_blocks_many_bound(kind, a(ln, C.c_uint64), a(bs, C.c_uint32), a(fl, C.c_uint8), a(gh, C.c_uint32), a(gt, C.c_uint32), n,
+                                                      a(nbs, C.c_uint32), a(need, C.c_uint64)))
+        return [(int(nbs[c]), int(need[c])) for c in range(n)]
+
+    @staticmethod
+    def containerBlocksMany(kind, items, blockSizes, blockChecksums=False, level=0, gapHead=0, gapTail=0, contentHash=False):
+        """containerBlocks for MANY payloads of one kind in one call (lz4hip_container_blocks_many): `items` is a list of payloads;
+        blockSizes, blockChecksums, gapHead, gapTail and contentHash are lists of the same length (or one value for all).  ->
+        (dst, off, hashes): item c's bytes are dst[off[c]:off[c + 1]] (a writable numpy uint8 array): gapHead[c] zero bytes, the bytes
+        containerBlocks(kind, items[c], blockSizes[c], blockChecksums[c], level) returns, gapTail[c] zero bytes; hashes[c] is the XXH32
+        (seed 0) of items[c] where contentHash[c] is set, else 0.  A group of items costs one launch sequence, whatever their number"""
+        import numpy as np
+        n = len(items)
+        per = lambda v: list(v) if hasattr(v, "__len__") else [v] * n
+        bsl, ckl, ghl, gtl, chl = per(blockSizes), per(blockChecksums), per(gapHead), per(gapTail), per(contentHash)
+        if not (len(bsl) == len(ckl) == len(ghl) == len(gtl) == len(chl) == n):
+            raise ValueError("per-item lists differ in length")
+        doff = np.zeros(n + 1, dtype=np.uint64)
+        if n == 0:
+            return np.zeros(0, dtype=np.uint8), doff, np.zeros(0, dtype=np.uint32)
+        lens = np.fromiter((len(b) for b in items), dtype=np.uint64, count=n)
+        offs = np.zeros(n, dtype=np.uint64)
+        np.cumsum(lens[:-1], out=offs[1:])
+        blob = b"".join(bytes(b) if not isinstance(b, (bytes, bytearray)) else b for b in items)
+        sp, sk = _ro_ptr(blob if blob else b"\0")
+        bs, gh, gt = np.asarray(bsl, dtype=np.uint32), np.asarray(ghl, dtype=np.uint32), np.asarray(gtl, dtype=np.uint32)
+        fl = np.asarray([(1 if c else 0) | (2 if h else 0) for c, h in zip(ckl, chl)], dtype=np.uint8)
+        a = lambda v, t: v.ctypes.data_as(C.POINTER(t))
+        nbs, need = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+        _chk(lib().lz4hip_container_blocks_many_bound(kind, a(lens, C.c_uint64), a(bs, C.c_uint32), a(fl, C.c_uint8), a(gh, C.c_uint32), a(gt, C.c_uint32), n,
+                                                      a(nbs, C.c_uint32), a(need, C.c_uint64)))
+        cap = int(need.sum())
+        dst = np.empty(max(cap, 1), dtype=np.uint8)
+        hashes = np.zeros(n, dtype=np.uint32)
+        _chk(lib().lz4hip_container_blocks_many(kind, level, sp, a(offs, C.c_uint64), a(lens, C.c_uint64), a(bs, C.c_uint32), a(fl, C.c_uint8),
+                                                a(gh, C.c_uint32), a(gt, C.c_uint32), n, a(dst, C.c_uint8), cap, a(doff, C.c_uint64), a(hashes, C.c_uint32)))
+        return dst, doff, hashes
 
     # stop reasons of containerDecode (include/lz4hip.h)
     CR_END, CR_MORE, CR_TRUNCATED, CR_BLOCK_TOO_BIG, CR_BLOCK_CHECKSUM, CR_DECODE, CR_CORRUPT, CR_SLOTS = range(8)

@@ -21,6 +21,7 @@
 #include "kernels.h"
 #include "host_staging.h"
 #include "container_rules.h"
+#include "container_write_rules.h"
 
 namespace {
 
@@ -1976,6 +1977,127 @@ int lz4hip_container_decode_many(int kind, const uint8_t* bodies, const uint64_t
   std::string err;
   const int rc = container_many_shard(ord, kind, bodies, body_off, body_len, max_block, flags, n_items, n_max, nb.data(), slot.data(), first.data(), dst,
                                       item_dst_off, item_first, sizes, info, &err);
+  return rc ? fail(rc, err.c_str()) : (int)LZ4HIP_OK;
+}
+
+// ---- many containers written per call ----
+// what can be said about the items of a many-write without a device -> a message, or nullptr
+static const char* container_write_many_arg_error(int kind, const uint64_t* src_len, const uint32_t* block_size, const uint8_t* flags, uint32_t n_items) {
+  if (kind != 0 && kind != 1) return "container kind must be 0 (LZ4 Frame blocks) or 1 (LZ4Block blocks)";
+  if (n_items && (!src_len || !block_size || !flags)) return kNullArg;
+  for (uint32_t c = 0; c < n_items; c++)
+    if (const char* why = lz4hip::container_write_rules::item_error(kind, src_len[c], block_size[c], flags[c])) return why;
+  return nullptr;
+}
+int lz4hip_container_blocks_many_bound(int kind, const uint64_t* src_len, const uint32_t* block_size, const uint8_t* flags, const uint32_t* gap_head,
+                                       const uint32_t* gap_tail, uint32_t n_items, uint32_t* item_blocks, uint64_t* item_dst_bytes) {
+  namespace wr = lz4hip::container_write_rules;
+  if (const char* why = container_write_many_arg_error(kind, src_len, block_size, flags, n_items)) return fail(LZ4HIP_E_ARG, why);
+  if (n_items && (!item_blocks || !item_dst_bytes)) return fail(LZ4HIP_E_ARG, kNullArg);
+  for (uint32_t c = 0; c < n_items; c++) {
+    item_blocks[c] = wr::item_blocks(src_len[c], block_size[c]);
+    item_dst_bytes[c] = wr::item_bound(kind, flags[c], src_len[c], block_size[c], gap_head ? gap_head[c] : 0u, gap_tail ? gap_tail[c] : 0u);
+  }
+  return LZ4HIP_OK;
+}
+// The items of a many-write through the shared staging, a group at a time (chain_shard: an item is its unit, first[] counts its blocks):
+// a group is the items whose sources fit LZ4HIP_HOST_CHUNK_MB MiB and whose bounds fit 512 MiB, one item at least.  A group costs one
+// upload of the packed sources and the item arrays, one launch sequence, one copy of the results and one of the finished bytes, which
+// the device has laid back to back; compress slots (LZ4_compressBound of an item's largest block, per block: a payload far smaller than
+// its block size takes what it holds, so the slots of a group stay below 2.01 x its sources + 32 bytes per block) and the HC workspace
+// are sized by what the group holds.
+static int container_write_many_shard(int ord, int kind, int hc_lv, const uint8_t* src, const uint64_t* src_off, const uint64_t* src_len,
+                                      const uint32_t* block_size, const uint8_t* flags, const uint32_t* gap_head, const uint32_t* gap_tail, uint32_t n_items,
+                                      const uint32_t* first, const uint64_t* bound, uint8_t* dst, uint64_t* item_dst_off, uint32_t* content_hash,
+                                      std::string* err) {
+  namespace wr = lz4hip::container_write_rules;
+  auto cost = [&](uint32_t c) { return staging::Cost{al16((size_t)src_len[c]), (size_t)bound[c]}; };
+  uint64_t out_bytes = 0;
+  std::vector<uint64_t> so;
+  return chain_shard(ord, first, 0, n_items, err, cost, [&](ShardScope& sh, ChunkSlot& s, const ChainChunk& ck) {
+    const uint32_t c = ck.c, nc = ck.nc, nb = ck.nb;
+    const staging::ContainerWriteManyMeta m(nc);
+    if (!sh.reserve(s, ck.src, true, ck.dst, m.l.total)) return false;
+    uint8_t* const hs = (uint8_t*)s.h_src.p;
+    void *const hm = s.h_meta.p, *const dm = s.d_meta.p;
+    so.resize(nc);
+    bool any_cks = false, any_hash = false;
+    uint64_t slots = 0;
+    { size_t o = 0;
+      for (uint32_t t = 0; t < nc; t++) {
+        so[t] = o; o += al16((size_t)src_len[c + t]);
+        m.src_off.in(hm)[t] = so[t]; m.src_len.in(hm)[t] = (int32_t)src_len[c + t]; m.slot_base.in(hm)[t] = slots;
+        slots += (uint64_t)(first[c + t + 1] - first[c + t]) * wr::item_slot_bytes(src_len[c + t], block_size[c + t]);
+        m.hash_len.in(hm)[t] = (flags[c + t] & wr::kFlagContentHash) ? (int32_t)src_len[c + t] : 0;
+        m.block_size.in(hm)[t] = block_size[c + t]; m.flags.in(hm)[t] = flags[c + t];
+        m.gap_head.in(hm)[t] = gap_head ? gap_head[c + t] : 0u; m.gap_tail.in(hm)[t] = gap_tail ? gap_tail[c + t] : 0u;
+        any_cks |= (flags[c + t] & wr::kFlagBlockChecksum) != 0u; any_hash |= (flags[c + t] & wr::kFlagContentHash) != 0u;
+      } }
+    staging::rebase_first(first, c, nc, m.first.in(hm));
+    // the device scratch of the group: the block arrays and the slots | the HC workspace | the fast compressor's queue words
+    const size_t cws = (lz4hip::container_write_many_ws_bytes(nb, slots) + 256u + 255u) & ~(size_t)255u;
+    const size_t hcws = hc_lv > 0 && nb ? ((lz4hip::hc_ws_bytes(ck.src, nb, hc_lv) + 255u) & ~(size_t)255u) : 0u;
+    const size_t qwords = 3u + (size_t)nb + lz4hip::compress_fast_v2w_scratch_words(lz4hip::device_cus());
+    if (!sh.ok("staging allocation", s.d_ws.reserve(cws + hcws + qwords * sizeof(uint32_t) + 256u))) return false;
+    par_blocks(c, ck.j, ck.src, [=, &so](uint32_t t) { if (src_len[t]) memcpy(hs + so[t - c], src + src_off[t], (size_t)src_len[t]); });
+    if (!sh.upload(s, ck.src, m.l, s.st)) return false;
+    uint8_t* const w = (uint8_t*)s.d_ws.p;
+    const lz4hip::ContainerWriteManyItems items{m.src_off.in(dm), m.src_len.in(dm), m.hash_len.in(dm), m.slot_base.in(dm), m.block_size.in(dm), m.first.in(dm),
+                                                m.gap_head.in(dm), m.gap_tail.in(dm), m.flags.in(dm)};
+    if (!sh.launched(lz4hip::launch_container_blocks_many(kind, hc_lv, any_cks, any_hash, (const uint8_t*)s.d_src.p, ck.src, items, nc, nb, (uint8_t*)s.d_dst.p,
+                                                          ck.dst, (unsigned long long*)m.item_dst_off.in(dm), m.content_hash.in(dm), w, hcws ? w + cws : nullptr,
+                                                          (uint32_t*)(w + cws + hcws), 64u * (uint32_t)g_compress_switch.load(std::memory_order_relaxed),
+                                                          lz4hip::device_cus(), g_compress_core.load(std::memory_order_relaxed), s.st)))
+      return false;
+    if (!sh.fetch_results(s, m.l, s.st) || !sh.wait(s.st)) return false;
+    const uint64_t* const ido = m.item_dst_off.in(hm);
+    const uint64_t total = ido[nc];
+    if (total > ck.dst) { *sh.err = "container write: the device wrote more than the items' bounds"; sh.rc = LZ4HIP_E_HIP; return false; }
+    if (total) {
+      if (!sh.ok("D2H dst", hipMemcpyAsync(s.h_dst.p, s.d_dst.p, (size_t)total, hipMemcpyDeviceToHost, s.st)) || !sh.wait(s.st)) return false;
+      memcpy(dst + out_bytes, s.h_dst.p, (size_t)total);
+    }
+    for (uint32_t t = 0; t <= nc; t++) item_dst_off[c + t] = out_bytes + ido[t];
+    if (content_hash) for (uint32_t t = 0; t < nc; t++) content_hash[c + t] = (flags[c + t] & wr::kFlagContentHash) ? m.content_hash.in(hm)[t] : 0u;
+    out_bytes += total;
+    return true;
+  });
+}
+int lz4hip_container_blocks_many(int kind, int level, const uint8_t* src, const uint64_t* src_off, const uint64_t* src_len, const uint32_t* block_size,
+                                 const uint8_t* flags, const uint32_t* gap_head, const uint32_t* gap_tail, uint32_t n_items, uint8_t* dst, uint64_t dst_cap,
+                                 uint64_t* item_dst_off, uint32_t* content_hash) {
+  namespace wr = lz4hip::container_write_rules;
+  if (kind != 0 && kind != 1) return fail(LZ4HIP_E_ARG, "container kind must be 0 (LZ4 Frame blocks) or 1 (LZ4Block blocks)");
+  if (n_items > 0x7FFFFFFFu) return fail(LZ4HIP_E_ARG, "more than 2^31 - 1 items: split the call");   // (before any array is read)
+  if (!item_dst_off || (n_items && !src_off) || (dst_cap && !dst)) return fail(LZ4HIP_E_ARG, kNullArg);
+  if (const char* why = container_write_many_arg_error(kind, src_len, block_size, flags, n_items)) return fail(LZ4HIP_E_ARG, why);
+  std::vector<uint32_t> first((size_t)n_items + 1u);
+  std::vector<uint64_t> bound(n_items);
+  uint64_t need = 0, blocks = 0;
+  for (uint32_t c = 0; c < n_items; c++) {
+    if (src_len[c] && !src) return fail(LZ4HIP_E_ARG, kNullArg);
+    if ((flags[c] & wr::kFlagContentHash) && !content_hash) return fail(LZ4HIP_E_ARG, "an item asks for its content hash (flag bit 1) and content_hash is NULL");
+    first[c] = (uint32_t)blocks;
+    blocks += wr::item_blocks(src_len[c], block_size[c]);
+    if (blocks > 0x7FFFFFFFull - n_items) return fail(LZ4HIP_E_ARG, "the items hold more than 2^31 - 1 - n_items blocks: split the call");
+    bound[c] = wr::item_bound(kind, flags[c], src_len[c], block_size[c], gap_head ? gap_head[c] : 0u, gap_tail ? gap_tail[c] : 0u);
+    if (need + bound[c] < need) return fail(LZ4HIP_E_ARG, "the sum of item_dst_bytes does not fit 64 bits: split the call");
+    need += bound[c];
+  }
+  first[n_items] = (uint32_t)blocks;
+  if (dst_cap < need) return fail(LZ4HIP_E_ARG, "dst_cap is below the sum of item_dst_bytes (lz4hip_container_blocks_many_bound)");
+  int lv = 0;
+  if (level != 0 && hc_level(level, &lv)) return fail(LZ4HIP_E_UNSUPPORTED, "unsupported compression level");
+  item_dst_off[0] = 0;
+  if (n_items == 0) return LZ4HIP_OK;
+  if (content_hash) for (uint32_t c = 0; c < n_items; c++) content_hash[c] = 0;
+  if (const int rc = need_device()) return rc;
+  int ord;
+  if (ordinal(0, &ord)) return fail(LZ4HIP_E_NO_DEVICE, "no device");
+  DeviceGuard g(ord);
+  std::string err;
+  const int rc = container_write_many_shard(ord, kind, lv, src, src_off, src_len, block_size, flags, gap_head, gap_tail, n_items, first.data(), bound.data(),
+                                            dst, item_dst_off, content_hash, &err);
   return rc ? fail(rc, err.c_str()) : (int)LZ4HIP_OK;
 }
 #if defined(__GNUC__)

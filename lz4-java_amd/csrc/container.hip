@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "kernels.h"
 #include "container_rules.h"
+#include "container_write_rules.h"
 
 namespace lz4hip {
 
@@ -740,6 +741,187 @@ int launch_container_read_many(int kind, bool any_block_checksum, const uint8_t*
   hipLaunchKernelGGL(container_verdict_many_kernel, dim3(1), dim3(1024), 0, st, kind, m, sizes, info, item_first, item_dst_off);
   BatchArgs pk{nullptr, nullptr, nullptr, dst, c.dst_off, nullptr, m.deliver, ne};
   hipLaunchKernelGGL(pack_copy_kernel, dim3(ne), dim3(256), 0, st, pk, (const uint64_t*)m.poff, pack);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// MANY containers WRITTEN per launch sequence (lz4hip_container_blocks_many): the sources of a group of items -- thousands of small
+// payloads that each become the blocks of one LZ4 Frame or one LZ4Block stream -- lie packed in device memory, and the write sequence
+// of launch_container_blocks runs ONCE over the concatenation of all items' blocks.  Item t owns the blocks [first[t], first[t + 1])
+// (container_write_rules.h: ceil(src_len / block_size) of them, none for an item of 0 bytes), has its own block size, its own flags
+// (bit 0: block checksums, kind 0 only) and its own gaps: gap_head[t] bytes in front of its blocks and gap_tail[t] behind them come
+// back as zeros, for the frame header, the end mark and the content checksum a writer places there.  (1) container_layout_many_kernel,
+// a lane per block: its item by binary search in first[], its source and its compress slot (the slots of item t start at slot_base[t]
+// and are container_write_rules::item_slot_bytes(src_len[t], block_size[t]) apart: LZ4_compressBound of the item's largest block, so that
+// thousands of payloads far smaller than their block size take scratch by what they hold); (2) ONE compress launch over all blocks, the
+// dispatch of launch_container_blocks, so the compressor's device-side queueing sees the whole batch; (3) LZ4Block checksums over the
+// original blocks, and the content hashes (XXH32, seed 0) over the items; (4) container_scan_many_kernel: the raw-fallback decision and
+// the exclusive scan of the stored sizes with the gaps added at the item boundaries -> hdr_off per block, item_dst_off per item; one
+// workgroup, a run of neighbouring items per thread; (5) container_copy_many_kernel: container_copy_kernel with block checksum and
+// level nibble taken from the block's item, and further workgroups that zero the gaps; then the frame block checksums over the stored
+// payloads (hash length 0 for the blocks of items without them) and their placement.
+// ------------------------------------------------------------------------------------------------
+struct ContainerWrite {   // arrays of n blocks in the workspace
+  uint64_t* src_off; uint64_t* slot_off; uint64_t* hdr_off; uint64_t* pay_off;
+  int32_t* src_len; int32_t* slot_cap; int32_t* clen; int32_t* stored; int32_t* pay_len;
+  uint32_t* hashes; uint32_t* item;
+};
+__global__ void container_layout_many_kernel(ContainerWriteManyItems m, uint32_t n_items, uint32_t n, ContainerWrite w) {
+  namespace wr = container_write_rules;
+  const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+  if (b >= n) return;
+  const uint32_t t = wr::item_of_block(m.first, n_items, b), k = b - m.first[t];
+  const uint64_t n_bytes = (uint64_t)(uint32_t)m.src_len[t];
+  const uint32_t bs = m.block_size[t], bound = wr::item_slot_bytes(n_bytes, bs);
+  w.item[b] = t;
+  w.src_off[b] = m.src_off[t] + wr::block_offset(bs, k);
+  w.src_len[b] = (int32_t)wr::block_length(n_bytes, bs, k);
+  w.slot_off[b] = m.slot_base[t] + (uint64_t)k * bound;
+  w.slot_cap[b] = (int32_t)bound;
+}
+// stored length of every block (container_scan_kernel's test) and where its header goes; per item where it starts: its gap_head, its
+// blocks, its gap_tail.  item_dst_off: n_items + 1 entries, the last one the bytes written in all
+__global__ __launch_bounds__(1024) void container_scan_many_kernel(int kind, ContainerWriteManyItems m, uint32_t n_items, ContainerWrite w,
+                                                                    unsigned long long* item_dst_off) {
+  namespace wr = container_write_rules;
+  __shared__ uint64_t part[1024];
+  const uint32_t t = threadIdx.x;
+  const uint32_t per = (n_items + 1023u) / 1024u;
+  const uint32_t i0 = t * per < n_items ? t * per : n_items, i1 = (i0 + per < n_items) ? i0 + per : n_items;
+  uint64_t s = 0;
+  for (uint32_t it = i0; it < i1; it++) {
+    const uint64_t fixed = wr::block_fixed(kind, m.flags[it]);
+    s += (uint64_t)m.gap_head[it] + m.gap_tail[it];
+    for (uint32_t b = m.first[it]; b < m.first[it + 1u]; b++) {
+      const int32_t l = w.src_len[b], c = w.clen[b];
+      const bool raw = c <= 0 || c >= l;
+      w.stored[b] = raw ? (l | (int32_t)0x80000000) : c;     // (sign bit: stored uncompressed)
+      s += fixed + (uint64_t)(raw ? l : c);
+    }
+  }
+  part[t] = s;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024u; d <<= 1) {   // inclusive scan of the 1024 partial sums
+    const uint64_t v = t >= d ? part[t - d] : 0ull;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint64_t run = part[t] - s;
+  for (uint32_t it = i0; it < i1; it++) {
+    const uint64_t fixed = wr::block_fixed(kind, m.flags[it]);
+    item_dst_off[it] = run;
+    run += m.gap_head[it];
+    for (uint32_t b = m.first[it]; b < m.first[it + 1u]; b++) { w.hdr_off[b] = run; run += fixed + (uint64_t)(w.stored[b] & 0x7FFFFFFF); }
+    run += m.gap_tail[it];
+  }
+  if (t == 1023u) item_dst_off[n_items] = part[1023];
+}
+// workgroups [0, n): header + payload of block b (container_copy_kernel, the block's item says what the header holds); workgroups
+// [n, n + n_items): the gaps of item b - n are zeroed.  Whatever does not fit [0, dst_cap) is not written.
+__global__ __launch_bounds__(256) void container_copy_many_kernel(int kind, ContainerWriteManyItems m, uint32_t n_items, uint32_t n, const uint8_t* src,
+                                                                  const uint8_t* slots, ContainerWrite w, const unsigned long long* item_dst_off, uint8_t* dst,
+                                                                  uint64_t dst_cap) {
+  namespace wr = container_write_rules;
+  if (blockIdx.x >= n) {
+    const uint32_t it = blockIdx.x - n;
+    if (it >= n_items) return;
+    const uint64_t lo = item_dst_off[it], hi = item_dst_off[it + 1u];
+    const uint32_t gh = m.gap_head[it], gt = m.gap_tail[it];
+    if (hi > dst_cap || hi < lo || (uint64_t)gh + gt > hi - lo) return;
+    for (uint32_t i = threadIdx.x; i < gh; i += 256u) dst[lo + i] = 0;
+    for (uint32_t i = threadIdx.x; i < gt; i += 256u) dst[hi - gt + i] = 0;
+    return;
+  }
+  const uint32_t b = blockIdx.x, it = w.item[b];
+  const uint32_t flags = m.flags[it];
+  const int32_t st = w.stored[b];
+  const bool raw = st < 0;
+  const uint32_t len = (uint32_t)(st & 0x7FFFFFFF);
+  const uint32_t hl = wr::block_header(kind);
+  const uint64_t ho = w.hdr_off[b];
+  // (the capacity is the sum of the items' bounds, so every block fits; one that would not is skipped whole and hashes nothing)
+  const bool fits = ho + wr::block_fixed(kind, flags) + len <= dst_cap;
+  if (threadIdx.x == 0) { w.pay_off[b] = fits ? ho + hl : 0ull; w.pay_len[b] = (fits && kind == 0 && (flags & wr::kFlagBlockChecksum)) ? (int32_t)len : 0; }
+  if (!fits) return;
+  uint8_t* h = dst + ho;
+  if (threadIdx.x < hl) {
+    uint8_t v;
+    const uint32_t t = threadIdx.x;
+    if (kind == 0) {
+      const uint32_t word = len | (raw ? 0x80000000u : 0u);
+      v = (uint8_t)(word >> (8u * t));
+    } else {
+      const uint32_t olen = (uint32_t)w.src_len[b], chk = w.hashes[b] & 0x0FFFFFFFu;
+      if (t < 8u) v = (uint8_t)"LZ4Block"[t];
+      else if (t == 8u) v = (uint8_t)((raw ? 0x10u : 0x20u) | wr::level_nibble(m.block_size[it]));
+      else if (t < 13u) v = (uint8_t)(len >> (8u * (t - 9u)));
+      else if (t < 17u) v = (uint8_t)(olen >> (8u * (t - 13u)));
+      else v = (uint8_t)(chk >> (8u * (t - 17u)));
+    }
+    h[t] = v;
+  }
+  const uint8_t* s = raw ? src + w.src_off[b] : slots + w.slot_off[b];
+  uint8_t* d = h + hl;
+  const uint32_t body = len & ~15u;
+  for (uint32_t i = threadIdx.x * 16u; i < body; i += 256u * 16u) {
+    uint4 v;
+    __builtin_memcpy(&v, s + i, 16);
+    __builtin_memcpy(d + i, &v, 16);
+  }
+  const uint32_t i = body + threadIdx.x;
+  if (i < len) d[i] = s[i];
+}
+// kind 0: the XXH32 (seed 0) of each stored payload goes behind it, for the blocks of the items with block checksums
+__global__ void container_put_hashes_many_kernel(uint32_t n, ContainerWriteManyItems m, ContainerWrite w, uint8_t* dst, uint64_t dst_cap) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  if (!(m.flags[w.item[i]] & container_write_rules::kFlagBlockChecksum) || w.pay_off[i] == 0ull) return;
+  const uint64_t o = w.pay_off[i] + (uint64_t)w.pay_len[i];
+  if (o + 4u > dst_cap) return;
+  const uint32_t h = w.hashes[i];
+  dst[o] = (uint8_t)h; dst[o + 1] = (uint8_t)(h >> 8); dst[o + 2] = (uint8_t)(h >> 16); dst[o + 3] = (uint8_t)(h >> 24);
+}
+// src_off, slot_off, hdr_off, pay_off (u64) | src_len, slot_cap, clen, stored, pay_len (i32) | hashes, item (u32); the slots follow
+// on a 256-byte boundary (slot_bytes_total: the sum over the items of blocks x container_write_rules::item_slot_bytes(src_len, block_size))
+static size_t container_write_many_arrays(uint32_t n_blocks) { return ((size_t)n_blocks * (4u * 8u + 7u * 4u) + 255u) & ~(size_t)255u; }
+size_t container_write_many_ws_bytes(uint32_t n_blocks, uint64_t slot_bytes_total) { return container_write_many_arrays(n_blocks) + (size_t)slot_bytes_total; }
+int launch_container_blocks_many(int kind, int hc_level, bool any_block_checksum, bool any_content_hash, const uint8_t* src, uint64_t src_span,
+                                 const ContainerWriteManyItems& items, uint32_t n_items, uint32_t n_blocks, uint8_t* dst, uint64_t dst_cap,
+                                 unsigned long long* item_dst_off, uint32_t* content_hash, void* ws, void* hc_ws, uint32_t* q_scratch, uint32_t dense64,
+                                 uint32_t n_cus, int core, void* stream) {
+  if (n_items == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t n = n_blocks;
+  uint8_t* p = (uint8_t*)ws;
+  ContainerWrite w;
+  w.src_off = (uint64_t*)p; w.slot_off = w.src_off + n; w.hdr_off = w.slot_off + n; w.pay_off = w.hdr_off + n;
+  w.src_len = (int32_t*)(w.pay_off + n); w.slot_cap = w.src_len + n; w.clen = w.slot_cap + n; w.stored = w.clen + n; w.pay_len = w.stored + n;
+  w.hashes = (uint32_t*)(w.pay_len + n); w.item = w.hashes + n;
+  uint8_t* slots = p + container_write_many_arrays(n);
+  int e;
+  if (n) {
+    hipLaunchKernelGGL(container_layout_many_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, items, n_items, n, w);
+    BatchArgs a{src, w.src_off, w.src_len, slots, w.slot_off, w.slot_cap, w.clen, n};
+    if (hc_level > 0) e = launch_compress_hc(a, hc_level, hc_ws, src_span, stream);
+    else if (core == 1) e = launch_compress_fast_ms(a, q_scratch, nullptr, true, n_cus, stream);
+    else if (core == 3) e = launch_compress_fast_v2w(a, q_scratch, nullptr, 0u, n_cus, q_scratch + 3 + n, stream);
+    else {
+      e = launch_compress_fast_v2w(a, q_scratch, q_scratch + 3, dense64, n_cus, q_scratch + 3 + n, stream);
+      if (e == 0) e = launch_compress_fast_ms(a, q_scratch, q_scratch + 3, false, n_cus, stream);
+    }
+    if (e) return e;
+    if (kind == 1 && (e = launch_xxh32(src, w.src_off, w.src_len, 0x9747b28cu, w.hashes, n, stream)) != 0) return e;
+  }
+  // (hash_len[t] is 0 for the items that do not ask: their sources are not read a second time)
+  if (any_content_hash && (e = launch_xxh32(src, items.src_off, items.hash_len, 0u, content_hash, n_items, stream)) != 0) return e;
+  hipLaunchKernelGGL(container_scan_many_kernel, dim3(1), dim3(1024), 0, st, kind, items, n_items, w, item_dst_off);
+  hipLaunchKernelGGL(container_copy_many_kernel, dim3(n + n_items), dim3(256), 0, st, kind, items, n_items, n, src, (const uint8_t*)slots, w,
+                     (const unsigned long long*)item_dst_off, dst, dst_cap);
+  if (n && kind == 0 && any_block_checksum) {
+    if ((e = launch_xxh32(dst, w.pay_off, w.pay_len, 0u, w.hashes, n, stream)) != 0) return e;
+    hipLaunchKernelGGL(container_put_hashes_many_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, n, items, w, dst, dst_cap);
+  }
   return (int)hipGetLastError();
 }
 

@@ -100,6 +100,15 @@ struct ContainerManyMeta {   // many containers per call (container_many_shard):
         max_block(l.input<uint32_t>(nc)), first(l.input<uint32_t>(nc + 1)), flags(l.input<uint8_t>(nc)),
         info(l.result<uint64_t>(5 * nc)), item_dst_off(l.result<uint64_t>(nc + 1)), item_first(l.result<uint32_t>(nc + 1)), sizes(l.result<int32_t>(ne)) {}
 };
+struct ContainerWriteManyMeta {   // many containers written per call (container_write_many_shard): nc items
+  MetaLayout l;
+  Region<uint64_t> src_off, slot_base; Region<int32_t> src_len, hash_len; Region<uint32_t> block_size, first, gap_head, gap_tail; Region<uint8_t> flags;
+  Region<uint64_t> item_dst_off; Region<uint32_t> content_hash;
+  explicit ContainerWriteManyMeta(size_t nc)
+      : src_off(l.input<uint64_t>(nc)), slot_base(l.input<uint64_t>(nc)), src_len(l.input<int32_t>(nc)), hash_len(l.input<int32_t>(nc)),
+        block_size(l.input<uint32_t>(nc)), first(l.input<uint32_t>(nc + 1)), gap_head(l.input<uint32_t>(nc)), gap_tail(l.input<uint32_t>(nc)), flags(l.input<uint8_t>(nc)),
+        item_dst_off(l.result<uint64_t>(nc + 1)), content_hash(l.result<uint32_t>(nc)) {}
+};
 
 // The scratch of the HC chain compressor's layout kernel (compress_hc.hip) for n_blocks blocks in n_chains chains whose regions end at or
 // before `span`, with build segments of `seg` positions (4096 .. 2^30): byte offsets of its arrays, 8-byte ones first.  max_items: a

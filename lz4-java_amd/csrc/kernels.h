@@ -102,6 +102,23 @@ size_t container_many_ws_bytes(uint32_t n_entries, uint32_t n_items);
 int launch_container_read_many(int kind, bool any_block_checksum, const uint8_t* bodies, const ContainerManyItems& items, uint32_t n_items, uint32_t n_entries,
                                uint32_t n_max, uint8_t* dst, uint8_t* pack, int32_t* sizes, unsigned long long* info, uint32_t* item_first,
                                unsigned long long* item_dst_off, void* ws, void* stream);
+// The write sequence over MANY items of one kind at once (container.hip): item t is src[src_off[t], + src_len[t]) cut into pieces of
+// block_size[t] bytes, with its own flags[t] (bit 0: block checksums, kind 0 only) and gap_head[t] / gap_tail[t] zero bytes in front of
+// and behind its blocks; it owns the blocks [first[t], first[t + 1]) and the compress slots from slot_base[t] on, which are
+// container_write_rules::item_slot_bytes(src_len[t], block_size[t]) bytes apart.  The items' bytes lie back to back in dst from
+// item_dst_off[t] on (n_items + 1 entries, the last one the total); when any_content_hash, content_hash[t] = XXH32(seed 0) of the item's
+// first hash_len[t] bytes: src_len[t] for an item that asks, 0 for one that does not.  Every array is device
+// memory; ws = container_write_many_ws_bytes(n_blocks, the slots' bytes) of scratch; hc_ws, q_scratch, dense64, n_cus, core as in
+// launch_container_blocks, hc_ws sized for src_span = the end of the last item's source.  n_blocks + n_items <= 2^31 - 1.
+struct ContainerWriteManyItems {
+  const uint64_t* src_off; const int32_t* src_len; const int32_t* hash_len; const uint64_t* slot_base; const uint32_t* block_size; const uint32_t* first;
+  const uint32_t* gap_head; const uint32_t* gap_tail; const uint8_t* flags;
+};
+size_t container_write_many_ws_bytes(uint32_t n_blocks, uint64_t slot_bytes_total);
+int launch_container_blocks_many(int kind, int hc_level, bool any_block_checksum, bool any_content_hash, const uint8_t* src, uint64_t src_span,
+                                 const ContainerWriteManyItems& items, uint32_t n_items, uint32_t n_blocks, uint8_t* dst, uint64_t dst_cap,
+                                 unsigned long long* item_dst_off, uint32_t* content_hash, void* ws, void* hc_ws, uint32_t* q_scratch, uint32_t dense64,
+                                 uint32_t n_cus, int core, void* stream);
 // lanes_per_block: lanes of a wavefront that share one block in the decoder (4..64); 0 = default
 // pipe: 1 = pipelined interior loop (lz4_decode_core.h PIPE), 0 = plain, -1 = default for the batch size
 // stage: 1 = the plain interior loop writes through LDS staging (whole-line output), 0 / -1 = off

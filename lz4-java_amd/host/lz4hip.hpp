@@ -246,6 +246,33 @@ struct LZ4HIPBatch {
     }
   }
   static void status(int rc) { if (rc != 0) throw LZ4Exception(std::string("liblz4hip status ") + std::to_string(rc) + ": " + lz4hip_last_error()); }
+  // The blocks of MANY LZ4 Frames (kind 0) or LZ4Block streams (kind 1) in one call (lz4hip_container_blocks_many): item c is items[c]
+  // cut into pieces of blockSize[c] bytes at `level` (0: fast, else lz4-java's HC level); flags[c]: bit 0 block checksums (kind 0), bit
+  // 1 the XXH32 (seed 0) of the item is wanted; gapHead[c] / gapTail[c] zero bytes lie in front of and behind its blocks.  Item c is
+  // data[offsets[c], offsets[c + 1]); contentHash[c] is 0 where flags[c] has no bit 1.
+  struct ManyWritten { bytes data; std::vector<uint64_t> offsets; std::vector<uint32_t> contentHash; };
+  static ManyWritten containerBlocksMany(int kind, int level, const std::vector<bytes>& items, const std::vector<uint32_t>& blockSize,
+                                         const std::vector<uint8_t>& flags, const std::vector<uint32_t>& gapHead, const std::vector<uint32_t>& gapTail) {
+    const size_t n = items.size();
+    if (blockSize.size() != n || flags.size() != n || gapHead.size() != n || gapTail.size() != n) throw std::invalid_argument("per-item lists differ in length");
+    ManyWritten w;
+    w.offsets.assign(n + 1, 0);
+    w.contentHash.assign(n, 0);
+    if (n == 0) return w;
+    std::vector<uint64_t> off(n), len(n), need(n);
+    std::vector<uint32_t> nb(n);
+    bytes blob;
+    for (size_t c = 0; c < n; c++) { off[c] = blob.size(); len[c] = items[c].size(); blob.insert(blob.end(), items[c].begin(), items[c].end()); }
+    blob.push_back(0);                            // (empty buffers still hand the library a pointer)
+    status(lz4hip_container_blocks_many_bound(kind, len.data(), blockSize.data(), flags.data(), gapHead.data(), gapTail.data(), (uint32_t)n, nb.data(), need.data()));
+    uint64_t cap = 0;
+    for (size_t c = 0; c < n; c++) cap += need[c];
+    w.data.resize((size_t)cap + 1u);
+    status(lz4hip_container_blocks_many(kind, level, blob.data(), off.data(), len.data(), blockSize.data(), flags.data(), gapHead.data(), gapTail.data(),
+                                        (uint32_t)n, w.data.data(), cap, w.offsets.data(), w.contentHash.data()));
+    w.data.resize((size_t)w.offsets[n]);
+    return w;
+  }
   // LZ4_loadDict + LZ4_compress_fast_continue per block, a fresh stream each, against one dictionary: block i is compressed into
   // dest[destOff[i], + maxDestLen[i]); returns the compressed sizes, 0 where the slot is too small (lz4hip_compress_fast_dict_batch)
   static std::vector<int32_t> compressDict(const bytes& src, const std::vector<uint64_t>& srcOff, const std::vector<int32_t>& srcLen, bytes& dest,

@@ -155,6 +155,12 @@ struct BatchEngine {
     }
     return out;
   }
+  // containerBlocks for MANY payloads of one kind in ONE call (lz4hip_container_blocks_many, LZ4HIPBatch::containerBlocksMany): item c's
+  // blocks lie between gapHead[c] and gapTail[c] zero bytes; flags[c]: bit 0 block checksums (kind 0), bit 1 the item's XXH32 is wanted
+  LZ4HIPBatch::ManyWritten containerBlocksMany(int kind, const std::vector<bytes>& items, const std::vector<uint32_t>& blockSize, const std::vector<uint8_t>& flags,
+                                               const std::vector<uint32_t>& gapHead, const std::vector<uint32_t>& gapTail) const {
+    return LZ4HIPBatch::containerBlocksMany(kind, hcLevel, items, blockSize, flags, gapHead, gapTail);
+  }
   uint32_t xxh32_one(const uint8_t* buf, size_t n, uint32_t seed) const {
     static const uint8_t dummy = 0;
     return xxh32(n ? buf : &dummy, {0}, {(int32_t)n}, seed)[0];
@@ -1110,6 +1116,88 @@ inline std::vector<ReadResult> readBlockStreams(const std::vector<bytes>& items,
     readers.emplace_back(ins.back(), true, engine, batchBlocks);
   }
   return detail::ManyDriver::run(readers, engine, 1, (uint32_t)(batchBlocks ? batchBlocks : 1));
+}
+
+// Many LZ4 Frames written together: per payload the complete frame, byte for byte what LZ4FrameOutputStream(out, blockSize,
+// payload.size(), bits, engine) writes when the payload is written to it and it is closed (with CONTENT_SIZE every frame carries its
+// payload's length).  All payloads' blocks are made by ONE containerBlocksMany; the frame header, the end mark and the content checksum --
+// taken on the device in the same call -- go into the gaps the call leaves around each item's blocks.  Frames with linked blocks are not
+// part of the many-call.  engine.hostAssembly: frame by frame through the writer.
+inline std::vector<bytes> writeFrames(const std::vector<bytes>& payloads, BatchEngine engine = BatchEngine(), frame::BLOCKSIZE blockSize = frame::SIZE_4MB,
+                                      std::initializer_list<frame::Bits> bits = {frame::BLOCK_INDEPENDENCE}) {
+  std::vector<bytes> out;
+  int m = 0;
+  for (auto b : bits) m |= 1 << b;
+  const frame::FLG flg(1, m);
+  const frame::BD bd((int)blockSize);
+  const bool sized = flg.isEnabled(frame::CONTENT_SIZE), summed = flg.isEnabled(frame::CONTENT_CHECKSUM);
+  if (engine.hostAssembly) {
+    for (const bytes& p : payloads) {
+      std::ostringstream sink;
+      { LZ4FrameOutputStream w(sink, blockSize, sized ? (int64_t)p.size() : -1, bits, engine); w.write(p); w.close(); }
+      const std::string s = sink.str();
+      out.emplace_back(s.begin(), s.end());
+    }
+    return out;
+  }
+  const size_t n = payloads.size();
+  if (n == 0) return out;
+  std::vector<bytes> heads(n);
+  bytes descs;                                    // the descriptors (the writer's constructor): one xxh32 batch over them
+  std::vector<uint64_t> doff(n);
+  std::vector<int32_t> dlen(n);
+  for (size_t c = 0; c < n; c++) {
+    doff[c] = descs.size();
+    descs.push_back(flg.toByte());
+    descs.push_back(bd.toByte());
+    if (sized) detail::putLE64(descs, (uint64_t)payloads[c].size());
+    dlen[c] = (int32_t)(descs.size() - doff[c]);
+  }
+  const std::vector<uint32_t> hc = engine.xxh32(descs.data(), doff, dlen, 0);
+  std::vector<uint32_t> bs(n, (uint32_t)bd.getBlockMaximumSize()), gh(n), gt(n, summed ? 8u : 4u);
+  std::vector<uint8_t> fl(n, (uint8_t)((flg.isEnabled(frame::BLOCK_CHECKSUM) ? 1 : 0) | (summed ? 2 : 0)));
+  for (size_t c = 0; c < n; c++) {
+    detail::putLE32(heads[c], frame::MAGIC);
+    heads[c].insert(heads[c].end(), descs.begin() + (std::ptrdiff_t)doff[c], descs.begin() + (std::ptrdiff_t)doff[c] + dlen[c]);
+    heads[c].push_back((uint8_t)((hc[c] >> 8) & 0xFF));
+    gh[c] = (uint32_t)heads[c].size();
+  }
+  const LZ4HIPBatch::ManyWritten w = engine.containerBlocksMany(0, payloads, bs, fl, gh, gt);
+  for (size_t c = 0; c < n; c++) {
+    bytes item(w.data.begin() + (std::ptrdiff_t)w.offsets[c], w.data.begin() + (std::ptrdiff_t)w.offsets[c + 1]);
+    std::copy(heads[c].begin(), heads[c].end(), item.begin());
+    if (summed)                                   // (the four bytes in front of it are the end mark: zeros already)
+      for (int k = 0; k < 4; k++) item[item.size() - 4 + (size_t)k] = (uint8_t)(w.contentHash[c] >> (8 * k));
+    out.push_back(std::move(item));
+  }
+  return out;
+}
+// writeFrames' twin: per payload what LZ4BlockOutputStream(out, blockSize, engine) writes when the payload is written to it and it is
+// closed (the default checksum); the empty end block goes into the gap behind each item's blocks
+inline std::vector<bytes> writeBlockStreams(const std::vector<bytes>& payloads, BatchEngine engine = BatchEngine(), int blockSize = 1 << 16) {
+  std::vector<bytes> out;
+  const int level = blockstream::compressionLevel(blockSize);
+  if (engine.hostAssembly) {
+    for (const bytes& p : payloads) {
+      std::ostringstream sink;
+      { LZ4BlockOutputStream w(sink, blockSize, engine); w.write(p); w.close(); }
+      const std::string s = sink.str();
+      out.emplace_back(s.begin(), s.end());
+    }
+    return out;
+  }
+  const size_t n = payloads.size();
+  if (n == 0) return out;
+  const LZ4HIPBatch::ManyWritten w = engine.containerBlocksMany(1, payloads, std::vector<uint32_t>(n, (uint32_t)blockSize), std::vector<uint8_t>(n, 0),
+                                                                std::vector<uint32_t>(n, 0), std::vector<uint32_t>(n, (uint32_t)blockstream::HEADER_LENGTH));
+  for (size_t c = 0; c < n; c++) {
+    bytes item(w.data.begin() + (std::ptrdiff_t)w.offsets[c], w.data.begin() + (std::ptrdiff_t)w.offsets[c + 1]);
+    uint8_t* end = item.data() + item.size() - (size_t)blockstream::HEADER_LENGTH;   // (LZ4BlockOutputStream::finish: twelve zero bytes follow)
+    std::copy(blockstream::magic(), blockstream::magic() + 8, end);
+    end[8] = (uint8_t)(blockstream::COMPRESSION_METHOD_RAW | level);
+    out.push_back(std::move(item));
+  }
+  return out;
 }
 
 // =====================================================================================================

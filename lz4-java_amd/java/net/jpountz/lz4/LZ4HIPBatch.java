@@ -942,6 +942,66 @@ public final class LZ4HIPBatch {
     }
   }
 
+  /**
+   * What a {@link #containerBlocksMany} call over the same items can need: {@code itemBlocks[c]} = ceil(srcLen[c] / blockSize[c]),
+   * {@code itemDstBytes[c]} = gapHead[c] + srcLen[c] + itemBlocks[c] x (frame blocks: 4, 8 with block checksums; LZ4Block blocks: 21)
+   * + gapTail[c].  No device work.  Size {@code dest} by the sum of {@code itemDstBytes}.  {@code gapHead} and {@code gapTail} may be
+   * null: no gaps.
+   */
+  public static void containerBlocksManyBound(int kind, long[] srcLen, int[] blockSize, boolean[] blockChecksum, int[] gapHead, int[] gapTail,
+                                              int[] itemBlocks, long[] itemDstBytes) {
+    final int n = srcLen.length;
+    if (blockSize.length != n || blockChecksum.length != n || (gapHead != null && gapHead.length != n) || (gapTail != null && gapTail.length != n)
+        || itemBlocks.length < n || itemDstBytes.length < n) {
+      throw new ArrayIndexOutOfBoundsException();
+    }
+    final int[] flags = new int[n];
+    for (int c = 0; c < n; c++) {
+      flags[c] = blockChecksum[c] ? 1 : 0;
+    }
+    final int r = LZ4HIPJNI.LZ4HIP_containerBlocksManyBound(kind, srcLen, blockSize, flags, gapHead != null ? gapHead : new int[n],
+        gapTail != null ? gapTail : new int[n], n, itemBlocks, itemDstBytes);
+    if (r != 0) {
+      throw new LZ4Exception("liblz4hip status " + r + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
+  /**
+   * {@link #containerBlocks} for MANY payloads of one kind in ONE call: item c is {@code src[srcOff[c], + srcLen[c])} cut into pieces of
+   * {@code blockSize[c]} bytes, with block checksums where {@code blockChecksum[c]} ({@link #FRAME_BLOCKS} only).  {@code level}: 0 for
+   * the fast compressor, else the HC level.  Item c lands at {@code dest[destOff + itemDstOff[c] .. destOff + itemDstOff[c+1])}:
+   * {@code gapHead[c]} zero bytes, the bytes {@link #containerBlocks} writes for the item, {@code gapTail[c]} zero bytes -- room for a
+   * frame header, the end mark and the content checksum, so that a writer places them without copying the blocks again.  Where
+   * {@code contentHash[c]} is asked for ({@code wantContentHash[c]}), it is the XXH32 (seed 0) of the item's source, else 0.  A group of
+   * items costs one launch sequence, whatever their number.  {@code itemDstOff} has one entry more than there are items;
+   * {@code gapHead}, {@code gapTail} and {@code wantContentHash} may be null (no gaps, no hashes; {@code contentHash} may then be null).
+   */
+  public static void containerBlocksMany(int kind, int level, ByteBuffer src, long[] srcOff, long[] srcLen, int[] blockSize, boolean[] blockChecksum,
+                                         int[] gapHead, int[] gapTail, boolean[] wantContentHash, ByteBuffer dest, long destOff, long[] itemDstOff,
+                                         int[] contentHash) {
+    final int n = srcOff.length;
+    if (!src.isDirect() || !dest.isDirect()) {
+      throw new IllegalArgumentException("LZ4HIPBatch needs direct ByteBuffers");
+    }
+    if (dest.isReadOnly()) {
+      throw new java.nio.ReadOnlyBufferException();
+    }
+    if (srcLen.length != n || blockSize.length != n || blockChecksum.length != n || (gapHead != null && gapHead.length != n)
+        || (gapTail != null && gapTail.length != n) || (wantContentHash != null && (wantContentHash.length != n || contentHash == null))
+        || (contentHash != null && contentHash.length < n) || destOff < 0 || destOff > dest.capacity() || itemDstOff.length < n + 1) {
+      throw new ArrayIndexOutOfBoundsException();
+    }
+    final int[] flags = manyFlags(src, srcOff, srcLen, blockChecksum);
+    for (int c = 0; wantContentHash != null && c < n; c++) {
+      flags[c] |= wantContentHash[c] ? 2 : 0;
+    }
+    final int r = LZ4HIPJNI.LZ4HIP_containerBlocksMany(kind, level, src, srcOff, srcLen, blockSize, flags, gapHead != null ? gapHead : new int[n],
+        gapTail != null ? gapTail : new int[n], n, dest, destOff, dest.capacity() - destOff, itemDstOff, contentHash != null ? contentHash : new int[n]);
+    if (r != 0) {
+      throw new LZ4Exception("liblz4hip status " + r + ": " + LZ4HIPJNI.lastError());
+    }
+  }
+
   /** the items' ranges checked against the buffer (SafeUtils.checkRange per item) -> the flag word of every item */
   private static int[] manyFlags(ByteBuffer bodies, long[] bodyOff, long[] bodyLen, boolean[] blockChecksum) {
     final int[] flags = new int[bodyOff.length];

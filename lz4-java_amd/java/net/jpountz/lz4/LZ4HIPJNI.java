@@ -219,5 +219,13 @@ enum LZ4HIPJNI {
   static native int LZ4HIP_containerDecodeManyBound(int kind, ByteBuffer bodies, long[] bodyOff, long[] bodyLen, int[] maxBlock, int[] flags,
       int nItems, int nMax, int[] itemBlocks, long[] itemDstBytes);
 
+  /** Many containers of one kind written in one call (LZ4HIPBatch.containerBlocksMany); returns 0 or the negative lz4hip_status. */
+  static native int LZ4HIP_containerBlocksMany(int kind, int level, ByteBuffer src, long[] srcOff, long[] srcLen, int[] blockSize, int[] flags,
+      int[] gapHead, int[] gapTail, int nItems, ByteBuffer dest, long destOff, long destCap, long[] itemDstOff, int[] contentHash);
+
+  /** Per item its blocks and its worst case with the gaps (arithmetic, no device); returns 0 or the negative lz4hip_status. */
+  static native int LZ4HIP_containerBlocksManyBound(int kind, long[] srcLen, int[] blockSize, int[] flags, int[] gapHead, int[] gapTail,
+      int nItems, int[] itemBlocks, long[] itemDstBytes);
+
   static native String lastError();
 }

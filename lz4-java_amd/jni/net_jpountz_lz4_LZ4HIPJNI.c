@@ -852,6 +852,72 @@ JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1containerDecodeMan
   return container_many(env, 1, kind, bodies, bodyOff, bodyLen, maxBlock, flags, nItems, nMax, NULL, 0, 0, itemBlocks, itemDstBytes, NULL, NULL);
 }
 
+/* MANY containers WRITTEN in one call (include/lz4hip.h lz4hip_container_blocks_many{,_bound}): item c is src[srcOff[c], + srcLen[c]) cut
+ * into blockSize[c] pieces, with flags[c] (bit 0: block checksums, kind 0; bit 1: its content hash is wanted) and gapHead[c] / gapTail[c]
+ * zero bytes around its blocks.  bound != 0: the arithmetic alone -- outA = itemBlocks[nItems], outB = itemDstBytes[nItems], no buffer is
+ * looked at.  Otherwise the write: the items land back to back at dest[destOff ..), outB = itemDstOff[nItems + 1], outA =
+ * contentHash[nItems].  Direct buffers; NULL arrays (gapHead and gapTail too: Java passes arrays of zeros) and arrays that are too short
+ * are argument errors; returns 0 or the (negative) lz4hip_status. */
+static jint container_write_many(JNIEnv* env, int bound, jint kind, jint level, jobject src, jlongArray srcOff, jlongArray srcLen, jintArray blockSize,
+                                 jintArray flags, jintArray gapHead, jintArray gapTail, jint nItems, jobject dest, jlong destOff, jlong destCap, jintArray outA,
+                                 jlongArray outB) {
+  if (!bound && (src == NULL || dest == NULL)) return LZ4HIP_E_ARG;
+  const uint8_t* s = bound ? NULL : (const uint8_t*)(*env)->GetDirectBufferAddress(env, src);
+  uint8_t* d = bound ? NULL : (uint8_t*)(*env)->GetDirectBufferAddress(env, dest);
+  if (nItems < 0 || (!bound && (s == NULL || d == NULL || destOff < 0 || destCap < 0))) return LZ4HIP_E_ARG;
+  if ((!bound && srcOff == NULL) || srcLen == NULL || blockSize == NULL || flags == NULL || gapHead == NULL || gapTail == NULL || outA == NULL || outB == NULL)
+    return LZ4HIP_E_ARG;   /* (GetArrayLength of a null reference crashes a real JVM) */
+  const jint nOut = bound ? nItems : nItems + 1;
+  if ((!bound && (*env)->GetArrayLength(env, srcOff) < nItems) || (*env)->GetArrayLength(env, srcLen) < nItems ||
+      (*env)->GetArrayLength(env, blockSize) < nItems || (*env)->GetArrayLength(env, flags) < nItems || (*env)->GetArrayLength(env, gapHead) < nItems ||
+      (*env)->GetArrayLength(env, gapTail) < nItems || (*env)->GetArrayLength(env, outA) < nItems || (*env)->GetArrayLength(env, outB) < nOut)
+    return LZ4HIP_E_ARG;
+  uint8_t* fl = (uint8_t*)malloc((size_t)nItems + 1u);
+  jlong* so = bound ? NULL : (*env)->GetLongArrayElements(env, srcOff, NULL);
+  jlong* sl = (*env)->GetLongArrayElements(env, srcLen, NULL);
+  jint* bs = (*env)->GetIntArrayElements(env, blockSize, NULL);
+  jint* fi = (*env)->GetIntArrayElements(env, flags, NULL);
+  jint* gh = (*env)->GetIntArrayElements(env, gapHead, NULL);
+  jint* gt = (*env)->GetIntArrayElements(env, gapTail, NULL);
+  jint* oa = (*env)->GetIntArrayElements(env, outA, NULL);
+  jlong* ob = (*env)->GetLongArrayElements(env, outB, NULL);
+  jint rc = LZ4HIP_E_NOMEM;
+  if (fl && (bound || so) && sl && bs && fi && gh && gt && oa && ob) {
+    rc = 0;
+    for (jint c = 0; c < nItems; c++) {
+      if ((!bound && so[c] < 0) || sl[c] < 0 || fi[c] < 0 || fi[c] > 255 || gh[c] < 0 || gt[c] < 0) rc = LZ4HIP_E_ARG;
+      fl[c] = (uint8_t)fi[c];
+    }
+    if (rc == 0 && bound)
+      rc = lz4hip_container_blocks_many_bound(kind, (const uint64_t*)sl, (const uint32_t*)bs, fl, (const uint32_t*)gh, (const uint32_t*)gt, (uint32_t)nItems,
+                                              (uint32_t*)oa, (uint64_t*)ob);
+    else if (rc == 0)
+      rc = lz4hip_container_blocks_many(kind, level, s, (const uint64_t*)so, (const uint64_t*)sl, (const uint32_t*)bs, fl, (const uint32_t*)gh,
+                                        (const uint32_t*)gt, (uint32_t)nItems, d + destOff, (uint64_t)destCap, (uint64_t*)ob, (uint32_t*)oa);
+  }
+  if (so) (*env)->ReleaseLongArrayElements(env, srcOff, so, 0);
+  if (sl) (*env)->ReleaseLongArrayElements(env, srcLen, sl, 0);
+  if (bs) (*env)->ReleaseIntArrayElements(env, blockSize, bs, 0);
+  if (fi) (*env)->ReleaseIntArrayElements(env, flags, fi, 0);
+  if (gh) (*env)->ReleaseIntArrayElements(env, gapHead, gh, 0);
+  if (gt) (*env)->ReleaseIntArrayElements(env, gapTail, gt, 0);
+  if (oa) (*env)->ReleaseIntArrayElements(env, outA, oa, 0);
+  if (ob) (*env)->ReleaseLongArrayElements(env, outB, ob, 0);
+  free(fl);
+  return rc;
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1containerBlocksMany(JNIEnv* env, jclass cls, jint kind, jint level, jobject src, jlongArray srcOff,
+    jlongArray srcLen, jintArray blockSize, jintArray flags, jintArray gapHead, jintArray gapTail, jint nItems, jobject dest, jlong destOff, jlong destCap,
+    jlongArray itemDstOff, jintArray contentHash) {
+  (void)cls;
+  return container_write_many(env, 0, kind, level, src, srcOff, srcLen, blockSize, flags, gapHead, gapTail, nItems, dest, destOff, destCap, contentHash, itemDstOff);
+}
+JNIEXPORT jint JNICALL Java_net_jpountz_lz4_LZ4HIPJNI_LZ4HIP_1containerBlocksManyBound(JNIEnv* env, jclass cls, jint kind, jlongArray srcLen, jintArray blockSize,
+    jintArray flags, jintArray gapHead, jintArray gapTail, jint nItems, jintArray itemBlocks, jlongArray itemDstBytes) {
+  (void)cls;
+  return container_write_many(env, 1, kind, 0, NULL, NULL, srcLen, blockSize, flags, gapHead, gapTail, nItems, NULL, 0, 0, itemBlocks, itemDstBytes);
+}
+
 /* ---- xxhash (XXHashJNI.c:42-82, :152-192 counterparts) ---- */
 static int hash_region(JNIEnv* env, jbyteArray arr, jobject buf, jint off, jint len, int is64, uint64_t seed, uint64_t* out) {
   region_t in;

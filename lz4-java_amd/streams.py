@@ -71,6 +71,13 @@ class HIPEngine:
         containerDecode returns"""
         return LZ4HIPBatch.containerDecodeMany(kind, bodies, maxBlock, nMax, blockChecksum)
 
+    def containerBlocksMany(self, kind, items, blockSizes, blockChecksums=False, gapHead=0, gapTail=0, contentHash=False):
+        """containerBlocks for many payloads of one kind in ONE call (lz4hip_container_blocks_many): lists in (or one value for all
+        items) -> (dst, off, hashes): item c is dst[off[c]:off[c + 1]], its blocks between gapHead[c] and gapTail[c] zero bytes;
+        hashes[c] is the XXH32 (seed 0) of items[c] where contentHash[c] is set"""
+        lv = 0 if self.hcLevel is None else (9 if self.hcLevel < 1 else self.hcLevel)
+        return LZ4HIPBatch.containerBlocksMany(kind, items, blockSizes, blockChecksums, lv, gapHead, gapTail, contentHash)
+
     @staticmethod
     def newStreamingHash32(seed):
         """content checksum state (LZ4FrameOutputStream.java:116: `XXHashFactory...newStreamingHash32(0)`)"""
@@ -1190,6 +1197,81 @@ def readBlockStreams(items, engine=None, batchBlocks=256):
     """Many lz4-java "LZ4Block" streams read together: readFrames' twin over LZ4BlockInputStream(io.BytesIO(item))"""
     engine = engine or HIPEngine()
     return _read_many([LZ4BlockInputStream(io.BytesIO(bytes(it)), engine=engine, batchBlocks=batchBlocks) for it in items], engine, LZ4HIPBatch.LZ4BLOCK_BLOCKS)
+
+
+def writeFrames(payloads, engine=None, blockSize=BLOCKSIZE.SIZE_4MB, bits=()):
+    """Many LZ4 Frames written together: for each payload the complete frame, byte for byte what
+    LZ4FrameOutputStream(out, blockSize, len(payload), *bits, engine=engine) writes when the payload is written to it and it is closed
+    (bits: FLG.Bits values; with CONTENT_SIZE every frame carries its payload's length).  All payloads' blocks are made by ONE
+    containerBlocksMany (lz4hip_container_blocks_many) where the writers make a containerBlocks each; the frame header, the end mark
+    and the content checksum -- taken on the device in the same call -- go into the gaps the call leaves around each item's blocks.
+    Frames with linked blocks are not part of the many-call.  An engine without containerBlocksMany writes frame by frame."""
+    engine = engine or HIPEngine()
+    bits = tuple(bits) or (FLG.Bits.BLOCK_INDEPENDENCE,)
+    payloads = [bytes(p) if not isinstance(p, (bytes, bytearray)) else p for p in payloads]
+    many = getattr(engine, "containerBlocksMany", None)
+    if many is None:
+        out = []
+        for p in payloads:
+            sink = io.BytesIO()
+            w = LZ4FrameOutputStream(sink, blockSize, len(p) if FLG.Bits.CONTENT_SIZE in bits else -1, *bits, engine=engine)
+            w.write(p)
+            w.close()
+            out.append(sink.getvalue())
+        return out
+    flg, bd = FLG.of(*bits), BD(blockSize)
+    if not payloads:
+        return []
+    sized, summed = flg.isEnabled(FLG.Bits.CONTENT_SIZE), flg.isEnabled(FLG.Bits.CONTENT_CHECKSUM)
+    # the descriptors (LZ4FrameOutputStream._writeHeader): one xxh32 batch over the distinct ones
+    desc = [bytes((flg.toByte(), bd.toByte())) + (_U64.pack(len(p)) if sized else b"") for p in payloads]
+    distinct = sorted(set(desc))
+    offs, at = [], 0
+    for d in distinct:
+        offs.append(at); at += len(d)
+    hc = dict(zip(distinct, engine.xxh32(b"".join(distinct), offs, [len(d) for d in distinct], 0)))
+    heads = [_U32.pack(MAGIC) + d + bytes(((hc[d] >> 8) & 0xFF,)) for d in desc]
+    n = len(payloads)
+    dst, off, hashes = many(LZ4HIPBatch.FRAME_BLOCKS, payloads, [bd.getBlockMaximumSize()] * n, [flg.isEnabled(FLG.Bits.BLOCK_CHECKSUM)] * n,
+                            [len(h) for h in heads], [8 if summed else 4] * n, [summed] * n)
+    out = []
+    for c in range(n):
+        item = bytearray(dst[int(off[c]):int(off[c + 1])])
+        item[:len(heads[c])] = heads[c]
+        if summed:                       # (the four bytes in front of it are the end mark: zeros already)
+            _U32.pack_into(item, len(item) - 4, int(hashes[c]))
+        out.append(bytes(item))
+    return out
+
+
+def writeBlockStreams(payloads, engine=None, blockSize=1 << 16):
+    """Many lz4-java "LZ4Block" streams written together: writeFrames' twin -- for each payload what LZ4BlockOutputStream(out,
+    blockSize, engine=engine) writes when the payload is written to it and it is closed (the default checksum); the empty end block
+    goes into the gap behind each item's blocks"""
+    engine = engine or HIPEngine()
+    level = _compressionLevel(blockSize)
+    payloads = [bytes(p) if not isinstance(p, (bytes, bytearray)) else p for p in payloads]
+    many = getattr(engine, "containerBlocksMany", None)
+    if many is None:
+        out = []
+        for p in payloads:
+            sink = io.BytesIO()
+            w = LZ4BlockOutputStream(sink, blockSize, engine=engine)
+            w.write(p)
+            w.close()
+            out.append(sink.getvalue())
+        return out
+    if not payloads:
+        return []
+    n = len(payloads)
+    end = BLOCK_MAGIC + bytes((COMPRESSION_METHOD_RAW | level,))   # (LZ4BlockOutputStream.finish: twelve zero bytes follow)
+    dst, off, _ = many(LZ4HIPBatch.LZ4BLOCK_BLOCKS, payloads, [blockSize] * n, [False] * n, [0] * n, [21] * n, [False] * n)
+    out = []
+    for c in range(n):
+        item = bytearray(dst[int(off[c]):int(off[c + 1])])
+        item[len(item) - 21:len(item) - 21 + len(end)] = end
+        out.append(bytes(item))
+    return out
 
 
 # =================================================================================================
